@@ -109,6 +109,9 @@ def parse():
                     help="elements of the workload the CPU baseline round runs on (default: all of config 2; ~0.2-2 s)")
     ap.add_argument("--no-python-baseline", action="store_true", help="skip the structure-faithful Python baseline (~10-20 s)")
     ap.add_argument("--no-e2e", action="store_true", help="skip the one PCIe-inclusive round through the host-pointer API")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the decrypted sum, the ciphertexts, ...) as "
+                         "DIR/<name>.npy, float64, at most 64 MB in all (see dump_outputs); rank 0 only")
     return ap.parse_args()
 
 
@@ -516,6 +519,38 @@ def timed_region(ops, K, step):
     return ops.allreduce(time.perf_counter() - t0, 0)
 
 
+def keep_last(step, box):
+    """step, with what its last call returned kept in box["last"] (--dump-outputs only: the timed path is otherwise left as it is)."""
+    def run(k):
+        box["last"] = step(k)
+    return run
+
+
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(directory, outputs):
+    """--dump-outputs: outputs = {name: () -> array of rows} (uint64 limbs [n][L] or [n], uint32, float32 / float64 [n]), read from the
+    device after the timed region.  Each becomes DIR/<name>.npy in float64, exactly: a uint64 limb is two columns, its low and its high
+    32 bits, limb by limb.  An array whose rows do not fit its share of the 64 MB is cut to a fixed sample of rows (seeded by its length,
+    so the same arguments give the same rows), sorted, whose row numbers go to DIR/<name>_rows.npy."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = (DUMP_BUDGET_BYTES - 4096 * len(outputs)) // max(len(outputs), 1)       # (npy headers)
+    for name, read in outputs.items():
+        a = np.asarray(read())
+        a = a.reshape(len(a), -1)
+        n, width = a.shape[0], a.shape[1] * (2 if a.dtype == np.uint64 else 1)
+        m = min(n, share // (8 * width + 8))
+        if m < n:
+            rows = np.sort(np.random.Generator(np.random.PCG64(n)).choice(n, m, replace=False))
+            np.save(os.path.join(directory, f"{name}_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        if a.dtype == np.uint64:
+            a = np.stack([a & np.uint64(0xFFFFFFFF), a >> np.uint64(32)], axis=2).reshape(len(a), -1)
+        np.save(os.path.join(directory, f"{name}.npy"), a.astype(np.float64))
+
+
 def settle(ops, step, seconds=0.1):
     """The parity checks before a timed region leave the GPU idle while the host compares vectors, and its clocks drop; a round of
     well under a millisecond does not bring them back within --warmup steps (tests/perf/compact_encrypt_time.py: the first 13 ms of
@@ -685,7 +720,13 @@ def bench_dense(args, cfg, n, ops, rank, world, out, wd, state):
                 ops.sync()
         for w in range(W):
             run_schedule(schedule, w)
-        elapsed = timed_region(ops, K, lambda k: run_schedule(schedule, k, k))
+        step = lambda k: run_schedule(schedule, k, k)                     # noqa: E731
+        last = {}
+        elapsed = timed_region(ops, K, keep_last(step, last) if args.dump_outputs else step)
+        if args.dump_outputs and rank == 0:          # (the last call leaves the files of the schedule the line reports)
+            outputs = {"decrypted_sum": lambda: ops.read((last["last"], 0), n * L).reshape(n, L)}
+            outputs.update({f"ciphertext_c{mine[c]}": (lambda c=c: ops.read(rnd.ct[c], n * L).reshape(n, L)) for c in range(C)})
+            dump_outputs(args.dump_outputs, outputs)
         if schedule == "sequential":
             enc_pairs = [(p[0], p[1]) for p in ph_ev]      # the batched encrypt launch of every timed round
         else:
@@ -1122,6 +1163,10 @@ def bench_plumbing(args, n, ops, rank, world, out):
     elapsed = timed_region(ops, K, lambda k: step(k, k))
     if rank != 0:
         return None
+    if args.dump_outputs:
+        outputs = {"unquantized_sum": lambda: res.download(np.float64, n)}
+        outputs.update({f"ciphertext_c{c}": (lambda c=c: cts[c].download(np.uint64, n * L).reshape(n, L)) for c in range(C)})
+        dump_outputs(args.dump_outputs, outputs)
     ph = two_event_phases(eng, ev)
     enc_ms = float(ph[:, 0].mean())
     alg_bytes = C * n * (4 + 8 + 8 * L)                   # fp32 value + its draw in, ciphertext out
@@ -1231,6 +1276,10 @@ def bench_precompute(args, n, ops, rank, world, out):
     for it in range(max(W, 3)):
         step(it)
     elapsed = timed_region(ops, K, lambda k: step(k, k))
+    if args.dump_outputs and rank == 0:
+        outputs = {"decrypted_sum": lambda: dec.download(np.uint64, n * L).reshape(n, L)}
+        outputs.update({f"ciphertext_c{c}": (lambda c=c: cts[c].download(np.uint64, n * L).reshape(n, L)) for c in range(C)})
+        dump_outputs(args.dump_outputs, outputs)
     pre_ms = float(two_event_phases(eng, ev)[:, 0].mean())               # the precompute launch, HIP events inside the timed region
     for k in range(K):                                                    # the split of the online half: the same K rounds again, untimed
         step(k, k, split=True)
@@ -1343,6 +1392,10 @@ def bench_compact(args, n, ops, rank, world, out):
     elapsed = timed_region(ops, K, lambda k: step(k, k))
     if rank != 0:
         return None
+    if args.dump_outputs:
+        outputs = {"decrypted_sum": lambda: dec.download(np.uint32, n)}
+        outputs.update({f"ciphertext_c{c}": (lambda c=c: cts[c].download(np.uint32, n)) for c in range(C)})
+        dump_outputs(args.dump_outputs, outputs)
     ph = two_event_phases(eng, ev)
     enc_ms = float(ph[:, 0].mean())
     m = 128 // b
@@ -1503,6 +1556,10 @@ def bench_sparse(args, total, ops, rank, world, out):
     for it in range(max(W, 2)):
         step(it)
     elapsed = timed_region(ops, K, lambda kk: step(kk, kk))
+    if args.dump_outputs and rank == 0:
+        outputs = {"decrypted_sum": lambda: d_dec.download(np.uint64, total * L).reshape(total, L)}
+        outputs.update({f"ciphertext_c{c}": (lambda c=c: d_ct[c].download(np.uint64, k * L).reshape(k, L)) for c in range(C)})
+        dump_outputs(args.dump_outputs, outputs)
     d0 = 1 if fused_ok else 0
     dom_ms = float(np.mean([eng.elapsed_ms(e[d0], e[d0 + 1]) for e in ev]))   # the dominant launch, HIP events inside the timed region
     for kk in range(K):                                   # the split of the rest of the round: the same K rounds again, untimed, every event

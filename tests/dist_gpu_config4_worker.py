@@ -14,13 +14,12 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from flashe_amd.dist import HipOps, ShardedRound, deal_clients  # noqa: E402
 from flashe_amd.engine import Engine  # noqa: E402
 from oracle import flashe_oracle as orc  # noqa: E402
-from shm_comm import ShmComm  # noqa: E402
+from shm_comm import ShmComm, run_ranks  # noqa: E402
 
 KEY = bytes(range(32))
 
 
-def main():
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+def main(rank, world):
     n = int(os.environ.get("CONFIG4_N", 25_557_032))
     comm = ShmComm(rank, world, os.environ["FLASHE_TEST_SHM_DIR"])
     orc.set_num_threads(2)
@@ -69,4 +68,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    run_ranks(main)

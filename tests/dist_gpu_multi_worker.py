@@ -13,13 +13,12 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from flashe_amd.dist import HipOps, ShardedRound, SparseShardedRound, deal_clients  # noqa: E402
 from flashe_amd.engine import SCHEME_DOUBLE, SCHEME_SINGLE, Engine  # noqa: E402
 from oracle import flashe_oracle as orc  # noqa: E402
-from shm_comm import ShmComm  # noqa: E402
+from shm_comm import ShmComm, run_ranks  # noqa: E402
 
 KEY = bytes(range(32))
 
 
-def main():
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+def main(rank, world):
     comm = ShmComm(rank, world, os.environ["FLASHE_TEST_SHM_DIR"])
     orc.set_num_threads(2)
     cases = [(128, 300_007, "equal2", 16, SCHEME_DOUBLE), (128, 70_001, "uneven", 16, SCHEME_DOUBLE), (20, 50_001, "equal2", 16, SCHEME_DOUBLE),
@@ -177,4 +176,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    run_ranks(main)

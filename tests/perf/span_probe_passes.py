@@ -1,5 +1,5 @@
 import os, sys
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 os.environ["FLASHE_LIB_NAME"] = "libflashe_hip_tuning.so"
 import numpy as np
 from flashe_amd.engine import Engine

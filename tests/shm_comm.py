@@ -1,8 +1,15 @@
 """A communicator double for -m gpu tests of the N > 1 path on ONE GPU: several processes share device 0, every rank runs the real
 HIP kernels through HipOps, and the exchange -- where production uses RCCL (flashe_rccl_*) -- goes through files in a shared
-directory (device -> host -> file -> host -> device).  Same method surface as flashe_amd.dist.RcclComm.  Test infrastructure."""
+directory (device -> host -> file -> host -> device).  Same method surface as flashe_amd.dist.RcclComm.  Test infrastructure.
+
+launch_ranks / run_ranks host the ranks: at most RANK_PROCS processes open the GPU (the test process makes one more), so a world
+larger than that runs several ranks per process, one thread each, every rank with its own engines and its own ShmComm."""
 import os
+import subprocess
+import sys
+import threading
 import time
+import traceback
 
 import numpy as np
 
@@ -109,3 +116,50 @@ class ShmComm:
 
     def close(self):
         pass
+
+
+RANK_PROCS = 4
+
+
+def launch_ranks(script, world, directory, timeout):
+    """Runs ranks 0 .. world - 1 of `script` (which calls run_ranks) on device 0: rank r in process r % P, P = min(world, RANK_PROCS).
+    -> [(returncode, stdout, stderr)] per process; process 0 hosts rank 0.  Processes still running at the deadline are killed."""
+    P = min(world, RANK_PROCS)
+    procs = []
+    try:
+        for p in range(P):
+            env = dict(os.environ, RANKS=",".join(str(r) for r in range(p, world, P)), WORLD_SIZE=str(world),
+                       FLASHE_TEST_SHM_DIR=str(directory), OMP_WAIT_POLICY="passive")
+            procs.append(subprocess.Popen([sys.executable, script], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
+        deadline = time.time() + timeout
+        outs = [p.communicate(timeout=max(deadline - time.time(), 1.0)) for p in procs]
+    finally:
+        for p in procs:
+            if p.poll() is None:
+                p.kill()
+                p.wait()
+    return [(p.returncode, so, se) for p, (so, se) in zip(procs, outs)]
+
+
+def run_ranks(main):
+    """The worker side of launch_ranks: main(rank, world) for every rank in RANKS (comma-separated), each in its own thread.
+    Exit status 1 when any rank raised (its traceback on stderr)."""
+    world = int(os.environ["WORLD_SIZE"])
+    ranks = [int(r) for r in os.environ["RANKS"].split(",")]
+    failed = []
+
+    def body(rank):
+        try:
+            main(rank, world)
+        except BaseException:
+            failed.append(rank)
+            traceback.print_exc()
+
+    threads = [threading.Thread(target=body, args=(r,), name=f"rank-{r}") for r in ranks]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    if failed:
+        print(f"ranks {sorted(failed)} failed", file=sys.stderr)
+        sys.exit(1)

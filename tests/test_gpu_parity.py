@@ -15,6 +15,9 @@ KEY = bytes(range(32))
 # The bit-sliced PRF backends live in a separate library (make -C flashe_amd/csrc bitslice): tests/test_gpu_bitslice.py re-runs the
 # backend-parametrised tests of this file in a process that loads it (FLASHE_LIB_NAME) with this switch on.
 BITSLICE_BACKENDS = [2, 4] if os.environ.get("FLASHE_TEST_BITSLICE") == "1" else []
+# In a process on the product library, test_bitsliced_prf_backend_vs_oracle checks both backends in a child process that loads the
+# bit-sliced library (one parameter, None; its id is the one these cases have always carried here).
+BITSLICE_CASES = BITSLICE_BACKENDS or [pytest.param(None, id="NOTSET")]
 
 
 @pytest.fixture(scope="module")
@@ -184,11 +187,40 @@ def test_encrypt_decrypt_vs_oracle(E, oracle, b, n, J):
     assert np.array_equal(eng.mask(it, [9], n, J), oracle.mask(KEY, it, 9, n, J, b))
 
 
-@pytest.mark.parametrize("backend", BITSLICE_BACKENDS)
+_BITSLICE_CHILD = r"""
+import os, sys
+root = sys.argv[1]
+sys.path.insert(0, root); sys.path.insert(0, os.path.join(root, "tests"))
+from flashe_amd import engine
+from oracle import flashe_oracle
+import test_gpu_parity
+flashe_oracle.build()
+flashe_oracle.set_num_threads(min(os.cpu_count() or 1, 16))
+for backend in test_gpu_parity.BITSLICE_BACKENDS:
+    test_gpu_parity.check_bitsliced_backend(engine, flashe_oracle, int(sys.argv[2]), int(sys.argv[3]), backend)
+print("BITSLICE_OK", test_gpu_parity.BITSLICE_BACKENDS)
+"""
+
+
+@pytest.mark.parametrize("backend", BITSLICE_CASES)
 @pytest.mark.parametrize("b,n", [(128, 100003), (128, 1024), (128, 1), (128, 2049), (127, 4099), (65, 70001), (100, 1000000)])
 def test_bitsliced_prf_backend_vs_oracle(E, oracle, b, n, backend):
     """The bit-sliced VALU PRF kernels (2: 32 blocks per lane, 4: packed, 16 blocks per lane) must give the
-    same bits as the LDS-table kernel and the oracle."""
+    same bits as the LDS-table kernel and the oracle.  backend None: both, in a child process on libflashe_hip_bitslice.so."""
+    if backend is not None:
+        check_bitsliced_backend(E, oracle, b, n, backend)
+        return
+    import subprocess
+    import sys
+    from conftest import ROOT
+    assert os.path.exists(os.path.join(ROOT, "flashe_amd", "libflashe_hip_bitslice.so")), "libflashe_hip_bitslice.so not built"
+    env = dict(os.environ, FLASHE_LIB_NAME="libflashe_hip_bitslice.so", FLASHE_TEST_BITSLICE="1", OMP_WAIT_POLICY="passive")
+    r = subprocess.run([sys.executable, "-c", _BITSLICE_CHILD, ROOT, str(b), str(n)], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0 and "BITSLICE_OK [2, 4]" in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]
+
+
+def check_bitsliced_backend(E, oracle, b, n, backend):
+    """One bit-sliced backend on the library this process loaded, against the oracle and the table backend."""
     rng = np.random.Generator(np.random.PCG64(b + n))
     eng = make(E, b)
     eng.set_prf_backend(backend)
@@ -638,23 +670,17 @@ def test_sharded_round_through_rccl_single_rank():
 
 @pytest.mark.parametrize("world", [2, 3, 8])
 def test_sharded_round_several_ranks_real_kernels(world, tmp_path):
-    """The N > 1 round with REAL kernels and `world` ranks: processes share device 0 and run flashe_amd.dist.ShardedRound through
-    HipOps exactly as on a multi-GPU node (slices, block-cyclic chunks, sliced decrypts at non-zero `first`, chained job lists,
-    device-side packed carry resolution); only the transport is swapped for a file-based double of RcclComm (tests/shm_comm.py),
-    because an RCCL group cannot have two ranks on one GPU.  Every schedule, equal / unequal / sparse dealing, vs the oracle.  With
-    world = 8 the "uneven" case IS BASELINE config 4's dealing: 10 clients as 2, 2, 1, 1, 1, 1, 1, 1."""
-    import subprocess
-    import sys
+    """The N > 1 round with REAL kernels and `world` ranks: the ranks share device 0 (a thread each, in at most four processes) and run
+    flashe_amd.dist.ShardedRound through HipOps exactly as on a multi-GPU node (slices, block-cyclic chunks, sliced decrypts at non-zero
+    `first`, chained job lists, device-side packed carry resolution); only the transport is swapped for a file-based double of RcclComm
+    (tests/shm_comm.py), because an RCCL group cannot have two ranks on one GPU.  Every schedule, equal / unequal / sparse dealing, vs
+    the oracle.  With world = 8 the "uneven" case IS BASELINE config 4's dealing: 10 clients as 2, 2, 1, 1, 1, 1, 1, 1."""
     from conftest import ROOT
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), FLASHE_TEST_SHM_DIR=str(tmp_path), OMP_WAIT_POLICY="passive")
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "dist_gpu_multi_worker.py")], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
-    outs = [p.communicate(timeout=900) for p in procs]
-    for r, (p, (so, se)) in enumerate(zip(procs, outs)):
-        assert p.returncode == 0, f"rank {r}: {so[-1500:]}{se[-3000:]}"
-    assert "DIST_GPU_MULTI_OK" in outs[0][0]
+    from shm_comm import launch_ranks
+    outs = launch_ranks(os.path.join(ROOT, "tests", "dist_gpu_multi_worker.py"), world, tmp_path, timeout=900)
+    for p, (rc, so, se) in enumerate(outs):
+        assert rc == 0, f"process {p}: {so[-1500:]}{se[-3000:]}"
+    assert "DIST_GPU_MULTI_OK" in outs[0][1]
 
 
 def _bench_shm(tmp_path, extra, env_extra=None, timeout=600):
