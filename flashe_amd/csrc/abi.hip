@@ -137,6 +137,10 @@ int fail(flashe_ctx *ctx, int code, const char *fmt, ...)
 }  // namespace flashe_host
 
 using flashe_host::fail;
+using flashe_host::Tmp;
+using flashe_host::vec_bytes;
+using flashe_host::check_double_idx;
+using flashe_host::check_field_bits;
 
 namespace {
 
@@ -149,6 +153,20 @@ int ensure(flashe_ctx *ctx, flashe_ctx::Buf &b, size_t bytes)
     size_t cap = std::max<size_t>(bytes, 4096);
     HIP_TRY(ctx, hipMalloc(&b.p, cap));
     b.cap = cap;
+    return FLASHE_OK;
+}
+
+// A model-wide codec call's layer table into ctx->codec_tab.  (Pageable source: the copy has left `tab` when the call returns; stream
+// order keeps an earlier launch's table intact until it ends.)
+template <class Layer> int stage_table(flashe_ctx *ctx, const std::vector<Layer> &tab, const Layer **tab_dev, int *n_tab)
+{
+    if (tab.empty()) { *tab_dev = nullptr; *n_tab = 0; return FLASHE_OK; }
+    int rc = ensure(ctx, ctx->codec_tab, tab.size() * sizeof(Layer));
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->codec_tab.p, tab.data(), tab.size() * sizeof(Layer), hipMemcpyHostToDevice, ctx->env.stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->env.stream));
+    *tab_dev = static_cast<const Layer *>(ctx->codec_tab.p);
+    *n_tab = static_cast<int>(tab.size());
     return FLASHE_OK;
 }
 
@@ -192,12 +210,7 @@ int check_device_flag(flashe_ctx *ctx)
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-size_t vec_bytes(const flashe_ctx *ctx, uint64_t n) { return static_cast<size_t>(n) * ctx->limbs * 8; }
-
-// RAII temp device buffer for the host-pointer wrappers.  Staging blocks are kept by the ctx and reused: a hipMalloc + hipFree
-// pair of a 160 MB block costs more than moving 160 MB over PCIe Gen5 on this platform (measured 7 ms against 2.9 ms,
-// tests/perf/e2e_calls.py).  The blocks a ctx keeps are bounded by a byte budget (FLASHE_STAGING_POOL_MB, default 8 GiB of the
-// 288 GB); beyond it the largest free block makes room, and a request that still does not fit is a plain allocation.
+// (Tmp, the staging lease of the host-pointer twins: ctx.h)
 size_t pool_budget()
 {
     static const size_t v = [] {
@@ -215,26 +228,88 @@ struct HipBackend final : flashe_pool::Backend {
 };
 HipBackend &hip_backend() { static HipBackend b; return b; }
 
-struct Tmp {
-    void *p = nullptr;
-    flashe_ctx *owner = nullptr;
-    int slot = -1;
-    ~Tmp()
-    {
-        if (!p) return;
-        if (slot >= 0) owner->staging->give_back(slot);
-        else (void)hipFree(p);
-    }
-    hipError_t alloc(flashe_ctx *ctx, size_t bytes)
-    {
-        if (!ctx->staging) ctx->staging = new flashe_pool::StagingPool(&hip_backend(), pool_budget());
-        owner = ctx;
-        return static_cast<hipError_t>(ctx->staging->lease(bytes, &p, &slot));
-    }
-    template <class T> T *as() { return static_cast<T *>(p); }
-};
+// ---- argument checks shared by the entry points ----
+int check_scheme(flashe_ctx *ctx, int scheme)
+{
+    if (scheme != FLASHE_SCHEME_SINGLE && scheme != FLASHE_SCHEME_DOUBLE) return fail(ctx, FLASHE_EINVAL, "unknown scheme %d", scheme);
+    return FLASHE_OK;
+}
+
+// 2-limb elements move 16 bytes at a time
+int check_wide_aligned(flashe_ctx *ctx, std::initializer_list<const void *> vecs)
+{
+    if (ctx->limbs == 2)
+        for (const void *p : vecs)
+            if (!aligned16(p)) return fail(ctx, FLASHE_EINVAL, "device vectors must be 16-byte aligned");
+    return FLASHE_OK;
+}
+
+// every one of the n vectors given and `align`-byte aligned
+template <class T> int check_operands(flashe_ctx *ctx, int n, const T *const *v, int align)
+{
+    for (int c = 0; c < n; c++)
+        if (!v[c] || (reinterpret_cast<uintptr_t>(v[c]) & static_cast<uintptr_t>(align - 1)))
+            return fail(ctx, FLASHE_EINVAL, "operand %d is null or not %d-byte aligned", c, align);
+    return FLASHE_OK;
+}
+
+bool ct_aligned(const flashe_ctx *ctx, const void *p) { return (reinterpret_cast<uintptr_t>(p) & (ctx->limbs == 2 ? 15u : 7u)) == 0; }
+
+// a sum written by the pass that reads the vectors: aligned like a ciphertext vector, and none of them
+int check_sum_aligned(flashe_ctx *ctx, const void *sum_out_dev)
+{
+    return ct_aligned(ctx, sum_out_dev) ? FLASHE_OK : fail(ctx, FLASHE_EINVAL, "sum_out_dev must be aligned like a ciphertext vector");
+}
+template <class P, class Q> int check_sum_apart(flashe_ctx *ctx, const void *sum_out_dev, int n_vec, P pt_dev, Q ct_dev)
+{
+    for (int v = 0; v < n_vec; v++)
+        if ((ct_dev && ct_dev[v] == sum_out_dev) || (pt_dev && pt_dev[v] == sum_out_dev))
+            return fail(ctx, FLASHE_EINVAL, "sum_out_dev must not be one of the plaintext or ciphertext vectors (vector %d)", v);
+    return FLASHE_OK;
+}
+
+// Equal shares when several launches are needed (b <= 64, 100 vectors: 4 x 25, not 32 + 32 + 32 + 4); 2-limb vectors travel in the
+// compact table, up to 128 per launch (the chained launch holds 128 outputs for every int_bits; without it the b <= 64 job table holds
+// kMaxBatch).  launch(v0, nv) covers vectors [v0, v0 + nv).
+template <class Launch> int batch_shares(flashe_ctx *ctx, int n_vec, Launch &&launch)
+{
+    const int cap = (ctx->limbs == 2 || ctx->env.use_chain) ? kMaxUniformBatch : kMaxBatch;
+    const int launches = (n_vec + cap - 1) / cap, per_launch = launches ? (n_vec + launches - 1) / launches : 1;
+    for (int v0 = 0; v0 < n_vec; v0 += per_launch) HIP_TRY(ctx, launch(v0, std::min(per_launch, n_vec - v0)));
+    return FLASHE_OK;
+}
 
 }  // namespace
+
+namespace flashe_host {
+
+// The double mask of client idx subtracts the stream of prefix idx + 1, and the reference builds that prefix with
+// (self.idx + 1).to_bytes(4, 'big') (jzf_flashe.py:352-353): OverflowError for idx = 2^32 - 1.  The raw ABI refuses the same value
+// instead of wrapping to prefix 0 (SURVEY.md section 8, "ranges: idx + 1 < 2^32").
+int check_double_idx(flashe_ctx *ctx, int scheme, const uint32_t *idx, int n_idx)
+{
+    if (scheme != FLASHE_SCHEME_DOUBLE || !idx) return FLASHE_OK;
+    for (int v = 0; v < n_idx; v++)
+        if (idx[v] == 0xffffffffu)
+            return fail(ctx, FLASHE_EINVAL, "double mask: idx + 1 = 2^32 does not fit the 4-byte prefix field (entry %d; the reference raises OverflowError, jzf_flashe.py:352-353)", v);
+    return FLASHE_OK;
+}
+
+int check_field_bits(flashe_ctx *ctx, int field_bits)
+{
+    if (field_bits < 1 || field_bits > 64 || field_bits > ctx->int_bits)
+        return fail(ctx, FLASHE_EINVAL, "field_bits must be in [1, min(64, int_bits)], got %d", field_bits);
+    return FLASHE_OK;
+}
+
+}  // namespace flashe_host
+
+hipError_t flashe_host::Tmp::alloc(flashe_ctx *ctx, size_t bytes)
+{
+    if (!ctx->staging) ctx->staging = new flashe_pool::StagingPool(&hip_backend(), pool_budget());
+    owner = ctx;
+    return static_cast<hipError_t>(ctx->staging->lease(bytes, &p, &slot));
+}
 
 extern "C" {
 
@@ -702,18 +777,6 @@ int flashe_event_elapsed_ms(flashe_ctx *ctx, void *start, void *stop, float *ms)
 }
 
 // ---- PRF / encrypt / decrypt ----
-// The double mask of client idx subtracts the stream of prefix idx + 1, and the reference builds that prefix with
-// (self.idx + 1).to_bytes(4, 'big') (jzf_flashe.py:352-353): OverflowError for idx = 2^32 - 1.  The raw ABI refuses the same value
-// instead of wrapping to prefix 0 (SURVEY.md section 8, "ranges: idx + 1 < 2^32").
-static int check_double_idx(flashe_ctx *ctx, int scheme, const uint32_t *idx, int n_idx)
-{
-    if (scheme != FLASHE_SCHEME_DOUBLE || !idx) return FLASHE_OK;
-    for (int v = 0; v < n_idx; v++)
-        if (idx[v] == 0xffffffffu)
-            return fail(ctx, FLASHE_EINVAL, "double mask: idx + 1 = 2^32 does not fit the 4-byte prefix field (entry %d; the reference raises OverflowError, jzf_flashe.py:352-353)", v);
-    return FLASHE_OK;
-}
-
 static int check_prf_args(flashe_ctx *ctx, int n_add, int n_minus, uint32_t n_jobs, const void *out, const void *in, int in_limbs)
 {
     if (n_add < 0 || n_minus < 0) return fail(ctx, FLASHE_EINVAL, "negative prefix list length: add %d minus %d", n_add, n_minus);
@@ -749,36 +812,23 @@ static hipError_t prf_lists(flashe_ctx *ctx, uint32_t iter, const uint32_t *add,
     return hipSuccess;
 }
 
+// the whole-vector forms: their range twins over [0, n)
 int flashe_mask_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_idx, uint64_t n, uint32_t n_jobs, uint64_t *out_dev)
 {
-    CHECK_CTX(ctx);
-    if (n && !out_dev) return fail(ctx, FLASHE_EINVAL, "null output");
-    int rc = check_prf_args(ctx, n_idx, 0, n_jobs, out_dev, nullptr, 0);
-    if (rc) return rc;
-    if (n_idx == 0) { if (n) HIP_TRY(ctx, hipMemsetAsync(out_dev, 0, vec_bytes(ctx, n), ctx->env.stream)); return FLASHE_OK; }
-    HIP_TRY(ctx, prf_lists(ctx, iter, idx, n_idx, nullptr, 0, n, n_jobs, 0, n, nullptr, 0, out_dev));
-    return FLASHE_OK;
+    return flashe_mask_range_dev(ctx, iter, idx, n_idx, n, n_jobs, 0, n, out_dev);
 }
 
 int flashe_encrypt_dev(flashe_ctx *ctx, uint32_t iter, uint32_t idx, int scheme, uint64_t n, uint32_t n_jobs,
                        const uint64_t *pt_dev, int pt_limbs, uint64_t *ct_dev)
 {
-    CHECK_CTX(ctx);
-    if (scheme != FLASHE_SCHEME_SINGLE && scheme != FLASHE_SCHEME_DOUBLE) return fail(ctx, FLASHE_EINVAL, "unknown scheme %d", scheme);
-    if (n && (!pt_dev || !ct_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    int rc = check_prf_args(ctx, 1, scheme, n_jobs, ct_dev, pt_dev, pt_limbs);
-    if (rc) return rc;
-    if ((rc = check_double_idx(ctx, scheme, &idx, 1))) return rc;
-    const uint32_t add = idx, minus = idx + 1;
-    HIP_TRY(ctx, launch_prf(ctx->env, iter, &add, 1, &minus, scheme == FLASHE_SCHEME_DOUBLE ? 1 : 0, n, n_jobs, 0, n, pt_dev, pt_limbs, ct_dev));
-    return FLASHE_OK;
+    return flashe_encrypt_range_dev(ctx, iter, idx, scheme, n, n_jobs, 0, n, pt_dev, pt_limbs, ct_dev);
 }
 
 int flashe_encrypt_batch_dev(flashe_ctx *ctx, uint32_t iter, int scheme, uint64_t n, uint32_t n_jobs, int n_vec, const uint32_t *idx,
                              const uint64_t *const *pt_dev, int pt_limbs, uint64_t *const *ct_dev)
 {
     CHECK_CTX(ctx);
-    if (scheme != FLASHE_SCHEME_SINGLE && scheme != FLASHE_SCHEME_DOUBLE) return fail(ctx, FLASHE_EINVAL, "unknown scheme %d", scheme);
+    if (int rc = check_scheme(ctx, scheme)) return rc;
     if (n_vec < 0 || (n_vec && (!idx || !pt_dev || !ct_dev))) return fail(ctx, FLASHE_EINVAL, "bad batch arguments");
     if (int rc = check_double_idx(ctx, scheme, idx, n_vec)) return rc;
     for (int v = 0; v < n_vec; v++) {
@@ -794,17 +844,9 @@ int flashe_encrypt_batch_dev(flashe_ctx *ctx, uint32_t iter, int scheme, uint64_
         }
         return FLASHE_OK;
     }
-    // equal shares when several launches are needed (b <= 64, 100 vectors: 4 x 25, not 32 + 32 + 32 + 4); 2-limb vectors
-    // travel in the compact table, up to 128 per launch
-    // (the chained launch holds 128 outputs for every int_bits; without it the b <= 64 job table holds kMaxBatch)
-    const int cap = (ctx->limbs == 2 || ctx->env.use_chain) ? kMaxUniformBatch : kMaxBatch;
-    const int per_launch = n_vec ? (n_vec + (n_vec + cap - 1) / cap - 1) / ((n_vec + cap - 1) / cap) : 1;
-    for (int v0 = 0; v0 < n_vec; v0 += per_launch) {
-        const int nv = std::min(per_launch, n_vec - v0);
-        HIP_TRY(ctx, launch_prf_batch(ctx->env, iter, scheme == FLASHE_SCHEME_DOUBLE, nv, idx + v0, pt_dev + v0, pt_limbs, ct_dev + v0, n,
-                                      n_jobs));
-    }
-    return FLASHE_OK;
+    return batch_shares(ctx, n_vec, [&](int v0, int nv) {
+        return launch_prf_batch(ctx->env, iter, scheme == FLASHE_SCHEME_DOUBLE, nv, idx + v0, pt_dev + v0, pt_limbs, ct_dev + v0, n, n_jobs);
+    });
 }
 
 // ---- compact layout for int_bits <= 32 (new; no reference counterpart) ----
@@ -827,7 +869,7 @@ int flashe_encrypt_batch_u32_dev(flashe_ctx *ctx, uint32_t iter, int scheme, uin
                                  const uint32_t *const *pt_dev, uint32_t *const *ct_dev)
 {
     CHECK_CTX(ctx);
-    if (scheme != FLASHE_SCHEME_SINGLE && scheme != FLASHE_SCHEME_DOUBLE) return fail(ctx, FLASHE_EINVAL, "unknown scheme %d", scheme);
+    if (int rc = check_scheme(ctx, scheme)) return rc;
     if (n_vec < 0 || (n_vec && (!idx || !pt_dev || !ct_dev))) return fail(ctx, FLASHE_EINVAL, "bad batch arguments");
     int rc = check_u32(ctx, n, n_jobs);
     if (rc || (rc = check_double_idx(ctx, scheme, idx, n_vec))) return rc;
@@ -838,15 +880,10 @@ int flashe_encrypt_batch_u32_dev(flashe_ctx *ctx, uint32_t iter, int scheme, uin
     }
     LaunchEnv env = ctx->env;
     env.elem32 = 1;
-    const int cap = kMaxUniformBatch;
-    const int per_launch = (n_vec + (n_vec + cap - 1) / cap - 1) / ((n_vec + cap - 1) / cap);
-    for (int v0 = 0; v0 < n_vec; v0 += per_launch) {
-        const int nv = std::min(per_launch, n_vec - v0);
-        const hipError_t e = launch_prf_batch(env, iter, scheme == FLASHE_SCHEME_DOUBLE, nv, idx + v0, reinterpret_cast<const uint64_t *const *>(pt_dev + v0), 1,
-                                              reinterpret_cast<uint64_t *const *>(ct_dev + v0), n, n_jobs);
-        HIP_TRY(ctx, e);
-    }
-    return FLASHE_OK;
+    return batch_shares(ctx, n_vec, [&](int v0, int nv) {           // (check_u32: the chained kernels, up to kMaxUniformBatch per launch)
+        return launch_prf_batch(env, iter, scheme == FLASHE_SCHEME_DOUBLE, nv, idx + v0, reinterpret_cast<const uint64_t *const *>(pt_dev + v0), 1,
+                                reinterpret_cast<uint64_t *const *>(ct_dev + v0), n, n_jobs);
+    });
 }
 
 // flashe_encrypt_batch_u32_dev AND sum_out_dev = sum_v ct[v] mod 2^b written by the same launch: the compact twin of
@@ -861,9 +898,7 @@ int flashe_encrypt_batch_sum_u32_dev(flashe_ctx *ctx, uint32_t iter, int scheme,
     // from the memset)
     if (n && !sum_out_dev) return fail(ctx, FLASHE_EINVAL, "flashe_encrypt_batch_sum_u32_dev: null sum_out_dev");
     if (reinterpret_cast<uintptr_t>(sum_out_dev) & 3u) return fail(ctx, FLASHE_EINVAL, "sum_out_dev must be 4-byte aligned");
-    for (int v = 0; v < n_vec && ct_dev; v++)
-        if (n && (ct_dev[v] == sum_out_dev || (pt_dev && pt_dev[v] == sum_out_dev)))
-            return fail(ctx, FLASHE_EINVAL, "sum_out_dev must not be one of the plaintext or ciphertext vectors");
+    if (n && ct_dev) { if (int rc = check_sum_apart(ctx, sum_out_dev, n_vec, pt_dev, ct_dev)) return rc; }
     if (scheme == FLASHE_SCHEME_DOUBLE && n && n_vec > 0 && n_vec <= kMaxUniformBatch && idx && pt_dev && ct_dev) {
         int rc = check_u32(ctx, n, n_jobs);
         if (rc || (rc = check_double_idx(ctx, scheme, idx, n_vec))) return rc;
@@ -902,8 +937,7 @@ int flashe_aggregate_decrypt_u32_dev(flashe_ctx *ctx, uint32_t iter, const uint3
     rc = check_range(ctx, n, first, count);
     if (rc) return rc;
     if (count == 0) return FLASHE_OK;
-    for (int c = 0; c < C; c++)
-        if (!cts_dev[c] || (reinterpret_cast<uintptr_t>(cts_dev[c]) & 3u)) return fail(ctx, FLASHE_EINVAL, "operand %d is null or not 4-byte aligned", c);
+    if ((rc = check_operands(ctx, C, cts_dev, 4))) return rc;
     const uintptr_t need = static_cast<uintptr_t>(out_elem_bytes - 1);
     if ((reinterpret_cast<uintptr_t>(out_dev) | reinterpret_cast<uintptr_t>(agg_out_dev)) & need) return fail(ctx, FLASHE_EINVAL, "outputs must be %d-byte aligned", out_elem_bytes);
     LaunchEnv env = ctx->env;
@@ -931,8 +965,7 @@ int flashe_aggregate_elem_u32_dev(flashe_ctx *ctx, int C, const uint32_t *const 
     CHECK_CTX(ctx);
     if (ctx->int_bits > 32) return fail(ctx, FLASHE_EINVAL, "the uint32 layout needs int_bits <= 32, this ctx has %d", ctx->int_bits);
     if (C < 1 || !cts_dev || (n && !out_dev)) return fail(ctx, FLASHE_EINVAL, "aggregate_elem_u32: bad arguments");
-    for (int c = 0; c < C; c++)
-        if (n && (!cts_dev[c] || (reinterpret_cast<uintptr_t>(cts_dev[c]) & 3u))) return fail(ctx, FLASHE_EINVAL, "operand %d is null or not 4-byte aligned", c);
+    if (n) { if (int rc = check_operands(ctx, C, cts_dev, 4)) return rc; }
     if (reinterpret_cast<uintptr_t>(out_dev) & 3u) return fail(ctx, FLASHE_EINVAL, "out_dev must be 4-byte aligned");
     // more operands than one pass holds: partial sums accumulate in out (every pass reads out as one operand)
     int done = 0;
@@ -969,12 +1002,9 @@ int flashe_encrypt_batch_sum_dev(flashe_ctx *ctx, uint32_t iter, int scheme, uin
     CHECK_CTX(ctx);
     if (!sum_out_dev && n && n_vec) return fail(ctx, FLASHE_EINVAL, "flashe_encrypt_batch_sum_dev: null sum_out_dev");
     if (n_vec > 0) { if (int rc = check_double_idx(ctx, scheme, idx, n_vec)) return rc; }
-    if (n && n_vec && ((ctx->limbs == 2 && !aligned16(sum_out_dev)) || (reinterpret_cast<uintptr_t>(sum_out_dev) & 7u)))
-        return fail(ctx, FLASHE_EINVAL, "sum_out_dev must be aligned like a ciphertext vector");
-    if (n_vec > 0 && n) {
-        for (int v = 0; v < n_vec; v++)
-            if ((ct_dev && ct_dev[v] == sum_out_dev) || (pt_dev && pt_dev[v] == sum_out_dev))
-                return fail(ctx, FLASHE_EINVAL, "sum_out_dev must not be one of the plaintext or ciphertext vectors");
+    if (n && n_vec) {
+        if (int rc = check_sum_aligned(ctx, sum_out_dev)) return rc;
+        if (int rc = check_sum_apart(ctx, sum_out_dev, n_vec, pt_dev, ct_dev)) return rc;
     }
     if (scheme == FLASHE_SCHEME_DOUBLE && n && n_vec > 0 && idx && pt_dev && ct_dev) {
         // one launch: the chained encrypt keeps the running sum of its outputs in registers and stores it once
@@ -1038,16 +1068,7 @@ int flashe_prf_jobs_dev(flashe_ctx *ctx, uint32_t iter, uint64_t n, uint32_t n_j
 int flashe_decrypt_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx, int n_minus,
                        uint64_t n, uint32_t n_jobs, const uint64_t *in_dev, uint64_t *out_dev)
 {
-    CHECK_CTX(ctx);
-    if (n && (!in_dev || !out_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    int rc = check_prf_args(ctx, n_add, n_minus, n_jobs, out_dev, in_dev, ctx->limbs);
-    if (rc) return rc;
-    if (n_add == 0 && n_minus == 0) {
-        HIP_TRY(ctx, launch_combine(ctx->env, n, in_dev, ctx->limbs, nullptr, nullptr, out_dev));
-        return FLASHE_OK;
-    }
-    HIP_TRY(ctx, prf_lists(ctx, iter, add_idx, n_add, minus_idx, n_minus, n, n_jobs, 0, n, in_dev, ctx->limbs, out_dev));
-    return FLASHE_OK;
+    return flashe_decrypt_range_dev(ctx, iter, add_idx, n_add, minus_idx, n_minus, n, n_jobs, 0, n, in_dev, out_dev);
 }
 
 // ---- fused codec: quantise -> encrypt and decrypt -> unquantise in ONE launch each ----
@@ -1056,7 +1077,7 @@ int flashe_quantize_encrypt_dev(flashe_ctx *ctx, uint32_t iter, uint32_t idx, in
                                 int x_is_f64, double alpha, int element_bits, const double *u_dev, uint64_t *ct_dev)
 {
     CHECK_CTX(ctx);
-    if (scheme != FLASHE_SCHEME_SINGLE && scheme != FLASHE_SCHEME_DOUBLE) return fail(ctx, FLASHE_EINVAL, "unknown scheme %d", scheme);
+    if (int rc = check_scheme(ctx, scheme)) return rc;
     if (n && (!x_dev || !u_dev || !ct_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
     if (!(alpha > 0)) return fail(ctx, FLASHE_EINVAL, "alpha must be positive");
     if (element_bits < 1 || element_bits > 62 || element_bits > ctx->int_bits)
@@ -1069,6 +1090,30 @@ int flashe_quantize_encrypt_dev(flashe_ctx *ctx, uint32_t iter, uint32_t idx, in
     if ((rc = check_double_idx(ctx, scheme, &idx, 1))) return rc;
     const uint32_t add = idx, minus = idx + 1;
     HIP_TRY(ctx, launch_prf(env, iter, &add, 1, &minus, scheme == FLASHE_SCHEME_DOUBLE ? 1 : 0, n, n_jobs, 0, n, nullptr, 0, ct_dev));
+    return FLASHE_OK;
+}
+
+// the unmask + unquantise of prefix lists of any length: all but the last group accumulate into ctx scratch, the last launch writes
+// the floats
+static int prf_lists_unquantize(flashe_ctx *ctx, const Codec &cq, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx,
+                                int n_minus, uint64_t n, uint32_t n_jobs, uint64_t first, uint64_t count, const uint64_t *in_dev)
+{
+    const uint64_t *src = in_dev;
+    int a = 0, m = 0;
+    if (n_add > kMaxIdx || n_minus > kMaxIdx) {
+        const int rc = ensure(ctx, ctx->stream_tmp, vec_bytes(ctx, count));
+        if (rc) return rc;
+        uint64_t *tmp = static_cast<uint64_t *>(ctx->stream_tmp.p);
+        while (n_add - a > kMaxIdx || n_minus - m > kMaxIdx) {
+            const int na = std::min(kMaxIdx, n_add - a), nm = std::min(kMaxIdx, n_minus - m);
+            HIP_TRY(ctx, launch_prf(ctx->env, iter, add_idx + a, na, minus_idx + m, nm, n, n_jobs, first, count, src, ctx->limbs, tmp));
+            a += na; m += nm; src = tmp;
+        }
+    }
+    LaunchEnv env = ctx->env;
+    env.codec = &cq;
+    HIP_TRY(ctx, launch_prf(env, iter, add_idx + a, n_add - a, minus_idx + m, n_minus - m, n, n_jobs, first, count, src, ctx->limbs,
+                            const_cast<uint64_t *>(src)));
     return FLASHE_OK;
 }
 
@@ -1095,24 +1140,7 @@ int flashe_decrypt_unquantize_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t
         HIP_TRY(ctx, launch_unquantize(ctx->env, n, tmp, ctx->limbs, alpha, element_bits, num_clients, out_dev));
         return FLASHE_OK;
     }
-    // lists longer than one launch holds: all but the last group accumulate into ctx scratch, the last launch writes the floats
-    const uint64_t *src = in_dev;
-    int a = 0, m = 0;
-    if (n_add > kMaxIdx || n_minus > kMaxIdx) {
-        rc = ensure(ctx, ctx->stream_tmp, vec_bytes(ctx, n));
-        if (rc) return rc;
-        uint64_t *tmp = static_cast<uint64_t *>(ctx->stream_tmp.p);
-        while (n_add - a > kMaxIdx || n_minus - m > kMaxIdx) {
-            const int na = std::min(kMaxIdx, n_add - a), nm = std::min(kMaxIdx, n_minus - m);
-            HIP_TRY(ctx, launch_prf(ctx->env, iter, add_idx + a, na, minus_idx + m, nm, n, n_jobs, 0, n, src, ctx->limbs, tmp));
-            a += na; m += nm; src = tmp;
-        }
-    }
-    LaunchEnv env = ctx->env;
-    env.codec = &cq;
-    HIP_TRY(ctx, launch_prf(env, iter, add_idx + a, n_add - a, minus_idx + m, n_minus - m, n, n_jobs, 0, n, src, ctx->limbs,
-                            const_cast<uint64_t *>(src)));
-    return FLASHE_OK;
+    return prf_lists_unquantize(ctx, cq, iter, add_idx, n_add, minus_idx, n_minus, n, n_jobs, 0, n, in_dev);
 }
 
 // ---- the same over a flattened model: one launch, per-layer parameters from a device table (jzf_aggregator.py:721-741, :887-899) ----
@@ -1139,15 +1167,7 @@ static int stage_codec_layers(flashe_ctx *ctx, uint64_t n, const flashe_codec_la
         tab.push_back(front ? codec_layer_front(e.start, e.x_dev, e.x_is_f64 != 0, e.alpha, element_bits)
                             : codec_layer_back(e.start, e.alpha, element_bits, num_clients));
     }
-    if (tab.empty()) { *tab_dev = nullptr; *n_tab = 0; return FLASHE_OK; }
-    int rc = ensure(ctx, ctx->codec_tab, tab.size() * sizeof(CodecLayer));
-    if (rc) return rc;
-    // (pageable source: the copy has left `tab` when the call returns; stream order keeps an earlier launch's table intact until it ends)
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->codec_tab.p, tab.data(), tab.size() * sizeof(CodecLayer), hipMemcpyHostToDevice, ctx->env.stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->env.stream));
-    *tab_dev = static_cast<const CodecLayer *>(ctx->codec_tab.p);
-    *n_tab = static_cast<int>(tab.size());
-    return FLASHE_OK;
+    return stage_table(ctx, tab, tab_dev, n_tab);
 }
 
 int flashe_quantize_encrypt_model_dev(flashe_ctx *ctx, uint32_t iter, uint32_t idx, int scheme, uint64_t n, uint32_t n_jobs, uint64_t first,
@@ -1155,7 +1175,7 @@ int flashe_quantize_encrypt_model_dev(flashe_ctx *ctx, uint32_t iter, uint32_t i
                                       uint64_t *ct_dev)
 {
     CHECK_CTX(ctx);
-    if (scheme != FLASHE_SCHEME_SINGLE && scheme != FLASHE_SCHEME_DOUBLE) return fail(ctx, FLASHE_EINVAL, "unknown scheme %d", scheme);
+    if (int rc = check_scheme(ctx, scheme)) return rc;
     if (count && (!u_dev || !ct_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
     if (element_bits < 1 || element_bits > 62 || element_bits > ctx->int_bits)
         return fail(ctx, FLASHE_EINVAL, "element_bits must be in [1, min(62, int_bits)], got %d", element_bits);
@@ -1196,24 +1216,7 @@ int flashe_decrypt_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const ui
     if (rc || count == 0) return rc;
     Codec cq{};
     cq.fout = out_dev; cq.layers = tab; cq.n_layers = n_tab; cq.k0 = first;
-    // lists longer than one launch holds: all but the last group accumulate into ctx scratch, the last launch writes the floats
-    const uint64_t *src = in_dev;
-    int a = 0, m = 0;
-    if (n_add > kMaxIdx || n_minus > kMaxIdx) {
-        rc = ensure(ctx, ctx->stream_tmp, vec_bytes(ctx, count));
-        if (rc) return rc;
-        uint64_t *tmp = static_cast<uint64_t *>(ctx->stream_tmp.p);
-        while (n_add - a > kMaxIdx || n_minus - m > kMaxIdx) {
-            const int na = std::min(kMaxIdx, n_add - a), nm = std::min(kMaxIdx, n_minus - m);
-            HIP_TRY(ctx, launch_prf(ctx->env, iter, add_idx + a, na, minus_idx + m, nm, n, n_jobs, first, count, src, ctx->limbs, tmp));
-            a += na; m += nm; src = tmp;
-        }
-    }
-    LaunchEnv env = ctx->env;
-    env.codec = &cq;
-    HIP_TRY(ctx, launch_prf(env, iter, add_idx + a, n_add - a, minus_idx + m, n_minus - m, n, n_jobs, first, count, src, ctx->limbs,
-                            const_cast<uint64_t *>(src)));
-    return FLASHE_OK;
+    return prf_lists_unquantize(ctx, cq, iter, add_idx, n_add, minus_idx, n_minus, n, n_jobs, first, count, in_dev);
 }
 
 // unflatten_weights + QuantizingClient.unquantize (jzf_aggregator.py:652-671, jzf_quantize.py:493-540) of a flattened vector that is
@@ -1261,14 +1264,7 @@ static int stage_batch_layers(flashe_ctx *ctx, const flashe_batch_layer *layers,
         v += y.size;
     }
     *n_elems = e; *n_values = v;
-    if (tab.empty()) { *tab_dev = nullptr; *n_tab = 0; return FLASHE_OK; }
-    int rc = ensure(ctx, ctx->codec_tab, tab.size() * sizeof(BatchLayer));
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->codec_tab.p, tab.data(), tab.size() * sizeof(BatchLayer), hipMemcpyHostToDevice, ctx->env.stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->env.stream));
-    *tab_dev = static_cast<const BatchLayer *>(ctx->codec_tab.p);
-    *n_tab = static_cast<int>(tab.size());
-    return FLASHE_OK;
+    return stage_table(ctx, tab, tab_dev, n_tab);
 }
 
 int flashe_quantize_batch_model_dev(flashe_ctx *ctx, const flashe_batch_layer *layers, int n_layers, int element_bits, int field_bits,
@@ -1370,7 +1366,7 @@ int flashe_encrypt_range_dev(flashe_ctx *ctx, uint32_t iter, uint32_t idx, int s
                              uint64_t first, uint64_t count, const uint64_t *pt_dev, int pt_limbs, uint64_t *ct_dev)
 {
     CHECK_CTX(ctx);
-    if (scheme != FLASHE_SCHEME_SINGLE && scheme != FLASHE_SCHEME_DOUBLE) return fail(ctx, FLASHE_EINVAL, "unknown scheme %d", scheme);
+    if (int rc = check_scheme(ctx, scheme)) return rc;
     if (count && (!pt_dev || !ct_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
     int rc = check_prf_args(ctx, 1, scheme, n_jobs, ct_dev, pt_dev, pt_limbs);
     if (rc || (rc = check_range(ctx, n, first, count))) return rc;
@@ -1388,7 +1384,7 @@ int flashe_encrypt_batch_range_dev(flashe_ctx *ctx, uint32_t iter, int scheme, u
                                    uint64_t *sum_out_dev)
 {
     CHECK_CTX(ctx);
-    if (scheme != FLASHE_SCHEME_SINGLE && scheme != FLASHE_SCHEME_DOUBLE) return fail(ctx, FLASHE_EINVAL, "unknown scheme %d", scheme);
+    if (int rc = check_scheme(ctx, scheme)) return rc;
     if (n_vec < 0 || (n_vec && (!idx || !pt_dev || !ct_dev))) return fail(ctx, FLASHE_EINVAL, "bad batch arguments");
     int rc = check_range(ctx, n, first, count);
     if (rc || (rc = check_double_idx(ctx, scheme, idx, n_vec))) return rc;
@@ -1401,8 +1397,7 @@ int flashe_encrypt_batch_range_dev(flashe_ctx *ctx, uint32_t iter, int scheme, u
         rc = check_prf_args(ctx, 1, scheme, n_jobs, ct_dev[v], pt_dev[v], pt_limbs);
         if (rc) return rc;
     }
-    if (sum_out_dev && ((ctx->limbs == 2 && !aligned16(sum_out_dev)) || (reinterpret_cast<uintptr_t>(sum_out_dev) & 7u)))
-        return fail(ctx, FLASHE_EINVAL, "sum_out_dev must be aligned like a ciphertext vector");
+    if (sum_out_dev && (rc = check_sum_aligned(ctx, sum_out_dev))) return rc;
     if (count == 0) return FLASHE_OK;
     if (n_vec == 0) { if (sum_out_dev) HIP_TRY(ctx, hipMemsetAsync(sum_out_dev, 0, vec_bytes(ctx, count), ctx->env.stream)); return FLASHE_OK; }
     if (sum_out_dev && scheme == FLASHE_SCHEME_DOUBLE) {
@@ -1410,13 +1405,11 @@ int flashe_encrypt_batch_range_dev(flashe_ctx *ctx, uint32_t iter, int scheme, u
         if (e == hipSuccess) return FLASHE_OK;
         if (e != hipErrorNotSupported) HIP_TRY(ctx, e);
     }
-    const int cap = (ctx->limbs == 2 || ctx->env.use_chain) ? kMaxUniformBatch : kMaxBatch;
-    const int per_launch = (n_vec + (n_vec + cap - 1) / cap - 1) / ((n_vec + cap - 1) / cap);
-    for (int v0 = 0; v0 < n_vec; v0 += per_launch) {
-        const int nv = std::min(per_launch, n_vec - v0);
-        HIP_TRY(ctx, launch_prf_batch_range(ctx->env, iter, scheme == FLASHE_SCHEME_DOUBLE, nv, idx + v0, pt_dev + v0, pt_limbs, ct_dev + v0, n, n_jobs,
-                                            first, count));
-    }
+    rc = batch_shares(ctx, n_vec, [&](int v0, int nv) {
+        return launch_prf_batch_range(ctx->env, iter, scheme == FLASHE_SCHEME_DOUBLE, nv, idx + v0, pt_dev + v0, pt_limbs, ct_dev + v0, n, n_jobs,
+                                      first, count);
+    });
+    if (rc) return rc;
     if (sum_out_dev) return flashe_aggregate_elem_dev(ctx, n_vec, ct_dev, count, sum_out_dev);
     return FLASHE_OK;
 }
@@ -1473,7 +1466,7 @@ static int prepare_masks(flashe_ctx *ctx, flashe_ctx::Prepared &pr, uint32_t ite
 int flashe_prepare_encrypt(flashe_ctx *ctx, uint32_t iter_next, uint32_t idx, int scheme, uint64_t num_params, uint32_t n_jobs)
 {
     CHECK_CTX(ctx);
-    if (scheme != FLASHE_SCHEME_SINGLE && scheme != FLASHE_SCHEME_DOUBLE) return fail(ctx, FLASHE_EINVAL, "unknown scheme %d", scheme);
+    if (int rc = check_scheme(ctx, scheme)) return rc;
     // (iter_next is the caller's iter + 1 already: the reference's own range check of that sum, jzf_flashe.py:606, is the caller's)
     int rc = check_double_idx(ctx, scheme, &idx, 1);
     if (rc) return rc;
@@ -1584,8 +1577,7 @@ int flashe_combine_batch_sum_dev(flashe_ctx *ctx, uint64_t n, int n_vec, const u
     if (n_vec < 0 || (n_vec && (!in_dev || !out_dev))) return fail(ctx, FLASHE_EINVAL, "bad batch arguments");
     if (n && !sum_out_dev) return fail(ctx, FLASHE_EINVAL, "flashe_combine_batch_sum_dev: null sum_out_dev");
     if (in_limbs != 1 && in_limbs != ctx->limbs) return fail(ctx, FLASHE_EINVAL, "in_limbs must be 1 or %d", ctx->limbs);
-    if ((ctx->limbs == 2 && !aligned16(sum_out_dev)) || (reinterpret_cast<uintptr_t>(sum_out_dev) & 7u))
-        return fail(ctx, FLASHE_EINVAL, "sum_out_dev must be aligned like a ciphertext vector");
+    if (int rc = check_sum_aligned(ctx, sum_out_dev)) return rc;
     for (int v = 0; v < n_vec; v++) {
         if (n && (!in_dev[v] || !out_dev[v])) return fail(ctx, FLASHE_EINVAL, "null vector %d", v);
         if (n && out_dev[v] == sum_out_dev) return fail(ctx, FLASHE_EINVAL, "sum_out_dev must not be one of the output vectors");
@@ -1612,9 +1604,8 @@ int flashe_combine_batch_sum_decrypt_dev(flashe_ctx *ctx, uint64_t n, int n_vec,
     if (n_vec < 0 || (n_vec && (!in_dev || !out_dev))) return fail(ctx, FLASHE_EINVAL, "bad batch arguments");
     if (n && !sum_out_dev) return fail(ctx, FLASHE_EINVAL, "flashe_combine_batch_sum_decrypt_dev: null sum_out_dev");
     if (in_limbs != 1 && in_limbs != ctx->limbs) return fail(ctx, FLASHE_EINVAL, "in_limbs must be 1 or %d", ctx->limbs);
-    const uintptr_t need = ctx->limbs == 2 ? 15u : 7u;
     for (const void *q : {static_cast<const void *>(sum_out_dev), static_cast<const void *>(dec_add_dev), static_cast<const void *>(dec_minus_dev), static_cast<const void *>(dec_out_dev)})
-        if (reinterpret_cast<uintptr_t>(q) & need) return fail(ctx, FLASHE_EINVAL, "sum / decrypt vectors must be aligned like a ciphertext vector");
+        if (!ct_aligned(ctx, q)) return fail(ctx, FLASHE_EINVAL, "sum / decrypt vectors must be aligned like a ciphertext vector");
     if (n && (dec_out_dev == sum_out_dev || dec_add_dev == sum_out_dev || dec_minus_dev == sum_out_dev))
         return fail(ctx, FLASHE_EINVAL, "dec_out_dev and the decrypt masks must not be sum_out_dev");
     for (int v = 0; v < n_vec; v++) {
@@ -1639,9 +1630,7 @@ int flashe_aggregate_elem_dev(flashe_ctx *ctx, int C, const uint64_t *const *cts
     // two-limb vectors: 16-byte aligned; one-limb vectors: 8 bytes suffice (a sub-range may start at an odd element: slower 8-byte form)
     const uintptr_t need = ctx->limbs == 2 ? 15u : 7u;
     if (reinterpret_cast<uintptr_t>(out_dev) & need) return fail(ctx, FLASHE_EINVAL, "device vectors must be %d-byte aligned", static_cast<int>(need + 1));
-    for (int c = 0; c < C; c++)
-        if (!cts_dev[c] || (reinterpret_cast<uintptr_t>(cts_dev[c]) & need))
-            return fail(ctx, FLASHE_EINVAL, "operand %d is null or not %d-byte aligned", c, static_cast<int>(need + 1));
+    if (int rc = check_operands(ctx, C, cts_dev, static_cast<int>(need + 1))) return rc;
     if (n == 0) return FLASHE_OK;
     // at most kMaxOps operands per pass; later passes fold the running sum (out) back in
     std::vector<const uint64_t *> ops;
@@ -1730,8 +1719,7 @@ int flashe_aggregate_packed_dev(flashe_ctx *ctx, int C, const uint64_t *const *p
     if (C < 1 || !packed_dev || (n_limbs && !out_dev)) return fail(ctx, FLASHE_EINVAL, "aggregate_packed: bad arguments (C = %d)", C);
     if (n_limbs != (total_bits + 63) / 64) return fail(ctx, FLASHE_EINVAL, "n_limbs must equal ceil(total_bits / 64)");
     if (!aligned16(out_dev)) return fail(ctx, FLASHE_EINVAL, "device vectors must be 16-byte aligned");
-    for (int c = 0; c < C; c++)
-        if (!packed_dev[c] || !aligned16(packed_dev[c])) return fail(ctx, FLASHE_EINVAL, "operand %d is null or not 16-byte aligned", c);
+    if (int rc = check_operands(ctx, C, packed_dev, 16)) return rc;
     for (int c = 0; c < C; c++)
         if (packed_dev[c] == out_dev) return fail(ctx, FLASHE_EINVAL, "aggregate_packed: out must not alias operand %d", c);
     if (n_limbs == 0) return FLASHE_OK;
@@ -1779,11 +1767,7 @@ int flashe_packed_add_carry_dev(flashe_ctx *ctx, uint64_t n_limbs, uint64_t tota
 int flashe_packed_resolve_carry_dev(flashe_ctx *ctx, uint64_t n_limbs, uint64_t total_bits, const uint64_t *infos_dev, int n_below,
                                     uint64_t *x_dev)
 {
-    CHECK_CTX(ctx);
-    if (n_limbs != (total_bits + 63) / 64) return fail(ctx, FLASHE_EINVAL, "n_limbs must equal ceil(total_bits / 64)");
-    if ((n_limbs && !x_dev) || n_below < 0 || (n_below && !infos_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    HIP_TRY(ctx, launch_packed_resolve_carry(ctx->env, n_limbs, total_bits, infos_dev, n_below, x_dev));
-    return FLASHE_OK;
+    return flashe_packed_resolve_carry_strided_dev(ctx, n_limbs, total_bits, infos_dev, n_below, 3, x_dev);   // (adjacent triples)
 }
 
 int flashe_packed_resolve_carry_strided_dev(flashe_ctx *ctx, uint64_t n_limbs, uint64_t total_bits, const uint64_t *infos_dev, int n_below,
@@ -1802,7 +1786,7 @@ int flashe_pack_dev(flashe_ctx *ctx, uint64_t n, const uint64_t *in_dev, uint64_
 {
     CHECK_CTX(ctx);
     if (n && (!in_dev || !out_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if (ctx->limbs == 2 && !aligned16(in_dev)) return fail(ctx, FLASHE_EINVAL, "device vectors must be 16-byte aligned");
+    if (int rc = check_wide_aligned(ctx, {in_dev})) return rc;
     if (ctx->int_bits == 128 && !aligned16(out_dev)) return fail(ctx, FLASHE_EINVAL, "int_bits = 128: the packed buffer must be 16-byte aligned");
     HIP_TRY(ctx, launch_pack(ctx->env, n, in_dev, out_dev));
     return FLASHE_OK;
@@ -1811,7 +1795,7 @@ int flashe_unpack_dev(flashe_ctx *ctx, uint64_t n, const uint64_t *in_dev, uint6
 {
     CHECK_CTX(ctx);
     if (n && (!in_dev || !out_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if (ctx->limbs == 2 && !aligned16(out_dev)) return fail(ctx, FLASHE_EINVAL, "device vectors must be 16-byte aligned");
+    if (int rc = check_wide_aligned(ctx, {out_dev})) return rc;
     if (ctx->int_bits == 128 && !aligned16(in_dev)) return fail(ctx, FLASHE_EINVAL, "int_bits = 128: the packed buffer must be 16-byte aligned");
     HIP_TRY(ctx, launch_unpack(ctx->env, n, in_dev, out_dev));
     return FLASHE_OK;
@@ -1823,7 +1807,7 @@ int flashe_expand_to_dense_dev(flashe_ctx *ctx, uint64_t total, uint64_t k, cons
 {
     CHECK_CTX(ctx);
     if (!zero || (total && !out_dev) || (k && (!loc_dev || !vals_dev))) return fail(ctx, FLASHE_EINVAL, "null argument");
-    if (ctx->limbs == 2 && (!aligned16(out_dev) || !aligned16(vals_dev))) return fail(ctx, FLASHE_EINVAL, "device vectors must be 16-byte aligned");
+    if (int rc = check_wide_aligned(ctx, {out_dev, vals_dev})) return rc;
     HIP_TRY(ctx, launch_fill(ctx->env, total, zero[0], ctx->limbs == 2 ? zero[1] : 0, out_dev));
     HIP_TRY(ctx, launch_scatter(ctx->env, total, k, loc_dev, vals_dev, out_dev, false));
     return FLASHE_OK;
@@ -1957,7 +1941,7 @@ static int sparse_aggregate_impl(flashe_ctx *ctx, uint64_t total, int C, const u
     CHECK_CTX(ctx);
     { const int brc = C > 0 && loc_dev && k ? check_bounds(ctx, bounds, total, C, loc_dev, k) : FLASHE_OK; if (brc) return brc; }
     if (C < 0 || (C && (!loc_dev || !k || !vals_dev || !zeros)) || (total && !out_dev)) return fail(ctx, FLASHE_EINVAL, "bad arguments");
-    if (ctx->limbs == 2 && !aligned16(out_dev)) return fail(ctx, FLASHE_EINVAL, "device vectors must be 16-byte aligned");
+    if (int rc = check_wide_aligned(ctx, {out_dev})) return rc;
     const int L = ctx->limbs;
     using u128 = unsigned __int128;
     const u128 mask = ctx->int_bits == 128 ? ~static_cast<u128>(0) : ((static_cast<u128>(1) << ctx->int_bits) - 1);
@@ -2003,7 +1987,7 @@ static int sparse_encrypt_aggregate_impl(flashe_ctx *ctx, uint32_t iter, uint32_
     if (C < 1 || !idx || !loc_dev || !k || !pt_dev || !zeros || !ct_dev || (total && !agg_out_dev) || n_jobs == 0)
         return fail(ctx, FLASHE_EINVAL, "flashe_sparse_encrypt_aggregate_dev: bad arguments");
     { const int brc = check_bounds(ctx, bounds, total, C, loc_dev, k); if (brc) return brc; }
-    if (ctx->limbs == 2 && !aligned16(agg_out_dev)) return fail(ctx, FLASHE_EINVAL, "device vectors must be 16-byte aligned");
+    if (int rc = check_wide_aligned(ctx, {agg_out_dev})) return rc;
     const int L = ctx->limbs;
     using u128 = unsigned __int128;
     const u128 mask = ctx->int_bits == 128 ? ~static_cast<u128>(0) : ((static_cast<u128>(1) << ctx->int_bits) - 1);
@@ -2085,7 +2069,7 @@ static int sparse_minus_mask_impl(flashe_ctx *ctx, uint32_t iter, int C, const u
     if (whole) count = total;
     if (C < 0 || (C && (!loc_dev || !k)) || (total && !out_dev) || n_jobs == 0) return fail(ctx, FLASHE_EINVAL, "bad arguments");
     { const int brc = C > 0 ? check_bounds(ctx, bounds, total, C, loc_dev, k) : FLASHE_OK; if (brc) return brc; }
-    if (ctx->limbs == 2 && (!aligned16(out_dev) || !aligned16(agg_dev))) return fail(ctx, FLASHE_EINVAL, "device vectors must be 16-byte aligned");
+    if (int rc = check_wide_aligned(ctx, {out_dev, agg_dev})) return rc;
     uint64_t kmax = 0;
     for (int c = 0; c < C; c++) {
         if (k[c] > total) return fail(ctx, FLASHE_EINVAL, "client %d: more locations (%llu) than positions (%llu)", c,
@@ -2212,7 +2196,7 @@ int flashe_sparse_double_masks_dev(flashe_ctx *ctx, uint32_t iter, int C, const 
     CHECK_CTX(ctx);
     if (C < 0 || (C && (!loc_dev || !k)) || (total && (!add_out_dev || !minus_out_dev)) || add_out_dev == minus_out_dev)
         return fail(ctx, FLASHE_EINVAL, "flashe_sparse_double_masks_dev: bad arguments");
-    if (ctx->limbs == 2 && (!aligned16(add_out_dev) || !aligned16(minus_out_dev))) return fail(ctx, FLASHE_EINVAL, "device vectors must be 16-byte aligned");
+    if (int rc = check_wide_aligned(ctx, {add_out_dev, minus_out_dev})) return rc;
     if (total >= (1ull << 32)) return fail(ctx, FLASHE_EINVAL, "total must be below 2^32 (32-bit locations)");
     uint64_t kmax = 0;
     for (int c = 0; c < C; c++) {
@@ -2297,7 +2281,7 @@ int flashe_sparse_dense_mask_dev(flashe_ctx *ctx, uint32_t iter, int n_lists, co
 {
     CHECK_CTX(ctx);
     if (n_lists < 0 || (n_lists && !sel_dev) || (total && !out_dev)) return fail(ctx, FLASHE_EINVAL, "bad arguments");
-    if (ctx->limbs == 2 && !aligned16(out_dev)) return fail(ctx, FLASHE_EINVAL, "device vectors must be 16-byte aligned");
+    if (int rc = check_wide_aligned(ctx, {out_dev})) return rc;
     if (total) HIP_TRY(ctx, hipMemsetAsync(out_dev, 0, vec_bytes(ctx, total), ctx->env.stream));
     int rc = ensure(ctx, ctx->stream_tmp, vec_bytes(ctx, total));
     if (rc) return rc;
@@ -2344,20 +2328,13 @@ int flashe_unquantize_dev(flashe_ctx *ctx, uint64_t n, const uint64_t *v_dev, in
     return FLASHE_OK;
 }
 
-static int check_field_bits(flashe_ctx *ctx, int field_bits)
-{
-    if (field_bits < 1 || field_bits > 64 || field_bits > ctx->int_bits)
-        return fail(ctx, FLASHE_EINVAL, "field_bits must be in [1, min(64, int_bits)], got %d", field_bits);
-    return FLASHE_OK;
-}
-
 int flashe_batch_dev(flashe_ctx *ctx, uint64_t n, const uint64_t *vals_dev, int field_bits, uint64_t *out_dev)
 {
     CHECK_CTX(ctx);
     if (n && (!vals_dev || !out_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
     int rc = check_field_bits(ctx, field_bits);
     if (rc) return rc;
-    if (ctx->limbs == 2 && !aligned16(out_dev)) return fail(ctx, FLASHE_EINVAL, "device vectors must be 16-byte aligned");
+    if (int rc = check_wide_aligned(ctx, {out_dev})) return rc;
     HIP_TRY(ctx, launch_batch(ctx->env, n, vals_dev, field_bits, out_dev));
     return FLASHE_OK;
 }
@@ -2368,7 +2345,7 @@ int flashe_unbatch_dev(flashe_ctx *ctx, uint64_t n_batches, const uint64_t *in_d
     if (n_batches && (!in_dev || !out_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
     int rc = check_field_bits(ctx, field_bits);
     if (rc) return rc;
-    if (ctx->limbs == 2 && !aligned16(in_dev)) return fail(ctx, FLASHE_EINVAL, "device vectors must be 16-byte aligned");
+    if (int rc = check_wide_aligned(ctx, {in_dev})) return rc;
     HIP_TRY(ctx, launch_unbatch(ctx->env, n_batches, in_dev, field_bits, out_dev));
     return FLASHE_OK;
 }
@@ -2414,481 +2391,6 @@ int flashe_sparsify_batch_dev(flashe_ctx *ctx, int n_layers, const uint64_t *n, 
     HIP_TRY(ctx, hipMemcpyAsync(ctx->sp_ws.p, desc.data(), desc.size(), hipMemcpyHostToDevice, ctx->env.stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->env.stream));                  // the table is on the device before `desc` goes away
     HIP_TRY(ctx, launch_sparsify_batch(ctx->env, n_layers, blocks, x_dev, x_is_f64 != 0, residual_dev, loc_dev, vals_dev, ctx->sp_ws.p));
-    return FLASHE_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// Host-pointer twins: H2D, the _dev call, D2H, synchronous.
-// ------------------------------------------------------------------------------------------
-#define H2D(dst, src, bytes) HIP_TRY(ctx, hipMemcpyAsync((dst), (src), (bytes), hipMemcpyHostToDevice, ctx->env.stream))
-#define D2H(dst, src, bytes)                                                                         \
-    do {                                                                                             \
-        HIP_TRY(ctx, hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, ctx->env.stream)); \
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->env.stream));                                         \
-    } while (0)
-
-// Pipelined form of the big twins (encrypt / decrypt / aggregate_elem): the vector is cut into chunks; chunk q's upload and kernel run
-// on the ctx stream while chunk q - 1's result travels back on a second stream, so a call costs max(upload, download) instead of
-// their sum.  It needs a PAGE-LOCKED destination: a download into pageable memory blocks the host until it is done (measured: an H2D
-// and a D2H issued on two streams take 5.96 ms with pageable buffers, 3.46 ms pinned, tests/perf/pcie_probe.py), while an upload from
-// pageable memory -- blocking as well -- runs at the pinned rate and overlaps with a download that is already in flight.  So the
-// path is taken when the caller's output pointer is pinned (flashe_host_alloc / hipHostMalloc / hipHostRegister; the Python layer's
-// result pool hands out such arrays) and the vector is large enough for chunks to matter.
-namespace {
-
-constexpr size_t kPipeMinBytes = 16u << 20;
-
-bool host_pinned(const void *p)
-{
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }      // plain malloc memory: an error, not a type
-    return a.type == hipMemoryTypeHost;
-}
-
-// elements per chunk: FLASHE_TWIN_CHUNK_MB of output (default 32 MB), a multiple of 4096 elements (block- and tile-aligned for every b)
-uint64_t pipe_chunk_elems(const flashe_ctx *ctx)
-{
-    const char *e = getenv("FLASHE_TWIN_CHUNK_MB");          // read per call: a tuning knob, and tests shrink it
-    const long v = e ? atol(e) : 32;
-    const size_t mb = static_cast<size_t>(v < 1 ? 1 : v);
-    const uint64_t per = (mb << 20) / (static_cast<size_t>(ctx->limbs) * 8);
-    return std::max<uint64_t>(4096, per & ~static_cast<uint64_t>(4095));
-}
-
-bool pipe_wanted(const flashe_ctx *ctx, uint64_t n, const void *out_host)
-{
-    const char *e = getenv("FLASHE_TWIN_PIPELINE");
-    const bool off = e && atoi(e) == 0;
-    return !off && !ctx->capturing && ctx->env.stream2 && vec_bytes(ctx, n) >= kPipeMinBytes && n > pipe_chunk_elems(ctx) && host_pinned(out_host);
-}
-
-// chunk results: device -> pinned host on the second stream, behind everything the ctx stream has been given so far
-hipError_t pipe_copy_out(flashe_ctx *ctx, void *dst_host, const void *src_dev, size_t bytes, int q)
-{
-    hipEvent_t &ev = ctx->ev_copy[q & 1];
-    hipError_t e;
-    if (!ev && (e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e;
-    if ((e = hipEventRecord(ev, ctx->env.stream)) != hipSuccess) return e;
-    if ((e = hipStreamWaitEvent(ctx->env.stream2, ev, 0)) != hipSuccess) return e;
-    return hipMemcpyAsync(dst_host, src_dev, bytes, hipMemcpyDeviceToHost, ctx->env.stream2);
-}
-
-// both streams idle: the staging blocks may be handed back (also on the error paths: a copy must not outlive its block's lease)
-hipError_t pipe_drain(flashe_ctx *ctx)
-{
-    const hipError_t a = hipStreamSynchronize(ctx->env.stream), b = hipStreamSynchronize(ctx->env.stream2);
-    return a != hipSuccess ? a : b;
-}
-
-}  // namespace
-
-#define PIPE_TRY(expr)                                                       \
-    do {                                                                     \
-        hipError_t pe_ = (expr);                                             \
-        if (pe_ != hipSuccess) { (void)pipe_drain(ctx); HIP_TRY(ctx, pe_); } \
-    } while (0)
-
-int flashe_mask(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_idx, uint64_t n, uint32_t n_jobs, uint64_t *out)
-{
-    CHECK_CTX(ctx);
-    if (n == 0) return FLASHE_OK;
-    if (!out) return fail(ctx, FLASHE_EINVAL, "null output");
-    Tmp d;
-    HIP_TRY(ctx, d.alloc(ctx, vec_bytes(ctx, n)));
-    int rc = flashe_mask_dev(ctx, iter, idx, n_idx, n, n_jobs, d.as<uint64_t>());
-    if (rc) return rc;
-    D2H(out, d.p, vec_bytes(ctx, n));
-    return FLASHE_OK;
-}
-
-int flashe_encrypt(flashe_ctx *ctx, uint32_t iter, uint32_t idx, int scheme, uint64_t n, uint32_t n_jobs, const uint64_t *pt,
-                   int pt_limbs, uint64_t *ct)
-{
-    CHECK_CTX(ctx);
-    if (int rc = check_double_idx(ctx, scheme, &idx, 1)) return rc;
-    if (n == 0) return FLASHE_OK;
-    if (!pt || !ct) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if (pt_limbs != 1 && pt_limbs != ctx->limbs) return fail(ctx, FLASHE_EINVAL, "pt_limbs must be 1 or %d", ctx->limbs);
-    Tmp dp, dc;
-    HIP_TRY(ctx, dp.alloc(ctx, static_cast<size_t>(n) * pt_limbs * 8));
-    HIP_TRY(ctx, dc.alloc(ctx, vec_bytes(ctx, n)));
-    if (pipe_wanted(ctx, n, ct)) {
-        const uint64_t ch = pipe_chunk_elems(ctx);
-        int q = 0;
-        for (uint64_t f = 0; f < n; f += ch, q++) {
-            const uint64_t cnt = std::min(ch, n - f);
-            PIPE_TRY(hipMemcpyAsync(dp.as<uint64_t>() + f * pt_limbs, pt + f * pt_limbs, static_cast<size_t>(cnt) * pt_limbs * 8, hipMemcpyHostToDevice,
-                                    ctx->env.stream));
-            const int rc = flashe_encrypt_range_dev(ctx, iter, idx, scheme, n, n_jobs, f, cnt, dp.as<uint64_t>() + f * pt_limbs, pt_limbs,
-                                                    dc.as<uint64_t>() + f * ctx->limbs);
-            if (rc) { (void)pipe_drain(ctx); return rc; }
-            PIPE_TRY(pipe_copy_out(ctx, ct + f * ctx->limbs, dc.as<uint64_t>() + f * ctx->limbs, vec_bytes(ctx, cnt), q));
-        }
-        HIP_TRY(ctx, pipe_drain(ctx));
-        return FLASHE_OK;
-    }
-    H2D(dp.p, pt, static_cast<size_t>(n) * pt_limbs * 8);
-    int rc = flashe_encrypt_dev(ctx, iter, idx, scheme, n, n_jobs, dp.as<uint64_t>(), pt_limbs, dc.as<uint64_t>());
-    if (rc) return rc;
-    D2H(ct, dc.p, vec_bytes(ctx, n));
-    return FLASHE_OK;
-}
-
-// host-pointer twins of the prepared calls (synchronous: H2D + one HBM-bound kernel + D2H; the masks never leave the device)
-int flashe_encrypt_prepared(flashe_ctx *ctx, uint64_t n, const uint64_t *pt, int pt_limbs, uint64_t *ct)
-{
-    CHECK_CTX(ctx);
-    if (n && (!pt || !ct)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if (pt_limbs != 1 && pt_limbs != ctx->limbs) return fail(ctx, FLASHE_EINVAL, "pt_limbs must be 1 or %d", ctx->limbs);
-    if (n == 0) return flashe_encrypt_prepared_dev(ctx, 0, nullptr, pt_limbs, nullptr);
-    Tmp dp, dc;
-    HIP_TRY(ctx, dp.alloc(ctx, static_cast<size_t>(n) * pt_limbs * 8));
-    HIP_TRY(ctx, dc.alloc(ctx, vec_bytes(ctx, n)));
-    H2D(dp.p, pt, static_cast<size_t>(n) * pt_limbs * 8);
-    int rc = flashe_encrypt_prepared_dev(ctx, n, dp.as<uint64_t>(), pt_limbs, dc.as<uint64_t>());
-    if (rc) return rc;
-    D2H(ct, dc.p, vec_bytes(ctx, n));
-    return FLASHE_OK;
-}
-
-int flashe_decrypt_prepared(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx, int n_minus,
-                            uint64_t n, uint32_t n_jobs, const uint64_t *in, uint64_t *out)
-{
-    CHECK_CTX(ctx);
-    if (n && (!in || !out)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if (n == 0) return flashe_decrypt_prepared_dev(ctx, iter, add_idx, n_add, minus_idx, n_minus, 0, n_jobs, nullptr, nullptr);
-    Tmp di, dout;
-    HIP_TRY(ctx, di.alloc(ctx, vec_bytes(ctx, n)));
-    HIP_TRY(ctx, dout.alloc(ctx, vec_bytes(ctx, n)));
-    H2D(di.p, in, vec_bytes(ctx, n));
-    int rc = flashe_decrypt_prepared_dev(ctx, iter, add_idx, n_add, minus_idx, n_minus, n, n_jobs, di.as<uint64_t>(), dout.as<uint64_t>());
-    if (rc) return rc;
-    D2H(out, dout.p, vec_bytes(ctx, n));
-    return FLASHE_OK;
-}
-
-int flashe_decrypt(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx, int n_minus,
-                   uint64_t n, uint32_t n_jobs, const uint64_t *in, uint64_t *out)
-{
-    CHECK_CTX(ctx);
-    if (n == 0) return FLASHE_OK;
-    if (!in || !out) return fail(ctx, FLASHE_EINVAL, "null vector");
-    Tmp di, dout;
-    HIP_TRY(ctx, di.alloc(ctx, vec_bytes(ctx, n)));
-    HIP_TRY(ctx, dout.alloc(ctx, vec_bytes(ctx, n)));
-    if (pipe_wanted(ctx, n, out)) {
-        const uint64_t ch = pipe_chunk_elems(ctx);
-        int q = 0;
-        for (uint64_t f = 0; f < n; f += ch, q++) {
-            const uint64_t cnt = std::min(ch, n - f), off = f * ctx->limbs;
-            PIPE_TRY(hipMemcpyAsync(di.as<uint64_t>() + off, in + off, vec_bytes(ctx, cnt), hipMemcpyHostToDevice, ctx->env.stream));
-            const int rc = flashe_decrypt_range_dev(ctx, iter, add_idx, n_add, minus_idx, n_minus, n, n_jobs, f, cnt, di.as<uint64_t>() + off,
-                                                    dout.as<uint64_t>() + off);
-            if (rc) { (void)pipe_drain(ctx); return rc; }
-            PIPE_TRY(pipe_copy_out(ctx, out + off, dout.as<uint64_t>() + off, vec_bytes(ctx, cnt), q));
-        }
-        HIP_TRY(ctx, pipe_drain(ctx));
-        return FLASHE_OK;
-    }
-    H2D(di.p, in, vec_bytes(ctx, n));
-    int rc = flashe_decrypt_dev(ctx, iter, add_idx, n_add, minus_idx, n_minus, n, n_jobs, di.as<uint64_t>(), dout.as<uint64_t>());
-    if (rc) return rc;
-    D2H(out, dout.p, vec_bytes(ctx, n));
-    return FLASHE_OK;
-}
-
-int flashe_combine(flashe_ctx *ctx, uint64_t n, const uint64_t *in, int in_limbs, const uint64_t *add, const uint64_t *minus, uint64_t *out)
-{
-    CHECK_CTX(ctx);
-    if (n == 0) return FLASHE_OK;
-    if (!in || !out) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if (in_limbs != 1 && in_limbs != ctx->limbs) return fail(ctx, FLASHE_EINVAL, "in_limbs must be 1 or %d", ctx->limbs);
-    Tmp di, da, dm, dout;
-    HIP_TRY(ctx, di.alloc(ctx, static_cast<size_t>(n) * in_limbs * 8));
-    HIP_TRY(ctx, dout.alloc(ctx, vec_bytes(ctx, n)));
-    H2D(di.p, in, static_cast<size_t>(n) * in_limbs * 8);
-    if (add) { HIP_TRY(ctx, da.alloc(ctx, vec_bytes(ctx, n))); H2D(da.p, add, vec_bytes(ctx, n)); }
-    if (minus) { HIP_TRY(ctx, dm.alloc(ctx, vec_bytes(ctx, n))); H2D(dm.p, minus, vec_bytes(ctx, n)); }
-    int rc = flashe_combine_dev(ctx, n, di.as<uint64_t>(), in_limbs, add ? da.as<uint64_t>() : nullptr,
-                                minus ? dm.as<uint64_t>() : nullptr, dout.as<uint64_t>());
-    if (rc) return rc;
-    D2H(out, dout.p, vec_bytes(ctx, n));
-    return FLASHE_OK;
-}
-
-int flashe_aggregate_elem(flashe_ctx *ctx, int C, const uint64_t *const *cts, uint64_t n, uint64_t *out)
-{
-    CHECK_CTX(ctx);
-    if (C < 1 || !cts) return fail(ctx, FLASHE_EINVAL, "aggregate_elem: bad arguments (C = %d)", C);
-    if (n == 0) return FLASHE_OK;
-    if (!out) return fail(ctx, FLASHE_EINVAL, "null output");
-    const size_t vb = (vec_bytes(ctx, n) + 15) & ~static_cast<size_t>(15);
-    Tmp all, dout;
-    HIP_TRY(ctx, all.alloc(ctx, vb * C));
-    HIP_TRY(ctx, dout.alloc(ctx, vb));
-    std::vector<const uint64_t *> ptrs(C);
-    for (int c = 0; c < C; c++) {
-        if (!cts[c]) return fail(ctx, FLASHE_EINVAL, "operand %d is null", c);
-        ptrs[c] = reinterpret_cast<const uint64_t *>(all.as<char>() + vb * c);
-    }
-    if (pipe_wanted(ctx, n, out)) {
-        // upload bound (C vectors up, one down): the chunks hide the reduce kernels and the download under the uploads
-        const uint64_t ch = pipe_chunk_elems(ctx);
-        std::vector<const uint64_t *> part(C);
-        int q = 0;
-        for (uint64_t f = 0; f < n; f += ch, q++) {
-            const uint64_t cnt = std::min(ch, n - f), off = f * ctx->limbs;
-            for (int c = 0; c < C; c++) {
-                part[c] = ptrs[c] + off;
-                PIPE_TRY(hipMemcpyAsync(const_cast<uint64_t *>(part[c]), cts[c] + off, vec_bytes(ctx, cnt), hipMemcpyHostToDevice, ctx->env.stream));
-            }
-            const int rc = flashe_aggregate_elem_dev(ctx, C, part.data(), cnt, dout.as<uint64_t>() + off);
-            if (rc) { (void)pipe_drain(ctx); return rc; }
-            PIPE_TRY(pipe_copy_out(ctx, out + off, dout.as<uint64_t>() + off, vec_bytes(ctx, cnt), q));
-        }
-        HIP_TRY(ctx, pipe_drain(ctx));
-        return FLASHE_OK;
-    }
-    for (int c = 0; c < C; c++) H2D(const_cast<uint64_t *>(ptrs[c]), cts[c], vec_bytes(ctx, n));
-    int rc = flashe_aggregate_elem_dev(ctx, C, ptrs.data(), n, dout.as<uint64_t>());
-    if (rc) return rc;
-    D2H(out, dout.p, vec_bytes(ctx, n));
-    return FLASHE_OK;
-}
-
-int flashe_aggregate_packed(flashe_ctx *ctx, int C, const uint64_t *const *packed, uint64_t n_limbs, uint64_t total_bits, uint64_t *out)
-{
-    CHECK_CTX(ctx);
-    if (C < 1 || !packed) return fail(ctx, FLASHE_EINVAL, "aggregate_packed: bad arguments (C = %d)", C);
-    if (n_limbs != (total_bits + 63) / 64) return fail(ctx, FLASHE_EINVAL, "n_limbs must equal ceil(total_bits / 64)");
-    if (n_limbs == 0) return FLASHE_OK;
-    if (!out) return fail(ctx, FLASHE_EINVAL, "null output");
-    const size_t vb = (static_cast<size_t>(n_limbs) * 8 + 15) & ~static_cast<size_t>(15);
-    Tmp all, dout;
-    HIP_TRY(ctx, all.alloc(ctx, vb * C));
-    HIP_TRY(ctx, dout.alloc(ctx, vb));
-    std::vector<const uint64_t *> ptrs(C);
-    for (int c = 0; c < C; c++) {
-        if (!packed[c]) return fail(ctx, FLASHE_EINVAL, "operand %d is null", c);
-        ptrs[c] = reinterpret_cast<const uint64_t *>(all.as<char>() + vb * c);
-        H2D(const_cast<uint64_t *>(ptrs[c]), packed[c], static_cast<size_t>(n_limbs) * 8);
-    }
-    int rc = flashe_aggregate_packed_dev(ctx, C, ptrs.data(), n_limbs, total_bits, dout.as<uint64_t>());
-    if (rc) return rc;
-    D2H(out, dout.p, static_cast<size_t>(n_limbs) * 8);
-    return FLASHE_OK;
-}
-
-int flashe_pack(flashe_ctx *ctx, uint64_t n, const uint64_t *in, uint64_t *out)
-{
-    CHECK_CTX(ctx);
-    if (n == 0) return FLASHE_OK;
-    if (!in || !out) return fail(ctx, FLASHE_EINVAL, "null vector");
-    const size_t ob = static_cast<size_t>((n * ctx->int_bits + 63) / 64) * 8;
-    Tmp di, dout;
-    HIP_TRY(ctx, di.alloc(ctx, vec_bytes(ctx, n)));
-    HIP_TRY(ctx, dout.alloc(ctx, ob));
-    H2D(di.p, in, vec_bytes(ctx, n));
-    int rc = flashe_pack_dev(ctx, n, di.as<uint64_t>(), dout.as<uint64_t>());
-    if (rc) return rc;
-    D2H(out, dout.p, ob);
-    return FLASHE_OK;
-}
-
-int flashe_unpack(flashe_ctx *ctx, uint64_t n, const uint64_t *in, uint64_t *out)
-{
-    CHECK_CTX(ctx);
-    if (n == 0) return FLASHE_OK;
-    if (!in || !out) return fail(ctx, FLASHE_EINVAL, "null vector");
-    const size_t ib = static_cast<size_t>((n * ctx->int_bits + 63) / 64) * 8;
-    Tmp di, dout;
-    HIP_TRY(ctx, di.alloc(ctx, ib));
-    HIP_TRY(ctx, dout.alloc(ctx, vec_bytes(ctx, n)));
-    H2D(di.p, in, ib);
-    int rc = flashe_unpack_dev(ctx, n, di.as<uint64_t>(), dout.as<uint64_t>());
-    if (rc) return rc;
-    D2H(out, dout.p, vec_bytes(ctx, n));
-    return FLASHE_OK;
-}
-
-int flashe_expand_to_dense(flashe_ctx *ctx, uint64_t total, uint64_t k, const uint32_t *loc, const uint64_t *vals,
-                           const uint64_t *zero, uint64_t *out)
-{
-    CHECK_CTX(ctx);
-    if (total == 0) return FLASHE_OK;
-    if (!out || !zero || (k && (!loc || !vals))) return fail(ctx, FLASHE_EINVAL, "null argument");
-    for (uint64_t q = 0; q < k; q++)
-        if (loc[q] >= total) return fail(ctx, FLASHE_EINVAL, "location %llu out of range", static_cast<unsigned long long>(loc[q]));
-    Tmp dl, dv, dout;
-    HIP_TRY(ctx, dl.alloc(ctx, static_cast<size_t>(k) * 4));
-    HIP_TRY(ctx, dv.alloc(ctx, vec_bytes(ctx, k)));
-    HIP_TRY(ctx, dout.alloc(ctx, vec_bytes(ctx, total)));
-    if (k) { H2D(dl.p, loc, static_cast<size_t>(k) * 4); H2D(dv.p, vals, vec_bytes(ctx, k)); }
-    int rc = flashe_expand_to_dense_dev(ctx, total, k, dl.as<uint32_t>(), dv.as<uint64_t>(), zero, dout.as<uint64_t>());
-    if (rc) return rc;
-    D2H(out, dout.p, vec_bytes(ctx, total));
-    return FLASHE_OK;
-}
-
-int flashe_sparse_minus_mask(flashe_ctx *ctx, uint32_t iter, int C, const uint32_t *const *loc, const uint64_t *k, uint64_t total,
-                             uint32_t n_jobs, uint64_t *out)
-{
-    CHECK_CTX(ctx);
-    if (total == 0) return FLASHE_OK;
-    if (C < 0 || (C && (!loc || !k)) || !out) return fail(ctx, FLASHE_EINVAL, "bad arguments");
-    std::vector<Tmp> dl(C);
-    std::vector<const uint32_t *> ptrs(C);
-    bool sorted = true;            // the reference's lists are (jzf_aggregator.py:598); then the one-pass span reduce applies
-    for (int c = 0; c < C; c++) {
-        for (uint64_t q = 0; q < k[c]; q++) {
-            if (loc[c][q] >= total) return fail(ctx, FLASHE_EINVAL, "client %d location out of range", c);
-            if (q && loc[c][q] <= loc[c][q - 1]) sorted = false;
-        }
-        HIP_TRY(ctx, dl[c].alloc(ctx, static_cast<size_t>(k[c]) * 4));
-        if (k[c]) H2D(dl[c].p, loc[c], static_cast<size_t>(k[c]) * 4);
-        ptrs[c] = dl[c].as<uint32_t>();
-    }
-    Tmp dout;
-    HIP_TRY(ctx, dout.alloc(ctx, vec_bytes(ctx, total)));
-    int rc = sparse_minus_mask_impl(ctx, iter, C, ptrs.data(), k, total, n_jobs, sorted, nullptr, dout.as<uint64_t>());
-    if (rc) return rc;
-    D2H(out, dout.p, vec_bytes(ctx, total));
-    return FLASHE_OK;
-}
-
-int flashe_sparse_dense_mask(flashe_ctx *ctx, uint32_t iter, int n_lists, const uint8_t *const *sel, uint64_t total, uint64_t *out)
-{
-    CHECK_CTX(ctx);
-    if (total == 0) return FLASHE_OK;
-    if (n_lists < 0 || (n_lists && !sel) || !out) return fail(ctx, FLASHE_EINVAL, "bad arguments");
-    std::vector<Tmp> ds(n_lists);
-    std::vector<const uint8_t *> ptrs(n_lists);
-    for (int i = 0; i < n_lists; i++) {
-        HIP_TRY(ctx, ds[i].alloc(ctx, static_cast<size_t>(total)));
-        H2D(ds[i].p, sel[i], static_cast<size_t>(total));
-        ptrs[i] = ds[i].as<uint8_t>();
-    }
-    Tmp dout;
-    HIP_TRY(ctx, dout.alloc(ctx, vec_bytes(ctx, total)));
-    int rc = flashe_sparse_dense_mask_dev(ctx, iter, n_lists, ptrs.data(), total, dout.as<uint64_t>());
-    if (rc) return rc;
-    D2H(out, dout.p, vec_bytes(ctx, total));
-    return FLASHE_OK;
-}
-
-int flashe_quantize(flashe_ctx *ctx, uint64_t n, const void *x, int x_is_f64, double alpha, int element_bits, const double *u,
-                    uint64_t *q)
-{
-    CHECK_CTX(ctx);
-    if (n == 0) return FLASHE_OK;
-    if (!x || !u || !q) return fail(ctx, FLASHE_EINVAL, "null vector");
-    const size_t xb = static_cast<size_t>(n) * (x_is_f64 ? 8 : 4);
-    Tmp dx, du, dq;
-    HIP_TRY(ctx, dx.alloc(ctx, xb));
-    HIP_TRY(ctx, du.alloc(ctx, static_cast<size_t>(n) * 8));
-    HIP_TRY(ctx, dq.alloc(ctx, static_cast<size_t>(n) * 8));
-    H2D(dx.p, x, xb);
-    H2D(du.p, u, static_cast<size_t>(n) * 8);
-    int rc = flashe_quantize_dev(ctx, n, dx.p, x_is_f64, alpha, element_bits, du.as<double>(), dq.as<uint64_t>());
-    if (rc) return rc;
-    D2H(q, dq.p, static_cast<size_t>(n) * 8);
-    return FLASHE_OK;
-}
-
-int flashe_unquantize(flashe_ctx *ctx, uint64_t n, const uint64_t *v, int v_limbs, double alpha, int element_bits, int num_clients,
-                      double *out)
-{
-    CHECK_CTX(ctx);
-    if (n == 0) return FLASHE_OK;
-    if (!v || !out) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if (v_limbs != 1 && v_limbs != 2) return fail(ctx, FLASHE_EINVAL, "v_limbs must be 1 or 2");
-    Tmp dv, dout;
-    HIP_TRY(ctx, dv.alloc(ctx, static_cast<size_t>(n) * v_limbs * 8));
-    HIP_TRY(ctx, dout.alloc(ctx, static_cast<size_t>(n) * 8));
-    H2D(dv.p, v, static_cast<size_t>(n) * v_limbs * 8);
-    int rc = flashe_unquantize_dev(ctx, n, dv.as<uint64_t>(), v_limbs, alpha, element_bits, num_clients, dout.as<double>());
-    if (rc) return rc;
-    D2H(out, dout.p, static_cast<size_t>(n) * 8);
-    return FLASHE_OK;
-}
-
-int flashe_batch(flashe_ctx *ctx, uint64_t n, const uint64_t *vals, int field_bits, uint64_t *out)
-{
-    CHECK_CTX(ctx);
-    if (n == 0) return FLASHE_OK;
-    if (!vals || !out) return fail(ctx, FLASHE_EINVAL, "null vector");
-    int rc = check_field_bits(ctx, field_bits);
-    if (rc) return rc;
-    const uint64_t bs = ctx->int_bits / field_bits, nb = (n + bs - 1) / bs;
-    Tmp dv, dout;
-    HIP_TRY(ctx, dv.alloc(ctx, static_cast<size_t>(n) * 8));
-    HIP_TRY(ctx, dout.alloc(ctx, vec_bytes(ctx, nb)));
-    H2D(dv.p, vals, static_cast<size_t>(n) * 8);
-    rc = flashe_batch_dev(ctx, n, dv.as<uint64_t>(), field_bits, dout.as<uint64_t>());
-    if (rc) return rc;
-    D2H(out, dout.p, vec_bytes(ctx, nb));
-    return FLASHE_OK;
-}
-
-int flashe_unbatch(flashe_ctx *ctx, uint64_t n_batches, const uint64_t *in, int field_bits, uint64_t *out)
-{
-    CHECK_CTX(ctx);
-    if (n_batches == 0) return FLASHE_OK;
-    if (!in || !out) return fail(ctx, FLASHE_EINVAL, "null vector");
-    int rc = check_field_bits(ctx, field_bits);
-    if (rc) return rc;
-    const uint64_t bs = ctx->int_bits / field_bits;
-    Tmp di, dout;
-    HIP_TRY(ctx, di.alloc(ctx, vec_bytes(ctx, n_batches)));
-    HIP_TRY(ctx, dout.alloc(ctx, static_cast<size_t>(n_batches * bs) * 8));
-    H2D(di.p, in, vec_bytes(ctx, n_batches));
-    rc = flashe_unbatch_dev(ctx, n_batches, di.as<uint64_t>(), field_bits, dout.as<uint64_t>());
-    if (rc) return rc;
-    D2H(out, dout.p, static_cast<size_t>(n_batches * bs) * 8);
-    return FLASHE_OK;
-}
-
-int flashe_sparsify(flashe_ctx *ctx, uint64_t n, uint64_t k, const void *x, int x_is_f64, void *residual, uint32_t *loc, void *vals)
-{
-    CHECK_CTX(ctx);
-    if (n == 0 || k == 0) return FLASHE_OK;
-    if (!x || !loc || !vals) return fail(ctx, FLASHE_EINVAL, "null vector");
-    const size_t es = x_is_f64 ? 8 : 4;
-    Tmp dx, dr, dl, dv;
-    HIP_TRY(ctx, dx.alloc(ctx, n * es));
-    HIP_TRY(ctx, dl.alloc(ctx, k * 4));
-    HIP_TRY(ctx, dv.alloc(ctx, k * es));
-    H2D(dx.p, x, n * es);
-    if (residual) { HIP_TRY(ctx, dr.alloc(ctx, n * es)); H2D(dr.p, residual, n * es); }
-    int rc = flashe_sparsify_dev(ctx, n, k, dx.p, x_is_f64, residual ? dr.p : nullptr, dl.as<uint32_t>(), dv.p);
-    if (rc) return rc;
-    if (residual) HIP_TRY(ctx, hipMemcpyAsync(residual, dr.p, n * es, hipMemcpyDeviceToHost, ctx->env.stream));
-    HIP_TRY(ctx, hipMemcpyAsync(loc, dl.p, k * 4, hipMemcpyDeviceToHost, ctx->env.stream));
-    D2H(vals, dv.p, k * es);
-    return FLASHE_OK;
-}
-
-int flashe_sparsify_batch(flashe_ctx *ctx, int n_layers, const uint64_t *n, const uint64_t *k, const void *x, int x_is_f64, void *residual,
-                          uint32_t *loc, void *vals)
-{
-    CHECK_CTX(ctx);
-    if (n_layers < 0 || (n_layers && (!n || !k))) return fail(ctx, FLASHE_EINVAL, "sparsify_batch: bad arguments");
-    uint64_t total = 0, total_k = 0;
-    for (int l = 0; l < n_layers; l++) { total += n[l]; total_k += k[l]; }
-    if (total == 0 || total_k == 0) return FLASHE_OK;
-    if (!x || !loc || !vals) return fail(ctx, FLASHE_EINVAL, "null vector");
-    const size_t es = x_is_f64 ? 8 : 4;
-    Tmp dx, dr, dl, dv;
-    HIP_TRY(ctx, dx.alloc(ctx, total * es));
-    HIP_TRY(ctx, dl.alloc(ctx, total_k * 4));
-    HIP_TRY(ctx, dv.alloc(ctx, total_k * es));
-    H2D(dx.p, x, total * es);
-    if (residual) { HIP_TRY(ctx, dr.alloc(ctx, total * es)); H2D(dr.p, residual, total * es); }
-    int rc = flashe_sparsify_batch_dev(ctx, n_layers, n, k, dx.p, x_is_f64, residual ? dr.p : nullptr, dl.as<uint32_t>(), dv.p);
-    if (rc) return rc;
-    if (residual) HIP_TRY(ctx, hipMemcpyAsync(residual, dr.p, total * es, hipMemcpyDeviceToHost, ctx->env.stream));
-    HIP_TRY(ctx, hipMemcpyAsync(loc, dl.p, total_k * 4, hipMemcpyDeviceToHost, ctx->env.stream));
-    D2H(vals, dv.p, total_k * es);
     return FLASHE_OK;
 }
 

@@ -1,5 +1,5 @@
-// Private to the host side of libflashe_hip.so (abi.hip, comm.hip): the context object behind the opaque flashe_ctx of
-// include/flashe.h, and the error-reporting helpers every entry point uses.
+// Private to the host side of libflashe_hip.so (abi.hip, host_twins.hip, comm.hip): the context object behind the opaque flashe_ctx
+// of include/flashe.h, and the error-reporting and argument helpers the entry points share.
 #pragma once
 #include "flashe.h"
 #include "kernels.h"
@@ -47,6 +47,33 @@ namespace flashe_host {
 
 // Records the message on ctx (or, ctx == NULL, as this thread's context-creation error) and returns `code`.
 int fail(flashe_ctx *ctx, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
+
+inline size_t vec_bytes(const flashe_ctx *ctx, uint64_t n) { return static_cast<size_t>(n) * ctx->limbs * 8; }
+
+// FLASHE_EINVAL when the double mask would need prefix idx + 1 = 2^32 for one of the n_idx entries (abi.hip)
+int check_double_idx(flashe_ctx *ctx, int scheme, const uint32_t *idx, int n_idx);
+int check_field_bits(flashe_ctx *ctx, int field_bits);
+
+// RAII temp device buffer for the host-pointer twins.  Staging blocks are kept by the ctx and reused: a hipMalloc + hipFree
+// pair of a 160 MB block costs more than moving 160 MB over PCIe Gen5 on this platform (measured 7 ms against 2.9 ms,
+// tests/perf/e2e_calls.py).  The blocks a ctx keeps are bounded by a byte budget (FLASHE_STAGING_POOL_MB, default 8 GiB of the
+// 288 GB); beyond it the largest free block makes room, and a request that still does not fit is a plain allocation.
+struct Tmp {
+    void *p = nullptr;
+    flashe_ctx *owner = nullptr;
+    int slot = -1;
+    Tmp() = default;
+    Tmp(const Tmp &) = delete;
+    Tmp &operator=(const Tmp &) = delete;
+    ~Tmp()
+    {
+        if (!p) return;
+        if (slot >= 0) owner->staging->give_back(slot);
+        else (void)hipFree(p);
+    }
+    hipError_t alloc(flashe_ctx *ctx, size_t bytes);   // (abi.hip: creates the ctx's pool on first use)
+    template <class T> T *as() { return static_cast<T *>(p); }
+};
 
 }  // namespace flashe_host
 

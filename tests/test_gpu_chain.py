@@ -191,6 +191,13 @@ def test_encrypt_batch_with_partial_aggregate(E, oracle, b, n, idx, scheme):
         eng.encrypt_batch_sum_dev(6, idx, E.SCHEME_DOUBLE, n, 16, dpt, 1, dct, dct[0])      # the sum must not alias a ciphertext
     with pytest.raises(E.FlasheError):
         eng.encrypt_batch_sum_dev(6, idx, E.SCHEME_DOUBLE, n, 16, dpt, 1, dct, dpt[-1])     # ... nor a plaintext (chunk ends add to the sum in memory)
+    for alias in (dct[-1], dpt[0]):                                                           # the element-range form refuses the same
+        with pytest.raises(E.FlasheError, match="sum_out_dev must not be one of the plaintext or ciphertext vectors"):
+            eng.encrypt_batch_range_dev(6, idx, E.SCHEME_DOUBLE, n, 16, 0, n, dpt, 1, dct, sum_out=alias)
+    if scheme == "double":                                                                    # ... and takes the same call with its own sum
+        eng._check(eng._lib.flashe_memset_dev(eng._h, dsum.ptr, 0xA5, dsum.nbytes))
+        eng.encrypt_batch_range_dev(6, idx, E.SCHEME_DOUBLE, n, 16, 0, n, dpt, 1, dct, sum_out=dsum)
+        assert np.array_equal(dsum.download(np.uint64, n * Lb).reshape(n, Lb), oracle.aggregate_elem(want, b)), (b, n, "range-form sum")
 
 
 @pytest.mark.parametrize("b,n,J,C,scheme", [(20, 6_400_007, 16, 3, "double"), (23, 5_300_003, 7, 2, "double"), (16, 8_388_608, 1, 2, "double"),

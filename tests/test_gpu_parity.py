@@ -942,7 +942,7 @@ def test_ctx_resident_precompute_vs_oracle(E, oracle, b, n, J):
 
 
 def test_staging_pool_under_a_tight_budget():
-    """The host-pointer calls keep their device staging blocks (abi.hip `Tmp`) within FLASHE_STAGING_POOL_MB: with 3 MB allowed,
+    """The host-pointer calls keep their device staging blocks (host_twins.hip, ctx.h `Tmp`) within FLASHE_STAGING_POOL_MB: with 3 MB allowed,
     a mix of sizes forces reuse, eviction of parked blocks, slots emptied in place and plain allocations for what does not
     fit -- every result still equals the oracle's, and the recycled host result arrays (engine._HostPool, 2 MB allowed) never
     alias while alive.  Own process: both budgets are read once."""
