@@ -414,6 +414,7 @@ int flashe_ctx_create(flashe_ctx **out, const uint8_t key[32], int int_bits, int
 #endif
     ctx->env.use_chain = 1;
     if (const char *ch = getenv("FLASHE_CHAIN")) ctx->env.use_chain = atoi(ch) != 0;   // 0: every job computes both of its streams (A/B runs)
+    if (const char *dm = getenv("FLASHE_CHAIN_DMASK")) ctx->chain_dmask_on = atoi(dm) != 0;   // 0: no chain decrypt mask (A/B runs, memory)
     *out = ctx;
     return FLASHE_OK;
 }
@@ -424,7 +425,7 @@ int flashe_ctx_destroy(flashe_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     if (ctx->env.stream) (void)hipStreamSynchronize(ctx->env.stream);
     for (flashe_ctx::Buf *b : {&ctx->summaries, &ctx->stream_tmp, &ctx->acc_tmp[0], &ctx->acc_tmp[1], &ctx->sp_ws, &ctx->bounds, &ctx->mt_ws, &ctx->codec_tab, &ctx->prep_enc.add,
-                               &ctx->prep_enc.minus, &ctx->prep_dec.add, &ctx->prep_dec.minus})
+                               &ctx->prep_enc.minus, &ctx->prep_dec.add, &ctx->prep_dec.minus, &ctx->chain_dmask.d})
         if (b->p) (void)hipFree(b->p);
     if (ctx->staging) { ctx->staging->destroy(); delete ctx->staging; ctx->staging = nullptr; }      // staging blocks held plaintexts and ciphertexts (wiped)
     if (ctx->te0_dev) (void)hipFree(ctx->te0_dev);
@@ -450,6 +451,7 @@ int flashe_ctx_set_key(flashe_ctx *ctx, const uint8_t key[32])
     wipe(&ctx->env.rk, sizeof(ctx->env.rk));
     expand_key(key, &ctx->env.rk);
     ctx->key_epoch++;             // graphs captured under the previous key refuse to replay
+    ctx->chain_dmask.valid = false;
     return upload_key_words(ctx);
 }
 
@@ -710,6 +712,7 @@ int flashe_graph_begin(flashe_ctx *ctx)
     if (ctx->capturing) return fail(ctx, FLASHE_EINVAL, "a capture is already in progress on this context");
     HIP_TRY(ctx, hipStreamBeginCapture(ctx->env.stream, hipStreamCaptureModeThreadLocal));
     ctx->capturing = true;
+    ctx->chain_dmask.valid = false;
     return FLASHE_OK;
 }
 
@@ -718,6 +721,7 @@ int flashe_graph_end(flashe_ctx *ctx, flashe_graph **graph)
     CHECK_CTX(ctx);
     if (!ctx->capturing) return fail(ctx, FLASHE_EINVAL, "no capture in progress");
     ctx->capturing = false;
+    ctx->chain_dmask.valid = false;
     hipGraph_t g = nullptr;
     hipError_t e = hipStreamEndCapture(ctx->env.stream, &g);
     if (e != hipSuccess || !g) {
@@ -749,6 +753,7 @@ int flashe_graph_launch_shifted(flashe_ctx *ctx, flashe_graph *graph, uint32_t i
                                         "key schedule in their argument blocks -- capture it again");
     // kernel arguments (iter included) are frozen into the graph; the shift is a device word every PRF kernel adds to its
     // iter at run time, set and reset in stream order around the replay
+    ctx->chain_dmask.valid = false;
     uint32_t *shift = ctx->te0_dev + 1024;
     if (iter_shift) HIP_TRY(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(shift), static_cast<int>(iter_shift), 1, ctx->env.stream));
     HIP_TRY(ctx, hipGraphLaunch(graph->exec, ctx->env.stream));
@@ -996,6 +1001,45 @@ int flashe_narrow_u32_dev(flashe_ctx *ctx, uint64_t n, const uint64_t *in_dev, u
     return FLASHE_OK;
 }
 
+// ---- chain decrypt mask (ctx.h: flashe_ctx::ChainDmask) ----
+// Before a summed launch over [first, first + count): the slot is invalid from here on; returns the block the launch writes the decrypt
+// mask to, or nullptr (option off, a capture in progress, or no memory for the block -- then the launch simply writes none).
+static uint64_t *chain_dmask_begin(flashe_ctx *ctx, uint64_t count)
+{
+    flashe_ctx::ChainDmask &s = ctx->chain_dmask;
+    s.valid = false;
+    if (!ctx->chain_dmask_on || ctx->capturing || ctx->limbs != 2 || count == 0) return nullptr;
+    if (ensure(ctx, s.d, vec_bytes(ctx, count)) != FLASHE_OK) {
+        (void)hipGetLastError();                 // (a failed allocation must not surface as the launch's error)
+        ctx->err.clear();
+        return nullptr;
+    }
+    return static_cast<uint64_t *>(s.d.p);
+}
+
+// After the summed launch has been enqueued with the block chain_dmask_begin returned: the slot now holds the mask of that launch.
+static void chain_dmask_commit(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_vec, uint64_t n, uint32_t n_jobs, uint64_t first,
+                               uint64_t count)
+{
+    flashe_ctx::ChainDmask &s = ctx->chain_dmask;
+    s.iter = iter; s.key_epoch = ctx->key_epoch; s.add_idx = idx[n_vec - 1] + 1u; s.minus_idx = idx[0];
+    s.n = n; s.n_jobs = n_jobs; s.first = first; s.count = count;
+    s.valid = true;
+}
+
+// The slot's mask at element `first` when it is exactly what a decrypt of [first, first + count) with these lists adds, else nullptr.
+static const uint64_t *chain_dmask_match(const flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx,
+                                         int n_minus, uint64_t n, uint32_t n_jobs, uint64_t first, uint64_t count)
+{
+    const flashe_ctx::ChainDmask &s = ctx->chain_dmask;
+    if (!s.valid || ctx->capturing || n_add != 1 || n_minus != 1 || count == 0) return nullptr;
+    if (add_idx[0] != s.add_idx || minus_idx[0] != s.minus_idx || iter != s.iter || ctx->key_epoch != s.key_epoch || n != s.n ||
+        n_jobs != s.n_jobs)
+        return nullptr;
+    if (first < s.first || first - s.first > s.count || count > s.count - (first - s.first)) return nullptr;
+    return static_cast<const uint64_t *>(s.d.p) + (first - s.first) * 2;
+}
+
 int flashe_encrypt_batch_sum_dev(flashe_ctx *ctx, uint32_t iter, int scheme, uint64_t n, uint32_t n_jobs, int n_vec, const uint32_t *idx,
                                  const uint64_t *const *pt_dev, int pt_limbs, uint64_t *const *ct_dev, uint64_t *sum_out_dev)
 {
@@ -1015,8 +1059,12 @@ int flashe_encrypt_batch_sum_dev(flashe_ctx *ctx, uint32_t iter, int scheme, uin
                 int rc = check_prf_args(ctx, 1, scheme, n_jobs, ct_dev[v], pt_dev[v], pt_limbs);
                 if (rc) return rc;
             }
-            const hipError_t e = launch_prf_batch_sum(ctx->env, iter, n_vec, idx, pt_dev, pt_limbs, ct_dev, sum_out_dev, n, n_jobs, 0, n);
-            if (e == hipSuccess) return FLASHE_OK;
+            uint64_t *const dmask = chain_dmask_begin(ctx, n);
+            const hipError_t e = launch_prf_batch_sum(ctx->env, iter, n_vec, idx, pt_dev, pt_limbs, ct_dev, sum_out_dev, n, n_jobs, 0, n, dmask);
+            if (e == hipSuccess) {
+                if (dmask) chain_dmask_commit(ctx, iter, idx, n_vec, n, n_jobs, 0, n);
+                return FLASHE_OK;
+            }
             if (e != hipErrorNotSupported) HIP_TRY(ctx, e);
         }
     }
@@ -1401,8 +1449,12 @@ int flashe_encrypt_batch_range_dev(flashe_ctx *ctx, uint32_t iter, int scheme, u
     if (count == 0) return FLASHE_OK;
     if (n_vec == 0) { if (sum_out_dev) HIP_TRY(ctx, hipMemsetAsync(sum_out_dev, 0, vec_bytes(ctx, count), ctx->env.stream)); return FLASHE_OK; }
     if (sum_out_dev && scheme == FLASHE_SCHEME_DOUBLE) {
-        const hipError_t e = launch_prf_batch_sum(ctx->env, iter, n_vec, idx, pt_dev, pt_limbs, ct_dev, sum_out_dev, n, n_jobs, first, count);
-        if (e == hipSuccess) return FLASHE_OK;
+        uint64_t *const dmask = chain_dmask_begin(ctx, count);
+        const hipError_t e = launch_prf_batch_sum(ctx->env, iter, n_vec, idx, pt_dev, pt_limbs, ct_dev, sum_out_dev, n, n_jobs, first, count, dmask);
+        if (e == hipSuccess) {
+            if (dmask) chain_dmask_commit(ctx, iter, idx, n_vec, n, n_jobs, first, count);
+            return FLASHE_OK;
+        }
         if (e != hipErrorNotSupported) HIP_TRY(ctx, e);
     }
     rc = batch_shares(ctx, n_vec, [&](int v0, int nv) {
@@ -1424,6 +1476,11 @@ int flashe_decrypt_range_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add
     if (rc || (rc = check_range(ctx, n, first, count))) return rc;
     if (n_add == 0 && n_minus == 0) {
         HIP_TRY(ctx, launch_combine(ctx->env, count, in_dev, ctx->limbs, nullptr, nullptr, out_dev));
+        return FLASHE_OK;
+    }
+    // the arbiter's decrypt of a sum this ctx's summed encrypt launch has just produced: its mask is already in HBM
+    if (const uint64_t *d = chain_dmask_match(ctx, iter, add_idx, n_add, minus_idx, n_minus, n, n_jobs, first, count)) {
+        HIP_TRY(ctx, launch_combine(ctx->env, count, in_dev, ctx->limbs, d, nullptr, out_dev));
         return FLASHE_OK;
     }
     HIP_TRY(ctx, prf_lists(ctx, iter, add_idx, n_add, minus_idx, n_minus, n, n_jobs, first, count, in_dev, ctx->limbs, out_dev));

@@ -33,6 +33,14 @@ struct flashe_ctx {
     // flashe_decrypt_prepared* call; the blocks are kept for the next round's masks
     struct Prepared { Buf add, minus; uint64_t n = 0; bool valid = false, has_minus = false; uint32_t iter = 0, add_idx = 0, minus_idx = 0; };
     Prepared prep_enc, prep_dec;
+    // chain decrypt mask: the summed double-mask encrypt launch (flashe_encrypt_batch_sum_dev, the summed flashe_encrypt_batch_range_dev)
+    // over clients a .. b also writes D = term(b + 1) - term(a) mod 2^int_bits of its elements [first, first + count), the mask the
+    // arbiter's decrypt of the sum adds; a flashe_decrypt_range_dev with exactly that key (iter, key epoch, (add, minus) = ([b + 1], [a]),
+    // n, n_jobs) on a range inside the covered one is then one combine pass.  Not consumed (D is deterministic for its key); its own
+    // slot, so that an explicit flashe_prepare_decrypt survives.  Per ctx and so per stream: a decrypt on another ctx never sees it.
+    struct ChainDmask { Buf d; uint64_t n = 0, first = 0, count = 0; uint32_t iter = 0, key_epoch = 0, add_idx = 0, minus_idx = 0, n_jobs = 0; bool valid = false; };
+    ChainDmask chain_dmask;
+    bool chain_dmask_on = true;   // FLASHE_CHAIN_DMASK=0 at ctx creation: the summed launches write no decrypt mask
     // staging blocks of the host-pointer twins: hipMalloc / hipFree cost more than the kernels on LeNet-sized vectors and more than
     // the PCIe transfer on 160 MB ones, so blocks are kept and reused within a byte budget (the twins are synchronous: a block is
     // free again when its call returns)

@@ -76,9 +76,11 @@ hipError_t launch_prf_batch(const LaunchEnv &env, uint32_t iter, bool dbl, int n
 // The same batch as ONE chain that also writes sum_v out[v] mod 2^b to sum_out_dev (the local partial aggregate).  Returns
 // hipErrorNotSupported -- nothing launched -- unless the batch is one run of consecutive cipher indices of the double mask with
 // int_bits > 64, at most kMaxUniformBatch vectors, long enough to fill the chip: the caller then encrypts and reduces separately.
+// dmask_dev (optional, pointer addresses element `first`): the same launch also writes the decrypt mask of the batch,
+// term(idx[n_vec - 1] + 1) - term(idx[0]) mod 2^b -- what a decrypt of the sum with add = [idx[n_vec - 1] + 1], minus = [idx[0]] adds.
 hipError_t launch_prf_batch_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const uint64_t *const *in_dev,
                                 int in_limbs, uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs, uint64_t first,
-                                uint64_t count);
+                                uint64_t count, uint64_t *dmask_dev = nullptr);
 // launch_prf_batch on elements [first, first + count) of the n-element vectors (pointers address element `first`): what a GPU that owns
 // an element slice of every client's vector runs
 hipError_t launch_prf_batch_range(const LaunchEnv &env, uint32_t iter, bool dbl, int n_vec, const uint32_t *idx, const uint64_t *const *in_dev,
@@ -117,6 +119,7 @@ struct PrfChain {
     int in_limbs;
     uint64_t *const *out_dev;
     uint64_t *sum_out_dev = nullptr;   // optional (int_bits > 64, n_out <= kMaxLinks): receives sum_c out[c] mod 2^b, written by the same launch
+    uint64_t *dmask_dev = nullptr;     // optional, with sum_out_dev, the launch's only chain: receives term(idx[n_out]) - term(idx[0]) mod 2^b
 };
 hipError_t launch_prf_chains(const LaunchEnv &env, uint32_t iter, int n_chains, const PrfChain *chains, uint64_t n, uint32_t n_jobs);
 

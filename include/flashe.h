@@ -239,7 +239,14 @@ int flashe_encrypt_batch_range_dev(flashe_ctx *ctx, uint32_t iter, int scheme, u
  * device: ONE launch (every ciphertext of an element passes through the lane's registers, the running sum costs one extra 16-byte
  * store per element and the C ciphertexts are never re-read).  Any other shape: the encrypts followed by flashe_aggregate_elem_dev.
  * The ciphertexts are written as by flashe_encrypt_batch_dev; sum_out_dev (n x L limbs) must not be one of them nor a plaintext
- * (FLASHE_EINVAL; the same holds for the _range and _u32 forms). */
+ * (FLASHE_EINVAL; the same holds for the _range and _u32 forms).
+ * Chain decrypt mask: when that one launch runs (and the ctx is not capturing a graph), it also writes the arbiter's decrypt mask of
+ * the clients idx[0] .. idx[n_vec - 1], D = term(idx[n_vec - 1] + 1) - term(idx[0]) mod 2^b, into a block the ctx holds (16 bytes
+ * per element of the launch: 160 MB at n = 1e7, kept and reused; the same for the summed flashe_encrypt_batch_range_dev on its
+ * slice).  A later flashe_decrypt_range_dev on this ctx with add = {idx[n_vec - 1] + 1}, minus = {idx[0]} and the same iter, key, n
+ * and n_jobs on elements inside the covered ones adds D in one memory-bound pass instead of computing the two streams again.
+ * flashe_ctx_set_key, flashe_graph_begin / _end / _launch* and the next summed launch invalidate it; a decrypt on another ctx never
+ * sees it; flashe_prepare_decrypt's cache is not touched.  FLASHE_CHAIN_DMASK=0 in the environment at flashe_ctx_create: no mask. */
 int flashe_encrypt_batch_sum_dev(flashe_ctx *ctx, uint32_t iter, int scheme, uint64_t n, uint32_t n_jobs, int n_vec,
                                  const uint32_t *idx, const uint64_t *const *pt_dev, int pt_limbs, uint64_t *const *ct_dev,
                                  uint64_t *sum_out_dev);
@@ -291,7 +298,9 @@ int flashe_decrypt(flashe_ctx *ctx, uint32_t iter,
  * covers global elements [first, first + count) of an n-element vector; the device pointers
  * address element `first` (i.e. are indexed by element - first).  n and n_jobs still describe the
  * WHOLE vector, because the PRF counters depend on chunks_idx(range(n), n_jobs)
- * (jzf_flashe.py:12-16, :34). */
+ * (jzf_flashe.py:12-16, :34).  flashe_decrypt_range_dev (and flashe_decrypt_dev) with one add and one minus index is a combine
+ * with the ctx's chain decrypt mask when that mask matches the call (see flashe_encrypt_batch_sum_dev), the PRF launch otherwise;
+ * the result is the same. */
 int flashe_mask_range_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_idx,
                           uint64_t n, uint32_t n_jobs, uint64_t first, uint64_t count, uint64_t *out_dev);
 int flashe_encrypt_range_dev(flashe_ctx *ctx, uint32_t iter, uint32_t idx, int scheme,
