@@ -434,6 +434,32 @@ __device__ __forceinline__ void st128_nt(uint64_t *p, u128 v)
     __builtin_nontemporal_store(r, reinterpret_cast<u64x2 *>(p));
 }
 
+// Buffer-resource forms: a wave-uniform descriptor (base, byte count) in SGPRs and a 32-bit per-lane byte offset.  Streams that
+// touch the same element index through different arrays share one offset VGPR; only the descriptor changes.  The hardware range
+// check drops an access at or past `bytes` -- a safety net only, callers still predicate their lanes: the compiler folds constant
+// addends of the offset into the instruction's immediate, and a lane whose offset wrapped below zero is NOT caught by it then.
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void *p, uint32_t bytes)
+{
+    const uint64_t a = reinterpret_cast<uintptr_t>(p);
+    const uint64_t u = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(a))) |
+                       (static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(a >> 32)))) << 32);
+    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(u), 0, static_cast<int>(__builtin_amdgcn_readfirstlane(bytes)), 0x00020000);
+}
+// (soffset is always the constant 0: with a register there, the compiler assumes no store-data hazard and may overwrite the data VGPRs
+// of a dwordx4 store in the very next instruction -- measured on gfx950 to corrupt the stored value)
+__device__ __forceinline__ uint64_t buf_ld64(__amdgpu_buffer_rsrc_t r, uint32_t voff)
+{
+    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, 0, 0);
+    return (static_cast<uint64_t>(v.y) << 32) | v.x;
+}
+// aux 2 = nt: the non-temporal store of st128_nt
+template <int AUX = 0> __device__ __forceinline__ void buf_st128(__amdgpu_buffer_rsrc_t r, uint32_t voff, u128 v)
+{
+    const u32x4 w = {static_cast<uint32_t>(v), static_cast<uint32_t>(v >> 32), static_cast<uint32_t>(v >> 64), static_cast<uint32_t>(v >> 96)};
+    __builtin_amdgcn_raw_buffer_store_b128(w, r, voff, 0, AUX);
+}
 
 // correctly rounded (nearest-even) u128 -> double, as Python's int -> float
 __device__ __forceinline__ double u128_to_double(u128 v)

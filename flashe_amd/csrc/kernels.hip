@@ -12,6 +12,7 @@
 //   * persistent launch: one 1024-thread workgroup per CU (128 KiB of LDS tables), tiles dealt
 //     round-robin; there is no inter-workgroup reuse, so no XCD remap is needed.
 #include "device_common.h"
+#include <type_traits>
 
 namespace flashe {
 
@@ -318,7 +319,16 @@ __device__ __forceinline__ void loads_landed(const u128 &a, const u128 &b)
                  "v"(static_cast<uint64_t>(b >> 64)));
 }
 
+__device__ __forceinline__ void loads_landed(const uint64_t &a, const uint64_t &b)
+{
+    asm volatile("" ::"v"(a), "v"(b));
+}
+
 template <class T> __device__ __forceinline__ void swap_regs(T &a, T &b) { const T t = a; a = b; b = t; }
+
+// a 96-bit running sum of 64-bit values (lo, carries): at most 2^32 terms
+__device__ __forceinline__ void add96(uint64_t &lo, uint32_t &hi, uint64_t x) { lo += x; hi += lo < x ? 1u : 0u; }
+__device__ __forceinline__ u128 join96(uint64_t lo, uint32_t hi) { return (static_cast<u128>(hi) << 64) | lo; }
 
 // a wave-uniform 64-bit value read from LDS, moved to SGPRs so that what is derived from it stays scalar
 __device__ __forceinline__ uint64_t uniform64(uint64_t v)
@@ -343,7 +353,7 @@ __global__ __launch_bounds__(THREADS) void prf_chain_kernel(const RoundKeys rk, 
                                                               uint32_t iter0, uint64_t mask_lo, uint64_t mask_hi,
                                                               const uint32_t *__restrict__ te0, const Codec cq)
 {
-    constexpr bool DMASK = false;
+    constexpr bool DMASK = false, D128 = false;
     uint64_t *const dmask = nullptr;
 #include "prf_chain_body.inc"
 }
@@ -354,7 +364,23 @@ __global__ __launch_bounds__(THREADS) void prf_chain_dmask_kernel(const RoundKey
                                                                     uint32_t iter0, uint64_t mask_lo, uint64_t mask_hi,
                                                                     const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask)
 {
-    constexpr bool SUM = true, CODEC = false, DMASK = true;
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false;
+    const Codec cq{};
+#include "prf_chain_body.inc"
+}
+
+// the same launch specialised for its headline shape (D128 in prf_chain_body.inc): int_bits = 128, one-limb inputs, every input and
+// output present, the chain's n x 16 B below 4 GiB -- its whole tiles run prf_chain_sum128_tile.inc
+#ifndef FLASHE_SUM128
+#define FLASHE_SUM128 1        // 0: every decrypt-mask chain runs prf_chain_dmask_kernel (A/B builds)
+#endif
+constexpr uint64_t kSum128MaxCount = 0x0fffff00ull;      // n x 16 B of every array below 4 GiB, with room for a tile's wrapped offsets
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void prf_dmask_sum128_kernel(const RoundKeys rk, const ChainTable tb, int n_chains, int all_half_arg,
+                                                                     uint32_t iter0, uint64_t mask_lo, uint64_t mask_hi,
+                                                                     const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask)
+{
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = true;
     const Codec cq{};
 #include "prf_chain_body.inc"
 }
@@ -2062,6 +2088,15 @@ static hipError_t launch_small_chains(const LaunchEnv &env, uint32_t iter, int n
 #ifndef FLASHE_CHAIN_QUARTER_DEFAULT
 #define FLASHE_CHAIN_QUARTER_DEFAULT 1   // quarter tiles for the shortest chained launches (0: half tiles as before round 6; A/B builds)
 #endif
+// the shape of prf_dmask_sum128_kernel: one summed double-mask chain at int_bits = 128, one-limb inputs, every input and output present
+static bool sum128_shape(const LaunchEnv &env, int nc, const ChainTable &tb, uint64_t lo, uint64_t hi)
+{
+    if (env.b != 128 || ~lo != 0 || ~hi != 0 || nc != 1 || (tb.flags[0] & 3) != 0 || !tb.sum_out[0] || tb.count[0] > kSum128MaxCount) return false;
+    for (int l = 0; l < tb.len[0]; l++)
+        if (!tb.in[tb.link0[0] + l] || !tb.out[tb.link0[0] + l]) return false;
+    return true;
+}
+
 hipError_t launch_prf_chains(const LaunchEnv &env, uint32_t iter, int n_chains, const PrfChain *chains, uint64_t n, uint32_t n_jobs)
 {
     if (env.b <= 64) return launch_small_chains(env, iter, n_chains, chains, n, n_jobs);
@@ -2190,7 +2225,10 @@ hipError_t launch_prf_chains(const LaunchEnv &env, uint32_t iter, int n_chains, 
             cq = *env.codec;
         }
         if (env.codec && summed) return hipErrorInvalidValue;
-        if (dmask)
+        if (dmask && FLASHE_SUM128 && sum128_shape(env, nc, tb, lo, hi))
+            hipLaunchKernelGGL((prf_dmask_sum128_kernel<kPrfThreads>), dim3(grid), dim3(kPrfThreads), 0, env.stream, env.rk, tb, nc,
+                               (all_half ? 1 : 0) | (quarter ? 4 : 0) | probe, iter, lo, hi, env.te0_dev, dmask);
+        else if (dmask)
             hipLaunchKernelGGL((prf_chain_dmask_kernel<kPrfThreads>), dim3(grid), dim3(kPrfThreads), 0, env.stream, env.rk, tb, nc,
                                (all_half ? 1 : 0) | (quarter ? 4 : 0) | probe, iter, lo, hi, env.te0_dev, dmask);
         else if (env.codec)

@@ -1,9 +1,11 @@
-// The body of prf_chain_kernel<THREADS, SUM, CODEC> and prf_chain_dmask_kernel<THREADS> (kernels.hip), included INSIDE each kernel: the
-// kernel defines THREADS, SUM, CODEC and DMASK as compile-time constants and has the arguments rk, tb, n_chains, all_half_arg, iter0,
-// mask_lo, mask_hi, te0, cq and dmask in scope.  (A __device__ function shared by both would do, but its blockDim is lowered before it
+// The body of prf_chain_kernel<THREADS, SUM, CODEC>, prf_chain_dmask_kernel<THREADS> and prf_dmask_sum128_kernel<THREADS> (kernels.hip),
+// included INSIDE each kernel: the kernel defines THREADS, SUM, CODEC, DMASK and D128 as compile-time constants and has the arguments
+// rk, tb, n_chains, all_half_arg, iter0, mask_lo, mask_hi, te0, cq and dmask in scope.  D128: the launch is one summed double-mask
+// chain at int_bits = 128 with one-limb inputs (launch_prf_chains), and its whole tiles run prf_chain_sum128_tile.inc.  (A __device__ function shared by both would do, but its blockDim is lowered before it
 // is inlined -- the non-uniform-workgroup form -- and the headline kernel's code would change with it; included text compiles to
 // exactly the kernel it was before.)
     static_assert(!DMASK || (SUM && !CODEC), "the decrypt mask is written by summed chains only");
+    static_assert(!D128 || DMASK, "the int_bits = 128 specialisation is the decrypt-mask chain's");
     (void)dmask;
     const uint32_t iter = iter0 + te0[kIterShiftWord];
     constexpr uint32_t WAVES = THREADS / 64;
@@ -16,7 +18,7 @@
     if (all_half & 0x100) return;                  // timing probes of the prologue (FLASHE_CHAIN_TUNE / FLASHE_CHAIN_PROBE only)
 #endif
     const LaneRegs lr = lane_regs(tab);
-    const u128 mask = (static_cast<u128>(mask_hi) << 64) | mask_lo;
+    const u128 mask = D128 ? ~static_cast<u128>(0) : (static_cast<u128>(mask_hi) << 64) | mask_lo;
     {
         // round-1 prefix words of every stream (chains never straddle a 2^32 counter window: host-checked)
         const int last = n_chains - 1;
@@ -81,8 +83,14 @@
         const uint64_t tj = (first & ~255ull) + 256u * (uniform64(d_tlo[cur]) + (L - cbeg)) + 128u * half +
                             (quarter ? 64u * static_cast<uint32_t>(q & 3u) : 0u);                             // first counter of the item
         const int link0 = tb.link0[cur], sbase = tb.sbase[cur];
-        const bool single = tb.flags[cur] & 1, in2 = tb.flags[cur] & 2;
+        const bool single = !D128 && (tb.flags[cur] & 1), in2 = !D128 && (tb.flags[cur] & 2);
         const int n_streams = tb.len[cur] + (single ? 0 : 1);
+        if constexpr (D128) {
+            if (whole) {
+#include "prf_chain_sum128_tile.inc"
+                continue;
+            }
+        }
         if (whole) {
             // ---- 256 elements: two pairs per lane, wave-uniform part of rounds 1-2 through the scalar cache ----
             const uint32_t x3 = static_cast<uint32_t>(tj) ^ rk.w[3];
