@@ -1902,10 +1902,11 @@ static int ensure_reduce_table(flashe_ctx *ctx, const flashe_span_bounds *b)
     return FLASHE_OK;
 }
 
-// int_bits > 64 on the table PRF: the sparse single-mask passes run as launch_span_prf
-static bool span_prf_ok(const flashe_ctx *ctx)
+// the table PRF: the sparse single-mask passes run as launch_span_prf (one kernel per width: span_prf_kernel at int_bits > 64,
+// span_prf_small_kernel at int_bits <= 64); the bit-sliced backends keep the separate encrypts / streams
+static bool span_prf_table(const flashe_ctx *ctx)
 {
-    return ctx->limbs == 2 && (ctx->env.prf_backend == PRF_AUTO || ctx->env.prf_backend == PRF_TABLE);
+    return ctx->env.prf_backend == PRF_AUTO || ctx->env.prf_backend == PRF_TABLE;
 }
 
 int flashe_span_bounds_create(flashe_ctx *ctx, uint64_t total, int C, const uint32_t *const *loc_dev, const uint64_t *k, flashe_span_bounds **out)
@@ -1924,7 +1925,7 @@ int flashe_span_bounds_create(flashe_ctx *ctx, uint64_t total, int C, const uint
     b->loc.assign(loc_dev, loc_dev + C); b->k.assign(k, k + C);
     const int group = std::min(C, kMaxScatter), groups = (C + kMaxScatter - 1) / kMaxScatter;
     b->group_stride = (span_count(total, kSpanReduce) + 1) * static_cast<size_t>(group);
-    b->group_stride_fused = span_prf_ok(ctx) ? (span_count(total, kSpanFused) + 1) * static_cast<size_t>(group) : 0;
+    b->group_stride_fused = span_prf_table(ctx) ? (span_count(total, kSpanFused) + 1) * static_cast<size_t>(group) : 0;
     const hipError_t e = hipMalloc(&b->start, std::max<size_t>((b->group_stride + b->group_stride_fused) * groups * sizeof(uint32_t), 16));
     if (e != hipSuccess) { delete b; return fail(ctx, e == hipErrorOutOfMemory ? FLASHE_ENOMEM : FLASHE_EIO, "hipMalloc: %s", hipGetErrorString(e)); }
     if (b->group_stride_fused) b->start_fused = b->start + b->group_stride * groups;
@@ -2058,10 +2059,12 @@ static int sparse_encrypt_aggregate_impl(flashe_ctx *ctx, uint32_t iter, uint32_
         if (z & ~mask) return fail(ctx, FLASHE_EINVAL, "zero value of client %d exceeds int_bits", c);
         zsum = (zsum + z) & mask;
     }
-    if (!whole && (!span_prf_ok(ctx) || !bounds || !bounds->start_fused))
-        return fail(ctx, FLASHE_EINVAL, "the position-range form needs int_bits > 64 on the table PRF and a bounds handle");
-    if (!span_prf_ok(ctx) || (bounds && !bounds->start_fused)) {
-        // int_bits <= 64 / another PRF backend: the encrypts, then the sparse reduce of what they wrote
+    if (!whole && (!span_prf_table(ctx) || !bounds || !bounds->start_fused))
+        return fail(ctx, FLASHE_EINVAL, "the position-range form needs the table PRF and a bounds handle");
+    // whole vectors at int_bits <= 64 keep the two calls too: the fused pass measured slower than them at the sparse jobs' 10 % density
+    // (profiles/r09_ab_sparse_small.log); the position ranges run it
+    if (!span_prf_table(ctx) || (bounds && !bounds->start_fused) || (whole && L == 1)) {
+        // another PRF backend / int_bits <= 64: the encrypts, then the sparse reduce of what they wrote
         for (int c = 0; c < C; c++) {
             if (!k[c]) continue;
             const int rc = flashe_encrypt_dev(ctx, iter, idx[c], FLASHE_SCHEME_SINGLE, k[c], n_jobs, pt_dev[c], pt_limbs, ct_dev[c]);
@@ -2075,7 +2078,7 @@ static int sparse_encrypt_aggregate_impl(flashe_ctx *ctx, uint32_t iter, uint32_
         const int nc = std::min(kMaxScatter, C - c0);
         uint32_t *start = bounds ? bounds->start_fused + (c0 / kMaxScatter) * bounds->group_stride_fused : static_cast<uint32_t *>(ctx->bounds.p);
         if (!bounds) HIP_TRY(ctx, launch_span_bounds(ctx->env, nc, loc_dev + c0, k + c0, total, nullptr, start));
-        HIP_TRY(ctx, launch_span_prf(ctx->env, iter, nc, idx + c0, loc_dev + c0, k + c0, pt_dev + c0, pt_limbs, ct_dev + c0, zeros + 2 * static_cast<size_t>(c0),
+        HIP_TRY(ctx, launch_span_prf(ctx->env, iter, n_jobs, nc, idx + c0, loc_dev + c0, k + c0, pt_dev + c0, pt_limbs, ct_dev + c0, zeros + static_cast<size_t>(L) * c0,
                                      c0 ? 0 : static_cast<uint64_t>(zsum), c0 ? 0 : static_cast<uint64_t>(zsum >> 64), total, start,
                                      c0 != 0 ? agg_out_dev : nullptr, false, agg_out_dev, first, count));
     }
@@ -2133,14 +2136,17 @@ static int sparse_minus_mask_impl(flashe_ctx *ctx, uint32_t iter, int C, const u
                                       static_cast<unsigned long long>(k[c]), static_cast<unsigned long long>(total));
         kmax = std::max(kmax, k[c]);
     }
-    const bool jobs_path = span_prf_ok(ctx);
+    const bool span_prf = sorted && span_prf_table(ctx) && C > 0;           // the passes with the PRF inside (launch_span_prf), any width
+    const bool jobs_path = ctx->limbs == 2 && span_prf_table(ctx);          // int_bits > 64: m = 1 compact streams from one job-list launch
     const bool fused = sorted && jobs_path && C > 0;      // the span reduce writes (or subtracts from agg) the whole vector itself
-    if (!whole && !(fused && bounds)) return fail(ctx, FLASHE_EINVAL, "the position-range form needs int_bits > 64 on the table PRF, sorted lists and a bounds handle");
+    if (!whole && !(span_prf && bounds)) return fail(ctx, FLASHE_EINVAL, "the position-range form needs the table PRF, sorted lists and a bounds handle");
 #ifdef FLASHE_TUNING
-    const char *two_pass = getenv("FLASHE_SPAN_PRF");     // "0" = compact streams through HBM, then the plain span reduce (the round-2 .. 4 form; A/B runs)
-    const bool prf_inside = fused && !(two_pass && two_pass[0] == '0' && !bounds);
+    // "0" = the two-call form: int_bits > 64 compact streams through HBM, then the plain span reduce (the round-2 .. 4 form);
+    // int_bits <= 64 one stream + scatter per client, then a combine (A/B runs)
+    const char *two_pass = getenv("FLASHE_SPAN_PRF");
+    const bool prf_inside = span_prf && !(two_pass && two_pass[0] == '0' && !bounds);
 #else
-    const bool prf_inside = fused;
+    const bool prf_inside = span_prf;
 #endif
     if (prf_inside) {
         // strictly increasing lists: ONE persistent launch per group of clients generates the mask blocks inside the span reduce
@@ -2154,7 +2160,7 @@ static int sparse_minus_mask_impl(flashe_ctx *ctx, uint32_t iter, int C, const u
             for (int e = 0; e < nc; e++) idx[e] = static_cast<uint32_t>(c0 + e);
             uint32_t *start = bounds ? bounds->start_fused + (c0 / kMaxScatter) * bounds->group_stride_fused : static_cast<uint32_t *>(ctx->bounds.p);
             if (!bounds) HIP_TRY(ctx, launch_span_bounds(ctx->env, nc, loc_dev + c0, k + c0, total, nullptr, start));
-            HIP_TRY(ctx, launch_span_prf(ctx->env, iter, nc, idx, loc_dev + c0, k + c0, nullptr, 2, nullptr, nullptr, 0, 0, total, start,
+            HIP_TRY(ctx, launch_span_prf(ctx->env, iter, n_jobs, nc, idx, loc_dev + c0, k + c0, nullptr, ctx->limbs, nullptr, nullptr, 0, 0, total, start,
                                          c0 != 0 ? out_dev : agg_dev, agg_dev != nullptr, out_dev, first, count));
         }
         return FLASHE_OK;
@@ -2228,8 +2234,8 @@ int flashe_sparse_decrypt_bounds_dev(flashe_ctx *ctx, uint32_t iter, int C, cons
     CHECK_CTX(ctx);
     if (!bounds) return fail(ctx, FLASHE_EINVAL, "null bounds handle");
     if (total && (!agg_dev || agg_dev == out_dev)) return fail(ctx, FLASHE_EINVAL, "the aggregate must be given and must not be the output vector");
-    if (!span_prf_ok(ctx) || std::min(C, kMaxScatter) != std::min(bounds->C, kMaxScatter))
-        return fail(ctx, FLASHE_EINVAL, "sparse_decrypt_bounds needs int_bits > 64 on the table PRF (the span reduce is what consumes the bounds)");
+    if (!span_prf_table(ctx) || std::min(C, kMaxScatter) != std::min(bounds->C, kMaxScatter))
+        return fail(ctx, FLASHE_EINVAL, "sparse_decrypt_bounds needs the table PRF (the span reduce with the PRF inside is what consumes the bounds)");
     return sparse_minus_mask_impl(ctx, iter, C, loc_dev, k, total, n_jobs, true, agg_dev, out_dev, bounds);
 }
 

@@ -1450,19 +1450,227 @@ hipError_t span_prf_cycles(unsigned long long *out8, bool reset)
 }
 #endif
 
+// ---- the same passes at int_bits <= 64 (one limb, table PRF) -----------------------------------------------------------------------
+// At b <= 64 an AES block carries m = 128 / b terms and the counters depend on the chunking (jzf_flashe.py:19-45, :316-343): client c's
+// k = k[c] compact entries are cut into n_jobs chunks (d, r = divmod(k, n_jobs): the first r chunks hold d + 1 entries), and entry q
+// of the chunk [begin, end) is slot (q - begin) % m -- bits [b slot, b slot + b) -- of AES(key, iter | idx[c] | begin + (q - begin) / m).
+// Number a client's blocks 0, 1, ... in list order, chunk after chunk: entry q lies in block g(q), g never decreases, so the entries
+// [f0, f1) the client has in a span share the blocks g(f0) .. g(f1 - 1).  Those blocks are the span's work items -- per span
+// sum_c (g(f1 - 1) - g(f0) + 1) blocks, i.e. entries / m + one per client and per chunk edge in the span (a block cut by a span edge is
+// computed by both spans) -- and the lane that computes a block adds the terms of its up-to-m entries into ONE u64 accumulator plane
+// (mod 2^64: exact, 2^b divides 2^64; the write-out masks to b bits).  The phases meet at barriers: the AES work of these widths is
+// small (config 5's shape at b = 20: about 2.1 M blocks), the pass is bound by the LDS atomics and the dense read / write.
+//   ENC = false: out[p] = from[p] +/- sum of the terms of the entries at p;  ENC = true: ct[c][q] = (pt[c][q] + term) mod 2^b is
+//   stored where ct[c] is not null, and out[p] = from[p] + sum (ct - sub[c]).  (from = src when SRC, the constant base otherwise)
+struct SpanSmallTable {
+    const uint32_t *loc[kMaxScatter];
+    const uint64_t *pt[kMaxScatter];
+    uint64_t *ct[kMaxScatter];
+    uint32_t k[kMaxScatter], idx[kMaxScatter];
+    uint64_t sub[kMaxScatter];
+};
+
+// block number of entry q of a list with chunk geometry g = (d, r, blocks of a (d + 1)-entry chunk, blocks of a d-entry chunk)
+__device__ __forceinline__ uint32_t small_block_of(const uint4 g, uint32_t q, uint32_t m)
+{
+    const uint32_t big = g.y * (g.x + 1);
+    if (q < big) {
+        const uint32_t j = q / (g.x + 1);
+        return j * g.z + (q - j * (g.x + 1)) / m;
+    }
+    const uint32_t q2 = q - big, j = q2 / g.x;
+    return g.y * g.z + j * g.w + (q2 - j * g.x) / m;
+}
+
+constexpr int kSmallBatch = 8;       // entries of a block whose position / plaintext loads are in flight at once (the first batch under the rounds)
+
+template <bool ENC, bool SRC>
+__global__ __launch_bounds__(kPrfThreads) void span_prf_small_kernel(const RoundKeys rk, const SpanSmallTable tb, int C, uint32_t iter0, uint32_t n_jobs,
+                                                                     uint32_t b, uint64_t total, uint32_t n_spans, uint32_t sp_first, uint32_t sp_end,
+                                                                     const uint32_t *__restrict__ start, uint64_t base, uint64_t mask, const uint64_t *src,
+                                                                     bool negate, uint64_t *out, const uint32_t *__restrict__ te0, uint32_t *err_flag)
+{
+    constexpr int SPAN = kSpanFused, THREADS = kPrfThreads, PER = (SPAN + THREADS - 1) / THREADS;
+    const uint32_t iter = iter0 + te0[kIterShiftWord];
+    const uint32_t m = 128u / b;
+    __shared__ uint32_t tab[kTabWords];
+    __shared__ unsigned long long acc[SPAN];
+    __shared__ uint4 s_pref[kMaxScatter];                     // CtrPrefix of (iter, idx[c], counter high word 0)
+    __shared__ uint4 s_geo[kMaxScatter];                      // chunk geometry of client c's list (small_block_of)
+    __shared__ const uint32_t *s_loc[kMaxScatter];
+    __shared__ const uint64_t *s_pt[ENC ? kMaxScatter : 1];
+    __shared__ uint64_t *s_ct[ENC ? kMaxScatter : 1];
+    __shared__ uint64_t s_sub[ENC ? kMaxScatter : 1];
+    // the span in flight: client c's entries [s_f0[c], s_f1[c]) lie in it and touch its blocks s_g0[c] ..; work items s_w[c] .. s_w[c + 1]
+    // are client c's (s_w[C] = the span's blocks; the entries past C are sentinels, so the owner search needs no bounds)
+    __shared__ uint32_t s_w[kMaxScatter + 1], s_f0[kMaxScatter], s_f1[kMaxScatter], s_g0[kMaxScatter];
+    fill_tables(tab, te0);
+    const LaneRegs lr = lane_regs(tab);
+    const int tid = threadIdx.x;
+    for (int i = tid; i < SPAN; i += THREADS) acc[i] = 0;
+    if (tid < C) {
+        const CtrPrefix p = ctr_prefix(rk, lr, iter, tb.idx[tid], 0u);
+        s_pref[tid] = make_uint4(p.u[0], p.u[1], p.u[2], p.u[3]);
+        const uint32_t kc = tb.k[tid], d = kc / n_jobs, r = kc % n_jobs;
+        s_geo[tid] = make_uint4(d, r, static_cast<uint32_t>((static_cast<uint64_t>(d) + m) / m), static_cast<uint32_t>((static_cast<uint64_t>(d) + m - 1) / m));
+        s_loc[tid] = tb.loc[tid];
+        if (ENC) { s_pt[tid] = tb.pt[tid]; s_ct[tid] = tb.ct[tid]; s_sub[tid] = tb.sub[tid]; }
+    }
+    __syncthreads();
+    // wave 0: the work items of span sp (the slice [f0, f1) of client `tid`'s list, clamped like span_reduce_kernel's)
+    auto span_table = [&](uint64_t sp) {
+        const uint32_t ln_c = static_cast<uint32_t>(min(tid, C - 1));
+        uint32_t f0, f1;
+        if (FLASHE_BOUNDS_TR) { const uint64_t at = static_cast<uint64_t>(ln_c) * (static_cast<uint64_t>(n_spans) + 1) + sp; f0 = start[at]; f1 = start[at + 1]; }
+        else { f0 = start[sp * C + ln_c]; f1 = start[(sp + 1) * C + ln_c]; }
+        const uint32_t kc = tb.k[ln_c];
+        f0 = min(f0, kc); f1 = min(f1, kc);
+        uint32_t nw = 0, g0 = 0;
+        if (tid < C && f1 > f0) {
+            const uint4 geo = s_geo[tid];
+            g0 = small_block_of(geo, f0, m);
+            nw = small_block_of(geo, f1 - 1, m) - g0 + 1;
+        }
+        const uint32_t run = wave_scan_u32(nw);
+        if (tid == 0) s_w[0] = 0;
+        if (tid < C) { s_f0[tid] = f0; s_f1[tid] = f1; s_g0[tid] = g0; }
+        s_w[tid + 1] = tid < C ? run : 0xffffffffu;
+    };
+    uint64_t sp = static_cast<uint64_t>(sp_first) + blockIdx.x;
+    const uint32_t stride = gridDim.x;
+    if (tid < 64 && sp < sp_end) span_table(sp);
+    __syncthreads();
+    for (; sp < sp_end; sp += stride) {
+        const uint64_t p0 = sp * SPAN;
+        const uint32_t span_len = static_cast<uint32_t>(total - p0 < SPAN ? total - p0 : SPAN);
+        // the dense values this lane writes out at the end of the span, requested ahead of the span's rounds
+        uint64_t from[PER];
+#pragma unroll
+        for (int e = 0; e < PER; e++) {
+            const uint32_t r = tid + e * THREADS;
+            from[e] = SRC && r < span_len ? __builtin_nontemporal_load(src + p0 + r) : base;
+        }
+        const uint32_t n_work = s_w[C];
+        for (uint32_t w = tid; w < n_work; w += THREADS) {
+            int c = 0;
+#pragma unroll
+            for (int step = 32; step; step >>= 1)
+                if (s_w[c + step] <= w) c += step;
+            const uint4 geo = s_geo[c];
+            const uint32_t G = s_g0[c] + (w - s_w[c]);
+            uint32_t begin, len, i;
+            if (G < geo.y * geo.z) {
+                const uint32_t j = G / geo.z;
+                i = G - j * geo.z; begin = j * (geo.x + 1); len = geo.x + 1;
+            } else {
+                const uint32_t G2 = G - geo.y * geo.z, j = G2 / geo.w;
+                i = G2 - j * geo.w; begin = geo.y * (geo.x + 1) + j * geo.x; len = geo.x;
+            }
+            const uint32_t e_first = begin + i * m;                                   // the block's slot 0
+            const uint32_t e_end = begin + static_cast<uint32_t>(min(static_cast<uint64_t>(len), static_cast<uint64_t>(i + 1) * m));
+            const uint32_t q0 = max(e_first, s_f0[c]), q1 = min(e_end, s_f1[c]);
+            const uint32_t *loc = s_loc[c];
+            const uint64_t *pt = ENC ? s_pt[c] : nullptr;
+            uint32_t pos[kSmallBatch];
+            uint64_t pv[kSmallBatch];
+            auto fetch = [&](uint32_t qa) {
+#pragma unroll
+                for (int u = 0; u < kSmallBatch; u++) {
+                    const bool on = qa + u < q1;
+                    pos[u] = on ? ld32_g(loc + qa + u) : 0u;
+                    pv[u] = ENC && on ? ld64_nt_g(pt + qa + u) : 0ull;
+                }
+            };
+            fetch(q0);                                                             // in flight under the rounds
+            const uint4 pr = s_pref[c];
+            const CtrPrefix pre{{pr.x, pr.y, pr.z, pr.w}};
+            uint32_t s[4];
+            ctr_round1(pre, ctr_var(rk, lr, begin + i), s);
+            aes256_rounds1_deep<2>(rk, lr, s);
+            const u128 S = words_to_u128(s);
+            for (uint32_t qa = q0; qa < q1; qa += kSmallBatch) {
+                if (qa != q0) fetch(qa);
+#pragma unroll
+                for (int u = 0; u < kSmallBatch; u++) {
+                    const uint32_t q = qa + u;
+                    if (q >= q1) break;
+                    uint64_t t = static_cast<uint64_t>(S >> (b * (q - e_first))) & mask;
+                    if (ENC) {
+                        t = (pv[u] + t) & mask;
+                        if (s_ct[c]) __builtin_nontemporal_store(t, FLASHE_GLOBAL(uint64_t, s_ct[c] + q));
+                        t -= s_sub[c];
+                    }
+                    const uint32_t r = pos[u] - static_cast<uint32_t>(p0);
+                    if (r >= span_len) { *err_flag = 1; continue; }          // a list that is not strictly increasing or reaches beyond the vector
+                    atomicAdd(&acc[r], static_cast<unsigned long long>(t));
+                }
+            }
+        }
+        __syncthreads();                                                           // every entry of the span is in
+#pragma unroll
+        for (int e = 0; e < PER; e++) {
+            const uint32_t r = tid + e * THREADS;
+            if (r < span_len) {
+                const uint64_t v = acc[r];
+                acc[r] = 0;
+                __builtin_nontemporal_store((negate ? from[e] - v : from[e] + v) & mask, out + p0 + r);
+            }
+        }
+        // (the span table was last read before the barrier above)
+        if (tid < 64 && sp + stride < sp_end) span_table(sp + stride);
+        __syncthreads();
+    }
+}
+
+// launch_span_prf at int_bits <= 64 (the arguments checked there, src_dev / out_dev already moved back to position 0)
+static hipError_t launch_span_prf_small(const LaunchEnv &env, uint32_t iter, uint32_t n_jobs, int C, const uint32_t *idx, const uint32_t *const *loc_dev,
+                                        const uint64_t *k, const uint64_t *const *pt_dev, uint64_t *const *ct_dev, const uint64_t *sub, uint64_t base,
+                                        uint64_t total, uint64_t n_spans, uint32_t sp_first, uint32_t sp_end, const uint32_t *start_dev, const uint64_t *src_dev,
+                                        bool negate, uint64_t *out_dev)
+{
+    SpanSmallTable tb{};
+    for (int c = 0; c < C; c++) {
+        tb.loc[c] = loc_dev[c]; tb.k[c] = static_cast<uint32_t>(k[c]); tb.idx[c] = idx[c];
+        if (pt_dev) { tb.pt[c] = pt_dev[c]; tb.ct[c] = ct_dev ? ct_dev[c] : nullptr; tb.sub[c] = sub ? sub[c] : 0; }
+    }
+    uint64_t lo, hi;
+    masks_of(env.b, &lo, &hi);
+    const dim3 grid(static_cast<unsigned>(std::min<uint64_t>(sp_end - sp_first, static_cast<uint64_t>(std::max(env.num_cus, 1)))));
+#define SPAN_PRF_SMALL_LAUNCH(E, S)                                                                                                      \
+    hipLaunchKernelGGL((span_prf_small_kernel<E, S>), grid, dim3(kPrfThreads), 0, env.stream, env.rk, tb, C, iter, n_jobs,              \
+                       static_cast<uint32_t>(env.b), total, static_cast<uint32_t>(n_spans), sp_first, sp_end, start_dev, base, lo, src_dev, negate, \
+                       out_dev, env.te0_dev, env.err_flag)
+    if (!pt_dev) { if (src_dev) SPAN_PRF_SMALL_LAUNCH(false, true); else SPAN_PRF_SMALL_LAUNCH(false, false); }
+    else { if (src_dev) SPAN_PRF_SMALL_LAUNCH(true, true); else SPAN_PRF_SMALL_LAUNCH(true, false); }
+#undef SPAN_PRF_SMALL_LAUNCH
+    return hipGetLastError();
+}
+
 // start_dev: the bounds of exactly these lists at kSpanFused positions per span (launch_span_bounds).  first / count: the position
 // range the launch covers -- first a multiple of kSpanFused, first + count a multiple of it or the end of the vector; src_dev / out_dev
-// address position `first`.
-hipError_t launch_span_prf(const LaunchEnv &env, uint32_t iter, int C, const uint32_t *idx, const uint32_t *const *loc_dev, const uint64_t *k,
+// address position `first`.  sub: L words per client (L = limbs of int_bits); n_jobs: the chunking of every list (int_bits <= 64 counters).
+hipError_t launch_span_prf(const LaunchEnv &env, uint32_t iter, uint32_t n_jobs, int C, const uint32_t *idx, const uint32_t *const *loc_dev, const uint64_t *k,
                            const uint64_t *const *pt_dev, int pt_limbs, uint64_t *const *ct_dev, const uint64_t *sub, uint64_t base_lo, uint64_t base_hi,
                            uint64_t total, const uint32_t *start_dev, const uint64_t *src_dev, bool negate, uint64_t *out_dev, uint64_t first, uint64_t count)
 {
-    if (C > kMaxScatter || C < 1 || env.b <= 64 || (pt_dev && pt_limbs != 1 && pt_limbs != 2)) return hipErrorInvalidValue;
+    const int L = env.b > 64 ? 2 : 1;
+    if (C > kMaxScatter || C < 1 || env.b < 1 || n_jobs == 0 || (pt_dev && pt_limbs != 1 && pt_limbs != L)) return hipErrorInvalidValue;
     if (first > total || count > total - first || first % kSpanFused || (first + count != total && (first + count) % kSpanFused)) return hipErrorInvalidValue;
     if (total == 0 || count == 0) return hipSuccess;
+    for (int c = 0; c < C; c++)
+        if (k[c] >= (1ull << 32)) return hipErrorInvalidValue;
+    const uint64_t n_spans = span_count(total, kSpanFused);
+    if (n_spans >= (1ull << 32)) return hipErrorInvalidValue;
+    const uint32_t sp_first = static_cast<uint32_t>(first / kSpanFused), sp_end = static_cast<uint32_t>(span_count(first + count, kSpanFused));
+    // the kernel indexes the dense vectors by absolute position: pointers that address position `first` are moved back by it
+    const uint64_t back = 8 * static_cast<uint64_t>(L) * first;
+    if (src_dev) src_dev = reinterpret_cast<const uint64_t *>(reinterpret_cast<uintptr_t>(src_dev) - back);
+    out_dev = reinterpret_cast<uint64_t *>(reinterpret_cast<uintptr_t>(out_dev) - back);
+    if (L == 1)
+        return launch_span_prf_small(env, iter, n_jobs, C, idx, loc_dev, k, pt_dev, ct_dev, sub, base_lo, total, n_spans, sp_first, sp_end, start_dev,
+                                     src_dev, negate, out_dev);
     SpanPrfTable tb{};
     for (int c = 0; c < C; c++) {
-        if (k[c] >= (1ull << 32)) return hipErrorInvalidValue;
         tb.loc[c] = loc_dev[c]; tb.k[c] = static_cast<uint32_t>(k[c]); tb.idx[c] = idx[c];
         if (pt_dev) {
             tb.pt[c] = pt_dev[c]; tb.ct[c] = ct_dev ? ct_dev[c] : nullptr;
@@ -1471,12 +1679,6 @@ hipError_t launch_span_prf(const LaunchEnv &env, uint32_t iter, int C, const uin
     }
     uint64_t lo, hi;
     masks_of(env.b, &lo, &hi);
-    const uint64_t n_spans = span_count(total, kSpanFused);
-    if (n_spans >= (1ull << 32)) return hipErrorInvalidValue;
-    const uint32_t sp_first = static_cast<uint32_t>(first / kSpanFused), sp_end = static_cast<uint32_t>(span_count(first + count, kSpanFused));
-    // the kernel indexes the dense vectors by absolute position: pointers that address position `first` are moved back by it
-    if (src_dev) src_dev = reinterpret_cast<const uint64_t *>(reinterpret_cast<uintptr_t>(src_dev) - 16 * first);
-    out_dev = reinterpret_cast<uint64_t *>(reinterpret_cast<uintptr_t>(out_dev) - 16 * first);
     const dim3 grid(static_cast<unsigned>(std::min<uint64_t>(sp_end - sp_first, static_cast<uint64_t>(std::max(env.num_cus, 1)))));
     const char *pe = FLASHE_TUNE_ENV("FLASHE_SPAN_PROBE");
     const int probe = pe ? atoi(pe) : 0;

@@ -992,16 +992,14 @@ class SparseShardedRound:
     (SURVEY.md 8e (i) applied to the sparse path): rank g owns the positions [g S, (g + 1) S), S a whole number of spans, and plays EVERY
     client on them: the entries of each (sorted) location list that fall into its range are encrypted and summed in one pass
     (flashe_sparse_encrypt_aggregate_range_dev), the range of the dense minus-mask is rebuilt and subtracted in another
-    (flashe_sparse_decrypt_range_dev).  PRF counters are compact positions of the WHOLE list, so a rank's ciphertext entries are exactly
-    those a single GPU would have produced; nothing is exchanged for the aggregate, the one collective is the optional all-gather of the
+    (flashe_sparse_decrypt_range_dev).  PRF counters are compact positions of the WHOLE list (at int_bits <= 64 with its n_jobs chunking), so a rank's
+    ciphertext entries are exactly those a single GPU would have produced, at any int_bits; nothing is exchanged for the aggregate, the one collective is the optional all-gather of the
     decrypted ranges.  Every rank holds all location lists (they are what the arbiter redistributes for the decrypt anyway) and the
     plaintext values of the entries it owns."""
 
     def __init__(self, ops, total, int_bits, n_clients, n_jobs, rank=0, world=1):
         self.ops, self.total, self.b, self.C, self.n_jobs, self.rank, self.world = ops, int(total), int_bits, int(n_clients), n_jobs, rank, world
-        if int_bits <= 64:
-            raise ValueError("the position-sharded sparse round runs at int_bits > 64 (the passes with the PRF inside the span reduce)")
-        self.L = 2
+        self.L = limbs_of(int_bits)
         span = ops.sparse_span()
         n_spans = -(-self.total // span)
         self.slice = span * (-(-n_spans // world))

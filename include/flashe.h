@@ -483,8 +483,9 @@ int flashe_sparse_decrypt_bounds_dev(flashe_ctx *ctx, uint32_t iter, int C, cons
  * mask -- ct_dev[c] = flashe_encrypt_dev(iter, idx[c], SINGLE, k[c], n_jobs) of pt_dev[c] (jzf_flashe.py:471-478) -- AND the sum of
  * their expanded uploads, flashe_sparse_aggregate_dev(loc_dev, ct_dev, zeros) (jzf_aggregator.py:150-165, :419-430), is written to
  * agg_out_dev in the same pass.  int_bits > 64 on the table PRF: ONE persistent launch per 64 clients computes every entry's mask block
- * inside the LDS-staged span reduce (the ciphertexts are stored on the way, the compact values never travel twice); otherwise the two
- * calls it stands for.  loc_dev[c] strictly increasing; bounds: NULL or the handle of exactly these lists. */
+ * inside the LDS-staged span reduce (the ciphertexts are stored on the way, the compact values never travel twice); int_bits <= 64 and
+ * the bit-sliced backends: the two calls it stands for (measured faster at that width; the position-range form below runs the fused
+ * pass at every int_bits, one block serving the up to 128 / int_bits entries of a chunk that share it).  loc_dev[c] strictly increasing; bounds: NULL or the handle of exactly these lists. */
 int flashe_sparse_encrypt_aggregate_dev(flashe_ctx *ctx, uint32_t iter, uint32_t n_jobs, uint64_t total, int C, const uint32_t *idx,
                                         const uint32_t *const *loc_dev, const uint64_t *k, const uint64_t *const *pt_dev, int pt_limbs,
                                         const uint64_t *zeros, const flashe_span_bounds *bounds, uint64_t *const *ct_dev,
@@ -493,7 +494,7 @@ int flashe_sparse_encrypt_aggregate_dev(flashe_ctx *ctx, uint32_t iter, uint32_t
  * [first, first + count) of the dense vector and runs every client's entries that fall into them -- counters and list indices stay
  * global (the full lists and their bounds handle are passed), nothing is exchanged for the aggregate.  first is a multiple of
  * flashe_sparse_span(), first + count one or the end of the vector; agg_out_dev / agg_dev / out_dev address position `first`; only the
- * ciphertexts of entries inside the range are written.  int_bits > 64 on the table PRF, strictly increasing lists, bounds required. */
+ * ciphertexts of entries inside the range are written.  Any int_bits on the table PRF, strictly increasing lists, bounds required. */
 int flashe_sparse_span(void);
 int flashe_sparse_encrypt_aggregate_range_dev(flashe_ctx *ctx, uint32_t iter, uint32_t n_jobs, uint64_t total, int C, const uint32_t *idx,
                                               const uint32_t *const *loc_dev, const uint64_t *k, const uint64_t *const *pt_dev,
