@@ -220,6 +220,14 @@ class DeviceBuffer:
         self.engine._check(self.engine._lib.flashe_memcpy_d2h(self.engine._h, out.ctypes.data, self.ptr, out.nbytes))
         return out
 
+    def download_at(self, offset, dtype, count):
+        """`count` values of `dtype` from byte `offset` of the block (the mirror of upload_at: a window of a large vector)."""
+        out = host_empty(int(count), dtype)
+        assert 0 <= offset and offset + out.nbytes <= self.nbytes
+        if out.nbytes:
+            self.engine._check(self.engine._lib.flashe_memcpy_d2h(self.engine._h, out.ctypes.data, self.ptr + int(offset), out.nbytes))
+        return out
+
 
 class DeviceVector:
     """A vector of `n` elements (L = `limbs` uint64 limbs each) that STAYS in HBM between calls of the drop-in API: what
