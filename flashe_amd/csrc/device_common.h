@@ -80,65 +80,12 @@ __device__ __forceinline__ LaneRegs lane_regs(uint32_t *tab)
     return LaneRegs{lane4, lane4 | 0x00010000u, (const lds_u8 *)(lds_u32 *)tab};
 }
 
-#ifndef FLASHE_CTR2
-#define FLASHE_CTR2 1   // wave-uniform part of rounds 1-2 through the scalar cache
-#endif
-// Wave priority inside the software-pipelined rounds (round 5): a wave RAISES its s_setprio as it advances through the rounds of a
-// block pair (0 until round P1, then 1, 2, 3 from rounds P1 / P2 / P3), so the SIMD's arbiter serves the wave closest to the end of its
-// dependent chain first instead of round-robin -- the waves of a SIMD drift apart and one wave's loads, stores and loop head fall under
-// the others' lookups.  prf_chain_kernel<1024, SUM>: 1.440 -> 1.305 ms (-9.3 %), the decrypt of one vector 0.272 -> 0.250, b = 64
-// -5 %; the VALU-bound compact kernels: 0 ... -3 % (tests/perf/ab_chain_libs.py, ab_compact_libs.py; 0 = off, 1 = falling: -4 %;
-// thresholds 5/8/11, 3/6/9, 3/6/10, 6/9/12 within 1 % of 4/7/10, two levels only -6.7 %).  The span kernel keeps its own, FALLING,
-// schedule: its waves meet at a counter every span (rising measured +5.6 % there).  `prio` is a per-launch choice (the last argument of
-// aes256_rounds): on in the int_bits > 64 kernels; int_bits <= 64 (tests/perf/ab_compact_libs.py, 0 against 2): one-limb layout b = 64
-// -5 % (its reduce + decrypt -11.6 %), 40: -7 %, 32: -5 %, but the staged walk of b <= 25: +15 %; compact layout 23 / 24 / 32: -8 %,
-// 16: -2 %, 20: +1.5 % -- the launcher's table follows these (small_swp_prio).
-#ifndef FLASHE_SWP_PRIO
-#define FLASHE_SWP_PRIO 2
-#endif
-#ifndef FLASHE_SWP_P1
-#define FLASHE_SWP_P1 4
-#define FLASHE_SWP_P2 7
-#define FLASHE_SWP_P3 10
-#endif
-#ifndef FLASHE_SWP_PRIO_HALF
-#define FLASHE_SWP_PRIO_HALF 1  // prf_chain_kernel's half tiles (short launches, ragged ends): ten 1e6-element vectors -5 %, config 3's shape +-1 %
-#endif
-#ifndef FLASHE_DEEP_PRIO
-#define FLASHE_DEEP_PRIO 1      // the rising schedule in small_reduce_decrypt_split_kernel (one block per lane): compact b = 20 -6.6 %, 23 -10 %, 16 -2 %
-#endif
-#ifndef FLASHE_SMALL_NP_PRIO
-#define FLASHE_SMALL_NP_PRIO 1  // ... in the two-streams-per-step form of prf_small_chain_kernel and in prf_small_kernel (config 3 at b = 23: -2 %)
-#endif
-#ifndef FLASHE_EDGE_PRIO
-#define FLASHE_EDGE_PRIO 1      // ... in sparse_edge_prf_kernel (the run edges of the sparse double mask): -3.5 %
-#endif
-#ifndef FLASHE_SWP_POST
-#define FLASHE_SWP_POST -1      // >= 0: the priority a wave returns to after the rounds (measured: no difference)
-#endif
-#ifndef FLASHE_SWP
-#define FLASHE_SWP 1   // two-block calls run software pipelined (measured 4.6 % faster than the compiler's own order)
-#endif
-#ifndef FLASHE_ADDR_BITOP
-#define FLASHE_ADDR_BITOP 0   // 1 = lookup addresses by shift + v_bitop3 instead of v_perm_b32 (round 4 A/B builds: measured SLOWER in the kernels, see below)
-#endif
+// address = (byte k of w) << 8 | lane register in one v_perm_b32 (a shift + v_bitop3 form measured slower in the kernels:
+// tests/perf/experiments/README.md).  `sel` is a compile-time constant at every call site.
 template <int OFF>
 __device__ __forceinline__ uint32_t lut(const lds_u8 *base, uint32_t w, uint32_t lanereg, uint32_t sel)
 {
-#if FLASHE_ADDR_BITOP
-    // address = (byte k of w) << 8 | lane register.  v_perm_b32 builds it in one instruction, but every three-source VALU op except
-    // v_bitop3_b32 issues at ~4.3 cycles per wave here and the rounds are bound by VALU issue as much as by the LDS; a shift that brings
-    // byte k to bits 8..15 (a two-source op, 1.9 cycles; none for k = 1) and one v_bitop3 ((x & 0xff00) | lane register, 2.5 cycles)
-    // cost 12 x 1.9 + 16 x 2.5 = 63 cycles per block-round instead of 69 (tools/ubench_lds.hip: 23.2 -> 25.1 lookups per clock per CU
-    // with one block per lane, 24.1 -> 25.2 with two).  In the KERNELS the two builds alternated in one process say the opposite:
-    // ten chained 1e7-element encrypts 1.575 ms against 1.429 with v_perm, b = 64 0.882 / 0.799, config 5 0.655 / 0.62 -- twelve more
-    // instructions per block-round and a two-deep dependent chain in front of every lookup cost more than the cycles they save once the
-    // software-pipelined rounds compete for issue slots.  Kept as a build option, off.  `sel` is a compile-time constant at every call site.
-    const uint32_t x = sel == SEL_B1 ? w : sel == SEL_B0 ? w << 8 : sel == SEL_B2 ? w >> 8 : w >> 16;
-    const uint32_t addr = __builtin_amdgcn_bitop3_b32(x, 0xff00u, lanereg, 0xea);
-#else
     const uint32_t addr = __builtin_amdgcn_perm(w, lanereg, sel);
-#endif
     return *reinterpret_cast<const lds_u32 *>(base + addr + OFF);
 }
 
@@ -160,7 +107,7 @@ __device__ __forceinline__ void aes256_rounds2_swp(const RoundKeys &rk, const La
 template <int NB, int FIRST>
 __device__ __forceinline__ void aes256_rounds(const RoundKeys &rk, const LaneRegs lr, uint32_t (&s)[NB][4], bool prio = false)
 {
-    if constexpr (NB == 2 && FLASHE_SWP) {
+    if constexpr (NB == 2) {
         aes256_rounds2_swp<FIRST>(rk, lr, s, prio);
         return;
     }
@@ -237,6 +184,14 @@ __device__ __forceinline__ void finish_final(const RoundKeys &rk, const Lk16 &k,
                rk.w[56 + j];
 }
 
+// Wave priority inside the software-pipelined rounds: a wave RAISES its s_setprio as it advances through the rounds of a block pair
+// (0, then 1, 2, 3 from rounds 4 / 7 / 10), so the SIMD's arbiter serves the wave closest to the end of its dependent chain first
+// instead of round-robin -- the waves of a SIMD drift apart and one wave's loads, stores and loop head fall under the others' lookups
+// (prf_chain_kernel<1024, SUM>: -9.3 %; the schedules measured against it: tests/perf/experiments/README.md).  The span kernel keeps
+// its own, FALLING, schedule: its waves meet at a counter every span.  `prio` is a per-launch choice (the last argument of
+// aes256_rounds): on in the int_bits > 64 kernels; int_bits <= 64 (tests/perf/ab_compact_libs.py, off against on): one-limb layout
+// b = 64 -5 % (its reduce + decrypt -11.6 %), 40: -7 %, 32: -5 %, but the staged walk of b <= 25: +15 %; compact layout 23 / 24 / 32:
+// -8 %, 16: -2 %, 20: +1.5 % -- the launcher's table follows these (small_swp_prio).
 template <int FIRST>
 __device__ __forceinline__ void aes256_rounds2_swp(const RoundKeys &rk, const LaneRegs lr, uint32_t (&s)[2][4], bool prio)
 {
@@ -247,17 +202,10 @@ __device__ __forceinline__ void aes256_rounds2_swp(const RoundKeys &rk, const La
 #pragma unroll
     for (int r = FIRST; r < 14; r++) {
         // (prio: wave-uniform, chosen per launch -- a scalar branch around each s_setprio)
-#if FLASHE_SWP_PRIO == 1            // (falling with the progress through the rounds: the A/B alternative)
-        if (prio && r == FIRST) __builtin_amdgcn_s_setprio(3);
-        else if (prio && r == 5) __builtin_amdgcn_s_setprio(2);
-        else if (prio && r == 8) __builtin_amdgcn_s_setprio(1);
-        else if (prio && r == 11) __builtin_amdgcn_s_setprio(0);
-#elif FLASHE_SWP_PRIO == 2
         if (prio && r == FIRST) __builtin_amdgcn_s_setprio(0);
-        if (prio && r == FLASHE_SWP_P1) __builtin_amdgcn_s_setprio(1);
-        if (prio && r == FLASHE_SWP_P2) __builtin_amdgcn_s_setprio(2);
-        if (prio && r == FLASHE_SWP_P3) __builtin_amdgcn_s_setprio(3);
-#endif
+        if (prio && r == 4) __builtin_amdgcn_s_setprio(1);
+        if (prio && r == 7) __builtin_amdgcn_s_setprio(2);
+        if (prio && r == 10) __builtin_amdgcn_s_setprio(3);
         finish_main(rk, r, ka, s[0]);
         ka = r < 13 ? issue_main(lr, s[0]) : issue_final(lr, s[0]);
         __builtin_amdgcn_sched_barrier(0);
@@ -267,9 +215,6 @@ __device__ __forceinline__ void aes256_rounds2_swp(const RoundKeys &rk, const La
     }
     finish_final(rk, ka, s[0]);
     finish_final(rk, kb, s[1]);
-#if FLASHE_SWP_PRIO == 2 && FLASHE_SWP_POST >= 0
-    if (prio) __builtin_amdgcn_s_setprio(FLASHE_SWP_POST);
-#endif
 }
 
 // One block per lane where there is no second one to pipeline against: all sixteen lookups of a round are issued as their state
@@ -283,9 +228,9 @@ __device__ __forceinline__ void aes256_rounds1_deep(const RoundKeys &rk, const L
 #pragma unroll
     for (int r = FIRST; r < 14; r++) {
         if (prio && r == FIRST) __builtin_amdgcn_s_setprio(0);           // (the rising schedule of aes256_rounds2_swp)
-        if (prio && r == FLASHE_SWP_P1) __builtin_amdgcn_s_setprio(1);
-        if (prio && r == FLASHE_SWP_P2) __builtin_amdgcn_s_setprio(2);
-        if (prio && r == FLASHE_SWP_P3) __builtin_amdgcn_s_setprio(3);
+        if (prio && r == 4) __builtin_amdgcn_s_setprio(1);
+        if (prio && r == 7) __builtin_amdgcn_s_setprio(2);
+        if (prio && r == 10) __builtin_amdgcn_s_setprio(3);
         finish_main(rk, r, k, s);
         k = r < 13 ? issue_main(lr, s) : issue_final(lr, s);
         __builtin_amdgcn_sched_barrier(0);

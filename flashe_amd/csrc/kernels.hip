@@ -214,7 +214,7 @@ __global__ __launch_bounds__(THREADS) void prf_wide_batch_kernel(const RoundKeys
         const uint64_t in_stride = tb.in_stride_of(v);
         uint64_t *sum_out = tb.sum_out_of(v);
         // wave-uniform part of rounds 1-2: valid while the wave's 256 counters share bytes 1..3
-        const bool uni = FLASHE_CTR2 && epl == kBigEpl && ctr_fast && ((first + kw) & 255u) == 0;
+        const bool uni = epl == kBigEpl && ctr_fast && ((first + kw) & 255u) == 0;
         CtrUniform Ua{}, Ub{};
         if (uni) {
             const uint32_t x3 = static_cast<uint32_t>(first + kw) ^ rk.w[3];
@@ -285,10 +285,6 @@ __global__ __launch_bounds__(THREADS) void prf_wide_batch_kernel(const RoundKeys
 // left of a workgroup's share after whole rounds is cut into HALF tiles (one pair per lane, one-step shortcut) so
 // that no wave ends up with a whole 256 x (len + 1)-block tile more than its neighbours.  Short launches
 // (all_half) run entirely in half tiles.
-#ifndef FLASHE_HALF_U
-#define FLASHE_HALF_U 1        // round 6: the half tiles of prf_chain_kernel take the second counter shortcut too (a half tile is 128 aligned counters: ctr_uniform per
-                               // item and stream, 196 lookups per block instead of 208) -- launches of 1e6 .. 2e6 elements -3.5 ... -5 %, the headline unchanged (0: A/B builds)
-#endif
 constexpr int kMaxChains = 16;       // chains per launch
 constexpr int kMaxLinks = 128;       // outputs per launch, all chains together
 struct ChainTable {
@@ -371,9 +367,6 @@ __global__ __launch_bounds__(THREADS) void prf_chain_dmask_kernel(const RoundKey
 
 // the same launch specialised for its headline shape (D128 in prf_chain_body.inc): int_bits = 128, one-limb inputs, every input and
 // output present, the chain's n x 16 B below 4 GiB -- its whole tiles run prf_chain_sum128_tile.inc
-#ifndef FLASHE_SUM128
-#define FLASHE_SUM128 1        // 0: every decrypt-mask chain runs prf_chain_dmask_kernel (A/B builds)
-#endif
 constexpr uint64_t kSum128MaxCount = 0x0fffff00ull;      // n x 16 B of every array below 4 GiB, with room for a tile's wrapped offsets
 template <int THREADS>
 __global__ __launch_bounds__(THREADS) void prf_dmask_sum128_kernel(const RoundKeys rk, const ChainTable tb, int n_chains, int all_half_arg,
@@ -690,7 +683,7 @@ __global__ __launch_bounds__(kSmallThreads) void prf_small_jobs_kernel(const Rou
             const CtrVar x = ctr_var(rk, lr, static_cast<uint32_t>(ctr));
             ctr_round1(pre_a, x, s[0]);
             if (DBL) ctr_round1(pre_b, x, s[DBL ? 1 : 0]);
-            aes256_rounds<DBL ? 2 : 1, 2>(rk, lr, s, FLASHE_SMALL_NP_PRIO != 0);
+            aes256_rounds<DBL ? 2 : 1, 2>(rk, lr, s, true);
         } else {
             set_block(s[0], iter, ia, ctr);
             if (DBL) set_block(s[DBL ? 1 : 0], iter, im, ctr);
@@ -862,13 +855,8 @@ __device__ __forceinline__ WalkPt small_walk32_load(const ET *__restrict__ in, u
         r.v[u] = 0u;
         // b <= 32: only the low word of the 8-byte element takes part (little endian: the first four bytes); a 4-byte load holds one
         // VGPR while it is in flight instead of two -- up to sixteen fewer live registers across the AES rounds of a pair in a
-        // kernel that sits at 128 VGPRs with spills.  Two builds alternated in one process (tests/perf/ab_two_libs.py), ten
-        // 1e7-element vectors: b = 16 0.343 -> 0.310 ms, b = 20 0.351 -> 0.346, b = 25 and b = 8 unchanged
-#ifdef FLASHE_WALK_LOAD64       // (A/B build: tests/perf/ab_two_libs.py)
-        if (pin && u < m) r.v[u] = static_cast<uint32_t>(__builtin_nontemporal_load(pin + 64u * u));
-#else
+        // kernel that sits at 128 VGPRs with spills (the 8-byte load's times: tests/perf/experiments/README.md)
         if (pin && u < m) r.v[u] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(pin + 64u * u));
-#endif
     }
     return r;
 }
@@ -989,18 +977,6 @@ static bool fixed32_width(int b)
     default: return false;
     }
 }
-#ifndef FLASHE_SMALL_U2
-#define FLASHE_SMALL_U2 1      // small_chain_fast32 takes the second counter shortcut where both of a lane's blocks lie in one 256-counter window each -- on chains of
-                               // at most FLASHE_SMALL_U2_STREAMS streams (the decrypt of one vector: 0.0587 -> 0.0571 ms at int_bits 20, -3 ... -5 % at every width).  On the
-                               // ten-client chain it LOSES 10-15 % (0.278 -> 0.320 ms: thirty dependent scalar loads and two unpipelined lookup steps at the head
-                               // of every one of eleven steps, with one pair per step to spread them over; the wide kernel has two) -- ab_compact_libs.py, round 6
-#ifndef FLASHE_SMALL_U2_STREAMS
-#define FLASHE_SMALL_U2_STREAMS 2
-#endif
-#endif
-#ifndef FLASHE_SMALL_FAST32
-#define FLASHE_SMALL_FAST32 1   // whole tiles of the compile-time-width compact kernels in a loop of their own (small_chain_fast32; 0: the general loop, for A/B builds)
-#endif
 template <int M> struct DirectPt { uint32_t v[M]; };
 typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
 typedef uint32_t u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
@@ -1159,7 +1135,7 @@ __device__ __forceinline__ void small_chain_fast32(const RoundKeys &rk, const La
             dB = direct32_load<M>(in, kB);
         }
         uint32_t s[2][4];
-        if (FLASHE_SMALL_U2 && uni) {
+        if (uni) {
             // both blocks' sixty-four counters share bytes 1 .. 3 (x3A / x3B): the second counter shortcut of the wide kernel, 196 lookups
             // per block instead of 208 (the wave-uniform part of rounds 1-2 through the scalar cache, device_common.h)
             const CtrUniform UA = ctr_uniform(rk, te4, pre, x3A), UB = ctr_uniform(rk, te4, pre, x3B);
@@ -1291,13 +1267,15 @@ __global__ __launch_bounds__(kSmallThreads) void prf_small_chain_kernel(const Ro
 #pragma unroll
         for (int t = 0; t < MB; t++) { accA[t] = 0u; accB[t] = 0u; }
         uint32_t *const sum32 = B != 0 && B != 64 ? reinterpret_cast<uint32_t *>(tb.sum_out[cur]) : nullptr;
-#if FLASHE_SMALL_FAST32
         if constexpr (PAIR && B != 0 && B != 64) {
             if (fastA && fastB) {                                  // (wave-uniform) both blocks of every lane whole and inside the range
                 // the lanes' counters are consecutive inside a chunk; where a set of sixty-four does not cross a multiple of 256 its
-                // bytes 1 .. 3 are the wave's (three sets of four in the chunks whose first counter is not a multiple of 64)
+                // bytes 1 .. 3 are the wave's (three sets of four in the chunks whose first counter is not a multiple of 64).  The second
+                // counter shortcut only on short chains: on the ten-client chain its scalar loads at the head of every step cost more than
+                // it saves (tests/perf/experiments/README.md)
+                constexpr int kU2MaxStreams = 2;
                 const uint32_t bA = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(ctrA)), bB = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(ctrB));
-                const bool uni = FLASHE_SMALL_U2 && n_streams <= FLASHE_SMALL_U2_STREAMS && __ballot(ctrA - bA == lane && ctrB - bB == lane) == ~0ull &&
+                const bool uni = n_streams <= kU2MaxStreams && __ballot(ctrA - bA == lane && ctrB - bB == lane) == ~0ull &&
                                  (bA & 255u) <= 192u && (bB & 255u) <= 192u;
                 if (single) small_chain_fast32<B, true>(rk, lr, pre_lds, sbase, n_streams, tb.in + link0, tb.out + link0, xA, xB, j0A - first, j0B - first, sum32, p.swp_prio != 0,
                                                         p.te0, uni, bA ^ rk.w[3], bB ^ rk.w[3]);
@@ -1306,7 +1284,6 @@ __global__ __launch_bounds__(kSmallThreads) void prf_small_chain_kernel(const Ro
                 continue;
             }
         }
-#endif
         if (PAIR) {
             // two blocks per lane on the same prefix, one stream per step
             for (int c = 0; c < n_streams; c++) {
@@ -1393,7 +1370,7 @@ __global__ __launch_bounds__(kSmallThreads) void prf_small_chain_kernel(const Ro
                 uint32_t s[2][4];
                 ctr_round1(pre0, xA, s[0]);
                 ctr_round1(pre1, xA, s[1]);
-                aes256_rounds<2, 2>(rk, lr, s, FLASHE_SMALL_NP_PRIO != 0);
+                aes256_rounds<2, 2>(rk, lr, s, true);
                 const u128 S0 = words_to_u128(s[0]), S1 = words_to_u128(s[1]);
                 if (l0 >= 0) {
                     const u128 D = single ? S0 : slot_diff(prevA, S0, top, p.b);
@@ -1580,7 +1557,7 @@ __global__ __launch_bounds__(kSmallThreads) void small_reduce_decrypt_split_kern
 #ifdef FLASHE_TUNING
         if (!(has_minus & 0x100))                                        // (0x100: timing probe without the rounds)
 #endif
-        aes256_rounds1_deep<2>(rk, lr, s[0], FLASHE_DEEP_PRIO != 0);     // (one block per lane: all sixteen lookups of a round in flight)
+        aes256_rounds1_deep<2>(rk, lr, s[0], true);     // (one block per lane: all sixteen lookups of a round in flight)
         // row word order = little-endian words of the 128-bit block value (word 0 = bits 0..31)
         *reinterpret_cast<uint4 *>(row0 + 4 * lane) = drop ? make_uint4(0u, 0u, 0u, 0u) : make_uint4(s[0][3], s[0][2], s[0][1], s[0][0]);
         __builtin_amdgcn_wave_barrier();
@@ -2085,9 +2062,6 @@ hipError_t launch_prf_jobs(const LaunchEnv &env, uint32_t iter, bool dbl, int n_
 // cut is computed by both pieces); short launches are cut further so that every wave of the chip gets an item.
 static hipError_t launch_small_chains(const LaunchEnv &env, uint32_t iter, int n_chains, const PrfChain *chains, uint64_t n, uint32_t n_jobs);
 
-#ifndef FLASHE_CHAIN_QUARTER_DEFAULT
-#define FLASHE_CHAIN_QUARTER_DEFAULT 1   // quarter tiles for the shortest chained launches (0: half tiles as before round 6; A/B builds)
-#endif
 // the shape of prf_dmask_sum128_kernel: one summed double-mask chain at int_bits = 128, one-limb inputs, every input and output present
 static bool sum128_shape(const LaunchEnv &env, int nc, const ChainTable &tb, uint64_t lo, uint64_t hi)
 {
@@ -2152,7 +2126,7 @@ hipError_t launch_prf_chains(const LaunchEnv &env, uint32_t iter, int n_chains, 
     // the kernel's quarter branch) -- four items per tile, a chain cut into as few pieces as fill the chip ONCE (every wave one item
     // of the same length; pieces of at least eight outputs).  Config 3's mask precompute (242 tiles x 101 + 2 streams): 3 pieces of
     // the hundred-client chain instead of 10-12, 0.111 -> see DESIGN 4.4.  Not with a fused codec (its instantiation keeps half tiles).
-    bool quarter = !env.codec && !summed && !single_parts && all_half && 4 * total_tiles <= waves && !force_parts && FLASHE_CHAIN_QUARTER_DEFAULT;
+    bool quarter = !env.codec && !summed && !single_parts && all_half && (4 * total_tiles <= waves && !force_parts);
     if (tune) {                                                            // (tests/perf/quarter_sweep.py: 1 / 0 force the mode on / off)
         if (const char *e = FLASHE_TUNE_ENV("FLASHE_CHAIN_QUARTER")) quarter = atoi(e) != 0 && !env.codec && !summed && !single_parts && all_half;
     }
@@ -2225,7 +2199,7 @@ hipError_t launch_prf_chains(const LaunchEnv &env, uint32_t iter, int n_chains, 
             cq = *env.codec;
         }
         if (env.codec && summed) return hipErrorInvalidValue;
-        if (dmask && FLASHE_SUM128 && sum128_shape(env, nc, tb, lo, hi))
+        if (dmask && sum128_shape(env, nc, tb, lo, hi))
             hipLaunchKernelGGL((prf_dmask_sum128_kernel<kPrfThreads>), dim3(grid), dim3(kPrfThreads), 0, env.stream, env.rk, tb, nc,
                                (all_half ? 1 : 0) | (quarter ? 4 : 0) | probe, iter, lo, hi, env.te0_dev, dmask);
         else if (dmask)
@@ -2371,10 +2345,7 @@ static hipError_t launch_small_chains(const LaunchEnv &env, uint32_t iter, int n
     // a chain of two streams: -9 %, 0.0616 -> 0.0562 ms) and not the staged walk of the one-limb layout at m >= 5 (+15 %)
     int longest = 0;
     for (int i = 0; i < n_chains; i++) longest = std::max(longest, chains[i].n_out);
-#ifndef FLASHE_PRIO_B20
-#define FLASHE_PRIO_B20 0      // (A/B builds: the rising wave priority at int_bits 20 in the compact layout whatever the chain length)
-#endif
-    p.swp_prio = env.elem32 ? (!p.no_fixed_width && fixed32_width(env.b) && (FLASHE_PRIO_B20 || env.b != 20 || longest <= 1)) : (p.m <= 4 && !p.no_direct);
+    p.swp_prio = env.elem32 ? (!p.no_fixed_width && fixed32_width(env.b) && (env.b != 20 || longest <= 1)) : (p.m <= 4 && !p.no_direct);
     { static const int v = FLASHE_TUNE_ENV("FLASHE_SMALL_PRIO") ? atoi(FLASHE_TUNE_ENV("FLASHE_SMALL_PRIO")) : -1; if (v >= 0) p.swp_prio = v; }
     struct Piece { const PrfChain *ch; int l0, l1; uint64_t blk_first, blk_count; };
     std::vector<Piece> pieces;

@@ -202,7 +202,7 @@
                     uint32_t s[2][4];
                     ctr_round2(lr, pre0.u[0], v0, U0, s[0]);
                     ctr_round2(lr, pre1.u[0], v0, U1, s[1]);
-                    aes256_rounds<2, 3>(rk, lr, s, FLASHE_SWP_PRIO_HALF != 0);
+                    aes256_rounds<2, 3>(rk, lr, s, true);
                     loads_landed(x0, x1);
                     const u128 c0 = words_to_u128(s[0]), c1 = words_to_u128(s[1]);
                     if (l0 >= 0) {
@@ -221,9 +221,7 @@
             const uint64_t j0 = tj + lane, j1 = j0 + 64u, k0 = j0 - first, k1 = j1 - first;
             const bool a0 = j0 >= first && j0 < end, a1 = j1 >= first && j1 < end;
             const CtrVar xv0 = ctr_var(rk, lr, static_cast<uint32_t>(j0)), xv1 = ctr_var(rk, lr, static_cast<uint32_t>(j1));
-#if FLASHE_HALF_U
             const uint32_t x3h = static_cast<uint32_t>(tj) ^ rk.w[3];        // (a half tile is 128 aligned counters: bytes 1 .. 3 are the wave's)
-#endif
             u128 p0 = 0, p1 = 0, q0 = 0, q1 = 0;
             uint64_t *const sum_out = SUM ? tb.sum_out[cur] : nullptr;
             u128 d0 = 0, d1 = 0;                                        // DMASK: the first stream's blocks of the lane's two elements
@@ -244,18 +242,12 @@
                     if (a1) x1 = static_cast<u128>(in[k1]);
                 }
                 uint32_t s[2][4];
-#if FLASHE_HALF_U
                 {
                     const CtrUniform U = ctr_uniform(rk, te0, pre, x3h);
                     ctr_round2(lr, pre.u[0], xv0.v[0], U, s[0]);
                     ctr_round2(lr, pre.u[0], xv1.v[0], U, s[1]);
                 }
-                aes256_rounds<2, 3>(rk, lr, s, FLASHE_SWP_PRIO_HALF != 0);
-#else
-                ctr_round1(pre, xv0, s[0]);
-                ctr_round1(pre, xv1, s[1]);
-                aes256_rounds<2, 2>(rk, lr, s, FLASHE_SWP_PRIO_HALF != 0);
-#endif
+                aes256_rounds<2, 3>(rk, lr, s, true);
                 loads_landed(x0, x1);
                 const u128 c0 = words_to_u128(s[0]), c1 = words_to_u128(s[1]);
                 const u128 r0 = x0 + (single ? c0 : p0 - c0), r1 = x1 + (single ? c1 : p1 - c1);

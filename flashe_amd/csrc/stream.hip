@@ -757,24 +757,15 @@ struct ScatterTable {
     uint64_t k[kMaxScatter], sub_lo[kMaxScatter], sub_hi[kMaxScatter];
 };
 
-#ifndef FLASHE_BOUNDS_TR
-#define FLASHE_BOUNDS_TR 0          // 1 (A/B builds): the fused passes' table transposed, start[client][span] -- VERDICT r5 #1 (b), measured in round 6: the
-                                    // bounds pass 0.0225 -> 0.0188 ms, but the two passes that read it 0.2567 -> 0.2589 and 0.2508 -> 0.2520 (the keeper's
-                                    // fifty words now come from fifty lines): round 0.5300 against 0.5297 ms -- nothing gained, the simpler layout stays
-#endif
 constexpr int kBoundsPerThread = 8;
-// entry q of client c (prev = the entry before it, cur = itself; q == k closes the list) opens the spans of SPAN positions between them
-// TR (an A/B build option, see FLASHE_BOUNDS_TR): the table as start[client][span] (rows of n_spans + 1 words) instead of
-// start[span][client]: a client's consecutive entries open consecutive spans, so with a row per client the stores of a wave fall into
-// one or two lines instead of one line per span (730 k four-byte stores to as many lines in config 5), and a long run of empty spans
-// is one contiguous fill.  The scatter moves to the readers: the keeper wave of span_prf_kernel reads one word per client from C
-// different lines, three spans ahead of their use.
-template <int SPAN, bool TR>
+// entry q of client c (prev = the entry before it, cur = itself; q == k closes the list) opens the spans of SPAN positions between them:
+// start[span * C + c] = q (the transposed table, start[c][span], measured no faster: tests/perf/experiments/README.md)
+template <int SPAN>
 __device__ __forceinline__ void span_open(uint32_t *start, int C, int c, uint64_t q, bool live, uint64_t k, uint64_t prev, uint64_t cur, uint64_t total,
                                           uint32_t lane)
 {
     const uint64_t n_spans = (total + SPAN - 1) / SPAN;
-    const uint64_t row = TR ? static_cast<uint64_t>(c) * (n_spans + 1) : static_cast<uint64_t>(c), step = TR ? 1 : static_cast<uint64_t>(C);
+    const uint64_t row = static_cast<uint64_t>(c), step = static_cast<uint64_t>(C);
     const uint64_t s_last = q < k ? std::min<uint64_t>(static_cast<uint32_t>(cur) / static_cast<uint32_t>(SPAN), n_spans) : n_spans;
     const uint64_t s_first = !live ? s_last + 1 : q ? std::min<uint64_t>(static_cast<uint32_t>(prev) / static_cast<uint32_t>(SPAN), n_spans) + 1 : 0;
     const bool is_long = s_first + 16 <= s_last;
@@ -821,8 +812,8 @@ __global__ __launch_bounds__(kStreamThreads) void span_bounds_kernel(const Scatt
         const bool live = q <= k;
         const uint64_t prev = live && q ? v[i] : 0, cur = live && q < k ? v[1 + i] : 0;
         if (live && q < k && (cur >= total || (q && cur <= prev))) *err_flag = 1;
-        if (start_reduce) span_open<kSpanReduce, false>(start_reduce, C, c, q, live, k, prev, cur, total, lane);
-        if (start_fused) span_open<kSpanFused, FLASHE_BOUNDS_TR != 0>(start_fused, C, c, q, live, k, prev, cur, total, lane);
+        if (start_reduce) span_open<kSpanReduce>(start_reduce, C, c, q, live, k, prev, cur, total, lane);
+        if (start_fused) span_open<kSpanFused>(start_fused, C, c, q, live, k, prev, cur, total, lane);
     }
 }
 
@@ -1053,14 +1044,6 @@ struct SpanPrfEntry {
                                  // 0.2696 against 0.2704 ms with all sixteen waves writing: nothing (the heavier SIMDs' waves shed a tenth of their instructions
                                  // and the wait in front of the write-out, and the span's period does not move)
 #endif
-#ifndef FLASHE_SPAN_PRIO
-#define FLASHE_SPAN_PRIO 1       // waves yield as they advance through the rounds of a span (0 = off, 2 = rising: +5.6 %; for A/B builds)
-#endif
-#ifndef FLASHE_SPAN_P1
-#define FLASHE_SPAN_P1 5         // the rounds at which the priority steps down (3 from round 2)
-#define FLASHE_SPAN_P2 8
-#define FLASHE_SPAN_P3 11
-#endif
 
 __device__ __forceinline__ void phase_arrive(uint32_t *ctr)
 {
@@ -1153,8 +1136,7 @@ __global__ __launch_bounds__(kPrfThreads) void span_prf_kernel(const RoundKeys r
     do {                                                                                                                 \
         const uint64_t sp_ = (spx), sc_ = sp_ < n_spans ? sp_ : n_spans - 1;                                             \
         f_live = ln < C && sp_ < sp_end;                                                                                 \
-        if (FLASHE_BOUNDS_TR) { const uint64_t at_ = static_cast<uint64_t>(ln_c) * (static_cast<uint64_t>(n_spans) + 1) + sc_; f0 = start[at_]; f1 = start[at_ + 1]; } \
-        else { f0 = start[sc_ * C + ln_c]; f1 = start[(sc_ + 1) * C + ln_c]; }                                           \
+        f0 = start[sc_ * C + ln_c]; f1 = start[(sc_ + 1) * C + ln_c];                                                    \
     } while (0)
 #define SPAN_PRF_PUBLISH(buf)                                                                                            \
     do {                                                                                                                 \
@@ -1322,16 +1304,13 @@ __global__ __launch_bounds__(kPrfThreads) void span_prf_kernel(const RoundKeys r
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int r = 2; r < 14; r++) {
-#if FLASHE_SPAN_PRIO
-                // waves that are ahead yield to the ones behind: a wave that runs its rounds alone on its SIMD sees the full lookup latency
-                // every round while the other SIMD slots idle.  (Measured and dropped, tests/perf/experiments/r05_*: the waves in two
-                // priority classes half a span apart, so that one class's atomics / loop head fall into the other's rounds -- the waits
-                // below then block for a round each and the passes get 5-9 % slower; no priorities at all: 15-20 % slower.)
-                if (r == 2) __builtin_amdgcn_s_setprio(FLASHE_SPAN_PRIO == 2 ? 0 : 3);
-                else if (r == FLASHE_SPAN_P1) __builtin_amdgcn_s_setprio(FLASHE_SPAN_PRIO == 2 ? 1 : 2);
-                else if (r == FLASHE_SPAN_P2) __builtin_amdgcn_s_setprio(FLASHE_SPAN_PRIO == 2 ? 2 : 1);
-                else if (r == FLASHE_SPAN_P3) __builtin_amdgcn_s_setprio(FLASHE_SPAN_PRIO == 2 ? 3 : 0);
-#endif
+                // waves that are ahead yield to the ones behind (3, 2, 1, 0 from rounds 2 / 5 / 8 / 11): a wave that runs its rounds alone
+                // on its SIMD sees the full lookup latency every round while the other SIMD slots idle (the other schedules measured:
+                // tests/perf/experiments/README.md)
+                if (r == 2) __builtin_amdgcn_s_setprio(3);
+                else if (r == 5) __builtin_amdgcn_s_setprio(2);
+                else if (r == 8) __builtin_amdgcn_s_setprio(1);
+                else if (r == 11) __builtin_amdgcn_s_setprio(0);
                 if (r < 10) finish_main(rk, r, k, s);
                 else {
 #pragma unroll
@@ -1520,9 +1499,7 @@ __global__ __launch_bounds__(kPrfThreads) void span_prf_small_kernel(const Round
     // wave 0: the work items of span sp (the slice [f0, f1) of client `tid`'s list, clamped like span_reduce_kernel's)
     auto span_table = [&](uint64_t sp) {
         const uint32_t ln_c = static_cast<uint32_t>(min(tid, C - 1));
-        uint32_t f0, f1;
-        if (FLASHE_BOUNDS_TR) { const uint64_t at = static_cast<uint64_t>(ln_c) * (static_cast<uint64_t>(n_spans) + 1) + sp; f0 = start[at]; f1 = start[at + 1]; }
-        else { f0 = start[sp * C + ln_c]; f1 = start[(sp + 1) * C + ln_c]; }
+        uint32_t f0 = start[sp * C + ln_c], f1 = start[(sp + 1) * C + ln_c];
         const uint32_t kc = tb.k[ln_c];
         f0 = min(f0, kc); f1 = min(f1, kc);
         uint32_t nw = 0, g0 = 0;
@@ -1744,7 +1721,7 @@ __global__ __launch_bounds__(kPrfThreads) void sparse_edge_prf_kernel(const Roun
         uint32_t s[2][4];
         set_block(s[0], iter, c + 1u, ctr);            // add side: list (prefix) c + 1
         set_block(s[1], iter, c, ctr);                 // minus side: list c
-        aes256_encrypt<2>(rk, lr, s, FLASHE_EDGE_PRIO != 0);
+        aes256_encrypt<2>(rk, lr, s, true);
         const int sh = static_cast<int>(static_cast<uint32_t>(b) * (p - static_cast<uint32_t>(ctr) * m));
         const u128 A = in_next ? static_cast<u128>(0) : (words_to_u128(s[0]) >> sh) & mask;
         const u128 M = in_prev ? static_cast<u128>(0) : (words_to_u128(s[1]) >> sh) & mask;

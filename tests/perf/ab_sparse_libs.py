@@ -2,7 +2,7 @@
 """Config 5's two fused sparse passes under two BUILDS of the library alternated inside one process (same box, same clock):
 flashe_sparse_encrypt_aggregate_dev (50 encrypts + the aggregate of their uploads) and flashe_sparse_decrypt_dev, HIP-event times, and
 the results of the two builds compared byte for byte (the GPU suite compares the product build with the oracle).
-usage: ab_sparse_libs.py <.so in flashe_amd/> [more .so ...]      e.g. after  make -C flashe_amd/csrc ab ABFLAGS=-DFLASHE_SPAN_OVERLAP=0
+usage: ab_sparse_libs.py <.so in flashe_amd/> [more .so ...]      e.g. after  make -C flashe_amd/csrc ab ABFLAGS=-DFLASHE_SOME_VARIANT=1
        (the first library named is the reference of the byte comparison; AB_REPS = alternations, default 6; `make ab` builds carry
        -DFLASHE_TUNING, so compare them with libflashe_hip_tuning.so rather than with the product library)"""
 import os

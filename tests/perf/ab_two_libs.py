@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Two BUILDS of the library alternated inside one process (the shader clock and the box are then the same for both): ten 1e7-element
 chained encrypts per bit width, HIP-event times.
-usage: ab_two_libs.py <other .so in flashe_amd/> [bits ...]      e.g. after
-       hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -I../../include -DFLASHE_WALK_LOAD64 -shared -o ../libflashe_hip_ab.so kernels.hip sparsify.hip mt19937.hip abi.hip comm.hip -ldl"""
+usage: ab_two_libs.py <other .so in flashe_amd/> [bits ...]      e.g. after  make -C flashe_amd/csrc ab ABFLAGS=-DFLASHE_SOME_VARIANT=1
+       (-> libflashe_hip_ab.so, every translation unit of the library)"""
 import os
 import sys
 

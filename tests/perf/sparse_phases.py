@@ -55,7 +55,7 @@ if os.environ.get("FLASHE_SPAN_PROBE") == "9":              # tuning build: wher
     fn = eng._lib.flashe_tune_span_prf_cycles
     fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int], ctypes.c_int
     fn(eng._h, out, 1)
-    # (round 5, FLASHE_SPAN_OVERLAP: order in the loop = head, rounds, wait + write-out of the previous span, barrier A, atomics, second pass,
+    # (round 5's overlapped span loop: order in the loop = head, rounds, wait + write-out of the previous span, barrier A, atomics, second pass,
     # barrier B; the per-wave figures = loop head -> end of the wave's rounds)
     names = ["search + round 1", "rounds 2..14", "atomics (+ ct store)", "second pass (crowded spans)", "barrier A (after the write-out)", "wait + write-out of the previous span",
              "barrier B (entries in)", "loop head"]
