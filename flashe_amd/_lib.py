@@ -45,6 +45,16 @@ class BatchLayer(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class TensorLayer(ctypes.Structure):
+    """flashe_tensor_layer of include/flashe.h."""
+    _fields_ = [("start", ctypes.c_uint64), ("ptr", ctypes.c_void_p), ("alpha", ctypes.c_double), ("shift", ctypes.c_double),
+                ("dtype", ctypes.c_int32), ("flags", ctypes.c_int32)]
+
+
+TENSOR_F32, TENSOR_F64, TENSOR_F16, TENSOR_BF16 = 0, 1, 2, 3
+TENSOR_SHIFT, TENSOR_SHIFT_WIDE, TENSOR_LOOP_F64 = 1, 2, 4
+
+
 class FlasheError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"flashe error {code}: {msg}")
@@ -175,6 +185,13 @@ _SIGNATURES = {
     "flashe_unquantize_model_dev": (c_int, [c_vp, c_u64, c_u64, c_u64, c_vp, ctypes.POINTER(CodecLayer), c_int, c_int, c_int, c_vp]),
     "flashe_shift_dev": (c_int, [c_vp, c_u64, c_vp, c_int, ctypes.c_double, c_int]),
     "flashe_mean_std_dev": (c_int, [c_vp, c_u64, c_vp, c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "flashe_ctx_stream": (c_int, [c_vp, ctypes.POINTER(c_vp)]),
+    "flashe_stream_wait_stream": (c_int, [c_vp, c_vp]),
+    "flashe_event_query": (c_int, [c_vp, c_vp, ctypes.POINTER(c_int)]),
+    "flashe_quantize_encrypt_tensors_dev": (c_int, [c_vp, c_u32, c_u32, c_int, c_u64, c_u32, c_u64, c_u64, ctypes.POINTER(TensorLayer), c_int, c_int,
+                                                    c_vp, c_vp]),
+    "flashe_quantize_batch_tensors_dev": (c_int, [c_vp, ctypes.POINTER(TensorLayer), c_int, c_u64, c_int, c_int, c_vp, c_u64, c_vp]),
+    "flashe_store_layers_dev": (c_int, [c_vp, c_vp, c_u64, ctypes.POINTER(TensorLayer), c_int, c_u64, c_vp]),
     "flashe_mt19937_random_dev": (c_int, [c_vp, c_u32p, c_u32p, c_u64, c_vp]),
     "flashe_mt19937_jump_selfcheck": (c_int, []),
     "flashe_mt19937_plan": (c_int, [c_u32, c_u64, c_u32p, c_u32p, c_u32p]),

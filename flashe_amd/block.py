@@ -92,7 +92,8 @@ class FlasheClient(object):
     reference's method names, so `JZFWeights.encrypted(cipher)` / `.decrypted(cipher)`
     (jzf_weights.py:334-338) can be handed this object unchanged."""
 
-    def __init__(self, args, device=0):
+    def __init__(self, args, device=0, stream=None):
+        """stream (new): a framework's hipStream_t as an int -- the cipher's engine runs on it (FlasheCipher(stream=...))."""
         q = args['quantize']
         self.int_bits = q['int_bits']
         self.batch = q.get('batch')
@@ -108,11 +109,12 @@ class FlasheClient(object):
         self.shape_dict = None           # layer shapes of the flattened model (what the aggregator-side Client keeps, jzf_aggregator.py:648)
         self.fuse = True                 # False: quantize_encrypt / decrypt_unquantize run the reference's sequence call by call
         self._device = device
+        self._stream = stream
 
     def create_cipher(self, idx, num_clients, prp_seed):
         """What Guest/Host.create_cipher leave behind (:193-244, :287-326): a keyed cipher that knows its
         client index and, with precompute enabled, the masks of iteration 0."""
-        self.cipher = FlasheCipher(self.int_bits, device=self._device)
+        self.cipher = FlasheCipher(self.int_bits, device=self._device, stream=self._stream)
         self.cipher.idx = idx
         self.cipher.set_num_clients(num_clients)
         self.cipher.generate_prp_seed(prp_seed)
@@ -209,8 +211,12 @@ class FlasheClient(object):
         order = list(weights.walking_order)
         return not self.batch and len(order) > 1 and order[-1] == "zzz" and np.size(weights._weights["zzz"]) == 1
 
-    def quantize_encrypt(self, weights, device=True):
-        """What Client.secure_aggregate does between "begin encoding" and "end encryption" (jzf_aggregator.py:721-743):
+    def quantize_encrypt(self, weights, device=True, normalize=False):
+        """normalize (new): QuantizingClient.normalize first (`-= past_layer_mean_list[i]`, jzf_quantize.py:542-547).  Layers may also be
+        a framework's float DEVICE tensors (float32 / float64 / float16 / bfloat16, DLPack or __cuda_array_interface__), mixed with host
+        layers: they are read where they lie (see _quantize_encrypt_tensors), no layer byte crosses PCIe.
+
+        What Client.secure_aggregate does between "begin encoding" and "end encryption" (jzf_aggregator.py:721-743):
         `self.quantize(weights)` -> `flatten_weights` -> [sparse job: strip the trailing quantised zero] -> `weights.encrypted(self)`
         -> [re-append it] -- QuantizingClient.quantize (jzf_quantize.py:394-491), then ONE cipher.encrypt over the flattened model
         (jzf_weights.py:334-338 -> jzf_flashe_block.py:142-150), so that element j of the model is masked with PRF counter j whatever
@@ -230,7 +236,12 @@ class FlasheClient(object):
         from . import cipher as _cipher_mod
         from .engine import DeviceVector
         from .quantize import ACIQ, DEVICE_RNG_MIN, _loop_dtype
+        from . import interop
         q, c = self.quantizer, self.cipher
+        if any(interop.is_foreign(weights._weights[k]) for k in weights.walking_order):
+            return self._quantize_encrypt_tensors(weights, device, normalize)
+        if normalize:
+            self.normalize(weights)
         if q.layer_size_list is None:
             q.set_layer_size_list(weights)
         if not self._fusable(weights):
@@ -337,8 +348,13 @@ class FlasheClient(object):
         weights.walking_order = sorted(weights._weights.keys(), key=str)
         return weights
 
-    def decrypt_unquantize(self, weights):
-        """What Client.aggregate does between "begin decryption" and "end decoding" (jzf_aggregator.py:881-899): `weights.decrypted(self)`
+    def decrypt_unquantize(self, weights, out=None, unnormalize=False):
+        """out (new): {layer name: framework float device tensor (float64 / float32 / float16 / bfloat16) of the layer's shape} -- the
+        values are written there in place (see _decrypt_unquantize_tensors) and weights._weights[name] becomes out[name].  unnormalize
+        (new): QuantizingClient.unnormalize after it (jzf_quantize.py:549-564): the layer mean added back and the statistics of the next
+        round's alpha refreshed -- with `out`, on the device, bit-identical to np.mean / np.std of the float64 result.
+
+        What Client.aggregate does between "begin decryption" and "end decoding" (jzf_aggregator.py:881-899): `weights.decrypted(self)`
         (jzf_weights.py:334-335 -> _Client.decrypt) of the ONE flattened aggregate, `unflatten_weights` by `self.shape_dict`, then
         QuantizingClient.unquantize layer by layer (jzf_quantize.py:493-540) -- as ONE launch (flashe_decrypt_unquantize_model_dev): the
         aggregate -- a DeviceVector, uint64 limbs or object ints -- is decrypted with the prefixes `set_idx_list` left behind and comes
@@ -348,6 +364,10 @@ class FlasheClient(object):
         from . import cipher as _cipher_mod
         from .engine import DeviceVector
         q, c = self.quantizer, self.cipher
+        if out is not None:
+            return self._decrypt_unquantize_tensors(weights, out, unnormalize)
+        if unnormalize:
+            return self.unnormalize(self.decrypt_unquantize(weights))
         fus = (self.fuse and c.masks is None and c.prp_seed is not None and not c.next_iter_decrypt_prepared
                and hasattr(c.engine, "decrypt_unquantize_model_dev"))
         k0 = weights.walking_order[0]
@@ -434,6 +454,227 @@ class FlasheClient(object):
         out = dout.download(np.float64, n)
         weights._weights[k0] = out
         return self.unflatten_weights(weights)
+
+    # ---- a framework's device tensors either side of the client step (new; interop.py) ---------------------------------------
+    def _quantize_encrypt_tensors(self, weights, device, normalize):
+        """quantize_encrypt with framework device tensors among the layers: each foreign layer is read in place (its own dtype; a layer
+        that needs a conversion -- 16-bit, float32 quantised in float64, or normalised -- goes through one streaming pass into engine
+        scratch, flashe_quantize_encrypt_tensors_dev / flashe_quantize_batch_tensors_dev), host layers go up as in the host path.  Bit for
+        bit the host path on `t.cpu().numpy()` (float16 / bfloat16: `t.float().cpu().numpy()`), with `normalize()` first when asked."""
+        from . import cipher as _cipher_mod
+        from . import interop
+        from ._lib import TENSOR_BF16, TENSOR_F16, TENSOR_F32, TENSOR_F64, TENSOR_LOOP_F64, TENSOR_SHIFT, TENSOR_SHIFT_WIDE
+        from .engine import DeviceVector
+        from .quantize import ACIQ, DEVICE_RNG_MIN, _loop_dtype
+        q, c = self.quantizer, self.cipher
+        if "zzz" in weights._weights:
+            raise TypeError("framework tensors are not supported by the sparse job (the 'zzz' layer)")
+        if not self._fusable(weights):
+            raise TypeError("framework tensors need the fused client step (fuse=True, no precomputed encrypt masks, no location masks)")
+        eng = c.engine
+        codes = {"float32": TENSOR_F32, "float64": TENSOR_F64, "float16": TENSOR_F16, "bfloat16": TENSOR_BF16}
+        order = list(weights.walking_order)
+        layers = []                                   # (ForeignArray or host flat array, shape, NumPy dtype of its host copy)
+        for k in order:
+            v = weights._weights[k]
+            if interop.is_foreign(v):
+                fa = eng.foreign(v, what=f"layer {k!r}")
+                if fa.dtype not in codes:
+                    raise TypeError(f"layer {k!r}: unsupported dtype {fa.dtype} (float32, float64, float16 or bfloat16)")
+                layers.append((fa, fa.shape, np.dtype(np.float64 if fa.dtype == "float64" else np.float32)))
+            else:
+                a = np.asarray(v)
+                flat = np.ascontiguousarray(a).reshape(-1)
+                if flat.dtype not in (np.float32, np.float64):
+                    flat = flat.astype(np.float64)
+                layers.append((flat, a.shape, flat.dtype))
+        if q.layer_size_list is None:                 # set_layer_size_list (jzf_quantize.py:380-392) on the sizes the tensors report
+            q.layer_size_list = [int(np.prod(shape, dtype=np.int64)) for _x, shape, _d in layers]
+            for _ in q.layer_size_list:
+                q.past_layer_mean_list.append(q.expected_mean_for_first_round)
+                q.past_layer_std_list.append(q.expected_std_for_first_round)
+        aciq = ACIQ(q.element_bits)
+        alphas = []
+        for i, _size in enumerate(q.layer_size_list):
+            a = aciq.get_alpha_gaus_direct(q.past_layer_std_list[i])
+            alphas.append(0.1 if a == 0 else a)
+        q.r_max_list, q.alpha_list = [], []
+        c.set_idx_list(mode="encrypt")
+        scheme = 1 if c.masking_scheme == "double" else 0
+        host_off, nbytes = {}, 0
+        for li, (x, _shape, _dt) in enumerate(layers):
+            if isinstance(x, np.ndarray):
+                host_off[li] = nbytes
+                nbytes += (x.nbytes + 15) & ~15
+        xbuf = eng.alloc(max(nbytes, 16)) if host_off else None
+        for li, off in host_off.items():
+            xbuf.upload_at(off, layers[li][0])
+        table, sizes, n, keep = [], [], 0, []
+        for li, (x, shape, hdt) in enumerate(layers):
+            alpha = alphas[li]
+            q.r_max_list.append(alpha * q.num_clients)
+            q.alpha_list.append(alpha)
+            size = int(np.prod(shape, dtype=np.int64))
+            flags, shift = 0, 0.0
+            if hdt != np.float64 and _loop_dtype(hdt, alpha) == np.float64:
+                flags |= TENSOR_LOOP_F64
+            if normalize:                             # QuantizingClient._shift(layer, -mean): the same wide / narrow rule
+                shift = -q.past_layer_mean_list[li]
+                flags |= TENSOR_SHIFT
+                if hdt == np.float32 and _loop_dtype(hdt, shift) == np.float64:
+                    flags |= TENSOR_SHIFT_WIDE
+            if isinstance(x, np.ndarray):
+                ptr, code = xbuf.ptr + host_off[li], TENSOR_F64 if hdt == np.float64 else TENSOR_F32
+            else:
+                ptr, code = x.ptr, codes[x.dtype]
+                keep.append(x.keep)
+            table.append((n, ptr, alpha, float(shift), code, flags))
+            sizes.append(size)
+            n += size
+        dev_rng = os.environ.get("FLASHE_DEVICE_RNG", "1") != "0" and np.random.get_state()[0] == "MT19937"
+        shape_dict = {k: shape for k, (_x, shape, _d) in zip(order, layers)}
+        if self.batch:
+            factor = int(np.ceil(np.log2(q.num_clients)))
+            field_bits = q.element_bits + factor
+            bs = self.int_bits // field_bits
+            q.shape_list = [shape_dict[k] for k in order]
+            n_elems = sum((s_ + bs - 1) // bs for s_ in sizes)
+            du = (eng.numpy_random_dev(n) if dev_rng and n >= DEVICE_RNG_MIN else eng.upload(np.random.random(n))) if n else eng.alloc(16)
+            pt = eng.alloc_vec(max(n_elems, 1))
+            eng.quantize_batch_tensors_dev(table, n, q.element_bits, field_bits, du, n_elems, pt)
+            ct = DeviceVector(eng, n_elems)
+            if n_elems:
+                eng.encrypt_dev(c.iter_index, c.idx, scheme, n_elems, _cipher_mod.N_JOBS, pt, eng.limbs, ct.buf)
+            self.shape_dict = {k: ((s_ + bs - 1) // bs,) for k, s_ in zip(order, sizes)}
+        else:
+            ct = DeviceVector(eng, n)
+            at = 0
+            while at < len(order):                    # the draws in runs of whole layers, as in quantize_encrypt
+                end, tot = at, 0
+                while end < len(order) and (end == at or tot + sizes[end] <= _RNG_RUN_MAX):
+                    tot += sizes[end]
+                    end += 1
+                if tot:
+                    du = eng.numpy_random_dev(tot) if dev_rng and tot >= DEVICE_RNG_MIN else eng.upload(np.random.random(tot))
+                    first = table[at][0]
+                    eng.quantize_encrypt_tensors_dev(c.iter_index, c.idx, scheme, n, _cipher_mod.N_JOBS, first, tot, table, q.element_bits, du,
+                                                     ct.ptr + first * eng.limbs * 8)
+                at = end
+            self.shape_dict = shape_dict
+        eng.hold(keep)
+        for k in order:
+            del weights._weights[k]
+        if order:
+            weights._weights[order[0]] = ct.mark_ready() if device else ct.to_host()
+        weights.walking_order = sorted(weights._weights.keys(), key=str)
+        return weights
+
+    def _decrypt_unquantize_tensors(self, weights, out, unnormalize):
+        """decrypt_unquantize into the caller's tensors: the fused back end writes the flat float64 model into engine scratch, one
+        streaming pass (flashe_store_layers_dev) adds the layer means back (unnormalize) and stores every layer in its tensor's dtype --
+        float64 -> float32 -> 16 bits, each step round to nearest even -- and, with unnormalize, sums every layer the way np.mean /
+        np.std do, so past_layer_mean_list / past_layer_std_list get the host path's np.float64 values.  Only those 16 bytes per layer come
+        back to the host.  Own-stream engines synchronise before returning."""
+        from . import cipher as _cipher_mod
+        from . import interop
+        from ._lib import TENSOR_BF16, TENSOR_F16, TENSOR_F32, TENSOR_F64, TENSOR_SHIFT
+        from .engine import DeviceVector
+        q, c = self.quantizer, self.cipher
+        if c.masks is not None or "zzz" in weights._weights:
+            raise TypeError("out= is not supported by the sparse job")
+        if not (self.fuse and c.prp_seed is not None and not c.next_iter_decrypt_prepared):
+            raise TypeError("out= needs the fused client step (fuse=True, no precomputed decrypt masks)")
+        if self.shape_dict is None:
+            raise ValueError("decrypt_unquantize(out=...) needs the layer shapes a quantize_encrypt left behind (shape_dict)")
+        eng = c.engine
+        codes = {"float32": TENSOR_F32, "float64": TENSOR_F64, "float16": TENSOR_F16, "bfloat16": TENSOR_BF16}
+        names = list(self.shape_dict)
+        shapes = list(q.shape_list) if self.batch else [self.shape_dict[k] for k in names]
+        missing = [k for k in names if k not in out]
+        if missing:
+            raise KeyError(f"out has no tensor for layer(s) {missing}")
+        fas = []
+        for k, shape in zip(names, shapes):
+            if not interop.is_foreign(out[k]):
+                raise TypeError(f"out[{k!r}]: expected a framework device tensor, got {type(out[k]).__name__}")
+            fa = eng.foreign(out[k], writable=True, what=f"out[{k!r}]")
+            if fa.dtype not in codes:
+                raise TypeError(f"out[{k!r}]: unsupported dtype {fa.dtype} (float64, float32, float16 or bfloat16)")
+            if tuple(fa.shape) != tuple(shape):
+                raise ValueError(f"out[{k!r}]: expected shape {tuple(shape)}, got {tuple(fa.shape)}")
+            fas.append(fa)
+        if c.masking_scheme == "double":
+            add_idx = [c._idx_of(p) for p in (c.index_prefix_for_add or [])]
+            minus_idx = [c._idx_of(p) for p in (c.index_prefix_for_minus or [])]
+            if not add_idx and not minus_idx:
+                raise KeyError('add')
+        else:
+            add_idx, minus_idx = [], [c._idx_of(p) for p in c.index_prefix_for_minus]
+        k0 = weights.walking_order[0]
+        v = weights._weights[k0]
+        keep = [fa.keep for fa in fas]
+        if interop.is_foreign(v):                                 # (the aggregate as a framework integer tensor: read in place)
+            v, kv = c._foreign_vec(eng, v, "aggregate")
+            keep.append(kv)
+        elif not isinstance(v, DeviceVector):
+            v = np.asarray(v)
+            if v.dtype == object:
+                v = v.reshape(-1)
+        dv, _kind = c._on_device(v, full_width=True)
+        dv = c._as_wide(dv)
+        n = len(dv)
+        sizes = [int(np.prod(shape, dtype=np.int64)) for shape in shapes]
+        n_values = sum(sizes)
+        if self.batch:
+            factor = int(np.ceil(np.log2(q.num_clients)))
+            field_bits = q.element_bits + factor
+            bs = self.int_bits // field_bits
+            if sum((s_ + bs - 1) // bs for s_ in sizes) != n:
+                raise ValueError(f"the aggregate has {n} elements, the batched layers describe {sum((s_ + bs - 1) // bs for s_ in sizes)}")
+            dec = eng.alloc_vec(max(n, 1))
+            if n:
+                eng.decrypt_dev(c.iter_index, add_idx, minus_idx, n, _cipher_mod.N_JOBS, dv.buf, dec)
+            dout = eng.alloc(max(8 * n_values, 16))
+            eng.unbatch_unquantize_model_dev([(s_, None, q.alpha_list[li], False) for li, s_ in enumerate(sizes)], q.element_bits, field_bits,
+                                             q.num_clients, dec, n, dout)
+        else:
+            if n_values > n:
+                raise ValueError(f"the aggregate has {n} elements, shape_dict describes {n_values}")
+            table, at = [], 0
+            for li, size in enumerate(sizes):
+                table.append((at, None, q.alpha_list[li], False))
+                at += size
+            dout = eng.alloc(max(8 * n, 16))
+            if n:
+                eng.decrypt_unquantize_model_dev(c.iter_index, add_idx, minus_idx, n, _cipher_mod.N_JOBS, 0, n, dv.buf, table, q.element_bits,
+                                                 q.num_clients, dout)
+        layers, at = [], 0
+        for li, (fa, size) in enumerate(zip(fas, sizes)):
+            shift = float(q.past_layer_mean_list[li]) if unnormalize else 0.0
+            layers.append((at, fa.ptr, 1.0, shift, codes[fa.dtype], TENSOR_SHIFT if unnormalize else 0))
+            at += size
+        stats = eng.alloc(max(16 * len(layers), 16)) if unnormalize else None
+        if n_values:
+            eng.store_layers_dev(dout, n_values, layers, block=np.getbufsize() if unnormalize else 0, stats=stats)
+        eng.hold(keep + [dout])
+        if unnormalize:
+            st = stats.download(np.float64, 2 * len(layers))          # (synchronises: 16 bytes per layer)
+            for li, size in enumerate(sizes):
+                if size:
+                    # np.mean = S / n, np.std = sqrt(S2 / n): the same float64 operations on NumPy's own sums
+                    q.past_layer_mean_list[li] = np.float64(st[2 * li]) / size
+                    q.past_layer_std_list[li] = np.sqrt(np.float64(st[2 * li + 1]) / size)
+                else:
+                    e = np.zeros(0, dtype=np.float64)
+                    q.past_layer_mean_list[li], q.past_layer_std_list[li] = np.mean(e), np.std(e)
+        elif not eng.shared_stream:
+            eng.sync()
+        for k in list(weights._weights):
+            del weights._weights[k]
+        for k in names:
+            weights._weights[k] = out[k]
+        weights.walking_order = sorted(weights._weights.keys(), key=str)
+        return weights
 
     def prepare_encrypt(self):
         if self.precompute:

@@ -197,7 +197,9 @@ class FlasheCipher(object):
 
     _engine_cls = Engine      # the device context type (the HIP engine; tests may inject a double)
 
-    def __init__(self, int_bits, mask="double", device=0):
+    def __init__(self, int_bits, mask="double", device=0, stream=None):
+        """stream (new): a framework's hipStream_t as an int (e.g. torch.cuda.current_stream().cuda_stream): the engine runs ON it, so
+        every call is stream-ordered with the framework's own work.  None: the engine has a stream of its own (see encrypt's `out`)."""
         if 128 // int_bits < 1:          # the reference divides by merge_size = 128 // int_bits
             raise ZeroDivisionError("integer division or modulo by zero")
         self.int_bits = int_bits
@@ -215,6 +217,7 @@ class FlasheCipher(object):
         self.next_iter_decrypt_prepared_idx = {}
 
         self._device = device
+        self._stream = stream
         self._engine = None
         self._key = None
         self._ctx_holds = 0           # which precompute caches the engine's ctx may hold (PREPARED_ENCRYPT | PREPARED_DECRYPT bits)
@@ -249,7 +252,8 @@ class FlasheCipher(object):
         # AESCipher.generate_key (jzf_aes.py:21-28): the AES-256 key is the low 256 bits, big-endian
         self._key = (int.from_bytes(seed, 'big') & (256 ** 32 - 1)).to_bytes(32, 'big')
         if self._engine is None:
-            self._engine = self._engine_cls(self._key, self.int_bits, device=self._device)
+            kw = {"stream": self._stream} if self._stream else {}
+            self._engine = self._engine_cls(self._key, self.int_bits, device=self._device, **kw)
         else:
             self._engine.set_key(self._key)
 
@@ -510,14 +514,20 @@ class FlasheCipher(object):
         if LOGGER.isEnabledFor(logging.INFO):
             LOGGER.info("end %s (scheme=%s iter=%s n=%d seconds=%.6f)", name, self.masking_scheme, self.iter_index, n, time.perf_counter() - t0)
 
-    def encrypt(self, plaintext, device=None):                           # jzf_flashe.py:490-504
-        """device: None = the result has the form of the input (ndarray -> ndarray, DeviceVector -> DeviceVector);
-        True = keep the ciphertext in HBM and return a DeviceVector; False = return a host array."""
+    def encrypt(self, plaintext, device=None, out=None):                 # jzf_flashe.py:490-504
+        """device: None = the result has the form of the input (ndarray -> ndarray, DeviceVector or framework tensor -> DeviceVector);
+        True = keep the ciphertext in HBM and return a DeviceVector; False = return a host array.
+        plaintext may also be a framework's integer DEVICE tensor (DLPack / __cuda_array_interface__: uint64 / int64 [n] or [n, L], and
+        uint32 / int32 [n] at int_bits <= 32), read in place.  out (new): a framework integer device tensor of the result's shape; the
+        ciphertext is written there and `out` is returned.  Without a `stream` the engine synchronises before returning a foreign out."""
         if self.prp_seed is not None:
             if self.masking_scheme == "double":
                 self.set_idx_list(mode="encrypt")
             else:
                 self.set_idx_list_single(mode="encrypt")
+            if self._foreign_call(plaintext, out):
+                return self._foreign_op("encryption", [plaintext], out, device,
+                                        lambda v, d: self._encrypt_double(v, d) if self.masking_scheme == "double" else self._encrypt_single(v, d))
             if not isinstance(plaintext, (np.ndarray, DeviceVector)):
                 return None
             self._reconcile_prepared()
@@ -526,6 +536,57 @@ class FlasheCipher(object):
             self._phase("encryption", len(plaintext), t0)
             return out
         return None
+
+    # ---- framework device tensors (new; interop.py) ----
+    @staticmethod
+    def _foreign_call(value, out):
+        from . import interop
+        return out is not None or interop.is_foreign(value)
+
+    def _foreign_vec(self, eng, obj, what):
+        """A framework integer device tensor as a DeviceVector VIEW of its memory (no copy) and the object that keeps it alive."""
+        fa = eng.foreign(obj, what=what)
+        return _foreign_view(eng, fa, what), fa.keep
+
+    def _foreign_out(self, eng, obj):
+        """The caller's `out` tensor, checked (device, dtype, contiguity, writable) before anything is launched."""
+        fa = eng.foreign(obj, writable=True, what="out")
+        if fa.dtype not in ("uint64", "int64", "uint32", "int32"):
+            raise TypeError(f"out: unsupported dtype {fa.dtype} (uint64 / int64, or uint32 / int32 at int_bits <= 32)")
+        if fa.itemsize == 4 and self.int_bits > 32:
+            raise TypeError(f"out: a 32-bit integer tensor cannot hold {self.int_bits}-bit ciphertexts")
+        return fa
+
+    def _foreign_op(self, name, values, out, device, op, n_of=None):
+        """One encrypt / decrypt with a framework tensor as the operand and / or the destination."""
+        eng = self._engine
+        if self.masks is not None:
+            raise TypeError("framework tensors are not supported by the sparse job (location masks set on the cipher)")
+        if self.next_iter_encrypt_prepared or self.next_iter_decrypt_prepared:
+            raise TypeError("framework tensors are not supported with precomputed masks (prepare_encrypt / prepare_decrypt)")
+        keep, args = [], []
+        for v in values:
+            from . import interop
+            if interop.is_foreign(v):
+                v, k = self._foreign_vec(eng, v, "operand")
+                keep.append(k)
+            args.append(v)
+        fo = self._foreign_out(eng, out) if out is not None else None
+        n = len(args[0])
+        if fo is not None:
+            _check_out_shape(fo, n, eng.limbs)
+        self._reconcile_prepared()
+        t0 = self._begin(name)
+        res = op(args[0], True if (fo is not None or device is None) else device)
+        self._phase(name, n, t0)
+        if fo is None:
+            eng.hold(keep)
+            return res
+        _write_out(eng, res, fo)
+        eng.hold(keep + [fo.keep, res])
+        if not eng.shared_stream:
+            eng.sync()
+        return out
 
     # ------------------------------------------------------------------ decrypt
     def _decrypt_single(self, value, device=None):                       # jzf_flashe.py:506-535
@@ -618,9 +679,12 @@ class FlasheCipher(object):
                     del d[k]
         return res
 
-    def decrypt(self, ciphertext, device=None):                          # jzf_flashe.py:584-594
-        """device: as for encrypt()."""
+    def decrypt(self, ciphertext, device=None, out=None):                # jzf_flashe.py:584-594
+        """device, out: as for encrypt() (framework integer device tensors in and out)."""
         if self.prp_seed is not None:
+            if self._foreign_call(ciphertext, out):
+                return self._foreign_op("decryption", [ciphertext], out, device,
+                                        lambda v, d: self._decrypt_double(v, d) if self.masking_scheme == "double" else self._decrypt_single(v, d))
             if not isinstance(ciphertext, (np.ndarray, DeviceVector)):
                 return None
             self._reconcile_prepared()
@@ -653,13 +717,42 @@ class FlasheCipher(object):
         self.next_iter_decrypt_prepared_idx['minus'] = [0]
 
     # ------------------------------------------------------------------ arbiter reduce (new)
-    def aggregate(self, ciphertexts, packed=False, device=None):
+    def aggregate(self, ciphertexts, packed=False, device=None, out=None):
         """Server-side reduce of a list of ciphertext vectors.  The reference has no such method;
         this equals Arbiter.aggregate_model's flashe branch: element-wise
         (jzf_aggregator.py:424-430) or, with packed=True, on the bit-packed integers
-        (jzf_aggregator.py:406-419), returned unpacked.  Operands may be DeviceVectors (they stay where they are);
-        device: as for encrypt() -- None returns a DeviceVector iff the first operand is one."""
-        eng = self._engine or self._engine_cls(bytes(32), self.int_bits, device=self._device)
+        (jzf_aggregator.py:406-419), returned unpacked.  Operands may be DeviceVectors (they stay where they are) or framework integer
+        device tensors (read in place); device: as for encrypt() -- None returns a DeviceVector iff the first operand is one (or a
+        framework tensor).  out (new, element-wise only): a framework integer device tensor that receives the sum; `out` is returned."""
+        kw = {"stream": self._stream} if self._stream else {}
+        eng = self._engine or self._engine_cls(bytes(32), self.int_bits, device=self._device, **kw)
+        from . import interop
+        if out is not None or any(interop.is_foreign(c) for c in ciphertexts):
+            if out is not None and packed:
+                raise TypeError("out= is not supported for packed=True aggregation")
+            if len(ciphertexts) == 0:
+                raise TypeError("reduce() of empty sequence with no initial value")
+            keep, ops = [], []
+            for c in ciphertexts:
+                if interop.is_foreign(c):
+                    c, k = self._foreign_vec(eng, c, "operand")
+                    keep.append(k)
+                ops.append(c)
+            fo = self._foreign_out(eng, out) if out is not None else None
+            if fo is not None:
+                _check_out_shape(fo, len(ops[0]), eng.limbs)
+            t0 = self._begin("aggregation")
+            res = aggregate(ops, self.int_bits, packed=packed, device=self._device, _engine=eng,
+                            keep_on_device=True if (fo is not None or device is None) else device)
+            self._phase("aggregation", len(res), t0)
+            if fo is None:
+                eng.hold(keep)
+                return res
+            _write_out(eng, res, fo)
+            eng.hold(keep + [fo.keep, res])
+            if not eng.shared_stream:
+                eng.sync()
+            return out
         t0 = self._begin("aggregation")
         out = aggregate(ciphertexts, self.int_bits, packed=packed, device=self._device, _engine=eng, keep_on_device=device)
         self._phase("aggregation", len(out), t0)
@@ -744,3 +837,58 @@ def aggregate(ciphertexts, int_bits, packed=False, device=0, _engine=None, keep_
     if want_dev:
         return out.mark_ready()
     return _from_limbs(out.to_host(), kind)
+
+
+# ------------------------------------------------------------------------------ framework device tensors (new)
+class _ForeignBuf(_engine.DeviceBuffer):
+    """Device memory the engine does not own (a framework tensor): a DeviceBuffer that never frees."""
+
+    def __init__(self, engine, ptr, nbytes):
+        self.engine, self.ptr, self.nbytes = engine, int(ptr), int(nbytes)
+
+    def free(self):
+        self.ptr = None
+
+
+def _foreign_view(eng, fa, what):
+    """interop.ForeignArray of an integer tensor -> DeviceVector over its memory: uint64 / int64 [n] or [n, L] (the same bits), uint32 /
+    int32 [n] in the compact layout at int_bits <= 32."""
+    shape = fa.shape
+    if fa.dtype in ("uint64", "int64"):
+        if len(shape) == 1:
+            limbs = 1
+        elif len(shape) == 2 and shape[1] in (1, eng.limbs):
+            limbs = shape[1]
+        else:
+            raise ValueError(f"{what}: a 64-bit integer tensor must be [n] or [n, {eng.limbs}], got {list(shape)}")
+        return DeviceVector(eng, shape[0], limbs, buf=_ForeignBuf(eng, fa.ptr, fa.nbytes))
+    if fa.dtype in ("uint32", "int32"):
+        if eng.int_bits > 32:
+            raise TypeError(f"{what}: a 32-bit integer tensor holds int_bits <= 32 values only (this cipher: {eng.int_bits})")
+        if len(shape) != 1:
+            raise ValueError(f"{what}: a 32-bit integer tensor must be [n], got {list(shape)}")
+        return DeviceVector(eng, shape[0], 1, buf=_ForeignBuf(eng, fa.ptr, fa.nbytes), elem_bytes=4)
+    raise TypeError(f"{what}: unsupported dtype {fa.dtype} (uint64 / int64 [n] or [n, L]; uint32 / int32 [n] at int_bits <= 32)")
+
+
+def _check_out_shape(fo, n, limbs):
+    ok = (fo.itemsize == 4 and fo.shape == (n,)) or (fo.itemsize == 8 and (fo.shape in ((n,), (n, 1)) if limbs == 1 else fo.shape == (n, limbs)))
+    if not ok:
+        want = f"[{n}]" if limbs == 1 else f"[{n}, {limbs}]"
+        raise ValueError(f"out: expected shape {want} for {n} ciphertext elements, got {list(fo.shape)}")
+
+
+def _write_out(eng, res, fo):
+    """The result DeviceVector into the caller's tensor, converting between the compact and the one-limb layout on the device."""
+    n = len(res)
+    if n == 0:
+        return
+    if fo.itemsize == 4:
+        if res.compact:
+            eng._check(eng._lib.flashe_memcpy_d2d(eng._h, fo.ptr, res.ptr, 4 * n))
+        else:
+            eng.narrow_u32_dev(n, res.buf, fo.ptr)
+    elif res.compact:
+        eng.widen_u32_dev(n, res.buf, fo.ptr)
+    else:
+        eng._check(eng._lib.flashe_memcpy_d2d(eng._h, fo.ptr, res.ptr, 8 * n * res.limbs))

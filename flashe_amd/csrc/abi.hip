@@ -425,8 +425,10 @@ int flashe_ctx_destroy(flashe_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     if (ctx->env.stream) (void)hipStreamSynchronize(ctx->env.stream);
     for (flashe_ctx::Buf *b : {&ctx->summaries, &ctx->stream_tmp, &ctx->acc_tmp[0], &ctx->acc_tmp[1], &ctx->sp_ws, &ctx->bounds, &ctx->mt_ws, &ctx->codec_tab, &ctx->prep_enc.add,
-                               &ctx->prep_enc.minus, &ctx->prep_dec.add, &ctx->prep_dec.minus, &ctx->chain_dmask.d})
+                               &ctx->prep_enc.minus, &ctx->prep_dec.add, &ctx->prep_dec.minus, &ctx->chain_dmask.d, &ctx->tensor_ws, &ctx->tensor_tab,
+                               &ctx->stat_ws})
         if (b->p) (void)hipFree(b->p);
+    if (ctx->ev_foreign) (void)hipEventDestroy(ctx->ev_foreign);
     if (ctx->staging) { ctx->staging->destroy(); delete ctx->staging; ctx->staging = nullptr; }      // staging blocks held plaintexts and ciphertexts (wiped)
     if (ctx->te0_dev) (void)hipFree(ctx->te0_dev);
     // the expanded AES-256 key leaves neither HBM nor host memory behind
@@ -1386,6 +1388,208 @@ int flashe_mean_std_dev(flashe_ctx *ctx, uint64_t n, const void *x_dev, int x_is
     if ((rc = total(mu, 2, &s2))) return rc;
     *mean = mu;
     *stddev = sqrt(s2 / static_cast<double>(n));
+    return FLASHE_OK;
+}
+
+// ---- caller-owned tensors either side of the model-wide codec (tensors.hip) ----
+int flashe_ctx_stream(const flashe_ctx *ctx, void **stream)
+{
+    if (!ctx || !stream) return FLASHE_EINVAL;
+    *stream = ctx->env.stream;
+    return FLASHE_OK;
+}
+
+int flashe_stream_wait_stream(flashe_ctx *ctx, void *other)
+{
+    CHECK_CTX(ctx);
+    if (static_cast<hipStream_t>(other) == ctx->env.stream) return FLASHE_OK;
+    if (ctx->capturing) return fail(ctx, FLASHE_EINVAL, "flashe_stream_wait_stream cannot be captured into a graph");
+    if (!ctx->ev_foreign) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_foreign, hipEventDisableTiming));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_foreign, static_cast<hipStream_t>(other)));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->env.stream, ctx->ev_foreign, 0));
+    return FLASHE_OK;
+}
+
+int flashe_event_query(flashe_ctx *ctx, void *event, int *done)
+{
+    CHECK_CTX(ctx);
+    if (!event || !done) return fail(ctx, FLASHE_EINVAL, "null argument");
+    const hipError_t e = hipEventQuery(static_cast<hipEvent_t>(event));
+    if (e == hipErrorNotReady) { (void)hipGetLastError(); *done = 0; return FLASHE_OK; }
+    HIP_TRY(ctx, e);
+    *done = 1;
+    return FLASHE_OK;
+}
+
+static int tensor_elem_bytes(int32_t dtype)
+{
+    return dtype == FLASHE_TENSOR_F64 ? 8 : dtype == FLASHE_TENSOR_F32 ? 4 : (dtype == FLASHE_TENSOR_F16 || dtype == FLASHE_TENSOR_BF16) ? 2 : 0;
+}
+
+// the table's shape, dtypes, flags and pointers (nothing is launched before every layer passed)
+static int check_tensor_layers(flashe_ctx *ctx, uint64_t n, const flashe_tensor_layer *layers, int n_layers)
+{
+    if (n_layers < 1 || !layers) return fail(ctx, FLASHE_EINVAL, "the layer table needs at least one entry");
+    if (layers[0].start != 0) return fail(ctx, FLASHE_EINVAL, "layers[0].start must be 0");
+    if (ctx->capturing) return fail(ctx, FLASHE_EINVAL, "the tensor codec calls stage their layer table per call and cannot be captured into a graph");
+    for (int l = 0; l < n_layers; l++) {
+        const flashe_tensor_layer &y = layers[l];
+        const uint64_t end = l + 1 < n_layers ? layers[l + 1].start : n;
+        if (y.start > end || end > n) return fail(ctx, FLASHE_EINVAL, "layer %d: starts must ascend and stay within n", l);
+        const int es = tensor_elem_bytes(y.dtype);
+        if (!es) return fail(ctx, FLASHE_EINVAL, "layer %d: unknown dtype %d", l, static_cast<int>(y.dtype));
+        if (y.flags & ~(FLASHE_TENSOR_SHIFT | FLASHE_TENSOR_SHIFT_WIDE | FLASHE_TENSOR_LOOP_F64))
+            return fail(ctx, FLASHE_EINVAL, "layer %d: unknown flags 0x%x", l, static_cast<unsigned>(y.flags));
+        if (y.start == end) continue;
+        if (!y.ptr) return fail(ctx, FLASHE_EINVAL, "layer %d: null ptr", l);
+        if (reinterpret_cast<uintptr_t>(y.ptr) % static_cast<uintptr_t>(es)) return fail(ctx, FLASHE_EINVAL, "layer %d: ptr is not aligned to its element size", l);
+    }
+    return FLASHE_OK;
+}
+
+extern "C++" template <class T> static int upload_tab(flashe_ctx *ctx, flashe_ctx::Buf &b, const std::vector<T> &tab, const T **tab_dev)
+{
+    int rc = ensure(ctx, b, std::max<size_t>(tab.size(), 1) * sizeof(T));
+    if (rc) return rc;
+    if (!tab.empty()) {
+        HIP_TRY(ctx, hipMemcpyAsync(b.p, tab.data(), tab.size() * sizeof(T), hipMemcpyHostToDevice, ctx->env.stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->env.stream));
+    }
+    *tab_dev = static_cast<const T *>(b.p);
+    return FLASHE_OK;
+}
+
+// the compute-type values of every layer of [first, first + count): x[l] = where the codec reads layer l, f64[l] = its loop dtype
+static int stage_tensor_front(flashe_ctx *ctx, uint64_t n, const flashe_tensor_layer *layers, int n_layers, uint64_t first, uint64_t count,
+                              std::vector<const void *> &x, std::vector<int> &f64)
+{
+    x.assign(static_cast<size_t>(n_layers), nullptr);
+    f64.assign(static_cast<size_t>(n_layers), 0);
+    std::vector<TensorStage> st;
+    std::vector<size_t> at;
+    std::vector<int> which;
+    uint64_t total = 0;
+    size_t bytes = 0;
+    for (int l = 0; l < n_layers; l++) {
+        const flashe_tensor_layer &y = layers[l];
+        const uint64_t end = l + 1 < n_layers ? layers[l + 1].start : n;
+        const bool loop64 = y.dtype == FLASHE_TENSOR_F64 || (y.flags & FLASHE_TENSOR_LOOP_F64);
+        f64[l] = loop64 ? 1 : 0;
+        x[l] = y.ptr;
+        const bool touched = y.start < first + count && end > first;
+        const bool direct = !(y.flags & FLASHE_TENSOR_SHIFT) && (y.dtype == FLASHE_TENSOR_F64 || (y.dtype == FLASHE_TENSOR_F32 && !loop64));
+        if (y.start == end || !touched || direct) continue;
+        bytes = (bytes + 15) & ~static_cast<size_t>(15);
+        st.push_back(TensorStage{total, y.ptr, nullptr, y.shift, y.dtype, y.flags | (loop64 ? kTensorLoopF64 : 0)});
+        at.push_back(bytes);
+        which.push_back(l);
+        total += end - y.start;
+        bytes += static_cast<size_t>(end - y.start) * (loop64 ? 8 : 4);
+    }
+    if (st.empty()) return FLASHE_OK;
+    int rc = ensure(ctx, ctx->tensor_ws, bytes);
+    if (rc) return rc;
+    for (size_t i = 0; i < st.size(); i++) {
+        st[i].dst = static_cast<char *>(ctx->tensor_ws.p) + at[i];
+        x[which[i]] = st[i].dst;
+    }
+    const TensorStage *tab = nullptr;
+    if ((rc = upload_tab(ctx, ctx->tensor_tab, st, &tab))) return rc;
+    HIP_TRY(ctx, launch_stage_layers(ctx->env, tab, static_cast<int>(st.size()), total));
+    return FLASHE_OK;
+}
+
+int flashe_quantize_encrypt_tensors_dev(flashe_ctx *ctx, uint32_t iter, uint32_t idx, int scheme, uint64_t n, uint32_t n_jobs, uint64_t first,
+                                        uint64_t count, const flashe_tensor_layer *layers, int n_layers, int element_bits, const double *u_dev,
+                                        uint64_t *ct_dev)
+{
+    CHECK_CTX(ctx);
+    // the checks of flashe_quantize_encrypt_model_dev that do not need the table, before anything is launched
+    if (int rc = check_scheme(ctx, scheme)) return rc;
+    if (count && (!u_dev || !ct_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
+    if (element_bits < 1 || element_bits > 62 || element_bits > ctx->int_bits)
+        return fail(ctx, FLASHE_EINVAL, "element_bits must be in [1, min(62, int_bits)], got %d", element_bits);
+    int rc = check_prf_args(ctx, 1, scheme, n_jobs, ct_dev, nullptr, 0);
+    if (rc || (rc = check_range(ctx, n, first, count)) || (rc = check_tensor_layers(ctx, n, layers, n_layers))) return rc;
+    if ((rc = check_double_idx(ctx, scheme, &idx, 1))) return rc;
+    for (int l = 0; l < n_layers; l++)
+        if (!(layers[l].alpha > 0) && (l + 1 < n_layers ? layers[l + 1].start : n) > layers[l].start)
+            return fail(ctx, FLASHE_EINVAL, "layer %d: alpha must be positive", l);
+    std::vector<const void *> x;
+    std::vector<int> f64;
+    if ((rc = stage_tensor_front(ctx, n, layers, n_layers, first, count, x, f64))) return rc;
+    std::vector<flashe_codec_layer> cl(static_cast<size_t>(n_layers));
+    for (int l = 0; l < n_layers; l++) cl[l] = flashe_codec_layer{layers[l].start, x[l], layers[l].alpha, f64[l], 0};
+    return flashe_quantize_encrypt_model_dev(ctx, iter, idx, scheme, n, n_jobs, first, count, cl.data(), n_layers, element_bits, u_dev, ct_dev);
+}
+
+int flashe_quantize_batch_tensors_dev(flashe_ctx *ctx, const flashe_tensor_layer *layers, int n_layers, uint64_t n_values, int element_bits,
+                                      int field_bits, const double *u_dev, uint64_t n_elems, uint64_t *out_dev)
+{
+    CHECK_CTX(ctx);
+    int rc = check_tensor_layers(ctx, n_values, layers, n_layers);
+    if (rc) return rc;
+    if (element_bits < 1 || element_bits > 62 || field_bits < element_bits || field_bits > ctx->int_bits)
+        return fail(ctx, FLASHE_EINVAL, "need 1 <= element_bits <= field_bits <= int_bits (element_bits <= 62)");
+    const uint64_t bs = static_cast<uint64_t>(ctx->int_bits / field_bits);
+    uint64_t e = 0;
+    for (int l = 0; l < n_layers; l++) {
+        const uint64_t size = (l + 1 < n_layers ? layers[l + 1].start : n_values) - layers[l].start;
+        if (size && !(layers[l].alpha > 0)) return fail(ctx, FLASHE_EINVAL, "layer %d: alpha must be positive", l);
+        e += (size + bs - 1) / bs;
+    }
+    if (e != n_elems) return fail(ctx, FLASHE_EINVAL, "the layers batch into %llu elements, n_elems says %llu", static_cast<unsigned long long>(e),
+                                  static_cast<unsigned long long>(n_elems));
+    if (n_elems && (!u_dev || !out_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
+    if ((ctx->limbs == 2 && !aligned16(out_dev)) || (reinterpret_cast<uintptr_t>(out_dev) & 7u) || (reinterpret_cast<uintptr_t>(u_dev) & 7u))
+        return fail(ctx, FLASHE_EINVAL, "misaligned vector");
+    std::vector<const void *> x;
+    std::vector<int> f64;
+    if ((rc = stage_tensor_front(ctx, n_values, layers, n_layers, 0, n_values, x, f64))) return rc;
+    std::vector<flashe_batch_layer> bl(static_cast<size_t>(n_layers));
+    for (int l = 0; l < n_layers; l++)
+        bl[l] = flashe_batch_layer{(l + 1 < n_layers ? layers[l + 1].start : n_values) - layers[l].start, x[l], layers[l].alpha, f64[l], 0};
+    return flashe_quantize_batch_model_dev(ctx, bl.data(), n_layers, element_bits, field_bits, u_dev, n_elems, out_dev);
+}
+
+int flashe_store_layers_dev(flashe_ctx *ctx, const double *in_dev, uint64_t n, const flashe_tensor_layer *layers, int n_layers, uint64_t block,
+                            double *stats_dev)
+{
+    CHECK_CTX(ctx);
+    int rc = check_tensor_layers(ctx, n, layers, n_layers);
+    if (rc) return rc;
+    if (n && (!in_dev || (reinterpret_cast<uintptr_t>(in_dev) & 7u))) return fail(ctx, FLASHE_EINVAL, "null or misaligned in_dev");
+    if (stats_dev && (block < 1 || block > 16384)) return fail(ctx, FLASHE_EINVAL, "block must be in [1, 16384], got %llu", static_cast<unsigned long long>(block));
+    if (reinterpret_cast<uintptr_t>(stats_dev) & 7u) return fail(ctx, FLASHE_EINVAL, "misaligned stats_dev");
+    std::vector<TensorStore> st;
+    std::vector<StatLayer> sl;
+    uint64_t groups = 0, blocks = 0;
+    for (int l = 0; l < n_layers; l++) {
+        const flashe_tensor_layer &y = layers[l];
+        const uint64_t size = (l + 1 < n_layers ? layers[l + 1].start : n) - y.start;
+        if (!size) continue;
+        st.push_back(TensorStore{y.start, groups, size, y.ptr, y.shift, y.dtype, y.flags});
+        groups += (size + 7) / 8;
+        if (stats_dev) {
+            sl.push_back(StatLayer{y.start, blocks, size, y.shift, y.flags, l});
+            blocks += (size + block - 1) / block;
+        }
+    }
+    if (st.empty()) return FLASHE_OK;
+    if (!sl.empty()) {
+        // table, then the per-buffer sums and the layer means behind it
+        const size_t tab_bytes = (sl.size() * sizeof(StatLayer) + 15) & ~static_cast<size_t>(15);
+        if ((rc = ensure(ctx, ctx->stat_ws, tab_bytes + (blocks + sl.size()) * sizeof(double)))) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->stat_ws.p, sl.data(), sl.size() * sizeof(StatLayer), hipMemcpyHostToDevice, ctx->env.stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->env.stream));
+        double *bsum = reinterpret_cast<double *>(static_cast<char *>(ctx->stat_ws.p) + tab_bytes);
+        // (the statistics read in_dev before the store pass, which may write in place)
+        HIP_TRY(ctx, launch_layer_stats(ctx->env, static_cast<const StatLayer *>(ctx->stat_ws.p), static_cast<int>(sl.size()), blocks, in_dev, block, bsum,
+                                        bsum + blocks, stats_dev));
+    }
+    const TensorStore *tab = nullptr;
+    if ((rc = upload_tab(ctx, ctx->tensor_tab, st, &tab))) return rc;
+    HIP_TRY(ctx, launch_store_layers(ctx->env, tab, static_cast<int>(st.size()), groups, in_dev));
     return FLASHE_OK;
 }
 

@@ -28,6 +28,10 @@ struct flashe_ctx {
     Buf bounds;       // span reduce: first entry of every client in every span
     Buf mt_ws;        // flashe_mt19937_random_dev: state in / out and the substream windows
     Buf codec_tab;    // layer table of the fused quantise / unquantise over a flattened model
+    Buf tensor_ws;    // caller tensors: the front end's converted layers (flashe_quantize_*_tensors_dev)
+    Buf tensor_tab;   // caller tensors: stage / store table
+    Buf stat_ws;      // caller tensors: stat table, per-buffer sums and layer means of flashe_store_layers_dev
+    hipEvent_t ev_foreign = nullptr;   // flashe_stream_wait_stream's marker on the other stream (created on first use)
     // ctx-resident mask precompute (flashe_prepare_encrypt / flashe_prepare_decrypt): the masks of the reference's next_iter_*_prepared
     // caches (jzf_flashe.py:599-666) stay in HBM inside the ctx and are consumed by the next flashe_encrypt_prepared* /
     // flashe_decrypt_prepared* call; the blocks are kept for the next round's masks

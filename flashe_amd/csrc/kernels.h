@@ -270,6 +270,38 @@ BatchLayer batch_layer_front(uint64_t elem_start, uint64_t value_start, uint64_t
 BatchLayer batch_layer_back(uint64_t elem_start, uint64_t value_start, uint64_t size, double alpha, int bits, int num_clients);
 hipError_t launch_unbatch(const LaunchEnv &env, uint64_t nb, const uint64_t *in_dev, int field_bits, uint64_t *out_dev);
 
+// Caller-owned tensors either side of the model-wide codec (tensors.hip).  dtype / flags as in flashe_tensor_layer (include/flashe.h);
+// kTensorLoopF64: the front end widens to float64 (the layer's NumPy loop dtype is float64).
+constexpr int kTensorF32 = 0, kTensorF64 = 1, kTensorF16 = 2, kTensorBF16 = 3;
+constexpr int kTensorShift = 1, kTensorShiftWide = 2, kTensorLoopF64 = 4;
+struct TensorStage {          // front end: src (stored dtype) -> dst (compute type), value k of the layer = staged value start + k
+    uint64_t start;
+    const void *src;
+    void *dst;
+    double shift;
+    int dtype, flags;
+};
+// dst[k] = src[k] as float32 / float64, normalised first with SHIFT; one lane per value of the concatenated staged layers
+hipError_t launch_stage_layers(const LaunchEnv &env, const TensorStage *tab_dev, int n_tab, uint64_t total);
+struct TensorStore {          // back end: groups of 8 values of the flat float64 vector -> the layer's tensor
+    uint64_t start;           // flat index of the layer's first value
+    uint64_t group_start;     // first 8-value group of the layer among all groups
+    uint64_t size;
+    void *dst;
+    double shift;
+    int dtype, flags;
+};
+hipError_t launch_store_layers(const LaunchEnv &env, const TensorStore *tab_dev, int n_tab, uint64_t n_groups, const double *in_dev);
+struct StatLayer {            // NumPy-exact sum and sum of squared deviations of y = in (+ shift) over one layer
+    uint64_t start;           // flat index of the layer's first value
+    uint64_t blk_start;       // first summation buffer of the layer among all buffers
+    uint64_t size;
+    double shift;
+    int flags, out_index;     // stats[2 * out_index] = sum, stats[2 * out_index + 1] = sum of (y - sum / size)^2
+};
+hipError_t launch_layer_stats(const LaunchEnv &env, const StatLayer *tab_dev, int n_tab, uint64_t n_blocks, const double *in_dev, uint64_t block,
+                              double *bsum_dev, double *means_dev, double *stats_dev);
+
 // Top-k of every layer of a model in one set of launches: the layers lie back to back in flat buffers.  The caller fills the host
 // layer table with sparsify_batch_layout (-> number of 1024-element blocks), copies its sparsify_batch_desc_bytes(L) bytes to the START
 // of a device workspace of sparsify_batch_workspace_bytes(L, blocks), then launches.

@@ -1,0 +1,262 @@
+// gfx950 kernels either side of the fused codec for caller-owned tensors (flashe_quantize_encrypt_tensors_dev,
+// flashe_quantize_batch_tensors_dev, flashe_store_layers_dev): the front end that turns float16 / bfloat16 / float32 / float64 layers
+// (optionally normalised) into the compute type the codec reads, the back end that writes the unquantised float64 values into the
+// caller's tensors in their own dtype, and NumPy's blocked pairwise summation of every layer for unnormalize's statistics.
+// All three are HBM-bound streaming passes; the layer tables are small device arrays staged per call.
+#include "device_common.h"
+
+namespace flashe {
+
+namespace {
+
+template <class Tab>
+__device__ __forceinline__ int layer_by(const Tab *tab, int n, uint64_t key, uint64_t Tab::*field)
+{
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tab[mid].*field <= key) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __builtin_bit_cast(float, static_cast<uint32_t>(h) << 16); }
+__device__ __forceinline__ float f16_to_f32(uint16_t h) { return static_cast<float>(__builtin_bit_cast(_Float16, h)); }
+// the hardware converts (round to nearest even; a NaN stays a NaN): v_cvt_f16_f32 / v_cvt_pk_bf16_f32
+__device__ __forceinline__ uint16_t f32_to_f16(float f) { return __builtin_bit_cast(uint16_t, static_cast<_Float16>(f)); }
+__device__ __forceinline__ uint16_t f32_to_bf16(float f) { return __builtin_bit_cast(uint16_t, static_cast<__bf16>(f)); }
+
+}  // namespace
+
+// ---- front end: one value per lane, grid-stride over the staged values of all layers ----
+__global__ __launch_bounds__(kStreamThreads) void stage_layers_kernel(const TensorStage *__restrict__ tab, int n_tab, uint64_t total)
+{
+#pragma clang fp contract(off)
+    for (uint64_t j = static_cast<uint64_t>(blockIdx.x) * kStreamThreads + threadIdx.x; j < total; j += static_cast<uint64_t>(gridDim.x) * kStreamThreads) {
+        const TensorStage &L = tab[layer_by(tab, n_tab, j, &TensorStage::start)];
+        const uint64_t k = j - L.start;
+        if (L.dtype == kTensorF64) {
+            double x = static_cast<const double *>(L.src)[k];
+            if (L.flags & kTensorShift) x = x + L.shift;
+            static_cast<double *>(L.dst)[k] = x;
+            continue;
+        }
+        float x;                                                        // 1. exact upcast of a 16-bit value
+        if (L.dtype == kTensorF32) x = static_cast<const float *>(L.src)[k];
+        else if (L.dtype == kTensorF16) x = f16_to_f32(static_cast<const uint16_t *>(L.src)[k]);
+        else x = bf16_to_f32(static_cast<const uint16_t *>(L.src)[k]);
+        if (L.flags & kTensorShift)                                     // 2. normalise in float32 (shift_kernel's arithmetic)
+            x = (L.flags & kTensorShiftWide) ? static_cast<float>(static_cast<double>(x) + L.shift) : x + static_cast<float>(L.shift);
+        if (L.flags & kTensorLoopF64) static_cast<double *>(L.dst)[k] = static_cast<double>(x);   // 3. exact widening
+        else static_cast<float *>(L.dst)[k] = x;
+    }
+}
+
+hipError_t launch_stage_layers(const LaunchEnv &env, const TensorStage *tab_dev, int n_tab, uint64_t total)
+{
+    if (total == 0 || n_tab < 1) return hipSuccess;
+    hipLaunchKernelGGL(stage_layers_kernel, dim3(stream_grid(env, total)), dim3(kStreamThreads), 0, env.stream, tab_dev, n_tab, total);
+    return hipGetLastError();
+}
+
+// ---- back end: eight values of one layer per lane; 16-byte stores where the layer's pointer allows them ----
+__global__ __launch_bounds__(kStreamThreads) void store_layers_kernel(const TensorStore *__restrict__ tab, int n_tab, uint64_t n_groups,
+                                                                      const double *__restrict__ in)
+{
+#pragma clang fp contract(off)
+    for (uint64_t g = static_cast<uint64_t>(blockIdx.x) * kStreamThreads + threadIdx.x; g < n_groups; g += static_cast<uint64_t>(gridDim.x) * kStreamThreads) {
+        const TensorStore &L = tab[layer_by(tab, n_tab, g, &TensorStore::group_start)];
+        const uint64_t j0 = (g - L.group_start) * 8;
+        const int cnt = L.size - j0 < 8 ? static_cast<int>(L.size - j0) : 8;
+        double y[8];
+#pragma unroll
+        for (int t = 0; t < 8; t++) {
+            y[t] = t < cnt ? in[L.start + j0 + t] : 0.0;
+            if (L.flags & kTensorShift) y[t] = y[t] + L.shift;
+        }
+        const bool vec = cnt == 8 && (reinterpret_cast<uintptr_t>(L.dst) & 15u) == 0;
+        if (L.dtype == kTensorF64) {
+            double *d = static_cast<double *>(L.dst) + j0;
+            if (vec) {
+#pragma unroll
+                for (int t = 0; t < 8; t += 2) *reinterpret_cast<double2 *>(d + t) = make_double2(y[t], y[t + 1]);
+            } else {
+                for (int t = 0; t < cnt; t++) d[t] = y[t];
+            }
+        } else if (L.dtype == kTensorF32) {
+            float *d = static_cast<float *>(L.dst) + j0;
+            if (vec) {
+#pragma unroll
+                for (int t = 0; t < 8; t += 4)
+                    *reinterpret_cast<float4 *>(d + t) = make_float4(static_cast<float>(y[t]), static_cast<float>(y[t + 1]), static_cast<float>(y[t + 2]),
+                                                                     static_cast<float>(y[t + 3]));
+            } else {
+                for (int t = 0; t < cnt; t++) d[t] = static_cast<float>(y[t]);
+            }
+        } else {
+            // f64 -> f32 -> 16 bits, each step round to nearest even (what torch's .to(float16 / bfloat16) of a float64 tensor does)
+            uint16_t h[8];
+#pragma unroll
+            for (int t = 0; t < 8; t++) {
+                const float f = static_cast<float>(y[t]);
+                h[t] = L.dtype == kTensorF16 ? f32_to_f16(f) : f32_to_bf16(f);
+            }
+            uint16_t *d = static_cast<uint16_t *>(L.dst) + j0;
+            if (vec) {
+                uint4 w;
+                w.x = h[0] | (static_cast<uint32_t>(h[1]) << 16); w.y = h[2] | (static_cast<uint32_t>(h[3]) << 16);
+                w.z = h[4] | (static_cast<uint32_t>(h[5]) << 16); w.w = h[6] | (static_cast<uint32_t>(h[7]) << 16);
+                *reinterpret_cast<uint4 *>(d) = w;
+            } else {
+                for (int t = 0; t < cnt; t++) d[t] = h[t];
+            }
+        }
+    }
+}
+
+hipError_t launch_store_layers(const LaunchEnv &env, const TensorStore *tab_dev, int n_tab, uint64_t n_groups, const double *in_dev)
+{
+    if (n_groups == 0 || n_tab < 1) return hipSuccess;
+    hipLaunchKernelGGL(store_layers_kernel, dim3(stream_grid(env, n_groups)), dim3(kStreamThreads), 0, env.stream, tab_dev, n_tab, n_groups, in_dev);
+    return hipGetLastError();
+}
+
+// ---- NumPy's np.sum of a C-contiguous float64 array, bit for bit ----
+// The reduction runs over buffers of `block` (np.getbufsize()) values, added left to right to an accumulator that starts at 0.0; each
+// buffer is summed by the pairwise tree of NumPy's loops: n < 8 sequential from 0.0; n <= 128 eight strided accumulators combined as
+// ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)) plus the tail in order; otherwise split at n2 = n / 2 - (n / 2) % 8.  One wave per
+// buffer: lane 0 lists the leaves of the tree in order (LDS), the lanes sum the leaves, lane 0 combines them in the tree's order.
+// pass 0 sums y = x (+ shift); pass 1 sums (y - mean)^2 with the layer's mean from pass 0.
+constexpr int kStatThreads = 64;
+constexpr int kStatMaxLeaves = 512;        // enough for buffers of up to 16,384 values (every leaf of a split tree holds > 56)
+constexpr int kStatMaxDepth = 32;
+
+__global__ __launch_bounds__(kStatThreads) void stat_blocks_kernel(const StatLayer *__restrict__ tab, int n_tab, uint64_t n_blocks,
+                                                                   const double *__restrict__ in, uint64_t block, int pass,
+                                                                   const double *__restrict__ means, double *__restrict__ bsum)
+{
+#pragma clang fp contract(off)
+    __shared__ uint32_t leaf_off[kStatMaxLeaves];
+    __shared__ uint32_t leaf_len[kStatMaxLeaves];
+    __shared__ double leaf_sum[kStatMaxLeaves];
+    __shared__ uint32_t st_len[kStatMaxDepth];
+    __shared__ uint32_t st_off[kStatMaxDepth];
+    __shared__ uint32_t st_state[kStatMaxDepth];
+    __shared__ double st_left[kStatMaxDepth];
+    __shared__ int n_leaves;
+    for (uint64_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
+        const int li = layer_by(tab, n_tab, b, &StatLayer::blk_start);
+        const StatLayer &L = tab[li];
+        const uint64_t off0 = (b - L.blk_start) * block;
+        const uint32_t m = static_cast<uint32_t>(L.size - off0 < block ? L.size - off0 : block);
+        const double *x = in + L.start + off0;
+        const bool shift = (L.flags & kTensorShift) != 0;
+        const double mean = pass ? means[li] : 0.0;
+        if (threadIdx.x == 0) {                                         // the leaves, left to right
+            int sp = 0, nl = 0;
+            st_off[0] = 0; st_len[0] = m;
+            while (sp >= 0) {
+                const uint32_t o = st_off[sp], len = st_len[sp];
+                sp--;
+                if (len <= 128) { leaf_off[nl] = o; leaf_len[nl] = len; nl++; continue; }
+                uint32_t n2 = len / 2;
+                n2 -= n2 % 8;
+                sp++; st_off[sp] = o + n2; st_len[sp] = len - n2;         // right child below the left one
+                sp++; st_off[sp] = o; st_len[sp] = n2;
+            }
+            n_leaves = nl;
+        }
+        __syncthreads();
+        const int nl = n_leaves;
+        for (int l = threadIdx.x; l < nl; l += kStatThreads) {
+            const uint32_t o = leaf_off[l], len = leaf_len[l];
+            auto val = [&](uint32_t i) {
+                double y = x[o + i];
+                if (shift) y = y + L.shift;
+                if (pass) { const double d = y - mean; y = d * d; }
+                return y;
+            };
+            double res;
+            if (len < 8) {
+                res = 0.0;
+                for (uint32_t i = 0; i < len; i++) res += val(i);
+            } else {
+                double r0 = val(0), r1 = val(1), r2 = val(2), r3 = val(3), r4 = val(4), r5 = val(5), r6 = val(6), r7 = val(7);
+                uint32_t i = 8;
+                for (; i < len - (len % 8); i += 8) {
+                    r0 += val(i); r1 += val(i + 1); r2 += val(i + 2); r3 += val(i + 3);
+                    r4 += val(i + 4); r5 += val(i + 5); r6 += val(i + 6); r7 += val(i + 7);
+                }
+                res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
+                for (; i < len; i++) res += val(i);
+            }
+            leaf_sum[l] = res;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {                                         // the tree, combined in its own order (post-order walk)
+            int sp = 0, leaf = 0;
+            st_len[0] = m; st_state[0] = 0;
+            double ret = 0.0;
+            bool have = false;
+            while (true) {
+                if (have) {
+                    if (sp < 0) break;
+                    if (st_state[sp] == 1) {                            // left child done: descend into the right one
+                        st_left[sp] = ret;
+                        st_state[sp] = 2;
+                        uint32_t n2 = st_len[sp] / 2;
+                        n2 -= n2 % 8;
+                        const uint32_t right = st_len[sp] - n2;
+                        sp++; st_len[sp] = right; st_state[sp] = 0;
+                        have = false;
+                    } else {                                            // both children done
+                        ret = st_left[sp] + ret;
+                        sp--;
+                    }
+                    continue;
+                }
+                const uint32_t len = st_len[sp];
+                if (len <= 128) { ret = leaf_sum[leaf++]; sp--; have = true; continue; }
+                uint32_t n2 = len / 2;
+                n2 -= n2 % 8;
+                st_state[sp] = 1;
+                sp++; st_len[sp] = n2; st_state[sp] = 0;
+            }
+            bsum[b] = ret;
+        }
+        __syncthreads();
+    }
+}
+
+// one lane per layer: the buffer sums added in order from 0.0; pass 0 also leaves the layer's mean (S / n) for pass 1
+__global__ __launch_bounds__(kStreamThreads) void stat_combine_kernel(const StatLayer *__restrict__ tab, int n_tab, const double *__restrict__ bsum,
+                                                                      uint64_t block, int pass, double *__restrict__ means, double *__restrict__ stats)
+{
+#pragma clang fp contract(off)
+    const int l = blockIdx.x * kStreamThreads + threadIdx.x;
+    if (l >= n_tab) return;
+    const StatLayer &L = tab[l];
+    const uint64_t nb = (L.size + block - 1) / block;
+    double s = 0.0;
+    for (uint64_t b = 0; b < nb; b++) s += bsum[L.blk_start + b];
+    stats[2 * L.out_index + pass] = s;
+    if (pass == 0) means[l] = s / static_cast<double>(L.size);
+}
+
+hipError_t launch_layer_stats(const LaunchEnv &env, const StatLayer *tab_dev, int n_tab, uint64_t n_blocks, const double *in_dev, uint64_t block,
+                              double *bsum_dev, double *means_dev, double *stats_dev)
+{
+    if (n_blocks == 0 || n_tab < 1) return hipSuccess;
+    if (block < 1 || block > 16384) return hipErrorInvalidValue;
+    const int grid = static_cast<int>(n_blocks < 65536 ? n_blocks : 65536);
+    const int cgrid = (n_tab + kStreamThreads - 1) / kStreamThreads;
+    for (int pass = 0; pass < 2; pass++) {
+        hipLaunchKernelGGL(stat_blocks_kernel, dim3(grid), dim3(kStatThreads), 0, env.stream, tab_dev, n_tab, n_blocks, in_dev, block, pass, means_dev,
+                           bsum_dev);
+        hipLaunchKernelGGL(stat_combine_kernel, dim3(cgrid), dim3(kStreamThreads), 0, env.stream, tab_dev, n_tab, bsum_dev, block, pass, means_dev,
+                           stats_dev);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace flashe

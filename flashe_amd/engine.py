@@ -495,6 +495,8 @@ class Engine:
         self.int_bits = int(int_bits)
         self.limbs = limbs_of(int_bits)
         self.device = device
+        self.shared_stream = bool(stream)       # created on the caller's stream (everything is stream-ordered with the framework)
+        self._held = []                         # (event, keep-alive) of foreign arrays device work may still touch
 
     # -- plumbing -------------------------------------------------------------------------
     def _check(self, rc):
@@ -550,6 +552,81 @@ class Engine:
 
     def sync(self):
         self._check(self._lib.flashe_sync(self._h))
+        self._reap()
+
+    # -- foreign device arrays (interop.py): stream hand-off and lifetime ----------------------------
+    @property
+    def stream(self):
+        """The ctx's hipStream_t as an int (what a DLPack producer orders its pending writes before)."""
+        p = c_vp()
+        self._check(self._lib.flashe_ctx_stream(self._h, ctypes.byref(p)))
+        return int(p.value or 0)
+
+    def wait_stream(self, other):
+        """This engine's stream waits, on the device, for the work queued so far on the hipStream_t `other` (int; 0 = null stream)."""
+        self._check(self._lib.flashe_stream_wait_stream(self._h, c_vp(int(other)) if other else None))
+
+    def event_query(self, ev):
+        done = c_int(0)
+        self._check(self._lib.flashe_event_query(self._h, ev, ctypes.byref(done)))
+        return bool(done.value)
+
+    def foreign(self, obj, writable=False, what="array"):
+        """A framework array as an interop.ForeignArray on this engine's device: the DLPack handshake on this engine's stream, or a
+        cuda-array-interface producer's `stream` waited for on the device.  writable: refuse a read-only (cuda-array-interface) array."""
+        from . import interop
+        fa = interop.as_foreign(obj, self.device, self.stream)
+        if writable and fa.readonly:
+            raise ValueError(f"{what}: the array is read-only (__cuda_array_interface__ data[1] is True)")
+        if fa.stream is not None:
+            self.wait_stream(0 if fa.stream in (1, 2) else fa.stream)
+        return fa
+
+    def hold(self, keep):
+        """Keep `keep` (foreign arrays' owners) alive until the work queued so far on this engine's stream has finished: an event is
+        recorded behind it and the pair released at a later call once the event reports done (own-stream mode: a tensor the caller drops
+        right after the call must not go back to the framework's allocator while a kernel still reads it)."""
+        self._reap()
+        if keep:
+            ev = self.event()
+            self.record(ev)
+            self._held.append((ev, keep))
+
+    def _reap(self):
+        if not self._held or self._h is None:
+            return
+        still = []
+        for ev, keep in self._held:
+            if self.event_query(ev):
+                self.event_destroy(ev)
+            else:
+                still.append((ev, keep))
+        self._held = still
+
+    def quantize_encrypt_tensors_dev(self, it, idx, scheme, n, n_jobs, first, count, layers, element_bits, u, ct):
+        """quantize_encrypt_model_dev with tensor layers: (start, ptr, alpha, shift, dtype code, flags) per layer (flashe_tensor_layer)."""
+        arr, nl = self._tensor_layers(layers)
+        self._check(self._lib.flashe_quantize_encrypt_tensors_dev(self._h, it, idx, scheme, n, n_jobs, first, count, arr, nl, element_bits,
+                                                                  self._ptr(u), self._ptr(ct)))
+
+    def quantize_batch_tensors_dev(self, layers, n_values, element_bits, field_bits, u, n_elems, out):
+        arr, nl = self._tensor_layers(layers)
+        self._check(self._lib.flashe_quantize_batch_tensors_dev(self._h, arr, nl, int(n_values), element_bits, field_bits, self._ptr(u), int(n_elems),
+                                                                self._ptr(out)))
+
+    def store_layers_dev(self, inp, n, layers, block=0, stats=None):
+        """The flat float64 vector `inp` into the layers' tensors (cast to their dtype, + shift with SHIFT); stats (device, 2 doubles per
+        layer): NumPy-exact (sum, sum of squared deviations) of every non-empty layer over buffers of `block` values."""
+        arr, nl = self._tensor_layers(layers)
+        self._check(self._lib.flashe_store_layers_dev(self._h, self._ptr(inp), int(n), arr, nl, int(block), self._ptr(stats)))
+
+    @staticmethod
+    def _tensor_layers(layers):
+        layers = list(layers)
+        arr = (_lib.TensorLayer * max(len(layers), 1))()
+        for i, (start, ptr, alpha, shift, dtype, flags) in enumerate(layers):
+            arr[i].start, arr[i].ptr, arr[i].alpha, arr[i].shift, arr[i].dtype, arr[i].flags = int(start), ptr, float(alpha), float(shift), int(dtype), int(flags)
+        return arr, len(layers)
 
     def memset_dev(self, buf, byte, nbytes):
         """Fills the first nbytes of a device buffer with `byte` (asynchronous on the ctx stream)."""

@@ -62,7 +62,10 @@ typedef struct flashe_ctx flashe_ctx;
  *      prefix 0; flashe_prepared_discard releases the cached mask buffers; flashe_combine_batch_sum_dev (online encrypts with
  *      precomputed masks + their sum in one pass); flashe_encrypt_batch_sum_u32_dev (the compact layout's encrypts + their sum)
  *   4  round 6: flashe_device_peer_access and flashe_rccl_version (the preflight a rank of a multi-GPU launch runs before it creates
- *      its ctx); flashe_combine_batch_sum_decrypt_dev (online encrypts + their sum + the decrypt of the sum in one pass) */
+ *      its ctx); flashe_combine_batch_sum_decrypt_dev (online encrypts + their sum + the decrypt of the sum in one pass);
+ *      later additions without a bump (existing signatures unchanged; a caller checks for the symbols): flashe_ctx_stream,
+ *      flashe_stream_wait_stream, flashe_event_query, flashe_tensor_layer + flashe_quantize_encrypt_tensors_dev /
+ *      flashe_quantize_batch_tensors_dev / flashe_store_layers_dev (caller-owned tensors either side of the model-wide codec) */
 #define FLASHE_ABI_VERSION 4
 int flashe_abi_version(void);
 int flashe_device_count(int *count);
@@ -140,6 +143,14 @@ int flashe_event_elapsed_ms(flashe_ctx *ctx, void *start, void *stop, float *ms)
 /* Make ctx's stream wait (on the device, not the host) for an event recorded by ANOTHER ctx of the
  * same device: the fork/join primitive for running e.g. the arbiter reduce on a second stream. */
 int flashe_stream_wait_event(flashe_ctx *ctx, void *event);
+/* new: the ctx's hipStream_t (the caller's own stream when flashe_ctx_create was handed one) -- what a framework's DLPack export
+ * (__dlpack__(stream=...)) orders its pending writes before. */
+int flashe_ctx_stream(const flashe_ctx *ctx, void **stream);
+/* new: ctx's stream waits, on the device, for the work queued so far on `other` (a hipStream_t of the same device; NULL = the null
+ * stream): the consumer side of a __cuda_array_interface__ `stream` key.  The host never blocks. */
+int flashe_stream_wait_stream(flashe_ctx *ctx, void *other);
+/* new: non-blocking: *done = 1 once the work before the event's last record has finished, 0 while it is pending. */
+int flashe_event_query(flashe_ctx *ctx, void *event, int *done);
 
 /* Capture and replay (HIP graphs): the *_dev calls made on ctx between begin and end are recorded instead of
  * run; launch replays the whole sequence with one submission -- for launch-bound work such as a round over a
@@ -600,6 +611,49 @@ int flashe_unbatch_unquantize_model_dev(flashe_ctx *ctx, const flashe_batch_laye
  * reference sums a Python-float object array left to right): agreement is to ~1e-12 relative, tests use 1e-10.  Synchronous. */
 int flashe_shift_dev(flashe_ctx *ctx, uint64_t n, void *x_dev, int x_is_f64, double shift, int wide);
 int flashe_mean_std_dev(flashe_ctx *ctx, uint64_t n, const void *x_dev, int x_is_f64, double *mean, double *stddev);
+
+/* Caller-owned tensors either side of the model-wide codec (new): a training framework's layers in HBM, handed over by pointer (DLPack /
+ * __cuda_array_interface__ on the Python side), in their own dtype.  One flashe_tensor_layer per layer (HOST array, ascending start,
+ * layers[0].start == 0, the last entry with start <= j holds flat element j; ptr points to the layer's own first value, C-contiguous).
+ * dtype: FLASHE_TENSOR_F32 / F64 / F16 / BF16.  flags: FLASHE_TENSOR_SHIFT adds `shift` (normalize passes -mean, unnormalize +mean:
+ * QuantizingClient.normalize / unnormalize, jzf_quantize.py:542-564); FLASHE_TENSOR_SHIFT_WIDE: a float32 add runs in float64 and is
+ * rounded once (NumPy's loop for an np.float64 scalar, as flashe_shift_dev's `wide`); FLASHE_TENSOR_LOOP_F64: the front end quantises a
+ * 32- or 16-bit layer in float64 (NumPy's loop dtype for a float32 array and an np.float64 alpha, jzf_quantize.py:55-67 under :394-491). */
+#define FLASHE_TENSOR_F32 0
+#define FLASHE_TENSOR_F64 1
+#define FLASHE_TENSOR_F16 2
+#define FLASHE_TENSOR_BF16 3
+#define FLASHE_TENSOR_SHIFT 1
+#define FLASHE_TENSOR_SHIFT_WIDE 2
+#define FLASHE_TENSOR_LOOP_F64 4
+typedef struct flashe_tensor_layer {
+    uint64_t start;        /* flat index of the layer's first value */
+    void *ptr;             /* the layer's values (front end: read; flashe_store_layers_dev: written) */
+    double alpha;          /* front end: the clipping threshold (as flashe_codec_layer.alpha); ignored by flashe_store_layers_dev */
+    double shift;          /* with FLASHE_TENSOR_SHIFT */
+    int32_t dtype;         /* F32 0, F64 1, F16 2, BF16 3 */
+    int32_t flags;         /* SHIFT 1, SHIFT_WIDE 2, LOOP_F64 4 */
+} flashe_tensor_layer;
+/* Front end, jzf_quantize.py:55-67, 542-547 (normalize): the same contract as flashe_quantize_encrypt_model_dev with tensor layers.  A
+ * layer already in its compute type without SHIFT is read where it lies; every other layer touched by [first, first + count) is
+ * converted by one streaming pass into ctx scratch -- a 16-bit value upcast to float32 exactly, SHIFT applied in float32 (float64 for an
+ * F64 layer), then widened exactly with LOOP_F64 -- and read from there.  The table upload synchronises. */
+int flashe_quantize_encrypt_tensors_dev(flashe_ctx *ctx, uint32_t iter, uint32_t idx, int scheme, uint64_t n, uint32_t n_jobs,
+                                        uint64_t first, uint64_t count, const flashe_tensor_layer *layers, int n_layers,
+                                        int element_bits, const double *u_dev, uint64_t *ct_dev);
+/* The batched job's front end, jzf_quantize.py:55-67, 162-185 (new): flashe_quantize_batch_model_dev with tensor layers; the layer
+ * sizes are the differences of consecutive starts, the last one ends at n_values. */
+int flashe_quantize_batch_tensors_dev(flashe_ctx *ctx, const flashe_tensor_layer *layers, int n_layers, uint64_t n_values, int element_bits,
+                                      int field_bits, const double *u_dev, uint64_t n_elems, uint64_t *out_dev);
+/* Back end, jzf_quantize.py:102-107, 549-564 (unnormalize): the flat float64 vector in_dev[n] (what flashe_decrypt_unquantize_model_dev /
+ * flashe_unbatch_unquantize_model_dev / flashe_unquantize_model_dev write) goes into the layers' tensors: y = in (+ shift with SHIFT) in
+ * float64, stored as the layer's dtype (float64 -> float32 -> 16 bits, each step round to nearest even).  ptr may be the layer's own
+ * place in in_dev (in place).  stats_dev (device, 2 doubles per layer; NULL = none): (sum, sum of squared deviations) of y of every
+ * non-empty layer exactly as NumPy sums a C-contiguous float64 array -- buffers of `block` values (np.getbufsize(), <= 16,384) added in
+ * order to 0.0, each by NumPy's pairwise tree -- so that the caller's S / n and sqrt(S2 / n) ARE np.mean and np.std of y, bit for bit
+ * (the deviations are taken from the correctly rounded S / n).  The table upload synchronises; the passes are asynchronous. */
+int flashe_store_layers_dev(flashe_ctx *ctx, const double *in_dev, uint64_t n, const flashe_tensor_layer *layers, int n_layers, uint64_t block,
+                            double *stats_dev);
 
 /* np.random.random(n) ON THE DEVICE, bit for bit (new): the stochastic-rounding draws of _static_quantize_padding_asymmetric
  * (jzf_quantize.py:61, `np.random.random(value.shape)`) come from NumPy's global MT19937 generator; this writes the same n doubles
