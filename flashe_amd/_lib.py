@@ -192,6 +192,14 @@ _SIGNATURES = {
                                                     c_vp, c_vp]),
     "flashe_quantize_batch_tensors_dev": (c_int, [c_vp, ctypes.POINTER(TensorLayer), c_int, c_u64, c_int, c_int, c_vp, c_u64, c_vp]),
     "flashe_store_layers_dev": (c_int, [c_vp, c_vp, c_u64, ctypes.POINTER(TensorLayer), c_int, c_u64, c_vp]),
+    "flashe_quantize_encrypt_prepared_model_dev": (c_int, [c_vp, c_u64, c_u64, c_u64, ctypes.POINTER(CodecLayer), c_int, c_int, c_vp, c_vp]),
+    "flashe_quantize_encrypt_prepared_tensors_dev": (c_int, [c_vp, c_u64, c_u64, c_u64, ctypes.POINTER(TensorLayer), c_int, c_int, c_vp, c_vp]),
+    "flashe_quantize_batch_encrypt_prepared_model_dev": (c_int, [c_vp, ctypes.POINTER(BatchLayer), c_int, c_int, c_int, c_vp, c_u64, c_vp]),
+    "flashe_quantize_batch_encrypt_prepared_tensors_dev": (c_int, [c_vp, ctypes.POINTER(TensorLayer), c_int, c_u64, c_int, c_int, c_vp, c_u64, c_vp]),
+    "flashe_decrypt_prepared_unquantize_model_dev": (c_int, [c_vp, c_u32, c_u32p, c_int, c_u32p, c_int, c_u64, c_u32, c_vp, ctypes.POINTER(CodecLayer),
+                                                             c_int, c_int, c_int, c_vp]),
+    "flashe_decrypt_prepared_unbatch_unquantize_model_dev": (c_int, [c_vp, c_u32, c_u32p, c_int, c_u32p, c_int, c_u32, ctypes.POINTER(BatchLayer), c_int,
+                                                                     c_int, c_int, c_int, c_vp, c_u64, c_vp]),
     "flashe_mt19937_random_dev": (c_int, [c_vp, c_u32p, c_u32p, c_u64, c_vp]),
     "flashe_mt19937_jump_selfcheck": (c_int, []),
     "flashe_mt19937_plan": (c_int, [c_u32, c_u64, c_u32p, c_u32p, c_u32p]),

@@ -8,7 +8,7 @@ import os
 
 import numpy as np
 
-from .cipher import FlasheCipher
+from .cipher import FlasheCipher, _CtxMask
 from .quantize import QuantizingClient
 
 _RNG_RUN_MAX = 1 << 26          # draws per device call of quantize_encrypt (512 MiB of float64)
@@ -202,14 +202,63 @@ class FlasheClient(object):
     # ---- the client step with nothing on the host in between (new) ------------------------------------------------------------
     def _fusable(self, weights=None):
         c = self.cipher
-        if not (self.fuse and c.prp_seed is not None and not c.next_iter_encrypt_prepared and hasattr(c.engine, "quantize_encrypt_model_dev")):
+        if not (self.fuse and c.prp_seed is not None and hasattr(c.engine, "quantize_encrypt_model_dev")):
             return False
+        c._reconcile_prepared()
         if weights is None or "zzz" not in weights._weights:
-            return c.masks is None
+            return c.masks is None and self._prepared_mode(c.next_iter_encrypt_prepared) is not False
+        if c.next_iter_encrypt_prepared:
+            return False
         # the sparse job: compact layers + the sparsifier's trailing one-value layer (the masks a previous round's decrypt left in the
         # cipher do not touch the encrypt)
         order = list(weights.walking_order)
         return not self.batch and len(order) > 1 and order[-1] == "zzz" and np.size(weights._weights["zzz"]) == 1
+
+    def _prepared_mode(self, prep):
+        """What the fused step does with a next_iter_*_prepared dict (the reference's mask cache, jzf_flashe.py:599-666):
+        None   = empty;
+        "ctx"  = double mask, both entries handles of masks the engine's ctx holds: the fused launches read them and consume the cache;
+        "single" = single mask: the reference does not read the cache, it only drops one entry (:452-454, :533-535);
+        False  = anything else (plain arrays a caller assigned): the call-by-call step."""
+        c = self.cipher
+        if not prep:
+            return None
+        if c.masking_scheme != "double":
+            return "single"
+        ok = (isinstance(prep, dict) and isinstance(prep.get('add'), _CtxMask) and isinstance(prep.get('minus'), _CtxMask)
+              and hasattr(c.engine, "quantize_encrypt_prepared_model_dev"))
+        return "ctx" if ok else False
+
+    def _encrypt_done(self, mode):
+        """The entries the call-by-call encrypt deletes (:452-454, :483-486); the ctx has consumed its cache in the last launch."""
+        c = self.cipher
+        if mode == "ctx":
+            del c.next_iter_encrypt_prepared['add'], c.next_iter_encrypt_prepared['minus']
+            c._ctx_holds &= ~c.engine.PREPARED_ENCRYPT
+        elif mode == "single":
+            c.next_iter_encrypt_prepared.pop('add', None)
+
+    def _decrypt_done(self, mode):
+        """The same for the decrypt (:533-535, :573-580): the encrypt cache of the next round is not touched."""
+        c = self.cipher
+        if mode == "ctx":
+            for d in (c.next_iter_decrypt_prepared, c.next_iter_decrypt_prepared_idx):
+                d.pop('add', None)
+                d.pop('minus', None)
+            c._ctx_holds &= ~c.engine.PREPARED_DECRYPT
+        elif mode == "single":
+            c.next_iter_decrypt_prepared.pop('minus', None)
+
+    def _refuse_prepared_len(self, n_ct, n_values):
+        """An encrypt cache of another length: the call-by-call step's ValueError (cipher._check_prepared_len), raised where that step
+        raises it -- after its quantiser has drawn one value of NumPy's stream per model value.  The cache stays."""
+        c = self.cipher
+        cache = c.next_iter_encrypt_prepared['add']
+        if len(cache) == n_ct:
+            return
+        for at in range(0, n_values, _RNG_RUN_MAX):
+            np.random.random(min(_RNG_RUN_MAX, n_values - at))
+        c._check_prepared_len(cache, n_ct)
 
     def quantize_encrypt(self, weights, device=True, normalize=False):
         """normalize (new): QuantizingClient.normalize first (`-= past_layer_mean_list[i]`, jzf_quantize.py:542-547).  Layers may also be
@@ -231,8 +280,11 @@ class FlasheClient(object):
         (flashe_quantize_batch_model_dev), then the encrypt of the flattened batched vector.  The SPARSE job (compact layers from
         `Client.sparsify` plus the one-value 'zzz' layer, jzf_aggregator.py:717-743) is the same one launch over the compact layers; the
         'zzz' value is quantised on the host with the draw that follows theirs (alpha 1.0, jzf_quantize.py:433-435) and appended
-        UN-encrypted: the result holds n + 1 elements.  Batched sparse jobs and precomputed encrypt masks take the same sequence call by
-        call on the host and return object arrays like the reference."""
+        UN-encrypted: the result holds n + 1 elements.  PRECOMPUTED encrypt masks (precompute jobs: the handles prepare_encrypt leaves in
+        next_iter_encrypt_prepared) are added by the same launches in place of the PRF streams -- no AES; the batched job's quantise +
+        batch + encrypt becomes one launch -- and consumed as the call-by-call encrypt consumes them; a single-mask cipher ignores them
+        and drops 'add' as the reference does.  Batched sparse jobs, sparse jobs with a cache and masks a caller assigned as plain arrays
+        take the same sequence call by call on the host and return object arrays like the reference."""
         from . import cipher as _cipher_mod
         from .engine import DeviceVector
         from .quantize import ACIQ, DEVICE_RNG_MIN, _loop_dtype
@@ -255,6 +307,7 @@ class FlasheClient(object):
             weights._weights[k0] = np.append(ct, [zero_quantized]) if sparse else ct
             return weights
         eng = c.engine
+        mode = self._prepared_mode(c.next_iter_encrypt_prepared)
         aciq = ACIQ(q.element_bits)
         alphas = []
         for i, _size in enumerate(q.layer_size_list):
@@ -299,13 +352,19 @@ class FlasheClient(object):
             bs = self.int_bits // field_bits
             q.shape_list = [shape_dict[k] for k in order]
             n_elems = sum((int(h.size) + bs - 1) // bs for h in host)
+            if mode == "ctx":
+                self._refuse_prepared_len(n_elems, n)
             du = (eng.numpy_random_dev(n) if dev_rng and n >= DEVICE_RNG_MIN else eng.upload(np.random.random(n))) if n else eng.alloc(16)
-            pt = eng.alloc_vec(max(n_elems, 1))
-            eng.quantize_batch_model_dev([(int(host[li].size), xbuf.ptr + offs[li], q.alpha_list[li], host[li].dtype == np.float64)
-                                          for li in range(len(order))], q.element_bits, field_bits, du, n_elems, pt)
+            blayers = [(int(host[li].size), xbuf.ptr + offs[li], q.alpha_list[li], host[li].dtype == np.float64) for li in range(len(order))]
             ct = DeviceVector(eng, n_elems)
-            if n_elems:
-                eng.encrypt_dev(c.iter_index, c.idx, scheme, n_elems, _cipher_mod.N_JOBS, pt, eng.limbs, ct.buf)
+            if mode == "ctx":                   # quantise + batch + the prepared masks: one launch, no AES
+                eng.quantize_batch_encrypt_prepared_model_dev(blayers, q.element_bits, field_bits, du, n_elems, ct.buf)
+            else:
+                pt = eng.alloc_vec(max(n_elems, 1))
+                eng.quantize_batch_model_dev(blayers, q.element_bits, field_bits, du, n_elems, pt)
+                if n_elems:
+                    eng.encrypt_dev(c.iter_index, c.idx, scheme, n_elems, _cipher_mod.N_JOBS, pt, eng.limbs, ct.buf)
+            self._encrypt_done(mode)
             for k in order:
                 del weights._weights[k]
             self.shape_dict = {k: ((int(h.size) + bs - 1) // bs,) for k, h in zip(order, host)}      # the batched layers are 1-D (:448)
@@ -317,7 +376,10 @@ class FlasheClient(object):
         ct = DeviceVector(eng, n + (1 if zzz is not None else 0))
         # the draws of consecutive layers are ONE stretch of NumPy's stream (np.random.random(layer.shape) per layer in walking order,
         # jzf_quantize.py:55-67 under :417-462), i.e. flat element j takes draw j: a run of whole layers is drawn by one device call and
-        # quantised + encrypted by one launch over its range.  Runs are capped so the draws of a huge model stay bounded.
+        # quantised + encrypted by one launch over its range.  Runs are capped so the draws of a huge model stay bounded.  With the ctx's
+        # prepared masks the launches add them in place of the PRF streams; the run that ends the vector consumes them.
+        if mode == "ctx":
+            self._refuse_prepared_len(n, n)
         at = 0
         while at < len(order):
             end, tot = at, 0
@@ -327,9 +389,15 @@ class FlasheClient(object):
             if tot:
                 du = eng.numpy_random_dev(tot) if dev_rng and tot >= DEVICE_RNG_MIN else eng.upload(np.random.random(tot))
                 first = starts[at]
-                eng.quantize_encrypt_model_dev(c.iter_index, c.idx, scheme, n, _cipher_mod.N_JOBS, first, tot, table, q.element_bits, du,
-                                               ct.ptr + first * eng.limbs * 8)
+                if mode == "ctx":
+                    eng.quantize_encrypt_prepared_model_dev(n, first, tot, table, q.element_bits, du, ct.ptr + first * eng.limbs * 8)
+                else:
+                    eng.quantize_encrypt_model_dev(c.iter_index, c.idx, scheme, n, _cipher_mod.N_JOBS, first, tot, table, q.element_bits, du,
+                                                   ct.ptr + first * eng.limbs * 8)
             at = end
+        if mode == "ctx" and n == 0:
+            eng.prepared_discard(eng.PREPARED_ENCRYPT)          # (nothing to add the masks to: consumed all the same)
+        self._encrypt_done(mode)
         if zzz is not None:
             # the trailing layer: the next draw of the stream, alpha 1.0, not encrypted (:735-743 strips it before and re-appends it after)
             from .quantize import _as_object, _static_quantize_padding_asymmetric
@@ -360,16 +428,23 @@ class FlasheClient(object):
         aggregate -- a DeviceVector, uint64 limbs or object ints -- is decrypted with the prefixes `set_idx_list` left behind and comes
         back as unquantised float64 layers.  The SPARSE job (location lists in `cipher.masks`; it sets `self.shape_dict =
         shape_dict_used_for_sparsification` first, :893-894) decrypts on the device with the sparse minus-mask pass and unquantises the
-        dense result in a second launch (flashe_unquantize_model_dev).  Precomputed decrypt masks take the same sequence call by call."""
-        from . import cipher as _cipher_mod
+        dense result in a second launch (flashe_unquantize_model_dev).  PRECOMPUTED decrypt masks (the handles prepare_decrypt leaves) are
+        added by the same one launch in place of the PRF streams (flashe_decrypt_prepared_unquantize_model_dev / _unbatch_: the batched job's
+        decrypt + unbatch becomes one launch); the prefixes set_idx_list leaves uncovered (dropouts) go through a PRF launch first.  The
+        cache is consumed as the call-by-call decrypt consumes it; the encrypt cache of the next round is not touched.  Masks a caller
+        assigned as plain arrays take the same sequence call by call."""
         from .engine import DeviceVector
         q, c = self.quantizer, self.cipher
         if out is not None:
             return self._decrypt_unquantize_tensors(weights, out, unnormalize)
         if unnormalize:
             return self.unnormalize(self.decrypt_unquantize(weights))
-        fus = (self.fuse and c.masks is None and c.prp_seed is not None and not c.next_iter_decrypt_prepared
-               and hasattr(c.engine, "decrypt_unquantize_model_dev"))
+        fus = self.fuse and c.masks is None and c.prp_seed is not None and hasattr(c.engine, "decrypt_unquantize_model_dev")
+        mode = None
+        if fus:
+            c._reconcile_prepared()
+            mode = self._prepared_mode(c.next_iter_decrypt_prepared)
+            fus = mode is not False
         k0 = weights.walking_order[0]
         from .cipher import _SparseMinus
         prep = c.next_iter_decrypt_prepared
@@ -400,14 +475,7 @@ class FlasheClient(object):
                 res = _from_limbs(res, "object")          # (limbs in, limbs out: the layer-by-layer sequence works on the reference's object ints)
             weights._weights[k0] = res
             return self.unquantize(self.unflatten_weights(weights))
-        eng = c.engine
-        if c.masking_scheme == "double":
-            add_idx = [c._idx_of(p) for p in (c.index_prefix_for_add or [])]
-            minus_idx = [c._idx_of(p) for p in (c.index_prefix_for_minus or [])]
-            if not add_idx and not minus_idx:
-                raise KeyError('add')
-        else:
-            add_idx, minus_idx = [], [c._idx_of(p) for p in c.index_prefix_for_minus]
+        add_idx, minus_idx = self._decrypt_prefixes(mode)
         v = weights._weights[k0]
         if not isinstance(v, DeviceVector):
             v = np.asarray(v)
@@ -417,22 +485,9 @@ class FlasheClient(object):
         dv = c._as_wide(dv)                       # (a compact uint32 aggregate: the fused launch reads one-limb vectors)
         n = len(dv)
         if self.batch:
-            # decrypt of the flattened batched vector, then unbatch + `[:size]` + unquantise of every layer in ONE launch
-            factor = int(np.ceil(np.log2(q.num_clients)))
-            field_bits = q.element_bits + factor
-            bs = self.int_bits // field_bits
             names = list(self.shape_dict)
             sizes = [int(np.prod(shape)) for shape in q.shape_list]
-            if sum((s_ + bs - 1) // bs for s_ in sizes) != n:
-                raise ValueError(f"the aggregate has {n} elements, the batched layers describe {sum((s_ + bs - 1) // bs for s_ in sizes)}")
-            dec = eng.alloc_vec(max(n, 1))
-            if n:
-                eng.decrypt_dev(c.iter_index, add_idx, minus_idx, n, _cipher_mod.N_JOBS, dv.buf, dec)
-            n_values = sum(sizes)
-            dout = eng.alloc(max(8 * n_values, 16))
-            eng.unbatch_unquantize_model_dev([(s_, None, q.alpha_list[li], False) for li, s_ in enumerate(sizes)], q.element_bits, field_bits,
-                                             q.num_clients, dec, n, dout)
-            out = dout.download(np.float64, n_values)
+            out = self._decrypt_floats(dv, sizes, mode, add_idx, minus_idx).download(np.float64, sum(sizes))
             del weights._weights[k0]
             at = 0
             for name, shape, s_ in zip(names, q.shape_list, sizes):
@@ -441,6 +496,49 @@ class FlasheClient(object):
             weights.walking_order = sorted(weights._weights.keys(), key=str)
             return weights
         sizes = [int(np.prod(shape)) for shape in self.shape_dict.values()]
+        weights._weights[k0] = self._decrypt_floats(dv, sizes, mode, add_idx, minus_idx).download(np.float64, n)
+        return self.unflatten_weights(weights)
+
+    def _decrypt_prefixes(self, mode):
+        """The prefix lists set_idx_list left behind: those of the online decrypt, or -- mode "ctx" -- the extras the prepared masks do
+        not cover (dropouts; empty when nobody dropped out)."""
+        c = self.cipher
+        if c.masking_scheme != "double":
+            return [], [c._idx_of(p) for p in c.index_prefix_for_minus]
+        add_idx = [c._idx_of(p) for p in (c.index_prefix_for_add or [])]
+        minus_idx = [c._idx_of(p) for p in (c.index_prefix_for_minus or [])]
+        if not add_idx and not minus_idx and mode != "ctx":
+            raise KeyError('add')
+        return add_idx, minus_idx
+
+    def _decrypt_floats(self, dv, sizes, mode, add_idx, minus_idx):
+        """The fused back end of the flattened aggregate `dv` (in HBM, L limbs): the model's float64 values in walking order as a device
+        buffer -- batched: the sum(sizes) values of the layers (unbatch + `[:size]` + unquantise in one launch behind the decrypt); else
+        all n elements, the last layer running to the end (decrypt + unquantise in one launch).  mode "ctx": with the ctx's prepared
+        decrypt masks, the prefix lists being the extras, in ONE launch either way (two with extras); the cache is consumed."""
+        from . import cipher as _cipher_mod
+        q, c = self.quantizer, self.cipher
+        eng, n = c.engine, len(dv)
+        if mode == "ctx":
+            c._check_prepared_len(c.next_iter_decrypt_prepared['add'], n)          # (the call-by-call decrypt's error; the cache stays)
+        if self.batch:
+            factor = int(np.ceil(np.log2(q.num_clients)))
+            field_bits = q.element_bits + factor
+            bs = self.int_bits // field_bits
+            if sum((s_ + bs - 1) // bs for s_ in sizes) != n:
+                raise ValueError(f"the aggregate has {n} elements, the batched layers describe {sum((s_ + bs - 1) // bs for s_ in sizes)}")
+            layers = [(s_, None, q.alpha_list[li], False) for li, s_ in enumerate(sizes)]
+            dout = eng.alloc(max(8 * sum(sizes), 16))
+            if mode == "ctx":
+                eng.decrypt_prepared_unbatch_unquantize_model_dev(c.iter_index, add_idx, minus_idx, _cipher_mod.N_JOBS, layers, q.element_bits, field_bits,
+                                                                  q.num_clients, dv.buf, n, dout)
+            else:
+                dec = eng.alloc_vec(max(n, 1))
+                if n:
+                    eng.decrypt_dev(c.iter_index, add_idx, minus_idx, n, _cipher_mod.N_JOBS, dv.buf, dec)
+                eng.unbatch_unquantize_model_dev(layers, q.element_bits, field_bits, q.num_clients, dec, n, dout)
+            self._decrypt_done(mode)
+            return dout
         if sum(sizes) > n:
             raise ValueError(f"the aggregate has {n} elements, shape_dict describes {sum(sizes)}")
         table, at = [], 0
@@ -448,12 +546,14 @@ class FlasheClient(object):
             table.append((at, None, q.alpha_list[li], False))
             at += size
         dout = eng.alloc(max(8 * n, 16))
-        if n:
+        if mode == "ctx":
+            eng.decrypt_prepared_unquantize_model_dev(c.iter_index, add_idx, minus_idx, n, _cipher_mod.N_JOBS, dv.buf, table, q.element_bits,
+                                                      q.num_clients, dout)
+        elif n:
             eng.decrypt_unquantize_model_dev(c.iter_index, add_idx, minus_idx, n, _cipher_mod.N_JOBS, 0, n, dv.buf, table, q.element_bits,
                                              q.num_clients, dout)
-        out = dout.download(np.float64, n)
-        weights._weights[k0] = out
-        return self.unflatten_weights(weights)
+        self._decrypt_done(mode)
+        return dout
 
     # ---- a framework's device tensors either side of the client step (new; interop.py) ---------------------------------------
     def _quantize_encrypt_tensors(self, weights, device, normalize):
@@ -470,8 +570,10 @@ class FlasheClient(object):
         if "zzz" in weights._weights:
             raise TypeError("framework tensors are not supported by the sparse job (the 'zzz' layer)")
         if not self._fusable(weights):
-            raise TypeError("framework tensors need the fused client step (fuse=True, no precomputed encrypt masks, no location masks)")
+            raise TypeError("framework tensors need the fused client step (fuse=True, no location masks, precomputed encrypt masks only as "
+                            "the handles prepare_encrypt leaves)")
         eng = c.engine
+        mode = self._prepared_mode(c.next_iter_encrypt_prepared)
         codes = {"float32": TENSOR_F32, "float64": TENSOR_F64, "float16": TENSOR_F16, "bfloat16": TENSOR_BF16}
         order = list(weights.walking_order)
         layers = []                                   # (ForeignArray or host flat array, shape, NumPy dtype of its host copy)
@@ -539,14 +641,21 @@ class FlasheClient(object):
             bs = self.int_bits // field_bits
             q.shape_list = [shape_dict[k] for k in order]
             n_elems = sum((s_ + bs - 1) // bs for s_ in sizes)
+            if mode == "ctx":
+                self._refuse_prepared_len(n_elems, n)
             du = (eng.numpy_random_dev(n) if dev_rng and n >= DEVICE_RNG_MIN else eng.upload(np.random.random(n))) if n else eng.alloc(16)
-            pt = eng.alloc_vec(max(n_elems, 1))
-            eng.quantize_batch_tensors_dev(table, n, q.element_bits, field_bits, du, n_elems, pt)
             ct = DeviceVector(eng, n_elems)
-            if n_elems:
-                eng.encrypt_dev(c.iter_index, c.idx, scheme, n_elems, _cipher_mod.N_JOBS, pt, eng.limbs, ct.buf)
+            if mode == "ctx":
+                eng.quantize_batch_encrypt_prepared_tensors_dev(table, n, q.element_bits, field_bits, du, n_elems, ct.buf)
+            else:
+                pt = eng.alloc_vec(max(n_elems, 1))
+                eng.quantize_batch_tensors_dev(table, n, q.element_bits, field_bits, du, n_elems, pt)
+                if n_elems:
+                    eng.encrypt_dev(c.iter_index, c.idx, scheme, n_elems, _cipher_mod.N_JOBS, pt, eng.limbs, ct.buf)
             self.shape_dict = {k: ((s_ + bs - 1) // bs,) for k, s_ in zip(order, sizes)}
         else:
+            if mode == "ctx":
+                self._refuse_prepared_len(n, n)
             ct = DeviceVector(eng, n)
             at = 0
             while at < len(order):                    # the draws in runs of whole layers, as in quantize_encrypt
@@ -557,10 +666,16 @@ class FlasheClient(object):
                 if tot:
                     du = eng.numpy_random_dev(tot) if dev_rng and tot >= DEVICE_RNG_MIN else eng.upload(np.random.random(tot))
                     first = table[at][0]
-                    eng.quantize_encrypt_tensors_dev(c.iter_index, c.idx, scheme, n, _cipher_mod.N_JOBS, first, tot, table, q.element_bits, du,
-                                                     ct.ptr + first * eng.limbs * 8)
+                    if mode == "ctx":
+                        eng.quantize_encrypt_prepared_tensors_dev(n, first, tot, table, q.element_bits, du, ct.ptr + first * eng.limbs * 8)
+                    else:
+                        eng.quantize_encrypt_tensors_dev(c.iter_index, c.idx, scheme, n, _cipher_mod.N_JOBS, first, tot, table, q.element_bits, du,
+                                                         ct.ptr + first * eng.limbs * 8)
                 at = end
+            if mode == "ctx" and n == 0:
+                eng.prepared_discard(eng.PREPARED_ENCRYPT)
             self.shape_dict = shape_dict
+        self._encrypt_done(mode)
         eng.hold(keep)
         for k in order:
             del weights._weights[k]
@@ -575,15 +690,18 @@ class FlasheClient(object):
         float64 -> float32 -> 16 bits, each step round to nearest even -- and, with unnormalize, sums every layer the way np.mean /
         np.std do, so past_layer_mean_list / past_layer_std_list get the host path's np.float64 values.  Only those 16 bytes per layer come
         back to the host.  Own-stream engines synchronise before returning."""
-        from . import cipher as _cipher_mod
         from . import interop
         from ._lib import TENSOR_BF16, TENSOR_F16, TENSOR_F32, TENSOR_F64, TENSOR_SHIFT
         from .engine import DeviceVector
         q, c = self.quantizer, self.cipher
         if c.masks is not None or "zzz" in weights._weights:
             raise TypeError("out= is not supported by the sparse job")
-        if not (self.fuse and c.prp_seed is not None and not c.next_iter_decrypt_prepared):
-            raise TypeError("out= needs the fused client step (fuse=True, no precomputed decrypt masks)")
+        mode = False
+        if self.fuse and c.prp_seed is not None:
+            c._reconcile_prepared()
+            mode = self._prepared_mode(c.next_iter_decrypt_prepared)
+        if mode is False:
+            raise TypeError("out= needs the fused client step (fuse=True, precomputed decrypt masks only as the handles prepare_decrypt leaves)")
         if self.shape_dict is None:
             raise ValueError("decrypt_unquantize(out=...) needs the layer shapes a quantize_encrypt left behind (shape_dict)")
         eng = c.engine
@@ -603,13 +721,7 @@ class FlasheClient(object):
             if tuple(fa.shape) != tuple(shape):
                 raise ValueError(f"out[{k!r}]: expected shape {tuple(shape)}, got {tuple(fa.shape)}")
             fas.append(fa)
-        if c.masking_scheme == "double":
-            add_idx = [c._idx_of(p) for p in (c.index_prefix_for_add or [])]
-            minus_idx = [c._idx_of(p) for p in (c.index_prefix_for_minus or [])]
-            if not add_idx and not minus_idx:
-                raise KeyError('add')
-        else:
-            add_idx, minus_idx = [], [c._idx_of(p) for p in c.index_prefix_for_minus]
+        add_idx, minus_idx = self._decrypt_prefixes(mode)
         k0 = weights.walking_order[0]
         v = weights._weights[k0]
         keep = [fa.keep for fa in fas]
@@ -622,32 +734,9 @@ class FlasheClient(object):
                 v = v.reshape(-1)
         dv, _kind = c._on_device(v, full_width=True)
         dv = c._as_wide(dv)
-        n = len(dv)
         sizes = [int(np.prod(shape, dtype=np.int64)) for shape in shapes]
         n_values = sum(sizes)
-        if self.batch:
-            factor = int(np.ceil(np.log2(q.num_clients)))
-            field_bits = q.element_bits + factor
-            bs = self.int_bits // field_bits
-            if sum((s_ + bs - 1) // bs for s_ in sizes) != n:
-                raise ValueError(f"the aggregate has {n} elements, the batched layers describe {sum((s_ + bs - 1) // bs for s_ in sizes)}")
-            dec = eng.alloc_vec(max(n, 1))
-            if n:
-                eng.decrypt_dev(c.iter_index, add_idx, minus_idx, n, _cipher_mod.N_JOBS, dv.buf, dec)
-            dout = eng.alloc(max(8 * n_values, 16))
-            eng.unbatch_unquantize_model_dev([(s_, None, q.alpha_list[li], False) for li, s_ in enumerate(sizes)], q.element_bits, field_bits,
-                                             q.num_clients, dec, n, dout)
-        else:
-            if n_values > n:
-                raise ValueError(f"the aggregate has {n} elements, shape_dict describes {n_values}")
-            table, at = [], 0
-            for li, size in enumerate(sizes):
-                table.append((at, None, q.alpha_list[li], False))
-                at += size
-            dout = eng.alloc(max(8 * n, 16))
-            if n:
-                eng.decrypt_unquantize_model_dev(c.iter_index, add_idx, minus_idx, n, _cipher_mod.N_JOBS, 0, n, dv.buf, table, q.element_bits,
-                                                 q.num_clients, dout)
+        dout = self._decrypt_floats(dv, sizes, mode, add_idx, minus_idx)
         layers, at = [], 0
         for li, (fa, size) in enumerate(zip(fas, sizes)):
             shift = float(q.past_layer_mean_list[li]) if unnormalize else 0.0

@@ -562,8 +562,10 @@ class FlasheCipher(object):
         eng = self._engine
         if self.masks is not None:
             raise TypeError("framework tensors are not supported by the sparse job (location masks set on the cipher)")
-        if self.next_iter_encrypt_prepared or self.next_iter_decrypt_prepared:
-            raise TypeError("framework tensors are not supported with precomputed masks (prepare_encrypt / prepare_decrypt)")
+        # (the masks prepare_encrypt / prepare_decrypt leave live in the engine's ctx: the combine reads them beside the tensor)
+        if any(not isinstance(h, _CtxMask) for d in (self.next_iter_encrypt_prepared, self.next_iter_decrypt_prepared) for h in d.values()):
+            raise TypeError("framework tensors are not supported with precomputed masks held as plain arrays (only with the handles "
+                            "prepare_encrypt / prepare_decrypt leave)")
         keep, args = [], []
         for v in values:
             from . import interop

@@ -1499,36 +1499,26 @@ static int stage_tensor_front(flashe_ctx *ctx, uint64_t n, const flashe_tensor_l
     return FLASHE_OK;
 }
 
-int flashe_quantize_encrypt_tensors_dev(flashe_ctx *ctx, uint32_t iter, uint32_t idx, int scheme, uint64_t n, uint32_t n_jobs, uint64_t first,
-                                        uint64_t count, const flashe_tensor_layer *layers, int n_layers, int element_bits, const double *u_dev,
-                                        uint64_t *ct_dev)
+// the codec table of the model-wide front end from a checked tensor table: alphas checked, the stage pass run (what the prepared and
+// the online forms share)
+static int tensor_codec_layers(flashe_ctx *ctx, uint64_t n, const flashe_tensor_layer *layers, int n_layers, uint64_t first, uint64_t count,
+                               std::vector<flashe_codec_layer> &cl)
 {
-    CHECK_CTX(ctx);
-    // the checks of flashe_quantize_encrypt_model_dev that do not need the table, before anything is launched
-    if (int rc = check_scheme(ctx, scheme)) return rc;
-    if (count && (!u_dev || !ct_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if (element_bits < 1 || element_bits > 62 || element_bits > ctx->int_bits)
-        return fail(ctx, FLASHE_EINVAL, "element_bits must be in [1, min(62, int_bits)], got %d", element_bits);
-    int rc = check_prf_args(ctx, 1, scheme, n_jobs, ct_dev, nullptr, 0);
-    if (rc || (rc = check_range(ctx, n, first, count)) || (rc = check_tensor_layers(ctx, n, layers, n_layers))) return rc;
-    if ((rc = check_double_idx(ctx, scheme, &idx, 1))) return rc;
     for (int l = 0; l < n_layers; l++)
         if (!(layers[l].alpha > 0) && (l + 1 < n_layers ? layers[l + 1].start : n) > layers[l].start)
             return fail(ctx, FLASHE_EINVAL, "layer %d: alpha must be positive", l);
     std::vector<const void *> x;
     std::vector<int> f64;
-    if ((rc = stage_tensor_front(ctx, n, layers, n_layers, first, count, x, f64))) return rc;
-    std::vector<flashe_codec_layer> cl(static_cast<size_t>(n_layers));
+    if (int rc = stage_tensor_front(ctx, n, layers, n_layers, first, count, x, f64)) return rc;
+    cl.resize(static_cast<size_t>(n_layers));
     for (int l = 0; l < n_layers; l++) cl[l] = flashe_codec_layer{layers[l].start, x[l], layers[l].alpha, f64[l], 0};
-    return flashe_quantize_encrypt_model_dev(ctx, iter, idx, scheme, n, n_jobs, first, count, cl.data(), n_layers, element_bits, u_dev, ct_dev);
+    return FLASHE_OK;
 }
 
-int flashe_quantize_batch_tensors_dev(flashe_ctx *ctx, const flashe_tensor_layer *layers, int n_layers, uint64_t n_values, int element_bits,
-                                      int field_bits, const double *u_dev, uint64_t n_elems, uint64_t *out_dev)
+// the batched form: the checks of flashe_quantize_batch_model_dev that do not need the staged table, the stage pass, the batch table
+static int tensor_batch_layers(flashe_ctx *ctx, const flashe_tensor_layer *layers, int n_layers, uint64_t n_values, int element_bits, int field_bits,
+                               const double *u_dev, uint64_t n_elems, const uint64_t *out_dev, std::vector<flashe_batch_layer> &bl)
 {
-    CHECK_CTX(ctx);
-    int rc = check_tensor_layers(ctx, n_values, layers, n_layers);
-    if (rc) return rc;
     if (element_bits < 1 || element_bits > 62 || field_bits < element_bits || field_bits > ctx->int_bits)
         return fail(ctx, FLASHE_EINVAL, "need 1 <= element_bits <= field_bits <= int_bits (element_bits <= 62)");
     const uint64_t bs = static_cast<uint64_t>(ctx->int_bits / field_bits);
@@ -1545,10 +1535,38 @@ int flashe_quantize_batch_tensors_dev(flashe_ctx *ctx, const flashe_tensor_layer
         return fail(ctx, FLASHE_EINVAL, "misaligned vector");
     std::vector<const void *> x;
     std::vector<int> f64;
-    if ((rc = stage_tensor_front(ctx, n_values, layers, n_layers, 0, n_values, x, f64))) return rc;
-    std::vector<flashe_batch_layer> bl(static_cast<size_t>(n_layers));
+    if (int rc = stage_tensor_front(ctx, n_values, layers, n_layers, 0, n_values, x, f64)) return rc;
+    bl.resize(static_cast<size_t>(n_layers));
     for (int l = 0; l < n_layers; l++)
         bl[l] = flashe_batch_layer{(l + 1 < n_layers ? layers[l + 1].start : n_values) - layers[l].start, x[l], layers[l].alpha, f64[l], 0};
+    return FLASHE_OK;
+}
+
+int flashe_quantize_encrypt_tensors_dev(flashe_ctx *ctx, uint32_t iter, uint32_t idx, int scheme, uint64_t n, uint32_t n_jobs, uint64_t first,
+                                        uint64_t count, const flashe_tensor_layer *layers, int n_layers, int element_bits, const double *u_dev,
+                                        uint64_t *ct_dev)
+{
+    CHECK_CTX(ctx);
+    // the checks of flashe_quantize_encrypt_model_dev that do not need the table, before anything is launched
+    if (int rc = check_scheme(ctx, scheme)) return rc;
+    if (count && (!u_dev || !ct_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
+    if (element_bits < 1 || element_bits > 62 || element_bits > ctx->int_bits)
+        return fail(ctx, FLASHE_EINVAL, "element_bits must be in [1, min(62, int_bits)], got %d", element_bits);
+    int rc = check_prf_args(ctx, 1, scheme, n_jobs, ct_dev, nullptr, 0);
+    if (rc || (rc = check_range(ctx, n, first, count)) || (rc = check_tensor_layers(ctx, n, layers, n_layers))) return rc;
+    if ((rc = check_double_idx(ctx, scheme, &idx, 1))) return rc;
+    std::vector<flashe_codec_layer> cl;
+    if ((rc = tensor_codec_layers(ctx, n, layers, n_layers, first, count, cl))) return rc;
+    return flashe_quantize_encrypt_model_dev(ctx, iter, idx, scheme, n, n_jobs, first, count, cl.data(), n_layers, element_bits, u_dev, ct_dev);
+}
+
+int flashe_quantize_batch_tensors_dev(flashe_ctx *ctx, const flashe_tensor_layer *layers, int n_layers, uint64_t n_values, int element_bits,
+                                      int field_bits, const double *u_dev, uint64_t n_elems, uint64_t *out_dev)
+{
+    CHECK_CTX(ctx);
+    int rc = check_tensor_layers(ctx, n_values, layers, n_layers);
+    std::vector<flashe_batch_layer> bl;
+    if (rc || (rc = tensor_batch_layers(ctx, layers, n_layers, n_values, element_bits, field_bits, u_dev, n_elems, out_dev, bl))) return rc;
     return flashe_quantize_batch_model_dev(ctx, bl.data(), n_layers, element_bits, field_bits, u_dev, n_elems, out_dev);
 }
 
@@ -1809,6 +1827,172 @@ int flashe_decrypt_prepared_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *
         if (n_add || n_minus) HIP_TRY(ctx, prf_lists(ctx, iter, add_idx, n_add, minus_idx, n_minus, n, n_jobs, 0, n, out_dev, ctx->limbs, out_dev));
     }
     pr.valid = false;                                                    // consumed (:573-580)
+    return FLASHE_OK;
+}
+
+// ---- the fused client step with the ctx's precomputed masks (jzf_aggregator.py:721-741, :881-899 with next_iter_*_prepared populated,
+// jzf_flashe.py:456-488, :537-582): the model-wide codec and the combine of the two calls above in one pass each, no AES ----
+static int check_prepared(flashe_ctx *ctx, const flashe_ctx::Prepared &pr, uint64_t n, const char *what)
+{
+    if (!pr.valid) return fail(ctx, FLASHE_EINVAL, "no prepared %s masks: call flashe_prepare_%s first (they are consumed by one %s)", what, what, what);
+    // (a length mismatch leaves the cache in place, as NumPy's broadcast error does in the reference, jzf_flashe.py:480)
+    if (n != pr.n) return fail(ctx, FLASHE_EINVAL, "the prepared masks cover %llu elements, the vector has %llu", static_cast<unsigned long long>(pr.n),
+                               static_cast<unsigned long long>(n));
+    return FLASHE_OK;
+}
+
+// element `first` of a cached mask (null: a single-mask cache has no minus stream)
+static const uint64_t *prepared_at(const flashe_ctx *ctx, const flashe_ctx::Buf &b, bool held, uint64_t first)
+{
+    return held ? static_cast<const uint64_t *>(b.p) + first * static_cast<uint64_t>(ctx->limbs) : nullptr;
+}
+
+int flashe_quantize_encrypt_prepared_model_dev(flashe_ctx *ctx, uint64_t n, uint64_t first, uint64_t count, const flashe_codec_layer *layers,
+                                               int n_layers, int element_bits, const double *u_dev, uint64_t *ct_dev)
+{
+    CHECK_CTX(ctx);
+    flashe_ctx::Prepared &pr = ctx->prep_enc;
+    int rc = check_prepared(ctx, pr, n, "encrypt");
+    if (rc) return rc;
+    if (count && (!u_dev || !ct_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
+    if (element_bits < 1 || element_bits > 62 || element_bits > ctx->int_bits)
+        return fail(ctx, FLASHE_EINVAL, "element_bits must be in [1, min(62, int_bits)], got %d", element_bits);
+    if ((rc = check_prf_args(ctx, 0, 0, 1, ct_dev, nullptr, 0)) || (rc = check_range(ctx, n, first, count))) return rc;
+    if (reinterpret_cast<uintptr_t>(u_dev) & 7u) return fail(ctx, FLASHE_EINVAL, "u_dev must be 8-byte aligned");
+    const CodecLayer *tab = nullptr;
+    int n_tab = 0;
+    if ((rc = stage_codec_layers(ctx, n, layers, n_layers, true, element_bits, 1, first, count, &tab, &n_tab))) return rc;
+    if (count) {
+        Codec cq{};
+        cq.x = tab; cq.u = u_dev; cq.layers = tab; cq.n_layers = n_tab; cq.k0 = first;
+        HIP_TRY(ctx, launch_quantize_combine_model(ctx->env, count, cq, prepared_at(ctx, pr.add, true, first), prepared_at(ctx, pr.minus, pr.has_minus, first),
+                                                   ct_dev));
+    }
+    if (first + count == n) pr.valid = false;                           // the call that completes the vector consumes the cache (:483-486)
+    return FLASHE_OK;
+}
+
+int flashe_quantize_encrypt_prepared_tensors_dev(flashe_ctx *ctx, uint64_t n, uint64_t first, uint64_t count, const flashe_tensor_layer *layers,
+                                                 int n_layers, int element_bits, const double *u_dev, uint64_t *ct_dev)
+{
+    CHECK_CTX(ctx);
+    // the checks of the codec-layer form that do not need the table, before the stage pass launches
+    int rc = check_prepared(ctx, ctx->prep_enc, n, "encrypt");
+    if (rc) return rc;
+    if (count && (!u_dev || !ct_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
+    if (element_bits < 1 || element_bits > 62 || element_bits > ctx->int_bits)
+        return fail(ctx, FLASHE_EINVAL, "element_bits must be in [1, min(62, int_bits)], got %d", element_bits);
+    if ((rc = check_prf_args(ctx, 0, 0, 1, ct_dev, nullptr, 0)) || (rc = check_range(ctx, n, first, count)) || (rc = check_tensor_layers(ctx, n, layers, n_layers)))
+        return rc;
+    if (reinterpret_cast<uintptr_t>(u_dev) & 7u) return fail(ctx, FLASHE_EINVAL, "u_dev must be 8-byte aligned");
+    std::vector<flashe_codec_layer> cl;
+    if ((rc = tensor_codec_layers(ctx, n, layers, n_layers, first, count, cl))) return rc;
+    return flashe_quantize_encrypt_prepared_model_dev(ctx, n, first, count, cl.data(), n_layers, element_bits, u_dev, ct_dev);
+}
+
+int flashe_quantize_batch_encrypt_prepared_model_dev(flashe_ctx *ctx, const flashe_batch_layer *layers, int n_layers, int element_bits, int field_bits,
+                                                     const double *u_dev, uint64_t n_elems, uint64_t *ct_dev)
+{
+    CHECK_CTX(ctx);
+    flashe_ctx::Prepared &pr = ctx->prep_enc;
+    int rc = check_prepared(ctx, pr, n_elems, "encrypt");
+    if (rc) return rc;
+    const BatchLayer *tab = nullptr;
+    int n_tab = 0;
+    uint64_t e = 0, v = 0;
+    if ((rc = stage_batch_layers(ctx, layers, n_layers, true, element_bits, field_bits, 1, &e, &v, &tab, &n_tab))) return rc;
+    if (e != n_elems) return fail(ctx, FLASHE_EINVAL, "the layers batch into %llu elements, n_elems says %llu", static_cast<unsigned long long>(e),
+                                  static_cast<unsigned long long>(n_elems));
+    if (n_elems && (!u_dev || !ct_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
+    if ((ctx->limbs == 2 && !aligned16(ct_dev)) || (reinterpret_cast<uintptr_t>(ct_dev) & 7u) || (reinterpret_cast<uintptr_t>(u_dev) & 7u))
+        return fail(ctx, FLASHE_EINVAL, "misaligned vector");
+    if (n_elems)
+        HIP_TRY(ctx, launch_quantize_batch_combine_model(ctx->env, tab, n_tab, field_bits, u_dev, n_elems, prepared_at(ctx, pr.add, true, 0),
+                                                         prepared_at(ctx, pr.minus, pr.has_minus, 0), ct_dev));
+    pr.valid = false;
+    return FLASHE_OK;
+}
+
+int flashe_quantize_batch_encrypt_prepared_tensors_dev(flashe_ctx *ctx, const flashe_tensor_layer *layers, int n_layers, uint64_t n_values,
+                                                       int element_bits, int field_bits, const double *u_dev, uint64_t n_elems, uint64_t *ct_dev)
+{
+    CHECK_CTX(ctx);
+    int rc = check_prepared(ctx, ctx->prep_enc, n_elems, "encrypt");
+    std::vector<flashe_batch_layer> bl;
+    if (rc || (rc = check_tensor_layers(ctx, n_values, layers, n_layers)) ||
+        (rc = tensor_batch_layers(ctx, layers, n_layers, n_values, element_bits, field_bits, u_dev, n_elems, ct_dev, bl)))
+        return rc;
+    return flashe_quantize_batch_encrypt_prepared_model_dev(ctx, bl.data(), n_layers, element_bits, field_bits, u_dev, n_elems, ct_dev);
+}
+
+// The way back.  The prefixes the precompute does not cover (dropouts) go first, into ctx scratch: the sum mod 2^b is the same in either
+// order, and the codec pass then reads every cached mask once.  *src = what that pass reads (in_dev when nobody dropped out).
+static int prepared_extras(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx, int n_minus, uint64_t n,
+                           uint32_t n_jobs, const uint64_t *in_dev, const uint64_t **src)
+{
+    *src = in_dev;
+    if (n == 0 || (n_add == 0 && n_minus == 0)) return FLASHE_OK;
+    if (int rc = ensure(ctx, ctx->stream_tmp, vec_bytes(ctx, n))) return rc;
+    uint64_t *tmp = static_cast<uint64_t *>(ctx->stream_tmp.p);
+    HIP_TRY(ctx, prf_lists(ctx, iter, add_idx, n_add, minus_idx, n_minus, n, n_jobs, 0, n, in_dev, ctx->limbs, tmp));
+    *src = tmp;
+    return FLASHE_OK;
+}
+
+int flashe_decrypt_prepared_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx,
+                                                 int n_minus, uint64_t n, uint32_t n_jobs, const uint64_t *in_dev, const flashe_codec_layer *layers,
+                                                 int n_layers, int element_bits, int num_clients, double *out_dev)
+{
+    CHECK_CTX(ctx);
+    flashe_ctx::Prepared &pr = ctx->prep_dec;
+    int rc = check_prepared(ctx, pr, n, "decrypt");
+    if (rc) return rc;
+    if (n && (!in_dev || !out_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
+    if (num_clients < 1) return fail(ctx, FLASHE_EINVAL, "num_clients must be >= 1");
+    if ((rc = check_codec_bits(ctx, element_bits)) || (rc = check_prf_args(ctx, n_add, n_minus, n_jobs, in_dev, in_dev, ctx->limbs))) return rc;
+    if (reinterpret_cast<uintptr_t>(out_dev) & 7u) return fail(ctx, FLASHE_EINVAL, "out_dev must be 8-byte aligned");
+    if ((n_add && !add_idx) || (n_minus && !minus_idx)) return fail(ctx, FLASHE_EINVAL, "null prefix list");
+    const CodecLayer *tab = nullptr;
+    int n_tab = 0;
+    if ((rc = stage_codec_layers(ctx, n, layers, n_layers, false, element_bits, num_clients, 0, n, &tab, &n_tab))) return rc;
+    if (n) {
+        const uint64_t *src = nullptr;
+        if ((rc = prepared_extras(ctx, iter, add_idx, n_add, minus_idx, n_minus, n, n_jobs, in_dev, &src))) return rc;
+        Codec cq{};
+        cq.fout = out_dev; cq.layers = tab; cq.n_layers = n_tab; cq.k0 = 0;
+        HIP_TRY(ctx, launch_combine_unquantize_model(ctx->env, n, src, prepared_at(ctx, pr.add, true, 0), prepared_at(ctx, pr.minus, pr.has_minus, 0), cq,
+                                                     out_dev));
+    }
+    pr.valid = false;                                                    // consumed (:573-580)
+    return FLASHE_OK;
+}
+
+int flashe_decrypt_prepared_unbatch_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx,
+                                                         int n_minus, uint32_t n_jobs, const flashe_batch_layer *layers, int n_layers, int element_bits,
+                                                         int field_bits, int num_clients, const uint64_t *in_dev, uint64_t n_elems, double *out_dev)
+{
+    CHECK_CTX(ctx);
+    flashe_ctx::Prepared &pr = ctx->prep_dec;
+    int rc = check_prepared(ctx, pr, n_elems, "decrypt");
+    if (rc) return rc;
+    if (num_clients < 1) return fail(ctx, FLASHE_EINVAL, "num_clients must be >= 1");
+    if ((rc = check_prf_args(ctx, n_add, n_minus, n_jobs, in_dev, in_dev, ctx->limbs))) return rc;
+    if ((n_add && !add_idx) || (n_minus && !minus_idx)) return fail(ctx, FLASHE_EINVAL, "null prefix list");
+    const BatchLayer *tab = nullptr;
+    int n_tab = 0;
+    uint64_t e = 0, v = 0;
+    if ((rc = stage_batch_layers(ctx, layers, n_layers, false, element_bits, field_bits, num_clients, &e, &v, &tab, &n_tab))) return rc;
+    if (e != n_elems) return fail(ctx, FLASHE_EINVAL, "the layers batch into %llu elements, n_elems says %llu", static_cast<unsigned long long>(e),
+                                  static_cast<unsigned long long>(n_elems));
+    if (v && (!in_dev || !out_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
+    if (reinterpret_cast<uintptr_t>(out_dev) & 7u) return fail(ctx, FLASHE_EINVAL, "out_dev must be 8-byte aligned");
+    if (v) {
+        const uint64_t *src = nullptr;
+        if ((rc = prepared_extras(ctx, iter, add_idx, n_add, minus_idx, n_minus, n_elems, n_jobs, in_dev, &src))) return rc;
+        HIP_TRY(ctx, launch_combine_unbatch_unquantize_model(ctx->env, tab, n_tab, field_bits, src, prepared_at(ctx, pr.add, true, 0),
+                                                             prepared_at(ctx, pr.minus, pr.has_minus, 0), v, out_dev));
+    }
+    pr.valid = false;
     return FLASHE_OK;
 }
 

@@ -272,6 +272,175 @@ hipError_t launch_unquantize(const LaunchEnv &env, uint64_t n, const uint64_t *v
     return hipGetLastError();
 }
 
+// ---- the client step with the ctx's precomputed masks (jzf_flashe.py:456-488, :537-582 with the caches populated): the codec of the
+// model-wide kernels above and the combine of stream.hip in one pass, no AES.  Masks read once are non-temporal loads, 16 bytes per
+// 128-bit element; add / minus / ct / in address the launch's first element ----
+template <bool WIDE>
+__global__ __launch_bounds__(kStreamThreads) void quantize_combine_model_kernel(uint64_t count, const Codec cq, const uint64_t *__restrict__ add,
+                                                                                const uint64_t *__restrict__ minus, uint64_t *out, uint64_t mask_lo,
+                                                                                uint64_t mask_hi)
+{
+    const u128 mask = (static_cast<u128>(mask_hi) << 64) | mask_lo;
+    for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * kStreamThreads + threadIdx.x; k < count; k += static_cast<uint64_t>(gridDim.x) * kStreamThreads) {
+        const uint64_t q = codec_quantize(cq, k);
+        if (WIDE) {
+            u128 v = static_cast<u128>(q) + ld128_nt(add + 2 * k);
+            if (minus) v -= ld128_nt(minus + 2 * k);
+            st128_nt(out + 2 * k, v & mask);
+        } else {
+            uint64_t v = q + __builtin_nontemporal_load(add + k);
+            if (minus) v -= __builtin_nontemporal_load(minus + k);
+            out[k] = v & mask_lo;
+        }
+    }
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(kStreamThreads) void combine_unquantize_model_kernel(uint64_t count, const uint64_t *__restrict__ in,
+                                                                                  const uint64_t *__restrict__ add, const uint64_t *__restrict__ minus,
+                                                                                  const Codec cq, double *out, uint64_t mask_lo, uint64_t mask_hi)
+{
+    const u128 mask = (static_cast<u128>(mask_hi) << 64) | mask_lo;
+    for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * kStreamThreads + threadIdx.x; k < count; k += static_cast<uint64_t>(gridDim.x) * kStreamThreads) {
+        u128 v;
+        if (WIDE) {
+            v = ld128_nt(in + 2 * k) + ld128_nt(add + 2 * k);
+            if (minus) v -= ld128_nt(minus + 2 * k);
+            v &= mask;
+        } else {
+            uint64_t x = __builtin_nontemporal_load(in + k) + __builtin_nontemporal_load(add + k);
+            if (minus) x -= __builtin_nontemporal_load(minus + k);
+            v = static_cast<u128>(x & mask_lo);
+        }
+        __builtin_nontemporal_store(codec_unquantize(cq, k, v), out + k);
+    }
+}
+
+// the batched walks of quantize_batch_model_kernel / unbatch_unquantize_model_kernel with the combine folded in.  On the way back the
+// bs lanes of one element read it and its masks side by side: plain loads, so the element stays in cache for its neighbours
+template <bool WIDE>
+__global__ __launch_bounds__(kStreamThreads) void quantize_batch_combine_model_kernel(const BatchLayer *__restrict__ layers, int n_layers, int bs,
+                                                                                      int field_bits, const double *__restrict__ u, uint64_t n_elems,
+                                                                                      const uint64_t *__restrict__ add, const uint64_t *__restrict__ minus,
+                                                                                      uint64_t *out, uint64_t mask_lo, uint64_t mask_hi)
+{
+    const u128 mask = (static_cast<u128>(mask_hi) << 64) | mask_lo;
+    for (uint64_t e = static_cast<uint64_t>(blockIdx.x) * kStreamThreads + threadIdx.x; e < n_elems; e += static_cast<uint64_t>(gridDim.x) * kStreamThreads) {
+        const BatchLayer *Ly = batch_layer_of<false>(layers, n_layers, e);
+        const uint64_t j0 = (e - Ly->elem_start) * static_cast<uint64_t>(bs);
+        u128 t = 0;
+        for (int i = 0; i < bs; i++) {
+            const uint64_t j = j0 + i;
+            uint64_t v = 0;
+            if (j < Ly->size) {
+                const double draw = u[Ly->value_start + j];
+                v = Ly->x_is_f64 ? quantize_one<double>(*FLASHE_GLOBAL(const double, static_cast<const double *>(Ly->x) + j), Ly->p0, Ly->p1, Ly->p2, draw)
+                                 : quantize_one<float>(*FLASHE_GLOBAL(const float, static_cast<const float *>(Ly->x) + j), static_cast<float>(Ly->p0),
+                                                       static_cast<float>(Ly->p1), static_cast<float>(Ly->p2), draw);
+            }
+            t = (field_bits >= 128 ? 0 : t << field_bits) + v;
+        }
+        if (WIDE) {
+            t += ld128_nt(add + 2 * e);
+            if (minus) t -= ld128_nt(minus + 2 * e);
+            st128_nt(out + 2 * e, t & mask);
+        } else {
+            uint64_t x = static_cast<uint64_t>(t) + __builtin_nontemporal_load(add + e);
+            if (minus) x -= __builtin_nontemporal_load(minus + e);
+            out[e] = x & mask_lo;
+        }
+    }
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(kStreamThreads) void combine_unbatch_unquantize_model_kernel(const BatchLayer *__restrict__ layers, int n_layers, int bs,
+                                                                                          int field_bits, const uint64_t *__restrict__ in,
+                                                                                          const uint64_t *__restrict__ add, const uint64_t *__restrict__ minus,
+                                                                                          uint64_t n_values, double *out, uint64_t mask_lo, uint64_t mask_hi)
+{
+#pragma clang fp contract(off)
+    const u128 mask = (static_cast<u128>(mask_hi) << 64) | mask_lo;
+    const u128 mk = field_bits >= 128 ? ~static_cast<u128>(0) : ((static_cast<u128>(1) << field_bits) - 1);
+    for (uint64_t g = static_cast<uint64_t>(blockIdx.x) * kStreamThreads + threadIdx.x; g < n_values; g += static_cast<uint64_t>(gridDim.x) * kStreamThreads) {
+        const BatchLayer *Ly = batch_layer_of<true>(layers, n_layers, g);
+        const uint64_t j = g - Ly->value_start;
+        if (j >= Ly->size) continue;                                    // (cannot happen for a well-formed table)
+        const uint64_t e = Ly->elem_start + j / static_cast<uint64_t>(bs);
+        const int slot = static_cast<int>(j % static_cast<uint64_t>(bs));
+        u128 item;
+        if (WIDE) {
+            item = ld128(in + 2 * e) + ld128(add + 2 * e);
+            if (minus) item -= ld128(minus + 2 * e);
+            item &= mask;
+        } else {
+            uint64_t x = in[e] + add[e];
+            if (minus) x -= minus[e];
+            item = static_cast<u128>(x & mask_lo);
+        }
+        const int sh = field_bits * (bs - 1 - slot);
+        const u128 v = (sh >= 128 ? static_cast<u128>(0) : item >> sh) & mk;
+        out[g] = u128_to_double(v) * Ly->p1 / Ly->p2 - Ly->p0;
+    }
+}
+
+hipError_t launch_quantize_combine_model(const LaunchEnv &env, uint64_t count, const Codec &cq, const uint64_t *add_dev, const uint64_t *minus_dev,
+                                         uint64_t *ct_dev)
+{
+    if (count == 0) return hipSuccess;
+    uint64_t lo, hi;
+    masks_of(env.b, &lo, &hi);
+    const dim3 g(stream_grid(env, count)), t(kStreamThreads);
+    if (env.b > 64) hipLaunchKernelGGL(quantize_combine_model_kernel<true>, g, t, 0, env.stream, count, cq, add_dev, minus_dev, ct_dev, lo, hi);
+    else hipLaunchKernelGGL(quantize_combine_model_kernel<false>, g, t, 0, env.stream, count, cq, add_dev, minus_dev, ct_dev, lo, hi);
+    return hipGetLastError();
+}
+
+hipError_t launch_combine_unquantize_model(const LaunchEnv &env, uint64_t count, const uint64_t *in_dev, const uint64_t *add_dev,
+                                           const uint64_t *minus_dev, const Codec &cq, double *out_dev)
+{
+    if (count == 0) return hipSuccess;
+    uint64_t lo, hi;
+    masks_of(env.b, &lo, &hi);
+    const dim3 g(stream_grid(env, count)), t(kStreamThreads);
+    if (env.b > 64) hipLaunchKernelGGL(combine_unquantize_model_kernel<true>, g, t, 0, env.stream, count, in_dev, add_dev, minus_dev, cq, out_dev, lo, hi);
+    else hipLaunchKernelGGL(combine_unquantize_model_kernel<false>, g, t, 0, env.stream, count, in_dev, add_dev, minus_dev, cq, out_dev, lo, hi);
+    return hipGetLastError();
+}
+
+hipError_t launch_quantize_batch_combine_model(const LaunchEnv &env, const BatchLayer *layers_dev, int n_layers, int field_bits, const double *u_dev,
+                                               uint64_t n_elems, const uint64_t *add_dev, const uint64_t *minus_dev, uint64_t *ct_dev)
+{
+    if (n_elems == 0) return hipSuccess;
+    if (field_bits < 1 || field_bits > env.b || n_layers < 1) return hipErrorInvalidValue;
+    uint64_t lo, hi;
+    masks_of(env.b, &lo, &hi);
+    const dim3 g(stream_grid(env, n_elems)), t(kStreamThreads);
+    if (env.b > 64)
+        hipLaunchKernelGGL(quantize_batch_combine_model_kernel<true>, g, t, 0, env.stream, layers_dev, n_layers, env.b / field_bits, field_bits, u_dev,
+                           n_elems, add_dev, minus_dev, ct_dev, lo, hi);
+    else
+        hipLaunchKernelGGL(quantize_batch_combine_model_kernel<false>, g, t, 0, env.stream, layers_dev, n_layers, env.b / field_bits, field_bits, u_dev,
+                           n_elems, add_dev, minus_dev, ct_dev, lo, hi);
+    return hipGetLastError();
+}
+
+hipError_t launch_combine_unbatch_unquantize_model(const LaunchEnv &env, const BatchLayer *layers_dev, int n_layers, int field_bits, const uint64_t *in_dev,
+                                                   const uint64_t *add_dev, const uint64_t *minus_dev, uint64_t n_values, double *out_dev)
+{
+    if (n_values == 0) return hipSuccess;
+    if (field_bits < 1 || field_bits > env.b || n_layers < 1) return hipErrorInvalidValue;
+    uint64_t lo, hi;
+    masks_of(env.b, &lo, &hi);
+    const dim3 g(stream_grid(env, n_values)), t(kStreamThreads);
+    if (env.b > 64)
+        hipLaunchKernelGGL(combine_unbatch_unquantize_model_kernel<true>, g, t, 0, env.stream, layers_dev, n_layers, env.b / field_bits, field_bits,
+                           in_dev, add_dev, minus_dev, n_values, out_dev, lo, hi);
+    else
+        hipLaunchKernelGGL(combine_unbatch_unquantize_model_kernel<false>, g, t, 0, env.stream, layers_dev, n_layers, env.b / field_bits, field_bits,
+                           in_dev, add_dev, minus_dev, n_values, out_dev, lo, hi);
+    return hipGetLastError();
+}
+
 hipError_t launch_batch(const LaunchEnv &env, uint64_t n, const uint64_t *vals_dev, int field_bits, uint64_t *out_dev)
 {
     const int bs = env.b / field_bits;

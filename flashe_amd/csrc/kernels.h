@@ -268,6 +268,17 @@ hipError_t launch_unbatch_unquantize_model(const LaunchEnv &env, const BatchLaye
                                            uint64_t n_values, double *out_dev);
 BatchLayer batch_layer_front(uint64_t elem_start, uint64_t value_start, uint64_t size, const void *x_dev, bool is_f64, double alpha, int bits);
 BatchLayer batch_layer_back(uint64_t elem_start, uint64_t value_start, uint64_t size, double alpha, int bits, int num_clients);
+// The same codec walks with the ctx's precomputed masks in place of the PRF streams (no AES): ct = (quantize + add - minus) mod 2^b and
+// out = unquantize((in + add - minus) mod 2^b).  minus_dev may be null (a single-mask cache); the un-batched forms take cq's layer table
+// (k0 = the launch's first element; add / minus / ct / in address that element)
+hipError_t launch_quantize_combine_model(const LaunchEnv &env, uint64_t count, const Codec &cq, const uint64_t *add_dev, const uint64_t *minus_dev,
+                                         uint64_t *ct_dev);
+hipError_t launch_combine_unquantize_model(const LaunchEnv &env, uint64_t count, const uint64_t *in_dev, const uint64_t *add_dev,
+                                           const uint64_t *minus_dev, const Codec &cq, double *out_dev);
+hipError_t launch_quantize_batch_combine_model(const LaunchEnv &env, const BatchLayer *layers_dev, int n_layers, int field_bits, const double *u_dev,
+                                               uint64_t n_elems, const uint64_t *add_dev, const uint64_t *minus_dev, uint64_t *ct_dev);
+hipError_t launch_combine_unbatch_unquantize_model(const LaunchEnv &env, const BatchLayer *layers_dev, int n_layers, int field_bits, const uint64_t *in_dev,
+                                                   const uint64_t *add_dev, const uint64_t *minus_dev, uint64_t n_values, double *out_dev);
 hipError_t launch_unbatch(const LaunchEnv &env, uint64_t nb, const uint64_t *in_dev, int field_bits, uint64_t *out_dev);
 
 // Caller-owned tensors either side of the model-wide codec (tensors.hip).  dtype / flags as in flashe_tensor_layer (include/flashe.h);

@@ -752,6 +752,45 @@ class Engine:
         pm, _m = _u32_list(minus_idx)
         self._check(self._lib.flashe_decrypt_prepared_dev(self._h, it, pa, len(add_idx), pm, len(minus_idx), n, n_jobs, self._ptr(inp), self._ptr(out)))
 
+    # the model-wide codec with the ctx's prepared masks (no AES; the cache rules of encrypt_prepared_dev / decrypt_prepared_dev: a range
+    # encrypt consumes the cache with the call that ends at n, a length mismatch leaves it valid)
+    def quantize_encrypt_prepared_model_dev(self, n, first, count, layers, element_bits, u, ct):
+        """quantize_encrypt_model_dev with the prepared encrypt masks in place of the PRF: ct = quantize + add - minus."""
+        arr, nl = self._codec_layers(layers)
+        self._check(self._lib.flashe_quantize_encrypt_prepared_model_dev(self._h, n, first, count, arr, nl, element_bits, self._ptr(u), self._ptr(ct)))
+
+    def quantize_encrypt_prepared_tensors_dev(self, n, first, count, layers, element_bits, u, ct):
+        arr, nl = self._tensor_layers(layers)
+        self._check(self._lib.flashe_quantize_encrypt_prepared_tensors_dev(self._h, n, first, count, arr, nl, element_bits, self._ptr(u), self._ptr(ct)))
+
+    def quantize_batch_encrypt_prepared_model_dev(self, layers, element_bits, field_bits, u, n_elems, ct):
+        """quantize_batch_model_dev and the prepared encrypt of its result in one launch."""
+        arr, nl = self._batch_layers(layers)
+        self._check(self._lib.flashe_quantize_batch_encrypt_prepared_model_dev(self._h, arr, nl, element_bits, field_bits, self._ptr(u), int(n_elems),
+                                                                               self._ptr(ct)))
+
+    def quantize_batch_encrypt_prepared_tensors_dev(self, layers, n_values, element_bits, field_bits, u, n_elems, ct):
+        arr, nl = self._tensor_layers(layers)
+        self._check(self._lib.flashe_quantize_batch_encrypt_prepared_tensors_dev(self._h, arr, nl, int(n_values), element_bits, field_bits, self._ptr(u),
+                                                                                 int(n_elems), self._ptr(ct)))
+
+    def decrypt_prepared_unquantize_model_dev(self, it, add_idx, minus_idx, n, n_jobs, inp, layers, element_bits, num_clients, out):
+        """decrypt_unquantize_model_dev with the prepared decrypt masks (+ the listed extra prefixes, computed online)."""
+        pa, _a = _u32_list(add_idx)
+        pm, _m = _u32_list(minus_idx)
+        arr, nl = self._codec_layers(layers)
+        self._check(self._lib.flashe_decrypt_prepared_unquantize_model_dev(self._h, it, pa, len(add_idx), pm, len(minus_idx), n, n_jobs, self._ptr(inp), arr,
+                                                                           nl, element_bits, num_clients, self._ptr(out)))
+
+    def decrypt_prepared_unbatch_unquantize_model_dev(self, it, add_idx, minus_idx, n_jobs, layers, element_bits, field_bits, num_clients, inp, n_elems,
+                                                      out):
+        pa, _a = _u32_list(add_idx)
+        pm, _m = _u32_list(minus_idx)
+        arr, nl = self._batch_layers(layers)
+        self._check(self._lib.flashe_decrypt_prepared_unbatch_unquantize_model_dev(self._h, it, pa, len(add_idx), pm, len(minus_idx), n_jobs, arr, nl,
+                                                                                   element_bits, field_bits, num_clients, self._ptr(inp), int(n_elems),
+                                                                                   self._ptr(out)))
+
     def decrypt_dev(self, it, add_idx, minus_idx, n, n_jobs, inp, out):
         pa, _a = _u32_list(add_idx)
         pm, _m = _u32_list(minus_idx)

@@ -65,7 +65,10 @@ typedef struct flashe_ctx flashe_ctx;
  *      its ctx); flashe_combine_batch_sum_decrypt_dev (online encrypts + their sum + the decrypt of the sum in one pass);
  *      later additions without a bump (existing signatures unchanged; a caller checks for the symbols): flashe_ctx_stream,
  *      flashe_stream_wait_stream, flashe_event_query, flashe_tensor_layer + flashe_quantize_encrypt_tensors_dev /
- *      flashe_quantize_batch_tensors_dev / flashe_store_layers_dev (caller-owned tensors either side of the model-wide codec) */
+ *      flashe_quantize_batch_tensors_dev / flashe_store_layers_dev (caller-owned tensors either side of the model-wide codec);
+ *      flashe_quantize_encrypt_prepared_{model,tensors}_dev, flashe_quantize_batch_encrypt_prepared_{model,tensors}_dev,
+ *      flashe_decrypt_prepared_unquantize_model_dev, flashe_decrypt_prepared_unbatch_unquantize_model_dev (the model-wide codec with the
+ *      ctx's precomputed masks) */
 #define FLASHE_ABI_VERSION 4
 int flashe_abi_version(void);
 int flashe_device_count(int *count);
@@ -654,6 +657,38 @@ int flashe_quantize_batch_tensors_dev(flashe_ctx *ctx, const flashe_tensor_layer
  * (the deviations are taken from the correctly rounded S / n).  The table upload synchronises; the passes are asynchronous. */
 int flashe_store_layers_dev(flashe_ctx *ctx, const double *in_dev, uint64_t n, const flashe_tensor_layer *layers, int n_layers, uint64_t block,
                             double *stats_dev);
+
+/* The model-wide codec with the ctx's PRECOMPUTED masks (new): the client step of a job with precompute enabled (jzf_flashe.py:456-488,
+ * :537-582 once prepare_encrypt / prepare_decrypt, :599-666, filled the caches) -- the codec of the calls above and the combine of
+ * flashe_encrypt_prepared_dev / flashe_decrypt_prepared_dev in one pass, no AES:
+ *   quantize_encrypt_prepared_{model,tensors}: ct[k] = (quantize(x[k], u[k]) + add[k] - minus[k]) mod 2^b for the elements
+ *       [first, first + count) of the n-element flattened model (flashe_quantize_encrypt_{model,tensors}_dev's tables and pointers);
+ *   quantize_batch_encrypt_prepared_{model,tensors}: ct[e] = (batched[e] + add[e] - minus[e]) mod 2^b over the whole batched vector
+ *       (flashe_quantize_batch_{model,tensors}_dev's walk; n_elems elements);
+ *   decrypt_prepared_unquantize_model: out[k] = unquantize((in[k] + add[k] - minus[k]) mod 2^b) as float64, k < n;
+ *   decrypt_prepared_unbatch_unquantize_model: flashe_unbatch_unquantize_model_dev's walk over (in + add - minus) mod 2^b.
+ * The decrypt forms take the extra add / minus prefixes of flashe_decrypt_prepared_dev (the dropouts set_idx_list leaves uncovered, merged
+ * in online, :557-564): then a PRF launch writes in + extras into ctx scratch first and the codec pass reads that (two launches).
+ * Cache rules (those of flashe_encrypt_prepared_dev / flashe_decrypt_prepared_dev): FLASHE_EINVAL without a valid cache of the direction,
+ * and FLASHE_EINVAL with the cache left valid when the vector's length (n, n_elems) differs from the cached one; the cache is consumed once
+ * per WHOLE vector -- an un-batched encrypt may come as several range calls over [first, first + count), and the call whose range ends
+ * at n consumes it (a call that fails, or a range that ends before n, leaves it valid).  A decrypt never touches the encrypt cache, an
+ * encrypt never the decrypt cache.  The masks' iteration is not checked (the reference uses whatever it prepared).  Not capturable
+ * into a graph (the tables are staged per call). */
+int flashe_quantize_encrypt_prepared_model_dev(flashe_ctx *ctx, uint64_t n, uint64_t first, uint64_t count, const flashe_codec_layer *layers,
+                                               int n_layers, int element_bits, const double *u_dev, uint64_t *ct_dev);
+int flashe_quantize_encrypt_prepared_tensors_dev(flashe_ctx *ctx, uint64_t n, uint64_t first, uint64_t count, const flashe_tensor_layer *layers,
+                                                 int n_layers, int element_bits, const double *u_dev, uint64_t *ct_dev);
+int flashe_quantize_batch_encrypt_prepared_model_dev(flashe_ctx *ctx, const flashe_batch_layer *layers, int n_layers, int element_bits, int field_bits,
+                                                     const double *u_dev, uint64_t n_elems, uint64_t *ct_dev);
+int flashe_quantize_batch_encrypt_prepared_tensors_dev(flashe_ctx *ctx, const flashe_tensor_layer *layers, int n_layers, uint64_t n_values,
+                                                       int element_bits, int field_bits, const double *u_dev, uint64_t n_elems, uint64_t *ct_dev);
+int flashe_decrypt_prepared_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx,
+                                                 int n_minus, uint64_t n, uint32_t n_jobs, const uint64_t *in_dev, const flashe_codec_layer *layers,
+                                                 int n_layers, int element_bits, int num_clients, double *out_dev);
+int flashe_decrypt_prepared_unbatch_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx,
+                                                         int n_minus, uint32_t n_jobs, const flashe_batch_layer *layers, int n_layers, int element_bits,
+                                                         int field_bits, int num_clients, const uint64_t *in_dev, uint64_t n_elems, double *out_dev);
 
 /* np.random.random(n) ON THE DEVICE, bit for bit (new): the stochastic-rounding draws of _static_quantize_padding_asymmetric
  * (jzf_quantize.py:61, `np.random.random(value.shape)`) come from NumPy's global MT19937 generator; this writes the same n doubles
