@@ -567,15 +567,31 @@ class FlasheClient(object):
         from .engine import DeviceVector
         from .quantize import ACIQ, DEVICE_RNG_MIN, _loop_dtype
         q, c = self.quantizer, self.cipher
-        if "zzz" in weights._weights:
-            raise TypeError("framework tensors are not supported by the sparse job (the 'zzz' layer)")
-        if not self._fusable(weights):
+        zzz = None
+        if "zzz" in weights._weights:                 # the sparse job: compact layers (Sparsifier's CompactLayer or any tensors) + 'zzz'
+            if not self.fuse:
+                raise TypeError("framework tensors in the sparse job need the fused client step (fuse=True)")
+            if self.batch:
+                raise TypeError("framework tensors are not supported by batched sparse jobs")
+            if c.prp_seed is not None:
+                c._reconcile_prepared()
+            if c.next_iter_encrypt_prepared:
+                raise TypeError("framework tensors are not supported by sparse jobs with precomputed encrypt masks")
+            if not self._fusable(weights):
+                raise TypeError("framework tensors in the sparse job need the one-value 'zzz' layer at the end of the walking order")
+            zzz = weights._weights["zzz"]
+            if interop.is_foreign(zzz):
+                raise TypeError("the sparse job's 'zzz' layer must be a host value")
+            zzz = np.asarray(zzz)
+        elif not self._fusable(weights):
             raise TypeError("framework tensors need the fused client step (fuse=True, no location masks, precomputed encrypt masks only as "
                             "the handles prepare_encrypt leaves)")
         eng = c.engine
-        mode = self._prepared_mode(c.next_iter_encrypt_prepared)
+        mode = self._prepared_mode(c.next_iter_encrypt_prepared) if zzz is None else None
         codes = {"float32": TENSOR_F32, "float64": TENSOR_F64, "float16": TENSOR_F16, "bfloat16": TENSOR_BF16}
         order = list(weights.walking_order)
+        if zzz is not None:
+            order = order[:-1]
         layers = []                                   # (ForeignArray or host flat array, shape, NumPy dtype of its host copy)
         for k in order:
             v = weights._weights[k]
@@ -591,7 +607,7 @@ class FlasheClient(object):
                     flat = flat.astype(np.float64)
                 layers.append((flat, a.shape, flat.dtype))
         if q.layer_size_list is None:                 # set_layer_size_list (jzf_quantize.py:380-392) on the sizes the tensors report
-            q.layer_size_list = [int(np.prod(shape, dtype=np.int64)) for _x, shape, _d in layers]
+            q.layer_size_list = [int(np.prod(shape, dtype=np.int64)) for _x, shape, _d in layers] + ([int(zzz.size)] if zzz is not None else [])
             for _ in q.layer_size_list:
                 q.past_layer_mean_list.append(q.expected_mean_for_first_round)
                 q.past_layer_std_list.append(q.expected_std_for_first_round)
@@ -656,7 +672,7 @@ class FlasheClient(object):
         else:
             if mode == "ctx":
                 self._refuse_prepared_len(n, n)
-            ct = DeviceVector(eng, n)
+            ct = DeviceVector(eng, n + (1 if zzz is not None else 0))
             at = 0
             while at < len(order):                    # the draws in runs of whole layers, as in quantize_encrypt
                 end, tot = at, 0
@@ -677,6 +693,19 @@ class FlasheClient(object):
             self.shape_dict = shape_dict
         self._encrypt_done(mode)
         eng.hold(keep)
+        if zzz is not None:
+            # the trailing layer as the host path takes it (normalised with its own mean, then the next draw, alpha 1.0, not encrypted)
+            from .quantize import _as_object, _static_quantize_padding_asymmetric
+            if normalize:
+                d, a = q._shift(zzz, -q.past_layer_mean_list[len(order)])
+                zzz = d.download(a.dtype, a.size).reshape(a.shape)
+            flat = zzz.flatten()
+            want = _loop_dtype(flat.dtype, 1.0)
+            if flat.dtype != want:
+                flat = flat.astype(want)
+            zq = int(_as_object(_static_quantize_padding_asymmetric(flat, 1.0, q.element_bits, device=q._device, as_object=False)).reshape(-1)[0])
+            ct.buf.upload_at(n * eng.limbs * 8, np.array([zq & (2 ** 64 - 1), zq >> 64][:eng.limbs], dtype=np.uint64))
+            del weights._weights["zzz"]
         for k in order:
             del weights._weights[k]
         if order:
@@ -691,13 +720,27 @@ class FlasheClient(object):
         np.std do, so past_layer_mean_list / past_layer_std_list get the host path's np.float64 values.  Only those 16 bytes per layer come
         back to the host.  Own-stream engines synchronise before returning."""
         from . import interop
-        from ._lib import TENSOR_BF16, TENSOR_F16, TENSOR_F32, TENSOR_F64, TENSOR_SHIFT
+        from ._lib import TENSOR_BF16, TENSOR_F16, TENSOR_F32, TENSOR_F64
         from .engine import DeviceVector
+        from .cipher import _SparseMinus
         q, c = self.quantizer, self.cipher
-        if c.masks is not None or "zzz" in weights._weights:
-            raise TypeError("out= is not supported by the sparse job")
+        if "zzz" in weights._weights:
+            raise TypeError("out= takes the dense aggregate, not an upload with the sparse job's 'zzz' layer")
+        sparse = c.masks is not None
         mode = False
-        if self.fuse and c.prp_seed is not None:
+        if sparse:                                    # the sparse job: location masks, the single-mask minus pass (decrypt_unquantize)
+            if not self.fuse:
+                raise TypeError("out= in the sparse job needs the fused client step (fuse=True)")
+            if self.batch:
+                raise TypeError("out= is not supported by batched sparse jobs")
+            if c.masking_scheme != "single":
+                raise TypeError("out= is not supported with the sparse job's dense-position double mask (masking_scheme 'double')")
+            prep = c.next_iter_decrypt_prepared
+            if c.prp_seed is None or set(prep) != {"minus"} or not isinstance(prep["minus"], _SparseMinus):
+                raise TypeError("out= in the sparse job needs the location masks set_idx_list(mode='decrypt') leaves (no precomputed decrypt "
+                                "masks)")
+            mode = None
+        elif self.fuse and c.prp_seed is not None:
             c._reconcile_prepared()
             mode = self._prepared_mode(c.next_iter_decrypt_prepared)
         if mode is False:
@@ -721,10 +764,27 @@ class FlasheClient(object):
             if tuple(fa.shape) != tuple(shape):
                 raise ValueError(f"out[{k!r}]: expected shape {tuple(shape)}, got {tuple(fa.shape)}")
             fas.append(fa)
-        add_idx, minus_idx = self._decrypt_prefixes(mode)
         k0 = weights.walking_order[0]
         v = weights._weights[k0]
         keep = [fa.keep for fa in fas]
+        if sparse:
+            # the sparse minus-mask pass (result in HBM), then the unquantise of the dense model (decrypt_unquantize's sparse branch)
+            dec = c._as_wide(c.decrypt(v, device=True))
+            n = len(dec)
+            sizes = [int(np.prod(shape, dtype=np.int64)) for shape in shapes]
+            if sum(sizes) > n:
+                raise ValueError(f"the aggregate has {n} elements, shape_dict describes {sum(sizes)}")
+            table, at = [], 0
+            for li, size in enumerate(sizes):
+                table.append((at, None, q.alpha_list[li], False))
+                at += size
+            dout = eng.alloc(max(8 * n, 16))
+            if n:
+                dec.wait_on(eng)
+                eng.unquantize_model_dev(n, 0, n, dec.buf, table, q.element_bits, q.num_clients, dout)
+            keep.append(dec)
+            return self._store_tensors(weights, out, names, fas, sizes, dout, keep, unnormalize)
+        add_idx, minus_idx = self._decrypt_prefixes(mode)
         if interop.is_foreign(v):                                 # (the aggregate as a framework integer tensor: read in place)
             v, kv = c._foreign_vec(eng, v, "aggregate")
             keep.append(kv)
@@ -735,8 +795,15 @@ class FlasheClient(object):
         dv, _kind = c._on_device(v, full_width=True)
         dv = c._as_wide(dv)
         sizes = [int(np.prod(shape, dtype=np.int64)) for shape in shapes]
-        n_values = sum(sizes)
         dout = self._decrypt_floats(dv, sizes, mode, add_idx, minus_idx)
+        return self._store_tensors(weights, out, names, fas, sizes, dout, keep, unnormalize)
+
+    def _store_tensors(self, weights, out, names, fas, sizes, dout, keep, unnormalize):
+        """The back end's flat float64 model `dout` (in HBM) into the out= tensors, with the exact statistics when unnormalising."""
+        from ._lib import TENSOR_BF16, TENSOR_F16, TENSOR_F32, TENSOR_F64, TENSOR_SHIFT
+        q, eng = self.quantizer, self.cipher.engine
+        codes = {"float32": TENSOR_F32, "float64": TENSOR_F64, "float16": TENSOR_F16, "bfloat16": TENSOR_BF16}
+        n_values = sum(sizes)
         layers, at = [], 0
         for li, (fa, size) in enumerate(zip(fas, sizes)):
             shift = float(q.past_layer_mean_list[li]) if unnormalize else 0.0

@@ -2845,6 +2845,51 @@ int flashe_sparsify_batch_dev(flashe_ctx *ctx, int n_layers, const uint64_t *n, 
     return FLASHE_OK;
 }
 
+// Every layer of a model where its owner keeps it (include/flashe.h): the tables are built on the host in the caller's layer order, sorted
+// by compute class for the launches, uploaded once.
+int flashe_sparsify_tensors_dev(flashe_ctx *ctx, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const uint64_t *k, void *residual_dev,
+                                uint32_t *loc_dev, void *vals_dev, uint64_t *packed_dev, int bits)
+{
+    CHECK_CTX(ctx);
+    if (n >= (1ull << 32)) return fail(ctx, FLASHE_EINVAL, "sparsify_tensors: n must be < 2^32");
+    if (!k) return fail(ctx, FLASHE_EINVAL, "sparsify_tensors: null k");
+    int rc = check_tensor_layers(ctx, n, layers, n_layers);
+    if (rc) return rc;
+    if (packed_dev && (bits < 1 || bits > 32 || (bits < 32 && n > (1ull << bits))))
+        return fail(ctx, FLASHE_EINVAL, "sparsify_tensors: bits (%d) must be in [1, 32] and cover n (%llu)", bits, static_cast<unsigned long long>(n));
+    std::vector<const void *> x(n_layers);
+    std::vector<int> dt(n_layers);
+    std::vector<uint64_t> nl(n_layers), koff(n_layers), start(n_layers), roff(n_layers), voff(n_layers);
+    uint64_t total_k = 0, r = 0, v = 0;
+    for (int l = 0; l < n_layers; l++) {
+        const flashe_tensor_layer &y = layers[l];
+        nl[l] = (l + 1 < n_layers ? layers[l + 1].start : n) - y.start;
+        if (k[l] > nl[l]) return fail(ctx, FLASHE_EINVAL, "sparsify_tensors: layer %d: k (%llu) > n (%llu)", l, static_cast<unsigned long long>(k[l]),
+                                      static_cast<unsigned long long>(nl[l]));
+        const uint64_t cs = y.dtype == FLASHE_TENSOR_F64 ? 8 : 4;
+        r = (r + cs - 1) / cs * cs;
+        v = (v + cs - 1) / cs * cs;
+        x[l] = y.ptr; dt[l] = y.dtype; start[l] = y.start; koff[l] = total_k; roff[l] = r; voff[l] = v;
+        r += nl[l] * cs;
+        v += k[l] * cs;
+        total_k += k[l];
+    }
+    if (n == 0 || total_k == 0) return FLASHE_OK;
+    if (!loc_dev || !vals_dev) return fail(ctx, FLASHE_EINVAL, "null vector");
+    std::vector<unsigned char> desc(sparsify_tensors_desc_bytes(n_layers));
+    int l32 = 0;
+    uint64_t nb32 = 0;
+    const uint64_t blocks = sparsify_tensors_layout(n_layers, x.data(), dt.data(), nl.data(), k, koff.data(), start.data(), roff.data(), voff.data(),
+                                                    desc.data(), &l32, &nb32);
+    if (blocks >= (1ull << 32)) return fail(ctx, FLASHE_EINVAL, "sparsify_tensors: too many elements");
+    if (ctx->capturing) return fail(ctx, FLASHE_EINVAL, "sparsify_tensors: not inside a graph capture (the layer table is uploaded synchronously)");
+    if ((rc = ensure(ctx, ctx->sp_ws, sparsify_tensors_workspace_bytes(n_layers, blocks)))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->sp_ws.p, desc.data(), desc.size(), hipMemcpyHostToDevice, ctx->env.stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->env.stream));
+    HIP_TRY(ctx, launch_sparsify_tensors(ctx->env, n_layers, l32, blocks, nb32, residual_dev, loc_dev, vals_dev, total_k, bits, packed_dev, ctx->sp_ws.p));
+    return FLASHE_OK;
+}
+
 #ifdef FLASHE_TUNING
 // tuning build only: phase cycle sums of span_prf_kernel's workgroup 0 (FLASHE_SPAN_PROBE=9), tests/perf/sparse_phases.py
 int flashe_tune_span_prf_cycles(flashe_ctx *ctx, unsigned long long *out8, int reset)

@@ -321,6 +321,16 @@ size_t sparsify_batch_desc_bytes(int L);
 uint64_t sparsify_batch_layout(int L, const uint64_t *n, const uint64_t *k, void *desc_host);
 hipError_t launch_sparsify_batch(const LaunchEnv &env, int L, uint64_t n_blocks, const void *x, bool is_f64, void *residual, uint32_t *loc, void *vals,
                                  void *ws);
+// The same over caller-owned layers in their own dtypes (flashe_sparsify_tensors_dev): the caller fills the host tables with
+// sparsify_tensors_layout (sorted by compute class; -> blocks), copies their sparsify_tensors_desc_bytes(L) bytes to the START of a device
+// workspace of sparsify_tensors_workspace_bytes(L, blocks), then launches; packed (may be null) receives `_to_bytes(loc, bits)`.
+size_t sparsify_tensors_workspace_bytes(int L, uint64_t n_blocks);
+size_t sparsify_tensors_desc_bytes(int L);
+uint64_t sparsify_tensors_layout(int L, const void *const *x, const int *dtype, const uint64_t *n, const uint64_t *k, const uint64_t *koff,
+                                 const uint64_t *start, const uint64_t *roff, const uint64_t *voff, void *desc_host, int *n_f32_layers,
+                                 uint64_t *n_f32_blocks);
+hipError_t launch_sparsify_tensors(const LaunchEnv &env, int L, int L32, uint64_t n_blocks, uint64_t nb32, void *residual, uint32_t *loc, void *vals,
+                                   uint64_t total_k, int bits, uint64_t *packed, void *ws);
 // Top-k sparsifier; ws = device workspace of sparsify_workspace_bytes(n).
 size_t sparsify_workspace_bytes(uint64_t n);
 hipError_t launch_sparsify(const LaunchEnv &env, uint64_t n, uint64_t k, const void *x, bool is_f64, void *residual, uint32_t *loc,

@@ -464,6 +464,306 @@ hipError_t launch_sparsify_batch(const LaunchEnv &env, int L, uint64_t n_blocks,
                                                static_cast<float *>(vals), ws);
 }
 
+// ---- caller-owned layers (flashe_sparsify_tensors_dev) -----------------------------------------------------------------------------
+// The batch passes above on layers that lie wherever their owner put them, each in its own dtype: float32 / float16 / bfloat16 layers
+// compute in float32 (16-bit values widened exactly), float64 layers in float64.  The layer table is sorted by compute class -- float32
+// layers first, then float64 -- so the blocks of one class are one contiguous range and each pass is one launch per class present; the
+// SpLayer table drives the shared kernels (block map, init, scan), a parallel SptLayer table says where a layer's values, residual and
+// outputs are.  A block never crosses a layer, so its dtype is uniform over the workgroup and the dtype dispatch of the loads is a scalar
+// branch.
+struct SptLayer {
+    const void *x;                  // the layer's values, `dtype`
+    uint64_t start;                 // the layer's first element in the dense model (added to its locations)
+    uint64_t roff, voff;            // byte offsets of its residual / compact values (compute type)
+    int32_t dtype, pad;
+};
+
+// elements i .. i + 3 of a layer of n elements in its compute type CT: 16 bytes per lane for float32, 8 for 16 bits, 2 x 16 for float64
+template <typename CT>
+__device__ __forceinline__ void spt_load4(const void *p, int dtype, uint64_t i, uint64_t n, CT (&v)[4])
+{
+    if constexpr (sizeof(CT) == 8) {
+        sp_load4(static_cast<const double *>(p), i, n, v);
+    } else if (dtype == kTensorF32) {
+        sp_load4(static_cast<const float *>(p), i, n, v);
+    } else {
+        const uint16_t *h = static_cast<const uint16_t *>(p);
+        uint16_t u[4];
+        if (i + 4 <= n) {
+            typedef uint16_t u16x4_a2 __attribute__((ext_vector_type(4), aligned(2)));
+            const u16x4_a2 q = *reinterpret_cast<const u16x4_a2 *>(h + i);
+            u[0] = q[0]; u[1] = q[1]; u[2] = q[2]; u[3] = q[3];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; j++) u[j] = i + j < n ? h[i + j] : uint16_t(0);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            v[j] = dtype == kTensorBF16 ? __uint_as_float(static_cast<uint32_t>(u[j]) << 16)
+                                        : static_cast<float>(__builtin_bit_cast(_Float16, u[j]));
+    }
+}
+
+__global__ void spt_pick_digit_kernel(SelectState *st_all, int l0, int shift, uint32_t *hist_all)
+{
+    sp_pick(st_all + l0 + blockIdx.x, shift, hist_all + static_cast<size_t>(l0 + blockIdx.x) * 256);
+}
+
+// spb_hist_kernel over the blocks [b0, b1) of one compute class
+template <typename CT>
+__global__ __launch_bounds__(kSpWg) void spt_hist_kernel(const uint32_t *blk_layer, const SpLayer *ly, const SptLayer *ty, uint32_t b0, uint32_t b1,
+                                                           const SelectState *st, int shift, uint32_t *hist)
+{
+    __shared__ uint32_t lh[256];
+    lh[threadIdx.x] = 0;
+    __syncthreads();
+    int cur = -1;
+    const uint32_t n_trips = (b1 - b0 + kSpPer - 1) / kSpPer;
+    for (uint32_t trip = blockIdx.x; trip < n_trips; trip += gridDim.x) {
+        int lay[kSpPer];
+        uint64_t base[kSpPer], nl[kSpPer];
+        CT v[kSpPer][4];
+#pragma unroll
+        for (uint32_t s = 0; s < kSpPer; s++) {
+            const uint32_t b = b0 + trip * kSpPer + s;
+            lay[s] = b < b1 ? __builtin_amdgcn_readfirstlane(static_cast<int>(blk_layer[b])) : -1;
+            const int l = lay[s] < 0 ? 0 : lay[s];
+            base[s] = static_cast<uint64_t>(b - ly[l].blk0) * kSpThreads + 4u * threadIdx.x;
+            nl[s] = lay[s] < 0 ? 0 : ly[l].n;
+            spt_load4(ty[l].x, ty[l].dtype, base[s], nl[s], v[s]);
+        }
+#pragma unroll
+        for (uint32_t s = 0; s < kSpPer; s++) {
+            const int l = lay[s];
+            if (l < 0) break;
+            if (l != cur) {
+                __syncthreads();
+                if (cur >= 0 && lh[threadIdx.x]) atomicAdd(&hist[cur * 256 + threadIdx.x], lh[threadIdx.x]);
+                lh[threadIdx.x] = 0;
+                cur = l;
+                __syncthreads();
+            }
+            const unsigned long long prefix = st[l].prefix, mask = st[l].mask;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const unsigned long long key = static_cast<unsigned long long>(KeyOf<CT>::get(v[s][j]));
+                sp_vote(lh, base[s] + j < nl[s] && (key & mask) == prefix, static_cast<uint32_t>((key >> shift) & 255u));
+            }
+        }
+    }
+    __syncthreads();
+    if (cur >= 0 && lh[threadIdx.x]) atomicAdd(&hist[cur * 256 + threadIdx.x], lh[threadIdx.x]);
+}
+
+// spb_count_kernel over the blocks [b0, b1)
+template <typename CT>
+__global__ __launch_bounds__(kSpWg) void spt_count_kernel(const uint32_t *blk_layer, const SpLayer *ly, const SptLayer *ty, uint32_t b0, uint32_t b1,
+                                                            const SelectState *st, uint32_t *blk_gt, uint32_t *blk_eq)
+{
+    __shared__ uint32_t c[kSpPer][2];
+    if (threadIdx.x < 2 * kSpPer) c[threadIdx.x >> 1][threadIdx.x & 1] = 0;
+    int lay[kSpPer];
+    uint64_t base[kSpPer], nl[kSpPer];
+    CT v[kSpPer][4];
+#pragma unroll
+    for (uint32_t s = 0; s < kSpPer; s++) {
+        const uint32_t b = b0 + blockIdx.x * kSpPer + s;
+        lay[s] = b < b1 ? __builtin_amdgcn_readfirstlane(static_cast<int>(blk_layer[b])) : -1;
+        const int l = lay[s] < 0 ? 0 : lay[s];
+        base[s] = static_cast<uint64_t>(b - ly[l].blk0) * kSpThreads + 4u * threadIdx.x;
+        nl[s] = lay[s] < 0 ? 0 : ly[l].n;
+        spt_load4(ty[l].x, ty[l].dtype, base[s], nl[s], v[s]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t s = 0; s < kSpPer; s++) {
+        if (lay[s] < 0) break;
+        const unsigned long long thr = st[lay[s]].prefix;
+        uint32_t cg = 0, ce = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const unsigned long long key = static_cast<unsigned long long>(KeyOf<CT>::get(v[s][j]));
+            const bool live = base[s] + j < nl[s];
+            cg += live && key > thr; ce += live && key == thr;
+        }
+        const uint32_t tg = sp_wave_scan(cg), te = sp_wave_scan(ce);
+        if ((threadIdx.x & 63) == 63) { atomicAdd(&c[s][0], tg); atomicAdd(&c[s][1], te); }
+    }
+    __syncthreads();
+    const uint32_t b = b0 + blockIdx.x * kSpPer + threadIdx.x;
+    if (threadIdx.x < kSpPer && b < b1) {
+        blk_gt[b] = c[threadIdx.x][0];
+        blk_eq[b] = c[threadIdx.x][1];
+    }
+}
+
+// spb_write_kernel over the blocks [b0, b1): the locations are model-wide (the layer's dense start + the index in the layer), values and
+// residuals sit at the layer's byte offsets of their buffers
+template <typename CT>
+__global__ __launch_bounds__(kSpWg) void spt_write_kernel(const uint32_t *blk_layer, const SpLayer *ly, const SptLayer *ty, uint32_t b0, uint32_t b1,
+                                                            unsigned char *residual_all, const SelectState *st_all, const uint32_t *blk_gt_off,
+                                                            const uint32_t *blk_eq_off, uint32_t *loc_all, unsigned char *vals_all)
+{
+    constexpr int WV = kSpWg / 64;
+    __shared__ uint32_t wg[kSpPer][WV], we[kSpPer][WV];
+    const int wave = threadIdx.x >> 6;
+    int lay[kSpPer];
+    uint64_t base[kSpPer], nl[kSpPer];
+    CT xv[kSpPer][4], rv[kSpPer][4];
+    uint32_t g0[kSpPer], e0[kSpPer];
+#pragma unroll
+    for (uint32_t s = 0; s < kSpPer; s++) {
+        const uint32_t b = b0 + blockIdx.x * kSpPer + s;
+        lay[s] = b < b1 ? __builtin_amdgcn_readfirstlane(static_cast<int>(blk_layer[b])) : -1;
+        const int l = lay[s] < 0 ? 0 : lay[s];
+        base[s] = static_cast<uint64_t>(b - ly[l].blk0) * kSpThreads + 4u * threadIdx.x;
+        nl[s] = lay[s] < 0 ? 0 : ly[l].n;
+        spt_load4(ty[l].x, ty[l].dtype, base[s], nl[s], xv[s]);
+        if (residual_all) sp_load4(reinterpret_cast<const CT *>(residual_all + ty[l].roff), base[s], nl[s], rv[s]);
+        else { rv[s][0] = rv[s][1] = rv[s][2] = rv[s][3] = CT(0); }
+        g0[s] = lay[s] < 0 ? 0u : blk_gt_off[b]; e0[s] = lay[s] < 0 ? 0u : blk_eq_off[b];
+    }
+    uint32_t pg[kSpPer], pe[kSpPer], fg[kSpPer], fe[kSpPer];
+#pragma unroll
+    for (uint32_t s = 0; s < kSpPer; s++) {
+        const unsigned long long thr = st_all[lay[s] < 0 ? 0 : lay[s]].prefix;
+        fg[s] = 0; fe[s] = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const unsigned long long key = static_cast<unsigned long long>(KeyOf<CT>::get(xv[s][j]));
+            const bool live = base[s] + j < nl[s];
+            fg[s] |= static_cast<uint32_t>(live && key > thr) << j;
+            fe[s] |= static_cast<uint32_t>(live && key == thr) << j;
+        }
+        const uint32_t cg = __popc(fg[s]), ce = __popc(fe[s]);
+        const uint32_t ig = sp_wave_scan(cg), ie = sp_wave_scan(ce);
+        pg[s] = ig - cg; pe[s] = ie - ce;
+        if ((threadIdx.x & 63) == 63) { wg[s][wave] = ig; we[s][wave] = ie; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t s = 0; s < kSpPer; s++) {
+        const int l = lay[s];
+        if (l < 0 || base[s] >= nl[s]) continue;
+        uint32_t og = 0, oe = 0;
+#pragma unroll
+        for (int w = 0; w < WV; w++) { if (w < wave) { og += wg[s][w]; oe += we[s][w]; } }
+        unsigned long long gt_before = static_cast<unsigned long long>(g0[s]) + og + pg[s];
+        unsigned long long eq_before = static_cast<unsigned long long>(e0[s]) + oe + pe[s];
+        const unsigned long long skip = st_all[l].total_eq - st_all[l].remaining;
+        const bool any_k = ly[l].k != 0;
+        uint32_t *loc = loc_all + ly[l].koff;
+        CT *vals = reinterpret_cast<CT *>(vals_all + ty[l].voff);
+        const uint32_t start = static_cast<uint32_t>(ty[l].start);
+        CT out_r[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const bool is_gt = (fg[s] >> j) & 1u, is_eq = (fe[s] >> j) & 1u;
+            const bool selected = any_k && (is_gt || (is_eq && eq_before >= skip));
+            const CT v = xv[s][j] + rv[s][j];
+            if (selected) {
+                const unsigned long long pos = gt_before + (eq_before > skip ? eq_before - skip : 0ull);
+                loc[pos] = start + static_cast<uint32_t>(base[s] + j);
+                vals[pos] = v;
+            }
+            out_r[j] = selected ? CT(0) : v;
+            gt_before += is_gt; eq_before += is_eq;
+        }
+        if (residual_all) sp_store4(reinterpret_cast<CT *>(residual_all + ty[l].roff), base[s], nl[s], out_r);
+    }
+}
+
+// `_to_bytes(locations, bits)` (jzf_weights.py:36-84) as little-endian limbs: entry j of K fills bits [bits (K-1-j), bits (K-j)) of the
+// integer.  One lane per output limb gathers the (at most 64 / bits + 2) entries that overlap it.
+__global__ void spt_pack_kernel(const uint32_t *loc, uint64_t K, int bits, uint64_t n_limbs, uint64_t *packed)
+{
+    const uint64_t w = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (w >= n_limbs) return;
+    const uint64_t lo = 64 * w;
+    const uint64_t r_lo = lo / static_cast<uint64_t>(bits);
+    const uint64_t r_hi = std::min<uint64_t>(K - 1, (lo + 63) / static_cast<uint64_t>(bits));
+    uint64_t v = 0;
+    for (uint64_t r = r_lo; r <= r_hi; r++) {
+        const uint64_t x = loc[K - 1 - r];
+        const int64_t pos = static_cast<int64_t>(r * static_cast<uint64_t>(bits)) - static_cast<int64_t>(lo);
+        v |= pos >= 0 ? x << pos : x >> (-pos);
+    }
+    packed[w] = v;
+}
+
+size_t sparsify_tensors_workspace_bytes(int L, uint64_t n_blocks)
+{
+    return static_cast<size_t>(L) * sizeof(SptLayer) + sparsify_batch_workspace_bytes(L, n_blocks);
+}
+
+size_t sparsify_tensors_desc_bytes(int L) { return static_cast<size_t>(L) * (sizeof(SpLayer) + sizeof(SptLayer)); }
+
+// The host tables, sorted by compute class (float32 first), each layer's block range in that order; -> the number of blocks, the number
+// of float32-class layers and blocks.  Layer i of the caller: x[i], dtype[i], n[i] elements, k[i] entries, koff[i] / start[i] / roff[i] /
+// voff[i] as documented in include/flashe.h.
+uint64_t sparsify_tensors_layout(int L, const void *const *x, const int *dtype, const uint64_t *n, const uint64_t *k, const uint64_t *koff,
+                                 const uint64_t *start, const uint64_t *roff, const uint64_t *voff, void *desc_host, int *n_f32_layers,
+                                 uint64_t *n_f32_blocks)
+{
+    SpLayer *ly = static_cast<SpLayer *>(desc_host);
+    SptLayer *ty = reinterpret_cast<SptLayer *>(ly + L);
+    uint64_t blk = 0;
+    int o = 0;
+    for (int cls = 0; cls < 2; cls++) {
+        for (int i = 0; i < L; i++) {
+            if ((dtype[i] == kTensorF64) != (cls == 1)) continue;
+            const uint64_t nb = (n[i] + kSpThreads - 1) / kSpThreads;
+            ly[o] = SpLayer{0, n[i], k[i], koff[i], static_cast<uint32_t>(blk), static_cast<uint32_t>(nb)};
+            ty[o] = SptLayer{x[i], start[i], roff[i], voff[i], dtype[i], 0};
+            blk += nb;
+            o++;
+        }
+        if (cls == 0) { *n_f32_layers = o; *n_f32_blocks = blk; }
+    }
+    return blk;
+}
+
+hipError_t launch_sparsify_tensors(const LaunchEnv &env, int L, int L32, uint64_t n_blocks, uint64_t nb32, void *residual, uint32_t *loc, void *vals,
+                                   uint64_t total_k, int bits, uint64_t *packed, void *ws)
+{
+    // workspace: SpLayer[L] | SptLayer[L] (both uploaded) | SelectState[L] | hist[L][256] | blk_gt | blk_eq | blk_layer
+    if (L <= 0 || n_blocks == 0) return hipSuccess;
+    const SpLayer *ly = static_cast<const SpLayer *>(ws);
+    const SptLayer *ty = reinterpret_cast<const SptLayer *>(ly + L);
+    SelectState *st = reinterpret_cast<SelectState *>(const_cast<SptLayer *>(ty) + L);
+    uint32_t *hist = reinterpret_cast<uint32_t *>(st + L);
+    uint32_t *blk_gt = hist + static_cast<size_t>(L) * 256, *blk_eq = blk_gt + n_blocks, *blk_layer = blk_eq + n_blocks;
+    const unsigned nb = static_cast<unsigned>(n_blocks), nbf = static_cast<unsigned>(nb32);
+    hipLaunchKernelGGL(spb_map_kernel, dim3((nb + 255) / 256), dim3(256), 0, env.stream, L, ly, nb, blk_layer);
+    hipLaunchKernelGGL(spb_init_kernel, dim3(L), dim3(256), 0, env.stream, ly, st, hist);
+    const unsigned cus = static_cast<unsigned>(std::max(env.num_cus, 1));
+    const unsigned trips_f = (nbf + kSpPer - 1) / kSpPer, trips_d = (nb - nbf + kSpPer - 1) / kSpPer;
+    unsigned char *res = static_cast<unsigned char *>(residual), *out = static_cast<unsigned char *>(vals);
+    for (int p = 0; p < 8; p++) {              // digits, most significant first: four for the float32 class, eight for float64
+        if (p < 4 && nbf) {
+            hipLaunchKernelGGL(spt_hist_kernel<float>, dim3(std::min(trips_f, cus * 8u)), dim3(kSpWg), 0, env.stream, blk_layer, ly, ty, 0u, nbf, st,
+                               24 - 8 * p, hist);
+            hipLaunchKernelGGL(spt_pick_digit_kernel, dim3(L32), dim3(256), 0, env.stream, st, 0, 24 - 8 * p, hist);
+        }
+        if (nb > nbf) {
+            hipLaunchKernelGGL(spt_hist_kernel<double>, dim3(std::min(trips_d, cus * 8u)), dim3(kSpWg), 0, env.stream, blk_layer, ly, ty, nbf, nb, st,
+                               56 - 8 * p, hist);
+            hipLaunchKernelGGL(spt_pick_digit_kernel, dim3(L - L32), dim3(256), 0, env.stream, st, L32, 56 - 8 * p, hist);
+        }
+    }
+    if (nbf) hipLaunchKernelGGL(spt_count_kernel<float>, dim3(trips_f), dim3(kSpWg), 0, env.stream, blk_layer, ly, ty, 0u, nbf, st, blk_gt, blk_eq);
+    if (nb > nbf) hipLaunchKernelGGL(spt_count_kernel<double>, dim3(trips_d), dim3(kSpWg), 0, env.stream, blk_layer, ly, ty, nbf, nb, st, blk_gt, blk_eq);
+    hipLaunchKernelGGL(spb_scan_kernel, dim3(L), dim3(kSpThreads), 0, env.stream, ly, blk_gt, blk_eq, st);
+    if (nbf) hipLaunchKernelGGL(spt_write_kernel<float>, dim3(trips_f), dim3(kSpWg), 0, env.stream, blk_layer, ly, ty, 0u, nbf, res, st, blk_gt, blk_eq, loc, out);
+    if (nb > nbf)
+        hipLaunchKernelGGL(spt_write_kernel<double>, dim3(trips_d), dim3(kSpWg), 0, env.stream, blk_layer, ly, ty, nbf, nb, res, st, blk_gt, blk_eq, loc, out);
+    if (packed && total_k) {
+        const uint64_t n_limbs = (total_k * static_cast<uint64_t>(bits) + 63) / 64;
+        hipLaunchKernelGGL(spt_pack_kernel, dim3(static_cast<unsigned>((n_limbs + 255) / 256)), dim3(256), 0, env.stream, loc, total_k, bits, n_limbs, packed);
+    }
+    return hipGetLastError();
+}
+
 // One layer: the model-wide passes on a ONE-layer table that a kernel writes on the device -- table, block map, select state and
 // histogram in one launch, no upload, no synchronisation (capturable).  Round 5: the single-layer kernels this replaces kept one element
 // per lane in their count / write passes and a strided single-workgroup scan.

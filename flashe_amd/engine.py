@@ -1301,6 +1301,15 @@ class Engine:
         self._check(self._lib.flashe_sparsify_batch_dev(self._h, L, an, ak, self._ptr(x), 1 if x_is_f64 else 0, self._ptr(residual),
                                                         self._ptr(loc), self._ptr(vals)))
 
+    def sparsify_tensors_dev(self, n, layers, ks, residual, loc, vals, packed=None, bits=0):
+        """Top-k of every layer where its owner keeps it (flashe_sparsify_tensors_dev): layers = [(start, ptr, dtype code)] in model order,
+        ks the entries each keeps.  The residual / value buffers hold layer after layer in its compute type (float64 for TENSOR_F64, else
+        float32), each aligned to its element size; loc receives the model-wide locations, packed (optional) `_to_bytes(loc, bits)`."""
+        arr, nl = self._tensor_layers([(start, ptr, 1.0, 0.0, dtype, 0) for start, ptr, dtype in layers])
+        ak = (c_u64 * max(nl, 1))(*[int(v) for v in ks])
+        self._check(self._lib.flashe_sparsify_tensors_dev(self._h, int(n), arr, nl, ak, self._ptr(residual), self._ptr(loc), self._ptr(vals),
+                                                          self._ptr(packed), int(bits)))
+
     def sparsify_batch(self, layers, ks, residuals=None):
         """[(loc uint32[k_l] ascending, vals[k_l], new residual or None) per layer] -- Client.sparsify's layer loop
         (jzf_aggregator.py:585-613) as ONE upload, one set of launches and one download.  All layers share one float type."""

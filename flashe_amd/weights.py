@@ -114,12 +114,24 @@ class Sparsifier(object):
     before `flatten += remain`); ties at the k-th magnitude go to the higher index (numpy's default argsort
     leaves them unspecified)."""
 
-    def __init__(self, sparsity, device=0):
+    def __init__(self, sparsity, device=0, stream=None):
+        """stream (new): a framework's hipStream_t as an int -- the engine runs on it, as FlasheClient(stream=...)."""
         self._sparsity = sparsity
         self._device = device
+        self._stream = stream
+        self._own_engine = None
         self._remain_host = None            # name -> residual array (what the reference keeps in self.remain_weights)
-        self._remain_dev = None             # or: (DeviceBuffer of the flat residuals, names, sizes, dtype) -- they stay in HBM between rounds
+        self._remain_dev = None             # or: (DeviceBuffer of the residuals, names, sizes, dtype) -- they stay in HBM between rounds;
+        #                                     dtype: one NumPy dtype (layers back to back), or a tuple of per-layer compute types (_compact_layout)
         self.shape_dict_used_for_sparsification = None
+        self.locations = None               # tensor path: (DeviceBuffer of the last call's uint32 model-wide locations, count)
+
+    def _engine(self):
+        if not self._stream:
+            return _engine(128, self._device)
+        if self._own_engine is None:
+            self._own_engine = Engine(bytes(32), 128, device=self._device, stream=self._stream)
+        return self._own_engine
 
     @property
     def remain_weights(self):
@@ -127,11 +139,16 @@ class Sparsifier(object):
         and updated by the next sparsify); reading this attribute downloads them."""
         if self._remain_dev is not None and self._remain_host is None:
             buf, names, sizes, dt = self._remain_dev
-            flat = buf.download(dt, sum(sizes))
-            self._remain_host, o = {}, 0
-            for name, n in zip(names, sizes):
-                self._remain_host[name] = flat[o:o + n]
-                o += n
+            if isinstance(dt, tuple):               # (a mixed float32 / float64 model of the tensor path)
+                offs, nbytes = _compact_layout(sizes, dt)
+                raw = buf.download(np.uint8, nbytes)
+                self._remain_host = {name: raw[o:o + n * d.itemsize].view(d).copy() for name, n, d, o in zip(names, sizes, dt, offs)}
+            else:
+                flat = buf.download(dt, sum(sizes))
+                self._remain_host, o = {}, 0
+                for name, n in zip(names, sizes):
+                    self._remain_host[name] = flat[o:o + n]
+                    o += n
         return self._remain_host
 
     @remain_weights.setter
@@ -140,9 +157,18 @@ class Sparsifier(object):
 
     def sparsify(self, weights, walking_order=None):
         """weights: dict name -> float ndarray, replaced IN PLACE by the compact masked layers.
-        Returns (encoded_locations, length, bits, total) like the reference."""
-        eng = _engine(128, self._device)
+        Returns (encoded_locations, length, bits, total) like the reference.
+
+        Layers may also be a framework's float DEVICE tensors (float32 / float64 / float16 / bfloat16, DLPack or __cuda_array_interface__);
+        with any of them the whole model goes through ONE set of launches where the tensors lie (flashe_sparsify_tensors_dev; host layers
+        among them go up into engine scratch), the tensors are not written, and weights[k] becomes a CompactLayer -- the kept values in
+        HBM, read in place by FlasheClient.quantize_encrypt.  Only the packed locations come down.  Bit for bit the host path on the
+        tensors' host copies (float16 / bfloat16: widened to float32), residuals included."""
+        from . import interop
+        eng = self._engine()
         order = list(walking_order) if walking_order is not None else sorted(weights.keys(), key=str)
+        if any(interop.is_foreign(weights[k]) for k in order):
+            return self._sparsify_tensors(eng, weights, order)
         base, locations, shapes = 0, [], {}
         layers, ks = [], []
         for k in order:
@@ -157,7 +183,7 @@ class Sparsifier(object):
             # every layer in one set of launches (a layer-by-layer walk is ~12 launches and three synchronous transfers PER LAYER), the
             # layers copied straight into one flat device buffer, the residuals kept in HBM from round to round
             dev = self._remain_dev
-            if dev is None or dev[1] != order or dev[2] != sizes or dev[3] != dt:
+            if dev is None or dev[1] != order or dev[2] != sizes or not _same_dtype(dev[3], dt):
                 host = self.remain_weights or {}            # (downloads what a differently shaped earlier round left on the device)
                 if not any(host.get(k) is not None for k in order):
                     # the first round: no residual yet -- zeroed where it will live, not 4 or 8 bytes per value of zeros over PCIe
@@ -190,3 +216,132 @@ class Sparsifier(object):
         bits = int(base).bit_length()
         encoded, le = to_big_int(all_loc, bits, self._device)
         return encoded, le, bits, base
+
+    def _sparsify_tensors(self, eng, weights, order):
+        """sparsify() with framework tensors among the layers (see there)."""
+        from . import interop
+        from ._lib import TENSOR_BF16, TENSOR_F16, TENSOR_F32, TENSOR_F64
+        codes = {"float32": TENSOR_F32, "float64": TENSOR_F64, "float16": TENSOR_F16, "bfloat16": TENSOR_BF16}
+        layers = []                                 # [ForeignArray or host flat array, shape, dtype code, compute dtype]
+        for k in order:
+            v = weights[k]
+            if interop.is_foreign(v):
+                fa = eng.foreign(v, what=f"layer {k!r}")
+                if fa.dtype not in codes:
+                    raise TypeError(f"layer {k!r}: unsupported dtype {fa.dtype} (float32, float64, float16 or bfloat16)")
+                layers.append([fa, fa.shape, codes[fa.dtype], np.dtype(np.float64 if fa.dtype == "float64" else np.float32)])
+            else:
+                a = np.asarray(v)
+                flat = np.ascontiguousarray(a).reshape(-1)
+                if flat.dtype not in (np.float32, np.float64):
+                    flat = flat.astype(np.float64)
+                layers.append([flat, a.shape, TENSOR_F64 if flat.dtype == np.float64 else TENSOR_F32, flat.dtype])
+        sizes = [int(np.prod(shape, dtype=np.int64)) for _x, shape, _c, _d in layers]
+        for k, size in zip(order, sizes):
+            if size == 0:
+                raise ValueError(f"layer {k!r} is empty: the sparsifier keeps max(1, floor(sparsity * size)) values of every layer")
+        ks = [max(1, int(np.floor(self._sparsity * size))) for size in sizes]
+        cts = tuple(d for _x, _s, _c, d in layers)
+        dt = cts[0] if len(set(cts)) == 1 else cts
+        host_off, nbytes = {}, 0
+        for li, (x, _shape, _code, _d) in enumerate(layers):
+            if isinstance(x, np.ndarray):
+                host_off[li] = nbytes
+                nbytes += (x.nbytes + 15) & ~15
+        xbuf = eng.alloc(max(nbytes, 16)) if host_off else None
+        for li, off in host_off.items():
+            xbuf.upload_at(off, layers[li][0])
+        # the residuals: kept in HBM in the layout of the call; a round of another layout (or a host round) continues from the host copy
+        roffs, rbytes = _compact_layout(sizes, cts)
+        dev = self._remain_dev
+        if dev is None or dev[1] != order or dev[2] != sizes or not _same_dtype(dev[3], dt):
+            host = self.remain_weights or {}
+            buf = eng.alloc(max(rbytes, 16))
+            if not any(host.get(k) is not None for k in order):
+                eng.memset_dev(buf, 0, buf.nbytes)
+            else:
+                raw = np.zeros(rbytes, dtype=np.uint8)
+                for k, n, d, o in zip(order, sizes, cts, roffs):
+                    if host.get(k) is not None:
+                        raw[o:o + n * d.itemsize] = np.ascontiguousarray(host[k], dtype=d).reshape(-1).view(np.uint8)
+                buf.upload(raw)
+            dev = (buf, order, sizes, dt)
+        voffs, vbytes = _compact_layout(ks, cts)
+        total, total_k = sum(sizes), sum(ks)
+        bits = int(total).bit_length()
+        n_limbs = (total_k * bits + 63) // 64
+        loc, vals, packed = eng.alloc(max(4 * total_k, 16)), eng.alloc(max(vbytes, 16)), eng.alloc(max(8 * n_limbs, 16))
+        table, starts, at, keep = [], [], 0, []
+        for li, (x, _shape, code, _d) in enumerate(layers):
+            if isinstance(x, np.ndarray):
+                ptr = xbuf.ptr + host_off[li]
+            else:
+                ptr = x.ptr
+                keep.append(x.keep)
+            table.append((at, ptr, code))
+            starts.append(at)
+            at += sizes[li]
+        eng.sparsify_tensors_dev(total, table, ks, dev[0], loc, vals, packed, bits)
+        eng.hold(keep + [xbuf] if xbuf is not None else keep)
+        self._remain_dev, self._remain_host = dev, None
+        for k, kl, d, o in zip(order, ks, cts, voffs):
+            weights[k] = CompactLayer(eng, vals, o, kl, d)
+        self.locations = (loc, total_k)
+        if self.shape_dict_used_for_sparsification is None:
+            self.shape_dict_used_for_sparsification = {k: tuple(shape) for k, (_x, shape, _c, _d) in zip(order, layers)}
+        encoded = int.from_bytes(packed.download(np.uint64, n_limbs).tobytes(), "little") if total_k else 0
+        return encoded, total_k, bits, total
+
+
+def _compact_layout(counts, dtypes):
+    """Byte offsets of consecutive per-layer runs of counts[l] values of dtypes[l], each aligned to its element size (the residual /
+    value layout of flashe_sparsify_tensors_dev) -> (offsets, total bytes).  One dtype: the plain back-to-back layout."""
+    offs, at = [], 0
+    for n, d in zip(counts, dtypes):
+        sz = np.dtype(d).itemsize
+        at = (at + sz - 1) // sz * sz
+        offs.append(at)
+        at += int(n) * sz
+    return offs, at
+
+
+def _same_dtype(a, b):
+    if isinstance(a, tuple) or isinstance(b, tuple):
+        return isinstance(a, tuple) and isinstance(b, tuple) and a == b
+    return np.dtype(a) == np.dtype(b)
+
+
+class CompactLayer(object):
+    """The values Sparsifier kept of one layer, left in HBM (a view into the engine's buffer of the round's compact values): 1-D float32
+    or float64 with `__cuda_array_interface__` v3 on the engine's stream -- what FlasheClient.quantize_encrypt reads in place -- and
+    `to_host()`."""
+
+    def __init__(self, engine, buf, offset, n, dtype):
+        self.engine, self.buf, self.offset, self.n, self.dtype = engine, buf, int(offset), int(n), np.dtype(dtype)
+
+    @property
+    def ptr(self):
+        return self.buf.ptr + self.offset
+
+    @property
+    def shape(self):
+        return (self.n,)
+
+    @property
+    def size(self):
+        return self.n
+
+    def __len__(self):
+        return self.n
+
+    @property
+    def __cuda_array_interface__(self):
+        s = self.engine.stream
+        return {"shape": (self.n,), "typestr": self.dtype.str, "data": (self.ptr, True), "strides": None, "version": 3,
+                "stream": s if s else 1}
+
+    def to_host(self):
+        return self.buf.download_at(self.offset, self.dtype, self.n)
+
+    def __repr__(self):
+        return f"CompactLayer({self.dtype.name}[{self.n}] on device {self.engine.device})"

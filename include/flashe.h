@@ -749,6 +749,21 @@ int flashe_sparsify_batch_dev(flashe_ctx *ctx, int n_layers, const uint64_t *n, 
                               void *residual_dev, uint32_t *loc_dev, void *vals_dev);
 int flashe_sparsify_batch(flashe_ctx *ctx, int n_layers, const uint64_t *n, const uint64_t *k, const void *x, int x_is_f64,
                           void *residual, uint32_t *loc, void *vals);
+/* Client.sparsify over a framework's own layers (new): flashe_sparsify_batch_dev's selection (same ranking and tie rule) on layers that
+ * lie where their owner put them, in their own dtypes, with the outputs the sparse job sends.  layers: HOST table as for the tensor codec
+ * (flashe_tensor_layer; ascending start, layers[0].start == 0, layer l holds dense elements [start_l, start_l+1), the last one ends at n;
+ * ptr at any element-aligned address; alpha, shift and flags are ignored); k: HOST array of the entries each layer keeps (k_l <= n_l).
+ * Compute type c_l: float64 for an F64 layer, float32 for F32, F16 and BF16 (16-bit values widened exactly); any mix in one call.
+ *   residual_dev (engine-owned; NULL = zeros, not written): layer l's n_l values in c_l at byte offset R_l, R_0 = 0,
+ *       R_l = align(R_{l-1} + n_{l-1} size(c_{l-1}), size(c_l)) -- for one compute type exactly flashe_sparsify_batch_dev's flat layout.
+ *       Updated in place: 0 where an entry was kept, x + residual elsewhere (in c_l).
+ *   vals_dev: layer l's k_l kept values x + residual (in c_l), ascending index, at byte offset V_l (the same rule on k).
+ *   loc_dev: the K = sum k_l model-wide locations start_l + index, uint32, layer after layer (ascending across the model).
+ *   packed_dev (NULL = none): `_to_bytes(loc, bits)` (jzf_aggregator.py:615-623) as ceil(K bits / 64) little-endian uint64 limbs -- what
+ *       weights.to_big_int(loc, bits) returns; 1 <= bits <= 32, n <= 2^bits.
+ * n < 2^32.  The tables are uploaded synchronously (not inside a graph capture); 14 launches for a float32-class model, 24 mixed. */
+int flashe_sparsify_tensors_dev(flashe_ctx *ctx, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const uint64_t *k, void *residual_dev,
+                                uint32_t *loc_dev, void *vals_dev, uint64_t *packed_dev, int bits);
 
 /* ---- multi-GPU exchange (RCCL over xGMI; one process per GPU) ----------------------------------------------- */
 /* Replaces, inside one node, the arbiter's gather of client models + reduce in Python + broadcast of the aggregate
