@@ -1,0 +1,77 @@
+#!/usr/bin/env python3
+"""A federation of ten clients simulated on ONE GPU: ten small PyTorch models in, the new global model out.
+
+FlasheCohort takes one Weights per client (the parameters as they are, read through DLPack), runs the clients' quantise + encrypt as one
+chained launch where the model is long enough to fill the chip (shorter models take the staged form: `upload.path` says which), and
+decrypt_unquantize writes the new global model into `out`.  The result is bit for bit what ten FlasheClients produce one after the other,
+which this example checks."""
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from flashe_amd import cipher as cm  # noqa: E402
+from flashe_amd.block import FlasheClient, FlasheCohort  # noqa: E402
+
+
+class Weights:
+    """What the clients walk: JZFOrderDictWeights' surface (walking_order, _weights)."""
+
+    def __init__(self, layers):
+        self.walking_order = sorted(layers)
+        self._weights = dict(layers)
+
+
+def make_model(seed):
+    torch.manual_seed(seed)
+    return torch.nn.Sequential(torch.nn.Conv2d(3, 16, 5), torch.nn.ReLU(), torch.nn.Flatten(), torch.nn.Linear(16 * 28 * 28, 10)).cuda()
+
+
+def main():
+    cm.N_JOBS = 16                                           # every party must use the same value
+    C, key = 10, bytes(range(32))
+    args = {"quantize": {"int_bits": 128, "batch": False, "element_bits": 16, "padding": True, "secure": True}, "precompute": {"enable": False}}
+    models = [make_model(c) for c in range(C)]
+    layers = [{name: p.detach() for name, p in m.named_parameters()} for m in models]
+
+    cohort = FlasheCohort(args, first_idx=0, n_local=C, num_clients=C, prp_seed=key)
+    cohort.set_iter_index(0)
+    np.random.seed(0)
+    with torch.no_grad():
+        upload = cohort.quantize_encrypt([Weights(l) for l in layers], normalize=True)
+        new_global = {name: torch.empty_like(t) for name, t in layers[0].items()}
+        cohort.decrypt_unquantize(out=new_global, unnormalize=True)
+    print(f"{C} clients, {sum(t.numel() for t in layers[0].values())} parameters each: path {upload.path!r}, "
+          f"{len(upload.ciphertexts)} ciphertexts and their sum in HBM")
+
+    # the same round as ten FlasheClients, one after the other
+    clients = []
+    for c in range(C):
+        cl = FlasheClient(args)
+        cl.create_cipher(c, C, key)
+        cl.set_iter_index(0)
+        clients.append(cl)
+    np.random.seed(0)
+    with torch.no_grad():
+        cts = []
+        for cl, l in zip(clients, layers):
+            w = cl.quantize_encrypt(Weights(l), device=True, normalize=True)
+            cts.append(w._weights[w.walking_order[0]])
+        agg = clients[0].cipher.aggregate(cts)
+        clients[0].set_idx_list(list(range(C)))
+        want = {name: torch.empty_like(t) for name, t in layers[0].items()}
+        clients[0].decrypt_unquantize(Weights({sorted(layers[0])[0]: agg}), out=want, unnormalize=True)
+    for c in range(C):
+        assert upload.ciphertexts[c].to_host().tobytes() == cts[c].to_host().tobytes(), f"client {c}'s upload differs"
+    assert upload.partial_sum.to_host().tobytes() == agg.to_host().tobytes()
+    for name in want:
+        assert torch.equal(want[name].view(torch.uint8), new_global[name].view(torch.uint8)), name
+    mean = sum(l["3.bias"].double() for l in layers) / C
+    print("new global model equals ten FlasheClient steps bit for bit; |3.bias - mean of the clients'| <=",
+          float((new_global["3.bias"].double() - mean).abs().max()))
+
+
+if __name__ == "__main__":
+    main()

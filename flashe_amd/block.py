@@ -13,7 +13,7 @@ from .quantize import QuantizingClient
 
 _RNG_RUN_MAX = 1 << 26          # draws per device call of quantize_encrypt (512 MiB of float64)
 
-__all__ = ["dynamic_masking_choice", "FlasheClient"]
+__all__ = ["dynamic_masking_choice", "FlasheClient", "FlasheCohort", "CohortPlan", "CohortUpload", "plan_cohort"]
 
 
 def dynamic_masking_choice(masks, total, engine=None):
@@ -839,3 +839,381 @@ class FlasheClient(object):
     def prepare_decrypt(self):
         if self.precompute:
             self.cipher.prepare_decrypt()
+
+
+# ---- a cohort of consecutive clients hosted on one GPU (new) --------------------------------------------------------------------
+COHORT_CHAIN, STAGED_CHAIN, PER_CLIENT = "cohort-chain", "staged-chain", "per-client"
+_COHORT_MAX_LINKS = 128          # outputs of one chained launch (kMaxLinks, kernels.hip)
+
+
+class _Layers(object):
+    """The surface FlasheClient walks (JZFOrderDictWeights': walking_order, _weights) around a dict of layers."""
+
+    def __init__(self, layers):
+        self._weights = dict(layers)
+        self.walking_order = sorted(self._weights.keys(), key=str)
+
+
+class CohortPlan(object):
+    """What plan_cohort returns: names / shapes / sizes / starts of the shared layer table, n (values of one model), n_elems (ciphertext
+    elements of one upload: n, or the batched count), draw_offsets (client c's first draw in the client-major draws), path and the
+    reason for it."""
+
+    def __init__(self, names, shapes, sizes, starts, n, n_elems, draw_offsets, path, reason):
+        self.names, self.shapes, self.sizes, self.starts = names, shapes, sizes, starts
+        self.n, self.n_elems, self.draw_offsets, self.path, self.reason = n, n_elems, draw_offsets, path, reason
+
+
+class CohortUpload(object):
+    """FlasheCohort.quantize_encrypt's result: ciphertexts (one DeviceVector per client), partial_sum (their sum mod 2^b) and path."""
+
+    def __init__(self, ciphertexts, partial_sum, path):
+        self.ciphertexts, self.partial_sum, self.path = ciphertexts, partial_sum, path
+
+
+def _layer_shape(v):
+    return tuple(int(d) for d in (v.shape if hasattr(v, "shape") else np.shape(v)))
+
+
+def _layer_is_f64(v):
+    """Does the layer compute in float64 whatever its alpha is -- a float64 array, or a host array that is not a float array at all?"""
+    name = str(getattr(v, "dtype", "float64")).replace("torch.", "")
+    if isinstance(v, np.ndarray) or not hasattr(v, "shape"):
+        return name != "float32"                   # (a host layer that is not float32 is quantised as float64)
+    return name not in ("float32", "float16", "bfloat16")
+
+
+def cohort_admission_length(cu_count):
+    """The shortest vector the summed chain takes uncut: two whole 256-element tiles for each of the chip's 16 x cu_count waves."""
+    return (2 * 16 * int(cu_count) - 1) * 256 + 1
+
+
+def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, mask="double", num_clients=None, precompute=False, chain=True,
+                location_masks=False):
+    """The engine-free part of FlasheCohort.quantize_encrypt: checks that the clients' Weights describe one model (the same layer names
+    in the same walking order with the same shapes: ValueError naming the client and the layer otherwise; a sparse upload -- a 'zzz'
+    layer or location masks -- is a TypeError), lays out the shared layer table and the client-major draws, and picks the path:
+      "cohort-chain"  one chained launch from the floats (flashe_quantize_encrypt_cohort_dev): double mask, int_bits > 64, not batched, at
+                      most 128 clients, a model of at least cohort_admission_length(cu_count) values, FLASHE_CHAIN not 0, every layer
+                      float64 for all clients or for none;
+      "per-client"    precompute handles (and masks other than single / double): the clients' own steps, then aggregate;
+      "staged-chain"  everything else: a quantise (+ batch) pass per client into plaintexts, then the summed batch encrypt.
+    Touches no device.  The library's own answer stays the last word: a "cohort-chain" plan it declines runs "staged-chain"."""
+    if len(weights_list) < 1:
+        raise ValueError("a cohort needs at least one client's Weights")
+    C = len(weights_list)
+    num_clients = C if num_clients is None else int(num_clients)
+    names = None
+    shapes, f64 = [], []
+    mixed = False
+    for c, w in enumerate(weights_list):
+        order = list(w.walking_order)
+        if "zzz" in w._weights or location_masks:
+            raise TypeError(f"client {c}: sparse uploads (a 'zzz' layer or location masks) are not supported by FlasheCohort")
+        if names is None:
+            names = order
+            shapes = [_layer_shape(w._weights[k]) for k in order]
+            f64 = [_layer_is_f64(w._weights[k]) for k in order]
+            continue
+        if order != names:
+            odd = next((k for k in order if k not in names), None) or next((k for k in names if k not in order), None)
+            if odd is None:
+                odd = next(a for a, b in zip(order, names) if a != b)
+                raise ValueError(f"client {c}: layer {odd!r} comes at another place of the walking order than in client 0's")
+            raise ValueError(f"client {c}: layer {odd!r} is not a layer of every client of the cohort")
+        for li, k in enumerate(order):
+            shp = _layer_shape(w._weights[k])
+            if shp != shapes[li]:
+                raise ValueError(f"client {c}: layer {k!r} has shape {shp}, client 0's has {shapes[li]}")
+            mixed |= _layer_is_f64(w._weights[k]) != f64[li]
+    sizes = [int(np.prod(shp, dtype=np.int64)) for shp in shapes]
+    starts, n = [], 0
+    for s_ in sizes:
+        starts.append(n)
+        n += s_
+    n_elems = n
+    if batch:
+        bs = int_bits // (element_bits + int(np.ceil(np.log2(num_clients))))
+        n_elems = sum((s_ + bs - 1) // bs for s_ in sizes)
+    if precompute:
+        path, reason = PER_CLIENT, "precomputed masks are held per client"
+    elif mask not in ("double", "single"):
+        path, reason = PER_CLIENT, f"mask {mask!r}"
+    elif mask != "double":
+        path, reason = STAGED_CHAIN, "single mask: no stream is shared"
+    elif int_bits <= 64:
+        path, reason = STAGED_CHAIN, "int_bits <= 64"
+    elif batch:
+        path, reason = STAGED_CHAIN, "batched job"
+    elif C > _COHORT_MAX_LINKS:
+        path, reason = STAGED_CHAIN, f"more than {_COHORT_MAX_LINKS} clients"
+    elif not chain:
+        path, reason = STAGED_CHAIN, "FLASHE_CHAIN=0"
+    elif n < cohort_admission_length(cu_count) or n > 2 ** 32:
+        path, reason = STAGED_CHAIN, "the vector does not fill the chip uncut"
+    elif mixed:
+        path, reason = STAGED_CHAIN, "a layer is float64 for some clients only"
+    else:
+        path, reason = COHORT_CHAIN, ""
+    return CohortPlan(names, shapes, sizes, starts, n, n_elems, [c * n for c in range(C)], path, reason)
+
+
+class _CohortLead(FlasheClient):
+    """The cohort's one FlasheClient (its quantiser state is the cohort's): the decrypt of the cohort's own sum adds the mask the chained
+    launch wrote -- one memory-bound pass -- instead of computing its two PRF streams again."""
+    _cohort_mask = None          # (sum's device pointer, mask DeviceVector, iter, add prefix, minus prefix)
+
+    def _decrypt_floats(self, dv, sizes, mode, add_idx, minus_idx):
+        m, q, c = self._cohort_mask, self.quantizer, self.cipher
+        if (m is None or mode is not None or self.batch or dv.ptr != m[0] or c.iter_index != m[2] or list(add_idx) != [m[3]]
+                or list(minus_idx) != [m[4]] or len(dv) != len(m[1])):
+            return super()._decrypt_floats(dv, sizes, mode, add_idx, minus_idx)
+        eng, n = c.engine, len(dv)
+        if sum(sizes) > n:
+            raise ValueError(f"the aggregate has {n} elements, shape_dict describes {sum(sizes)}")
+        table, at = [], 0
+        for li, size in enumerate(sizes):
+            table.append((at, None, q.alpha_list[li], False))
+            at += size
+        dout = eng.alloc(max(8 * n, 16))
+        eng.combine_unquantize_model_dev(n, dv.buf, m[1].buf, None, table, q.element_bits, q.num_clients, dout)
+        return dout
+
+
+class FlasheCohort(object):
+    """`n_local` consecutive clients (ciphers first_idx .. first_idx + n_local - 1 of a federation of num_clients) hosted on ONE GPU --
+    a federation simulated on one card, or one card's share of it.  The results are those of n_local FlasheClients run one after the
+    other in one process -- every ciphertext, their aggregate, decrypt_unquantize's floats, shape_dict, alpha_list and the mean / std
+    history, bit for bit -- but the clients' steps run as ONE chained launch where the chain admits the shape: it quantises every client's
+    float model, encrypts with the PRF streams consecutive clients share (n_local + 1 instead of 2 n_local) and writes their sum and the
+    decrypt mask, and one memory-bound pass turns the sum into the new float model.  All clients share one quantiser state (every
+    client's mean / std / alpha history derives from the same global model).  `path` of the result names the form that ran."""
+
+    def __init__(self, args, first_idx, n_local, num_clients, prp_seed, device=0, stream=None):
+        if n_local < 1 or first_idx < 0 or first_idx + n_local > num_clients:
+            raise ValueError(f"clients {first_idx} .. {first_idx + n_local - 1} are not clients of a federation of {num_clients}")
+        self.first_idx, self.n_local, self.num_clients = int(first_idx), int(n_local), int(num_clients)
+        self.lead = _CohortLead(args, device=device, stream=stream)
+        self.lead.create_cipher(self.first_idx, self.num_clients, prp_seed)
+        self._clients = None
+        if self.lead.precompute:                       # precomputed masks are per cipher: every client its own, one quantiser state
+            self._clients = [self.lead]
+            for c in range(1, self.n_local):
+                cl = FlasheClient(args, device=device, stream=stream)
+                cl.create_cipher(self.first_idx + c, self.num_clients, prp_seed)
+                cl.quantizer = self.lead.quantizer
+                self._clients.append(cl)
+        self._last = None                              # the last upload (its sum is what decrypt_unquantize() decrypts)
+        self.prefer = None                             # "staged-chain" / "per-client": run that fallback form where the chain would be taken (A/B runs)
+
+    quantizer = property(lambda self: self.lead.quantizer)
+    cipher = property(lambda self: self.lead.cipher)
+    shape_dict = property(lambda self: self.lead.shape_dict)
+
+    def set_iter_index(self, iter_index):
+        for cl in (self._clients or [self.lead]):
+            cl.cipher.set_iter_index(iter_index)
+        self.lead.quantizer.set_iter(iter_index)
+        self.lead._cohort_mask = None
+        self._last = None
+
+    def plan(self, weights_list):
+        """plan_cohort with this cohort's settings and the engine's CU count."""
+        ld = self.lead
+        return plan_cohort(weights_list, ld.int_bits, ld.cipher.engine.cu_count, element_bits=ld.quantizer.element_bits, batch=bool(ld.batch),
+                           mask=ld.cipher.masking_scheme, num_clients=self.num_clients, precompute=bool(ld.precompute),
+                           chain=os.environ.get("FLASHE_CHAIN", "1") != "0", location_masks=ld.cipher.masks is not None)
+
+    def quantize_encrypt(self, weights_list, normalize=False, seeds=None):
+        """One Weights per client (host arrays and / or framework float device tensors, as FlasheClient.quantize_encrypt takes them) ->
+        CohortUpload.  seeds=None: the stochastic-rounding draws come from NumPy's global stream in client order (client c takes draws
+        [c n, (c + 1) n) and the generator is left where n_local sequential steps leave it); seeds=[s_0 ..]: client c draws after
+        np.random.seed(s_c), as separate processes would.  The draws of ALL clients are materialised in HBM (8 bytes each: 2.3 GB for ten
+        29.2 M-parameter models), on the device under quantize_encrypt's conditions (MT19937, DEVICE_RNG_MIN).  Mismatched Weights raise
+        ValueError and unusable tensors are refused before anything is launched.  Own-stream engines keep the tensors alive until the
+        last kernel that reads them has finished."""
+        from . import cipher as _cipher_mod
+        from . import interop
+        from ._lib import TENSOR_BF16, TENSOR_F16, TENSOR_F32, TENSOR_F64, TENSOR_LOOP_F64, TENSOR_SHIFT, TENSOR_SHIFT_WIDE
+        from .engine import DeviceVector
+        from .quantize import ACIQ, DEVICE_RNG_MIN, _loop_dtype
+        ld = self.lead
+        q, c = ld.quantizer, ld.cipher
+        C = self.n_local
+        if len(weights_list) != C:
+            raise ValueError(f"the cohort holds {C} clients, got {len(weights_list)} Weights")
+        if seeds is not None and len(seeds) != C:
+            raise ValueError(f"seeds: one per client ({C}), got {len(seeds)}")
+        plan = self.plan(weights_list)
+        eng = c.engine
+        codes = {"float32": TENSOR_F32, "float64": TENSOR_F64, "float16": TENSOR_F16, "bfloat16": TENSOR_BF16}
+        # every layer of every client as (ForeignArray or flat host array, NumPy dtype of its host copy): the refusals come first
+        layers = []
+        for ci, w in enumerate(weights_list):
+            row = []
+            for k in plan.names:
+                v = w._weights[k]
+                if interop.is_foreign(v):
+                    fa = eng.foreign(v, what=f"client {ci} layer {k!r}")
+                    if fa.dtype not in codes:
+                        raise TypeError(f"client {ci} layer {k!r}: unsupported dtype {fa.dtype} (float32, float64, float16 or bfloat16)")
+                    row.append((fa, np.dtype(np.float64 if fa.dtype == "float64" else np.float32)))
+                else:
+                    flat = np.ascontiguousarray(np.asarray(v)).reshape(-1)
+                    if flat.dtype not in (np.float32, np.float64):
+                        flat = flat.astype(np.float64)
+                    row.append((flat, flat.dtype))
+            layers.append(row)
+        self._last, ld._cohort_mask = None, None
+        if any(row[li][1] != layers[0][li][1] for row in layers for li in range(len(row))) and plan.path == COHORT_CHAIN:
+            plan.path = STAGED_CHAIN                   # (a layer that computes in float64 for some clients only: no shared row)
+        if self.prefer == PER_CLIENT or (self.prefer == STAGED_CHAIN and plan.path == COHORT_CHAIN):
+            plan.path = self.prefer
+        if plan.path == PER_CLIENT:
+            return self._per_client(weights_list, normalize, seeds)
+        if not ld._fusable():
+            raise TypeError("FlasheCohort needs the fused client step (fuse=True, a keyed cipher, no location masks)")
+        # the one quantiser state: set_layer_size_list and the alphas of this round, as FlasheClient._quantize_encrypt_tensors
+        if q.layer_size_list is None:
+            q.layer_size_list = list(plan.sizes)
+            for _ in q.layer_size_list:
+                q.past_layer_mean_list.append(q.expected_mean_for_first_round)
+                q.past_layer_std_list.append(q.expected_std_for_first_round)
+        aciq = ACIQ(q.element_bits)
+        alphas = []
+        for i, _size in enumerate(q.layer_size_list):
+            a = aciq.get_alpha_gaus_direct(q.past_layer_std_list[i])
+            alphas.append(0.1 if a == 0 else a)
+        q.r_max_list = [alphas[li] * q.num_clients for li in range(len(plan.names))]
+        q.alpha_list = [alphas[li] for li in range(len(plan.names))]
+        c.set_idx_list(mode="encrypt")
+        scheme = 1 if c.masking_scheme == "double" else 0
+        n, n_elems, nl = plan.n, plan.n_elems, len(plan.names)
+        # host layers go up once, client by client
+        keep, tables = [], []
+        for ci, row in enumerate(layers):
+            offs, nbytes = {}, 0
+            for li, (x, _dt) in enumerate(row):
+                if isinstance(x, np.ndarray):
+                    offs[li] = nbytes
+                    nbytes += (x.nbytes + 15) & ~15
+            xbuf = eng.alloc(max(nbytes, 16)) if offs else None
+            for li, off in offs.items():
+                xbuf.upload_at(off, row[li][0])
+            if xbuf is not None:
+                keep.append(xbuf)
+            table = []
+            for li, (x, hdt) in enumerate(row):
+                alpha = alphas[li]
+                flags, shift = 0, 0.0
+                if hdt != np.float64 and _loop_dtype(hdt, alpha) == np.float64:
+                    flags |= TENSOR_LOOP_F64
+                if normalize:
+                    shift = -q.past_layer_mean_list[li]
+                    flags |= TENSOR_SHIFT
+                    if hdt == np.float32 and _loop_dtype(hdt, shift) == np.float64:
+                        flags |= TENSOR_SHIFT_WIDE
+                if isinstance(x, np.ndarray):
+                    ptr, code = xbuf.ptr + offs[li], TENSOR_F64 if hdt == np.float64 else TENSOR_F32
+                else:
+                    ptr, code = x.ptr, codes[x.dtype]
+                    keep.append(x.keep)
+                table.append((plan.starts[li], ptr, alpha, float(shift), code, flags))
+            tables.append(table)
+        # the draws, client-major: client c's are draws [c n, (c + 1) n).  From the global stream they are ONE stretch of C n draws (the
+        # clients draw one after the other), generated in device calls of at most _RNG_RUN_MAX draws whatever client they belong to --
+        # the jump-ahead of a device call is paid per call, not per client; with seeds every client's stretch starts at its own seed
+        dev_rng = os.environ.get("FLASHE_DEVICE_RNG", "1") != "0"
+        du = eng.alloc(max(8 * C * n, 16))
+        for seed, first, count in ([(None, 0, C * n)] if seeds is None else [(seeds[ci], plan.draw_offsets[ci], n) for ci in range(C)]):
+            if seed is not None:
+                np.random.seed(seed)
+            mt = dev_rng and np.random.get_state()[0] == "MT19937"
+            for at in range(first, first + count, _RNG_RUN_MAX):
+                tot = min(_RNG_RUN_MAX, first + count - at)
+                if mt and tot >= DEVICE_RNG_MIN:
+                    eng.numpy_random_dev(tot, out=du.ptr + 8 * at)
+                else:
+                    du.upload_at(8 * at, np.random.random(tot))
+        cts = [DeviceVector(eng, n_elems) for _ in range(C)]
+        psum = DeviceVector(eng, n_elems)
+        idxs = [self.first_idx + ci for ci in range(C)]
+        whole = self.n_local == self.num_clients
+        path = plan.path
+        if path == COHORT_CHAIN:
+            # the shared rows name the compute type; the sources keep their own storage dtypes
+            rows = [(st, None, al, sh, TENSOR_F64 if layers[0][li][1] == np.float64 else TENSOR_F32, fl)
+                    for li, (st, _p, al, sh, _code, fl) in enumerate(tables[0])]
+            srcs = [[t[1] for t in table] for table in tables]
+            dts = [[t[4] for t in table] for table in tables]
+            dmask = DeviceVector(eng, n) if whole else None
+            if eng.quantize_encrypt_cohort_dev(c.iter_index, self.first_idx, n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du,
+                                               [v.buf for v in cts], psum.buf, dmask.buf if dmask is not None else None):
+                if dmask is not None:
+                    ld._cohort_mask = (psum.ptr, dmask, c.iter_index, self.first_idx + C, self.first_idx)
+            else:
+                path = STAGED_CHAIN                    # the library declined: the planner's guess was wrong, the result is not
+        if path == STAGED_CHAIN and n_elems:
+            # a quantise (+ batch) pass per client into plaintexts -- un-batched: one value per element, field_bits = int_bits -- then the
+            # summed batch encrypt, which chains where it can
+            field_bits = q.element_bits + int(np.ceil(np.log2(q.num_clients))) if ld.batch else ld.int_bits
+            pts = [eng.alloc_vec(n_elems) for _ in range(C)]
+            for ci in range(C):
+                eng.quantize_batch_tensors_dev(tables[ci], n, q.element_bits, field_bits, du.ptr + 8 * plan.draw_offsets[ci], n_elems, pts[ci])
+            eng.encrypt_batch_sum_dev(c.iter_index, idxs, scheme, n_elems, _cipher_mod.N_JOBS, pts, eng.limbs, [v.buf for v in cts], psum.buf)
+            keep += pts
+        eng.hold(keep + [du])
+        if ld.batch:
+            bs = ld.int_bits // (q.element_bits + int(np.ceil(np.log2(q.num_clients))))
+            q.shape_list = list(plan.shapes)
+            ld.shape_dict = {k: ((s_ + bs - 1) // bs,) for k, s_ in zip(plan.names, plan.sizes)}
+        else:
+            ld.shape_dict = dict(zip(plan.names, plan.shapes))
+        for v in cts:
+            v.mark_ready()
+        psum.mark_ready()
+        self._last = CohortUpload(cts, psum, path)
+        return self._last
+
+    def _per_client(self, weights_list, normalize, seeds):
+        """The clients' own steps one after the other (one cipher re-indexed per client; with precompute: every client's own cipher and
+        masks), then the aggregate of what they wrote."""
+        ld = self.lead
+        cts = []
+        try:
+            for ci, w in enumerate(weights_list):
+                cl = self._clients[ci] if self._clients else ld
+                cl.cipher.idx = self.first_idx + ci
+                if seeds is not None:
+                    np.random.seed(seeds[ci])
+                lw = _Layers({k: w._weights[k] for k in w.walking_order})
+                lw.walking_order = list(w.walking_order)
+                up = cl.quantize_encrypt(lw, device=True, normalize=normalize)
+                cts.append(up._weights[up.walking_order[0]])
+                ld.shape_dict = cl.shape_dict
+        finally:
+            ld.cipher.idx = self.first_idx
+        psum = ld.cipher.aggregate(cts, device=True)
+        self._last = CohortUpload(cts, psum, PER_CLIENT)
+        return self._last
+
+    def decrypt_unquantize(self, aggregate=None, uploaded=None, out=None, unnormalize=False):
+        """The new global model as FlasheClient.decrypt_unquantize returns it (out=: written into the caller's tensors, in place).  Without
+        an aggregate: the cohort is the whole federation and its own last partial_sum is decrypted -- after a "cohort-chain" upload by adding
+        the mask that launch wrote (one memory-bound pass); ValueError when clients outside the cohort exist.  With an aggregate (a
+        DeviceVector, limbs, a framework tensor, or Weights holding one): `uploaded` lists the clients it sums (default: all num_clients)."""
+        ld = self.lead
+        if aggregate is None:
+            if self.n_local != self.num_clients:
+                raise ValueError(f"the cohort holds {self.n_local} of {self.num_clients} clients: decrypt_unquantize needs the federation's aggregate")
+            if self._last is None:
+                raise ValueError("decrypt_unquantize() without an aggregate needs the upload of this iteration (quantize_encrypt first)")
+            aggregate = self._last.partial_sum
+        if uploaded is None:
+            uploaded = list(range(self.num_clients))
+        if ld.shape_dict is None:
+            raise ValueError("decrypt_unquantize needs the layer shapes a quantize_encrypt left behind (shape_dict)")
+        if not hasattr(aggregate, "walking_order"):
+            aggregate = _Layers({next(iter(ld.shape_dict), "w"): aggregate})
+        ld.set_idx_list(list(uploaded))
+        return ld.decrypt_unquantize(aggregate, out=out, unnormalize=unnormalize)

@@ -1447,6 +1447,23 @@ static int check_tensor_layers(flashe_ctx *ctx, uint64_t n, const flashe_tensor_
     return FLASHE_OK;
 }
 
+// the cohort's shared rows carry no pointer: starts, dtypes and flags only
+static int check_tensor_layers_shape(flashe_ctx *ctx, uint64_t n, const flashe_tensor_layer *layers, int n_layers)
+{
+    if (n_layers < 1 || !layers) return fail(ctx, FLASHE_EINVAL, "the layer table needs at least one entry");
+    if (layers[0].start != 0) return fail(ctx, FLASHE_EINVAL, "layers[0].start must be 0");
+    if (ctx->capturing) return fail(ctx, FLASHE_EINVAL, "the tensor codec calls stage their layer table per call and cannot be captured into a graph");
+    for (int l = 0; l < n_layers; l++) {
+        const flashe_tensor_layer &y = layers[l];
+        const uint64_t end = l + 1 < n_layers ? layers[l + 1].start : n;
+        if (y.start > end || end > n) return fail(ctx, FLASHE_EINVAL, "layer %d: starts must ascend and stay within n", l);
+        if (!tensor_elem_bytes(y.dtype)) return fail(ctx, FLASHE_EINVAL, "layer %d: unknown dtype %d", l, static_cast<int>(y.dtype));
+        if (y.flags & ~(FLASHE_TENSOR_SHIFT | FLASHE_TENSOR_SHIFT_WIDE | FLASHE_TENSOR_LOOP_F64))
+            return fail(ctx, FLASHE_EINVAL, "layer %d: unknown flags 0x%x", l, static_cast<unsigned>(y.flags));
+    }
+    return FLASHE_OK;
+}
+
 extern "C++" template <class T> static int upload_tab(flashe_ctx *ctx, flashe_ctx::Buf &b, const std::vector<T> &tab, const T **tab_dev)
 {
     int rc = ensure(ctx, b, std::max<size_t>(tab.size(), 1) * sizeof(T));
@@ -1558,6 +1575,132 @@ int flashe_quantize_encrypt_tensors_dev(flashe_ctx *ctx, uint32_t iter, uint32_t
     std::vector<flashe_codec_layer> cl;
     if ((rc = tensor_codec_layers(ctx, n, layers, n_layers, first, count, cl))) return rc;
     return flashe_quantize_encrypt_model_dev(ctx, iter, idx, scheme, n, n_jobs, first, count, cl.data(), n_layers, element_bits, u_dev, ct_dev);
+}
+
+// ---- a cohort of co-located clients: C float models -> C ciphertexts + their sum (+ the decrypt mask) in one chained launch ----
+// The shared layer table, the C x n_layers sources and their storage dtypes.  A source already in its row's compute type without SHIFT is
+// read where it lies; every other one goes through ONE stage pass (tensors.hip) into ctx scratch, all clients together.
+int flashe_quantize_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                       const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                       int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev, uint64_t *dmask_dev)
+{
+    CHECK_CTX(ctx);
+    if (n_clients < 1) return fail(ctx, FLASHE_EINVAL, "flashe_quantize_encrypt_cohort_dev: n_clients must be >= 1");
+    if (!src_dev || !ct_dev || !sum_out_dev || (n && !u_dev)) return fail(ctx, FLASHE_EINVAL, "flashe_quantize_encrypt_cohort_dev: null argument");
+    if (element_bits < 1 || element_bits > 62 || element_bits > ctx->int_bits)
+        return fail(ctx, FLASHE_EINVAL, "element_bits must be in [1, min(62, int_bits)], got %d", element_bits);
+    if (reinterpret_cast<uintptr_t>(u_dev) & 7u) return fail(ctx, FLASHE_EINVAL, "u_dev must be 8-byte aligned");
+    int rc = check_tensor_layers_shape(ctx, n, layers, n_layers);
+    if (rc) return rc;
+    std::vector<uint32_t> idx(static_cast<size_t>(n_clients));
+    for (int c = 0; c < n_clients; c++) {
+        idx[c] = first_idx + static_cast<uint32_t>(c);
+        if (idx[c] < first_idx) return fail(ctx, FLASHE_EINVAL, "the cohort's cipher indices wrap around 2^32");
+    }
+    if ((rc = check_double_idx(ctx, FLASHE_SCHEME_DOUBLE, idx.data(), n_clients))) return rc;
+    for (int c = 0; c < n_clients; c++) {
+        if (!ct_dev[c]) return fail(ctx, FLASHE_EINVAL, "client %d: null ciphertext", c);
+        if ((rc = check_prf_args(ctx, 1, 1, n_jobs, ct_dev[c], nullptr, 0))) return rc;
+        if (ct_dev[c] == sum_out_dev || ct_dev[c] == dmask_dev) return fail(ctx, FLASHE_EINVAL, "client %d: the ciphertext aliases the sum or the mask", c);
+    }
+    if ((rc = check_sum_aligned(ctx, sum_out_dev))) return rc;
+    if (dmask_dev && (!aligned16(dmask_dev) || dmask_dev == sum_out_dev)) return fail(ctx, FLASHE_EINVAL, "dmask_dev must be 16-byte aligned and apart from the sum");
+    // the shapes the chained launch does not take, refused before anything is staged (launch_prf_cohort_sum's own rule is the final word)
+    {
+        const uint64_t waves = static_cast<uint64_t>(ctx->env.num_cus) * 16;
+        if (ctx->limbs != 2 || !ctx->env.use_chain || n_clients > 128 || (n + 255) / 256 < 2 * waves || n == 0 || ((n - 1) >> 32) ||
+            (ctx->env.prf_backend != PRF_AUTO && ctx->env.prf_backend != PRF_TABLE))
+            return fail(ctx, FLASHE_ENOTSUP, "flashe_quantize_encrypt_cohort_dev: not a shape of the chained cohort launch");
+    }
+    // rows of the device table (non-empty layers), the sources behind them, and what has to be staged first
+    std::vector<CodecLayer> tab;
+    std::vector<int> row_of;
+    for (int l = 0; l < n_layers; l++) {
+        const flashe_tensor_layer &y = layers[l];
+        const uint64_t end = l + 1 < n_layers ? layers[l + 1].start : n;
+        if (y.start == end) continue;
+        if (!(y.alpha > 0)) return fail(ctx, FLASHE_EINVAL, "layer %d: alpha must be positive", l);
+        if (y.dtype != FLASHE_TENSOR_F32 && y.dtype != FLASHE_TENSOR_F64)
+            return fail(ctx, FLASHE_EINVAL, "layer %d: the shared row names the COMPUTE type, FLASHE_TENSOR_F32 or FLASHE_TENSOR_F64", l);
+        tab.push_back(codec_layer_front(y.start, nullptr, y.dtype == FLASHE_TENSOR_F64 || (y.flags & FLASHE_TENSOR_LOOP_F64), y.alpha, element_bits));
+        row_of.push_back(l);
+    }
+    const size_t n_tab = tab.size();
+    std::vector<const void *> src(static_cast<size_t>(n_clients) * n_tab);
+    std::vector<TensorStage> st;
+    std::vector<size_t> st_at, st_slot;
+    uint64_t total = 0;
+    size_t bytes = 0;
+    for (int c = 0; c < n_clients; c++)
+        for (size_t r = 0; r < n_tab; r++) {
+            const int l = row_of[r];
+            const flashe_tensor_layer &y = layers[l];
+            const uint64_t size = (l + 1 < n_layers ? layers[l + 1].start : n) - y.start;
+            const size_t at = static_cast<size_t>(c) * n_layers + l;
+            const int32_t dt = src_dtype ? src_dtype[at] : y.dtype;
+            const int es = tensor_elem_bytes(dt);
+            const void *p = src_dev[at];
+            if (!es) return fail(ctx, FLASHE_EINVAL, "client %d layer %d: unknown dtype %d", c, l, static_cast<int>(dt));
+            if (!p || reinterpret_cast<uintptr_t>(p) % static_cast<uintptr_t>(es)) return fail(ctx, FLASHE_EINVAL, "client %d layer %d: null or misaligned source", c, l);
+            const bool f64 = tab[r].x_is_f64 != 0;
+            if (dt == FLASHE_TENSOR_F64 && !f64) return fail(ctx, FLASHE_EINVAL, "client %d layer %d: a float64 source under a float32 row", c, l);
+            const bool direct = !(y.flags & FLASHE_TENSOR_SHIFT) && (dt == FLASHE_TENSOR_F64 || (dt == FLASHE_TENSOR_F32 && !f64));
+            src[static_cast<size_t>(c) * n_tab + r] = p;
+            if (direct) continue;
+            bytes = (bytes + 15) & ~static_cast<size_t>(15);
+            st.push_back(TensorStage{total, p, nullptr, y.shift, dt, (y.flags & (FLASHE_TENSOR_SHIFT | FLASHE_TENSOR_SHIFT_WIDE)) | (f64 ? kTensorLoopF64 : 0)});
+            st_at.push_back(bytes);
+            st_slot.push_back(static_cast<size_t>(c) * n_tab + r);
+            total += size;
+            bytes += static_cast<size_t>(size) * (f64 ? 8 : 4);
+        }
+    if (!st.empty()) {
+        if ((rc = ensure(ctx, ctx->tensor_ws, bytes))) return rc;
+        for (size_t i = 0; i < st.size(); i++) {
+            st[i].dst = static_cast<char *>(ctx->tensor_ws.p) + st_at[i];
+            src[st_slot[i]] = st[i].dst;
+        }
+    }
+    // one block in ctx->codec_tab: the rows, then the source pointers
+    const size_t rows_bytes = (n_tab * sizeof(CodecLayer) + 15) & ~static_cast<size_t>(15);
+    std::vector<char> blob(rows_bytes + src.size() * sizeof(void *));
+    memcpy(blob.data(), tab.data(), n_tab * sizeof(CodecLayer));
+    memcpy(blob.data() + rows_bytes, src.data(), src.size() * sizeof(void *));
+    const char *blob_dev = nullptr;
+    if ((rc = upload_tab(ctx, ctx->codec_tab, blob, &blob_dev))) return rc;
+    if (!st.empty()) {
+        const TensorStage *stab = nullptr;
+        if ((rc = upload_tab(ctx, ctx->tensor_tab, st, &stab))) return rc;
+        HIP_TRY(ctx, launch_stage_layers(ctx->env, stab, static_cast<int>(st.size()), total));
+    }
+    CohortCodec cc{};
+    cc.layers = reinterpret_cast<const CodecLayer *>(blob_dev);
+    cc.src = reinterpret_cast<const void *const *>(blob_dev + rows_bytes);
+    cc.n_layers = static_cast<int>(n_tab);
+    const hipError_t e = launch_prf_cohort_sum(ctx->env, iter, n_clients, idx.data(), cc, u_dev, ct_dev, sum_out_dev, n, n_jobs, dmask_dev);
+    if (e == hipErrorNotSupported) return fail(ctx, FLASHE_ENOTSUP, "flashe_quantize_encrypt_cohort_dev: not a shape of the chained cohort launch");
+    HIP_TRY(ctx, e);
+    return FLASHE_OK;
+}
+
+int flashe_combine_unquantize_model_dev(flashe_ctx *ctx, uint64_t n, const uint64_t *in_dev, const uint64_t *add_dev, const uint64_t *minus_dev,
+                                        const flashe_codec_layer *layers, int n_layers, int element_bits, int num_clients, double *out_dev)
+{
+    CHECK_CTX(ctx);
+    if (n && (!in_dev || !out_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
+    if (num_clients < 1) return fail(ctx, FLASHE_EINVAL, "num_clients must be >= 1");
+    int rc = check_codec_bits(ctx, element_bits);
+    if (rc) return rc;
+    for (const uint64_t *p : {in_dev, add_dev, minus_dev})
+        if (p && ((ctx->limbs == 2 && !aligned16(p)) || (reinterpret_cast<uintptr_t>(p) & 7u))) return fail(ctx, FLASHE_EINVAL, "misaligned vector");
+    if (reinterpret_cast<uintptr_t>(out_dev) & 7u) return fail(ctx, FLASHE_EINVAL, "out_dev must be 8-byte aligned");
+    const CodecLayer *tab = nullptr;
+    int n_tab = 0;
+    if ((rc = stage_codec_layers(ctx, n, layers, n_layers, false, element_bits, num_clients, 0, n, &tab, &n_tab)) || n == 0) return rc;
+    Codec cq{};
+    cq.fout = out_dev; cq.layers = tab; cq.n_layers = n_tab; cq.k0 = 0;
+    HIP_TRY(ctx, launch_combine_unquantize_model(ctx->env, n, in_dev, add_dev, minus_dev, cq, out_dev));
+    return FLASHE_OK;
 }
 
 int flashe_quantize_batch_tensors_dev(flashe_ctx *ctx, const flashe_tensor_layer *layers, int n_layers, uint64_t n_values, int element_bits,

@@ -459,6 +459,44 @@ __device__ __forceinline__ uint64_t codec_quantize(const Codec &c, uint64_t k)
                                             static_cast<float>(c.den), c.u[k]);
 }
 
+// ---- the cohort front end (CohortCodec, prf_chain_cohort_kernel) ----
+// The tables are written before the launch and only read by it: wave-uniform reads go through the scalar cache.
+#define FLASHE_CONSTANT(T, p) (reinterpret_cast<__attribute__((address_space(4))) T *>(reinterpret_cast<uintptr_t>(p)))
+// wave-uniform key: the table row that holds flat element `key` (the last row with start <= key), found with scalar loads
+__device__ __forceinline__ int cohort_layer_of(const CohortCodec &cc, uint64_t key)
+{
+    int lo = 0, hi = cc.n_layers - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (*FLASHE_CONSTANT(const uint64_t, &cc.layers[mid].start) <= key) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+// one value of a row whose parameters the wave holds in SGPRs: raw = the float's bits as cohort_load left them
+__device__ __forceinline__ uint64_t cohort_load(const void *x, bool f64, uint64_t r)
+{
+    return f64 ? *FLASHE_GLOBAL(const uint64_t, static_cast<const uint64_t *>(x) + r)
+               : static_cast<uint64_t>(*FLASHE_GLOBAL(const uint32_t, static_cast<const uint32_t *>(x) + r));
+}
+__device__ __forceinline__ uint64_t cohort_quantize_raw(uint64_t raw, bool f64, double p0, double p1, double p2, double u)
+{
+    return f64 ? quantize_one<double>(__longlong_as_double(static_cast<long long>(raw)), p0, p1, p2, u)
+               : quantize_one<float>(__uint_as_float(static_cast<uint32_t>(raw)), static_cast<float>(p0), static_cast<float>(p1),
+                                     static_cast<float>(p2), u);
+}
+// the per-lane form for the few pairs that straddle a layer boundary: link's plaintext of flat element k
+__device__ __forceinline__ uint64_t cohort_quantize_lane(const CohortCodec &cc, int link, uint64_t k, double u)
+{
+    int lo = 0, hi = cc.n_layers - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (cc.layers[mid].start <= k) lo = mid; else hi = mid - 1;
+    }
+    const CodecLayer *L = cc.layers + lo;
+    const bool f64 = L->x_is_f64 != 0;
+    return cohort_quantize_raw(cohort_load(cc.src[static_cast<size_t>(link) * cc.n_layers + lo], f64, k - L->start), f64, L->p0, L->p1, L->p2, u);
+}
+
 // _static_unquantize_padding_asymmetric (jzf_quantize.py:102-107); k = the element's index in the launch (selects the layer)
 __device__ __forceinline__ double codec_unquantize(const Codec &c, uint64_t k, u128 v)
 {

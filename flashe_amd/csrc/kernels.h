@@ -81,6 +81,20 @@ hipError_t launch_prf_batch(const LaunchEnv &env, uint32_t iter, bool dbl, int n
 hipError_t launch_prf_batch_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const uint64_t *const *in_dev,
                                 int in_limbs, uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs, uint64_t first,
                                 uint64_t count, uint64_t *dmask_dev = nullptr);
+// The quantising front end of a COHORT launch (prf_chain_cohort_kernel): every output of one summed double-mask chain is a client's
+// own float model, all clients sharing one layer table.  layers: device table of the non-empty layers, ascending start, x unused
+// (p0, p1, p2 = alpha, scale, den: codec_layer_front); src: device table, src[c * n_layers + l] = client c's values of table row l
+// (float32, or float64 where the row says x_is_f64), read in place.
+struct CohortCodec {
+    const CodecLayer *layers;
+    const void *const *src;
+    int n_layers, pad_;
+};
+// launch_prf_batch_sum over whole n-element vectors with that front end: client c's plaintext k is the stochastic-rounded quantisation
+// of its float k with the draw u_dev[c * n + k] (codec_quantize's arithmetic), no integer plaintext exists in HBM.  The same admission
+// rule and the same hipErrorNotSupported -- nothing launched -- contract; dmask_dev is optional.
+hipError_t launch_prf_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
+                                 uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs, uint64_t *dmask_dev = nullptr);
 // launch_prf_batch on elements [first, first + count) of the n-element vectors (pointers address element `first`): what a GPU that owns
 // an element slice of every client's vector runs
 hipError_t launch_prf_batch_range(const LaunchEnv &env, uint32_t iter, bool dbl, int n_vec, const uint32_t *idx, const uint64_t *const *in_dev,

@@ -320,6 +320,12 @@ __device__ __forceinline__ void loads_landed(const uint64_t &a, const uint64_t &
     asm volatile("" ::"v"(a), "v"(b));
 }
 
+// the same for the cohort front end's raw floats and draws
+__device__ __forceinline__ void cohort_loads_landed(const uint64_t &a, const uint64_t &b, const double &u, const double &v)
+{
+    asm volatile("" ::"v"(a), "v"(b), "v"(u), "v"(v));
+}
+
 template <class T> __device__ __forceinline__ void swap_regs(T &a, T &b) { const T t = a; a = b; b = t; }
 
 // a 96-bit running sum of 64-bit values (lo, carries): at most 2^32 terms
@@ -349,8 +355,9 @@ __global__ __launch_bounds__(THREADS) void prf_chain_kernel(const RoundKeys rk, 
                                                               uint32_t iter0, uint64_t mask_lo, uint64_t mask_hi,
                                                               const uint32_t *__restrict__ te0, const Codec cq)
 {
-    constexpr bool DMASK = false, D128 = false;
+    constexpr bool DMASK = false, D128 = false, COHORT = false;
     uint64_t *const dmask = nullptr;
+    const CohortCodec cc{};
 #include "prf_chain_body.inc"
 }
 
@@ -360,8 +367,9 @@ __global__ __launch_bounds__(THREADS) void prf_chain_dmask_kernel(const RoundKey
                                                                     uint32_t iter0, uint64_t mask_lo, uint64_t mask_hi,
                                                                     const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask)
 {
-    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false;
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = false;
     const Codec cq{};
+    const CohortCodec cc{};
 #include "prf_chain_body.inc"
 }
 
@@ -373,7 +381,26 @@ __global__ __launch_bounds__(THREADS) void prf_dmask_sum128_kernel(const RoundKe
                                                                      uint32_t iter0, uint64_t mask_lo, uint64_t mask_hi,
                                                                      const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask)
 {
-    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = true;
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = true, COHORT = false;
+    const Codec cq{};
+    const CohortCodec cc{};
+#include "prf_chain_body.inc"
+}
+
+// COHORT: the summed decrypt-mask chain of a cohort of co-located clients, every output with a quantising front end -- output c of
+// element k is client c's stochastically rounded quantisation of its own float (codec_quantize's arithmetic on cc's tables), so that one
+// launch takes C float models to their C ciphertexts, the cohort's partial aggregate and its decrypt mask, and no integer plaintext
+// exists in HBM.  All links work on the same elements and share one layer table: a pair's row is looked up once per tile with scalar
+// loads, its alpha / scale / den stay in SGPRs, and per link only the client's layer pointer (scalar) and its float and draw (12 or
+// 16 bytes per element, requested before the AES rounds, consumed after them) are read.  tb.in[link] carries the client's draws;
+// dmask may be null.  A separate kernel: the headline kernels keep their code objects.
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void prf_chain_cohort_kernel(const RoundKeys rk, const ChainTable tb, int n_chains, int all_half_arg,
+                                                                     uint32_t iter0, uint64_t mask_lo, uint64_t mask_hi,
+                                                                     const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask,
+                                                                     const CohortCodec cc)
+{
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true;
     const Codec cq{};
 #include "prf_chain_body.inc"
 }
@@ -1886,6 +1913,39 @@ hipError_t launch_prf_batch_sum(const LaunchEnv &env, uint32_t iter, int n_vec, 
     ch.sum_out_dev = sum_out_dev;
     ch.dmask_dev = dmask_dev;
     return launch_prf_chains(env, iter, 1, &ch, n, n_jobs);
+}
+
+// the shape launch_prf_batch_sum admits (one uncut summed double-mask chain of whole vectors), with the quantising front end per output
+hipError_t launch_prf_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
+                                 uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs, uint64_t *dmask_dev)
+{
+    (void)n_jobs;                            // (int_bits > 64: counters do not depend on the chunking)
+    if (n == 0 || n_vec <= 0) return hipErrorNotSupported;
+    if (!env.use_chain || env.b <= 64 || env.codec || n_vec > kMaxLinks || !sum_out_dev || cc.n_layers < 1) return hipErrorNotSupported;
+    if (env.prf_backend != PRF_AUTO && env.prf_backend != PRF_TABLE) return hipErrorNotSupported;
+    for (int v = 1; v < n_vec; v++) if (idx[v] != idx[v - 1] + 1u) return hipErrorNotSupported;
+    if (idx[n_vec - 1] == 0xffffffffu) return hipErrorNotSupported;
+    const uint64_t waves = static_cast<uint64_t>(env.num_cus) * (kPrfThreads / 64), tiles = (n + 255) / 256;
+    if (tiles < 2 * waves) return hipErrorNotSupported;                 // (launch_prf_batch_sum's rule: two whole tiles per wave, uncut)
+    if ((n - 1) >> 32) return hipErrorNotSupported;                      // one counter window
+    for (int v = 0; v < n_vec; v++) if (!out_dev[v]) return hipErrorNotSupported;
+    ChainTable tb{};
+    tb.first[0] = 0; tb.count[0] = n;
+    tb.len[0] = static_cast<uint8_t>(n_vec);
+    tb.sum_out[0] = sum_out_dev;
+    for (int s = 0; s < n_vec; s++) tb.idx[s] = idx[s];
+    tb.idx[n_vec] = idx[n_vec - 1] + 1u;
+    for (int l = 0; l < n_vec; l++) {
+        tb.in[l] = reinterpret_cast<const uint64_t *>(u_dev + static_cast<uint64_t>(l) * n);       // the link's draws (CohortCodec)
+        tb.out[l] = out_dev[l];
+    }
+    tb.wend[0] = tiles * static_cast<uint64_t>(n_vec + 1);
+    uint64_t lo, hi;
+    masks_of(env.b, &lo, &hi);
+    const int grid = static_cast<int>(std::min<uint64_t>(tiles, static_cast<uint64_t>(env.num_cus)));
+    hipLaunchKernelGGL((prf_chain_cohort_kernel<kPrfThreads>), dim3(grid), dim3(kPrfThreads), 0, env.stream, env.rk, tb, 1, 0, iter, lo, hi,
+                       env.te0_dev, dmask_dev, cc);
+    return hipGetLastError();
 }
 
 // b <= 64 form of launch_prf_jobs

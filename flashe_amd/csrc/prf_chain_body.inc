@@ -1,12 +1,15 @@
-// The body of prf_chain_kernel<THREADS, SUM, CODEC>, prf_chain_dmask_kernel<THREADS> and prf_dmask_sum128_kernel<THREADS> (kernels.hip),
-// included INSIDE each kernel: the kernel defines THREADS, SUM, CODEC, DMASK and D128 as compile-time constants and has the arguments
-// rk, tb, n_chains, all_half_arg, iter0, mask_lo, mask_hi, te0, cq and dmask in scope.  D128: the launch is one summed double-mask
+// The body of prf_chain_kernel<THREADS, SUM, CODEC>, prf_chain_dmask_kernel<THREADS>, prf_dmask_sum128_kernel<THREADS> and
+// prf_chain_cohort_kernel<THREADS> (kernels.hip), included INSIDE each kernel: the kernel defines THREADS, SUM, CODEC, DMASK, D128 and COHORT
+// as compile-time constants and has the arguments rk, tb, n_chains, all_half_arg, iter0, mask_lo, mask_hi, te0, cq, cc and dmask in scope.
+// COHORT: one summed double-mask chain whose every output has a quantising front end (CohortCodec cc; tb.in[link] = that client's draws).  D128: the launch is one summed double-mask
 // chain at int_bits = 128 with one-limb inputs (launch_prf_chains), and its whole tiles run prf_chain_sum128_tile.inc.  (A __device__ function shared by both would do, but its blockDim is lowered before it
 // is inlined -- the non-uniform-workgroup form -- and the headline kernel's code would change with it; included text compiles to
 // exactly the kernel it was before.)
     static_assert(!DMASK || (SUM && !CODEC), "the decrypt mask is written by summed chains only");
     static_assert(!D128 || DMASK, "the int_bits = 128 specialisation is the decrypt-mask chain's");
+    static_assert(!COHORT || (DMASK && !D128), "the cohort front end rides on the summed decrypt-mask chain");
     (void)dmask;
+    (void)cc;
     const uint32_t iter = iter0 + te0[kIterShiftWord];
     constexpr uint32_t WAVES = THREADS / 64;
     __shared__ uint32_t tab[kTabWords];
@@ -101,6 +104,20 @@
             u128 qA0 = 0, qA1 = 0, qB0 = 0, qB1 = 0;                   // SUM: running sum of the outputs of the lane's four elements
             u128 dA0 = 0, dA1 = 0, dB0 = 0, dB1 = 0;                   // DMASK: the first stream's blocks of the lane's four elements
             uint64_t *const sum_out = SUM ? tb.sum_out[cur] : nullptr;
+            // COHORT: the table row of each pair's first element, found once per tile (every link works on the same elements); -1 = the
+            // pair straddles a layer boundary (at most one pair per layer of the model) and its lanes look their rows up themselves
+            int layA = -1, layB = -1;
+            if constexpr (COHORT) {
+                for (int p = 0; p < 2; p++) {
+                    const uint64_t jb = tj + 128u * p, kb = (jb > first ? jb : first) - first, ke = (jb + 128u < end ? jb + 128u : end) - first;
+                    int l = -1;
+                    if (jb < end && jb + 128u > first) {
+                        l = cohort_layer_of(cc, kb);
+                        if (l + 1 < cc.n_layers && *FLASHE_CONSTANT(const uint64_t, &cc.layers[l + 1].start) < ke) l = -1;
+                    }
+                    if (p == 0) layA = l; else layB = l;
+                }
+            }
             for (int c = 0; c < n_streams; c++) {
                 const CtrPrefix pre = load_prefix(pre_lds, sbase + c);
                 const CtrUniform U = ctr_uniform(rk, te0, pre, x3);
@@ -117,8 +134,33 @@
                         // every load is consumed on every path (the adds below are unconditional, only the stores are
                         // predicated): otherwise the compiler must assume a load may still be in flight at the loop's back
                         // edge and drains the memory queue -- stores included -- every iteration
+                        // COHORT: the float's bits and the draw are requested here and quantised after the rounds with the row's
+                        // parameters in SGPRs (crow < 0: already the plaintext)
+                        uint64_t raw0 = 0, raw1 = 0;
+                        double u0 = 0, u1 = 0, cp0 = 0, cp1 = 0, cp2 = 0;
+                        bool cf64 = false;
+                        const int crow = COHORT && link >= 0 ? layA : -1;
                         u128 x0 = 0, x1 = 0;
-                        if (CODEC && cq.x != nullptr && link >= 0) {
+                        if constexpr (COHORT) {
+                            if (link >= 0) {
+                                const double *const ud = reinterpret_cast<const double *>(in);
+                                if (a0) u0 = *FLASHE_GLOBAL(const double, ud + k0);
+                                if (a1) u1 = *FLASHE_GLOBAL(const double, ud + k1);
+                                if (crow >= 0) {
+                                    const CodecLayer *const L = cc.layers + crow;
+                                    const uint64_t ls = *FLASHE_CONSTANT(const uint64_t, &L->start);
+                                    const void *const xs = reinterpret_cast<const void *>(*FLASHE_CONSTANT(const uintptr_t, cc.src + static_cast<size_t>(link0 + link) * cc.n_layers + crow));
+                                    cf64 = *FLASHE_CONSTANT(const int, &L->x_is_f64) != 0;
+                                    cp0 = *FLASHE_CONSTANT(const double, &L->p0); cp1 = *FLASHE_CONSTANT(const double, &L->p1);
+                                    cp2 = *FLASHE_CONSTANT(const double, &L->p2);
+                                    if (a0) raw0 = cohort_load(xs, cf64, k0 - ls);
+                                    if (a1) raw1 = cohort_load(xs, cf64, k1 - ls);
+                                } else {
+                                    if (a0) raw0 = cohort_quantize_lane(cc, link0 + link, k0, u0);
+                                    if (a1) raw1 = cohort_quantize_lane(cc, link0 + link, k1, u1);
+                                }
+                            }
+                        } else if (CODEC && cq.x != nullptr && link >= 0) {
                             if (a0) x0 = codec_quantize(cq, k0);
                             if (a1) x1 = codec_quantize(cq, k1);
                         } else if (in != nullptr && in2) {
@@ -132,6 +174,11 @@
                         ctr_round2(lr, pre.u[0], vA0, U, s[0]);
                         ctr_round2(lr, pre.u[0], vA1, U, s[1]);
                         aes256_rounds<2, 3>(rk, lr, s, true);
+                        if constexpr (COHORT) {
+                            cohort_loads_landed(raw0, raw1, u0, u1);
+                            x0 = crow >= 0 ? cohort_quantize_raw(raw0, cf64, cp0, cp1, cp2, u0) : raw0;
+                            x1 = crow >= 0 ? cohort_quantize_raw(raw1, cf64, cp0, cp1, cp2, u1) : raw1;
+                        }
                         loads_landed(x0, x1);
                         const u128 c0 = words_to_u128(s[0]), c1 = words_to_u128(s[1]);
                         const u128 r0 = x0 + (single ? c0 : pA0 - c0), r1 = x1 + (single ? c1 : pA1 - c1);
@@ -163,7 +210,7 @@
                             if (c == 0) {
                                 if (p == 0) { dA0 = c0; dA1 = c1; } else { dB0 = c0; dB1 = c1; }
                             }
-                            if (last_stream) {
+                            if (last_stream && (!COHORT || dmask != nullptr)) {
                                 if (p == 0) {
                                     if (a0) st128_nt(dmask + 2 * k0, (c0 - dA0) & mask);
                                     if (a1) st128_nt(dmask + 2 * k1, (c1 - dA1) & mask);
@@ -176,6 +223,7 @@
                         pA0 = c0; pA1 = c1;
                     }
                     swap_regs(pA0, pB0); swap_regs(pA1, pB1); swap_regs(vA0, vB0); swap_regs(vA1, vB1);
+                    if constexpr (COHORT) swap_regs(layA, layB);
                 }
             }
         } else if (quarter) {
@@ -222,6 +270,12 @@
             const bool a0 = j0 >= first && j0 < end, a1 = j1 >= first && j1 < end;
             const CtrVar xv0 = ctr_var(rk, lr, static_cast<uint32_t>(j0)), xv1 = ctr_var(rk, lr, static_cast<uint32_t>(j1));
             const uint32_t x3h = static_cast<uint32_t>(tj) ^ rk.w[3];        // (a half tile is 128 aligned counters: bytes 1 .. 3 are the wave's)
+            int lay = -1;                                               // COHORT: the pair's table row, as in a whole tile
+            if constexpr (COHORT) {
+                const uint64_t kb = (tj > first ? tj : first) - first, ke = (tj + 128u < end ? tj + 128u : end) - first;
+                lay = cohort_layer_of(cc, kb);
+                if (lay + 1 < cc.n_layers && *FLASHE_CONSTANT(const uint64_t, &cc.layers[lay + 1].start) < ke) lay = -1;
+            }
             u128 p0 = 0, p1 = 0, q0 = 0, q1 = 0;
             uint64_t *const sum_out = SUM ? tb.sum_out[cur] : nullptr;
             u128 d0 = 0, d1 = 0;                                        // DMASK: the first stream's blocks of the lane's two elements
@@ -231,7 +285,25 @@
                 const uint64_t *in = link >= 0 ? tb.in[link0 + link] : nullptr;
                 uint64_t *out = link >= 0 ? tb.out[link0 + link] : nullptr;
                 u128 x0 = 0, x1 = 0;
-                if (CODEC && cq.x != nullptr && link >= 0) {
+                if constexpr (COHORT) {
+                    // (a launch's few half tiles: quantised before the rounds)
+                    if (link >= 0) {
+                        const double *const ud = reinterpret_cast<const double *>(in);
+                        if (lay >= 0) {
+                            const CodecLayer *const L = cc.layers + lay;
+                            const uint64_t ls = *FLASHE_CONSTANT(const uint64_t, &L->start);
+                            const void *const xs = reinterpret_cast<const void *>(*FLASHE_CONSTANT(const uintptr_t, cc.src + static_cast<size_t>(link0 + link) * cc.n_layers + lay));
+                            const bool f64 = *FLASHE_CONSTANT(const int, &L->x_is_f64) != 0;
+                            const double q0 = *FLASHE_CONSTANT(const double, &L->p0), q1 = *FLASHE_CONSTANT(const double, &L->p1),
+                                         q2 = *FLASHE_CONSTANT(const double, &L->p2);
+                            if (a0) x0 = cohort_quantize_raw(cohort_load(xs, f64, k0 - ls), f64, q0, q1, q2, *FLASHE_GLOBAL(const double, ud + k0));
+                            if (a1) x1 = cohort_quantize_raw(cohort_load(xs, f64, k1 - ls), f64, q0, q1, q2, *FLASHE_GLOBAL(const double, ud + k1));
+                        } else {
+                            if (a0) x0 = cohort_quantize_lane(cc, link0 + link, k0, *FLASHE_GLOBAL(const double, ud + k0));
+                            if (a1) x1 = cohort_quantize_lane(cc, link0 + link, k1, *FLASHE_GLOBAL(const double, ud + k1));
+                        }
+                    }
+                } else if (CODEC && cq.x != nullptr && link >= 0) {
                     if (a0) x0 = codec_quantize(cq, k0);
                     if (a1) x1 = codec_quantize(cq, k1);
                 } else if (in != nullptr && in2) {
@@ -267,7 +339,7 @@
                 }
                 if constexpr (DMASK) {
                     if (c == 0) { d0 = c0; d1 = c1; }
-                    if (c == n_streams - 1) {
+                    if (c == n_streams - 1 && (!COHORT || dmask != nullptr)) {
                         if (a0) st128_nt(dmask + 2 * k0, (c0 - d0) & mask);
                         if (a1) st128_nt(dmask + 2 * k1, (c1 - d1) & mask);
                     }

@@ -609,6 +609,31 @@ class Engine:
         self._check(self._lib.flashe_quantize_encrypt_tensors_dev(self._h, it, idx, scheme, n, n_jobs, first, count, arr, nl, element_bits,
                                                                   self._ptr(u), self._ptr(ct)))
 
+    def quantize_encrypt_cohort_dev(self, it, first_idx, n, n_jobs, layers, srcs, dtypes, element_bits, u, cts, sum_out, dmask=None):
+        """A cohort's client steps as ONE chained launch (flashe_quantize_encrypt_cohort_dev): layers = the shared table, (start, None,
+        alpha, shift, compute dtype code, flags) per layer; srcs[c][l] / dtypes[c][l] = device pointer and storage dtype code of client
+        c's layer l; u = the len(srcs) * n draws, client-major; cts = one n-element vector per client; sum_out / dmask (optional) = their
+        sum and the cohort's decrypt mask.  Returns False -- nothing was launched -- when the library declines the shape (FLASHE_ENOTSUP:
+        the caller quantises per client and calls encrypt_batch_sum_dev), True otherwise."""
+        arr, nl = self._tensor_layers(layers)
+        C = len(srcs)
+        ps = (c_vp * max(C * nl, 1))(*[int(p) if p else None for row in srcs for p in row])
+        pd = (ctypes.c_int32 * max(C * nl, 1))(*[int(d) for row in dtypes for d in row])
+        pc, _k = self._ptr_array(cts)
+        rc = self._lib.flashe_quantize_encrypt_cohort_dev(self._h, it, int(first_idx), C, int(n), n_jobs, arr, nl, ps, pd, element_bits,
+                                                          self._ptr(u), pc, self._ptr(sum_out), self._ptr(dmask))
+        if rc == _lib.ENOTSUP:
+            return False
+        self._check(rc)
+        return True
+
+    def combine_unquantize_model_dev(self, n, inp, add, minus, layers, element_bits, num_clients, out):
+        """out = unquantise((inp + add - minus) mod 2^b) as float64 over a flattened model, one memory-bound pass (add / minus: device
+        vectors or None); layers as for decrypt_unquantize_model_dev."""
+        arr, nl = self._codec_layers(layers)
+        self._check(self._lib.flashe_combine_unquantize_model_dev(self._h, int(n), self._ptr(inp), self._ptr(add), self._ptr(minus), arr, nl,
+                                                                  element_bits, num_clients, self._ptr(out)))
+
     def quantize_batch_tensors_dev(self, layers, n_values, element_bits, field_bits, u, n_elems, out):
         arr, nl = self._tensor_layers(layers)
         self._check(self._lib.flashe_quantize_batch_tensors_dev(self._h, arr, nl, int(n_values), element_bits, field_bits, self._ptr(u), int(n_elems),

@@ -37,6 +37,7 @@ extern "C" {
 #define FLASHE_ENOMEM  (-12)
 #define FLASHE_ENODEV  (-19)   /* no usable HIP device */
 #define FLASHE_EINVAL  (-22)
+#define FLASHE_ENOTSUP (-95)   /* the call's shape is outside what this entry point launches; nothing was launched, use the general calls */
 
 #define FLASHE_SCHEME_SINGLE 0 /* FlasheCipher(int_bits, mask="single") */
 #define FLASHE_SCHEME_DOUBLE 1 /* FlasheCipher(int_bits)  (default "double") */
@@ -68,7 +69,9 @@ typedef struct flashe_ctx flashe_ctx;
  *      flashe_quantize_batch_tensors_dev / flashe_store_layers_dev (caller-owned tensors either side of the model-wide codec);
  *      flashe_quantize_encrypt_prepared_{model,tensors}_dev, flashe_quantize_batch_encrypt_prepared_{model,tensors}_dev,
  *      flashe_decrypt_prepared_unquantize_model_dev, flashe_decrypt_prepared_unbatch_unquantize_model_dev (the model-wide codec with the
- *      ctx's precomputed masks) */
+ *      ctx's precomputed masks); FLASHE_ENOTSUP + flashe_quantize_encrypt_cohort_dev (a cohort of co-located clients: C float models
+ *      to C ciphertexts, their sum and the decrypt mask in one chained launch) and flashe_combine_unquantize_model_dev (the codec back
+ *      end over a sum and caller-held masks) */
 #define FLASHE_ABI_VERSION 4
 int flashe_abi_version(void);
 int flashe_device_count(int *count);
@@ -644,6 +647,29 @@ typedef struct flashe_tensor_layer {
 int flashe_quantize_encrypt_tensors_dev(flashe_ctx *ctx, uint32_t iter, uint32_t idx, int scheme, uint64_t n, uint32_t n_jobs,
                                         uint64_t first, uint64_t count, const flashe_tensor_layer *layers, int n_layers,
                                         int element_bits, const double *u_dev, uint64_t *ct_dev);
+/* A COHORT of n_clients consecutive clients (cipher indices first_idx .. first_idx + n_clients - 1, double mask) hosted on this GPU (new):
+ * ONE chained launch quantises every client's float model (jzf_quantize.py:55-67, client c's element k with the draw
+ * u_dev[c * n + k]), encrypts with the PRF streams the consecutive clients share (n_clients + 1 streams instead of 2 n_clients,
+ * jzf_flashe.py:349-353), and writes ct_dev[c] (n x L limbs each, bit for bit flashe_quantize_encrypt_tensors_dev of that client),
+ * sum_out_dev = sum_c ct_dev[c] mod 2^b (jzf_aggregator.py:424-430) and, when dmask_dev is not NULL, the cohort's decrypt mask
+ * term(first_idx + n_clients) - term(first_idx) mod 2^b (what a decrypt of the sum adds when the cohort is the whole federation; feed it
+ * to flashe_combine_unquantize_model_dev).  No integer plaintext exists in HBM.  `layers` is ONE table shared by all clients (HOST
+ * array, rows as above; ptr is ignored, dtype names the row's COMPUTE type F32 / F64, LOOP_F64 makes an F32 row compute in float64,
+ * SHIFT / SHIFT_WIDE / shift normalise every client's layer alike); src_dev[c * n_layers + l] is client c's layer l and
+ * src_dtype[c * n_layers + l] its storage dtype (NULL: the row's dtype).  A source already in the row's compute type without SHIFT is
+ * read in place; the others take one stage pass into ctx scratch first (as flashe_quantize_encrypt_tensors_dev), all clients at once.
+ * A float64 source under a float32 row is FLASHE_EINVAL.
+ * Returns FLASHE_ENOTSUP -- nothing launched -- for every shape outside the chained launch: int_bits <= 64, more than 128 clients, fewer
+ * than two 256-element tiles per wave of the chip (2 x 16 x flashe_ctx_cu_count tiles), n > 2^32, FLASHE_CHAIN=0, another PRF backend;
+ * the caller then quantises per client and uses flashe_encrypt_batch_sum_dev.  The table uploads synchronise; not capturable. */
+int flashe_quantize_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                       const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                       int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev, uint64_t *dmask_dev);
+/* The codec back end over caller-held vectors (new), jzf_quantize.py:102-107: out[k] = unquantize((in[k] + add[k] - minus[k]) mod 2^b)
+ * as float64 for the n elements of a flattened model, one memory-bound pass; add_dev / minus_dev may be NULL (zeros).  With in = a
+ * cohort's sum and add = its decrypt mask this is the cohort's decrypt_unquantize. */
+int flashe_combine_unquantize_model_dev(flashe_ctx *ctx, uint64_t n, const uint64_t *in_dev, const uint64_t *add_dev, const uint64_t *minus_dev,
+                                        const flashe_codec_layer *layers, int n_layers, int element_bits, int num_clients, double *out_dev);
 /* The batched job's front end, jzf_quantize.py:55-67, 162-185 (new): flashe_quantize_batch_model_dev with tensor layers; the layer
  * sizes are the differences of consecutive starts, the last one ends at n_values. */
 int flashe_quantize_batch_tensors_dev(flashe_ctx *ctx, const flashe_tensor_layer *layers, int n_layers, uint64_t n_values, int element_bits,
