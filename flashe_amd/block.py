@@ -13,7 +13,8 @@ from .quantize import QuantizingClient
 
 _RNG_RUN_MAX = 1 << 26          # draws per device call of quantize_encrypt (512 MiB of float64)
 
-__all__ = ["dynamic_masking_choice", "FlasheClient", "FlasheCohort", "CohortPlan", "CohortUpload", "plan_cohort"]
+__all__ = ["dynamic_masking_choice", "FlasheClient", "FlasheCohort", "CohortPlan", "CohortUpload", "plan_cohort", "FlasheSparseCohort",
+           "SparseCohortPlan", "SparseCohortEncoding", "SparseCohortUpload", "plan_sparse_cohort"]
 
 
 def dynamic_masking_choice(masks, total, engine=None):
@@ -1217,3 +1218,623 @@ class FlasheCohort(object):
             aggregate = _Layers({next(iter(ld.shape_dict), "w"): aggregate})
         ld.set_idx_list(list(uploaded))
         return ld.decrypt_unquantize(aggregate, out=out, unnormalize=unnormalize)
+
+
+# ---- a cohort of sparse-job clients hosted on one GPU (new) ----------------------------------------------------------------------
+SPARSE_COHORT = "sparse-cohort"
+
+
+class SparseCohortPlan(object):
+    """What plan_sparse_cohort returns: names / shapes / sizes / starts of the shared DENSE layer table, total (values of one model) and
+    bits = total.bit_length(); ks (entries Client.sparsify keeps of every layer: max(1, floor(sparsity * size)), a function of the shape
+    only), K = sum(ks), compact_starts (layer l's first compact value), n_elems = K + 1 (elements of one upload), draw_offsets (client
+    c's first draw in the client-major draws: c (K + 1), the last of its K + 1 draws is its 'zzz' draw), f64 (does layer l compute in
+    float64?), path and the reason for it."""
+
+    def __init__(self, names, shapes, sizes, starts, total, ks, compact_starts, draw_offsets, f64, path, reason):
+        self.names, self.shapes, self.sizes, self.starts, self.total, self.bits = names, shapes, sizes, starts, total, int(total).bit_length()
+        self.ks, self.K, self.compact_starts, self.n_elems = ks, sum(ks), compact_starts, sum(ks) + 1
+        self.draw_offsets, self.f64, self.path, self.reason = draw_offsets, f64, path, reason
+
+
+class SparseCohortEncoding(object):
+    """FlasheSparseCohort.sparsify's result: encoded (per client what Sparsifier.sparsify returns: (packed locations, K, bits, total)),
+    locations (per client (DeviceBuffer of K uint32 model-wide locations, K): what dynamic_masking_choice takes) and compact (per client
+    {layer name: CompactLayer}: the kept values where they lie in HBM)."""
+
+    def __init__(self, encoded, locations, compact):
+        self.encoded, self.locations, self.compact = encoded, locations, compact
+
+
+class SparseCohortUpload(object):
+    """FlasheSparseCohort.quantize_encrypt's result: uploads (one DeviceVector of K + 1 elements per client: the K ciphertexts and the
+    un-encrypted quantised zero), aggregate (aggregate_sparse_uploads of them: `total` elements) and path."""
+
+    def __init__(self, uploads, aggregate, path):
+        self.uploads, self.aggregate, self.path = uploads, aggregate, path
+
+
+def _client_layers(w, walking_order=None):
+    """(names in walking order, {name: layer}) of a Weights-like object or a plain dict."""
+    if hasattr(w, "_weights"):
+        return list(walking_order if walking_order is not None else w.walking_order), w._weights
+    return list(walking_order) if walking_order is not None else sorted(w.keys(), key=str), w
+
+
+def plan_sparse_cohort(weights_list, sparsity, int_bits, element_bits=16, batch=False, choice="single", precompute=False, fuse=True,
+                       walking_order=None):
+    """The engine-free part of FlasheSparseCohort: checks that the clients' dense models describe ONE model (the same layer names in the
+    same walking order with the same shapes: ValueError naming the client and the layer, as plan_cohort; an empty layer: Sparsifier's
+    ValueError), lays out the shared layer table, the compact layers and the client-major draws, and picks the path:
+      "sparse-cohort"  one set of sparsifier launches, one quantise launch, the fused encrypt + aggregate: choice "single" (what the
+                       arbiter's cost rule answers for every sparsifier-fed round), not batched, no precompute cache, fuse, every layer in
+                       the same compute class (float64, or float32 / float16 / bfloat16) for all clients.  There is NO minimum size;
+      "per-client"     everything else (choice "double" set by hand, batched jobs, precompute, fuse off, a layer that is float64 for some
+                       clients only): the clients' own FlasheClient steps on the shared quantiser state, then aggregate_sparse_uploads.
+    Touches no device."""
+    if len(weights_list) < 1:
+        raise ValueError("a cohort needs at least one client's model")
+    C = len(weights_list)
+    names, shapes, f64, mixed = None, [], [], False
+    for c, w in enumerate(weights_list):
+        order, layers = _client_layers(w, walking_order)
+        if names is None:
+            names = order
+            shapes = [_layer_shape(layers[k]) for k in order]
+            f64 = [_layer_is_f64(layers[k]) for k in order]
+            continue
+        if order != names:
+            odd = next((k for k in order if k not in names), None) or next((k for k in names if k not in order), None)
+            if odd is None:
+                odd = next(a for a, b in zip(order, names) if a != b)
+                raise ValueError(f"client {c}: layer {odd!r} comes at another place of the walking order than in client 0's")
+            raise ValueError(f"client {c}: layer {odd!r} is not a layer of every client of the cohort")
+        for li, k in enumerate(order):
+            shp = _layer_shape(layers[k])
+            if shp != shapes[li]:
+                raise ValueError(f"client {c}: layer {k!r} has shape {shp}, client 0's has {shapes[li]}")
+            mixed |= _layer_is_f64(layers[k]) != f64[li]
+    sizes = [int(np.prod(shp, dtype=np.int64)) for shp in shapes]
+    for k, size in zip(names, sizes):
+        if size == 0:
+            raise ValueError(f"layer {k!r} is empty: the sparsifier keeps max(1, floor(sparsity * size)) values of every layer")
+    ks = [max(1, int(np.floor(sparsity * size))) for size in sizes]
+    starts, total = [], 0
+    for s_ in sizes:
+        starts.append(total)
+        total += s_
+    cstarts, K = [], 0
+    for k_l in ks:
+        cstarts.append(K)
+        K += k_l
+    path, reason = _sparse_path(choice, batch, precompute, fuse, mixed)
+    return SparseCohortPlan(names, shapes, sizes, starts, total, ks, cstarts, [c * (K + 1) for c in range(C)], f64, path, reason)
+
+
+def _sparse_path(choice, batch, precompute, fuse, mixed):
+    if choice != "single":
+        return PER_CLIENT, f"masking choice {choice!r} (set by hand: strictly increasing lists always cost 'single')"
+    if batch:
+        return PER_CLIENT, "batched job"
+    if precompute:
+        return PER_CLIENT, "precomputed masks are held per client"
+    if not fuse:
+        return PER_CLIENT, "fuse is off"
+    if mixed:
+        return PER_CLIENT, "a layer is float64 for some clients only"
+    return SPARSE_COHORT, ""
+
+
+class FlasheSparseCohort(object):
+    """`n_local` consecutive clients of the SPARSE job (ciphers first_idx .. first_idx + n_local - 1 of a federation of num_clients)
+    hosted on ONE GPU: Client.sparsify -> locations to the arbiter -> dynamic_masking -> Client.secure_aggregate's quantise + encrypt ->
+    Arbiter.expand_to_dense + reduce -> Client.aggregate's decrypt + unquantise (jzf_aggregator.py:578-623, 717-743, 881-899;
+    jzf_flashe_block.py:92-117; jzf_quantize.py:433-465), one method per step.  Every result is that of n_local Sparsifiers +
+    FlasheClients run one after the other in one process on ONE shared quantiser state (FlasheCohort's rule), followed by
+    aggregate_sparse_uploads and client first_idx's decrypt_unquantize -- bit for bit -- but the device work of the whole cohort is a
+    number of launches that does not grow with n_local: one set of sparsifier launches over a C x L row table
+    (flashe_sparsify_cohort_tensors_dev), one quantise launch (flashe_quantize_cohort_dev), the fused encrypt + aggregate
+    (flashe_sparse_encrypt_aggregate_dev; at int_bits <= 64 that entry point keeps one encrypt launch per client) with the span bounds of
+    the round's lists computed once, and the sparse decrypt + unquantise + store.  One engine and one stream carry everything, the sparsifier passes included.  `path` of an upload names the form that ran."""
+
+    def __init__(self, args, first_idx, n_local, num_clients, prp_seed, sparsity, device=0, stream=None):
+        if n_local < 1 or first_idx < 0 or first_idx + n_local > num_clients:
+            raise ValueError(f"clients {first_idx} .. {first_idx + n_local - 1} are not clients of a federation of {num_clients}")
+        if args.get("mask", "double") != "dynamic":
+            raise ValueError("FlasheSparseCohort runs the sparse job: args['mask'] must be 'dynamic' (the arbiter's choice reaches the clients)")
+        self.first_idx, self.n_local, self.num_clients, self.sparsity = int(first_idx), int(n_local), int(num_clients), sparsity
+        self.lead = FlasheClient(args, device=device, stream=stream)
+        self.lead.create_cipher(self.first_idx, self.num_clients, prp_seed)
+        self._clients = None
+        if self.lead.precompute:                       # precomputed masks are per cipher: every client its own, one quantiser state
+            self._clients = [self.lead]
+            for c in range(1, self.n_local):
+                cl = FlasheClient(args, device=device, stream=stream)
+                cl.create_cipher(self.first_idx + c, self.num_clients, prp_seed)
+                cl.quantizer = self.lead.quantizer
+                self._clients.append(cl)
+        self.shape_dict_used_for_sparsification = None
+        self.plan = None                # of the last sparsify
+        self._remain = None             # (DeviceBuffer, names, sizes, per-layer compute dtypes, stride in bytes): C residual blocks in HBM
+        self._fallback = None           # per-client Sparsifiers (a layer that is float64 for some clients only)
+        self._compact = None            # per client [(ptr, dtype code, NumPy dtype)] of the compact layers + what keeps them alive
+        self._own_lists = None          # per client (DeviceBuffer of uint32 locations, K) from the last sparsify
+        self._lists = None              # the round's lists of ALL num_clients clients: (DeviceBuffer, k), + are they strictly increasing
+        self._sorted = True
+        self._host_masks = None
+        self._bounds = None             # (SpanBounds of the cohort's own lists, (total, C)): reused over rounds of the same shape
+        self._last = None
+        self._last_bounds = None        # the handle the decrypt of the cohort's own aggregate may take
+
+    quantizer = property(lambda self: self.lead.quantizer)
+    cipher = property(lambda self: self.lead.cipher)
+    shape_dict = property(lambda self: self.lead.shape_dict)
+    alpha_list = property(lambda self: self.lead.quantizer.alpha_list)
+    engine = property(lambda self: self.lead.cipher.engine)
+
+    def set_iter_index(self, iter_index):
+        for cl in (self._clients or [self.lead]):
+            cl.cipher.set_iter_index(iter_index)
+        self.lead.quantizer.set_iter(iter_index)
+        self._last = None
+
+    # ---- Client.sparsify for all clients ---------------------------------------------------------------------------------------
+    def sparsify(self, weights_list, walking_order=None):
+        """One dense model per client (Weights or dict; host arrays and / or framework float device tensors) -> SparseCohortEncoding.
+        Client c's result is its own Sparsifier(sparsity).sparsify(W_c, order): the same (encoded, le, bits, total), compact values and
+        residuals as bytes.  The residuals stay in HBM per client between rounds (remain_weights(c) downloads them) and continue a
+        previous round; the caller's models are neither written nor replaced.  Everything is checked before a residual is touched."""
+        from . import interop
+        from ._lib import TENSOR_BF16, TENSOR_F16, TENSOR_F32, TENSOR_F64
+        from .engine import DeviceBufferView
+        from .weights import CompactLayer, _compact_layout
+        C = self.n_local
+        if len(weights_list) != C:
+            raise ValueError(f"the cohort holds {C} clients, got {len(weights_list)} models")
+        ld = self.lead
+        plan = plan_sparse_cohort(weights_list, self.sparsity, ld.int_bits, element_bits=ld.quantizer.element_bits, walking_order=walking_order)
+        eng = self.engine
+        codes = {"float32": TENSOR_F32, "float64": TENSOR_F64, "float16": TENSOR_F16, "bfloat16": TENSOR_BF16}
+        names, L = plan.names, len(plan.names)
+        rows = []                                     # per client [(ForeignArray or flat host array, dtype code)]
+        for ci, w in enumerate(weights_list):
+            _o, layers = _client_layers(w, walking_order)
+            row = []
+            for k in names:
+                v = layers[k]
+                if interop.is_foreign(v):
+                    fa = eng.foreign(v, what=f"client {ci} layer {k!r}")
+                    if fa.dtype not in codes:
+                        raise TypeError(f"client {ci} layer {k!r}: unsupported dtype {fa.dtype} (float32, float64, float16 or bfloat16)")
+                    row.append((fa, codes[fa.dtype]))
+                else:
+                    flat = np.ascontiguousarray(np.asarray(v)).reshape(-1)
+                    if flat.dtype not in (np.float32, np.float64):
+                        flat = flat.astype(np.float64)
+                    row.append((flat, TENSOR_F64 if flat.dtype == np.float64 else TENSOR_F32))
+            rows.append(row)
+        if self.shape_dict_used_for_sparsification is None:
+            self.shape_dict_used_for_sparsification = dict(zip(names, plan.shapes))
+        self.plan, self._last = plan, None
+        if plan.path == PER_CLIENT:                   # (here: a layer that is float64 for some clients only -- no shared row)
+            return self._sparsify_per_client(weights_list, walking_order, plan)
+        cts = tuple(np.dtype(np.float64 if f else np.float32) for f in plan.f64)
+        roffs, rbytes = _compact_layout(plan.sizes, cts)
+        voffs, vbytes = _compact_layout(plan.ks, cts)
+        rstride, vstride = (rbytes + 15) & ~15, (vbytes + 15) & ~15
+        K, bits = plan.K, plan.bits
+        lstride = (K + 3) & ~3
+        n_limbs = (K * bits + 63) // 64
+        # the residuals: C blocks in the layout of the call; another layout (or the per-client form) continues from the host copies
+        rem = self._remain
+        if rem is None or rem[1] != names or rem[2] != plan.sizes or rem[3] != cts:
+            host = [self.remain_weights(ci) for ci in range(C)] if (rem is not None or self._fallback is not None) else None
+            buf = eng.alloc(max(C * rstride, 16))
+            if host is None or not any(h for h in host):
+                eng.memset_dev(buf, 0, buf.nbytes)
+            else:
+                raw = np.zeros(C * rstride, dtype=np.uint8)
+                for ci, h in enumerate(host):
+                    for k, n, d, o in zip(names, plan.sizes, cts, roffs):
+                        if h and h.get(k) is not None:
+                            raw[ci * rstride + o:ci * rstride + o + n * d.itemsize] = np.ascontiguousarray(h[k], dtype=d).reshape(-1).view(np.uint8)
+                buf.upload(raw)
+            rem = (buf, names, plan.sizes, cts, rstride)
+            self._fallback = None
+        keep, srcs, dts = [], [], []
+        for row in rows:
+            offs, nbytes = {}, 0
+            for li, (x, _code) in enumerate(row):
+                if isinstance(x, np.ndarray):
+                    offs[li] = nbytes
+                    nbytes += (x.nbytes + 15) & ~15
+            xbuf = eng.alloc(max(nbytes, 16)) if offs else None
+            for li, off in offs.items():
+                xbuf.upload_at(off, row[li][0])
+            if xbuf is not None:
+                keep.append(xbuf)
+            srcs.append([xbuf.ptr + offs[li] if isinstance(x, np.ndarray) else x.ptr for li, (x, _code) in enumerate(row)])
+            dts.append([code for _x, code in row])
+            keep += [x.keep for x, _code in row if not isinstance(x, np.ndarray)]
+        loc, vals, packed = eng.alloc(max(4 * C * lstride, 16)), eng.alloc(max(C * vstride, 16)), eng.alloc(max(8 * C * n_limbs, 16))
+        table = [(plan.starts[li], TENSOR_F64 if plan.f64[li] else TENSOR_F32) for li in range(L)]
+        eng.sparsify_cohort_tensors_dev(plan.total, table, plan.ks, srcs, dts, rem[0], rstride, loc, lstride, vals, vstride, packed, n_limbs, bits)
+        eng.hold(keep)
+        self._remain = rem
+        pk = packed.download(np.uint64, C * n_limbs)          # the C packed location integers: the one download of the step
+        encoded = [(int.from_bytes(pk[ci * n_limbs:(ci + 1) * n_limbs].tobytes(), "little"), K, bits, plan.total) for ci in range(C)]
+        self._own_lists = [(DeviceBufferView(loc, 4 * ci * lstride, max(4 * K, 4)), K) for ci in range(C)]
+        compact = [{k: CompactLayer(eng, vals, ci * vstride + o, kl, d) for k, kl, d, o in zip(names, plan.ks, cts, voffs)} for ci in range(C)]
+        self._compact = ([[(cl[k].ptr, TENSOR_F64 if d == np.float64 else TENSOR_F32, d) for k, d in zip(names, cts)] for cl in compact], [vals],
+                         names, [all(isinstance(x, np.ndarray) for x, _c in row) for row in rows], compact)
+        self._lists = None
+        return SparseCohortEncoding(encoded, list(self._own_lists), compact)
+
+    def _sparsify_per_client(self, weights_list, walking_order, plan):
+        """Every client through its own Sparsifier on the cohort's engine; the residuals move there."""
+        from ._lib import TENSOR_F32, TENSOR_F64
+        from .weights import CompactLayer, Sparsifier, from_big_int
+        eng = self.engine
+        if self._fallback is None:
+            self._fallback = []
+            for ci in range(self.n_local):
+                sp = Sparsifier(self.sparsity, device=self.lead._device)
+                sp._engine = lambda eng=eng: eng
+                old = self.remain_weights(ci) if self._remain is not None else None
+                if old:
+                    sp.remain_weights = old
+                self._fallback.append(sp)
+            self._remain = None
+        encoded, lists, compact, srcs, all_host = [], [], [], [], []
+        for ci, (w, sp) in enumerate(zip(weights_list, self._fallback)):
+            _o, layers = _client_layers(w, walking_order)
+            d = {k: layers[k] for k in plan.names}
+            enc = sp.sparsify(d, plan.names)
+            encoded.append(enc)
+            if isinstance(d[plan.names[0]], CompactLayer):
+                lists.append(sp.locations)
+            else:
+                lists.append((eng.upload(np.asarray(from_big_int(enc[0], enc[1], enc[2], as_object=False)).astype(np.uint32)), enc[1]))
+            compact.append(d)
+            all_host.append(not isinstance(d[plan.names[0]], CompactLayer))
+            srcs.append(None)
+        self._own_lists = lists
+        self._compact = (srcs, [], plan.names, all_host, compact)
+        self._lists = None
+        return SparseCohortEncoding(encoded, list(lists), compact)
+
+    def remain_weights(self, c):
+        """Client c's residuals {layer name: array} (what the reference keeps in Client.remain_weights), downloaded."""
+        from .weights import _compact_layout
+        if self._fallback is not None:
+            return self._fallback[c].remain_weights
+        if self._remain is None:
+            return None
+        buf, names, sizes, cts, stride = self._remain
+        offs, nbytes = _compact_layout(sizes, cts)
+        raw = buf.download_at(c * stride, np.uint8, nbytes)
+        return {name: raw[o:o + n * d.itemsize].view(d).copy() for name, n, d, o in zip(names, sizes, cts, offs)}
+
+    # ---- the arbiter's hint ----------------------------------------------------------------------------------------------------
+    def dynamic_masking(self, choice=None, masks=None, total=None):
+        """Without arguments the cohort IS the federation: dynamic_masking_choice over its own device lists (the arbiter's rule,
+        jzf_flashe_block.py:92-112, counted on the device), then what every client's dynamic_masking(choice, masks) and cipher.total =
+        total leave.  Otherwise the arbiter's answer: `masks` = the num_clients location lists of the round (host integers, DeviceBuffers
+        of uint32 or (DeviceBuffer, length) pairs); after a sparsify the cohort's own clients keep the device lists it produced.
+        Returns the choice."""
+        from .engine import DeviceBuffer
+        eng, ld = self.engine, self.lead
+        if total is None:
+            if self.plan is None:
+                raise ValueError("dynamic_masking needs `total` (no sparsify has told the cohort the model's size)")
+            total = self.plan.total
+        total = int(total)
+        if choice is None:
+            if self.n_local != self.num_clients:
+                raise ValueError(f"the cohort holds {self.n_local} of {self.num_clients} clients: dynamic_masking() needs the arbiter's choice and lists")
+            if self._own_lists is None:
+                raise ValueError("dynamic_masking() without arguments needs the lists of this round (sparsify first)")
+            lists, sorted_all = list(self._own_lists), True
+            choice = dynamic_masking_choice(lists, total, eng)
+        else:
+            if masks is None or len(masks) != self.num_clients:
+                raise ValueError(f"masks: one location list per client of the federation ({self.num_clients})")
+            lists, sorted_all = [], True
+            for c, m in enumerate(masks):
+                own = c - self.first_idx
+                if self._own_lists is not None and 0 <= own < self.n_local:
+                    lists.append(self._own_lists[own])
+                elif isinstance(m, tuple):
+                    lists.append((m[0], int(m[1])))
+                elif isinstance(m, DeviceBuffer):
+                    lists.append((m, m.nbytes // 4))
+                else:
+                    la = np.asarray(m, dtype=np.int64).reshape(-1)
+                    if la.size and (int(la.max()) >= total or int(la.min()) < 0):
+                        bad = int(la.max()) if int(la.max()) >= total else int(la.min())
+                        raise IndexError(f"index {bad} is out of bounds for axis 0 with size {total}")
+                    sorted_all = sorted_all and bool(np.all(la[1:] > la[:-1]))
+                    lists.append((eng.upload(la.astype(np.uint32)) if la.size else eng.alloc(16), int(la.size)))
+        for cl in (self._clients or [ld]):
+            cl.cipher.masking_scheme = choice
+            cl.cipher.masks = lists
+            cl.cipher.total = total
+        self._lists, self._sorted, self._host_masks = lists, sorted_all, None
+        return choice
+
+    def _host_lists(self):
+        """The round's lists as host integers (what the per-client form hands to FlasheClient.dynamic_masking)."""
+        if self._host_masks is None:
+            self._host_masks = [buf.download_at(0, np.uint32, k).astype(np.int64) if k else np.zeros(0, dtype=np.int64) for buf, k in self._lists]
+        return self._host_masks
+
+    # ---- Client.secure_aggregate's quantise + encrypt, and the arbiter's expand + reduce --------------------------------------------
+    def quantize_encrypt(self, normalize=False, seeds=None, compact=None):
+        """-> SparseCohortUpload.  Client c's upload is its own FlasheClient.quantize_encrypt(compact_c + 'zzz', device=True,
+        normalize=...) (K + 1 elements of uint64 limbs), `aggregate` is aggregate_sparse_uploads of the cohort's uploads.  compact: C
+        dicts / Weights of compact layers given directly (host arrays, tensors or CompactLayers, with or without the trailing 'zzz'
+        value; a bare list holds the compact layers in walking order) instead of the ones the last sparsify left.  seeds=None: the draws come from NumPy's global stream in client order -- client
+        c takes [c (K + 1), (c + 1)(K + 1)), the last one is its 'zzz' draw -- and the generator is left where the sequential steps leave
+        it; seeds=[s_0 ..]: client c draws after np.random.seed(s_c).  Generated on the device under quantize_encrypt's rule (MT19937,
+        DEVICE_RNG_MIN)."""
+        from . import cipher as _cipher_mod
+        from . import interop
+        from ._lib import TENSOR_BF16, TENSOR_F16, TENSOR_F32, TENSOR_F64, TENSOR_LOOP_F64, TENSOR_SHIFT, TENSOR_SHIFT_WIDE
+        from .engine import DeviceVector
+        from .quantize import ACIQ, DEVICE_RNG_MIN, _loop_dtype
+        ld = self.lead
+        q, c = ld.quantizer, ld.cipher
+        eng, C = c.engine, self.n_local
+        if self._lists is None:
+            raise ValueError("quantize_encrypt needs the round's masking choice and lists (dynamic_masking first)")
+        if seeds is not None and len(seeds) != C:
+            raise ValueError(f"seeds: one per client ({C}), got {len(seeds)}")
+        codes = {"float32": TENSOR_F32, "float64": TENSOR_F64, "float16": TENSOR_F16, "bfloat16": TENSOR_BF16}
+        zzzs = [np.array([0.0])] * C
+        if compact is not None:
+            if len(compact) != C:
+                raise ValueError(f"compact: one set of compact layers per client ({C}), got {len(compact)}")
+            names, given = None, []
+            for ci, w in enumerate(compact):
+                if hasattr(w, "_weights") or isinstance(w, dict):
+                    order, layers = _client_layers(w)
+                else:
+                    layers = {f"l{i:05d}": v for i, v in enumerate(w)}          # (a bare list: the compact layers in walking order)
+                    order = list(layers)
+                layers = dict(layers)
+                if "zzz" in layers:
+                    z = layers.pop("zzz")
+                    if interop.is_foreign(z):
+                        raise TypeError("the sparse job's 'zzz' layer must be a host value")
+                    z = np.asarray(z)
+                    if z.size != 1:
+                        raise ValueError(f"client {ci}: the 'zzz' layer holds {z.size} values, the sparsifier's holds one")
+                    zzzs[ci] = z
+                    order = [k for k in order if k != "zzz"]
+                if names is None:
+                    names = order
+                elif order != names:
+                    raise ValueError(f"client {ci}: the compact layers {order} are not client 0's {names}")
+                given.append(layers)
+            rows, keep, all_host = [], [], []
+            for ci, layers in enumerate(given):
+                row = []
+                for k in names:
+                    v = layers[k]
+                    if interop.is_foreign(v):
+                        fa = eng.foreign(v, what=f"client {ci} compact layer {k!r}")
+                        if fa.dtype not in codes:
+                            raise TypeError(f"client {ci} compact layer {k!r}: unsupported dtype {fa.dtype} (float32, float64, float16 or bfloat16)")
+                        row.append((fa, codes[fa.dtype], np.dtype(np.float64 if fa.dtype == "float64" else np.float32), int(np.prod(fa.shape, dtype=np.int64))))
+                    else:
+                        flat = np.ascontiguousarray(np.asarray(v)).reshape(-1)
+                        if flat.dtype not in (np.float32, np.float64):
+                            flat = flat.astype(np.float64)
+                        row.append((flat, TENSOR_F64 if flat.dtype == np.float64 else TENSOR_F32, flat.dtype, int(flat.size)))
+                if ci and [r[3] for r in row] != [r[3] for r in rows[0]]:
+                    raise ValueError(f"client {ci}: the compact layers have sizes {[r[3] for r in row]}, client 0's {[r[3] for r in rows[0]]}")
+                rows.append(row)
+                all_host.append(all(isinstance(r[0], np.ndarray) for r in row))
+            ks = [r[3] for r in rows[0]]
+            mixed = any(r[2] != r0[2] for row in rows for r, r0 in zip(row, rows[0]))
+            per_client_layers = given
+        else:
+            if self._compact is None:
+                raise ValueError("quantize_encrypt needs compact layers: sparsify first, or pass compact=")
+            srcs0, keep0, names, all_host, per_client_layers = self._compact
+            ks = list(self.plan.ks)
+            mixed = self.plan.path == PER_CLIENT
+            rows = None if mixed else [[(ptr, code, d, kl) for (ptr, code, d), kl in zip(row, ks)] for row in srcs0]
+            keep = list(keep0)
+        K = sum(ks)
+        for ci in range(C):
+            if self._lists[self.first_idx + ci][1] != K:
+                raise ValueError(f"client {ci}: {self._lists[self.first_idx + ci][1]} locations for {K} compact values")
+        zdt = {np.asarray(z).dtype for z in zzzs}
+        path, _reason = _sparse_path(c.masking_scheme, bool(ld.batch), bool(ld.precompute or c.next_iter_encrypt_prepared), bool(ld.fuse),
+                                     mixed or len(zdt) != 1)
+        self._last = None
+        if path == PER_CLIENT:
+            return self._per_client(per_client_layers, names, zzzs, all_host, normalize, seeds)
+        # ---- one quantiser state: set_layer_size_list and the alphas of the round, as FlasheClient._quantize_encrypt_tensors
+        L = len(names)
+        if q.layer_size_list is None:
+            q.layer_size_list = list(ks) + [1]
+            for _ in q.layer_size_list:
+                q.past_layer_mean_list.append(q.expected_mean_for_first_round)
+                q.past_layer_std_list.append(q.expected_std_for_first_round)
+        aciq = ACIQ(q.element_bits)
+        alphas = []
+        for i, _size in enumerate(q.layer_size_list):
+            a = aciq.get_alpha_gaus_direct(q.past_layer_std_list[i])
+            alphas.append(0.1 if a == 0 else a)
+        q.r_max_list = [alphas[li] * q.num_clients for li in range(L)]
+        q.alpha_list = [alphas[li] for li in range(L)]
+        c.set_idx_list(mode="encrypt")
+        # host layers of the compact= form go up once, client by client
+        srcs, dts = [], []
+        for ci, row in enumerate(rows):
+            offs, nbytes = {}, 0
+            for li, r in enumerate(row):
+                if isinstance(r[0], np.ndarray):
+                    offs[li] = nbytes
+                    nbytes += (r[0].nbytes + 15) & ~15
+            xbuf = eng.alloc(max(nbytes, 16)) if offs else None
+            for li, off in offs.items():
+                xbuf.upload_at(off, row[li][0])
+            if xbuf is not None:
+                keep.append(xbuf)
+            ps = []
+            for li, r in enumerate(row):
+                if isinstance(r[0], np.ndarray):
+                    ps.append(xbuf.ptr + offs[li])
+                elif isinstance(r[0], int):
+                    ps.append(r[0])
+                else:
+                    ps.append(r[0].ptr)
+                    keep.append(r[0].keep)
+            srcs.append(ps)
+            dts.append([r[1] for r in row])
+        table, at = [], 0
+        for li in range(L):
+            hdt, alpha = rows[0][li][2], alphas[li]
+            flags, shift = 0, 0.0
+            if hdt != np.float64 and _loop_dtype(hdt, alpha) == np.float64:
+                flags |= TENSOR_LOOP_F64
+            if normalize:                             # QuantizingClient._shift(layer, -mean): the same wide / narrow rule
+                shift = -q.past_layer_mean_list[li]
+                flags |= TENSOR_SHIFT
+                if hdt == np.float32 and _loop_dtype(hdt, shift) == np.float64:
+                    flags |= TENSOR_SHIFT_WIDE
+            table.append((at, None, alpha, float(shift), TENSOR_F64 if hdt == np.float64 else TENSOR_F32, flags))
+            at += ks[li]
+        # the trailing layer as the host path takes it: normalised with its own mean (NumPy's in-place rule), alpha 1.0, not encrypted
+        zvals, z64 = [], True
+        for z in zzzs:
+            a = np.ascontiguousarray(z).reshape(-1)
+            if a.dtype not in (np.float32, np.float64):
+                a = a.astype(np.float64)
+            if normalize:
+                shift = -q.past_layer_mean_list[L] if len(q.past_layer_mean_list) > L else 0.0
+                a = (a.astype(_loop_dtype(a.dtype, shift)) + shift).astype(a.dtype)
+            z64 = _loop_dtype(a.dtype, 1.0) == np.float64
+            zvals.append(float(a[0]))
+        # the draws, client-major with stride K + 1: from the global stream ONE stretch of C (K + 1) draws (the clients draw one after the
+        # other, each its K values and then its 'zzz'), in device calls of at most _RNG_RUN_MAX draws whatever client they belong to
+        dev_rng = os.environ.get("FLASHE_DEVICE_RNG", "1") != "0"
+        du = eng.alloc(max(8 * C * (K + 1), 16))
+        for seed, first, count in ([(None, 0, C * (K + 1))] if seeds is None else [(seeds[ci], ci * (K + 1), K + 1) for ci in range(C)]):
+            if seed is not None:
+                np.random.seed(seed)
+            mt = dev_rng and np.random.get_state()[0] == "MT19937"
+            for a0 in range(first, first + count, _RNG_RUN_MAX):
+                tot = min(_RNG_RUN_MAX, first + count - a0)
+                if mt and tot >= DEVICE_RNG_MIN:
+                    eng.numpy_random_dev(tot, out=du.ptr + 8 * a0)
+                else:
+                    du.upload_at(8 * a0, np.random.random(tot))
+        pstride = (8 * K + 15) & ~15
+        ptbuf = eng.alloc(max(C * pstride, 16))
+        pts = [ptbuf.ptr + ci * pstride for ci in range(C)]
+        ups = [DeviceVector(eng, K + 1) for _ in range(C)]
+        zbuf = eng.alloc(max(8 * C, 16))
+        eng.quantize_cohort_dev(K, table, srcs, dts, q.element_bits, du, K + 1, zvals, z64, pts, [u.ptr + 8 * eng.limbs * K for u in ups], zbuf)
+        zeros = [int(v) for v in zbuf.download(np.uint64, C)]          # the C quantised zeros: the one download of the step
+        own = self._lists[self.first_idx:self.first_idx + C]
+        locs, lks = [b for b, _k in own], [k for _b, k in own]
+        total = int(c.total)
+        agg = DeviceVector(eng, total)
+        bounds = None
+        if self._sorted:
+            # the span bounds of the round's lists, once: the fused encrypt + aggregate takes them and, when the cohort is the federation,
+            # so does the decrypt.  A handle of the same shape is recomputed (the list buffers may have been rewritten in place).
+            if self._bounds is not None and self._bounds[1] == (total, C):
+                bounds = self._bounds[0].recompute(locs, lks)
+            else:
+                bounds = eng.span_bounds(total, locs, lks)
+            self._bounds = (bounds, (total, C))
+            eng.sparse_encrypt_aggregate_dev(c.iter_index, [self.first_idx + ci for ci in range(C)], locs, lks, pts, 1, [[z, 0] for z in zeros], total,
+                                             _cipher_mod.N_JOBS, [u.buf for u in ups], agg.buf, bounds=bounds)
+        else:
+            for ci in range(C):
+                eng.encrypt_dev(c.iter_index, self.first_idx + ci, 0, K, _cipher_mod.N_JOBS, pts[ci], 1, ups[ci].buf)
+            eng.sparse_aggregate_dev(total, locs, lks, [u.buf for u in ups], [[z, 0] for z in zeros], agg.buf, sorted_lists=False)
+        eng.hold(keep + [du, ptbuf, zbuf])
+        ld.shape_dict = {k: (kl,) for k, kl in zip(names, ks)}
+        for u in ups:
+            u.mark_ready()
+        agg.mark_ready()
+        self._last = SparseCohortUpload(ups, agg, SPARSE_COHORT)
+        self._last_bounds = bounds if self.n_local == self.num_clients else None
+        return self._last
+
+    def _per_client(self, per_client_layers, names, zzzs, all_host, normalize, seeds):
+        """The clients' own FlasheClient steps one after the other on the shared quantiser state (one cipher re-indexed per client; with
+        precompute: every client's own cipher), then aggregate_sparse_uploads of what they wrote.  What FlasheClient refuses is refused
+        by the first client's step, before any draw is taken."""
+        from .weights import CompactLayer
+        ld = self.lead
+        eng = self.engine
+        masks = self._host_lists()
+        ups = []
+        try:
+            for ci, layers in enumerate(per_client_layers):
+                cl = self._clients[ci] if self._clients else ld
+                cl.cipher.idx = self.first_idx + ci
+                cl.cipher.masks = masks
+                if seeds is not None:
+                    np.random.seed(seeds[ci])
+                d = {k: (layers[k].to_host() if all_host[ci] and isinstance(layers[k], CompactLayer) else layers[k]) for k in names}
+                d["zzz"] = np.array(zzzs[ci], copy=True)
+                lw = _Layers(d)
+                up = cl.quantize_encrypt(lw, device=True, normalize=normalize)
+                ups.append(up._weights[up.walking_order[0]])
+                ld.shape_dict = cl.shape_dict
+        finally:
+            ld.cipher.idx = self.first_idx
+        own = self._lists[self.first_idx:self.first_idx + self.n_local]
+        agg = aggregate_sparse_uploads(eng, ups, [b for b, _k in own] if self._sorted else masks[self.first_idx:self.first_idx + self.n_local],
+                                       int(ld.cipher.total), device=True)
+        self._last = SparseCohortUpload(ups, agg, PER_CLIENT)
+        self._last_bounds = None
+        return self._last
+
+    # ---- Client.aggregate's decrypt + unquantise -------------------------------------------------------------------------------
+    def decrypt_unquantize(self, aggregate=None, uploaded=None, out=None, unnormalize=False):
+        """The new global model: set_idx_list(uploaded) + shape_dict = shape_dict_used_for_sparsification +
+        FlasheClient.decrypt_unquantize(aggregate, out=, unnormalize=) of client first_idx (jzf_aggregator.py:881-899) -- the same floats,
+        past_layer_mean_list / past_layer_std_list bit for bit.  Without an aggregate the cohort is the whole federation and its own last
+        `aggregate` is decrypted, with the span bounds the upload computed; ValueError when clients outside the cohort exist."""
+        from .cipher import _SparseMinus
+        ld = self.lead
+        c = ld.cipher
+        own = aggregate is None
+        if own:
+            if self.n_local != self.num_clients:
+                raise ValueError(f"the cohort holds {self.n_local} of {self.num_clients} clients: decrypt_unquantize needs the federation's aggregate")
+            if self._last is None:
+                raise ValueError("decrypt_unquantize() without an aggregate needs the upload of this iteration (quantize_encrypt first)")
+            aggregate = self._last.aggregate
+        if self._lists is None:
+            raise ValueError("decrypt_unquantize needs the round's masking choice and lists (dynamic_masking first)")
+        if uploaded is None:
+            uploaded = list(range(self.num_clients))
+        if self.shape_dict_used_for_sparsification is None:
+            raise ValueError("decrypt_unquantize needs the dense layer shapes (shape_dict_used_for_sparsification: sparsify sets it)")
+        if not hasattr(aggregate, "walking_order"):
+            aggregate = _Layers({next(iter(self.shape_dict_used_for_sparsification), "w"): aggregate})
+        saved = ld.shape_dict
+        ld.shape_dict = dict(self.shape_dict_used_for_sparsification)
+        try:
+            if c.masking_scheme == "single" and ld.fuse and not ld.batch:
+                # set_idx_list_single's sparse branch (jzf_flashe.py:316-343) on lists that are in HBM already
+                bounds = self._last_bounds if own and self._last is not None and self._last.path == SPARSE_COHORT else None
+                c.next_iter_decrypt_prepared["minus"] = _SparseMinus(c.engine, c.iter_index, [b for b, _k in self._lists], [k for _b, k in self._lists],
+                                                                     int(c.total), self._sorted, bounds=bounds)
+            else:
+                c.masks = self._host_lists()
+                ld.set_idx_list(list(uploaded))
+            return ld.decrypt_unquantize(aggregate, out=out, unnormalize=unnormalize)
+        except Exception:
+            ld.shape_dict = saved
+            raise

@@ -153,8 +153,9 @@ class _SparseMinus:
     subtracts the mask from the aggregate in the pass that computes it (flashe_sparse_decrypt_dev: one read and one write of the dense
     vector instead of building 16 B x total, reading it back and combining)."""
 
-    def __init__(self, eng, it, dloc, ks, total, sorted_lists):
-        self.eng, self.it, self.dloc, self.ks, self.n, self.sorted_lists = eng, it, dloc, ks, total, sorted_lists
+    def __init__(self, eng, it, dloc, ks, total, sorted_lists, bounds=None):
+        """bounds: a SpanBounds of exactly these lists, computed earlier in the round (FlasheSparseCohort): the decrypt does not recompute it."""
+        self.eng, self.it, self.dloc, self.ks, self.n, self.sorted_lists, self.bounds = eng, it, dloc, ks, total, sorted_lists, bounds
         self._vec = None
 
     def __len__(self):
@@ -607,7 +608,8 @@ class FlasheCipher(object):
                 minus = self.next_iter_decrypt_prepared['minus']
                 self._check_prepared_len(minus, n)
                 if isinstance(minus, _SparseMinus) and not minus.materialized and minus.it == self.iter_index:
-                    eng.sparse_decrypt_dev(minus.it, minus.dloc, minus.ks, n, N_JOBS, dv.buf, out.buf, sorted_lists=minus.sorted_lists)
+                    eng.sparse_decrypt_dev(minus.it, minus.dloc, minus.ks, n, N_JOBS, dv.buf, out.buf, sorted_lists=minus.sorted_lists,
+                                           bounds=minus.bounds)
                 else:
                     eng.combine_dev(n, dv.buf, eng.limbs, None, minus.buf, out.buf)
             if was_compact and self._compact_ok():

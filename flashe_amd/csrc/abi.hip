@@ -3033,6 +3033,157 @@ int flashe_sparsify_tensors_dev(flashe_ctx *ctx, uint64_t n, const flashe_tensor
     return FLASHE_OK;
 }
 
+// ---- a cohort of sparse-job clients on one device (include/flashe.h) ----
+// flashe_sparsify_tensors_dev for C models of one shape: the shared table gives starts and compute classes, the C x L sources their
+// pointers and storage dtypes; client c's residuals / values / locations / packed locations are block c of equal-stride buffers, laid
+// out inside the block exactly as flashe_sparsify_tensors_dev lays out one model.  One set of launches whatever C is.
+int flashe_sparsify_cohort_tensors_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const uint64_t *k,
+                                       const void *const *src_dev, const int32_t *src_dtype, void *residual_dev, uint64_t residual_stride,
+                                       uint32_t *loc_dev, uint64_t loc_stride, void *vals_dev, uint64_t vals_stride, uint64_t *packed_dev,
+                                       uint64_t packed_stride, int bits)
+{
+    CHECK_CTX(ctx);
+    if (n_clients < 1 || n_clients > 65535) return fail(ctx, FLASHE_EINVAL, "sparsify_cohort: n_clients must be in [1, 65535]");
+    if (n >= (1ull << 32)) return fail(ctx, FLASHE_EINVAL, "sparsify_cohort: n must be < 2^32");
+    if (!k || !src_dev || !src_dtype) return fail(ctx, FLASHE_EINVAL, "sparsify_cohort: null argument");
+    int rc = check_tensor_layers_shape(ctx, n, layers, n_layers);
+    if (rc) return rc;
+    if (packed_dev && (bits < 1 || bits > 32 || (bits < 32 && n > (1ull << bits))))
+        return fail(ctx, FLASHE_EINVAL, "sparsify_cohort: bits (%d) must be in [1, 32] and cover n (%llu)", bits, static_cast<unsigned long long>(n));
+    if (static_cast<uint64_t>(n_clients) * static_cast<uint64_t>(n_layers) > (1u << 24)) return fail(ctx, FLASHE_EINVAL, "sparsify_cohort: too many table rows");
+    const size_t rows = static_cast<size_t>(n_clients) * n_layers;
+    // one client's block: flashe_sparsify_tensors_dev's layout
+    std::vector<uint64_t> nl(n_layers), koff1(n_layers), roff1(n_layers), voff1(n_layers);
+    uint64_t total_k = 0, r = 0, v = 0;
+    for (int l = 0; l < n_layers; l++) {
+        const flashe_tensor_layer &y = layers[l];
+        if (y.dtype != FLASHE_TENSOR_F32 && y.dtype != FLASHE_TENSOR_F64)
+            return fail(ctx, FLASHE_EINVAL, "layer %d: the shared row names the COMPUTE type, FLASHE_TENSOR_F32 or FLASHE_TENSOR_F64", l);
+        nl[l] = (l + 1 < n_layers ? layers[l + 1].start : n) - y.start;
+        if (k[l] > nl[l]) return fail(ctx, FLASHE_EINVAL, "sparsify_cohort: layer %d: k (%llu) > n (%llu)", l, static_cast<unsigned long long>(k[l]),
+                                      static_cast<unsigned long long>(nl[l]));
+        const uint64_t cs = y.dtype == FLASHE_TENSOR_F64 ? 8 : 4;
+        r = (r + cs - 1) / cs * cs;
+        v = (v + cs - 1) / cs * cs;
+        koff1[l] = total_k; roff1[l] = r; voff1[l] = v;
+        r += nl[l] * cs;
+        v += k[l] * cs;
+        total_k += k[l];
+    }
+    if (n == 0 || total_k == 0) return FLASHE_OK;
+    if (!loc_dev || !vals_dev) return fail(ctx, FLASHE_EINVAL, "null vector");
+    if (loc_stride < total_k || vals_stride < v || (vals_stride & 7u) || (residual_dev && (residual_stride < r || (residual_stride & 7u))))
+        return fail(ctx, FLASHE_EINVAL, "sparsify_cohort: a stride is shorter than one client's block or not a multiple of 8 bytes");
+    if (static_cast<uint64_t>(n_clients) * loc_stride >= (1ull << 32)) return fail(ctx, FLASHE_EINVAL, "sparsify_cohort: too many locations");
+    const uint64_t n_limbs = (total_k * static_cast<uint64_t>(bits > 0 ? bits : 1) + 63) / 64;
+    if (packed_dev && packed_stride < n_limbs) return fail(ctx, FLASHE_EINVAL, "sparsify_cohort: packed_stride is shorter than one client's packed locations");
+    std::vector<const void *> x(rows);
+    std::vector<int> dt(rows);
+    std::vector<uint64_t> nn(rows), kk(rows), koff(rows), start(rows), roff(rows), voff(rows);
+    for (int c = 0; c < n_clients; c++)
+        for (int l = 0; l < n_layers; l++) {
+            const size_t at = static_cast<size_t>(c) * n_layers + l;
+            const int es = tensor_elem_bytes(src_dtype[at]);
+            if (!es) return fail(ctx, FLASHE_EINVAL, "client %d layer %d: unknown dtype %d", c, l, static_cast<int>(src_dtype[at]));
+            if ((src_dtype[at] == FLASHE_TENSOR_F64) != (layers[l].dtype == FLASHE_TENSOR_F64))
+                return fail(ctx, FLASHE_EINVAL, "client %d layer %d: the source is of another compute class than the shared row", c, l);
+            if (nl[l] && (!src_dev[at] || reinterpret_cast<uintptr_t>(src_dev[at]) % static_cast<uintptr_t>(es)))
+                return fail(ctx, FLASHE_EINVAL, "client %d layer %d: null or misaligned source", c, l);
+            x[at] = src_dev[at]; dt[at] = src_dtype[at]; nn[at] = nl[l]; kk[at] = k[l]; start[at] = layers[l].start;
+            koff[at] = static_cast<uint64_t>(c) * loc_stride + koff1[l];
+            roff[at] = static_cast<uint64_t>(c) * residual_stride + roff1[l];
+            voff[at] = static_cast<uint64_t>(c) * vals_stride + voff1[l];
+        }
+    std::vector<unsigned char> desc(sparsify_tensors_desc_bytes(static_cast<int>(rows)));
+    int r32 = 0;
+    uint64_t nb32 = 0;
+    const uint64_t blocks = sparsify_tensors_layout(static_cast<int>(rows), x.data(), dt.data(), nn.data(), kk.data(), koff.data(), start.data(), roff.data(),
+                                                    voff.data(), desc.data(), &r32, &nb32);
+    if (blocks >= (1ull << 32)) return fail(ctx, FLASHE_EINVAL, "sparsify_cohort: too many elements");
+    if ((rc = ensure(ctx, ctx->sp_ws, sparsify_tensors_workspace_bytes(static_cast<int>(rows), blocks)))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->sp_ws.p, desc.data(), desc.size(), hipMemcpyHostToDevice, ctx->env.stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->env.stream));
+    HIP_TRY(ctx, launch_sparsify_cohort(ctx->env, n_clients, static_cast<int>(rows), r32, blocks, nb32, residual_dev, loc_dev, loc_stride, vals_dev, total_k, bits,
+                                        packed_dev, packed_stride, ctx->sp_ws.p));
+    return FLASHE_OK;
+}
+
+// The sparse job's codec front end for all clients of a cohort in one launch: shared compact layer table (start, alpha, shift, flags;
+// dtype = the compute class), C x L sources, client-major draws -> C one-limb plaintext vectors + the C quantised 'zzz' values.
+int flashe_quantize_cohort_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
+                               const int32_t *src_dtype, int element_bits, const double *u_dev, uint64_t u_stride, const double *zzz, int zzz_is_f64,
+                               uint64_t *const *pt_dev, uint64_t *const *tail_dev, uint64_t *zeros_dev)
+{
+    CHECK_CTX(ctx);
+    if (n_clients < 1 || n_clients > 65535) return fail(ctx, FLASHE_EINVAL, "quantize_cohort: n_clients must be in [1, 65535]");
+    if (!src_dev || !src_dtype || !u_dev || !zzz || !pt_dev || !zeros_dev) return fail(ctx, FLASHE_EINVAL, "quantize_cohort: null argument");
+    if (element_bits < 1 || element_bits > 62 || element_bits > ctx->int_bits)
+        return fail(ctx, FLASHE_EINVAL, "element_bits must be in [1, min(62, int_bits)], got %d", element_bits);
+    if ((reinterpret_cast<uintptr_t>(u_dev) & 7u) || (reinterpret_cast<uintptr_t>(zeros_dev) & 7u)) return fail(ctx, FLASHE_EINVAL, "misaligned vector");
+    if (u_stride < n + 1) return fail(ctx, FLASHE_EINVAL, "quantize_cohort: u_stride must cover a client's n + 1 draws");
+    if (n >= (1ull << 32)) return fail(ctx, FLASHE_EINVAL, "quantize_cohort: n must be < 2^32");
+    int rc = check_tensor_layers_shape(ctx, n, layers, n_layers);
+    if (rc) return rc;
+    std::vector<QuantCohortRow> tab;
+    std::vector<int> row_of;
+    for (int l = 0; l < n_layers; l++) {
+        const flashe_tensor_layer &y = layers[l];
+        const uint64_t end = l + 1 < n_layers ? layers[l + 1].start : n;
+        if (y.start == end) continue;
+        if (!(y.alpha > 0)) return fail(ctx, FLASHE_EINVAL, "layer %d: alpha must be positive", l);
+        if (y.dtype != FLASHE_TENSOR_F32 && y.dtype != FLASHE_TENSOR_F64)
+            return fail(ctx, FLASHE_EINVAL, "layer %d: the shared row names the COMPUTE type, FLASHE_TENSOR_F32 or FLASHE_TENSOR_F64", l);
+        const Codec c = codec_quantize_front(nullptr, y.dtype == FLASHE_TENSOR_F64 || (y.flags & FLASHE_TENSOR_LOOP_F64), y.alpha, element_bits, nullptr);
+        tab.push_back(QuantCohortRow{y.start, c.alpha, c.scale, c.den, y.shift, c.x_is_f64, y.flags & (FLASHE_TENSOR_SHIFT | FLASHE_TENSOR_SHIFT_WIDE)});
+        row_of.push_back(l);
+    }
+    const size_t n_tab = tab.size(), C = static_cast<size_t>(n_clients);
+    std::vector<const void *> src(C * n_tab);
+    std::vector<int32_t> sdt(C * n_tab);
+    for (size_t c = 0; c < C; c++) {
+        if (n && (!pt_dev[c] || (reinterpret_cast<uintptr_t>(pt_dev[c]) & 7u))) return fail(ctx, FLASHE_EINVAL, "client %d: null or misaligned plaintext vector", static_cast<int>(c));
+        if (tail_dev && tail_dev[c] && (reinterpret_cast<uintptr_t>(tail_dev[c]) & 7u)) return fail(ctx, FLASHE_EINVAL, "client %d: misaligned tail", static_cast<int>(c));
+        for (size_t rr = 0; rr < n_tab; rr++) {
+            const int l = row_of[rr];
+            const size_t at = c * n_layers + l;
+            const int es = tensor_elem_bytes(src_dtype[at]);
+            if (!es) return fail(ctx, FLASHE_EINVAL, "client %d layer %d: unknown dtype %d", static_cast<int>(c), l, static_cast<int>(src_dtype[at]));
+            if ((src_dtype[at] == FLASHE_TENSOR_F64) != (layers[l].dtype == FLASHE_TENSOR_F64))
+                return fail(ctx, FLASHE_EINVAL, "client %d layer %d: the source is of another compute class than the shared row", static_cast<int>(c), l);
+            if (!src_dev[at] || reinterpret_cast<uintptr_t>(src_dev[at]) % static_cast<uintptr_t>(es))
+                return fail(ctx, FLASHE_EINVAL, "client %d layer %d: null or misaligned source", static_cast<int>(c), l);
+            src[c * n_tab + rr] = src_dev[at];
+            sdt[c * n_tab + rr] = src_dtype[at];
+        }
+    }
+    // one block in ctx->codec_tab: rows | sources | plaintext pointers | tails | zzz values | source dtypes
+    auto up16 = [](size_t b) { return (b + 15) & ~static_cast<size_t>(15); };
+    const size_t o_src = up16(n_tab * sizeof(QuantCohortRow)), o_pt = o_src + up16(src.size() * sizeof(void *)), o_tail = o_pt + up16(C * sizeof(void *)),
+                 o_zzz = o_tail + up16(C * sizeof(void *)), o_dt = o_zzz + up16(C * sizeof(double));
+    std::vector<char> blob(o_dt + up16(sdt.size() * sizeof(int32_t)) + 16, 0);
+    if (n_tab) memcpy(blob.data(), tab.data(), n_tab * sizeof(QuantCohortRow));
+    if (!src.empty()) memcpy(blob.data() + o_src, src.data(), src.size() * sizeof(void *));
+    memcpy(blob.data() + o_pt, pt_dev, C * sizeof(void *));
+    if (tail_dev) memcpy(blob.data() + o_tail, tail_dev, C * sizeof(void *));
+    memcpy(blob.data() + o_zzz, zzz, C * sizeof(double));
+    if (!sdt.empty()) memcpy(blob.data() + o_dt, sdt.data(), sdt.size() * sizeof(int32_t));
+    const char *blob_dev = nullptr;
+    if ((rc = upload_tab(ctx, ctx->codec_tab, blob, &blob_dev))) return rc;
+    QuantCohort qc{};
+    qc.rows = reinterpret_cast<const QuantCohortRow *>(blob_dev);
+    qc.src = reinterpret_cast<const void *const *>(blob_dev + o_src);
+    qc.pt = reinterpret_cast<uint64_t *const *>(blob_dev + o_pt);
+    qc.tail = reinterpret_cast<uint64_t *const *>(blob_dev + o_tail);
+    qc.zzz = reinterpret_cast<const double *>(blob_dev + o_zzz);
+    qc.src_dtype = reinterpret_cast<const int32_t *>(blob_dev + o_dt);
+    qc.zeros = zeros_dev;
+    qc.n_rows = static_cast<int>(n_tab); qc.n_clients = n_clients; qc.tail_limbs = ctx->limbs;
+    const Codec z = codec_quantize_front(nullptr, zzz_is_f64 != 0, 1.0, element_bits, nullptr);
+    qc.zrow = QuantCohortRow{n, z.alpha, z.scale, z.den, 0.0, z.x_is_f64, 0};
+    HIP_TRY(ctx, launch_quantize_cohort(ctx->env, qc, n, u_dev, u_stride));
+    return FLASHE_OK;
+}
+
 #ifdef FLASHE_TUNING
 // tuning build only: phase cycle sums of span_prf_kernel's workgroup 0 (FLASHE_SPAN_PROBE=9), tests/perf/sparse_phases.py
 int flashe_tune_span_prf_cycles(flashe_ctx *ctx, unsigned long long *out8, int reset)

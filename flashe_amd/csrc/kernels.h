@@ -327,6 +327,30 @@ struct StatLayer {            // NumPy-exact sum and sum of squared deviations o
 hipError_t launch_layer_stats(const LaunchEnv &env, const StatLayer *tab_dev, int n_tab, uint64_t n_blocks, const double *in_dev, uint64_t block,
                               double *bsum_dev, double *means_dev, double *stats_dev);
 
+// The sparse job's codec front end for a cohort of co-located clients (flashe_quantize_cohort_dev, tensors.hip): C clients' compact
+// layers -> C one-limb plaintext vectors in ONE launch, shift + quantise in registers (no staged copy).  Row r of the shared table:
+// compact values [start, next start) of every client, quantised with (alpha, scale, den) in float32 or -- loop_f64 -- float64, after
+// stage_layers_kernel's normalise rule (flags: kTensorShift / kTensorShiftWide).  src[c * n_rows + r] / src_dtype[...] = where client
+// c's values of row r lie and how they are stored.  Client c's value j takes the draw u[c * u_stride + j]; its trailing 'zzz' value
+// zzz[c] (alpha 1.0: zrow) takes the draw u[c * u_stride + n], goes to zeros[c] and, as `tail_limbs` limbs, to tail[c].
+struct QuantCohortRow {
+    uint64_t start;
+    double alpha, scale, den, shift;
+    int32_t loop_f64, flags;
+};
+struct QuantCohort {
+    const QuantCohortRow *rows;
+    const void *const *src;
+    const int32_t *src_dtype;
+    uint64_t *const *pt;       // [n_clients] plaintexts of n values, one limb each
+    uint64_t *const *tail;     // [n_clients] element n of client c's upload
+    const double *zzz;         // [n_clients]
+    uint64_t *zeros;           // [n_clients]
+    int n_rows, n_clients, tail_limbs, pad_;
+    QuantCohortRow zrow;
+};
+hipError_t launch_quantize_cohort(const LaunchEnv &env, const QuantCohort &qc, uint64_t n, const double *u_dev, uint64_t u_stride);
+
 // Top-k of every layer of a model in one set of launches: the layers lie back to back in flat buffers.  The caller fills the host
 // layer table with sparsify_batch_layout (-> number of 1024-element blocks), copies its sparsify_batch_desc_bytes(L) bytes to the START
 // of a device workspace of sparsify_batch_workspace_bytes(L, blocks), then launches.
@@ -345,6 +369,11 @@ uint64_t sparsify_tensors_layout(int L, const void *const *x, const int *dtype, 
                                  uint64_t *n_f32_blocks);
 hipError_t launch_sparsify_tensors(const LaunchEnv &env, int L, int L32, uint64_t n_blocks, uint64_t nb32, void *residual, uint32_t *loc, void *vals,
                                    uint64_t total_k, int bits, uint64_t *packed, void *ws);
+// The same for C clients of one model at once (flashe_sparsify_cohort_tensors_dev): `rows` = C x L table rows laid out with
+// sparsify_tensors_layout (row c L + l = client c's layer l; koff / roff / voff inside client c's equal-stride block), then
+// `_to_bytes(loc_c, bits)` of every client's K locations in one launch (packed: C blocks of packed_stride limbs; may be null).
+hipError_t launch_sparsify_cohort(const LaunchEnv &env, int C, int rows, int rows32, uint64_t n_blocks, uint64_t nb32, void *residual, uint32_t *loc,
+                                  uint64_t loc_stride, void *vals, uint64_t K, int bits, uint64_t *packed, uint64_t packed_stride, void *ws);
 // Top-k sparsifier; ws = device workspace of sparsify_workspace_bytes(n).
 size_t sparsify_workspace_bytes(uint64_t n);
 hipError_t launch_sparsify(const LaunchEnv &env, uint64_t n, uint64_t k, const void *x, bool is_f64, void *residual, uint32_t *loc,

@@ -764,6 +764,45 @@ hipError_t launch_sparsify_tensors(const LaunchEnv &env, int L, int L32, uint64_
     return hipGetLastError();
 }
 
+// ---- a cohort of co-located clients (flashe_sparsify_cohort_tensors_dev) -------------------------------------------------------------
+// Client.sparsify (jzf_aggregator.py:578-623) keeps k_l = max(1, floor(sparsity * size_l)) entries of layer l: the COUNT depends on the
+// shape only, so the C clients of a cohort share one layer table and differ in where their values lie.  The passes above are driven by
+// per-row start / roff / voff / koff, so the cohort is a table of C x L rows -- row c L + l: client c's layer l, its residual, values and
+// locations in client c's equal-stride block -- and every stage stays ONE launch whatever C is.  What has a client dimension is the
+// pack pass: `_to_bytes(loc_c, bits)` (jzf_aggregator.py:615-623) of every client in one launch, blockIdx.y = the client.
+__global__ void spc_pack_kernel(const uint32_t *loc_all, uint64_t loc_stride, uint64_t K, int bits, uint64_t n_limbs, uint64_t *packed_all,
+                                uint64_t packed_stride)
+{
+    const uint64_t w = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (w >= n_limbs) return;
+    const uint32_t *loc = loc_all + static_cast<uint64_t>(blockIdx.y) * loc_stride;
+    const uint64_t lo = 64 * w;
+    const uint64_t r_lo = lo / static_cast<uint64_t>(bits);
+    const uint64_t r_hi = std::min<uint64_t>(K - 1, (lo + 63) / static_cast<uint64_t>(bits));
+    uint64_t v = 0;
+    for (uint64_t r = r_lo; r <= r_hi; r++) {                       // entry j of K fills bits [bits (K-1-j), bits (K-j)), as spt_pack_kernel
+        const uint64_t x = loc[K - 1 - r];
+        const int64_t pos = static_cast<int64_t>(r * static_cast<uint64_t>(bits)) - static_cast<int64_t>(lo);
+        v |= pos >= 0 ? x << pos : x >> (-pos);
+    }
+    packed_all[static_cast<uint64_t>(blockIdx.y) * packed_stride + w] = v;
+}
+
+// rows = C x L table rows laid out by sparsify_tensors_layout (the workspace rules of launch_sparsify_tensors); K = entries per client
+hipError_t launch_sparsify_cohort(const LaunchEnv &env, int C, int rows, int rows32, uint64_t n_blocks, uint64_t nb32, void *residual, uint32_t *loc,
+                                  uint64_t loc_stride, void *vals, uint64_t K, int bits, uint64_t *packed, uint64_t packed_stride, void *ws)
+{
+    if (C <= 0 || rows <= 0 || n_blocks == 0) return hipSuccess;
+    const hipError_t e = launch_sparsify_tensors(env, rows, rows32, n_blocks, nb32, residual, loc, vals, 0, bits, nullptr, ws);
+    if (e != hipSuccess) return e;
+    if (packed && K) {
+        const uint64_t n_limbs = (K * static_cast<uint64_t>(bits) + 63) / 64;
+        hipLaunchKernelGGL(spc_pack_kernel, dim3(static_cast<unsigned>((n_limbs + 255) / 256), static_cast<unsigned>(C)), dim3(256), 0, env.stream, loc,
+                           loc_stride, K, bits, n_limbs, packed, packed_stride);
+    }
+    return hipGetLastError();
+}
+
 // One layer: the model-wide passes on a ONE-layer table that a kernel writes on the device -- table, block map, select state and
 // histogram in one launch, no upload, no synchronisation (capturable).  Round 5: the single-layer kernels this replaces kept one element
 // per lane in their count / write passes and a strided single-workgroup scan.

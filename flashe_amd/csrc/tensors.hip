@@ -59,6 +59,155 @@ hipError_t launch_stage_layers(const LaunchEnv &env, const TensorStage *tab_dev,
     return hipGetLastError();
 }
 
+// ---- the sparse job's front end for a cohort: C clients' compact layers -> C plaintext vectors in one launch ----
+// What Client.secure_aggregate does to the compact layers Client.sparsify kept (jzf_aggregator.py:717-743: quantize, flatten, strip the
+// quantised 'zzz' value, encrypt, re-append it) starts with QuantizingClient.quantize (jzf_quantize.py:433-465) per client.  Here: a
+// workgroup owns a 1024-value tile of ONE client's compact vector (blockIdx.y = the client), finds the tile's table row once with
+// scalar loads and keeps the row's alpha / scale / den / shift in SGPRs; a lane takes four consecutive values -- one 16-byte load of
+// float32 values, two of the draws, two 16-byte stores of the plaintexts where the pointers allow them, scalar accesses at row ends and
+// on odd alignments -- and normalises (stage_layers_kernel's rule) and quantises (quantize_one) in registers.  Only a tile that
+// straddles a row boundary (at most one per row) looks the row up per value.  The extra workgroup blockIdx.x == n_tiles quantises the
+// client's trailing 'zzz' value (alpha 1.0, :433-435) with the draw behind the client's n.
+constexpr int kQcThreads = 256;
+constexpr uint64_t kQcTile = 4 * kQcThreads;
+
+struct QcRowRegs {             // one row's parameters and one client's source of it
+    const void *x;
+    uint64_t start;
+    double alpha, scale, den, shift;
+    int dtype, flags, loop64;
+};
+
+__device__ __forceinline__ uint64_t qc_quantize(const QcRowRegs &R, uint64_t r, double u)
+{
+#pragma clang fp contract(off)
+    if (R.dtype == kTensorF64) {
+        double x = static_cast<const double *>(R.x)[r];
+        if (R.flags & kTensorShift) x = x + R.shift;
+        return quantize_one<double>(x, R.alpha, R.scale, R.den, u);
+    }
+    float x;
+    if (R.dtype == kTensorF32) x = static_cast<const float *>(R.x)[r];
+    else if (R.dtype == kTensorF16) x = f16_to_f32(static_cast<const uint16_t *>(R.x)[r]);
+    else x = bf16_to_f32(static_cast<const uint16_t *>(R.x)[r]);
+    if (R.flags & kTensorShift)
+        x = (R.flags & kTensorShiftWide) ? static_cast<float>(static_cast<double>(x) + R.shift) : x + static_cast<float>(R.shift);
+    return R.loop64 ? quantize_one<double>(static_cast<double>(x), R.alpha, R.scale, R.den, u)
+                    : quantize_one<float>(x, static_cast<float>(R.alpha), static_cast<float>(R.scale), static_cast<float>(R.den), u);
+}
+
+// the same on a float32 value already in a register (the vector path of float32 sources)
+__device__ __forceinline__ uint64_t qc_quantize_f32(const QcRowRegs &R, float x, double u)
+{
+#pragma clang fp contract(off)
+    if (R.flags & kTensorShift)
+        x = (R.flags & kTensorShiftWide) ? static_cast<float>(static_cast<double>(x) + R.shift) : x + static_cast<float>(R.shift);
+    return R.loop64 ? quantize_one<double>(static_cast<double>(x), R.alpha, R.scale, R.den, u)
+                    : quantize_one<float>(x, static_cast<float>(R.alpha), static_cast<float>(R.scale), static_cast<float>(R.den), u);
+}
+
+__global__ __launch_bounds__(kQcThreads) void quantize_cohort_kernel(const QuantCohort qc, uint64_t n, const double *__restrict__ u_all, uint64_t u_stride,
+                                                                     uint32_t n_tiles)
+{
+#pragma clang fp contract(off)
+    const uint32_t c = blockIdx.y;
+    const double *u = u_all + static_cast<uint64_t>(c) * u_stride;
+    if (blockIdx.x >= n_tiles) {                                      // the trailing value: not encrypted, element n of the upload
+        if (threadIdx.x == 0) {
+            const double v = qc.zzz[c];
+            const uint64_t q = qc.zrow.loop_f64 ? quantize_one<double>(v, qc.zrow.alpha, qc.zrow.scale, qc.zrow.den, u[n])
+                                                : quantize_one<float>(static_cast<float>(v), static_cast<float>(qc.zrow.alpha),
+                                                                      static_cast<float>(qc.zrow.scale), static_cast<float>(qc.zrow.den), u[n]);
+            qc.zeros[c] = q;
+            uint64_t *t = qc.tail[c];
+            if (t) {
+                t[0] = q;
+                if (qc.tail_limbs == 2) t[1] = 0;
+            }
+        }
+        return;
+    }
+    const uint64_t t0 = static_cast<uint64_t>(blockIdx.x) * kQcTile;
+    const uint64_t t1 = t0 + kQcTile < n ? t0 + kQcTile : n;
+    uint64_t *pt = reinterpret_cast<uint64_t *>(*FLASHE_CONSTANT(const uint64_t, reinterpret_cast<const uint64_t *>(qc.pt) + c));
+    const uint64_t j0 = t0 + 4u * threadIdx.x;
+    // the tile's first row, with scalar loads (t0 is uniform over the workgroup)
+    int lo = 0, hi = qc.n_rows - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (*FLASHE_CONSTANT(const uint64_t, &qc.rows[mid].start) <= t0) lo = mid; else hi = mid - 1;
+    }
+    const uint64_t next = lo + 1 < qc.n_rows ? *FLASHE_CONSTANT(const uint64_t, &qc.rows[lo + 1].start) : n;
+    if (next >= t1) {
+        // the whole tile lies in row `lo`: its parameters and the client's source pointer are wave-uniform
+        const QuantCohortRow *row = qc.rows + lo;
+        const size_t at = static_cast<size_t>(c) * qc.n_rows + lo;
+        QcRowRegs R;
+        R.x = reinterpret_cast<const void *>(*FLASHE_CONSTANT(const uint64_t, reinterpret_cast<const uint64_t *>(qc.src) + at));
+        R.dtype = *FLASHE_CONSTANT(const int32_t, qc.src_dtype + at);
+        R.start = *FLASHE_CONSTANT(const uint64_t, &row->start);
+        R.alpha = *FLASHE_CONSTANT(const double, &row->alpha);
+        R.scale = *FLASHE_CONSTANT(const double, &row->scale);
+        R.den = *FLASHE_CONSTANT(const double, &row->den);
+        R.shift = *FLASHE_CONSTANT(const double, &row->shift);
+        R.flags = *FLASHE_CONSTANT(const int32_t, &row->flags);
+        R.loop64 = *FLASHE_CONSTANT(const int32_t, &row->loop_f64);
+        if (j0 >= t1) return;
+        const uint64_t r = j0 - R.start;
+        if (j0 + 4 > t1) {                                            // the vector's last lane
+            for (uint64_t j = j0; j < t1; j++) pt[j] = qc_quantize(R, j - R.start, u[j]);
+            return;
+        }
+        double uu[4];
+        if ((reinterpret_cast<uintptr_t>(u + j0) & 15u) == 0) {
+            const double2 a = *reinterpret_cast<const double2 *>(u + j0), b = *reinterpret_cast<const double2 *>(u + j0 + 2);
+            uu[0] = a.x; uu[1] = a.y; uu[2] = b.x; uu[3] = b.y;
+        } else {
+#pragma unroll
+            for (int t = 0; t < 4; t++) uu[t] = u[j0 + t];
+        }
+        uint64_t q[4];
+        if (R.dtype == kTensorF32 && (reinterpret_cast<uintptr_t>(static_cast<const float *>(R.x) + r) & 15u) == 0) {
+            const float4 v = *reinterpret_cast<const float4 *>(static_cast<const float *>(R.x) + r);
+            q[0] = qc_quantize_f32(R, v.x, uu[0]); q[1] = qc_quantize_f32(R, v.y, uu[1]);
+            q[2] = qc_quantize_f32(R, v.z, uu[2]); q[3] = qc_quantize_f32(R, v.w, uu[3]);
+        } else {
+#pragma unroll
+            for (int t = 0; t < 4; t++) q[t] = qc_quantize(R, r + t, uu[t]);
+        }
+        if ((reinterpret_cast<uintptr_t>(pt + j0) & 15u) == 0) {
+            *reinterpret_cast<ulonglong2 *>(pt + j0) = make_ulonglong2(q[0], q[1]);
+            *reinterpret_cast<ulonglong2 *>(pt + j0 + 2) = make_ulonglong2(q[2], q[3]);
+        } else {
+#pragma unroll
+            for (int t = 0; t < 4; t++) pt[j0 + t] = q[t];
+        }
+        return;
+    }
+    // a tile that straddles a row boundary: every value finds its own row (the search starts at the tile's first row)
+    for (uint64_t j = j0; j < j0 + 4 && j < t1; j++) {
+        int a = lo, b = qc.n_rows - 1;
+        while (a < b) {
+            const int mid = (a + b + 1) >> 1;
+            if (qc.rows[mid].start <= j) a = mid; else b = mid - 1;
+        }
+        const QuantCohortRow &row = qc.rows[a];
+        const size_t at = static_cast<size_t>(c) * qc.n_rows + a;
+        const QcRowRegs R{qc.src[at], row.start, row.alpha, row.scale, row.den, row.shift, qc.src_dtype[at], row.flags, row.loop_f64};
+        pt[j] = qc_quantize(R, j - row.start, u[j]);
+    }
+}
+
+hipError_t launch_quantize_cohort(const LaunchEnv &env, const QuantCohort &qc, uint64_t n, const double *u_dev, uint64_t u_stride)
+{
+    if (qc.n_clients < 1 || qc.n_clients > 65535 || (n && qc.n_rows < 1)) return hipErrorInvalidValue;
+    const uint64_t tiles = (n + kQcTile - 1) / kQcTile;
+    if (tiles >= (1ull << 31)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(quantize_cohort_kernel, dim3(static_cast<unsigned>(tiles) + 1u, static_cast<unsigned>(qc.n_clients)), dim3(kQcThreads), 0, env.stream,
+                       qc, n, u_dev, u_stride, static_cast<uint32_t>(tiles));
+    return hipGetLastError();
+}
+
 // ---- back end: eight values of one layer per lane; 16-byte stores where the layer's pointer allows them ----
 __global__ __launch_bounds__(kStreamThreads) void store_layers_kernel(const TensorStore *__restrict__ tab, int n_tab, uint64_t n_groups,
                                                                       const double *__restrict__ in)

@@ -229,6 +229,19 @@ class DeviceBuffer:
         return out
 
 
+class DeviceBufferView(DeviceBuffer):
+    """`nbytes` at byte `offset` of another DeviceBuffer (one client's block of a cohort's buffer): the same surface, owns nothing and
+    keeps its parent alive."""
+
+    def __init__(self, parent, offset, nbytes):
+        assert 0 <= offset and offset + nbytes <= parent.nbytes
+        self.engine, self.nbytes, self.parent = parent.engine, int(nbytes), parent
+        self.ptr = parent.ptr + int(offset)
+
+    def free(self):
+        self.ptr = None
+
+
 class DeviceVector:
     """A vector of `n` elements (L = `limbs` uint64 limbs each) that STAYS in HBM between calls of the drop-in API: what
     FlasheCipher.encrypt / aggregate / decrypt return with device=True and accept in place of an ndarray, so that a round moves
@@ -1334,6 +1347,36 @@ class Engine:
         ak = (c_u64 * max(nl, 1))(*[int(v) for v in ks])
         self._check(self._lib.flashe_sparsify_tensors_dev(self._h, int(n), arr, nl, ak, self._ptr(residual), self._ptr(loc), self._ptr(vals),
                                                           self._ptr(packed), int(bits)))
+
+    def sparsify_cohort_tensors_dev(self, n, layers, ks, srcs, dtypes, residual, residual_stride, loc, loc_stride, vals, vals_stride, packed=None,
+                                    packed_stride=0, bits=0):
+        """sparsify_tensors_dev for C models of one shape in one set of launches (flashe_sparsify_cohort_tensors_dev): layers = the shared
+        table [(start, compute dtype code)], srcs[c][l] / dtypes[c][l] = client c's layer l and its storage dtype; client c's residuals,
+        values, locations and packed locations are block c of the equal-stride buffers (byte strides for residual / vals, entries for loc,
+        limbs for packed), each block in sparsify_tensors_dev's layout."""
+        arr, nl = self._tensor_layers([(start, None, 1.0, 0.0, dtype, 0) for start, dtype in layers])
+        C = len(srcs)
+        ak = (c_u64 * max(nl, 1))(*[int(v) for v in ks])
+        ps = (c_vp * max(C * nl, 1))(*[int(p) if p else None for row in srcs for p in row])
+        pd = (ctypes.c_int32 * max(C * nl, 1))(*[int(d) for row in dtypes for d in row])
+        self._check(self._lib.flashe_sparsify_cohort_tensors_dev(self._h, C, int(n), arr, nl, ak, ps, pd, self._ptr(residual), int(residual_stride),
+                                                                 self._ptr(loc), int(loc_stride), self._ptr(vals), int(vals_stride), self._ptr(packed),
+                                                                 int(packed_stride), int(bits)))
+
+    def quantize_cohort_dev(self, n, layers, srcs, dtypes, element_bits, u, u_stride, zzz, zzz_is_f64, pts, tails, zeros):
+        """The sparse job's codec front end for a cohort in one launch (flashe_quantize_cohort_dev): layers = the shared compact table
+        (start, None, alpha, shift, compute dtype code, flags); srcs[c][l] / dtypes[c][l] = client c's compact layer l; client c's value j
+        takes the draw u[c * u_stride + j], its 'zzz' value zzz[c] the draw u[c * u_stride + n]; pts[c] = its n one-limb plaintexts,
+        tails[c] (or None) = where its quantised 'zzz' goes as a ciphertext-width element; zeros = device uint64[C] of those values."""
+        arr, nl = self._tensor_layers(layers)
+        C = len(srcs)
+        ps = (c_vp * max(C * nl, 1))(*[int(p) if p else None for row in srcs for p in row])
+        pd = (ctypes.c_int32 * max(C * nl, 1))(*[int(d) for row in dtypes for d in row])
+        pz = (ctypes.c_double * max(C, 1))(*[float(z) for z in zzz])
+        pp, _kp = self._ptr_array(pts)
+        pt, _kt = self._ptr_array(tails) if tails is not None else (None, None)
+        self._check(self._lib.flashe_quantize_cohort_dev(self._h, C, int(n), arr, nl, ps, pd, int(element_bits), self._ptr(u), int(u_stride), pz,
+                                                         1 if zzz_is_f64 else 0, pp, pt, self._ptr(zeros)))
 
     def sparsify_batch(self, layers, ks, residuals=None):
         """[(loc uint32[k_l] ascending, vals[k_l], new residual or None) per layer] -- Client.sparsify's layer loop

@@ -71,7 +71,8 @@ typedef struct flashe_ctx flashe_ctx;
  *      flashe_decrypt_prepared_unquantize_model_dev, flashe_decrypt_prepared_unbatch_unquantize_model_dev (the model-wide codec with the
  *      ctx's precomputed masks); FLASHE_ENOTSUP + flashe_quantize_encrypt_cohort_dev (a cohort of co-located clients: C float models
  *      to C ciphertexts, their sum and the decrypt mask in one chained launch) and flashe_combine_unquantize_model_dev (the codec back
- *      end over a sum and caller-held masks) */
+ *      end over a sum and caller-held masks); flashe_sparsify_cohort_tensors_dev and flashe_quantize_cohort_dev (a cohort of sparse-job
+ *      clients: C models sparsified in one set of launches, their compact layers quantised in one launch) */
 #define FLASHE_ABI_VERSION 4
 int flashe_abi_version(void);
 int flashe_device_count(int *count);
@@ -790,6 +791,32 @@ int flashe_sparsify_batch(flashe_ctx *ctx, int n_layers, const uint64_t *n, cons
  * n < 2^32.  The tables are uploaded synchronously (not inside a graph capture); 14 launches for a float32-class model, 24 mixed. */
 int flashe_sparsify_tensors_dev(flashe_ctx *ctx, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const uint64_t *k, void *residual_dev,
                                 uint32_t *loc_dev, void *vals_dev, uint64_t *packed_dev, int bits);
+/* A cohort of sparse-job clients hosted on one device (new): Client.sparsify (jzf_aggregator.py:578-623) of C models of ONE shape in ONE
+ * set of launches.  k_l = max(1, floor(sparsity * size_l)) depends on the shape only, so the clients share the layer table and differ in
+ * where their values lie.  layers: the shared HOST table (start as above; dtype = the layer's COMPUTE class, FLASHE_TENSOR_F32 or
+ * FLASHE_TENSOR_F64, the same for all clients; ptr, alpha, shift and flags ignored); src_dev / src_dtype: HOST arrays of n_clients x n_layers
+ * entries, [c * n_layers + l] = client c's layer l and its storage dtype (F16 / BF16 under an F32 row are widened exactly).
+ * Client c's residuals, values, locations and packed locations are block c of equal-stride buffers -- residual_dev + c residual_stride
+ * bytes, vals_dev + c vals_stride bytes, loc_dev + c loc_stride entries, packed_dev + c packed_stride limbs -- each block laid out as
+ * flashe_sparsify_tensors_dev lays out one model; byte strides are multiples of 8.  Results are, client by client, those of C
+ * flashe_sparsify_tensors_dev calls.  The launch count does not depend on n_clients: 14 for a float32-class cohort, 24 mixed. */
+int flashe_sparsify_cohort_tensors_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const uint64_t *k,
+                                       const void *const *src_dev, const int32_t *src_dtype, void *residual_dev, uint64_t residual_stride,
+                                       uint32_t *loc_dev, uint64_t loc_stride, void *vals_dev, uint64_t vals_stride, uint64_t *packed_dev,
+                                       uint64_t packed_stride, int bits);
+/* The codec front end of those clients' uploads in ONE launch (new): what QuantizingClient.quantize (jzf_quantize.py:433-465) makes of
+ * the compact layers inside Client.secure_aggregate (jzf_aggregator.py:717-743), for all clients of the cohort.  layers: the shared
+ * HOST table over the n compact values of one client (start, alpha, shift, flags as flashe_quantize_encrypt_tensors_dev reads them;
+ * dtype = the COMPUTE class); src_dev / src_dtype as above (e.g. the values flashe_sparsify_cohort_tensors_dev left).  u_dev: the
+ * draws, client c's value j takes u_dev[c * u_stride + j] and its trailing 'zzz' value the draw behind them, u_dev[c * u_stride + n]
+ * (u_stride >= n + 1).  pt_dev[c] (HOST array of device pointers): client c's n plaintexts, ONE uint64 limb each -- what
+ * flashe_sparse_encrypt_aggregate_dev reads with pt_limbs = 1.  zzz: HOST array of the clients' (normalised) 'zzz' values, quantised
+ * with alpha 1.0 in float64 (zzz_is_f64) or float32 into zeros_dev[c] (device, uint64) and, when tail_dev (HOST array, may be NULL) names
+ * one, into the flashe_limbs(int_bits) limbs at tail_dev[c] -- element n of client c's upload.  Bit for bit the values of
+ * flashe_quantize_encrypt_tensors_dev's front end.  The table is uploaded synchronously (not inside a graph capture). */
+int flashe_quantize_cohort_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
+                               const int32_t *src_dtype, int element_bits, const double *u_dev, uint64_t u_stride, const double *zzz, int zzz_is_f64,
+                               uint64_t *const *pt_dev, uint64_t *const *tail_dev, uint64_t *zeros_dev);
 
 /* ---- multi-GPU exchange (RCCL over xGMI; one process per GPU) ----------------------------------------------- */
 /* Replaces, inside one node, the arbiter's gather of client models + reduce in Python + broadcast of the aggregate
