@@ -146,6 +146,13 @@ BatchLayer batch_layer_back(uint64_t elem_start, uint64_t value_start, uint64_t 
     return BatchLayer{elem_start, value_start, size, nullptr, c.ac, c.two_a, c.uden, 0, 0};
 }
 
+// (2^bits - 1) * num_clients as the reference forms it on Python ints: the exact product, rounded once to float64.  In 64 bits it
+// wraps from (62, 5) on; int -> float64 of a 128-bit integer is correctly rounded on the host
+static double codec_denominator(int bits, int num_clients)
+{
+    return static_cast<double>(static_cast<unsigned __int128>((1ull << bits) - 1) * static_cast<unsigned __int128>(num_clients));
+}
+
 Codec codec_quantize_front(const void *x_dev, bool is_f64, double alpha, int bits, const double *u_dev)
 {
     Codec c{};
@@ -158,7 +165,7 @@ void codec_unquantize_back(Codec *c, double alpha, int bits, int num_clients, do
     c->fout = out_dev;
     c->ac = alpha * static_cast<double>(num_clients);
     c->two_a = 2 * c->ac;
-    c->uden = static_cast<double>(((1ull << bits) - 1) * static_cast<uint64_t>(num_clients));
+    c->uden = codec_denominator(bits, num_clients);
 }
 
 CodecLayer codec_layer_front(uint64_t start, const void *x_dev, bool is_f64, double alpha, int bits)
@@ -266,7 +273,7 @@ hipError_t launch_unquantize(const LaunchEnv &env, uint64_t n, const uint64_t *v
 {
     if (n == 0) return hipSuccess;
     const double ac = alpha * static_cast<double>(num_clients);
-    const double den = static_cast<double>(((1ull << bits) - 1) * static_cast<uint64_t>(num_clients));
+    const double den = codec_denominator(bits, num_clients);
     hipLaunchKernelGGL(unquantize_kernel, dim3(stream_grid(env, n)), dim3(kStreamThreads), 0, env.stream, n, v_dev, v_limbs, ac,
                        2 * ac, den, out_dev);
     return hipGetLastError();
@@ -304,11 +311,13 @@ __global__ __launch_bounds__(kStreamThreads) void combine_unquantize_model_kerne
     for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * kStreamThreads + threadIdx.x; k < count; k += static_cast<uint64_t>(gridDim.x) * kStreamThreads) {
         u128 v;
         if (WIDE) {
-            v = ld128_nt(in + 2 * k) + ld128_nt(add + 2 * k);
+            v = ld128_nt(in + 2 * k);
+            if (add) v += ld128_nt(add + 2 * k);                        // (NULL = zeros: flashe_combine_unquantize_model_dev admits it)
             if (minus) v -= ld128_nt(minus + 2 * k);
             v &= mask;
         } else {
-            uint64_t x = __builtin_nontemporal_load(in + k) + __builtin_nontemporal_load(add + k);
+            uint64_t x = __builtin_nontemporal_load(in + k);
+            if (add) x += __builtin_nontemporal_load(add + k);
             if (minus) x -= __builtin_nontemporal_load(minus + k);
             v = static_cast<u128>(x & mask_lo);
         }

@@ -504,6 +504,14 @@ def gen_codec():
         r = RQ._static_unquantize_padding_asymmetric(np.array(vals, dtype=object), alpha, eb, C)
         out["unquantize"].append({"element_bits": eb, "num_clients": C, "n": n, "alpha": float(alpha).hex(),
                                   "vals": hxl(vals), "out": np.array([float(v) for v in r], dtype=np.float64).tobytes().hex()})
+    # the (element_bits, num_clients) pairs whose denominator (2^bits - 1) * num_clients needs more than 64 bits (appended: the draws
+    # of the cases above stay what they were); the first value of (62, 5) is 5 * (2^62 - 1), which comes back as alpha * num_clients
+    for eb, C, n, top_bits in [(62, 5, 40, 66), (62, 10, 40, 66), (58, 100, 40, 128)]:
+        alpha = 6.5
+        vals = [((1 << eb) - 1) * C] + rand_ints(rng, n - 1, top_bits)
+        r = RQ._static_unquantize_padding_asymmetric(np.array(vals, dtype=object), alpha, eb, C)
+        out["unquantize"].append({"element_bits": eb, "num_clients": C, "n": n, "alpha": float(alpha).hex(),
+                                  "vals": hxl(vals), "out": np.array([float(v) for v in r], dtype=np.float64).tobytes().hex()})
     dump("codec.json", out)
 
 

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, load_golden, unhex
+import codec_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -486,6 +487,7 @@ def test_client_step_of_a_large_model_vs_oracle(oracle, b, scheme, n_jobs):
         v = np.array(dec[at:at + size], dtype=np.float64) if size else np.zeros(0)
         want = v * (2 * alpha) / (((1 << eb) - 1) * C) - alpha                      # jzf_quantize.py:102-107
         assert back._weights[k].shape == sh and np.asarray(back._weights[k]).tobytes() == want.reshape(sh).tobytes(), (b, k)
+        assert want.tobytes() == codec_ref.ref_unquantize(dec[at:at + size], clients[0].quantizer.alpha_list[li], eb, C).tobytes()      # on Python ints
         at += size
 
 
@@ -625,3 +627,4 @@ def test_batched_client_step_of_a_large_model_vs_oracle(oracle, b, eb, C, n_jobs
         v = np.array(vals[:size], dtype=np.float64) if size else np.zeros(0)
         want = v * (2 * alpha) / (((1 << eb) - 1) * C) - alpha
         assert back._weights[k].shape == sh and np.asarray(back._weights[k]).tobytes() == want.reshape(sh).tobytes(), (b, k)
+        assert want.tobytes() == codec_ref.ref_unquantize(vals[:size], clients[0].quantizer.alpha_list[li], eb, C).tobytes()          # on Python ints

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, load_golden, unhex
+import codec_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -1094,17 +1095,25 @@ def test_codec_vs_oracle_large(E, oracle):
     for dtype, bits in ((np.float32, 16), (np.float32, 32), (np.float64, 24)):
         x = (rng.standard_normal(300001) * 4).astype(dtype)
         u = rng.random(300001)
-        assert np.array_equal(e64.quantize(x, 8.17121, bits, u), oracle.quantize(x, 8.17121, bits, u))
+        got = e64.quantize(x, 8.17121, bits, u)
+        assert np.array_equal(got, oracle.quantize(x, 8.17121, bits, u))
+        # and against the independent NumPy reference: a change made to oracle and kernel together is caught at full size too
+        assert np.array_equal(got, codec_ref.ref_quantize(x, 8.17121, bits, u).astype(np.uint64))
     v = rng.integers(0, 2 ** 64, size=(200001, 2), dtype=np.uint64)
     v[::3, 1] = 0
     v[1::7, 1] &= np.uint64(0xFF)
-    assert e128.unquantize(v, 6.5, 32, 10).tobytes() == oracle.unquantize(v, 6.5, 32, 10).tobytes()
+    got = e128.unquantize(v, 6.5, 32, 10)
+    assert got.tobytes() == oracle.unquantize(v, 6.5, 32, 10).tobytes()
+    assert got.tobytes() == codec_ref.ref_unquantize(codec_ref.from_limbs(v), 6.5, 32, 10).tobytes()
     for int_bits, fb in ((128, 20), (120, 20), (64, 17), (20, 20), (100, 33)):
         eng = make(E, int_bits)
         vals = rng.integers(0, 2 ** fb, 100003, dtype=np.uint64)
         b = eng.batch(vals, fb)
         assert np.array_equal(b, oracle.batch(vals, int_bits, fb))
-        assert np.array_equal(eng.unbatch(b, fb), oracle.unbatch(b, int_bits, fb))
+        assert codec_ref.from_limbs(b) == codec_ref.ref_batch(vals, int_bits, fb)
+        back = eng.unbatch(b, fb)
+        assert np.array_equal(back, oracle.unbatch(b, int_bits, fb))
+        assert [int(t) for t in back] == codec_ref.ref_unbatch(codec_ref.from_limbs(b), int_bits, fb)
 
 
 def test_config1_end_to_end_with_codec(E):
