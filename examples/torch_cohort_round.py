@@ -4,7 +4,12 @@
 FlasheCohort takes one Weights per client (the parameters as they are, read through DLPack), runs the clients' quantise + encrypt as one
 chained launch where the model is long enough to fill the chip (shorter models take the staged form: `upload.path` says which), and
 decrypt_unquantize writes the new global model into `out`.  The result is bit for bit what ten FlasheClients produce one after the other,
-which this example checks."""
+which this example checks.
+
+  --bits B     int_bits of the job (default 128; the reference's shipped un-batched jobs run 20)
+  --compact    with --bits <= 32: uint32 ciphertexts and sum (FlasheCohort(compact=True)); at int_bits 16 / 20 / 23 / 24 / 32 the chained
+               launch then goes from the floats to the uint32 ciphertexts"""
+import argparse
 import os
 import sys
 
@@ -29,14 +34,23 @@ def make_model(seed):
     return torch.nn.Sequential(torch.nn.Conv2d(3, 16, 5), torch.nn.ReLU(), torch.nn.Flatten(), torch.nn.Linear(16 * 28 * 28, 10)).cuda()
 
 
+def values(dv):
+    """A DeviceVector's elements, whatever its layout (uint32 [n] compact, uint64 [n, limbs] otherwise)."""
+    return np.asarray(dv.to_host(), dtype=np.uint64).reshape(len(dv), -1)
+
+
 def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--bits", type=int, default=128)
+    ap.add_argument("--compact", action="store_true")
+    opt = ap.parse_args()
     cm.N_JOBS = 16                                           # every party must use the same value
     C, key = 10, bytes(range(32))
-    args = {"quantize": {"int_bits": 128, "batch": False, "element_bits": 16, "padding": True, "secure": True}, "precompute": {"enable": False}}
+    args = {"quantize": {"int_bits": opt.bits, "batch": False, "element_bits": 16, "padding": True, "secure": True}, "precompute": {"enable": False}}
     models = [make_model(c) for c in range(C)]
     layers = [{name: p.detach() for name, p in m.named_parameters()} for m in models]
 
-    cohort = FlasheCohort(args, first_idx=0, n_local=C, num_clients=C, prp_seed=key)
+    cohort = FlasheCohort(args, first_idx=0, n_local=C, num_clients=C, prp_seed=key, compact=opt.compact)
     cohort.set_iter_index(0)
     np.random.seed(0)
     with torch.no_grad():
@@ -44,7 +58,7 @@ def main():
         new_global = {name: torch.empty_like(t) for name, t in layers[0].items()}
         cohort.decrypt_unquantize(out=new_global, unnormalize=True)
     print(f"{C} clients, {sum(t.numel() for t in layers[0].values())} parameters each: path {upload.path!r}, "
-          f"{len(upload.ciphertexts)} ciphertexts and their sum in HBM")
+          f"{len(upload.ciphertexts)} ciphertexts and their sum in HBM ({upload.partial_sum.elem_bytes * upload.partial_sum.limbs} bytes per element)")
 
     # the same round as ten FlasheClients, one after the other
     clients = []
@@ -64,8 +78,8 @@ def main():
         want = {name: torch.empty_like(t) for name, t in layers[0].items()}
         clients[0].decrypt_unquantize(Weights({sorted(layers[0])[0]: agg}), out=want, unnormalize=True)
     for c in range(C):
-        assert upload.ciphertexts[c].to_host().tobytes() == cts[c].to_host().tobytes(), f"client {c}'s upload differs"
-    assert upload.partial_sum.to_host().tobytes() == agg.to_host().tobytes()
+        assert np.array_equal(values(upload.ciphertexts[c]), values(cts[c])), f"client {c}'s upload differs"
+    assert np.array_equal(values(upload.partial_sum), values(agg))
     for name in want:
         assert torch.equal(want[name].view(torch.uint8), new_global[name].view(torch.uint8)), name
     mean = sum(l["3.bias"].double() for l in layers) / C

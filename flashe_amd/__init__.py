@@ -9,6 +9,7 @@ from .cipher import FlasheCipher, aggregate          # noqa: F401
 from .engine import Engine, DeviceBuffer, DeviceVector, FlasheError  # noqa: F401
 from .block import FlasheClient, FlasheCohort, aggregate_sparse_uploads, dynamic_masking_choice, plan_cohort  # noqa: F401
 from .block import FlasheSparseCohort, plan_sparse_cohort  # noqa: F401
+from .block import cohort_admission_length, compact_cohort_admission_length, compact_cohort_blocks  # noqa: F401
 
 __all__ = ["FlasheCipher", "aggregate", "Engine", "DeviceBuffer", "DeviceVector", "FlasheError", "FlasheClient", "FlasheCohort", "plan_cohort", "aggregate_sparse_uploads", "dynamic_masking_choice",
            "FlasheSparseCohort", "plan_sparse_cohort"]

@@ -889,8 +889,31 @@ def cohort_admission_length(cu_count):
     return (2 * 16 * int(cu_count) - 1) * 256 + 1
 
 
+_COMPACT_COHORT_WIDTHS = (16, 20, 23, 24, 32)       # the widths compiled into the compact chain (FLASHE_FIXED32_WIDTHS, csrc/kernels.hip)
+
+
+def compact_cohort_blocks(n, int_bits, n_jobs):
+    """The AES blocks of an n-element vector at int_bits <= 64: every one of the n_jobs chunks (n % n_jobs of them one element longer) is
+    cut into blocks of m = 128 // int_bits elements of its own."""
+    m, (d, r) = 128 // int(int_bits), divmod(int(n), int(n_jobs))
+    return r * ((d + m) // m) + (int(n_jobs) - r) * ((d + m - 1) // m)
+
+
+def compact_cohort_admission_length(cu_count, int_bits, n_jobs):
+    """The shortest vector the summed compact chain takes uncut: 2 x 128 AES blocks for each of the chip's 16 x cu_count waves."""
+    need = 2 * 128 * 16 * int(cu_count)
+    lo, hi = 1, need * (128 // int(int_bits))           # (hi: need whole blocks in one chunk at the least)
+    while lo < hi:
+        mid = (lo + hi) // 2
+        if compact_cohort_blocks(mid, int_bits, n_jobs) >= need:
+            hi = mid
+        else:
+            lo = mid + 1
+    return lo
+
+
 def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, mask="double", num_clients=None, precompute=False, chain=True,
-                location_masks=False):
+                location_masks=False, compact=False, n_jobs=None):
     """The engine-free part of FlasheCohort.quantize_encrypt: checks that the clients' Weights describe one model (the same layer names
     in the same walking order with the same shapes: ValueError naming the client and the layer otherwise; a sparse upload -- a 'zzz'
     layer or location masks -- is a TypeError), lays out the shared layer table and the client-major draws, and picks the path:
@@ -899,11 +922,18 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
                       float64 for all clients or for none;
       "per-client"    precompute handles (and masks other than single / double): the clients' own steps, then aggregate;
       "staged-chain"  everything else: a quantise (+ batch) pass per client into plaintexts, then the summed batch encrypt.
+    compact=True (FlasheCohort(compact=True): uint32 ciphertexts at int_bits <= 32) chains through
+    flashe_quantize_encrypt_cohort_u32_dev instead: int_bits 16 / 20 / 23 / 24 / 32 in place of int_bits > 64, and a model of at least
+    compact_cohort_admission_length(cu_count, int_bits, n_jobs) values (n_jobs: the chunking of the counters, default cipher.N_JOBS)
+    and fewer than 2^32 in place of the length rule above; the other conditions and every fallback are the same.
     Touches no device.  The library's own answer stays the last word: a "cohort-chain" plan it declines runs "staged-chain"."""
     if len(weights_list) < 1:
         raise ValueError("a cohort needs at least one client's Weights")
     C = len(weights_list)
     num_clients = C if num_clients is None else int(num_clients)
+    if n_jobs is None:
+        from . import cipher as _cipher_mod
+        n_jobs = _cipher_mod.N_JOBS
     names = None
     shapes, f64 = [], []
     mixed = False
@@ -942,7 +972,9 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
         path, reason = PER_CLIENT, f"mask {mask!r}"
     elif mask != "double":
         path, reason = STAGED_CHAIN, "single mask: no stream is shared"
-    elif int_bits <= 64:
+    elif compact and int_bits not in _COMPACT_COHORT_WIDTHS:
+        path, reason = STAGED_CHAIN, f"int_bits {int_bits} is not a width of the compact chain {_COMPACT_COHORT_WIDTHS}"
+    elif not compact and int_bits <= 64:
         path, reason = STAGED_CHAIN, "int_bits <= 64"
     elif batch:
         path, reason = STAGED_CHAIN, "batched job"
@@ -950,7 +982,9 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
         path, reason = STAGED_CHAIN, f"more than {_COHORT_MAX_LINKS} clients"
     elif not chain:
         path, reason = STAGED_CHAIN, "FLASHE_CHAIN=0"
-    elif n < cohort_admission_length(cu_count) or n > 2 ** 32:
+    elif compact and (n >= 2 ** 32 or compact_cohort_blocks(n, int_bits, n_jobs) < 2 * 128 * 16 * int(cu_count)):
+        path, reason = STAGED_CHAIN, "the vector does not fill the chip uncut"
+    elif not compact and (n < cohort_admission_length(cu_count) or n > 2 ** 32):
         path, reason = STAGED_CHAIN, "the vector does not fill the chip uncut"
     elif mixed:
         path, reason = STAGED_CHAIN, "a layer is float64 for some clients only"
@@ -988,14 +1022,26 @@ class FlasheCohort(object):
     history, bit for bit -- but the clients' steps run as ONE chained launch where the chain admits the shape: it quantises every client's
     float model, encrypts with the PRF streams consecutive clients share (n_local + 1 instead of 2 n_local) and writes their sum and the
     decrypt mask, and one memory-bound pass turns the sum into the new float model.  All clients share one quantiser state (every
-    client's mean / std / alpha history derives from the same global model).  `path` of the result names the form that ran."""
+    client's mean / std / alpha history derives from the same global model).  `path` of the result names the form that ran.
+    compact=True (int_bits <= 32 on an engine whose compact_supported() is true; ValueError otherwise): every ciphertext and the sum are
+    compact DeviceVectors (uint32, elem_bytes 4) whatever path ran, and at int_bits 16 / 20 / 23 / 24 / 32 -- the widths the shipped jobs
+    run -- the chained launch goes from the floats to the uint32 ciphertexts and their sum (flashe_quantize_encrypt_cohort_u32_dev: 16
+    bytes moved per value and client instead of 36).  No decrypt mask is kept at these widths: decrypt_unquantize() decrypts the
+    sum."""
 
-    def __init__(self, args, first_idx, n_local, num_clients, prp_seed, device=0, stream=None):
+    def __init__(self, args, first_idx, n_local, num_clients, prp_seed, device=0, stream=None, compact=False):
         if n_local < 1 or first_idx < 0 or first_idx + n_local > num_clients:
             raise ValueError(f"clients {first_idx} .. {first_idx + n_local - 1} are not clients of a federation of {num_clients}")
         self.first_idx, self.n_local, self.num_clients = int(first_idx), int(n_local), int(num_clients)
         self.lead = _CohortLead(args, device=device, stream=stream)
         self.lead.create_cipher(self.first_idx, self.num_clients, prp_seed)
+        self.compact = bool(compact)
+        if self.compact:
+            if self.lead.int_bits > 32:
+                raise ValueError(f"compact=True needs int_bits <= 32, this job runs int_bits {self.lead.int_bits}")
+            ask = getattr(self.lead.cipher.engine, "compact_supported", None)
+            if ask is None or not ask():
+                raise ValueError("compact=True needs an engine with the uint32 entry points (the table PRF backend, FLASHE_CHAIN not 0)")
         self._clients = None
         if self.lead.precompute:                       # precomputed masks are per cipher: every client its own, one quantiser state
             self._clients = [self.lead]
@@ -1020,10 +1066,12 @@ class FlasheCohort(object):
 
     def plan(self, weights_list):
         """plan_cohort with this cohort's settings and the engine's CU count."""
+        from . import cipher as _cipher_mod
         ld = self.lead
         return plan_cohort(weights_list, ld.int_bits, ld.cipher.engine.cu_count, element_bits=ld.quantizer.element_bits, batch=bool(ld.batch),
                            mask=ld.cipher.masking_scheme, num_clients=self.num_clients, precompute=bool(ld.precompute),
-                           chain=os.environ.get("FLASHE_CHAIN", "1") != "0", location_masks=ld.cipher.masks is not None)
+                           chain=os.environ.get("FLASHE_CHAIN", "1") != "0", location_masks=ld.cipher.masks is not None, compact=self.compact,
+                           n_jobs=_cipher_mod.N_JOBS)
 
     def quantize_encrypt(self, weights_list, normalize=False, seeds=None):
         """One Weights per client (host arrays and / or framework float device tensors, as FlasheClient.quantize_encrypt takes them) ->
@@ -1136,8 +1184,12 @@ class FlasheCohort(object):
                     eng.numpy_random_dev(tot, out=du.ptr + 8 * at)
                 else:
                     du.upload_at(8 * at, np.random.random(tot))
-        cts = [DeviceVector(eng, n_elems) for _ in range(C)]
-        psum = DeviceVector(eng, n_elems)
+        if self.compact:
+            cts = [DeviceVector(eng, n_elems, 1, elem_bytes=4) for _ in range(C)]
+            psum = DeviceVector(eng, n_elems, 1, elem_bytes=4)
+        else:
+            cts = [DeviceVector(eng, n_elems) for _ in range(C)]
+            psum = DeviceVector(eng, n_elems)
         idxs = [self.first_idx + ci for ci in range(C)]
         whole = self.n_local == self.num_clients
         path = plan.path
@@ -1147,8 +1199,13 @@ class FlasheCohort(object):
                     for li, (st, _p, al, sh, _code, fl) in enumerate(tables[0])]
             srcs = [[t[1] for t in table] for table in tables]
             dts = [[t[4] for t in table] for table in tables]
-            dmask = DeviceVector(eng, n) if whole else None
-            if eng.quantize_encrypt_cohort_dev(c.iter_index, self.first_idx, n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du,
+            dmask = DeviceVector(eng, n) if whole and not self.compact else None
+            if self.compact:
+                # (no decrypt mask at these widths: the decrypt of the sum is 2 / m AES blocks per element)
+                if not eng.quantize_encrypt_cohort_u32_dev(c.iter_index, self.first_idx, n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du,
+                                                           [v.buf for v in cts], psum.buf):
+                    path = STAGED_CHAIN
+            elif eng.quantize_encrypt_cohort_dev(c.iter_index, self.first_idx, n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du,
                                                [v.buf for v in cts], psum.buf, dmask.buf if dmask is not None else None):
                 if dmask is not None:
                     ld._cohort_mask = (psum.ptr, dmask, c.iter_index, self.first_idx + C, self.first_idx)
@@ -1161,7 +1218,11 @@ class FlasheCohort(object):
             pts = [eng.alloc_vec(n_elems) for _ in range(C)]
             for ci in range(C):
                 eng.quantize_batch_tensors_dev(tables[ci], n, q.element_bits, field_bits, du.ptr + 8 * plan.draw_offsets[ci], n_elems, pts[ci])
-            eng.encrypt_batch_sum_dev(c.iter_index, idxs, scheme, n_elems, _cipher_mod.N_JOBS, pts, eng.limbs, [v.buf for v in cts], psum.buf)
+            if self.compact:
+                pts = [DeviceVector(eng, n_elems, 1, buf=pt).narrowed().buf for pt in pts]
+                eng.encrypt_batch_sum_u32_dev(c.iter_index, idxs, scheme, n_elems, _cipher_mod.N_JOBS, pts, [v.buf for v in cts], psum.buf)
+            else:
+                eng.encrypt_batch_sum_dev(c.iter_index, idxs, scheme, n_elems, _cipher_mod.N_JOBS, pts, eng.limbs, [v.buf for v in cts], psum.buf)
             keep += pts
         eng.hold(keep + [du])
         if ld.batch:
@@ -1190,7 +1251,8 @@ class FlasheCohort(object):
                 lw = _Layers({k: w._weights[k] for k in w.walking_order})
                 lw.walking_order = list(w.walking_order)
                 up = cl.quantize_encrypt(lw, device=True, normalize=normalize)
-                cts.append(up._weights[up.walking_order[0]])
+                ct = up._weights[up.walking_order[0]]
+                cts.append(cl.cipher._as_compact(ct) if self.compact else ct)
                 ld.shape_dict = cl.shape_dict
         finally:
             ld.cipher.idx = self.first_idx

@@ -1580,39 +1580,30 @@ int flashe_quantize_encrypt_tensors_dev(flashe_ctx *ctx, uint32_t iter, uint32_t
 // ---- a cohort of co-located clients: C float models -> C ciphertexts + their sum (+ the decrypt mask) in one chained launch ----
 // The shared layer table, the C x n_layers sources and their storage dtypes.  A source already in its row's compute type without SHIFT is
 // read where it lies; every other one goes through ONE stage pass (tensors.hip) into ctx scratch, all clients together.
-int flashe_quantize_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs,
-                                       const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
-                                       int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev, uint64_t *dmask_dev)
+// (the two entry points below share their argument checks -- cohort_check -- and their table and stage pass -- cohort_stage)
+static int cohort_check(flashe_ctx *ctx, const char *who, uint32_t first_idx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers,
+                        const void *const *src_dev, bool outs, int element_bits, const double *u_dev, std::vector<uint32_t> &idx)
 {
-    CHECK_CTX(ctx);
-    if (n_clients < 1) return fail(ctx, FLASHE_EINVAL, "flashe_quantize_encrypt_cohort_dev: n_clients must be >= 1");
-    if (!src_dev || !ct_dev || !sum_out_dev || (n && !u_dev)) return fail(ctx, FLASHE_EINVAL, "flashe_quantize_encrypt_cohort_dev: null argument");
+    if (n_clients < 1) return fail(ctx, FLASHE_EINVAL, "%s: n_clients must be >= 1", who);
+    if (!src_dev || !outs || (n && !u_dev)) return fail(ctx, FLASHE_EINVAL, "%s: null argument", who);
     if (element_bits < 1 || element_bits > 62 || element_bits > ctx->int_bits)
         return fail(ctx, FLASHE_EINVAL, "element_bits must be in [1, min(62, int_bits)], got %d", element_bits);
     if (reinterpret_cast<uintptr_t>(u_dev) & 7u) return fail(ctx, FLASHE_EINVAL, "u_dev must be 8-byte aligned");
     int rc = check_tensor_layers_shape(ctx, n, layers, n_layers);
     if (rc) return rc;
-    std::vector<uint32_t> idx(static_cast<size_t>(n_clients));
+    idx.resize(static_cast<size_t>(n_clients));
     for (int c = 0; c < n_clients; c++) {
         idx[c] = first_idx + static_cast<uint32_t>(c);
         if (idx[c] < first_idx) return fail(ctx, FLASHE_EINVAL, "the cohort's cipher indices wrap around 2^32");
     }
-    if ((rc = check_double_idx(ctx, FLASHE_SCHEME_DOUBLE, idx.data(), n_clients))) return rc;
-    for (int c = 0; c < n_clients; c++) {
-        if (!ct_dev[c]) return fail(ctx, FLASHE_EINVAL, "client %d: null ciphertext", c);
-        if ((rc = check_prf_args(ctx, 1, 1, n_jobs, ct_dev[c], nullptr, 0))) return rc;
-        if (ct_dev[c] == sum_out_dev || ct_dev[c] == dmask_dev) return fail(ctx, FLASHE_EINVAL, "client %d: the ciphertext aliases the sum or the mask", c);
-    }
-    if ((rc = check_sum_aligned(ctx, sum_out_dev))) return rc;
-    if (dmask_dev && (!aligned16(dmask_dev) || dmask_dev == sum_out_dev)) return fail(ctx, FLASHE_EINVAL, "dmask_dev must be 16-byte aligned and apart from the sum");
-    // the shapes the chained launch does not take, refused before anything is staged (launch_prf_cohort_sum's own rule is the final word)
-    {
-        const uint64_t waves = static_cast<uint64_t>(ctx->env.num_cus) * 16;
-        if (ctx->limbs != 2 || !ctx->env.use_chain || n_clients > 128 || (n + 255) / 256 < 2 * waves || n == 0 || ((n - 1) >> 32) ||
-            (ctx->env.prf_backend != PRF_AUTO && ctx->env.prf_backend != PRF_TABLE))
-            return fail(ctx, FLASHE_ENOTSUP, "flashe_quantize_encrypt_cohort_dev: not a shape of the chained cohort launch");
-    }
-    // rows of the device table (non-empty layers), the sources behind them, and what has to be staged first
+    return check_double_idx(ctx, FLASHE_SCHEME_DOUBLE, idx.data(), n_clients);
+}
+
+// rows of the device table (non-empty layers), the sources behind them, and ONE stage pass for every source that is not read in place
+static int cohort_stage(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
+                        const int32_t *src_dtype, int element_bits, CohortCodec &cc)
+{
+    int rc;
     std::vector<CodecLayer> tab;
     std::vector<int> row_of;
     for (int l = 0; l < n_layers; l++) {
@@ -1673,12 +1664,73 @@ int flashe_quantize_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uint32_t 
         if ((rc = upload_tab(ctx, ctx->tensor_tab, st, &stab))) return rc;
         HIP_TRY(ctx, launch_stage_layers(ctx->env, stab, static_cast<int>(st.size()), total));
     }
-    CohortCodec cc{};
     cc.layers = reinterpret_cast<const CodecLayer *>(blob_dev);
     cc.src = reinterpret_cast<const void *const *>(blob_dev + rows_bytes);
     cc.n_layers = static_cast<int>(n_tab);
+    return FLASHE_OK;
+}
+
+int flashe_quantize_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                       const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                       int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev, uint64_t *dmask_dev)
+{
+    CHECK_CTX(ctx);
+    static const char who[] = "flashe_quantize_encrypt_cohort_dev";
+    std::vector<uint32_t> idx;
+    int rc = cohort_check(ctx, who, first_idx, n_clients, n, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, idx);
+    if (rc) return rc;
+    for (int c = 0; c < n_clients; c++) {
+        if (!ct_dev[c]) return fail(ctx, FLASHE_EINVAL, "client %d: null ciphertext", c);
+        if ((rc = check_prf_args(ctx, 1, 1, n_jobs, ct_dev[c], nullptr, 0))) return rc;
+        if (ct_dev[c] == sum_out_dev || ct_dev[c] == dmask_dev) return fail(ctx, FLASHE_EINVAL, "client %d: the ciphertext aliases the sum or the mask", c);
+    }
+    if ((rc = check_sum_aligned(ctx, sum_out_dev))) return rc;
+    if (dmask_dev && (!aligned16(dmask_dev) || dmask_dev == sum_out_dev)) return fail(ctx, FLASHE_EINVAL, "dmask_dev must be 16-byte aligned and apart from the sum");
+    // the shapes the chained launch does not take, refused before anything is staged (launch_prf_cohort_sum's own rule is the final word)
+    {
+        const uint64_t waves = static_cast<uint64_t>(ctx->env.num_cus) * 16;
+        if (ctx->limbs != 2 || !ctx->env.use_chain || n_clients > 128 || (n + 255) / 256 < 2 * waves || n == 0 || ((n - 1) >> 32) ||
+            (ctx->env.prf_backend != PRF_AUTO && ctx->env.prf_backend != PRF_TABLE))
+            return fail(ctx, FLASHE_ENOTSUP, "%s: not a shape of the chained cohort launch", who);
+    }
+    CohortCodec cc{};
+    if ((rc = cohort_stage(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, cc))) return rc;
     const hipError_t e = launch_prf_cohort_sum(ctx->env, iter, n_clients, idx.data(), cc, u_dev, ct_dev, sum_out_dev, n, n_jobs, dmask_dev);
-    if (e == hipErrorNotSupported) return fail(ctx, FLASHE_ENOTSUP, "flashe_quantize_encrypt_cohort_dev: not a shape of the chained cohort launch");
+    if (e == hipErrorNotSupported) return fail(ctx, FLASHE_ENOTSUP, "%s: not a shape of the chained cohort launch", who);
+    HIP_TRY(ctx, e);
+    return FLASHE_OK;
+}
+
+// the same cohort in the compact layout at int_bits <= 32 (prf_small_cohort_kernel): uint32 ciphertexts and their uint32 sum, no decrypt mask
+int flashe_quantize_encrypt_cohort_u32_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                           const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                           int element_bits, const double *u_dev, uint32_t *const *ct_dev, uint32_t *sum_out_dev)
+{
+    CHECK_CTX(ctx);
+    static const char who[] = "flashe_quantize_encrypt_cohort_u32_dev";
+    std::vector<uint32_t> idx;
+    int rc = cohort_check(ctx, who, first_idx, n_clients, n, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, idx);
+    if (rc) return rc;
+    if (n_jobs == 0) return fail(ctx, FLASHE_EINVAL, "n_jobs must be >= 1");
+    for (int c = 0; c < n_clients; c++) {
+        if (!ct_dev[c]) return fail(ctx, FLASHE_EINVAL, "client %d: null ciphertext", c);
+        if (reinterpret_cast<uintptr_t>(ct_dev[c]) & 3u) return fail(ctx, FLASHE_EINVAL, "client %d: the ciphertext is not 4-byte aligned", c);
+        if (ct_dev[c] == sum_out_dev) return fail(ctx, FLASHE_EINVAL, "client %d: the ciphertext aliases the sum", c);
+    }
+    if (reinterpret_cast<uintptr_t>(sum_out_dev) & 3u) return fail(ctx, FLASHE_EINVAL, "sum_out_dev must be 4-byte aligned");
+    // the shapes the chained launch does not take, refused before anything is staged (launch_small_cohort_sum's own rule is the final word)
+    if (flashe_ctx_compact_layout(ctx) != 1 || !small_cohort_width(ctx->int_bits) || n_clients > 128 || n == 0 || n >= (1ull << 32))
+        return fail(ctx, FLASHE_ENOTSUP, "%s: not a shape of the chained compact cohort launch", who);
+    {
+        const uint64_t m = 128 / static_cast<uint64_t>(ctx->int_bits), d = n / n_jobs, r = n % n_jobs;
+        const uint64_t blocks = r * ((d + m) / m) + (n_jobs - r) * ((d + m - 1) / m);
+        if (blocks < 2ull * 128 * 16 * static_cast<uint64_t>(ctx->env.num_cus))
+            return fail(ctx, FLASHE_ENOTSUP, "%s: not a shape of the chained compact cohort launch", who);
+    }
+    CohortCodec cc{};
+    if ((rc = cohort_stage(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, cc))) return rc;
+    const hipError_t e = launch_small_cohort_sum(ctx->env, iter, n_clients, idx.data(), cc, u_dev, ct_dev, sum_out_dev, n, n_jobs);
+    if (e == hipErrorNotSupported) return fail(ctx, FLASHE_ENOTSUP, "%s: not a shape of the chained compact cohort launch", who);
     HIP_TRY(ctx, e);
     return FLASHE_OK;
 }

@@ -459,7 +459,7 @@ __device__ __forceinline__ uint64_t codec_quantize(const Codec &c, uint64_t k)
                                             static_cast<float>(c.den), c.u[k]);
 }
 
-// ---- the cohort front end (CohortCodec, prf_chain_cohort_kernel) ----
+// ---- the cohort front end (CohortCodec, prf_chain_cohort_kernel, prf_small_cohort_kernel) ----
 // The tables are written before the launch and only read by it: wave-uniform reads go through the scalar cache.
 #define FLASHE_CONSTANT(T, p) (reinterpret_cast<__attribute__((address_space(4))) T *>(reinterpret_cast<uintptr_t>(p)))
 // wave-uniform key: the table row that holds flat element `key` (the last row with start <= key), found with scalar loads
@@ -483,6 +483,38 @@ __device__ __forceinline__ uint64_t cohort_quantize_raw(uint64_t raw, bool f64, 
     return f64 ? quantize_one<double>(__longlong_as_double(static_cast<long long>(raw)), p0, p1, p2, u)
                : quantize_one<float>(__uint_as_float(static_cast<uint32_t>(raw)), static_cast<float>(p0), static_cast<float>(p1),
                                      static_cast<float>(p2), u);
+}
+// M consecutive values of a row for the lane that owns them (prf_small_cohort_kernel: the M = 128 / int_bits elements of its AES block): 4-byte
+// words -- float32 bits -- or 8-byte words -- float64 bits, draws -- in 16-byte accesses at the element's own alignment
+typedef uint32_t cohort_u32x4 __attribute__((ext_vector_type(4), aligned(4)));
+typedef uint32_t cohort_u32x2 __attribute__((ext_vector_type(2), aligned(4)));
+typedef uint64_t cohort_u64x2 __attribute__((ext_vector_type(2), aligned(8)));
+template <int M>
+__device__ __forceinline__ void cohort_load_run(const uint32_t *q, uint32_t (&v)[M])
+{
+    int t = 0;
+#pragma unroll
+    for (; t + 4 <= M; t += 4) {
+        const cohort_u32x4 x = *FLASHE_GLOBAL(const cohort_u32x4, q + t);
+        v[t] = x[0]; v[t + 1] = x[1]; v[t + 2] = x[2]; v[t + 3] = x[3];
+    }
+    if (M - t >= 2) {
+        const cohort_u32x2 x = *FLASHE_GLOBAL(const cohort_u32x2, q + t);
+        v[t] = x[0]; v[t + 1] = x[1];
+        t += 2;
+    }
+    if (t < M) v[t] = *FLASHE_GLOBAL(const uint32_t, q + t);
+}
+template <int M>
+__device__ __forceinline__ void cohort_load_run(const uint64_t *q, uint64_t (&v)[M])
+{
+    int t = 0;
+#pragma unroll
+    for (; t + 2 <= M; t += 2) {
+        const cohort_u64x2 x = *FLASHE_GLOBAL(const cohort_u64x2, q + t);
+        v[t] = x[0]; v[t + 1] = x[1];
+    }
+    if (t < M) v[t] = *FLASHE_GLOBAL(const uint64_t, q + t);
 }
 // the per-lane form for the few pairs that straddle a layer boundary: link's plaintext of flat element k
 __device__ __forceinline__ uint64_t cohort_quantize_lane(const CohortCodec &cc, int link, uint64_t k, double u)

@@ -95,6 +95,14 @@ struct CohortCodec {
 // rule and the same hipErrorNotSupported -- nothing launched -- contract; dmask_dev is optional.
 hipError_t launch_prf_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
                                  uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs, uint64_t *dmask_dev = nullptr);
+// The same cohort at int_bits <= 32 in the compact layout (prf_small_cohort_kernel): uint32 ciphertexts and their uint32 sum from the
+// floats, admitted where the summed compact chain is -- int_bits 16 / 20 / 23 / 24 / 32, the table PRF, the chained kernels, consecutive
+// idx below 2^32 - 1, at most kMaxLinks clients, 0 < n < 2^32 and at least 2 x 128 AES blocks (of 128 / int_bits elements, per the
+// chunking of n_jobs) for each of the chip's waves.  hipErrorNotSupported: nothing launched.
+hipError_t launch_small_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
+                                   uint32_t *const *out_dev, uint32_t *sum_out_dev, uint64_t n, uint32_t n_jobs);
+// is int_bits one of the widths compiled into that launch? (what a caller asks before it stages anything for it)
+bool small_cohort_width(int int_bits);
 // launch_prf_batch on elements [first, first + count) of the n-element vectors (pointers address element `first`): what a GPU that owns
 // an element slice of every client's vector runs
 hipError_t launch_prf_batch_range(const LaunchEnv &env, uint32_t iter, bool dbl, int n_vec, const uint32_t *idx, const uint64_t *const *in_dev,

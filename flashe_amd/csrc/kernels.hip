@@ -812,9 +812,11 @@ __device__ __forceinline__ void small_block_params(uint32_t B32, uint32_t nb1_32
 // uint32_t (the compact layout of the *_u32_dev entry points: half the bytes of a kernel that is bound by them)
 // sum / sum_first (summed chains, the tiles that do not take the direct path): sum[j] = out[j] for the chain's first output, += for the
 // later ones -- the element -> lane mapping of a tile is the same for every output, so each word is read and written by one lane only
-template <class ET>
+// PT (pt_of): the plaintexts come from a front end, pt_of->at(k) for range element k (CohortWalk), instead of the array `in`
+template <class ET, class PT = void>
 __device__ __forceinline__ void small_walk(uint32_t *row0, uint32_t lane, bool valid, int cnt, uint64_t j0, u128 D, const ET *in,
-                                           ET *out, uint64_t first, uint64_t range_end, const SmallParams &p, ET *sum = nullptr, bool sum_first = false)
+                                           ET *out, uint64_t first, uint64_t range_end, const SmallParams &p, ET *sum = nullptr, bool sum_first = false,
+                                           const PT *pt_of = nullptr)
 {
     const uint64_t valid_mask = __ballot(valid), partial_mask = __ballot(valid && cnt < p.m);
     if (__popcll(partial_mask) <= 1) {
@@ -842,7 +844,9 @@ __device__ __forceinline__ void small_walk(uint32_t *row0, uint32_t lane, bool v
                 if (sh) val |= static_cast<uint64_t>(w[2]) << (64u - sh);
                 const uint64_t j = e0 + x;
                 if (j >= first && j < range_end) {
-                    const uint64_t pt = in ? static_cast<uint64_t>(__builtin_nontemporal_load(in + (j - first))) : 0ull;
+                    uint64_t pt;
+                    if constexpr (std::is_void_v<PT>) pt = in ? static_cast<uint64_t>(__builtin_nontemporal_load(in + (j - first))) : 0ull;
+                    else pt = pt_of->at(j - first);
                     const uint64_t r = (pt + val) & p.mask_lo;
                     __builtin_nontemporal_store(static_cast<ET>(r), out + (j - first));
                     if (sum) sum[j - first] = static_cast<ET>((r + (sum_first ? 0ull : static_cast<uint64_t>(sum[j - first]))) & p.mask_lo);
@@ -855,7 +859,10 @@ __device__ __forceinline__ void small_walk(uint32_t *row0, uint32_t lane, bool v
             const uint64_t j = j0 + tt;
             if (j < first || j >= range_end) continue;
             const uint64_t val = extract64(D, p.b * tt);
-            const uint64_t r = ((in ? static_cast<uint64_t>(in[j - first]) : 0ull) + val) & p.mask_lo;
+            uint64_t pt;
+            if constexpr (std::is_void_v<PT>) pt = in ? static_cast<uint64_t>(in[j - first]) : 0ull;
+            else pt = pt_of->at(j - first);
+            const uint64_t r = (pt + val) & p.mask_lo;
             out[j - first] = static_cast<ET>(r);
             if (sum) sum[j - first] = static_cast<ET>((r + (sum_first ? 0ull : static_cast<uint64_t>(sum[j - first]))) & p.mask_lo);
         }
@@ -1031,6 +1038,57 @@ __device__ __forceinline__ DirectPt<M> direct32_load(const uint32_t *__restrict_
     return r;
 }
 
+// Where the plaintexts of a whole block come from when not from the chain's input arrays: block<M>(link, k, half) = the M words at range
+// element k of the chain's output `link` (half: 0 / 1, the lane's first / second block of the tile).
+// CohortDirect (prf_small_cohort_kernel): client `link`'s floats k .. k + M - 1 quantised with its draws (u[link], client-major as the wide
+// cohort kernel takes them) -- cohort_quantize_raw on the parameters of the table row that holds the whole half tile (row[half], found
+// once per tile: they stay in SGPRs; a half that straddles a row boundary walks, see CohortWalk).  The lane reads 4 M (float32) or 8 M bytes of the model and 8 M of draws and keeps M words: nothing but the M
+// plaintexts lives through the AES rounds that follow.
+struct CohortDirect {
+    const CohortCodec &cc;
+    const uint64_t *const *u;
+    int link0;
+    int row[2];
+    template <int M> __device__ __forceinline__ DirectPt<M> block(int link, uint64_t k, int half) const
+    {
+        DirectPt<M> r;
+        uint64_t ub[M];
+        cohort_load_run<M>(u[link] + k, ub);
+        const int lay = row[half];
+        const CodecLayer *L = cc.layers + lay;
+        const uint64_t ls = *FLASHE_CONSTANT(const uint64_t, &L->start);
+        const void *const xs = reinterpret_cast<const void *>(*FLASHE_CONSTANT(const uintptr_t, cc.src + static_cast<size_t>(link0 + link) * cc.n_layers + lay));
+        const bool f64 = *FLASHE_CONSTANT(const int, &L->x_is_f64) != 0;
+        const double p0 = *FLASHE_CONSTANT(const double, &L->p0), p1 = *FLASHE_CONSTANT(const double, &L->p1), p2 = *FLASHE_CONSTANT(const double, &L->p2);
+        if (f64) {
+            uint64_t raw[M];
+            cohort_load_run<M>(static_cast<const uint64_t *>(xs) + (k - ls), raw);
+#pragma unroll
+            for (int t = 0; t < M; t++)
+                r.v[t] = static_cast<uint32_t>(cohort_quantize_raw(raw[t], true, p0, p1, p2, __longlong_as_double(static_cast<long long>(ub[t]))));
+        } else {
+            uint32_t raw[M];
+            cohort_load_run<M>(static_cast<const uint32_t *>(xs) + (k - ls), raw);
+#pragma unroll
+            for (int t = 0; t < M; t++)
+                r.v[t] = static_cast<uint32_t>(cohort_quantize_raw(raw[t], false, p0, p1, p2, __longlong_as_double(static_cast<long long>(ub[t]))));
+        }
+        return r;
+    }
+};
+// the same front end element by element with the row looked up per lane (cohort_quantize_lane), for the tiles that walk: chunk ends, the
+// last partial tile, and the whole half tiles that straddle a row boundary (M unrolled per-lane lookups in the lane that owns a block
+// cost the kernel its register budget; such tiles are at most one per layer and chunk).  u = the link's draws
+struct CohortWalk {
+    const CohortCodec &cc;
+    const uint64_t *u;
+    int link;
+    __device__ __forceinline__ uint64_t at(uint64_t k) const
+    {
+        return cohort_quantize_lane(cc, link, k, __longlong_as_double(static_cast<long long>(*FLASHE_GLOBAL(const uint64_t, u + k))));
+    }
+};
+
 // out[k + t] = (pt[t] + slot_t(add) - slot_t(minus)) mod 2^B for the M = 128 / B elements of the lane's block; `single`: no minus stream
 // (acc: the running sum of the chain's outputs for this block, kept in registers -- a summed chain)
 template <int B>
@@ -1111,11 +1169,11 @@ __device__ __forceinline__ void direct32_put(uint32_t *__restrict__ q, const uin
 // 16: 0.2234 -> 0.2156, 23 / 24 / 32: within 1 %.  Measured and dropped (tests/perf/experiments/r06_small_chain_fast32_pipelined.patch):
 // the streams software-pipelined against each other (the next stream's first lookups issued before this stream's outputs): 0.2769
 // against 0.2740 at int_bits 20, 127 VGPRs -- what is left between two steps is not what holds these kernels back.
-template <int B, bool SINGLE>
+template <int B, bool SINGLE, class SRC = void>
 __device__ __forceinline__ void small_chain_fast32(const RoundKeys &rk, const LaneRegs lr, const uint32_t *pre_lds, int sbase, int n_streams,
                                                    const uint64_t *const *in_tab, uint64_t *const *out_tab, const CtrVar &xA, const CtrVar &xB,
                                                    uint64_t kA, uint64_t kB, uint32_t *sum32, bool prio,
-                                                   const uint32_t *__restrict__ te4, bool uni, uint32_t x3A, uint32_t x3B)
+                                                   const uint32_t *__restrict__ te4, bool uni, uint32_t x3A, uint32_t x3B, const SRC *src = nullptr)
 {
     constexpr int M = 128 / B;
     constexpr uint32_t mask = B >= 32 ? 0xffffffffu : ((1u << (B & 31)) - 1u);
@@ -1157,9 +1215,14 @@ __device__ __forceinline__ void small_chain_fast32(const RoundKeys &rk, const La
         const int link = SINGLE ? c : c - 1;
         DirectPt<M> dA{}, dB{};
         if (link >= 0) {
-            const uint32_t *in = reinterpret_cast<const uint32_t *>(in_tab[link]);
-            dA = direct32_load<M>(in, kA);
-            dB = direct32_load<M>(in, kB);
+            if constexpr (std::is_void_v<SRC>) {
+                const uint32_t *in = reinterpret_cast<const uint32_t *>(in_tab[link]);
+                dA = direct32_load<M>(in, kA);
+                dB = direct32_load<M>(in, kB);
+            } else {                                     // (a front end: the plaintexts are computed here, before the rounds)
+                dA = src->template block<M>(link, kA, 0);
+                dB = src->template block<M>(link, kB, 1);
+            }
         }
         uint32_t s[2][4];
         if (uni) {
@@ -1199,226 +1262,24 @@ __device__ __forceinline__ u128 slot_diff(u128 prev, u128 cur, u128 top, int b)
 template <bool PAIR, class ET = uint64_t, int B = 0>
 __global__ __launch_bounds__(kSmallThreads) void prf_small_chain_kernel(const RoundKeys rk, const SmallChainTable tb, int n_chains, const SmallParams p)
 {
-    static_assert(B == 0 || (PAIR && ((sizeof(ET) == 4 && B <= 32) || (sizeof(ET) == 8 && B == 64))), "compile-time widths: the paired kernel, compact layout or int_bits 64");
-    constexpr uint32_t WAVES = kSmallThreads / 64, TILE = PAIR ? 128u : 64u;
-    constexpr int MB = B ? 128 / B : 1;
-    __shared__ uint32_t tab[kTabWords];
-    __shared__ uint32_t scratch[(kSmallThreads / 64) * 256 + 8];
-    __shared__ __attribute__((aligned(16))) uint32_t pre_lds[(kMaxLinks + kMaxChains) * 4];
-    __shared__ uint64_t d_tlo[kMaxChains], d_cend[kMaxChains];
-    const uint32_t iter = p.iter + p.te0[kIterShiftWord];
-    fill_tables(tab, p.te0);
-    const LaneRegs lr = lane_regs(tab);
-    {
-        const int last = n_chains - 1;
-        const int n_streams = tb.sbase[last] + tb.len[last] + ((tb.flags[last] & 1) ? 0 : 1);
-        for (int s = threadIdx.x; s < n_streams; s += kSmallThreads) {
-            const CtrPrefix c = ctr_prefix(rk, lr, iter, tb.idx[s], 0u);          // n < 2^32 (host-checked): the high counter word is 0
-            *reinterpret_cast<uint4 *>(pre_lds + 4 * s) = make_uint4(c.u[0], c.u[1], c.u[2], c.u[3]);
-        }
-        if (threadIdx.x < static_cast<unsigned>(n_chains)) {                          // this workgroup's tiles of every chain (see prf_chain_kernel)
-            const int i = threadIdx.x;
-            const uint64_t Wt = tb.wend[last], cw = i ? tb.wend[i - 1] : 0;
-            const uint32_t w = tb.len[i] + ((tb.flags[i] & 1) ? 0u : 1u);
-            uint64_t a, b, T;
-            if (Wt <= 0xffffffffull && gridDim.x <= 0xffffu) {
-                const uint32_t W32 = static_cast<uint32_t>(Wt), G = gridDim.x, g = blockIdx.x, c32 = static_cast<uint32_t>(cw);
-                const uint32_t q = W32 / G, r = W32 % G;
-                const uint32_t lo = q * g + r * g / G, hi = q * (g + 1) + r * (g + 1) / G;
-                T = (static_cast<uint32_t>(tb.wend[i]) - c32) / w;
-                a = lo > c32 ? (lo - c32 + w - 1) / w : 0; b = hi > c32 ? (hi - c32 + w - 1) / w : 0;
-            } else {
-                const uint64_t G = gridDim.x, g = blockIdx.x;
-                const uint64_t lo = Wt / G * g + (Wt % G) * g / G, hi = Wt / G * (g + 1) + (Wt % G) * (g + 1) / G;
-                T = (tb.wend[i] - cw) / w;
-                a = lo > cw ? (lo - cw + w - 1) / w : 0; b = hi > cw ? (hi - cw + w - 1) / w : 0;
-            }
-            if (a > T) a = T;
-            if (b > T) b = T;
-            d_tlo[i] = a; d_cend[i] = b - a;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint64_t acc = 0;
-            for (int i = 0; i < n_chains; i++) { acc += d_cend[i]; d_cend[i] = acc; }
-        }
-        __syncthreads();
-    }
-    const uint64_t J = p.n_jobs, d = p.n / J, r = p.n % J, m64 = static_cast<uint64_t>(p.m);
-    const uint32_t nb1_32 = static_cast<uint32_t>((d + 1 + m64 - 1) / m64), nb0_32 = static_cast<uint32_t>(d ? (d + m64 - 1) / m64 : 0);
-    const uint32_t d32 = static_cast<uint32_t>(d), r32 = static_cast<uint32_t>(r), m32 = static_cast<uint32_t>(p.m);
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
-    uint32_t *row0 = scratch + wave * 256;
-    const u128 top = (static_cast<u128>(p.top_hi) << 64) | p.top_lo;
-    const bool direct = p.m <= 4 && !p.no_direct;
-    const bool walk32 = p.b <= 32 && !direct && p.no_direct != 2;     // (FLASHE_SMALL_DIRECT=2: A/B knob, general walk everywhere)
-    const uint32_t wblk0 = lane / m32, wo0 = (lane - wblk0 * m32) * static_cast<uint32_t>(p.b);       // m >= 5 measured 35-150 % slower than the staged walk (40 .. 64-byte lane stride)      // m = 3, 4 measured: 8-byte accesses at a 24 / 32-byte lane stride lose 60-130 % against the staged walk
-    const uint64_t Ng = uniform64(d_cend[n_chains - 1]);
-    int cur = 0;
-    uint64_t cbeg = 0;
-    for (uint64_t q = wave; q < Ng; q += WAVES) {
-        while (q >= uniform64(d_cend[cur])) cbeg = uniform64(d_cend[cur++]);
-        const uint64_t first = tb.first[cur], range_end = first + tb.count[cur], blk_count = tb.blk_count[cur];
-        const uint64_t Bw = (uniform64(d_tlo[cur]) + (q - cbeg)) * TILE;             // the tile's first block (chain-local)
-        const int link0 = tb.link0[cur], sbase = tb.sbase[cur];
-        const bool single = tb.flags[cur] & 1;
-        const int n_streams = tb.len[cur] + (single ? 0 : 1);
-        // per-lane block(s): chunk arithmetic and the counter-dependent quarter of round 1, once for all streams
-        const bool vA = Bw + lane < blk_count, vB = PAIR && Bw + 64u + lane < blk_count;
-        uint64_t j0A = 0, j0B = 0;
-        int cntA = 0, cntB = 0;
-        uint32_t ctrA = 0, ctrB = 0;
-        small_block_params(static_cast<uint32_t>(tb.blk_first[cur] + (vA ? Bw + lane : 0)), nb1_32, nb0_32, d32, r32, m32, p, &j0A, &cntA, &ctrA);
-        if (PAIR) small_block_params(static_cast<uint32_t>(tb.blk_first[cur] + (vB ? Bw + 64u + lane : 0)), nb1_32, nb0_32, d32, r32, m32, p, &j0B, &cntB, &ctrB);
-        const CtrVar xA = ctr_var(rk, lr, ctrA);
-        CtrVar xB{};
-        if (PAIR) xB = ctr_var(rk, lr, ctrB);
-        // the common tile: 64 whole blocks, all inside the range -> their 64 m elements are one contiguous run
-        uint64_t e0A = 0, e0B = 0;
-        bool fastA = false, fastB = false;
-        if (walk32) {
-            e0A = uniform64(j0A);
-            fastA = __ballot(vA && cntA == p.m) == ~0ull && e0A >= first && e0A + 64u * m64 <= range_end;
-            if (PAIR) {
-                e0B = uniform64(j0B);
-                fastB = __ballot(vB && cntB == p.m) == ~0ull && e0B >= first && e0B + 64u * m64 <= range_end;
-            }
-        }
-        // (int_bits 64 at compile time: the lane's block is whole and inside the range -> one 16-byte access)
-        const bool wholeA = B == 64 && vA && cntA == 2 && j0A >= first && j0A + 2 <= range_end;
-        const bool wholeB = B == 64 && vB && cntB == 2 && j0B >= first && j0B + 2 <= range_end;
-        u128 prevA = 0, prevB = 0;
-        // (a summed chain, compile-time width: the blocks' running sums; irregular tiles keep theirs in memory, see small_walk)
-        uint32_t accA[MB], accB[MB];
-#pragma unroll
-        for (int t = 0; t < MB; t++) { accA[t] = 0u; accB[t] = 0u; }
-        uint32_t *const sum32 = B != 0 && B != 64 ? reinterpret_cast<uint32_t *>(tb.sum_out[cur]) : nullptr;
-        if constexpr (PAIR && B != 0 && B != 64) {
-            if (fastA && fastB) {                                  // (wave-uniform) both blocks of every lane whole and inside the range
-                // the lanes' counters are consecutive inside a chunk; where a set of sixty-four does not cross a multiple of 256 its
-                // bytes 1 .. 3 are the wave's (three sets of four in the chunks whose first counter is not a multiple of 64).  The second
-                // counter shortcut only on short chains: on the ten-client chain its scalar loads at the head of every step cost more than
-                // it saves (tests/perf/experiments/README.md)
-                constexpr int kU2MaxStreams = 2;
-                const uint32_t bA = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(ctrA)), bB = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(ctrB));
-                const bool uni = n_streams <= kU2MaxStreams && __ballot(ctrA - bA == lane && ctrB - bB == lane) == ~0ull &&
-                                 (bA & 255u) <= 192u && (bB & 255u) <= 192u;
-                if (single) small_chain_fast32<B, true>(rk, lr, pre_lds, sbase, n_streams, tb.in + link0, tb.out + link0, xA, xB, j0A - first, j0B - first, sum32, p.swp_prio != 0,
-                                                        p.te0, uni, bA ^ rk.w[3], bB ^ rk.w[3]);
-                else small_chain_fast32<B, false>(rk, lr, pre_lds, sbase, n_streams, tb.in + link0, tb.out + link0, xA, xB, j0A - first, j0B - first, sum32, p.swp_prio != 0,
-                                                  p.te0, uni, bA ^ rk.w[3], bB ^ rk.w[3]);
-                continue;
-            }
-        }
-        if (PAIR) {
-            // two blocks per lane on the same prefix, one stream per step
-            for (int c = 0; c < n_streams; c++) {
-                const CtrPrefix pre = load_prefix(pre_lds, sbase + c);
-                const int link = single ? c : c - 1;
-                WalkPt ptA{}, ptB{};
-                DirectPt<MB> dA{}, dB{};
-                u64x2 qA = {0ull, 0ull}, qB = {0ull, 0ull};
-                if (B == 64) {
-                    if (link >= 0 && wholeA) qA = direct64_load(tb.in[link0 + link], j0A - first);
-                    if (link >= 0 && wholeB) qB = direct64_load(tb.in[link0 + link], j0B - first);
-                } else if (B) {
-                    if (link >= 0 && fastA) dA = direct32_load<MB>(reinterpret_cast<const uint32_t *>(tb.in[link0 + link]), j0A - first);
-                    if (link >= 0 && fastB) dB = direct32_load<MB>(reinterpret_cast<const uint32_t *>(tb.in[link0 + link]), j0B - first);
-                } else {
-                    if (link >= 0 && fastA) ptA = small_walk32_load(reinterpret_cast<const ET *>(tb.in[link0 + link]), e0A, first, lane, m32);
-                    if (link >= 0 && fastB) ptB = small_walk32_load(reinterpret_cast<const ET *>(tb.in[link0 + link]), e0B, first, lane, m32);
-                }
-                uint32_t s[2][4];
-                ctr_round1(pre, xA, s[0]);
-                ctr_round1(pre, xB, s[1]);
-                aes256_rounds<2, 2>(rk, lr, s, p.swp_prio != 0);
-                const u128 SA = words_to_u128(s[0]), SB = words_to_u128(s[1]);
-                if (link >= 0) {
-                    const uint64_t *in = tb.in[link0 + link];
-                    uint64_t *out = tb.out[link0 + link];
-                    const ET *ein = reinterpret_cast<const ET *>(in);
-                    ET *eout = reinterpret_cast<ET *>(out);
-                    if (B == 64) {
-                        if constexpr (B == 64) {
-                            if (wholeA) direct64_store(out, j0A - first, qA, single ? SA : prevA, SA, single);
-                            else small_direct(vA, cntA, j0A, single ? SA : slot_diff(prevA, SA, top, 64), in, out, first, range_end, p);
-                            if (wholeB) direct64_store(out, j0B - first, qB, single ? SB : prevB, SB, single);
-                            else small_direct(vB, cntB, j0B, single ? SB : slot_diff(prevB, SB, top, 64), in, out, first, range_end, p);
-                        }
-                        prevA = SA; prevB = SB;
-                        continue;
-                    }
-                    if (B) {
-                        // compile-time width: whole tiles element by element from the two streams' slots, everything else the general walk
-                        if constexpr (B != 0 && B != 64) {
-                            uint32_t *o32 = reinterpret_cast<uint32_t *>(out);
-                            ET *const sm = reinterpret_cast<ET *>(sum32);
-                            if (fastA) direct32_store<B>(o32, j0A - first, dA, single ? SA : prevA, SA, single, accA);
-                            else small_walk(row0, lane, vA, cntA, j0A, single ? SA : slot_diff(prevA, SA, top, p.b), ein, eout, first, range_end, p, sm, link == 0);
-                            if (fastB) direct32_store<B>(o32, j0B - first, dB, single ? SB : prevB, SB, single, accB);
-                            else small_walk(row0, lane, vB, cntB, j0B, single ? SB : slot_diff(prevB, SB, top, p.b), ein, eout, first, range_end, p, sm, link == 0);
-                        }
-                        prevA = SA; prevB = SB;
-                        continue;
-                    }
-                    // per slot (previous - current) mod 2^b: the previous stream is this client's add stream, the current its minus stream
-                    const u128 DA = single ? SA : slot_diff(prevA, SA, top, p.b);
-                    const u128 DB = single ? SB : slot_diff(prevB, SB, top, p.b);
-                    if (direct) {                                  // (never with the compact layout: the host turns `direct` off)
-                        small_direct(vA, cntA, j0A, DA, in, out, first, range_end, p);
-                        small_direct(vB, cntB, j0B, DB, in, out, first, range_end, p);
-                    } else {
-                        if (fastA) small_walk32(row0, lane, e0A, DA, ptA, ein, eout, first, p, wblk0, wo0);
-                        else small_walk(row0, lane, vA, cntA, j0A, DA, ein, eout, first, range_end, p);
-                        if (fastB) small_walk32(row0, lane, e0B, DB, ptB, ein, eout, first, p, wblk0, wo0);
-                        else small_walk(row0, lane, vB, cntB, j0B, DB, ein, eout, first, range_end, p);
-                    }
-                }
-                prevA = SA; prevB = SB;
-            }
-            if constexpr (B != 0 && B != 64) {
-                if (sum32) {                                         // the sums of the blocks that took the direct path, one store each
-                    constexpr uint32_t bmask = B >= 32 ? 0xffffffffu : ((1u << (B & 31)) - 1u);
-                    if (fastA) direct32_put<MB>(sum32 + (j0A - first), accA, bmask);
-                    if (fastB) direct32_put<MB>(sum32 + (j0B - first), accB, bmask);
-                }
-            }
-        } else {
-            // one block per lane, TWO STREAMS per step (short launches: half the dependent AES depth per wave; an odd stream count
-            // computes its last stream twice)
-            for (int c = 0; c < n_streams; c += 2) {
-                const bool has1 = c + 1 < n_streams;
-                const CtrPrefix pre0 = load_prefix(pre_lds, sbase + c), pre1 = load_prefix(pre_lds, sbase + (has1 ? c + 1 : c));
-                const int l0 = single ? c : c - 1;
-                WalkPt pt0{}, pt1{};
-                if (fastA && l0 >= 0) pt0 = small_walk32_load(reinterpret_cast<const ET *>(tb.in[link0 + l0]), e0A, first, lane, m32);
-                if (fastA && has1) pt1 = small_walk32_load(reinterpret_cast<const ET *>(tb.in[link0 + l0 + 1]), e0A, first, lane, m32);
-                uint32_t s[2][4];
-                ctr_round1(pre0, xA, s[0]);
-                ctr_round1(pre1, xA, s[1]);
-                aes256_rounds<2, 2>(rk, lr, s, true);
-                const u128 S0 = words_to_u128(s[0]), S1 = words_to_u128(s[1]);
-                if (l0 >= 0) {
-                    const u128 D = single ? S0 : slot_diff(prevA, S0, top, p.b);
-                    const ET *ein = reinterpret_cast<const ET *>(tb.in[link0 + l0]);
-                    ET *eout = reinterpret_cast<ET *>(tb.out[link0 + l0]);
-                    if (direct) small_direct(vA, cntA, j0A, D, tb.in[link0 + l0], tb.out[link0 + l0], first, range_end, p);
-                    else if (fastA) small_walk32(row0, lane, e0A, D, pt0, ein, eout, first, p, wblk0, wo0);
-                    else small_walk(row0, lane, vA, cntA, j0A, D, ein, eout, first, range_end, p);
-                }
-                if (has1) {
-                    const u128 D = single ? S1 : slot_diff(S0, S1, top, p.b);
-                    const ET *ein = reinterpret_cast<const ET *>(tb.in[link0 + l0 + 1]);
-                    ET *eout = reinterpret_cast<ET *>(tb.out[link0 + l0 + 1]);
-                    if (direct) small_direct(vA, cntA, j0A, D, tb.in[link0 + l0 + 1], tb.out[link0 + l0 + 1], first, range_end, p);
-                    else if (fastA) small_walk32(row0, lane, e0A, D, pt1, ein, eout, first, p, wblk0, wo0);
-                    else small_walk(row0, lane, vA, cntA, j0A, D, ein, eout, first, range_end, p);
-                }
-                prevA = has1 ? S1 : S0;
-            }
-        }
-    }
+    constexpr bool COHORT = false;
+    const CohortCodec cc{};
+#include "prf_small_chain_body.inc"
+}
+
+// COHORT: the summed compact chain of a cohort of co-located clients at the widths the shipped jobs run (int_bits <= 32), every output with
+// the quantising front end of prf_chain_cohort_kernel -- one launch takes C float models to their C uint32 ciphertexts and their sum, and
+// no integer plaintext exists in HBM (per value and client 4 + 8 bytes read and 4 written, against 36 through a quantise pass and the
+// one-limb encrypt).  The lane that owns a block quantises its M = 128 / B values BEFORE the stream's AES rounds, so only the M plaintext
+// words live through them, as the loaded plaintexts of the plain chain do.  A separate kernel: prf_small_chain_kernel's instantiations
+// keep their code objects.
+template <int B>
+__global__ __launch_bounds__(kSmallThreads) void prf_small_cohort_kernel(const RoundKeys rk, const SmallChainTable tb, int n_chains, const SmallParams p,
+                                                                          const CohortCodec cc)
+{
+    constexpr bool PAIR = true, COHORT = true;
+    using ET = uint32_t;
+#include "prf_small_chain_body.inc"
 }
 
 
@@ -2383,6 +2244,14 @@ hipError_t launch_small_reduce_decrypt(const LaunchEnv &env, uint32_t iter, uint
     return hipGetLastError();
 }
 
+// the measured table of launch_small_chains below (`longest`: the outputs of the launch's longest chain; elem32: the compact layout)
+static int small_swp_prio(const LaunchEnv &env, const SmallParams &p, int longest)
+{
+    int prio = env.elem32 ? (!p.no_fixed_width && fixed32_width(env.b) && (env.b != 20 || longest <= 1)) : (p.m <= 4 && !p.no_direct);
+    { static const int v = FLASHE_TUNE_ENV("FLASHE_SMALL_PRIO") ? atoi(FLASHE_TUNE_ENV("FLASHE_SMALL_PRIO")) : -1; if (v >= 0) prio = v; }
+    return prio;
+}
+
 // b <= 64 form of launch_prf_chains.  hipErrorNotSupported (-> job-table kernel) for what this kernel does not carry: a fused
 // codec, vectors of 2^32 elements or more.
 static hipError_t launch_small_chains(const LaunchEnv &env, uint32_t iter, int n_chains, const PrfChain *chains, uint64_t n, uint32_t n_jobs)
@@ -2405,8 +2274,7 @@ static hipError_t launch_small_chains(const LaunchEnv &env, uint32_t iter, int n
     // a chain of two streams: -9 %, 0.0616 -> 0.0562 ms) and not the staged walk of the one-limb layout at m >= 5 (+15 %)
     int longest = 0;
     for (int i = 0; i < n_chains; i++) longest = std::max(longest, chains[i].n_out);
-    p.swp_prio = env.elem32 ? (!p.no_fixed_width && fixed32_width(env.b) && (env.b != 20 || longest <= 1)) : (p.m <= 4 && !p.no_direct);
-    { static const int v = FLASHE_TUNE_ENV("FLASHE_SMALL_PRIO") ? atoi(FLASHE_TUNE_ENV("FLASHE_SMALL_PRIO")) : -1; if (v >= 0) p.swp_prio = v; }
+    p.swp_prio = small_swp_prio(env, p, longest);
     struct Piece { const PrfChain *ch; int l0, l1; uint64_t blk_first, blk_count; };
     std::vector<Piece> pieces;
     uint64_t total_blocks = 0;
@@ -2487,6 +2355,51 @@ static hipError_t launch_small_chains(const LaunchEnv &env, uint32_t iter, int n
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+bool small_cohort_width(int int_bits) { return int_bits <= 32 && fixed32_width(int_bits); }
+
+// The summed compact chain over whole vectors with the quantising front end per output (prf_small_cohort_kernel): the admission of the
+// summed chain of launch_small_chains -- a compiled-in width, one uncut run of consecutive clients, enough AES blocks for the paired
+// kernel -- and launch_prf_cohort_sum's contract: hipErrorNotSupported = nothing launched.
+hipError_t launch_small_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
+                                   uint32_t *const *out_dev, uint32_t *sum_out_dev, uint64_t n, uint32_t n_jobs)
+{
+    if (n == 0 || n >= (1ull << 32) || n_vec <= 0 || n_jobs == 0) return hipErrorNotSupported;
+    if (!env.use_chain || !small_cohort_width(env.b) || env.codec || n_vec > kMaxLinks || !sum_out_dev || !u_dev || cc.n_layers < 1) return hipErrorNotSupported;
+    if (env.prf_backend != PRF_AUTO && env.prf_backend != PRF_TABLE) return hipErrorNotSupported;
+    for (int v = 1; v < n_vec; v++) if (idx[v] != idx[v - 1] + 1u) return hipErrorNotSupported;
+    if (idx[n_vec - 1] == 0xffffffffu) return hipErrorNotSupported;
+    for (int v = 0; v < n_vec; v++) if (!out_dev[v]) return hipErrorNotSupported;
+    LaunchEnv e32 = env;
+    e32.elem32 = 1;
+    SmallParams p = small_params_of(e32, iter, n, n_jobs);
+    if (p.no_fixed_width) return hipErrorNotSupported;
+    p.no_direct = 1;                          // (the compact layout walks its rows: launch_small_chains)
+    p.swp_prio = small_swp_prio(e32, p, n_vec);
+    const uint64_t blocks = block_of(n - 1, n, n_jobs, p.m) + 1;
+    const uint64_t waves = static_cast<uint64_t>(env.num_cus) * (kSmallThreads / 64);
+    if (blocks < 2 * 128 * waves) return hipErrorNotSupported;          // (launch_small_chains' `pair`: a summed chain is never cut)
+    SmallChainTable tb{};
+    tb.first[0] = 0; tb.count[0] = n; tb.blk_first[0] = 0; tb.blk_count[0] = blocks;
+    tb.len[0] = static_cast<uint8_t>(n_vec);
+    for (int s = 0; s < n_vec; s++) tb.idx[s] = idx[s];
+    tb.idx[n_vec] = idx[n_vec - 1] + 1u;
+    for (int l = 0; l < n_vec; l++) {
+        tb.in[l] = reinterpret_cast<const uint64_t *>(u_dev + static_cast<uint64_t>(l) * n);       // the link's draws (CohortDirect, CohortWalk)
+        tb.out[l] = reinterpret_cast<uint64_t *>(out_dev[l]);
+    }
+    tb.sum_out[0] = reinterpret_cast<uint64_t *>(sum_out_dev);
+    const uint64_t tiles = (blocks + 127) / 128, cus = static_cast<uint64_t>(env.num_cus);
+    tb.wend[0] = tiles * static_cast<uint64_t>(n_vec + 1);
+    const int grid = static_cast<int>(tiles < cus ? tiles : cus);
+    switch (env.b) {
+#define FLASHE_FIXED32(B) case B: hipLaunchKernelGGL((prf_small_cohort_kernel<B>), dim3(grid), dim3(kSmallThreads), 0, env.stream, env.rk, tb, 1, p, cc); break;
+        FLASHE_FIXED32_WIDTHS(FLASHE_FIXED32)
+#undef FLASHE_FIXED32
+    default: return hipErrorNotSupported;
+    }
+    return hipGetLastError();
 }
 
 hipError_t launch_aes_blocks(const LaunchEnv &env, uint32_t nblk, const uint32_t *in_words_dev, uint32_t *out_words_dev)

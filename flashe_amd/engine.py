@@ -640,6 +640,22 @@ class Engine:
         self._check(rc)
         return True
 
+    def quantize_encrypt_cohort_u32_dev(self, it, first_idx, n, n_jobs, layers, srcs, dtypes, element_bits, u, cts, sum_out):
+        """quantize_encrypt_cohort_dev in the compact layout (flashe_quantize_encrypt_cohort_u32_dev, int_bits 16 / 20 / 23 / 24 / 32): cts and
+        sum_out are uint32 vectors of n elements, there is no decrypt mask.  Returns False -- nothing was launched -- when the library
+        declines the shape (FLASHE_ENOTSUP: the caller quantises per client and calls encrypt_batch_sum_u32_dev), True otherwise."""
+        arr, nl = self._tensor_layers(layers)
+        C = len(srcs)
+        ps = (c_vp * max(C * nl, 1))(*[int(p) if p else None for row in srcs for p in row])
+        pd = (ctypes.c_int32 * max(C * nl, 1))(*[int(d) for row in dtypes for d in row])
+        pc, _k = self._ptr_array(cts)
+        rc = self._lib.flashe_quantize_encrypt_cohort_u32_dev(self._h, it, int(first_idx), C, int(n), n_jobs, arr, nl, ps, pd, element_bits,
+                                                              self._ptr(u), pc, self._ptr(sum_out))
+        if rc == _lib.ENOTSUP:
+            return False
+        self._check(rc)
+        return True
+
     def combine_unquantize_model_dev(self, n, inp, add, minus, layers, element_bits, num_clients, out):
         """out = unquantise((inp + add - minus) mod 2^b) as float64 over a flattened model, one memory-bound pass (add / minus: device
         vectors or None); layers as for decrypt_unquantize_model_dev."""

@@ -72,7 +72,8 @@ typedef struct flashe_ctx flashe_ctx;
  *      ctx's precomputed masks); FLASHE_ENOTSUP + flashe_quantize_encrypt_cohort_dev (a cohort of co-located clients: C float models
  *      to C ciphertexts, their sum and the decrypt mask in one chained launch) and flashe_combine_unquantize_model_dev (the codec back
  *      end over a sum and caller-held masks); flashe_sparsify_cohort_tensors_dev and flashe_quantize_cohort_dev (a cohort of sparse-job
- *      clients: C models sparsified in one set of launches, their compact layers quantised in one launch) */
+ *      clients: C models sparsified in one set of launches, their compact layers quantised in one launch);
+ *      flashe_quantize_encrypt_cohort_u32_dev (the cohort's chained launch in the compact layout, int_bits 16 / 20 / 23 / 24 / 32) */
 #define FLASHE_ABI_VERSION 4
 int flashe_abi_version(void);
 int flashe_device_count(int *count);
@@ -666,6 +667,19 @@ int flashe_quantize_encrypt_tensors_dev(flashe_ctx *ctx, uint32_t iter, uint32_t
 int flashe_quantize_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs,
                                        const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
                                        int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev, uint64_t *dmask_dev);
+/* The same cohort at the widths the reference's jobs ship, in the compact layout (new): int_bits 16 / 20 / 23 / 24 / 32, ct_dev[c] and
+ * sum_out_dev are uint32 arrays of n elements (4-byte aligned, the values of flashe_quantize_encrypt_tensors_dev of client c and their
+ * sum mod 2^b, as the other *_u32_dev entry points lay them out), no decrypt mask (a decrypt at these widths is 2 / m AES blocks per
+ * element, m = 128 / int_bits).  ONE chained launch from the floats: per value and client it reads the float and its draw and writes
+ * 4 bytes; no integer plaintext exists in HBM.  layers, src_dev, src_dtype, u_dev and the stage pass are those of
+ * flashe_quantize_encrypt_cohort_dev; the counters follow the chunking of n_jobs.
+ * Returns FLASHE_ENOTSUP -- nothing launched -- for every shape outside the launch: a ctx whose flashe_ctx_compact_layout is 0, another
+ * int_bits, more than 128 clients, n = 0 or n >= 2^32, fewer AES blocks than 2 x 128 x 16 x flashe_ctx_cu_count (the vector has
+ * r ceil((d + 1) / m) + (n_jobs - r) ceil(d / m) of them, d = n / n_jobs, r = n % n_jobs); the caller then quantises per client and uses
+ * flashe_encrypt_batch_sum_u32_dev.  The table uploads synchronise; not capturable. */
+int flashe_quantize_encrypt_cohort_u32_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                           const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                           int element_bits, const double *u_dev, uint32_t *const *ct_dev, uint32_t *sum_out_dev);
 /* The codec back end over caller-held vectors (new), jzf_quantize.py:102-107: out[k] = unquantize((in[k] + add[k] - minus[k]) mod 2^b)
  * as float64 for the n elements of a flattened model, one memory-bound pass; add_dev / minus_dev may be NULL (zeros).  With in = a
  * cohort's sum and add = its decrypt mask this is the cohort's decrypt_unquantize. */
