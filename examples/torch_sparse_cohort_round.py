@@ -59,7 +59,7 @@ def main():
             new_global = {name: torch.empty_like(t) for name, t in layers[0].items()}
             cohort.decrypt_unquantize(out=new_global, unnormalize=True)
         K, total = enc.encoded[0][1], enc.encoded[0][3]
-        print(f"round {it}: {C} clients, {total} parameters each, {K} kept: choice {choice!r}, path {upload.path!r}")
+        print(f"round {it}: {C} clients, {total} parameters each, {K} kept: choice {choice!r}, path {upload.path!r}, front end {upload.front_end!r}")
 
         with torch.no_grad():
             masks, compact = [], []

@@ -226,6 +226,9 @@ _SIGNATURES = {
                                                    ctypes.POINTER(ctypes.c_int32), c_vp, c_u64, c_vp, c_u64, c_vp, c_u64, c_vp, c_u64, c_int]),
     "flashe_quantize_cohort_dev": (c_int, [c_vp, c_int, c_u64, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp), ctypes.POINTER(ctypes.c_int32),
                                            c_int, c_vp, c_u64, ctypes.POINTER(ctypes.c_double), c_int, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
+    "flashe_quantize_encrypt_sparse_cohort_dev": (c_int, [c_vp, c_u32, c_int, ctypes.POINTER(c_u32), c_u64, c_u32, ctypes.POINTER(TensorLayer), c_int,
+                                                          ctypes.POINTER(c_vp), ctypes.POINTER(ctypes.c_int32), c_int, c_vp, c_u64,
+                                                          ctypes.POINTER(ctypes.c_double), c_int, ctypes.POINTER(c_vp), c_vp]),
     "flashe_rccl_unique_id": (c_int, [c_u8p]),
     "flashe_rccl_init": (c_int, [c_vp, c_u8p, c_int, c_int, ctypes.POINTER(c_vp)]),
     "flashe_rccl_destroy": (c_int, [c_vp]),

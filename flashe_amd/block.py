@@ -1284,6 +1284,9 @@ class FlasheCohort(object):
 
 # ---- a cohort of sparse-job clients hosted on one GPU (new) ----------------------------------------------------------------------
 SPARSE_COHORT = "sparse-cohort"
+FRONT_FUSED, FRONT_STAGED = "fused", "staged"
+SPARSE_FUSED_WIDTHS = (16, 20, 23, 24, 32)     # the widths compiled into prf_small_sparse_cohort_kernel (FLASHE_FIXED32_WIDTHS)
+SPARSE_FUSED_MAX_CLIENTS = 128
 
 
 class SparseCohortPlan(object):
@@ -1291,12 +1294,14 @@ class SparseCohortPlan(object):
     bits = total.bit_length(); ks (entries Client.sparsify keeps of every layer: max(1, floor(sparsity * size)), a function of the shape
     only), K = sum(ks), compact_starts (layer l's first compact value), n_elems = K + 1 (elements of one upload), draw_offsets (client
     c's first draw in the client-major draws: c (K + 1), the last of its K + 1 draws is its 'zzz' draw), f64 (does layer l compute in
-    float64?), path and the reason for it."""
+    float64?), path and the reason for it; front_end ("fused": the uploads come out of ONE chained launch from the floats, "staged": one
+    quantise launch into plaintexts, then the encrypts) and front_end_reason, why it is "staged"."""
 
-    def __init__(self, names, shapes, sizes, starts, total, ks, compact_starts, draw_offsets, f64, path, reason):
+    def __init__(self, names, shapes, sizes, starts, total, ks, compact_starts, draw_offsets, f64, path, reason, front_end=None, front_end_reason=""):
         self.names, self.shapes, self.sizes, self.starts, self.total, self.bits = names, shapes, sizes, starts, total, int(total).bit_length()
         self.ks, self.K, self.compact_starts, self.n_elems = ks, sum(ks), compact_starts, sum(ks) + 1
         self.draw_offsets, self.f64, self.path, self.reason = draw_offsets, f64, path, reason
+        self.front_end, self.front_end_reason = front_end or FRONT_STAGED, front_end_reason
 
 
 class SparseCohortEncoding(object):
@@ -1310,10 +1315,11 @@ class SparseCohortEncoding(object):
 
 class SparseCohortUpload(object):
     """FlasheSparseCohort.quantize_encrypt's result: uploads (one DeviceVector of K + 1 elements per client: the K ciphertexts and the
-    un-encrypted quantised zero), aggregate (aggregate_sparse_uploads of them: `total` elements) and path."""
+    un-encrypted quantised zero), aggregate (aggregate_sparse_uploads of them: `total` elements), path and front_end ("fused" / "staged":
+    the form that made the uploads)."""
 
-    def __init__(self, uploads, aggregate, path):
-        self.uploads, self.aggregate, self.path = uploads, aggregate, path
+    def __init__(self, uploads, aggregate, path, front_end=FRONT_STAGED):
+        self.uploads, self.aggregate, self.path, self.front_end = uploads, aggregate, path, front_end
 
 
 def _client_layers(w, walking_order=None):
@@ -1370,7 +1376,24 @@ def plan_sparse_cohort(weights_list, sparsity, int_bits, element_bits=16, batch=
         cstarts.append(K)
         K += k_l
     path, reason = _sparse_path(choice, batch, precompute, fuse, mixed)
-    return SparseCohortPlan(names, shapes, sizes, starts, total, ks, cstarts, [c * (K + 1) for c in range(C)], f64, path, reason)
+    front, front_reason = _sparse_front_end(path, reason, int_bits, C, K)
+    return SparseCohortPlan(names, shapes, sizes, starts, total, ks, cstarts, [c * (K + 1) for c in range(C)], f64, path, reason, front, front_reason)
+
+
+def _sparse_front_end(path, reason, int_bits, n_clients, K):
+    """("fused" | "staged", reason): does flashe_quantize_encrypt_sparse_cohort_dev take the cohort's uploads?  The library's own admission
+    rule, without a device (another PRF backend than the table one is the library's to refuse)."""
+    if path != SPARSE_COHORT:
+        return FRONT_STAGED, reason
+    if int_bits not in SPARSE_FUSED_WIDTHS:
+        return FRONT_STAGED, f"int_bits {int_bits} is not one of the chained widths {SPARSE_FUSED_WIDTHS}"
+    if n_clients > SPARSE_FUSED_MAX_CLIENTS:
+        return FRONT_STAGED, f"{n_clients} clients (the chained launch takes {SPARSE_FUSED_MAX_CLIENTS})"
+    if K >= 1 << 32:
+        return FRONT_STAGED, "2^32 compact values or more"
+    if os.environ.get("FLASHE_CHAIN", "1") == "0":
+        return FRONT_STAGED, "FLASHE_CHAIN=0"
+    return FRONT_FUSED, ""
 
 
 def _sparse_path(choice, batch, precompute, fuse, mixed):
@@ -1395,8 +1418,10 @@ class FlasheSparseCohort(object):
     FlasheClients run one after the other in one process on ONE shared quantiser state (FlasheCohort's rule), followed by
     aggregate_sparse_uploads and client first_idx's decrypt_unquantize -- bit for bit -- but the device work of the whole cohort is a
     number of launches that does not grow with n_local: one set of sparsifier launches over a C x L row table
-    (flashe_sparsify_cohort_tensors_dev), one quantise launch (flashe_quantize_cohort_dev), the fused encrypt + aggregate
-    (flashe_sparse_encrypt_aggregate_dev; at int_bits <= 64 that entry point keeps one encrypt launch per client) with the span bounds of
+    (flashe_sparsify_cohort_tensors_dev), the uploads in ONE chained launch from the floats at int_bits 16 / 20 / 23 / 24 / 32
+    (flashe_quantize_encrypt_sparse_cohort_dev, front_end "fused": no plaintext vector in HBM) followed by the sparse aggregate -- at
+    the other widths one quantise launch (flashe_quantize_cohort_dev) and the fused encrypt + aggregate
+    (flashe_sparse_encrypt_aggregate_dev; at int_bits <= 64 one batched encrypt launch and the aggregate) -- with the span bounds of
     the round's lists computed once, and the sparse decrypt + unquantise + store.  One engine and one stream carry everything, the sparsifier passes included.  `path` of an upload names the form that ran."""
 
     def __init__(self, args, first_idx, n_local, num_clients, prp_seed, sparsity, device=0, stream=None):
@@ -1427,6 +1452,7 @@ class FlasheSparseCohort(object):
         self._bounds = None             # (SpanBounds of the cohort's own lists, (total, C)): reused over rounds of the same shape
         self._last = None
         self._last_bounds = None        # the handle the decrypt of the cohort's own aggregate may take
+        self.prefer_front_end = None    # "staged": quantise into plaintexts, then encrypt, where the chained launch would be taken (A/B runs)
 
     quantizer = property(lambda self: self.lead.quantizer)
     cipher = property(lambda self: self.lead.cipher)
@@ -1795,19 +1821,41 @@ class FlasheSparseCohort(object):
                     eng.numpy_random_dev(tot, out=du.ptr + 8 * a0)
                 else:
                     du.upload_at(8 * a0, np.random.random(tot))
-        pstride = (8 * K + 15) & ~15
-        ptbuf = eng.alloc(max(C * pstride, 16))
-        pts = [ptbuf.ptr + ci * pstride for ci in range(C)]
         ups = [DeviceVector(eng, K + 1) for _ in range(C)]
         zbuf = eng.alloc(max(8 * C, 16))
-        eng.quantize_cohort_dev(K, table, srcs, dts, q.element_bits, du, K + 1, zvals, z64, pts, [u.ptr + 8 * eng.limbs * K for u in ups], zbuf)
+        # the uploads: ONE chained launch from the floats where the plan says so (int_bits 16 - 32: no plaintext vector in HBM, the
+        # launch count does not grow with C), else -- or when the library declines -- the quantise launch and the encrypts
+        front, _why = _sparse_front_end(path, "", ld.int_bits, C, K)
+        if self.prefer_front_end == FRONT_STAGED:
+            front = FRONT_STAGED
+        fused = getattr(eng, "quantize_encrypt_sparse_cohort_dev", None) if front == FRONT_FUSED else None
+        if fused is None or not fused(c.iter_index, [self.first_idx + ci for ci in range(C)], K, _cipher_mod.N_JOBS, table, srcs, dts, q.element_bits,
+                                      du, K + 1, zvals, z64, [u.buf for u in ups], zbuf):
+            front = FRONT_STAGED
+        ptbuf, pts = None, None
+        if front == FRONT_STAGED:
+            pstride = (8 * K + 15) & ~15
+            ptbuf = eng.alloc(max(C * pstride, 16))
+            pts = [ptbuf.ptr + ci * pstride for ci in range(C)]
+            eng.quantize_cohort_dev(K, table, srcs, dts, q.element_bits, du, K + 1, zvals, z64, pts, [u.ptr + 8 * eng.limbs * K for u in ups], zbuf)
         zeros = [int(v) for v in zbuf.download(np.uint64, C)]          # the C quantised zeros: the one download of the step
         own = self._lists[self.first_idx:self.first_idx + C]
         locs, lks = [b for b, _k in own], [k for _b, k in own]
         total = int(c.total)
         agg = DeviceVector(eng, total)
         bounds = None
-        if self._sorted:
+        if front == FRONT_FUSED:
+            # the ciphertexts are written: the aggregate each branch below runs, on the uploads
+            if self._sorted:
+                if self._bounds is not None and self._bounds[1] == (total, C):
+                    bounds = self._bounds[0].recompute(locs, lks)
+                else:
+                    bounds = eng.span_bounds(total, locs, lks)
+                self._bounds = (bounds, (total, C))
+                eng.sparse_aggregate_dev(total, locs, lks, [u.buf for u in ups], [[z, 0] for z in zeros], agg.buf, bounds=bounds)
+            else:
+                eng.sparse_aggregate_dev(total, locs, lks, [u.buf for u in ups], [[z, 0] for z in zeros], agg.buf, sorted_lists=False)
+        elif self._sorted:
             # the span bounds of the round's lists, once: the fused encrypt + aggregate takes them and, when the cohort is the federation,
             # so does the decrypt.  A handle of the same shape is recomputed (the list buffers may have been rewritten in place).
             if self._bounds is not None and self._bounds[1] == (total, C):
@@ -1821,12 +1869,12 @@ class FlasheSparseCohort(object):
             for ci in range(C):
                 eng.encrypt_dev(c.iter_index, self.first_idx + ci, 0, K, _cipher_mod.N_JOBS, pts[ci], 1, ups[ci].buf)
             eng.sparse_aggregate_dev(total, locs, lks, [u.buf for u in ups], [[z, 0] for z in zeros], agg.buf, sorted_lists=False)
-        eng.hold(keep + [du, ptbuf, zbuf])
+        eng.hold(keep + [du, zbuf] + ([ptbuf] if ptbuf is not None else []))
         ld.shape_dict = {k: (kl,) for k, kl in zip(names, ks)}
         for u in ups:
             u.mark_ready()
         agg.mark_ready()
-        self._last = SparseCohortUpload(ups, agg, SPARSE_COHORT)
+        self._last = SparseCohortUpload(ups, agg, SPARSE_COHORT, front)
         self._last_bounds = bounds if self.n_local == self.num_clients else None
         return self._last
 

@@ -1600,8 +1600,10 @@ static int cohort_check(flashe_ctx *ctx, const char *who, uint32_t first_idx, in
 }
 
 // rows of the device table (non-empty layers), the sources behind them, and ONE stage pass for every source that is not read in place
+// (extra / extra_dev: a further small block for the same launch, uploaded behind the table -- the sparse cohort's 'zzz' values)
 static int cohort_stage(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
-                        const int32_t *src_dtype, int element_bits, CohortCodec &cc)
+                        const int32_t *src_dtype, int element_bits, CohortCodec &cc, const void *extra = nullptr, size_t extra_bytes = 0,
+                        const char **extra_dev = nullptr)
 {
     int rc;
     std::vector<CodecLayer> tab;
@@ -1654,11 +1656,14 @@ static int cohort_stage(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe
     }
     // one block in ctx->codec_tab: the rows, then the source pointers
     const size_t rows_bytes = (n_tab * sizeof(CodecLayer) + 15) & ~static_cast<size_t>(15);
-    std::vector<char> blob(rows_bytes + src.size() * sizeof(void *));
+    const size_t extra_at = (rows_bytes + src.size() * sizeof(void *) + 15) & ~static_cast<size_t>(15);
+    std::vector<char> blob(extra ? extra_at + extra_bytes : rows_bytes + src.size() * sizeof(void *));
     memcpy(blob.data(), tab.data(), n_tab * sizeof(CodecLayer));
     memcpy(blob.data() + rows_bytes, src.data(), src.size() * sizeof(void *));
+    if (extra) memcpy(blob.data() + extra_at, extra, extra_bytes);
     const char *blob_dev = nullptr;
     if ((rc = upload_tab(ctx, ctx->codec_tab, blob, &blob_dev))) return rc;
+    if (extra_dev) *extra_dev = blob_dev + extra_at;
     if (!st.empty()) {
         const TensorStage *stab = nullptr;
         if ((rc = upload_tab(ctx, ctx->tensor_tab, st, &stab))) return rc;
@@ -2648,10 +2653,32 @@ static int sparse_encrypt_aggregate_impl(flashe_ctx *ctx, uint32_t iter, uint32_
     // (profiles/r09_ab_sparse_small.log); the position ranges run it
     if (!span_prf_table(ctx) || (bounds && !bounds->start_fused) || (whole && L == 1)) {
         // another PRF backend / int_bits <= 64: the encrypts, then the sparse reduce of what they wrote
+        // (non-empty clients of ONE k -- a cohort of one model shape: one batched single-mask launch per group launch_prf_batch admits,
+        // the same bytes as the per-client calls)
+        std::vector<uint32_t> bidx;
+        std::vector<const uint64_t *> bpt;
+        std::vector<uint64_t *> bct;
+        bool equal_k = true;
         for (int c = 0; c < C; c++) {
             if (!k[c]) continue;
-            const int rc = flashe_encrypt_dev(ctx, iter, idx[c], FLASHE_SCHEME_SINGLE, k[c], n_jobs, pt_dev[c], pt_limbs, ct_dev[c]);
+            bidx.push_back(idx[c]); bpt.push_back(pt_dev[c]); bct.push_back(ct_dev[c]);
+        }
+        uint64_t k0 = 0;
+        for (int c = 0; c < C; c++) {
+            if (!k[c]) continue;
+            if (!k0) k0 = k[c];
+            equal_k = equal_k && k[c] == k0;
+        }
+        if (equal_k && bidx.size() > 1) {
+            const int rc = flashe_encrypt_batch_dev(ctx, iter, FLASHE_SCHEME_SINGLE, k0, n_jobs, static_cast<int>(bidx.size()), bidx.data(), bpt.data(), pt_limbs,
+                                                    bct.data());
             if (rc) return rc;
+        } else {
+            for (int c = 0; c < C; c++) {
+                if (!k[c]) continue;
+                const int rc = flashe_encrypt_dev(ctx, iter, idx[c], FLASHE_SCHEME_SINGLE, k[c], n_jobs, pt_dev[c], pt_limbs, ct_dev[c]);
+                if (rc) return rc;
+            }
         }
         return sparse_aggregate_impl(ctx, total, C, loc_dev, k, ct_dev, zeros, 1, bounds, agg_out_dev);
     }
@@ -3162,22 +3189,21 @@ int flashe_sparsify_cohort_tensors_dev(flashe_ctx *ctx, int n_clients, uint64_t 
 
 // The sparse job's codec front end for all clients of a cohort in one launch: shared compact layer table (start, alpha, shift, flags;
 // dtype = the compute class), C x L sources, client-major draws -> C one-limb plaintext vectors + the C quantised 'zzz' values.
-int flashe_quantize_cohort_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
-                               const int32_t *src_dtype, int element_bits, const double *u_dev, uint64_t u_stride, const double *zzz, int zzz_is_f64,
-                               uint64_t *const *pt_dev, uint64_t *const *tail_dev, uint64_t *zeros_dev)
+// (the argument checks of the two entry points that take a sparse cohort's compact layers: the one below and
+// flashe_quantize_encrypt_sparse_cohort_dev; outs = the HOST array of output vectors; row_of = the non-empty layers)
+static int quantize_cohort_check(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
+                                 const int32_t *src_dtype, int element_bits, const double *u_dev, uint64_t u_stride, const double *zzz,
+                                 const void *outs, const uint64_t *zeros_dev, std::vector<int> &row_of)
 {
-    CHECK_CTX(ctx);
     if (n_clients < 1 || n_clients > 65535) return fail(ctx, FLASHE_EINVAL, "quantize_cohort: n_clients must be in [1, 65535]");
-    if (!src_dev || !src_dtype || !u_dev || !zzz || !pt_dev || !zeros_dev) return fail(ctx, FLASHE_EINVAL, "quantize_cohort: null argument");
+    if (!src_dev || !src_dtype || !u_dev || !zzz || !outs || !zeros_dev) return fail(ctx, FLASHE_EINVAL, "quantize_cohort: null argument");
     if (element_bits < 1 || element_bits > 62 || element_bits > ctx->int_bits)
         return fail(ctx, FLASHE_EINVAL, "element_bits must be in [1, min(62, int_bits)], got %d", element_bits);
     if ((reinterpret_cast<uintptr_t>(u_dev) & 7u) || (reinterpret_cast<uintptr_t>(zeros_dev) & 7u)) return fail(ctx, FLASHE_EINVAL, "misaligned vector");
     if (u_stride < n + 1) return fail(ctx, FLASHE_EINVAL, "quantize_cohort: u_stride must cover a client's n + 1 draws");
-    if (n >= (1ull << 32)) return fail(ctx, FLASHE_EINVAL, "quantize_cohort: n must be < 2^32");
     int rc = check_tensor_layers_shape(ctx, n, layers, n_layers);
     if (rc) return rc;
-    std::vector<QuantCohortRow> tab;
-    std::vector<int> row_of;
+    row_of.clear();
     for (int l = 0; l < n_layers; l++) {
         const flashe_tensor_layer &y = layers[l];
         const uint64_t end = l + 1 < n_layers ? layers[l + 1].start : n;
@@ -3185,9 +3211,35 @@ int flashe_quantize_cohort_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const
         if (!(y.alpha > 0)) return fail(ctx, FLASHE_EINVAL, "layer %d: alpha must be positive", l);
         if (y.dtype != FLASHE_TENSOR_F32 && y.dtype != FLASHE_TENSOR_F64)
             return fail(ctx, FLASHE_EINVAL, "layer %d: the shared row names the COMPUTE type, FLASHE_TENSOR_F32 or FLASHE_TENSOR_F64", l);
+        row_of.push_back(l);
+    }
+    for (int c = 0; c < n_clients; c++)
+        for (const int l : row_of) {
+            const size_t at = static_cast<size_t>(c) * n_layers + l;
+            const int es = tensor_elem_bytes(src_dtype[at]);
+            if (!es) return fail(ctx, FLASHE_EINVAL, "client %d layer %d: unknown dtype %d", c, l, static_cast<int>(src_dtype[at]));
+            if ((src_dtype[at] == FLASHE_TENSOR_F64) != (layers[l].dtype == FLASHE_TENSOR_F64))
+                return fail(ctx, FLASHE_EINVAL, "client %d layer %d: the source is of another compute class than the shared row", c, l);
+            if (!src_dev[at] || reinterpret_cast<uintptr_t>(src_dev[at]) % static_cast<uintptr_t>(es))
+                return fail(ctx, FLASHE_EINVAL, "client %d layer %d: null or misaligned source", c, l);
+        }
+    return FLASHE_OK;
+}
+
+int flashe_quantize_cohort_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
+                               const int32_t *src_dtype, int element_bits, const double *u_dev, uint64_t u_stride, const double *zzz, int zzz_is_f64,
+                               uint64_t *const *pt_dev, uint64_t *const *tail_dev, uint64_t *zeros_dev)
+{
+    CHECK_CTX(ctx);
+    if (n >= (1ull << 32)) return fail(ctx, FLASHE_EINVAL, "quantize_cohort: n must be < 2^32");
+    std::vector<int> row_of;
+    int rc = quantize_cohort_check(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, u_dev, u_stride, zzz, pt_dev, zeros_dev, row_of);
+    if (rc) return rc;
+    std::vector<QuantCohortRow> tab;
+    for (const int l : row_of) {
+        const flashe_tensor_layer &y = layers[l];
         const Codec c = codec_quantize_front(nullptr, y.dtype == FLASHE_TENSOR_F64 || (y.flags & FLASHE_TENSOR_LOOP_F64), y.alpha, element_bits, nullptr);
         tab.push_back(QuantCohortRow{y.start, c.alpha, c.scale, c.den, y.shift, c.x_is_f64, y.flags & (FLASHE_TENSOR_SHIFT | FLASHE_TENSOR_SHIFT_WIDE)});
-        row_of.push_back(l);
     }
     const size_t n_tab = tab.size(), C = static_cast<size_t>(n_clients);
     std::vector<const void *> src(C * n_tab);
@@ -3196,14 +3248,7 @@ int flashe_quantize_cohort_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const
         if (n && (!pt_dev[c] || (reinterpret_cast<uintptr_t>(pt_dev[c]) & 7u))) return fail(ctx, FLASHE_EINVAL, "client %d: null or misaligned plaintext vector", static_cast<int>(c));
         if (tail_dev && tail_dev[c] && (reinterpret_cast<uintptr_t>(tail_dev[c]) & 7u)) return fail(ctx, FLASHE_EINVAL, "client %d: misaligned tail", static_cast<int>(c));
         for (size_t rr = 0; rr < n_tab; rr++) {
-            const int l = row_of[rr];
-            const size_t at = c * n_layers + l;
-            const int es = tensor_elem_bytes(src_dtype[at]);
-            if (!es) return fail(ctx, FLASHE_EINVAL, "client %d layer %d: unknown dtype %d", static_cast<int>(c), l, static_cast<int>(src_dtype[at]));
-            if ((src_dtype[at] == FLASHE_TENSOR_F64) != (layers[l].dtype == FLASHE_TENSOR_F64))
-                return fail(ctx, FLASHE_EINVAL, "client %d layer %d: the source is of another compute class than the shared row", static_cast<int>(c), l);
-            if (!src_dev[at] || reinterpret_cast<uintptr_t>(src_dev[at]) % static_cast<uintptr_t>(es))
-                return fail(ctx, FLASHE_EINVAL, "client %d layer %d: null or misaligned source", static_cast<int>(c), l);
+            const size_t at = c * n_layers + row_of[rr];
             src[c * n_tab + rr] = src_dev[at];
             sdt[c * n_tab + rr] = src_dtype[at];
         }
@@ -3233,6 +3278,42 @@ int flashe_quantize_cohort_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const
     const Codec z = codec_quantize_front(nullptr, zzz_is_f64 != 0, 1.0, element_bits, nullptr);
     qc.zrow = QuantCohortRow{n, z.alpha, z.scale, z.den, 0.0, z.x_is_f64, 0};
     HIP_TRY(ctx, launch_quantize_cohort(ctx->env, qc, n, u_dev, u_stride));
+    return FLASHE_OK;
+}
+
+// The two steps of a sparse cohort's uploads -- flashe_quantize_cohort_dev, then one flashe_encrypt_dev(SINGLE) per client
+// (jzf_quantize.py:433-465, jzf_aggregator.py:717-743, jzf_flashe.py:471-478) -- as ONE chained launch from the floats at int_bits
+// 16 / 20 / 23 / 24 / 32 (prf_small_sparse_cohort_kernel): no plaintext vector exists in HBM.  The checks are quantize_cohort_check's, the
+// table and the stage pass cohort_stage's; what the launch does not take is refused with FLASHE_ENOTSUP before anything is staged.
+int flashe_quantize_encrypt_sparse_cohort_dev(flashe_ctx *ctx, uint32_t iter, int n_clients, const uint32_t *idx, uint64_t n, uint32_t n_jobs,
+                                              const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                              int element_bits, const double *u_dev, uint64_t u_stride, const double *zzz, int zzz_is_f64,
+                                              uint64_t *const *ct_dev, uint64_t *zeros_dev)
+{
+    CHECK_CTX(ctx);
+    static const char who[] = "flashe_quantize_encrypt_sparse_cohort_dev";
+    std::vector<int> row_of;
+    int rc = quantize_cohort_check(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, u_dev, u_stride, zzz, ct_dev, zeros_dev, row_of);
+    if (rc) return rc;
+    if (!idx) return fail(ctx, FLASHE_EINVAL, "%s: null argument", who);
+    if (n_jobs == 0) return fail(ctx, FLASHE_EINVAL, "n_jobs must be >= 1");
+    for (int c = 0; c < n_clients; c++) {
+        if (!ct_dev[c] || (reinterpret_cast<uintptr_t>(ct_dev[c]) & 7u)) return fail(ctx, FLASHE_EINVAL, "client %d: null or misaligned upload", c);
+        if (reinterpret_cast<uint64_t *>(ct_dev[c]) == zeros_dev) return fail(ctx, FLASHE_EINVAL, "client %d: the upload aliases zeros_dev", c);
+    }
+    if (!ctx->env.use_chain || !small_cohort_width(ctx->int_bits) || n_clients > 128 || n == 0 || n >= (1ull << 32) ||
+        (ctx->env.prf_backend != PRF_AUTO && ctx->env.prf_backend != PRF_TABLE))
+        return fail(ctx, FLASHE_ENOTSUP, "%s: not a shape of the chained sparse cohort launch", who);
+    const Codec z = codec_quantize_front(nullptr, zzz_is_f64 != 0, 1.0, element_bits, nullptr);
+    CohortCodec cc{};
+    const char *zzz_dev = nullptr;
+    if ((rc = cohort_stage(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, cc, zzz, static_cast<size_t>(n_clients) * sizeof(double),
+                           &zzz_dev)))
+        return rc;
+    const hipError_t e = launch_small_sparse_cohort(ctx->env, iter, n_clients, idx, cc, u_dev, u_stride, ct_dev, n, n_jobs,
+                                                    reinterpret_cast<const double *>(zzz_dev), z.x_is_f64 != 0, z.alpha, z.scale, z.den, zeros_dev);
+    if (e == hipErrorNotSupported) return fail(ctx, FLASHE_ENOTSUP, "%s: not a shape of the chained sparse cohort launch", who);
+    HIP_TRY(ctx, e);
     return FLASHE_OK;
 }
 

@@ -101,6 +101,14 @@ hipError_t launch_prf_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec,
 // chunking of n_jobs) for each of the chip's waves.  hipErrorNotSupported: nothing launched.
 hipError_t launch_small_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
                                    uint32_t *const *out_dev, uint32_t *sum_out_dev, uint64_t n, uint32_t n_jobs);
+// The sparse job's cohort at the same widths (prf_small_sparse_cohort_kernel): out_dev[c][k] = SINGLE-mask encrypt (idx[c]; any indices) of the
+// quantisation of client c's compact value k with the draw u_dev[c * u_stride + k], k < n, in the ONE-LIMB layout (uint64 elements, 8-byte
+// aligned), and out_dev[c][n] = zeros_dev[c] = the client's 'zzz' value zzz_dev[c] quantised in plain with (z_alpha, z_scale, z_den) in
+// float64 / float32 and the draw u_dev[c * u_stride + n].  No minimum length: short vectors are cut into runs of clients.
+// hipErrorNotSupported -- nothing launched -- for another width, PRF backend or FLASHE_CHAIN=0, more than kMaxLinks clients, n = 0 or >= 2^32.
+hipError_t launch_small_sparse_cohort(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
+                                      uint64_t u_stride, uint64_t *const *out_dev, uint64_t n, uint32_t n_jobs, const double *zzz_dev, bool zzz_f64,
+                                      double z_alpha, double z_scale, double z_den, uint64_t *zeros_dev);
 // is int_bits one of the widths compiled into that launch? (what a caller asks before it stages anything for it)
 bool small_cohort_width(int int_bits);
 // launch_prf_batch on elements [first, first + count) of the n-element vectors (pointers address element `first`): what a GPU that owns

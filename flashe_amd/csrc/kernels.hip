@@ -1089,10 +1089,37 @@ struct CohortWalk {
     }
 };
 
+// the M words of a lane's block as M elements of the ONE-LIMB layout (prf_small_sparse_cohort_kernel: a sparse upload is a uint64 vector that
+// is only 8-byte aligned, and at odd M every other block starts at an odd element): 16-byte stores for the pairs that lie on a 16-byte
+// boundary, the element before the first / behind the last such pair on its own
+template <int M>
+__device__ __forceinline__ void direct32_put(uint64_t *__restrict__ q, const uint32_t (&r)[M], uint32_t mask)
+{
+    const int lead = (reinterpret_cast<uintptr_t>(q) & 8u) ? 1 : 0;
+    if (lead) {
+        q[0] = r[0] & mask;
+#pragma unroll
+        for (int t = 1; t + 2 <= M; t += 2) {
+            u64x2 x;
+            x[0] = r[t] & mask; x[1] = r[t + 1] & mask;
+            *reinterpret_cast<u64x2 *>(q + t) = x;
+        }
+        if ((M & 1) == 0) q[M - 1] = r[M - 1] & mask;
+    } else {
+#pragma unroll
+        for (int t = 0; t + 2 <= M; t += 2) {
+            u64x2 x;
+            x[0] = r[t] & mask; x[1] = r[t + 1] & mask;
+            *reinterpret_cast<u64x2 *>(q + t) = x;
+        }
+        if (M & 1) q[M - 1] = r[M - 1] & mask;
+    }
+}
+
 // out[k + t] = (pt[t] + slot_t(add) - slot_t(minus)) mod 2^B for the M = 128 / B elements of the lane's block; `single`: no minus stream
-// (acc: the running sum of the chain's outputs for this block, kept in registers -- a summed chain)
-template <int B>
-__device__ __forceinline__ void direct32_store(uint32_t *__restrict__ out, uint64_t k, const DirectPt<128 / B> &pt, u128 add, u128 minus, bool single,
+// (acc: the running sum of the chain's outputs for this block, kept in registers -- a summed chain; OT = uint64_t: one-limb outputs)
+template <int B, class OT = uint32_t>
+__device__ __forceinline__ void direct32_store(OT *__restrict__ out, uint64_t k, const DirectPt<128 / B> &pt, u128 add, u128 minus, bool single,
                                                uint32_t (&acc)[128 / B])
 {
     constexpr int M = 128 / B;
@@ -1104,6 +1131,10 @@ __device__ __forceinline__ void direct32_store(uint32_t *__restrict__ out, uint6
         r[t] = (pt.v[t] + a - (single ? 0u : m)) & mask;
         acc[t] += r[t];
     }
+    if constexpr (sizeof(OT) == 8) {
+        direct32_put<M>(out + k, r, mask);
+        return;
+    } else {
     uint32_t *q = out + k;
     int t = 0;
 #pragma unroll
@@ -1119,6 +1150,7 @@ __device__ __forceinline__ void direct32_store(uint32_t *__restrict__ out, uint6
         t += 2;
     }
     if (t < M) q[t] = r[t];
+    }
 }
 
 // int_bits = 64 in the one-limb layout at compile time (round 5): the two elements of a lane's block are one 16-byte access, the slots are
@@ -1169,7 +1201,8 @@ __device__ __forceinline__ void direct32_put(uint32_t *__restrict__ q, const uin
 // 16: 0.2234 -> 0.2156, 23 / 24 / 32: within 1 %.  Measured and dropped (tests/perf/experiments/r06_small_chain_fast32_pipelined.patch):
 // the streams software-pipelined against each other (the next stream's first lookups issued before this stream's outputs): 0.2769
 // against 0.2740 at int_bits 20, 127 VGPRs -- what is left between two steps is not what holds these kernels back.
-template <int B, bool SINGLE, class SRC = void>
+// (OT = uint64_t: the outputs in the one-limb layout, direct32_put's uint64 form)
+template <int B, bool SINGLE, class SRC = void, class OT = uint32_t>
 __device__ __forceinline__ void small_chain_fast32(const RoundKeys &rk, const LaneRegs lr, const uint32_t *pre_lds, int sbase, int n_streams,
                                                    const uint64_t *const *in_tab, uint64_t *const *out_tab, const CtrVar &xA, const CtrVar &xB,
                                                    uint64_t kA, uint64_t kB, uint32_t *sum32, bool prio,
@@ -1201,7 +1234,7 @@ __device__ __forceinline__ void small_chain_fast32(const RoundKeys &rk, const La
                 accA[t] += ua; accB[t] += ub;
                 rA[t] = ua; rB[t] = ub;
             }
-            uint32_t *out = reinterpret_cast<uint32_t *>(out_tab[link]);
+            OT *out = reinterpret_cast<OT *>(out_tab[link]);
             direct32_put<M>(out + kA, rA, mask);
             direct32_put<M>(out + kB, rB, mask);
         }
@@ -1279,6 +1312,37 @@ __global__ __launch_bounds__(kSmallThreads) void prf_small_cohort_kernel(const R
 {
     constexpr bool PAIR = true, COHORT = true;
     using ET = uint32_t;
+#include "prf_small_chain_body.inc"
+}
+
+// The sparse job's cohort at the same widths (flashe_quantize_encrypt_sparse_cohort_dev): C SINGLE-mask encrypts of the clients' quantised compact
+// values, uploads in the one-limb layout, no sum -- per value and client 4 + 8 bytes read and 8 written, against 36 through
+// quantize_cohort's plaintexts and one encrypt launch per client.  Chains without a sum may be cut: the launch deals (run of clients, tile)
+// items, so a short compact vector still reaches every wave.  The first lanes of workgroup 0 write the clients' trailing 'zzz' values
+// (jzf_quantize.py:433-435: alpha 1.0, the draw behind the client's n), in plain, to element n of the uploads and to `zeros`.
+struct SparseCohortTail {
+    const double *zzz;          // device: the C 'zzz' values
+    uint64_t *zeros;            // device: receives the C quantised values
+    const double *u_n;          // client 0's 'zzz' draw; client c's lies c * u_stride doubles on
+    uint64_t u_stride, n;
+    double alpha, scale, den;
+    int f64, n_clients;
+};
+template <int B>
+__global__ __launch_bounds__(kSmallThreads) void prf_small_sparse_cohort_kernel(const RoundKeys rk, const SmallChainTable tb, int n_chains, const SmallParams p,
+                                                                                 const CohortCodec cc, const SparseCohortTail tail)
+{
+    constexpr bool PAIR = true, COHORT = true;
+    using ET = uint64_t;
+    if (blockIdx.x == 0 && threadIdx.x < static_cast<unsigned>(tail.n_clients)) {
+        const int c = threadIdx.x;
+        const double v = tail.zzz[c], u = tail.u_n[static_cast<uint64_t>(c) * tail.u_stride];
+        const uint64_t q = tail.f64 ? quantize_one<double>(v, tail.alpha, tail.scale, tail.den, u)
+                                    : quantize_one<float>(static_cast<float>(v), static_cast<float>(tail.alpha), static_cast<float>(tail.scale),
+                                                          static_cast<float>(tail.den), u);
+        tail.zeros[c] = q;
+        tb.out[c][tail.n] = q;
+    }
 #include "prf_small_chain_body.inc"
 }
 
@@ -2395,6 +2459,57 @@ hipError_t launch_small_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_ve
     const int grid = static_cast<int>(tiles < cus ? tiles : cus);
     switch (env.b) {
 #define FLASHE_FIXED32(B) case B: hipLaunchKernelGGL((prf_small_cohort_kernel<B>), dim3(grid), dim3(kSmallThreads), 0, env.stream, env.rk, tb, 1, p, cc); break;
+        FLASHE_FIXED32_WIDTHS(FLASHE_FIXED32)
+#undef FLASHE_FIXED32
+    default: return hipErrorNotSupported;
+    }
+    return hipGetLastError();
+}
+
+// The sparse cohort's encrypts from the floats (prf_small_sparse_cohort_kernel): ONE single-mask chain of n_vec links over elements [0, n), cut
+// into runs of clients where the vector alone has fewer tiles than the chip has waves (launch_small_chains' rule for unsummed chains; a
+// single-mask cut costs no stream).  hipErrorNotSupported = nothing launched.
+hipError_t launch_small_sparse_cohort(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
+                                      uint64_t u_stride, uint64_t *const *out_dev, uint64_t n, uint32_t n_jobs, const double *zzz_dev, bool zzz_f64,
+                                      double z_alpha, double z_scale, double z_den, uint64_t *zeros_dev)
+{
+    if (n == 0 || n >= (1ull << 32) || n_vec <= 0 || n_jobs == 0) return hipErrorNotSupported;
+    if (!env.use_chain || !small_cohort_width(env.b) || env.codec || n_vec > kMaxLinks || !u_dev || cc.n_layers < 1) return hipErrorNotSupported;
+    if (env.prf_backend != PRF_AUTO && env.prf_backend != PRF_TABLE) return hipErrorNotSupported;
+    for (int v = 0; v < n_vec; v++) if (!out_dev[v]) return hipErrorNotSupported;
+    LaunchEnv e32 = env;
+    e32.elem32 = 1;                           // (the measured priority table of the compile-time widths; the kernel's outputs are one-limb)
+    SmallParams p = small_params_of(e32, iter, n, n_jobs);
+    if (p.no_fixed_width) return hipErrorNotSupported;
+    p.no_direct = 1;
+    p.swp_prio = small_swp_prio(e32, p, n_vec);
+    const uint64_t blocks = block_of(n - 1, n, n_jobs, p.m) + 1;
+    const uint64_t waves = static_cast<uint64_t>(env.num_cus) * (kSmallThreads / 64), tiles = (blocks + 127) / 128;
+    int parts = 1;
+    if (tiles < waves) parts = static_cast<int>(std::min<uint64_t>(std::min<uint64_t>(waves / tiles, static_cast<uint64_t>(n_vec)), kMaxChains));
+    SmallChainTable tb{};
+    int nc = 0;
+    uint64_t wend = 0;
+    for (int k = 0; k < parts; k++) {
+        const int a = static_cast<int>(static_cast<int64_t>(n_vec) * k / parts), b = static_cast<int>(static_cast<int64_t>(n_vec) * (k + 1) / parts);
+        if (b <= a) continue;
+        tb.first[nc] = 0; tb.count[nc] = n; tb.blk_first[nc] = 0; tb.blk_count[nc] = blocks;
+        tb.link0[nc] = static_cast<uint16_t>(a); tb.sbase[nc] = static_cast<uint16_t>(a);
+        tb.len[nc] = static_cast<uint8_t>(b - a); tb.flags[nc] = 1;
+        wend += tiles * static_cast<uint64_t>(b - a);
+        tb.wend[nc] = wend;
+        nc++;
+    }
+    for (int l = 0; l < n_vec; l++) {
+        tb.idx[l] = idx[l];
+        tb.in[l] = reinterpret_cast<const uint64_t *>(u_dev + static_cast<uint64_t>(l) * u_stride);       // the link's draws (CohortDirect, CohortWalk)
+        tb.out[l] = out_dev[l];
+    }
+    const SparseCohortTail tail{zzz_dev, zeros_dev, u_dev + n, u_stride, n, z_alpha, z_scale, z_den, zzz_f64 ? 1 : 0, n_vec};
+    const uint64_t items = tiles * static_cast<uint64_t>(nc), cus = static_cast<uint64_t>(env.num_cus);
+    const int grid = static_cast<int>(items < cus ? items : cus);
+    switch (env.b) {
+#define FLASHE_FIXED32(B) case B: hipLaunchKernelGGL((prf_small_sparse_cohort_kernel<B>), dim3(grid), dim3(kSmallThreads), 0, env.stream, env.rk, tb, nc, p, cc, tail); break;
         FLASHE_FIXED32_WIDTHS(FLASHE_FIXED32)
 #undef FLASHE_FIXED32
     default: return hipErrorNotSupported;

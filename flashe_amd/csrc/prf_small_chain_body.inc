@@ -4,9 +4,12 @@
 // COHORT (PAIR, the compact layout at a compile-time width, one summed double-mask chain over whole vectors): the plaintext of output
 // `link` at element k is the quantisation of client link's float k (CohortCodec cc; tb.in[link] = that client's draws) -- whole tiles
 // through CohortDirect, the tiles that walk through CohortWalk.
-    static_assert(!COHORT || (PAIR && sizeof(ET) == 4 && B != 0 && B <= 32), "the cohort front end rides on the paired compact chain at a compile-time width");
+// COHORT with ET = uint64_t (prf_small_sparse_cohort_kernel<B>, the sparse job's cohort): the same front end on SINGLE-mask chains without a
+// sum, the outputs in the one-limb layout -- a whole block's M words go out as M uint64 elements (direct32_put's uint64 form).
+    static_assert(!COHORT || (PAIR && B != 0 && B <= 32), "the cohort front end rides on the paired chain at a compile-time width");
     (void)cc;
-    static_assert(B == 0 || (PAIR && ((sizeof(ET) == 4 && B <= 32) || (sizeof(ET) == 8 && B == 64))), "compile-time widths: the paired kernel, compact layout or int_bits 64");
+    constexpr bool LIMB_OUT = COHORT && sizeof(ET) == 8;
+    static_assert(B == 0 || (PAIR && ((sizeof(ET) == 4 && B <= 32) || (sizeof(ET) == 8 && (B == 64 || LIMB_OUT)))), "compile-time widths: the paired kernel, compact layout or int_bits 64");
     constexpr uint32_t WAVES = kSmallThreads / 64, TILE = PAIR ? 128u : 64u;
     constexpr int MB = B ? 128 / B : 1;
     __shared__ uint32_t tab[kTabWords];
@@ -100,7 +103,7 @@
         uint32_t accA[MB], accB[MB];
 #pragma unroll
         for (int t = 0; t < MB; t++) { accA[t] = 0u; accB[t] = 0u; }
-        uint32_t *const sum32 = B != 0 && B != 64 ? reinterpret_cast<uint32_t *>(tb.sum_out[cur]) : nullptr;
+        uint32_t *const sum32 = B != 0 && B != 64 && !LIMB_OUT ? reinterpret_cast<uint32_t *>(tb.sum_out[cur]) : nullptr;
         // COHORT: the table row of each whole half tile, found once per tile with scalar loads (every link works on the same elements); a
         // half that straddles a row boundary is walked like a chunk end, its lanes look their rows up themselves (CohortWalk)
         int layA = -1, layB = -1;
@@ -126,7 +129,12 @@
                 const uint32_t bA = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(ctrA)), bB = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(ctrB));
                 const bool uni = n_streams <= kU2MaxStreams && __ballot(ctrA - bA == lane && ctrB - bB == lane) == ~0ull &&
                                  (bA & 255u) <= 192u && (bB & 255u) <= 192u;
-                if constexpr (COHORT) {
+                if constexpr (LIMB_OUT) {
+                    const CohortDirect csrc{cc, tb.in + link0, link0, {layA, layB}};
+                    small_chain_fast32<B, true, CohortDirect, uint64_t>(rk, lr, pre_lds, sbase, n_streams, tb.in + link0, tb.out + link0, xA, xB, j0A - first, j0B - first,
+                                                                        nullptr, p.swp_prio != 0, p.te0, uni, bA ^ rk.w[3], bB ^ rk.w[3], &csrc);
+                    continue;
+                } else if constexpr (COHORT) {
                     const CohortDirect csrc{cc, tb.in + link0, link0, {layA, layB}};
                     small_chain_fast32<B, false>(rk, lr, pre_lds, sbase, n_streams, tb.in + link0, tb.out + link0, xA, xB, j0A - first, j0B - first, sum32, p.swp_prio != 0,
                                                  p.te0, uni, bA ^ rk.w[3], bB ^ rk.w[3], &csrc);
@@ -186,15 +194,16 @@
                     if (B) {
                         // compile-time width: whole tiles element by element from the two streams' slots, everything else the general walk
                         if constexpr (B != 0 && B != 64) {
-                            uint32_t *o32 = reinterpret_cast<uint32_t *>(out);
+                            using OT = std::conditional_t<LIMB_OUT, uint64_t, uint32_t>;
+                            OT *o32 = reinterpret_cast<OT *>(out);
                             ET *const sm = reinterpret_cast<ET *>(sum32);
-                            if (fastA) direct32_store<B>(o32, j0A - first, dA, single ? SA : prevA, SA, single, accA);
+                            if (fastA) direct32_store<B, OT>(o32, j0A - first, dA, single ? SA : prevA, SA, single, accA);
                             else if constexpr (COHORT) {
                                 const CohortWalk cw{cc, in, link0 + link};
                                 small_walk(row0, lane, vA, cntA, j0A, single ? SA : slot_diff(prevA, SA, top, p.b), ein, eout, first, range_end, p, sm, link == 0, &cw);
                             }
                             else small_walk(row0, lane, vA, cntA, j0A, single ? SA : slot_diff(prevA, SA, top, p.b), ein, eout, first, range_end, p, sm, link == 0);
-                            if (fastB) direct32_store<B>(o32, j0B - first, dB, single ? SB : prevB, SB, single, accB);
+                            if (fastB) direct32_store<B, OT>(o32, j0B - first, dB, single ? SB : prevB, SB, single, accB);
                             else if constexpr (COHORT) {
                                 const CohortWalk cw{cc, in, link0 + link};
                                 small_walk(row0, lane, vB, cntB, j0B, single ? SB : slot_diff(prevB, SB, top, p.b), ein, eout, first, range_end, p, sm, link == 0, &cw);

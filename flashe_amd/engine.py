@@ -1394,6 +1394,26 @@ class Engine:
         self._check(self._lib.flashe_quantize_cohort_dev(self._h, C, int(n), arr, nl, ps, pd, int(element_bits), self._ptr(u), int(u_stride), pz,
                                                          1 if zzz_is_f64 else 0, pp, pt, self._ptr(zeros)))
 
+    def quantize_encrypt_sparse_cohort_dev(self, it, idx, n, n_jobs, layers, srcs, dtypes, element_bits, u, u_stride, zzz, zzz_is_f64, cts, zeros):
+        """quantize_cohort_dev and the clients' single-mask encrypts as ONE chained launch from the floats
+        (flashe_quantize_encrypt_sparse_cohort_dev, int_bits 16 / 20 / 23 / 24 / 32): layers, srcs, dtypes, u, u_stride, zzz, zzz_is_f64 and
+        zeros as quantize_cohort_dev takes them; idx[c] = client c's cipher index; cts[c] = its upload of n + 1 one-limb elements (n
+        ciphertexts, then the plain quantised 'zzz').  Returns False -- nothing was launched -- when the library declines the shape
+        (FLASHE_ENOTSUP: the caller runs quantize_cohort_dev and the encrypts), True otherwise."""
+        arr, nl = self._tensor_layers(layers)
+        C = len(srcs)
+        ps = (c_vp * max(C * nl, 1))(*[int(p) if p else None for row in srcs for p in row])
+        pd = (ctypes.c_int32 * max(C * nl, 1))(*[int(d) for row in dtypes for d in row])
+        pz = (ctypes.c_double * max(C, 1))(*[float(z) for z in zzz])
+        ii = (ctypes.c_uint32 * max(C, 1))(*[int(v) for v in idx])
+        pc, _kc = self._ptr_array(cts)
+        rc = self._lib.flashe_quantize_encrypt_sparse_cohort_dev(self._h, it, C, ii, int(n), n_jobs, arr, nl, ps, pd, int(element_bits), self._ptr(u),
+                                                                 int(u_stride), pz, 1 if zzz_is_f64 else 0, pc, self._ptr(zeros))
+        if rc == _lib.ENOTSUP:
+            return False
+        self._check(rc)
+        return True
+
     def sparsify_batch(self, layers, ks, residuals=None):
         """[(loc uint32[k_l] ascending, vals[k_l], new residual or None) per layer] -- Client.sparsify's layer loop
         (jzf_aggregator.py:585-613) as ONE upload, one set of launches and one download.  All layers share one float type."""

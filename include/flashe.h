@@ -71,7 +71,8 @@ typedef struct flashe_ctx flashe_ctx;
  *      flashe_decrypt_prepared_unquantize_model_dev, flashe_decrypt_prepared_unbatch_unquantize_model_dev (the model-wide codec with the
  *      ctx's precomputed masks); FLASHE_ENOTSUP + flashe_quantize_encrypt_cohort_dev (a cohort of co-located clients: C float models
  *      to C ciphertexts, their sum and the decrypt mask in one chained launch) and flashe_combine_unquantize_model_dev (the codec back
- *      end over a sum and caller-held masks); flashe_sparsify_cohort_tensors_dev and flashe_quantize_cohort_dev (a cohort of sparse-job
+ *      end over a sum and caller-held masks); flashe_quantize_encrypt_sparse_cohort_dev (a sparse cohort's quantise + encrypts in one
+ *      launch at int_bits 16 - 32); flashe_sparsify_cohort_tensors_dev and flashe_quantize_cohort_dev (a cohort of sparse-job
  *      clients: C models sparsified in one set of launches, their compact layers quantised in one launch);
  *      flashe_quantize_encrypt_cohort_u32_dev (the cohort's chained launch in the compact layout, int_bits 16 / 20 / 23 / 24 / 32) */
 #define FLASHE_ABI_VERSION 4
@@ -831,6 +832,20 @@ int flashe_sparsify_cohort_tensors_dev(flashe_ctx *ctx, int n_clients, uint64_t 
 int flashe_quantize_cohort_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
                                const int32_t *src_dtype, int element_bits, const double *u_dev, uint64_t u_stride, const double *zzz, int zzz_is_f64,
                                uint64_t *const *pt_dev, uint64_t *const *tail_dev, uint64_t *zeros_dev);
+/* Those two steps of a sparse cohort's uploads in ONE launch (new): flashe_quantize_cohort_dev followed by flashe_encrypt_dev(iter, idx[c],
+ * FLASHE_SCHEME_SINGLE, n, n_jobs) per client (jzf_quantize.py:433-465, jzf_aggregator.py:717-743, jzf_flashe.py:471-478), chained from
+ * the floats: no plaintext vector exists in HBM and the launch count does not depend on n_clients.  layers, src_dev, src_dtype, u_dev,
+ * u_stride, zzz, zzz_is_f64 and zeros_dev exactly as flashe_quantize_cohort_dev takes them; idx: HOST array of the clients' cipher
+ * indices (any values).  ct_dev[c] (HOST array of device pointers, 8-byte aligned): client c's upload of n + 1 ONE-LIMB elements --
+ * elements [0, n) are the single-mask ciphertexts of what flashe_quantize_cohort_dev would have written to pt_dev[c], bit for bit (the
+ * chunking runs over n), element n is the plain quantised 'zzz' value that also goes to zeros_dev[c].
+ * FLASHE_ENOTSUP -- nothing was launched, run the two steps -- unless int_bits is 16, 20, 23, 24 or 32, the PRF backend the table one,
+ * FLASHE_CHAIN not 0, n_clients <= 128 and 0 < n < 2^32.  Sources that are not read in place (float16 / bfloat16, SHIFT, a float32 source
+ * under a LOOP_F64 row) go through one stage pass for all clients.  The tables are uploaded synchronously (not inside a graph capture). */
+int flashe_quantize_encrypt_sparse_cohort_dev(flashe_ctx *ctx, uint32_t iter, int n_clients, const uint32_t *idx, uint64_t n, uint32_t n_jobs,
+                                              const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                              int element_bits, const double *u_dev, uint64_t u_stride, const double *zzz, int zzz_is_f64,
+                                              uint64_t *const *ct_dev, uint64_t *zeros_dev);
 
 /* ---- multi-GPU exchange (RCCL over xGMI; one process per GPU) ----------------------------------------------- */
 /* Replaces, inside one node, the arbiter's gather of client models + reduce in Python + broadcast of the aggregate
