@@ -3031,7 +3031,9 @@ int flashe_sparsify_dev(flashe_ctx *ctx, uint64_t n, uint64_t k, const void *x_d
     if (n >= (1ull << 32)) return fail(ctx, FLASHE_EINVAL, "sparsify: n must be < 2^32");
     if (k > n) return fail(ctx, FLASHE_EINVAL, "sparsify: k (%llu) > n (%llu)", static_cast<unsigned long long>(k),
                            static_cast<unsigned long long>(n));
-    if (n && k && (!x_dev || !loc_dev || !vals_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
+    // (a layer that keeps nothing only updates its residual: x is read whenever there is something to write, loc / vals only when k > 0)
+    if (n && (k || residual_dev) && !x_dev) return fail(ctx, FLASHE_EINVAL, "null vector");
+    if (n && k && (!loc_dev || !vals_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
     int rc = ensure(ctx, ctx->sp_ws, sparsify_workspace_bytes(n));
     if (rc) return rc;
     HIP_TRY(ctx, launch_sparsify(ctx->env, n, k, x_dev, x_is_f64 != 0, residual_dev, loc_dev, vals_dev, ctx->sp_ws.p));
@@ -3054,8 +3056,8 @@ int flashe_sparsify_batch_dev(flashe_ctx *ctx, int n_layers, const uint64_t *n, 
                                      static_cast<unsigned long long>(n[l]));
         total += n[l]; total_k += k[l];
     }
-    if (total == 0 || total_k == 0) return FLASHE_OK;
-    if (!x_dev || !loc_dev || !vals_dev) return fail(ctx, FLASHE_EINVAL, "null vector");
+    if (total == 0 || (total_k == 0 && !residual_dev)) return FLASHE_OK;       // (total_k == 0 with a residual: every layer only updates it)
+    if (!x_dev || (total_k && (!loc_dev || !vals_dev))) return fail(ctx, FLASHE_EINVAL, "null vector");
     std::vector<unsigned char> desc(sparsify_batch_desc_bytes(n_layers));
     const uint64_t blocks = sparsify_batch_layout(n_layers, n, k, desc.data());
     if (blocks >= (1ull << 32)) return fail(ctx, FLASHE_EINVAL, "sparsify_batch: too many elements");
@@ -3096,8 +3098,8 @@ int flashe_sparsify_tensors_dev(flashe_ctx *ctx, uint64_t n, const flashe_tensor
         v += k[l] * cs;
         total_k += k[l];
     }
-    if (n == 0 || total_k == 0) return FLASHE_OK;
-    if (!loc_dev || !vals_dev) return fail(ctx, FLASHE_EINVAL, "null vector");
+    if (n == 0 || (total_k == 0 && !residual_dev)) return FLASHE_OK;          // (total_k == 0 with a residual: every layer only updates it)
+    if (total_k && (!loc_dev || !vals_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
     std::vector<unsigned char> desc(sparsify_tensors_desc_bytes(n_layers));
     int l32 = 0;
     uint64_t nb32 = 0;
@@ -3149,8 +3151,8 @@ int flashe_sparsify_cohort_tensors_dev(flashe_ctx *ctx, int n_clients, uint64_t 
         v += k[l] * cs;
         total_k += k[l];
     }
-    if (n == 0 || total_k == 0) return FLASHE_OK;
-    if (!loc_dev || !vals_dev) return fail(ctx, FLASHE_EINVAL, "null vector");
+    if (n == 0 || (total_k == 0 && !residual_dev)) return FLASHE_OK;          // (total_k == 0 with residuals: every layer only updates its own)
+    if (total_k && (!loc_dev || !vals_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
     if (loc_stride < total_k || vals_stride < v || (vals_stride & 7u) || (residual_dev && (residual_stride < r || (residual_stride & 7u))))
         return fail(ctx, FLASHE_EINVAL, "sparsify_cohort: a stride is shorter than one client's block or not a multiple of 8 bytes");
     if (static_cast<uint64_t>(n_clients) * loc_stride >= (1ull << 32)) return fail(ctx, FLASHE_EINVAL, "sparsify_cohort: too many locations");

@@ -37,6 +37,7 @@ template <class T> Operand gather(const T *const *srcs, int n, size_t bytes, siz
     return Operand{stride * n, bytes, nullptr, reinterpret_cast<const void *const *>(srcs), n};
 }
 Operand optional(const Operand &o) { return o.src ? o : Operand{0, 0, nullptr, nullptr, 0, nullptr, true}; }
+Operand unless_empty(const Operand &o) { return o.bytes ? o : Operand{0, 0, nullptr, nullptr, 0, nullptr, true}; }
 
 // the device addresses of a gathered operand's parts
 template <class T> std::vector<const T *> parts_of(const Dev &d, int n, size_t stride)
@@ -360,11 +361,11 @@ int flashe_unbatch(flashe_ctx *ctx, uint64_t n_batches, const uint64_t *in, int 
 int flashe_sparsify(flashe_ctx *ctx, uint64_t n, uint64_t k, const void *x, int x_is_f64, void *residual, uint32_t *loc, void *vals)
 {
     CHECK_CTX(ctx);
-    if (n == 0 || k == 0) return FLASHE_OK;
-    if (!x || !loc || !vals) return fail(ctx, FLASHE_EINVAL, "null vector");
+    if (n == 0 || (k == 0 && !residual)) return FLASHE_OK;          // (k == 0 with a residual: the layer only updates it)
+    if (!x || (k && (!loc || !vals))) return fail(ctx, FLASHE_EINVAL, "null vector");
     const size_t es = x_is_f64 ? 8 : 4;
     enum { X, LOC, VALS, RESIDUAL };                              // (the order the blocks are leased in)
-    return staged(ctx, {up(x, n * es), down(loc, k * 4), down(vals, k * es), optional(up_down(residual, n * es))},
+    return staged(ctx, {up(x, n * es), unless_empty(down(loc, k * 4)), unless_empty(down(vals, k * es)), optional(up_down(residual, n * es))},
                   [&](Dev *d) { return flashe_sparsify_dev(ctx, n, k, d[X], x_is_f64, d[RESIDUAL], d[LOC], d[VALS]); });
 }
 
@@ -375,11 +376,11 @@ int flashe_sparsify_batch(flashe_ctx *ctx, int n_layers, const uint64_t *n, cons
     if (n_layers < 0 || (n_layers && (!n || !k))) return fail(ctx, FLASHE_EINVAL, "sparsify_batch: bad arguments");
     uint64_t total = 0, total_k = 0;
     for (int l = 0; l < n_layers; l++) { total += n[l]; total_k += k[l]; }
-    if (total == 0 || total_k == 0) return FLASHE_OK;
-    if (!x || !loc || !vals) return fail(ctx, FLASHE_EINVAL, "null vector");
+    if (total == 0 || (total_k == 0 && !residual)) return FLASHE_OK;
+    if (!x || (total_k && (!loc || !vals))) return fail(ctx, FLASHE_EINVAL, "null vector");
     const size_t es = x_is_f64 ? 8 : 4;
     enum { X, LOC, VALS, RESIDUAL };
-    return staged(ctx, {up(x, total * es), down(loc, total_k * 4), down(vals, total_k * es), optional(up_down(residual, total * es))},
+    return staged(ctx, {up(x, total * es), unless_empty(down(loc, total_k * 4)), unless_empty(down(vals, total_k * es)), optional(up_down(residual, total * es))},
                   [&](Dev *d) { return flashe_sparsify_batch_dev(ctx, n_layers, n, k, d[X], x_is_f64, d[RESIDUAL], d[LOC], d[VALS]); });
 }
 

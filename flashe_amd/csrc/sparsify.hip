@@ -829,7 +829,7 @@ size_t sparsify_workspace_bytes(uint64_t n)
 hipError_t launch_sparsify(const LaunchEnv &env, uint64_t n, uint64_t k, const void *x, bool is_f64, void *residual, uint32_t *loc,
                            void *vals, void *ws)
 {
-    if (n == 0 || k == 0) return hipSuccess;
+    if (n == 0 || (k == 0 && !residual)) return hipSuccess;        // (k == 0 with a residual: the layer only updates it, as in the batch form)
     const uint64_t nb = (n + kSpThreads - 1) / kSpThreads;
     const unsigned g = static_cast<unsigned>(std::min<uint64_t>((nb + 255) / 256, 256));
     hipLaunchKernelGGL(spb_single_kernel, dim3(g), dim3(256), 0, env.stream, static_cast<SpLayer *>(ws), n, k, static_cast<uint32_t>(nb));

@@ -777,7 +777,10 @@ int flashe_unbatch(flashe_ctx *ctx, uint64_t n_batches, const uint64_t *in, int 
  * higher index) are emitted in ascending index order -- loc[k] and vals[k] = x + residual -- and the residual is
  * updated in place (selected positions 0, the others x + residual).  residual may be NULL (treated as zeros, not
  * written).  x / residual / vals are float32 (x_is_f64 == 0) or float64; n < 2^32; k <= n with
- * k = max(1, floor(sparsity * n)) in the reference. */
+ * k = max(1, floor(sparsity * n)) in the reference.
+ * A layer that keeps nothing (k == 0) only updates its residual: residual becomes x + residual, nothing is written to loc / vals.
+ * That holds in every entry point below, whatever the other layers of the call keep -- also when NO layer keeps anything.  loc / vals
+ * may be NULL exactly when the call keeps nothing in total (sum of k == 0); with no residual either, such a call does nothing. */
 int flashe_sparsify_dev(flashe_ctx *ctx, uint64_t n, uint64_t k, const void *x_dev, int x_is_f64, void *residual_dev,
                         uint32_t *loc_dev, void *vals_dev);
 int flashe_sparsify(flashe_ctx *ctx, uint64_t n, uint64_t k, const void *x, int x_is_f64, void *residual,

@@ -205,8 +205,7 @@ def fuzz_sparsify(rng, case):
     at = off = 0
     for li, (s, k) in enumerate(zip(sizes, ks)):
         wl, wv, wr = _topk_ref(layers[li], res[li], k)
-        if single and k == 0:                                           # (flashe_sparsify_dev with k = 0 is a no-op: the residual stays as it was)
-            wr = res[li]
+        # (k = 0: the layer only updates its residual -- in every entry point, whatever the other layers keep)
         assert np.array_equal(loc[at:at + k], wl), ("sparsify/loc", case, li, s, k, dt.__name__, quant)
         assert val[at:at + k].tobytes() == wv.tobytes(), ("sparsify/val", case, li, s, k)
         assert nres[off:off + s].tobytes() == wr.tobytes(), ("sparsify/res", case, li, s, k)
