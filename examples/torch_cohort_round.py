@@ -8,7 +8,9 @@ which this example checks.
 
   --bits B     int_bits of the job (default 128; the reference's shipped un-batched jobs run 20)
   --compact    with --bits <= 32: uint32 ciphertexts and sum (FlasheCohort(compact=True)); at int_bits 16 / 20 / 23 / 24 / 32 the chained
-               launch then goes from the floats to the uint32 ciphertexts"""
+               launch then goes from the floats to the uint32 ciphertexts
+  --batch      a batched job (the reference's *_q16_b6_pad jobs: --bits 120 --batch packs six 20-bit fields per element); the chained
+               launch takes it when the model has enough batched elements to fill the chip"""
 import argparse
 import os
 import sys
@@ -43,10 +45,11 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--bits", type=int, default=128)
     ap.add_argument("--compact", action="store_true")
+    ap.add_argument("--batch", action="store_true")
     opt = ap.parse_args()
     cm.N_JOBS = 16                                           # every party must use the same value
     C, key = 10, bytes(range(32))
-    args = {"quantize": {"int_bits": opt.bits, "batch": False, "element_bits": 16, "padding": True, "secure": True}, "precompute": {"enable": False}}
+    args = {"quantize": {"int_bits": opt.bits, "batch": opt.batch, "element_bits": 16, "padding": True, "secure": True}, "precompute": {"enable": False}}
     models = [make_model(c) for c in range(C)]
     layers = [{name: p.detach() for name, p in m.named_parameters()} for m in models]
 

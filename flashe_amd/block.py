@@ -889,6 +889,7 @@ def cohort_admission_length(cu_count):
     return (2 * 16 * int(cu_count) - 1) * 256 + 1
 
 
+_COHORT_BATCH_SIZES = (5, 6, 7)                     # the values per element compiled into the batched cohort chain (prf_chain_cohort_batch_kernel)
 _COMPACT_COHORT_WIDTHS = (16, 20, 23, 24, 32)       # the widths compiled into the compact chain (FLASHE_FIXED32_WIDTHS, csrc/kernels.hip)
 
 
@@ -919,7 +920,10 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
     layer or location masks -- is a TypeError), lays out the shared layer table and the client-major draws, and picks the path:
       "cohort-chain"  one chained launch from the floats (flashe_quantize_encrypt_cohort_dev): double mask, int_bits > 64, not batched, at
                       most 128 clients, a model of at least cohort_admission_length(cu_count) values, FLASHE_CHAIN not 0, every layer
-                      float64 for all clients or for none;
+                      float64 for all clients or for none.  A batched job at int_bits > 64 takes it too
+                      (flashe_quantize_batch_encrypt_cohort_dev) when bs = int_bits // (element_bits + ceil(log2 num_clients)) is 5, 6
+                      or 7 -- what element_bits 16 gives at int_bits 120 / 128 -- with the length rule counted in batched elements
+                      (n_elems, every layer padded to whole elements on its own);
       "per-client"    precompute handles (and masks other than single / double): the clients' own steps, then aggregate;
       "staged-chain"  everything else: a quantise (+ batch) pass per client into plaintexts, then the summed batch encrypt.
     compact=True (FlasheCohort(compact=True): uint32 ciphertexts at int_bits <= 32) chains through
@@ -962,7 +966,7 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
     for s_ in sizes:
         starts.append(n)
         n += s_
-    n_elems = n
+    n_elems, bs = n, 1
     if batch:
         bs = int_bits // (element_bits + int(np.ceil(np.log2(num_clients))))
         n_elems = sum((s_ + bs - 1) // bs for s_ in sizes)
@@ -976,15 +980,17 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
         path, reason = STAGED_CHAIN, f"int_bits {int_bits} is not a width of the compact chain {_COMPACT_COHORT_WIDTHS}"
     elif not compact and int_bits <= 64:
         path, reason = STAGED_CHAIN, "int_bits <= 64"
-    elif batch:
+    elif batch and compact:
         path, reason = STAGED_CHAIN, "batched job"
+    elif batch and bs not in _COHORT_BATCH_SIZES:
+        path, reason = STAGED_CHAIN, f"batched job with bs {bs}: the chained launch packs {_COHORT_BATCH_SIZES} values per element"
     elif C > _COHORT_MAX_LINKS:
         path, reason = STAGED_CHAIN, f"more than {_COHORT_MAX_LINKS} clients"
     elif not chain:
         path, reason = STAGED_CHAIN, "FLASHE_CHAIN=0"
     elif compact and (n >= 2 ** 32 or compact_cohort_blocks(n, int_bits, n_jobs) < 2 * 128 * 16 * int(cu_count)):
         path, reason = STAGED_CHAIN, "the vector does not fill the chip uncut"
-    elif not compact and (n < cohort_admission_length(cu_count) or n > 2 ** 32):
+    elif not compact and (n_elems < cohort_admission_length(cu_count) or n_elems > 2 ** 32):
         path, reason = STAGED_CHAIN, "the vector does not fill the chip uncut"
     elif mixed:
         path, reason = STAGED_CHAIN, "a layer is float64 for some clients only"
@@ -1000,10 +1006,20 @@ class _CohortLead(FlasheClient):
 
     def _decrypt_floats(self, dv, sizes, mode, add_idx, minus_idx):
         m, q, c = self._cohort_mask, self.quantizer, self.cipher
-        if (m is None or mode is not None or self.batch or dv.ptr != m[0] or c.iter_index != m[2] or list(add_idx) != [m[3]]
+        if (m is None or mode is not None or dv.ptr != m[0] or c.iter_index != m[2] or list(add_idx) != [m[3]]
                 or list(minus_idx) != [m[4]] or len(dv) != len(m[1])):
             return super()._decrypt_floats(dv, sizes, mode, add_idx, minus_idx)
         eng, n = c.engine, len(dv)
+        if self.batch:
+            # (the batched sum: combine + unbatch + `[:size]` + unquantise in one pass, as the parent's decrypt launch + unbatch launch)
+            field_bits = q.element_bits + int(np.ceil(np.log2(q.num_clients)))
+            bs = self.int_bits // field_bits
+            if sum((s_ + bs - 1) // bs for s_ in sizes) != n:
+                raise ValueError(f"the aggregate has {n} elements, the batched layers describe {sum((s_ + bs - 1) // bs for s_ in sizes)}")
+            layers = [(s_, None, q.alpha_list[li], False) for li, s_ in enumerate(sizes)]
+            dout = eng.alloc(max(8 * sum(sizes), 16))
+            eng.combine_unbatch_unquantize_model_dev(layers, q.element_bits, field_bits, q.num_clients, dv.buf, m[1].buf, None, n, dout)
+            return dout
         if sum(sizes) > n:
             raise ValueError(f"the aggregate has {n} elements, shape_dict describes {sum(sizes)}")
         table, at = [], 0
@@ -1023,6 +1039,8 @@ class FlasheCohort(object):
     float model, encrypts with the PRF streams consecutive clients share (n_local + 1 instead of 2 n_local) and writes their sum and the
     decrypt mask, and one memory-bound pass turns the sum into the new float model.  All clients share one quantiser state (every
     client's mean / std / alpha history derives from the same global model).  `path` of the result names the form that ran.
+    A batched job at int_bits > 64 whose elements hold 5, 6 or 7 values (element_bits 16 at int_bits 120 / 128) chains too, over its batched
+    elements (flashe_quantize_batch_encrypt_cohort_dev), and the decrypt of its own sum is one combine + unbatch + unquantise pass.
     compact=True (int_bits <= 32 on an engine whose compact_supported() is true; ValueError otherwise): every ciphertext and the sum are
     compact DeviceVectors (uint32, elem_bytes 4) whatever path ran, and at int_bits 16 / 20 / 23 / 24 / 32 -- the widths the shipped jobs
     run -- the chained launch goes from the floats to the uint32 ciphertexts and their sum (flashe_quantize_encrypt_cohort_u32_dev: 16
@@ -1199,8 +1217,16 @@ class FlasheCohort(object):
                     for li, (st, _p, al, sh, _code, fl) in enumerate(tables[0])]
             srcs = [[t[1] for t in table] for table in tables]
             dts = [[t[4] for t in table] for table in tables]
-            dmask = DeviceVector(eng, n) if whole and not self.compact else None
-            if self.compact:
+            dmask = DeviceVector(eng, n_elems) if whole and not self.compact else None
+            if ld.batch and not self.compact:
+                field_bits = q.element_bits + int(np.ceil(np.log2(q.num_clients)))
+                if eng.quantize_batch_encrypt_cohort_dev(c.iter_index, self.first_idx, n, n_elems, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits,
+                                                         field_bits, du, [v.buf for v in cts], psum.buf, dmask.buf if dmask is not None else None):
+                    if dmask is not None:
+                        ld._cohort_mask = (psum.ptr, dmask, c.iter_index, self.first_idx + C, self.first_idx)
+                else:
+                    path = STAGED_CHAIN
+            elif self.compact:
                 # (no decrypt mask at these widths: the decrypt of the sum is 2 / m AES blocks per element)
                 if not eng.quantize_encrypt_cohort_u32_dev(c.iter_index, self.first_idx, n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du,
                                                            [v.buf for v in cts], psum.buf):

@@ -1740,6 +1740,62 @@ int flashe_quantize_encrypt_cohort_u32_dev(flashe_ctx *ctx, uint32_t iter, uint3
     return FLASHE_OK;
 }
 
+// the cohort of a BATCHED job (prf_chain_cohort_batch_kernel): the same table, sources and stage pass over the n_values values; the chain
+// runs over the n_elems batched elements
+int flashe_quantize_batch_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n_values, uint64_t n_elems,
+                                             uint32_t n_jobs, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
+                                             const int32_t *src_dtype, int element_bits, int field_bits, const double *u_dev, uint64_t *const *ct_dev,
+                                             uint64_t *sum_out_dev, uint64_t *dmask_dev)
+{
+    CHECK_CTX(ctx);
+    static const char who[] = "flashe_quantize_batch_encrypt_cohort_dev";
+    std::vector<uint32_t> idx;
+    int rc = cohort_check(ctx, who, first_idx, n_clients, n_values, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, idx);
+    if (rc) return rc;
+    if (field_bits < element_bits || field_bits > ctx->int_bits)
+        return fail(ctx, FLASHE_EINVAL, "need 1 <= element_bits <= field_bits <= int_bits (element_bits <= 62)");
+    // the batched rows of the non-empty layers (cohort_stage's rows, in its order): first element, value count
+    const uint64_t bs = static_cast<uint64_t>(ctx->int_bits / field_bits);
+    std::vector<uint64_t> rows;
+    uint64_t e = 0;
+    for (int l = 0; l < n_layers; l++) {
+        const uint64_t size = (l + 1 < n_layers ? layers[l + 1].start : n_values) - layers[l].start;
+        if (size == 0) continue;
+        rows.push_back(e);
+        rows.push_back(size);
+        e += (size + bs - 1) / bs;                         // every layer is padded to whole elements on its own (jzf_quantize.py:166-171)
+    }
+    if (e != n_elems) return fail(ctx, FLASHE_EINVAL, "the layers batch into %llu elements, n_elems says %llu", static_cast<unsigned long long>(e),
+                                  static_cast<unsigned long long>(n_elems));
+    for (int c = 0; c < n_clients; c++) {
+        if (!ct_dev[c]) return fail(ctx, FLASHE_EINVAL, "client %d: null ciphertext", c);
+        if ((rc = check_prf_args(ctx, 1, 1, n_jobs, ct_dev[c], nullptr, 0))) return rc;
+        if (ct_dev[c] == sum_out_dev || ct_dev[c] == dmask_dev) return fail(ctx, FLASHE_EINVAL, "client %d: the ciphertext aliases the sum or the mask", c);
+    }
+    if ((rc = check_sum_aligned(ctx, sum_out_dev))) return rc;
+    if (dmask_dev && (!aligned16(dmask_dev) || dmask_dev == sum_out_dev)) return fail(ctx, FLASHE_EINVAL, "dmask_dev must be 16-byte aligned and apart from the sum");
+    // the shapes the chained launch does not take, refused before anything is staged (launch_prf_cohort_batch_sum's own rule is the final word)
+    {
+        const uint64_t waves = static_cast<uint64_t>(ctx->env.num_cus) * 16;
+        if (ctx->limbs != 2 || !ctx->env.use_chain || n_clients > 128 || bs < 5 || bs > 7 || (n_elems + 255) / 256 < 2 * waves || n_elems == 0 ||
+            ((n_elems - 1) >> 32) || (ctx->env.prf_backend != PRF_AUTO && ctx->env.prf_backend != PRF_TABLE))
+            return fail(ctx, FLASHE_ENOTSUP, "%s: not a shape of the chained batched cohort launch", who);
+    }
+    CohortCodec cc{};
+    const char *rows_dev = nullptr;
+    if ((rc = cohort_stage(ctx, n_clients, n_values, layers, n_layers, src_dev, src_dtype, element_bits, cc, rows.data(), rows.size() * sizeof(uint64_t),
+                           &rows_dev)))
+        return rc;
+    CohortBatch cb{};
+    cb.rows = reinterpret_cast<const uint64_t *>(rows_dev);
+    cb.n_values = n_values;
+    cb.field_bits = field_bits;
+    const hipError_t err = launch_prf_cohort_batch_sum(ctx->env, iter, n_clients, idx.data(), cc, cb, u_dev, ct_dev, sum_out_dev, n_elems, n_jobs, dmask_dev);
+    if (err == hipErrorNotSupported) return fail(ctx, FLASHE_ENOTSUP, "%s: not a shape of the chained batched cohort launch", who);
+    HIP_TRY(ctx, err);
+    return FLASHE_OK;
+}
+
 int flashe_combine_unquantize_model_dev(flashe_ctx *ctx, uint64_t n, const uint64_t *in_dev, const uint64_t *add_dev, const uint64_t *minus_dev,
                                         const flashe_codec_layer *layers, int n_layers, int element_bits, int num_clients, double *out_dev)
 {
@@ -1757,6 +1813,28 @@ int flashe_combine_unquantize_model_dev(flashe_ctx *ctx, uint64_t n, const uint6
     Codec cq{};
     cq.fout = out_dev; cq.layers = tab; cq.n_layers = n_tab; cq.k0 = 0;
     HIP_TRY(ctx, launch_combine_unquantize_model(ctx->env, n, in_dev, add_dev, minus_dev, cq, out_dev));
+    return FLASHE_OK;
+}
+
+// the batched sibling: unbatch + unquantise over (in + add - minus) mod 2^b, the masks held by the caller
+int flashe_combine_unbatch_unquantize_model_dev(flashe_ctx *ctx, const flashe_batch_layer *layers, int n_layers, int element_bits, int field_bits,
+                                                int num_clients, const uint64_t *in_dev, const uint64_t *add_dev, const uint64_t *minus_dev,
+                                                uint64_t n_elems, double *out_dev)
+{
+    CHECK_CTX(ctx);
+    if (num_clients < 1) return fail(ctx, FLASHE_EINVAL, "num_clients must be >= 1");
+    const BatchLayer *tab = nullptr;
+    int n_tab = 0;
+    uint64_t e = 0, v = 0;
+    int rc = stage_batch_layers(ctx, layers, n_layers, false, element_bits, field_bits, num_clients, &e, &v, &tab, &n_tab);
+    if (rc) return rc;
+    if (e != n_elems) return fail(ctx, FLASHE_EINVAL, "the layers batch into %llu elements, n_elems says %llu", static_cast<unsigned long long>(e),
+                                  static_cast<unsigned long long>(n_elems));
+    if (v && (!in_dev || !out_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
+    for (const uint64_t *p : {in_dev, add_dev, minus_dev})
+        if (p && ((ctx->limbs == 2 && !aligned16(p)) || (reinterpret_cast<uintptr_t>(p) & 7u))) return fail(ctx, FLASHE_EINVAL, "misaligned vector");
+    if (reinterpret_cast<uintptr_t>(out_dev) & 7u) return fail(ctx, FLASHE_EINVAL, "out_dev must be 8-byte aligned");
+    if (v) HIP_TRY(ctx, launch_combine_unbatch_unquantize_model(ctx->env, tab, n_tab, field_bits, in_dev, add_dev, minus_dev, v, out_dev));
     return FLASHE_OK;
 }
 

@@ -378,11 +378,13 @@ __global__ __launch_bounds__(kStreamThreads) void combine_unbatch_unquantize_mod
         const int slot = static_cast<int>(j % static_cast<uint64_t>(bs));
         u128 item;
         if (WIDE) {
-            item = ld128(in + 2 * e) + ld128(add + 2 * e);
+            item = ld128(in + 2 * e);
+            if (add) item += ld128(add + 2 * e);                        // (NULL = zeros: flashe_combine_unbatch_unquantize_model_dev admits it)
             if (minus) item -= ld128(minus + 2 * e);
             item &= mask;
         } else {
-            uint64_t x = in[e] + add[e];
+            uint64_t x = in[e];
+            if (add) x += add[e];
             if (minus) x -= minus[e];
             item = static_cast<u128>(x & mask_lo);
         }

@@ -529,6 +529,76 @@ __device__ __forceinline__ uint64_t cohort_quantize_lane(const CohortCodec &cc, 
     return cohort_quantize_raw(cohort_load(cc.src[static_cast<size_t>(link) * cc.n_layers + lo], f64, k - L->start), f64, L->p0, L->p1, L->p2, u);
 }
 
+// ---- the batched cohort front end (CohortBatch, prf_chain_cohort_batch_kernel) ----
+// wave-uniform key: the table row that holds batched element `key` (the last row whose first element is <= key), found with scalar loads
+__device__ __forceinline__ int cohort_batch_row_of(const CohortBatch &cb, int n_layers, uint64_t key)
+{
+    int lo = 0, hi = n_layers - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (*FLASHE_CONSTANT(const uint64_t, cb.rows + 2 * mid) <= key) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+// One batched element of one client: values j0 .. j0 + BS - 1 of a row (xs = the client's values of the row, ud = its draws of the row,
+// size = the row's value count; values at or past it are pads, 0), quantised and packed first value most significant --
+// quantize_batch_model_kernel's arithmetic.
+// The walking form, value by value in a rolled loop (a handful of registers): the row's last element when it has pads, and every element
+// whose row is looked up per lane.
+template <int BS>
+__device__ __forceinline__ u128 cohort_batch_walk(const void *xs, bool f64, double p0, double p1, double p2, const double *ud, uint64_t j0,
+                                                  uint64_t size, int field_bits)
+{
+    u128 x = 0;
+#pragma unroll 1
+    for (int t = 0; t < BS; t++) {
+        const uint64_t j = j0 + t;
+        uint64_t q = 0;
+        if (j < size) q = cohort_quantize_raw(cohort_load(xs, f64, j), f64, p0, p1, p2, *FLASHE_GLOBAL(const double, ud + j));
+        x = (x << field_bits) + q;                                                                       // temp *= mod; temp += value
+    }
+    return x;
+}
+// The form of the whole tiles: a whole element requests its floats and its draws in runs (cohort_load_run), and nothing but the packed
+// plaintext is live afterwards.
+template <int BS>
+__device__ __forceinline__ u128 cohort_batch_element(const void *xs, bool f64, double p0, double p1, double p2, const double *ud, uint64_t j0,
+                                                     uint64_t size, int field_bits)
+{
+    if (j0 + BS > size) return cohort_batch_walk<BS>(xs, f64, p0, p1, p2, ud, j0, size, field_bits);
+    uint64_t ub[BS], q[BS];
+    cohort_load_run<BS>(reinterpret_cast<const uint64_t *>(ud) + j0, ub);
+    if (f64) {
+        uint64_t raw[BS];
+        cohort_load_run<BS>(static_cast<const uint64_t *>(xs) + j0, raw);
+#pragma unroll
+        for (int t = 0; t < BS; t++) q[t] = cohort_quantize_raw(raw[t], true, p0, p1, p2, __longlong_as_double(static_cast<long long>(ub[t])));
+    } else {
+        uint32_t raw[BS];
+        cohort_load_run<BS>(static_cast<const uint32_t *>(xs) + j0, raw);
+#pragma unroll
+        for (int t = 0; t < BS; t++) q[t] = cohort_quantize_raw(raw[t], false, p0, p1, p2, __longlong_as_double(static_cast<long long>(ub[t])));
+    }
+    u128 x = 0;
+#pragma unroll
+    for (int t = 0; t < BS; t++) x = (x << field_bits) + q[t];
+    return x;
+}
+// the row looked up per lane, for the pairs that straddle a row boundary and the tiles at the range ends: link's plaintext of batched
+// element e (u = the link's draws, value-indexed)
+template <int BS>
+__device__ __forceinline__ u128 cohort_batch_lane(const CohortCodec &cc, const CohortBatch &cb, int link, uint64_t e, const double *u)
+{
+    int lo = 0, hi = cc.n_layers - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (cb.rows[2 * mid] <= e) lo = mid; else hi = mid - 1;
+    }
+    const CodecLayer *L = cc.layers + lo;
+    return cohort_batch_walk<BS>(cc.src[static_cast<size_t>(link) * cc.n_layers + lo], L->x_is_f64 != 0, L->p0, L->p1, L->p2, u + L->start,
+                                 (e - cb.rows[2 * lo]) * static_cast<uint64_t>(BS), cb.rows[2 * lo + 1], cb.field_bits);
+}
+
 // _static_unquantize_padding_asymmetric (jzf_quantize.py:102-107); k = the element's index in the launch (selects the layer)
 __device__ __forceinline__ double codec_unquantize(const Codec &c, uint64_t k, u128 v)
 {

@@ -95,6 +95,21 @@ struct CohortCodec {
 // rule and the same hipErrorNotSupported -- nothing launched -- contract; dmask_dev is optional.
 hipError_t launch_prf_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
                                  uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs, uint64_t *dmask_dev = nullptr);
+// The BATCHED cohort (prf_chain_cohort_batch_kernel): the chain runs over the model's n_elems batched elements (as BatchLayer's: every
+// layer padded to whole elements on its own) and element e of table row l holds bs = int_bits / field_bits values of every client, the
+// first one most significant.  cc is the table of the un-batched launch (row l: start = the layer's first VALUE among the n_values of the
+// model, alpha / scale / den, the compute type; src as above); rows[2 l], rows[2 l + 1] = the row's first element and its value count.
+struct CohortBatch {
+    const uint64_t *rows;
+    uint64_t n_values;         // values of one model: client c's draws are u_dev[c * n_values ..]
+    int field_bits, pad_;
+};
+// launch_prf_cohort_sum with that front end: client c's plaintext of element e = quantize_batch_model_kernel's, with the draws
+// u_dev[c * n_values + value index].  Admitted where launch_prf_cohort_sum is, counted in elements (two whole 256-element tiles per
+// wave, n_elems <= 2^32), and for bs = env.b / field_bits in {5, 6, 7} only; hipErrorNotSupported: nothing launched.
+hipError_t launch_prf_cohort_batch_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const CohortBatch &cb,
+                                       const double *u_dev, uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n_elems, uint32_t n_jobs,
+                                       uint64_t *dmask_dev = nullptr);
 // The same cohort at int_bits <= 32 in the compact layout (prf_small_cohort_kernel): uint32 ciphertexts and their uint32 sum from the
 // floats, admitted where the summed compact chain is -- int_bits 16 / 20 / 23 / 24 / 32, the table PRF, the chained kernels, consecutive
 // idx below 2^32 - 1, at most kMaxLinks clients, 0 < n < 2^32 and at least 2 x 128 AES blocks (of 128 / int_bits elements, per the

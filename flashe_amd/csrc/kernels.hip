@@ -356,8 +356,10 @@ __global__ __launch_bounds__(THREADS) void prf_chain_kernel(const RoundKeys rk, 
                                                               const uint32_t *__restrict__ te0, const Codec cq)
 {
     constexpr bool DMASK = false, D128 = false, COHORT = false;
+    constexpr int BS = 0;
     uint64_t *const dmask = nullptr;
     const CohortCodec cc{};
+    const CohortBatch cb{};
 #include "prf_chain_body.inc"
 }
 
@@ -368,8 +370,10 @@ __global__ __launch_bounds__(THREADS) void prf_chain_dmask_kernel(const RoundKey
                                                                     const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask)
 {
     constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = false;
+    constexpr int BS = 0;
     const Codec cq{};
     const CohortCodec cc{};
+    const CohortBatch cb{};
 #include "prf_chain_body.inc"
 }
 
@@ -382,8 +386,10 @@ __global__ __launch_bounds__(THREADS) void prf_dmask_sum128_kernel(const RoundKe
                                                                      const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask)
 {
     constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = true, COHORT = false;
+    constexpr int BS = 0;
     const Codec cq{};
     const CohortCodec cc{};
+    const CohortBatch cb{};
 #include "prf_chain_body.inc"
 }
 
@@ -401,6 +407,23 @@ __global__ __launch_bounds__(THREADS) void prf_chain_cohort_kernel(const RoundKe
                                                                      const CohortCodec cc)
 {
     constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true;
+    constexpr int BS = 0;
+    const Codec cq{};
+    const CohortBatch cb{};
+#include "prf_chain_body.inc"
+}
+
+// BS > 0: the same cohort for a BATCHED job -- the chain runs over the model's batched elements, and output c of element e packs BS_ values
+// of client c (quantize_batch_model_kernel's plaintext, first value most significant), quantised from its floats and draws before the
+// stream's rounds.  Compiled for the BS_ the shipped batched jobs give (element_bits 16: int_bits // (16 + ceil(log2 num_clients))).
+template <int THREADS, int BS_>
+__global__ __launch_bounds__(THREADS) void prf_chain_cohort_batch_kernel(const RoundKeys rk, const ChainTable tb, int n_chains, int all_half_arg,
+                                                                           uint32_t iter0, uint64_t mask_lo, uint64_t mask_hi,
+                                                                           const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask,
+                                                                           const CohortCodec cc, const CohortBatch cb)
+{
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true;
+    constexpr int BS = BS_;
     const Codec cq{};
 #include "prf_chain_body.inc"
 }
@@ -1870,6 +1893,46 @@ hipError_t launch_prf_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec,
     const int grid = static_cast<int>(std::min<uint64_t>(tiles, static_cast<uint64_t>(env.num_cus)));
     hipLaunchKernelGGL((prf_chain_cohort_kernel<kPrfThreads>), dim3(grid), dim3(kPrfThreads), 0, env.stream, env.rk, tb, 1, 0, iter, lo, hi,
                        env.te0_dev, dmask_dev, cc);
+    return hipGetLastError();
+}
+
+// the batched form of launch_prf_cohort_sum (prf_chain_cohort_batch_kernel): the same uncut chain over the n_elems batched elements
+hipError_t launch_prf_cohort_batch_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const CohortBatch &cb,
+                                       const double *u_dev, uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n_elems, uint32_t n_jobs,
+                                       uint64_t *dmask_dev)
+{
+    (void)n_jobs;                            // (int_bits > 64: counters do not depend on the chunking)
+    if (n_elems == 0 || n_vec <= 0) return hipErrorNotSupported;
+    if (!env.use_chain || env.b <= 64 || env.codec || n_vec > kMaxLinks || !sum_out_dev || !u_dev || cc.n_layers < 1 || !cb.rows) return hipErrorNotSupported;
+    if (env.prf_backend != PRF_AUTO && env.prf_backend != PRF_TABLE) return hipErrorNotSupported;
+    for (int v = 1; v < n_vec; v++) if (idx[v] != idx[v - 1] + 1u) return hipErrorNotSupported;
+    if (idx[n_vec - 1] == 0xffffffffu) return hipErrorNotSupported;
+    if (cb.field_bits < 1 || cb.field_bits > env.b) return hipErrorNotSupported;
+    const int bs = env.b / cb.field_bits;
+    if (bs < 5 || bs > 7) return hipErrorNotSupported;                   // the compiled batch sizes
+    const uint64_t waves = static_cast<uint64_t>(env.num_cus) * (kPrfThreads / 64), tiles = (n_elems + 255) / 256;
+    if (tiles < 2 * waves) return hipErrorNotSupported;                 // (launch_prf_batch_sum's rule, counted in elements)
+    if ((n_elems - 1) >> 32) return hipErrorNotSupported;                // one counter window
+    for (int v = 0; v < n_vec; v++) if (!out_dev[v]) return hipErrorNotSupported;
+    ChainTable tb{};
+    tb.first[0] = 0; tb.count[0] = n_elems;
+    tb.len[0] = static_cast<uint8_t>(n_vec);
+    tb.sum_out[0] = sum_out_dev;
+    for (int s = 0; s < n_vec; s++) tb.idx[s] = idx[s];
+    tb.idx[n_vec] = idx[n_vec - 1] + 1u;
+    for (int l = 0; l < n_vec; l++) {
+        tb.in[l] = reinterpret_cast<const uint64_t *>(u_dev + static_cast<uint64_t>(l) * cb.n_values);     // the link's draws, one per VALUE
+        tb.out[l] = out_dev[l];
+    }
+    tb.wend[0] = tiles * static_cast<uint64_t>(n_vec + 1);
+    uint64_t lo, hi;
+    masks_of(env.b, &lo, &hi);
+    const dim3 grid(static_cast<unsigned>(std::min<uint64_t>(tiles, static_cast<uint64_t>(env.num_cus)))), block(kPrfThreads);
+    switch (bs) {
+    case 5: hipLaunchKernelGGL((prf_chain_cohort_batch_kernel<kPrfThreads, 5>), grid, block, 0, env.stream, env.rk, tb, 1, 0, iter, lo, hi, env.te0_dev, dmask_dev, cc, cb); break;
+    case 6: hipLaunchKernelGGL((prf_chain_cohort_batch_kernel<kPrfThreads, 6>), grid, block, 0, env.stream, env.rk, tb, 1, 0, iter, lo, hi, env.te0_dev, dmask_dev, cc, cb); break;
+    default: hipLaunchKernelGGL((prf_chain_cohort_batch_kernel<kPrfThreads, 7>), grid, block, 0, env.stream, env.rk, tb, 1, 0, iter, lo, hi, env.te0_dev, dmask_dev, cc, cb); break;
+    }
     return hipGetLastError();
 }
 

@@ -1,6 +1,11 @@
 // The body of prf_chain_kernel<THREADS, SUM, CODEC>, prf_chain_dmask_kernel<THREADS>, prf_dmask_sum128_kernel<THREADS> and
-// prf_chain_cohort_kernel<THREADS> (kernels.hip), included INSIDE each kernel: the kernel defines THREADS, SUM, CODEC, DMASK, D128 and COHORT
-// as compile-time constants and has the arguments rk, tb, n_chains, all_half_arg, iter0, mask_lo, mask_hi, te0, cq, cc and dmask in scope.
+// prf_chain_cohort_kernel<THREADS> and prf_chain_cohort_batch_kernel<THREADS, BS> (kernels.hip), included INSIDE each kernel: the kernel defines
+// THREADS, SUM, CODEC, DMASK, D128, COHORT and BS as compile-time constants and has the arguments rk, tb, n_chains, all_half_arg, iter0, mask_lo,
+// mask_hi, te0, cq, cc, cb and dmask in scope.
+// BS > 0 (COHORT only): the BATCHED cohort -- the chain's elements are the model's batched elements and every output's plaintext packs BS
+// quantised values of its client (CohortBatch cb beside cc; tb.in[link] = that client's draws, value-indexed).  The floats and draws of an
+// element are requested in runs, quantised and packed BEFORE the stream's rounds (cohort_batch_element): only the two packed plaintexts
+// live through the rounds.  Every branch on BS is an `if constexpr`: the other instantiations compile to the kernels they were.
 // COHORT: one summed double-mask chain whose every output has a quantising front end (CohortCodec cc; tb.in[link] = that client's draws).  D128: the launch is one summed double-mask
 // chain at int_bits = 128 with one-limb inputs (launch_prf_chains), and its whole tiles run prf_chain_sum128_tile.inc.  (A __device__ function shared by both would do, but its blockDim is lowered before it
 // is inlined -- the non-uniform-workgroup form -- and the headline kernel's code would change with it; included text compiles to
@@ -8,8 +13,10 @@
     static_assert(!DMASK || (SUM && !CODEC), "the decrypt mask is written by summed chains only");
     static_assert(!D128 || DMASK, "the int_bits = 128 specialisation is the decrypt-mask chain's");
     static_assert(!COHORT || (DMASK && !D128), "the cohort front end rides on the summed decrypt-mask chain");
+    static_assert(BS == 0 || COHORT, "batching is a form of the cohort front end");
     (void)dmask;
     (void)cc;
+    (void)cb;
     const uint32_t iter = iter0 + te0[kIterShiftWord];
     constexpr uint32_t WAVES = THREADS / 64;
     __shared__ uint32_t tab[kTabWords];
@@ -112,8 +119,13 @@
                     const uint64_t jb = tj + 128u * p, kb = (jb > first ? jb : first) - first, ke = (jb + 128u < end ? jb + 128u : end) - first;
                     int l = -1;
                     if (jb < end && jb + 128u > first) {
-                        l = cohort_layer_of(cc, kb);
-                        if (l + 1 < cc.n_layers && *FLASHE_CONSTANT(const uint64_t, &cc.layers[l + 1].start) < ke) l = -1;
+                        if constexpr (BS > 0) {
+                            l = cohort_batch_row_of(cb, cc.n_layers, kb);
+                            if (l + 1 < cc.n_layers && *FLASHE_CONSTANT(const uint64_t, cb.rows + 2 * (l + 1)) < ke) l = -1;
+                        } else {
+                            l = cohort_layer_of(cc, kb);
+                            if (l + 1 < cc.n_layers && *FLASHE_CONSTANT(const uint64_t, &cc.layers[l + 1].start) < ke) l = -1;
+                        }
                     }
                     if (p == 0) layA = l; else layB = l;
                 }
@@ -141,7 +153,26 @@
                         bool cf64 = false;
                         const int crow = COHORT && link >= 0 ? layA : -1;
                         u128 x0 = 0, x1 = 0;
-                        if constexpr (COHORT) {
+                        if constexpr (BS > 0) {
+                            // (the batched front end: packed before the rounds; row crow >= 0: its parameters in SGPRs, else looked up per lane)
+                            if (link >= 0) {
+                                const double *const ud = reinterpret_cast<const double *>(in);
+                                if (crow >= 0) {
+                                    const CodecLayer *const L = cc.layers + crow;
+                                    const uint64_t vs = *FLASHE_CONSTANT(const uint64_t, &L->start), es = *FLASHE_CONSTANT(const uint64_t, cb.rows + 2 * crow),
+                                                   sz = *FLASHE_CONSTANT(const uint64_t, cb.rows + 2 * crow + 1);
+                                    const void *const xs = reinterpret_cast<const void *>(*FLASHE_CONSTANT(const uintptr_t, cc.src + static_cast<size_t>(link0 + link) * cc.n_layers + crow));
+                                    const bool bf64 = *FLASHE_CONSTANT(const int, &L->x_is_f64) != 0;
+                                    const double b0 = *FLASHE_CONSTANT(const double, &L->p0), b1 = *FLASHE_CONSTANT(const double, &L->p1),
+                                                 b2 = *FLASHE_CONSTANT(const double, &L->p2);
+                                    if (a0) x0 = cohort_batch_element<BS>(xs, bf64, b0, b1, b2, ud + vs, (k0 - es) * static_cast<uint64_t>(BS), sz, cb.field_bits);
+                                    if (a1) x1 = cohort_batch_element<BS>(xs, bf64, b0, b1, b2, ud + vs, (k1 - es) * static_cast<uint64_t>(BS), sz, cb.field_bits);
+                                } else {
+                                    if (a0) x0 = cohort_batch_lane<BS>(cc, cb, link0 + link, k0, ud);
+                                    if (a1) x1 = cohort_batch_lane<BS>(cc, cb, link0 + link, k1, ud);
+                                }
+                            }
+                        } else if constexpr (COHORT) {
                             if (link >= 0) {
                                 const double *const ud = reinterpret_cast<const double *>(in);
                                 if (a0) u0 = *FLASHE_GLOBAL(const double, ud + k0);
@@ -174,7 +205,7 @@
                         ctr_round2(lr, pre.u[0], vA0, U, s[0]);
                         ctr_round2(lr, pre.u[0], vA1, U, s[1]);
                         aes256_rounds<2, 3>(rk, lr, s, true);
-                        if constexpr (COHORT) {
+                        if constexpr (COHORT && BS == 0) {
                             cohort_loads_landed(raw0, raw1, u0, u1);
                             x0 = crow >= 0 ? cohort_quantize_raw(raw0, cf64, cp0, cp1, cp2, u0) : raw0;
                             x1 = crow >= 0 ? cohort_quantize_raw(raw1, cf64, cp0, cp1, cp2, u1) : raw1;
@@ -273,8 +304,13 @@
             int lay = -1;                                               // COHORT: the pair's table row, as in a whole tile
             if constexpr (COHORT) {
                 const uint64_t kb = (tj > first ? tj : first) - first, ke = (tj + 128u < end ? tj + 128u : end) - first;
-                lay = cohort_layer_of(cc, kb);
-                if (lay + 1 < cc.n_layers && *FLASHE_CONSTANT(const uint64_t, &cc.layers[lay + 1].start) < ke) lay = -1;
+                if constexpr (BS > 0) {
+                    lay = cohort_batch_row_of(cb, cc.n_layers, kb);
+                    if (lay + 1 < cc.n_layers && *FLASHE_CONSTANT(const uint64_t, cb.rows + 2 * (lay + 1)) < ke) lay = -1;
+                } else {
+                    lay = cohort_layer_of(cc, kb);
+                    if (lay + 1 < cc.n_layers && *FLASHE_CONSTANT(const uint64_t, &cc.layers[lay + 1].start) < ke) lay = -1;
+                }
             }
             u128 p0 = 0, p1 = 0, q0 = 0, q1 = 0;
             uint64_t *const sum_out = SUM ? tb.sum_out[cur] : nullptr;
@@ -285,7 +321,26 @@
                 const uint64_t *in = link >= 0 ? tb.in[link0 + link] : nullptr;
                 uint64_t *out = link >= 0 ? tb.out[link0 + link] : nullptr;
                 u128 x0 = 0, x1 = 0;
-                if constexpr (COHORT) {
+                if constexpr (BS > 0) {
+                    // (the batched front end: packed before the rounds; row lay >= 0: its parameters in SGPRs, else looked up per lane)
+                    if (link >= 0) {
+                        const double *const ud = reinterpret_cast<const double *>(in);
+                        if (lay >= 0) {
+                            const CodecLayer *const L = cc.layers + lay;
+                            const uint64_t vs = *FLASHE_CONSTANT(const uint64_t, &L->start), es = *FLASHE_CONSTANT(const uint64_t, cb.rows + 2 * lay),
+                                           sz = *FLASHE_CONSTANT(const uint64_t, cb.rows + 2 * lay + 1);
+                            const void *const xs = reinterpret_cast<const void *>(*FLASHE_CONSTANT(const uintptr_t, cc.src + static_cast<size_t>(link0 + link) * cc.n_layers + lay));
+                            const bool bf64 = *FLASHE_CONSTANT(const int, &L->x_is_f64) != 0;
+                            const double b0 = *FLASHE_CONSTANT(const double, &L->p0), b1 = *FLASHE_CONSTANT(const double, &L->p1),
+                                         b2 = *FLASHE_CONSTANT(const double, &L->p2);
+                            if (a0) x0 = cohort_batch_element<BS>(xs, bf64, b0, b1, b2, ud + vs, (k0 - es) * static_cast<uint64_t>(BS), sz, cb.field_bits);
+                            if (a1) x1 = cohort_batch_element<BS>(xs, bf64, b0, b1, b2, ud + vs, (k1 - es) * static_cast<uint64_t>(BS), sz, cb.field_bits);
+                        } else {
+                            if (a0) x0 = cohort_batch_lane<BS>(cc, cb, link0 + link, k0, ud);
+                            if (a1) x1 = cohort_batch_lane<BS>(cc, cb, link0 + link, k1, ud);
+                        }
+                    }
+                } else if constexpr (COHORT) {
                     // (a launch's few half tiles: quantised before the rounds)
                     if (link >= 0) {
                         const double *const ud = reinterpret_cast<const double *>(in);

@@ -656,6 +656,32 @@ class Engine:
         self._check(rc)
         return True
 
+    def quantize_batch_encrypt_cohort_dev(self, it, first_idx, n_values, n_elems, n_jobs, layers, srcs, dtypes, element_bits, field_bits, u, cts,
+                                          sum_out, dmask=None):
+        """quantize_encrypt_cohort_dev for a BATCHED job (flashe_quantize_batch_encrypt_cohort_dev, int_bits > 64, int_bits // field_bits
+        in 5 .. 7): layers / srcs / dtypes describe the n_values values of the model as there, u = the len(srcs) * n_values draws,
+        client-major; cts, sum_out and dmask (optional) are vectors of the n_elems batched elements.  Returns False -- nothing was
+        launched -- when the library declines the shape (FLASHE_ENOTSUP: the caller runs quantize_batch_tensors_dev per client and
+        encrypt_batch_sum_dev), True otherwise."""
+        arr, nl = self._tensor_layers(layers)
+        C = len(srcs)
+        ps = (c_vp * max(C * nl, 1))(*[int(p) if p else None for row in srcs for p in row])
+        pd = (ctypes.c_int32 * max(C * nl, 1))(*[int(d) for row in dtypes for d in row])
+        pc, _k = self._ptr_array(cts)
+        rc = self._lib.flashe_quantize_batch_encrypt_cohort_dev(self._h, it, int(first_idx), C, int(n_values), int(n_elems), n_jobs, arr, nl, ps, pd,
+                                                                element_bits, field_bits, self._ptr(u), pc, self._ptr(sum_out), self._ptr(dmask))
+        if rc == _lib.ENOTSUP:
+            return False
+        self._check(rc)
+        return True
+
+    def combine_unbatch_unquantize_model_dev(self, layers, element_bits, field_bits, num_clients, inp, add, minus, n_elems, out):
+        """unbatch_unquantize_model_dev over (inp + add - minus) mod 2^b, one memory-bound pass (add / minus: device vectors of n_elems
+        elements or None); layers as for unbatch_unquantize_model_dev."""
+        arr, nl = self._batch_layers(layers)
+        self._check(self._lib.flashe_combine_unbatch_unquantize_model_dev(self._h, arr, nl, element_bits, field_bits, num_clients, self._ptr(inp),
+                                                                          self._ptr(add), self._ptr(minus), int(n_elems), self._ptr(out)))
+
     def combine_unquantize_model_dev(self, n, inp, add, minus, layers, element_bits, num_clients, out):
         """out = unquantise((inp + add - minus) mod 2^b) as float64 over a flattened model, one memory-bound pass (add / minus: device
         vectors or None); layers as for decrypt_unquantize_model_dev."""

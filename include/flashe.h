@@ -74,7 +74,9 @@ typedef struct flashe_ctx flashe_ctx;
  *      end over a sum and caller-held masks); flashe_quantize_encrypt_sparse_cohort_dev (a sparse cohort's quantise + encrypts in one
  *      launch at int_bits 16 - 32); flashe_sparsify_cohort_tensors_dev and flashe_quantize_cohort_dev (a cohort of sparse-job
  *      clients: C models sparsified in one set of launches, their compact layers quantised in one launch);
- *      flashe_quantize_encrypt_cohort_u32_dev (the cohort's chained launch in the compact layout, int_bits 16 / 20 / 23 / 24 / 32) */
+ *      flashe_quantize_encrypt_cohort_u32_dev (the cohort's chained launch in the compact layout, int_bits 16 / 20 / 23 / 24 / 32);
+ *      flashe_quantize_batch_encrypt_cohort_dev (the cohort's chained launch for a batched job at int_bits > 64, 5 - 7 values per
+ *      element) and flashe_combine_unbatch_unquantize_model_dev (the batched codec back end over a sum and caller-held masks) */
 #define FLASHE_ABI_VERSION 4
 int flashe_abi_version(void);
 int flashe_device_count(int *count);
@@ -681,11 +683,34 @@ int flashe_quantize_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uint32_t 
 int flashe_quantize_encrypt_cohort_u32_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs,
                                            const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
                                            int element_bits, const double *u_dev, uint32_t *const *ct_dev, uint32_t *sum_out_dev);
+/* The same cohort for a BATCHED job at int_bits > 64 (new), jzf_quantize.py:55-67, 162-185, jzf_flashe.py:349-353, jzf_aggregator.py:424-430:
+ * ONE chained launch over the n_elems = sum_l ceil(size_l / bs) batched elements of the model (bs = int_bits / field_bits values per
+ * element, every layer padded to whole elements on its own, the first value of an element in its most significant field).  It writes
+ * ct_dev[c] (n_elems x 2 limbs: bit for bit flashe_quantize_batch_tensors_dev of client c with the draws u_dev[c * n_values ..], followed
+ * by its double-mask flashe_encrypt_dev with cipher index first_idx + c), sum_out_dev = sum_c ct_dev[c] mod 2^b and, when dmask_dev is
+ * not NULL, term(first_idx + n_clients) - term(first_idx) mod 2^b over the n_elems elements (feed it to
+ * flashe_combine_unbatch_unquantize_model_dev).  No batched plaintext exists in HBM.  layers (sizes = the differences of consecutive
+ * starts, the last one ends at n_values), src_dev, src_dtype, the stage pass and the argument checks are those of
+ * flashe_quantize_encrypt_cohort_dev; FLASHE_EINVAL when n_elems is not what the layers batch into.
+ * Returns FLASHE_ENOTSUP -- nothing launched -- for every shape outside the launch: int_bits <= 64, bs outside 5 .. 7 (the
+ * batch sizes compiled in: what the reference's element_bits 16 jobs give at int_bits 120 / 128), more than 128 clients, fewer than two 256-element tiles per wave of the chip counted
+ * in elements (2 x 16 x flashe_ctx_cu_count tiles), n_elems > 2^32, FLASHE_CHAIN=0, another PRF backend; the caller then runs
+ * flashe_quantize_batch_tensors_dev per client and flashe_encrypt_batch_sum_dev.  The table uploads synchronise; not capturable. */
+int flashe_quantize_batch_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n_values, uint64_t n_elems,
+                                             uint32_t n_jobs, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
+                                             const int32_t *src_dtype, int element_bits, int field_bits, const double *u_dev, uint64_t *const *ct_dev,
+                                             uint64_t *sum_out_dev, uint64_t *dmask_dev);
 /* The codec back end over caller-held vectors (new), jzf_quantize.py:102-107: out[k] = unquantize((in[k] + add[k] - minus[k]) mod 2^b)
  * as float64 for the n elements of a flattened model, one memory-bound pass; add_dev / minus_dev may be NULL (zeros).  With in = a
  * cohort's sum and add = its decrypt mask this is the cohort's decrypt_unquantize. */
 int flashe_combine_unquantize_model_dev(flashe_ctx *ctx, uint64_t n, const uint64_t *in_dev, const uint64_t *add_dev, const uint64_t *minus_dev,
                                         const flashe_codec_layer *layers, int n_layers, int element_bits, int num_clients, double *out_dev);
+/* Its batched sibling (new), jzf_quantize.py:102-107, 240-246: flashe_unbatch_unquantize_model_dev over (in + add - minus) mod 2^b, one
+ * memory-bound pass over the n_elems batched elements; add_dev / minus_dev may be NULL (zeros).  With in = a batched cohort's sum and
+ * add = its decrypt mask this is the cohort's decrypt_unquantize. */
+int flashe_combine_unbatch_unquantize_model_dev(flashe_ctx *ctx, const flashe_batch_layer *layers, int n_layers, int element_bits, int field_bits,
+                                                int num_clients, const uint64_t *in_dev, const uint64_t *add_dev, const uint64_t *minus_dev,
+                                                uint64_t n_elems, double *out_dev);
 /* The batched job's front end, jzf_quantize.py:55-67, 162-185 (new): flashe_quantize_batch_model_dev with tensor layers; the layer
  * sizes are the differences of consecutive starts, the last one ends at n_values. */
 int flashe_quantize_batch_tensors_dev(flashe_ctx *ctx, const flashe_tensor_layer *layers, int n_layers, uint64_t n_values, int element_bits,
