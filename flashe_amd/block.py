@@ -884,13 +884,38 @@ def _layer_is_f64(v):
     return name not in ("float32", "float16", "bfloat16")
 
 
+def _one_model(clients):
+    """(names, shapes, f64, mixed) of the ONE model that the clients' (walking order, layers) pairs describe: ValueError naming the client and
+    the layer where the names, their order or a shape differ from client 0's; mixed: a layer is float64 for some clients only."""
+    names, shapes, f64, mixed = None, [], [], False
+    for c, (order, layers) in enumerate(clients):
+        if names is None:
+            names = order
+            shapes = [_layer_shape(layers[k]) for k in order]
+            f64 = [_layer_is_f64(layers[k]) for k in order]
+            continue
+        if order != names:
+            odd = next((k for k in order if k not in names), None) or next((k for k in names if k not in order), None)
+            if odd is None:
+                odd = next(a for a, b in zip(order, names) if a != b)
+                raise ValueError(f"client {c}: layer {odd!r} comes at another place of the walking order than in client 0's")
+            raise ValueError(f"client {c}: layer {odd!r} is not a layer of every client of the cohort")
+        for li, k in enumerate(order):
+            shp = _layer_shape(layers[k])
+            if shp != shapes[li]:
+                raise ValueError(f"client {c}: layer {k!r} has shape {shp}, client 0's has {shapes[li]}")
+            mixed |= _layer_is_f64(layers[k]) != f64[li]
+    return names, shapes, f64, mixed
+
+
 def cohort_admission_length(cu_count):
     """The shortest vector the summed chain takes uncut: two whole 256-element tiles for each of the chip's 16 x cu_count waves."""
     return (2 * 16 * int(cu_count) - 1) * 256 + 1
 
 
 _COHORT_BATCH_SIZES = (5, 6, 7)                     # the values per element compiled into the batched cohort chain (prf_chain_cohort_batch_kernel)
-_COMPACT_COHORT_WIDTHS = (16, 20, 23, 24, 32)       # the widths compiled into the compact chain (FLASHE_FIXED32_WIDTHS, csrc/kernels.hip)
+# the widths compiled into the compact chains, dense and sparse (FLASHE_FIXED32_WIDTHS, csrc/kernels.hip)
+_COMPACT_COHORT_WIDTHS = (16, 20, 23, 24, 32)
 
 
 def compact_cohort_blocks(n, int_bits, n_jobs):
@@ -938,29 +963,13 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
     if n_jobs is None:
         from . import cipher as _cipher_mod
         n_jobs = _cipher_mod.N_JOBS
-    names = None
-    shapes, f64 = [], []
-    mixed = False
-    for c, w in enumerate(weights_list):
-        order = list(w.walking_order)
-        if "zzz" in w._weights or location_masks:
-            raise TypeError(f"client {c}: sparse uploads (a 'zzz' layer or location masks) are not supported by FlasheCohort")
-        if names is None:
-            names = order
-            shapes = [_layer_shape(w._weights[k]) for k in order]
-            f64 = [_layer_is_f64(w._weights[k]) for k in order]
-            continue
-        if order != names:
-            odd = next((k for k in order if k not in names), None) or next((k for k in names if k not in order), None)
-            if odd is None:
-                odd = next(a for a, b in zip(order, names) if a != b)
-                raise ValueError(f"client {c}: layer {odd!r} comes at another place of the walking order than in client 0's")
-            raise ValueError(f"client {c}: layer {odd!r} is not a layer of every client of the cohort")
-        for li, k in enumerate(order):
-            shp = _layer_shape(w._weights[k])
-            if shp != shapes[li]:
-                raise ValueError(f"client {c}: layer {k!r} has shape {shp}, client 0's has {shapes[li]}")
-            mixed |= _layer_is_f64(w._weights[k]) != f64[li]
+
+    def dense_clients():
+        for c, w in enumerate(weights_list):
+            if "zzz" in w._weights or location_masks:
+                raise TypeError(f"client {c}: sparse uploads (a 'zzz' layer or location masks) are not supported by FlasheCohort")
+            yield list(w.walking_order), w._weights
+    names, shapes, _f64, mixed = _one_model(dense_clients())
     sizes = [int(np.prod(shp, dtype=np.int64)) for shp in shapes]
     starts, n = [], 0
     for s_ in sizes:
@@ -1217,26 +1226,23 @@ class FlasheCohort(object):
                     for li, (st, _p, al, sh, _code, fl) in enumerate(tables[0])]
             srcs = [[t[1] for t in table] for table in tables]
             dts = [[t[4] for t in table] for table in tables]
+            # (no decrypt mask at the compact widths: the decrypt of the sum is 2 / m AES blocks per element)
             dmask = DeviceVector(eng, n_elems) if whole and not self.compact else None
-            if ld.batch and not self.compact:
+            outs, mask_buf = [v.buf for v in cts], dmask.buf if dmask is not None else None
+            if self.compact:
+                took = eng.quantize_encrypt_cohort_u32_dev(c.iter_index, self.first_idx, n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du, outs,
+                                                           psum.buf)
+            elif ld.batch:
                 field_bits = q.element_bits + int(np.ceil(np.log2(q.num_clients)))
-                if eng.quantize_batch_encrypt_cohort_dev(c.iter_index, self.first_idx, n, n_elems, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits,
-                                                         field_bits, du, [v.buf for v in cts], psum.buf, dmask.buf if dmask is not None else None):
-                    if dmask is not None:
-                        ld._cohort_mask = (psum.ptr, dmask, c.iter_index, self.first_idx + C, self.first_idx)
-                else:
-                    path = STAGED_CHAIN
-            elif self.compact:
-                # (no decrypt mask at these widths: the decrypt of the sum is 2 / m AES blocks per element)
-                if not eng.quantize_encrypt_cohort_u32_dev(c.iter_index, self.first_idx, n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du,
-                                                           [v.buf for v in cts], psum.buf):
-                    path = STAGED_CHAIN
-            elif eng.quantize_encrypt_cohort_dev(c.iter_index, self.first_idx, n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du,
-                                               [v.buf for v in cts], psum.buf, dmask.buf if dmask is not None else None):
-                if dmask is not None:
-                    ld._cohort_mask = (psum.ptr, dmask, c.iter_index, self.first_idx + C, self.first_idx)
+                took = eng.quantize_batch_encrypt_cohort_dev(c.iter_index, self.first_idx, n, n_elems, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits,
+                                                             field_bits, du, outs, psum.buf, mask_buf)
             else:
+                took = eng.quantize_encrypt_cohort_dev(c.iter_index, self.first_idx, n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du, outs,
+                                                       psum.buf, mask_buf)
+            if not took:
                 path = STAGED_CHAIN                    # the library declined: the planner's guess was wrong, the result is not
+            elif dmask is not None:
+                ld._cohort_mask = (psum.ptr, dmask, c.iter_index, self.first_idx + C, self.first_idx)
         if path == STAGED_CHAIN and n_elems:
             # a quantise (+ batch) pass per client into plaintexts -- un-batched: one value per element, field_bits = int_bits -- then the
             # summed batch encrypt, which chains where it can
@@ -1311,8 +1317,6 @@ class FlasheCohort(object):
 # ---- a cohort of sparse-job clients hosted on one GPU (new) ----------------------------------------------------------------------
 SPARSE_COHORT = "sparse-cohort"
 FRONT_FUSED, FRONT_STAGED = "fused", "staged"
-SPARSE_FUSED_WIDTHS = (16, 20, 23, 24, 32)     # the widths compiled into prf_small_sparse_cohort_kernel (FLASHE_FIXED32_WIDTHS)
-SPARSE_FUSED_MAX_CLIENTS = 128
 
 
 class SparseCohortPlan(object):
@@ -1369,25 +1373,7 @@ def plan_sparse_cohort(weights_list, sparsity, int_bits, element_bits=16, batch=
     if len(weights_list) < 1:
         raise ValueError("a cohort needs at least one client's model")
     C = len(weights_list)
-    names, shapes, f64, mixed = None, [], [], False
-    for c, w in enumerate(weights_list):
-        order, layers = _client_layers(w, walking_order)
-        if names is None:
-            names = order
-            shapes = [_layer_shape(layers[k]) for k in order]
-            f64 = [_layer_is_f64(layers[k]) for k in order]
-            continue
-        if order != names:
-            odd = next((k for k in order if k not in names), None) or next((k for k in names if k not in order), None)
-            if odd is None:
-                odd = next(a for a, b in zip(order, names) if a != b)
-                raise ValueError(f"client {c}: layer {odd!r} comes at another place of the walking order than in client 0's")
-            raise ValueError(f"client {c}: layer {odd!r} is not a layer of every client of the cohort")
-        for li, k in enumerate(order):
-            shp = _layer_shape(layers[k])
-            if shp != shapes[li]:
-                raise ValueError(f"client {c}: layer {k!r} has shape {shp}, client 0's has {shapes[li]}")
-            mixed |= _layer_is_f64(layers[k]) != f64[li]
+    names, shapes, f64, mixed = _one_model(_client_layers(w, walking_order) for w in weights_list)
     sizes = [int(np.prod(shp, dtype=np.int64)) for shp in shapes]
     for k, size in zip(names, sizes):
         if size == 0:
@@ -1411,10 +1397,10 @@ def _sparse_front_end(path, reason, int_bits, n_clients, K):
     rule, without a device (another PRF backend than the table one is the library's to refuse)."""
     if path != SPARSE_COHORT:
         return FRONT_STAGED, reason
-    if int_bits not in SPARSE_FUSED_WIDTHS:
-        return FRONT_STAGED, f"int_bits {int_bits} is not one of the chained widths {SPARSE_FUSED_WIDTHS}"
-    if n_clients > SPARSE_FUSED_MAX_CLIENTS:
-        return FRONT_STAGED, f"{n_clients} clients (the chained launch takes {SPARSE_FUSED_MAX_CLIENTS})"
+    if int_bits not in _COMPACT_COHORT_WIDTHS:
+        return FRONT_STAGED, f"int_bits {int_bits} is not one of the chained widths {_COMPACT_COHORT_WIDTHS}"
+    if n_clients > _COHORT_MAX_LINKS:
+        return FRONT_STAGED, f"{n_clients} clients (the chained launch takes {_COHORT_MAX_LINKS})"
     if K >= 1 << 32:
         return FRONT_STAGED, "2^32 compact values or more"
     if os.environ.get("FLASHE_CHAIN", "1") == "0":

@@ -1599,24 +1599,36 @@ static int cohort_check(flashe_ctx *ctx, const char *who, uint32_t first_idx, in
     return check_double_idx(ctx, FLASHE_SCHEME_DOUBLE, idx.data(), n_clients);
 }
 
-// rows of the device table (non-empty layers), the sources behind them, and ONE stage pass for every source that is not read in place
-// (extra / extra_dev: a further small block for the same launch, uploaded behind the table -- the sparse cohort's 'zzz' values)
-static int cohort_stage(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
-                        const int32_t *src_dtype, int element_bits, CohortCodec &cc, const void *extra = nullptr, size_t extra_bytes = 0,
-                        const char **extra_dev = nullptr)
+// row_of = the non-empty layers of a cohort's shared table (the rows of the device table), each with a positive alpha and a compute dtype
+static int cohort_rows(flashe_ctx *ctx, uint64_t n, const flashe_tensor_layer *layers, int n_layers, std::vector<int> &row_of)
 {
-    int rc;
-    std::vector<CodecLayer> tab;
-    std::vector<int> row_of;
+    row_of.clear();
     for (int l = 0; l < n_layers; l++) {
         const flashe_tensor_layer &y = layers[l];
-        const uint64_t end = l + 1 < n_layers ? layers[l + 1].start : n;
-        if (y.start == end) continue;
+        if (y.start == (l + 1 < n_layers ? layers[l + 1].start : n)) continue;
         if (!(y.alpha > 0)) return fail(ctx, FLASHE_EINVAL, "layer %d: alpha must be positive", l);
         if (y.dtype != FLASHE_TENSOR_F32 && y.dtype != FLASHE_TENSOR_F64)
             return fail(ctx, FLASHE_EINVAL, "layer %d: the shared row names the COMPUTE type, FLASHE_TENSOR_F32 or FLASHE_TENSOR_F64", l);
-        tab.push_back(codec_layer_front(y.start, nullptr, y.dtype == FLASHE_TENSOR_F64 || (y.flags & FLASHE_TENSOR_LOOP_F64), y.alpha, element_bits));
         row_of.push_back(l);
+    }
+    return FLASHE_OK;
+}
+
+// rows of the device table (non-empty layers), the sources behind them, and ONE stage pass for every source that is not read in place
+// (extra / extra_dev: a further small block for the same launch, uploaded behind the table -- the sparse cohort's 'zzz' values; rows: what
+// cohort_rows gave a caller that has asked already)
+static int cohort_stage(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
+                        const int32_t *src_dtype, int element_bits, CohortCodec &cc, const void *extra = nullptr, size_t extra_bytes = 0,
+                        const char **extra_dev = nullptr, const std::vector<int> *rows = nullptr)
+{
+    int rc;
+    std::vector<int> own_rows;
+    if (!rows && (rc = cohort_rows(ctx, n, layers, n_layers, own_rows))) return rc;
+    const std::vector<int> &row_of = rows ? *rows : own_rows;
+    std::vector<CodecLayer> tab;
+    for (const int l : row_of) {
+        const flashe_tensor_layer &y = layers[l];
+        tab.push_back(codec_layer_front(y.start, nullptr, y.dtype == FLASHE_TENSOR_F64 || (y.flags & FLASHE_TENSOR_LOOP_F64), y.alpha, element_bits));
     }
     const size_t n_tab = tab.size();
     std::vector<const void *> src(static_cast<size_t>(n_clients) * n_tab);
@@ -1675,6 +1687,39 @@ static int cohort_stage(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe
     return FLASHE_OK;
 }
 
+// the outputs of a double-mask cohort: every client's ciphertext non-null, aligned for its element type (uint64: a two-limb vector's 16
+// bytes, check_prf_args; uint32: 4 bytes) and apart from the sum and the mask, then the sum and the mask themselves
+extern "C++" template <class T> static int cohort_check_outs(flashe_ctx *ctx, int n_clients, uint32_t n_jobs, T *const *ct_dev, const T *sum_out_dev, const T *dmask_dev)
+{
+    constexpr bool wide = sizeof(T) == 8;
+    for (int c = 0; c < n_clients; c++) {
+        if (!ct_dev[c]) return fail(ctx, FLASHE_EINVAL, "client %d: null ciphertext", c);
+        if constexpr (wide) {
+            if (int rc = check_prf_args(ctx, 1, 1, n_jobs, ct_dev[c], nullptr, 0)) return rc;
+        } else if (reinterpret_cast<uintptr_t>(ct_dev[c]) & 3u)
+            return fail(ctx, FLASHE_EINVAL, "client %d: the ciphertext is not 4-byte aligned", c);
+        if (ct_dev[c] == sum_out_dev || ct_dev[c] == dmask_dev)
+            return fail(ctx, FLASHE_EINVAL, "client %d: the ciphertext aliases the sum%s", c, wide ? " or the mask" : "");
+    }
+    if constexpr (!wide) return (reinterpret_cast<uintptr_t>(sum_out_dev) & 3u) ? fail(ctx, FLASHE_EINVAL, "sum_out_dev must be 4-byte aligned") : FLASHE_OK;
+    if (int rc = check_sum_aligned(ctx, sum_out_dev)) return rc;
+    if (dmask_dev && (!aligned16(dmask_dev) || dmask_dev == sum_out_dev)) return fail(ctx, FLASHE_EINVAL, "dmask_dev must be 16-byte aligned and apart from the sum");
+    return FLASHE_OK;
+}
+
+// A shape the chained launch `what` does not take: asked of the launcher's own predicate before anything is staged, and once more of the
+// launcher's answer (hipErrorNotSupported = nothing launched), which is the final word.
+static int cohort_declined(flashe_ctx *ctx, const char *who, const char *what)
+{
+    return fail(ctx, FLASHE_ENOTSUP, "%s: not a shape of the chained %s launch", who, what);
+}
+static int cohort_launched(flashe_ctx *ctx, hipError_t e, const char *who, const char *what)
+{
+    if (e == hipErrorNotSupported) return cohort_declined(ctx, who, what);
+    HIP_TRY(ctx, e);
+    return FLASHE_OK;
+}
+
 int flashe_quantize_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs,
                                        const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
                                        int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev, uint64_t *dmask_dev)
@@ -1684,26 +1729,12 @@ int flashe_quantize_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uint32_t 
     std::vector<uint32_t> idx;
     int rc = cohort_check(ctx, who, first_idx, n_clients, n, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, idx);
     if (rc) return rc;
-    for (int c = 0; c < n_clients; c++) {
-        if (!ct_dev[c]) return fail(ctx, FLASHE_EINVAL, "client %d: null ciphertext", c);
-        if ((rc = check_prf_args(ctx, 1, 1, n_jobs, ct_dev[c], nullptr, 0))) return rc;
-        if (ct_dev[c] == sum_out_dev || ct_dev[c] == dmask_dev) return fail(ctx, FLASHE_EINVAL, "client %d: the ciphertext aliases the sum or the mask", c);
-    }
-    if ((rc = check_sum_aligned(ctx, sum_out_dev))) return rc;
-    if (dmask_dev && (!aligned16(dmask_dev) || dmask_dev == sum_out_dev)) return fail(ctx, FLASHE_EINVAL, "dmask_dev must be 16-byte aligned and apart from the sum");
-    // the shapes the chained launch does not take, refused before anything is staged (launch_prf_cohort_sum's own rule is the final word)
-    {
-        const uint64_t waves = static_cast<uint64_t>(ctx->env.num_cus) * 16;
-        if (ctx->limbs != 2 || !ctx->env.use_chain || n_clients > 128 || (n + 255) / 256 < 2 * waves || n == 0 || ((n - 1) >> 32) ||
-            (ctx->env.prf_backend != PRF_AUTO && ctx->env.prf_backend != PRF_TABLE))
-            return fail(ctx, FLASHE_ENOTSUP, "%s: not a shape of the chained cohort launch", who);
-    }
+    if ((rc = cohort_check_outs(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, dmask_dev))) return rc;
+    if (!cohort_chain_admits(ctx->env, n_clients, n, 0)) return cohort_declined(ctx, who, "cohort");
     CohortCodec cc{};
     if ((rc = cohort_stage(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, cc))) return rc;
-    const hipError_t e = launch_prf_cohort_sum(ctx->env, iter, n_clients, idx.data(), cc, u_dev, ct_dev, sum_out_dev, n, n_jobs, dmask_dev);
-    if (e == hipErrorNotSupported) return fail(ctx, FLASHE_ENOTSUP, "%s: not a shape of the chained cohort launch", who);
-    HIP_TRY(ctx, e);
-    return FLASHE_OK;
+    return cohort_launched(ctx, launch_prf_cohort_sum(ctx->env, iter, n_clients, idx.data(), cc, nullptr, u_dev, ct_dev, sum_out_dev, n, n_jobs, dmask_dev),
+                           who, "cohort");
 }
 
 // the same cohort in the compact layout at int_bits <= 32 (prf_small_cohort_kernel): uint32 ciphertexts and their uint32 sum, no decrypt mask
@@ -1717,27 +1748,11 @@ int flashe_quantize_encrypt_cohort_u32_dev(flashe_ctx *ctx, uint32_t iter, uint3
     int rc = cohort_check(ctx, who, first_idx, n_clients, n, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, idx);
     if (rc) return rc;
     if (n_jobs == 0) return fail(ctx, FLASHE_EINVAL, "n_jobs must be >= 1");
-    for (int c = 0; c < n_clients; c++) {
-        if (!ct_dev[c]) return fail(ctx, FLASHE_EINVAL, "client %d: null ciphertext", c);
-        if (reinterpret_cast<uintptr_t>(ct_dev[c]) & 3u) return fail(ctx, FLASHE_EINVAL, "client %d: the ciphertext is not 4-byte aligned", c);
-        if (ct_dev[c] == sum_out_dev) return fail(ctx, FLASHE_EINVAL, "client %d: the ciphertext aliases the sum", c);
-    }
-    if (reinterpret_cast<uintptr_t>(sum_out_dev) & 3u) return fail(ctx, FLASHE_EINVAL, "sum_out_dev must be 4-byte aligned");
-    // the shapes the chained launch does not take, refused before anything is staged (launch_small_cohort_sum's own rule is the final word)
-    if (flashe_ctx_compact_layout(ctx) != 1 || !small_cohort_width(ctx->int_bits) || n_clients > 128 || n == 0 || n >= (1ull << 32))
-        return fail(ctx, FLASHE_ENOTSUP, "%s: not a shape of the chained compact cohort launch", who);
-    {
-        const uint64_t m = 128 / static_cast<uint64_t>(ctx->int_bits), d = n / n_jobs, r = n % n_jobs;
-        const uint64_t blocks = r * ((d + m) / m) + (n_jobs - r) * ((d + m - 1) / m);
-        if (blocks < 2ull * 128 * 16 * static_cast<uint64_t>(ctx->env.num_cus))
-            return fail(ctx, FLASHE_ENOTSUP, "%s: not a shape of the chained compact cohort launch", who);
-    }
+    if ((rc = cohort_check_outs<uint32_t>(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, nullptr))) return rc;
+    if (flashe_ctx_compact_layout(ctx) != 1 || !small_cohort_admits(ctx->env, n_clients, n, n_jobs, true)) return cohort_declined(ctx, who, "compact cohort");
     CohortCodec cc{};
     if ((rc = cohort_stage(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, cc))) return rc;
-    const hipError_t e = launch_small_cohort_sum(ctx->env, iter, n_clients, idx.data(), cc, u_dev, ct_dev, sum_out_dev, n, n_jobs);
-    if (e == hipErrorNotSupported) return fail(ctx, FLASHE_ENOTSUP, "%s: not a shape of the chained compact cohort launch", who);
-    HIP_TRY(ctx, e);
-    return FLASHE_OK;
+    return cohort_launched(ctx, launch_small_cohort_sum(ctx->env, iter, n_clients, idx.data(), cc, u_dev, ct_dev, sum_out_dev, n, n_jobs), who, "compact cohort");
 }
 
 // the cohort of a BATCHED job (prf_chain_cohort_batch_kernel): the same table, sources and stage pass over the n_values values; the chain
@@ -1767,20 +1782,8 @@ int flashe_quantize_batch_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uin
     }
     if (e != n_elems) return fail(ctx, FLASHE_EINVAL, "the layers batch into %llu elements, n_elems says %llu", static_cast<unsigned long long>(e),
                                   static_cast<unsigned long long>(n_elems));
-    for (int c = 0; c < n_clients; c++) {
-        if (!ct_dev[c]) return fail(ctx, FLASHE_EINVAL, "client %d: null ciphertext", c);
-        if ((rc = check_prf_args(ctx, 1, 1, n_jobs, ct_dev[c], nullptr, 0))) return rc;
-        if (ct_dev[c] == sum_out_dev || ct_dev[c] == dmask_dev) return fail(ctx, FLASHE_EINVAL, "client %d: the ciphertext aliases the sum or the mask", c);
-    }
-    if ((rc = check_sum_aligned(ctx, sum_out_dev))) return rc;
-    if (dmask_dev && (!aligned16(dmask_dev) || dmask_dev == sum_out_dev)) return fail(ctx, FLASHE_EINVAL, "dmask_dev must be 16-byte aligned and apart from the sum");
-    // the shapes the chained launch does not take, refused before anything is staged (launch_prf_cohort_batch_sum's own rule is the final word)
-    {
-        const uint64_t waves = static_cast<uint64_t>(ctx->env.num_cus) * 16;
-        if (ctx->limbs != 2 || !ctx->env.use_chain || n_clients > 128 || bs < 5 || bs > 7 || (n_elems + 255) / 256 < 2 * waves || n_elems == 0 ||
-            ((n_elems - 1) >> 32) || (ctx->env.prf_backend != PRF_AUTO && ctx->env.prf_backend != PRF_TABLE))
-            return fail(ctx, FLASHE_ENOTSUP, "%s: not a shape of the chained batched cohort launch", who);
-    }
+    if ((rc = cohort_check_outs(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, dmask_dev))) return rc;
+    if (!cohort_chain_admits(ctx->env, n_clients, n_elems, static_cast<int>(bs))) return cohort_declined(ctx, who, "batched cohort");
     CohortCodec cc{};
     const char *rows_dev = nullptr;
     if ((rc = cohort_stage(ctx, n_clients, n_values, layers, n_layers, src_dev, src_dtype, element_bits, cc, rows.data(), rows.size() * sizeof(uint64_t),
@@ -1790,10 +1793,8 @@ int flashe_quantize_batch_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uin
     cb.rows = reinterpret_cast<const uint64_t *>(rows_dev);
     cb.n_values = n_values;
     cb.field_bits = field_bits;
-    const hipError_t err = launch_prf_cohort_batch_sum(ctx->env, iter, n_clients, idx.data(), cc, cb, u_dev, ct_dev, sum_out_dev, n_elems, n_jobs, dmask_dev);
-    if (err == hipErrorNotSupported) return fail(ctx, FLASHE_ENOTSUP, "%s: not a shape of the chained batched cohort launch", who);
-    HIP_TRY(ctx, err);
-    return FLASHE_OK;
+    return cohort_launched(ctx, launch_prf_cohort_sum(ctx->env, iter, n_clients, idx.data(), cc, &cb, u_dev, ct_dev, sum_out_dev, n_elems, n_jobs, dmask_dev),
+                           who, "batched cohort");
 }
 
 int flashe_combine_unquantize_model_dev(flashe_ctx *ctx, uint64_t n, const uint64_t *in_dev, const uint64_t *add_dev, const uint64_t *minus_dev,
@@ -3283,16 +3284,7 @@ static int quantize_cohort_check(flashe_ctx *ctx, int n_clients, uint64_t n, con
     if (u_stride < n + 1) return fail(ctx, FLASHE_EINVAL, "quantize_cohort: u_stride must cover a client's n + 1 draws");
     int rc = check_tensor_layers_shape(ctx, n, layers, n_layers);
     if (rc) return rc;
-    row_of.clear();
-    for (int l = 0; l < n_layers; l++) {
-        const flashe_tensor_layer &y = layers[l];
-        const uint64_t end = l + 1 < n_layers ? layers[l + 1].start : n;
-        if (y.start == end) continue;
-        if (!(y.alpha > 0)) return fail(ctx, FLASHE_EINVAL, "layer %d: alpha must be positive", l);
-        if (y.dtype != FLASHE_TENSOR_F32 && y.dtype != FLASHE_TENSOR_F64)
-            return fail(ctx, FLASHE_EINVAL, "layer %d: the shared row names the COMPUTE type, FLASHE_TENSOR_F32 or FLASHE_TENSOR_F64", l);
-        row_of.push_back(l);
-    }
+    if ((rc = cohort_rows(ctx, n, layers, n_layers, row_of))) return rc;
     for (int c = 0; c < n_clients; c++)
         for (const int l : row_of) {
             const size_t at = static_cast<size_t>(c) * n_layers + l;
@@ -3381,20 +3373,16 @@ int flashe_quantize_encrypt_sparse_cohort_dev(flashe_ctx *ctx, uint32_t iter, in
         if (!ct_dev[c] || (reinterpret_cast<uintptr_t>(ct_dev[c]) & 7u)) return fail(ctx, FLASHE_EINVAL, "client %d: null or misaligned upload", c);
         if (reinterpret_cast<uint64_t *>(ct_dev[c]) == zeros_dev) return fail(ctx, FLASHE_EINVAL, "client %d: the upload aliases zeros_dev", c);
     }
-    if (!ctx->env.use_chain || !small_cohort_width(ctx->int_bits) || n_clients > 128 || n == 0 || n >= (1ull << 32) ||
-        (ctx->env.prf_backend != PRF_AUTO && ctx->env.prf_backend != PRF_TABLE))
-        return fail(ctx, FLASHE_ENOTSUP, "%s: not a shape of the chained sparse cohort launch", who);
+    if (!small_cohort_admits(ctx->env, n_clients, n, n_jobs, false)) return cohort_declined(ctx, who, "sparse cohort");
     const Codec z = codec_quantize_front(nullptr, zzz_is_f64 != 0, 1.0, element_bits, nullptr);
     CohortCodec cc{};
     const char *zzz_dev = nullptr;
     if ((rc = cohort_stage(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, cc, zzz, static_cast<size_t>(n_clients) * sizeof(double),
-                           &zzz_dev)))
+                           &zzz_dev, &row_of)))
         return rc;
-    const hipError_t e = launch_small_sparse_cohort(ctx->env, iter, n_clients, idx, cc, u_dev, u_stride, ct_dev, n, n_jobs,
-                                                    reinterpret_cast<const double *>(zzz_dev), z.x_is_f64 != 0, z.alpha, z.scale, z.den, zeros_dev);
-    if (e == hipErrorNotSupported) return fail(ctx, FLASHE_ENOTSUP, "%s: not a shape of the chained sparse cohort launch", who);
-    HIP_TRY(ctx, e);
-    return FLASHE_OK;
+    return cohort_launched(ctx, launch_small_sparse_cohort(ctx->env, iter, n_clients, idx, cc, u_dev, u_stride, ct_dev, n, n_jobs,
+                                                           reinterpret_cast<const double *>(zzz_dev), z.x_is_f64 != 0, z.alpha, z.scale, z.den, zeros_dev),
+                           who, "sparse cohort");
 }
 
 #ifdef FLASHE_TUNING

@@ -90,11 +90,6 @@ struct CohortCodec {
     const void *const *src;
     int n_layers, pad_;
 };
-// launch_prf_batch_sum over whole n-element vectors with that front end: client c's plaintext k is the stochastic-rounded quantisation
-// of its float k with the draw u_dev[c * n + k] (codec_quantize's arithmetic), no integer plaintext exists in HBM.  The same admission
-// rule and the same hipErrorNotSupported -- nothing launched -- contract; dmask_dev is optional.
-hipError_t launch_prf_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
-                                 uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs, uint64_t *dmask_dev = nullptr);
 // The BATCHED cohort (prf_chain_cohort_batch_kernel): the chain runs over the model's n_elems batched elements (as BatchLayer's: every
 // layer padded to whole elements on its own) and element e of table row l holds bs = int_bits / field_bits values of every client, the
 // first one most significant.  cc is the table of the un-batched launch (row l: start = the layer's first VALUE among the n_values of the
@@ -104,28 +99,35 @@ struct CohortBatch {
     uint64_t n_values;         // values of one model: client c's draws are u_dev[c * n_values ..]
     int field_bits, pad_;
 };
-// launch_prf_cohort_sum with that front end: client c's plaintext of element e = quantize_batch_model_kernel's, with the draws
-// u_dev[c * n_values + value index].  Admitted where launch_prf_cohort_sum is, counted in elements (two whole 256-element tiles per
-// wave, n_elems <= 2^32), and for bs = env.b / field_bits in {5, 6, 7} only; hipErrorNotSupported: nothing launched.
-hipError_t launch_prf_cohort_batch_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const CohortBatch &cb,
-                                       const double *u_dev, uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n_elems, uint32_t n_jobs,
-                                       uint64_t *dmask_dev = nullptr);
+// The shapes the wide cohort launch takes, on the environment and the sizes alone (no HIP call; what a caller asks before it stages anything):
+// the chained table PRF at int_bits > 64 without a fused codec, 1 .. kMaxLinks clients, n_elems in one 2^32 counter window and at least two
+// whole 256-element tiles for each of the chip's waves; bs = 0: un-batched, else the values per element, 5, 6 or 7.
+bool cohort_chain_admits(const LaunchEnv &env, int n_vec, uint64_t n_elems, int bs);
+// launch_prf_batch_sum over whole n-element vectors with the cohort's front end.  cb == null: client c's plaintext k is the
+// stochastic-rounded quantisation of its float k with the draw u_dev[c * n + k] (codec_quantize's arithmetic), no integer plaintext exists
+// in HBM.  cb: n counts batched elements, client c's plaintext of element e = quantize_batch_model_kernel's with the draws
+// u_dev[c * n_values + value index], bs = env.b / field_bits.  hipErrorNotSupported -- nothing launched -- outside cohort_chain_admits, for
+// idx that are not one consecutive run below 2^32 - 1, a null output or an empty table; dmask_dev is optional.
+hipError_t launch_prf_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const CohortBatch *cb,
+                                 const double *u_dev, uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs,
+                                 uint64_t *dmask_dev = nullptr);
+// The shapes the two compact cohort launches below take, in the same terms: int_bits 16 / 20 / 23 / 24 / 32, the chained table PRF without
+// a fused codec, 1 .. kMaxLinks clients, 0 < n < 2^32, n_jobs != 0 and, for the `summed` one, at least 2 x 128 AES blocks (of
+// 128 / int_bits elements, per the chunking of n_jobs) for each of the chip's waves.
+bool small_cohort_admits(const LaunchEnv &env, int n_vec, uint64_t n, uint32_t n_jobs, bool summed);
 // The same cohort at int_bits <= 32 in the compact layout (prf_small_cohort_kernel): uint32 ciphertexts and their uint32 sum from the
-// floats, admitted where the summed compact chain is -- int_bits 16 / 20 / 23 / 24 / 32, the table PRF, the chained kernels, consecutive
-// idx below 2^32 - 1, at most kMaxLinks clients, 0 < n < 2^32 and at least 2 x 128 AES blocks (of 128 / int_bits elements, per the
-// chunking of n_jobs) for each of the chip's waves.  hipErrorNotSupported: nothing launched.
+// floats, admitted where the summed compact chain is -- small_cohort_admits(summed) and consecutive idx below 2^32 - 1.
+// hipErrorNotSupported: nothing launched.
 hipError_t launch_small_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
                                    uint32_t *const *out_dev, uint32_t *sum_out_dev, uint64_t n, uint32_t n_jobs);
 // The sparse job's cohort at the same widths (prf_small_sparse_cohort_kernel): out_dev[c][k] = SINGLE-mask encrypt (idx[c]; any indices) of the
 // quantisation of client c's compact value k with the draw u_dev[c * u_stride + k], k < n, in the ONE-LIMB layout (uint64 elements, 8-byte
 // aligned), and out_dev[c][n] = zeros_dev[c] = the client's 'zzz' value zzz_dev[c] quantised in plain with (z_alpha, z_scale, z_den) in
 // float64 / float32 and the draw u_dev[c * u_stride + n].  No minimum length: short vectors are cut into runs of clients.
-// hipErrorNotSupported -- nothing launched -- for another width, PRF backend or FLASHE_CHAIN=0, more than kMaxLinks clients, n = 0 or >= 2^32.
+// hipErrorNotSupported -- nothing launched -- outside small_cohort_admits(not summed).
 hipError_t launch_small_sparse_cohort(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
                                       uint64_t u_stride, uint64_t *const *out_dev, uint64_t n, uint32_t n_jobs, const double *zzz_dev, bool zzz_f64,
                                       double z_alpha, double z_scale, double z_den, uint64_t *zeros_dev);
-// is int_bits one of the widths compiled into that launch? (what a caller asks before it stages anything for it)
-bool small_cohort_width(int int_bits);
 // launch_prf_batch on elements [first, first + count) of the n-element vectors (pointers address element `first`): what a GPU that owns
 // an element slice of every client's vector runs
 hipError_t launch_prf_batch_range(const LaunchEnv &env, uint32_t iter, bool dbl, int n_vec, const uint32_t *idx, const uint64_t *const *in_dev,

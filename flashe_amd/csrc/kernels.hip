@@ -1863,20 +1863,31 @@ hipError_t launch_prf_batch_sum(const LaunchEnv &env, uint32_t iter, int n_vec, 
     return launch_prf_chains(env, iter, 1, &ch, n, n_jobs);
 }
 
-// the shape launch_prf_batch_sum admits (one uncut summed double-mask chain of whole vectors), with the quantising front end per output
-hipError_t launch_prf_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
-                                 uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs, uint64_t *dmask_dev)
+// ---- what the chained cohort launches admit: arithmetic on the environment and the sizes, no HIP call, no pointer.  Each launcher
+// begins with its predicate; the C ABI asks the same predicate before it stages anything ----
+static bool table_prf(const LaunchEnv &env) { return env.prf_backend == PRF_AUTO || env.prf_backend == PRF_TABLE; }
+
+bool cohort_chain_admits(const LaunchEnv &env, int n_vec, uint64_t n_elems, int bs)
+{
+    if (!env.use_chain || env.b <= 64 || env.codec || !table_prf(env) || n_vec < 1 || n_vec > kMaxLinks) return false;
+    if (n_elems == 0 || ((n_elems - 1) >> 32)) return false;            // one counter window
+    if (bs != 0 && (bs < 5 || bs > 7)) return false;                    // the compiled batch sizes
+    // (launch_prf_batch_sum's rule, counted in elements: two whole 256-element tiles per wave, uncut)
+    return (n_elems + 255) / 256 >= 2 * static_cast<uint64_t>(env.num_cus) * (kPrfThreads / 64);
+}
+
+// The shape launch_prf_batch_sum admits (one uncut summed double-mask chain of whole vectors), with the quantising front end per output;
+// cb: the batched form (prf_chain_cohort_batch_kernel), the same uncut chain over the n batched elements with one draw per VALUE.
+hipError_t launch_prf_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const CohortBatch *cb,
+                                 const double *u_dev, uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs, uint64_t *dmask_dev)
 {
     (void)n_jobs;                            // (int_bits > 64: counters do not depend on the chunking)
-    if (n == 0 || n_vec <= 0) return hipErrorNotSupported;
-    if (!env.use_chain || env.b <= 64 || env.codec || n_vec > kMaxLinks || !sum_out_dev || cc.n_layers < 1) return hipErrorNotSupported;
-    if (env.prf_backend != PRF_AUTO && env.prf_backend != PRF_TABLE) return hipErrorNotSupported;
+    const int bs = !cb ? 0 : (cb->field_bits < 1 || cb->field_bits > env.b) ? -1 : env.b / cb->field_bits;
+    if (!cohort_chain_admits(env, n_vec, n, bs) || !sum_out_dev || !u_dev || cc.n_layers < 1 || (cb && !cb->rows)) return hipErrorNotSupported;
     for (int v = 1; v < n_vec; v++) if (idx[v] != idx[v - 1] + 1u) return hipErrorNotSupported;
     if (idx[n_vec - 1] == 0xffffffffu) return hipErrorNotSupported;
-    const uint64_t waves = static_cast<uint64_t>(env.num_cus) * (kPrfThreads / 64), tiles = (n + 255) / 256;
-    if (tiles < 2 * waves) return hipErrorNotSupported;                 // (launch_prf_batch_sum's rule: two whole tiles per wave, uncut)
-    if ((n - 1) >> 32) return hipErrorNotSupported;                      // one counter window
     for (int v = 0; v < n_vec; v++) if (!out_dev[v]) return hipErrorNotSupported;
+    const uint64_t tiles = (n + 255) / 256, u_stride = cb ? cb->n_values : n;
     ChainTable tb{};
     tb.first[0] = 0; tb.count[0] = n;
     tb.len[0] = static_cast<uint8_t>(n_vec);
@@ -1884,55 +1895,21 @@ hipError_t launch_prf_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec,
     for (int s = 0; s < n_vec; s++) tb.idx[s] = idx[s];
     tb.idx[n_vec] = idx[n_vec - 1] + 1u;
     for (int l = 0; l < n_vec; l++) {
-        tb.in[l] = reinterpret_cast<const uint64_t *>(u_dev + static_cast<uint64_t>(l) * n);       // the link's draws (CohortCodec)
-        tb.out[l] = out_dev[l];
-    }
-    tb.wend[0] = tiles * static_cast<uint64_t>(n_vec + 1);
-    uint64_t lo, hi;
-    masks_of(env.b, &lo, &hi);
-    const int grid = static_cast<int>(std::min<uint64_t>(tiles, static_cast<uint64_t>(env.num_cus)));
-    hipLaunchKernelGGL((prf_chain_cohort_kernel<kPrfThreads>), dim3(grid), dim3(kPrfThreads), 0, env.stream, env.rk, tb, 1, 0, iter, lo, hi,
-                       env.te0_dev, dmask_dev, cc);
-    return hipGetLastError();
-}
-
-// the batched form of launch_prf_cohort_sum (prf_chain_cohort_batch_kernel): the same uncut chain over the n_elems batched elements
-hipError_t launch_prf_cohort_batch_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const CohortBatch &cb,
-                                       const double *u_dev, uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n_elems, uint32_t n_jobs,
-                                       uint64_t *dmask_dev)
-{
-    (void)n_jobs;                            // (int_bits > 64: counters do not depend on the chunking)
-    if (n_elems == 0 || n_vec <= 0) return hipErrorNotSupported;
-    if (!env.use_chain || env.b <= 64 || env.codec || n_vec > kMaxLinks || !sum_out_dev || !u_dev || cc.n_layers < 1 || !cb.rows) return hipErrorNotSupported;
-    if (env.prf_backend != PRF_AUTO && env.prf_backend != PRF_TABLE) return hipErrorNotSupported;
-    for (int v = 1; v < n_vec; v++) if (idx[v] != idx[v - 1] + 1u) return hipErrorNotSupported;
-    if (idx[n_vec - 1] == 0xffffffffu) return hipErrorNotSupported;
-    if (cb.field_bits < 1 || cb.field_bits > env.b) return hipErrorNotSupported;
-    const int bs = env.b / cb.field_bits;
-    if (bs < 5 || bs > 7) return hipErrorNotSupported;                   // the compiled batch sizes
-    const uint64_t waves = static_cast<uint64_t>(env.num_cus) * (kPrfThreads / 64), tiles = (n_elems + 255) / 256;
-    if (tiles < 2 * waves) return hipErrorNotSupported;                 // (launch_prf_batch_sum's rule, counted in elements)
-    if ((n_elems - 1) >> 32) return hipErrorNotSupported;                // one counter window
-    for (int v = 0; v < n_vec; v++) if (!out_dev[v]) return hipErrorNotSupported;
-    ChainTable tb{};
-    tb.first[0] = 0; tb.count[0] = n_elems;
-    tb.len[0] = static_cast<uint8_t>(n_vec);
-    tb.sum_out[0] = sum_out_dev;
-    for (int s = 0; s < n_vec; s++) tb.idx[s] = idx[s];
-    tb.idx[n_vec] = idx[n_vec - 1] + 1u;
-    for (int l = 0; l < n_vec; l++) {
-        tb.in[l] = reinterpret_cast<const uint64_t *>(u_dev + static_cast<uint64_t>(l) * cb.n_values);     // the link's draws, one per VALUE
+        tb.in[l] = reinterpret_cast<const uint64_t *>(u_dev + static_cast<uint64_t>(l) * u_stride);       // the link's draws, one per value (CohortCodec)
         tb.out[l] = out_dev[l];
     }
     tb.wend[0] = tiles * static_cast<uint64_t>(n_vec + 1);
     uint64_t lo, hi;
     masks_of(env.b, &lo, &hi);
     const dim3 grid(static_cast<unsigned>(std::min<uint64_t>(tiles, static_cast<uint64_t>(env.num_cus)))), block(kPrfThreads);
+#define COHORT_BATCH(BS) hipLaunchKernelGGL((prf_chain_cohort_batch_kernel<kPrfThreads, BS>), grid, block, 0, env.stream, env.rk, tb, 1, 0, iter, lo, hi, env.te0_dev, dmask_dev, cc, *cb)
     switch (bs) {
-    case 5: hipLaunchKernelGGL((prf_chain_cohort_batch_kernel<kPrfThreads, 5>), grid, block, 0, env.stream, env.rk, tb, 1, 0, iter, lo, hi, env.te0_dev, dmask_dev, cc, cb); break;
-    case 6: hipLaunchKernelGGL((prf_chain_cohort_batch_kernel<kPrfThreads, 6>), grid, block, 0, env.stream, env.rk, tb, 1, 0, iter, lo, hi, env.te0_dev, dmask_dev, cc, cb); break;
-    default: hipLaunchKernelGGL((prf_chain_cohort_batch_kernel<kPrfThreads, 7>), grid, block, 0, env.stream, env.rk, tb, 1, 0, iter, lo, hi, env.te0_dev, dmask_dev, cc, cb); break;
+    case 0: hipLaunchKernelGGL((prf_chain_cohort_kernel<kPrfThreads>), grid, block, 0, env.stream, env.rk, tb, 1, 0, iter, lo, hi, env.te0_dev, dmask_dev, cc); break;
+    case 5: COHORT_BATCH(5); break;
+    case 6: COHORT_BATCH(6); break;
+    default: COHORT_BATCH(7); break;
     }
+#undef COHORT_BATCH
     return hipGetLastError();
 }
 
@@ -2268,13 +2245,20 @@ hipError_t launch_prf_chains(const LaunchEnv &env, uint32_t iter, int n_chains, 
     return hipSuccess;
 }
 
+// (tuning build: FLASHE_SMALL_FIXED=0 takes the compile-time widths out)
+static bool small_no_fixed_width()
+{
+    static const int v = FLASHE_TUNE_ENV("FLASHE_SMALL_FIXED") ? atoi(FLASHE_TUNE_ENV("FLASHE_SMALL_FIXED")) : 1;
+    return v == 0;
+}
+
 // the per-launch constants of the b <= 64 chained kernels (n < 2^32)
 static SmallParams small_params_of(const LaunchEnv &env, uint32_t iter, uint64_t n, uint32_t n_jobs)
 {
     SmallParams p{};
     p.n = n; p.n_jobs = n_jobs; p.iter = iter; p.b = env.b; p.m = 128 / env.b; p.te0 = env.te0_dev;
     { static const int v = FLASHE_TUNE_ENV("FLASHE_SMALL_DIRECT") ? atoi(FLASHE_TUNE_ENV("FLASHE_SMALL_DIRECT")) : 1; p.no_direct = v == 0 ? 1 : v == 2 ? 2 : 0; }
-    { static const int v = FLASHE_TUNE_ENV("FLASHE_SMALL_FIXED") ? atoi(FLASHE_TUNE_ENV("FLASHE_SMALL_FIXED")) : 1; p.no_fixed_width = v == 0; }
+    p.no_fixed_width = small_no_fixed_width();
     p.m_magic = static_cast<uint32_t>(((1ull << 32) + p.m - 1) / p.m);
     uint64_t hi;
     masks_of(env.b, &p.mask_lo, &hi);
@@ -2484,7 +2468,26 @@ static hipError_t launch_small_chains(const LaunchEnv &env, uint32_t iter, int n
     return hipSuccess;
 }
 
-bool small_cohort_width(int int_bits) { return int_bits <= 32 && fixed32_width(int_bits); }
+// What the compact cohort launches admit (cohort_chain_admits' contract): a compiled-in width, the table PRF, the chained kernels, and for
+// the `summed` chain, which is never cut, enough AES blocks for the paired kernel (launch_small_chains' `pair`).
+bool small_cohort_admits(const LaunchEnv &env, int n_vec, uint64_t n, uint32_t n_jobs, bool summed)
+{
+    if (!env.use_chain || env.b > 32 || !fixed32_width(env.b) || env.codec || !table_prf(env) || n_vec < 1 || n_vec > kMaxLinks) return false;
+    if (n == 0 || n >= (1ull << 32) || n_jobs == 0 || small_no_fixed_width()) return false;
+    return !summed || block_of(n - 1, n, n_jobs, 128 / env.b) + 1 >= 2 * 128 * static_cast<uint64_t>(env.num_cus) * (kSmallThreads / 64);
+}
+
+// what the two launches below share: the compact layout's constants with its measured priority table, and the vector's AES blocks
+static SmallParams small_cohort_params(const LaunchEnv &env, uint32_t iter, int n_vec, uint64_t n, uint32_t n_jobs, uint64_t *blocks)
+{
+    LaunchEnv e32 = env;
+    e32.elem32 = 1;                           // (the sparse launch too: its outputs are one-limb, the priority table is the compile-time widths')
+    SmallParams p = small_params_of(e32, iter, n, n_jobs);
+    p.no_direct = 1;                          // (the compact layout walks its rows: launch_small_chains)
+    p.swp_prio = small_swp_prio(e32, p, n_vec);
+    *blocks = block_of(n - 1, n, n_jobs, p.m) + 1;
+    return p;
+}
 
 // The summed compact chain over whole vectors with the quantising front end per output (prf_small_cohort_kernel): the admission of the
 // summed chain of launch_small_chains -- a compiled-in width, one uncut run of consecutive clients, enough AES blocks for the paired
@@ -2492,21 +2495,12 @@ bool small_cohort_width(int int_bits) { return int_bits <= 32 && fixed32_width(i
 hipError_t launch_small_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
                                    uint32_t *const *out_dev, uint32_t *sum_out_dev, uint64_t n, uint32_t n_jobs)
 {
-    if (n == 0 || n >= (1ull << 32) || n_vec <= 0 || n_jobs == 0) return hipErrorNotSupported;
-    if (!env.use_chain || !small_cohort_width(env.b) || env.codec || n_vec > kMaxLinks || !sum_out_dev || !u_dev || cc.n_layers < 1) return hipErrorNotSupported;
-    if (env.prf_backend != PRF_AUTO && env.prf_backend != PRF_TABLE) return hipErrorNotSupported;
+    if (!small_cohort_admits(env, n_vec, n, n_jobs, true) || !sum_out_dev || !u_dev || cc.n_layers < 1) return hipErrorNotSupported;
     for (int v = 1; v < n_vec; v++) if (idx[v] != idx[v - 1] + 1u) return hipErrorNotSupported;
     if (idx[n_vec - 1] == 0xffffffffu) return hipErrorNotSupported;
     for (int v = 0; v < n_vec; v++) if (!out_dev[v]) return hipErrorNotSupported;
-    LaunchEnv e32 = env;
-    e32.elem32 = 1;
-    SmallParams p = small_params_of(e32, iter, n, n_jobs);
-    if (p.no_fixed_width) return hipErrorNotSupported;
-    p.no_direct = 1;                          // (the compact layout walks its rows: launch_small_chains)
-    p.swp_prio = small_swp_prio(e32, p, n_vec);
-    const uint64_t blocks = block_of(n - 1, n, n_jobs, p.m) + 1;
-    const uint64_t waves = static_cast<uint64_t>(env.num_cus) * (kSmallThreads / 64);
-    if (blocks < 2 * 128 * waves) return hipErrorNotSupported;          // (launch_small_chains' `pair`: a summed chain is never cut)
+    uint64_t blocks;
+    const SmallParams p = small_cohort_params(env, iter, n_vec, n, n_jobs, &blocks);
     SmallChainTable tb{};
     tb.first[0] = 0; tb.count[0] = n; tb.blk_first[0] = 0; tb.blk_count[0] = blocks;
     tb.len[0] = static_cast<uint8_t>(n_vec);
@@ -2536,17 +2530,10 @@ hipError_t launch_small_sparse_cohort(const LaunchEnv &env, uint32_t iter, int n
                                       uint64_t u_stride, uint64_t *const *out_dev, uint64_t n, uint32_t n_jobs, const double *zzz_dev, bool zzz_f64,
                                       double z_alpha, double z_scale, double z_den, uint64_t *zeros_dev)
 {
-    if (n == 0 || n >= (1ull << 32) || n_vec <= 0 || n_jobs == 0) return hipErrorNotSupported;
-    if (!env.use_chain || !small_cohort_width(env.b) || env.codec || n_vec > kMaxLinks || !u_dev || cc.n_layers < 1) return hipErrorNotSupported;
-    if (env.prf_backend != PRF_AUTO && env.prf_backend != PRF_TABLE) return hipErrorNotSupported;
+    if (!small_cohort_admits(env, n_vec, n, n_jobs, false) || !u_dev || cc.n_layers < 1) return hipErrorNotSupported;
     for (int v = 0; v < n_vec; v++) if (!out_dev[v]) return hipErrorNotSupported;
-    LaunchEnv e32 = env;
-    e32.elem32 = 1;                           // (the measured priority table of the compile-time widths; the kernel's outputs are one-limb)
-    SmallParams p = small_params_of(e32, iter, n, n_jobs);
-    if (p.no_fixed_width) return hipErrorNotSupported;
-    p.no_direct = 1;
-    p.swp_prio = small_swp_prio(e32, p, n_vec);
-    const uint64_t blocks = block_of(n - 1, n, n_jobs, p.m) + 1;
+    uint64_t blocks;
+    const SmallParams p = small_cohort_params(env, iter, n_vec, n, n_jobs, &blocks);
     const uint64_t waves = static_cast<uint64_t>(env.num_cus) * (kSmallThreads / 64), tiles = (blocks + 127) / 128;
     int parts = 1;
     if (tiles < waves) parts = static_cast<int>(std::min<uint64_t>(std::min<uint64_t>(waves / tiles, static_cast<uint64_t>(n_vec)), kMaxChains));
