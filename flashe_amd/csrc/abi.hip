@@ -134,16 +134,6 @@ int fail(flashe_ctx *ctx, int code, const char *fmt, ...)
     return code;
 }
 
-}  // namespace flashe_host
-
-using flashe_host::fail;
-using flashe_host::Tmp;
-using flashe_host::vec_bytes;
-using flashe_host::check_double_idx;
-using flashe_host::check_field_bits;
-
-namespace {
-
 int ensure(flashe_ctx *ctx, flashe_ctx::Buf &b, size_t bytes)
 {
     if (bytes <= b.cap) return FLASHE_OK;
@@ -156,19 +146,99 @@ int ensure(flashe_ctx *ctx, flashe_ctx::Buf &b, size_t bytes)
     return FLASHE_OK;
 }
 
-// A model-wide codec call's layer table into ctx->codec_tab.  (Pageable source: the copy has left `tab` when the call returns; stream
-// order keeps an earlier launch's table intact until it ends.)
-template <class Layer> int stage_table(flashe_ctx *ctx, const std::vector<Layer> &tab, const Layer **tab_dev, int *n_tab)
+bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+bool ct_aligned(const flashe_ctx *ctx, const void *p) { return (reinterpret_cast<uintptr_t>(p) & (ctx->limbs == 2 ? 15u : 7u)) == 0; }
+
+// ---- argument checks shared by the entry points ----
+int check_scheme(flashe_ctx *ctx, int scheme)
 {
-    if (tab.empty()) { *tab_dev = nullptr; *n_tab = 0; return FLASHE_OK; }
-    int rc = ensure(ctx, ctx->codec_tab, tab.size() * sizeof(Layer));
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->codec_tab.p, tab.data(), tab.size() * sizeof(Layer), hipMemcpyHostToDevice, ctx->env.stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->env.stream));
-    *tab_dev = static_cast<const Layer *>(ctx->codec_tab.p);
-    *n_tab = static_cast<int>(tab.size());
+    if (scheme != FLASHE_SCHEME_SINGLE && scheme != FLASHE_SCHEME_DOUBLE) return fail(ctx, FLASHE_EINVAL, "unknown scheme %d", scheme);
     return FLASHE_OK;
 }
+
+// 2-limb elements move 16 bytes at a time
+int check_wide_aligned(flashe_ctx *ctx, std::initializer_list<const void *> vecs)
+{
+    if (ctx->limbs == 2)
+        for (const void *p : vecs)
+            if (!aligned16(p)) return fail(ctx, FLASHE_EINVAL, "device vectors must be 16-byte aligned");
+    return FLASHE_OK;
+}
+
+// a sum written by the pass that reads the vectors: aligned like a ciphertext vector
+int check_sum_aligned(flashe_ctx *ctx, const void *sum_out_dev)
+{
+    return ct_aligned(ctx, sum_out_dev) ? FLASHE_OK : fail(ctx, FLASHE_EINVAL, "sum_out_dev must be aligned like a ciphertext vector");
+}
+
+// The double mask of client idx subtracts the stream of prefix idx + 1, and the reference builds that prefix with
+// (self.idx + 1).to_bytes(4, 'big') (jzf_flashe.py:352-353): OverflowError for idx = 2^32 - 1.  The raw ABI refuses the same value
+// instead of wrapping to prefix 0 (SURVEY.md section 8, "ranges: idx + 1 < 2^32").
+int check_double_idx(flashe_ctx *ctx, int scheme, const uint32_t *idx, int n_idx)
+{
+    if (scheme != FLASHE_SCHEME_DOUBLE || !idx) return FLASHE_OK;
+    for (int v = 0; v < n_idx; v++)
+        if (idx[v] == 0xffffffffu)
+            return fail(ctx, FLASHE_EINVAL, "double mask: idx + 1 = 2^32 does not fit the 4-byte prefix field (entry %d; the reference raises OverflowError, jzf_flashe.py:352-353)", v);
+    return FLASHE_OK;
+}
+
+int check_field_bits(flashe_ctx *ctx, int field_bits)
+{
+    if (field_bits < 1 || field_bits > 64 || field_bits > ctx->int_bits)
+        return fail(ctx, FLASHE_EINVAL, "field_bits must be in [1, min(64, int_bits)], got %d", field_bits);
+    return FLASHE_OK;
+}
+
+int check_range(flashe_ctx *ctx, uint64_t n, uint64_t first, uint64_t count)
+{
+    if (first > n || count > n - first) return fail(ctx, FLASHE_EINVAL, "range [%llu, +%llu) exceeds n = %llu",
+                                                    static_cast<unsigned long long>(first), static_cast<unsigned long long>(count),
+                                                    static_cast<unsigned long long>(n));
+    return FLASHE_OK;
+}
+
+int check_prf_args(flashe_ctx *ctx, int n_add, int n_minus, uint32_t n_jobs, const void *out, const void *in, int in_limbs)
+{
+    if (n_add < 0 || n_minus < 0) return fail(ctx, FLASHE_EINVAL, "negative prefix list length: add %d minus %d", n_add, n_minus);
+    if (n_jobs == 0) return fail(ctx, FLASHE_EINVAL, "n_jobs must be >= 1");
+    if (in && in_limbs != 1 && in_limbs != ctx->limbs) return fail(ctx, FLASHE_EINVAL, "in_limbs must be 1 or %d, got %d", ctx->limbs, in_limbs);
+    if (in && ctx->limbs == 1 && in_limbs != 1) return fail(ctx, FLASHE_EINVAL, "in_limbs must be 1 for int_bits <= 64");
+    if (ctx->limbs == 2 && (!aligned16(out) || (in && in_limbs == 2 && !aligned16(in))))
+        return fail(ctx, FLASHE_EINVAL, "device vectors of 2-limb elements must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(in)) & 7u)
+        return fail(ctx, FLASHE_EINVAL, "device vectors must be 8-byte aligned");
+    return FLASHE_OK;
+}
+
+// out = in + sum term(add[k]) - sum term(minus[k]) over prefix lists of ANY length (the reference sums whatever set_idx_list
+// produced: one minus prefix per uploaded client in single-mask mode, one pair per run of a dropout pattern,
+// jzf_flashe.py:126-150,311-314).  One launch holds kMaxIdx prefixes per list in its argument block; longer lists go in
+// several launches that accumulate in place (first pass in -> out, later passes out -> out: the sums are additive mod 2^b and
+// every lane reads its element before it writes it).
+hipError_t prf_lists(flashe_ctx *ctx, uint32_t iter, const uint32_t *add, int n_add, const uint32_t *minus, int n_minus,
+                     uint64_t n, uint32_t n_jobs, uint64_t first, uint64_t count, const uint64_t *in_dev, int in_limbs,
+                     uint64_t *out_dev)
+{
+    int a = 0, m = 0;
+    bool first_pass = true;
+    while (first_pass || a < n_add || m < n_minus) {
+        const int na = std::min(kMaxIdx, n_add - a), nm = std::min(kMaxIdx, n_minus - m);
+        const hipError_t e = launch_prf(ctx->env, iter, add + a, na, minus + m, nm, n, n_jobs, first, count,
+                                        first_pass ? in_dev : out_dev, first_pass ? in_limbs : ctx->limbs, out_dev);
+        if (e != hipSuccess) return e;
+        a += na; m += nm;
+        first_pass = false;
+    }
+    return hipSuccess;
+}
+
+}  // namespace flashe_host
+
+using namespace flashe_host;
+
+namespace {
 
 // Zero memory that held key material in a way the optimiser may not drop.
 void wipe(void *p, size_t bytes)
@@ -208,8 +278,6 @@ int check_device_flag(flashe_ctx *ctx)
     return FLASHE_OK;
 }
 
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 // (Tmp, the staging lease of the host-pointer twins: ctx.h)
 size_t pool_budget()
 {
@@ -228,22 +296,6 @@ struct HipBackend final : flashe_pool::Backend {
 };
 HipBackend &hip_backend() { static HipBackend b; return b; }
 
-// ---- argument checks shared by the entry points ----
-int check_scheme(flashe_ctx *ctx, int scheme)
-{
-    if (scheme != FLASHE_SCHEME_SINGLE && scheme != FLASHE_SCHEME_DOUBLE) return fail(ctx, FLASHE_EINVAL, "unknown scheme %d", scheme);
-    return FLASHE_OK;
-}
-
-// 2-limb elements move 16 bytes at a time
-int check_wide_aligned(flashe_ctx *ctx, std::initializer_list<const void *> vecs)
-{
-    if (ctx->limbs == 2)
-        for (const void *p : vecs)
-            if (!aligned16(p)) return fail(ctx, FLASHE_EINVAL, "device vectors must be 16-byte aligned");
-    return FLASHE_OK;
-}
-
 // every one of the n vectors given and `align`-byte aligned
 template <class T> int check_operands(flashe_ctx *ctx, int n, const T *const *v, int align)
 {
@@ -253,13 +305,6 @@ template <class T> int check_operands(flashe_ctx *ctx, int n, const T *const *v,
     return FLASHE_OK;
 }
 
-bool ct_aligned(const flashe_ctx *ctx, const void *p) { return (reinterpret_cast<uintptr_t>(p) & (ctx->limbs == 2 ? 15u : 7u)) == 0; }
-
-// a sum written by the pass that reads the vectors: aligned like a ciphertext vector, and none of them
-int check_sum_aligned(flashe_ctx *ctx, const void *sum_out_dev)
-{
-    return ct_aligned(ctx, sum_out_dev) ? FLASHE_OK : fail(ctx, FLASHE_EINVAL, "sum_out_dev must be aligned like a ciphertext vector");
-}
 template <class P, class Q> int check_sum_apart(flashe_ctx *ctx, const void *sum_out_dev, int n_vec, P pt_dev, Q ct_dev)
 {
     for (int v = 0; v < n_vec; v++)
@@ -280,29 +325,6 @@ template <class Launch> int batch_shares(flashe_ctx *ctx, int n_vec, Launch &&la
 }
 
 }  // namespace
-
-namespace flashe_host {
-
-// The double mask of client idx subtracts the stream of prefix idx + 1, and the reference builds that prefix with
-// (self.idx + 1).to_bytes(4, 'big') (jzf_flashe.py:352-353): OverflowError for idx = 2^32 - 1.  The raw ABI refuses the same value
-// instead of wrapping to prefix 0 (SURVEY.md section 8, "ranges: idx + 1 < 2^32").
-int check_double_idx(flashe_ctx *ctx, int scheme, const uint32_t *idx, int n_idx)
-{
-    if (scheme != FLASHE_SCHEME_DOUBLE || !idx) return FLASHE_OK;
-    for (int v = 0; v < n_idx; v++)
-        if (idx[v] == 0xffffffffu)
-            return fail(ctx, FLASHE_EINVAL, "double mask: idx + 1 = 2^32 does not fit the 4-byte prefix field (entry %d; the reference raises OverflowError, jzf_flashe.py:352-353)", v);
-    return FLASHE_OK;
-}
-
-int check_field_bits(flashe_ctx *ctx, int field_bits)
-{
-    if (field_bits < 1 || field_bits > 64 || field_bits > ctx->int_bits)
-        return fail(ctx, FLASHE_EINVAL, "field_bits must be in [1, min(64, int_bits)], got %d", field_bits);
-    return FLASHE_OK;
-}
-
-}  // namespace flashe_host
 
 hipError_t flashe_host::Tmp::alloc(flashe_ctx *ctx, size_t bytes)
 {
@@ -784,41 +806,6 @@ int flashe_event_elapsed_ms(flashe_ctx *ctx, void *start, void *stop, float *ms)
 }
 
 // ---- PRF / encrypt / decrypt ----
-static int check_prf_args(flashe_ctx *ctx, int n_add, int n_minus, uint32_t n_jobs, const void *out, const void *in, int in_limbs)
-{
-    if (n_add < 0 || n_minus < 0) return fail(ctx, FLASHE_EINVAL, "negative prefix list length: add %d minus %d", n_add, n_minus);
-    if (n_jobs == 0) return fail(ctx, FLASHE_EINVAL, "n_jobs must be >= 1");
-    if (in && in_limbs != 1 && in_limbs != ctx->limbs) return fail(ctx, FLASHE_EINVAL, "in_limbs must be 1 or %d, got %d", ctx->limbs, in_limbs);
-    if (in && ctx->limbs == 1 && in_limbs != 1) return fail(ctx, FLASHE_EINVAL, "in_limbs must be 1 for int_bits <= 64");
-    if (ctx->limbs == 2 && (!aligned16(out) || (in && in_limbs == 2 && !aligned16(in))))
-        return fail(ctx, FLASHE_EINVAL, "device vectors of 2-limb elements must be 16-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(in)) & 7u)
-        return fail(ctx, FLASHE_EINVAL, "device vectors must be 8-byte aligned");
-    return FLASHE_OK;
-}
-
-// out = in + sum term(add[k]) - sum term(minus[k]) over prefix lists of ANY length (the reference sums whatever set_idx_list
-// produced: one minus prefix per uploaded client in single-mask mode, one pair per run of a dropout pattern,
-// jzf_flashe.py:126-150,311-314).  One launch holds kMaxIdx prefixes per list in its argument block; longer lists go in
-// several launches that accumulate in place (first pass in -> out, later passes out -> out: the sums are additive mod 2^b and
-// every lane reads its element before it writes it).
-static hipError_t prf_lists(flashe_ctx *ctx, uint32_t iter, const uint32_t *add, int n_add, const uint32_t *minus, int n_minus,
-                            uint64_t n, uint32_t n_jobs, uint64_t first, uint64_t count, const uint64_t *in_dev, int in_limbs,
-                            uint64_t *out_dev)
-{
-    int a = 0, m = 0;
-    bool first_pass = true;
-    while (first_pass || a < n_add || m < n_minus) {
-        const int na = std::min(kMaxIdx, n_add - a), nm = std::min(kMaxIdx, n_minus - m);
-        const hipError_t e = launch_prf(ctx->env, iter, add + a, na, minus + m, nm, n, n_jobs, first, count,
-                                        first_pass ? in_dev : out_dev, first_pass ? in_limbs : ctx->limbs, out_dev);
-        if (e != hipSuccess) return e;
-        a += na; m += nm;
-        first_pass = false;
-    }
-    return hipSuccess;
-}
-
 // the whole-vector forms: their range twins over [0, n)
 int flashe_mask_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_idx, uint64_t n, uint32_t n_jobs, uint64_t *out_dev)
 {
@@ -861,7 +848,6 @@ int flashe_encrypt_batch_dev(flashe_ctx *ctx, uint32_t iter, int scheme, uint64_
 // that is 8 bytes moved for 20 useful bits, and the b <= 32 kernels are bound by exactly those bytes.  The *_u32_dev entry points
 // take and produce the same VALUES as uint32 arrays: the hot round (batched encrypt, reduce fused with the decrypt of its result)
 // moves half the bytes; flashe_widen_u32_dev / flashe_narrow_u32_dev convert at the edges.
-static int check_range(flashe_ctx *ctx, uint64_t n, uint64_t first, uint64_t count);
 static int check_u32(flashe_ctx *ctx, uint64_t n, uint32_t n_jobs)
 {
     if (ctx->int_bits > 32) return fail(ctx, FLASHE_EINVAL, "the uint32 layout needs int_bits <= 32, this ctx has %d", ctx->int_bits);
@@ -1121,239 +1107,6 @@ int flashe_decrypt_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, 
     return flashe_decrypt_range_dev(ctx, iter, add_idx, n_add, minus_idx, n_minus, n, n_jobs, 0, n, in_dev, out_dev);
 }
 
-// ---- fused codec: quantise -> encrypt and decrypt -> unquantise in ONE launch each ----
-static int check_codec_bits(flashe_ctx *ctx, int element_bits);
-int flashe_quantize_encrypt_dev(flashe_ctx *ctx, uint32_t iter, uint32_t idx, int scheme, uint64_t n, uint32_t n_jobs, const void *x_dev,
-                                int x_is_f64, double alpha, int element_bits, const double *u_dev, uint64_t *ct_dev)
-{
-    CHECK_CTX(ctx);
-    if (int rc = check_scheme(ctx, scheme)) return rc;
-    if (n && (!x_dev || !u_dev || !ct_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if (!(alpha > 0)) return fail(ctx, FLASHE_EINVAL, "alpha must be positive");
-    if (element_bits < 1 || element_bits > 62 || element_bits > ctx->int_bits)
-        return fail(ctx, FLASHE_EINVAL, "element_bits must be in [1, min(62, int_bits)], got %d", element_bits);
-    int rc = check_prf_args(ctx, 1, scheme, n_jobs, ct_dev, nullptr, 0);
-    if (rc) return rc;
-    const Codec cq = codec_quantize_front(x_dev, x_is_f64 != 0, alpha, element_bits, u_dev);
-    LaunchEnv env = ctx->env;
-    env.codec = &cq;
-    if ((rc = check_double_idx(ctx, scheme, &idx, 1))) return rc;
-    const uint32_t add = idx, minus = idx + 1;
-    HIP_TRY(ctx, launch_prf(env, iter, &add, 1, &minus, scheme == FLASHE_SCHEME_DOUBLE ? 1 : 0, n, n_jobs, 0, n, nullptr, 0, ct_dev));
-    return FLASHE_OK;
-}
-
-// the unmask + unquantise of prefix lists of any length: all but the last group accumulate into ctx scratch, the last launch writes
-// the floats
-static int prf_lists_unquantize(flashe_ctx *ctx, const Codec &cq, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx,
-                                int n_minus, uint64_t n, uint32_t n_jobs, uint64_t first, uint64_t count, const uint64_t *in_dev)
-{
-    const uint64_t *src = in_dev;
-    int a = 0, m = 0;
-    if (n_add > kMaxIdx || n_minus > kMaxIdx) {
-        const int rc = ensure(ctx, ctx->stream_tmp, vec_bytes(ctx, count));
-        if (rc) return rc;
-        uint64_t *tmp = static_cast<uint64_t *>(ctx->stream_tmp.p);
-        while (n_add - a > kMaxIdx || n_minus - m > kMaxIdx) {
-            const int na = std::min(kMaxIdx, n_add - a), nm = std::min(kMaxIdx, n_minus - m);
-            HIP_TRY(ctx, launch_prf(ctx->env, iter, add_idx + a, na, minus_idx + m, nm, n, n_jobs, first, count, src, ctx->limbs, tmp));
-            a += na; m += nm; src = tmp;
-        }
-    }
-    LaunchEnv env = ctx->env;
-    env.codec = &cq;
-    HIP_TRY(ctx, launch_prf(env, iter, add_idx + a, n_add - a, minus_idx + m, n_minus - m, n, n_jobs, first, count, src, ctx->limbs,
-                            const_cast<uint64_t *>(src)));
-    return FLASHE_OK;
-}
-
-int flashe_decrypt_unquantize_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx, int n_minus,
-                                  uint64_t n, uint32_t n_jobs, const uint64_t *in_dev, double alpha, int element_bits, int num_clients,
-                                  double *out_dev)
-{
-    CHECK_CTX(ctx);
-    if (n && (!in_dev || !out_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if (!(alpha > 0) || num_clients < 1) return fail(ctx, FLASHE_EINVAL, "alpha must be positive and num_clients >= 1");
-    int rc = check_codec_bits(ctx, element_bits);
-    if (rc) return rc;
-    rc = check_prf_args(ctx, n_add, n_minus, n_jobs, in_dev, in_dev, ctx->limbs);
-    if (rc) return rc;
-    if (n == 0) return FLASHE_OK;
-    Codec cq{};
-    codec_unquantize_back(&cq, alpha, element_bits, num_clients, out_dev);
-    if (n_add == 0 && n_minus == 0) {
-        // nothing to unmask: reduce mod 2^b like every decrypt does, then unquantise (two launches; not a shape a round produces)
-        rc = ensure(ctx, ctx->stream_tmp, vec_bytes(ctx, n));
-        if (rc) return rc;
-        uint64_t *tmp = static_cast<uint64_t *>(ctx->stream_tmp.p);
-        HIP_TRY(ctx, launch_combine(ctx->env, n, in_dev, ctx->limbs, nullptr, nullptr, tmp));
-        HIP_TRY(ctx, launch_unquantize(ctx->env, n, tmp, ctx->limbs, alpha, element_bits, num_clients, out_dev));
-        return FLASHE_OK;
-    }
-    return prf_lists_unquantize(ctx, cq, iter, add_idx, n_add, minus_idx, n_minus, n, n_jobs, 0, n, in_dev);
-}
-
-// ---- the same over a flattened model: one launch, per-layer parameters from a device table (jzf_aggregator.py:721-741, :887-899) ----
-static int check_range(flashe_ctx *ctx, uint64_t n, uint64_t first, uint64_t count);
-// validates the caller's table and stages the entries of the non-empty layers on the device (ctx->codec_tab)
-static int stage_codec_layers(flashe_ctx *ctx, uint64_t n, const flashe_codec_layer *layers, int n_layers, bool front, int element_bits,
-                              int num_clients, uint64_t first, uint64_t count, const CodecLayer **tab_dev, int *n_tab)
-{
-    if (n_layers < 1 || !layers) return fail(ctx, FLASHE_EINVAL, "the layer table needs at least one entry");
-    if (layers[0].start != 0) return fail(ctx, FLASHE_EINVAL, "layers[0].start must be 0");
-    if (ctx->capturing) return fail(ctx, FLASHE_EINVAL, "the model-wide codec calls stage their layer table per call and cannot be captured into a graph");
-    std::vector<CodecLayer> tab;
-    tab.reserve(static_cast<size_t>(n_layers));
-    for (int l = 0; l < n_layers; l++) {
-        const flashe_codec_layer &e = layers[l];
-        const uint64_t end = l + 1 < n_layers ? layers[l + 1].start : n;
-        if (e.start > end || end > n) return fail(ctx, FLASHE_EINVAL, "layer %d: starts must ascend and stay within n", l);
-        if (e.reserved) return fail(ctx, FLASHE_EINVAL, "layer %d: reserved field must be 0", l);
-        if (e.start == end) continue;                                   // an empty layer holds no element
-        if (!(e.alpha > 0)) return fail(ctx, FLASHE_EINVAL, "layer %d: alpha must be positive", l);
-        const bool touched = e.start < first + count && end > first;
-        if (front && touched && !e.x_dev) return fail(ctx, FLASHE_EINVAL, "layer %d: null x_dev", l);
-        if (front && (reinterpret_cast<uintptr_t>(e.x_dev) & (e.x_is_f64 ? 7u : 3u))) return fail(ctx, FLASHE_EINVAL, "layer %d: x_dev is misaligned", l);
-        tab.push_back(front ? codec_layer_front(e.start, e.x_dev, e.x_is_f64 != 0, e.alpha, element_bits)
-                            : codec_layer_back(e.start, e.alpha, element_bits, num_clients));
-    }
-    return stage_table(ctx, tab, tab_dev, n_tab);
-}
-
-int flashe_quantize_encrypt_model_dev(flashe_ctx *ctx, uint32_t iter, uint32_t idx, int scheme, uint64_t n, uint32_t n_jobs, uint64_t first,
-                                      uint64_t count, const flashe_codec_layer *layers, int n_layers, int element_bits, const double *u_dev,
-                                      uint64_t *ct_dev)
-{
-    CHECK_CTX(ctx);
-    if (int rc = check_scheme(ctx, scheme)) return rc;
-    if (count && (!u_dev || !ct_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if (element_bits < 1 || element_bits > 62 || element_bits > ctx->int_bits)
-        return fail(ctx, FLASHE_EINVAL, "element_bits must be in [1, min(62, int_bits)], got %d", element_bits);
-    int rc = check_prf_args(ctx, 1, scheme, n_jobs, ct_dev, nullptr, 0);
-    if (rc || (rc = check_range(ctx, n, first, count))) return rc;
-    if (reinterpret_cast<uintptr_t>(u_dev) & 7u) return fail(ctx, FLASHE_EINVAL, "u_dev must be 8-byte aligned");
-    const CodecLayer *tab = nullptr;
-    int n_tab = 0;
-    rc = stage_codec_layers(ctx, n, layers, n_layers, true, element_bits, 1, first, count, &tab, &n_tab);
-    if (rc || count == 0) return rc;
-    Codec cq{};
-    cq.x = tab;                     // (non-null = front end on; the values come through the table)
-    cq.u = u_dev; cq.layers = tab; cq.n_layers = n_tab; cq.k0 = first;
-    LaunchEnv env = ctx->env;
-    env.codec = &cq;
-    if ((rc = check_double_idx(ctx, scheme, &idx, 1))) return rc;
-    const uint32_t add = idx, minus = idx + 1;
-    HIP_TRY(ctx, launch_prf(env, iter, &add, 1, &minus, scheme == FLASHE_SCHEME_DOUBLE ? 1 : 0, n, n_jobs, first, count, nullptr, 0, ct_dev));
-    return FLASHE_OK;
-}
-
-int flashe_decrypt_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx, int n_minus,
-                                        uint64_t n, uint32_t n_jobs, uint64_t first, uint64_t count, const uint64_t *in_dev,
-                                        const flashe_codec_layer *layers, int n_layers, int element_bits, int num_clients, double *out_dev)
-{
-    CHECK_CTX(ctx);
-    if (count && (!in_dev || !out_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if (num_clients < 1) return fail(ctx, FLASHE_EINVAL, "num_clients must be >= 1");
-    if (n_add + n_minus == 0) return fail(ctx, FLASHE_EINVAL, "decrypt_unquantize_model: at least one prefix (a round always has one)");
-    int rc = check_codec_bits(ctx, element_bits);
-    if (rc) return rc;
-    rc = check_prf_args(ctx, n_add, n_minus, n_jobs, in_dev, in_dev, ctx->limbs);
-    if (rc || (rc = check_range(ctx, n, first, count))) return rc;
-    if ((n_add && !add_idx) || (n_minus && !minus_idx)) return fail(ctx, FLASHE_EINVAL, "null prefix list");
-    const CodecLayer *tab = nullptr;
-    int n_tab = 0;
-    rc = stage_codec_layers(ctx, n, layers, n_layers, false, element_bits, num_clients, first, count, &tab, &n_tab);
-    if (rc || count == 0) return rc;
-    Codec cq{};
-    cq.fout = out_dev; cq.layers = tab; cq.n_layers = n_tab; cq.k0 = first;
-    return prf_lists_unquantize(ctx, cq, iter, add_idx, n_add, minus_idx, n_minus, n, n_jobs, first, count, in_dev);
-}
-
-// unflatten_weights + QuantizingClient.unquantize (jzf_aggregator.py:652-671, jzf_quantize.py:493-540) of a flattened vector that is
-// already decrypted -- the sparse job's way back, whose decrypt is the sparse minus-mask pass, not a prefix list
-int flashe_unquantize_model_dev(flashe_ctx *ctx, uint64_t n, uint64_t first, uint64_t count, const uint64_t *in_dev,
-                                const flashe_codec_layer *layers, int n_layers, int element_bits, int num_clients, double *out_dev)
-{
-    CHECK_CTX(ctx);
-    if (count && (!in_dev || !out_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if (num_clients < 1) return fail(ctx, FLASHE_EINVAL, "num_clients must be >= 1");
-    int rc = check_codec_bits(ctx, element_bits);
-    if (rc || (rc = check_range(ctx, n, first, count))) return rc;
-    if ((ctx->limbs == 2 && !aligned16(in_dev)) || (reinterpret_cast<uintptr_t>(in_dev) & 7u) || (reinterpret_cast<uintptr_t>(out_dev) & 7u))
-        return fail(ctx, FLASHE_EINVAL, "misaligned vector");
-    const CodecLayer *tab = nullptr;
-    int n_tab = 0;
-    rc = stage_codec_layers(ctx, n, layers, n_layers, false, element_bits, num_clients, first, count, &tab, &n_tab);
-    if (rc || count == 0) return rc;
-    Codec cq{};
-    cq.fout = out_dev; cq.layers = tab; cq.n_layers = n_tab; cq.k0 = first;
-    HIP_TRY(ctx, launch_unquantize_model(ctx->env, count, in_dev, cq, out_dev));
-    return FLASHE_OK;
-}
-
-// ---- the BATCHED codec over a flattened model (the paper's main job configuration, "batch": true) ----
-static int stage_batch_layers(flashe_ctx *ctx, const flashe_batch_layer *layers, int n_layers, bool front, int element_bits, int field_bits,
-                              int num_clients, uint64_t *n_elems, uint64_t *n_values, const BatchLayer **tab_dev, int *n_tab)
-{
-    if (n_layers < 1 || !layers) return fail(ctx, FLASHE_EINVAL, "the layer table needs at least one entry");
-    if (ctx->capturing) return fail(ctx, FLASHE_EINVAL, "the model-wide codec calls stage their layer table per call and cannot be captured into a graph");
-    if (element_bits < 1 || element_bits > 62 || field_bits < element_bits || field_bits > ctx->int_bits)
-        return fail(ctx, FLASHE_EINVAL, "need 1 <= element_bits <= field_bits <= int_bits (element_bits <= 62)");
-    const uint64_t bs = static_cast<uint64_t>(ctx->int_bits / field_bits);
-    std::vector<BatchLayer> tab;
-    uint64_t e = 0, v = 0;
-    for (int l = 0; l < n_layers; l++) {
-        const flashe_batch_layer &y = layers[l];
-        if (y.reserved) return fail(ctx, FLASHE_EINVAL, "layer %d: reserved field must be 0", l);
-        if (y.size == 0) continue;
-        if (!(y.alpha > 0)) return fail(ctx, FLASHE_EINVAL, "layer %d: alpha must be positive", l);
-        if (front && (!y.x_dev || (reinterpret_cast<uintptr_t>(y.x_dev) & (y.x_is_f64 ? 7u : 3u)))) return fail(ctx, FLASHE_EINVAL, "layer %d: null or misaligned x_dev", l);
-        tab.push_back(front ? batch_layer_front(e, v, y.size, y.x_dev, y.x_is_f64 != 0, y.alpha, element_bits)
-                            : batch_layer_back(e, v, y.size, y.alpha, element_bits, num_clients));
-        e += (y.size + bs - 1) / bs;                       // every layer is padded to whole elements on its own (jzf_quantize.py:166-171)
-        v += y.size;
-    }
-    *n_elems = e; *n_values = v;
-    return stage_table(ctx, tab, tab_dev, n_tab);
-}
-
-int flashe_quantize_batch_model_dev(flashe_ctx *ctx, const flashe_batch_layer *layers, int n_layers, int element_bits, int field_bits,
-                                    const double *u_dev, uint64_t n_elems, uint64_t *out_dev)
-{
-    CHECK_CTX(ctx);
-    const BatchLayer *tab = nullptr;
-    int n_tab = 0;
-    uint64_t e = 0, v = 0;
-    int rc = stage_batch_layers(ctx, layers, n_layers, true, element_bits, field_bits, 1, &e, &v, &tab, &n_tab);
-    if (rc) return rc;
-    if (e != n_elems) return fail(ctx, FLASHE_EINVAL, "the layers batch into %llu elements, n_elems says %llu", static_cast<unsigned long long>(e),
-                                  static_cast<unsigned long long>(n_elems));
-    if (n_elems && (!u_dev || !out_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if ((ctx->limbs == 2 && !aligned16(out_dev)) || (reinterpret_cast<uintptr_t>(out_dev) & 7u) || (reinterpret_cast<uintptr_t>(u_dev) & 7u))
-        return fail(ctx, FLASHE_EINVAL, "misaligned vector");
-    if (n_elems) HIP_TRY(ctx, launch_quantize_batch_model(ctx->env, tab, n_tab, field_bits, u_dev, n_elems, out_dev));
-    return FLASHE_OK;
-}
-
-int flashe_unbatch_unquantize_model_dev(flashe_ctx *ctx, const flashe_batch_layer *layers, int n_layers, int element_bits, int field_bits,
-                                        int num_clients, const uint64_t *in_dev, uint64_t n_elems, double *out_dev)
-{
-    CHECK_CTX(ctx);
-    if (num_clients < 1) return fail(ctx, FLASHE_EINVAL, "num_clients must be >= 1");
-    const BatchLayer *tab = nullptr;
-    int n_tab = 0;
-    uint64_t e = 0, v = 0;
-    int rc = stage_batch_layers(ctx, layers, n_layers, false, element_bits, field_bits, num_clients, &e, &v, &tab, &n_tab);
-    if (rc) return rc;
-    if (e != n_elems) return fail(ctx, FLASHE_EINVAL, "the layers batch into %llu elements, n_elems says %llu", static_cast<unsigned long long>(e),
-                                  static_cast<unsigned long long>(n_elems));
-    if (v && (!in_dev || !out_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if ((ctx->limbs == 2 && !aligned16(in_dev)) || (reinterpret_cast<uintptr_t>(in_dev) & 7u) || (reinterpret_cast<uintptr_t>(out_dev) & 7u))
-        return fail(ctx, FLASHE_EINVAL, "misaligned vector");
-    if (v) HIP_TRY(ctx, launch_unbatch_unquantize_model(ctx->env, tab, n_tab, field_bits, in_dev, v, out_dev));
-    return FLASHE_OK;
-}
-
 // ---- normalise / unnormalise (QuantizingClient.normalize / unnormalize, jzf_quantize.py:542-564) ----
 int flashe_shift_dev(flashe_ctx *ctx, uint64_t n, void *x_dev, int x_is_f64, double shift, int wide)
 {
@@ -1391,7 +1144,7 @@ int flashe_mean_std_dev(flashe_ctx *ctx, uint64_t n, const void *x_dev, int x_is
     return FLASHE_OK;
 }
 
-// ---- caller-owned tensors either side of the model-wide codec (tensors.hip) ----
+// ---- the ctx stream among a framework's streams ----
 int flashe_ctx_stream(const flashe_ctx *ctx, void **stream)
 {
     if (!ctx || !stream) return FLASHE_EINVAL;
@@ -1421,484 +1174,7 @@ int flashe_event_query(flashe_ctx *ctx, void *event, int *done)
     return FLASHE_OK;
 }
 
-static int tensor_elem_bytes(int32_t dtype)
-{
-    return dtype == FLASHE_TENSOR_F64 ? 8 : dtype == FLASHE_TENSOR_F32 ? 4 : (dtype == FLASHE_TENSOR_F16 || dtype == FLASHE_TENSOR_BF16) ? 2 : 0;
-}
-
-// the table's shape, dtypes, flags and pointers (nothing is launched before every layer passed)
-static int check_tensor_layers(flashe_ctx *ctx, uint64_t n, const flashe_tensor_layer *layers, int n_layers)
-{
-    if (n_layers < 1 || !layers) return fail(ctx, FLASHE_EINVAL, "the layer table needs at least one entry");
-    if (layers[0].start != 0) return fail(ctx, FLASHE_EINVAL, "layers[0].start must be 0");
-    if (ctx->capturing) return fail(ctx, FLASHE_EINVAL, "the tensor codec calls stage their layer table per call and cannot be captured into a graph");
-    for (int l = 0; l < n_layers; l++) {
-        const flashe_tensor_layer &y = layers[l];
-        const uint64_t end = l + 1 < n_layers ? layers[l + 1].start : n;
-        if (y.start > end || end > n) return fail(ctx, FLASHE_EINVAL, "layer %d: starts must ascend and stay within n", l);
-        const int es = tensor_elem_bytes(y.dtype);
-        if (!es) return fail(ctx, FLASHE_EINVAL, "layer %d: unknown dtype %d", l, static_cast<int>(y.dtype));
-        if (y.flags & ~(FLASHE_TENSOR_SHIFT | FLASHE_TENSOR_SHIFT_WIDE | FLASHE_TENSOR_LOOP_F64))
-            return fail(ctx, FLASHE_EINVAL, "layer %d: unknown flags 0x%x", l, static_cast<unsigned>(y.flags));
-        if (y.start == end) continue;
-        if (!y.ptr) return fail(ctx, FLASHE_EINVAL, "layer %d: null ptr", l);
-        if (reinterpret_cast<uintptr_t>(y.ptr) % static_cast<uintptr_t>(es)) return fail(ctx, FLASHE_EINVAL, "layer %d: ptr is not aligned to its element size", l);
-    }
-    return FLASHE_OK;
-}
-
-// the cohort's shared rows carry no pointer: starts, dtypes and flags only
-static int check_tensor_layers_shape(flashe_ctx *ctx, uint64_t n, const flashe_tensor_layer *layers, int n_layers)
-{
-    if (n_layers < 1 || !layers) return fail(ctx, FLASHE_EINVAL, "the layer table needs at least one entry");
-    if (layers[0].start != 0) return fail(ctx, FLASHE_EINVAL, "layers[0].start must be 0");
-    if (ctx->capturing) return fail(ctx, FLASHE_EINVAL, "the tensor codec calls stage their layer table per call and cannot be captured into a graph");
-    for (int l = 0; l < n_layers; l++) {
-        const flashe_tensor_layer &y = layers[l];
-        const uint64_t end = l + 1 < n_layers ? layers[l + 1].start : n;
-        if (y.start > end || end > n) return fail(ctx, FLASHE_EINVAL, "layer %d: starts must ascend and stay within n", l);
-        if (!tensor_elem_bytes(y.dtype)) return fail(ctx, FLASHE_EINVAL, "layer %d: unknown dtype %d", l, static_cast<int>(y.dtype));
-        if (y.flags & ~(FLASHE_TENSOR_SHIFT | FLASHE_TENSOR_SHIFT_WIDE | FLASHE_TENSOR_LOOP_F64))
-            return fail(ctx, FLASHE_EINVAL, "layer %d: unknown flags 0x%x", l, static_cast<unsigned>(y.flags));
-    }
-    return FLASHE_OK;
-}
-
-extern "C++" template <class T> static int upload_tab(flashe_ctx *ctx, flashe_ctx::Buf &b, const std::vector<T> &tab, const T **tab_dev)
-{
-    int rc = ensure(ctx, b, std::max<size_t>(tab.size(), 1) * sizeof(T));
-    if (rc) return rc;
-    if (!tab.empty()) {
-        HIP_TRY(ctx, hipMemcpyAsync(b.p, tab.data(), tab.size() * sizeof(T), hipMemcpyHostToDevice, ctx->env.stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->env.stream));
-    }
-    *tab_dev = static_cast<const T *>(b.p);
-    return FLASHE_OK;
-}
-
-// the compute-type values of every layer of [first, first + count): x[l] = where the codec reads layer l, f64[l] = its loop dtype
-static int stage_tensor_front(flashe_ctx *ctx, uint64_t n, const flashe_tensor_layer *layers, int n_layers, uint64_t first, uint64_t count,
-                              std::vector<const void *> &x, std::vector<int> &f64)
-{
-    x.assign(static_cast<size_t>(n_layers), nullptr);
-    f64.assign(static_cast<size_t>(n_layers), 0);
-    std::vector<TensorStage> st;
-    std::vector<size_t> at;
-    std::vector<int> which;
-    uint64_t total = 0;
-    size_t bytes = 0;
-    for (int l = 0; l < n_layers; l++) {
-        const flashe_tensor_layer &y = layers[l];
-        const uint64_t end = l + 1 < n_layers ? layers[l + 1].start : n;
-        const bool loop64 = y.dtype == FLASHE_TENSOR_F64 || (y.flags & FLASHE_TENSOR_LOOP_F64);
-        f64[l] = loop64 ? 1 : 0;
-        x[l] = y.ptr;
-        const bool touched = y.start < first + count && end > first;
-        const bool direct = !(y.flags & FLASHE_TENSOR_SHIFT) && (y.dtype == FLASHE_TENSOR_F64 || (y.dtype == FLASHE_TENSOR_F32 && !loop64));
-        if (y.start == end || !touched || direct) continue;
-        bytes = (bytes + 15) & ~static_cast<size_t>(15);
-        st.push_back(TensorStage{total, y.ptr, nullptr, y.shift, y.dtype, y.flags | (loop64 ? kTensorLoopF64 : 0)});
-        at.push_back(bytes);
-        which.push_back(l);
-        total += end - y.start;
-        bytes += static_cast<size_t>(end - y.start) * (loop64 ? 8 : 4);
-    }
-    if (st.empty()) return FLASHE_OK;
-    int rc = ensure(ctx, ctx->tensor_ws, bytes);
-    if (rc) return rc;
-    for (size_t i = 0; i < st.size(); i++) {
-        st[i].dst = static_cast<char *>(ctx->tensor_ws.p) + at[i];
-        x[which[i]] = st[i].dst;
-    }
-    const TensorStage *tab = nullptr;
-    if ((rc = upload_tab(ctx, ctx->tensor_tab, st, &tab))) return rc;
-    HIP_TRY(ctx, launch_stage_layers(ctx->env, tab, static_cast<int>(st.size()), total));
-    return FLASHE_OK;
-}
-
-// the codec table of the model-wide front end from a checked tensor table: alphas checked, the stage pass run (what the prepared and
-// the online forms share)
-static int tensor_codec_layers(flashe_ctx *ctx, uint64_t n, const flashe_tensor_layer *layers, int n_layers, uint64_t first, uint64_t count,
-                               std::vector<flashe_codec_layer> &cl)
-{
-    for (int l = 0; l < n_layers; l++)
-        if (!(layers[l].alpha > 0) && (l + 1 < n_layers ? layers[l + 1].start : n) > layers[l].start)
-            return fail(ctx, FLASHE_EINVAL, "layer %d: alpha must be positive", l);
-    std::vector<const void *> x;
-    std::vector<int> f64;
-    if (int rc = stage_tensor_front(ctx, n, layers, n_layers, first, count, x, f64)) return rc;
-    cl.resize(static_cast<size_t>(n_layers));
-    for (int l = 0; l < n_layers; l++) cl[l] = flashe_codec_layer{layers[l].start, x[l], layers[l].alpha, f64[l], 0};
-    return FLASHE_OK;
-}
-
-// the batched form: the checks of flashe_quantize_batch_model_dev that do not need the staged table, the stage pass, the batch table
-static int tensor_batch_layers(flashe_ctx *ctx, const flashe_tensor_layer *layers, int n_layers, uint64_t n_values, int element_bits, int field_bits,
-                               const double *u_dev, uint64_t n_elems, const uint64_t *out_dev, std::vector<flashe_batch_layer> &bl)
-{
-    if (element_bits < 1 || element_bits > 62 || field_bits < element_bits || field_bits > ctx->int_bits)
-        return fail(ctx, FLASHE_EINVAL, "need 1 <= element_bits <= field_bits <= int_bits (element_bits <= 62)");
-    const uint64_t bs = static_cast<uint64_t>(ctx->int_bits / field_bits);
-    uint64_t e = 0;
-    for (int l = 0; l < n_layers; l++) {
-        const uint64_t size = (l + 1 < n_layers ? layers[l + 1].start : n_values) - layers[l].start;
-        if (size && !(layers[l].alpha > 0)) return fail(ctx, FLASHE_EINVAL, "layer %d: alpha must be positive", l);
-        e += (size + bs - 1) / bs;
-    }
-    if (e != n_elems) return fail(ctx, FLASHE_EINVAL, "the layers batch into %llu elements, n_elems says %llu", static_cast<unsigned long long>(e),
-                                  static_cast<unsigned long long>(n_elems));
-    if (n_elems && (!u_dev || !out_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if ((ctx->limbs == 2 && !aligned16(out_dev)) || (reinterpret_cast<uintptr_t>(out_dev) & 7u) || (reinterpret_cast<uintptr_t>(u_dev) & 7u))
-        return fail(ctx, FLASHE_EINVAL, "misaligned vector");
-    std::vector<const void *> x;
-    std::vector<int> f64;
-    if (int rc = stage_tensor_front(ctx, n_values, layers, n_layers, 0, n_values, x, f64)) return rc;
-    bl.resize(static_cast<size_t>(n_layers));
-    for (int l = 0; l < n_layers; l++)
-        bl[l] = flashe_batch_layer{(l + 1 < n_layers ? layers[l + 1].start : n_values) - layers[l].start, x[l], layers[l].alpha, f64[l], 0};
-    return FLASHE_OK;
-}
-
-int flashe_quantize_encrypt_tensors_dev(flashe_ctx *ctx, uint32_t iter, uint32_t idx, int scheme, uint64_t n, uint32_t n_jobs, uint64_t first,
-                                        uint64_t count, const flashe_tensor_layer *layers, int n_layers, int element_bits, const double *u_dev,
-                                        uint64_t *ct_dev)
-{
-    CHECK_CTX(ctx);
-    // the checks of flashe_quantize_encrypt_model_dev that do not need the table, before anything is launched
-    if (int rc = check_scheme(ctx, scheme)) return rc;
-    if (count && (!u_dev || !ct_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if (element_bits < 1 || element_bits > 62 || element_bits > ctx->int_bits)
-        return fail(ctx, FLASHE_EINVAL, "element_bits must be in [1, min(62, int_bits)], got %d", element_bits);
-    int rc = check_prf_args(ctx, 1, scheme, n_jobs, ct_dev, nullptr, 0);
-    if (rc || (rc = check_range(ctx, n, first, count)) || (rc = check_tensor_layers(ctx, n, layers, n_layers))) return rc;
-    if ((rc = check_double_idx(ctx, scheme, &idx, 1))) return rc;
-    std::vector<flashe_codec_layer> cl;
-    if ((rc = tensor_codec_layers(ctx, n, layers, n_layers, first, count, cl))) return rc;
-    return flashe_quantize_encrypt_model_dev(ctx, iter, idx, scheme, n, n_jobs, first, count, cl.data(), n_layers, element_bits, u_dev, ct_dev);
-}
-
-// ---- a cohort of co-located clients: C float models -> C ciphertexts + their sum (+ the decrypt mask) in one chained launch ----
-// The shared layer table, the C x n_layers sources and their storage dtypes.  A source already in its row's compute type without SHIFT is
-// read where it lies; every other one goes through ONE stage pass (tensors.hip) into ctx scratch, all clients together.
-// (the two entry points below share their argument checks -- cohort_check -- and their table and stage pass -- cohort_stage)
-static int cohort_check(flashe_ctx *ctx, const char *who, uint32_t first_idx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers,
-                        const void *const *src_dev, bool outs, int element_bits, const double *u_dev, std::vector<uint32_t> &idx)
-{
-    if (n_clients < 1) return fail(ctx, FLASHE_EINVAL, "%s: n_clients must be >= 1", who);
-    if (!src_dev || !outs || (n && !u_dev)) return fail(ctx, FLASHE_EINVAL, "%s: null argument", who);
-    if (element_bits < 1 || element_bits > 62 || element_bits > ctx->int_bits)
-        return fail(ctx, FLASHE_EINVAL, "element_bits must be in [1, min(62, int_bits)], got %d", element_bits);
-    if (reinterpret_cast<uintptr_t>(u_dev) & 7u) return fail(ctx, FLASHE_EINVAL, "u_dev must be 8-byte aligned");
-    int rc = check_tensor_layers_shape(ctx, n, layers, n_layers);
-    if (rc) return rc;
-    idx.resize(static_cast<size_t>(n_clients));
-    for (int c = 0; c < n_clients; c++) {
-        idx[c] = first_idx + static_cast<uint32_t>(c);
-        if (idx[c] < first_idx) return fail(ctx, FLASHE_EINVAL, "the cohort's cipher indices wrap around 2^32");
-    }
-    return check_double_idx(ctx, FLASHE_SCHEME_DOUBLE, idx.data(), n_clients);
-}
-
-// row_of = the non-empty layers of a cohort's shared table (the rows of the device table), each with a positive alpha and a compute dtype
-static int cohort_rows(flashe_ctx *ctx, uint64_t n, const flashe_tensor_layer *layers, int n_layers, std::vector<int> &row_of)
-{
-    row_of.clear();
-    for (int l = 0; l < n_layers; l++) {
-        const flashe_tensor_layer &y = layers[l];
-        if (y.start == (l + 1 < n_layers ? layers[l + 1].start : n)) continue;
-        if (!(y.alpha > 0)) return fail(ctx, FLASHE_EINVAL, "layer %d: alpha must be positive", l);
-        if (y.dtype != FLASHE_TENSOR_F32 && y.dtype != FLASHE_TENSOR_F64)
-            return fail(ctx, FLASHE_EINVAL, "layer %d: the shared row names the COMPUTE type, FLASHE_TENSOR_F32 or FLASHE_TENSOR_F64", l);
-        row_of.push_back(l);
-    }
-    return FLASHE_OK;
-}
-
-// rows of the device table (non-empty layers), the sources behind them, and ONE stage pass for every source that is not read in place
-// (extra / extra_dev: a further small block for the same launch, uploaded behind the table -- the sparse cohort's 'zzz' values; rows: what
-// cohort_rows gave a caller that has asked already)
-static int cohort_stage(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
-                        const int32_t *src_dtype, int element_bits, CohortCodec &cc, const void *extra = nullptr, size_t extra_bytes = 0,
-                        const char **extra_dev = nullptr, const std::vector<int> *rows = nullptr)
-{
-    int rc;
-    std::vector<int> own_rows;
-    if (!rows && (rc = cohort_rows(ctx, n, layers, n_layers, own_rows))) return rc;
-    const std::vector<int> &row_of = rows ? *rows : own_rows;
-    std::vector<CodecLayer> tab;
-    for (const int l : row_of) {
-        const flashe_tensor_layer &y = layers[l];
-        tab.push_back(codec_layer_front(y.start, nullptr, y.dtype == FLASHE_TENSOR_F64 || (y.flags & FLASHE_TENSOR_LOOP_F64), y.alpha, element_bits));
-    }
-    const size_t n_tab = tab.size();
-    std::vector<const void *> src(static_cast<size_t>(n_clients) * n_tab);
-    std::vector<TensorStage> st;
-    std::vector<size_t> st_at, st_slot;
-    uint64_t total = 0;
-    size_t bytes = 0;
-    for (int c = 0; c < n_clients; c++)
-        for (size_t r = 0; r < n_tab; r++) {
-            const int l = row_of[r];
-            const flashe_tensor_layer &y = layers[l];
-            const uint64_t size = (l + 1 < n_layers ? layers[l + 1].start : n) - y.start;
-            const size_t at = static_cast<size_t>(c) * n_layers + l;
-            const int32_t dt = src_dtype ? src_dtype[at] : y.dtype;
-            const int es = tensor_elem_bytes(dt);
-            const void *p = src_dev[at];
-            if (!es) return fail(ctx, FLASHE_EINVAL, "client %d layer %d: unknown dtype %d", c, l, static_cast<int>(dt));
-            if (!p || reinterpret_cast<uintptr_t>(p) % static_cast<uintptr_t>(es)) return fail(ctx, FLASHE_EINVAL, "client %d layer %d: null or misaligned source", c, l);
-            const bool f64 = tab[r].x_is_f64 != 0;
-            if (dt == FLASHE_TENSOR_F64 && !f64) return fail(ctx, FLASHE_EINVAL, "client %d layer %d: a float64 source under a float32 row", c, l);
-            const bool direct = !(y.flags & FLASHE_TENSOR_SHIFT) && (dt == FLASHE_TENSOR_F64 || (dt == FLASHE_TENSOR_F32 && !f64));
-            src[static_cast<size_t>(c) * n_tab + r] = p;
-            if (direct) continue;
-            bytes = (bytes + 15) & ~static_cast<size_t>(15);
-            st.push_back(TensorStage{total, p, nullptr, y.shift, dt, (y.flags & (FLASHE_TENSOR_SHIFT | FLASHE_TENSOR_SHIFT_WIDE)) | (f64 ? kTensorLoopF64 : 0)});
-            st_at.push_back(bytes);
-            st_slot.push_back(static_cast<size_t>(c) * n_tab + r);
-            total += size;
-            bytes += static_cast<size_t>(size) * (f64 ? 8 : 4);
-        }
-    if (!st.empty()) {
-        if ((rc = ensure(ctx, ctx->tensor_ws, bytes))) return rc;
-        for (size_t i = 0; i < st.size(); i++) {
-            st[i].dst = static_cast<char *>(ctx->tensor_ws.p) + st_at[i];
-            src[st_slot[i]] = st[i].dst;
-        }
-    }
-    // one block in ctx->codec_tab: the rows, then the source pointers
-    const size_t rows_bytes = (n_tab * sizeof(CodecLayer) + 15) & ~static_cast<size_t>(15);
-    const size_t extra_at = (rows_bytes + src.size() * sizeof(void *) + 15) & ~static_cast<size_t>(15);
-    std::vector<char> blob(extra ? extra_at + extra_bytes : rows_bytes + src.size() * sizeof(void *));
-    memcpy(blob.data(), tab.data(), n_tab * sizeof(CodecLayer));
-    memcpy(blob.data() + rows_bytes, src.data(), src.size() * sizeof(void *));
-    if (extra) memcpy(blob.data() + extra_at, extra, extra_bytes);
-    const char *blob_dev = nullptr;
-    if ((rc = upload_tab(ctx, ctx->codec_tab, blob, &blob_dev))) return rc;
-    if (extra_dev) *extra_dev = blob_dev + extra_at;
-    if (!st.empty()) {
-        const TensorStage *stab = nullptr;
-        if ((rc = upload_tab(ctx, ctx->tensor_tab, st, &stab))) return rc;
-        HIP_TRY(ctx, launch_stage_layers(ctx->env, stab, static_cast<int>(st.size()), total));
-    }
-    cc.layers = reinterpret_cast<const CodecLayer *>(blob_dev);
-    cc.src = reinterpret_cast<const void *const *>(blob_dev + rows_bytes);
-    cc.n_layers = static_cast<int>(n_tab);
-    return FLASHE_OK;
-}
-
-// the outputs of a double-mask cohort: every client's ciphertext non-null, aligned for its element type (uint64: a two-limb vector's 16
-// bytes, check_prf_args; uint32: 4 bytes) and apart from the sum and the mask, then the sum and the mask themselves
-extern "C++" template <class T> static int cohort_check_outs(flashe_ctx *ctx, int n_clients, uint32_t n_jobs, T *const *ct_dev, const T *sum_out_dev, const T *dmask_dev)
-{
-    constexpr bool wide = sizeof(T) == 8;
-    for (int c = 0; c < n_clients; c++) {
-        if (!ct_dev[c]) return fail(ctx, FLASHE_EINVAL, "client %d: null ciphertext", c);
-        if constexpr (wide) {
-            if (int rc = check_prf_args(ctx, 1, 1, n_jobs, ct_dev[c], nullptr, 0)) return rc;
-        } else if (reinterpret_cast<uintptr_t>(ct_dev[c]) & 3u)
-            return fail(ctx, FLASHE_EINVAL, "client %d: the ciphertext is not 4-byte aligned", c);
-        if (ct_dev[c] == sum_out_dev || ct_dev[c] == dmask_dev)
-            return fail(ctx, FLASHE_EINVAL, "client %d: the ciphertext aliases the sum%s", c, wide ? " or the mask" : "");
-    }
-    if constexpr (!wide) return (reinterpret_cast<uintptr_t>(sum_out_dev) & 3u) ? fail(ctx, FLASHE_EINVAL, "sum_out_dev must be 4-byte aligned") : FLASHE_OK;
-    if (int rc = check_sum_aligned(ctx, sum_out_dev)) return rc;
-    if (dmask_dev && (!aligned16(dmask_dev) || dmask_dev == sum_out_dev)) return fail(ctx, FLASHE_EINVAL, "dmask_dev must be 16-byte aligned and apart from the sum");
-    return FLASHE_OK;
-}
-
-// A shape the chained launch `what` does not take: asked of the launcher's own predicate before anything is staged, and once more of the
-// launcher's answer (hipErrorNotSupported = nothing launched), which is the final word.
-static int cohort_declined(flashe_ctx *ctx, const char *who, const char *what)
-{
-    return fail(ctx, FLASHE_ENOTSUP, "%s: not a shape of the chained %s launch", who, what);
-}
-static int cohort_launched(flashe_ctx *ctx, hipError_t e, const char *who, const char *what)
-{
-    if (e == hipErrorNotSupported) return cohort_declined(ctx, who, what);
-    HIP_TRY(ctx, e);
-    return FLASHE_OK;
-}
-
-int flashe_quantize_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs,
-                                       const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
-                                       int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev, uint64_t *dmask_dev)
-{
-    CHECK_CTX(ctx);
-    static const char who[] = "flashe_quantize_encrypt_cohort_dev";
-    std::vector<uint32_t> idx;
-    int rc = cohort_check(ctx, who, first_idx, n_clients, n, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, idx);
-    if (rc) return rc;
-    if ((rc = cohort_check_outs(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, dmask_dev))) return rc;
-    if (!cohort_chain_admits(ctx->env, n_clients, n, 0)) return cohort_declined(ctx, who, "cohort");
-    CohortCodec cc{};
-    if ((rc = cohort_stage(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, cc))) return rc;
-    return cohort_launched(ctx, launch_prf_cohort_sum(ctx->env, iter, n_clients, idx.data(), cc, nullptr, u_dev, ct_dev, sum_out_dev, n, n_jobs, dmask_dev),
-                           who, "cohort");
-}
-
-// the same cohort in the compact layout at int_bits <= 32 (prf_small_cohort_kernel): uint32 ciphertexts and their uint32 sum, no decrypt mask
-int flashe_quantize_encrypt_cohort_u32_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs,
-                                           const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
-                                           int element_bits, const double *u_dev, uint32_t *const *ct_dev, uint32_t *sum_out_dev)
-{
-    CHECK_CTX(ctx);
-    static const char who[] = "flashe_quantize_encrypt_cohort_u32_dev";
-    std::vector<uint32_t> idx;
-    int rc = cohort_check(ctx, who, first_idx, n_clients, n, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, idx);
-    if (rc) return rc;
-    if (n_jobs == 0) return fail(ctx, FLASHE_EINVAL, "n_jobs must be >= 1");
-    if ((rc = cohort_check_outs<uint32_t>(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, nullptr))) return rc;
-    if (flashe_ctx_compact_layout(ctx) != 1 || !small_cohort_admits(ctx->env, n_clients, n, n_jobs, true)) return cohort_declined(ctx, who, "compact cohort");
-    CohortCodec cc{};
-    if ((rc = cohort_stage(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, cc))) return rc;
-    return cohort_launched(ctx, launch_small_cohort_sum(ctx->env, iter, n_clients, idx.data(), cc, u_dev, ct_dev, sum_out_dev, n, n_jobs), who, "compact cohort");
-}
-
-// the cohort of a BATCHED job (prf_chain_cohort_batch_kernel): the same table, sources and stage pass over the n_values values; the chain
-// runs over the n_elems batched elements
-int flashe_quantize_batch_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n_values, uint64_t n_elems,
-                                             uint32_t n_jobs, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
-                                             const int32_t *src_dtype, int element_bits, int field_bits, const double *u_dev, uint64_t *const *ct_dev,
-                                             uint64_t *sum_out_dev, uint64_t *dmask_dev)
-{
-    CHECK_CTX(ctx);
-    static const char who[] = "flashe_quantize_batch_encrypt_cohort_dev";
-    std::vector<uint32_t> idx;
-    int rc = cohort_check(ctx, who, first_idx, n_clients, n_values, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, idx);
-    if (rc) return rc;
-    if (field_bits < element_bits || field_bits > ctx->int_bits)
-        return fail(ctx, FLASHE_EINVAL, "need 1 <= element_bits <= field_bits <= int_bits (element_bits <= 62)");
-    // the batched rows of the non-empty layers (cohort_stage's rows, in its order): first element, value count
-    const uint64_t bs = static_cast<uint64_t>(ctx->int_bits / field_bits);
-    std::vector<uint64_t> rows;
-    uint64_t e = 0;
-    for (int l = 0; l < n_layers; l++) {
-        const uint64_t size = (l + 1 < n_layers ? layers[l + 1].start : n_values) - layers[l].start;
-        if (size == 0) continue;
-        rows.push_back(e);
-        rows.push_back(size);
-        e += (size + bs - 1) / bs;                         // every layer is padded to whole elements on its own (jzf_quantize.py:166-171)
-    }
-    if (e != n_elems) return fail(ctx, FLASHE_EINVAL, "the layers batch into %llu elements, n_elems says %llu", static_cast<unsigned long long>(e),
-                                  static_cast<unsigned long long>(n_elems));
-    if ((rc = cohort_check_outs(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, dmask_dev))) return rc;
-    if (!cohort_chain_admits(ctx->env, n_clients, n_elems, static_cast<int>(bs))) return cohort_declined(ctx, who, "batched cohort");
-    CohortCodec cc{};
-    const char *rows_dev = nullptr;
-    if ((rc = cohort_stage(ctx, n_clients, n_values, layers, n_layers, src_dev, src_dtype, element_bits, cc, rows.data(), rows.size() * sizeof(uint64_t),
-                           &rows_dev)))
-        return rc;
-    CohortBatch cb{};
-    cb.rows = reinterpret_cast<const uint64_t *>(rows_dev);
-    cb.n_values = n_values;
-    cb.field_bits = field_bits;
-    return cohort_launched(ctx, launch_prf_cohort_sum(ctx->env, iter, n_clients, idx.data(), cc, &cb, u_dev, ct_dev, sum_out_dev, n_elems, n_jobs, dmask_dev),
-                           who, "batched cohort");
-}
-
-int flashe_combine_unquantize_model_dev(flashe_ctx *ctx, uint64_t n, const uint64_t *in_dev, const uint64_t *add_dev, const uint64_t *minus_dev,
-                                        const flashe_codec_layer *layers, int n_layers, int element_bits, int num_clients, double *out_dev)
-{
-    CHECK_CTX(ctx);
-    if (n && (!in_dev || !out_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if (num_clients < 1) return fail(ctx, FLASHE_EINVAL, "num_clients must be >= 1");
-    int rc = check_codec_bits(ctx, element_bits);
-    if (rc) return rc;
-    for (const uint64_t *p : {in_dev, add_dev, minus_dev})
-        if (p && ((ctx->limbs == 2 && !aligned16(p)) || (reinterpret_cast<uintptr_t>(p) & 7u))) return fail(ctx, FLASHE_EINVAL, "misaligned vector");
-    if (reinterpret_cast<uintptr_t>(out_dev) & 7u) return fail(ctx, FLASHE_EINVAL, "out_dev must be 8-byte aligned");
-    const CodecLayer *tab = nullptr;
-    int n_tab = 0;
-    if ((rc = stage_codec_layers(ctx, n, layers, n_layers, false, element_bits, num_clients, 0, n, &tab, &n_tab)) || n == 0) return rc;
-    Codec cq{};
-    cq.fout = out_dev; cq.layers = tab; cq.n_layers = n_tab; cq.k0 = 0;
-    HIP_TRY(ctx, launch_combine_unquantize_model(ctx->env, n, in_dev, add_dev, minus_dev, cq, out_dev));
-    return FLASHE_OK;
-}
-
-// the batched sibling: unbatch + unquantise over (in + add - minus) mod 2^b, the masks held by the caller
-int flashe_combine_unbatch_unquantize_model_dev(flashe_ctx *ctx, const flashe_batch_layer *layers, int n_layers, int element_bits, int field_bits,
-                                                int num_clients, const uint64_t *in_dev, const uint64_t *add_dev, const uint64_t *minus_dev,
-                                                uint64_t n_elems, double *out_dev)
-{
-    CHECK_CTX(ctx);
-    if (num_clients < 1) return fail(ctx, FLASHE_EINVAL, "num_clients must be >= 1");
-    const BatchLayer *tab = nullptr;
-    int n_tab = 0;
-    uint64_t e = 0, v = 0;
-    int rc = stage_batch_layers(ctx, layers, n_layers, false, element_bits, field_bits, num_clients, &e, &v, &tab, &n_tab);
-    if (rc) return rc;
-    if (e != n_elems) return fail(ctx, FLASHE_EINVAL, "the layers batch into %llu elements, n_elems says %llu", static_cast<unsigned long long>(e),
-                                  static_cast<unsigned long long>(n_elems));
-    if (v && (!in_dev || !out_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    for (const uint64_t *p : {in_dev, add_dev, minus_dev})
-        if (p && ((ctx->limbs == 2 && !aligned16(p)) || (reinterpret_cast<uintptr_t>(p) & 7u))) return fail(ctx, FLASHE_EINVAL, "misaligned vector");
-    if (reinterpret_cast<uintptr_t>(out_dev) & 7u) return fail(ctx, FLASHE_EINVAL, "out_dev must be 8-byte aligned");
-    if (v) HIP_TRY(ctx, launch_combine_unbatch_unquantize_model(ctx->env, tab, n_tab, field_bits, in_dev, add_dev, minus_dev, v, out_dev));
-    return FLASHE_OK;
-}
-
-int flashe_quantize_batch_tensors_dev(flashe_ctx *ctx, const flashe_tensor_layer *layers, int n_layers, uint64_t n_values, int element_bits,
-                                      int field_bits, const double *u_dev, uint64_t n_elems, uint64_t *out_dev)
-{
-    CHECK_CTX(ctx);
-    int rc = check_tensor_layers(ctx, n_values, layers, n_layers);
-    std::vector<flashe_batch_layer> bl;
-    if (rc || (rc = tensor_batch_layers(ctx, layers, n_layers, n_values, element_bits, field_bits, u_dev, n_elems, out_dev, bl))) return rc;
-    return flashe_quantize_batch_model_dev(ctx, bl.data(), n_layers, element_bits, field_bits, u_dev, n_elems, out_dev);
-}
-
-int flashe_store_layers_dev(flashe_ctx *ctx, const double *in_dev, uint64_t n, const flashe_tensor_layer *layers, int n_layers, uint64_t block,
-                            double *stats_dev)
-{
-    CHECK_CTX(ctx);
-    int rc = check_tensor_layers(ctx, n, layers, n_layers);
-    if (rc) return rc;
-    if (n && (!in_dev || (reinterpret_cast<uintptr_t>(in_dev) & 7u))) return fail(ctx, FLASHE_EINVAL, "null or misaligned in_dev");
-    if (stats_dev && (block < 1 || block > 16384)) return fail(ctx, FLASHE_EINVAL, "block must be in [1, 16384], got %llu", static_cast<unsigned long long>(block));
-    if (reinterpret_cast<uintptr_t>(stats_dev) & 7u) return fail(ctx, FLASHE_EINVAL, "misaligned stats_dev");
-    std::vector<TensorStore> st;
-    std::vector<StatLayer> sl;
-    uint64_t groups = 0, blocks = 0;
-    for (int l = 0; l < n_layers; l++) {
-        const flashe_tensor_layer &y = layers[l];
-        const uint64_t size = (l + 1 < n_layers ? layers[l + 1].start : n) - y.start;
-        if (!size) continue;
-        st.push_back(TensorStore{y.start, groups, size, y.ptr, y.shift, y.dtype, y.flags});
-        groups += (size + 7) / 8;
-        if (stats_dev) {
-            sl.push_back(StatLayer{y.start, blocks, size, y.shift, y.flags, l});
-            blocks += (size + block - 1) / block;
-        }
-    }
-    if (st.empty()) return FLASHE_OK;
-    if (!sl.empty()) {
-        // table, then the per-buffer sums and the layer means behind it
-        const size_t tab_bytes = (sl.size() * sizeof(StatLayer) + 15) & ~static_cast<size_t>(15);
-        if ((rc = ensure(ctx, ctx->stat_ws, tab_bytes + (blocks + sl.size()) * sizeof(double)))) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->stat_ws.p, sl.data(), sl.size() * sizeof(StatLayer), hipMemcpyHostToDevice, ctx->env.stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->env.stream));
-        double *bsum = reinterpret_cast<double *>(static_cast<char *>(ctx->stat_ws.p) + tab_bytes);
-        // (the statistics read in_dev before the store pass, which may write in place)
-        HIP_TRY(ctx, launch_layer_stats(ctx->env, static_cast<const StatLayer *>(ctx->stat_ws.p), static_cast<int>(sl.size()), blocks, in_dev, block, bsum,
-                                        bsum + blocks, stats_dev));
-    }
-    const TensorStore *tab = nullptr;
-    if ((rc = upload_tab(ctx, ctx->tensor_tab, st, &tab))) return rc;
-    HIP_TRY(ctx, launch_store_layers(ctx->env, tab, static_cast<int>(st.size()), groups, in_dev));
-    return FLASHE_OK;
-}
-
 // Range twins: operate on global elements [first, first + count) of an n-element vector.
-static int check_range(flashe_ctx *ctx, uint64_t n, uint64_t first, uint64_t count)
-{
-    if (first > n || count > n - first) return fail(ctx, FLASHE_EINVAL, "range [%llu, +%llu) exceeds n = %llu",
-                                                    static_cast<unsigned long long>(first), static_cast<unsigned long long>(count),
-                                                    static_cast<unsigned long long>(n));
-    return FLASHE_OK;
-}
-
 int flashe_mask_range_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_idx, uint64_t n, uint32_t n_jobs,
                           uint64_t first, uint64_t count, uint64_t *out_dev)
 {
@@ -2106,172 +1382,6 @@ int flashe_decrypt_prepared_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *
         if (n_add || n_minus) HIP_TRY(ctx, prf_lists(ctx, iter, add_idx, n_add, minus_idx, n_minus, n, n_jobs, 0, n, out_dev, ctx->limbs, out_dev));
     }
     pr.valid = false;                                                    // consumed (:573-580)
-    return FLASHE_OK;
-}
-
-// ---- the fused client step with the ctx's precomputed masks (jzf_aggregator.py:721-741, :881-899 with next_iter_*_prepared populated,
-// jzf_flashe.py:456-488, :537-582): the model-wide codec and the combine of the two calls above in one pass each, no AES ----
-static int check_prepared(flashe_ctx *ctx, const flashe_ctx::Prepared &pr, uint64_t n, const char *what)
-{
-    if (!pr.valid) return fail(ctx, FLASHE_EINVAL, "no prepared %s masks: call flashe_prepare_%s first (they are consumed by one %s)", what, what, what);
-    // (a length mismatch leaves the cache in place, as NumPy's broadcast error does in the reference, jzf_flashe.py:480)
-    if (n != pr.n) return fail(ctx, FLASHE_EINVAL, "the prepared masks cover %llu elements, the vector has %llu", static_cast<unsigned long long>(pr.n),
-                               static_cast<unsigned long long>(n));
-    return FLASHE_OK;
-}
-
-// element `first` of a cached mask (null: a single-mask cache has no minus stream)
-static const uint64_t *prepared_at(const flashe_ctx *ctx, const flashe_ctx::Buf &b, bool held, uint64_t first)
-{
-    return held ? static_cast<const uint64_t *>(b.p) + first * static_cast<uint64_t>(ctx->limbs) : nullptr;
-}
-
-int flashe_quantize_encrypt_prepared_model_dev(flashe_ctx *ctx, uint64_t n, uint64_t first, uint64_t count, const flashe_codec_layer *layers,
-                                               int n_layers, int element_bits, const double *u_dev, uint64_t *ct_dev)
-{
-    CHECK_CTX(ctx);
-    flashe_ctx::Prepared &pr = ctx->prep_enc;
-    int rc = check_prepared(ctx, pr, n, "encrypt");
-    if (rc) return rc;
-    if (count && (!u_dev || !ct_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if (element_bits < 1 || element_bits > 62 || element_bits > ctx->int_bits)
-        return fail(ctx, FLASHE_EINVAL, "element_bits must be in [1, min(62, int_bits)], got %d", element_bits);
-    if ((rc = check_prf_args(ctx, 0, 0, 1, ct_dev, nullptr, 0)) || (rc = check_range(ctx, n, first, count))) return rc;
-    if (reinterpret_cast<uintptr_t>(u_dev) & 7u) return fail(ctx, FLASHE_EINVAL, "u_dev must be 8-byte aligned");
-    const CodecLayer *tab = nullptr;
-    int n_tab = 0;
-    if ((rc = stage_codec_layers(ctx, n, layers, n_layers, true, element_bits, 1, first, count, &tab, &n_tab))) return rc;
-    if (count) {
-        Codec cq{};
-        cq.x = tab; cq.u = u_dev; cq.layers = tab; cq.n_layers = n_tab; cq.k0 = first;
-        HIP_TRY(ctx, launch_quantize_combine_model(ctx->env, count, cq, prepared_at(ctx, pr.add, true, first), prepared_at(ctx, pr.minus, pr.has_minus, first),
-                                                   ct_dev));
-    }
-    if (first + count == n) pr.valid = false;                           // the call that completes the vector consumes the cache (:483-486)
-    return FLASHE_OK;
-}
-
-int flashe_quantize_encrypt_prepared_tensors_dev(flashe_ctx *ctx, uint64_t n, uint64_t first, uint64_t count, const flashe_tensor_layer *layers,
-                                                 int n_layers, int element_bits, const double *u_dev, uint64_t *ct_dev)
-{
-    CHECK_CTX(ctx);
-    // the checks of the codec-layer form that do not need the table, before the stage pass launches
-    int rc = check_prepared(ctx, ctx->prep_enc, n, "encrypt");
-    if (rc) return rc;
-    if (count && (!u_dev || !ct_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if (element_bits < 1 || element_bits > 62 || element_bits > ctx->int_bits)
-        return fail(ctx, FLASHE_EINVAL, "element_bits must be in [1, min(62, int_bits)], got %d", element_bits);
-    if ((rc = check_prf_args(ctx, 0, 0, 1, ct_dev, nullptr, 0)) || (rc = check_range(ctx, n, first, count)) || (rc = check_tensor_layers(ctx, n, layers, n_layers)))
-        return rc;
-    if (reinterpret_cast<uintptr_t>(u_dev) & 7u) return fail(ctx, FLASHE_EINVAL, "u_dev must be 8-byte aligned");
-    std::vector<flashe_codec_layer> cl;
-    if ((rc = tensor_codec_layers(ctx, n, layers, n_layers, first, count, cl))) return rc;
-    return flashe_quantize_encrypt_prepared_model_dev(ctx, n, first, count, cl.data(), n_layers, element_bits, u_dev, ct_dev);
-}
-
-int flashe_quantize_batch_encrypt_prepared_model_dev(flashe_ctx *ctx, const flashe_batch_layer *layers, int n_layers, int element_bits, int field_bits,
-                                                     const double *u_dev, uint64_t n_elems, uint64_t *ct_dev)
-{
-    CHECK_CTX(ctx);
-    flashe_ctx::Prepared &pr = ctx->prep_enc;
-    int rc = check_prepared(ctx, pr, n_elems, "encrypt");
-    if (rc) return rc;
-    const BatchLayer *tab = nullptr;
-    int n_tab = 0;
-    uint64_t e = 0, v = 0;
-    if ((rc = stage_batch_layers(ctx, layers, n_layers, true, element_bits, field_bits, 1, &e, &v, &tab, &n_tab))) return rc;
-    if (e != n_elems) return fail(ctx, FLASHE_EINVAL, "the layers batch into %llu elements, n_elems says %llu", static_cast<unsigned long long>(e),
-                                  static_cast<unsigned long long>(n_elems));
-    if (n_elems && (!u_dev || !ct_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if ((ctx->limbs == 2 && !aligned16(ct_dev)) || (reinterpret_cast<uintptr_t>(ct_dev) & 7u) || (reinterpret_cast<uintptr_t>(u_dev) & 7u))
-        return fail(ctx, FLASHE_EINVAL, "misaligned vector");
-    if (n_elems)
-        HIP_TRY(ctx, launch_quantize_batch_combine_model(ctx->env, tab, n_tab, field_bits, u_dev, n_elems, prepared_at(ctx, pr.add, true, 0),
-                                                         prepared_at(ctx, pr.minus, pr.has_minus, 0), ct_dev));
-    pr.valid = false;
-    return FLASHE_OK;
-}
-
-int flashe_quantize_batch_encrypt_prepared_tensors_dev(flashe_ctx *ctx, const flashe_tensor_layer *layers, int n_layers, uint64_t n_values,
-                                                       int element_bits, int field_bits, const double *u_dev, uint64_t n_elems, uint64_t *ct_dev)
-{
-    CHECK_CTX(ctx);
-    int rc = check_prepared(ctx, ctx->prep_enc, n_elems, "encrypt");
-    std::vector<flashe_batch_layer> bl;
-    if (rc || (rc = check_tensor_layers(ctx, n_values, layers, n_layers)) ||
-        (rc = tensor_batch_layers(ctx, layers, n_layers, n_values, element_bits, field_bits, u_dev, n_elems, ct_dev, bl)))
-        return rc;
-    return flashe_quantize_batch_encrypt_prepared_model_dev(ctx, bl.data(), n_layers, element_bits, field_bits, u_dev, n_elems, ct_dev);
-}
-
-// The way back.  The prefixes the precompute does not cover (dropouts) go first, into ctx scratch: the sum mod 2^b is the same in either
-// order, and the codec pass then reads every cached mask once.  *src = what that pass reads (in_dev when nobody dropped out).
-static int prepared_extras(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx, int n_minus, uint64_t n,
-                           uint32_t n_jobs, const uint64_t *in_dev, const uint64_t **src)
-{
-    *src = in_dev;
-    if (n == 0 || (n_add == 0 && n_minus == 0)) return FLASHE_OK;
-    if (int rc = ensure(ctx, ctx->stream_tmp, vec_bytes(ctx, n))) return rc;
-    uint64_t *tmp = static_cast<uint64_t *>(ctx->stream_tmp.p);
-    HIP_TRY(ctx, prf_lists(ctx, iter, add_idx, n_add, minus_idx, n_minus, n, n_jobs, 0, n, in_dev, ctx->limbs, tmp));
-    *src = tmp;
-    return FLASHE_OK;
-}
-
-int flashe_decrypt_prepared_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx,
-                                                 int n_minus, uint64_t n, uint32_t n_jobs, const uint64_t *in_dev, const flashe_codec_layer *layers,
-                                                 int n_layers, int element_bits, int num_clients, double *out_dev)
-{
-    CHECK_CTX(ctx);
-    flashe_ctx::Prepared &pr = ctx->prep_dec;
-    int rc = check_prepared(ctx, pr, n, "decrypt");
-    if (rc) return rc;
-    if (n && (!in_dev || !out_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if (num_clients < 1) return fail(ctx, FLASHE_EINVAL, "num_clients must be >= 1");
-    if ((rc = check_codec_bits(ctx, element_bits)) || (rc = check_prf_args(ctx, n_add, n_minus, n_jobs, in_dev, in_dev, ctx->limbs))) return rc;
-    if (reinterpret_cast<uintptr_t>(out_dev) & 7u) return fail(ctx, FLASHE_EINVAL, "out_dev must be 8-byte aligned");
-    if ((n_add && !add_idx) || (n_minus && !minus_idx)) return fail(ctx, FLASHE_EINVAL, "null prefix list");
-    const CodecLayer *tab = nullptr;
-    int n_tab = 0;
-    if ((rc = stage_codec_layers(ctx, n, layers, n_layers, false, element_bits, num_clients, 0, n, &tab, &n_tab))) return rc;
-    if (n) {
-        const uint64_t *src = nullptr;
-        if ((rc = prepared_extras(ctx, iter, add_idx, n_add, minus_idx, n_minus, n, n_jobs, in_dev, &src))) return rc;
-        Codec cq{};
-        cq.fout = out_dev; cq.layers = tab; cq.n_layers = n_tab; cq.k0 = 0;
-        HIP_TRY(ctx, launch_combine_unquantize_model(ctx->env, n, src, prepared_at(ctx, pr.add, true, 0), prepared_at(ctx, pr.minus, pr.has_minus, 0), cq,
-                                                     out_dev));
-    }
-    pr.valid = false;                                                    // consumed (:573-580)
-    return FLASHE_OK;
-}
-
-int flashe_decrypt_prepared_unbatch_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx,
-                                                         int n_minus, uint32_t n_jobs, const flashe_batch_layer *layers, int n_layers, int element_bits,
-                                                         int field_bits, int num_clients, const uint64_t *in_dev, uint64_t n_elems, double *out_dev)
-{
-    CHECK_CTX(ctx);
-    flashe_ctx::Prepared &pr = ctx->prep_dec;
-    int rc = check_prepared(ctx, pr, n_elems, "decrypt");
-    if (rc) return rc;
-    if (num_clients < 1) return fail(ctx, FLASHE_EINVAL, "num_clients must be >= 1");
-    if ((rc = check_prf_args(ctx, n_add, n_minus, n_jobs, in_dev, in_dev, ctx->limbs))) return rc;
-    if ((n_add && !add_idx) || (n_minus && !minus_idx)) return fail(ctx, FLASHE_EINVAL, "null prefix list");
-    const BatchLayer *tab = nullptr;
-    int n_tab = 0;
-    uint64_t e = 0, v = 0;
-    if ((rc = stage_batch_layers(ctx, layers, n_layers, false, element_bits, field_bits, num_clients, &e, &v, &tab, &n_tab))) return rc;
-    if (e != n_elems) return fail(ctx, FLASHE_EINVAL, "the layers batch into %llu elements, n_elems says %llu", static_cast<unsigned long long>(e),
-                                  static_cast<unsigned long long>(n_elems));
-    if (v && (!in_dev || !out_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if (reinterpret_cast<uintptr_t>(out_dev) & 7u) return fail(ctx, FLASHE_EINVAL, "out_dev must be 8-byte aligned");
-    if (v) {
-        const uint64_t *src = nullptr;
-        if ((rc = prepared_extras(ctx, iter, add_idx, n_add, minus_idx, n_minus, n_elems, n_jobs, in_dev, &src))) return rc;
-        HIP_TRY(ctx, launch_combine_unbatch_unquantize_model(ctx->env, tab, n_tab, field_bits, src, prepared_at(ctx, pr.add, true, 0),
-                                                             prepared_at(ctx, pr.minus, pr.has_minus, 0), v, out_dev));
-    }
-    pr.valid = false;
     return FLASHE_OK;
 }
 
@@ -2645,22 +1755,6 @@ static int check_bounds(flashe_ctx *ctx, const flashe_span_bounds *b, uint64_t t
 }
 
 static int sparse_aggregate_impl(flashe_ctx *ctx, uint64_t total, int C, const uint32_t *const *loc_dev, const uint64_t *k,
-                                 const uint64_t *const *vals_dev, const uint64_t *zeros, int sorted, const flashe_span_bounds *bounds, uint64_t *out_dev);
-
-int flashe_sparse_aggregate_dev(flashe_ctx *ctx, uint64_t total, int C, const uint32_t *const *loc_dev, const uint64_t *k,
-                                const uint64_t *const *vals_dev, const uint64_t *zeros, int sorted, uint64_t *out_dev)
-{
-    return sparse_aggregate_impl(ctx, total, C, loc_dev, k, vals_dev, zeros, sorted, nullptr, out_dev);
-}
-
-int flashe_sparse_aggregate_bounds_dev(flashe_ctx *ctx, uint64_t total, int C, const uint32_t *const *loc_dev, const uint64_t *k,
-                                       const uint64_t *const *vals_dev, const uint64_t *zeros, const flashe_span_bounds *bounds, uint64_t *out_dev)
-{
-    if (!bounds) return ctx ? fail(ctx, FLASHE_EINVAL, "null bounds handle") : FLASHE_EINVAL;
-    return sparse_aggregate_impl(ctx, total, C, loc_dev, k, vals_dev, zeros, 1, bounds, out_dev);
-}
-
-static int sparse_aggregate_impl(flashe_ctx *ctx, uint64_t total, int C, const uint32_t *const *loc_dev, const uint64_t *k,
                                  const uint64_t *const *vals_dev, const uint64_t *zeros, int sorted, const flashe_span_bounds *bounds, uint64_t *out_dev)
 {
     CHECK_CTX(ctx);
@@ -2698,6 +1792,19 @@ static int sparse_aggregate_impl(flashe_ctx *ctx, uint64_t total, int C, const u
         HIP_TRY(ctx, launch_scatter(ctx->env, total, k[c], loc_dev[c], vals_dev[c], out_dev, true, zeros[static_cast<size_t>(L) * c],
                                     L == 2 ? zeros[2 * c + 1] : 0));
     return FLASHE_OK;
+}
+
+int flashe_sparse_aggregate_dev(flashe_ctx *ctx, uint64_t total, int C, const uint32_t *const *loc_dev, const uint64_t *k,
+                                const uint64_t *const *vals_dev, const uint64_t *zeros, int sorted, uint64_t *out_dev)
+{
+    return sparse_aggregate_impl(ctx, total, C, loc_dev, k, vals_dev, zeros, sorted, nullptr, out_dev);
+}
+
+int flashe_sparse_aggregate_bounds_dev(flashe_ctx *ctx, uint64_t total, int C, const uint32_t *const *loc_dev, const uint64_t *k,
+                                       const uint64_t *const *vals_dev, const uint64_t *zeros, const flashe_span_bounds *bounds, uint64_t *out_dev)
+{
+    if (!bounds) return ctx ? fail(ctx, FLASHE_EINVAL, "null bounds handle") : FLASHE_EINVAL;
+    return sparse_aggregate_impl(ctx, total, C, loc_dev, k, vals_dev, zeros, 1, bounds, out_dev);
 }
 
 // The sparse twin of flashe_encrypt_batch_sum_dev: the C clients this device plays encrypt their compact uploads (single mask over the
@@ -3045,344 +2152,6 @@ int flashe_sparse_dense_mask_dev(flashe_ctx *ctx, uint32_t iter, int n_lists, co
         HIP_TRY(ctx, launch_sel_accumulate(ctx->env, total, sel_dev[i], tmp, out_dev));
     }
     return FLASHE_OK;
-}
-
-// ---- quantise / batch codec ----
-static int check_codec_bits(flashe_ctx *ctx, int element_bits)
-{
-    if (element_bits < 1 || element_bits > 62) return fail(ctx, FLASHE_EINVAL, "element_bits must be in [1, 62], got %d", element_bits);
-    return FLASHE_OK;
-}
-
-int flashe_quantize_dev(flashe_ctx *ctx, uint64_t n, const void *x_dev, int x_is_f64, double alpha, int element_bits,
-                        const double *u_dev, uint64_t *q_dev)
-{
-    CHECK_CTX(ctx);
-    if (n && (!x_dev || !u_dev || !q_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if (!(alpha > 0)) return fail(ctx, FLASHE_EINVAL, "alpha must be positive");
-    int rc = check_codec_bits(ctx, element_bits);
-    if (rc) return rc;
-    HIP_TRY(ctx, launch_quantize(ctx->env, n, x_dev, x_is_f64 != 0, alpha, element_bits, u_dev, q_dev));
-    return FLASHE_OK;
-}
-
-int flashe_unquantize_dev(flashe_ctx *ctx, uint64_t n, const uint64_t *v_dev, int v_limbs, double alpha, int element_bits,
-                          int num_clients, double *out_dev)
-{
-    CHECK_CTX(ctx);
-    if (n && (!v_dev || !out_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if (v_limbs != 1 && v_limbs != 2) return fail(ctx, FLASHE_EINVAL, "v_limbs must be 1 or 2");
-    if (v_limbs == 2 && !aligned16(v_dev)) return fail(ctx, FLASHE_EINVAL, "device vectors must be 16-byte aligned");
-    if (num_clients < 1) return fail(ctx, FLASHE_EINVAL, "num_clients must be >= 1");
-    int rc = check_codec_bits(ctx, element_bits);
-    if (rc) return rc;
-    HIP_TRY(ctx, launch_unquantize(ctx->env, n, v_dev, v_limbs, alpha, element_bits, num_clients, out_dev));
-    return FLASHE_OK;
-}
-
-int flashe_batch_dev(flashe_ctx *ctx, uint64_t n, const uint64_t *vals_dev, int field_bits, uint64_t *out_dev)
-{
-    CHECK_CTX(ctx);
-    if (n && (!vals_dev || !out_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    int rc = check_field_bits(ctx, field_bits);
-    if (rc) return rc;
-    if (int rc = check_wide_aligned(ctx, {out_dev})) return rc;
-    HIP_TRY(ctx, launch_batch(ctx->env, n, vals_dev, field_bits, out_dev));
-    return FLASHE_OK;
-}
-
-int flashe_unbatch_dev(flashe_ctx *ctx, uint64_t n_batches, const uint64_t *in_dev, int field_bits, uint64_t *out_dev)
-{
-    CHECK_CTX(ctx);
-    if (n_batches && (!in_dev || !out_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    int rc = check_field_bits(ctx, field_bits);
-    if (rc) return rc;
-    if (int rc = check_wide_aligned(ctx, {in_dev})) return rc;
-    HIP_TRY(ctx, launch_unbatch(ctx->env, n_batches, in_dev, field_bits, out_dev));
-    return FLASHE_OK;
-}
-
-// ---- sparsifier ----
-int flashe_sparsify_dev(flashe_ctx *ctx, uint64_t n, uint64_t k, const void *x_dev, int x_is_f64, void *residual_dev, uint32_t *loc_dev,
-                        void *vals_dev)
-{
-    CHECK_CTX(ctx);
-    if (n >= (1ull << 32)) return fail(ctx, FLASHE_EINVAL, "sparsify: n must be < 2^32");
-    if (k > n) return fail(ctx, FLASHE_EINVAL, "sparsify: k (%llu) > n (%llu)", static_cast<unsigned long long>(k),
-                           static_cast<unsigned long long>(n));
-    // (a layer that keeps nothing only updates its residual: x is read whenever there is something to write, loc / vals only when k > 0)
-    if (n && (k || residual_dev) && !x_dev) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if (n && k && (!loc_dev || !vals_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    int rc = ensure(ctx, ctx->sp_ws, sparsify_workspace_bytes(n));
-    if (rc) return rc;
-    HIP_TRY(ctx, launch_sparsify(ctx->env, n, k, x_dev, x_is_f64 != 0, residual_dev, loc_dev, vals_dev, ctx->sp_ws.p));
-    return FLASHE_OK;
-}
-
-// Every layer of a model at once: layer l = elements [off_l, off_l + n[l]) of the flat vectors (layers back to back), its k[l] entries go
-// to [koff_l, koff_l + k[l]) of the flat outputs, locations relative to the layer.  n and k are HOST arrays.
-int flashe_sparsify_batch_dev(flashe_ctx *ctx, int n_layers, const uint64_t *n, const uint64_t *k, const void *x_dev, int x_is_f64, void *residual_dev,
-                              uint32_t *loc_dev, void *vals_dev)
-{
-    CHECK_CTX(ctx);
-    if (n_layers < 0 || (n_layers && (!n || !k))) return fail(ctx, FLASHE_EINVAL, "sparsify_batch: bad arguments");
-    if (n_layers == 0) return FLASHE_OK;
-    if (ctx->capturing) return fail(ctx, FLASHE_EINVAL, "sparsify_batch: not inside a graph capture (the layer table is uploaded synchronously)");
-    uint64_t total = 0, total_k = 0;
-    for (int l = 0; l < n_layers; l++) {
-        if (n[l] >= (1ull << 32)) return fail(ctx, FLASHE_EINVAL, "sparsify_batch: layer %d: n must be < 2^32", l);
-        if (k[l] > n[l]) return fail(ctx, FLASHE_EINVAL, "sparsify_batch: layer %d: k (%llu) > n (%llu)", l, static_cast<unsigned long long>(k[l]),
-                                     static_cast<unsigned long long>(n[l]));
-        total += n[l]; total_k += k[l];
-    }
-    if (total == 0 || (total_k == 0 && !residual_dev)) return FLASHE_OK;       // (total_k == 0 with a residual: every layer only updates it)
-    if (!x_dev || (total_k && (!loc_dev || !vals_dev))) return fail(ctx, FLASHE_EINVAL, "null vector");
-    std::vector<unsigned char> desc(sparsify_batch_desc_bytes(n_layers));
-    const uint64_t blocks = sparsify_batch_layout(n_layers, n, k, desc.data());
-    if (blocks >= (1ull << 32)) return fail(ctx, FLASHE_EINVAL, "sparsify_batch: too many elements");
-    int rc = ensure(ctx, ctx->sp_ws, sparsify_batch_workspace_bytes(n_layers, blocks));
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->sp_ws.p, desc.data(), desc.size(), hipMemcpyHostToDevice, ctx->env.stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->env.stream));                  // the table is on the device before `desc` goes away
-    HIP_TRY(ctx, launch_sparsify_batch(ctx->env, n_layers, blocks, x_dev, x_is_f64 != 0, residual_dev, loc_dev, vals_dev, ctx->sp_ws.p));
-    return FLASHE_OK;
-}
-
-// Every layer of a model where its owner keeps it (include/flashe.h): the tables are built on the host in the caller's layer order, sorted
-// by compute class for the launches, uploaded once.
-int flashe_sparsify_tensors_dev(flashe_ctx *ctx, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const uint64_t *k, void *residual_dev,
-                                uint32_t *loc_dev, void *vals_dev, uint64_t *packed_dev, int bits)
-{
-    CHECK_CTX(ctx);
-    if (n >= (1ull << 32)) return fail(ctx, FLASHE_EINVAL, "sparsify_tensors: n must be < 2^32");
-    if (!k) return fail(ctx, FLASHE_EINVAL, "sparsify_tensors: null k");
-    int rc = check_tensor_layers(ctx, n, layers, n_layers);
-    if (rc) return rc;
-    if (packed_dev && (bits < 1 || bits > 32 || (bits < 32 && n > (1ull << bits))))
-        return fail(ctx, FLASHE_EINVAL, "sparsify_tensors: bits (%d) must be in [1, 32] and cover n (%llu)", bits, static_cast<unsigned long long>(n));
-    std::vector<const void *> x(n_layers);
-    std::vector<int> dt(n_layers);
-    std::vector<uint64_t> nl(n_layers), koff(n_layers), start(n_layers), roff(n_layers), voff(n_layers);
-    uint64_t total_k = 0, r = 0, v = 0;
-    for (int l = 0; l < n_layers; l++) {
-        const flashe_tensor_layer &y = layers[l];
-        nl[l] = (l + 1 < n_layers ? layers[l + 1].start : n) - y.start;
-        if (k[l] > nl[l]) return fail(ctx, FLASHE_EINVAL, "sparsify_tensors: layer %d: k (%llu) > n (%llu)", l, static_cast<unsigned long long>(k[l]),
-                                      static_cast<unsigned long long>(nl[l]));
-        const uint64_t cs = y.dtype == FLASHE_TENSOR_F64 ? 8 : 4;
-        r = (r + cs - 1) / cs * cs;
-        v = (v + cs - 1) / cs * cs;
-        x[l] = y.ptr; dt[l] = y.dtype; start[l] = y.start; koff[l] = total_k; roff[l] = r; voff[l] = v;
-        r += nl[l] * cs;
-        v += k[l] * cs;
-        total_k += k[l];
-    }
-    if (n == 0 || (total_k == 0 && !residual_dev)) return FLASHE_OK;          // (total_k == 0 with a residual: every layer only updates it)
-    if (total_k && (!loc_dev || !vals_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    std::vector<unsigned char> desc(sparsify_tensors_desc_bytes(n_layers));
-    int l32 = 0;
-    uint64_t nb32 = 0;
-    const uint64_t blocks = sparsify_tensors_layout(n_layers, x.data(), dt.data(), nl.data(), k, koff.data(), start.data(), roff.data(), voff.data(),
-                                                    desc.data(), &l32, &nb32);
-    if (blocks >= (1ull << 32)) return fail(ctx, FLASHE_EINVAL, "sparsify_tensors: too many elements");
-    if (ctx->capturing) return fail(ctx, FLASHE_EINVAL, "sparsify_tensors: not inside a graph capture (the layer table is uploaded synchronously)");
-    if ((rc = ensure(ctx, ctx->sp_ws, sparsify_tensors_workspace_bytes(n_layers, blocks)))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->sp_ws.p, desc.data(), desc.size(), hipMemcpyHostToDevice, ctx->env.stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->env.stream));
-    HIP_TRY(ctx, launch_sparsify_tensors(ctx->env, n_layers, l32, blocks, nb32, residual_dev, loc_dev, vals_dev, total_k, bits, packed_dev, ctx->sp_ws.p));
-    return FLASHE_OK;
-}
-
-// ---- a cohort of sparse-job clients on one device (include/flashe.h) ----
-// flashe_sparsify_tensors_dev for C models of one shape: the shared table gives starts and compute classes, the C x L sources their
-// pointers and storage dtypes; client c's residuals / values / locations / packed locations are block c of equal-stride buffers, laid
-// out inside the block exactly as flashe_sparsify_tensors_dev lays out one model.  One set of launches whatever C is.
-int flashe_sparsify_cohort_tensors_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const uint64_t *k,
-                                       const void *const *src_dev, const int32_t *src_dtype, void *residual_dev, uint64_t residual_stride,
-                                       uint32_t *loc_dev, uint64_t loc_stride, void *vals_dev, uint64_t vals_stride, uint64_t *packed_dev,
-                                       uint64_t packed_stride, int bits)
-{
-    CHECK_CTX(ctx);
-    if (n_clients < 1 || n_clients > 65535) return fail(ctx, FLASHE_EINVAL, "sparsify_cohort: n_clients must be in [1, 65535]");
-    if (n >= (1ull << 32)) return fail(ctx, FLASHE_EINVAL, "sparsify_cohort: n must be < 2^32");
-    if (!k || !src_dev || !src_dtype) return fail(ctx, FLASHE_EINVAL, "sparsify_cohort: null argument");
-    int rc = check_tensor_layers_shape(ctx, n, layers, n_layers);
-    if (rc) return rc;
-    if (packed_dev && (bits < 1 || bits > 32 || (bits < 32 && n > (1ull << bits))))
-        return fail(ctx, FLASHE_EINVAL, "sparsify_cohort: bits (%d) must be in [1, 32] and cover n (%llu)", bits, static_cast<unsigned long long>(n));
-    if (static_cast<uint64_t>(n_clients) * static_cast<uint64_t>(n_layers) > (1u << 24)) return fail(ctx, FLASHE_EINVAL, "sparsify_cohort: too many table rows");
-    const size_t rows = static_cast<size_t>(n_clients) * n_layers;
-    // one client's block: flashe_sparsify_tensors_dev's layout
-    std::vector<uint64_t> nl(n_layers), koff1(n_layers), roff1(n_layers), voff1(n_layers);
-    uint64_t total_k = 0, r = 0, v = 0;
-    for (int l = 0; l < n_layers; l++) {
-        const flashe_tensor_layer &y = layers[l];
-        if (y.dtype != FLASHE_TENSOR_F32 && y.dtype != FLASHE_TENSOR_F64)
-            return fail(ctx, FLASHE_EINVAL, "layer %d: the shared row names the COMPUTE type, FLASHE_TENSOR_F32 or FLASHE_TENSOR_F64", l);
-        nl[l] = (l + 1 < n_layers ? layers[l + 1].start : n) - y.start;
-        if (k[l] > nl[l]) return fail(ctx, FLASHE_EINVAL, "sparsify_cohort: layer %d: k (%llu) > n (%llu)", l, static_cast<unsigned long long>(k[l]),
-                                      static_cast<unsigned long long>(nl[l]));
-        const uint64_t cs = y.dtype == FLASHE_TENSOR_F64 ? 8 : 4;
-        r = (r + cs - 1) / cs * cs;
-        v = (v + cs - 1) / cs * cs;
-        koff1[l] = total_k; roff1[l] = r; voff1[l] = v;
-        r += nl[l] * cs;
-        v += k[l] * cs;
-        total_k += k[l];
-    }
-    if (n == 0 || (total_k == 0 && !residual_dev)) return FLASHE_OK;          // (total_k == 0 with residuals: every layer only updates its own)
-    if (total_k && (!loc_dev || !vals_dev)) return fail(ctx, FLASHE_EINVAL, "null vector");
-    if (loc_stride < total_k || vals_stride < v || (vals_stride & 7u) || (residual_dev && (residual_stride < r || (residual_stride & 7u))))
-        return fail(ctx, FLASHE_EINVAL, "sparsify_cohort: a stride is shorter than one client's block or not a multiple of 8 bytes");
-    if (static_cast<uint64_t>(n_clients) * loc_stride >= (1ull << 32)) return fail(ctx, FLASHE_EINVAL, "sparsify_cohort: too many locations");
-    const uint64_t n_limbs = (total_k * static_cast<uint64_t>(bits > 0 ? bits : 1) + 63) / 64;
-    if (packed_dev && packed_stride < n_limbs) return fail(ctx, FLASHE_EINVAL, "sparsify_cohort: packed_stride is shorter than one client's packed locations");
-    std::vector<const void *> x(rows);
-    std::vector<int> dt(rows);
-    std::vector<uint64_t> nn(rows), kk(rows), koff(rows), start(rows), roff(rows), voff(rows);
-    for (int c = 0; c < n_clients; c++)
-        for (int l = 0; l < n_layers; l++) {
-            const size_t at = static_cast<size_t>(c) * n_layers + l;
-            const int es = tensor_elem_bytes(src_dtype[at]);
-            if (!es) return fail(ctx, FLASHE_EINVAL, "client %d layer %d: unknown dtype %d", c, l, static_cast<int>(src_dtype[at]));
-            if ((src_dtype[at] == FLASHE_TENSOR_F64) != (layers[l].dtype == FLASHE_TENSOR_F64))
-                return fail(ctx, FLASHE_EINVAL, "client %d layer %d: the source is of another compute class than the shared row", c, l);
-            if (nl[l] && (!src_dev[at] || reinterpret_cast<uintptr_t>(src_dev[at]) % static_cast<uintptr_t>(es)))
-                return fail(ctx, FLASHE_EINVAL, "client %d layer %d: null or misaligned source", c, l);
-            x[at] = src_dev[at]; dt[at] = src_dtype[at]; nn[at] = nl[l]; kk[at] = k[l]; start[at] = layers[l].start;
-            koff[at] = static_cast<uint64_t>(c) * loc_stride + koff1[l];
-            roff[at] = static_cast<uint64_t>(c) * residual_stride + roff1[l];
-            voff[at] = static_cast<uint64_t>(c) * vals_stride + voff1[l];
-        }
-    std::vector<unsigned char> desc(sparsify_tensors_desc_bytes(static_cast<int>(rows)));
-    int r32 = 0;
-    uint64_t nb32 = 0;
-    const uint64_t blocks = sparsify_tensors_layout(static_cast<int>(rows), x.data(), dt.data(), nn.data(), kk.data(), koff.data(), start.data(), roff.data(),
-                                                    voff.data(), desc.data(), &r32, &nb32);
-    if (blocks >= (1ull << 32)) return fail(ctx, FLASHE_EINVAL, "sparsify_cohort: too many elements");
-    if ((rc = ensure(ctx, ctx->sp_ws, sparsify_tensors_workspace_bytes(static_cast<int>(rows), blocks)))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->sp_ws.p, desc.data(), desc.size(), hipMemcpyHostToDevice, ctx->env.stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->env.stream));
-    HIP_TRY(ctx, launch_sparsify_cohort(ctx->env, n_clients, static_cast<int>(rows), r32, blocks, nb32, residual_dev, loc_dev, loc_stride, vals_dev, total_k, bits,
-                                        packed_dev, packed_stride, ctx->sp_ws.p));
-    return FLASHE_OK;
-}
-
-// The sparse job's codec front end for all clients of a cohort in one launch: shared compact layer table (start, alpha, shift, flags;
-// dtype = the compute class), C x L sources, client-major draws -> C one-limb plaintext vectors + the C quantised 'zzz' values.
-// (the argument checks of the two entry points that take a sparse cohort's compact layers: the one below and
-// flashe_quantize_encrypt_sparse_cohort_dev; outs = the HOST array of output vectors; row_of = the non-empty layers)
-static int quantize_cohort_check(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
-                                 const int32_t *src_dtype, int element_bits, const double *u_dev, uint64_t u_stride, const double *zzz,
-                                 const void *outs, const uint64_t *zeros_dev, std::vector<int> &row_of)
-{
-    if (n_clients < 1 || n_clients > 65535) return fail(ctx, FLASHE_EINVAL, "quantize_cohort: n_clients must be in [1, 65535]");
-    if (!src_dev || !src_dtype || !u_dev || !zzz || !outs || !zeros_dev) return fail(ctx, FLASHE_EINVAL, "quantize_cohort: null argument");
-    if (element_bits < 1 || element_bits > 62 || element_bits > ctx->int_bits)
-        return fail(ctx, FLASHE_EINVAL, "element_bits must be in [1, min(62, int_bits)], got %d", element_bits);
-    if ((reinterpret_cast<uintptr_t>(u_dev) & 7u) || (reinterpret_cast<uintptr_t>(zeros_dev) & 7u)) return fail(ctx, FLASHE_EINVAL, "misaligned vector");
-    if (u_stride < n + 1) return fail(ctx, FLASHE_EINVAL, "quantize_cohort: u_stride must cover a client's n + 1 draws");
-    int rc = check_tensor_layers_shape(ctx, n, layers, n_layers);
-    if (rc) return rc;
-    if ((rc = cohort_rows(ctx, n, layers, n_layers, row_of))) return rc;
-    for (int c = 0; c < n_clients; c++)
-        for (const int l : row_of) {
-            const size_t at = static_cast<size_t>(c) * n_layers + l;
-            const int es = tensor_elem_bytes(src_dtype[at]);
-            if (!es) return fail(ctx, FLASHE_EINVAL, "client %d layer %d: unknown dtype %d", c, l, static_cast<int>(src_dtype[at]));
-            if ((src_dtype[at] == FLASHE_TENSOR_F64) != (layers[l].dtype == FLASHE_TENSOR_F64))
-                return fail(ctx, FLASHE_EINVAL, "client %d layer %d: the source is of another compute class than the shared row", c, l);
-            if (!src_dev[at] || reinterpret_cast<uintptr_t>(src_dev[at]) % static_cast<uintptr_t>(es))
-                return fail(ctx, FLASHE_EINVAL, "client %d layer %d: null or misaligned source", c, l);
-        }
-    return FLASHE_OK;
-}
-
-int flashe_quantize_cohort_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
-                               const int32_t *src_dtype, int element_bits, const double *u_dev, uint64_t u_stride, const double *zzz, int zzz_is_f64,
-                               uint64_t *const *pt_dev, uint64_t *const *tail_dev, uint64_t *zeros_dev)
-{
-    CHECK_CTX(ctx);
-    if (n >= (1ull << 32)) return fail(ctx, FLASHE_EINVAL, "quantize_cohort: n must be < 2^32");
-    std::vector<int> row_of;
-    int rc = quantize_cohort_check(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, u_dev, u_stride, zzz, pt_dev, zeros_dev, row_of);
-    if (rc) return rc;
-    std::vector<QuantCohortRow> tab;
-    for (const int l : row_of) {
-        const flashe_tensor_layer &y = layers[l];
-        const Codec c = codec_quantize_front(nullptr, y.dtype == FLASHE_TENSOR_F64 || (y.flags & FLASHE_TENSOR_LOOP_F64), y.alpha, element_bits, nullptr);
-        tab.push_back(QuantCohortRow{y.start, c.alpha, c.scale, c.den, y.shift, c.x_is_f64, y.flags & (FLASHE_TENSOR_SHIFT | FLASHE_TENSOR_SHIFT_WIDE)});
-    }
-    const size_t n_tab = tab.size(), C = static_cast<size_t>(n_clients);
-    std::vector<const void *> src(C * n_tab);
-    std::vector<int32_t> sdt(C * n_tab);
-    for (size_t c = 0; c < C; c++) {
-        if (n && (!pt_dev[c] || (reinterpret_cast<uintptr_t>(pt_dev[c]) & 7u))) return fail(ctx, FLASHE_EINVAL, "client %d: null or misaligned plaintext vector", static_cast<int>(c));
-        if (tail_dev && tail_dev[c] && (reinterpret_cast<uintptr_t>(tail_dev[c]) & 7u)) return fail(ctx, FLASHE_EINVAL, "client %d: misaligned tail", static_cast<int>(c));
-        for (size_t rr = 0; rr < n_tab; rr++) {
-            const size_t at = c * n_layers + row_of[rr];
-            src[c * n_tab + rr] = src_dev[at];
-            sdt[c * n_tab + rr] = src_dtype[at];
-        }
-    }
-    // one block in ctx->codec_tab: rows | sources | plaintext pointers | tails | zzz values | source dtypes
-    auto up16 = [](size_t b) { return (b + 15) & ~static_cast<size_t>(15); };
-    const size_t o_src = up16(n_tab * sizeof(QuantCohortRow)), o_pt = o_src + up16(src.size() * sizeof(void *)), o_tail = o_pt + up16(C * sizeof(void *)),
-                 o_zzz = o_tail + up16(C * sizeof(void *)), o_dt = o_zzz + up16(C * sizeof(double));
-    std::vector<char> blob(o_dt + up16(sdt.size() * sizeof(int32_t)) + 16, 0);
-    if (n_tab) memcpy(blob.data(), tab.data(), n_tab * sizeof(QuantCohortRow));
-    if (!src.empty()) memcpy(blob.data() + o_src, src.data(), src.size() * sizeof(void *));
-    memcpy(blob.data() + o_pt, pt_dev, C * sizeof(void *));
-    if (tail_dev) memcpy(blob.data() + o_tail, tail_dev, C * sizeof(void *));
-    memcpy(blob.data() + o_zzz, zzz, C * sizeof(double));
-    if (!sdt.empty()) memcpy(blob.data() + o_dt, sdt.data(), sdt.size() * sizeof(int32_t));
-    const char *blob_dev = nullptr;
-    if ((rc = upload_tab(ctx, ctx->codec_tab, blob, &blob_dev))) return rc;
-    QuantCohort qc{};
-    qc.rows = reinterpret_cast<const QuantCohortRow *>(blob_dev);
-    qc.src = reinterpret_cast<const void *const *>(blob_dev + o_src);
-    qc.pt = reinterpret_cast<uint64_t *const *>(blob_dev + o_pt);
-    qc.tail = reinterpret_cast<uint64_t *const *>(blob_dev + o_tail);
-    qc.zzz = reinterpret_cast<const double *>(blob_dev + o_zzz);
-    qc.src_dtype = reinterpret_cast<const int32_t *>(blob_dev + o_dt);
-    qc.zeros = zeros_dev;
-    qc.n_rows = static_cast<int>(n_tab); qc.n_clients = n_clients; qc.tail_limbs = ctx->limbs;
-    const Codec z = codec_quantize_front(nullptr, zzz_is_f64 != 0, 1.0, element_bits, nullptr);
-    qc.zrow = QuantCohortRow{n, z.alpha, z.scale, z.den, 0.0, z.x_is_f64, 0};
-    HIP_TRY(ctx, launch_quantize_cohort(ctx->env, qc, n, u_dev, u_stride));
-    return FLASHE_OK;
-}
-
-// The two steps of a sparse cohort's uploads -- flashe_quantize_cohort_dev, then one flashe_encrypt_dev(SINGLE) per client
-// (jzf_quantize.py:433-465, jzf_aggregator.py:717-743, jzf_flashe.py:471-478) -- as ONE chained launch from the floats at int_bits
-// 16 / 20 / 23 / 24 / 32 (prf_small_sparse_cohort_kernel): no plaintext vector exists in HBM.  The checks are quantize_cohort_check's, the
-// table and the stage pass cohort_stage's; what the launch does not take is refused with FLASHE_ENOTSUP before anything is staged.
-int flashe_quantize_encrypt_sparse_cohort_dev(flashe_ctx *ctx, uint32_t iter, int n_clients, const uint32_t *idx, uint64_t n, uint32_t n_jobs,
-                                              const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
-                                              int element_bits, const double *u_dev, uint64_t u_stride, const double *zzz, int zzz_is_f64,
-                                              uint64_t *const *ct_dev, uint64_t *zeros_dev)
-{
-    CHECK_CTX(ctx);
-    static const char who[] = "flashe_quantize_encrypt_sparse_cohort_dev";
-    std::vector<int> row_of;
-    int rc = quantize_cohort_check(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, u_dev, u_stride, zzz, ct_dev, zeros_dev, row_of);
-    if (rc) return rc;
-    if (!idx) return fail(ctx, FLASHE_EINVAL, "%s: null argument", who);
-    if (n_jobs == 0) return fail(ctx, FLASHE_EINVAL, "n_jobs must be >= 1");
-    for (int c = 0; c < n_clients; c++) {
-        if (!ct_dev[c] || (reinterpret_cast<uintptr_t>(ct_dev[c]) & 7u)) return fail(ctx, FLASHE_EINVAL, "client %d: null or misaligned upload", c);
-        if (reinterpret_cast<uint64_t *>(ct_dev[c]) == zeros_dev) return fail(ctx, FLASHE_EINVAL, "client %d: the upload aliases zeros_dev", c);
-    }
-    if (!small_cohort_admits(ctx->env, n_clients, n, n_jobs, false)) return cohort_declined(ctx, who, "sparse cohort");
-    const Codec z = codec_quantize_front(nullptr, zzz_is_f64 != 0, 1.0, element_bits, nullptr);
-    CohortCodec cc{};
-    const char *zzz_dev = nullptr;
-    if ((rc = cohort_stage(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, cc, zzz, static_cast<size_t>(n_clients) * sizeof(double),
-                           &zzz_dev, &row_of)))
-        return rc;
-    return cohort_launched(ctx, launch_small_sparse_cohort(ctx->env, iter, n_clients, idx, cc, u_dev, u_stride, ct_dev, n, n_jobs,
-                                                           reinterpret_cast<const double *>(zzz_dev), z.x_is_f64 != 0, z.alpha, z.scale, z.den, zeros_dev),
-                           who, "sparse cohort");
 }
 
 #ifdef FLASHE_TUNING

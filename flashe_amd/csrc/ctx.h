@@ -1,10 +1,12 @@
-// Private to the host side of libflashe_hip.so (abi.hip, host_twins.hip, comm.hip): the context object behind the opaque flashe_ctx
+// Private to the host side of libflashe_hip.so (abi.hip, abi_layers.hip, host_twins.hip, comm.hip): the context object behind the opaque flashe_ctx
 // of include/flashe.h, and the error-reporting and argument helpers the entry points share.
 #pragma once
 #include "flashe.h"
 #include "kernels.h"
 #include "blockpool.h"
 
+#include <algorithm>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -62,9 +64,23 @@ int fail(flashe_ctx *ctx, int code, const char *fmt, ...) __attribute__((format(
 
 inline size_t vec_bytes(const flashe_ctx *ctx, uint64_t n) { return static_cast<size_t>(n) * ctx->limbs * 8; }
 
-// FLASHE_EINVAL when the double mask would need prefix idx + 1 = 2^32 for one of the n_idx entries (abi.hip)
+// b holds at least `bytes` (grown on demand; FLASHE_EINVAL while a graph is being captured)
+int ensure(flashe_ctx *ctx, flashe_ctx::Buf &b, size_t bytes);
+bool aligned16(const void *p);
+bool ct_aligned(const flashe_ctx *ctx, const void *p);   // aligned like a ciphertext vector: 16 bytes for 2-limb elements, else 8
+
+// The argument checks the entry points of abi.hip and abi_layers.hip share (abi.hip): FLASHE_OK, or FLASHE_EINVAL with the message set.
+int check_scheme(flashe_ctx *ctx, int scheme);
+int check_wide_aligned(flashe_ctx *ctx, std::initializer_list<const void *> vecs);
+int check_sum_aligned(flashe_ctx *ctx, const void *sum_out_dev);
+// ... when the double mask would need prefix idx + 1 = 2^32 for one of the n_idx entries
 int check_double_idx(flashe_ctx *ctx, int scheme, const uint32_t *idx, int n_idx);
 int check_field_bits(flashe_ctx *ctx, int field_bits);
+int check_range(flashe_ctx *ctx, uint64_t n, uint64_t first, uint64_t count);
+int check_prf_args(flashe_ctx *ctx, int n_add, int n_minus, uint32_t n_jobs, const void *out, const void *in, int in_limbs);
+// out = in + sum term(add[k]) - sum term(minus[k]) over prefix lists of any length (abi.hip)
+hipError_t prf_lists(flashe_ctx *ctx, uint32_t iter, const uint32_t *add, int n_add, const uint32_t *minus, int n_minus, uint64_t n, uint32_t n_jobs,
+                     uint64_t first, uint64_t count, const uint64_t *in_dev, int in_limbs, uint64_t *out_dev);
 
 // RAII temp device buffer for the host-pointer twins.  Staging blocks are kept by the ctx and reused: a hipMalloc + hipFree
 // pair of a 160 MB block costs more than moving 160 MB over PCIe Gen5 on this platform (measured 7 ms against 2.9 ms,
@@ -102,3 +118,27 @@ struct Tmp {
         if (!(ctx)) return FLASHE_EINVAL;                                     \
         HIP_TRY(ctx, hipSetDevice((ctx)->device));                            \
     } while (0)
+
+namespace flashe_host {
+
+// Host bytes to the device on the ctx stream.  (Pageable source: the copy has left `src` when the call returns; stream order keeps an
+// earlier launch's table intact until it ends.)
+inline int upload_bytes(flashe_ctx *ctx, void *dst, const void *src, size_t bytes)
+{
+    HIP_TRY(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->env.stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->env.stream));
+    return FLASHE_OK;
+}
+
+// A host table into a ctx buffer (grown to hold it; an empty table uploads nothing).
+template <class T> inline int upload_tab(flashe_ctx *ctx, flashe_ctx::Buf &b, const std::vector<T> &tab, const T **tab_dev, int *n_tab = nullptr)
+{
+    int rc = ensure(ctx, b, std::max<size_t>(tab.size(), 1) * sizeof(T));
+    if (rc) return rc;
+    if (!tab.empty() && (rc = upload_bytes(ctx, b.p, tab.data(), tab.size() * sizeof(T)))) return rc;
+    *tab_dev = static_cast<const T *>(b.p);
+    if (n_tab) *n_tab = static_cast<int>(tab.size());
+    return FLASHE_OK;
+}
+
+}  // namespace flashe_host
