@@ -10,7 +10,10 @@ which this example checks.
   --compact    with --bits <= 32: uint32 ciphertexts and sum (FlasheCohort(compact=True)); at int_bits 16 / 20 / 23 / 24 / 32 the chained
                launch then goes from the floats to the uint32 ciphertexts
   --batch      a batched job (the reference's *_q16_b6_pad jobs: --bits 120 --batch packs six 20-bit fields per element); the chained
-               launch takes it when the model has enough batched elements to fill the chip"""
+               launch takes it when the model has enough batched elements to fill the chip
+  --precompute a precompute job ("precompute": {"enable": true}): the cohort calls prepare_encrypt() one round ahead -- the masks of all
+               ten clients as one chain of eleven PRF streams, in idle time -- and the online step is ONE launch with no AES
+               (`upload.path` is "prepared-cohort"), at any --bits, with or without --compact / --batch"""
 import argparse
 import os
 import sys
@@ -46,15 +49,25 @@ def main():
     ap.add_argument("--bits", type=int, default=128)
     ap.add_argument("--compact", action="store_true")
     ap.add_argument("--batch", action="store_true")
+    ap.add_argument("--precompute", action="store_true")
     opt = ap.parse_args()
     cm.N_JOBS = 16                                           # every party must use the same value
     C, key = 10, bytes(range(32))
-    args = {"quantize": {"int_bits": opt.bits, "batch": opt.batch, "element_bits": 16, "padding": True, "secure": True}, "precompute": {"enable": False}}
     models = [make_model(c) for c in range(C)]
     layers = [{name: p.detach() for name, p in m.named_parameters()} for m in models]
+    # a precompute job states the length of its uploads: the values of the model, or -- batched -- its elements of bs values, every layer
+    # padded to whole elements on its own
+    bs = opt.bits // (16 + int(np.ceil(np.log2(C)))) if opt.batch else 1
+    num_params = sum((t.numel() + bs - 1) // bs for t in layers[0].values())
+    args = {"quantize": {"int_bits": opt.bits, "batch": opt.batch, "element_bits": 16, "padding": True, "secure": True},
+            "precompute": {"enable": opt.precompute, "num_params": num_params}}
+    it = 1 if opt.precompute else 0
 
     cohort = FlasheCohort(args, first_idx=0, n_local=C, num_clients=C, prp_seed=key, compact=opt.compact)
-    cohort.set_iter_index(0)
+    if opt.precompute:
+        cohort.set_iter_index(it - 1)
+        cohort.prepare_encrypt()                             # in idle time, one round ahead: the masks of iteration `it`
+    cohort.set_iter_index(it)
     np.random.seed(0)
     with torch.no_grad():
         upload = cohort.quantize_encrypt([Weights(l) for l in layers], normalize=True)
@@ -68,7 +81,10 @@ def main():
     for c in range(C):
         cl = FlasheClient(args)
         cl.create_cipher(c, C, key)
-        cl.set_iter_index(0)
+        if opt.precompute:
+            cl.set_iter_index(it - 1)
+            cl.prepare_encrypt()                             # every client its own two mask vectors
+        cl.set_iter_index(it)
         clients.append(cl)
     np.random.seed(0)
     with torch.no_grad():

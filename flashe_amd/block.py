@@ -844,6 +844,7 @@ class FlasheClient(object):
 
 # ---- a cohort of consecutive clients hosted on one GPU (new) --------------------------------------------------------------------
 COHORT_CHAIN, STAGED_CHAIN, PER_CLIENT = "cohort-chain", "staged-chain", "per-client"
+PREPARED_COHORT, PREPARED_STAGED = "prepared-cohort", "prepared-staged"   # with the cohort's own mask cache (FlasheCohort.prepare_encrypt)
 _COHORT_MAX_LINKS = 128          # outputs of one chained launch (kMaxLinks, kernels.hip)
 
 
@@ -939,7 +940,7 @@ def compact_cohort_admission_length(cu_count, int_bits, n_jobs):
 
 
 def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, mask="double", num_clients=None, precompute=False, chain=True,
-                location_masks=False, compact=False, n_jobs=None):
+                location_masks=False, compact=False, n_jobs=None, cohort_masks=False):
     """The engine-free part of FlasheCohort.quantize_encrypt: checks that the clients' Weights describe one model (the same layer names
     in the same walking order with the same shapes: ValueError naming the client and the layer otherwise; a sparse upload -- a 'zzz'
     layer or location masks -- is a TypeError), lays out the shared layer table and the client-major draws, and picks the path:
@@ -955,7 +956,14 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
     flashe_quantize_encrypt_cohort_u32_dev instead: int_bits 16 / 20 / 23 / 24 / 32 in place of int_bits > 64, and a model of at least
     compact_cohort_admission_length(cu_count, int_bits, n_jobs) values (n_jobs: the chunking of the counters, default cipher.N_JOBS)
     and fewer than 2^32 in place of the length rule above; the other conditions and every fallback are the same.
-    Touches no device.  The library's own answer stays the last word: a "cohort-chain" plan it declines runs "staged-chain"."""
+    cohort_masks=True (the cohort holds the masks of FlasheCohort.prepare_encrypt: a precompute job under the double mask) answers
+      "prepared-cohort"  one online launch from the floats and the masks, no AES (flashe_quantize_combine_cohort_dev, its _u32 form with
+                         compact=True, flashe_quantize_batch_combine_cohort_dev for a batched job): any int_bits, any length, any number
+                         of clients;
+      "prepared-staged"  a layer that is float64 for some clients only (no shared row), or a batched job in the compact layout: a
+                         quantise (+ batch) pass per client into plaintexts, then flashe_combine_batch_sum_dev with the masks.
+    Touches no device.  The library's own answer stays the last word: a "cohort-chain" plan it declines runs "staged-chain", a
+    "prepared-cohort" one "prepared-staged"."""
     if len(weights_list) < 1:
         raise ValueError("a cohort needs at least one client's Weights")
     C = len(weights_list)
@@ -979,7 +987,14 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
     if batch:
         bs = int_bits // (element_bits + int(np.ceil(np.log2(num_clients))))
         n_elems = sum((s_ + bs - 1) // bs for s_ in sizes)
-    if precompute:
+    if cohort_masks and mask == "double":
+        if mixed:
+            path, reason = PREPARED_STAGED, "a layer is float64 for some clients only: no shared row of one compute class"
+        elif batch and compact:
+            path, reason = PREPARED_STAGED, "batched job in the compact layout"
+        else:
+            path, reason = PREPARED_COHORT, "the cohort holds its clients' precomputed masks"
+    elif precompute:
         path, reason = PER_CLIENT, "precomputed masks are held per client"
     elif mask not in ("double", "single"):
         path, reason = PER_CLIENT, f"mask {mask!r}"
@@ -1054,7 +1069,10 @@ class FlasheCohort(object):
     compact DeviceVectors (uint32, elem_bytes 4) whatever path ran, and at int_bits 16 / 20 / 23 / 24 / 32 -- the widths the shipped jobs
     run -- the chained launch goes from the floats to the uint32 ciphertexts and their sum (flashe_quantize_encrypt_cohort_u32_dev: 16
     bytes moved per value and client instead of 36).  No decrypt mask is kept at these widths: decrypt_unquantize() decrypts the
-    sum."""
+    sum.
+    A precompute job ("precompute": {"enable": true}) calls prepare_encrypt() in idle time: the next round's masks of all clients as one
+    chain of n_local + 1 streams, held by the cohort; the next quantize_encrypt is then ONE online launch with no AES ("prepared-cohort")
+    at any int_bits, batched or not, compact or not.  Without that call the clients' own masks run "per-client" as before."""
 
     def __init__(self, args, first_idx, n_local, num_clients, prp_seed, device=0, stream=None, compact=False):
         if n_local < 1 or first_idx < 0 or first_idx + n_local > num_clients:
@@ -1077,6 +1095,7 @@ class FlasheCohort(object):
                 cl.create_cipher(self.first_idx + c, self.num_clients, prp_seed)
                 cl.quantizer = self.lead.quantizer
                 self._clients.append(cl)
+        self._masks = None                             # the cohort's own encrypt-mask cache (prepare_encrypt): one vector per client
         self._last = None                              # the last upload (its sum is what decrypt_unquantize() decrypts)
         self.prefer = None                             # "staged-chain" / "per-client": run that fallback form where the chain would be taken (A/B runs)
 
@@ -1098,7 +1117,38 @@ class FlasheCohort(object):
         return plan_cohort(weights_list, ld.int_bits, ld.cipher.engine.cu_count, element_bits=ld.quantizer.element_bits, batch=bool(ld.batch),
                            mask=ld.cipher.masking_scheme, num_clients=self.num_clients, precompute=bool(ld.precompute),
                            chain=os.environ.get("FLASHE_CHAIN", "1") != "0", location_masks=ld.cipher.masks is not None, compact=self.compact,
-                           n_jobs=_cipher_mod.N_JOBS)
+                           n_jobs=_cipher_mod.N_JOBS, cohort_masks=self._masks is not None)
+
+    def prepare_encrypt(self):
+        """A precompute job's idle-time step for the whole cohort.  Double mask: the encrypt masks of iteration iter_index + 1 for all
+        n_local clients as ONE chain of n_local + 1 PRF streams (consecutive clients share a stream: Engine.cohort_masks_dev) over
+        cipher.num_params elements, one vector per client held by the cohort -- compact (uint32) when the cohort is -- in place of the
+        clients' own add and minus vectors: masks the clients had prepared themselves are DISCARDED (FlasheCipher.discard_prepared_encrypt),
+        as a new prepare_encrypt overwrites them.  The next quantize_encrypt
+        consumes them in one online launch ("prepared-cohort").  Single mask (the reference does not read the cache there) or precompute
+        off: the clients' own prepare_encrypt."""
+        from . import cipher as _cipher_mod
+        from .engine import DeviceVector
+        ld = self.lead
+        c = ld.cipher
+        if not ld.precompute or c.masking_scheme != "double":
+            for cl in (self._clients or [ld]):
+                cl.prepare_encrypt()
+            return
+        (c.iter_index + 1).to_bytes(4, 'big')                              # same range check as FlasheCipher.prepare_encrypt
+        eng, n = c.engine, int(c.num_params)
+        masks = [DeviceVector(eng, n, 1, elem_bytes=4) if self.compact else DeviceVector(eng, n) for _ in range(self.n_local)]
+        eng.cohort_masks_dev(c.iter_index + 1, self.first_idx, self.n_local, n, _cipher_mod.N_JOBS, [m.buf for m in masks], compact=self.compact)
+        eng.sync()
+        for m in masks:
+            m.mark_ready()
+        for cl in self._clients:
+            cl.cipher.discard_prepared_encrypt()
+        self._masks = masks
+
+    def prepare_decrypt(self):
+        """The lead client's prepare_decrypt: the decrypting party's masks do not depend on the cohort."""
+        self.lead.prepare_decrypt()
 
     def quantize_encrypt(self, weights_list, normalize=False, seeds=None):
         """One Weights per client (host arrays and / or framework float device tensors, as FlasheClient.quantize_encrypt takes them) ->
@@ -1140,10 +1190,23 @@ class FlasheCohort(object):
                         flat = flat.astype(np.float64)
                     row.append((flat, flat.dtype))
             layers.append(row)
+        if self._masks is not None and plan.path in (PREPARED_COHORT, PREPARED_STAGED) and len(self._masks[0]) != plan.n_elems:
+            # a cache of another length: the call-by-call step's ValueError, where the first sequential client raises it (after its
+            # quantiser has drawn one value per model value, FlasheClient._refuse_prepared_len); the cache stays, and nothing of the
+            # cohort's state has been touched or uploaded yet
+            if seeds is not None:
+                np.random.seed(seeds[0])
+            for at in range(0, plan.n, _RNG_RUN_MAX):
+                np.random.random(min(_RNG_RUN_MAX, plan.n - at))
+            c._check_prepared_len(self._masks[0], plan.n_elems)
         self._last, ld._cohort_mask = None, None
-        if any(row[li][1] != layers[0][li][1] for row in layers for li in range(len(row))) and plan.path == COHORT_CHAIN:
-            plan.path = STAGED_CHAIN                   # (a layer that computes in float64 for some clients only: no shared row)
-        if self.prefer == PER_CLIENT or (self.prefer == STAGED_CHAIN and plan.path == COHORT_CHAIN):
+        if any(row[li][1] != layers[0][li][1] for row in layers for li in range(len(row))) and plan.path in (COHORT_CHAIN, PREPARED_COHORT):
+            # (a layer that computes in float64 for some clients only: no shared row)
+            plan.path = STAGED_CHAIN if plan.path == COHORT_CHAIN else PREPARED_STAGED
+        prepared = plan.path in (PREPARED_COHORT, PREPARED_STAGED)       # (the cohort's cache is consumed whatever `prefer` says)
+        if prepared and self.prefer == STAGED_CHAIN:
+            plan.path = PREPARED_STAGED
+        elif not prepared and (self.prefer == PER_CLIENT or (self.prefer == STAGED_CHAIN and plan.path == COHORT_CHAIN)):
             plan.path = self.prefer
         if plan.path == PER_CLIENT:
             return self._per_client(weights_list, normalize, seeds)
@@ -1243,6 +1306,34 @@ class FlasheCohort(object):
                 path = STAGED_CHAIN                    # the library declined: the planner's guess was wrong, the result is not
             elif dmask is not None:
                 ld._cohort_mask = (psum.ptr, dmask, c.iter_index, self.first_idx + C, self.first_idx)
+        if path == PREPARED_COHORT:
+            # ONE online launch: every client's floats and its precomputed mask -> its ciphertext, and their sum; no AES
+            rows = [(st, None, al, sh, TENSOR_F64 if layers[0][li][1] == np.float64 else TENSOR_F32, fl)
+                    for li, (st, _p, al, sh, _code, fl) in enumerate(tables[0])]
+            srcs = [[t[1] for t in table] for table in tables]
+            dts = [[t[4] for t in table] for table in tables]
+            field_bits = q.element_bits + int(np.ceil(np.log2(q.num_clients)))
+            took = eng.quantize_combine_cohort_dev(n, rows, srcs, dts, q.element_bits, du, [m.buf for m in self._masks], [v.buf for v in cts], psum.buf,
+                                                   compact=self.compact, batch=(n_elems, field_bits) if ld.batch else None)
+            if not took:
+                path = PREPARED_STAGED                 # the library declined: the same bytes from the fallback form
+        if path == PREPARED_STAGED and n_elems:
+            # a quantise (+ batch) pass per client into plaintexts, then the combines with the masks and their sum in one pass (one-limb
+            # vectors: a compact cohort widens its masks before and narrows the results after)
+            field_bits = q.element_bits + int(np.ceil(np.log2(q.num_clients))) if ld.batch else ld.int_bits
+            pts = [eng.alloc_vec(n_elems) for _ in range(C)]
+            for ci in range(C):
+                eng.quantize_batch_tensors_dev(tables[ci], n, q.element_bits, field_bits, du.ptr + 8 * plan.draw_offsets[ci], n_elems, pts[ci])
+            adds = [m.widened(eng) for m in self._masks]
+            wide = [DeviceVector(eng, n_elems) for _ in range(C)] if self.compact else cts
+            wsum = DeviceVector(eng, n_elems) if self.compact else psum
+            eng.combine_batch_sum_dev(n_elems, pts, eng.limbs, [a.buf for a in adds], None, [v.buf for v in wide], wsum.buf)
+            if self.compact:
+                cts, psum = [v.mark_ready().narrowed(eng) for v in wide], wsum.mark_ready().narrowed(eng)
+            keep += pts + adds
+        if prepared:
+            keep += list(self._masks)
+            self._masks = None                         # consumed by this call, whatever the iteration (the reference does not check it either)
         if path == STAGED_CHAIN and n_elems:
             # a quantise (+ batch) pass per client into plaintexts -- un-batched: one value per element, field_bits = int_bits -- then the
             # summed batch encrypt, which chains where it can

@@ -710,6 +710,13 @@ class FlasheCipher(object):
         self.next_iter_encrypt_prepared = {'add': _CtxMask(eng.PREPARED_ENCRYPT, 'add', n), 'minus': _CtxMask(eng.PREPARED_ENCRYPT, 'minus', n)}
         self._ctx_holds |= eng.PREPARED_ENCRYPT
 
+    def discard_prepared_encrypt(self):
+        """Drops the encrypt masks a prepare_encrypt left (new): the dict entries and the vectors the ctx holds for them, as assigning
+        `next_iter_encrypt_prepared = {}` and the next call's reconciliation would.  What a FlasheCohort calls on its clients when its own
+        mask chain replaces their masks."""
+        self.next_iter_encrypt_prepared = {}
+        self._reconcile_prepared()
+
     def prepare_decrypt(self):                                           # jzf_flashe.py:633-666
         eng, n = self._engine, self.num_params
         eng.prepare_decrypt(self.iter_index, self.num_clients, n, N_JOBS)

@@ -879,6 +879,33 @@ int flashe_encrypt_batch_u32_dev(flashe_ctx *ctx, uint32_t iter, int scheme, uin
     });
 }
 
+// A cohort's precomputed encrypt masks in the compact layout: mask_dev[c][j] = term(iter, first_idx + c)[j] - term(iter, first_idx + c + 1)[j]
+// mod 2^b for c < n_clients, j < n -- the double-mask encrypt of an all-zero plaintext, as ONE chain of n_clients + 1 streams with no input
+// (the chained kernels read a null input as zeros, whatever the element size) into vectors the caller owns.  check_u32's conditions, up
+// to kMaxUniformBatch vectors per launch (a further share recomputes the stream at its border).
+int flashe_cohort_masks_u32_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs, uint32_t *const *mask_dev)
+{
+    CHECK_CTX(ctx);
+    if (n_clients < 1 || !mask_dev) return fail(ctx, FLASHE_EINVAL, "flashe_cohort_masks_u32_dev: n_clients must be >= 1 and mask_dev given");
+    int rc = check_u32(ctx, n, n_jobs);
+    if (rc) return rc;
+    std::vector<uint32_t> idx(static_cast<size_t>(n_clients));
+    for (int c = 0; c < n_clients; c++) {
+        idx[c] = first_idx + static_cast<uint32_t>(c);
+        if (idx[c] < first_idx) return fail(ctx, FLASHE_EINVAL, "the cohort's cipher indices wrap around 2^32");
+    }
+    if ((rc = check_double_idx(ctx, FLASHE_SCHEME_DOUBLE, idx.data(), n_clients))) return rc;
+    if (n == 0) return FLASHE_OK;
+    for (int c = 0; c < n_clients; c++)
+        if (!mask_dev[c] || (reinterpret_cast<uintptr_t>(mask_dev[c]) & 3u)) return fail(ctx, FLASHE_EINVAL, "vector %d: null or not 4-byte aligned", c);
+    LaunchEnv env = ctx->env;
+    env.elem32 = 1;
+    const std::vector<const uint64_t *> none(static_cast<size_t>(n_clients), nullptr);
+    return batch_shares(ctx, n_clients, [&](int v0, int nv) {
+        return launch_prf_batch(env, iter, true, nv, idx.data() + v0, none.data() + v0, 1, reinterpret_cast<uint64_t *const *>(mask_dev + v0), n, n_jobs);
+    });
+}
+
 // flashe_encrypt_batch_u32_dev AND sum_out_dev = sum_v ct[v] mod 2^b written by the same launch: the compact twin of
 // flashe_encrypt_batch_sum_dev ("each GPU encrypts and locally mod-adds its share").  One launch for a run of
 // consecutive clients under the double mask at the compiled-in widths (int_bits 16 / 20 / 23 / 24 / 32) when the launch is long enough for the paired kernel (the lane that

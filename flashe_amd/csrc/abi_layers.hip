@@ -721,6 +721,88 @@ int flashe_quantize_batch_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uin
                            who, "batched cohort");
 }
 
+// ---- the cohort's ONLINE step with masks the caller holds (a precompute job's cohort: the mask chain ran in idle time) ----
+// What the three entry points below share: the checks of the chained cohorts (cohort_check's, without cipher indices), the vectors -- every
+// mask and ciphertext given and aligned to its element, the sum apart from all of them and from every source --, cohort_stage's table,
+// sources and stage pass with the mask and ciphertext pointers (and the batched rows) behind it in the same upload, one launch.
+static int quantize_combine_cohort(flashe_ctx *ctx, const char *who, int elem_bytes, int n_clients, uint64_t n_values, uint64_t n_elems, const uint64_t *n_elems_arg,
+                                   const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype, int element_bits,
+                                   int field_bits, const double *u_dev, const void *const *mask_dev, void *const *ct_dev, void *sum_out_dev)
+{
+    const bool batched = n_elems_arg != nullptr;
+    if (n_clients < 1) return fail(ctx, FLASHE_EINVAL, "%s: n_clients must be >= 1", who);
+    if (!src_dev || !mask_dev || !ct_dev || (n_values && !u_dev)) return fail(ctx, FLASHE_EINVAL, "%s: null argument", who);
+    int rc = check_element_bits(ctx, element_bits);
+    if (rc || (rc = check_f64_aligned(ctx, u_dev, "u_dev")) || (rc = check_tensor_layers(ctx, n_values, layers, n_layers, false))) return rc;
+    std::vector<uint64_t> extra(2 * static_cast<size_t>(n_clients));
+    uint64_t bs = 1;
+    if (batched) {
+        if ((rc = check_batch_bits(ctx, element_bits, field_bits, &bs))) return rc;
+        auto size_of = [&](int l) { return layer_end(layers, n_layers, l, n_values) - layers[l].start; };
+        n_elems = flashe_tables::batched_elems(n_layers, bs, size_of, [&](int l, uint64_t elem, uint64_t) { extra.push_back(elem); extra.push_back(size_of(l)); });
+        if ((rc = check_batched_count(ctx, n_elems, *n_elems_arg))) return rc;
+    }
+    const uintptr_t amask = static_cast<uintptr_t>(elem_bytes - 1);
+    for (int c = 0; c < n_clients; c++) {
+        if (n_elems && (!mask_dev[c] || !ct_dev[c])) return fail(ctx, FLASHE_EINVAL, "client %d: null mask or ciphertext", c);
+        if ((reinterpret_cast<uintptr_t>(mask_dev[c]) | reinterpret_cast<uintptr_t>(ct_dev[c])) & amask)
+            return fail(ctx, FLASHE_EINVAL, "client %d: the mask or the ciphertext is not %d-byte aligned", c, elem_bytes);
+        if (sum_out_dev && (mask_dev[c] == sum_out_dev || ct_dev[c] == sum_out_dev)) return fail(ctx, FLASHE_EINVAL, "client %d: the sum aliases the mask or the ciphertext", c);
+        extra[static_cast<size_t>(c)] = reinterpret_cast<uintptr_t>(mask_dev[c]);
+        extra[static_cast<size_t>(n_clients) + c] = reinterpret_cast<uintptr_t>(ct_dev[c]);
+    }
+    if (reinterpret_cast<uintptr_t>(sum_out_dev) & amask) return fail(ctx, FLASHE_EINVAL, "sum_out_dev must be %d-byte aligned", elem_bytes);
+    if (sum_out_dev)
+        for (size_t i = 0; i < flashe_tables::cohort_sources(n_clients, n_layers); i++)
+            if (src_dev[i] == sum_out_dev) return fail(ctx, FLASHE_EINVAL, "the sum aliases a source (client %d layer %d)", static_cast<int>(i / n_layers), static_cast<int>(i % n_layers));
+    if (elem_bytes == 4 && flashe_ctx_compact_layout(ctx) != 1) return cohort_declined(ctx, who, "prepared compact cohort");
+    if (n_elems == 0) return FLASHE_OK;                                    // (an empty model: nothing staged, nothing launched)
+    CohortCodec cc{};
+    const char *extra_dev = nullptr;
+    if ((rc = cohort_stage(ctx, n_clients, n_values, layers, n_layers, src_dev, src_dtype, element_bits, cc, extra.data(), extra.size() * sizeof(uint64_t), &extra_dev)))
+        return rc;
+    const flashe_tables::PreparedBlock at = flashe_tables::prepared_block(n_clients);
+    PrepCohort pc{};
+    pc.layers = cc.layers; pc.src = cc.src; pc.n_layers = cc.n_layers;
+    pc.mask = reinterpret_cast<const void *const *>(extra_dev + at.mask);
+    pc.ct = reinterpret_cast<void *const *>(extra_dev + at.ct);
+    pc.rows = reinterpret_cast<const uint64_t *>(extra_dev + at.rows);
+    pc.u = u_dev; pc.sum = sum_out_dev; pc.n = n_elems; pc.n_values = n_values; pc.n_clients = n_clients; pc.field_bits = field_bits; pc.bs = static_cast<int>(bs);
+    HIP_TRY(ctx, launch_quantize_combine_cohort(ctx->env, pc, elem_bytes, batched));
+    return FLASHE_OK;
+}
+
+int flashe_quantize_combine_cohort_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
+                                       const int32_t *src_dtype, int element_bits, const double *u_dev, const uint64_t *const *mask_dev,
+                                       uint64_t *const *ct_dev, uint64_t *sum_out_dev)
+{
+    CHECK_CTX(ctx);
+    return quantize_combine_cohort(ctx, "flashe_quantize_combine_cohort_dev", ctx->limbs == 2 ? 16 : 8, n_clients, n, n, nullptr, layers, n_layers, src_dev, src_dtype,
+                                   element_bits, 0, u_dev, reinterpret_cast<const void *const *>(mask_dev), reinterpret_cast<void *const *>(ct_dev), sum_out_dev);
+}
+
+// the same in the compact layout at int_bits <= 32 (any such width: there is no AES here): uint32 masks, ciphertexts and sum
+int flashe_quantize_combine_cohort_u32_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
+                                           const int32_t *src_dtype, int element_bits, const double *u_dev, const uint32_t *const *mask_dev,
+                                           uint32_t *const *ct_dev, uint32_t *sum_out_dev)
+{
+    CHECK_CTX(ctx);
+    if (ctx->int_bits > 32) return fail(ctx, FLASHE_EINVAL, "the uint32 layout needs int_bits <= 32, this ctx has %d", ctx->int_bits);
+    return quantize_combine_cohort(ctx, "flashe_quantize_combine_cohort_u32_dev", 4, n_clients, n, n, nullptr, layers, n_layers, src_dev, src_dtype, element_bits, 0,
+                                   u_dev, reinterpret_cast<const void *const *>(mask_dev), reinterpret_cast<void *const *>(ct_dev), sum_out_dev);
+}
+
+// the BATCHED job over its n_elems elements (any bs = int_bits / field_bits >= 1)
+int flashe_quantize_batch_combine_cohort_dev(flashe_ctx *ctx, int n_clients, uint64_t n_values, uint64_t n_elems, const flashe_tensor_layer *layers, int n_layers,
+                                             const void *const *src_dev, const int32_t *src_dtype, int element_bits, int field_bits, const double *u_dev,
+                                             const uint64_t *const *mask_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev)
+{
+    CHECK_CTX(ctx);
+    return quantize_combine_cohort(ctx, "flashe_quantize_batch_combine_cohort_dev", ctx->limbs == 2 ? 16 : 8, n_clients, n_values, 0, &n_elems, layers, n_layers, src_dev,
+                                   src_dtype, element_bits, field_bits, u_dev, reinterpret_cast<const void *const *>(mask_dev), reinterpret_cast<void *const *>(ct_dev),
+                                   sum_out_dev);
+}
+
 int flashe_combine_unquantize_model_dev(flashe_ctx *ctx, uint64_t n, const uint64_t *in_dev, const uint64_t *add_dev, const uint64_t *minus_dev,
                                         const flashe_codec_layer *layers, int n_layers, int element_bits, int num_clients, double *out_dev)
 {

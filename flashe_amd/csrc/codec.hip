@@ -452,6 +452,230 @@ hipError_t launch_combine_unbatch_unquantize_model(const LaunchEnv &env, const B
     return hipGetLastError();
 }
 
+// ---- a COHORT's online step with masks the caller holds (flashe_quantize_combine_cohort*_dev): C float models + C precomputed masks ->
+// C ciphertexts + their sum in ONE memory-bound pass, no AES, no integer plaintext in HBM.  E = the element type of masks, ciphertexts
+// and sum: uint32_t (compact layout), uint64_t (one limb) or u128 (two limbs).
+// Un-batched: a lane owns FOUR consecutive values.  Where they lie inside one layer -- all but the few runs across a layer boundary and
+// the model's tail -- every stream is read and written in 16-byte accesses at the element's own alignment (layer starts are arbitrary):
+// four float32 or two float64, two draws, four uint32 / two uint64 / one 128-bit element; masks and draws are non-temporal loads, the
+// ciphertexts non-temporal stores.  The clients are walked G at a time (3 G streams in flight per lane, the running sum in registers):
+// fewer streams at once stream faster (NOTES section 4); G is kPrepCohortGroup.
+template <class E> __device__ __forceinline__ E prep_ld(const void *p, uint64_t k)
+{
+    if constexpr (sizeof(E) == 16) return ld128_nt_g(static_cast<const uint64_t *>(p) + 2 * k);
+    else return __builtin_nontemporal_load(FLASHE_GLOBAL(const E, static_cast<const E *>(p) + k));
+}
+template <class E> __device__ __forceinline__ void prep_st(void *p, uint64_t k, E v)
+{
+    if constexpr (sizeof(E) == 16) st128_nt_g(static_cast<uint64_t *>(p) + 2 * k, v);
+    else __builtin_nontemporal_store(v, FLASHE_GLOBAL(E, static_cast<E *>(p) + k));
+}
+__device__ __forceinline__ void prep_ld4(const void *p, uint64_t k, uint32_t (&v)[4])
+{
+    const cohort_u32x4 x = __builtin_nontemporal_load(FLASHE_GLOBAL(const cohort_u32x4, static_cast<const uint32_t *>(p) + k));
+    v[0] = x[0]; v[1] = x[1]; v[2] = x[2]; v[3] = x[3];
+}
+__device__ __forceinline__ void prep_ld4(const void *p, uint64_t k, uint64_t (&v)[4])
+{
+    const cohort_u64x2 a = __builtin_nontemporal_load(FLASHE_GLOBAL(const cohort_u64x2, static_cast<const uint64_t *>(p) + k));
+    const cohort_u64x2 b = __builtin_nontemporal_load(FLASHE_GLOBAL(const cohort_u64x2, static_cast<const uint64_t *>(p) + k + 2));
+    v[0] = a[0]; v[1] = a[1]; v[2] = b[0]; v[3] = b[1];
+}
+__device__ __forceinline__ void prep_ld4(const void *p, uint64_t k, u128 (&v)[4])
+{
+#pragma unroll
+    for (int t = 0; t < 4; t++) v[t] = ld128_nt_g(static_cast<const uint64_t *>(p) + 2 * (k + t));
+}
+__device__ __forceinline__ void prep_st4(void *p, uint64_t k, const uint32_t (&v)[4])
+{
+    const cohort_u32x4 x = {v[0], v[1], v[2], v[3]};
+    __builtin_nontemporal_store(x, FLASHE_GLOBAL(cohort_u32x4, static_cast<uint32_t *>(p) + k));
+}
+__device__ __forceinline__ void prep_st4(void *p, uint64_t k, const uint64_t (&v)[4])
+{
+    const cohort_u64x2 a = {v[0], v[1]}, b = {v[2], v[3]};
+    __builtin_nontemporal_store(a, FLASHE_GLOBAL(cohort_u64x2, static_cast<uint64_t *>(p) + k));
+    __builtin_nontemporal_store(b, FLASHE_GLOBAL(cohort_u64x2, static_cast<uint64_t *>(p) + k + 2));
+}
+__device__ __forceinline__ void prep_st4(void *p, uint64_t k, const u128 (&v)[4])
+{
+#pragma unroll
+    for (int t = 0; t < 4; t++) st128_nt_g(static_cast<uint64_t *>(p) + 2 * (k + t), v[t]);
+}
+// the float bits of four values of a row: one 16-byte access (float32) or two (float64)
+__device__ __forceinline__ void prep_src4(const void *x, bool f64, uint64_t r, uint64_t (&raw)[4])
+{
+    if (f64) {
+        const cohort_u64x2 a = *FLASHE_GLOBAL(const cohort_u64x2, static_cast<const uint64_t *>(x) + r);
+        const cohort_u64x2 b = *FLASHE_GLOBAL(const cohort_u64x2, static_cast<const uint64_t *>(x) + r + 2);
+        raw[0] = a[0]; raw[1] = a[1]; raw[2] = b[0]; raw[3] = b[1];
+    } else {
+        const cohort_u32x4 a = *FLASHE_GLOBAL(const cohort_u32x4, static_cast<const uint32_t *>(x) + r);
+        raw[0] = a[0]; raw[1] = a[1]; raw[2] = a[2]; raw[3] = a[3];
+    }
+}
+
+// clients c .. c + G - 1 over the four values k0 .. k0 + 3 of table row `row` (r = k0 - the row's start)
+template <class E, int G>
+__device__ __forceinline__ void prep_cohort_run(const PrepCohort &pc, int row, bool f64, double p0, double p1, double p2, int c, uint64_t k0, uint64_t r,
+                                                E modmask, E (&sum)[4])
+{
+    uint64_t raw[G][4], ub[G][4];
+    E mk[G][4];
+#pragma unroll
+    for (int i = 0; i < G; i++) {
+        prep_src4(pc.src[static_cast<size_t>(c + i) * pc.n_layers + row], f64, r, raw[i]);
+        prep_ld4(pc.u, static_cast<uint64_t>(c + i) * pc.n_values + k0, ub[i]);
+        prep_ld4(pc.mask[c + i], k0, mk[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < G; i++) {
+        E v[4];
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            v[t] = (static_cast<E>(cohort_quantize_raw(raw[i][t], f64, p0, p1, p2, __longlong_as_double(static_cast<long long>(ub[i][t])))) + mk[i][t]) & modmask;
+            sum[t] += v[t];
+        }
+        prep_st4(pc.ct[c + i], k0, v);
+    }
+}
+
+template <class E, int G>
+__global__ __launch_bounds__(kStreamThreads) void quantize_combine_cohort_kernel(const PrepCohort pc, E modmask)
+{
+    const uint64_t n = pc.n, runs = (n + 3) / 4;
+    const int C = pc.n_clients;
+    for (uint64_t g = static_cast<uint64_t>(blockIdx.x) * kStreamThreads + threadIdx.x; g < runs; g += static_cast<uint64_t>(gridDim.x) * kStreamThreads) {
+        const uint64_t k0 = 4 * g;
+        int lo = 0, hi = pc.n_layers - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (pc.layers[mid].start <= k0) lo = mid; else hi = mid - 1;
+        }
+        const uint64_t end = lo + 1 < pc.n_layers ? pc.layers[lo + 1].start : n;
+        if (k0 + 4 <= end) {
+            const CodecLayer *L = pc.layers + lo;
+            const bool f64 = L->x_is_f64 != 0;
+            const double p0 = L->p0, p1 = L->p1, p2 = L->p2;
+            const uint64_t r = k0 - L->start;
+            E sum[4] = {0, 0, 0, 0};
+            int c = 0;
+            for (; c + G <= C; c += G) prep_cohort_run<E, G>(pc, lo, f64, p0, p1, p2, c, k0, r, modmask, sum);
+            for (; c < C; c++) prep_cohort_run<E, 1>(pc, lo, f64, p0, p1, p2, c, k0, r, modmask, sum);
+            if (pc.sum) {
+#pragma unroll
+                for (int t = 0; t < 4; t++) sum[t] &= modmask;
+                prep_st4(pc.sum, k0, sum);
+            }
+            continue;
+        }
+        // a run across a layer boundary, or the model's tail: value by value (the rows hold no empty layer: starts ascend strictly)
+        const uint64_t kend = k0 + 4 < n ? k0 + 4 : n;
+        for (uint64_t k = k0; k < kend; k++) {
+            while (lo + 1 < pc.n_layers && pc.layers[lo + 1].start <= k) lo++;
+            const CodecLayer *L = pc.layers + lo;
+            const bool f64 = L->x_is_f64 != 0;
+            E sum = 0;
+            for (int c = 0; c < C; c++) {
+                const double u = __longlong_as_double(static_cast<long long>(ld64_nt_g(reinterpret_cast<const uint64_t *>(pc.u) + static_cast<uint64_t>(c) * pc.n_values + k)));
+                const uint64_t q = cohort_quantize_raw(cohort_load(pc.src[static_cast<size_t>(c) * pc.n_layers + lo], f64, k - L->start), f64, L->p0, L->p1, L->p2, u);
+                const E v = (static_cast<E>(q) + prep_ld<E>(pc.mask[c], k)) & modmask;
+                prep_st<E>(pc.ct[c], k, v);
+                sum += v;
+            }
+            if (pc.sum) prep_st<E>(pc.sum, k, sum & modmask);
+        }
+    }
+}
+
+// The batched job: a lane owns one batched element of every client -- quantize_batch_model_kernel's plaintext (every layer padded to whole
+// elements on its own, the first value most significant; a whole element reads its floats and draws in 16-byte runs where BS is compiled
+// in, 5 / 6 / 7; BS = 0: any bs, value by value) -- plus the client's mask.  pc.n counts elements, pc.rows[2 r], pc.rows[2 r + 1] = row
+// r's first element and its value count, layers[r].start = its first value.
+template <class E, int G, int BS>
+__device__ __forceinline__ void prep_batch_run(const PrepCohort &pc, int row, bool f64, double p0, double p1, double p2, uint64_t vstart, uint64_t j0,
+                                               uint64_t size, int c, uint64_t e, E modmask, E &sum)
+{
+    u128 x[G];
+    E mk[G];
+#pragma unroll
+    for (int i = 0; i < G; i++) {
+        const void *xs = pc.src[static_cast<size_t>(c + i) * pc.n_layers + row];
+        const double *ud = pc.u + static_cast<uint64_t>(c + i) * pc.n_values + vstart;
+        mk[i] = prep_ld<E>(pc.mask[c + i], e);
+        if constexpr (BS != 0) x[i] = cohort_batch_element<BS>(xs, f64, p0, p1, p2, ud, j0, size, pc.field_bits);
+        else x[i] = cohort_batch_walk<0>(xs, f64, p0, p1, p2, ud, j0, size, pc.field_bits, pc.bs);
+    }
+#pragma unroll
+    for (int i = 0; i < G; i++) {
+        const E v = (static_cast<E>(x[i]) + mk[i]) & modmask;
+        prep_st<E>(pc.ct[c + i], e, v);
+        sum += v;
+    }
+}
+
+template <class E, int G, int BS>
+__global__ __launch_bounds__(kStreamThreads) void quantize_batch_combine_cohort_kernel(const PrepCohort pc, E modmask)
+{
+    const int C = pc.n_clients;
+    for (uint64_t e = static_cast<uint64_t>(blockIdx.x) * kStreamThreads + threadIdx.x; e < pc.n; e += static_cast<uint64_t>(gridDim.x) * kStreamThreads) {
+        int lo = 0, hi = pc.n_layers - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (pc.rows[2 * mid] <= e) lo = mid; else hi = mid - 1;
+        }
+        const CodecLayer *L = pc.layers + lo;
+        const bool f64 = L->x_is_f64 != 0;
+        const double p0 = L->p0, p1 = L->p1, p2 = L->p2;
+        const uint64_t vstart = L->start, size = pc.rows[2 * lo + 1], j0 = (e - pc.rows[2 * lo]) * static_cast<uint64_t>(BS ? BS : pc.bs);
+        E sum = 0;
+        int c = 0;
+        for (; c + G <= C; c += G) prep_batch_run<E, G, BS>(pc, lo, f64, p0, p1, p2, vstart, j0, size, c, e, modmask, sum);
+        for (; c < C; c++) prep_batch_run<E, 1, BS>(pc, lo, f64, p0, p1, p2, vstart, j0, size, c, e, modmask, sum);
+        if (pc.sum) prep_st<E>(pc.sum, e, sum & modmask);
+    }
+}
+
+// clients per group of the kernels above.  NOT MEASURED yet: 2 is the largest group at which every instantiation stays within 128 VGPRs
+// (4 takes up to 178).  tests/perf/prepared_cohort_step.py alternates 1 / 2 / 4 in one process on the tuning build; no log of it exists.
+constexpr int kPrepCohortGroup = 2;
+
+template <class E> static hipError_t launch_prep_cohort(const LaunchEnv &env, const PrepCohort &pc, bool batched, int group, E modmask)
+{
+    const dim3 g(stream_grid(env, batched ? pc.n : (pc.n + 3) / 4)), t(kStreamThreads);
+#define FLASHE_PREP_LAUNCH(G)                                                                                                                  \
+    do {                                                                                                                                       \
+        if (!batched) hipLaunchKernelGGL((quantize_combine_cohort_kernel<E, G>), g, t, 0, env.stream, pc, modmask);                             \
+        else if constexpr (sizeof(E) == 4) return hipErrorInvalidValue;                                                                        \
+        else if (pc.bs == 5) hipLaunchKernelGGL((quantize_batch_combine_cohort_kernel<E, G, 5>), g, t, 0, env.stream, pc, modmask);            \
+        else if (pc.bs == 6) hipLaunchKernelGGL((quantize_batch_combine_cohort_kernel<E, G, 6>), g, t, 0, env.stream, pc, modmask);            \
+        else if (pc.bs == 7) hipLaunchKernelGGL((quantize_batch_combine_cohort_kernel<E, G, 7>), g, t, 0, env.stream, pc, modmask);            \
+        else hipLaunchKernelGGL((quantize_batch_combine_cohort_kernel<E, G, 0>), g, t, 0, env.stream, pc, modmask);                            \
+    } while (0)
+#ifdef FLASHE_TUNING
+    if (group == 1) FLASHE_PREP_LAUNCH(1);           // (the alternatives of the A/B ride in the tuning build only)
+    else if (group == 4) FLASHE_PREP_LAUNCH(4);
+    else
+#endif
+    FLASHE_PREP_LAUNCH(kPrepCohortGroup);
+#undef FLASHE_PREP_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t launch_quantize_combine_cohort(const LaunchEnv &env, const PrepCohort &pc, int elem_bytes, bool batched)
+{
+    if (pc.n == 0 || pc.n_clients == 0) return hipSuccess;
+    if (pc.n_layers < 1 || (batched && (pc.bs < 1 || pc.field_bits < 1 || pc.field_bits > env.b))) return hipErrorInvalidValue;
+    int group = kPrepCohortGroup;
+    if (const char *e = FLASHE_TUNE_ENV("FLASHE_PREP_COHORT_GROUP")) group = atoi(e);      // (read per call: an in-process A/B alternates it)
+    uint64_t lo, hi;
+    masks_of(env.b, &lo, &hi);
+    if (elem_bytes == 4) return env.b > 32 ? hipErrorInvalidValue : launch_prep_cohort<uint32_t>(env, pc, batched, group, static_cast<uint32_t>(lo));
+    if (elem_bytes == 8) return env.b > 64 ? hipErrorInvalidValue : launch_prep_cohort<uint64_t>(env, pc, batched, group, lo);
+    if (elem_bytes == 16) return env.b <= 64 ? hipErrorInvalidValue : launch_prep_cohort<u128>(env, pc, batched, group, (static_cast<u128>(hi) << 64) | lo);
+    return hipErrorInvalidValue;
+}
+
 hipError_t launch_batch(const LaunchEnv &env, uint64_t n, const uint64_t *vals_dev, int field_bits, uint64_t *out_dev)
 {
     const int bs = env.b / field_bits;

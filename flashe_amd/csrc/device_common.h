@@ -545,17 +545,21 @@ __device__ __forceinline__ int cohort_batch_row_of(const CohortBatch &cb, int n_
 // quantize_batch_model_kernel's arithmetic.
 // The walking form, value by value in a rolled loop (a handful of registers): the row's last element when it has pads, and every element
 // whose row is looked up per lane.
+// (BS = 0: the values per element are `bs`, known at run time only, and may be one field of 128 bits)
 template <int BS>
 __device__ __forceinline__ u128 cohort_batch_walk(const void *xs, bool f64, double p0, double p1, double p2, const double *ud, uint64_t j0,
-                                                  uint64_t size, int field_bits)
+                                                  uint64_t size, int field_bits, int bs = BS)
 {
+    const int count = BS ? BS : bs;
     u128 x = 0;
 #pragma unroll 1
-    for (int t = 0; t < BS; t++) {
+    for (int t = 0; t < count; t++) {
         const uint64_t j = j0 + t;
         uint64_t q = 0;
         if (j < size) q = cohort_quantize_raw(cohort_load(xs, f64, j), f64, p0, p1, p2, *FLASHE_GLOBAL(const double, ud + j));
-        x = (x << field_bits) + q;                                                                       // temp *= mod; temp += value
+        if constexpr (BS == 0) x = field_bits >= 128 ? static_cast<u128>(0) : x << field_bits;
+        else x <<= field_bits;
+        x += q;                                                                                          // temp *= mod; temp += value
     }
     return x;
 }

@@ -326,6 +326,24 @@ hipError_t launch_quantize_batch_combine_model(const LaunchEnv &env, const Batch
                                                uint64_t n_elems, const uint64_t *add_dev, const uint64_t *minus_dev, uint64_t *ct_dev);
 hipError_t launch_combine_unbatch_unquantize_model(const LaunchEnv &env, const BatchLayer *layers_dev, int n_layers, int field_bits, const uint64_t *in_dev,
                                                    const uint64_t *add_dev, const uint64_t *minus_dev, uint64_t n_values, double *out_dev);
+// A COHORT's online step with masks the caller holds (codec.hip): ct[c][k] = (plaintext of client c's element k + mask[c][k]) mod 2^b
+// for every client and sum[k] = sum_c ct[c][k] mod 2^b, in one pass with no AES.  layers / src: CohortCodec's tables (n_layers rows);
+// mask / ct: DEVICE tables of the n_clients vectors, so one launch takes any number of clients; sum may be null.  Un-batched: n values,
+// plaintext = the quantisation with the draw u[c * n_values + k] (n_values = n).  Batched: n elements of bs values in fields of
+// field_bits, plaintext = quantize_batch_model_kernel's with the draws u[c * n_values + value index]; rows as CohortBatch's.
+struct PrepCohort {
+    const CodecLayer *layers;
+    const void *const *src;
+    const void *const *mask;
+    void *const *ct;
+    const uint64_t *rows;
+    const double *u;
+    void *sum;
+    uint64_t n, n_values;
+    int n_layers, n_clients, field_bits, bs;
+};
+// elem_bytes = what masks, ciphertexts and sum are made of: 4 (uint32, int_bits <= 32, un-batched), 8 (one limb, int_bits <= 64) or 16
+hipError_t launch_quantize_combine_cohort(const LaunchEnv &env, const PrepCohort &pc, int elem_bytes, bool batched);
 hipError_t launch_unbatch(const LaunchEnv &env, uint64_t nb, const uint64_t *in_dev, int field_bits, uint64_t *out_dev);
 
 // Caller-owned tensors either side of the model-wide codec (tensors.hip).  dtype / flags as in flashe_tensor_layer (include/flashe.h);

@@ -76,4 +76,15 @@ struct StageSlots {
     }
 };
 
+// The block the prepared cohort launches upload behind cohort_stage's tables (8-byte words): the n_clients mask pointers, the n_clients
+// ciphertext pointers, then two words per batched row.  Byte offsets inside the block, and its words for n_rows batched rows.
+struct PreparedBlock { size_t mask, ct, rows, words; };
+inline PreparedBlock prepared_block(int n_clients, size_t n_rows = 0)
+{
+    const size_t c = static_cast<size_t>(n_clients);
+    return PreparedBlock{0, c * 8, 2 * c * 8, 2 * c + 2 * n_rows};
+}
+// entries of a cohort's n_clients x n_layers source table
+inline size_t cohort_sources(int n_clients, int n_layers) { return static_cast<size_t>(n_clients) * static_cast<size_t>(n_layers); }
+
 }  // namespace flashe_tables

@@ -675,6 +675,39 @@ class Engine:
         self._check(rc)
         return True
 
+    def cohort_masks_dev(self, it, first_idx, n_clients, n, n_jobs, masks, compact=False):
+        """A cohort's precomputed encrypt masks as ONE chain of n_clients + 1 streams into the caller's vectors:
+        masks[c][j] = term(it, first_idx + c)[j] - term(it, first_idx + c + 1)[j] mod 2^b.  Limb layout (n x L limbs each): n_clients linked
+        jobs without an input through prf_jobs_dev; compact=True (int_bits <= 32, uint32 vectors): flashe_cohort_masks_u32_dev."""
+        if compact:
+            pm, _k = self._ptr_array(masks)
+            self._check(self._lib.flashe_cohort_masks_u32_dev(self._h, it, int(first_idx), int(n_clients), int(n), n_jobs, pm))
+        elif n and n_clients:
+            self.prf_jobs_dev(it, n, n_jobs, [(int(first_idx) + c, int(first_idx) + c + 1, 0, n, None, 0, self._ptr(masks[c])) for c in range(n_clients)])
+
+    def quantize_combine_cohort_dev(self, n, layers, srcs, dtypes, element_bits, u, masks, cts, sum_out, compact=False, batch=None):
+        """A precompute cohort's ONLINE step in one pass, no AES (flashe_quantize_combine_cohort_dev; compact=True: _u32_dev on uint32
+        vectors; batch=(n_elems, field_bits): flashe_quantize_batch_combine_cohort_dev over the batched elements): cts[c] = (client c's
+        plaintext + masks[c]) mod 2^b and sum_out (optional) = their sum.  layers / srcs / dtypes / u as quantize_encrypt_cohort_dev.
+        Returns False -- nothing was launched -- when the library declines (FLASHE_ENOTSUP), True otherwise."""
+        arr, nl = self._tensor_layers(layers)
+        C = len(srcs)
+        ps = (c_vp * max(C * nl, 1))(*[int(p) if p else None for row in srcs for p in row])
+        pd = (ctypes.c_int32 * max(C * nl, 1))(*[int(d) for row in dtypes for d in row])
+        pm, _a = self._ptr_array(masks)
+        pc, _b = self._ptr_array(cts)
+        if batch is not None:
+            n_elems, field_bits = batch
+            rc = self._lib.flashe_quantize_batch_combine_cohort_dev(self._h, C, int(n), int(n_elems), arr, nl, ps, pd, element_bits, int(field_bits),
+                                                                    self._ptr(u), pm, pc, self._ptr(sum_out))
+        else:
+            fn = self._lib.flashe_quantize_combine_cohort_u32_dev if compact else self._lib.flashe_quantize_combine_cohort_dev
+            rc = fn(self._h, C, int(n), arr, nl, ps, pd, element_bits, self._ptr(u), pm, pc, self._ptr(sum_out))
+        if rc == _lib.ENOTSUP:
+            return False
+        self._check(rc)
+        return True
+
     def combine_unbatch_unquantize_model_dev(self, layers, element_bits, field_bits, num_clients, inp, add, minus, n_elems, out):
         """unbatch_unquantize_model_dev over (inp + add - minus) mod 2^b, one memory-bound pass (add / minus: device vectors of n_elems
         elements or None); layers as for unbatch_unquantize_model_dev."""

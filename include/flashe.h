@@ -76,7 +76,10 @@ typedef struct flashe_ctx flashe_ctx;
  *      clients: C models sparsified in one set of launches, their compact layers quantised in one launch);
  *      flashe_quantize_encrypt_cohort_u32_dev (the cohort's chained launch in the compact layout, int_bits 16 / 20 / 23 / 24 / 32);
  *      flashe_quantize_batch_encrypt_cohort_dev (the cohort's chained launch for a batched job at int_bits > 64, 5 - 7 values per
- *      element) and flashe_combine_unbatch_unquantize_model_dev (the batched codec back end over a sum and caller-held masks) */
+ *      element) and flashe_combine_unbatch_unquantize_model_dev (the batched codec back end over a sum and caller-held masks);
+ *      flashe_cohort_masks_u32_dev (a cohort's precomputed encrypt masks in the compact layout, one chain of C + 1 streams) and
+ *      flashe_quantize_combine_cohort_dev / flashe_quantize_combine_cohort_u32_dev / flashe_quantize_batch_combine_cohort_dev (a
+ *      precompute job's cohort online: C float models + C caller-held masks to C ciphertexts and their sum in one pass, no AES) */
 #define FLASHE_ABI_VERSION 4
 int flashe_abi_version(void);
 int flashe_device_count(int *count);
@@ -700,6 +703,40 @@ int flashe_quantize_batch_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uin
                                              uint32_t n_jobs, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
                                              const int32_t *src_dtype, int element_bits, int field_bits, const double *u_dev, uint64_t *const *ct_dev,
                                              uint64_t *sum_out_dev, uint64_t *dmask_dev);
+/* A precompute job's cohort (new), jzf_flashe.py:599-631, 456-488: every client computes its next round's encrypt mask in idle time and
+ * its online step is a quantise plus a mask add.  For a cohort the masks are ONE chain of n_clients + 1 streams into vectors the caller
+ * owns, mask[c][j] = term(iter, first_idx + c)[j] - term(iter, first_idx + c + 1)[j] mod 2^b: in the limb layout
+ * flashe_prf_jobs_dev with n_clients linked jobs (in_dev = NULL, minus_idx[e] = add_idx[e + 1]); in the compact layout
+ * flashe_cohort_masks_u32_dev (uint32 vectors of n elements, 4-byte aligned; check_u32's conditions -- FLASHE_EINVAL at int_bits > 32,
+ * n >= 2^32, n_jobs = 0, another PRF backend or FLASHE_CHAIN=0 --, every int_bits <= 32, up to 128 vectors per launch).  The ctx's own
+ * precompute caches (flashe_prepare_*, flashe_prepared_query / _discard) are not touched. */
+int flashe_cohort_masks_u32_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                uint32_t *const *mask_dev);
+/* The cohort's ONLINE step with those masks (new): ONE memory-bound pass, no AES, writes
+ *   ct_dev[c][k] = (quantize(x_c[k], u_dev[c * n + k]) + mask_dev[c][k]) mod 2^b   and   sum_out_dev[k] = sum_c ct_dev[c][k] mod 2^b
+ * for the n values of every client (n x L limbs per vector); with the chain's masks ct_dev[c] is bit for bit the double-mask
+ * flashe_quantize_encrypt_tensors_dev of client c.  No integer plaintext exists in HBM.  layers, src_dev, src_dtype, LOOP_F64 / SHIFT /
+ * SHIFT_WIDE, the stage pass for sources not in their row's compute type and the argument checks are those of
+ * flashe_quantize_encrypt_cohort_dev (a float64 source under a float32 row, a misaligned or missing vector: FLASHE_EINVAL).  Any
+ * int_bits, any n (n = 0: FLASHE_OK, nothing launched), any n_clients >= 1 in one launch (the vector pointers travel in a device
+ * table).  sum_out_dev may be NULL; it must not be a mask, a ciphertext or a source (FLASHE_EINVAL).  mask_dev[c] and ct_dev[c] of
+ * different clients must not overlap.  The table uploads synchronise; not capturable. */
+int flashe_quantize_combine_cohort_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers,
+                                       const void *const *src_dev, const int32_t *src_dtype, int element_bits, const double *u_dev,
+                                       const uint64_t *const *mask_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev);
+/* The same in the compact layout (new): uint32 masks, ciphertexts and sum (4-byte aligned) at ANY int_bits <= 32 -- there is no AES
+ * here, so the widths compiled into the compact chains do not matter.  FLASHE_EINVAL at int_bits > 32; FLASHE_ENOTSUP -- nothing
+ * launched -- on a ctx whose flashe_ctx_compact_layout is 0. */
+int flashe_quantize_combine_cohort_u32_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers,
+                                           const void *const *src_dev, const int32_t *src_dtype, int element_bits, const double *u_dev,
+                                           const uint32_t *const *mask_dev, uint32_t *const *ct_dev, uint32_t *sum_out_dev);
+/* The same for a BATCHED job (new) over its n_elems = sum_l ceil(size_l / bs) elements, bs = int_bits / field_bits >= 1 (any: the
+ * 5 / 6 / 7 of the chained launch does not apply; those three read whole elements in 16-byte runs): client c's plaintext of element e
+ * is flashe_quantize_batch_tensors_dev's with the draws u_dev[c * n_values + value index].  FLASHE_EINVAL when n_elems is not what the
+ * layers batch into. */
+int flashe_quantize_batch_combine_cohort_dev(flashe_ctx *ctx, int n_clients, uint64_t n_values, uint64_t n_elems, const flashe_tensor_layer *layers,
+                                             int n_layers, const void *const *src_dev, const int32_t *src_dtype, int element_bits, int field_bits,
+                                             const double *u_dev, const uint64_t *const *mask_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev);
 /* The codec back end over caller-held vectors (new), jzf_quantize.py:102-107: out[k] = unquantize((in[k] + add[k] - minus[k]) mod 2^b)
  * as float64 for the n elements of a flattened model, one memory-bound pass; add_dev / minus_dev may be NULL (zeros).  With in = a
  * cohort's sum and add = its decrypt mask this is the cohort's decrypt_unquantize. */
