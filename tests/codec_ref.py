@@ -17,6 +17,10 @@ Two rules keep a case out of the plane, both because the reference itself is pla
 Everything else stays: +-0, +-alpha and their neighbours, +-inf, subnormals, the dtype's extremes, values whose scaled image is an
 integer or one ulp off it, every width from 1 to 62 bits.  A case the rules drop is dropped when the plane is built, and the plane says how
 many it kept, so a test can hold a floor against an over-eager filter.
+
+The last section builds whole cohorts for the fused cohort launches (cohort_model and what hangs off it): C clients' models of rows in
+every storage format, filled by layer_fill, with the plaintexts the reference quantises them to -- q == 2^bits and 2^bits + 1 kept as they
+are -- and the batched elements, in which such a q carries out of a field that is exactly element_bits wide.
 """
 from fractions import Fraction
 
@@ -287,3 +291,96 @@ def sum_plane(bits, C, int_bits=128, n_random=3000, seed=0):
         v = int.from_bytes(rng.bytes(16), "little") >> (128 - nb)
         pts.append(v | (1 << (nb - 1)))
     return [p for p in pts if 0 <= p < (1 << int_bits)]
+
+
+# ---------------------------------------------------------------------------------------------------------------- cohort models
+F32, F64, F16, BF16 = 0, 1, 2, 3                                        # flashe_tensor_layer dtype codes (include/flashe.h)
+SHIFT, SHIFT_WIDE, LOOP_F64 = 1, 2, 4                                   # and flags
+_STORAGE = {"float32": F32, "float64": F64, "float16": F16, "bfloat16": BF16}
+
+
+def bits16(x32, storage):
+    """The 16-bit patterns of float32 values the format holds exactly."""
+    if storage == "float16":
+        return x32.astype(np.float16).view(np.uint16)
+    assert storage == "bfloat16"
+    return (np.ascontiguousarray(x32).view(np.uint32) >> np.uint32(16)).astype(np.uint16)
+
+
+class CohortModel:
+    """What cohort_model returns: spec, C, sizes, starts, n; rows = the shared table (start, None, alpha, shift, compute dtype code, flags);
+    dts[l] = layer l's storage dtype code; storage[c][l] = what client c holds in memory (float arrays, uint16 patterns for the 16-bit
+    formats); ref[c][l] = the compute-type array the codec quantises (upcast, shifted, widened); u = mixed_draws(C * n), client-major."""
+
+
+def cohort_model(spec, C, seed=0):
+    """A cohort's model from rows of (storage, alpha, shift, wide, loop64, size): every client's every row is layer_fill's (an edge value
+    either side of every row boundary), the draws are mixed_draws."""
+    m = CohortModel()
+    m.spec, m.C = list(spec), C
+    m.sizes = [s[5] for s in m.spec]
+    m.starts = [int(v) for v in np.concatenate([[0], np.cumsum(m.sizes)[:-1]])]
+    m.n = int(sum(m.sizes))
+    m.rows, m.dts = [], []
+    for (storage, alpha, shift, wide, loop64, _size), start in zip(m.spec, m.starts):
+        flags = (SHIFT if shift is not None else 0) | (SHIFT_WIDE if shift is not None and wide else 0) | (LOOP_F64 if loop64 else 0)
+        m.rows.append((start, None, alpha, 0.0 if shift is None else shift, F64 if storage == "float64" else F32, flags))
+        m.dts.append(_STORAGE[storage])
+    m.storage, m.ref = [], []
+    for c in range(C):
+        held, ref = [], []
+        for li, (storage, alpha, shift, wide, loop64, size) in enumerate(m.spec):
+            half = storage in ("float16", "bfloat16")
+            x = layer_fill(np.float64 if storage == "float64" else np.float32, alpha, size, seed + 10 * c + li, storage=storage if half else None)
+            held.append(bits16(x, storage) if half else x.copy())
+            if shift is not None:
+                x = ref_shift(x, np.float64(shift) if wide else float(shift))
+            if loop64:
+                x = x.astype(np.float64)
+            ref.append(x)
+        m.storage.append(held)
+        m.ref.append(ref)
+    m.u = mixed_draws(C * m.n, seed)
+    return m
+
+
+def _cohort_rows_q(model, bits, c):
+    u = model.u[c * model.n:(c + 1) * model.n]
+    return [ref_quantize(x, row[2], bits, u[at:at + len(x)]) for x, row, at in zip(model.ref[c], model.rows, model.starts)]
+
+
+def cohort_plaintexts(model, bits):
+    """Per client the concatenated ref_quantize of its rows as int64 (bits <= 62: Python-int safe); 2^bits and 2^bits + 1 are kept."""
+    return [np.concatenate(_cohort_rows_q(model, bits, c) + [np.zeros(0, np.int64)]) for c in range(model.C)]
+
+
+def cohort_batched(model, bits, int_bits, field_bits):
+    """Per client the batched plaintext as Python ints: ref_batch of every row on its own (each padded to whole elements), reduced
+    mod 2^int_bits as the cipher reduces it."""
+    return [[t % (1 << int_bits) for q in _cohort_rows_q(model, bits, c) for t in ref_batch(q, int_bits, field_bits)] for c in range(model.C)]
+
+
+def cohort_field_overflows(model, bits, int_bits, field_bits):
+    """Where a quantised value does not fit its field: (client, row, element of the row, slot, the row's element count, the row's size)
+    for every q >= 2^field_bits.  Slot 0 is the most significant field; an overflow there carries out of bit bs * field_bits."""
+    bs, out = int_bits // field_bits, []
+    for c in range(model.C):
+        for li, q in enumerate(_cohort_rows_q(model, bits, c)):
+            for j in np.flatnonzero(q >= (1 << field_bits)):
+                out.append((c, li, int(j) // bs, int(j) % bs, -(-len(q) // bs), len(q)))
+    return out
+
+
+def check_cohort_case(model, bits):
+    """The conditions a cohort case meets on the reference alone: no row under overflows() (asserted, not filtered), every client holds a
+    q == 2^bits, and a case with a float32 compute row at bits >= 25 holds a q == 2^bits + 1 (float32 rounds the image 2^bits - 1 up to
+    2^bits there, and the float64 sum 2^bits + (1 - 2^-53) rounds to 2^bits + 1 -- while that integer is a float64 at all, bits <= 52;
+    beyond, the sum is 2^bits itself)."""
+    for x, row in zip(model.ref[0], model.rows):
+        assert not overflows(x.dtype, row[2], bits), (x.dtype, row[2], bits)
+    pts = cohort_plaintexts(model, bits)
+    for c, q in enumerate(pts):
+        assert (q == 1 << bits).any(), ("no q == 2^bits", c, bits)
+    if 25 <= bits <= 52 and any(x.dtype == np.float32 and len(x) for x in model.ref[0]):
+        assert any((q == (1 << bits) + 1).any() for q in pts), ("no q == 2^bits + 1", bits)
+    return pts

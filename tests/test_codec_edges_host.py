@@ -98,3 +98,60 @@ def test_ref_shift_and_16_bit_upcasts_are_numpy_and_torch():
     torch = pytest.importorskip("torch")
     b = R.edge_plane(np.float32, 1.0, n_fill=100, storage="bfloat16")
     assert (torch.from_numpy(b).to(torch.bfloat16).to(torch.float32).numpy() == b).all() and np.isfinite(b[:4]).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------- cohort cases
+def _round_trips(model, bits, b, fb):
+    """Per client and row: does ref_unbatch(ref_batch(q)) give q back?"""
+    out = []
+    for c in range(model.C):
+        u = model.u[c * model.n:(c + 1) * model.n]
+        for li, (x, row, at) in enumerate(zip(model.ref[c], model.rows, model.starts)):
+            q = [int(v) for v in R.ref_quantize(x, row[2], bits, u[at:at + len(x)])]
+            out.append((c, li, R.ref_unbatch(R.ref_batch(q, b, fb), b, fb)[:len(q)] == q))
+    return out
+
+
+def test_the_cohort_edge_cases_hold_their_conditions_on_the_reference_alone():
+    """Every case of tests/test_gpu_cohort_edges.py, built as the GPU tests build it: no row under overflows() (asserted inside
+    check_cohort_case, nothing filtered), a q == 2^bits for every client, a q == 2^bits + 1 wherever a float32 row is quantised to 25 bits
+    or more; the batched cases' carries (asserted inside batch_case), told apart by the round trip through ref_unbatch: it gives the
+    values back exactly for the rows in which no field overflowed."""
+    import test_gpu_cohort_edges as G
+    n_cases = 0
+    for b, bits in G.COMPACT:
+        for J in G.COMPACT_J:
+            model, pts = G.compact_case(b, bits, J)
+            assert model.n % 2 == 1 and all(s % 2 for s in model.sizes) and len(pts) == G.C == 3
+            if bits >= 25:
+                assert any((q == (1 << bits) + 1).any() for q in pts)
+            n_cases += 1
+    for cases, ne in ((G.BATCH_CHAIN, G.CHAIN_ELEMS), (G.BATCH_PREPARED, G.PREPARED_ELEMS)):
+        for b, fb, eb in cases:
+            model, pts, batched, over = G.batch_case(b, fb, eb, ne)
+            bs = b // fb
+            assert bs == 1 or ({s % bs for s in model.sizes} >= {0, 1, bs - 1} and 1 in model.sizes and 0 in model.sizes)
+            spoilt = {(c, li) for c, li, _e, _s, _ne, _size in over}
+            assert bool(spoilt) == (fb == eb)
+            for c, li, same in _round_trips(model, eb, b, fb):
+                assert same == ((c, li) not in spoilt), (b, fb, eb, c, li)
+            if fb == eb and bs * fb == b:
+                # the carry out of bit b is what the reduction mod 2^b drops: the unreduced element does not fit b bits
+                c, li, e, _s, _ne, _size = next(o for o in over if o[3] == 0)
+                u = model.u[c * model.n + model.starts[li]:c * model.n + model.starts[li] + model.sizes[li]]
+                q = R.ref_quantize(model.ref[c][li], model.rows[li][2], eb, u)
+                assert R.ref_batch(q, b, fb)[e] >> b == 1
+            n_cases += 1
+    for b, eb, shape in G.SPARSE:
+        model, pts, u, zzz, zeros, K, n_jobs = G.sparse_case(b, eb, shape)
+        assert model.n == K and len(u) == G.C * (K + 1) and zeros[1] == 1 << eb and zeros[2] == 0
+        n_cases += 1
+    for b, bits, _compact in G.PREPARED:
+        for n in (None, 4097, 4098, 4099) if (b, bits, _compact) in G.PREPARED_TYPES else (None,):
+            G.prepared_case(b, bits, n)
+            n_cases += 1
+    for case in G.BACK_END:
+        layers, items, want = G.back_end_case(*case)
+        assert len(want) == sum(l[0] for l in layers) and any(l[0] % (case[0] // case[1]) for l in layers)
+        n_cases += 1
+    assert n_cases == 12 + 5 + 8 + 18 + 7 + 9 + 2

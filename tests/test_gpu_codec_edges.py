@@ -37,11 +37,7 @@ def _limbs(q, L):
     return out
 
 
-def _bits16(x32, storage):
-    """The 16-bit patterns of float32 values the format holds exactly."""
-    if storage == "float16":
-        return x32.astype(np.float16).view(np.uint16)
-    return (np.ascontiguousarray(x32).view(np.uint32) >> np.uint32(16)).astype(np.uint16)
+_bits16 = R.bits16
 
 
 # ------------------------------------------------------------------------------------------------ plain quantise / unquantise
@@ -190,7 +186,8 @@ def test_model_tables_pick_each_layers_alpha_and_dtype(E, oracle, b, scheme, bit
 
 
 # ------------------------------------------------------------------------------------------------ batched
-BATCHED = [(128, 20, 16, 10), (120, 20, 16, 10), (64, 17, 16, 2), (100, 33, 32, 2), (64, 64, 62, 4)]      # int_bits, field_bits, element_bits, C
+# int_bits, field_bits, element_bits, C; the last two: field_bits == element_bits, where q == 2^bits carries into the neighbouring field
+BATCHED = [(128, 20, 16, 10), (120, 20, 16, 10), (64, 17, 16, 2), (100, 33, 32, 2), (64, 64, 62, 4), (120, 24, 24, 1), (128, 25, 25, 1)]
 
 
 def _batched_ref(layers, u, b, fb, eb):
@@ -208,7 +205,7 @@ def test_batched_model_both_ways(E, b, fb, eb, C):
     layers, n, u = _model(eng, seed=fb)
     assert any(len(x) % bs for x, _a, _s, _d in layers) or bs == 1
     want = _batched_ref(layers, u, b, fb, eb)
-    if eb == 32:
+    if eb == 32 or fb == eb:
         assert any((R.ref_quantize(x, a, eb, u[s:s + len(x)]) == 1 << eb).any() for x, a, s, _d in layers), "q == 2^bits inside a padded field"
     ne = len(want)
     table = [(len(x), d.ptr, alpha, x.dtype == np.float64) for x, alpha, _at, d in layers]
