@@ -4,12 +4,14 @@ the arbiter's `dynamic_masking` cost model (:89-117).  Key exchange, uuid sync a
 transfer variables of the reference classes are control plane and are not reproduced; the PRP seed
 is handed in directly.
 """
+import math
 import os
 
 import numpy as np
 
+from . import _lib, interop
 from .cipher import FlasheCipher, _CtxMask
-from .quantize import QuantizingClient
+from .quantize import ACIQ, QuantizingClient, _loop_dtype
 
 _RNG_RUN_MAX = 1 << 26          # draws per device call of quantize_encrypt (512 MiB of float64)
 
@@ -86,6 +88,112 @@ def aggregate_sparse_uploads(engine, uploads, locations, total, device=True):
     if total:
         engine.sparse_aggregate_dev(int(total), locs, ks, vals, zeros, out.buf, sorted_lists=sorted_all)
     return out.mark_ready() if device else out.to_host()
+
+
+# ---- the client step's front-end rules, each stated once (FlasheClient's tensor step and both cohorts) ---------------------------------
+_F32, _F64 = np.dtype(np.float32), np.dtype(np.float64)
+_TENSOR_CODES = {"float32": _lib.TENSOR_F32, "float64": _lib.TENSOR_F64, "float16": _lib.TENSOR_F16, "bfloat16": _lib.TENSOR_BF16}
+
+
+def _field_bits(element_bits, num_clients):
+    """The bits of one batched field: the quantised value and room for the sum over the clients."""
+    return element_bits + int(np.ceil(np.log2(num_clients)))
+
+
+def _layer_source(eng, v, what):
+    """One layer value -> (x, storage dtype code, NumPy dtype of its host copy, size, shape).  x is the ForeignArray of a framework device
+    tensor, read where it lies (TypeError naming `what` for a dtype the kernels do not read), or the flat contiguous host array of anything
+    else -- float32 and float64 as they are, every other dtype as float64."""
+    if interop.is_foreign(v):
+        fa = eng.foreign(v, what=what)
+        if fa.dtype not in _TENSOR_CODES:
+            raise TypeError(f"{what}: unsupported dtype {fa.dtype} (float32, float64, float16 or bfloat16)")
+        return fa, _TENSOR_CODES[fa.dtype], _F64 if fa.dtype == "float64" else _F32, math.prod(fa.shape), fa.shape
+    a = np.asarray(v)
+    flat = np.ascontiguousarray(a).reshape(-1)
+    if flat.dtype not in (np.float32, np.float64):
+        flat = flat.astype(np.float64)
+    return flat, _lib.TENSOR_F64 if flat.dtype == np.float64 else _lib.TENSOR_F32, flat.dtype, int(flat.size), a.shape
+
+
+def _stage_host_layers(eng, row):
+    """One client's layer sources -- flat host arrays, ForeignArrays, bare device pointers -- as (device pointers, keep).  The host arrays
+    go up once into ONE buffer at 16-byte-aligned offsets (no buffer for a client without a host layer); keep holds that buffer and the
+    owner of every ForeignArray: what must outlive the last kernel that reads the pointers."""
+    offs, nbytes = {}, 0
+    for li, x in enumerate(row):
+        if isinstance(x, np.ndarray):
+            offs[li] = nbytes
+            nbytes += (x.nbytes + 15) & ~15
+    keep = []
+    if offs:
+        xbuf = eng.alloc(max(nbytes, 16))
+        for li, off in offs.items():
+            xbuf.upload_at(off, row[li])
+        keep.append(xbuf)
+    ptrs = []
+    for li, x in enumerate(row):
+        if isinstance(x, np.ndarray):
+            ptrs.append(xbuf.ptr + offs[li])
+        elif isinstance(x, int):
+            ptrs.append(x)
+        else:
+            ptrs.append(x.ptr)
+            keep.append(x.keep)
+    return ptrs, keep
+
+
+def _round_alphas(q, sizes):
+    """The alpha of every entry of q.layer_size_list for this round (ACIQ on the std history; 0 -> 0.1).  On first use `sizes` becomes the
+    layer_size_list with the first round's expected mean / std (set_layer_size_list, jzf_quantize.py:380-392)."""
+    if q.layer_size_list is None:
+        q.layer_size_list = list(sizes)
+        for _ in q.layer_size_list:
+            q.past_layer_mean_list.append(q.expected_mean_for_first_round)
+            q.past_layer_std_list.append(q.expected_std_for_first_round)
+    aciq = ACIQ(q.element_bits)
+    alphas = []
+    for i in range(len(q.layer_size_list)):
+        a = aciq.get_alpha_gaus_direct(q.past_layer_std_list[i])
+        alphas.append(0.1 if a == 0 else a)
+    return alphas
+
+
+def _tensor_flags(hdt, alpha, normalize, mean):
+    """(shift, flags) of a tensor-layer row whose host copy has NumPy dtype hdt: TENSOR_LOOP_F64 where NumPy's clip / scale arithmetic with
+    alpha runs in float64 on a narrower layer; with normalize, shift = -mean (QuantizingClient._shift(layer, -mean)) under TENSOR_SHIFT, and
+    TENSOR_SHIFT_WIDE where NumPy adds it to a float32 layer in float64."""
+    flags, shift = 0, 0.0
+    if hdt != np.float64 and _loop_dtype(hdt, alpha) == np.float64:
+        flags |= _lib.TENSOR_LOOP_F64
+    if normalize:
+        shift = -mean
+        flags |= _lib.TENSOR_SHIFT
+        if hdt == np.float32 and _loop_dtype(hdt, shift) == np.float64:
+            flags |= _lib.TENSOR_SHIFT_WIDE
+    return float(shift), flags
+
+
+def _cohort_draws(eng, C, per_client, seeds):
+    """The stochastic-rounding draws of C clients, client-major, as a device buffer: client c's are draws [c per_client, (c + 1) per_client).
+    From the global stream (seeds=None) they are ONE stretch of C per_client draws -- the clients draw one after the other -- generated in
+    device calls of at most _RNG_RUN_MAX draws whatever client they belong to (the jump-ahead of a device call is paid per call, not per
+    client); with seeds every client's stretch starts at its own seed.  On the device under quantize_encrypt's rule (FLASHE_DEVICE_RNG,
+    MT19937, DEVICE_RNG_MIN draws or more in the call), else drawn on the host and uploaded."""
+    from .quantize import DEVICE_RNG_MIN
+    dev_rng = os.environ.get("FLASHE_DEVICE_RNG", "1") != "0"
+    du = eng.alloc(max(8 * C * per_client, 16))
+    for seed, first, count in ([(None, 0, C * per_client)] if seeds is None else [(seeds[ci], ci * per_client, per_client) for ci in range(C)]):
+        if seed is not None:
+            np.random.seed(seed)
+        mt = dev_rng and np.random.get_state()[0] == "MT19937"
+        for at in range(first, first + count, _RNG_RUN_MAX):
+            tot = min(_RNG_RUN_MAX, first + count - at)
+            if mt and tot >= DEVICE_RNG_MIN:
+                eng.numpy_random_dev(tot, out=du.ptr + 8 * at)
+            else:
+                du.upload_at(8 * at, np.random.random(tot))
+    return du
 
 
 class FlasheClient(object):
@@ -288,8 +396,7 @@ class FlasheClient(object):
         take the same sequence call by call on the host and return object arrays like the reference."""
         from . import cipher as _cipher_mod
         from .engine import DeviceVector
-        from .quantize import ACIQ, DEVICE_RNG_MIN, _loop_dtype
-        from . import interop
+        from .quantize import DEVICE_RNG_MIN
         q, c = self.quantizer, self.cipher
         if any(interop.is_foreign(weights._weights[k]) for k in weights.walking_order):
             return self._quantize_encrypt_tensors(weights, device, normalize)
@@ -309,11 +416,7 @@ class FlasheClient(object):
             return weights
         eng = c.engine
         mode = self._prepared_mode(c.next_iter_encrypt_prepared)
-        aciq = ACIQ(q.element_bits)
-        alphas = []
-        for i, _size in enumerate(q.layer_size_list):
-            a = aciq.get_alpha_gaus_direct(q.past_layer_std_list[i])
-            alphas.append(0.1 if a == 0 else a)
+        alphas = _round_alphas(q, q.layer_size_list)
         q.r_max_list, q.alpha_list = [], []
         c.set_idx_list(mode="encrypt")
         scheme = 1 if c.masking_scheme == "double" else 0
@@ -348,8 +451,7 @@ class FlasheClient(object):
         if self.batch:
             # quantise + batch of the whole model in ONE launch (per-layer alpha, per-layer zero padding), then the encrypt of the flattened
             # batched vector: the draws are one stretch of NumPy's stream over all VALUES in walking order
-            factor = int(np.ceil(np.log2(q.num_clients)))
-            field_bits = q.element_bits + factor
+            field_bits = _field_bits(q.element_bits, q.num_clients)
             bs = self.int_bits // field_bits
             q.shape_list = [shape_dict[k] for k in order]
             n_elems = sum((int(h.size) + bs - 1) // bs for h in host)
@@ -523,8 +625,7 @@ class FlasheClient(object):
         if mode == "ctx":
             c._check_prepared_len(c.next_iter_decrypt_prepared['add'], n)          # (the call-by-call decrypt's error; the cache stays)
         if self.batch:
-            factor = int(np.ceil(np.log2(q.num_clients)))
-            field_bits = q.element_bits + factor
+            field_bits = _field_bits(q.element_bits, q.num_clients)
             bs = self.int_bits // field_bits
             if sum((s_ + bs - 1) // bs for s_ in sizes) != n:
                 raise ValueError(f"the aggregate has {n} elements, the batched layers describe {sum((s_ + bs - 1) // bs for s_ in sizes)}")
@@ -563,10 +664,8 @@ class FlasheClient(object):
         scratch, flashe_quantize_encrypt_tensors_dev / flashe_quantize_batch_tensors_dev), host layers go up as in the host path.  Bit for
         bit the host path on `t.cpu().numpy()` (float16 / bfloat16: `t.float().cpu().numpy()`), with `normalize()` first when asked."""
         from . import cipher as _cipher_mod
-        from . import interop
-        from ._lib import TENSOR_BF16, TENSOR_F16, TENSOR_F32, TENSOR_F64, TENSOR_LOOP_F64, TENSOR_SHIFT, TENSOR_SHIFT_WIDE
         from .engine import DeviceVector
-        from .quantize import ACIQ, DEVICE_RNG_MIN, _loop_dtype
+        from .quantize import DEVICE_RNG_MIN
         q, c = self.quantizer, self.cipher
         zzz = None
         if "zzz" in weights._weights:                 # the sparse job: compact layers (Sparsifier's CompactLayer or any tensors) + 'zzz'
@@ -589,39 +688,17 @@ class FlasheClient(object):
                             "the handles prepare_encrypt leaves)")
         eng = c.engine
         mode = self._prepared_mode(c.next_iter_encrypt_prepared) if zzz is None else None
-        codes = {"float32": TENSOR_F32, "float64": TENSOR_F64, "float16": TENSOR_F16, "bfloat16": TENSOR_BF16}
         order = list(weights.walking_order)
         if zzz is not None:
             order = order[:-1]
-        layers = []                                   # (ForeignArray or host flat array, shape, NumPy dtype of its host copy)
-        for k in order:
-            v = weights._weights[k]
-            if interop.is_foreign(v):
-                fa = eng.foreign(v, what=f"layer {k!r}")
-                if fa.dtype not in codes:
-                    raise TypeError(f"layer {k!r}: unsupported dtype {fa.dtype} (float32, float64, float16 or bfloat16)")
-                layers.append((fa, fa.shape, np.dtype(np.float64 if fa.dtype == "float64" else np.float32)))
-            else:
-                a = np.asarray(v)
-                flat = np.ascontiguousarray(a).reshape(-1)
-                if flat.dtype not in (np.float32, np.float64):
-                    flat = flat.astype(np.float64)
-                layers.append((flat, a.shape, flat.dtype))
-        if q.layer_size_list is None:                 # set_layer_size_list (jzf_quantize.py:380-392) on the sizes the tensors report
-            q.layer_size_list = [int(np.prod(shape, dtype=np.int64)) for _x, shape, _d in layers] + ([int(zzz.size)] if zzz is not None else [])
-            for _ in q.layer_size_list:
-                q.past_layer_mean_list.append(q.expected_mean_for_first_round)
-                q.past_layer_std_list.append(q.expected_std_for_first_round)
-        aciq = ACIQ(q.element_bits)
-        alphas = []
-        for i, _size in enumerate(q.layer_size_list):
-            a = aciq.get_alpha_gaus_direct(q.past_layer_std_list[i])
-            alphas.append(0.1 if a == 0 else a)
+        layers = [_layer_source(eng, weights._weights[k], f"layer {k!r}") for k in order]
+        # (set_layer_size_list on the sizes the tensors report)
+        alphas = _round_alphas(q, [size for _x, _code, _d, size, _shape in layers] + ([int(zzz.size)] if zzz is not None else []))
         q.r_max_list, q.alpha_list = [], []
         c.set_idx_list(mode="encrypt")
         scheme = 1 if c.masking_scheme == "double" else 0
         host_off, nbytes = {}, 0
-        for li, (x, _shape, _dt) in enumerate(layers):
+        for li, (x, _code, _dt, _size, _shape) in enumerate(layers):
             if isinstance(x, np.ndarray):
                 host_off[li] = nbytes
                 nbytes += (x.nbytes + 15) & ~15
@@ -629,32 +706,23 @@ class FlasheClient(object):
         for li, off in host_off.items():
             xbuf.upload_at(off, layers[li][0])
         table, sizes, n, keep = [], [], 0, []
-        for li, (x, shape, hdt) in enumerate(layers):
+        for li, (x, code, hdt, size, _shape) in enumerate(layers):
             alpha = alphas[li]
             q.r_max_list.append(alpha * q.num_clients)
             q.alpha_list.append(alpha)
-            size = int(np.prod(shape, dtype=np.int64))
-            flags, shift = 0, 0.0
-            if hdt != np.float64 and _loop_dtype(hdt, alpha) == np.float64:
-                flags |= TENSOR_LOOP_F64
-            if normalize:                             # QuantizingClient._shift(layer, -mean): the same wide / narrow rule
-                shift = -q.past_layer_mean_list[li]
-                flags |= TENSOR_SHIFT
-                if hdt == np.float32 and _loop_dtype(hdt, shift) == np.float64:
-                    flags |= TENSOR_SHIFT_WIDE
+            shift, flags = _tensor_flags(hdt, alpha, normalize, q.past_layer_mean_list[li])
             if isinstance(x, np.ndarray):
-                ptr, code = xbuf.ptr + host_off[li], TENSOR_F64 if hdt == np.float64 else TENSOR_F32
+                ptr = xbuf.ptr + host_off[li]
             else:
-                ptr, code = x.ptr, codes[x.dtype]
+                ptr = x.ptr
                 keep.append(x.keep)
-            table.append((n, ptr, alpha, float(shift), code, flags))
+            table.append((n, ptr, alpha, shift, code, flags))
             sizes.append(size)
             n += size
         dev_rng = os.environ.get("FLASHE_DEVICE_RNG", "1") != "0" and np.random.get_state()[0] == "MT19937"
-        shape_dict = {k: shape for k, (_x, shape, _d) in zip(order, layers)}
+        shape_dict = {k: layer[4] for k, layer in zip(order, layers)}
         if self.batch:
-            factor = int(np.ceil(np.log2(q.num_clients)))
-            field_bits = q.element_bits + factor
+            field_bits = _field_bits(q.element_bits, q.num_clients)
             bs = self.int_bits // field_bits
             q.shape_list = [shape_dict[k] for k in order]
             n_elems = sum((s_ + bs - 1) // bs for s_ in sizes)
@@ -985,7 +1053,7 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
         n += s_
     n_elems, bs = n, 1
     if batch:
-        bs = int_bits // (element_bits + int(np.ceil(np.log2(num_clients))))
+        bs = int_bits // _field_bits(element_bits, num_clients)
         n_elems = sum((s_ + bs - 1) // bs for s_ in sizes)
     if cohort_masks and mask == "double":
         if mixed:
@@ -1036,7 +1104,7 @@ class _CohortLead(FlasheClient):
         eng, n = c.engine, len(dv)
         if self.batch:
             # (the batched sum: combine + unbatch + `[:size]` + unquantise in one pass, as the parent's decrypt launch + unbatch launch)
-            field_bits = q.element_bits + int(np.ceil(np.log2(q.num_clients)))
+            field_bits = _field_bits(q.element_bits, q.num_clients)
             bs = self.int_bits // field_bits
             if sum((s_ + bs - 1) // bs for s_ in sizes) != n:
                 raise ValueError(f"the aggregate has {n} elements, the batched layers describe {sum((s_ + bs - 1) // bs for s_ in sizes)}")
@@ -1158,198 +1226,46 @@ class FlasheCohort(object):
         29.2 M-parameter models), on the device under quantize_encrypt's conditions (MT19937, DEVICE_RNG_MIN).  Mismatched Weights raise
         ValueError and unusable tensors are refused before anything is launched.  Own-stream engines keep the tensors alive until the
         last kernel that reads them has finished."""
-        from . import cipher as _cipher_mod
-        from . import interop
-        from ._lib import TENSOR_BF16, TENSOR_F16, TENSOR_F32, TENSOR_F64, TENSOR_LOOP_F64, TENSOR_SHIFT, TENSOR_SHIFT_WIDE
         from .engine import DeviceVector
-        from .quantize import ACIQ, DEVICE_RNG_MIN, _loop_dtype
         ld = self.lead
-        q, c = ld.quantizer, ld.cipher
-        C = self.n_local
-        if len(weights_list) != C:
-            raise ValueError(f"the cohort holds {C} clients, got {len(weights_list)} Weights")
-        if seeds is not None and len(seeds) != C:
-            raise ValueError(f"seeds: one per client ({C}), got {len(seeds)}")
-        plan = self.plan(weights_list)
-        eng = c.engine
-        codes = {"float32": TENSOR_F32, "float64": TENSOR_F64, "float16": TENSOR_F16, "bfloat16": TENSOR_BF16}
-        # every layer of every client as (ForeignArray or flat host array, NumPy dtype of its host copy): the refusals come first
-        layers = []
-        for ci, w in enumerate(weights_list):
-            row = []
-            for k in plan.names:
-                v = w._weights[k]
-                if interop.is_foreign(v):
-                    fa = eng.foreign(v, what=f"client {ci} layer {k!r}")
-                    if fa.dtype not in codes:
-                        raise TypeError(f"client {ci} layer {k!r}: unsupported dtype {fa.dtype} (float32, float64, float16 or bfloat16)")
-                    row.append((fa, np.dtype(np.float64 if fa.dtype == "float64" else np.float32)))
-                else:
-                    flat = np.ascontiguousarray(np.asarray(v)).reshape(-1)
-                    if flat.dtype not in (np.float32, np.float64):
-                        flat = flat.astype(np.float64)
-                    row.append((flat, flat.dtype))
-            layers.append(row)
-        if self._masks is not None and plan.path in (PREPARED_COHORT, PREPARED_STAGED) and len(self._masks[0]) != plan.n_elems:
-            # a cache of another length: the call-by-call step's ValueError, where the first sequential client raises it (after its
-            # quantiser has drawn one value per model value, FlasheClient._refuse_prepared_len); the cache stays, and nothing of the
-            # cohort's state has been touched or uploaded yet
-            if seeds is not None:
-                np.random.seed(seeds[0])
-            for at in range(0, plan.n, _RNG_RUN_MAX):
-                np.random.random(min(_RNG_RUN_MAX, plan.n - at))
-            c._check_prepared_len(self._masks[0], plan.n_elems)
+        q, eng, C = ld.quantizer, ld.cipher.engine, self.n_local
+        plan, layers = self._collect(weights_list, seeds)
+        self._refuse_prepared_len(plan, seeds)
         self._last, ld._cohort_mask = None, None
-        if any(row[li][1] != layers[0][li][1] for row in layers for li in range(len(row))) and plan.path in (COHORT_CHAIN, PREPARED_COHORT):
-            # (a layer that computes in float64 for some clients only: no shared row)
-            plan.path = STAGED_CHAIN if plan.path == COHORT_CHAIN else PREPARED_STAGED
-        prepared = plan.path in (PREPARED_COHORT, PREPARED_STAGED)       # (the cohort's cache is consumed whatever `prefer` says)
-        if prepared and self.prefer == STAGED_CHAIN:
-            plan.path = PREPARED_STAGED
-        elif not prepared and (self.prefer == PER_CLIENT or (self.prefer == STAGED_CHAIN and plan.path == COHORT_CHAIN)):
-            plan.path = self.prefer
-        if plan.path == PER_CLIENT:
+        path = self._choose_path(plan, layers)
+        if path == PER_CLIENT:
             return self._per_client(weights_list, normalize, seeds)
         if not ld._fusable():
             raise TypeError("FlasheCohort needs the fused client step (fuse=True, a keyed cipher, no location masks)")
-        # the one quantiser state: set_layer_size_list and the alphas of this round, as FlasheClient._quantize_encrypt_tensors
-        if q.layer_size_list is None:
-            q.layer_size_list = list(plan.sizes)
-            for _ in q.layer_size_list:
-                q.past_layer_mean_list.append(q.expected_mean_for_first_round)
-                q.past_layer_std_list.append(q.expected_std_for_first_round)
-        aciq = ACIQ(q.element_bits)
-        alphas = []
-        for i, _size in enumerate(q.layer_size_list):
-            a = aciq.get_alpha_gaus_direct(q.past_layer_std_list[i])
-            alphas.append(0.1 if a == 0 else a)
-        q.r_max_list = [alphas[li] * q.num_clients for li in range(len(plan.names))]
-        q.alpha_list = [alphas[li] for li in range(len(plan.names))]
-        c.set_idx_list(mode="encrypt")
-        scheme = 1 if c.masking_scheme == "double" else 0
-        n, n_elems, nl = plan.n, plan.n_elems, len(plan.names)
-        # host layers go up once, client by client
-        keep, tables = [], []
-        for ci, row in enumerate(layers):
-            offs, nbytes = {}, 0
-            for li, (x, _dt) in enumerate(row):
-                if isinstance(x, np.ndarray):
-                    offs[li] = nbytes
-                    nbytes += (x.nbytes + 15) & ~15
-            xbuf = eng.alloc(max(nbytes, 16)) if offs else None
-            for li, off in offs.items():
-                xbuf.upload_at(off, row[li][0])
-            if xbuf is not None:
-                keep.append(xbuf)
-            table = []
-            for li, (x, hdt) in enumerate(row):
-                alpha = alphas[li]
-                flags, shift = 0, 0.0
-                if hdt != np.float64 and _loop_dtype(hdt, alpha) == np.float64:
-                    flags |= TENSOR_LOOP_F64
-                if normalize:
-                    shift = -q.past_layer_mean_list[li]
-                    flags |= TENSOR_SHIFT
-                    if hdt == np.float32 and _loop_dtype(hdt, shift) == np.float64:
-                        flags |= TENSOR_SHIFT_WIDE
-                if isinstance(x, np.ndarray):
-                    ptr, code = xbuf.ptr + offs[li], TENSOR_F64 if hdt == np.float64 else TENSOR_F32
-                else:
-                    ptr, code = x.ptr, codes[x.dtype]
-                    keep.append(x.keep)
-                table.append((plan.starts[li], ptr, alpha, float(shift), code, flags))
-            tables.append(table)
-        # the draws, client-major: client c's are draws [c n, (c + 1) n).  From the global stream they are ONE stretch of C n draws (the
-        # clients draw one after the other), generated in device calls of at most _RNG_RUN_MAX draws whatever client they belong to --
-        # the jump-ahead of a device call is paid per call, not per client; with seeds every client's stretch starts at its own seed
-        dev_rng = os.environ.get("FLASHE_DEVICE_RNG", "1") != "0"
-        du = eng.alloc(max(8 * C * n, 16))
-        for seed, first, count in ([(None, 0, C * n)] if seeds is None else [(seeds[ci], plan.draw_offsets[ci], n) for ci in range(C)]):
-            if seed is not None:
-                np.random.seed(seed)
-            mt = dev_rng and np.random.get_state()[0] == "MT19937"
-            for at in range(first, first + count, _RNG_RUN_MAX):
-                tot = min(_RNG_RUN_MAX, first + count - at)
-                if mt and tot >= DEVICE_RNG_MIN:
-                    eng.numpy_random_dev(tot, out=du.ptr + 8 * at)
-                else:
-                    du.upload_at(8 * at, np.random.random(tot))
+        alphas = self._begin_round(plan)
+        tables, keep = self._tables(plan, layers, alphas, normalize)
+        du = _cohort_draws(eng, C, plan.n, seeds)
         if self.compact:
-            cts = [DeviceVector(eng, n_elems, 1, elem_bytes=4) for _ in range(C)]
-            psum = DeviceVector(eng, n_elems, 1, elem_bytes=4)
+            cts = [DeviceVector(eng, plan.n_elems, 1, elem_bytes=4) for _ in range(C)]
+            psum = DeviceVector(eng, plan.n_elems, 1, elem_bytes=4)
         else:
-            cts = [DeviceVector(eng, n_elems) for _ in range(C)]
-            psum = DeviceVector(eng, n_elems)
-        idxs = [self.first_idx + ci for ci in range(C)]
-        whole = self.n_local == self.num_clients
-        path = plan.path
-        if path == COHORT_CHAIN:
+            cts = [DeviceVector(eng, plan.n_elems) for _ in range(C)]
+            psum = DeviceVector(eng, plan.n_elems)
+        prepared = path in (PREPARED_COHORT, PREPARED_STAGED)       # (the cohort's cache is consumed whatever form runs)
+        if path in (COHORT_CHAIN, PREPARED_COHORT):
             # the shared rows name the compute type; the sources keep their own storage dtypes
-            rows = [(st, None, al, sh, TENSOR_F64 if layers[0][li][1] == np.float64 else TENSOR_F32, fl)
+            rows = [(st, None, al, sh, _lib.TENSOR_F64 if layers[0][li][2] == np.float64 else _lib.TENSOR_F32, fl)
                     for li, (st, _p, al, sh, _code, fl) in enumerate(tables[0])]
             srcs = [[t[1] for t in table] for table in tables]
             dts = [[t[4] for t in table] for table in tables]
-            # (no decrypt mask at the compact widths: the decrypt of the sum is 2 / m AES blocks per element)
-            dmask = DeviceVector(eng, n_elems) if whole and not self.compact else None
-            outs, mask_buf = [v.buf for v in cts], dmask.buf if dmask is not None else None
-            if self.compact:
-                took = eng.quantize_encrypt_cohort_u32_dev(c.iter_index, self.first_idx, n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du, outs,
-                                                           psum.buf)
-            elif ld.batch:
-                field_bits = q.element_bits + int(np.ceil(np.log2(q.num_clients)))
-                took = eng.quantize_batch_encrypt_cohort_dev(c.iter_index, self.first_idx, n, n_elems, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits,
-                                                             field_bits, du, outs, psum.buf, mask_buf)
-            else:
-                took = eng.quantize_encrypt_cohort_dev(c.iter_index, self.first_idx, n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du, outs,
-                                                       psum.buf, mask_buf)
-            if not took:
-                path = STAGED_CHAIN                    # the library declined: the planner's guess was wrong, the result is not
-            elif dmask is not None:
-                ld._cohort_mask = (psum.ptr, dmask, c.iter_index, self.first_idx + C, self.first_idx)
-        if path == PREPARED_COHORT:
-            # ONE online launch: every client's floats and its precomputed mask -> its ciphertext, and their sum; no AES
-            rows = [(st, None, al, sh, TENSOR_F64 if layers[0][li][1] == np.float64 else TENSOR_F32, fl)
-                    for li, (st, _p, al, sh, _code, fl) in enumerate(tables[0])]
-            srcs = [[t[1] for t in table] for table in tables]
-            dts = [[t[4] for t in table] for table in tables]
-            field_bits = q.element_bits + int(np.ceil(np.log2(q.num_clients)))
-            took = eng.quantize_combine_cohort_dev(n, rows, srcs, dts, q.element_bits, du, [m.buf for m in self._masks], [v.buf for v in cts], psum.buf,
-                                                   compact=self.compact, batch=(n_elems, field_bits) if ld.batch else None)
-            if not took:
-                path = PREPARED_STAGED                 # the library declined: the same bytes from the fallback form
-        if path == PREPARED_STAGED and n_elems:
-            # a quantise (+ batch) pass per client into plaintexts, then the combines with the masks and their sum in one pass (one-limb
-            # vectors: a compact cohort widens its masks before and narrows the results after)
-            field_bits = q.element_bits + int(np.ceil(np.log2(q.num_clients))) if ld.batch else ld.int_bits
-            pts = [eng.alloc_vec(n_elems) for _ in range(C)]
-            for ci in range(C):
-                eng.quantize_batch_tensors_dev(tables[ci], n, q.element_bits, field_bits, du.ptr + 8 * plan.draw_offsets[ci], n_elems, pts[ci])
-            adds = [m.widened(eng) for m in self._masks]
-            wide = [DeviceVector(eng, n_elems) for _ in range(C)] if self.compact else cts
-            wsum = DeviceVector(eng, n_elems) if self.compact else psum
-            eng.combine_batch_sum_dev(n_elems, pts, eng.limbs, [a.buf for a in adds], None, [v.buf for v in wide], wsum.buf)
-            if self.compact:
-                cts, psum = [v.mark_ready().narrowed(eng) for v in wide], wsum.mark_ready().narrowed(eng)
-            keep += pts + adds
+            launch = self._launch_prepared if prepared else self._launch_chain
+            if not launch(plan, rows, srcs, dts, du, cts, psum):
+                # the library declined: the planner's guess was wrong, the result is not -- the same bytes from the fallback form
+                path = PREPARED_STAGED if prepared else STAGED_CHAIN
+        if path in (STAGED_CHAIN, PREPARED_STAGED) and plan.n_elems:
+            cts, psum, held = self._launch_staged(plan, tables, du, cts, psum, prepared)
+            keep += held
         if prepared:
             keep += list(self._masks)
             self._masks = None                         # consumed by this call, whatever the iteration (the reference does not check it either)
-        if path == STAGED_CHAIN and n_elems:
-            # a quantise (+ batch) pass per client into plaintexts -- un-batched: one value per element, field_bits = int_bits -- then the
-            # summed batch encrypt, which chains where it can
-            field_bits = q.element_bits + int(np.ceil(np.log2(q.num_clients))) if ld.batch else ld.int_bits
-            pts = [eng.alloc_vec(n_elems) for _ in range(C)]
-            for ci in range(C):
-                eng.quantize_batch_tensors_dev(tables[ci], n, q.element_bits, field_bits, du.ptr + 8 * plan.draw_offsets[ci], n_elems, pts[ci])
-            if self.compact:
-                pts = [DeviceVector(eng, n_elems, 1, buf=pt).narrowed().buf for pt in pts]
-                eng.encrypt_batch_sum_u32_dev(c.iter_index, idxs, scheme, n_elems, _cipher_mod.N_JOBS, pts, [v.buf for v in cts], psum.buf)
-            else:
-                eng.encrypt_batch_sum_dev(c.iter_index, idxs, scheme, n_elems, _cipher_mod.N_JOBS, pts, eng.limbs, [v.buf for v in cts], psum.buf)
-            keep += pts
         eng.hold(keep + [du])
         if ld.batch:
-            bs = ld.int_bits // (q.element_bits + int(np.ceil(np.log2(q.num_clients))))
+            bs = ld.int_bits // _field_bits(q.element_bits, q.num_clients)
             q.shape_list = list(plan.shapes)
             ld.shape_dict = {k: ((s_ + bs - 1) // bs,) for k, s_ in zip(plan.names, plan.sizes)}
         else:
@@ -1359,6 +1275,130 @@ class FlasheCohort(object):
         psum.mark_ready()
         self._last = CohortUpload(cts, psum, path)
         return self._last
+
+    def _collect(self, weights_list, seeds):
+        """(plan, every layer of every client as _layer_source gives it): the refusals, before anything of the cohort's state is touched."""
+        C = self.n_local
+        if len(weights_list) != C:
+            raise ValueError(f"the cohort holds {C} clients, got {len(weights_list)} Weights")
+        if seeds is not None and len(seeds) != C:
+            raise ValueError(f"seeds: one per client ({C}), got {len(seeds)}")
+        plan = self.plan(weights_list)
+        eng = self.lead.cipher.engine
+        return plan, [[_layer_source(eng, w._weights[k], f"client {ci} layer {k!r}") for k in plan.names] for ci, w in enumerate(weights_list)]
+
+    def _refuse_prepared_len(self, plan, seeds):
+        """A cache of another length: the call-by-call step's ValueError, where the first sequential client raises it (after its quantiser
+        has drawn one value per model value, FlasheClient._refuse_prepared_len); the cache stays, and nothing of the cohort's state has
+        been touched or uploaded yet."""
+        if self._masks is None or plan.path not in (PREPARED_COHORT, PREPARED_STAGED) or len(self._masks[0]) == plan.n_elems:
+            return
+        if seeds is not None:
+            np.random.seed(seeds[0])
+        for at in range(0, plan.n, _RNG_RUN_MAX):
+            np.random.random(min(_RNG_RUN_MAX, plan.n - at))
+        self.lead.cipher._check_prepared_len(self._masks[0], plan.n_elems)
+
+    def _choose_path(self, plan, layers):
+        """The plan's path after what only the layers themselves and `prefer` tell."""
+        path = plan.path
+        if any(layer[2] != first[2] for row in layers for layer, first in zip(row, layers[0])) and path in (COHORT_CHAIN, PREPARED_COHORT):
+            # (a layer that computes in float64 for some clients only: no shared row)
+            path = STAGED_CHAIN if path == COHORT_CHAIN else PREPARED_STAGED
+        prepared = path in (PREPARED_COHORT, PREPARED_STAGED)       # (the cohort's cache is consumed whatever `prefer` says)
+        if prepared and self.prefer == STAGED_CHAIN:
+            return PREPARED_STAGED
+        if not prepared and (self.prefer == PER_CLIENT or (self.prefer == STAGED_CHAIN and path == COHORT_CHAIN)):
+            return self.prefer
+        return path
+
+    def _begin_round(self, plan):
+        """The one quantiser state -- set_layer_size_list and r_max_list / alpha_list of this round, as FlasheClient's tensor step leaves
+        them -- and the cipher's encrypt prefixes.  Returns the alphas."""
+        q = self.lead.quantizer
+        alphas = _round_alphas(q, plan.sizes)
+        q.r_max_list = [alphas[li] * q.num_clients for li in range(len(plan.names))]
+        q.alpha_list = [alphas[li] for li in range(len(plan.names))]
+        self.lead.cipher.set_idx_list(mode="encrypt")
+        return alphas
+
+    def _tables(self, plan, layers, alphas, normalize):
+        """(every client's tensor-layer table, keep): host layers go up once, client by client."""
+        eng, means = self.lead.cipher.engine, self.lead.quantizer.past_layer_mean_list
+        tables, keep = [], []
+        for row in layers:
+            ptrs, held = _stage_host_layers(eng, [layer[0] for layer in row])
+            keep += held
+            table = []
+            for li, (_x, code, hdt, _size, _shape) in enumerate(row):
+                shift, flags = _tensor_flags(hdt, alphas[li], normalize, means[li])
+                table.append((plan.starts[li], ptrs[li], alphas[li], shift, code, flags))
+            tables.append(table)
+        return tables, keep
+
+    def _launch_chain(self, plan, rows, srcs, dts, du, cts, psum):
+        """"cohort-chain": ONE chained launch from the floats to the ciphertexts, their sum and -- when the cohort is the whole federation --
+        the decrypt mask, which the lead keeps for the decrypt of that sum.  False: the library declined, nothing was launched."""
+        from . import cipher as _cipher_mod
+        from .engine import DeviceVector
+        ld = self.lead
+        q, c, eng = ld.quantizer, ld.cipher, ld.cipher.engine
+        n, n_elems = plan.n, plan.n_elems
+        # (no decrypt mask at the compact widths: the decrypt of the sum is 2 / m AES blocks per element)
+        dmask = DeviceVector(eng, n_elems) if self.n_local == self.num_clients and not self.compact else None
+        outs, mask_buf = [v.buf for v in cts], dmask.buf if dmask is not None else None
+        if self.compact:
+            took = eng.quantize_encrypt_cohort_u32_dev(c.iter_index, self.first_idx, n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du, outs,
+                                                       psum.buf)
+        elif ld.batch:
+            took = eng.quantize_batch_encrypt_cohort_dev(c.iter_index, self.first_idx, n, n_elems, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits,
+                                                         _field_bits(q.element_bits, q.num_clients), du, outs, psum.buf, mask_buf)
+        else:
+            took = eng.quantize_encrypt_cohort_dev(c.iter_index, self.first_idx, n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du, outs,
+                                                   psum.buf, mask_buf)
+        if took and dmask is not None:
+            ld._cohort_mask = (psum.ptr, dmask, c.iter_index, self.first_idx + self.n_local, self.first_idx)
+        return took
+
+    def _launch_prepared(self, plan, rows, srcs, dts, du, cts, psum):
+        """"prepared-cohort": ONE online launch, every client's floats and its precomputed mask -> its ciphertext, and their sum; no AES.
+        False: the library declined, nothing was launched."""
+        ld = self.lead
+        q = ld.quantizer
+        return ld.cipher.engine.quantize_combine_cohort_dev(plan.n, rows, srcs, dts, q.element_bits, du, [m.buf for m in self._masks],
+                                                            [v.buf for v in cts], psum.buf, compact=self.compact,
+                                                            batch=(plan.n_elems, _field_bits(q.element_bits, q.num_clients)) if ld.batch else None)
+
+    def _launch_staged(self, plan, tables, du, cts, psum, prepared):
+        """A quantise (+ batch) pass per client into plaintexts -- un-batched: one value per element, field_bits = int_bits -- then
+        "staged-chain": the summed batch encrypt, which chains where it can; "prepared-staged": the combines with the masks and their sum
+        in one pass (one-limb vectors: a compact cohort widens its masks before and narrows the results after).
+        Returns (ciphertexts, sum, what the launches read)."""
+        from . import cipher as _cipher_mod
+        from .engine import DeviceVector
+        ld = self.lead
+        q, c, eng = ld.quantizer, ld.cipher, ld.cipher.engine
+        C, n_elems = self.n_local, plan.n_elems
+        field_bits = _field_bits(q.element_bits, q.num_clients) if ld.batch else ld.int_bits
+        pts = [eng.alloc_vec(n_elems) for _ in range(C)]
+        for ci in range(C):
+            eng.quantize_batch_tensors_dev(tables[ci], plan.n, q.element_bits, field_bits, du.ptr + 8 * plan.draw_offsets[ci], n_elems, pts[ci])
+        if prepared:
+            adds = [m.widened(eng) for m in self._masks]
+            wide = [DeviceVector(eng, n_elems) for _ in range(C)] if self.compact else cts
+            wsum = DeviceVector(eng, n_elems) if self.compact else psum
+            eng.combine_batch_sum_dev(n_elems, pts, eng.limbs, [a.buf for a in adds], None, [v.buf for v in wide], wsum.buf)
+            if self.compact:
+                cts, psum = [v.mark_ready().narrowed(eng) for v in wide], wsum.mark_ready().narrowed(eng)
+            return cts, psum, pts + adds
+        idxs = [self.first_idx + ci for ci in range(C)]
+        scheme = 1 if c.masking_scheme == "double" else 0
+        if self.compact:
+            pts = [DeviceVector(eng, n_elems, 1, buf=pt).narrowed().buf for pt in pts]
+            eng.encrypt_batch_sum_u32_dev(c.iter_index, idxs, scheme, n_elems, _cipher_mod.N_JOBS, pts, [v.buf for v in cts], psum.buf)
+        else:
+            eng.encrypt_batch_sum_dev(c.iter_index, idxs, scheme, n_elems, _cipher_mod.N_JOBS, pts, eng.limbs, [v.buf for v in cts], psum.buf)
+        return cts, psum, pts
 
     def _per_client(self, weights_list, normalize, seeds):
         """The clients' own steps one after the other (one cipher re-indexed per client; with precompute: every client's own cipher and
@@ -1575,8 +1615,7 @@ class FlasheSparseCohort(object):
         Client c's result is its own Sparsifier(sparsity).sparsify(W_c, order): the same (encoded, le, bits, total), compact values and
         residuals as bytes.  The residuals stay in HBM per client between rounds (remain_weights(c) downloads them) and continue a
         previous round; the caller's models are neither written nor replaced.  Everything is checked before a residual is touched."""
-        from . import interop
-        from ._lib import TENSOR_BF16, TENSOR_F16, TENSOR_F32, TENSOR_F64
+        from ._lib import TENSOR_F32, TENSOR_F64
         from .engine import DeviceBufferView
         from .weights import CompactLayer, _compact_layout
         C = self.n_local
@@ -1585,25 +1624,11 @@ class FlasheSparseCohort(object):
         ld = self.lead
         plan = plan_sparse_cohort(weights_list, self.sparsity, ld.int_bits, element_bits=ld.quantizer.element_bits, walking_order=walking_order)
         eng = self.engine
-        codes = {"float32": TENSOR_F32, "float64": TENSOR_F64, "float16": TENSOR_F16, "bfloat16": TENSOR_BF16}
         names, L = plan.names, len(plan.names)
         rows = []                                     # per client [(ForeignArray or flat host array, dtype code)]
         for ci, w in enumerate(weights_list):
             _o, layers = _client_layers(w, walking_order)
-            row = []
-            for k in names:
-                v = layers[k]
-                if interop.is_foreign(v):
-                    fa = eng.foreign(v, what=f"client {ci} layer {k!r}")
-                    if fa.dtype not in codes:
-                        raise TypeError(f"client {ci} layer {k!r}: unsupported dtype {fa.dtype} (float32, float64, float16 or bfloat16)")
-                    row.append((fa, codes[fa.dtype]))
-                else:
-                    flat = np.ascontiguousarray(np.asarray(v)).reshape(-1)
-                    if flat.dtype not in (np.float32, np.float64):
-                        flat = flat.astype(np.float64)
-                    row.append((flat, TENSOR_F64 if flat.dtype == np.float64 else TENSOR_F32))
-            rows.append(row)
+            rows.append([_layer_source(eng, layers[k], f"client {ci} layer {k!r}")[:2] for k in names])
         if self.shape_dict_used_for_sparsification is None:
             self.shape_dict_used_for_sparsification = dict(zip(names, plan.shapes))
         self.plan, self._last = plan, None
@@ -1632,21 +1657,12 @@ class FlasheSparseCohort(object):
                 buf.upload(raw)
             rem = (buf, names, plan.sizes, cts, rstride)
             self._fallback = None
-        keep, srcs, dts = [], [], []
+        keep, srcs = [], []
         for row in rows:
-            offs, nbytes = {}, 0
-            for li, (x, _code) in enumerate(row):
-                if isinstance(x, np.ndarray):
-                    offs[li] = nbytes
-                    nbytes += (x.nbytes + 15) & ~15
-            xbuf = eng.alloc(max(nbytes, 16)) if offs else None
-            for li, off in offs.items():
-                xbuf.upload_at(off, row[li][0])
-            if xbuf is not None:
-                keep.append(xbuf)
-            srcs.append([xbuf.ptr + offs[li] if isinstance(x, np.ndarray) else x.ptr for li, (x, _code) in enumerate(row)])
-            dts.append([code for _x, code in row])
-            keep += [x.keep for x, _code in row if not isinstance(x, np.ndarray)]
+            ptrs, held = _stage_host_layers(eng, [x for x, _code in row])
+            srcs.append(ptrs)
+            keep += held
+        dts = [[code for _x, code in row] for row in rows]
         loc, vals, packed = eng.alloc(max(4 * C * lstride, 16)), eng.alloc(max(C * vstride, 16)), eng.alloc(max(8 * C * n_limbs, 16))
         table = [(plan.starts[li], TENSOR_F64 if plan.f64[li] else TENSOR_F32) for li in range(L)]
         eng.sparsify_cohort_tensors_dev(plan.total, table, plan.ks, srcs, dts, rem[0], rstride, loc, lstride, vals, vstride, packed, n_limbs, bits)
@@ -1768,11 +1784,7 @@ class FlasheSparseCohort(object):
         c takes [c (K + 1), (c + 1)(K + 1)), the last one is its 'zzz' draw -- and the generator is left where the sequential steps leave
         it; seeds=[s_0 ..]: client c draws after np.random.seed(s_c).  Generated on the device under quantize_encrypt's rule (MT19937,
         DEVICE_RNG_MIN)."""
-        from . import cipher as _cipher_mod
-        from . import interop
-        from ._lib import TENSOR_BF16, TENSOR_F16, TENSOR_F32, TENSOR_F64, TENSOR_LOOP_F64, TENSOR_SHIFT, TENSOR_SHIFT_WIDE
         from .engine import DeviceVector
-        from .quantize import ACIQ, DEVICE_RNG_MIN, _loop_dtype
         ld = self.lead
         q, c = ld.quantizer, ld.cipher
         eng, C = c.engine, self.n_local
@@ -1780,64 +1792,19 @@ class FlasheSparseCohort(object):
             raise ValueError("quantize_encrypt needs the round's masking choice and lists (dynamic_masking first)")
         if seeds is not None and len(seeds) != C:
             raise ValueError(f"seeds: one per client ({C}), got {len(seeds)}")
-        codes = {"float32": TENSOR_F32, "float64": TENSOR_F64, "float16": TENSOR_F16, "bfloat16": TENSOR_BF16}
         zzzs = [np.array([0.0])] * C
         if compact is not None:
-            if len(compact) != C:
-                raise ValueError(f"compact: one set of compact layers per client ({C}), got {len(compact)}")
-            names, given = None, []
-            for ci, w in enumerate(compact):
-                if hasattr(w, "_weights") or isinstance(w, dict):
-                    order, layers = _client_layers(w)
-                else:
-                    layers = {f"l{i:05d}": v for i, v in enumerate(w)}          # (a bare list: the compact layers in walking order)
-                    order = list(layers)
-                layers = dict(layers)
-                if "zzz" in layers:
-                    z = layers.pop("zzz")
-                    if interop.is_foreign(z):
-                        raise TypeError("the sparse job's 'zzz' layer must be a host value")
-                    z = np.asarray(z)
-                    if z.size != 1:
-                        raise ValueError(f"client {ci}: the 'zzz' layer holds {z.size} values, the sparsifier's holds one")
-                    zzzs[ci] = z
-                    order = [k for k in order if k != "zzz"]
-                if names is None:
-                    names = order
-                elif order != names:
-                    raise ValueError(f"client {ci}: the compact layers {order} are not client 0's {names}")
-                given.append(layers)
-            rows, keep, all_host = [], [], []
-            for ci, layers in enumerate(given):
-                row = []
-                for k in names:
-                    v = layers[k]
-                    if interop.is_foreign(v):
-                        fa = eng.foreign(v, what=f"client {ci} compact layer {k!r}")
-                        if fa.dtype not in codes:
-                            raise TypeError(f"client {ci} compact layer {k!r}: unsupported dtype {fa.dtype} (float32, float64, float16 or bfloat16)")
-                        row.append((fa, codes[fa.dtype], np.dtype(np.float64 if fa.dtype == "float64" else np.float32), int(np.prod(fa.shape, dtype=np.int64))))
-                    else:
-                        flat = np.ascontiguousarray(np.asarray(v)).reshape(-1)
-                        if flat.dtype not in (np.float32, np.float64):
-                            flat = flat.astype(np.float64)
-                        row.append((flat, TENSOR_F64 if flat.dtype == np.float64 else TENSOR_F32, flat.dtype, int(flat.size)))
-                if ci and [r[3] for r in row] != [r[3] for r in rows[0]]:
-                    raise ValueError(f"client {ci}: the compact layers have sizes {[r[3] for r in row]}, client 0's {[r[3] for r in rows[0]]}")
-                rows.append(row)
-                all_host.append(all(isinstance(r[0], np.ndarray) for r in row))
-            ks = [r[3] for r in rows[0]]
+            names, rows, all_host, per_client_layers = self._given_compact(compact, zzzs)
+            ks, keep = [r[3] for r in rows[0]], []
             mixed = any(r[2] != r0[2] for row in rows for r, r0 in zip(row, rows[0]))
-            per_client_layers = given
         else:
             if self._compact is None:
                 raise ValueError("quantize_encrypt needs compact layers: sparsify first, or pass compact=")
             srcs0, keep0, names, all_host, per_client_layers = self._compact
-            ks = list(self.plan.ks)
+            ks, keep = list(self.plan.ks), list(keep0)
             mixed = self.plan.path == PER_CLIENT
             rows = None if mixed else [[(ptr, code, d, kl) for (ptr, code, d), kl in zip(row, ks)] for row in srcs0]
-            keep = list(keep0)
-        K = sum(ks)
+        K, L = sum(ks), len(names)
         for ci in range(C):
             if self._lists[self.first_idx + ci][1] != K:
                 raise ValueError(f"client {ci}: {self._lists[self.first_idx + ci][1]} locations for {K} compact values")
@@ -1847,59 +1814,81 @@ class FlasheSparseCohort(object):
         self._last = None
         if path == PER_CLIENT:
             return self._per_client(per_client_layers, names, zzzs, all_host, normalize, seeds)
-        # ---- one quantiser state: set_layer_size_list and the alphas of the round, as FlasheClient._quantize_encrypt_tensors
-        L = len(names)
-        if q.layer_size_list is None:
-            q.layer_size_list = list(ks) + [1]
-            for _ in q.layer_size_list:
-                q.past_layer_mean_list.append(q.expected_mean_for_first_round)
-                q.past_layer_std_list.append(q.expected_std_for_first_round)
-        aciq = ACIQ(q.element_bits)
-        alphas = []
-        for i, _size in enumerate(q.layer_size_list):
-            a = aciq.get_alpha_gaus_direct(q.past_layer_std_list[i])
-            alphas.append(0.1 if a == 0 else a)
+        # one quantiser state: the compact layers and the one-value 'zzz' layer are the layer_size_list, the lists hold the L compact layers
+        alphas = _round_alphas(q, list(ks) + [1])
         q.r_max_list = [alphas[li] * q.num_clients for li in range(L)]
         q.alpha_list = [alphas[li] for li in range(L)]
         c.set_idx_list(mode="encrypt")
         # host layers of the compact= form go up once, client by client
-        srcs, dts = [], []
-        for ci, row in enumerate(rows):
-            offs, nbytes = {}, 0
-            for li, r in enumerate(row):
-                if isinstance(r[0], np.ndarray):
-                    offs[li] = nbytes
-                    nbytes += (r[0].nbytes + 15) & ~15
-            xbuf = eng.alloc(max(nbytes, 16)) if offs else None
-            for li, off in offs.items():
-                xbuf.upload_at(off, row[li][0])
-            if xbuf is not None:
-                keep.append(xbuf)
-            ps = []
-            for li, r in enumerate(row):
-                if isinstance(r[0], np.ndarray):
-                    ps.append(xbuf.ptr + offs[li])
-                elif isinstance(r[0], int):
-                    ps.append(r[0])
-                else:
-                    ps.append(r[0].ptr)
-                    keep.append(r[0].keep)
-            srcs.append(ps)
-            dts.append([r[1] for r in row])
+        srcs = []
+        for row in rows:
+            ptrs, held = _stage_host_layers(eng, [r[0] for r in row])
+            srcs.append(ptrs)
+            keep += held
+        dts = [[r[1] for r in row] for row in rows]
         table, at = [], 0
         for li in range(L):
-            hdt, alpha = rows[0][li][2], alphas[li]
-            flags, shift = 0, 0.0
-            if hdt != np.float64 and _loop_dtype(hdt, alpha) == np.float64:
-                flags |= TENSOR_LOOP_F64
-            if normalize:                             # QuantizingClient._shift(layer, -mean): the same wide / narrow rule
-                shift = -q.past_layer_mean_list[li]
-                flags |= TENSOR_SHIFT
-                if hdt == np.float32 and _loop_dtype(hdt, shift) == np.float64:
-                    flags |= TENSOR_SHIFT_WIDE
-            table.append((at, None, alpha, float(shift), TENSOR_F64 if hdt == np.float64 else TENSOR_F32, flags))
+            hdt = rows[0][li][2]
+            shift, flags = _tensor_flags(hdt, alphas[li], normalize, q.past_layer_mean_list[li])
+            table.append((at, None, alphas[li], shift, _lib.TENSOR_F64 if hdt == np.float64 else _lib.TENSOR_F32, flags))
             at += ks[li]
-        # the trailing layer as the host path takes it: normalised with its own mean (NumPy's in-place rule), alpha 1.0, not encrypted
+        zvals, z64 = self._zzz_values(zzzs, normalize, L)
+        du = _cohort_draws(eng, C, K + 1, seeds)
+        ups = [DeviceVector(eng, K + 1) for _ in range(C)]
+        zbuf = eng.alloc(max(8 * C, 16))
+        front, ptbuf, pts = self._launch_uploads(path, K, table, srcs, dts, du, zvals, z64, ups, zbuf)
+        zeros = [int(v) for v in zbuf.download(np.uint64, C)]          # the C quantised zeros: the one download of the step
+        agg, bounds = self._aggregate(front, K, pts, ups, zeros)
+        eng.hold(keep + [du, zbuf] + ([ptbuf] if ptbuf is not None else []))
+        ld.shape_dict = {k: (kl,) for k, kl in zip(names, ks)}
+        for u in ups:
+            u.mark_ready()
+        agg.mark_ready()
+        self._last = SparseCohortUpload(ups, agg, SPARSE_COHORT, front)
+        self._last_bounds = bounds if self.n_local == self.num_clients else None
+        return self._last
+
+    def _given_compact(self, compact, zzzs):
+        """The compact= form: C dicts / Weights / bare lists of compact layers -> (names, per client [(source, dtype code, NumPy dtype of its
+        host copy, size)], is every layer of client c a host array?, per client {name: layer}).  A client's 'zzz' value goes into zzzs."""
+        C = self.n_local
+        if len(compact) != C:
+            raise ValueError(f"compact: one set of compact layers per client ({C}), got {len(compact)}")
+        names, given = None, []
+        for ci, w in enumerate(compact):
+            if hasattr(w, "_weights") or isinstance(w, dict):
+                order, layers = _client_layers(w)
+            else:
+                layers = {f"l{i:05d}": v for i, v in enumerate(w)}          # (a bare list: the compact layers in walking order)
+                order = list(layers)
+            layers = dict(layers)
+            if "zzz" in layers:
+                z = layers.pop("zzz")
+                if interop.is_foreign(z):
+                    raise TypeError("the sparse job's 'zzz' layer must be a host value")
+                z = np.asarray(z)
+                if z.size != 1:
+                    raise ValueError(f"client {ci}: the 'zzz' layer holds {z.size} values, the sparsifier's holds one")
+                zzzs[ci] = z
+                order = [k for k in order if k != "zzz"]
+            if names is None:
+                names = order
+            elif order != names:
+                raise ValueError(f"client {ci}: the compact layers {order} are not client 0's {names}")
+            given.append(layers)
+        rows, all_host = [], []
+        for ci, layers in enumerate(given):
+            row = [_layer_source(self.engine, layers[k], f"client {ci} compact layer {k!r}")[:4] for k in names]
+            if ci and [r[3] for r in row] != [r[3] for r in rows[0]]:
+                raise ValueError(f"client {ci}: the compact layers have sizes {[r[3] for r in row]}, client 0's {[r[3] for r in rows[0]]}")
+            rows.append(row)
+            all_host.append(all(isinstance(r[0], np.ndarray) for r in row))
+        return names, rows, all_host, given
+
+    def _zzz_values(self, zzzs, normalize, L):
+        """(the clients' 'zzz' values, are they quantised in float64?): the trailing layer as the host path takes it -- normalised with its
+        own mean (NumPy's in-place rule), alpha 1.0, not encrypted."""
+        q = self.lead.quantizer
         zvals, z64 = [], True
         for z in zzzs:
             a = np.ascontiguousarray(z).reshape(-1)
@@ -1910,76 +1899,67 @@ class FlasheSparseCohort(object):
                 a = (a.astype(_loop_dtype(a.dtype, shift)) + shift).astype(a.dtype)
             z64 = _loop_dtype(a.dtype, 1.0) == np.float64
             zvals.append(float(a[0]))
-        # the draws, client-major with stride K + 1: from the global stream ONE stretch of C (K + 1) draws (the clients draw one after the
-        # other, each its K values and then its 'zzz'), in device calls of at most _RNG_RUN_MAX draws whatever client they belong to
-        dev_rng = os.environ.get("FLASHE_DEVICE_RNG", "1") != "0"
-        du = eng.alloc(max(8 * C * (K + 1), 16))
-        for seed, first, count in ([(None, 0, C * (K + 1))] if seeds is None else [(seeds[ci], ci * (K + 1), K + 1) for ci in range(C)]):
-            if seed is not None:
-                np.random.seed(seed)
-            mt = dev_rng and np.random.get_state()[0] == "MT19937"
-            for a0 in range(first, first + count, _RNG_RUN_MAX):
-                tot = min(_RNG_RUN_MAX, first + count - a0)
-                if mt and tot >= DEVICE_RNG_MIN:
-                    eng.numpy_random_dev(tot, out=du.ptr + 8 * a0)
-                else:
-                    du.upload_at(8 * a0, np.random.random(tot))
-        ups = [DeviceVector(eng, K + 1) for _ in range(C)]
-        zbuf = eng.alloc(max(8 * C, 16))
-        # the uploads: ONE chained launch from the floats where the plan says so (int_bits 16 - 32: no plaintext vector in HBM, the
-        # launch count does not grow with C), else -- or when the library declines -- the quantise launch and the encrypts
+        return zvals, z64
+
+    def _launch_uploads(self, path, K, table, srcs, dts, du, zvals, z64, ups, zbuf):
+        """The uploads: ONE chained launch from the floats where the plan says so (int_bits 16 - 32: no plaintext vector in HBM, the launch
+        count does not grow with C), else -- or when the library declines -- the quantise launch into plaintexts; the encrypts follow
+        with the aggregate.  Returns (front end that ran, the plaintexts' buffer, client c's plaintext pointer)."""
+        from . import cipher as _cipher_mod
+        ld = self.lead
+        q, c = ld.quantizer, ld.cipher
+        eng, C = c.engine, self.n_local
         front, _why = _sparse_front_end(path, "", ld.int_bits, C, K)
         if self.prefer_front_end == FRONT_STAGED:
             front = FRONT_STAGED
         fused = getattr(eng, "quantize_encrypt_sparse_cohort_dev", None) if front == FRONT_FUSED else None
-        if fused is None or not fused(c.iter_index, [self.first_idx + ci for ci in range(C)], K, _cipher_mod.N_JOBS, table, srcs, dts, q.element_bits,
-                                      du, K + 1, zvals, z64, [u.buf for u in ups], zbuf):
-            front = FRONT_STAGED
-        ptbuf, pts = None, None
-        if front == FRONT_STAGED:
-            pstride = (8 * K + 15) & ~15
-            ptbuf = eng.alloc(max(C * pstride, 16))
-            pts = [ptbuf.ptr + ci * pstride for ci in range(C)]
-            eng.quantize_cohort_dev(K, table, srcs, dts, q.element_bits, du, K + 1, zvals, z64, pts, [u.ptr + 8 * eng.limbs * K for u in ups], zbuf)
-        zeros = [int(v) for v in zbuf.download(np.uint64, C)]          # the C quantised zeros: the one download of the step
+        if fused is not None and fused(c.iter_index, [self.first_idx + ci for ci in range(C)], K, _cipher_mod.N_JOBS, table, srcs, dts, q.element_bits,
+                                       du, K + 1, zvals, z64, [u.buf for u in ups], zbuf):
+            return FRONT_FUSED, None, None
+        pstride = (8 * K + 15) & ~15
+        ptbuf = eng.alloc(max(C * pstride, 16))
+        pts = [ptbuf.ptr + ci * pstride for ci in range(C)]
+        eng.quantize_cohort_dev(K, table, srcs, dts, q.element_bits, du, K + 1, zvals, z64, pts, [u.ptr + 8 * eng.limbs * K for u in ups], zbuf)
+        return FRONT_STAGED, ptbuf, pts
+
+    def _aggregate(self, front, K, pts, ups, zeros):
+        """(aggregate, span bounds or None) of the cohort's uploads: the sparse aggregate of the ciphertexts the fused front end wrote, or
+        the encrypts of the staged front end's plaintexts with it -- one fused launch over strictly increasing lists, which takes their
+        span bounds and, when the cohort is the federation, leaves them to the decrypt."""
+        from . import cipher as _cipher_mod
+        from .engine import DeviceVector
+        c = self.lead.cipher
+        eng, C = c.engine, self.n_local
         own = self._lists[self.first_idx:self.first_idx + C]
         locs, lks = [b for b, _k in own], [k for _b, k in own]
         total = int(c.total)
         agg = DeviceVector(eng, total)
-        bounds = None
+        outs, zs = [u.buf for u in ups], [[z, 0] for z in zeros]
+        bounds = self._round_bounds(total, locs, lks) if self._sorted else None
         if front == FRONT_FUSED:
-            # the ciphertexts are written: the aggregate each branch below runs, on the uploads
-            if self._sorted:
-                if self._bounds is not None and self._bounds[1] == (total, C):
-                    bounds = self._bounds[0].recompute(locs, lks)
-                else:
-                    bounds = eng.span_bounds(total, locs, lks)
-                self._bounds = (bounds, (total, C))
-                eng.sparse_aggregate_dev(total, locs, lks, [u.buf for u in ups], [[z, 0] for z in zeros], agg.buf, bounds=bounds)
+            if bounds is not None:
+                eng.sparse_aggregate_dev(total, locs, lks, outs, zs, agg.buf, bounds=bounds)
             else:
-                eng.sparse_aggregate_dev(total, locs, lks, [u.buf for u in ups], [[z, 0] for z in zeros], agg.buf, sorted_lists=False)
-        elif self._sorted:
-            # the span bounds of the round's lists, once: the fused encrypt + aggregate takes them and, when the cohort is the federation,
-            # so does the decrypt.  A handle of the same shape is recomputed (the list buffers may have been rewritten in place).
-            if self._bounds is not None and self._bounds[1] == (total, C):
-                bounds = self._bounds[0].recompute(locs, lks)
-            else:
-                bounds = eng.span_bounds(total, locs, lks)
-            self._bounds = (bounds, (total, C))
-            eng.sparse_encrypt_aggregate_dev(c.iter_index, [self.first_idx + ci for ci in range(C)], locs, lks, pts, 1, [[z, 0] for z in zeros], total,
-                                             _cipher_mod.N_JOBS, [u.buf for u in ups], agg.buf, bounds=bounds)
+                eng.sparse_aggregate_dev(total, locs, lks, outs, zs, agg.buf, sorted_lists=False)
+        elif bounds is not None:
+            eng.sparse_encrypt_aggregate_dev(c.iter_index, [self.first_idx + ci for ci in range(C)], locs, lks, pts, 1, zs, total, _cipher_mod.N_JOBS, outs,
+                                             agg.buf, bounds=bounds)
         else:
             for ci in range(C):
                 eng.encrypt_dev(c.iter_index, self.first_idx + ci, 0, K, _cipher_mod.N_JOBS, pts[ci], 1, ups[ci].buf)
-            eng.sparse_aggregate_dev(total, locs, lks, [u.buf for u in ups], [[z, 0] for z in zeros], agg.buf, sorted_lists=False)
-        eng.hold(keep + [du, zbuf] + ([ptbuf] if ptbuf is not None else []))
-        ld.shape_dict = {k: (kl,) for k, kl in zip(names, ks)}
-        for u in ups:
-            u.mark_ready()
-        agg.mark_ready()
-        self._last = SparseCohortUpload(ups, agg, SPARSE_COHORT, front)
-        self._last_bounds = bounds if self.n_local == self.num_clients else None
-        return self._last
+            eng.sparse_aggregate_dev(total, locs, lks, outs, zs, agg.buf, sorted_lists=False)
+        return agg, bounds
+
+    def _round_bounds(self, total, locs, lks):
+        """The span bounds of the round's lists, once: the aggregate takes them and, when the cohort is the federation, so does the decrypt.
+        A handle of the same shape is recomputed (the list buffers may have been rewritten in place)."""
+        shape = (total, self.n_local)
+        if self._bounds is not None and self._bounds[1] == shape:
+            bounds = self._bounds[0].recompute(locs, lks)
+        else:
+            bounds = self.engine.span_bounds(total, locs, lks)
+        self._bounds = (bounds, shape)
+        return bounds
 
     def _per_client(self, per_client_layers, names, zzzs, all_host, normalize, seeds):
         """The clients' own FlasheClient steps one after the other on the shared quantiser state (one cipher re-indexed per client; with

@@ -629,32 +629,22 @@ class Engine:
         sum and the cohort's decrypt mask.  Returns False -- nothing was launched -- when the library declines the shape (FLASHE_ENOTSUP:
         the caller quantises per client and calls encrypt_batch_sum_dev), True otherwise."""
         arr, nl = self._tensor_layers(layers)
-        C = len(srcs)
-        ps = (c_vp * max(C * nl, 1))(*[int(p) if p else None for row in srcs for p in row])
-        pd = (ctypes.c_int32 * max(C * nl, 1))(*[int(d) for row in dtypes for d in row])
+        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
         pc, _k = self._ptr_array(cts)
         rc = self._lib.flashe_quantize_encrypt_cohort_dev(self._h, it, int(first_idx), C, int(n), n_jobs, arr, nl, ps, pd, element_bits,
                                                           self._ptr(u), pc, self._ptr(sum_out), self._ptr(dmask))
-        if rc == _lib.ENOTSUP:
-            return False
-        self._check(rc)
-        return True
+        return self._took(rc)
 
     def quantize_encrypt_cohort_u32_dev(self, it, first_idx, n, n_jobs, layers, srcs, dtypes, element_bits, u, cts, sum_out):
         """quantize_encrypt_cohort_dev in the compact layout (flashe_quantize_encrypt_cohort_u32_dev, int_bits 16 / 20 / 23 / 24 / 32): cts and
         sum_out are uint32 vectors of n elements, there is no decrypt mask.  Returns False -- nothing was launched -- when the library
         declines the shape (FLASHE_ENOTSUP: the caller quantises per client and calls encrypt_batch_sum_u32_dev), True otherwise."""
         arr, nl = self._tensor_layers(layers)
-        C = len(srcs)
-        ps = (c_vp * max(C * nl, 1))(*[int(p) if p else None for row in srcs for p in row])
-        pd = (ctypes.c_int32 * max(C * nl, 1))(*[int(d) for row in dtypes for d in row])
+        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
         pc, _k = self._ptr_array(cts)
         rc = self._lib.flashe_quantize_encrypt_cohort_u32_dev(self._h, it, int(first_idx), C, int(n), n_jobs, arr, nl, ps, pd, element_bits,
                                                               self._ptr(u), pc, self._ptr(sum_out))
-        if rc == _lib.ENOTSUP:
-            return False
-        self._check(rc)
-        return True
+        return self._took(rc)
 
     def quantize_batch_encrypt_cohort_dev(self, it, first_idx, n_values, n_elems, n_jobs, layers, srcs, dtypes, element_bits, field_bits, u, cts,
                                           sum_out, dmask=None):
@@ -664,16 +654,11 @@ class Engine:
         launched -- when the library declines the shape (FLASHE_ENOTSUP: the caller runs quantize_batch_tensors_dev per client and
         encrypt_batch_sum_dev), True otherwise."""
         arr, nl = self._tensor_layers(layers)
-        C = len(srcs)
-        ps = (c_vp * max(C * nl, 1))(*[int(p) if p else None for row in srcs for p in row])
-        pd = (ctypes.c_int32 * max(C * nl, 1))(*[int(d) for row in dtypes for d in row])
+        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
         pc, _k = self._ptr_array(cts)
         rc = self._lib.flashe_quantize_batch_encrypt_cohort_dev(self._h, it, int(first_idx), C, int(n_values), int(n_elems), n_jobs, arr, nl, ps, pd,
                                                                 element_bits, field_bits, self._ptr(u), pc, self._ptr(sum_out), self._ptr(dmask))
-        if rc == _lib.ENOTSUP:
-            return False
-        self._check(rc)
-        return True
+        return self._took(rc)
 
     def cohort_masks_dev(self, it, first_idx, n_clients, n, n_jobs, masks, compact=False):
         """A cohort's precomputed encrypt masks as ONE chain of n_clients + 1 streams into the caller's vectors:
@@ -691,9 +676,7 @@ class Engine:
         plaintext + masks[c]) mod 2^b and sum_out (optional) = their sum.  layers / srcs / dtypes / u as quantize_encrypt_cohort_dev.
         Returns False -- nothing was launched -- when the library declines (FLASHE_ENOTSUP), True otherwise."""
         arr, nl = self._tensor_layers(layers)
-        C = len(srcs)
-        ps = (c_vp * max(C * nl, 1))(*[int(p) if p else None for row in srcs for p in row])
-        pd = (ctypes.c_int32 * max(C * nl, 1))(*[int(d) for row in dtypes for d in row])
+        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
         pm, _a = self._ptr_array(masks)
         pc, _b = self._ptr_array(cts)
         if batch is not None:
@@ -703,10 +686,7 @@ class Engine:
         else:
             fn = self._lib.flashe_quantize_combine_cohort_u32_dev if compact else self._lib.flashe_quantize_combine_cohort_dev
             rc = fn(self._h, C, int(n), arr, nl, ps, pd, element_bits, self._ptr(u), pm, pc, self._ptr(sum_out))
-        if rc == _lib.ENOTSUP:
-            return False
-        self._check(rc)
-        return True
+        return self._took(rc)
 
     def combine_unbatch_unquantize_model_dev(self, layers, element_bits, field_bits, num_clients, inp, add, minus, n_elems, out):
         """unbatch_unquantize_model_dev over (inp + add - minus) mod 2^b, one memory-bound pass (add / minus: device vectors of n_elems
@@ -740,6 +720,21 @@ class Engine:
         for i, (start, ptr, alpha, shift, dtype, flags) in enumerate(layers):
             arr[i].start, arr[i].ptr, arr[i].alpha, arr[i].shift, arr[i].dtype, arr[i].flags = int(start), ptr, float(alpha), float(shift), int(dtype), int(flags)
         return arr, len(layers)
+
+    @staticmethod
+    def _cohort_sources(srcs, dtypes, nl):
+        """(C, pointers, dtype codes) of a cohort launch: srcs[c][l] / dtypes[c][l] flattened client-major into C * nl entries."""
+        C = len(srcs)
+        ps = (c_vp * max(C * nl, 1))(*[int(p) if p else None for row in srcs for p in row])
+        pd = (ctypes.c_int32 * max(C * nl, 1))(*[int(d) for row in dtypes for d in row])
+        return C, ps, pd
+
+    def _took(self, rc):
+        """False when the library declined the shape (FLASHE_ENOTSUP: nothing was launched); any other error raises; True otherwise."""
+        if rc == _lib.ENOTSUP:
+            return False
+        self._check(rc)
+        return True
 
     def memset_dev(self, buf, byte, nbytes):
         """Fills the first nbytes of a device buffer with `byte` (asynchronous on the ctx stream)."""
@@ -1430,10 +1425,8 @@ class Engine:
         values, locations and packed locations are block c of the equal-stride buffers (byte strides for residual / vals, entries for loc,
         limbs for packed), each block in sparsify_tensors_dev's layout."""
         arr, nl = self._tensor_layers([(start, None, 1.0, 0.0, dtype, 0) for start, dtype in layers])
-        C = len(srcs)
+        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
         ak = (c_u64 * max(nl, 1))(*[int(v) for v in ks])
-        ps = (c_vp * max(C * nl, 1))(*[int(p) if p else None for row in srcs for p in row])
-        pd = (ctypes.c_int32 * max(C * nl, 1))(*[int(d) for row in dtypes for d in row])
         self._check(self._lib.flashe_sparsify_cohort_tensors_dev(self._h, C, int(n), arr, nl, ak, ps, pd, self._ptr(residual), int(residual_stride),
                                                                  self._ptr(loc), int(loc_stride), self._ptr(vals), int(vals_stride), self._ptr(packed),
                                                                  int(packed_stride), int(bits)))
@@ -1444,9 +1437,7 @@ class Engine:
         takes the draw u[c * u_stride + j], its 'zzz' value zzz[c] the draw u[c * u_stride + n]; pts[c] = its n one-limb plaintexts,
         tails[c] (or None) = where its quantised 'zzz' goes as a ciphertext-width element; zeros = device uint64[C] of those values."""
         arr, nl = self._tensor_layers(layers)
-        C = len(srcs)
-        ps = (c_vp * max(C * nl, 1))(*[int(p) if p else None for row in srcs for p in row])
-        pd = (ctypes.c_int32 * max(C * nl, 1))(*[int(d) for row in dtypes for d in row])
+        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
         pz = (ctypes.c_double * max(C, 1))(*[float(z) for z in zzz])
         pp, _kp = self._ptr_array(pts)
         pt, _kt = self._ptr_array(tails) if tails is not None else (None, None)
@@ -1460,18 +1451,13 @@ class Engine:
         ciphertexts, then the plain quantised 'zzz').  Returns False -- nothing was launched -- when the library declines the shape
         (FLASHE_ENOTSUP: the caller runs quantize_cohort_dev and the encrypts), True otherwise."""
         arr, nl = self._tensor_layers(layers)
-        C = len(srcs)
-        ps = (c_vp * max(C * nl, 1))(*[int(p) if p else None for row in srcs for p in row])
-        pd = (ctypes.c_int32 * max(C * nl, 1))(*[int(d) for row in dtypes for d in row])
+        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
         pz = (ctypes.c_double * max(C, 1))(*[float(z) for z in zzz])
         ii = (ctypes.c_uint32 * max(C, 1))(*[int(v) for v in idx])
         pc, _kc = self._ptr_array(cts)
         rc = self._lib.flashe_quantize_encrypt_sparse_cohort_dev(self._h, it, C, ii, int(n), n_jobs, arr, nl, ps, pd, int(element_bits), self._ptr(u),
                                                                  int(u_stride), pz, 1 if zzz_is_f64 else 0, pc, self._ptr(zeros))
-        if rc == _lib.ENOTSUP:
-            return False
-        self._check(rc)
-        return True
+        return self._took(rc)
 
     def sparsify_batch(self, layers, ks, residuals=None):
         """[(loc uint32[k_l] ascending, vals[k_l], new residual or None) per layer] -- Client.sparsify's layer loop
