@@ -174,22 +174,37 @@ def _tensor_flags(hdt, alpha, normalize, mean):
     return float(shift), flags
 
 
+def _size(shape):
+    """The number of values of a layer of that shape, as a Python int (it reaches ctypes)."""
+    return int(math.prod(shape))
+
+
+def _draws_on_device(count):
+    """Does a call for `count` draws of NumPy's global stream generate them on the device?  FLASHE_DEVICE_RNG not 0, DEVICE_RNG_MIN draws
+    or more, and the stream is MT19937 (the generator the device call continues and jumps ahead)."""
+    from .quantize import DEVICE_RNG_MIN
+    return os.environ.get("FLASHE_DEVICE_RNG", "1") != "0" and count >= DEVICE_RNG_MIN and np.random.get_state()[0] == "MT19937"
+
+
+def _draws(eng, count):
+    """The next `count` stochastic-rounding draws of NumPy's global stream as a device buffer: generated on the device
+    (_draws_on_device), else drawn on the host and uploaded."""
+    return eng.numpy_random_dev(count) if _draws_on_device(count) else eng.upload(np.random.random(count))
+
+
 def _cohort_draws(eng, C, per_client, seeds):
     """The stochastic-rounding draws of C clients, client-major, as a device buffer: client c's are draws [c per_client, (c + 1) per_client).
     From the global stream (seeds=None) they are ONE stretch of C per_client draws -- the clients draw one after the other -- generated in
     device calls of at most _RNG_RUN_MAX draws whatever client they belong to (the jump-ahead of a device call is paid per call, not per
-    client); with seeds every client's stretch starts at its own seed.  On the device under quantize_encrypt's rule (FLASHE_DEVICE_RNG,
-    MT19937, DEVICE_RNG_MIN draws or more in the call), else drawn on the host and uploaded."""
-    from .quantize import DEVICE_RNG_MIN
-    dev_rng = os.environ.get("FLASHE_DEVICE_RNG", "1") != "0"
+    client); with seeds every client's stretch starts at its own seed.  On the device under quantize_encrypt's rule (_draws_on_device, per
+    call), else drawn on the host and uploaded."""
     du = eng.alloc(max(8 * C * per_client, 16))
     for seed, first, count in ([(None, 0, C * per_client)] if seeds is None else [(seeds[ci], ci * per_client, per_client) for ci in range(C)]):
         if seed is not None:
             np.random.seed(seed)
-        mt = dev_rng and np.random.get_state()[0] == "MT19937"
         for at in range(first, first + count, _RNG_RUN_MAX):
             tot = min(_RNG_RUN_MAX, first + count - at)
-            if mt and tot >= DEVICE_RNG_MIN:
+            if _draws_on_device(tot):
                 eng.numpy_random_dev(tot, out=du.ptr + 8 * at)
             else:
                 du.upload_at(8 * at, np.random.random(tot))
@@ -302,7 +317,7 @@ class FlasheClient(object):
         only_key = weights.walking_order[0]
         flat = weights._weights[only_key]
         for k, shape in self.shape_dict.items():
-            size = int(np.prod(shape))
+            size = _size(shape)
             weights._weights[k] = flat[:size].reshape(shape)
             flat = flat[size:]
         weights.walking_order = sorted(weights._weights.keys(), key=str)
@@ -394,10 +409,7 @@ class FlasheClient(object):
         batch + encrypt becomes one launch -- and consumed as the call-by-call encrypt consumes them; a single-mask cipher ignores them
         and drops 'add' as the reference does.  Batched sparse jobs, sparse jobs with a cache and masks a caller assigned as plain arrays
         take the same sequence call by call on the host and return object arrays like the reference."""
-        from . import cipher as _cipher_mod
-        from .engine import DeviceVector
-        from .quantize import DEVICE_RNG_MIN
-        q, c = self.quantizer, self.cipher
+        q = self.quantizer
         if any(interop.is_foreign(weights._weights[k]) for k in weights.walking_order):
             return self._quantize_encrypt_tensors(weights, device, normalize)
         if normalize:
@@ -414,96 +426,105 @@ class FlasheClient(object):
             ct = self.cipher.encrypt(flat)
             weights._weights[k0] = np.append(ct, [zero_quantized]) if sparse else ct
             return weights
+        return self._encrypt_tail(weights, device, *self._host_front_end(weights))
+
+    def _host_front_end(self, weights):
+        """The fused step's front end for host layers (normalised on the host already, layer_size_list set): every layer goes up once,
+        widened on the host to the dtype NumPy's clip / scale arithmetic with its alpha runs in, and the launches are the *_model_dev entry
+        points over 4-field rows (start -- batched: size --, pointer, alpha, is float64).  Returns _encrypt_tail's arguments."""
+        q, c = self.quantizer, self.cipher
         eng = c.engine
         mode = self._prepared_mode(c.next_iter_encrypt_prepared)
         alphas = _round_alphas(q, q.layer_size_list)
         q.r_max_list, q.alpha_list = [], []
         c.set_idx_list(mode="encrypt")
-        scheme = 1 if c.masking_scheme == "double" else 0
-        order = list(weights.walking_order)
-        zzz = None
+        order, zzz = list(weights.walking_order), None
         if "zzz" in weights._weights:                       # (_fusable: it closes the walking order)
             zzz = np.asarray(weights._weights["zzz"])
             order = order[:-1]
-        host, starts, offs, shape_dict = [], [], [], {}
-        n, nbytes = 0, 0
+        host, sizes, starts, shape_dict, n = [], [], [], {}, 0
         for li, k in enumerate(order):
             alpha = alphas[li]
             q.r_max_list.append(alpha * q.num_clients)
             q.alpha_list.append(alpha)
-            layer = np.asarray(weights._weights[k])
-            shape_dict[k] = layer.shape
-            flat = np.ascontiguousarray(layer).reshape(-1)
-            if flat.dtype not in (np.float32, np.float64):
-                flat = flat.astype(np.float64)
-            want = _loop_dtype(flat.dtype, alpha)                         # the dtype NumPy's clip / scale arithmetic runs in
-            if flat.dtype != want:
-                flat = flat.astype(want)
-            host.append(flat)
+            flat, _code, hdt, size, shape_dict[k] = _layer_source(eng, weights._weights[k], f"layer {k!r}")
+            want = _loop_dtype(hdt, alpha)                         # the dtype NumPy's clip / scale arithmetic runs in
+            host.append(flat if hdt == want else flat.astype(want))
+            sizes.append(size)
             starts.append(n)
-            offs.append(nbytes)
-            n += int(flat.size)
-            nbytes += (flat.nbytes + 15) & ~15
-        xbuf = eng.alloc(max(nbytes, 16))
-        for flat, off in zip(host, offs):
-            xbuf.upload_at(off, flat)
-        dev_rng = os.environ.get("FLASHE_DEVICE_RNG", "1") != "0" and np.random.get_state()[0] == "MT19937"
+            n += size
+        ptrs, keep = _stage_host_layers(eng, host)
+        rows = [(sizes[li] if self.batch else starts[li], ptrs[li], q.alpha_list[li], host[li].dtype == np.float64) for li in range(len(order))]
+        launch = (eng.quantize_encrypt_model_dev, eng.quantize_encrypt_prepared_model_dev, eng.quantize_batch_model_dev,
+                  eng.quantize_batch_encrypt_prepared_model_dev)
+        return mode, order, zzz, sizes, starts, shape_dict, rows, launch, keep
+
+    def _encrypt_tail(self, weights, device, mode, order, zzz, sizes, starts, shape_dict, rows, launch, keep, hold=None, normalize=False):
+        """The fused step behind either front end: the draws, the launches and the result.  `rows` are the layers `order` (sizes, starts,
+        shape_dict) as the four entry points in `launch` -- un-batched online and prepared, batched online and prepared -- read them; mode
+        is _prepared_mode of the encrypt cache; zzz the sparse job's trailing value (host) or None; keep what the launches read: it lives to
+        the end of the call.  The tensor front end also passes hold (the owners of the caller's tensors: held on the engine until the
+        launches have finished) and normalize (the 'zzz' value is still to be normalised -- the host front end has normalised the whole
+        model)."""
+        from . import cipher as _cipher_mod
+        from .engine import DeviceVector
+        q, c = self.quantizer, self.cipher
+        eng, n = c.engine, sum(sizes)
+        online, prepared, batch, batch_prepared = launch
+        scheme = 1 if c.masking_scheme == "double" else 0
         if self.batch:
             # quantise + batch of the whole model in ONE launch (per-layer alpha, per-layer zero padding), then the encrypt of the flattened
             # batched vector: the draws are one stretch of NumPy's stream over all VALUES in walking order
             field_bits = _field_bits(q.element_bits, q.num_clients)
             bs = self.int_bits // field_bits
             q.shape_list = [shape_dict[k] for k in order]
-            n_elems = sum((int(h.size) + bs - 1) // bs for h in host)
+            n_elems = sum((s_ + bs - 1) // bs for s_ in sizes)
             if mode == "ctx":
                 self._refuse_prepared_len(n_elems, n)
-            du = (eng.numpy_random_dev(n) if dev_rng and n >= DEVICE_RNG_MIN else eng.upload(np.random.random(n))) if n else eng.alloc(16)
-            blayers = [(int(host[li].size), xbuf.ptr + offs[li], q.alpha_list[li], host[li].dtype == np.float64) for li in range(len(order))]
+            du = _draws(eng, n) if n else eng.alloc(16)
             ct = DeviceVector(eng, n_elems)
             if mode == "ctx":                   # quantise + batch + the prepared masks: one launch, no AES
-                eng.quantize_batch_encrypt_prepared_model_dev(blayers, q.element_bits, field_bits, du, n_elems, ct.buf)
+                batch_prepared(rows, q.element_bits, field_bits, du, n_elems, ct.buf)
             else:
                 pt = eng.alloc_vec(max(n_elems, 1))
-                eng.quantize_batch_model_dev(blayers, q.element_bits, field_bits, du, n_elems, pt)
+                batch(rows, q.element_bits, field_bits, du, n_elems, pt)
                 if n_elems:
                     eng.encrypt_dev(c.iter_index, c.idx, scheme, n_elems, _cipher_mod.N_JOBS, pt, eng.limbs, ct.buf)
-            self._encrypt_done(mode)
-            for k in order:
-                del weights._weights[k]
-            self.shape_dict = {k: ((int(h.size) + bs - 1) // bs,) for k, h in zip(order, host)}      # the batched layers are 1-D (:448)
-            if order:
-                weights._weights[order[0]] = ct.mark_ready() if device else ct.to_host()
-            weights.walking_order = sorted(weights._weights.keys(), key=str)
-            return weights
-        table = [(starts[li], xbuf.ptr + offs[li], q.alpha_list[li], host[li].dtype == np.float64) for li in range(len(order))]
-        ct = DeviceVector(eng, n + (1 if zzz is not None else 0))
-        # the draws of consecutive layers are ONE stretch of NumPy's stream (np.random.random(layer.shape) per layer in walking order,
-        # jzf_quantize.py:55-67 under :417-462), i.e. flat element j takes draw j: a run of whole layers is drawn by one device call and
-        # quantised + encrypted by one launch over its range.  Runs are capped so the draws of a huge model stay bounded.  With the ctx's
-        # prepared masks the launches add them in place of the PRF streams; the run that ends the vector consumes them.
-        if mode == "ctx":
-            self._refuse_prepared_len(n, n)
-        at = 0
-        while at < len(order):
-            end, tot = at, 0
-            while end < len(order) and (end == at or tot + host[end].size <= _RNG_RUN_MAX):
-                tot += int(host[end].size)
-                end += 1
-            if tot:
-                du = eng.numpy_random_dev(tot) if dev_rng and tot >= DEVICE_RNG_MIN else eng.upload(np.random.random(tot))
-                first = starts[at]
-                if mode == "ctx":
-                    eng.quantize_encrypt_prepared_model_dev(n, first, tot, table, q.element_bits, du, ct.ptr + first * eng.limbs * 8)
-                else:
-                    eng.quantize_encrypt_model_dev(c.iter_index, c.idx, scheme, n, _cipher_mod.N_JOBS, first, tot, table, q.element_bits, du,
-                                                   ct.ptr + first * eng.limbs * 8)
-            at = end
-        if mode == "ctx" and n == 0:
-            eng.prepared_discard(eng.PREPARED_ENCRYPT)          # (nothing to add the masks to: consumed all the same)
+            shape_dict = {k: ((s_ + bs - 1) // bs,) for k, s_ in zip(order, sizes)}      # the batched layers are 1-D (:448)
+        else:
+            # the draws of consecutive layers are ONE stretch of NumPy's stream (np.random.random(layer.shape) per layer in walking order,
+            # jzf_quantize.py:55-67 under :417-462), i.e. flat element j takes draw j: a run of whole layers is drawn by one device call and
+            # quantised + encrypted by one launch over its range.  Runs are capped so the draws of a huge model stay bounded.  With the ctx's
+            # prepared masks the launches add them in place of the PRF streams; the run that ends the vector consumes them.
+            if mode == "ctx":
+                self._refuse_prepared_len(n, n)
+            ct = DeviceVector(eng, n + (1 if zzz is not None else 0))
+            at = 0
+            while at < len(order):
+                end, tot = at, 0
+                while end < len(order) and (end == at or tot + sizes[end] <= _RNG_RUN_MAX):
+                    tot += sizes[end]
+                    end += 1
+                if tot:
+                    du, first = _draws(eng, tot), starts[at]
+                    if mode == "ctx":
+                        prepared(n, first, tot, rows, q.element_bits, du, ct.ptr + first * eng.limbs * 8)
+                    else:
+                        online(c.iter_index, c.idx, scheme, n, _cipher_mod.N_JOBS, first, tot, rows, q.element_bits, du,
+                               ct.ptr + first * eng.limbs * 8)
+                at = end
+            if mode == "ctx" and n == 0:
+                eng.prepared_discard(eng.PREPARED_ENCRYPT)          # (nothing to add the masks to: consumed all the same)
         self._encrypt_done(mode)
+        if hold is not None:
+            eng.hold(hold)
         if zzz is not None:
-            # the trailing layer: the next draw of the stream, alpha 1.0, not encrypted (:735-743 strips it before and re-appends it after)
+            # the trailing layer: (normalised with its own mean, then) the next draw of the stream, alpha 1.0, not encrypted (:735-743
+            # strips it before and re-appends it after)
             from .quantize import _as_object, _static_quantize_padding_asymmetric
+            if normalize:
+                d, a = q._shift(zzz, -q.past_layer_mean_list[len(order)])
+                zzz = d.download(a.dtype, a.size).reshape(a.shape)
             flat = zzz.flatten()
             want = _loop_dtype(flat.dtype, 1.0)
             if flat.dtype != want:
@@ -536,7 +557,6 @@ class FlasheClient(object):
         decrypt + unbatch becomes one launch); the prefixes set_idx_list leaves uncovered (dropouts) go through a PRF launch first.  The
         cache is consumed as the call-by-call decrypt consumes it; the encrypt cache of the next round is not touched.  Masks a caller
         assigned as plain arrays take the same sequence call by call."""
-        from .engine import DeviceVector
         q, c = self.quantizer, self.cipher
         if out is not None:
             return self._decrypt_unquantize_tensors(weights, out, unnormalize)
@@ -554,21 +574,8 @@ class FlasheClient(object):
         sparse_dev = (self.fuse and c.masks is not None and c.masking_scheme == "single" and not self.batch and c.prp_seed is not None
                       and set(prep) == {"minus"} and isinstance(prep["minus"], _SparseMinus) and hasattr(c.engine, "unquantize_model_dev"))
         if sparse_dev:
-            eng = c.engine
-            dec = self.cipher.decrypt(weights._weights[k0], device=True)                 # the sparse minus-mask pass, result in HBM
-            dec = c._as_wide(dec)
-            n = len(dec)
-            sizes = [int(np.prod(shape)) for shape in self.shape_dict.values()]
-            if sum(sizes) > n:
-                raise ValueError(f"the aggregate has {n} elements, shape_dict describes {sum(sizes)}")
-            table, at = [], 0
-            for li, size in enumerate(sizes):
-                table.append((at, None, q.alpha_list[li], False))
-                at += size
-            dout = eng.alloc(max(8 * n, 16))
-            if n:
-                dec.wait_on(eng)
-                eng.unquantize_model_dev(n, 0, n, dec.buf, table, q.element_bits, q.num_clients, dout)
+            keep = []                                 # (the minus-mask pass's result: alive until the download has synchronised)
+            dout, n = self._sparse_floats(weights._weights[k0], [_size(shape) for shape in self.shape_dict.values()], keep)
             weights._weights[k0] = dout.download(np.float64, n)
             return self.unflatten_weights(weights)
         if not fus:
@@ -579,17 +586,11 @@ class FlasheClient(object):
             weights._weights[k0] = res
             return self.unquantize(self.unflatten_weights(weights))
         add_idx, minus_idx = self._decrypt_prefixes(mode)
-        v = weights._weights[k0]
-        if not isinstance(v, DeviceVector):
-            v = np.asarray(v)
-            if v.dtype == object:
-                v = v.reshape(-1)
-        dv, _kind = c._on_device(v, full_width=True)
-        dv = c._as_wide(dv)                       # (a compact uint32 aggregate: the fused launch reads one-limb vectors)
+        dv = self._wide_aggregate(weights._weights[k0])
         n = len(dv)
         if self.batch:
             names = list(self.shape_dict)
-            sizes = [int(np.prod(shape)) for shape in q.shape_list]
+            sizes = [_size(shape) for shape in q.shape_list]
             out = self._decrypt_floats(dv, sizes, mode, add_idx, minus_idx).download(np.float64, sum(sizes))
             del weights._weights[k0]
             at = 0
@@ -598,7 +599,7 @@ class FlasheClient(object):
                 at += s_
             weights.walking_order = sorted(weights._weights.keys(), key=str)
             return weights
-        sizes = [int(np.prod(shape)) for shape in self.shape_dict.values()]
+        sizes = [_size(shape) for shape in self.shape_dict.values()]
         weights._weights[k0] = self._decrypt_floats(dv, sizes, mode, add_idx, minus_idx).download(np.float64, n)
         return self.unflatten_weights(weights)
 
@@ -614,6 +615,59 @@ class FlasheClient(object):
             raise KeyError('add')
         return add_idx, minus_idx
 
+    def _wide_aggregate(self, v, keep=None):
+        """The flattened aggregate -- a DeviceVector, uint64 limbs, object ints or, with `keep` (out=), a framework integer tensor, read
+        in place and its owner appended to keep -- as a DeviceVector of L limbs in HBM (a compact uint32 aggregate widened: the fused
+        launches read one-limb vectors)."""
+        from .engine import DeviceVector
+        c = self.cipher
+        if keep is not None and interop.is_foreign(v):
+            v, kv = c._foreign_vec(c.engine, v, "aggregate")
+            keep.append(kv)
+        elif not isinstance(v, DeviceVector):
+            v = np.asarray(v)
+            if v.dtype == object:
+                v = v.reshape(-1)
+        dv, _kind = c._on_device(v, full_width=True)
+        return c._as_wide(dv)
+
+    def _back_table(self, sizes, n):
+        """The back end's layer table over an aggregate of n elements: (start, None, alpha, False) per layer of `sizes`, the last layer
+        running to the end."""
+        q = self.quantizer
+        if sum(sizes) > n:
+            raise ValueError(f"the aggregate has {n} elements, shape_dict describes {sum(sizes)}")
+        table, at = [], 0
+        for li, size in enumerate(sizes):
+            table.append((at, None, q.alpha_list[li], False))
+            at += size
+        return table
+
+    def _batched_back_table(self, sizes, n):
+        """The same for a batched aggregate of n elements: ((size, None, alpha, False) per layer, field_bits), every layer padded to whole
+        elements on its own."""
+        q = self.quantizer
+        field_bits = _field_bits(q.element_bits, q.num_clients)
+        bs = self.int_bits // field_bits
+        if sum((s_ + bs - 1) // bs for s_ in sizes) != n:
+            raise ValueError(f"the aggregate has {n} elements, the batched layers describe {sum((s_ + bs - 1) // bs for s_ in sizes)}")
+        return [(s_, None, q.alpha_list[li], False) for li, s_ in enumerate(sizes)], field_bits
+
+    def _sparse_floats(self, v, sizes, keep):
+        """The sparse job's back end: the minus-mask pass over the aggregate v (result in HBM, appended to keep), then the unquantise of
+        the dense model in a second launch.  Returns (the n float64 values as a device buffer, n)."""
+        q, c = self.quantizer, self.cipher
+        eng = c.engine
+        dec = c._as_wide(c.decrypt(v, device=True))
+        n = len(dec)
+        table = self._back_table(sizes, n)
+        dout = eng.alloc(max(8 * n, 16))
+        if n:
+            dec.wait_on(eng)
+            eng.unquantize_model_dev(n, 0, n, dec.buf, table, q.element_bits, q.num_clients, dout)
+        keep.append(dec)
+        return dout, n
+
     def _decrypt_floats(self, dv, sizes, mode, add_idx, minus_idx):
         """The fused back end of the flattened aggregate `dv` (in HBM, L limbs): the model's float64 values in walking order as a device
         buffer -- batched: the sum(sizes) values of the layers (unbatch + `[:size]` + unquantise in one launch behind the decrypt); else
@@ -625,11 +679,7 @@ class FlasheClient(object):
         if mode == "ctx":
             c._check_prepared_len(c.next_iter_decrypt_prepared['add'], n)          # (the call-by-call decrypt's error; the cache stays)
         if self.batch:
-            field_bits = _field_bits(q.element_bits, q.num_clients)
-            bs = self.int_bits // field_bits
-            if sum((s_ + bs - 1) // bs for s_ in sizes) != n:
-                raise ValueError(f"the aggregate has {n} elements, the batched layers describe {sum((s_ + bs - 1) // bs for s_ in sizes)}")
-            layers = [(s_, None, q.alpha_list[li], False) for li, s_ in enumerate(sizes)]
+            layers, field_bits = self._batched_back_table(sizes, n)
             dout = eng.alloc(max(8 * sum(sizes), 16))
             if mode == "ctx":
                 eng.decrypt_prepared_unbatch_unquantize_model_dev(c.iter_index, add_idx, minus_idx, _cipher_mod.N_JOBS, layers, q.element_bits, field_bits,
@@ -641,12 +691,7 @@ class FlasheClient(object):
                 eng.unbatch_unquantize_model_dev(layers, q.element_bits, field_bits, q.num_clients, dec, n, dout)
             self._decrypt_done(mode)
             return dout
-        if sum(sizes) > n:
-            raise ValueError(f"the aggregate has {n} elements, shape_dict describes {sum(sizes)}")
-        table, at = [], 0
-        for li, size in enumerate(sizes):
-            table.append((at, None, q.alpha_list[li], False))
-            at += size
+        table = self._back_table(sizes, n)
         dout = eng.alloc(max(8 * n, 16))
         if mode == "ctx":
             eng.decrypt_prepared_unquantize_model_dev(c.iter_index, add_idx, minus_idx, n, _cipher_mod.N_JOBS, dv.buf, table, q.element_bits,
@@ -662,10 +707,9 @@ class FlasheClient(object):
         """quantize_encrypt with framework device tensors among the layers: each foreign layer is read in place (its own dtype; a layer
         that needs a conversion -- 16-bit, float32 quantised in float64, or normalised -- goes through one streaming pass into engine
         scratch, flashe_quantize_encrypt_tensors_dev / flashe_quantize_batch_tensors_dev), host layers go up as in the host path.  Bit for
-        bit the host path on `t.cpu().numpy()` (float16 / bfloat16: `t.float().cpu().numpy()`), with `normalize()` first when asked."""
-        from . import cipher as _cipher_mod
-        from .engine import DeviceVector
-        from .quantize import DEVICE_RNG_MIN
+        bit the host path on `t.cpu().numpy()` (float16 / bfloat16: `t.float().cpu().numpy()`), with `normalize()` first when asked.
+        The refusals, then the front end for tensors: 6-field rows (start, pointer, alpha, shift, dtype code, flags) for the *_tensors_dev
+        entry points, and _encrypt_tail behind them."""
         q, c = self.quantizer, self.cipher
         zzz = None
         if "zzz" in weights._weights:                 # the sparse job: compact layers (Sparsifier's CompactLayer or any tensors) + 'zzz'
@@ -692,95 +736,26 @@ class FlasheClient(object):
         if zzz is not None:
             order = order[:-1]
         layers = [_layer_source(eng, weights._weights[k], f"layer {k!r}") for k in order]
-        # (set_layer_size_list on the sizes the tensors report)
-        alphas = _round_alphas(q, [size for _x, _code, _d, size, _shape in layers] + ([int(zzz.size)] if zzz is not None else []))
+        sizes = [size for _x, _code, _hdt, size, _shape in layers]
+        alphas = _round_alphas(q, sizes + ([int(zzz.size)] if zzz is not None else []))      # (set_layer_size_list on the sizes the tensors report)
         q.r_max_list, q.alpha_list = [], []
         c.set_idx_list(mode="encrypt")
-        scheme = 1 if c.masking_scheme == "double" else 0
-        host_off, nbytes = {}, 0
-        for li, (x, _code, _dt, _size, _shape) in enumerate(layers):
-            if isinstance(x, np.ndarray):
-                host_off[li] = nbytes
-                nbytes += (x.nbytes + 15) & ~15
-        xbuf = eng.alloc(max(nbytes, 16)) if host_off else None
-        for li, off in host_off.items():
-            xbuf.upload_at(off, layers[li][0])
-        table, sizes, n, keep = [], [], 0, []
-        for li, (x, code, hdt, size, _shape) in enumerate(layers):
+        ptrs, keep = _stage_host_layers(eng, [x for x, _code, _hdt, _size, _shape in layers])
+        owners = [x.keep for x, _code, _hdt, _size, _shape in layers if not isinstance(x, np.ndarray)]
+        rows, starts, n = [], [], 0
+        for li, (_x, code, hdt, size, _shape) in enumerate(layers):
             alpha = alphas[li]
             q.r_max_list.append(alpha * q.num_clients)
             q.alpha_list.append(alpha)
             shift, flags = _tensor_flags(hdt, alpha, normalize, q.past_layer_mean_list[li])
-            if isinstance(x, np.ndarray):
-                ptr = xbuf.ptr + host_off[li]
-            else:
-                ptr = x.ptr
-                keep.append(x.keep)
-            table.append((n, ptr, alpha, shift, code, flags))
-            sizes.append(size)
+            rows.append((n, ptrs[li], alpha, shift, code, flags))
+            starts.append(n)
             n += size
-        dev_rng = os.environ.get("FLASHE_DEVICE_RNG", "1") != "0" and np.random.get_state()[0] == "MT19937"
+        launch = (eng.quantize_encrypt_tensors_dev, eng.quantize_encrypt_prepared_tensors_dev,                # (the batched two also take n)
+                  lambda r, *a: eng.quantize_batch_tensors_dev(r, n, *a),
+                  lambda r, *a: eng.quantize_batch_encrypt_prepared_tensors_dev(r, n, *a))
         shape_dict = {k: layer[4] for k, layer in zip(order, layers)}
-        if self.batch:
-            field_bits = _field_bits(q.element_bits, q.num_clients)
-            bs = self.int_bits // field_bits
-            q.shape_list = [shape_dict[k] for k in order]
-            n_elems = sum((s_ + bs - 1) // bs for s_ in sizes)
-            if mode == "ctx":
-                self._refuse_prepared_len(n_elems, n)
-            du = (eng.numpy_random_dev(n) if dev_rng and n >= DEVICE_RNG_MIN else eng.upload(np.random.random(n))) if n else eng.alloc(16)
-            ct = DeviceVector(eng, n_elems)
-            if mode == "ctx":
-                eng.quantize_batch_encrypt_prepared_tensors_dev(table, n, q.element_bits, field_bits, du, n_elems, ct.buf)
-            else:
-                pt = eng.alloc_vec(max(n_elems, 1))
-                eng.quantize_batch_tensors_dev(table, n, q.element_bits, field_bits, du, n_elems, pt)
-                if n_elems:
-                    eng.encrypt_dev(c.iter_index, c.idx, scheme, n_elems, _cipher_mod.N_JOBS, pt, eng.limbs, ct.buf)
-            self.shape_dict = {k: ((s_ + bs - 1) // bs,) for k, s_ in zip(order, sizes)}
-        else:
-            if mode == "ctx":
-                self._refuse_prepared_len(n, n)
-            ct = DeviceVector(eng, n + (1 if zzz is not None else 0))
-            at = 0
-            while at < len(order):                    # the draws in runs of whole layers, as in quantize_encrypt
-                end, tot = at, 0
-                while end < len(order) and (end == at or tot + sizes[end] <= _RNG_RUN_MAX):
-                    tot += sizes[end]
-                    end += 1
-                if tot:
-                    du = eng.numpy_random_dev(tot) if dev_rng and tot >= DEVICE_RNG_MIN else eng.upload(np.random.random(tot))
-                    first = table[at][0]
-                    if mode == "ctx":
-                        eng.quantize_encrypt_prepared_tensors_dev(n, first, tot, table, q.element_bits, du, ct.ptr + first * eng.limbs * 8)
-                    else:
-                        eng.quantize_encrypt_tensors_dev(c.iter_index, c.idx, scheme, n, _cipher_mod.N_JOBS, first, tot, table, q.element_bits, du,
-                                                         ct.ptr + first * eng.limbs * 8)
-                at = end
-            if mode == "ctx" and n == 0:
-                eng.prepared_discard(eng.PREPARED_ENCRYPT)
-            self.shape_dict = shape_dict
-        self._encrypt_done(mode)
-        eng.hold(keep)
-        if zzz is not None:
-            # the trailing layer as the host path takes it (normalised with its own mean, then the next draw, alpha 1.0, not encrypted)
-            from .quantize import _as_object, _static_quantize_padding_asymmetric
-            if normalize:
-                d, a = q._shift(zzz, -q.past_layer_mean_list[len(order)])
-                zzz = d.download(a.dtype, a.size).reshape(a.shape)
-            flat = zzz.flatten()
-            want = _loop_dtype(flat.dtype, 1.0)
-            if flat.dtype != want:
-                flat = flat.astype(want)
-            zq = int(_as_object(_static_quantize_padding_asymmetric(flat, 1.0, q.element_bits, device=q._device, as_object=False)).reshape(-1)[0])
-            ct.buf.upload_at(n * eng.limbs * 8, np.array([zq & (2 ** 64 - 1), zq >> 64][:eng.limbs], dtype=np.uint64))
-            del weights._weights["zzz"]
-        for k in order:
-            del weights._weights[k]
-        if order:
-            weights._weights[order[0]] = ct.mark_ready() if device else ct.to_host()
-        weights.walking_order = sorted(weights._weights.keys(), key=str)
-        return weights
+        return self._encrypt_tail(weights, device, mode, order, zzz, sizes, starts, shape_dict, rows, launch, keep, hold=owners, normalize=normalize)
 
     def _decrypt_unquantize_tensors(self, weights, out, unnormalize):
         """decrypt_unquantize into the caller's tensors: the fused back end writes the flat float64 model into engine scratch, one
@@ -788,9 +763,6 @@ class FlasheClient(object):
         float64 -> float32 -> 16 bits, each step round to nearest even -- and, with unnormalize, sums every layer the way np.mean /
         np.std do, so past_layer_mean_list / past_layer_std_list get the host path's np.float64 values.  Only those 16 bytes per layer come
         back to the host.  Own-stream engines synchronise before returning."""
-        from . import interop
-        from ._lib import TENSOR_BF16, TENSOR_F16, TENSOR_F32, TENSOR_F64
-        from .engine import DeviceVector
         from .cipher import _SparseMinus
         q, c = self.quantizer, self.cipher
         if "zzz" in weights._weights:
@@ -817,7 +789,6 @@ class FlasheClient(object):
         if self.shape_dict is None:
             raise ValueError("decrypt_unquantize(out=...) needs the layer shapes a quantize_encrypt left behind (shape_dict)")
         eng = c.engine
-        codes = {"float32": TENSOR_F32, "float64": TENSOR_F64, "float16": TENSOR_F16, "bfloat16": TENSOR_BF16}
         names = list(self.shape_dict)
         shapes = list(q.shape_list) if self.batch else [self.shape_dict[k] for k in names]
         missing = [k for k in names if k not in out]
@@ -828,7 +799,7 @@ class FlasheClient(object):
             if not interop.is_foreign(out[k]):
                 raise TypeError(f"out[{k!r}]: expected a framework device tensor, got {type(out[k]).__name__}")
             fa = eng.foreign(out[k], writable=True, what=f"out[{k!r}]")
-            if fa.dtype not in codes:
+            if fa.dtype not in _TENSOR_CODES:
                 raise TypeError(f"out[{k!r}]: unsupported dtype {fa.dtype} (float64, float32, float16 or bfloat16)")
             if tuple(fa.shape) != tuple(shape):
                 raise ValueError(f"out[{k!r}]: expected shape {tuple(shape)}, got {tuple(fa.shape)}")
@@ -836,47 +807,22 @@ class FlasheClient(object):
         k0 = weights.walking_order[0]
         v = weights._weights[k0]
         keep = [fa.keep for fa in fas]
+        sizes = [_size(shape) for shape in shapes]
         if sparse:
-            # the sparse minus-mask pass (result in HBM), then the unquantise of the dense model (decrypt_unquantize's sparse branch)
-            dec = c._as_wide(c.decrypt(v, device=True))
-            n = len(dec)
-            sizes = [int(np.prod(shape, dtype=np.int64)) for shape in shapes]
-            if sum(sizes) > n:
-                raise ValueError(f"the aggregate has {n} elements, shape_dict describes {sum(sizes)}")
-            table, at = [], 0
-            for li, size in enumerate(sizes):
-                table.append((at, None, q.alpha_list[li], False))
-                at += size
-            dout = eng.alloc(max(8 * n, 16))
-            if n:
-                dec.wait_on(eng)
-                eng.unquantize_model_dev(n, 0, n, dec.buf, table, q.element_bits, q.num_clients, dout)
-            keep.append(dec)
+            dout, _n = self._sparse_floats(v, sizes, keep)
             return self._store_tensors(weights, out, names, fas, sizes, dout, keep, unnormalize)
         add_idx, minus_idx = self._decrypt_prefixes(mode)
-        if interop.is_foreign(v):                                 # (the aggregate as a framework integer tensor: read in place)
-            v, kv = c._foreign_vec(eng, v, "aggregate")
-            keep.append(kv)
-        elif not isinstance(v, DeviceVector):
-            v = np.asarray(v)
-            if v.dtype == object:
-                v = v.reshape(-1)
-        dv, _kind = c._on_device(v, full_width=True)
-        dv = c._as_wide(dv)
-        sizes = [int(np.prod(shape, dtype=np.int64)) for shape in shapes]
-        dout = self._decrypt_floats(dv, sizes, mode, add_idx, minus_idx)
+        dout = self._decrypt_floats(self._wide_aggregate(v, keep), sizes, mode, add_idx, minus_idx)
         return self._store_tensors(weights, out, names, fas, sizes, dout, keep, unnormalize)
 
     def _store_tensors(self, weights, out, names, fas, sizes, dout, keep, unnormalize):
         """The back end's flat float64 model `dout` (in HBM) into the out= tensors, with the exact statistics when unnormalising."""
-        from ._lib import TENSOR_BF16, TENSOR_F16, TENSOR_F32, TENSOR_F64, TENSOR_SHIFT
         q, eng = self.quantizer, self.cipher.engine
-        codes = {"float32": TENSOR_F32, "float64": TENSOR_F64, "float16": TENSOR_F16, "bfloat16": TENSOR_BF16}
         n_values = sum(sizes)
         layers, at = [], 0
         for li, (fa, size) in enumerate(zip(fas, sizes)):
             shift = float(q.past_layer_mean_list[li]) if unnormalize else 0.0
-            layers.append((at, fa.ptr, 1.0, shift, codes[fa.dtype], TENSOR_SHIFT if unnormalize else 0))
+            layers.append((at, fa.ptr, 1.0, shift, _TENSOR_CODES[fa.dtype], _lib.TENSOR_SHIFT if unnormalize else 0))
             at += size
         stats = eng.alloc(max(16 * len(layers), 16)) if unnormalize else None
         if n_values:
@@ -1046,7 +992,7 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
                 raise TypeError(f"client {c}: sparse uploads (a 'zzz' layer or location masks) are not supported by FlasheCohort")
             yield list(w.walking_order), w._weights
     names, shapes, _f64, mixed = _one_model(dense_clients())
-    sizes = [int(np.prod(shp, dtype=np.int64)) for shp in shapes]
+    sizes = [_size(shp) for shp in shapes]
     starts, n = [], 0
     for s_ in sizes:
         starts.append(n)
@@ -1104,20 +1050,11 @@ class _CohortLead(FlasheClient):
         eng, n = c.engine, len(dv)
         if self.batch:
             # (the batched sum: combine + unbatch + `[:size]` + unquantise in one pass, as the parent's decrypt launch + unbatch launch)
-            field_bits = _field_bits(q.element_bits, q.num_clients)
-            bs = self.int_bits // field_bits
-            if sum((s_ + bs - 1) // bs for s_ in sizes) != n:
-                raise ValueError(f"the aggregate has {n} elements, the batched layers describe {sum((s_ + bs - 1) // bs for s_ in sizes)}")
-            layers = [(s_, None, q.alpha_list[li], False) for li, s_ in enumerate(sizes)]
+            layers, field_bits = self._batched_back_table(sizes, n)
             dout = eng.alloc(max(8 * sum(sizes), 16))
             eng.combine_unbatch_unquantize_model_dev(layers, q.element_bits, field_bits, q.num_clients, dv.buf, m[1].buf, None, n, dout)
             return dout
-        if sum(sizes) > n:
-            raise ValueError(f"the aggregate has {n} elements, shape_dict describes {sum(sizes)}")
-        table, at = [], 0
-        for li, size in enumerate(sizes):
-            table.append((at, None, q.alpha_list[li], False))
-            at += size
+        table = self._back_table(sizes, n)
         dout = eng.alloc(max(8 * n, 16))
         eng.combine_unquantize_model_dev(n, dv.buf, m[1].buf, None, table, q.element_bits, q.num_clients, dout)
         return dout
@@ -1505,7 +1442,7 @@ def plan_sparse_cohort(weights_list, sparsity, int_bits, element_bits=16, batch=
         raise ValueError("a cohort needs at least one client's model")
     C = len(weights_list)
     names, shapes, f64, mixed = _one_model(_client_layers(w, walking_order) for w in weights_list)
-    sizes = [int(np.prod(shp, dtype=np.int64)) for shp in shapes]
+    sizes = [_size(shp) for shp in shapes]
     for k, size in zip(names, sizes):
         if size == 0:
             raise ValueError(f"layer {k!r} is empty: the sparsifier keeps max(1, floor(sparsity * size)) values of every layer")
