@@ -13,7 +13,11 @@ which this example checks.
                launch takes it when the model has enough batched elements to fill the chip
   --precompute a precompute job ("precompute": {"enable": true}): the cohort calls prepare_encrypt() one round ahead -- the masks of all
                ten clients as one chain of eleven PRF streams, in idle time -- and the online step is ONE launch with no AES
-               (`upload.path` is "prepared-cohort"), at any --bits, with or without --compact / --batch"""
+               (`upload.path` is "prepared-cohort"), at any --bits, with or without --compact / --batch
+  --drop i,j   clients i and j miss the round (dropout-aware decrypt is what FLASHE is for): quantize_encrypt(present=...) takes the
+               Weights of the clients that report, and at --bits > 64 the round is still one chained launch, over present + runs PRF
+               streams, whose decrypt mask is that of the telescoped index lists; the new global model is what the present clients'
+               own steps and a decrypt told who uploaded (set_idx_list(present)) give, which this example checks"""
 import argparse
 import os
 import sys
@@ -50,9 +54,12 @@ def main():
     ap.add_argument("--compact", action="store_true")
     ap.add_argument("--batch", action="store_true")
     ap.add_argument("--precompute", action="store_true")
+    ap.add_argument("--drop", default="", help="comma-separated clients that miss the round, e.g. 2,7")
     opt = ap.parse_args()
     cm.N_JOBS = 16                                           # every party must use the same value
     C, key = 10, bytes(range(32))
+    dropped = sorted({int(c) for c in opt.drop.split(",") if c})
+    present = [c for c in range(C) if c not in dropped]
     models = [make_model(c) for c in range(C)]
     layers = [{name: p.detach() for name, p in m.named_parameters()} for m in models]
     # a precompute job states the length of its uploads: the values of the model, or -- batched -- its elements of bs values, every layer
@@ -70,13 +77,13 @@ def main():
     cohort.set_iter_index(it)
     np.random.seed(0)
     with torch.no_grad():
-        upload = cohort.quantize_encrypt([Weights(l) for l in layers], normalize=True)
+        upload = cohort.quantize_encrypt([Weights(layers[c]) for c in present], normalize=True, present=present if dropped else None)
         new_global = {name: torch.empty_like(t) for name, t in layers[0].items()}
         cohort.decrypt_unquantize(out=new_global, unnormalize=True)
-    print(f"{C} clients, {sum(t.numel() for t in layers[0].values())} parameters each: path {upload.path!r}, "
+    print(f"{C} clients{f' of which {dropped} dropped out' if dropped else ''}, {sum(t.numel() for t in layers[0].values())} parameters each: path {upload.path!r}, "
           f"{len(upload.ciphertexts)} ciphertexts and their sum in HBM ({upload.partial_sum.elem_bytes * upload.partial_sum.limbs} bytes per element)")
 
-    # the same round as ten FlasheClients, one after the other
+    # the same round as the present FlasheClients, one after the other
     clients = []
     for c in range(C):
         cl = FlasheClient(args)
@@ -89,18 +96,23 @@ def main():
     np.random.seed(0)
     with torch.no_grad():
         cts = []
-        for cl, l in zip(clients, layers):
-            w = cl.quantize_encrypt(Weights(l), device=True, normalize=True)
+        for c in present:
+            w = clients[c].quantize_encrypt(Weights(layers[c]), device=True, normalize=True)
             cts.append(w._weights[w.walking_order[0]])
-        agg = clients[0].cipher.aggregate(cts)
-        clients[0].set_idx_list(list(range(C)))
+        lead = clients[present[0]]
+        agg = lead.cipher.aggregate(cts)
+        lead.set_idx_list(list(present))                     # who uploaded: the decrypt telescopes the runs of indices
         want = {name: torch.empty_like(t) for name, t in layers[0].items()}
-        clients[0].decrypt_unquantize(Weights({sorted(layers[0])[0]: agg}), out=want, unnormalize=True)
-    for c in range(C):
-        assert np.array_equal(values(upload.ciphertexts[c]), values(cts[c])), f"client {c}'s upload differs"
+        lead.decrypt_unquantize(Weights({sorted(layers[0])[0]: agg}), out=want, unnormalize=True)
+    assert upload.present == present
+    for p, c in enumerate(present):
+        assert np.array_equal(values(upload.ciphertexts[p]), values(cts[p])), f"client {c}'s upload differs"
     assert np.array_equal(values(upload.partial_sum), values(agg))
     for name in want:
         assert torch.equal(want[name].view(torch.uint8), new_global[name].view(torch.uint8)), name
+    if dropped:
+        print(f"new global model equals {len(present)} FlasheClient steps and their dropout-aware decrypt bit for bit")
+        return
     mean = sum(l["3.bias"].double() for l in layers) / C
     print("new global model equals ten FlasheClient steps bit for bit; |3.bias - mean of the clients'| <=",
           float((new_global["3.bias"].double() - mean).abs().max()))

@@ -860,6 +860,7 @@ class FlasheClient(object):
 COHORT_CHAIN, STAGED_CHAIN, PER_CLIENT = "cohort-chain", "staged-chain", "per-client"
 PREPARED_COHORT, PREPARED_STAGED = "prepared-cohort", "prepared-staged"   # with the cohort's own mask cache (FlasheCohort.prepare_encrypt)
 _COHORT_MAX_LINKS = 128          # outputs of one chained launch (kMaxLinks, kernels.hip)
+_COHORT_MAX_STREAMS = 144        # PRF streams of one chained launch (kCohortMaxStreams, cohort_streams.h): present clients + runs
 
 
 class _Layers(object):
@@ -872,19 +873,56 @@ class _Layers(object):
 
 class CohortPlan(object):
     """What plan_cohort returns: names / shapes / sizes / starts of the shared layer table, n (values of one model), n_elems (ciphertext
-    elements of one upload: n, or the batched count), draw_offsets (client c's first draw in the client-major draws), path and the
-    reason for it."""
+    elements of one upload: n, or the batched count), draw_offsets (the p-th present client's first draw in the client-major draws), path
+    and the reason for it, present (the local positions of the clients that report: all of them unless some dropped out) and runs (the
+    runs of consecutive positions among them)."""
 
-    def __init__(self, names, shapes, sizes, starts, n, n_elems, draw_offsets, path, reason):
+    def __init__(self, names, shapes, sizes, starts, n, n_elems, draw_offsets, path, reason, present=None, runs=1):
         self.names, self.shapes, self.sizes, self.starts = names, shapes, sizes, starts
         self.n, self.n_elems, self.draw_offsets, self.path, self.reason = n, n_elems, draw_offsets, path, reason
+        self.present, self.runs = list(range(len(draw_offsets))) if present is None else list(present), runs
 
 
 class CohortUpload(object):
-    """FlasheCohort.quantize_encrypt's result: ciphertexts (one DeviceVector per client), partial_sum (their sum mod 2^b) and path."""
+    """FlasheCohort.quantize_encrypt's result: ciphertexts (one DeviceVector per present client), partial_sum (their sum mod 2^b), path
+    and present (the GLOBAL cipher indices of the clients the upload holds, ascending: what a decrypt of the sum passes to
+    set_idx_list)."""
 
-    def __init__(self, ciphertexts, partial_sum, path):
-        self.ciphertexts, self.partial_sum, self.path = ciphertexts, partial_sum, path
+    def __init__(self, ciphertexts, partial_sum, path, present=None):
+        self.ciphertexts, self.partial_sum, self.path, self.present = ciphertexts, partial_sum, path, present
+
+
+def _present_runs(present, count):
+    """The refusals of a `present` list (one local position per Weights, strictly ascending, none negative) and the runs of consecutive
+    positions it forms.  present=None: everyone, one run."""
+    if present is None:
+        return list(range(count)), 1
+    try:
+        pos = [int(p) for p in present]
+        exact = all(p == q for p, q in zip(pos, present))
+    except (TypeError, ValueError):
+        raise ValueError("present: a list of the local positions of the clients that report") from None
+    if not exact:
+        raise ValueError("present: the positions must be integers")
+    if len(pos) != count:
+        raise ValueError(f"present names {len(pos)} clients, got {count} Weights")
+    if any(p < 0 for p in pos):
+        raise ValueError("present: a negative position")
+    if any(b <= a for a, b in zip(pos, pos[1:])):
+        raise ValueError("present: the positions must be strictly ascending (sorted, no client twice)")
+    return pos, 1 + sum(1 for a, b in zip(pos, pos[1:]) if b != a + 1)
+
+
+def _telescoped(idxs):
+    """(add, minus) of engine.telescope for strictly ascending indices: one past every run's end, every run's start, ascending."""
+    add, minus = [], []
+    for i in idxs:
+        if add and add[-1] == i:
+            add[-1] = i + 1
+        else:
+            add.append(i + 1)
+            minus.append(i)
+    return add, minus
 
 
 def _layer_shape(v):
@@ -954,7 +992,7 @@ def compact_cohort_admission_length(cu_count, int_bits, n_jobs):
 
 
 def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, mask="double", num_clients=None, precompute=False, chain=True,
-                location_masks=False, compact=False, n_jobs=None, cohort_masks=False):
+                location_masks=False, compact=False, n_jobs=None, cohort_masks=False, present=None):
     """The engine-free part of FlasheCohort.quantize_encrypt: checks that the clients' Weights describe one model (the same layer names
     in the same walking order with the same shapes: ValueError naming the client and the layer otherwise; a sparse upload -- a 'zzz'
     layer or location masks -- is a TypeError), lays out the shared layer table and the client-major draws, and picks the path:
@@ -976,11 +1014,18 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
                          of clients;
       "prepared-staged"  a layer that is float64 for some clients only (no shared row), or a batched job in the compact layout: a
                          quantise (+ batch) pass per client into plaintexts, then flashe_combine_batch_sum_dev with the masks.
+    present=[positions] (a round in which clients dropped out: the strictly ascending local positions of the clients that report, one
+    Weights each; ValueError for a list that is unsorted, repeats a client, is negative or of another length) keeps every rule above with
+    C = the clients present.  Positions in SEVERAL runs ({0,1,3,4}) still take "cohort-chain" at int_bits > 64
+    (flashe_quantize_encrypt_cohort_runs_dev / flashe_quantize_batch_encrypt_cohort_runs_dev: present + runs PRF streams, at most 144 of
+    them) and "prepared-cohort" with the present clients' masks; the compact chain takes one run only, so a gapped compact cohort runs
+    "staged-chain", as does one of more than 144 streams.  present=None and present=all positions give equal plans.
     Touches no device.  The library's own answer stays the last word: a "cohort-chain" plan it declines runs "staged-chain", a
     "prepared-cohort" one "prepared-staged"."""
     if len(weights_list) < 1:
         raise ValueError("a cohort needs at least one client's Weights")
     C = len(weights_list)
+    present, runs = _present_runs(present, C)
     num_clients = C if num_clients is None else int(num_clients)
     if n_jobs is None:
         from . import cipher as _cipher_mod
@@ -1030,22 +1075,26 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
         path, reason = STAGED_CHAIN, "the vector does not fill the chip uncut"
     elif not compact and (n_elems < cohort_admission_length(cu_count) or n_elems > 2 ** 32):
         path, reason = STAGED_CHAIN, "the vector does not fill the chip uncut"
+    elif runs > 1 and compact:
+        path, reason = STAGED_CHAIN, f"clients dropped out ({runs} runs of indices): the compact chain takes one run of consecutive clients"
+    elif C + runs > _COHORT_MAX_STREAMS:
+        path, reason = STAGED_CHAIN, f"clients dropped out: {C} clients in {runs} runs need more than {_COHORT_MAX_STREAMS} PRF streams"
     elif mixed:
         path, reason = STAGED_CHAIN, "a layer is float64 for some clients only"
     else:
         path, reason = COHORT_CHAIN, ""
-    return CohortPlan(names, shapes, sizes, starts, n, n_elems, [c * n for c in range(C)], path, reason)
+    return CohortPlan(names, shapes, sizes, starts, n, n_elems, [c * n for c in range(C)], path, reason, present, runs)
 
 
 class _CohortLead(FlasheClient):
     """The cohort's one FlasheClient (its quantiser state is the cohort's): the decrypt of the cohort's own sum adds the mask the chained
     launch wrote -- one memory-bound pass -- instead of computing its two PRF streams again."""
-    _cohort_mask = None          # (sum's device pointer, mask DeviceVector, iter, add prefix, minus prefix)
+    _cohort_mask = None          # (sum's device pointer, mask DeviceVector, iter, add prefixes, minus prefixes): the lists of the present clients' runs
 
     def _decrypt_floats(self, dv, sizes, mode, add_idx, minus_idx):
         m, q, c = self._cohort_mask, self.quantizer, self.cipher
-        if (m is None or mode is not None or dv.ptr != m[0] or c.iter_index != m[2] or list(add_idx) != [m[3]]
-                or list(minus_idx) != [m[4]] or len(dv) != len(m[1])):
+        if (m is None or mode is not None or dv.ptr != m[0] or c.iter_index != m[2] or list(add_idx) != m[3]
+                or list(minus_idx) != m[4] or len(dv) != len(m[1])):
             return super()._decrypt_floats(dv, sizes, mode, add_idx, minus_idx)
         eng, n = c.engine, len(dv)
         if self.batch:
@@ -1075,6 +1124,10 @@ class FlasheCohort(object):
     run -- the chained launch goes from the floats to the uint32 ciphertexts and their sum (flashe_quantize_encrypt_cohort_u32_dev: 16
     bytes moved per value and client instead of 36).  No decrypt mask is kept at these widths: decrypt_unquantize() decrypts the
     sum.
+    A round in which clients DROPPED OUT is quantize_encrypt(..., present=[positions]): the present clients' steps one after the other, and
+    at int_bits > 64 still one chained launch (flashe_quantize_encrypt_cohort_runs_dev / flashe_quantize_batch_encrypt_cohort_runs_dev)
+    over present + runs PRF streams that writes the decrypt mask of the telescoped index lists, so decrypt_unquantize() of that round
+    stays one pass; a gapped compact cohort runs the staged form.
     A precompute job ("precompute": {"enable": true}) calls prepare_encrypt() in idle time: the next round's masks of all clients as one
     chain of n_local + 1 streams, held by the cohort; the next quantize_encrypt is then ONE online launch with no AES ("prepared-cohort")
     at any int_bits, batched or not, compact or not.  Without that call the clients' own masks run "per-client" as before."""
@@ -1115,14 +1168,16 @@ class FlasheCohort(object):
         self.lead._cohort_mask = None
         self._last = None
 
-    def plan(self, weights_list):
-        """plan_cohort with this cohort's settings and the engine's CU count."""
+    def plan(self, weights_list, present=None):
+        """plan_cohort with this cohort's settings and the engine's CU count (present: quantize_encrypt's)."""
         from . import cipher as _cipher_mod
         ld = self.lead
+        if present is not None and _present_runs(present, len(weights_list))[0][-1:] >= [self.n_local]:
+            raise ValueError(f"present: the cohort holds positions 0 .. {self.n_local - 1}")
         return plan_cohort(weights_list, ld.int_bits, ld.cipher.engine.cu_count, element_bits=ld.quantizer.element_bits, batch=bool(ld.batch),
                            mask=ld.cipher.masking_scheme, num_clients=self.num_clients, precompute=bool(ld.precompute),
                            chain=os.environ.get("FLASHE_CHAIN", "1") != "0", location_masks=ld.cipher.masks is not None, compact=self.compact,
-                           n_jobs=_cipher_mod.N_JOBS, cohort_masks=self._masks is not None)
+                           n_jobs=_cipher_mod.N_JOBS, cohort_masks=self._masks is not None, present=present)
 
     def prepare_encrypt(self):
         """A precompute job's idle-time step for the whole cohort.  Double mask: the encrypt masks of iteration iter_index + 1 for all
@@ -1155,9 +1210,14 @@ class FlasheCohort(object):
         """The lead client's prepare_decrypt: the decrypting party's masks do not depend on the cohort."""
         self.lead.prepare_decrypt()
 
-    def quantize_encrypt(self, weights_list, normalize=False, seeds=None):
+    def quantize_encrypt(self, weights_list, normalize=False, seeds=None, present=None):
         """One Weights per client (host arrays and / or framework float device tensors, as FlasheClient.quantize_encrypt takes them) ->
-        CohortUpload.  seeds=None: the stochastic-rounding draws come from NumPy's global stream in client order (client c takes draws
+        CohortUpload.  present=[positions]: a round in which clients DROPPED OUT -- the strictly ascending local positions (0 .. n_local - 1)
+        of the clients that report; weights_list and seeds then hold one entry per present client, the result is that of the present
+        clients' FlasheClient steps run one after the other (the p-th present client takes draws [p n, (p + 1) n), absent clients draw
+        nothing), CohortUpload.present names their global indices, and where the chain admits the shape the round is still ONE chained
+        launch over present + runs PRF streams that writes the decrypt mask of the telescoped index lists.  present=None: everyone, the
+        call as it always was.  seeds=None: the stochastic-rounding draws come from NumPy's global stream in client order (client c takes draws
         [c n, (c + 1) n) and the generator is left where n_local sequential steps leave it); seeds=[s_0 ..]: client c draws after
         np.random.seed(s_c), as separate processes would.  The draws of ALL clients are materialised in HBM (8 bytes each: 2.3 GB for ten
         29.2 M-parameter models), on the device under quantize_encrypt's conditions (MT19937, DEVICE_RNG_MIN).  Mismatched Weights raise
@@ -1165,13 +1225,14 @@ class FlasheCohort(object):
         last kernel that reads them has finished."""
         from .engine import DeviceVector
         ld = self.lead
-        q, eng, C = ld.quantizer, ld.cipher.engine, self.n_local
-        plan, layers = self._collect(weights_list, seeds)
+        q, eng = ld.quantizer, ld.cipher.engine
+        plan, layers = self._collect(weights_list, seeds, present)
+        C = len(plan.present)
         self._refuse_prepared_len(plan, seeds)
         self._last, ld._cohort_mask = None, None
         path = self._choose_path(plan, layers)
         if path == PER_CLIENT:
-            return self._per_client(weights_list, normalize, seeds)
+            return self._per_client(weights_list, normalize, seeds, plan.present)
         if not ld._fusable():
             raise TypeError("FlasheCohort needs the fused client step (fuse=True, a keyed cipher, no location masks)")
         alphas = self._begin_round(plan)
@@ -1191,7 +1252,7 @@ class FlasheCohort(object):
             srcs = [[t[1] for t in table] for table in tables]
             dts = [[t[4] for t in table] for table in tables]
             launch = self._launch_prepared if prepared else self._launch_chain
-            if not launch(plan, rows, srcs, dts, du, cts, psum):
+            if not launch(plan, rows, srcs, dts, du, cts, psum, present is not None):
                 # the library declined: the planner's guess was wrong, the result is not -- the same bytes from the fallback form
                 path = PREPARED_STAGED if prepared else STAGED_CHAIN
         if path in (STAGED_CHAIN, PREPARED_STAGED) and plan.n_elems:
@@ -1210,17 +1271,18 @@ class FlasheCohort(object):
         for v in cts:
             v.mark_ready()
         psum.mark_ready()
-        self._last = CohortUpload(cts, psum, path)
+        self._last = CohortUpload(cts, psum, path, [self.first_idx + p for p in plan.present])
         return self._last
 
-    def _collect(self, weights_list, seeds):
-        """(plan, every layer of every client as _layer_source gives it): the refusals, before anything of the cohort's state is touched."""
-        C = self.n_local
+    def _collect(self, weights_list, seeds, present=None):
+        """(plan, every layer of every present client as _layer_source gives it): the refusals, before anything of the cohort's state is
+        touched."""
+        C = self.n_local if present is None else len(weights_list)
         if len(weights_list) != C:
             raise ValueError(f"the cohort holds {C} clients, got {len(weights_list)} Weights")
         if seeds is not None and len(seeds) != C:
             raise ValueError(f"seeds: one per client ({C}), got {len(seeds)}")
-        plan = self.plan(weights_list)
+        plan = self.plan(weights_list, present)
         eng = self.lead.cipher.engine
         return plan, [[_layer_source(eng, w._weights[k], f"client {ci} layer {k!r}") for k in plan.names] for ci, w in enumerate(weights_list)]
 
@@ -1273,9 +1335,11 @@ class FlasheCohort(object):
             tables.append(table)
         return tables, keep
 
-    def _launch_chain(self, plan, rows, srcs, dts, du, cts, psum):
+    def _launch_chain(self, plan, rows, srcs, dts, du, cts, psum, by_idx=False):
         """"cohort-chain": ONE chained launch from the floats to the ciphertexts, their sum and -- when the cohort is the whole federation --
-        the decrypt mask, which the lead keeps for the decrypt of that sum.  False: the library declined, nothing was launched."""
+        the decrypt mask, which the lead keeps with the add / minus lists it stands for, for the decrypt of that sum.  by_idx (a call with
+        `present`): the launch is given the present clients' cipher indices, any number of runs.  False: the library declined, nothing was
+        launched."""
         from . import cipher as _cipher_mod
         from .engine import DeviceVector
         ld = self.lead
@@ -1284,9 +1348,17 @@ class FlasheCohort(object):
         # (no decrypt mask at the compact widths: the decrypt of the sum is 2 / m AES blocks per element)
         dmask = DeviceVector(eng, n_elems) if self.n_local == self.num_clients and not self.compact else None
         outs, mask_buf = [v.buf for v in cts], dmask.buf if dmask is not None else None
+        idxs = [self.first_idx + p for p in plan.present]
         if self.compact:
-            took = eng.quantize_encrypt_cohort_u32_dev(c.iter_index, self.first_idx, n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du, outs,
+            # (one run: plan_cohort sends a gapped compact cohort to the staged form)
+            took = eng.quantize_encrypt_cohort_u32_dev(c.iter_index, idxs[0], n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du, outs,
                                                        psum.buf)
+        elif by_idx and ld.batch:
+            took = eng.quantize_batch_encrypt_cohort_runs_dev(c.iter_index, idxs, n, n_elems, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits,
+                                                              _field_bits(q.element_bits, q.num_clients), du, outs, psum.buf, mask_buf)
+        elif by_idx:
+            took = eng.quantize_encrypt_cohort_runs_dev(c.iter_index, idxs, n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du, outs, psum.buf,
+                                                        mask_buf)
         elif ld.batch:
             took = eng.quantize_batch_encrypt_cohort_dev(c.iter_index, self.first_idx, n, n_elems, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits,
                                                          _field_bits(q.element_bits, q.num_clients), du, outs, psum.buf, mask_buf)
@@ -1294,15 +1366,15 @@ class FlasheCohort(object):
             took = eng.quantize_encrypt_cohort_dev(c.iter_index, self.first_idx, n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du, outs,
                                                    psum.buf, mask_buf)
         if took and dmask is not None:
-            ld._cohort_mask = (psum.ptr, dmask, c.iter_index, self.first_idx + self.n_local, self.first_idx)
+            ld._cohort_mask = (psum.ptr, dmask, c.iter_index) + _telescoped(idxs)
         return took
 
-    def _launch_prepared(self, plan, rows, srcs, dts, du, cts, psum):
+    def _launch_prepared(self, plan, rows, srcs, dts, du, cts, psum, by_idx=False):
         """"prepared-cohort": ONE online launch, every client's floats and its precomputed mask -> its ciphertext, and their sum; no AES.
         False: the library declined, nothing was launched."""
         ld = self.lead
         q = ld.quantizer
-        return ld.cipher.engine.quantize_combine_cohort_dev(plan.n, rows, srcs, dts, q.element_bits, du, [m.buf for m in self._masks],
+        return ld.cipher.engine.quantize_combine_cohort_dev(plan.n, rows, srcs, dts, q.element_bits, du, [self._masks[p].buf for p in plan.present],
                                                             [v.buf for v in cts], psum.buf, compact=self.compact,
                                                             batch=(plan.n_elems, _field_bits(q.element_bits, q.num_clients)) if ld.batch else None)
 
@@ -1315,20 +1387,20 @@ class FlasheCohort(object):
         from .engine import DeviceVector
         ld = self.lead
         q, c, eng = ld.quantizer, ld.cipher, ld.cipher.engine
-        C, n_elems = self.n_local, plan.n_elems
+        C, n_elems = len(plan.present), plan.n_elems
         field_bits = _field_bits(q.element_bits, q.num_clients) if ld.batch else ld.int_bits
         pts = [eng.alloc_vec(n_elems) for _ in range(C)]
         for ci in range(C):
             eng.quantize_batch_tensors_dev(tables[ci], plan.n, q.element_bits, field_bits, du.ptr + 8 * plan.draw_offsets[ci], n_elems, pts[ci])
         if prepared:
-            adds = [m.widened(eng) for m in self._masks]
+            adds = [self._masks[p].widened(eng) for p in plan.present]
             wide = [DeviceVector(eng, n_elems) for _ in range(C)] if self.compact else cts
             wsum = DeviceVector(eng, n_elems) if self.compact else psum
             eng.combine_batch_sum_dev(n_elems, pts, eng.limbs, [a.buf for a in adds], None, [v.buf for v in wide], wsum.buf)
             if self.compact:
                 cts, psum = [v.mark_ready().narrowed(eng) for v in wide], wsum.mark_ready().narrowed(eng)
             return cts, psum, pts + adds
-        idxs = [self.first_idx + ci for ci in range(C)]
+        idxs = [self.first_idx + p for p in plan.present]
         scheme = 1 if c.masking_scheme == "double" else 0
         if self.compact:
             pts = [DeviceVector(eng, n_elems, 1, buf=pt).narrowed().buf for pt in pts]
@@ -1337,15 +1409,16 @@ class FlasheCohort(object):
             eng.encrypt_batch_sum_dev(c.iter_index, idxs, scheme, n_elems, _cipher_mod.N_JOBS, pts, eng.limbs, [v.buf for v in cts], psum.buf)
         return cts, psum, pts
 
-    def _per_client(self, weights_list, normalize, seeds):
-        """The clients' own steps one after the other (one cipher re-indexed per client; with precompute: every client's own cipher and
-        masks), then the aggregate of what they wrote."""
+    def _per_client(self, weights_list, normalize, seeds, present=None):
+        """The present clients' own steps one after the other (one cipher re-indexed per client; with precompute: every client's own cipher
+        and masks), then the aggregate of what they wrote."""
         ld = self.lead
         cts = []
+        present = list(range(len(weights_list))) if present is None else present
         try:
             for ci, w in enumerate(weights_list):
-                cl = self._clients[ci] if self._clients else ld
-                cl.cipher.idx = self.first_idx + ci
+                cl = self._clients[present[ci]] if self._clients else ld
+                cl.cipher.idx = self.first_idx + present[ci]
                 if seeds is not None:
                     np.random.seed(seeds[ci])
                 lw = _Layers({k: w._weights[k] for k in w.walking_order})
@@ -1357,15 +1430,18 @@ class FlasheCohort(object):
         finally:
             ld.cipher.idx = self.first_idx
         psum = ld.cipher.aggregate(cts, device=True)
-        self._last = CohortUpload(cts, psum, PER_CLIENT)
+        self._last = CohortUpload(cts, psum, PER_CLIENT, [self.first_idx + p for p in present])
         return self._last
 
     def decrypt_unquantize(self, aggregate=None, uploaded=None, out=None, unnormalize=False):
         """The new global model as FlasheClient.decrypt_unquantize returns it (out=: written into the caller's tensors, in place).  Without
-        an aggregate: the cohort is the whole federation and its own last partial_sum is decrypted -- after a "cohort-chain" upload by adding
-        the mask that launch wrote (one memory-bound pass); ValueError when clients outside the cohort exist.  With an aggregate (a
-        DeviceVector, limbs, a framework tensor, or Weights holding one): `uploaded` lists the clients it sums (default: all num_clients)."""
+        an aggregate: the cohort is the whole federation and its own last partial_sum is decrypted, `uploaded` defaulting to the clients
+        that upload held (CohortUpload.present) -- after a "cohort-chain" upload by adding the mask that launch wrote (one memory-bound
+        pass) whenever set_idx_list yields exactly the add / minus lists the mask stands for; ValueError when clients outside the cohort
+        exist.  With an aggregate (a DeviceVector, limbs, a framework tensor, or Weights holding one): `uploaded` lists the clients it sums
+        (default: all num_clients)."""
         ld = self.lead
+        own = aggregate is None
         if aggregate is None:
             if self.n_local != self.num_clients:
                 raise ValueError(f"the cohort holds {self.n_local} of {self.num_clients} clients: decrypt_unquantize needs the federation's aggregate")
@@ -1373,7 +1449,7 @@ class FlasheCohort(object):
                 raise ValueError("decrypt_unquantize() without an aggregate needs the upload of this iteration (quantize_encrypt first)")
             aggregate = self._last.partial_sum
         if uploaded is None:
-            uploaded = list(range(self.num_clients))
+            uploaded = list(self._last.present) if own and self._last.present is not None else list(range(self.num_clients))
         if ld.shape_dict is None:
             raise ValueError("decrypt_unquantize needs the layer shapes a quantize_encrypt left behind (shape_dict)")
         if not hasattr(aggregate, "walking_order"):

@@ -3,6 +3,7 @@
 // Host-side glue only: argument checks, the tables and the stage pass; what it shares with abi.hip is declared in ctx.h.
 #include "ctx.h"
 #include "layer_tables.h"
+#include "cohort_streams.h"
 
 #include <algorithm>
 #include <cmath>
@@ -514,6 +515,32 @@ int flashe_quantize_encrypt_tensors_dev(flashe_ctx *ctx, uint32_t iter, uint32_t
     return quantize_encrypt_model(ctx, iter, idx, scheme, n, n_jobs, first, count, cl.data(), n_layers, element_bits, u_dev, ct_dev);
 }
 
+// what every chained cohort asks of its arguments before its cipher indices
+static int cohort_check_args(flashe_ctx *ctx, const char *who, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers,
+                             const void *const *src_dev, bool outs, int element_bits, const double *u_dev)
+{
+    if (n_clients < 1) return fail(ctx, FLASHE_EINVAL, "%s: n_clients must be >= 1", who);
+    if (!src_dev || !outs || (n && !u_dev)) return fail(ctx, FLASHE_EINVAL, "%s: null argument", who);
+    int rc = check_element_bits(ctx, element_bits);
+    if (rc || (rc = check_f64_aligned(ctx, u_dev, "u_dev")) || (rc = check_tensor_layers(ctx, n, layers, n_layers, false))) return rc;
+    return FLASHE_OK;
+}
+
+// the same checks for a cohort given by the cipher indices of the clients that report (the *_cohort_runs_dev entry points): strictly
+// ascending and below 2^32 - 1 (cohort_streams.h).  *too_many: the indices need more streams than one launch holds -- not an error of the
+// arguments but a shape the launch declines.
+static int cohort_check_runs(flashe_ctx *ctx, const char *who, const uint32_t *idx, int n_clients, uint64_t n, const flashe_tensor_layer *layers,
+                             int n_layers, const void *const *src_dev, bool outs, int element_bits, const double *u_dev, bool *too_many)
+{
+    if (int rc = cohort_check_args(ctx, who, n_clients, n, layers, n_layers, src_dev, outs && idx, element_bits, u_dev)) return rc;
+    flashe_tables::CohortStreams st;
+    const flashe_tables::CohortStreamsStatus v = flashe_tables::cohort_streams(idx, n_clients, flashe_tables::kCohortMaxStreams, st);
+    if (v == flashe_tables::kCohortStreamsBadIdx)
+        return fail(ctx, FLASHE_EINVAL, "%s: the cipher indices must be strictly ascending and below 2^32 - 1 (idx + 1 has to fit the 4-byte prefix field, jzf_flashe.py:352-353)", who);
+    *too_many = v == flashe_tables::kCohortStreamsTooMany;
+    return FLASHE_OK;
+}
+
 // ---- a cohort of co-located clients: C float models -> C ciphertexts + their sum (+ the decrypt mask) in one chained launch ----
 // The shared layer table, the C x n_layers sources and their storage dtypes.  A source already in its row's compute type without SHIFT is
 // read where it lies; every other one goes through ONE stage pass (tensors.hip) into ctx scratch, all clients together.
@@ -521,10 +548,7 @@ int flashe_quantize_encrypt_tensors_dev(flashe_ctx *ctx, uint32_t iter, uint32_t
 static int cohort_check(flashe_ctx *ctx, const char *who, uint32_t first_idx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers,
                         const void *const *src_dev, bool outs, int element_bits, const double *u_dev, std::vector<uint32_t> &idx)
 {
-    if (n_clients < 1) return fail(ctx, FLASHE_EINVAL, "%s: n_clients must be >= 1", who);
-    if (!src_dev || !outs || (n && !u_dev)) return fail(ctx, FLASHE_EINVAL, "%s: null argument", who);
-    int rc = check_element_bits(ctx, element_bits);
-    if (rc || (rc = check_f64_aligned(ctx, u_dev, "u_dev")) || (rc = check_tensor_layers(ctx, n, layers, n_layers, false))) return rc;
+    if (int rc = cohort_check_args(ctx, who, n_clients, n, layers, n_layers, src_dev, outs, element_bits, u_dev)) return rc;
     idx.resize(static_cast<size_t>(n_clients));
     for (int c = 0; c < n_clients; c++) {
         idx[c] = first_idx + static_cast<uint32_t>(c);
@@ -718,6 +742,53 @@ int flashe_quantize_batch_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uin
     cb.n_values = n_values;
     cb.field_bits = field_bits;
     return cohort_launched(ctx, launch_prf_cohort_sum(ctx->env, iter, n_clients, idx.data(), cc, &cb, u_dev, ct_dev, sum_out_dev, n_elems, n_jobs, dmask_dev),
+                           who, "batched cohort");
+}
+
+// ---- the same two launches for a round in which clients DROPPED OUT: the cipher indices of the clients that report, any strictly
+// ascending list (one run: the launches above, bit for bit; several runs: prf_chain_cohort_runs_kernel / prf_chain_cohort_batch_runs_kernel) ----
+int flashe_quantize_encrypt_cohort_runs_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                            const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                            int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev, uint64_t *dmask_dev)
+{
+    CHECK_CTX(ctx);
+    static const char who[] = "flashe_quantize_encrypt_cohort_runs_dev";
+    bool too_many = false;
+    int rc = cohort_check_runs(ctx, who, idx, n_clients, n, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, &too_many);
+    if (rc || (rc = cohort_check_outs(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, dmask_dev))) return rc;
+    if (too_many || !cohort_chain_admits(ctx->env, n_clients, n, 0)) return cohort_declined(ctx, who, "cohort");
+    CohortCodec cc{};
+    if ((rc = cohort_stage(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, cc))) return rc;
+    return cohort_launched(ctx, launch_prf_cohort_sum(ctx->env, iter, n_clients, idx, cc, nullptr, u_dev, ct_dev, sum_out_dev, n, n_jobs, dmask_dev), who, "cohort");
+}
+
+int flashe_quantize_batch_encrypt_cohort_runs_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n_values, uint64_t n_elems,
+                                                  uint32_t n_jobs, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
+                                                  const int32_t *src_dtype, int element_bits, int field_bits, const double *u_dev, uint64_t *const *ct_dev,
+                                                  uint64_t *sum_out_dev, uint64_t *dmask_dev)
+{
+    CHECK_CTX(ctx);
+    static const char who[] = "flashe_quantize_batch_encrypt_cohort_runs_dev";
+    bool too_many = false;
+    uint64_t bs = 0;
+    int rc = cohort_check_runs(ctx, who, idx, n_clients, n_values, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, &too_many);
+    if (rc || (rc = check_batch_bits(ctx, element_bits, field_bits, &bs))) return rc;
+    std::vector<uint64_t> rows;
+    auto size_of = [&](int l) { return layer_end(layers, n_layers, l, n_values) - layers[l].start; };
+    const uint64_t e = flashe_tables::batched_elems(n_layers, bs, size_of, [&](int l, uint64_t elem, uint64_t) { rows.push_back(elem); rows.push_back(size_of(l)); });
+    if ((rc = check_batched_count(ctx, e, n_elems))) return rc;
+    if ((rc = cohort_check_outs(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, dmask_dev))) return rc;
+    if (too_many || !cohort_chain_admits(ctx->env, n_clients, n_elems, static_cast<int>(bs))) return cohort_declined(ctx, who, "batched cohort");
+    CohortCodec cc{};
+    const char *rows_dev = nullptr;
+    if ((rc = cohort_stage(ctx, n_clients, n_values, layers, n_layers, src_dev, src_dtype, element_bits, cc, rows.data(), rows.size() * sizeof(uint64_t),
+                           &rows_dev)))
+        return rc;
+    CohortBatch cb{};
+    cb.rows = reinterpret_cast<const uint64_t *>(rows_dev);
+    cb.n_values = n_values;
+    cb.field_bits = field_bits;
+    return cohort_launched(ctx, launch_prf_cohort_sum(ctx->env, iter, n_clients, idx, cc, &cb, u_dev, ct_dev, sum_out_dev, n_elems, n_jobs, dmask_dev),
                            who, "batched cohort");
 }
 

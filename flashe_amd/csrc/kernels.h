@@ -106,8 +106,11 @@ bool cohort_chain_admits(const LaunchEnv &env, int n_vec, uint64_t n_elems, int 
 // launch_prf_batch_sum over whole n-element vectors with the cohort's front end.  cb == null: client c's plaintext k is the
 // stochastic-rounded quantisation of its float k with the draw u_dev[c * n + k] (codec_quantize's arithmetic), no integer plaintext exists
 // in HBM.  cb: n counts batched elements, client c's plaintext of element e = quantize_batch_model_kernel's with the draws
-// u_dev[c * n_values + value index], bs = env.b / field_bits.  hipErrorNotSupported -- nothing launched -- outside cohort_chain_admits, for
-// idx that are not one consecutive run below 2^32 - 1, a null output or an empty table; dmask_dev is optional.
+// u_dev[c * n_values + value index], bs = env.b / field_bits.  idx: any strictly ascending indices below 2^32 - 1 -- one run launches
+// prf_chain_cohort_kernel / prf_chain_cohort_batch_kernel, several runs (clients dropped out) their _runs_ forms over the |idx| + runs streams
+// of cohort_streams.h, whose decrypt mask is that of the telescoped lists.  hipErrorNotSupported -- nothing launched -- outside
+// cohort_chain_admits, for idx cohort_streams refuses (not ascending, 2^32 - 1, more than kCohortMaxStreams streams), a null output or an
+// empty table; dmask_dev is optional.
 hipError_t launch_prf_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const CohortBatch *cb,
                                  const double *u_dev, uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs,
                                  uint64_t *dmask_dev = nullptr);

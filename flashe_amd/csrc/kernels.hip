@@ -12,6 +12,7 @@
 //   * persistent launch: one 1024-thread workgroup per CU (128 KiB of LDS tables), tiles dealt
 //     round-robin; there is no inter-workgroup reuse, so no XCD remap is needed.
 #include "device_common.h"
+#include "cohort_streams.h"
 #include <type_traits>
 
 namespace flashe {
@@ -298,6 +299,27 @@ struct ChainTable {
     uint64_t *out[kMaxLinks];
     uint64_t *sum_out[kMaxChains];                     // SUM kernels only: where sum_c out_c of the chain goes (null = nowhere)
 };
+static_assert(kMaxLinks + kMaxChains == flashe_tables::kCohortMaxStreams, "cohort_streams.h states the prefix slots of ChainTable::idx");
+
+// GAPS (prf_chain_body.inc): the streams of a cohort whose cipher indices form several runs (cohort_streams.h) -- how many the launch's one
+// chain computes, two bits per stream (bit 0 = it completes an output, bit 1 = it opens a client) and, per word of sixteen streams, how
+// many outputs the streams before it complete: outputs are completed in turn, so stream c's link is that count plus the completing
+// streams below it in its own word.  A kernel argument of 52 bytes: a stream's word is a scalar load at a wave-uniform offset.
+constexpr int kGapsWords = (kMaxLinks + kMaxChains + 15) / 16;
+struct CohortGaps {
+    uint32_t bits[kGapsWords];
+    uint32_t base[(kGapsWords + 3) / 4];     // one byte per word of bits (at most kMaxLinks = 128)
+    int n_streams;
+};
+__device__ __forceinline__ uint32_t cohort_stream_bits(const CohortGaps &cg, int c) { return (cg.bits[c >> 4] >> ((c & 15) * 2)) & 3u; }
+// the output stream c completes, -1 where it completes none
+__device__ __forceinline__ int cohort_stream_link(const CohortGaps &cg, int c)
+{
+    const int w = c >> 4, sh = (c & 15) * 2;
+    const uint32_t word = cg.bits[w], below = word & ((1u << sh) - 1u) & 0x55555555u;
+    const uint32_t base = (cg.base[w >> 2] >> ((w & 3) * 8)) & 0xffu;
+    return ((word >> sh) & 1u) ? static_cast<int>(base) + __builtin_popcount(below) : -1;
+}
 
 __device__ __forceinline__ CtrPrefix load_prefix(const uint32_t *pre_lds, int s)
 {
@@ -355,8 +377,9 @@ __global__ __launch_bounds__(THREADS) void prf_chain_kernel(const RoundKeys rk, 
                                                               uint32_t iter0, uint64_t mask_lo, uint64_t mask_hi,
                                                               const uint32_t *__restrict__ te0, const Codec cq)
 {
-    constexpr bool DMASK = false, D128 = false, COHORT = false;
+    constexpr bool DMASK = false, D128 = false, COHORT = false, GAPS = false;
     constexpr int BS = 0;
+    const CohortGaps cg{};
     uint64_t *const dmask = nullptr;
     const CohortCodec cc{};
     const CohortBatch cb{};
@@ -369,8 +392,9 @@ __global__ __launch_bounds__(THREADS) void prf_chain_dmask_kernel(const RoundKey
                                                                     uint32_t iter0, uint64_t mask_lo, uint64_t mask_hi,
                                                                     const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask)
 {
-    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = false;
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = false, GAPS = false;
     constexpr int BS = 0;
+    const CohortGaps cg{};
     const Codec cq{};
     const CohortCodec cc{};
     const CohortBatch cb{};
@@ -385,8 +409,9 @@ __global__ __launch_bounds__(THREADS) void prf_dmask_sum128_kernel(const RoundKe
                                                                      uint32_t iter0, uint64_t mask_lo, uint64_t mask_hi,
                                                                      const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask)
 {
-    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = true, COHORT = false;
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = true, COHORT = false, GAPS = false;
     constexpr int BS = 0;
+    const CohortGaps cg{};
     const Codec cq{};
     const CohortCodec cc{};
     const CohortBatch cb{};
@@ -406,10 +431,11 @@ __global__ __launch_bounds__(THREADS) void prf_chain_cohort_kernel(const RoundKe
                                                                      const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask,
                                                                      const CohortCodec cc)
 {
-    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true;
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true, GAPS = false;
     constexpr int BS = 0;
     const Codec cq{};
     const CohortBatch cb{};
+    const CohortGaps cg{};
 #include "prf_chain_body.inc"
 }
 
@@ -422,7 +448,37 @@ __global__ __launch_bounds__(THREADS) void prf_chain_cohort_batch_kernel(const R
                                                                            const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask,
                                                                            const CohortCodec cc, const CohortBatch cb)
 {
-    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true;
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true, GAPS = false;
+    constexpr int BS = BS_;
+    const Codec cq{};
+    const CohortGaps cg{};
+#include "prf_chain_body.inc"
+}
+
+// GAPS: the two cohort chains for cipher indices in SEVERAL runs -- a round in which clients dropped out (cohort_streams.h; GAPS in
+// prf_chain_body.inc).  The one chain's streams are the |P| + runs of tb.idx; cg tells which of them complete an output and which open a
+// client, and the launch still writes every present client's ciphertext, their sum and the decrypt mask of the telescoped lists
+// (jzf_flashe.py:349-367, jzf_aggregator.py:424-430).  Separate kernels: the one-run launches keep their code objects.
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void prf_chain_cohort_runs_kernel(const RoundKeys rk, const ChainTable tb, int n_chains, int all_half_arg,
+                                                                          uint32_t iter0, uint64_t mask_lo, uint64_t mask_hi,
+                                                                          const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask,
+                                                                          const CohortCodec cc, const CohortGaps cg)
+{
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true, GAPS = true;
+    constexpr int BS = 0;
+    const Codec cq{};
+    const CohortBatch cb{};
+#include "prf_chain_body.inc"
+}
+
+template <int THREADS, int BS_>
+__global__ __launch_bounds__(THREADS) void prf_chain_cohort_batch_runs_kernel(const RoundKeys rk, const ChainTable tb, int n_chains, int all_half_arg,
+                                                                                uint32_t iter0, uint64_t mask_lo, uint64_t mask_hi,
+                                                                                const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask,
+                                                                                const CohortCodec cc, const CohortBatch cb, const CohortGaps cg)
+{
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true, GAPS = true;
     constexpr int BS = BS_;
     const Codec cq{};
 #include "prf_chain_body.inc"
@@ -1884,24 +1940,44 @@ hipError_t launch_prf_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec,
     (void)n_jobs;                            // (int_bits > 64: counters do not depend on the chunking)
     const int bs = !cb ? 0 : (cb->field_bits < 1 || cb->field_bits > env.b) ? -1 : env.b / cb->field_bits;
     if (!cohort_chain_admits(env, n_vec, n, bs) || !sum_out_dev || !u_dev || cc.n_layers < 1 || (cb && !cb->rows)) return hipErrorNotSupported;
-    for (int v = 1; v < n_vec; v++) if (idx[v] != idx[v - 1] + 1u) return hipErrorNotSupported;
-    if (idx[n_vec - 1] == 0xffffffffu) return hipErrorNotSupported;
+    // (any strictly ascending idx: one run launches the kernels it always has, several runs the GAPS ones over |P| + runs streams)
+    flashe_tables::CohortStreams st;
+    if (flashe_tables::cohort_streams(idx, n_vec, kMaxLinks + kMaxChains, st) != flashe_tables::kCohortStreamsOk) return hipErrorNotSupported;
     for (int v = 0; v < n_vec; v++) if (!out_dev[v]) return hipErrorNotSupported;
     const uint64_t tiles = (n + 255) / 256, u_stride = cb ? cb->n_values : n;
+    const int n_streams = static_cast<int>(st.idx.size());
     ChainTable tb{};
     tb.first[0] = 0; tb.count[0] = n;
     tb.len[0] = static_cast<uint8_t>(n_vec);
     tb.sum_out[0] = sum_out_dev;
-    for (int s = 0; s < n_vec; s++) tb.idx[s] = idx[s];
-    tb.idx[n_vec] = idx[n_vec - 1] + 1u;
+    for (int s = 0; s < n_streams; s++) tb.idx[s] = st.idx[s];
     for (int l = 0; l < n_vec; l++) {
         tb.in[l] = reinterpret_cast<const uint64_t *>(u_dev + static_cast<uint64_t>(l) * u_stride);       // the link's draws, one per value (CohortCodec)
         tb.out[l] = out_dev[l];
     }
-    tb.wend[0] = tiles * static_cast<uint64_t>(n_vec + 1);
+    tb.wend[0] = tiles * static_cast<uint64_t>(n_streams);
     uint64_t lo, hi;
     masks_of(env.b, &lo, &hi);
     const dim3 grid(static_cast<unsigned>(std::min<uint64_t>(tiles, static_cast<uint64_t>(env.num_cus)))), block(kPrfThreads);
+    if (st.runs > 1) {
+        CohortGaps cg{};
+        cg.n_streams = n_streams;
+        int done = 0;                        // outputs completed by the streams so far (cohort_streams: links are finished in turn)
+        for (int s = 0; s < n_streams; s++) {
+            if ((s & 15) == 0) cg.base[s >> 6] |= static_cast<uint32_t>(done) << (((s >> 4) & 3) * 8);
+            cg.bits[s >> 4] |= static_cast<uint32_t>(st.bits[s] & 3u) << ((s & 15) * 2);
+            if (st.bits[s] & flashe_tables::kStreamCompletes) done++;
+        }
+#define COHORT_BATCH_RUNS(BS) hipLaunchKernelGGL((prf_chain_cohort_batch_runs_kernel<kPrfThreads, BS>), grid, block, 0, env.stream, env.rk, tb, 1, 0, iter, lo, hi, env.te0_dev, dmask_dev, cc, *cb, cg)
+        switch (bs) {
+        case 0: hipLaunchKernelGGL((prf_chain_cohort_runs_kernel<kPrfThreads>), grid, block, 0, env.stream, env.rk, tb, 1, 0, iter, lo, hi, env.te0_dev, dmask_dev, cc, cg); break;
+        case 5: COHORT_BATCH_RUNS(5); break;
+        case 6: COHORT_BATCH_RUNS(6); break;
+        default: COHORT_BATCH_RUNS(7); break;
+        }
+#undef COHORT_BATCH_RUNS
+        return hipGetLastError();
+    }
 #define COHORT_BATCH(BS) hipLaunchKernelGGL((prf_chain_cohort_batch_kernel<kPrfThreads, BS>), grid, block, 0, env.stream, env.rk, tb, 1, 0, iter, lo, hi, env.te0_dev, dmask_dev, cc, *cb)
     switch (bs) {
     case 0: hipLaunchKernelGGL((prf_chain_cohort_kernel<kPrfThreads>), grid, block, 0, env.stream, env.rk, tb, 1, 0, iter, lo, hi, env.te0_dev, dmask_dev, cc); break;

@@ -1,7 +1,14 @@
 // The body of prf_chain_kernel<THREADS, SUM, CODEC>, prf_chain_dmask_kernel<THREADS>, prf_dmask_sum128_kernel<THREADS> and
 // prf_chain_cohort_kernel<THREADS> and prf_chain_cohort_batch_kernel<THREADS, BS> (kernels.hip), included INSIDE each kernel: the kernel defines
-// THREADS, SUM, CODEC, DMASK, D128, COHORT and BS as compile-time constants and has the arguments rk, tb, n_chains, all_half_arg, iter0, mask_lo,
-// mask_hi, te0, cq, cc, cb and dmask in scope.
+// THREADS, SUM, CODEC, DMASK, D128, COHORT, BS and GAPS as compile-time constants and has the arguments rk, tb, n_chains, all_half_arg, iter0, mask_lo,
+// mask_hi, te0, cq, cc, cb, cg and dmask in scope.
+// GAPS (COHORT only, prf_chain_cohort_runs_kernel / prf_chain_cohort_batch_runs_kernel): the cohort's cipher indices form SEVERAL runs -- clients
+// dropped out.  The stream loop runs over the cg.n_streams streams of tb.idx (cohort_streams.h); a stream's word of CohortGaps (a wave-uniform
+// scalar read of the kernel arguments) says whether it completes an output -- the next link in turn -- and whether it opens a client.  A stream
+// that completes nothing requests no float or draw, stores nothing and adds nothing to the sums; the registers that hold the first stream's
+// blocks in the other DMASK kernels accumulate the decrypt mask instead: -= on a run-opening stream, += on a run-closing one, stored
+// beside the sum on the last stream.  Every branch on GAPS is an `if constexpr` or a conditional on the constant, and the other instantiations
+// declare nothing for it: they compile to the kernels they were.
 // BS > 0 (COHORT only): the BATCHED cohort -- the chain's elements are the model's batched elements and every output's plaintext packs BS
 // quantised values of its client (CohortBatch cb beside cc; tb.in[link] = that client's draws, value-indexed).  The floats and draws of an
 // element are requested in runs, quantised and packed BEFORE the stream's rounds (cohort_batch_element): only the two packed plaintexts
@@ -14,6 +21,8 @@
     static_assert(!D128 || DMASK, "the int_bits = 128 specialisation is the decrypt-mask chain's");
     static_assert(!COHORT || (DMASK && !D128), "the cohort front end rides on the summed decrypt-mask chain");
     static_assert(BS == 0 || COHORT, "batching is a form of the cohort front end");
+    static_assert(!GAPS || COHORT, "several runs of indices are a form of the cohort chain");
+    (void)cg;
     (void)dmask;
     (void)cc;
     (void)cb;
@@ -32,7 +41,7 @@
     {
         // round-1 prefix words of every stream (chains never straddle a 2^32 counter window: host-checked)
         const int last = n_chains - 1;
-        const int n_streams = tb.sbase[last] + tb.len[last] + ((tb.flags[last] & 1) ? 0 : 1);
+        const int n_streams = GAPS ? cg.n_streams : tb.sbase[last] + tb.len[last] + ((tb.flags[last] & 1) ? 0 : 1);
         for (int s = threadIdx.x; s < n_streams; s += THREADS) {
             int i = 0;
             while (i < last && s >= tb.sbase[i + 1]) i++;
@@ -44,7 +53,7 @@
         if (threadIdx.x < static_cast<unsigned>(n_chains)) {
             const int i = threadIdx.x;
             const uint64_t Wt = tb.wend[last], cw = i ? tb.wend[i - 1] : 0;
-            const uint32_t w = tb.len[i] + ((tb.flags[i] & 1) ? 0u : 1u);
+            const uint32_t w = GAPS ? static_cast<uint32_t>(cg.n_streams) : tb.len[i] + ((tb.flags[i] & 1) ? 0u : 1u);      // (GAPS: tiles are weighted by the streams they compute)
             uint64_t a, b, T;
             if (Wt <= 0xffffffffull && gridDim.x <= 0xffffu) {
                 const uint32_t W32 = static_cast<uint32_t>(Wt), G = gridDim.x, g = blockIdx.x, c32 = static_cast<uint32_t>(cw);
@@ -94,7 +103,7 @@
                             (quarter ? 64u * static_cast<uint32_t>(q & 3u) : 0u);                             // first counter of the item
         const int link0 = tb.link0[cur], sbase = tb.sbase[cur];
         const bool single = !D128 && (tb.flags[cur] & 1), in2 = !D128 && (tb.flags[cur] & 2);
-        const int n_streams = tb.len[cur] + (single ? 0 : 1);
+        const int n_streams = GAPS ? cg.n_streams : tb.len[cur] + (single ? 0 : 1);
         if constexpr (D128) {
             if (whole) {
 #include "prf_chain_sum128_tile.inc"
@@ -109,7 +118,7 @@
             uint32_t vB0 = T3((jl + 128u) ^ rk.w[3], SEL_B0), vB1 = T3((jl + 192u) ^ rk.w[3], SEL_B0);
             u128 pA0 = 0, pA1 = 0, pB0 = 0, pB1 = 0;
             u128 qA0 = 0, qA1 = 0, qB0 = 0, qB1 = 0;                   // SUM: running sum of the outputs of the lane's four elements
-            u128 dA0 = 0, dA1 = 0, dB0 = 0, dB1 = 0;                   // DMASK: the first stream's blocks of the lane's four elements
+            u128 dA0 = 0, dA1 = 0, dB0 = 0, dB1 = 0;                   // DMASK: the first stream's blocks of the lane's four elements (GAPS: their running decrypt mask)
             uint64_t *const sum_out = SUM ? tb.sum_out[cur] : nullptr;
             // COHORT: the table row of each pair's first element, found once per tile (every link works on the same elements); -1 = the
             // pair straddles a layer boundary (at most one pair per layer of the model) and its lanes look their rows up themselves
@@ -133,7 +142,7 @@
             for (int c = 0; c < n_streams; c++) {
                 const CtrPrefix pre = load_prefix(pre_lds, sbase + c);
                 const CtrUniform U = ctr_uniform(rk, te0, pre, x3);
-                const int link = single ? c : c - 1;                   // the output this stream completes
+                const int link = GAPS ? cohort_stream_link(cg, c) : single ? c : c - 1;      // the output this stream completes
                 const uint64_t *in = link >= 0 ? tb.in[link0 + link] : nullptr;
                 uint64_t *out = link >= 0 ? tb.out[link0 + link] : nullptr;
                 const bool last_stream = c == n_streams - 1;
@@ -236,7 +245,24 @@
                                 }
                             }
                         }
-                        if constexpr (DMASK) {
+                        if constexpr (GAPS) {
+                            // (the running decrypt mask: the stream's bits and p are wave-uniform)
+                            const uint32_t sbits = cohort_stream_bits(cg, c);
+                            if (sbits == 2u) {
+                                if (p == 0) { dA0 -= c0; dA1 -= c1; } else { dB0 -= c0; dB1 -= c1; }
+                            } else if (sbits == 1u) {
+                                if (p == 0) { dA0 += c0; dA1 += c1; } else { dB0 += c0; dB1 += c1; }
+                            }
+                            if (last_stream && dmask != nullptr) {
+                                if (p == 0) {
+                                    if (a0) st128_nt(dmask + 2 * k0, dA0 & mask);
+                                    if (a1) st128_nt(dmask + 2 * k1, dA1 & mask);
+                                } else {
+                                    if (a0) st128_nt(dmask + 2 * k0, dB0 & mask);
+                                    if (a1) st128_nt(dmask + 2 * k1, dB1 & mask);
+                                }
+                            }
+                        } else if constexpr (DMASK) {
                             // (p is wave-uniform: the same scalar branch as the running sums)
                             if (c == 0) {
                                 if (p == 0) { dA0 = c0; dA1 = c1; } else { dB0 = c0; dB1 = c1; }
@@ -314,10 +340,10 @@
             }
             u128 p0 = 0, p1 = 0, q0 = 0, q1 = 0;
             uint64_t *const sum_out = SUM ? tb.sum_out[cur] : nullptr;
-            u128 d0 = 0, d1 = 0;                                        // DMASK: the first stream's blocks of the lane's two elements
+            u128 d0 = 0, d1 = 0;                                        // DMASK: the first stream's blocks of the lane's two elements (GAPS: their running decrypt mask)
             for (int c = 0; c < n_streams; c++) {
                 const CtrPrefix pre = load_prefix(pre_lds, sbase + c);
-                const int link = single ? c : c - 1;
+                const int link = GAPS ? cohort_stream_link(cg, c) : single ? c : c - 1;
                 const uint64_t *in = link >= 0 ? tb.in[link0 + link] : nullptr;
                 uint64_t *out = link >= 0 ? tb.out[link0 + link] : nullptr;
                 u128 x0 = 0, x1 = 0;
@@ -392,7 +418,14 @@
                         if (a1) st128_nt(sum_out + 2 * k1, q1 & mask);
                     }
                 }
-                if constexpr (DMASK) {
+                if constexpr (GAPS) {
+                    const uint32_t sbits = cohort_stream_bits(cg, c);
+                    if (sbits == 2u) { d0 -= c0; d1 -= c1; } else if (sbits == 1u) { d0 += c0; d1 += c1; }
+                    if (c == n_streams - 1 && dmask != nullptr) {
+                        if (a0) st128_nt(dmask + 2 * k0, d0 & mask);
+                        if (a1) st128_nt(dmask + 2 * k1, d1 & mask);
+                    }
+                } else if constexpr (DMASK) {
                     if (c == 0) { d0 = c0; d1 = c1; }
                     if (c == n_streams - 1 && (!COHORT || dmask != nullptr)) {
                         if (a0) st128_nt(dmask + 2 * k0, (c0 - d0) & mask);

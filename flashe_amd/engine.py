@@ -660,6 +660,42 @@ class Engine:
                                                                 element_bits, field_bits, self._ptr(u), pc, self._ptr(sum_out), self._ptr(dmask))
         return self._took(rc)
 
+    def quantize_encrypt_cohort_runs_dev(self, it, idx, n, n_jobs, layers, srcs, dtypes, element_bits, u, cts, sum_out, dmask=None):
+        """quantize_encrypt_cohort_dev for a round in which clients dropped out (flashe_quantize_encrypt_cohort_runs_dev): idx = the cipher
+        indices of the clients that report, strictly ascending and below 2^32 - 1 (ValueError for an index outside [0, 2^32)); srcs,
+        dtypes, the draws and cts hold one entry per index.  One run of consecutive indices is quantize_encrypt_cohort_dev bit for bit;
+        several runs share |idx| + runs streams and dmask receives the decrypt mask of telescope(idx).  Returns False -- nothing was
+        launched -- when the library declines the shape (FLASHE_ENOTSUP: also more than 144 streams), True otherwise."""
+        arr, nl = self._tensor_layers(layers)
+        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
+        pc, _k = self._ptr_array(cts)
+        pi, _ki = self._cohort_idx(idx, C)
+        rc = self._lib.flashe_quantize_encrypt_cohort_runs_dev(self._h, it, pi, C, int(n), n_jobs, arr, nl, ps, pd, element_bits, self._ptr(u), pc,
+                                                               self._ptr(sum_out), self._ptr(dmask))
+        return self._took(rc)
+
+    def quantize_batch_encrypt_cohort_runs_dev(self, it, idx, n_values, n_elems, n_jobs, layers, srcs, dtypes, element_bits, field_bits, u, cts,
+                                               sum_out, dmask=None):
+        """quantize_batch_encrypt_cohort_dev with the cipher indices of the clients that report
+        (flashe_quantize_batch_encrypt_cohort_runs_dev), under quantize_encrypt_cohort_runs_dev's rules."""
+        arr, nl = self._tensor_layers(layers)
+        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
+        pc, _k = self._ptr_array(cts)
+        pi, _ki = self._cohort_idx(idx, C)
+        rc = self._lib.flashe_quantize_batch_encrypt_cohort_runs_dev(self._h, it, pi, C, int(n_values), int(n_elems), n_jobs, arr, nl, ps, pd,
+                                                                     element_bits, field_bits, self._ptr(u), pc, self._ptr(sum_out), self._ptr(dmask))
+        return self._took(rc)
+
+    @staticmethod
+    def _cohort_idx(idx, C):
+        """The cipher indices of a cohort's C clients as a uint32 array (nothing is reduced mod 2^32 on the way)."""
+        idx = [int(v) for v in idx]
+        if len(idx) != C:
+            raise ValueError(f"{len(idx)} cipher indices for {C} clients")
+        if any(v < 0 or v >= 2 ** 32 for v in idx):
+            raise ValueError("cipher indices must lie in [0, 2^32)")
+        return _u32_list(idx)
+
     def cohort_masks_dev(self, it, first_idx, n_clients, n, n_jobs, masks, compact=False):
         """A cohort's precomputed encrypt masks as ONE chain of n_clients + 1 streams into the caller's vectors:
         masks[c][j] = term(it, first_idx + c)[j] - term(it, first_idx + c + 1)[j] mod 2^b.  Limb layout (n x L limbs each): n_clients linked

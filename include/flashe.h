@@ -79,7 +79,9 @@ typedef struct flashe_ctx flashe_ctx;
  *      element) and flashe_combine_unbatch_unquantize_model_dev (the batched codec back end over a sum and caller-held masks);
  *      flashe_cohort_masks_u32_dev (a cohort's precomputed encrypt masks in the compact layout, one chain of C + 1 streams) and
  *      flashe_quantize_combine_cohort_dev / flashe_quantize_combine_cohort_u32_dev / flashe_quantize_batch_combine_cohort_dev (a
- *      precompute job's cohort online: C float models + C caller-held masks to C ciphertexts and their sum in one pass, no AES) */
+ *      precompute job's cohort online: C float models + C caller-held masks to C ciphertexts and their sum in one pass, no AES);
+ *      flashe_quantize_encrypt_cohort_runs_dev / flashe_quantize_batch_encrypt_cohort_runs_dev (the cohort's chained launches for a round
+ *      in which clients dropped out: any strictly ascending cipher indices) */
 #define FLASHE_ABI_VERSION 4
 int flashe_abi_version(void);
 int flashe_device_count(int *count);
@@ -703,6 +705,30 @@ int flashe_quantize_batch_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uin
                                              uint32_t n_jobs, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
                                              const int32_t *src_dtype, int element_bits, int field_bits, const double *u_dev, uint64_t *const *ct_dev,
                                              uint64_t *sum_out_dev, uint64_t *dmask_dev);
+/* The two chained launches above for a round in which clients DROPPED OUT (new), jzf_flashe.py:349-367, jzf_aggregator.py:424-430: idx =
+ * the cipher indices of the n_clients clients that report, strictly ascending (P = {0,1,3,4} when client 2 of five misses the round);
+ * everything indexed by client -- src_dev, src_dtype, the draws u_dev[c * n ..] and ct_dev -- counts the clients of idx, c = 0 ..
+ * n_clients - 1.  The launch computes the streams S = { s : s in P or s - 1 in P }, |P| + runs of them instead of 2 |P| (a stream
+ * strictly inside a dropped run of two or more clients is not computed), and writes ct_dev[c] (bit for bit
+ * flashe_quantize_encrypt_tensors_dev with cipher index idx[c]), sum_out_dev = sum_c ct_dev[c] mod 2^b and, when dmask_dev is not NULL,
+ * the decrypt mask of the telescoped lists, sum_r term(last index of run r + 1) - term(first index of run r) mod 2^b: what
+ * flashe_decrypt_dev with flashe_telescope(idx) adds to the sum (feed it to flashe_combine_unquantize_model_dev).  One run of consecutive
+ * indices launches exactly what flashe_quantize_encrypt_cohort_dev launches and writes its bytes.
+ * FLASHE_EINVAL: idx NULL, not strictly ascending (unsorted, duplicates) or holding 2^32 - 1, and the argument errors of
+ * flashe_quantize_encrypt_cohort_dev.  FLASHE_ENOTSUP -- nothing launched -- outside that function's admission with n_clients = |P|, and
+ * when |P| + runs exceeds the 144 streams one launch holds (128 clients may form 16 runs); the caller then quantises per client and uses
+ * flashe_encrypt_batch_sum_dev, which takes any indices.  The table uploads synchronise; not capturable. */
+int flashe_quantize_encrypt_cohort_runs_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                            const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                            int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev, uint64_t *dmask_dev);
+/* The same for a BATCHED job at int_bits > 64 (new), jzf_quantize.py:162-185, jzf_flashe.py:349-367, jzf_aggregator.py:424-430:
+ * flashe_quantize_batch_encrypt_cohort_dev with the cipher indices idx of the clients that report, under the rules of
+ * flashe_quantize_encrypt_cohort_runs_dev (the length rule counted in the n_elems batched elements, bs = 5 .. 7; feed the mask to
+ * flashe_combine_unbatch_unquantize_model_dev). */
+int flashe_quantize_batch_encrypt_cohort_runs_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n_values, uint64_t n_elems,
+                                                  uint32_t n_jobs, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
+                                                  const int32_t *src_dtype, int element_bits, int field_bits, const double *u_dev, uint64_t *const *ct_dev,
+                                                  uint64_t *sum_out_dev, uint64_t *dmask_dev);
 /* A precompute job's cohort (new), jzf_flashe.py:599-631, 456-488: every client computes its next round's encrypt mask in idle time and
  * its online step is a quantise plus a mask add.  For a cohort the masks are ONE chain of n_clients + 1 streams into vectors the caller
  * owns, mask[c][j] = term(iter, first_idx + c)[j] - term(iter, first_idx + c + 1)[j] mod 2^b: in the limb layout
