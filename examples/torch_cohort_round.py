@@ -17,7 +17,12 @@ which this example checks.
   --drop i,j   clients i and j miss the round (dropout-aware decrypt is what FLASHE is for): quantize_encrypt(present=...) takes the
                Weights of the clients that report, and at --bits > 64 the round is still one chained launch, over present + runs PRF
                streams, whose decrypt mask is that of the telescoped index lists; the new global model is what the present clients'
-               own steps and a decrypt told who uploaded (set_idx_list(present)) give, which this example checks"""
+               own steps and a decrypt told who uploaded (set_idx_list(present)) give, which this example checks
+  --rng philox the stochastic-rounding draws come from one np.random.Generator per client instead of NumPy's global stream
+               (quantize_encrypt(rng=[...])): counter-based Philox generators, whose draws for the whole cohort are ONE asynchronous
+               launch on the device (models of 65,536 values or more: this example's hold 126,666) and whose advanced states come back
+               -- the sequential clients below draw from identically seeded generators and must leave them in the same place;
+               --rng pcg64 takes any other Generator: the same call, drawn on the host"""
 import argparse
 import os
 import sys
@@ -55,6 +60,7 @@ def main():
     ap.add_argument("--batch", action="store_true")
     ap.add_argument("--precompute", action="store_true")
     ap.add_argument("--drop", default="", help="comma-separated clients that miss the round, e.g. 2,7")
+    ap.add_argument("--rng", choices=["philox", "pcg64"], default=None, help="draw from one np.random.Generator per client")
     opt = ap.parse_args()
     cm.N_JOBS = 16                                           # every party must use the same value
     C, key = 10, bytes(range(32))
@@ -70,6 +76,13 @@ def main():
             "precompute": {"enable": opt.precompute, "num_params": num_params}}
     it = 1 if opt.precompute else 0
 
+    def generators():
+        """One Generator per present client, seeded alike on both sides (None: NumPy's global stream, seeded below)."""
+        if opt.rng is None:
+            return None
+        bitgen = np.random.Philox if opt.rng == "philox" else np.random.PCG64
+        return [np.random.Generator(bitgen(1000 + c)) for c in present]
+
     cohort = FlasheCohort(args, first_idx=0, n_local=C, num_clients=C, prp_seed=key, compact=opt.compact)
     if opt.precompute:
         cohort.set_iter_index(it - 1)
@@ -77,7 +90,8 @@ def main():
     cohort.set_iter_index(it)
     np.random.seed(0)
     with torch.no_grad():
-        upload = cohort.quantize_encrypt([Weights(layers[c]) for c in present], normalize=True, present=present if dropped else None)
+        gens = generators()
+        upload = cohort.quantize_encrypt([Weights(layers[c]) for c in present], normalize=True, present=present if dropped else None, rng=gens)
         new_global = {name: torch.empty_like(t) for name, t in layers[0].items()}
         cohort.decrypt_unquantize(out=new_global, unnormalize=True)
     print(f"{C} clients{f' of which {dropped} dropped out' if dropped else ''}, {sum(t.numel() for t in layers[0].values())} parameters each: path {upload.path!r}, "
@@ -95,9 +109,9 @@ def main():
         clients.append(cl)
     np.random.seed(0)
     with torch.no_grad():
-        cts = []
-        for c in present:
-            w = clients[c].quantize_encrypt(Weights(layers[c]), device=True, normalize=True)
+        cts, twins = [], generators()
+        for p, c in enumerate(present):
+            w = clients[c].quantize_encrypt(Weights(layers[c]), device=True, normalize=True, rng=twins[p] if twins else None)
             cts.append(w._weights[w.walking_order[0]])
         lead = clients[present[0]]
         agg = lead.cipher.aggregate(cts)
@@ -108,6 +122,8 @@ def main():
     for p, c in enumerate(present):
         assert np.array_equal(values(upload.ciphertexts[p]), values(cts[p])), f"client {c}'s upload differs"
     assert np.array_equal(values(upload.partial_sum), values(agg))
+    if gens:                                                 # the cohort handed every generator back where its client's own step leaves it
+        assert all(a.random() == b.random() for a, b in zip(gens, twins))
     for name in want:
         assert torch.equal(want[name].view(torch.uint8), new_global[name].view(torch.uint8)), name
     if dropped:

@@ -52,6 +52,12 @@ class TensorLayer(ctypes.Structure):
                 ("dtype", ctypes.c_int32), ("flags", ctypes.c_int32)]
 
 
+class PhiloxSegment(ctypes.Structure):
+    """flashe_philox_segment of include/flashe.h."""
+    _fields_ = [("key", ctypes.c_uint64 * 2), ("counter", ctypes.c_uint64 * 4), ("buffer", ctypes.c_uint64 * 4), ("buffer_pos", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("n", ctypes.c_uint64), ("offset", ctypes.c_uint64)]
+
+
 TENSOR_F32, TENSOR_F64, TENSOR_F16, TENSOR_BF16 = 0, 1, 2, 3
 TENSOR_SHIFT, TENSOR_SHIFT_WIDE, TENSOR_LOOP_F64 = 1, 2, 4
 
@@ -226,6 +232,10 @@ _SIGNATURES = {
     "flashe_mt19937_random_dev": (c_int, [c_vp, c_u32p, c_u32p, c_u64, c_vp]),
     "flashe_mt19937_jump_selfcheck": (c_int, []),
     "flashe_mt19937_plan": (c_int, [c_u32, c_u64, c_u32p, c_u32p, c_u32p]),
+    "flashe_philox_random_dev": (c_int, [c_vp, ctypes.POINTER(PhiloxSegment), c_int, c_vp]),
+    "flashe_philox_block": (c_int, [c_u64p, c_u64p, c_u64p]),
+    "flashe_philox_advance": (c_int, [c_u64p, c_u64p, c_u32p, c_u64p, c_u64]),
+    "flashe_philox_grid": (c_int, [c_vp, c_u64, c_u32, c_u32p, c_u64p]),
     "flashe_quantize_dev": (c_int, [c_vp, c_u64, c_vp, c_int, ctypes.c_double, c_int, c_vp, c_vp]),
     "flashe_quantize": (c_int, [c_vp, c_u64, c_vp, c_int, ctypes.c_double, c_int, c_vp, c_vp]),
     "flashe_unquantize_dev": (c_int, [c_vp, c_u64, c_vp, c_int, ctypes.c_double, c_int, c_int, c_vp]),

@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _lib, interop
 from .cipher import FlasheCipher, _CtxMask
-from .quantize import ACIQ, QuantizingClient, _loop_dtype
+from .quantize import ACIQ, QuantizingClient, _check_rng, _loop_dtype, _rng_on_device
 
 _RNG_RUN_MAX = 1 << 26          # draws per device call of quantize_encrypt (512 MiB of float64)
 
@@ -186,18 +186,57 @@ def _draws_on_device(count):
     return os.environ.get("FLASHE_DEVICE_RNG", "1") != "0" and count >= DEVICE_RNG_MIN and np.random.get_state()[0] == "MT19937"
 
 
-def _draws(eng, count):
+def _draws(eng, count, rng=None):
     """The next `count` stochastic-rounding draws of NumPy's global stream as a device buffer: generated on the device
-    (_draws_on_device), else drawn on the host and uploaded."""
+    (_draws_on_device), else drawn on the host and uploaded.  rng (a Generator): its next `count` draws instead -- on the device under
+    _rng_on_device (Philox), else rng.random(count) uploaded."""
+    if rng is not None:
+        return eng.philox_random_dev([rng], [count]) if _rng_on_device(eng, rng, count) else eng.upload(rng.random(count))
     return eng.numpy_random_dev(count) if _draws_on_device(count) else eng.upload(np.random.random(count))
 
 
-def _cohort_draws(eng, C, per_client, seeds):
+def _skip_draws(count, rng=None):
+    """`count` draws taken and dropped (a refusal that the call-by-call step raises after its quantiser has drawn): from rng, else from
+    NumPy's global stream."""
+    for at in range(0, count, _RNG_RUN_MAX):
+        (np.random.random if rng is None else rng.random)(min(_RNG_RUN_MAX, count - at))
+
+
+def _rng_kw(rng):
+    """rng= as a keyword for a forwarded call: absent without one, so that rng=None makes exactly the calls it always made."""
+    return {} if rng is None else {"rng": rng}
+
+
+def _client_rng(rng, ci):
+    """Client ci's Generator of a cohort's rng= (one Generator for all, or one per client), None without."""
+    return rng[ci] if isinstance(rng, list) else rng
+
+
+def _cohort_rng_draws(eng, C, per_client, rng):
+    """_cohort_draws from the caller's generators: one Generator gives ONE stretch of C per_client draws, a list client c's stretch from
+    rng[c].  Every stretch that runs on the device (_rng_on_device) is a segment of ONE launch whatever C is; the others are
+    rng.random(...) on the host, uploaded in runs of at most _RNG_RUN_MAX draws."""
+    du = eng.alloc(max(8 * C * per_client, 16))
+    stretches = [(rng[ci], ci * per_client, per_client) for ci in range(C)] if isinstance(rng, list) else [(rng, 0, C * per_client)]
+    dev = [st for st in stretches if _rng_on_device(eng, st[0], st[2])]
+    for g, first, count in stretches:
+        if not _rng_on_device(eng, g, count):
+            for at in range(first, first + count, _RNG_RUN_MAX):
+                du.upload_at(8 * at, g.random(min(_RNG_RUN_MAX, first + count - at)))
+    for at in range(0, len(dev), eng.PHILOX_MAX_SEGMENTS if dev else 1):              # (a cohort holds at most 128 clients: one launch)
+        part = dev[at:at + eng.PHILOX_MAX_SEGMENTS]
+        eng.philox_random_dev([g for g, _f, _c in part], [c for _g, _f, c in part], out=du, offsets=[f for _g, f, _c in part])
+    return du
+
+
+def _cohort_draws(eng, C, per_client, seeds, rng=None):
     """The stochastic-rounding draws of C clients, client-major, as a device buffer: client c's are draws [c per_client, (c + 1) per_client).
     From the global stream (seeds=None) they are ONE stretch of C per_client draws -- the clients draw one after the other -- generated in
     device calls of at most _RNG_RUN_MAX draws whatever client they belong to (the jump-ahead of a device call is paid per call, not per
     client); with seeds every client's stretch starts at its own seed.  On the device under quantize_encrypt's rule (_draws_on_device, per
-    call), else drawn on the host and uploaded."""
+    call), else drawn on the host and uploaded.  rng: the caller's generators instead (_cohort_rng_draws)."""
+    if rng is not None:
+        return _cohort_rng_draws(eng, C, per_client, rng)
     du = eng.alloc(max(8 * C * per_client, 16))
     for seed, first, count in ([(None, 0, C * per_client)] if seeds is None else [(seeds[ci], ci * per_client, per_client) for ci in range(C)]):
         if seed is not None:
@@ -276,10 +315,11 @@ class FlasheClient(object):
         self.quantizer.set_iter(iter_index)
 
     # the quantiser forwarders of _Client / Guest / Host (:159-163, :254-264)
-    def quantize(self, weights):
+    def quantize(self, weights, rng=None):
+        rng = _check_rng(rng)
         if self.quantizer.layer_size_list is None:
             self.quantizer.set_layer_size_list(weights)
-        return self.quantizer.quantize(weights)
+        return self.quantizer.quantize(weights, **_rng_kw(rng))
 
     def normalize(self, weights):
         if self.quantizer.layer_size_list is None:
@@ -373,19 +413,24 @@ class FlasheClient(object):
         elif mode == "single":
             c.next_iter_decrypt_prepared.pop('minus', None)
 
-    def _refuse_prepared_len(self, n_ct, n_values):
+    def _refuse_prepared_len(self, n_ct, n_values, rng=None):
         """An encrypt cache of another length: the call-by-call step's ValueError (cipher._check_prepared_len), raised where that step
-        raises it -- after its quantiser has drawn one value of NumPy's stream per model value.  The cache stays."""
+        raises it -- after its quantiser has drawn one value of NumPy's stream (of rng) per model value.  The cache stays."""
         c = self.cipher
         cache = c.next_iter_encrypt_prepared['add']
         if len(cache) == n_ct:
             return
-        for at in range(0, n_values, _RNG_RUN_MAX):
-            np.random.random(min(_RNG_RUN_MAX, n_values - at))
+        _skip_draws(n_values, rng)
         c._check_prepared_len(cache, n_ct)
 
-    def quantize_encrypt(self, weights, device=True, normalize=False):
-        """normalize (new): QuantizingClient.normalize first (`-= past_layer_mean_list[i]`, jzf_quantize.py:542-547).  Layers may also be
+    def quantize_encrypt(self, weights, device=True, normalize=False, rng=None):
+        """rng (new): a np.random.Generator the stochastic-rounding draws come from -- the result is that of the same call with every
+        np.random.random(k) replaced by rng.random(k), the sparse job's 'zzz' draw included (the next draw of the same generator); NumPy's
+        global stream is neither read nor advanced.  Over np.random.Philox, stretches of DEVICE_RNG_MIN draws or more are generated on
+        the device (flashe_philox_random_dev) and the advanced state is put back into the generator; any other generator draws on the
+        host.  Anything that is not a Generator: TypeError, before anything is touched.
+
+        normalize (new): QuantizingClient.normalize first (`-= past_layer_mean_list[i]`, jzf_quantize.py:542-547).  Layers may also be
         a framework's float DEVICE tensors (float32 / float64 / float16 / bfloat16, DLPack or __cuda_array_interface__), mixed with host
         layers: they are read where they lie (see _quantize_encrypt_tensors), no layer byte crosses PCIe.
 
@@ -410,15 +455,16 @@ class FlasheClient(object):
         and drops 'add' as the reference does.  Batched sparse jobs, sparse jobs with a cache and masks a caller assigned as plain arrays
         take the same sequence call by call on the host and return object arrays like the reference."""
         q = self.quantizer
+        rng = _check_rng(rng)
         if any(interop.is_foreign(weights._weights[k]) for k in weights.walking_order):
-            return self._quantize_encrypt_tensors(weights, device, normalize)
+            return self._quantize_encrypt_tensors(weights, device, normalize, rng)
         if normalize:
             self.normalize(weights)
         if q.layer_size_list is None:
             q.set_layer_size_list(weights)
         if not self._fusable(weights):
             sparse = "zzz" in weights._weights
-            weights = self.flatten_weights(self.quantize(weights))
+            weights = self.flatten_weights(self.quantize(weights, **_rng_kw(rng)))
             k0 = weights.walking_order[0]
             flat = weights._weights[k0]
             if sparse:                                                       # jzf_aggregator.py:735-743
@@ -426,7 +472,7 @@ class FlasheClient(object):
             ct = self.cipher.encrypt(flat)
             weights._weights[k0] = np.append(ct, [zero_quantized]) if sparse else ct
             return weights
-        return self._encrypt_tail(weights, device, *self._host_front_end(weights))
+        return self._encrypt_tail(weights, device, *self._host_front_end(weights), rng=rng)
 
     def _host_front_end(self, weights):
         """The fused step's front end for host layers (normalised on the host already, layer_size_list set): every layer goes up once,
@@ -459,13 +505,14 @@ class FlasheClient(object):
                   eng.quantize_batch_encrypt_prepared_model_dev)
         return mode, order, zzz, sizes, starts, shape_dict, rows, launch, keep
 
-    def _encrypt_tail(self, weights, device, mode, order, zzz, sizes, starts, shape_dict, rows, launch, keep, hold=None, normalize=False):
+    def _encrypt_tail(self, weights, device, mode, order, zzz, sizes, starts, shape_dict, rows, launch, keep, hold=None, normalize=False,
+                      rng=None):
         """The fused step behind either front end: the draws, the launches and the result.  `rows` are the layers `order` (sizes, starts,
         shape_dict) as the four entry points in `launch` -- un-batched online and prepared, batched online and prepared -- read them; mode
         is _prepared_mode of the encrypt cache; zzz the sparse job's trailing value (host) or None; keep what the launches read: it lives to
         the end of the call.  The tensor front end also passes hold (the owners of the caller's tensors: held on the engine until the
         launches have finished) and normalize (the 'zzz' value is still to be normalised -- the host front end has normalised the whole
-        model)."""
+        model); rng the Generator the draws come from (None: NumPy's global stream)."""
         from . import cipher as _cipher_mod
         from .engine import DeviceVector
         q, c = self.quantizer, self.cipher
@@ -480,8 +527,8 @@ class FlasheClient(object):
             q.shape_list = [shape_dict[k] for k in order]
             n_elems = sum((s_ + bs - 1) // bs for s_ in sizes)
             if mode == "ctx":
-                self._refuse_prepared_len(n_elems, n)
-            du = _draws(eng, n) if n else eng.alloc(16)
+                self._refuse_prepared_len(n_elems, n, rng)
+            du = _draws(eng, n, rng) if n else eng.alloc(16)
             ct = DeviceVector(eng, n_elems)
             if mode == "ctx":                   # quantise + batch + the prepared masks: one launch, no AES
                 batch_prepared(rows, q.element_bits, field_bits, du, n_elems, ct.buf)
@@ -497,7 +544,7 @@ class FlasheClient(object):
             # quantised + encrypted by one launch over its range.  Runs are capped so the draws of a huge model stay bounded.  With the ctx's
             # prepared masks the launches add them in place of the PRF streams; the run that ends the vector consumes them.
             if mode == "ctx":
-                self._refuse_prepared_len(n, n)
+                self._refuse_prepared_len(n, n, rng)
             ct = DeviceVector(eng, n + (1 if zzz is not None else 0))
             at = 0
             while at < len(order):
@@ -506,7 +553,7 @@ class FlasheClient(object):
                     tot += sizes[end]
                     end += 1
                 if tot:
-                    du, first = _draws(eng, tot), starts[at]
+                    du, first = _draws(eng, tot, rng), starts[at]
                     if mode == "ctx":
                         prepared(n, first, tot, rows, q.element_bits, du, ct.ptr + first * eng.limbs * 8)
                     else:
@@ -529,7 +576,8 @@ class FlasheClient(object):
             want = _loop_dtype(flat.dtype, 1.0)
             if flat.dtype != want:
                 flat = flat.astype(want)
-            zq = int(_as_object(_static_quantize_padding_asymmetric(flat, 1.0, q.element_bits, device=q._device, as_object=False)).reshape(-1)[0])
+            zq = int(_as_object(_static_quantize_padding_asymmetric(flat, 1.0, q.element_bits, device=q._device, as_object=False,
+                                                                     rng=rng)).reshape(-1)[0])
             ct.buf.upload_at(n * eng.limbs * 8, np.array([zq & (2 ** 64 - 1), zq >> 64][:eng.limbs], dtype=np.uint64))
             del weights._weights["zzz"]
         for k in order:
@@ -703,7 +751,7 @@ class FlasheClient(object):
         return dout
 
     # ---- a framework's device tensors either side of the client step (new; interop.py) ---------------------------------------
-    def _quantize_encrypt_tensors(self, weights, device, normalize):
+    def _quantize_encrypt_tensors(self, weights, device, normalize, rng=None):
         """quantize_encrypt with framework device tensors among the layers: each foreign layer is read in place (its own dtype; a layer
         that needs a conversion -- 16-bit, float32 quantised in float64, or normalised -- goes through one streaming pass into engine
         scratch, flashe_quantize_encrypt_tensors_dev / flashe_quantize_batch_tensors_dev), host layers go up as in the host path.  Bit for
@@ -755,7 +803,8 @@ class FlasheClient(object):
                   lambda r, *a: eng.quantize_batch_tensors_dev(r, n, *a),
                   lambda r, *a: eng.quantize_batch_encrypt_prepared_tensors_dev(r, n, *a))
         shape_dict = {k: layer[4] for k, layer in zip(order, layers)}
-        return self._encrypt_tail(weights, device, mode, order, zzz, sizes, starts, shape_dict, rows, launch, keep, hold=owners, normalize=normalize)
+        return self._encrypt_tail(weights, device, mode, order, zzz, sizes, starts, shape_dict, rows, launch, keep, hold=owners, normalize=normalize,
+                                  rng=rng)
 
     def _decrypt_unquantize_tensors(self, weights, out, unnormalize):
         """decrypt_unquantize into the caller's tensors: the fused back end writes the flat float64 model into engine scratch, one
@@ -1210,8 +1259,16 @@ class FlasheCohort(object):
         """The lead client's prepare_decrypt: the decrypting party's masks do not depend on the cohort."""
         self.lead.prepare_decrypt()
 
-    def quantize_encrypt(self, weights_list, normalize=False, seeds=None, present=None):
-        """One Weights per client (host arrays and / or framework float device tensors, as FlasheClient.quantize_encrypt takes them) ->
+    def quantize_encrypt(self, weights_list, normalize=False, seeds=None, present=None, rng=None):
+        """rng (new): the stochastic-rounding draws come from the caller's own np.random.Generator(s) -- ONE Generator: the (present) clients
+        draw one after the other from it, as seeds=None does with the global stream; a list of one Generator per (present) client: client c
+        draws from rng[c], as seeds=[...] does.  The result is that of the same call with every np.random.random(k) replaced by the
+        generator's .random(k), on every path; NumPy's global stream is neither read nor advanced.  Generators over np.random.Philox with
+        DEVICE_RNG_MIN draws or more generate on the device, the whole cohort in ONE asynchronous launch whatever C is
+        (flashe_philox_random_dev), and get their advanced states back; others draw on the host.  rng with seeds, a list of another length:
+        ValueError; anything that is not a Generator: TypeError -- before anything is touched.
+
+        One Weights per client (host arrays and / or framework float device tensors, as FlasheClient.quantize_encrypt takes them) ->
         CohortUpload.  present=[positions]: a round in which clients DROPPED OUT -- the strictly ascending local positions (0 .. n_local - 1)
         of the clients that report; weights_list and seeds then hold one entry per present client, the result is that of the present
         clients' FlasheClient steps run one after the other (the p-th present client takes draws [p n, (p + 1) n), absent clients draw
@@ -1226,18 +1283,19 @@ class FlasheCohort(object):
         from .engine import DeviceVector
         ld = self.lead
         q, eng = ld.quantizer, ld.cipher.engine
-        plan, layers = self._collect(weights_list, seeds, present)
+        plan, layers = self._collect(weights_list, seeds, present, rng)
         C = len(plan.present)
-        self._refuse_prepared_len(plan, seeds)
+        rng = _check_rng(rng, C)
+        self._refuse_prepared_len(plan, seeds, rng)
         self._last, ld._cohort_mask = None, None
         path = self._choose_path(plan, layers)
         if path == PER_CLIENT:
-            return self._per_client(weights_list, normalize, seeds, plan.present)
+            return self._per_client(weights_list, normalize, seeds, plan.present, rng)
         if not ld._fusable():
             raise TypeError("FlasheCohort needs the fused client step (fuse=True, a keyed cipher, no location masks)")
         alphas = self._begin_round(plan)
         tables, keep = self._tables(plan, layers, alphas, normalize)
-        du = _cohort_draws(eng, C, plan.n, seeds)
+        du = _cohort_draws(eng, C, plan.n, seeds, rng)
         if self.compact:
             cts = [DeviceVector(eng, plan.n_elems, 1, elem_bytes=4) for _ in range(C)]
             psum = DeviceVector(eng, plan.n_elems, 1, elem_bytes=4)
@@ -1274,7 +1332,7 @@ class FlasheCohort(object):
         self._last = CohortUpload(cts, psum, path, [self.first_idx + p for p in plan.present])
         return self._last
 
-    def _collect(self, weights_list, seeds, present=None):
+    def _collect(self, weights_list, seeds, present=None, rng=None):
         """(plan, every layer of every present client as _layer_source gives it): the refusals, before anything of the cohort's state is
         touched."""
         C = self.n_local if present is None else len(weights_list)
@@ -1282,11 +1340,14 @@ class FlasheCohort(object):
             raise ValueError(f"the cohort holds {C} clients, got {len(weights_list)} Weights")
         if seeds is not None and len(seeds) != C:
             raise ValueError(f"seeds: one per client ({C}), got {len(seeds)}")
+        if rng is not None and seeds is not None:
+            raise ValueError("rng and seeds: one source of draws at a time")
+        _check_rng(rng, C)
         plan = self.plan(weights_list, present)
         eng = self.lead.cipher.engine
         return plan, [[_layer_source(eng, w._weights[k], f"client {ci} layer {k!r}") for k in plan.names] for ci, w in enumerate(weights_list)]
 
-    def _refuse_prepared_len(self, plan, seeds):
+    def _refuse_prepared_len(self, plan, seeds, rng=None):
         """A cache of another length: the call-by-call step's ValueError, where the first sequential client raises it (after its quantiser
         has drawn one value per model value, FlasheClient._refuse_prepared_len); the cache stays, and nothing of the cohort's state has
         been touched or uploaded yet."""
@@ -1294,8 +1355,7 @@ class FlasheCohort(object):
             return
         if seeds is not None:
             np.random.seed(seeds[0])
-        for at in range(0, plan.n, _RNG_RUN_MAX):
-            np.random.random(min(_RNG_RUN_MAX, plan.n - at))
+        _skip_draws(plan.n, _client_rng(rng, 0))
         self.lead.cipher._check_prepared_len(self._masks[0], plan.n_elems)
 
     def _choose_path(self, plan, layers):
@@ -1409,7 +1469,7 @@ class FlasheCohort(object):
             eng.encrypt_batch_sum_dev(c.iter_index, idxs, scheme, n_elems, _cipher_mod.N_JOBS, pts, eng.limbs, [v.buf for v in cts], psum.buf)
         return cts, psum, pts
 
-    def _per_client(self, weights_list, normalize, seeds, present=None):
+    def _per_client(self, weights_list, normalize, seeds, present=None, rng=None):
         """The present clients' own steps one after the other (one cipher re-indexed per client; with precompute: every client's own cipher
         and masks), then the aggregate of what they wrote."""
         ld = self.lead
@@ -1423,7 +1483,7 @@ class FlasheCohort(object):
                     np.random.seed(seeds[ci])
                 lw = _Layers({k: w._weights[k] for k in w.walking_order})
                 lw.walking_order = list(w.walking_order)
-                up = cl.quantize_encrypt(lw, device=True, normalize=normalize)
+                up = cl.quantize_encrypt(lw, device=True, normalize=normalize, **_rng_kw(_client_rng(rng, ci)))
                 ct = up._weights[up.walking_order[0]]
                 cts.append(cl.cipher._as_compact(ct) if self.compact else ct)
                 ld.shape_dict = cl.shape_dict
@@ -1789,8 +1849,13 @@ class FlasheSparseCohort(object):
         return self._host_masks
 
     # ---- Client.secure_aggregate's quantise + encrypt, and the arbiter's expand + reduce --------------------------------------------
-    def quantize_encrypt(self, normalize=False, seeds=None, compact=None):
-        """-> SparseCohortUpload.  Client c's upload is its own FlasheClient.quantize_encrypt(compact_c + 'zzz', device=True,
+    def quantize_encrypt(self, normalize=False, seeds=None, compact=None, rng=None):
+        """rng (new): the draws come from the caller's np.random.Generator (one: the clients draw one after the other, K + 1 each, the last
+        one a client's 'zzz' draw) or a list of one Generator per client, as FlasheCohort.quantize_encrypt takes them: np.random.random(k)
+        replaced by the generator's .random(k) on every path, the global stream untouched, Philox generators on the device in ONE launch.
+        rng with seeds or a list of another length: ValueError; not a Generator: TypeError.
+
+        -> SparseCohortUpload.  Client c's upload is its own FlasheClient.quantize_encrypt(compact_c + 'zzz', device=True,
         normalize=...) (K + 1 elements of uint64 limbs), `aggregate` is aggregate_sparse_uploads of the cohort's uploads.  compact: C
         dicts / Weights of compact layers given directly (host arrays, tensors or CompactLayers, with or without the trailing 'zzz'
         value; a bare list holds the compact layers in walking order) instead of the ones the last sparsify left.  seeds=None: the draws come from NumPy's global stream in client order -- client
@@ -1805,6 +1870,9 @@ class FlasheSparseCohort(object):
             raise ValueError("quantize_encrypt needs the round's masking choice and lists (dynamic_masking first)")
         if seeds is not None and len(seeds) != C:
             raise ValueError(f"seeds: one per client ({C}), got {len(seeds)}")
+        if rng is not None and seeds is not None:
+            raise ValueError("rng and seeds: one source of draws at a time")
+        rng = _check_rng(rng, C)
         zzzs = [np.array([0.0])] * C
         if compact is not None:
             names, rows, all_host, per_client_layers = self._given_compact(compact, zzzs)
@@ -1826,7 +1894,7 @@ class FlasheSparseCohort(object):
                                      mixed or len(zdt) != 1)
         self._last = None
         if path == PER_CLIENT:
-            return self._per_client(per_client_layers, names, zzzs, all_host, normalize, seeds)
+            return self._per_client(per_client_layers, names, zzzs, all_host, normalize, seeds, rng)
         # one quantiser state: the compact layers and the one-value 'zzz' layer are the layer_size_list, the lists hold the L compact layers
         alphas = _round_alphas(q, list(ks) + [1])
         q.r_max_list = [alphas[li] * q.num_clients for li in range(L)]
@@ -1846,7 +1914,7 @@ class FlasheSparseCohort(object):
             table.append((at, None, alphas[li], shift, _lib.TENSOR_F64 if hdt == np.float64 else _lib.TENSOR_F32, flags))
             at += ks[li]
         zvals, z64 = self._zzz_values(zzzs, normalize, L)
-        du = _cohort_draws(eng, C, K + 1, seeds)
+        du = _cohort_draws(eng, C, K + 1, seeds, rng)
         ups = [DeviceVector(eng, K + 1) for _ in range(C)]
         zbuf = eng.alloc(max(8 * C, 16))
         front, ptbuf, pts = self._launch_uploads(path, K, table, srcs, dts, du, zvals, z64, ups, zbuf)
@@ -1974,7 +2042,7 @@ class FlasheSparseCohort(object):
         self._bounds = (bounds, shape)
         return bounds
 
-    def _per_client(self, per_client_layers, names, zzzs, all_host, normalize, seeds):
+    def _per_client(self, per_client_layers, names, zzzs, all_host, normalize, seeds, rng=None):
         """The clients' own FlasheClient steps one after the other on the shared quantiser state (one cipher re-indexed per client; with
         precompute: every client's own cipher), then aggregate_sparse_uploads of what they wrote.  What FlasheClient refuses is refused
         by the first client's step, before any draw is taken."""
@@ -1993,7 +2061,7 @@ class FlasheSparseCohort(object):
                 d = {k: (layers[k].to_host() if all_host[ci] and isinstance(layers[k], CompactLayer) else layers[k]) for k in names}
                 d["zzz"] = np.array(zzzs[ci], copy=True)
                 lw = _Layers(d)
-                up = cl.quantize_encrypt(lw, device=True, normalize=normalize)
+                up = cl.quantize_encrypt(lw, device=True, normalize=normalize, **_rng_kw(_client_rng(rng, ci)))
                 ups.append(up._weights[up.walking_order[0]])
                 ld.shape_dict = cl.shape_dict
         finally:

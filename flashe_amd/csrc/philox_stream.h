@@ -1,0 +1,153 @@
+// The stream of NumPy's np.random.Philox (Philox4x64-10) as Generator.random draws it, stated once: the block function, the order in
+// which a generator state hands out the words of its blocks, the state after n draws, the counter and word of draw i, and the checks of
+// a table of output segments.  No HIP header, so that tests/host_philox_stream_check.cpp runs it on the host under sanitizers (as
+// cohort_streams.h and layer_tables.h are); philox.hip compiles the same functions for the device through FLASHE_HD.
+//   block(counter[4], key[2]) -> word[4]: ten rounds; before each of rounds 2 .. 10 the key is bumped by the Weyl constants;
+//     a round maps (c0, c1, c2, c3) to (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0));
+//   NumPy INCREMENTS the 256-bit counter (four little-endian 64-bit words, wrapping at 2^256) BEFORE it generates a block, and keeps
+//     the block's words in `buffer` with buffer_pos = the next word to hand out: a state (counter, buffer_pos = p < 4) next returns
+//     words p .. 3 of block(counter), then all of block(counter + 1), ...; p = 4 (fresh or exhausted) starts at block(counter + 1);
+//   draw = (word >> 11) * 2^-53.
+// So with  base = counter (p < 4) or counter + 1 (p = 4)  and  skip = p (p < 4) or 0:  draw i is word (skip + i) % 4 of
+// block(base + (skip + i) / 4).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <algorithm>
+#include <vector>
+
+#ifndef FLASHE_HD
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define FLASHE_HD __host__ __device__ __forceinline__
+#else
+#define FLASHE_HD inline
+#endif
+#endif
+#ifdef __clang__
+#define FLASHE_UNROLL _Pragma("unroll")
+#else
+#define FLASHE_UNROLL
+#endif
+
+namespace flashe_philox {
+
+constexpr uint64_t kM0 = 0xD2E7470EE14C6C93ull, kM1 = 0xCA5A826395121157ull;
+constexpr uint64_t kWeyl0 = 0x9E3779B97F4A7C15ull, kWeyl1 = 0xBB67AE8584CAA73Bull;
+constexpr int kMaxSegments = 128;                   // the segments one launch holds
+constexpr uint64_t kMaxDraws = 1ull << 60;          // per segment, and offset + n: their byte counts stay inside 64 bits
+
+FLASHE_HD void mulhilo(uint64_t a, uint64_t b, uint64_t &hi, uint64_t &lo)
+{
+    const unsigned __int128 p = static_cast<unsigned __int128>(a) * b;
+    hi = static_cast<uint64_t>(p >> 64);
+    lo = static_cast<uint64_t>(p);
+}
+
+FLASHE_HD void block(const uint64_t counter[4], const uint64_t key[2], uint64_t word[4])
+{
+    uint64_t c0 = counter[0], c1 = counter[1], c2 = counter[2], c3 = counter[3], k0 = key[0], k1 = key[1];
+FLASHE_UNROLL
+    for (int r = 0; r < 10; r++) {
+        if (r) { k0 += kWeyl0; k1 += kWeyl1; }
+        uint64_t hi0, lo0, hi1, lo1;
+        mulhilo(kM0, c0, hi0, lo0);
+        mulhilo(kM1, c2, hi1, lo1);
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+    }
+    word[0] = c0; word[1] = c1; word[2] = c2; word[3] = c3;
+}
+
+// out = counter + add mod 2^256
+FLASHE_HD void counter_add(const uint64_t counter[4], uint64_t add, uint64_t out[4])
+{
+    uint64_t carry = add;
+FLASHE_UNROLL
+    for (int w = 0; w < 4; w++) {
+        const uint64_t s = counter[w] + carry;
+        carry = s < carry ? 1 : 0;
+        out[w] = s;
+    }
+}
+
+FLASHE_HD double to_double(uint64_t word) { return static_cast<double>(word >> 11) * (1.0 / 9007199254740992.0); }
+
+// Where the draws of a state (counter, buffer_pos <= 4) start: base[4] and skip (see the head of this file).
+FLASHE_HD void stream_start(const uint64_t counter[4], uint32_t buffer_pos, uint64_t base[4], uint32_t &skip)
+{
+    counter_add(counter, buffer_pos < 4 ? 0 : 1, base);
+    skip = buffer_pos < 4 ? buffer_pos : 0;
+}
+
+// Position arithmetic: draw i of the state is word `word` of block(at).
+FLASHE_HD void position(const uint64_t counter[4], uint32_t buffer_pos, uint64_t i, uint64_t at[4], uint32_t &word)
+{
+    uint64_t base[4];
+    uint32_t skip;
+    stream_start(counter, buffer_pos, base, skip);
+    const uint64_t v = skip + i;
+    counter_add(base, v >> 2, at);
+    word = static_cast<uint32_t>(v & 3);
+}
+
+// The state after n draws, in place: counter, buffer_pos and the buffered words (recomputed from the counter).  n = 0 changes nothing
+// -- a fresh generator's buffer is zeros, not a block, and stays so.
+inline void advance(const uint64_t key[2], uint64_t counter[4], uint32_t &buffer_pos, uint64_t buffer[4], uint64_t n)
+{
+    if (n == 0) return;
+    uint64_t at[4];
+    uint32_t word;
+    position(counter, buffer_pos, n - 1, at, word);
+    for (int w = 0; w < 4; w++) counter[w] = at[w];
+    buffer_pos = word + 1;
+    block(counter, key, buffer);
+}
+
+// One output segment of a launch: n draws of the state to draws [offset, offset + n) of the output buffer.
+struct Segment { uint64_t key[2]; uint64_t counter[4]; uint32_t buffer_pos; uint64_t n, offset; };
+
+enum SegmentsStatus { kSegmentsOk = 0, kSegmentsBadCount = 1, kSegmentsBadPos = 2, kSegmentsOverflow = 3, kSegmentsOverlap = 4 };
+
+// kSegmentsBadCount: n_segments < 0 or more than max_segments (or a null table with segments); kSegmentsBadPos: a buffer_pos above 4;
+// kSegmentsOverflow: an n, an offset or offset + n above kMaxDraws; kSegmentsOverlap: two non-empty output ranges share a draw.
+inline SegmentsStatus check_segments(const Segment *segs, int n_segments, int max_segments = kMaxSegments)
+{
+    if (n_segments < 0 || n_segments > max_segments || (n_segments && !segs)) return kSegmentsBadCount;
+    std::vector<std::pair<uint64_t, uint64_t>> ranges;
+    for (int s = 0; s < n_segments; s++) {
+        if (segs[s].buffer_pos > 4) return kSegmentsBadPos;
+        if (segs[s].n > kMaxDraws || segs[s].offset > kMaxDraws || segs[s].offset + segs[s].n > kMaxDraws) return kSegmentsOverflow;
+        if (segs[s].n) ranges.emplace_back(segs[s].offset, segs[s].offset + segs[s].n);
+    }
+    std::sort(ranges.begin(), ranges.end());
+    for (size_t r = 1; r < ranges.size(); r++)
+        if (ranges[r].first < ranges[r - 1].second) return kSegmentsOverlap;
+    return kSegmentsOk;
+}
+
+// The launch's view of a segment: whole blocks j = 0 .. blocks - 1 of block(base + j); block j holds the virtual draws 4 j .. 4 j + 3, of
+// which [skip, skip + n) exist and go to out draw  offset + v - skip.  Tiles of kTileBlocks blocks belong to one segment: tile_first is the
+// segment's first tile in the launch.
+constexpr uint32_t kTileBlocks = 256;
+struct Plan { uint64_t key[2]; uint64_t base[4]; uint64_t n, offset, tile_first; uint32_t skip, reserved; };
+
+inline uint64_t segment_blocks(uint32_t skip, uint64_t n) { return (skip + n + 3) / 4; }
+
+// The plans of the non-empty segments (checked already); returns the launch's tiles.
+inline uint64_t plan_segments(const Segment *segs, int n_segments, std::vector<Plan> &plans)
+{
+    plans.clear();
+    uint64_t tiles = 0;
+    for (int s = 0; s < n_segments; s++) {
+        if (!segs[s].n) continue;
+        Plan p{};
+        p.key[0] = segs[s].key[0]; p.key[1] = segs[s].key[1];
+        stream_start(segs[s].counter, segs[s].buffer_pos, p.base, p.skip);
+        p.n = segs[s].n; p.offset = segs[s].offset; p.tile_first = tiles;
+        tiles += (segment_blocks(p.skip, p.n) + kTileBlocks - 1) / kTileBlocks;
+        plans.push_back(p);
+    }
+    return tiles;
+}
+
+}  // namespace flashe_philox

@@ -1321,6 +1321,76 @@ class Engine:
         np.random.set_state((st[0], key, int(pos.value), st[3], st[4]))
         return out
 
+    PHILOX_MAX_SEGMENTS = 128        # the segments one flashe_philox_random_dev launch holds
+
+    @staticmethod
+    def _philox_segment(state, n, offset):
+        """A Philox bit generator's state dict as the flashe_philox_segment that draws n values to draw `offset` of the output."""
+        if state.get("bit_generator") != "Philox":
+            raise FlasheError(-22, f"the bit generator is {state.get('bit_generator')}, not Philox")
+        seg = _lib.PhiloxSegment()
+        seg.key[:] = [int(v) for v in state["state"]["key"]]
+        seg.counter[:] = [int(v) for v in state["state"]["counter"]]
+        seg.buffer[:] = [int(v) for v in state["buffer"]]
+        seg.buffer_pos, seg.n, seg.offset = int(state["buffer_pos"]), int(n), int(offset)
+        return seg
+
+    @staticmethod
+    def _philox_state(state, seg):
+        """The state dict with the segment's counter, buffer_pos and buffer (has_uint32 and uinteger stay as they are)."""
+        state["state"]["counter"] = np.array(list(seg.counter), dtype=np.uint64)
+        state["buffer"] = np.array(list(seg.buffer), dtype=np.uint64)
+        state["buffer_pos"] = int(seg.buffer_pos)
+        return state
+
+    def philox_random_dev(self, generators_or_states, counts, out=None, offsets=None):
+        """Generator(np.random.Philox(...)).random(n) generated on the device, bit for bit, for every entry of `generators_or_states` in ONE
+        asynchronous launch: entry s gives counts[s] draws to draws [offsets[s], offsets[s] + counts[s]) of `out` (a DeviceBuffer or a
+        device address of float64, 8-byte aligned; default: the entries back to back in a new buffer).  An entry is a np.random.Generator
+        over Philox -- its bit_generator.state is read and the advanced state put back, so host draws before and after continue one
+        stream -- or such a state dict, advanced in place.  The same Generator may appear several times: its segments continue one
+        another in list order, as sequential host draws would.  Returns the buffer.  Raises for another bit generator, overlapping ranges
+        or more than PHILOX_MAX_SEGMENTS entries; nothing is advanced then."""
+        counts = [int(c) for c in counts]
+        if len(counts) != len(generators_or_states):
+            raise ValueError(f"{len(generators_or_states)} generators, {len(counts)} counts")
+        if offsets is None:
+            offsets = [sum(counts[:s]) for s in range(len(counts))]
+        if len(offsets) != len(counts):
+            raise ValueError(f"{len(counts)} counts, {len(offsets)} offsets")
+        if len(counts) > self.PHILOX_MAX_SEGMENTS:
+            raise ValueError(f"{len(counts)} segments: one launch holds {self.PHILOX_MAX_SEGMENTS}")
+        segs = (_lib.PhiloxSegment * max(len(counts), 1))()
+        last = {}                         # id(entry) -> its latest segment: where a repeated entry continues, and what is handed back
+        states = {}
+        for s, (g, n, off) in enumerate(zip(generators_or_states, counts, offsets)):
+            if id(g) in last:
+                prev = last[id(g)]
+                seg = _lib.PhiloxSegment.from_buffer_copy(prev)
+                pos = c_u32(seg.buffer_pos)
+                self._check(self._lib.flashe_philox_advance(seg.key, seg.counter, ctypes.byref(pos), seg.buffer, prev.n))
+                seg.buffer_pos, seg.n, seg.offset = pos.value, n, int(off)
+            else:
+                states[id(g)] = (g, g.bit_generator.state if isinstance(g, np.random.Generator) else g)
+                seg = self._philox_segment(states[id(g)][1], n, off)
+            segs[s] = seg
+            last[id(g)] = segs[s]
+        if out is None:
+            out = self.alloc(max(8 * max([o + n for o, n in zip(offsets, counts)], default=0), 16))
+        self._check(self._lib.flashe_philox_random_dev(self._h, segs, len(counts), self._ptr(out)))
+        for key, (g, state) in states.items():
+            self._philox_state(state, last[key])
+            if isinstance(g, np.random.Generator):
+                g.bit_generator.state = state
+        return out
+
+    def philox_grid(self, n, buffer_pos=4):
+        """(workgroups, tiles) of the launch philox_random_dev makes for one segment of n draws: more tiles than workgroups are further
+        trips of a workgroup's loop."""
+        wg, tiles = c_u32(0), c_u64(0)
+        self._check(self._lib.flashe_philox_grid(self._h, int(n), int(buffer_pos), ctypes.byref(wg), ctypes.byref(tiles)))
+        return int(wg.value), int(tiles.value)
+
     def quantize_encrypt_dev(self, it, idx, scheme, n, n_jobs, x, x_is_f64, alpha, element_bits, u, ct):
         """ct = encrypt(quantize(x)) in one launch (un-batched values); x float32 / float64, u float64 uniforms, all device-resident."""
         self._check(self._lib.flashe_quantize_encrypt_dev(self._h, it, idx, scheme, n, n_jobs, self._ptr(x), 1 if x_is_f64 else 0,

@@ -10,7 +10,12 @@ integers are bit-identical: small layers draw on the host and ship the numbers, 
 DEVICE_RNG_MIN elements generate them ON THE DEVICE from NumPy's own MT19937 state
 (`flashe_mt19937_random_dev`: the state is read, advanced on the device exactly as NumPy would advance
 it, and put back -- host draws before and after continue one stream; FLASHE_DEVICE_RNG=0 turns it
-off).  Pass ``uniforms=`` to supply the draws yourself.
+off).  Pass ``uniforms=`` to supply the draws yourself, or ``rng=`` (a ``np.random.Generator``) to take them from a
+generator of your own: the result is that of the same call with every ``np.random.random(k)`` replaced by
+``rng.random(k)``, and NumPy's global stream is neither read nor advanced.  A Generator over ``np.random.Philox``
+generates DEVICE_RNG_MIN draws or more on the device (`flashe_philox_random_dev`: counter based, any number of
+streams in one launch, no synchronisation; the advanced state is handed back to the generator); any other
+generator, or a shorter stretch, draws ``rng.random(k)`` on the host and ships the numbers -- the same bits.
 """
 import os
 
@@ -34,13 +39,49 @@ def _as_object(arr):
     return np.asarray(arr, dtype=np.uint64).astype(object)
 
 
-def _static_quantize_padding_asymmetric(value, alpha, int_bits, uniforms=None, device=0, as_object=True):
-    """jzf_quantize.py:55-67."""
+def _check_rng(rng, n_clients=None):
+    """rng= as the callers take it: None, one np.random.Generator or -- n_clients given: the cohorts -- a list of one Generator per client.
+    TypeError for anything else, ValueError for a list of another length; nothing is drawn."""
+    if rng is None or isinstance(rng, np.random.Generator):
+        return rng
+    if n_clients is not None and isinstance(rng, (list, tuple)):
+        if len(rng) != n_clients:
+            raise ValueError(f"rng: one Generator per client ({n_clients}), got {len(rng)}")
+        for g in rng:
+            if not isinstance(g, np.random.Generator):
+                raise TypeError(f"rng: a list of np.random.Generator, got a {type(g).__name__}")
+        return list(rng)
+    raise TypeError(f"rng: a np.random.Generator{' or a list of them' if n_clients is not None else ''}, got a {type(rng).__name__}")
+
+
+def _rng_on_device(eng, rng, count):
+    """Does a stretch of `count` draws of the Generator rng run on the device?  FLASHE_DEVICE_RNG not 0, DEVICE_RNG_MIN draws or more, and
+    its bit generator is Philox (the counter-based stream flashe_philox_random_dev reproduces)."""
+    return (os.environ.get("FLASHE_DEVICE_RNG", "1") != "0" and count >= DEVICE_RNG_MIN and isinstance(rng.bit_generator, np.random.Philox)
+            and hasattr(eng, "philox_random_dev"))
+
+
+def _static_quantize_padding_asymmetric(value, alpha, int_bits, uniforms=None, device=0, as_object=True, rng=None):
+    """jzf_quantize.py:55-67.  rng (new): a np.random.Generator the draws come from in place of np.random.random."""
+    if rng is not None and uniforms is not None:
+        raise ValueError("rng and uniforms: one source of draws at a time")
+    rng = _check_rng(rng)
     value = np.asarray(value)
     shape = value.shape
     eng = _engine(64, device)
     n = int(value.size)
-    if (uniforms is None and n >= DEVICE_RNG_MIN and os.environ.get("FLASHE_DEVICE_RNG", "1") != "0"
+    if rng is not None:
+        if _rng_on_device(eng, rng, n):
+            x = np.ascontiguousarray(value).reshape(-1)
+            if x.dtype not in (np.float32, np.float64):
+                x = x.astype(np.float64)
+            dx, dq = eng.upload(x), eng.alloc(8 * n)
+            du = eng.philox_random_dev([rng], [n])
+            eng.quantize_dev(n, dx, x.dtype == np.float64, alpha, int_bits, du, dq)
+            q = dq.download(np.uint64, n).reshape(shape)
+        else:
+            q = eng.quantize(value.reshape(-1), alpha, int_bits, rng.random(shape).reshape(-1)).reshape(shape)
+    elif (uniforms is None and n >= DEVICE_RNG_MIN and os.environ.get("FLASHE_DEVICE_RNG", "1") != "0"
             and hasattr(eng, "numpy_random_dev") and np.random.get_state()[0] == "MT19937"):
         # np.random.random(shape) generated where it is consumed: no host loop over n draws, no 8 B / element upload
         x = np.ascontiguousarray(value).reshape(-1)
@@ -173,7 +214,8 @@ class QuantizingClient(object):
 
     send_layer_size_list = set_layer_size_list
 
-    def quantize(self, weights):                                     # :394-491
+    def quantize(self, weights, rng=None):                           # :394-491 (rng, new: the Generator the draws come from)
+        rng = _check_rng(rng)
         aciq = ACIQ(self.element_bits)
         alpha_list = []
         for i, _size in enumerate(self.layer_size_list):
@@ -201,7 +243,7 @@ class QuantizingClient(object):
             want = _loop_dtype(flat.dtype, alpha)                    # the dtype `np.clip(value, -alpha, alpha) + alpha` runs in
             if flat.dtype != want:
                 flat = flat.astype(want)                             # exact (float32 -> float64)
-            elements = _static_quantize_padding_asymmetric(flat, float(alpha), self.element_bits, device=self._device, as_object=False)
+            elements = _static_quantize_padding_asymmetric(flat, float(alpha), self.element_bits, device=self._device, as_object=False, rng=rng)
             if self.batch:
                 weights._weights[k] = _static_batching_padding_asymmetric(elements, self.int_bits, self.element_bits, factor, device=self._device)
             else:

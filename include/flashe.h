@@ -835,6 +835,37 @@ int flashe_mt19937_jump_selfcheck(void);
  * pass is cut into, the number the jump tables can start (a pass must never exceed it), and the number of passes. */
 int flashe_mt19937_plan(uint32_t pos, uint64_t n, uint32_t *max_substreams, uint32_t *substreams_available, uint32_t *passes);
 
+/* Generator(np.random.Philox(...)).random(n) ON THE DEVICE, bit for bit (new): the stochastic-rounding draws of a caller's OWN generator
+ * (rng=).  Philox4x64-10 is counter based -- block(counter[4], key[2]) -> four 64-bit words, ten rounds with the multipliers
+ * 0xD2E7470EE14C6C93 / 0xCA5A826395121157 and the key bumped by 0x9E3779B97F4A7C15 / 0xBB67AE8584CAA73B before rounds 2 .. 10 -- and NumPy
+ * increments the 256-bit counter (four little-endian words, wrapping at 2^256) BEFORE it generates a block: a state (counter,
+ * buffer_pos = p) next returns words p .. 3 of block(counter), then all of block(counter + 1), ...; p = 4 (a fresh or exhausted buffer)
+ * starts at block(counter + 1); draw = (word >> 11) * 2^-53.  A segment is one generator state (key, counter, buffer_pos exactly as
+ * Generator.bit_generator.state holds them; the buffered words are recomputed from the counter, `buffer` is only written) and the n draws it
+ * gives to draws [offset, offset + n) of u_dev, which need only be 8-byte aligned; bytes outside the ranges are not written.  ONE launch on
+ * the ctx stream fills up to 128 segments (the clients of a cohort) and does not synchronise; every segment's state is advanced in place
+ * on the host (counter, buffer_pos, buffer: what NumPy's own state is after n draws; n = 0 leaves it untouched), so the caller can put it
+ * back into bit_generator.state and host draws continue the stream.  FLASHE_EINVAL: a buffer_pos above 4, more than 128 segments, an n or
+ * offset + n above 2^60, overlapping output ranges, a misaligned u_dev, a graph being captured. */
+typedef struct flashe_philox_segment {
+    uint64_t key[2];
+    uint64_t counter[4];
+    uint64_t buffer[4];      /* out: the buffered words of the advanced state */
+    uint32_t buffer_pos;     /* 0 .. 4 */
+    uint32_t reserved;
+    uint64_t n;              /* draws */
+    uint64_t offset;         /* in draws into u_dev */
+} flashe_philox_segment;
+int flashe_philox_random_dev(flashe_ctx *ctx, flashe_philox_segment *segments, int n_segments, double *u_dev);
+/* Host only (new): one Philox4x64-10 block as NumPy computes it -- words[4] = block(counter[4], key[2]). */
+int flashe_philox_block(const uint64_t counter[4], const uint64_t key[2], uint64_t words[4]);
+/* Host only (new): the state NumPy's Philox bit generator is in after Generator.random(n) from (counter, buffer_pos), in place: counter,
+ * buffer_pos (1 .. 4) and the buffered words; n = 0 changes nothing. */
+int flashe_philox_advance(const uint64_t key[2], uint64_t counter[4], uint32_t *buffer_pos, uint64_t buffer[4], uint64_t n);
+/* Host only (new): the grid flashe_philox_random_dev launches for one segment of n draws from a state with that buffer_pos -- its tiles of
+ * 256 blocks (1,024 draws) and its workgroups (at most 8 per compute unit the ctx may use; more tiles than that are further trips). */
+int flashe_philox_grid(flashe_ctx *ctx, uint64_t n, uint32_t buffer_pos, uint32_t *workgroups, uint64_t *tiles);
+
 /* _static_quantize_padding_asymmetric -- federatedml/secureprotol/jzf_quantize.py:55-67:
  * q = floor(clip(x, -alpha, alpha) + alpha) * (2^element_bits - 1) / (2 alpha) + u), with numpy's
  * dtype rules (x_is_f64 == 0: x is float32 and every step before "+ u" is a float32 operation).
