@@ -5,7 +5,10 @@ The model's parameters go into FlasheClient.quantize_encrypt as they are (float3
 DLPack), and decrypt_unquantize writes the new global model straight back into them.  The client runs on torch's current stream, so the
 library's kernels are ordered with the framework's own work and nothing needs an explicit synchronisation.  A single client decrypts
 its own upload here; in a job the aggregate of all clients comes back from the arbiter.  flashe_amd itself never imports torch.
-`--precompute` runs the precompute job: the masks are prepared while the client waits, the step adds them without AES."""
+`--precompute` runs the precompute job: the masks are prepared while the client waits, the step adds them without AES.
+`--degree D --total-degree T` weights the model by the client's sample count as the aggregator does (jzf_aggregator.py:676, :902-907):
+the multiply rides the stage pass, the two divisions and the add of the last round's model ride the store pass, the parameters are
+updated in place; every round is checked against the same sequence written out with NumPy on host copies."""
 import os
 import sys
 
@@ -25,8 +28,29 @@ class Weights:
         self._weights = dict(layers)
 
 
+def _option(name):
+    """The float behind `name` on the command line, None without it."""
+    return float(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else None
+
+
+def _host_round(client, host, it, degree, total, seed):
+    """The reference's sequence on host copies: weights *= degree, the step, / (total / degree), unnormalize, / degree, + last round."""
+    client.set_iter_index(it)
+    np.random.seed(seed)
+    upload = client.quantize_encrypt(Weights({k: v * degree for k, v in host.items()}), device=True, normalize=True)
+    client.set_idx_list([0])
+    w = client.decrypt_unquantize(upload)
+    for k in w.walking_order:
+        w._weights[k] = w._weights[k] / (total / degree)
+    w = client.unnormalize(w)
+    return {k: (host[k] + w._weights[k] / degree).astype(np.float32) for k in w.walking_order}
+
+
 def main():
     cm.N_JOBS = 16                                           # every party must use the same value
+    degree, total = _option("--degree"), _option("--total-degree")
+    if (degree is None) != (total is None):
+        sys.exit("--degree and --total-degree come together")
     model = torch.nn.Sequential(torch.nn.Conv2d(3, 16, 5), torch.nn.ReLU(), torch.nn.Flatten(), torch.nn.Linear(16 * 28 * 28, 10)).cuda()
     params = {name: p for name, p in model.named_parameters()}
     # --precompute: the paper's own configuration -- the masks of the next round are computed while the client waits for the aggregate
@@ -37,9 +61,25 @@ def main():
             "precompute": {"enable": precompute, "num_params": num_params}}
     client = FlasheClient(args, stream=torch.cuda.current_stream().cuda_stream)
     client.create_cipher(0, 1, bytes(range(32)))             # (with precompute: also the masks of round 0)
+    if degree is not None:
+        twin = FlasheClient(dict(args, precompute={"enable": False}))        # the written-out sequence runs beside the fused step
+        twin.create_cipher(0, 1, bytes(range(32)))
     for it in range(3):
         client.set_iter_index(it)
         with torch.no_grad():                                # (a tensor that requires grad cannot be exported)
+            if degree is not None:
+                want = _host_round(twin, {k: p.detach().cpu().numpy() for k, p in params.items()}, it, degree, total, seed=it)
+                np.random.seed(it)
+                out = {k: p.detach() for k, p in params.items()}
+                upload = client.quantize_encrypt(Weights(dict(out)), device=True, normalize=True, degree=degree)
+                client.prepare_encrypt()
+                client.prepare_decrypt()
+                client.set_idx_list([0])
+                client.decrypt_unquantize(upload, out=out, unnormalize=True, total_degree=total, last_round=out)     # in place
+                same = all(p.detach().cpu().numpy().tobytes() == want[k].tobytes() for k, p in params.items())
+                same = same and [float(m).hex() for m in client.quantizer.past_layer_mean_list] == [float(m).hex() for m in twin.quantizer.past_layer_mean_list]
+                print(f"round {it}: degree {degree:g} of {total:g}, equal to the written-out host sequence: {same}")
+                continue
             upload = client.quantize_encrypt(Weights({k: p.detach() for k, p in params.items()}), device=True, normalize=True)
             client.prepare_encrypt()                         # no-ops without precompute: the next round's masks, then this one's
             client.prepare_decrypt()                         # decrypt masks, while the arbiter aggregates

@@ -58,8 +58,23 @@ class PhiloxSegment(ctypes.Structure):
                 ("reserved", ctypes.c_uint32), ("n", ctypes.c_uint64), ("offset", ctypes.c_uint64)]
 
 
+class StageRow(ctypes.Structure):
+    """flashe_stage_row of include/flashe.h."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("size", ctypes.c_uint64), ("scale", ctypes.c_double),
+                ("shift", ctypes.c_double), ("src_dtype", ctypes.c_int32), ("flags", ctypes.c_int32)]
+
+
+class FinishRow(ctypes.Structure):
+    """flashe_finish_row of include/flashe.h."""
+    _fields_ = [("start", ctypes.c_uint64), ("dst", ctypes.c_void_p), ("last", ctypes.c_void_p), ("div_total", ctypes.c_double),
+                ("shift", ctypes.c_double), ("div_own", ctypes.c_double), ("dst_dtype", ctypes.c_int32), ("last_dtype", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 TENSOR_F32, TENSOR_F64, TENSOR_F16, TENSOR_BF16 = 0, 1, 2, 3
 TENSOR_SHIFT, TENSOR_SHIFT_WIDE, TENSOR_LOOP_F64 = 1, 2, 4
+STAGE_SCALE, STAGE_SCALE_WIDE, STAGE_SHIFT, STAGE_SHIFT_WIDE, STAGE_OUT_F64 = 1, 2, 4, 8, 16
+FINISH_DIV_TOTAL, FINISH_SHIFT, FINISH_DIV_OWN, FINISH_ADD_LAST = 1, 2, 4, 8
 
 
 class FlasheError(RuntimeError):
@@ -199,6 +214,8 @@ _SIGNATURES = {
                                                     c_vp, c_vp]),
     "flashe_quantize_batch_tensors_dev": (c_int, [c_vp, ctypes.POINTER(TensorLayer), c_int, c_u64, c_int, c_int, c_vp, c_u64, c_vp]),
     "flashe_store_layers_dev": (c_int, [c_vp, c_vp, c_u64, ctypes.POINTER(TensorLayer), c_int, c_u64, c_vp]),
+    "flashe_stage_layers_dev": (c_int, [c_vp, ctypes.POINTER(StageRow), c_int]),
+    "flashe_finish_layers_dev": (c_int, [c_vp, c_vp, c_u64, ctypes.POINTER(FinishRow), c_int, c_u64, c_vp]),
     "flashe_quantize_encrypt_prepared_model_dev": (c_int, [c_vp, c_u64, c_u64, c_u64, ctypes.POINTER(CodecLayer), c_int, c_int, c_vp, c_vp]),
     "flashe_quantize_encrypt_prepared_tensors_dev": (c_int, [c_vp, c_u64, c_u64, c_u64, ctypes.POINTER(TensorLayer), c_int, c_int, c_vp, c_vp]),
     "flashe_quantize_batch_encrypt_prepared_model_dev": (c_int, [c_vp, ctypes.POINTER(BatchLayer), c_int, c_int, c_int, c_vp, c_u64, c_vp]),

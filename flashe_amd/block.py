@@ -4,7 +4,10 @@ the arbiter's `dynamic_masking` cost model (:89-117).  Key exchange, uuid sync a
 transfer variables of the reference classes are control plane and are not reproduced; the PRP seed
 is handed in directly.
 """
+import functools
 import math
+import numbers
+import operator
 import os
 
 import numpy as np
@@ -174,6 +177,63 @@ def _tensor_flags(hdt, alpha, normalize, mean):
     return float(shift), flags
 
 
+def _check_degree(v, what):
+    """The aggregator's degree / the arbiter's sum of degrees (jzf_aggregator.py:676, :380): None, or a positive finite real number --
+    anything else is a ValueError (the reference's `if degree:` takes 0 for "no degree" and then divides by it, :902)."""
+    if v is None:
+        return None
+    ok = isinstance(v, (numbers.Real, np.floating, np.integer)) and not isinstance(v, (bool, np.bool_))
+    try:
+        f = float(v) if ok else 0.0
+    except OverflowError:
+        f = math.inf
+    if not ok or not math.isfinite(f) or not f > 0:
+        raise ValueError(f"{what} must be a positive finite real number (None: no scaling), got {v!r}")
+    return v
+
+
+def _layers_of(w):
+    """The {name: layer} dict of a Weights-like object or of a plain dict."""
+    return w._weights if hasattr(w, "_weights") else w
+
+
+def _stage_scaled(eng, items):
+    """`weights *= degree` (jzf_aggregator.py:676) and normalize (jzf_quantize.py:542-547) of device-resident layers in ONE streaming
+    pass (flashe_stage_layers_dev).  items: (pointer, storage dtype code, NumPy dtype of the host copy, size, degree or None, alpha,
+    mean or None) per layer -- one model's, or every client's of a cohort.  Every step takes the dtype the running NumPy gives
+    `array <op> scalar` there: the multiply makes a new array (a float32 layer becomes float64 under an np.float64 degree), the shift is
+    in place, and the result is stored in the dtype the clip / scale arithmetic with alpha runs in.  Returns ([(pointer, F32 / F64 code)]
+    -- a layer that needs nothing is read where it lies --, the scratch buffer or None)."""
+    plans, nbytes = [], 0
+    for ptr, code, hdt, size, degree, alpha, mean in items:
+        cur, flags, scale, shift = np.dtype(hdt), 0, 1.0, 0.0
+        if degree is not None:
+            nxt = _loop_dtype(cur, degree)
+            if nxt not in (_F32, _F64):
+                raise TypeError(f"degree {degree!r} makes a {cur} layer {nxt}: float32 and float64 are what the kernels compute in")
+            flags |= _lib.STAGE_SCALE | (_lib.STAGE_SCALE_WIDE if cur == _F32 and nxt == _F64 else 0)
+            cur, scale = nxt, float(degree)
+        if mean is not None:
+            shift = -mean
+            flags |= _lib.STAGE_SHIFT | (_lib.STAGE_SHIFT_WIDE if cur == _F32 and _loop_dtype(cur, shift) == _F64 else 0)
+        out64 = cur == _F64 or _loop_dtype(cur, alpha) == _F64
+        direct = not flags and code == (_lib.TENSOR_F64 if out64 else _lib.TENSOR_F32)
+        if out64:
+            flags |= _lib.STAGE_OUT_F64
+        at = None
+        if not direct:
+            at = nbytes
+            nbytes += (size * (8 if out64 else 4) + 15) & ~15
+        plans.append((ptr, code, size, scale, float(shift), flags, out64, at))
+    if all(p[7] is None for p in plans):
+        return [(p[0], p[1]) for p in plans], None
+    buf = eng.alloc(max(nbytes, 16))
+    eng.stage_layers_dev([(ptr, buf.ptr + at, size, scale, shift, code, flags) for ptr, code, size, scale, shift, flags, _o, at in plans
+                          if at is not None])
+    return [(ptr, code) if at is None else (buf.ptr + at, _lib.TENSOR_F64 if out64 else _lib.TENSOR_F32)
+            for ptr, code, _size, _sc, _sh, _fl, out64, at in plans], buf
+
+
 def _size(shape):
     """The number of values of a layer of that shape, as a Python int (it reaches ctypes)."""
     return int(math.prod(shape))
@@ -271,6 +331,7 @@ class FlasheClient(object):
         self.quantizer = None
         self.shape_dict = None           # layer shapes of the flattened model (what the aggregator-side Client keeps, jzf_aggregator.py:648)
         self.fuse = True                 # False: quantize_encrypt / decrypt_unquantize run the reference's sequence call by call
+        self.degree = None               # the degree the last quantize_encrypt took (jzf_aggregator.py:676): decrypt_unquantize's default
         self._device = device
         self._stream = stream
 
@@ -423,8 +484,15 @@ class FlasheClient(object):
         _skip_draws(n_values, rng)
         c._check_prepared_len(cache, n_ct)
 
-    def quantize_encrypt(self, weights, device=True, normalize=False, rng=None):
-        """rng (new): a np.random.Generator the stochastic-rounding draws come from -- the result is that of the same call with every
+    def quantize_encrypt(self, weights, device=True, normalize=False, rng=None, degree=None):
+        """degree (new): `weights *= degree` first (jzf_aggregator.py:676, the client's sample count times aggregate_every_n_epoch): every
+        layer but the sparse job's 'zzz' becomes a NEW array `layer * degree` in the dtype NumPy gives that product (a float32 layer stays
+        float32 under a Python number and becomes float64 under an np.float64), the caller's arrays and tensors are never written; host
+        layers are multiplied on the host, framework tensors in the stage pass that normalisation pays anyway
+        (flashe_stage_layers_dev).  None: no scaling; zero, negative, non-finite or not a real number: ValueError before anything is
+        touched.  The client remembers it for decrypt_unquantize.
+
+        rng (new): a np.random.Generator the stochastic-rounding draws come from -- the result is that of the same call with every
         np.random.random(k) replaced by rng.random(k), the sparse job's 'zzz' draw included (the next draw of the same generator); NumPy's
         global stream is neither read nor advanced.  Over np.random.Philox, stretches of DEVICE_RNG_MIN draws or more are generated on
         the device (flashe_philox_random_dev) and the advanced state is put back into the generator; any other generator draws on the
@@ -456,8 +524,13 @@ class FlasheClient(object):
         take the same sequence call by call on the host and return object arrays like the reference."""
         q = self.quantizer
         rng = _check_rng(rng)
+        self.degree = _check_degree(degree, "degree")
         if any(interop.is_foreign(weights._weights[k]) for k in weights.walking_order):
-            return self._quantize_encrypt_tensors(weights, device, normalize, rng)
+            return self._quantize_encrypt_tensors(weights, device, normalize, rng, degree)
+        if degree is not None:
+            for k in weights.walking_order:
+                if k != "zzz":                                               # (the sparsifier creates it after :676)
+                    weights._weights[k] = np.asarray(weights._weights[k]) * degree
         if normalize:
             self.normalize(weights)
         if q.layer_size_list is None:
@@ -588,8 +661,54 @@ class FlasheClient(object):
         weights.walking_order = sorted(weights._weights.keys(), key=str)
         return weights
 
-    def decrypt_unquantize(self, weights, out=None, unnormalize=False):
-        """out (new): {layer name: framework float device tensor (float64 / float32 / float16 / bfloat16) of the layer's shape} -- the
+    def _back_degrees(self, degree, total_degree):
+        """decrypt_unquantize's (degree, total_degree) after their checks, before anything is touched: both None = no scaling; degree
+        defaults to the one the last quantize_encrypt took; ValueError for a value _check_degree refuses, a total_degree without any
+        degree, a degree given without a total_degree."""
+        _check_degree(degree, "degree")
+        _check_degree(total_degree, "total_degree")
+        if total_degree is None:
+            if degree is not None:
+                raise ValueError("degree without total_degree: the back end divides by total_degree / degree first (jzf_aggregator.py:902)")
+            return None, None
+        if degree is None:
+            degree = self.degree
+        if degree is None:
+            raise ValueError("total_degree without a degree: pass degree= (no quantize_encrypt of this client took one)")
+        return degree, total_degree
+
+    def _host_tail(self, weights, unnormalize, degree, total_degree, last):
+        """Client.get_aggregated_model behind the unquantise (jzf_aggregator.py:902-907) with the reference's NumPy operations on host
+        layers: `/= (degrees / self.degree)`, unnormalize (which records np.mean / np.std of the divided values), `/= self.degree`,
+        `+ weights_last_round` -- each only when asked (the reference's dense job would raise at :907 with its weights_last_round None)."""
+        w = weights._weights
+        if total_degree is not None:
+            s = total_degree / degree
+            for k in weights.walking_order:
+                w[k] = w[k] / s
+        if unnormalize:
+            weights = self.unnormalize(weights)
+            w = weights._weights
+        if total_degree is not None:
+            for k in weights.walking_order:
+                w[k] = w[k] / degree
+        if last is not None:
+            for k in weights.walking_order:
+                w[k] = np.asarray(last[k]) + w[k]
+        return weights
+
+    def decrypt_unquantize(self, weights, out=None, unnormalize=False, degree=None, total_degree=None, last_round=None):
+        """degree, total_degree, last_round (new): Client.get_aggregated_model's steps around unnormalize (jzf_aggregator.py:902-907), in
+        its order and with its operations: `/ (total_degree / degree)` (total_degree = the arbiter's sum of the clients' degrees, :380;
+        the quotient is computed once in Python), [unnormalize: `+ mean`, np.mean / np.std of THAT value recorded], `/ degree`,
+        `last_round + w` -- two correctly rounded divisions and no fused multiply-add.  degree defaults to the one the last
+        quantize_encrypt took; both None: no scaling.  last_round (None: no add): a Weights / dict of host arrays; with out=, of framework
+        device tensors of the layers' shapes (any of the four dtypes, upcast exactly), where last_round[name] may be out[name] itself --
+        the model is then updated in place.  With out= all of it is the ONE store + statistics pass (flashe_finish_layers_dev).
+        ValueError before anything is touched: a degree or total_degree that is zero, negative, non-finite or not a real number, a
+        total_degree without a degree, a degree without a total_degree.
+
+        out (new): {layer name: framework float device tensor (float64 / float32 / float16 / bfloat16) of the layer's shape} -- the
         values are written there in place (see _decrypt_unquantize_tensors) and weights._weights[name] becomes out[name].  unnormalize
         (new): QuantizingClient.unnormalize after it (jzf_quantize.py:549-564): the layer mean added back and the statistics of the next
         round's alpha refreshed -- with `out`, on the device, bit-identical to np.mean / np.std of the float64 result.
@@ -606,10 +725,17 @@ class FlasheClient(object):
         cache is consumed as the call-by-call decrypt consumes it; the encrypt cache of the next round is not touched.  Masks a caller
         assigned as plain arrays take the same sequence call by call."""
         q, c = self.quantizer, self.cipher
+        degree, total_degree = self._back_degrees(degree, total_degree)
         if out is not None:
-            return self._decrypt_unquantize_tensors(weights, out, unnormalize)
-        if unnormalize:
-            return self.unnormalize(self.decrypt_unquantize(weights))
+            return self._decrypt_unquantize_tensors(weights, out, unnormalize, degree, total_degree, last_round)
+        if unnormalize or total_degree is not None or last_round is not None:
+            last = None
+            if last_round is not None:
+                last = _layers_of(last_round)
+                bad = [k for k in (self.shape_dict or {}) if k not in last or interop.is_foreign(last[k])]
+                if bad:
+                    raise TypeError(f"last_round: without out= it holds a host array for every layer, not so for {bad}")
+            return self._host_tail(self.decrypt_unquantize(weights), unnormalize, degree, total_degree, last)
         fus = self.fuse and c.masks is None and c.prp_seed is not None and hasattr(c.engine, "decrypt_unquantize_model_dev")
         mode = None
         if fus:
@@ -751,14 +877,18 @@ class FlasheClient(object):
         return dout
 
     # ---- a framework's device tensors either side of the client step (new; interop.py) ---------------------------------------
-    def _quantize_encrypt_tensors(self, weights, device, normalize, rng=None):
+    def _quantize_encrypt_tensors(self, weights, device, normalize, rng=None, degree=None):
         """quantize_encrypt with framework device tensors among the layers: each foreign layer is read in place (its own dtype; a layer
         that needs a conversion -- 16-bit, float32 quantised in float64, or normalised -- goes through one streaming pass into engine
         scratch, flashe_quantize_encrypt_tensors_dev / flashe_quantize_batch_tensors_dev), host layers go up as in the host path.  Bit for
         bit the host path on `t.cpu().numpy()` (float16 / bfloat16: `t.float().cpu().numpy()`), with `normalize()` first when asked.
         The refusals, then the front end for tensors: 6-field rows (start, pointer, alpha, shift, dtype code, flags) for the *_tensors_dev
-        entry points, and _encrypt_tail behind them."""
+        entry points, and _encrypt_tail behind them.  degree: host layers are multiplied on the host, and ONE stage pass of the caller's
+        (_stage_scaled) multiplies and normalises the tensors into engine scratch, which the same entry points then read as plain float32 /
+        float64 layers without a shift."""
         q, c = self.quantizer, self.cipher
+        if degree is not None and not hasattr(c.engine, "stage_layers_dev"):
+            raise TypeError("degree with framework tensors needs an engine with flashe_stage_layers_dev")
         zzz = None
         if "zzz" in weights._weights:                 # the sparse job: compact layers (Sparsifier's CompactLayer or any tensors) + 'zzz'
             if not self.fuse:
@@ -783,20 +913,30 @@ class FlasheClient(object):
         order = list(weights.walking_order)
         if zzz is not None:
             order = order[:-1]
-        layers = [_layer_source(eng, weights._weights[k], f"layer {k!r}") for k in order]
+        scaled = lambda v: v if degree is None or interop.is_foreign(v) else np.asarray(v) * degree
+        layers = [_layer_source(eng, scaled(weights._weights[k]), f"layer {k!r}") for k in order]
         sizes = [size for _x, _code, _hdt, size, _shape in layers]
         alphas = _round_alphas(q, sizes + ([int(zzz.size)] if zzz is not None else []))      # (set_layer_size_list on the sizes the tensors report)
         q.r_max_list, q.alpha_list = [], []
         c.set_idx_list(mode="encrypt")
         ptrs, keep = _stage_host_layers(eng, [x for x, _code, _hdt, _size, _shape in layers])
         owners = [x.keep for x, _code, _hdt, _size, _shape in layers if not isinstance(x, np.ndarray)]
+        staged = None
+        if degree is not None:
+            staged, scratch = _stage_scaled(eng, [(ptrs[li], code, hdt, size, None if isinstance(x, np.ndarray) else degree, alphas[li],
+                                                   q.past_layer_mean_list[li] if normalize else None)
+                                                  for li, (x, code, hdt, size, _shape) in enumerate(layers)])
+            keep.append(scratch)
         rows, starts, n = [], [], 0
         for li, (_x, code, hdt, size, _shape) in enumerate(layers):
             alpha = alphas[li]
             q.r_max_list.append(alpha * q.num_clients)
             q.alpha_list.append(alpha)
-            shift, flags = _tensor_flags(hdt, alpha, normalize, q.past_layer_mean_list[li])
-            rows.append((n, ptrs[li], alpha, shift, code, flags))
+            if staged is not None:
+                rows.append((n, staged[li][0], alpha, 0.0, staged[li][1], 0))
+            else:
+                shift, flags = _tensor_flags(hdt, alpha, normalize, q.past_layer_mean_list[li])
+                rows.append((n, ptrs[li], alpha, shift, code, flags))
             starts.append(n)
             n += size
         launch = (eng.quantize_encrypt_tensors_dev, eng.quantize_encrypt_prepared_tensors_dev,                # (the batched two also take n)
@@ -806,14 +946,18 @@ class FlasheClient(object):
         return self._encrypt_tail(weights, device, mode, order, zzz, sizes, starts, shape_dict, rows, launch, keep, hold=owners, normalize=normalize,
                                   rng=rng)
 
-    def _decrypt_unquantize_tensors(self, weights, out, unnormalize):
+    def _decrypt_unquantize_tensors(self, weights, out, unnormalize, degree=None, total_degree=None, last_round=None):
         """decrypt_unquantize into the caller's tensors: the fused back end writes the flat float64 model into engine scratch, one
         streaming pass (flashe_store_layers_dev) adds the layer means back (unnormalize) and stores every layer in its tensor's dtype --
         float64 -> float32 -> 16 bits, each step round to nearest even -- and, with unnormalize, sums every layer the way np.mean /
         np.std do, so past_layer_mean_list / past_layer_std_list get the host path's np.float64 values.  Only those 16 bytes per layer come
-        back to the host.  Own-stream engines synchronise before returning."""
+        back to the host.  Own-stream engines synchronise before returning.  With total_degree / degree / last_round the pass is
+        flashe_finish_layers_dev: the two divisions and the add ride it, the statistics are those of the divided, shifted values."""
         from .cipher import _SparseMinus
         q, c = self.quantizer, self.cipher
+        scaling = total_degree is not None or last_round is not None
+        if scaling and not hasattr(c.engine, "finish_layers_dev"):
+            raise TypeError("degree / last_round with out= need an engine with flashe_finish_layers_dev")
         if "zzz" in weights._weights:
             raise TypeError("out= takes the dense aggregate, not an upload with the sparse job's 'zzz' layer")
         sparse = c.masks is not None
@@ -853,28 +997,55 @@ class FlasheClient(object):
             if tuple(fa.shape) != tuple(shape):
                 raise ValueError(f"out[{k!r}]: expected shape {tuple(shape)}, got {tuple(fa.shape)}")
             fas.append(fa)
+        lasts = None
+        if last_round is not None:
+            last, lasts = _layers_of(last_round), []
+            for k, shape, fa in zip(names, shapes, fas):
+                if k not in last or not interop.is_foreign(last[k]):
+                    raise TypeError(f"last_round[{k!r}]: with out= expected a framework device tensor")
+                la = fa if last[k] is out[k] else eng.foreign(last[k], what=f"last_round[{k!r}]")
+                if la.dtype not in _TENSOR_CODES:
+                    raise TypeError(f"last_round[{k!r}]: unsupported dtype {la.dtype} (float64, float32, float16 or bfloat16)")
+                if tuple(la.shape) != tuple(shape):
+                    raise ValueError(f"last_round[{k!r}]: expected shape {tuple(shape)}, got {tuple(la.shape)}")
+                lasts.append(la)
         k0 = weights.walking_order[0]
         v = weights._weights[k0]
-        keep = [fa.keep for fa in fas]
+        keep = [fa.keep for fa in fas] + [la.keep for la in (lasts or [])]
         sizes = [_size(shape) for shape in shapes]
+        tail = (degree, total_degree, lasts) if scaling else None
         if sparse:
             dout, _n = self._sparse_floats(v, sizes, keep)
-            return self._store_tensors(weights, out, names, fas, sizes, dout, keep, unnormalize)
+            return self._store_tensors(weights, out, names, fas, sizes, dout, keep, unnormalize, tail)
         add_idx, minus_idx = self._decrypt_prefixes(mode)
         dout = self._decrypt_floats(self._wide_aggregate(v, keep), sizes, mode, add_idx, minus_idx)
-        return self._store_tensors(weights, out, names, fas, sizes, dout, keep, unnormalize)
+        return self._store_tensors(weights, out, names, fas, sizes, dout, keep, unnormalize, tail)
 
-    def _store_tensors(self, weights, out, names, fas, sizes, dout, keep, unnormalize):
-        """The back end's flat float64 model `dout` (in HBM) into the out= tensors, with the exact statistics when unnormalising."""
+    def _store_tensors(self, weights, out, names, fas, sizes, dout, keep, unnormalize, tail=None):
+        """The back end's flat float64 model `dout` (in HBM) into the out= tensors, with the exact statistics when unnormalising.  tail =
+        (degree, total_degree, last-round ForeignArrays or None): jzf_aggregator.py:902-907 in the same pass (flashe_finish_layers_dev)."""
         q, eng = self.quantizer, self.cipher.engine
         n_values = sum(sizes)
         layers, at = [], 0
+        if tail is not None:
+            degree, total_degree, lasts = tail
+            scaled = total_degree is not None
+            s = float(total_degree / degree) if scaled else 1.0            # (:902: the quotient once, in Python)
+            flags = ((_lib.FINISH_DIV_TOTAL | _lib.FINISH_DIV_OWN) if scaled else 0) | (_lib.FINISH_SHIFT if unnormalize else 0) | \
+                    (_lib.FINISH_ADD_LAST if lasts is not None else 0)
         for li, (fa, size) in enumerate(zip(fas, sizes)):
             shift = float(q.past_layer_mean_list[li]) if unnormalize else 0.0
-            layers.append((at, fa.ptr, 1.0, shift, _TENSOR_CODES[fa.dtype], _lib.TENSOR_SHIFT if unnormalize else 0))
+            if tail is not None:
+                la = lasts[li] if lasts is not None else None
+                layers.append((at, fa.ptr, la.ptr if la is not None else None, s, shift, float(degree) if scaled else 1.0, _TENSOR_CODES[fa.dtype],
+                               _TENSOR_CODES[la.dtype] if la is not None else 0, flags))
+            else:
+                layers.append((at, fa.ptr, 1.0, shift, _TENSOR_CODES[fa.dtype], _lib.TENSOR_SHIFT if unnormalize else 0))
             at += size
         stats = eng.alloc(max(16 * len(layers), 16)) if unnormalize else None
-        if n_values:
+        if n_values and tail is not None:
+            eng.finish_layers_dev(dout, n_values, layers, block=np.getbufsize() if unnormalize else 0, stats=stats)
+        elif n_values:
             eng.store_layers_dev(dout, n_values, layers, block=np.getbufsize() if unnormalize else 0, stats=stats)
         eng.hold(keep + [dout])
         if unnormalize:
@@ -1204,7 +1375,8 @@ class FlasheCohort(object):
                 self._clients.append(cl)
         self._masks = None                             # the cohort's own encrypt-mask cache (prepare_encrypt): one vector per client
         self._last = None                              # the last upload (its sum is what decrypt_unquantize() decrypts)
-        self.prefer = None                             # "staged-chain" / "per-client": run that fallback form where the chain would be taken (A/B runs)
+        self._degrees = None                           # the present clients' degrees of the last quantize_encrypt (None: it took none)
+        self.prefer = None                            # "staged-chain" / "per-client": run that fallback form where the chain would be taken (A/B runs)
 
     quantizer = property(lambda self: self.lead.quantizer)
     cipher = property(lambda self: self.lead.cipher)
@@ -1259,8 +1431,15 @@ class FlasheCohort(object):
         """The lead client's prepare_decrypt: the decrypting party's masks do not depend on the cohort."""
         self.lead.prepare_decrypt()
 
-    def quantize_encrypt(self, weights_list, normalize=False, seeds=None, present=None, rng=None):
-        """rng (new): the stochastic-rounding draws come from the caller's own np.random.Generator(s) -- ONE Generator: the (present) clients
+    def quantize_encrypt(self, weights_list, normalize=False, seeds=None, present=None, rng=None, degrees=None):
+        """degrees (new): one degree per (present) client, FlasheClient.quantize_encrypt's `degree` of that client (jzf_aggregator.py:676);
+        another length or a value that call refuses: ValueError before anything is touched.  Host layers are multiplied on the host; the
+        tensors of ALL clients are multiplied and normalised by ONE stage pass (flashe_stage_layers_dev: a row per client and layer) and
+        the launches below read its output as plain layers.  A layer that becomes float64 for some clients only (degrees of mixed scalar
+        types) takes the staged form, as any layer that computes in float64 for some clients only does.  The cohort remembers them for
+        decrypt_unquantize.
+
+        rng (new): the stochastic-rounding draws come from the caller's own np.random.Generator(s) -- ONE Generator: the (present) clients
         draw one after the other from it, as seeds=None does with the global stream; a list of one Generator per (present) client: client c
         draws from rng[c], as seeds=[...] does.  The result is that of the same call with every np.random.random(k) replaced by the
         generator's .random(k), on every path; NumPy's global stream is neither read nor advanced.  Generators over np.random.Philox with
@@ -1283,18 +1462,20 @@ class FlasheCohort(object):
         from .engine import DeviceVector
         ld = self.lead
         q, eng = ld.quantizer, ld.cipher.engine
-        plan, layers = self._collect(weights_list, seeds, present, rng)
+        plan, layers, pre = self._collect(weights_list, seeds, present, rng, degrees)
         C = len(plan.present)
         rng = _check_rng(rng, C)
         self._refuse_prepared_len(plan, seeds, rng)
         self._last, ld._cohort_mask = None, None
+        self._degrees = None if degrees is None else list(degrees)
+        ld.degree = None if degrees is None else degrees[0]
         path = self._choose_path(plan, layers)
         if path == PER_CLIENT:
-            return self._per_client(weights_list, normalize, seeds, plan.present, rng)
+            return self._per_client(weights_list, normalize, seeds, plan.present, rng, degrees)
         if not ld._fusable():
             raise TypeError("FlasheCohort needs the fused client step (fuse=True, a keyed cipher, no location masks)")
         alphas = self._begin_round(plan)
-        tables, keep = self._tables(plan, layers, alphas, normalize)
+        tables, keep = self._tables(plan, layers, alphas, normalize, degrees if pre is not None else None, pre)
         du = _cohort_draws(eng, C, plan.n, seeds, rng)
         if self.compact:
             cts = [DeviceVector(eng, plan.n_elems, 1, elem_bytes=4) for _ in range(C)]
@@ -1305,8 +1486,9 @@ class FlasheCohort(object):
         prepared = path in (PREPARED_COHORT, PREPARED_STAGED)       # (the cohort's cache is consumed whatever form runs)
         if path in (COHORT_CHAIN, PREPARED_COHORT):
             # the shared rows name the compute type; the sources keep their own storage dtypes
-            rows = [(st, None, al, sh, _lib.TENSOR_F64 if layers[0][li][2] == np.float64 else _lib.TENSOR_F32, fl)
-                    for li, (st, _p, al, sh, _code, fl) in enumerate(tables[0])]
+            # (with degrees on tensors the tables name the stage pass's output: its code is the compute type)
+            rows = [(st, None, al, sh, code if pre is not None else _lib.TENSOR_F64 if layers[0][li][2] == np.float64 else _lib.TENSOR_F32, fl)
+                    for li, (st, _p, al, sh, code, fl) in enumerate(tables[0])]
             srcs = [[t[1] for t in table] for table in tables]
             dts = [[t[4] for t in table] for table in tables]
             launch = self._launch_prepared if prepared else self._launch_chain
@@ -1332,9 +1514,11 @@ class FlasheCohort(object):
         self._last = CohortUpload(cts, psum, path, [self.first_idx + p for p in plan.present])
         return self._last
 
-    def _collect(self, weights_list, seeds, present=None, rng=None):
-        """(plan, every layer of every present client as _layer_source gives it): the refusals, before anything of the cohort's state is
-        touched."""
+    def _collect(self, weights_list, seeds, present=None, rng=None, degrees=None):
+        """(plan, every layer of every present client as _layer_source gives it, pre): the refusals, before anything of the cohort's state
+        is touched.  With degrees a host layer is `layer * degree` already and a tensor's NumPy dtype is the one that product has;
+        pre[c][l] = the tensor's dtype before it (None for a host layer: nothing left to multiply), pre = None without degrees or
+        without a tensor."""
         C = self.n_local if present is None else len(weights_list)
         if len(weights_list) != C:
             raise ValueError(f"the cohort holds {C} clients, got {len(weights_list)} Weights")
@@ -1343,9 +1527,34 @@ class FlasheCohort(object):
         if rng is not None and seeds is not None:
             raise ValueError("rng and seeds: one source of draws at a time")
         _check_rng(rng, C)
+        if degrees is not None:
+            if len(degrees) != C:
+                raise ValueError(f"degrees: one per client ({C}), got {len(degrees)}")
+            for ci, d in enumerate(degrees):
+                if _check_degree(d, f"degrees[{ci}]") is None:
+                    raise ValueError(f"degrees[{ci}] is None: every present client has a degree, or degrees=None")
         plan = self.plan(weights_list, present)
         eng = self.lead.cipher.engine
-        return plan, [[_layer_source(eng, w._weights[k], f"client {ci} layer {k!r}") for k in plan.names] for ci, w in enumerate(weights_list)]
+        if degrees is None:
+            return plan, [[_layer_source(eng, w._weights[k], f"client {ci} layer {k!r}") for k in plan.names] for ci, w in enumerate(weights_list)], None
+        if not hasattr(eng, "stage_layers_dev") and any(interop.is_foreign(w._weights[k]) for w in weights_list for k in plan.names):
+            raise TypeError("degrees with framework tensors need an engine with flashe_stage_layers_dev")
+        layers, pre = [], []
+        for ci, w in enumerate(weights_list):
+            row, before = [], []
+            for k in plan.names:
+                v = w._weights[k]
+                if interop.is_foreign(v):
+                    x, code, hdt, size, shape = _layer_source(eng, v, f"client {ci} layer {k!r}")
+                    row.append((x, code, _loop_dtype(hdt, degrees[ci]), size, shape))
+                    before.append(hdt)
+                else:
+                    row.append(_layer_source(eng, np.asarray(v) * degrees[ci], f"client {ci} layer {k!r}"))
+                    before.append(None)
+            layers.append(row)
+            pre.append(before)
+        # (host layers only: they are multiplied already, nothing of the step changes)
+        return plan, layers, pre if any(b is not None for before in pre for b in before) else None
 
     def _refuse_prepared_len(self, plan, seeds, rng=None):
         """A cache of another length: the call-by-call step's ValueError, where the first sequential client raises it (after its quantiser
@@ -1381,10 +1590,26 @@ class FlasheCohort(object):
         self.lead.cipher.set_idx_list(mode="encrypt")
         return alphas
 
-    def _tables(self, plan, layers, alphas, normalize):
-        """(every client's tensor-layer table, keep): host layers go up once, client by client."""
+    def _tables(self, plan, layers, alphas, normalize, degrees=None, pre=None):
+        """(every client's tensor-layer table, keep): host layers go up once, client by client.  With degrees: ONE stage pass for all
+        clients (_stage_scaled), and the tables name its output as plain layers."""
         eng, means = self.lead.cipher.engine, self.lead.quantizer.past_layer_mean_list
         tables, keep = [], []
+        if degrees is not None:
+            items = []
+            for ci, row in enumerate(layers):
+                ptrs, held = _stage_host_layers(eng, [layer[0] for layer in row])
+                keep += held
+                for li, (_x, code, hdt, size, _shape) in enumerate(row):
+                    tensor = pre[ci][li] is not None
+                    items.append((ptrs[li], code, pre[ci][li] if tensor else hdt, size, degrees[ci] if tensor else None, alphas[li],
+                                  means[li] if normalize else None))
+            staged, scratch = _stage_scaled(eng, items)
+            keep.append(scratch)
+            L = len(plan.names)
+            for ci in range(len(layers)):
+                tables.append([(plan.starts[li], staged[ci * L + li][0], alphas[li], 0.0, staged[ci * L + li][1], 0) for li in range(L)])
+            return tables, keep
         for row in layers:
             ptrs, held = _stage_host_layers(eng, [layer[0] for layer in row])
             keep += held
@@ -1469,7 +1694,7 @@ class FlasheCohort(object):
             eng.encrypt_batch_sum_dev(c.iter_index, idxs, scheme, n_elems, _cipher_mod.N_JOBS, pts, eng.limbs, [v.buf for v in cts], psum.buf)
         return cts, psum, pts
 
-    def _per_client(self, weights_list, normalize, seeds, present=None, rng=None):
+    def _per_client(self, weights_list, normalize, seeds, present=None, rng=None, degrees=None):
         """The present clients' own steps one after the other (one cipher re-indexed per client; with precompute: every client's own cipher
         and masks), then the aggregate of what they wrote."""
         ld = self.lead
@@ -1483,18 +1708,24 @@ class FlasheCohort(object):
                     np.random.seed(seeds[ci])
                 lw = _Layers({k: w._weights[k] for k in w.walking_order})
                 lw.walking_order = list(w.walking_order)
-                up = cl.quantize_encrypt(lw, device=True, normalize=normalize, **_rng_kw(_client_rng(rng, ci)))
+                up = cl.quantize_encrypt(lw, device=True, normalize=normalize, **_rng_kw(_client_rng(rng, ci)),
+                                         **({} if degrees is None else {"degree": degrees[ci]}))
                 ct = up._weights[up.walking_order[0]]
                 cts.append(cl.cipher._as_compact(ct) if self.compact else ct)
                 ld.shape_dict = cl.shape_dict
         finally:
             ld.cipher.idx = self.first_idx
+            ld.degree = None if degrees is None else degrees[0]
         psum = ld.cipher.aggregate(cts, device=True)
         self._last = CohortUpload(cts, psum, PER_CLIENT, [self.first_idx + p for p in present])
         return self._last
 
-    def decrypt_unquantize(self, aggregate=None, uploaded=None, out=None, unnormalize=False):
-        """The new global model as FlasheClient.decrypt_unquantize returns it (out=: written into the caller's tensors, in place).  Without
+    def decrypt_unquantize(self, aggregate=None, uploaded=None, out=None, unnormalize=False, degree=None, total_degree=None, last_round=None):
+        """degree, total_degree, last_round (new): FlasheClient.decrypt_unquantize's, handed to the lead.  When the cohort decrypts its own
+        sum and both degrees are omitted after a quantize_encrypt(degrees=...), degree is the first present client's and total_degree the
+        left-to-right sum of the present clients' degrees (what the arbiter reduces, jzf_aggregator.py:380).
+
+        The new global model as FlasheClient.decrypt_unquantize returns it (out=: written into the caller's tensors, in place).  Without
         an aggregate: the cohort is the whole federation and its own last partial_sum is decrypted, `uploaded` defaulting to the clients
         that upload held (CohortUpload.present) -- after a "cohort-chain" upload by adding the mask that launch wrote (one memory-bound
         pass) whenever set_idx_list yields exactly the add / minus lists the mask stands for; ValueError when clients outside the cohort
@@ -1514,8 +1745,11 @@ class FlasheCohort(object):
             raise ValueError("decrypt_unquantize needs the layer shapes a quantize_encrypt left behind (shape_dict)")
         if not hasattr(aggregate, "walking_order"):
             aggregate = _Layers({next(iter(ld.shape_dict), "w"): aggregate})
+        if own and degree is None and total_degree is None and self._degrees:
+            degree, total_degree = self._degrees[0], functools.reduce(operator.add, self._degrees)
+        degree, total_degree = ld._back_degrees(degree, total_degree)      # (refused before set_idx_list touches the cipher)
         ld.set_idx_list(list(uploaded))
-        return ld.decrypt_unquantize(aggregate, out=out, unnormalize=unnormalize)
+        return ld.decrypt_unquantize(aggregate, out=out, unnormalize=unnormalize, degree=degree, total_degree=total_degree, last_round=last_round)
 
 
 # ---- a cohort of sparse-job clients hosted on one GPU (new) ----------------------------------------------------------------------
@@ -2074,14 +2308,19 @@ class FlasheSparseCohort(object):
         return self._last
 
     # ---- Client.aggregate's decrypt + unquantise -------------------------------------------------------------------------------
-    def decrypt_unquantize(self, aggregate=None, uploaded=None, out=None, unnormalize=False):
-        """The new global model: set_idx_list(uploaded) + shape_dict = shape_dict_used_for_sparsification +
+    def decrypt_unquantize(self, aggregate=None, uploaded=None, out=None, unnormalize=False, degree=None, total_degree=None, last_round=None):
+        """degree, total_degree, last_round (new): FlasheClient.decrypt_unquantize's, handed to the lead as they are (the sparse job's FRONT
+        takes no degree: jzf_aggregator.py:676 precedes `weights - before` and the sparsifier there, so the multiply belongs to the delta
+        the caller hands to sparsify).
+
+        The new global model: set_idx_list(uploaded) + shape_dict = shape_dict_used_for_sparsification +
         FlasheClient.decrypt_unquantize(aggregate, out=, unnormalize=) of client first_idx (jzf_aggregator.py:881-899) -- the same floats,
         past_layer_mean_list / past_layer_std_list bit for bit.  Without an aggregate the cohort is the whole federation and its own last
         `aggregate` is decrypted, with the span bounds the upload computed; ValueError when clients outside the cohort exist."""
         from .cipher import _SparseMinus
         ld = self.lead
         c = ld.cipher
+        degree, total_degree = ld._back_degrees(degree, total_degree)
         own = aggregate is None
         if own:
             if self.n_local != self.num_clients:
@@ -2108,7 +2347,7 @@ class FlasheSparseCohort(object):
             else:
                 c.masks = self._host_lists()
                 ld.set_idx_list(list(uploaded))
-            return ld.decrypt_unquantize(aggregate, out=out, unnormalize=unnormalize)
+            return ld.decrypt_unquantize(aggregate, out=out, unnormalize=unnormalize, degree=degree, total_degree=total_degree, last_round=last_round)
         except Exception:
             ld.shape_dict = saved
             raise

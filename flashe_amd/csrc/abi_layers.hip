@@ -1,5 +1,6 @@
 // C ABI of libflashe_hip.so, the codec and sparsifier entry points (see include/flashe.h): the flat forms and every form that takes a
-// per-layer table -- the model-wide codec, batched and tensor forms, the prepared client step, the cohorts, flashe_store_layers_dev.
+// per-layer table -- the model-wide codec, batched and tensor forms, the prepared client step, the cohorts, flashe_store_layers_dev,
+// flashe_stage_layers_dev / flashe_finish_layers_dev.
 // Host-side glue only: argument checks, the tables and the stage pass; what it shares with abi.hip is declared in ctx.h.
 #include "ctx.h"
 #include "layer_tables.h"
@@ -950,6 +951,117 @@ int flashe_store_layers_dev(flashe_ctx *ctx, const double *in_dev, uint64_t n, c
     const TensorStore *tab = nullptr;
     if ((rc = upload_tab(ctx, ctx->tensor_tab, st, &tab))) return rc;
     HIP_TRY(ctx, launch_store_layers(ctx->env, tab, static_cast<int>(st.size()), groups, in_dev));
+    return FLASHE_OK;
+}
+
+// ---- the aggregator's degree scaling either side of the step (jzf_aggregator.py:676, :902-907) ----
+// a multiplier or divisor the reference would not have reached the kernels with
+static bool usable_factor(double v) { return std::isfinite(v) && v != 0.0; }
+
+// a non-empty row's pointer: given and aligned to its element size
+static bool row_ptr_ok(const void *p, int es) { return p && reinterpret_cast<uintptr_t>(p) % static_cast<uintptr_t>(es) == 0; }
+
+int flashe_stage_layers_dev(flashe_ctx *ctx, const flashe_stage_row *rows, int n_rows)
+{
+    CHECK_CTX(ctx);
+    if (n_rows < 0 || (n_rows && !rows)) return fail(ctx, FLASHE_EINVAL, "stage_layers: bad row table");
+    if (ctx->capturing) return fail(ctx, FLASHE_EINVAL, "stage_layers: not inside a graph capture (the row table is staged per call)");
+    const int32_t known = FLASHE_STAGE_SCALE | FLASHE_STAGE_SCALE_WIDE | FLASHE_STAGE_SHIFT | FLASHE_STAGE_SHIFT_WIDE | FLASHE_STAGE_OUT_F64;
+    std::vector<StageRow> st;
+    uint64_t groups = 0;
+    for (int r = 0; r < n_rows; r++) {
+        const flashe_stage_row &y = rows[r];
+        const int es = tensor_elem_bytes(y.src_dtype);
+        if (!es) return fail(ctx, FLASHE_EINVAL, "row %d: unknown dtype %d", r, static_cast<int>(y.src_dtype));
+        if (y.flags & ~known) return fail(ctx, FLASHE_EINVAL, "row %d: unknown flags 0x%x", r, static_cast<unsigned>(y.flags));
+        const bool scale = y.flags & FLASHE_STAGE_SCALE, scale_wide = y.flags & FLASHE_STAGE_SCALE_WIDE, shift = y.flags & FLASHE_STAGE_SHIFT,
+                   shift_wide = y.flags & FLASHE_STAGE_SHIFT_WIDE, out64 = y.flags & FLASHE_STAGE_OUT_F64, src64 = y.src_dtype == FLASHE_TENSOR_F64;
+        if ((scale_wide && !scale) || (shift_wide && !shift)) return fail(ctx, FLASHE_EINVAL, "row %d: a WIDE flag without its operation", r);
+        if ((src64 && (scale_wide || shift_wide)) || (scale_wide && shift_wide))
+            return fail(ctx, FLASHE_EINVAL, "row %d: a WIDE flag on a value that is float64 already", r);
+        if ((scale_wide || src64) && !out64) return fail(ctx, FLASHE_EINVAL, "row %d: a float64 value needs FLASHE_STAGE_OUT_F64", r);
+        if (scale && !usable_factor(y.scale)) return fail(ctx, FLASHE_EINVAL, "row %d: the scale must be finite and not zero", r);
+        if (shift && !std::isfinite(y.shift)) return fail(ctx, FLASHE_EINVAL, "row %d: the shift must be finite", r);
+        if (y.size == 0) continue;
+        if (!row_ptr_ok(y.src, es) || !row_ptr_ok(y.dst, out64 ? 8 : 4)) return fail(ctx, FLASHE_EINVAL, "row %d: null or misaligned src / dst", r);
+        st.push_back(StageRow{groups, y.size, y.src, y.dst, y.scale, y.shift, y.src_dtype, y.flags});
+        groups += (y.size + 7) / 8;
+    }
+    if (st.empty()) return FLASHE_OK;
+    const StageRow *tab = nullptr;
+    if (int rc = upload_tab(ctx, ctx->tensor_tab, st, &tab)) return rc;
+    HIP_TRY(ctx, launch_stage_rows(ctx->env, tab, static_cast<int>(st.size()), groups));
+    return FLASHE_OK;
+}
+
+int flashe_finish_layers_dev(flashe_ctx *ctx, const double *in_dev, uint64_t n, const flashe_finish_row *rows, int n_rows, uint64_t block,
+                             double *stats_dev)
+{
+    CHECK_CTX(ctx);
+    if (n_rows < 1 || !rows) return fail(ctx, FLASHE_EINVAL, "the row table needs at least one entry");
+    if (rows[0].start != 0) return fail(ctx, FLASHE_EINVAL, "rows[0].start must be 0");
+    if (ctx->capturing) return fail(ctx, FLASHE_EINVAL, "finish_layers: not inside a graph capture (the row table is staged per call)");
+    if (n && (!in_dev || (reinterpret_cast<uintptr_t>(in_dev) & 7u))) return fail(ctx, FLASHE_EINVAL, "null or misaligned in_dev");
+    if (stats_dev && (block < 1 || block > 16384)) return fail(ctx, FLASHE_EINVAL, "block must be in [1, 16384], got %llu", static_cast<unsigned long long>(block));
+    if (reinterpret_cast<uintptr_t>(stats_dev) & 7u) return fail(ctx, FLASHE_EINVAL, "misaligned stats_dev");
+    const int32_t known = FLASHE_FINISH_DIV_TOTAL | FLASHE_FINISH_SHIFT | FLASHE_FINISH_DIV_OWN | FLASHE_FINISH_ADD_LAST;
+    std::vector<FinishRow> st;
+    std::vector<FinishStat> sl;
+    struct Span { uintptr_t lo, hi; int row; };
+    std::vector<Span> dsts, lasts;
+    uint64_t groups = 0, blocks = 0;
+    for (int r = 0; r < n_rows; r++) {
+        const flashe_finish_row &y = rows[r];
+        const uint64_t end = layer_end(rows, n_rows, r, n);
+        if (y.start > end || end > n) return fail(ctx, FLASHE_EINVAL, "row %d: starts must ascend and stay within n", r);
+        const int es = tensor_elem_bytes(y.dst_dtype);
+        if (!es) return fail(ctx, FLASHE_EINVAL, "row %d: unknown dtype %d", r, static_cast<int>(y.dst_dtype));
+        if (y.flags & ~known) return fail(ctx, FLASHE_EINVAL, "row %d: unknown flags 0x%x", r, static_cast<unsigned>(y.flags));
+        if (y.reserved) return fail(ctx, FLASHE_EINVAL, "row %d: reserved field must be 0", r);
+        const bool add_last = y.flags & FLASHE_FINISH_ADD_LAST;
+        const int ls = add_last ? tensor_elem_bytes(y.last_dtype) : 0;
+        if (add_last && !ls) return fail(ctx, FLASHE_EINVAL, "row %d: unknown last_dtype %d", r, static_cast<int>(y.last_dtype));
+        if (((y.flags & FLASHE_FINISH_DIV_TOTAL) && !usable_factor(y.div_total)) || ((y.flags & FLASHE_FINISH_DIV_OWN) && !usable_factor(y.div_own)))
+            return fail(ctx, FLASHE_EINVAL, "row %d: a divisor must be finite and not zero", r);
+        if ((y.flags & FLASHE_FINISH_SHIFT) && !std::isfinite(y.shift)) return fail(ctx, FLASHE_EINVAL, "row %d: the shift must be finite", r);
+        const uint64_t size = end - y.start;
+        if (!size) continue;
+        if (!row_ptr_ok(y.dst, es)) return fail(ctx, FLASHE_EINVAL, "row %d: null or misaligned dst", r);
+        if (add_last && !row_ptr_ok(y.last, ls)) return fail(ctx, FLASHE_EINVAL, "row %d: null or misaligned last", r);
+        const uintptr_t d = reinterpret_cast<uintptr_t>(y.dst);
+        dsts.push_back(Span{d, d + size * es, r});
+        if (add_last) {
+            const uintptr_t l = reinterpret_cast<uintptr_t>(y.last);
+            lasts.push_back(Span{l, l + size * ls, r});
+        }
+        st.push_back(FinishRow{y.start, groups, size, y.dst, y.last, y.div_total, y.shift, y.div_own, y.dst_dtype, add_last ? y.last_dtype : 0, y.flags, 0});
+        groups += (size + 7) / 8;
+        if (stats_dev) {
+            sl.push_back(FinishStat{y.start, blocks, size, y.div_total, y.shift, y.flags & (FLASHE_FINISH_DIV_TOTAL | FLASHE_FINISH_SHIFT), r});
+            blocks += (size + block - 1) / block;
+        }
+    }
+    // a last-round layer may be its own row's dst (same dtype: every value is read by the lane that writes it) and nothing else's
+    for (const Span &l : lasts)
+        for (const Span &d : dsts) {
+            if (l.hi <= d.lo || d.hi <= l.lo) continue;
+            const bool in_place = l.row == d.row && l.lo == d.lo && rows[l.row].last_dtype == rows[l.row].dst_dtype;
+            if (!in_place) return fail(ctx, FLASHE_EINVAL, "row %d: last overlaps row %d's dst (only last == dst with equal dtypes is in place)", l.row, d.row);
+        }
+    if (st.empty()) return FLASHE_OK;
+    int rc;
+    if (!sl.empty()) {
+        // table, then the per-buffer sums and the layer means behind it; the statistics read in_dev before the store pass, which may
+        // write in place
+        const size_t tab_bytes = flashe_tables::up16(sl.size() * sizeof(FinishStat));
+        if ((rc = ensure(ctx, ctx->stat_ws, tab_bytes + (blocks + sl.size()) * sizeof(double))) || (rc = upload_bytes(ctx, ctx->stat_ws.p, sl.data(), sl.size() * sizeof(FinishStat)))) return rc;
+        double *bsum = reinterpret_cast<double *>(static_cast<char *>(ctx->stat_ws.p) + tab_bytes);
+        HIP_TRY(ctx, launch_finish_stats(ctx->env, static_cast<const FinishStat *>(ctx->stat_ws.p), static_cast<int>(sl.size()), blocks, in_dev, block, bsum,
+                                         bsum + blocks, stats_dev));
+    }
+    const FinishRow *tab = nullptr;
+    if ((rc = upload_tab(ctx, ctx->tensor_tab, st, &tab))) return rc;
+    HIP_TRY(ctx, launch_finish_layers(ctx->env, tab, static_cast<int>(st.size()), groups, in_dev));
     return FLASHE_OK;
 }
 

@@ -381,6 +381,41 @@ struct StatLayer {            // NumPy-exact sum and sum of squared deviations o
 hipError_t launch_layer_stats(const LaunchEnv &env, const StatLayer *tab_dev, int n_tab, uint64_t n_blocks, const double *in_dev, uint64_t block,
                               double *bsum_dev, double *means_dev, double *stats_dev);
 
+// The two passes with the aggregator's degree scaling (flashe_stage_layers_dev / flashe_finish_layers_dev; flags as in include/flashe.h).
+// Front, jzf_aggregator.py:676 then jzf_quantize.py:542-547: dst[k] = src[k] (* scale) (+ shift) in the type NumPy gives the layer at
+// each step, stored as float32 or -- kStageOutF64 -- float64.  Rows of one model or of a cohort's C x L layers; groups of eight values
+// of one row per lane as in the store pass.
+constexpr int kStageScale = 1, kStageScaleWide = 2, kStageShift = 4, kStageShiftWide = 8, kStageOutF64 = 16;
+struct StageRow {
+    uint64_t group_start;     // first 8-value group of the row among all groups
+    uint64_t size;
+    const void *src;
+    void *dst;
+    double scale, shift;
+    int dtype, flags;         // dtype: how src is stored
+};
+hipError_t launch_stage_rows(const LaunchEnv &env, const StageRow *tab_dev, int n_tab, uint64_t n_groups);
+// Back, jzf_aggregator.py:902-907: y1 = in / div_total, y2 = y1 + shift, y3 = y2 / div_own, y4 = last + y3, each under its flag, stored in
+// the row's dtype; the statistics sum y2.  last may be dst itself (same dtype): a lane reads the eight values it writes.
+constexpr int kFinishDivTotal = 1, kFinishShift = 2, kFinishDivOwn = 4, kFinishAddLast = 8;
+struct FinishRow {
+    uint64_t start;           // flat index of the row's first value
+    uint64_t group_start;
+    uint64_t size;
+    void *dst;
+    const void *last;
+    double div_total, shift, div_own;
+    int dtype, last_dtype, flags, pad_;
+};
+hipError_t launch_finish_layers(const LaunchEnv &env, const FinishRow *tab_dev, int n_tab, uint64_t n_groups, const double *in_dev);
+struct FinishStat {           // StatLayer with the division in front of the shift
+    uint64_t start, blk_start, size;
+    double div_total, shift;
+    int flags, out_index;     // flags: kFinishDivTotal / kFinishShift
+};
+hipError_t launch_finish_stats(const LaunchEnv &env, const FinishStat *tab_dev, int n_tab, uint64_t n_blocks, const double *in_dev, uint64_t block,
+                               double *bsum_dev, double *means_dev, double *stats_dev);
+
 // The sparse job's codec front end for a cohort of co-located clients (flashe_quantize_cohort_dev, tensors.hip): C clients' compact
 // layers -> C one-limb plaintext vectors in ONE launch, shift + quantise in registers (no staged copy).  Row r of the shared table:
 // compact values [start, next start) of every client, quantised with (alpha, scale, den) in float32 or -- loop_f64 -- float64, after

@@ -2,7 +2,8 @@
 // flashe_quantize_batch_tensors_dev, flashe_store_layers_dev): the front end that turns float16 / bfloat16 / float32 / float64 layers
 // (optionally normalised) into the compute type the codec reads, the back end that writes the unquantised float64 values into the
 // caller's tensors in their own dtype, and NumPy's blocked pairwise summation of every layer for unnormalize's statistics.
-// All three are HBM-bound streaming passes; the layer tables are small device arrays staged per call.
+// All three are HBM-bound streaming passes; the layer tables are small device arrays staged per call.  Beside them, the two passes that
+// carry the aggregator's degree scaling (flashe_stage_layers_dev, flashe_finish_layers_dev; jzf_aggregator.py:676, :902-907).
 #include "device_common.h"
 
 namespace flashe {
@@ -280,9 +281,28 @@ constexpr int kStatThreads = 64;
 constexpr int kStatMaxLeaves = 512;        // enough for buffers of up to 16,384 values (every leaf of a split tree holds > 56)
 constexpr int kStatMaxDepth = 32;
 
-__global__ __launch_bounds__(kStatThreads) void stat_blocks_kernel(const StatLayer *__restrict__ tab, int n_tab, uint64_t n_blocks,
-                                                                   const double *__restrict__ in, uint64_t block, int pass,
-                                                                   const double *__restrict__ means, double *__restrict__ bsum)
+// y of a table row: what the row's store pass stores before its cast (StatLayer: in (+ shift))
+__device__ __forceinline__ double stat_value(const StatLayer &L, double x)
+{
+#pragma clang fp contract(off)
+    if (L.flags & kTensorShift) x = x + L.shift;
+    return x;
+}
+
+// y2 of jzf_aggregator.py:902-904 (FinishStat / FinishRow: in / div_total + shift), the value unnormalize's statistics see
+__device__ __forceinline__ double finish_y2(double x, int flags, double div_total, double shift)
+{
+#pragma clang fp contract(off)
+    if (flags & kFinishDivTotal) x = x / div_total;
+    if (flags & kFinishShift) x = x + shift;
+    return x;
+}
+
+__device__ __forceinline__ double stat_value(const FinishStat &L, double x) { return finish_y2(x, L.flags, L.div_total, L.shift); }
+
+template <class Tab>
+__device__ __forceinline__ void stat_blocks_body(const Tab *__restrict__ tab, int n_tab, uint64_t n_blocks, const double *__restrict__ in, uint64_t block,
+                                                 int pass, const double *__restrict__ means, double *__restrict__ bsum)
 {
 #pragma clang fp contract(off)
     __shared__ uint32_t leaf_off[kStatMaxLeaves];
@@ -294,12 +314,11 @@ __global__ __launch_bounds__(kStatThreads) void stat_blocks_kernel(const StatLay
     __shared__ double st_left[kStatMaxDepth];
     __shared__ int n_leaves;
     for (uint64_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
-        const int li = layer_by(tab, n_tab, b, &StatLayer::blk_start);
-        const StatLayer &L = tab[li];
+        const int li = layer_by(tab, n_tab, b, &Tab::blk_start);
+        const Tab &L = tab[li];
         const uint64_t off0 = (b - L.blk_start) * block;
         const uint32_t m = static_cast<uint32_t>(L.size - off0 < block ? L.size - off0 : block);
         const double *x = in + L.start + off0;
-        const bool shift = (L.flags & kTensorShift) != 0;
         const double mean = pass ? means[li] : 0.0;
         if (threadIdx.x == 0) {                                         // the leaves, left to right
             int sp = 0, nl = 0;
@@ -320,8 +339,7 @@ __global__ __launch_bounds__(kStatThreads) void stat_blocks_kernel(const StatLay
         for (int l = threadIdx.x; l < nl; l += kStatThreads) {
             const uint32_t o = leaf_off[l], len = leaf_len[l];
             auto val = [&](uint32_t i) {
-                double y = x[o + i];
-                if (shift) y = y + L.shift;
+                double y = stat_value(L, x[o + i]);
                 if (pass) { const double d = y - mean; y = d * d; }
                 return y;
             };
@@ -377,19 +395,254 @@ __global__ __launch_bounds__(kStatThreads) void stat_blocks_kernel(const StatLay
     }
 }
 
+__global__ __launch_bounds__(kStatThreads) void stat_blocks_kernel(const StatLayer *__restrict__ tab, int n_tab, uint64_t n_blocks,
+                                                                   const double *__restrict__ in, uint64_t block, int pass,
+                                                                   const double *__restrict__ means, double *__restrict__ bsum)
+{
+    stat_blocks_body(tab, n_tab, n_blocks, in, block, pass, means, bsum);
+}
+
 // one lane per layer: the buffer sums added in order from 0.0; pass 0 also leaves the layer's mean (S / n) for pass 1
-__global__ __launch_bounds__(kStreamThreads) void stat_combine_kernel(const StatLayer *__restrict__ tab, int n_tab, const double *__restrict__ bsum,
-                                                                      uint64_t block, int pass, double *__restrict__ means, double *__restrict__ stats)
+template <class Tab>
+__device__ __forceinline__ void stat_combine_body(const Tab *__restrict__ tab, int n_tab, const double *__restrict__ bsum, uint64_t block, int pass,
+                                                  double *__restrict__ means, double *__restrict__ stats)
 {
 #pragma clang fp contract(off)
     const int l = blockIdx.x * kStreamThreads + threadIdx.x;
     if (l >= n_tab) return;
-    const StatLayer &L = tab[l];
+    const Tab &L = tab[l];
     const uint64_t nb = (L.size + block - 1) / block;
     double s = 0.0;
     for (uint64_t b = 0; b < nb; b++) s += bsum[L.blk_start + b];
     stats[2 * L.out_index + pass] = s;
     if (pass == 0) means[l] = s / static_cast<double>(L.size);
+}
+
+__global__ __launch_bounds__(kStreamThreads) void stat_combine_kernel(const StatLayer *__restrict__ tab, int n_tab, const double *__restrict__ bsum,
+                                                                      uint64_t block, int pass, double *__restrict__ means, double *__restrict__ stats)
+{
+    stat_combine_body(tab, n_tab, bsum, block, pass, means, stats);
+}
+
+// ---- the aggregator's degree scaling either side of the step (jzf_aggregator.py:676, :902-907) ----
+// Eight values of one row per lane, as store_layers_kernel: 16-byte accesses where the row's pointer allows them (a group starts a
+// multiple of 16 bytes behind it), scalar ones at the row's end and on odd alignments.
+namespace {
+
+__device__ __forceinline__ bool vec_ok(const void *p, int cnt) { return cnt == 8 && (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// values [j0, j0 + cnt) of a float32 / float16 / bfloat16 row as float32 (a 16-bit value upcast exactly); the rest 0
+__device__ __forceinline__ void load8_f32(const void *p, int dtype, uint64_t j0, int cnt, float x[8])
+{
+    if (dtype == kTensorF32) {
+        const float *s = static_cast<const float *>(p) + j0;
+        if (vec_ok(p, cnt)) {
+            const float4 a = *reinterpret_cast<const float4 *>(s), b = *reinterpret_cast<const float4 *>(s + 4);
+            x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
+        } else {
+#pragma unroll
+            for (int t = 0; t < 8; t++) x[t] = t < cnt ? s[t] : 0.0f;
+        }
+        return;
+    }
+    const uint16_t *s = static_cast<const uint16_t *>(p) + j0;
+    uint16_t h[8];
+    if (vec_ok(p, cnt)) {
+        const uint4 w = *reinterpret_cast<const uint4 *>(s);
+        h[0] = static_cast<uint16_t>(w.x); h[1] = static_cast<uint16_t>(w.x >> 16); h[2] = static_cast<uint16_t>(w.y); h[3] = static_cast<uint16_t>(w.y >> 16);
+        h[4] = static_cast<uint16_t>(w.z); h[5] = static_cast<uint16_t>(w.z >> 16); h[6] = static_cast<uint16_t>(w.w); h[7] = static_cast<uint16_t>(w.w >> 16);
+    } else {
+#pragma unroll
+        for (int t = 0; t < 8; t++) h[t] = t < cnt ? s[t] : static_cast<uint16_t>(0);
+    }
+#pragma unroll
+    for (int t = 0; t < 8; t++) x[t] = dtype == kTensorF16 ? f16_to_f32(h[t]) : bf16_to_f32(h[t]);
+}
+
+__device__ __forceinline__ void load8_f64(const void *p, uint64_t j0, int cnt, double x[8])
+{
+    const double *s = static_cast<const double *>(p) + j0;
+    if (vec_ok(p, cnt)) {
+#pragma unroll
+        for (int t = 0; t < 8; t += 2) {
+            const double2 a = *reinterpret_cast<const double2 *>(s + t);
+            x[t] = a.x; x[t + 1] = a.y;
+        }
+    } else {
+#pragma unroll
+        for (int t = 0; t < 8; t++) x[t] = t < cnt ? s[t] : 0.0;
+    }
+}
+
+// y[0 .. cnt) into values [j0, j0 + cnt) of a row stored as dtype: float64 -> float32 -> 16 bits, each step round to nearest even
+// (store_layers_kernel's stores)
+__device__ __forceinline__ void store8(void *p, int dtype, uint64_t j0, int cnt, const double y[8])
+{
+    const bool vec = vec_ok(p, cnt);
+    if (dtype == kTensorF64) {
+        double *d = static_cast<double *>(p) + j0;
+        if (vec) {
+#pragma unroll
+            for (int t = 0; t < 8; t += 2) *reinterpret_cast<double2 *>(d + t) = make_double2(y[t], y[t + 1]);
+        } else {
+            for (int t = 0; t < cnt; t++) d[t] = y[t];
+        }
+    } else if (dtype == kTensorF32) {
+        float *d = static_cast<float *>(p) + j0;
+        if (vec) {
+#pragma unroll
+            for (int t = 0; t < 8; t += 4)
+                *reinterpret_cast<float4 *>(d + t) = make_float4(static_cast<float>(y[t]), static_cast<float>(y[t + 1]), static_cast<float>(y[t + 2]),
+                                                                 static_cast<float>(y[t + 3]));
+        } else {
+            for (int t = 0; t < cnt; t++) d[t] = static_cast<float>(y[t]);
+        }
+    } else {
+        uint16_t h[8];
+#pragma unroll
+        for (int t = 0; t < 8; t++) {
+            float f = static_cast<float>(y[t]);
+            // two roundings, as torch's .to() of a float64 tensor: behind a division the compiler otherwise folds the pair into ONE
+            // float64 -> float16 conversion, which differs wherever the float32 value is a tie of the 16-bit format
+            asm volatile("" : "+v"(f));
+            h[t] = dtype == kTensorF16 ? f32_to_f16(f) : f32_to_bf16(f);
+        }
+        uint16_t *d = static_cast<uint16_t *>(p) + j0;
+        if (vec) {
+            uint4 w;
+            w.x = h[0] | (static_cast<uint32_t>(h[1]) << 16); w.y = h[2] | (static_cast<uint32_t>(h[3]) << 16);
+            w.z = h[4] | (static_cast<uint32_t>(h[5]) << 16); w.w = h[6] | (static_cast<uint32_t>(h[7]) << 16);
+            *reinterpret_cast<uint4 *>(d) = w;
+        } else {
+            for (int t = 0; t < cnt; t++) d[t] = h[t];
+        }
+    }
+}
+
+// One float32 value through `weights *= degree` and normalize, in the types NumPy gives the layer: float32 * float32(scale), or -- WIDE,
+// an np.float64 degree -- float64 from there on; the shift by stage_layers_kernel's rule.  A float32 result widens exactly.
+__device__ __forceinline__ double stage_value(const StageRow &L, float x)
+{
+#pragma clang fp contract(off)
+    if (L.flags & kStageScaleWide) {
+        double d = static_cast<double>(x) * L.scale;
+        if (L.flags & kStageShift) d = d + L.shift;
+        return d;
+    }
+    if (L.flags & kStageScale) x = x * static_cast<float>(L.scale);
+    if (L.flags & kStageShift)
+        x = (L.flags & kStageShiftWide) ? static_cast<float>(static_cast<double>(x) + L.shift) : x + static_cast<float>(L.shift);
+    return static_cast<double>(x);
+}
+
+__device__ __forceinline__ double stage_value(const StageRow &L, double x)
+{
+#pragma clang fp contract(off)
+    if (L.flags & kStageScale) x = x * L.scale;
+    if (L.flags & kStageShift) x = x + L.shift;
+    return x;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kStreamThreads) void stage_rows_kernel(const StageRow *__restrict__ tab, int n_tab, uint64_t n_groups)
+{
+#pragma clang fp contract(off)
+    for (uint64_t g = static_cast<uint64_t>(blockIdx.x) * kStreamThreads + threadIdx.x; g < n_groups; g += static_cast<uint64_t>(gridDim.x) * kStreamThreads) {
+        const StageRow &L = tab[layer_by(tab, n_tab, g, &StageRow::group_start)];
+        const uint64_t j0 = (g - L.group_start) * 8;
+        const int cnt = L.size - j0 < 8 ? static_cast<int>(L.size - j0) : 8;
+        double y[8];
+        if (L.dtype == kTensorF64) {
+            double x[8];
+            load8_f64(L.src, j0, cnt, x);
+#pragma unroll
+            for (int t = 0; t < 8; t++) y[t] = stage_value(L, x[t]);
+        } else {
+            float x[8];
+            load8_f32(L.src, L.dtype, j0, cnt, x);
+#pragma unroll
+            for (int t = 0; t < 8; t++) y[t] = stage_value(L, x[t]);
+        }
+        store8(L.dst, (L.flags & kStageOutF64) ? kTensorF64 : kTensorF32, j0, cnt, y);
+    }
+}
+
+hipError_t launch_stage_rows(const LaunchEnv &env, const StageRow *tab_dev, int n_tab, uint64_t n_groups)
+{
+    if (n_groups == 0 || n_tab < 1) return hipSuccess;
+    hipLaunchKernelGGL(stage_rows_kernel, dim3(stream_grid(env, n_groups)), dim3(kStreamThreads), 0, env.stream, tab_dev, n_tab, n_groups);
+    return hipGetLastError();
+}
+
+// (no __restrict__ on the rows' pointers: last may be dst, and a lane has read its eight values of last before it stores)
+__global__ __launch_bounds__(kStreamThreads) void finish_layers_kernel(const FinishRow *__restrict__ tab, int n_tab, uint64_t n_groups,
+                                                                       const double *__restrict__ in)
+{
+#pragma clang fp contract(off)
+    for (uint64_t g = static_cast<uint64_t>(blockIdx.x) * kStreamThreads + threadIdx.x; g < n_groups; g += static_cast<uint64_t>(gridDim.x) * kStreamThreads) {
+        const FinishRow &L = tab[layer_by(tab, n_tab, g, &FinishRow::group_start)];
+        const uint64_t j0 = (g - L.group_start) * 8;
+        const int cnt = L.size - j0 < 8 ? static_cast<int>(L.size - j0) : 8;
+        double y[8];
+#pragma unroll
+        for (int t = 0; t < 8; t++) {
+            y[t] = finish_y2(t < cnt ? in[L.start + j0 + t] : 0.0, L.flags, L.div_total, L.shift);
+            if (L.flags & kFinishDivOwn) y[t] = y[t] / L.div_own;
+        }
+        if (L.flags & kFinishAddLast) {
+            double w[8];                                                // last, upcast exactly (16 bits -> float32 -> float64)
+            if (L.last_dtype == kTensorF64) {
+                load8_f64(L.last, j0, cnt, w);
+            } else {
+                float f[8];
+                load8_f32(L.last, L.last_dtype, j0, cnt, f);
+#pragma unroll
+                for (int t = 0; t < 8; t++) w[t] = static_cast<double>(f[t]);
+            }
+#pragma unroll
+            for (int t = 0; t < 8; t++) y[t] = w[t] + y[t];
+        }
+        store8(L.dst, L.dtype, j0, cnt, y);
+    }
+}
+
+hipError_t launch_finish_layers(const LaunchEnv &env, const FinishRow *tab_dev, int n_tab, uint64_t n_groups, const double *in_dev)
+{
+    if (n_groups == 0 || n_tab < 1) return hipSuccess;
+    hipLaunchKernelGGL(finish_layers_kernel, dim3(stream_grid(env, n_groups)), dim3(kStreamThreads), 0, env.stream, tab_dev, n_tab, n_groups, in_dev);
+    return hipGetLastError();
+}
+
+// the statistics of y2: stat_blocks_kernel's tree and combine over rows that divide before they shift
+__global__ __launch_bounds__(kStatThreads) void finish_stat_blocks_kernel(const FinishStat *__restrict__ tab, int n_tab, uint64_t n_blocks,
+                                                                          const double *__restrict__ in, uint64_t block, int pass,
+                                                                          const double *__restrict__ means, double *__restrict__ bsum)
+{
+    stat_blocks_body(tab, n_tab, n_blocks, in, block, pass, means, bsum);
+}
+
+__global__ __launch_bounds__(kStreamThreads) void finish_stat_combine_kernel(const FinishStat *__restrict__ tab, int n_tab, const double *__restrict__ bsum,
+                                                                             uint64_t block, int pass, double *__restrict__ means,
+                                                                             double *__restrict__ stats)
+{
+    stat_combine_body(tab, n_tab, bsum, block, pass, means, stats);
+}
+
+hipError_t launch_finish_stats(const LaunchEnv &env, const FinishStat *tab_dev, int n_tab, uint64_t n_blocks, const double *in_dev, uint64_t block,
+                               double *bsum_dev, double *means_dev, double *stats_dev)
+{
+    if (n_blocks == 0 || n_tab < 1) return hipSuccess;
+    if (block < 1 || block > 16384) return hipErrorInvalidValue;
+    const int grid = static_cast<int>(n_blocks < 65536 ? n_blocks : 65536);
+    const int cgrid = (n_tab + kStreamThreads - 1) / kStreamThreads;
+    for (int pass = 0; pass < 2; pass++) {
+        hipLaunchKernelGGL(finish_stat_blocks_kernel, dim3(grid), dim3(kStatThreads), 0, env.stream, tab_dev, n_tab, n_blocks, in_dev, block, pass,
+                           means_dev, bsum_dev);
+        hipLaunchKernelGGL(finish_stat_combine_kernel, dim3(cgrid), dim3(kStreamThreads), 0, env.stream, tab_dev, n_tab, bsum_dev, block, pass, means_dev,
+                           stats_dev);
+    }
+    return hipGetLastError();
 }
 
 hipError_t launch_layer_stats(const LaunchEnv &env, const StatLayer *tab_dev, int n_tab, uint64_t n_blocks, const double *in_dev, uint64_t block,

@@ -749,6 +749,29 @@ class Engine:
         arr, nl = self._tensor_layers(layers)
         self._check(self._lib.flashe_store_layers_dev(self._h, self._ptr(inp), int(n), arr, nl, int(block), self._ptr(stats)))
 
+    def stage_layers_dev(self, rows):
+        """`weights *= degree` and normalize as ONE streaming pass (flashe_stage_layers_dev): rows of (src, dst, size, scale, shift, storage
+        dtype code, STAGE_* flags) -- one model's layers or a cohort's C x L -- each from src as stored to dst as float32 (float64 with
+        STAGE_OUT_F64), in the types NumPy gives the layer at each step."""
+        rows = list(rows)
+        arr = (_lib.StageRow * max(len(rows), 1))()
+        for i, (src, dst, size, scale, shift, dtype, flags) in enumerate(rows):
+            arr[i].src, arr[i].dst, arr[i].size, arr[i].scale, arr[i].shift, arr[i].src_dtype, arr[i].flags = (
+                int(src) if src else None, int(dst) if dst else None, int(size), float(scale), float(shift), int(dtype), int(flags))
+        self._check(self._lib.flashe_stage_layers_dev(self._h, arr, len(rows)))
+
+    def finish_layers_dev(self, inp, n, rows, block=0, stats=None):
+        """store_layers_dev with the aggregator's degree scaling (flashe_finish_layers_dev): rows of (start, dst, last, div_total, shift,
+        div_own, dst dtype code, last dtype code, FINISH_* flags); y = ((inp / div_total + shift) / div_own) + last, every step under its
+        flag, stored in dst's dtype; stats as store_layers_dev, over inp / div_total + shift."""
+        rows = list(rows)
+        arr = (_lib.FinishRow * max(len(rows), 1))()
+        for i, (start, dst, last, div_total, shift, div_own, dtype, last_dtype, flags) in enumerate(rows):
+            arr[i].start, arr[i].dst, arr[i].last = int(start), int(dst) if dst else None, int(last) if last else None
+            arr[i].div_total, arr[i].shift, arr[i].div_own = float(div_total), float(shift), float(div_own)
+            arr[i].dst_dtype, arr[i].last_dtype, arr[i].flags = int(dtype), int(last_dtype), int(flags)
+        self._check(self._lib.flashe_finish_layers_dev(self._h, self._ptr(inp), int(n), arr, len(rows), int(block), self._ptr(stats)))
+
     @staticmethod
     def _tensor_layers(layers):
         layers = list(layers)

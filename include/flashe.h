@@ -81,7 +81,9 @@ typedef struct flashe_ctx flashe_ctx;
  *      flashe_quantize_combine_cohort_dev / flashe_quantize_combine_cohort_u32_dev / flashe_quantize_batch_combine_cohort_dev (a
  *      precompute job's cohort online: C float models + C caller-held masks to C ciphertexts and their sum in one pass, no AES);
  *      flashe_quantize_encrypt_cohort_runs_dev / flashe_quantize_batch_encrypt_cohort_runs_dev (the cohort's chained launches for a round
- *      in which clients dropped out: any strictly ascending cipher indices) */
+ *      in which clients dropped out: any strictly ascending cipher indices); flashe_stage_row + flashe_stage_layers_dev and
+ *      flashe_finish_row + flashe_finish_layers_dev (the aggregator's degree scaling either side of the fused client step: the multiply
+ *      in the stage pass, the two divisions and the last round's model in the store + statistics pass) */
 #define FLASHE_ABI_VERSION 4
 int flashe_abi_version(void);
 int flashe_device_count(int *count);
@@ -787,6 +789,67 @@ int flashe_quantize_batch_tensors_dev(flashe_ctx *ctx, const flashe_tensor_layer
  * (the deviations are taken from the correctly rounded S / n).  The table upload synchronises; the passes are asynchronous. */
 int flashe_store_layers_dev(flashe_ctx *ctx, const double *in_dev, uint64_t n, const flashe_tensor_layer *layers, int n_layers, uint64_t block,
                             double *stats_dev);
+/* The rows and flags of flashe_stage_layers_dev (new). */
+#define FLASHE_STAGE_SCALE 1
+#define FLASHE_STAGE_SCALE_WIDE 2
+#define FLASHE_STAGE_SHIFT 4
+#define FLASHE_STAGE_SHIFT_WIDE 8
+#define FLASHE_STAGE_OUT_F64 16
+typedef struct flashe_stage_row {
+    const void *src;       /* the layer's values as stored */
+    void *dst;             /* size float32 values, or float64 values with OUT_F64 */
+    uint64_t size;
+    double scale;          /* with SCALE: the degree */
+    double shift;          /* with SHIFT: -mean */
+    int32_t src_dtype;     /* F32 0, F64 1, F16 2, BF16 3 */
+    int32_t flags;
+} flashe_stage_row;
+/* The aggregator's degree scaling in front of the step (new), jzf_aggregator.py:676 (`weights *= degree`, a client's model weighted by its
+ * sample count) followed by jzf_quantize.py:542-547 (normalize): ONE streaming pass over n_rows rows (HOST array), each `size` values from
+ * src (stored as src_dtype, FLASHE_TENSOR_*) to dst, a buffer of the caller's -- the rows of one model, or the C x L layers of a cohort
+ * with a scale per client.  Per value, in the type NumPy gives the layer at each step: a 16-bit value is upcast to float32 exactly;
+ * FLASHE_STAGE_SCALE multiplies by `scale` -- a float64 value in float64, a float32 value by (float)scale in float32 (a Python number,
+ * an np.float32) or, with FLASHE_STAGE_SCALE_WIDE (an np.float64 degree), as (double)x * scale, the value being float64 from there on;
+ * FLASHE_STAGE_SHIFT adds `shift` to whatever the value now is, FLASHE_STAGE_SHIFT_WIDE as FLASHE_TENSOR_SHIFT_WIDE on a float32 value;
+ * the store is float32, or float64 with FLASHE_STAGE_OUT_F64 (an exact widening of a float32 value).  Nothing is contracted into an FMA.
+ * Without SCALE the bytes are those of the stage pass of flashe_quantize_encrypt_tensors_dev.  dst then goes to the *_tensors_dev /
+ * *_cohort_dev entry points as a plain F32 / F64 layer without SHIFT.
+ * FLASHE_EINVAL before anything is launched: a null or misaligned pointer (to the element size) of a non-empty row, an unknown dtype or
+ * flag, SCALE_WIDE without SCALE, SHIFT_WIDE without SHIFT, a WIDE flag on a float64 source or SHIFT_WIDE behind SCALE_WIDE (the value
+ * is float64 already), SCALE_WIDE or a float64 source without OUT_F64, a scale that is zero or not finite, a shift that is not finite,
+ * a call inside a graph capture.  The table upload synchronises; the pass is asynchronous. */
+int flashe_stage_layers_dev(flashe_ctx *ctx, const flashe_stage_row *rows, int n_rows);
+/* The rows and flags of flashe_finish_layers_dev (new). */
+#define FLASHE_FINISH_DIV_TOTAL 1
+#define FLASHE_FINISH_SHIFT 2
+#define FLASHE_FINISH_DIV_OWN 4
+#define FLASHE_FINISH_ADD_LAST 8
+typedef struct flashe_finish_row {
+    uint64_t start;        /* flat index of the row's first value */
+    void *dst;
+    const void *last;      /* with ADD_LAST */
+    double div_total, shift, div_own;
+    int32_t dst_dtype, last_dtype;   /* F32 0, F64 1, F16 2, BF16 3 */
+    int32_t flags;
+    int32_t reserved;      /* 0 */
+} flashe_finish_row;
+/* The aggregator's degree scaling behind the step (new), jzf_aggregator.py:902-907 around jzf_quantize.py:549-564 (unnormalize):
+ * flashe_store_layers_dev with the two divisions and the last round's model.  Row r (HOST array, ascending start, the last row ends at n)
+ * holds flat values [start, next start) of in_dev; per value, in float64 and under the row's flags,
+ *   y1 = in / div_total   (FLASHE_FINISH_DIV_TOTAL; :902, div_total = degrees / self.degree computed by the caller as the reference does)
+ *   y2 = y1 + shift       (FLASHE_FINISH_SHIFT;     :904, unnormalize's += mean)
+ *   y3 = y2 / div_own     (FLASHE_FINISH_DIV_OWN;   :905)
+ *   y4 = (double)last[k] + y3   (FLASHE_FINISH_ADD_LAST; :907, last stored as last_dtype and upcast exactly)
+ * stored in dst as dst_dtype (float64 -> float32 -> 16 bits, round to nearest even).  Both divisions are correctly rounded divisions,
+ * neither merged nor turned into a multiplication, and nothing is contracted into an FMA.  stats_dev / block: as flashe_store_layers_dev,
+ * over y2 (what unnormalize records, :904) and per row index.  last == dst with equal dtypes updates the model in place.  With no
+ * flag but SHIFT the bytes are flashe_store_layers_dev's.
+ * FLASHE_EINVAL before anything is launched: a null or misaligned in_dev / stats_dev, a null or misaligned dst (or last with ADD_LAST)
+ * of a non-empty row, an unknown dtype or flag, a non-zero reserved field, a divisor that is zero or not finite, a shift that is not
+ * finite, starts that do not ascend from 0 or leave n, a `last` that overlaps any row's dst other than as its own row's dst with the
+ * same dtype, a block outside [1, 16384] with stats_dev, a call inside a graph capture.  The table uploads synchronise. */
+int flashe_finish_layers_dev(flashe_ctx *ctx, const double *in_dev, uint64_t n, const flashe_finish_row *rows, int n_rows, uint64_t block,
+                             double *stats_dev);
 
 /* The model-wide codec with the ctx's PRECOMPUTED masks (new): the client step of a job with precompute enabled (jzf_flashe.py:456-488,
  * :537-582 once prepare_encrypt / prepare_decrypt, :599-666, filled the caches) -- the codec of the calls above and the combine of
