@@ -22,7 +22,9 @@ which this example checks.
                (quantize_encrypt(rng=[...])): counter-based Philox generators, whose draws for the whole cohort are ONE asynchronous
                launch on the device (models of 65,536 values or more: this example's hold 126,666) and whose advanced states come back
                -- the sequential clients below draw from identically seeded generators and must leave them in the same place;
-               --rng pcg64 takes any other Generator: the same call, drawn on the host"""
+               --rng pcg64 takes np.random.default_rng(seed) itself (PCG64, a 128-bit LCG): every lane of ONE launch jumps to its first
+               draw and walks a fixed stride, and the states come back the same way; --rng sfc64 takes any other Generator: the same
+               call, drawn on the host"""
 import argparse
 import os
 import sys
@@ -60,7 +62,7 @@ def main():
     ap.add_argument("--batch", action="store_true")
     ap.add_argument("--precompute", action="store_true")
     ap.add_argument("--drop", default="", help="comma-separated clients that miss the round, e.g. 2,7")
-    ap.add_argument("--rng", choices=["philox", "pcg64"], default=None, help="draw from one np.random.Generator per client")
+    ap.add_argument("--rng", choices=["philox", "pcg64", "sfc64"], default=None, help="draw from one np.random.Generator per client")
     opt = ap.parse_args()
     cm.N_JOBS = 16                                           # every party must use the same value
     C, key = 10, bytes(range(32))
@@ -80,7 +82,9 @@ def main():
         """One Generator per present client, seeded alike on both sides (None: NumPy's global stream, seeded below)."""
         if opt.rng is None:
             return None
-        bitgen = np.random.Philox if opt.rng == "philox" else np.random.PCG64
+        if opt.rng == "pcg64":
+            return [np.random.default_rng(1000 + c) for c in present]
+        bitgen = np.random.Philox if opt.rng == "philox" else np.random.SFC64
         return [np.random.Generator(bitgen(1000 + c)) for c in present]
 
     cohort = FlasheCohort(args, first_idx=0, n_local=C, num_clients=C, prp_seed=key, compact=opt.compact)

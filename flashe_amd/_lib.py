@@ -58,6 +58,12 @@ class PhiloxSegment(ctypes.Structure):
                 ("reserved", ctypes.c_uint32), ("n", ctypes.c_uint64), ("offset", ctypes.c_uint64)]
 
 
+class Pcg64Segment(ctypes.Structure):
+    """flashe_pcg64_segment of include/flashe.h."""
+    _fields_ = [("state", ctypes.c_uint64 * 2), ("inc", ctypes.c_uint64 * 2), ("variant", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("n", ctypes.c_uint64), ("offset", ctypes.c_uint64)]
+
+
 class StageRow(ctypes.Structure):
     """flashe_stage_row of include/flashe.h."""
     _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("size", ctypes.c_uint64), ("scale", ctypes.c_double),
@@ -253,6 +259,9 @@ _SIGNATURES = {
     "flashe_philox_block": (c_int, [c_u64p, c_u64p, c_u64p]),
     "flashe_philox_advance": (c_int, [c_u64p, c_u64p, c_u32p, c_u64p, c_u64]),
     "flashe_philox_grid": (c_int, [c_vp, c_u64, c_u32, c_u32p, c_u64p]),
+    "flashe_pcg64_random_dev": (c_int, [c_vp, ctypes.POINTER(Pcg64Segment), c_int, c_vp]),
+    "flashe_pcg64_advance": (c_int, [c_u32, c_u64p, c_u64p, c_u64p]),
+    "flashe_pcg64_grid": (c_int, [c_vp, c_u64, c_u32p, c_u64p, c_u32p]),
     "flashe_quantize_dev": (c_int, [c_vp, c_u64, c_vp, c_int, ctypes.c_double, c_int, c_vp, c_vp]),
     "flashe_quantize": (c_int, [c_vp, c_u64, c_vp, c_int, ctypes.c_double, c_int, c_vp, c_vp]),
     "flashe_unquantize_dev": (c_int, [c_vp, c_u64, c_vp, c_int, ctypes.c_double, c_int, c_int, c_vp]),

@@ -249,9 +249,10 @@ def _draws_on_device(count):
 def _draws(eng, count, rng=None):
     """The next `count` stochastic-rounding draws of NumPy's global stream as a device buffer: generated on the device
     (_draws_on_device), else drawn on the host and uploaded.  rng (a Generator): its next `count` draws instead -- on the device under
-    _rng_on_device (Philox), else rng.random(count) uploaded."""
+    _rng_on_device (Philox, PCG64, PCG64DXSM), else rng.random(count) uploaded."""
     if rng is not None:
-        return eng.philox_random_dev([rng], [count]) if _rng_on_device(eng, rng, count) else eng.upload(rng.random(count))
+        call = _rng_on_device(eng, rng, count)
+        return getattr(eng, call)([rng], [count]) if call else eng.upload(rng.random(count))
     return eng.numpy_random_dev(count) if _draws_on_device(count) else eng.upload(np.random.random(count))
 
 
@@ -272,20 +273,29 @@ def _client_rng(rng, ci):
     return rng[ci] if isinstance(rng, list) else rng
 
 
+_DRAW_CALL_SEGMENTS = {"philox_random_dev": "PHILOX_MAX_SEGMENTS", "pcg64_random_dev": "PCG64_MAX_SEGMENTS"}    # the segments a call holds
+
+
 def _cohort_rng_draws(eng, C, per_client, rng):
     """_cohort_draws from the caller's generators: one Generator gives ONE stretch of C per_client draws, a list client c's stretch from
-    rng[c].  Every stretch that runs on the device (_rng_on_device) is a segment of ONE launch whatever C is; the others are
-    rng.random(...) on the host, uploaded in runs of at most _RNG_RUN_MAX draws."""
+    rng[c].  The stretches that run on the device (_rng_on_device) are grouped by the call that takes them: every kind -- Philox, the
+    PCG64 family -- is ONE launch of a segment per stretch whatever C is; the others are rng.random(...) on the host, uploaded in runs
+    of at most _RNG_RUN_MAX draws."""
     du = eng.alloc(max(8 * C * per_client, 16))
     stretches = [(rng[ci], ci * per_client, per_client) for ci in range(C)] if isinstance(rng, list) else [(rng, 0, C * per_client)]
-    dev = [st for st in stretches if _rng_on_device(eng, st[0], st[2])]
+    dev = {}                                          # the device call -> its stretches
     for g, first, count in stretches:
-        if not _rng_on_device(eng, g, count):
-            for at in range(first, first + count, _RNG_RUN_MAX):
-                du.upload_at(8 * at, g.random(min(_RNG_RUN_MAX, first + count - at)))
-    for at in range(0, len(dev), eng.PHILOX_MAX_SEGMENTS if dev else 1):              # (a cohort holds at most 128 clients: one launch)
-        part = dev[at:at + eng.PHILOX_MAX_SEGMENTS]
-        eng.philox_random_dev([g for g, _f, _c in part], [c for _g, _f, c in part], out=du, offsets=[f for _g, f, _c in part])
+        call = _rng_on_device(eng, g, count)
+        if call:
+            dev.setdefault(call, []).append((g, first, count))
+            continue
+        for at in range(first, first + count, _RNG_RUN_MAX):
+            du.upload_at(8 * at, g.random(min(_RNG_RUN_MAX, first + count - at)))
+    for call, mine in dev.items():
+        most = getattr(eng, _DRAW_CALL_SEGMENTS[call])
+        for at in range(0, len(mine), most):                                            # (a cohort holds at most 128 clients: one launch)
+            part = mine[at:at + most]
+            getattr(eng, call)([g for g, _f, _c in part], [c for _g, _f, c in part], out=du, offsets=[f for _g, f, _c in part])
     return du
 
 
@@ -494,9 +504,9 @@ class FlasheClient(object):
 
         rng (new): a np.random.Generator the stochastic-rounding draws come from -- the result is that of the same call with every
         np.random.random(k) replaced by rng.random(k), the sparse job's 'zzz' draw included (the next draw of the same generator); NumPy's
-        global stream is neither read nor advanced.  Over np.random.Philox, stretches of DEVICE_RNG_MIN draws or more are generated on
-        the device (flashe_philox_random_dev) and the advanced state is put back into the generator; any other generator draws on the
-        host.  Anything that is not a Generator: TypeError, before anything is touched.
+        global stream is neither read nor advanced.  Over np.random.Philox, np.random.PCG64 (np.random.default_rng) or
+        np.random.PCG64DXSM, stretches of DEVICE_RNG_MIN draws or more are generated on the device (flashe_philox_random_dev,
+        flashe_pcg64_random_dev) and the advanced state is put back into the generator; any other generator draws on the host.  Anything that is not a Generator: TypeError, before anything is touched.
 
         normalize (new): QuantizingClient.normalize first (`-= past_layer_mean_list[i]`, jzf_quantize.py:542-547).  Layers may also be
         a framework's float DEVICE tensors (float32 / float64 / float16 / bfloat16, DLPack or __cuda_array_interface__), mixed with host
@@ -1442,9 +1452,9 @@ class FlasheCohort(object):
         rng (new): the stochastic-rounding draws come from the caller's own np.random.Generator(s) -- ONE Generator: the (present) clients
         draw one after the other from it, as seeds=None does with the global stream; a list of one Generator per (present) client: client c
         draws from rng[c], as seeds=[...] does.  The result is that of the same call with every np.random.random(k) replaced by the
-        generator's .random(k), on every path; NumPy's global stream is neither read nor advanced.  Generators over np.random.Philox with
-        DEVICE_RNG_MIN draws or more generate on the device, the whole cohort in ONE asynchronous launch whatever C is
-        (flashe_philox_random_dev), and get their advanced states back; others draw on the host.  rng with seeds, a list of another length:
+        generator's .random(k), on every path; NumPy's global stream is neither read nor advanced.  Generators over np.random.Philox,
+        np.random.PCG64 (np.random.default_rng) or np.random.PCG64DXSM with DEVICE_RNG_MIN draws or more generate on the device, the
+        whole cohort in ONE asynchronous launch per kind whatever C is (flashe_philox_random_dev, flashe_pcg64_random_dev), and get their advanced states back; others draw on the host.  rng with seeds, a list of another length:
         ValueError; anything that is not a Generator: TypeError -- before anything is touched.
 
         One Weights per client (host arrays and / or framework float device tensors, as FlasheClient.quantize_encrypt takes them) ->
@@ -2086,7 +2096,7 @@ class FlasheSparseCohort(object):
     def quantize_encrypt(self, normalize=False, seeds=None, compact=None, rng=None):
         """rng (new): the draws come from the caller's np.random.Generator (one: the clients draw one after the other, K + 1 each, the last
         one a client's 'zzz' draw) or a list of one Generator per client, as FlasheCohort.quantize_encrypt takes them: np.random.random(k)
-        replaced by the generator's .random(k) on every path, the global stream untouched, Philox generators on the device in ONE launch.
+        replaced by the generator's .random(k) on every path, the global stream untouched, Philox and PCG64-family generators on the device in ONE launch per kind.
         rng with seeds or a list of another length: ValueError; not a Generator: TypeError.
 
         -> SparseCohortUpload.  Client c's upload is its own FlasheClient.quantize_encrypt(compact_c + 'zzz', device=True,

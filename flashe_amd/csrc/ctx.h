@@ -30,6 +30,7 @@ struct flashe_ctx {
     Buf bounds;       // span reduce: first entry of every client in every span
     Buf mt_ws;        // flashe_mt19937_random_dev: state in / out and the substream windows
     Buf philox_tab;   // flashe_philox_random_dev: the plan table of a launch of more segments than its kernel arguments hold
+    Buf pcg64_tab;    // flashe_pcg64_random_dev: the same
     Buf codec_tab;    // layer table of the fused quantise / unquantise over a flattened model
     Buf tensor_ws;    // caller tensors: the front end's converted layers (flashe_quantize_*_tensors_dev)
     Buf tensor_tab;   // caller tensors: stage / store table

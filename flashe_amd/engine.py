@@ -1414,6 +1414,74 @@ class Engine:
         self._check(self._lib.flashe_philox_grid(self._h, int(n), int(buffer_pos), ctypes.byref(wg), ctypes.byref(tiles)))
         return int(wg.value), int(tiles.value)
 
+    PCG64_MAX_SEGMENTS = 128         # the segments one flashe_pcg64_random_dev call holds
+    PCG64_STRETCH = 16               # the draws a lane of its launch walks, at a stride of the workgroup's 256 lanes
+    _PCG64_VARIANTS = {"PCG64": 0, "PCG64DXSM": 1}
+
+    @classmethod
+    def _pcg64_segment(cls, state, n, offset):
+        """A PCG64 / PCG64DXSM bit generator's state dict as the flashe_pcg64_segment that draws n values to draw `offset` of the output."""
+        variant = cls._PCG64_VARIANTS.get(state.get("bit_generator"))
+        if variant is None:
+            raise FlasheError(-22, f"the bit generator is {state.get('bit_generator')}, not PCG64 or PCG64DXSM")
+        if not (0 <= int(n) < 1 << 64 and 0 <= int(offset) < 1 << 64):
+            raise FlasheError(-22, "a segment's n or offset overflows")
+        seg, m64 = _lib.Pcg64Segment(), (1 << 64) - 1
+        for words, v in ((seg.state, int(state["state"]["state"])), (seg.inc, int(state["state"]["inc"]))):
+            if not 0 <= v < 1 << 128:
+                raise FlasheError(-22, "a PCG64 state or inc outside 128 bits")
+            words[:] = [v & m64, v >> 64]
+        seg.variant, seg.n, seg.offset = variant, int(n), int(offset)
+        return seg
+
+    def pcg64_random_dev(self, generators_or_states, counts, out=None, offsets=None):
+        """Generator(np.random.PCG64(...)).random(n) -- the generator np.random.default_rng returns -- and Generator(np.random.PCG64DXSM(...))
+        .random(n) generated on the device, bit for bit, for every entry of `generators_or_states` in ONE asynchronous call (one launch per
+        variant present): entry s gives counts[s] draws to draws [offsets[s], offsets[s] + counts[s]) of `out` (a DeviceBuffer or a device
+        address of float64, 8-byte aligned; default: the entries back to back in a new buffer).  An entry is a np.random.Generator over
+        PCG64 or PCG64DXSM -- its bit_generator.state is read and the advanced state put back with has_uint32 / uinteger as they were, so
+        host draws before and after continue one stream -- or such a state dict, advanced in place.  The same Generator may appear several
+        times: its segments continue one another in list order, as sequential host draws would.  Returns the buffer.  Raises for another
+        bit generator, overlapping ranges, a misaligned output or more than PCG64_MAX_SEGMENTS entries; nothing is advanced then."""
+        counts = [int(c) for c in counts]
+        if len(counts) != len(generators_or_states):
+            raise ValueError(f"{len(generators_or_states)} generators, {len(counts)} counts")
+        if offsets is None:
+            offsets = [sum(counts[:s]) for s in range(len(counts))]
+        if len(offsets) != len(counts):
+            raise ValueError(f"{len(counts)} counts, {len(offsets)} offsets")
+        if len(counts) > self.PCG64_MAX_SEGMENTS:
+            raise ValueError(f"{len(counts)} segments: one launch holds {self.PCG64_MAX_SEGMENTS}")
+        segs = (_lib.Pcg64Segment * max(len(counts), 1))()
+        last = {}                         # id(entry) -> its latest segment: where a repeated entry continues, and what is handed back
+        states = {}
+        for s, (g, n, off) in enumerate(zip(generators_or_states, counts, offsets)):
+            if id(g) in last:
+                prev = last[id(g)]
+                seg = _lib.Pcg64Segment.from_buffer_copy(prev)
+                self._check(self._lib.flashe_pcg64_advance(seg.variant, seg.state, seg.inc, (c_u64 * 2)(prev.n, 0)))
+                seg.n, seg.offset = n, int(off)
+            else:
+                states[id(g)] = (g, g.bit_generator.state if isinstance(g, np.random.Generator) else g)
+                seg = self._pcg64_segment(states[id(g)][1], n, off)
+            segs[s] = seg
+            last[id(g)] = segs[s]
+        if out is None:
+            out = self.alloc(max(8 * max([o + n for o, n in zip(offsets, counts)], default=0), 16))
+        self._check(self._lib.flashe_pcg64_random_dev(self._h, segs, len(counts), self._ptr(out)))
+        for key, (g, state) in states.items():
+            state["state"]["state"] = int(last[key].state[0]) | (int(last[key].state[1]) << 64)
+            if isinstance(g, np.random.Generator):
+                g.bit_generator.state = state
+        return out
+
+    def pcg64_grid(self, n):
+        """(workgroups, tiles, draws per tile) of the launch pcg64_random_dev makes for one segment of n draws: more tiles than workgroups are
+        further trips of a workgroup's loop."""
+        wg, tiles, draws = c_u32(0), c_u64(0), c_u32(0)
+        self._check(self._lib.flashe_pcg64_grid(self._h, int(n), ctypes.byref(wg), ctypes.byref(tiles), ctypes.byref(draws)))
+        return int(wg.value), int(tiles.value), int(draws.value)
+
     def quantize_encrypt_dev(self, it, idx, scheme, n, n_jobs, x, x_is_f64, alpha, element_bits, u, ct):
         """ct = encrypt(quantize(x)) in one launch (un-batched values); x float32 / float64, u float64 uniforms, all device-resident."""
         self._check(self._lib.flashe_quantize_encrypt_dev(self._h, it, idx, scheme, n, n_jobs, self._ptr(x), 1 if x_is_f64 else 0,

@@ -14,7 +14,9 @@ off).  Pass ``uniforms=`` to supply the draws yourself, or ``rng=`` (a ``np.rand
 generator of your own: the result is that of the same call with every ``np.random.random(k)`` replaced by
 ``rng.random(k)``, and NumPy's global stream is neither read nor advanced.  A Generator over ``np.random.Philox``
 generates DEVICE_RNG_MIN draws or more on the device (`flashe_philox_random_dev`: counter based, any number of
-streams in one launch, no synchronisation; the advanced state is handed back to the generator); any other
+streams in one launch, no synchronisation; the advanced state is handed back to the generator), and so does one
+over ``np.random.PCG64`` -- what ``np.random.default_rng`` returns -- or ``np.random.PCG64DXSM`` (`flashe_pcg64_random_dev`:
+every lane jumps to its first draw and walks a fixed stride of the 128-bit LCG); any other
 generator, or a shorter stretch, draws ``rng.random(k)`` on the host and ships the numbers -- the same bits.
 """
 import os
@@ -55,10 +57,16 @@ def _check_rng(rng, n_clients=None):
 
 
 def _rng_on_device(eng, rng, count):
-    """Does a stretch of `count` draws of the Generator rng run on the device?  FLASHE_DEVICE_RNG not 0, DEVICE_RNG_MIN draws or more, and
-    its bit generator is Philox (the counter-based stream flashe_philox_random_dev reproduces)."""
-    return (os.environ.get("FLASHE_DEVICE_RNG", "1") != "0" and count >= DEVICE_RNG_MIN and isinstance(rng.bit_generator, np.random.Philox)
-            and hasattr(eng, "philox_random_dev"))
+    """Which device call takes a stretch of `count` draws of the Generator rng: the name of the engine's method -- "philox_random_dev" over
+    np.random.Philox (the counter-based stream flashe_philox_random_dev reproduces), "pcg64_random_dev" over np.random.PCG64 (what
+    np.random.default_rng returns) or np.random.PCG64DXSM (the LCG streams flashe_pcg64_random_dev jumps through) -- or None: the stretch
+    draws on the host.  On the device: FLASHE_DEVICE_RNG not 0, DEVICE_RNG_MIN draws or more, and an engine that has the call."""
+    if os.environ.get("FLASHE_DEVICE_RNG", "1") == "0" or count < DEVICE_RNG_MIN:
+        return None
+    bitgen = rng.bit_generator
+    call = ("philox_random_dev" if isinstance(bitgen, np.random.Philox) else
+            "pcg64_random_dev" if isinstance(bitgen, (np.random.PCG64, np.random.PCG64DXSM)) else None)
+    return call if call is not None and hasattr(eng, call) else None
 
 
 def _static_quantize_padding_asymmetric(value, alpha, int_bits, uniforms=None, device=0, as_object=True, rng=None):
@@ -71,12 +79,13 @@ def _static_quantize_padding_asymmetric(value, alpha, int_bits, uniforms=None, d
     eng = _engine(64, device)
     n = int(value.size)
     if rng is not None:
-        if _rng_on_device(eng, rng, n):
+        call = _rng_on_device(eng, rng, n)
+        if call:
             x = np.ascontiguousarray(value).reshape(-1)
             if x.dtype not in (np.float32, np.float64):
                 x = x.astype(np.float64)
             dx, dq = eng.upload(x), eng.alloc(8 * n)
-            du = eng.philox_random_dev([rng], [n])
+            du = getattr(eng, call)([rng], [n])
             eng.quantize_dev(n, dx, x.dtype == np.float64, alpha, int_bits, du, dq)
             q = dq.download(np.uint64, n).reshape(shape)
         else:

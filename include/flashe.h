@@ -929,6 +929,36 @@ int flashe_philox_advance(const uint64_t key[2], uint64_t counter[4], uint32_t *
  * 256 blocks (1,024 draws) and its workgroups (at most 8 per compute unit the ctx may use; more tiles than that are further trips). */
 int flashe_philox_grid(flashe_ctx *ctx, uint64_t n, uint32_t buffer_pos, uint32_t *workgroups, uint64_t *tiles);
 
+/* Generator(np.random.PCG64(...)).random(n) and Generator(np.random.PCG64DXSM(...)).random(n) ON THE DEVICE, bit for bit (new): the draws
+ * of the generator np.random.default_rng returns.  Both are the 128-bit LCG state' = A state + inc mod 2^128 with a 64-bit output function:
+ * PCG64 (variant 0), A = 0x2360ED051FC65DA44385DF649FCCF645, steps first and outputs rotr64(hi ^ lo, state >> 122) of the NEW state;
+ * PCG64DXSM (variant 1), A = 0xDA942042E4DD58B5, outputs from the OLD state (lo |= 1; hi ^= hi >> 32; hi *= A; hi ^= hi >> 48; hi *= lo)
+ * and then steps; draw = (word >> 11) * 2^-53.  k steps are one affine map that does not depend on the generator, so a lane jumps once to
+ * its first draw and walks a fixed stride.  A segment is one generator state (state and inc exactly as Generator.bit_generator.state holds
+ * them, as two 64-bit words each, low word first; any 128-bit values, an even inc included) and the n draws it gives to draws
+ * [offset, offset + n) of u_dev, which need only be 8-byte aligned; bytes outside the ranges are not written.  ONE launch per variant on
+ * the ctx stream fills up to 128 segments (the clients of a cohort) and does not synchronise; every segment's state is advanced in place
+ * on the host (what NumPy's own state is after n draws; has_uint32 / uinteger are no part of it: random() leaves them alone, and so must
+ * the caller -- bit_generator.advance would reset them), so the caller can put it back into bit_generator.state and host draws continue the
+ * stream.  FLASHE_EINVAL, and nothing advanced or written: a variant above 1, more than 128 segments, an n or offset + n above 2^60,
+ * overlapping output ranges, a misaligned u_dev, a graph being captured. */
+typedef struct flashe_pcg64_segment {
+    uint64_t state[2];       /* in / out: low word, high word */
+    uint64_t inc[2];
+    uint32_t variant;        /* 0: PCG64, 1: PCG64DXSM */
+    uint32_t reserved;
+    uint64_t n;              /* draws */
+    uint64_t offset;         /* in draws into u_dev */
+} flashe_pcg64_segment;
+int flashe_pcg64_random_dev(flashe_ctx *ctx, flashe_pcg64_segment *segments, int n_segments, double *u_dev);
+/* Host only (new): the state (in place) of a PCG64 / PCG64DXSM bit generator n steps on -- n draws of Generator.random -- for any n below
+ * 2^128 (two words, low first), by doubling: at most 128 rounds. */
+int flashe_pcg64_advance(uint32_t variant, uint64_t state[2], const uint64_t inc[2], const uint64_t n[2]);
+/* Host only (new): the grid flashe_pcg64_random_dev launches for one segment of n draws -- its tiles of *tile_draws (may be NULL) = 4,096
+ * draws, 16 per lane at a stride of 256, and its workgroups (at most 8 per compute unit the ctx may use; more tiles than that are further
+ * trips). */
+int flashe_pcg64_grid(flashe_ctx *ctx, uint64_t n, uint32_t *workgroups, uint64_t *tiles, uint32_t *tile_draws);
+
 /* _static_quantize_padding_asymmetric -- federatedml/secureprotol/jzf_quantize.py:55-67:
  * q = floor(clip(x, -alpha, alpha) + alpha) * (2^element_bits - 1) / (2 alpha) + u), with numpy's
  * dtype rules (x_is_f64 == 0: x is float32 and every step before "+ u" is a float32 operation).
