@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib, interop
 from .cipher import FlasheCipher, _CtxMask
-from .quantize import ACIQ, QuantizingClient, _check_rng, _loop_dtype, _rng_on_device
+from .quantize import ACIQ, QuantizingClient, _check_rng, _global_on_device, _loop_dtype, _rng_on_device
 
 _RNG_RUN_MAX = 1 << 26          # draws per device call of quantize_encrypt (512 MiB of float64)
 
@@ -239,21 +239,14 @@ def _size(shape):
     return int(math.prod(shape))
 
 
-def _draws_on_device(count):
-    """Does a call for `count` draws of NumPy's global stream generate them on the device?  FLASHE_DEVICE_RNG not 0, DEVICE_RNG_MIN draws
-    or more, and the stream is MT19937 (the generator the device call continues and jumps ahead)."""
-    from .quantize import DEVICE_RNG_MIN
-    return os.environ.get("FLASHE_DEVICE_RNG", "1") != "0" and count >= DEVICE_RNG_MIN and np.random.get_state()[0] == "MT19937"
-
-
 def _draws(eng, count, rng=None):
     """The next `count` stochastic-rounding draws of NumPy's global stream as a device buffer: generated on the device
-    (_draws_on_device), else drawn on the host and uploaded.  rng (a Generator): its next `count` draws instead -- on the device under
+    (_global_on_device), else drawn on the host and uploaded.  rng (a Generator): its next `count` draws instead -- on the device under
     _rng_on_device (Philox, PCG64, PCG64DXSM), else rng.random(count) uploaded."""
     if rng is not None:
         call = _rng_on_device(eng, rng, count)
         return getattr(eng, call)([rng], [count]) if call else eng.upload(rng.random(count))
-    return eng.numpy_random_dev(count) if _draws_on_device(count) else eng.upload(np.random.random(count))
+    return eng.numpy_random_dev(count) if _global_on_device(eng, count) else eng.upload(np.random.random(count))
 
 
 def _skip_draws(count, rng=None):
@@ -303,7 +296,7 @@ def _cohort_draws(eng, C, per_client, seeds, rng=None):
     """The stochastic-rounding draws of C clients, client-major, as a device buffer: client c's are draws [c per_client, (c + 1) per_client).
     From the global stream (seeds=None) they are ONE stretch of C per_client draws -- the clients draw one after the other -- generated in
     device calls of at most _RNG_RUN_MAX draws whatever client they belong to (the jump-ahead of a device call is paid per call, not per
-    client); with seeds every client's stretch starts at its own seed.  On the device under quantize_encrypt's rule (_draws_on_device, per
+    client); with seeds every client's stretch starts at its own seed.  On the device under quantize_encrypt's rule (_global_on_device, per
     call), else drawn on the host and uploaded.  rng: the caller's generators instead (_cohort_rng_draws)."""
     if rng is not None:
         return _cohort_rng_draws(eng, C, per_client, rng)
@@ -313,7 +306,7 @@ def _cohort_draws(eng, C, per_client, seeds, rng=None):
             np.random.seed(seed)
         for at in range(first, first + count, _RNG_RUN_MAX):
             tot = min(_RNG_RUN_MAX, first + count - at)
-            if _draws_on_device(tot):
+            if _global_on_device(eng, tot):
                 eng.numpy_random_dev(tot, out=du.ptr + 8 * at)
             else:
                 du.upload_at(8 * at, np.random.random(tot))

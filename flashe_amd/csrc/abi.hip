@@ -446,7 +446,7 @@ int flashe_ctx_destroy(flashe_ctx *ctx)
     if (!ctx) return FLASHE_EINVAL;
     (void)hipSetDevice(ctx->device);
     if (ctx->env.stream) (void)hipStreamSynchronize(ctx->env.stream);
-    for (flashe_ctx::Buf *b : {&ctx->summaries, &ctx->stream_tmp, &ctx->acc_tmp[0], &ctx->acc_tmp[1], &ctx->sp_ws, &ctx->bounds, &ctx->mt_ws, &ctx->philox_tab, &ctx->pcg64_tab, &ctx->codec_tab, &ctx->prep_enc.add,
+    for (flashe_ctx::Buf *b : {&ctx->summaries, &ctx->stream_tmp, &ctx->acc_tmp[0], &ctx->acc_tmp[1], &ctx->sp_ws, &ctx->bounds, &ctx->mt_ws, &ctx->draw_tab, &ctx->codec_tab, &ctx->prep_enc.add,
                                &ctx->prep_enc.minus, &ctx->prep_dec.add, &ctx->prep_dec.minus, &ctx->chain_dmask.d, &ctx->tensor_ws, &ctx->tensor_tab,
                                &ctx->stat_ws})
         if (b->p) (void)hipFree(b->p);

@@ -1,5 +1,5 @@
-// Private to the host side of libflashe_hip.so (abi.hip, abi_layers.hip, host_twins.hip, comm.hip): the context object behind the opaque flashe_ctx
-// of include/flashe.h, and the error-reporting and argument helpers the entry points share.
+// Private to the host side of libflashe_hip.so (abi.hip, abi_layers.hip, host_twins.hip, comm.hip, mt19937.hip and, through draw_launch.h, philox.hip
+// and pcg64.hip): the context object behind the opaque flashe_ctx of include/flashe.h, and the error-reporting and argument helpers the entry points share.
 #pragma once
 #include "flashe.h"
 #include "kernels.h"
@@ -29,8 +29,7 @@ struct flashe_ctx {
     Buf sp_ws;        // sparsifier workspace (select state, histogram, per-block counts)
     Buf bounds;       // span reduce: first entry of every client in every span
     Buf mt_ws;        // flashe_mt19937_random_dev: state in / out and the substream windows
-    Buf philox_tab;   // flashe_philox_random_dev: the plan table of a launch of more segments than its kernel arguments hold
-    Buf pcg64_tab;    // flashe_pcg64_random_dev: the same
+    Buf draw_tab;     // flashe_philox_random_dev, flashe_pcg64_random_dev: the plan table of a launch of more segments than its kernel arguments hold (one for both: draw_launch.h)
     Buf codec_tab;    // layer table of the fused quantise / unquantise over a flattened model
     Buf tensor_ws;    // caller tensors: the front end's converted layers (flashe_quantize_*_tensors_dev)
     Buf tensor_tab;   // caller tensors: stage / store table

@@ -9,26 +9,23 @@
 // jumps t draws on with one row of a 256-row table and walks 16 draws at a stride of 256, so that a wave's 64 stores are 512 contiguous
 // bytes; they are 8-byte non-temporal stores, which is all the alignment an output range has (a cohort's client stretch starts at any
 // draw).  Nothing outside [offset, offset + n) is written.  The variant is a template parameter: a table that holds both is two launches.
-// The plan table rides in the kernel-argument block up to kArgPlans segments and in a table of the ctx beyond that; the states are advanced
-// on the host (one jump per segment), so nothing is read back and the call does not synchronise.
-#include "ctx.h"
-#include "device_common.h"
+// The states are advanced on the host (one jump per segment), so nothing is read back and the call does not synchronise.
+//
+// Here: the tile body, the two kernels that call it, and the entry points.  pcg64_stream.h: the streams' arithmetic, the jump tables, the
+// segment checks and the plans (no HIP: run on the host under sanitizers).  draw_segments.h, draw_launch.h: what the launch of a plan table
+// shares with philox.hip -- the range checks and the tile search; where the table rides, the launch and the entry points' common checks.
+#include "draw_launch.h"
 #include "pcg64_stream.h"
-
-#include <vector>
-
-using flashe_host::fail;
 
 namespace {
 
+using flashe_draw::st_draw;
 using flashe_pcg64::Plan;
 using flashe_pcg64::u128;
 using flashe_pcg64::Variant;
-constexpr int kArgPlans = 48;                         // 48 x 80 bytes + the other arguments < the 4-KiB kernel-argument block
+using ArgPlans = flashe_draw::ArgPlans<Plan>;
 static_assert(sizeof(Plan) == 80, "the plan rows are 80 bytes");
 static_assert(flashe_pcg64::kLanes == flashe::kStreamThreads, "a tile is kStretch draws per thread of a stream workgroup");
-
-struct ArgPlans { Plan p[kArgPlans]; };
 
 // the jump tables of the two variants (pcg64_stream.h), built by the compiler
 alignas(32) __device__ const flashe_pcg64::Pow2Table kPow2[flashe_pcg64::kVariants] = {flashe_pcg64::make_pow2_table(flashe_pcg64::kPcg64),
@@ -36,22 +33,13 @@ alignas(32) __device__ const flashe_pcg64::Pow2Table kPow2[flashe_pcg64::kVarian
 alignas(32) __device__ const flashe_pcg64::LaneTable kLane[flashe_pcg64::kVariants] = {flashe_pcg64::make_lane_table(flashe_pcg64::kPcg64),
                                                                           flashe_pcg64::make_lane_table(flashe_pcg64::kDxsm)};
 
-// (the addresses are integers: said to be global memory, so that the stores are global_store and not flat_store -- FLASHE_GLOBAL)
-__device__ __forceinline__ void st_draw(uintptr_t at, double d) { __builtin_nontemporal_store(d, FLASHE_GLOBAL(double, at)); }
-
 template <Variant V>
 __device__ __forceinline__ void pcg64_tiles(const Plan *__restrict__ plans, int n_plans, uint64_t tiles, double *__restrict__ out)
 {
     using namespace flashe_pcg64;
     constexpr Jump kStride = from_row(make_pow2_table(V).row[kLanesLog2]);               // (A^256, G_256): the multiplier is a literal
     for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
-        // the segment of tile t: the last plan whose first tile is not above t
-        int lo = 0, hi = n_plans - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (plans[mid].tile_first <= t) lo = mid; else hi = mid - 1;
-        }
-        const Plan &p = plans[lo];
+        const Plan &p = flashe_draw::tile_plan(plans, n_plans, t);
         const uint64_t k = t - p.tile_first, i0 = k * kTileDraws + threadIdx.x, n = p.n;     // the lane's first draw of the segment
         if (i0 >= n) continue;
         const u128 inc = make128(p.inc[1], p.inc[0]), stride_add = make128(p.stride_add[1], p.stride_add[0]);
@@ -98,30 +86,16 @@ void to_segment(const flashe_pcg64_segment &s, flashe_pcg64::Segment &o)
     o.variant = s.variant; o.n = s.n; o.offset = s.offset;
 }
 
-// One variant's segments of the table: a launch of their tiles (none: nothing).  Rows [0, tab_first) of the ctx table are in use by the
-// launch of the other variant; *tab_used: the rows this one took.
+// One variant's segments of the table: a launch of their tiles (none: nothing).  Rows [0, *tab_rows) of the ctx table are in use by the
+// launch of the other variant; the rows this one takes are added.
 template <Variant V>
-int launch_variant(flashe_ctx *ctx, const std::vector<flashe_pcg64::Segment> &segs, size_t tab_first, size_t *tab_used, double *u_dev)
+int launch_variant(flashe_ctx *ctx, const std::vector<flashe_pcg64::Segment> &segs, size_t *tab_rows, double *u_dev)
 {
     std::vector<Plan> plans;
     const uint64_t tiles = flashe_pcg64::plan_segments(segs.data(), static_cast<int>(segs.size()), V, plans);
-    *tab_used = 0;
-    if (!tiles) return FLASHE_OK;
-    const int n_plans = static_cast<int>(plans.size());
-    const dim3 grid(flashe::stream_grid(ctx->env, tiles * flashe::kStreamThreads)), wg(flashe::kStreamThreads);
-    if (n_plans <= kArgPlans) {
-        ArgPlans tab{};
-        std::copy(plans.begin(), plans.end(), tab.p);
-        hipLaunchKernelGGL(pcg64_random_args_kernel<V>, grid, wg, 0, ctx->env.stream, tab, n_plans, tiles, u_dev);
-    } else {
-        // (pageable source: the copy has left `plans` when the call returns; stream order keeps an earlier launch's table intact)
-        Plan *tab = static_cast<Plan *>(ctx->pcg64_tab.p) + tab_first;
-        HIP_TRY(ctx, hipMemcpyAsync(tab, plans.data(), plans.size() * sizeof(Plan), hipMemcpyHostToDevice, ctx->env.stream));
-        hipLaunchKernelGGL(pcg64_random_table_kernel<V>, grid, wg, 0, ctx->env.stream, static_cast<const Plan *>(tab), n_plans, tiles, u_dev);
-        *tab_used = plans.size();
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    return FLASHE_OK;
+    const size_t first = *tab_rows;
+    if (plans.size() > static_cast<size_t>(flashe_draw::kArgPlans)) *tab_rows += plans.size();
+    return flashe_draw::launch_plans(ctx, plans, tiles, first, pcg64_random_args_kernel<V>, pcg64_random_table_kernel<V>, u_dev);
 }
 
 }  // namespace
@@ -146,31 +120,13 @@ extern "C" int flashe_pcg64_grid(flashe_ctx *ctx, uint64_t n, uint32_t *workgrou
 extern "C" int flashe_pcg64_random_dev(flashe_ctx *ctx, flashe_pcg64_segment *segments, int n_segments, double *u_dev)
 {
     CHECK_CTX(ctx);
-    if (n_segments < 0 || n_segments > flashe_pcg64::kMaxSegments)
-        return fail(ctx, FLASHE_EINVAL, "flashe_pcg64_random_dev: %d segments, a launch holds 0 .. %d", n_segments, flashe_pcg64::kMaxSegments);
-    if (n_segments && !segments) return fail(ctx, FLASHE_EINVAL, "flashe_pcg64_random_dev: no segment table");
-    if (ctx->capturing) return fail(ctx, FLASHE_EINVAL, "flashe_pcg64_random_dev advances the generator states it is given: a replay would repeat the draws");
-    std::vector<flashe_pcg64::Segment> segs(static_cast<size_t>(n_segments));
-    bool any = false;
-    for (int s = 0; s < n_segments; s++) {
-        to_segment(segments[s], segs[s]);
-        any = any || segs[s].n;
-    }
-    switch (flashe_pcg64::check_segments(segs.data(), n_segments)) {
-    case flashe_pcg64::kSegmentsOk: break;
-    case flashe_pcg64::kSegmentsBadVariant: return fail(ctx, FLASHE_EINVAL, "flashe_pcg64_random_dev: a variant that is neither PCG64 (0) nor PCG64DXSM (1)");
-    case flashe_pcg64::kSegmentsOverflow: return fail(ctx, FLASHE_EINVAL, "flashe_pcg64_random_dev: a segment's offset + n overflows");
-    case flashe_pcg64::kSegmentsOverlap: return fail(ctx, FLASHE_EINVAL, "flashe_pcg64_random_dev: two segments' output ranges overlap");
-    default: return fail(ctx, FLASHE_EINVAL, "flashe_pcg64_random_dev: bad segment table");
-    }
-    if (any) {
-        if (!u_dev || (reinterpret_cast<uintptr_t>(u_dev) & 7u)) return fail(ctx, FLASHE_EINVAL, "flashe_pcg64_random_dev: u_dev must be an 8-byte aligned device pointer");
-        if (n_segments > kArgPlans)
-            if (int rc = flashe_host::ensure(ctx, ctx->pcg64_tab, flashe_pcg64::kMaxSegments * sizeof(Plan))) return rc;
-        size_t used = 0, more = 0;
-        if (int rc = launch_variant<flashe_pcg64::kPcg64>(ctx, segs, 0, &used, u_dev)) return rc;
-        if (int rc = launch_variant<flashe_pcg64::kDxsm>(ctx, segs, used, &more, u_dev)) return rc;
-    }
+    std::vector<flashe_pcg64::Segment> segs;
+    if (int rc = flashe_draw::read_segments(ctx, "flashe_pcg64_random_dev", segments, n_segments, u_dev, to_segment, flashe_pcg64::check_segments,
+                                            "a variant that is neither PCG64 (0) nor PCG64DXSM (1)", segs))
+        return rc;
+    size_t tab_rows = 0;
+    if (int rc = launch_variant<flashe_pcg64::kPcg64>(ctx, segs, &tab_rows, u_dev)) return rc;
+    if (int rc = launch_variant<flashe_pcg64::kDxsm>(ctx, segs, &tab_rows, u_dev)) return rc;
     for (int s = 0; s < n_segments; s++) {
         const u128 a = flashe_pcg64::advance(static_cast<Variant>(segs[s].variant), segs[s].state, segs[s].inc, segs[s].n);
         segments[s].state[0] = flashe_pcg64::lo64(a); segments[s].state[1] = flashe_pcg64::hi64(a);

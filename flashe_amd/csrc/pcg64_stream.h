@@ -12,20 +12,11 @@
 // the variant only, not on the generator, and is found by doubling in at most 128 rounds.  With  origin = the state the FIRST draw outputs
 // from (the state stepped once for PCG64, the state itself for DXSM), draw i outputs from  A^i origin + G_i inc  for both variants.
 #pragma once
-#include <cstddef>
-#include <cstdint>
-#include <algorithm>
-#include <vector>
-
-#ifndef FLASHE_HD
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define FLASHE_HD __host__ __device__ __forceinline__
-#else
-#define FLASHE_HD inline
-#endif
-#endif
+#include "draw_segments.h"
 
 namespace flashe_pcg64 {
+
+using namespace flashe_draw;                         // kMaxSegments, kMaxDraws, to_double, SegmentsStatus and its values
 
 typedef unsigned __int128 u128;
 
@@ -33,8 +24,6 @@ enum Variant : uint32_t { kPcg64 = 0, kDxsm = 1, kVariants = 2 };
 
 constexpr uint64_t kMultHi = 0x2360ED051FC65DA4ull, kMultLo = 0x4385DF649FCCF645ull;   // PCG64's multiplier
 constexpr uint64_t kCheapMult = 0xDA942042E4DD58B5ull;                                   // PCG64DXSM's, and its output function's
-constexpr int kMaxSegments = 128;                   // the segments one launch holds
-constexpr uint64_t kMaxDraws = 1ull << 60;          // per segment, and offset + n: their byte counts stay inside 64 bits
 
 constexpr u128 make128(uint64_t hi, uint64_t lo) { return (static_cast<u128>(hi) << 64) | lo; }
 constexpr uint64_t lo64(u128 v) { return static_cast<uint64_t>(v); }
@@ -71,8 +60,6 @@ FLASHE_HD uint64_t output_dxsm(u128 state)
 
 template <Variant V> FLASHE_HD uint64_t output(u128 state) { return V == kPcg64 ? output_xsl_rr(state) : output_dxsm(state); }
 
-FLASHE_HD double to_double(uint64_t word) { return static_cast<double>(word >> 11) * (1.0 / 9007199254740992.0); }
-
 // k steps as one map: state -> mul state + add inc
 struct Jump { u128 mul, add; };
 
@@ -100,24 +87,12 @@ constexpr u128 advance(Variant v, u128 state, u128 inc, u128 n) { return apply(j
 // One output segment of a launch: n draws of the generator (variant, state, inc) to draws [offset, offset + n) of the output buffer.
 struct Segment { u128 state, inc; uint32_t variant; uint64_t n, offset; };
 
-enum SegmentsStatus { kSegmentsOk = 0, kSegmentsBadCount = 1, kSegmentsBadVariant = 2, kSegmentsOverflow = 3, kSegmentsOverlap = 4 };
+constexpr SegmentsStatus kSegmentsBadVariant = kSegmentsOwn;
 
-// kSegmentsBadCount: n_segments < 0 or more than max_segments (or a null table with segments); kSegmentsBadVariant: a variant that is
-// neither kPcg64 nor kDxsm; kSegmentsOverflow: an n, an offset or offset + n above kMaxDraws; kSegmentsOverlap: two non-empty output
-// ranges share a draw.
+// kSegmentsBadVariant: a variant that is neither kPcg64 nor kDxsm; the rest is flashe_draw::check_segments.
 inline SegmentsStatus check_segments(const Segment *segs, int n_segments, int max_segments = kMaxSegments)
 {
-    if (n_segments < 0 || n_segments > max_segments || (n_segments && !segs)) return kSegmentsBadCount;
-    std::vector<std::pair<uint64_t, uint64_t>> ranges;
-    for (int s = 0; s < n_segments; s++) {
-        if (segs[s].variant >= kVariants) return kSegmentsBadVariant;
-        if (segs[s].n > kMaxDraws || segs[s].offset > kMaxDraws || segs[s].offset + segs[s].n > kMaxDraws) return kSegmentsOverflow;
-        if (segs[s].n) ranges.emplace_back(segs[s].offset, segs[s].offset + segs[s].n);
-    }
-    std::sort(ranges.begin(), ranges.end());
-    for (size_t r = 1; r < ranges.size(); r++)
-        if (ranges[r].first < ranges[r - 1].second) return kSegmentsOverlap;
-    return kSegmentsOk;
+    return flashe_draw::check_segments(segs, n_segments, max_segments, [](const Segment &s) { return s.variant < kVariants; });
 }
 
 // ---- the launch's view ----

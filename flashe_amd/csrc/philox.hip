@@ -6,33 +6,27 @@
 // (the clients of a cohort) run in ONE launch, and the state after n draws is a few host additions (philox_stream.h), so nothing is read
 // back and the call does not synchronise.  The work per block is 20 64 x 64 -> 128 products, built from 32-bit multiply-adds.
 //
-// A launch is cut into tiles of 256 blocks that belong to one segment; a workgroup walks tiles blockIdx.x, + gridDim.x, ... (stream_grid's
-// rule: at most 8 workgroups per CU) and finds the tile's segment by a search of the plan table that is uniform over the workgroup.  The
-// table rides in the kernel-argument block up to kArgPlans segments -- no copy, nothing for the host to wait for -- and in a table of the
-// ctx beyond that.  Output ranges are only 8-byte aligned (a cohort's client stretch starts at any draw): a whole block is written as two
-// 16-byte non-temporal stores where its address allows, as 8 + 16 + 8 where it does not, and the ragged first and last block of a
+// A launch is cut into tiles of 256 blocks that belong to one segment; the search of the plan table that finds a tile's segment is uniform
+// over the workgroup.  Output ranges are only 8-byte aligned (a cohort's client stretch starts at any draw): a whole block is written as
+// two 16-byte non-temporal stores where its address allows, as 8 + 16 + 8 where it does not, and the ragged first and last block of a
 // segment word by word; nothing outside [offset, offset + n) is written.
-#include "ctx.h"
-#include "device_common.h"
+//
+// Here: the tile body, the two kernels that call it, and the entry points.  philox_stream.h: the stream's arithmetic, the segment checks and
+// the plans (no HIP: run on the host under sanitizers).  draw_segments.h, draw_launch.h: what the launch of a plan table shares with
+// pcg64.hip -- the range checks and the tile search; where the table rides, the launch and the entry points' common checks.
+#include "draw_launch.h"
 #include "philox_stream.h"
-
-#include <vector>
-
-using flashe_host::fail;
 
 namespace {
 
+using flashe_draw::st_draw;
 using flashe_philox::Plan;
-constexpr int kArgPlans = 48;                         // 48 x 80 bytes + the other arguments < the 4-KiB kernel-argument block
+using ArgPlans = flashe_draw::ArgPlans<Plan>;
 static_assert(sizeof(Plan) == 80, "the plan rows are 80 bytes");
 static_assert(flashe_philox::kTileBlocks == flashe::kStreamThreads, "a tile is one block per thread of a stream workgroup");
 
-struct ArgPlans { Plan p[kArgPlans]; };
-
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 
-// (the addresses are integers: said to be global memory, so that the stores are global_store and not flat_store -- FLASHE_GLOBAL)
-__device__ __forceinline__ void st_draw(uintptr_t at, double d) { __builtin_nontemporal_store(d, FLASHE_GLOBAL(double, at)); }
 __device__ __forceinline__ void st_draws2(uintptr_t at, double a, double b)
 {
     f64x2 v;
@@ -43,13 +37,7 @@ __device__ __forceinline__ void st_draws2(uintptr_t at, double a, double b)
 __device__ __forceinline__ void philox_tiles(const Plan *__restrict__ plans, int n_plans, uint64_t tiles, double *__restrict__ out)
 {
     for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
-        // the segment of tile t: the last plan whose first tile is not above t
-        int lo = 0, hi = n_plans - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (plans[mid].tile_first <= t) lo = mid; else hi = mid - 1;
-        }
-        const Plan &p = plans[lo];
+        const Plan &p = flashe_draw::tile_plan(plans, n_plans, t);
         const uint64_t j = (t - p.tile_first) * flashe_philox::kTileBlocks + threadIdx.x;
         const uint64_t v0 = 4 * j, skip = p.skip, end = skip + p.n;       // the block's virtual draws v0 .. v0 + 3; [skip, end) exist
         if (v0 >= end) continue;
@@ -124,37 +112,12 @@ extern "C" int flashe_philox_grid(flashe_ctx *ctx, uint64_t n, uint32_t buffer_p
 extern "C" int flashe_philox_random_dev(flashe_ctx *ctx, flashe_philox_segment *segments, int n_segments, double *u_dev)
 {
     CHECK_CTX(ctx);
-    if (n_segments < 0 || n_segments > flashe_philox::kMaxSegments)
-        return fail(ctx, FLASHE_EINVAL, "flashe_philox_random_dev: %d segments, a launch holds 0 .. %d", n_segments, flashe_philox::kMaxSegments);
-    if (n_segments && !segments) return fail(ctx, FLASHE_EINVAL, "flashe_philox_random_dev: no segment table");
-    if (ctx->capturing) return fail(ctx, FLASHE_EINVAL, "flashe_philox_random_dev advances the generator states it is given: a replay would repeat the draws");
-    std::vector<flashe_philox::Segment> segs(static_cast<size_t>(n_segments));
-    for (int s = 0; s < n_segments; s++) to_segment(segments[s], segs[s]);
-    switch (flashe_philox::check_segments(segs.data(), n_segments)) {
-    case flashe_philox::kSegmentsOk: break;
-    case flashe_philox::kSegmentsBadPos: return fail(ctx, FLASHE_EINVAL, "flashe_philox_random_dev: a buffer_pos above 4");
-    case flashe_philox::kSegmentsOverflow: return fail(ctx, FLASHE_EINVAL, "flashe_philox_random_dev: a segment's offset + n overflows");
-    case flashe_philox::kSegmentsOverlap: return fail(ctx, FLASHE_EINVAL, "flashe_philox_random_dev: two segments' output ranges overlap");
-    default: return fail(ctx, FLASHE_EINVAL, "flashe_philox_random_dev: bad segment table");
-    }
+    std::vector<flashe_philox::Segment> segs;
+    if (int rc = flashe_draw::read_segments(ctx, "flashe_philox_random_dev", segments, n_segments, u_dev, to_segment, flashe_philox::check_segments, "a buffer_pos above 4", segs))
+        return rc;
     std::vector<Plan> plans;
     const uint64_t tiles = flashe_philox::plan_segments(segs.data(), n_segments, plans);
-    if (tiles) {
-        if (!u_dev || (reinterpret_cast<uintptr_t>(u_dev) & 7u)) return fail(ctx, FLASHE_EINVAL, "flashe_philox_random_dev: u_dev must be an 8-byte aligned device pointer");
-        const int n_plans = static_cast<int>(plans.size());
-        const dim3 grid(flashe::stream_grid(ctx->env, tiles * flashe::kStreamThreads)), wg(flashe::kStreamThreads);
-        if (n_plans <= kArgPlans) {
-            ArgPlans tab{};
-            std::copy(plans.begin(), plans.end(), tab.p);
-            hipLaunchKernelGGL(philox_random_args_kernel, grid, wg, 0, ctx->env.stream, tab, n_plans, tiles, u_dev);
-        } else {
-            // (pageable source: the copy has left `plans` when the call returns; stream order keeps an earlier launch's table intact)
-            if (int rc = flashe_host::ensure(ctx, ctx->philox_tab, flashe_philox::kMaxSegments * sizeof(Plan))) return rc;
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->philox_tab.p, plans.data(), plans.size() * sizeof(Plan), hipMemcpyHostToDevice, ctx->env.stream));
-            hipLaunchKernelGGL(philox_random_table_kernel, grid, wg, 0, ctx->env.stream, static_cast<const Plan *>(ctx->philox_tab.p), n_plans, tiles, u_dev);
-        }
-        HIP_TRY(ctx, hipGetLastError());
-    }
+    if (int rc = flashe_draw::launch_plans(ctx, plans, tiles, 0, philox_random_args_kernel, philox_random_table_kernel, u_dev)) return rc;
     for (int s = 0; s < n_segments; s++)
         flashe_philox::advance(segments[s].key, segments[s].counter, segments[s].buffer_pos, segments[s].buffer, segments[s].n);
     return FLASHE_OK;

@@ -11,30 +11,14 @@
 // So with  base = counter (p < 4) or counter + 1 (p = 4)  and  skip = p (p < 4) or 0:  draw i is word (skip + i) % 4 of
 // block(base + (skip + i) / 4).
 #pragma once
-#include <cstddef>
-#include <cstdint>
-#include <algorithm>
-#include <vector>
-
-#ifndef FLASHE_HD
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define FLASHE_HD __host__ __device__ __forceinline__
-#else
-#define FLASHE_HD inline
-#endif
-#endif
-#ifdef __clang__
-#define FLASHE_UNROLL _Pragma("unroll")
-#else
-#define FLASHE_UNROLL
-#endif
+#include "draw_segments.h"
 
 namespace flashe_philox {
 
+using namespace flashe_draw;                         // kMaxSegments, kMaxDraws, to_double, SegmentsStatus and its values
+
 constexpr uint64_t kM0 = 0xD2E7470EE14C6C93ull, kM1 = 0xCA5A826395121157ull;
 constexpr uint64_t kWeyl0 = 0x9E3779B97F4A7C15ull, kWeyl1 = 0xBB67AE8584CAA73Bull;
-constexpr int kMaxSegments = 128;                   // the segments one launch holds
-constexpr uint64_t kMaxDraws = 1ull << 60;          // per segment, and offset + n: their byte counts stay inside 64 bits
 
 FLASHE_HD void mulhilo(uint64_t a, uint64_t b, uint64_t &hi, uint64_t &lo)
 {
@@ -70,8 +54,6 @@ FLASHE_UNROLL
     }
 }
 
-FLASHE_HD double to_double(uint64_t word) { return static_cast<double>(word >> 11) * (1.0 / 9007199254740992.0); }
-
 // Where the draws of a state (counter, buffer_pos <= 4) start: base[4] and skip (see the head of this file).
 FLASHE_HD void stream_start(const uint64_t counter[4], uint32_t buffer_pos, uint64_t base[4], uint32_t &skip)
 {
@@ -106,23 +88,12 @@ inline void advance(const uint64_t key[2], uint64_t counter[4], uint32_t &buffer
 // One output segment of a launch: n draws of the state to draws [offset, offset + n) of the output buffer.
 struct Segment { uint64_t key[2]; uint64_t counter[4]; uint32_t buffer_pos; uint64_t n, offset; };
 
-enum SegmentsStatus { kSegmentsOk = 0, kSegmentsBadCount = 1, kSegmentsBadPos = 2, kSegmentsOverflow = 3, kSegmentsOverlap = 4 };
+constexpr SegmentsStatus kSegmentsBadPos = kSegmentsOwn;
 
-// kSegmentsBadCount: n_segments < 0 or more than max_segments (or a null table with segments); kSegmentsBadPos: a buffer_pos above 4;
-// kSegmentsOverflow: an n, an offset or offset + n above kMaxDraws; kSegmentsOverlap: two non-empty output ranges share a draw.
+// kSegmentsBadPos: a buffer_pos above 4; the rest is flashe_draw::check_segments.
 inline SegmentsStatus check_segments(const Segment *segs, int n_segments, int max_segments = kMaxSegments)
 {
-    if (n_segments < 0 || n_segments > max_segments || (n_segments && !segs)) return kSegmentsBadCount;
-    std::vector<std::pair<uint64_t, uint64_t>> ranges;
-    for (int s = 0; s < n_segments; s++) {
-        if (segs[s].buffer_pos > 4) return kSegmentsBadPos;
-        if (segs[s].n > kMaxDraws || segs[s].offset > kMaxDraws || segs[s].offset + segs[s].n > kMaxDraws) return kSegmentsOverflow;
-        if (segs[s].n) ranges.emplace_back(segs[s].offset, segs[s].offset + segs[s].n);
-    }
-    std::sort(ranges.begin(), ranges.end());
-    for (size_t r = 1; r < ranges.size(); r++)
-        if (ranges[r].first < ranges[r - 1].second) return kSegmentsOverlap;
-    return kSegmentsOk;
+    return flashe_draw::check_segments(segs, n_segments, max_segments, [](const Segment &s) { return s.buffer_pos <= 4; });
 }
 
 // The launch's view of a segment: whole blocks j = 0 .. blocks - 1 of block(base + j); block j holds the virtual draws 4 j .. 4 j + 3, of

@@ -489,6 +489,101 @@ class SpanBounds:
             pass
 
 
+class _PhiloxDraws:
+    """np.random.Philox as _draw_table takes a kind of generator: the segment struct and the segments one call holds; a state dict as a
+    segment (n and offset are the table's to fill), a segment moved n draws on in place (flashe_philox_advance), and the segment's
+    generator fields put back into the state dict."""
+    Segment, max_segments = _lib.PhiloxSegment, 128
+
+    @staticmethod
+    def segment(state):
+        if state.get("bit_generator") != "Philox":
+            raise FlasheError(-22, f"the bit generator is {state.get('bit_generator')}, not Philox")
+        seg = _lib.PhiloxSegment()
+        seg.key[:] = [int(v) for v in state["state"]["key"]]
+        seg.counter[:] = [int(v) for v in state["state"]["counter"]]
+        seg.buffer[:] = [int(v) for v in state["buffer"]]
+        seg.buffer_pos = int(state["buffer_pos"])
+        return seg
+
+    @staticmethod
+    def move_on(seg, n):
+        pos = c_u32(seg.buffer_pos)
+        _lib.check(None, _lib.load().flashe_philox_advance(seg.key, seg.counter, ctypes.byref(pos), seg.buffer, n))
+        seg.buffer_pos = pos.value
+
+    @staticmethod
+    def hand_back(state, seg):                      # (has_uint32 and uinteger stay as they are)
+        state["state"]["counter"] = np.array(list(seg.counter), dtype=np.uint64)
+        state["buffer"] = np.array(list(seg.buffer), dtype=np.uint64)
+        state["buffer_pos"] = int(seg.buffer_pos)
+
+
+class _Pcg64Draws:
+    """np.random.PCG64 and np.random.PCG64DXSM, as _PhiloxDraws is Philox."""
+    Segment, max_segments = _lib.Pcg64Segment, 128
+
+    @staticmethod
+    def segment(state):
+        variant = {"PCG64": 0, "PCG64DXSM": 1}.get(state.get("bit_generator"))
+        if variant is None:
+            raise FlasheError(-22, f"the bit generator is {state.get('bit_generator')}, not PCG64 or PCG64DXSM")
+        seg, m64 = _lib.Pcg64Segment(), (1 << 64) - 1
+        for words, v in ((seg.state, int(state["state"]["state"])), (seg.inc, int(state["state"]["inc"]))):
+            if not 0 <= v < 1 << 128:
+                raise FlasheError(-22, "a PCG64 state or inc outside 128 bits")
+            words[:] = [v & m64, v >> 64]
+        seg.variant = variant
+        return seg
+
+    @staticmethod
+    def move_on(seg, n):
+        _lib.check(None, _lib.load().flashe_pcg64_advance(seg.variant, seg.state, seg.inc, (c_u64 * 2)(n, 0)))
+
+    @staticmethod
+    def hand_back(state, seg):                      # (has_uint32 and uinteger stay as they are)
+        state["state"]["state"] = int(seg.state[0]) | (int(seg.state[1]) << 64)
+
+
+def _draw_table(kind, generators_or_states, counts, offsets=None):
+    """The segment table of a kind's *_random_dev call, built on the host: entry s of `generators_or_states` -- a np.random.Generator or a
+    bit generator's state dict -- gives counts[s] draws to draws [offsets[s], offsets[s] + counts[s]) of the output (default: back to
+    back).  An entry that appears again continues where its earlier segment leaves it.  Returns (segs, counts, offsets, hand_back):
+    the C call advances every segment of segs in place, and hand_back() then puts each entry's latest segment into its state dict and
+    its Generator.  Raises ValueError for lists of different lengths or more segments than the call holds, FlasheError for another bit
+    generator or a count or offset outside 64 bits (ctypes would mask it silently); nothing has been advanced then."""
+    counts = [int(c) for c in counts]
+    if len(counts) != len(generators_or_states):
+        raise ValueError(f"{len(generators_or_states)} generators, {len(counts)} counts")
+    offsets = [sum(counts[:s]) for s in range(len(counts))] if offsets is None else [int(o) for o in offsets]
+    if len(offsets) != len(counts):
+        raise ValueError(f"{len(counts)} counts, {len(offsets)} offsets")
+    if len(counts) > kind.max_segments:
+        raise ValueError(f"{len(counts)} segments: one launch holds {kind.max_segments}")
+    if not all(0 <= v < 1 << 64 for v in counts + offsets):
+        raise FlasheError(-22, "a segment's n or offset overflows")
+    segs = (kind.Segment * max(len(counts), 1))()
+    latest = {}                       # id(entry) -> (entry, its state dict, its latest segment: where a repeat continues, what is handed back)
+    for s, (g, n, off) in enumerate(zip(generators_or_states, counts, offsets)):
+        if id(g) in latest:
+            state, seg = latest[id(g)][1], kind.Segment.from_buffer_copy(latest[id(g)][2])
+            kind.move_on(seg, seg.n)
+        else:
+            state = g.bit_generator.state if isinstance(g, np.random.Generator) else g
+            seg = kind.segment(state)
+        seg.n, seg.offset = n, off
+        segs[s] = seg
+        latest[id(g)] = (g, state, segs[s])
+
+    def hand_back():
+        for g, state, seg in latest.values():
+            kind.hand_back(state, seg)
+            if isinstance(g, np.random.Generator):
+                g.bit_generator.state = state
+
+    return segs, counts, offsets, hand_back
+
+
 class Engine:
     """One device context of the cipher engine (wraps flashe_ctx)."""
 
@@ -1344,27 +1439,17 @@ class Engine:
         np.random.set_state((st[0], key, int(pos.value), st[3], st[4]))
         return out
 
-    PHILOX_MAX_SEGMENTS = 128        # the segments one flashe_philox_random_dev launch holds
+    PHILOX_MAX_SEGMENTS = _PhiloxDraws.max_segments  # the segments one flashe_philox_random_dev launch holds
 
-    @staticmethod
-    def _philox_segment(state, n, offset):
-        """A Philox bit generator's state dict as the flashe_philox_segment that draws n values to draw `offset` of the output."""
-        if state.get("bit_generator") != "Philox":
-            raise FlasheError(-22, f"the bit generator is {state.get('bit_generator')}, not Philox")
-        seg = _lib.PhiloxSegment()
-        seg.key[:] = [int(v) for v in state["state"]["key"]]
-        seg.counter[:] = [int(v) for v in state["state"]["counter"]]
-        seg.buffer[:] = [int(v) for v in state["buffer"]]
-        seg.buffer_pos, seg.n, seg.offset = int(state["buffer_pos"]), int(n), int(offset)
-        return seg
-
-    @staticmethod
-    def _philox_state(state, seg):
-        """The state dict with the segment's counter, buffer_pos and buffer (has_uint32 and uinteger stay as they are)."""
-        state["state"]["counter"] = np.array(list(seg.counter), dtype=np.uint64)
-        state["buffer"] = np.array(list(seg.buffer), dtype=np.uint64)
-        state["buffer_pos"] = int(seg.buffer_pos)
-        return state
+    def _draw_random_dev(self, kind, call, generators_or_states, counts, out, offsets):
+        """philox_random_dev / pcg64_random_dev: the kind's table (_draw_table), its C call, and the advanced states handed back -- only
+        after the call has succeeded, so that a refusal advances nothing."""
+        segs, counts, offsets, hand_back = _draw_table(kind, generators_or_states, counts, offsets)
+        if out is None:
+            out = self.alloc(max(8 * max([o + n for o, n in zip(offsets, counts)], default=0), 16))
+        self._check(call(self._h, segs, len(counts), self._ptr(out)))
+        hand_back()
+        return out
 
     def philox_random_dev(self, generators_or_states, counts, out=None, offsets=None):
         """Generator(np.random.Philox(...)).random(n) generated on the device, bit for bit, for every entry of `generators_or_states` in ONE
@@ -1372,40 +1457,9 @@ class Engine:
         device address of float64, 8-byte aligned; default: the entries back to back in a new buffer).  An entry is a np.random.Generator
         over Philox -- its bit_generator.state is read and the advanced state put back, so host draws before and after continue one
         stream -- or such a state dict, advanced in place.  The same Generator may appear several times: its segments continue one
-        another in list order, as sequential host draws would.  Returns the buffer.  Raises for another bit generator, overlapping ranges
-        or more than PHILOX_MAX_SEGMENTS entries; nothing is advanced then."""
-        counts = [int(c) for c in counts]
-        if len(counts) != len(generators_or_states):
-            raise ValueError(f"{len(generators_or_states)} generators, {len(counts)} counts")
-        if offsets is None:
-            offsets = [sum(counts[:s]) for s in range(len(counts))]
-        if len(offsets) != len(counts):
-            raise ValueError(f"{len(counts)} counts, {len(offsets)} offsets")
-        if len(counts) > self.PHILOX_MAX_SEGMENTS:
-            raise ValueError(f"{len(counts)} segments: one launch holds {self.PHILOX_MAX_SEGMENTS}")
-        segs = (_lib.PhiloxSegment * max(len(counts), 1))()
-        last = {}                         # id(entry) -> its latest segment: where a repeated entry continues, and what is handed back
-        states = {}
-        for s, (g, n, off) in enumerate(zip(generators_or_states, counts, offsets)):
-            if id(g) in last:
-                prev = last[id(g)]
-                seg = _lib.PhiloxSegment.from_buffer_copy(prev)
-                pos = c_u32(seg.buffer_pos)
-                self._check(self._lib.flashe_philox_advance(seg.key, seg.counter, ctypes.byref(pos), seg.buffer, prev.n))
-                seg.buffer_pos, seg.n, seg.offset = pos.value, n, int(off)
-            else:
-                states[id(g)] = (g, g.bit_generator.state if isinstance(g, np.random.Generator) else g)
-                seg = self._philox_segment(states[id(g)][1], n, off)
-            segs[s] = seg
-            last[id(g)] = segs[s]
-        if out is None:
-            out = self.alloc(max(8 * max([o + n for o, n in zip(offsets, counts)], default=0), 16))
-        self._check(self._lib.flashe_philox_random_dev(self._h, segs, len(counts), self._ptr(out)))
-        for key, (g, state) in states.items():
-            self._philox_state(state, last[key])
-            if isinstance(g, np.random.Generator):
-                g.bit_generator.state = state
-        return out
+        another in list order (flashe_philox_advance), as sequential host draws would.  Returns the buffer.  Raises for another bit generator, overlapping ranges,
+        a misaligned output, a count or offset outside 64 bits or more than PHILOX_MAX_SEGMENTS entries; nothing is advanced then."""
+        return self._draw_random_dev(_PhiloxDraws, self._lib.flashe_philox_random_dev, generators_or_states, counts, out, offsets)
 
     def philox_grid(self, n, buffer_pos=4):
         """(workgroups, tiles) of the launch philox_random_dev makes for one segment of n draws: more tiles than workgroups are further
@@ -1414,66 +1468,16 @@ class Engine:
         self._check(self._lib.flashe_philox_grid(self._h, int(n), int(buffer_pos), ctypes.byref(wg), ctypes.byref(tiles)))
         return int(wg.value), int(tiles.value)
 
-    PCG64_MAX_SEGMENTS = 128         # the segments one flashe_pcg64_random_dev call holds
+    PCG64_MAX_SEGMENTS = _Pcg64Draws.max_segments    # the segments one flashe_pcg64_random_dev call holds
     PCG64_STRETCH = 16               # the draws a lane of its launch walks, at a stride of the workgroup's 256 lanes
-    _PCG64_VARIANTS = {"PCG64": 0, "PCG64DXSM": 1}
-
-    @classmethod
-    def _pcg64_segment(cls, state, n, offset):
-        """A PCG64 / PCG64DXSM bit generator's state dict as the flashe_pcg64_segment that draws n values to draw `offset` of the output."""
-        variant = cls._PCG64_VARIANTS.get(state.get("bit_generator"))
-        if variant is None:
-            raise FlasheError(-22, f"the bit generator is {state.get('bit_generator')}, not PCG64 or PCG64DXSM")
-        if not (0 <= int(n) < 1 << 64 and 0 <= int(offset) < 1 << 64):
-            raise FlasheError(-22, "a segment's n or offset overflows")
-        seg, m64 = _lib.Pcg64Segment(), (1 << 64) - 1
-        for words, v in ((seg.state, int(state["state"]["state"])), (seg.inc, int(state["state"]["inc"]))):
-            if not 0 <= v < 1 << 128:
-                raise FlasheError(-22, "a PCG64 state or inc outside 128 bits")
-            words[:] = [v & m64, v >> 64]
-        seg.variant, seg.n, seg.offset = variant, int(n), int(offset)
-        return seg
 
     def pcg64_random_dev(self, generators_or_states, counts, out=None, offsets=None):
         """Generator(np.random.PCG64(...)).random(n) -- the generator np.random.default_rng returns -- and Generator(np.random.PCG64DXSM(...))
         .random(n) generated on the device, bit for bit, for every entry of `generators_or_states` in ONE asynchronous call (one launch per
-        variant present): entry s gives counts[s] draws to draws [offsets[s], offsets[s] + counts[s]) of `out` (a DeviceBuffer or a device
-        address of float64, 8-byte aligned; default: the entries back to back in a new buffer).  An entry is a np.random.Generator over
-        PCG64 or PCG64DXSM -- its bit_generator.state is read and the advanced state put back with has_uint32 / uinteger as they were, so
-        host draws before and after continue one stream -- or such a state dict, advanced in place.  The same Generator may appear several
-        times: its segments continue one another in list order, as sequential host draws would.  Returns the buffer.  Raises for another
-        bit generator, overlapping ranges, a misaligned output or more than PCG64_MAX_SEGMENTS entries; nothing is advanced then."""
-        counts = [int(c) for c in counts]
-        if len(counts) != len(generators_or_states):
-            raise ValueError(f"{len(generators_or_states)} generators, {len(counts)} counts")
-        if offsets is None:
-            offsets = [sum(counts[:s]) for s in range(len(counts))]
-        if len(offsets) != len(counts):
-            raise ValueError(f"{len(counts)} counts, {len(offsets)} offsets")
-        if len(counts) > self.PCG64_MAX_SEGMENTS:
-            raise ValueError(f"{len(counts)} segments: one launch holds {self.PCG64_MAX_SEGMENTS}")
-        segs = (_lib.Pcg64Segment * max(len(counts), 1))()
-        last = {}                         # id(entry) -> its latest segment: where a repeated entry continues, and what is handed back
-        states = {}
-        for s, (g, n, off) in enumerate(zip(generators_or_states, counts, offsets)):
-            if id(g) in last:
-                prev = last[id(g)]
-                seg = _lib.Pcg64Segment.from_buffer_copy(prev)
-                self._check(self._lib.flashe_pcg64_advance(seg.variant, seg.state, seg.inc, (c_u64 * 2)(prev.n, 0)))
-                seg.n, seg.offset = n, int(off)
-            else:
-                states[id(g)] = (g, g.bit_generator.state if isinstance(g, np.random.Generator) else g)
-                seg = self._pcg64_segment(states[id(g)][1], n, off)
-            segs[s] = seg
-            last[id(g)] = segs[s]
-        if out is None:
-            out = self.alloc(max(8 * max([o + n for o, n in zip(offsets, counts)], default=0), 16))
-        self._check(self._lib.flashe_pcg64_random_dev(self._h, segs, len(counts), self._ptr(out)))
-        for key, (g, state) in states.items():
-            state["state"]["state"] = int(last[key].state[0]) | (int(last[key].state[1]) << 64)
-            if isinstance(g, np.random.Generator):
-                g.bit_generator.state = state
-        return out
+        variant present).  Arguments, result and refusals as philox_random_dev's, with PCG64_MAX_SEGMENTS entries at most: an entry is a
+        np.random.Generator over PCG64 or PCG64DXSM, or such a state dict (a repeated one continues through flashe_pcg64_advance); the
+        advanced state is put back with has_uint32 / uinteger as they were."""
+        return self._draw_random_dev(_Pcg64Draws, self._lib.flashe_pcg64_random_dev, generators_or_states, counts, out, offsets)
 
     def pcg64_grid(self, n):
         """(workgroups, tiles, draws per tile) of the launch pcg64_random_dev makes for one segment of n draws: more tiles than workgroups are

@@ -69,6 +69,14 @@ def _rng_on_device(eng, rng, count):
     return call if call is not None and hasattr(eng, call) else None
 
 
+def _global_on_device(eng, count):
+    """Does a call for `count` draws of NumPy's global stream generate them on the device (eng.numpy_random_dev)?  FLASHE_DEVICE_RNG not 0,
+    DEVICE_RNG_MIN draws or more, an engine that has the call, and the stream is MT19937 (the generator the device call continues and
+    jumps ahead)."""
+    return (os.environ.get("FLASHE_DEVICE_RNG", "1") != "0" and count >= DEVICE_RNG_MIN and hasattr(eng, "numpy_random_dev")
+            and np.random.get_state()[0] == "MT19937")
+
+
 def _static_quantize_padding_asymmetric(value, alpha, int_bits, uniforms=None, device=0, as_object=True, rng=None):
     """jzf_quantize.py:55-67.  rng (new): a np.random.Generator the draws come from in place of np.random.random."""
     if rng is not None and uniforms is not None:
@@ -78,30 +86,19 @@ def _static_quantize_padding_asymmetric(value, alpha, int_bits, uniforms=None, d
     shape = value.shape
     eng = _engine(64, device)
     n = int(value.size)
-    if rng is not None:
-        call = _rng_on_device(eng, rng, n)
-        if call:
-            x = np.ascontiguousarray(value).reshape(-1)
-            if x.dtype not in (np.float32, np.float64):
-                x = x.astype(np.float64)
-            dx, dq = eng.upload(x), eng.alloc(8 * n)
-            du = getattr(eng, call)([rng], [n])
-            eng.quantize_dev(n, dx, x.dtype == np.float64, alpha, int_bits, du, dq)
-            q = dq.download(np.uint64, n).reshape(shape)
-        else:
-            q = eng.quantize(value.reshape(-1), alpha, int_bits, rng.random(shape).reshape(-1)).reshape(shape)
-    elif (uniforms is None and n >= DEVICE_RNG_MIN and os.environ.get("FLASHE_DEVICE_RNG", "1") != "0"
-            and hasattr(eng, "numpy_random_dev") and np.random.get_state()[0] == "MT19937"):
-        # np.random.random(shape) generated where it is consumed: no host loop over n draws, no 8 B / element upload
+    call = _rng_on_device(eng, rng, n) if rng is not None else "numpy_random_dev" if uniforms is None and _global_on_device(eng, n) else None
+    if call:
+        # the draws generated where they are consumed: no host loop over n draws, no 8 B / element upload
         x = np.ascontiguousarray(value).reshape(-1)
         if x.dtype not in (np.float32, np.float64):
             x = x.astype(np.float64)
         dx, dq = eng.upload(x), eng.alloc(8 * n)
-        du = eng.numpy_random_dev(n)
+        du = getattr(eng, call)([rng], [n]) if rng is not None else eng.numpy_random_dev(n)
         eng.quantize_dev(n, dx, x.dtype == np.float64, alpha, int_bits, du, dq)
         q = dq.download(np.uint64, n).reshape(shape)
     else:
-        u = np.random.random(shape) if uniforms is None else np.asarray(uniforms, dtype=np.float64)
+        u = (rng.random(shape) if rng is not None else np.random.random(shape) if uniforms is None
+             else np.asarray(uniforms, dtype=np.float64))
         q = eng.quantize(value.reshape(-1), alpha, int_bits, u.reshape(-1)).reshape(shape)
     return _as_object(q) if as_object else q
 

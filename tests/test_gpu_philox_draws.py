@@ -3,7 +3,9 @@ Generator(np.random.Philox(key=..., counter=...)).random(n), compared as bytes: 
 lengths either side of a workgroup's second trip through its loop (read from the launcher's grid rule on a ctx limited to one CU), start
 states with buffer_pos 1, 2, 3 and 4, counters whose increment carries or wraps at 2^256, an output pointer 8 bytes past a 32-byte
 boundary, several ragged segments in one launch, more segments than the kernel arguments hold, the same generator twice -- with canary
-values either side of every range that must come back intact, and the host generator continuing NumPy's own stream afterwards."""
+values either side of every range that must come back intact, and the host generator continuing NumPy's own stream afterwards -- a state
+dict advanced in place, and the refusals (a count outside 64 bits and a call inside a graph capture among them), which advance and write
+nothing."""
 import numpy as np
 import pytest
 
@@ -133,3 +135,60 @@ def test_the_refusals_advance_nothing(eng):
     for gen, st in zip((g, h), before):
         now = gen.bit_generator.state
         assert now["buffer_pos"] == st["buffer_pos"] and np.array_equal(now["state"]["counter"], st["state"]["counter"])
+
+
+def _unmoved(g, before):
+    now = g.bit_generator.state
+    return (now["buffer_pos"] == before["buffer_pos"] and np.array_equal(now["state"]["counter"], before["state"]["counter"])
+            and np.array_equal(now["buffer"], before["buffer"]))
+
+
+def test_a_count_or_offset_outside_64_bits_is_refused(eng):
+    """(ctypes masks such a value silently: 2 ** 64 + 4 would draw 4 values and advance the generator by 4)"""
+    from flashe_amd._lib import FlasheError
+    g = _gen(KEYS[1], COUNTERS["zero"], 2)
+    before = g.bit_generator.state
+    buf = eng.upload(np.full(64, CANARY))
+    with pytest.raises(FlasheError):
+        eng.philox_random_dev([g], [2 ** 64 + 4], out=buf)
+    with pytest.raises(FlasheError):
+        eng.philox_random_dev([g], [4], out=buf, offsets=[2 ** 64 + 8])
+    with pytest.raises(FlasheError):
+        eng.philox_random_dev([g], [-1], out=buf)
+    eng.sync()
+    assert buf.download(np.float64, 64).tobytes() == np.full(64, CANARY).tobytes()
+    assert _unmoved(g, before)
+
+
+def test_state_dicts_are_advanced_in_place(eng):
+    for pre in (0, 3):
+        g, ref = _gen(KEYS[1], COUNTERS["carry"], pre), _gen(KEYS[1], COUNTERS["carry"], pre)
+        st, before = g.bit_generator.state, g.bit_generator.state
+        out = eng.philox_random_dev([st], [4097])
+        assert out.download(np.float64, 4097).tobytes() == ref.random(4097).tobytes()
+        want = ref.bit_generator.state
+        assert st["buffer_pos"] == want["buffer_pos"] and np.array_equal(st["state"]["counter"], want["state"]["counter"])
+        assert np.array_equal(st["buffer"], want["buffer"]) and (st["has_uint32"], st["uinteger"]) == (want["has_uint32"], want["uinteger"])
+        assert _unmoved(g, before)                                                        # the dict moved, the generator it came from did not
+
+
+def test_the_call_is_refused_in_a_capture():
+    """On an engine of its own between graph_begin and graph_end: refused, nothing written or advanced, and the capture still ends."""
+    from flashe_amd import Engine
+    from flashe_amd._lib import FlasheError
+    e2 = Engine(KEY, 64)
+    g = _gen(KEYS[0], COUNTERS["zero"], 1)
+    before = g.bit_generator.state
+    buf = e2.upload(np.full(16, CANARY))
+    e2.sync()
+    e2.graph_begin()
+    try:
+        with pytest.raises(FlasheError):
+            e2.philox_random_dev([g], [4], out=buf)
+    finally:
+        try:
+            e2.graph_end()
+        except Exception:
+            pass
+    e2.sync()
+    assert _unmoved(g, before) and buf.download(np.float64, 16).tobytes() == np.full(16, CANARY).tobytes()

@@ -2,13 +2,16 @@
 against NumPy's own bit generators -- bit_generator.state after Generator.random(n) from generators taken after 0 .. 3 draws and after a
 32-bit draw, at states and increments set by hand to 0, 2^128 - 1 and an even value, and at far distances (2^32 +- 1, 2^64 +- 1, 2^127:
 what no few-second device run reaches; the device launch compiles the same functions) against bit_generator.advance(k); a state set by
-hand from the advance's output continues NumPy's stream with has_uint32 / uinteger as they were.  Touches no device."""
+hand from the advance's output continues NumPy's stream with has_uint32 / uinteger as they were; then the segment table
+Engine.pcg64_random_dev builds on that advance, without a device (draw_table_cases.py).  Touches no device."""
 import ctypes
 
 import numpy as np
 import pytest
 
+import draw_table_cases as cases
 from flashe_amd import _lib
+from flashe_amd.engine import _Pcg64Draws
 
 U64 = ctypes.c_uint64
 M64 = 2 ** 64 - 1
@@ -98,3 +101,29 @@ def test_the_advance_refuses_a_bad_call():
     assert lib.flashe_pcg64_advance(2, s, _words(1), _words(1)) != 0
     assert lib.flashe_pcg64_advance(0, None, _words(1), _words(1)) != 0
     assert list(s) == [5, 0]
+
+
+# ---- the segment table Engine.pcg64_random_dev builds on that advance (draw_table_cases.py: the checks, shared with Philox) ----
+NAMES = {"PCG64": ["PCG64", "PCG64DXSM", "PCG64"], "PCG64DXSM": ["PCG64DXSM", "PCG64", "PCG64DXSM"]}    # both variants in every table
+
+
+@pytest.mark.parametrize("name", list(VARIANTS))
+@pytest.mark.parametrize("offsets", [cases.OFFSETS, None])
+def test_the_draw_table_hands_back_the_states_of_the_same_host_draws(name, offsets):
+    cases.handed_back_states_are_those_of_the_same_host_draws_in_list_order(_Pcg64Draws, NAMES[name], offsets)
+
+
+@pytest.mark.parametrize("name", list(VARIANTS))
+def test_the_draw_table_continues_a_repeated_entry(name):
+    cases.a_repeated_entry_starts_where_its_earlier_segment_ends(_Pcg64Draws, NAMES[name])
+
+
+@pytest.mark.parametrize("bad", cases.OUTSIDE_64_BITS)
+@pytest.mark.parametrize("name", list(VARIANTS))
+def test_the_draw_table_refuses_counts_and_offsets_outside_64_bits(name, bad):
+    cases.counts_and_offsets_outside_64_bits_are_refused_with_nothing_advanced(_Pcg64Draws, NAMES[name], bad)
+
+
+@pytest.mark.parametrize("name", list(VARIANTS))
+def test_the_draw_table_refusals_advance_nothing(name):
+    cases.the_other_refusals_advance_nothing(_Pcg64Draws, NAMES[name], [np.random.SFC64(1), np.random.MT19937(1), np.random.Philox(1)])

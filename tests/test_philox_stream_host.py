@@ -1,13 +1,16 @@
 """CPU-only: the host entry points that state the Philox stream (flashe_philox_block: one Philox4x64-10 block; flashe_philox_advance: the
 state after n draws) against NumPy's own np.random.Philox -- its first block for several keys and counters, Generator.bit_generator.state
 after g.random(n) from generators pre-advanced by 0 .. 4 draws (buffer_pos 4, 1, 2, 3, 4), counters whose increment carries or wraps at
-2^256, and a state set by hand from the advance's output that continues NumPy's stream.  Touches no device."""
+2^256, and a state set by hand from the advance's output that continues NumPy's stream; then the segment table Engine.philox_random_dev
+builds on that advance, without a device (draw_table_cases.py).  Touches no device."""
 import ctypes
 
 import numpy as np
 import pytest
 
+import draw_table_cases as cases
 from flashe_amd import _lib
+from flashe_amd.engine import _PhiloxDraws
 
 U64 = ctypes.c_uint64
 M64 = 2 ** 64 - 1
@@ -89,3 +92,25 @@ def test_the_advance_refuses_a_bad_state():
     assert lib.flashe_philox_advance(key, counter, ctypes.byref(ctypes.c_uint32(5)), buffer, 1) != 0
     assert lib.flashe_philox_advance(key, counter, ctypes.byref(ctypes.c_uint32(4)), buffer, 2 ** 60 + 1) != 0
     assert list(counter) == [0, 0, 0, 0]
+
+
+# ---- the segment table Engine.philox_random_dev builds on that advance (draw_table_cases.py: the checks, shared with the PCG64 kinds) ----
+NAMES = ["Philox"] * 3
+
+
+@pytest.mark.parametrize("offsets", [cases.OFFSETS, None])
+def test_the_draw_table_hands_back_the_states_of_the_same_host_draws(offsets):
+    cases.handed_back_states_are_those_of_the_same_host_draws_in_list_order(_PhiloxDraws, NAMES, offsets)
+
+
+def test_the_draw_table_continues_a_repeated_entry():
+    cases.a_repeated_entry_starts_where_its_earlier_segment_ends(_PhiloxDraws, NAMES)
+
+
+@pytest.mark.parametrize("bad", cases.OUTSIDE_64_BITS)
+def test_the_draw_table_refuses_counts_and_offsets_outside_64_bits(bad):
+    cases.counts_and_offsets_outside_64_bits_are_refused_with_nothing_advanced(_PhiloxDraws, NAMES, bad)
+
+
+def test_the_draw_table_refusals_advance_nothing():
+    cases.the_other_refusals_advance_nothing(_PhiloxDraws, NAMES, [np.random.SFC64(1), np.random.MT19937(1), np.random.PCG64(1)])
