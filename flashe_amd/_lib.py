@@ -137,6 +137,8 @@ _SIGNATURES = {
     "flashe_encrypt_batch_dev": (c_int, [c_vp, c_u32, c_int, c_u64, c_u32, c_int, c_u32p, ctypes.POINTER(c_vp), c_int, ctypes.POINTER(c_vp)]),
     "flashe_encrypt_batch_sum_dev": (c_int, [c_vp, c_u32, c_int, c_u64, c_u32, c_int, c_u32p, ctypes.POINTER(c_vp), c_int, ctypes.POINTER(c_vp),
                                              c_vp]),
+    "flashe_encrypt_batch_sum_decrypt_dev": (c_int, [c_vp, c_u32, c_int, c_u64, c_u32, c_int, c_u32p, ctypes.POINTER(c_vp), c_int,
+                                                     ctypes.POINTER(c_vp), c_vp, c_vp]),
     "flashe_span_bounds_create": (c_int, [c_vp, c_u64, c_int, ctypes.POINTER(c_vp), c_u64p, ctypes.POINTER(c_vp)]),
     "flashe_span_bounds_recompute": (c_int, [c_vp, c_vp, ctypes.POINTER(c_vp), c_u64p]),
     "flashe_span_bounds_destroy": (None, [c_vp]),

@@ -437,6 +437,7 @@ int flashe_ctx_create(flashe_ctx **out, const uint8_t key[32], int int_bits, int
     ctx->env.use_chain = 1;
     if (const char *ch = getenv("FLASHE_CHAIN")) ctx->env.use_chain = atoi(ch) != 0;   // 0: every job computes both of its streams (A/B runs)
     if (const char *dm = getenv("FLASHE_CHAIN_DMASK")) ctx->chain_dmask_on = atoi(dm) != 0;   // 0: no chain decrypt mask (A/B runs, memory)
+    if (const char *dc = getenv("FLASHE_CHAIN_DEC")) ctx->chain_dec_on = atoi(dc) != 0;       // 0: the summed launch never writes the decrypted sum (A/B runs)
     *out = ctx;
     return FLASHE_OK;
 }
@@ -1055,10 +1056,12 @@ static const uint64_t *chain_dmask_match(const flashe_ctx *ctx, uint32_t iter, c
     return static_cast<const uint64_t *>(s.d.p) + (first - s.first) * 2;
 }
 
-int flashe_encrypt_batch_sum_dev(flashe_ctx *ctx, uint32_t iter, int scheme, uint64_t n, uint32_t n_jobs, int n_vec, const uint32_t *idx,
-                                 const uint64_t *const *pt_dev, int pt_limbs, uint64_t *const *ct_dev, uint64_t *sum_out_dev)
+// flashe_encrypt_batch_sum_dev.  dec_out_dev (flashe_encrypt_batch_sum_decrypt_dev): where the one launch can also write the decrypt of its
+// sum (prf_dec_sum128_kernel) it does, and *dec_done says so; the chain decrypt mask of the ctx is then neither written nor invalidated.
+static int encrypt_batch_sum(flashe_ctx *ctx, uint32_t iter, int scheme, uint64_t n, uint32_t n_jobs, int n_vec, const uint32_t *idx,
+                             const uint64_t *const *pt_dev, int pt_limbs, uint64_t *const *ct_dev, uint64_t *sum_out_dev, uint64_t *dec_out_dev,
+                             bool *dec_done)
 {
-    CHECK_CTX(ctx);
     if (!sum_out_dev && n && n_vec) return fail(ctx, FLASHE_EINVAL, "flashe_encrypt_batch_sum_dev: null sum_out_dev");
     if (n_vec > 0) { if (int rc = check_double_idx(ctx, scheme, idx, n_vec)) return rc; }
     if (n && n_vec) {
@@ -1074,6 +1077,12 @@ int flashe_encrypt_batch_sum_dev(flashe_ctx *ctx, uint32_t iter, int scheme, uin
                 int rc = check_prf_args(ctx, 1, scheme, n_jobs, ct_dev[v], pt_dev[v], pt_limbs);
                 if (rc) return rc;
             }
+            if (dec_out_dev && ctx->chain_dec_on) {
+                const hipError_t e = launch_prf_batch_sum(ctx->env, iter, n_vec, idx, pt_dev, pt_limbs, ct_dev, sum_out_dev, n, n_jobs, 0, n, nullptr,
+                                                          dec_out_dev);
+                if (e == hipSuccess) { *dec_done = true; return FLASHE_OK; }
+                if (e != hipErrorNotSupported) HIP_TRY(ctx, e);
+            }
             uint64_t *const dmask = chain_dmask_begin(ctx, n);
             const hipError_t e = launch_prf_batch_sum(ctx->env, iter, n_vec, idx, pt_dev, pt_limbs, ct_dev, sum_out_dev, n, n_jobs, 0, n, dmask);
             if (e == hipSuccess) {
@@ -1088,6 +1097,41 @@ int flashe_encrypt_batch_sum_dev(flashe_ctx *ctx, uint32_t iter, int scheme, uin
     if (rc || n == 0) return rc;
     if (n_vec == 0) { HIP_TRY(ctx, hipMemsetAsync(sum_out_dev, 0, n * ctx->limbs * 8, ctx->env.stream)); return FLASHE_OK; }
     return flashe_aggregate_elem_dev(ctx, n_vec, ct_dev, n, sum_out_dev);
+}
+
+int flashe_encrypt_batch_sum_dev(flashe_ctx *ctx, uint32_t iter, int scheme, uint64_t n, uint32_t n_jobs, int n_vec, const uint32_t *idx,
+                                 const uint64_t *const *pt_dev, int pt_limbs, uint64_t *const *ct_dev, uint64_t *sum_out_dev)
+{
+    CHECK_CTX(ctx);
+    bool dec_done = false;
+    return encrypt_batch_sum(ctx, iter, scheme, n, n_jobs, n_vec, idx, pt_dev, pt_limbs, ct_dev, sum_out_dev, nullptr, &dec_done);
+}
+
+// The co-located round of a device that plays the clients and the arbiter: flashe_encrypt_batch_sum_dev, then flashe_decrypt_dev of the sum
+// with add = [idx[n_vec - 1] + 1], minus = [idx[0]] (no list when n_vec = 0) into dec_out_dev -- the same bytes for every shape, in ONE launch
+// where prf_dec_sum128_kernel carries it (the lane that stores an element's sum holds its decrypt), as those two calls otherwise.
+int flashe_encrypt_batch_sum_decrypt_dev(flashe_ctx *ctx, uint32_t iter, int scheme, uint64_t n, uint32_t n_jobs, int n_vec, const uint32_t *idx,
+                                         const uint64_t *const *pt_dev, int pt_limbs, uint64_t *const *ct_dev, uint64_t *sum_out_dev,
+                                         uint64_t *dec_out_dev)
+{
+    CHECK_CTX(ctx);
+    // (every check on dec_out_dev comes before the first launch: a refused call has written nothing)
+    if (n_vec < 0 || (n_vec && !idx)) return fail(ctx, FLASHE_EINVAL, "flashe_encrypt_batch_sum_decrypt_dev: bad batch arguments");
+    if (n_vec && idx[n_vec - 1] == 0xffffffffu)
+        return fail(ctx, FLASHE_EINVAL, "flashe_encrypt_batch_sum_decrypt_dev: the decrypt's add prefix idx + 1 = 2^32 does not fit the 4-byte prefix field");
+    if (n) {
+        if (!dec_out_dev) return fail(ctx, FLASHE_EINVAL, "flashe_encrypt_batch_sum_decrypt_dev: null dec_out_dev");
+        if (!ct_aligned(ctx, dec_out_dev)) return fail(ctx, FLASHE_EINVAL, "dec_out_dev must be aligned like a ciphertext vector");
+        if (dec_out_dev == sum_out_dev) return fail(ctx, FLASHE_EINVAL, "dec_out_dev must not be sum_out_dev");
+        for (int v = 0; v < n_vec; v++)
+            if ((ct_dev && ct_dev[v] == dec_out_dev) || (pt_dev && pt_dev[v] == dec_out_dev))
+                return fail(ctx, FLASHE_EINVAL, "dec_out_dev must not be one of the plaintext or ciphertext vectors (vector %d)", v);
+    }
+    bool dec_done = false;
+    const int rc = encrypt_batch_sum(ctx, iter, scheme, n, n_jobs, n_vec, idx, pt_dev, pt_limbs, ct_dev, sum_out_dev, dec_out_dev, &dec_done);
+    if (rc || dec_done || n == 0) return rc;
+    const uint32_t add = n_vec ? idx[n_vec - 1] + 1u : 0u, minus = n_vec ? idx[0] : 0u;
+    return flashe_decrypt_dev(ctx, iter, &add, n_vec ? 1 : 0, &minus, n_vec ? 1 : 0, n, n_jobs, sum_out_dev, dec_out_dev);
 }
 
 int flashe_prf_jobs_dev(flashe_ctx *ctx, uint32_t iter, uint64_t n, uint32_t n_jobs, int n_entries, const flashe_prf_job *entries)

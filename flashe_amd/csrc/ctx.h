@@ -48,6 +48,7 @@ struct flashe_ctx {
     struct ChainDmask { Buf d; uint64_t n = 0, first = 0, count = 0; uint32_t iter = 0, key_epoch = 0, add_idx = 0, minus_idx = 0, n_jobs = 0; bool valid = false; };
     ChainDmask chain_dmask;
     bool chain_dmask_on = true;   // FLASHE_CHAIN_DMASK=0 at ctx creation: the summed launches write no decrypt mask
+    bool chain_dec_on = true;     // FLASHE_CHAIN_DEC=0 at ctx creation: flashe_encrypt_batch_sum_decrypt_dev always runs as its two calls
     // staging blocks of the host-pointer twins: hipMalloc / hipFree cost more than the kernels on LeNet-sized vectors and more than
     // the PCIe transfer on 160 MB ones, so blocks are kept and reused within a byte budget (the twins are synchronous: a block is
     // free again when its call returns)

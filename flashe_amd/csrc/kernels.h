@@ -78,9 +78,11 @@ hipError_t launch_prf_batch(const LaunchEnv &env, uint32_t iter, bool dbl, int n
 // int_bits > 64, at most kMaxUniformBatch vectors, long enough to fill the chip: the caller then encrypts and reduces separately.
 // dmask_dev (optional, pointer addresses element `first`): the same launch also writes the decrypt mask of the batch,
 // term(idx[n_vec - 1] + 1) - term(idx[0]) mod 2^b -- what a decrypt of the sum with add = [idx[n_vec - 1] + 1], minus = [idx[0]] adds.
+// dec_out_dev (optional, instead of dmask_dev, pointer addresses element `first`): the same launch also writes that decrypt of the sum
+// itself (PrfChain::dec_out_dev); hipErrorNotSupported -- nothing launched -- outside the shape of prf_dec_sum128_kernel.
 hipError_t launch_prf_batch_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const uint64_t *const *in_dev,
                                 int in_limbs, uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs, uint64_t first,
-                                uint64_t count, uint64_t *dmask_dev = nullptr);
+                                uint64_t count, uint64_t *dmask_dev = nullptr, uint64_t *dec_out_dev = nullptr);
 // The quantising front end of a COHORT launch (prf_chain_cohort_kernel): every output of one summed double-mask chain is a client's
 // own float model, all clients sharing one layer table.  layers: device table of the non-empty layers, ascending start, x unused
 // (p0, p1, p2 = alpha, scale, den: codec_layer_front); src: device table, src[c * n_layers + l] = client c's values of table row l
@@ -170,6 +172,10 @@ struct PrfChain {
     uint64_t *const *out_dev;
     uint64_t *sum_out_dev = nullptr;   // optional (int_bits > 64, n_out <= kMaxLinks): receives sum_c out[c] mod 2^b, written by the same launch
     uint64_t *dmask_dev = nullptr;     // optional, with sum_out_dev, the launch's only chain: receives term(idx[n_out]) - term(idx[0]) mod 2^b
+    // optional, with sum_out_dev and without dmask_dev, the launch's only chain: receives the DECRYPT of the sum, sum + term(idx[n_out]) -
+    // term(idx[0]) mod 2^b (prf_dec_sum128_kernel).  Only at int_bits = 128 with one-limb inputs, every input and output present and at most
+    // kSum128MaxCount elements: launch_prf_chains returns hipErrorNotSupported -- nothing launched -- for any other chain that asks for it.
+    uint64_t *dec_out_dev = nullptr;
 };
 hipError_t launch_prf_chains(const LaunchEnv &env, uint32_t iter, int n_chains, const PrfChain *chains, uint64_t n, uint32_t n_jobs);
 

@@ -377,7 +377,7 @@ __global__ __launch_bounds__(THREADS) void prf_chain_kernel(const RoundKeys rk, 
                                                               uint32_t iter0, uint64_t mask_lo, uint64_t mask_hi,
                                                               const uint32_t *__restrict__ te0, const Codec cq)
 {
-    constexpr bool DMASK = false, D128 = false, COHORT = false, GAPS = false;
+    constexpr bool DMASK = false, D128 = false, COHORT = false, GAPS = false, DEC = false;
     constexpr int BS = 0;
     const CohortGaps cg{};
     uint64_t *const dmask = nullptr;
@@ -392,7 +392,7 @@ __global__ __launch_bounds__(THREADS) void prf_chain_dmask_kernel(const RoundKey
                                                                     uint32_t iter0, uint64_t mask_lo, uint64_t mask_hi,
                                                                     const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask)
 {
-    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = false, GAPS = false;
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = false, GAPS = false, DEC = false;
     constexpr int BS = 0;
     const CohortGaps cg{};
     const Codec cq{};
@@ -409,7 +409,26 @@ __global__ __launch_bounds__(THREADS) void prf_dmask_sum128_kernel(const RoundKe
                                                                      uint32_t iter0, uint64_t mask_lo, uint64_t mask_hi,
                                                                      const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask)
 {
-    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = true, COHORT = false, GAPS = false;
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = true, COHORT = false, GAPS = false, DEC = false;
+    constexpr int BS = 0;
+    const CohortGaps cg{};
+    const Codec cq{};
+    const CohortCodec cc{};
+    const CohortBatch cb{};
+#include "prf_chain_body.inc"
+}
+
+// DEC (prf_chain_body.inc): the headline launch of a device that plays the clients AND the arbiter -- in place of the decrypt mask D it
+// stores the DECRYPTED sum, dec[k] = sum[k] + D[k] mod 2^128, the value a flashe_decrypt_dev of the sum with add = [last stream's idx],
+// minus = [first stream's idx] writes.  One 16-byte store replaces another: the launch moves the bytes prf_dmask_sum128_kernel moves, and
+// the round needs no second pass over the sum and the mask.  The ciphertexts and the sum are the same bytes; `dmask` carries dec_out.
+// A separate kernel: the headline kernels keep their code objects.
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void prf_dec_sum128_kernel(const RoundKeys rk, const ChainTable tb, int n_chains, int all_half_arg,
+                                                                   uint32_t iter0, uint64_t mask_lo, uint64_t mask_hi,
+                                                                   const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask)
+{
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = true, COHORT = false, GAPS = false, DEC = true;
     constexpr int BS = 0;
     const CohortGaps cg{};
     const Codec cq{};
@@ -431,7 +450,7 @@ __global__ __launch_bounds__(THREADS) void prf_chain_cohort_kernel(const RoundKe
                                                                      const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask,
                                                                      const CohortCodec cc)
 {
-    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true, GAPS = false;
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true, GAPS = false, DEC = false;
     constexpr int BS = 0;
     const Codec cq{};
     const CohortBatch cb{};
@@ -448,7 +467,7 @@ __global__ __launch_bounds__(THREADS) void prf_chain_cohort_batch_kernel(const R
                                                                            const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask,
                                                                            const CohortCodec cc, const CohortBatch cb)
 {
-    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true, GAPS = false;
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true, GAPS = false, DEC = false;
     constexpr int BS = BS_;
     const Codec cq{};
     const CohortGaps cg{};
@@ -465,7 +484,7 @@ __global__ __launch_bounds__(THREADS) void prf_chain_cohort_runs_kernel(const Ro
                                                                           const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask,
                                                                           const CohortCodec cc, const CohortGaps cg)
 {
-    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true, GAPS = true;
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true, GAPS = true, DEC = false;
     constexpr int BS = 0;
     const Codec cq{};
     const CohortBatch cb{};
@@ -478,7 +497,7 @@ __global__ __launch_bounds__(THREADS) void prf_chain_cohort_batch_runs_kernel(co
                                                                                 const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask,
                                                                                 const CohortCodec cc, const CohortBatch cb, const CohortGaps cg)
 {
-    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true, GAPS = true;
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true, GAPS = true, DEC = false;
     constexpr int BS = BS_;
     const Codec cq{};
 #include "prf_chain_body.inc"
@@ -1901,7 +1920,7 @@ hipError_t launch_prf_batch_range(const LaunchEnv &env, uint32_t iter, bool dbl,
 
 hipError_t launch_prf_batch_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const uint64_t *const *in_dev,
                                 int in_limbs, uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs, uint64_t first,
-                                uint64_t count, uint64_t *dmask_dev)
+                                uint64_t count, uint64_t *dmask_dev, uint64_t *dec_out_dev)
 {
     if (count == 0 || n_vec == 0) return hipSuccess;
     if (!env.use_chain || env.b <= 64 || env.codec || n_vec > kMaxLinks || !sum_out_dev) return hipErrorNotSupported;
@@ -1916,6 +1935,7 @@ hipError_t launch_prf_batch_sum(const LaunchEnv &env, uint32_t iter, int n_vec, 
     PrfChain ch{sidx.data(), n_vec, false, first, count, in_dev, in_limbs, out_dev};
     ch.sum_out_dev = sum_out_dev;
     ch.dmask_dev = dmask_dev;
+    ch.dec_out_dev = dec_out_dev;
     return launch_prf_chains(env, iter, 1, &ch, n, n_jobs);
 }
 
@@ -2163,7 +2183,7 @@ hipError_t launch_prf_jobs(const LaunchEnv &env, uint32_t iter, bool dbl, int n_
 // cut is computed by both pieces); short launches are cut further so that every wave of the chip gets an item.
 static hipError_t launch_small_chains(const LaunchEnv &env, uint32_t iter, int n_chains, const PrfChain *chains, uint64_t n, uint32_t n_jobs);
 
-// the shape of prf_dmask_sum128_kernel: one summed double-mask chain at int_bits = 128, one-limb inputs, every input and output present
+// the shape of prf_dmask_sum128_kernel and prf_dec_sum128_kernel: one summed double-mask chain at int_bits = 128, one-limb inputs, every input and output present
 static bool sum128_shape(const LaunchEnv &env, int nc, const ChainTable &tb, uint64_t lo, uint64_t hi)
 {
     if (env.b != 128 || ~lo != 0 || ~hi != 0 || nc != 1 || (tb.flags[0] & 3) != 0 || !tb.sum_out[0] || tb.count[0] > kSum128MaxCount) return false;
@@ -2174,16 +2194,21 @@ static bool sum128_shape(const LaunchEnv &env, int nc, const ChainTable &tb, uin
 
 hipError_t launch_prf_chains(const LaunchEnv &env, uint32_t iter, int n_chains, const PrfChain *chains, uint64_t n, uint32_t n_jobs)
 {
-    if (env.b <= 64) return launch_small_chains(env, iter, n_chains, chains, n, n_jobs);
+    if (env.b <= 64) {
+        for (int i = 0; i < n_chains; i++) if (chains[i].dec_out_dev) return hipErrorNotSupported;     // (written at int_bits = 128 only)
+        return launch_small_chains(env, iter, n_chains, chains, n, n_jobs);
+    }
     struct Piece { const PrfChain *ch; int l0, l1; uint64_t tiles; };
     std::vector<Piece> pieces;
     uint64_t total_tiles = 0;
     bool summed = false;
-    uint64_t *dmask = nullptr;
+    uint64_t *dmask = nullptr, *dec_out = nullptr;
     for (int i = 0; i < n_chains; i++) {
         const PrfChain &c = chains[i];
         if (c.dmask_dev && (n_chains != 1 || !c.sum_out_dev || c.single)) return hipErrorInvalidValue;     // (one summed double-mask chain)
+        if (c.dec_out_dev && (n_chains != 1 || !c.sum_out_dev || c.single || c.dmask_dev)) return hipErrorInvalidValue;     // (the same, in place of the mask)
         dmask = c.dmask_dev;
+        dec_out = c.dec_out_dev;
         if (c.count == 0 || c.n_out == 0) continue;
         if (((c.first + c.count - 1) >> 32) != (c.first >> 32)) return hipErrorNotSupported;     // the CTR shortcuts need one counter window
         // a chain that also writes the sum of its outputs is never cut (a piece would only know its own share of the sum)
@@ -2300,7 +2325,12 @@ hipError_t launch_prf_chains(const LaunchEnv &env, uint32_t iter, int n_chains, 
             cq = *env.codec;
         }
         if (env.codec && summed) return hipErrorInvalidValue;
-        if (dmask && sum128_shape(env, nc, tb, lo, hi))
+        // (a summed chain is one table: nothing has been launched when the decrypted sum is refused)
+        if (dec_out && !sum128_shape(env, nc, tb, lo, hi)) return hipErrorNotSupported;
+        if (dec_out)
+            hipLaunchKernelGGL((prf_dec_sum128_kernel<kPrfThreads>), dim3(grid), dim3(kPrfThreads), 0, env.stream, env.rk, tb, nc,
+                               (all_half ? 1 : 0) | (quarter ? 4 : 0) | probe, iter, lo, hi, env.te0_dev, dec_out);
+        else if (dmask && sum128_shape(env, nc, tb, lo, hi))
             hipLaunchKernelGGL((prf_dmask_sum128_kernel<kPrfThreads>), dim3(grid), dim3(kPrfThreads), 0, env.stream, env.rk, tb, nc,
                                (all_half ? 1 : 0) | (quarter ? 4 : 0) | probe, iter, lo, hi, env.te0_dev, dmask);
         else if (dmask)

@@ -1,7 +1,9 @@
-// The body of prf_chain_kernel<THREADS, SUM, CODEC>, prf_chain_dmask_kernel<THREADS>, prf_dmask_sum128_kernel<THREADS> and
+// The body of prf_chain_kernel<THREADS, SUM, CODEC>, prf_chain_dmask_kernel<THREADS>, prf_dmask_sum128_kernel<THREADS>, prf_dec_sum128_kernel<THREADS> and
 // prf_chain_cohort_kernel<THREADS> and prf_chain_cohort_batch_kernel<THREADS, BS> (kernels.hip), included INSIDE each kernel: the kernel defines
-// THREADS, SUM, CODEC, DMASK, D128, COHORT, BS and GAPS as compile-time constants and has the arguments rk, tb, n_chains, all_half_arg, iter0, mask_lo,
+// THREADS, SUM, CODEC, DMASK, D128, COHORT, BS, GAPS and DEC as compile-time constants and has the arguments rk, tb, n_chains, all_half_arg, iter0, mask_lo,
 // mask_hi, te0, cq, cc, cb, cg and dmask in scope.
+// DEC (D128 only, prf_dec_sum128_kernel): where the DMASK kernels store the decrypt mask D on the last stream, the launch stores the decrypt of
+// the sum it writes beside it, sum + D mod 2^b; `dmask` addresses that output.  Every branch on DEC is an `if constexpr`.
 // GAPS (COHORT only, prf_chain_cohort_runs_kernel / prf_chain_cohort_batch_runs_kernel): the cohort's cipher indices form SEVERAL runs -- clients
 // dropped out.  The stream loop runs over the cg.n_streams streams of tb.idx (cohort_streams.h); a stream's word of CohortGaps (a wave-uniform
 // scalar read of the kernel arguments) says whether it completes an output -- the next link in turn -- and whether it opens a client.  A stream
@@ -22,6 +24,7 @@
     static_assert(!COHORT || (DMASK && !D128), "the cohort front end rides on the summed decrypt-mask chain");
     static_assert(BS == 0 || COHORT, "batching is a form of the cohort front end");
     static_assert(!GAPS || COHORT, "several runs of indices are a form of the cohort chain");
+    static_assert(!DEC || D128, "the decrypted sum is written by the int_bits = 128 specialisation");
     (void)cg;
     (void)dmask;
     (void)cc;
@@ -267,7 +270,18 @@
                             if (c == 0) {
                                 if (p == 0) { dA0 = c0; dA1 = c1; } else { dB0 = c0; dB1 = c1; }
                             }
-                            if (last_stream && (!COHORT || dmask != nullptr)) {
+                            if constexpr (DEC) {
+                                // (the decrypt of the sum stored above, sum + D mod 2^b, where the others store D)
+                                if (last_stream) {
+                                    if (p == 0) {
+                                        if (a0) st128_nt(dmask + 2 * k0, (qA0 + (c0 - dA0)) & mask);
+                                        if (a1) st128_nt(dmask + 2 * k1, (qA1 + (c1 - dA1)) & mask);
+                                    } else {
+                                        if (a0) st128_nt(dmask + 2 * k0, (qB0 + (c0 - dB0)) & mask);
+                                        if (a1) st128_nt(dmask + 2 * k1, (qB1 + (c1 - dB1)) & mask);
+                                    }
+                                }
+                            } else if (last_stream && (!COHORT || dmask != nullptr)) {
                                 if (p == 0) {
                                     if (a0) st128_nt(dmask + 2 * k0, (c0 - dA0) & mask);
                                     if (a1) st128_nt(dmask + 2 * k1, (c1 - dA1) & mask);
@@ -427,7 +441,13 @@
                     }
                 } else if constexpr (DMASK) {
                     if (c == 0) { d0 = c0; d1 = c1; }
-                    if (c == n_streams - 1 && (!COHORT || dmask != nullptr)) {
+                    if constexpr (DEC) {
+                        // (the decrypt of the sum stored above, sum + D mod 2^b, where the others store D)
+                        if (c == n_streams - 1) {
+                            if (a0) st128_nt(dmask + 2 * k0, (q0 + (c0 - d0)) & mask);
+                            if (a1) st128_nt(dmask + 2 * k1, (q1 + (c1 - d1)) & mask);
+                        }
+                    } else if (c == n_streams - 1 && (!COHORT || dmask != nullptr)) {
                         if (a0) st128_nt(dmask + 2 * k0, (c0 - d0) & mask);
                         if (a1) st128_nt(dmask + 2 * k1, (c1 - d1) & mask);
                     }

@@ -10,6 +10,7 @@
 //     sum = sum_c pt_c - D -- the same bytes as the general path (everything mod 2^128);
 //   - every access is a buffer access: one 32-bit byte offset per lane and pair serves all streams and arrays, only the SGPR
 //     descriptor changes from stream to stream;
+//   - DEC (prf_dec_sum128_kernel): the last stream stores dec = sum + D = sum_c pt_c where the others store D;
 //   - the range predicates exist only in the chain's first and last tile (EDGE); interior tiles have all 256 counters in range.
 {
     const uint32_t cnt = static_cast<uint32_t>(tb.count[cur]);
@@ -76,8 +77,16 @@
                         add96(s0, h0, x0); add96(s1, h1, x1);
                         if (last_stream) {
                             const u128 d0 = c0 - f0, d1 = c1 - f1;
-                            if (a0) { buf_st128<2>(rdm, o16, d0); buf_st128<2>(rsum, o16, join96(s0, h0) - d0); }
-                            if (a1) { buf_st128<2>(rdm, o16 + 1024u, d1); buf_st128<2>(rsum, o16 + 1024u, join96(s1, h1) - d1); }
+                            if constexpr (DEC) {
+                                // the decrypt of the sum stored beside it: dec = sum + D = (join96(s, h) - D) + D mod 2^128 -- the
+                                // plaintexts' sum the lane already holds -- in place of D (rdm addresses dec_out)
+                                const u128 t0 = join96(s0, h0), t1 = join96(s1, h1);
+                                if (a0) { buf_st128<2>(rdm, o16, t0); buf_st128<2>(rsum, o16, t0 - d0); }
+                                if (a1) { buf_st128<2>(rdm, o16 + 1024u, t1); buf_st128<2>(rsum, o16 + 1024u, t1 - d1); }
+                            } else {
+                                if (a0) { buf_st128<2>(rdm, o16, d0); buf_st128<2>(rsum, o16, join96(s0, h0) - d0); }
+                                if (a1) { buf_st128<2>(rdm, o16 + 1024u, d1); buf_st128<2>(rsum, o16 + 1024u, join96(s1, h1) - d1); }
+                            }
                         }
                         p0 = c0; p1 = c1;
                     };

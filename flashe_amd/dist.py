@@ -470,6 +470,12 @@ class HipOps:
         else:
             self.engine.encrypt_batch_dev(it, idx_list, scheme, n, n_jobs, [self._a(r) for r in pts], pt_limbs, [self._a(r) for r in cts])
 
+    def encrypt_batch_decrypt(self, it, idx_list, scheme, n, n_jobs, pts, pt_limbs, cts, sum_out, dec_out):
+        """encrypt_batch with sum_out, and the decrypt of that sum (add = [idx_list[-1] + 1], minus = [idx_list[0]]) to dec_out: the
+        round of a rank that plays its clients and the arbiter, one launch where the library has one (Engine.encrypt_batch_sum_decrypt_dev)."""
+        self.engine.encrypt_batch_sum_decrypt_dev(it, idx_list, scheme, n, n_jobs, [self._a(r) for r in pts], pt_limbs,
+                                                  [self._a(r) for r in cts], self._a(sum_out), self._a(dec_out))
+
     def encrypt_range(self, it, idx, scheme, n, n_jobs, first, count, pt, pt_limbs, ct):
         """pt / ct address element `first`."""
         self.engine.encrypt_range_dev(it, idx, scheme, n, n_jobs, first, count, self._a(pt), pt_limbs, self._a(ct))
@@ -651,8 +657,18 @@ class ShardedRound:
     def encrypt_phase(self, it, pts, pt_limbs, partial_agg=False):
         """Every local client encrypts its vector (cipher idx = global client number).  partial_agg: the same launch also writes
         this rank's partial aggregate, the sum of its clients' ciphertexts, to self.partial ("each GPU encrypts
-        and locally mod-adds its share"), so that reduce_decrypt_phase(partial_agg=True) does not re-read the ciphertexts."""
-        if self.cpr:
+        and locally mod-adds its share"), so that reduce_decrypt_phase(partial_agg=True) does not re-read the ciphertexts.
+        Without an exchange this rank is the arbiter as well, and the decrypt of self.partial is the round's result: where the ops
+        have the call (HipOps.encrypt_batch_decrypt) the same launch writes it to self.result, and the reduce_decrypt_phase of the
+        same `it` that follows only hands it out."""
+        self._dec_it = None
+        if (partial_agg and self.cpr and not self.exchange and self.shard == "clients" and self.scheme == SCHEME_DOUBLE
+                and hasattr(self.ops, "encrypt_batch_decrypt")
+                and self._prefixes() == ([self.clients[-1] + 1], [self.clients[0]])):
+            self.ops.encrypt_batch_decrypt(it, self.clients, self.scheme, self.n, self.n_jobs, pts, pt_limbs, self.ct,
+                                           (self.partial, 0), (self.result, 0))
+            self._dec_it = it                            # self.result holds the decrypt of this round's self.partial
+        elif self.cpr:
             self.ops.encrypt_batch(it, self.clients, self.scheme, self.n, self.n_jobs, pts, pt_limbs, self.ct,
                                    sum_out=(self.partial, 0) if partial_agg else None)
         elif partial_agg:
@@ -669,7 +685,11 @@ class ShardedRound:
     def reduce_decrypt_phase(self, it, partial_agg=False):
         """Reduce (+ exchange) with the last reduce fused into the decrypt (one pass over its operands): without an exchange the
         C local ciphertexts, with one the W received pieces of the owned slice.  partial_agg: self.partial already holds the local
-        sum (encrypt_phase(partial_agg=True)): it is decrypted, or exchanged, as it is."""
+        sum (encrypt_phase(partial_agg=True)): it is decrypted, or exchanged, as it is -- or was decrypted by that launch already
+        (its note of `it`, good for ONE call: a replaced or skipped encrypt_phase, or a second call, gets a real decrypt)."""
+        dec_it, self._dec_it = getattr(self, "_dec_it", None), None
+        if partial_agg and not self.exchange and dec_it is not None and dec_it == it:
+            return self.result
         add_idx, minus_idx = self._prefixes()
         ops, n, W, L = self.ops, self.n, self.world, self.L
         if not self.exchange:

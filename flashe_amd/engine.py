@@ -953,6 +953,16 @@ class Engine:
         self._check(self._lib.flashe_encrypt_batch_sum_dev(self._h, it, scheme, n, n_jobs, len(idx_list), pi, pp, pt_limbs, pc,
                                                            self._ptr(sum_out)))
 
+    def encrypt_batch_sum_decrypt_dev(self, it, idx_list, scheme, n, n_jobs, pts, pt_limbs, cts, sum_out, dec_out):
+        """encrypt_batch_sum_dev followed by decrypt_dev(it, [idx_list[-1] + 1], [idx_list[0]], sum_out -> dec_out), the round of a device
+        that plays the clients and the arbiter: one launch at int_bits 128 for a run of consecutive clients with one-limb plaintexts
+        on a vector long enough to fill the device, those two calls (the same bytes) otherwise or with FLASHE_CHAIN_DEC=0."""
+        pi, _k = _u32_list(idx_list)
+        pp, _a = self._ptr_array(pts)
+        pc, _b = self._ptr_array(cts)
+        self._check(self._lib.flashe_encrypt_batch_sum_decrypt_dev(self._h, it, scheme, n, n_jobs, len(idx_list), pi, pp, pt_limbs, pc,
+                                                                   self._ptr(sum_out), self._ptr(dec_out)))
+
     def encrypt_batch_range_dev(self, it, idx_list, scheme, n, n_jobs, first, count, pts, pt_limbs, cts, sum_out=None):
         """encrypt_batch_dev on elements [first, first + count) of the n-element vectors -- the launch of a GPU that owns that slice of
         every client's vector (pointers address element `first`); sum_out (optional) receives the slice of the ciphertexts' sum."""

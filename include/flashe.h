@@ -83,7 +83,9 @@ typedef struct flashe_ctx flashe_ctx;
  *      flashe_quantize_encrypt_cohort_runs_dev / flashe_quantize_batch_encrypt_cohort_runs_dev (the cohort's chained launches for a round
  *      in which clients dropped out: any strictly ascending cipher indices); flashe_stage_row + flashe_stage_layers_dev and
  *      flashe_finish_row + flashe_finish_layers_dev (the aggregator's degree scaling either side of the fused client step: the multiply
- *      in the stage pass, the two divisions and the last round's model in the store + statistics pass) */
+ *      in the stage pass, the two divisions and the last round's model in the store + statistics pass);
+ *      flashe_encrypt_batch_sum_decrypt_dev (a co-located round's encrypts, their sum and the decrypt of the sum: one launch at
+ *      int_bits 128) */
 #define FLASHE_ABI_VERSION 4
 int flashe_abi_version(void);
 int flashe_device_count(int *count);
@@ -279,6 +281,25 @@ int flashe_encrypt_batch_range_dev(flashe_ctx *ctx, uint32_t iter, int scheme, u
 int flashe_encrypt_batch_sum_dev(flashe_ctx *ctx, uint32_t iter, int scheme, uint64_t n, uint32_t n_jobs, int n_vec,
                                  const uint32_t *idx, const uint64_t *const *pt_dev, int pt_limbs, uint64_t *const *ct_dev,
                                  uint64_t *sum_out_dev);
+
+/* The co-located round in one call (new): a device that plays the clients idx[0] .. idx[n_vec - 1] AND the arbiter -- a simulator, a
+ * cohort host -- asks for the ciphertexts, their sum and the DECRYPTED sum together.  For every shape the bytes of ct, sum_out and
+ * dec_out are those of
+ *     flashe_encrypt_batch_sum_dev(ctx, iter, scheme, n, n_jobs, n_vec, idx, pt_dev, pt_limbs, ct_dev, sum_out_dev), then
+ *     flashe_decrypt_dev(ctx, iter, {idx[n_vec - 1] + 1}, 1, {idx[0]}, 1, n, n_jobs, sum_out_dev, dec_out_dev)
+ * (jzf_aggregator.py:424-430, then jzf_flashe.py:633-666, :570-571 with nobody dropped; n_vec = 0: the zero sum, decrypted with empty
+ * lists).  int_bits = 128, double mask, one-limb plaintexts, one run of consecutive cipher indices, a vector long enough to fill the
+ * device and n <= 268,435,200: ONE launch -- the lane that stores an element's sum already holds sum + D, and stores it where
+ * flashe_encrypt_batch_sum_dev's launch stores the decrypt mask D, so the launch moves the same bytes and the round has no second
+ * pass.  Any other shape (other widths, two-limb plaintexts, the single mask, short or longer vectors, another PRF backend), or
+ * FLASHE_CHAIN_DEC=0 in the environment at flashe_ctx_create: literally those two calls.
+ * dec_out_dev (n x L limbs) must be aligned like a ciphertext vector (16 bytes at int_bits > 64) and must not be sum_out_dev, a
+ * ciphertext or a plaintext, and idx[n_vec - 1] + 1 must fit 32 bits: FLASHE_EINVAL, nothing written.  The one launch neither uses nor
+ * touches the ctx's chain decrypt mask and keeps no state: it may be captured into a graph.  The arbiter's decrypt of a sum it RECEIVED
+ * (flashe_decrypt_dev after flashe_encrypt_batch_sum_dev on another call or ctx) is unchanged. */
+int flashe_encrypt_batch_sum_decrypt_dev(flashe_ctx *ctx, uint32_t iter, int scheme, uint64_t n, uint32_t n_jobs, int n_vec,
+                                         const uint32_t *idx, const uint64_t *const *pt_dev, int pt_limbs, uint64_t *const *ct_dev,
+                                         uint64_t *sum_out_dev, uint64_t *dec_out_dev);
 
 /* General batched form (new): every entry is one piece of mask arithmetic on elements
  * [first, first + count) of an n-element vector,
