@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""A federation of ten clients simulated on ONE GPU: ten small PyTorch models in, the new global model out.
+"""A federation of ten clients simulated on ONE GPU: ten PyTorch models of eight million parameters in, the new global model out.
 
 FlasheCohort takes one Weights per client (the parameters as they are, read through DLPack), runs the clients' quantise + encrypt as one
-chained launch where the model is long enough to fill the chip (shorter models take the staged form: `upload.path` says which), and
+chained launch where the model is long enough to fill the chip (this one is, un-batched, on 256 CUs; shorter models take the staged
+form: `upload.path` says which), and
 decrypt_unquantize writes the new global model into `out`.  The result is bit for bit what ten FlasheClients produce one after the other,
 which this example checks.
 
@@ -17,10 +18,12 @@ which this example checks.
   --drop i,j   clients i and j miss the round (dropout-aware decrypt is what FLASHE is for): quantize_encrypt(present=...) takes the
                Weights of the clients that report, and at --bits > 64 the round is still one chained launch, over present + runs PRF
                streams, whose decrypt mask is that of the telescoped index lists; the new global model is what the present clients'
-               own steps and a decrypt told who uploaded (set_idx_list(present)) give, which this example checks
+               own steps and a decrypt told who uploaded (set_idx_list(present)) give, which this example checks; with --compact at
+               --bits 16 / 20 / 23 / 24 / 32 the gapped round is one chained launch too (`upload.path` is "cohort-chain"), without a mask:
+               the decrypt of the sum takes the telescoped lists
   --rng philox the stochastic-rounding draws come from one np.random.Generator per client instead of NumPy's global stream
                (quantize_encrypt(rng=[...])): counter-based Philox generators, whose draws for the whole cohort are ONE asynchronous
-               launch on the device (models of 65,536 values or more: this example's hold 126,666) and whose advanced states come back
+               launch on the device (models of 65,536 values or more: this example's hold 8,036,426) and whose advanced states come back
                -- the sequential clients below draw from identically seeded generators and must leave them in the same place;
                --rng pcg64 takes np.random.default_rng(seed) itself (PCG64, a 128-bit LCG): every lane of ONE launch jumps to its first
                draw and walks a fixed stride, and the states come back the same way; --rng sfc64 takes any other Generator: the same
@@ -47,7 +50,8 @@ class Weights:
 
 def make_model(seed):
     torch.manual_seed(seed)
-    return torch.nn.Sequential(torch.nn.Conv2d(3, 16, 5), torch.nn.ReLU(), torch.nn.Flatten(), torch.nn.Linear(16 * 28 * 28, 10)).cuda()
+    return torch.nn.Sequential(torch.nn.Conv2d(3, 16, 5), torch.nn.ReLU(), torch.nn.Flatten(), torch.nn.Linear(16 * 28 * 28, 640), torch.nn.ReLU(),
+                               torch.nn.Linear(640, 10)).cuda()
 
 
 def values(dv):
@@ -133,9 +137,9 @@ def main():
     if dropped:
         print(f"new global model equals {len(present)} FlasheClient steps and their dropout-aware decrypt bit for bit")
         return
-    mean = sum(l["3.bias"].double() for l in layers) / C
-    print("new global model equals ten FlasheClient steps bit for bit; |3.bias - mean of the clients'| <=",
-          float((new_global["3.bias"].double() - mean).abs().max()))
+    mean = sum(l["5.bias"].double() for l in layers) / C
+    print("new global model equals ten FlasheClient steps bit for bit; |5.bias - mean of the clients'| <=",
+          float((new_global["5.bias"].double() - mean).abs().max()))
 
 
 if __name__ == "__main__":

@@ -1215,7 +1215,7 @@ def compact_cohort_admission_length(cu_count, int_bits, n_jobs):
 
 
 def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, mask="double", num_clients=None, precompute=False, chain=True,
-                location_masks=False, compact=False, n_jobs=None, cohort_masks=False, present=None):
+                location_masks=False, compact=False, n_jobs=None, cohort_masks=False, present=None, compact_runs=False):
     """The engine-free part of FlasheCohort.quantize_encrypt: checks that the clients' Weights describe one model (the same layer names
     in the same walking order with the same shapes: ValueError naming the client and the layer otherwise; a sparse upload -- a 'zzz'
     layer or location masks -- is a TypeError), lays out the shared layer table and the client-major draws, and picks the path:
@@ -1241,8 +1241,11 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
     Weights each; ValueError for a list that is unsorted, repeats a client, is negative or of another length) keeps every rule above with
     C = the clients present.  Positions in SEVERAL runs ({0,1,3,4}) still take "cohort-chain" at int_bits > 64
     (flashe_quantize_encrypt_cohort_runs_dev / flashe_quantize_batch_encrypt_cohort_runs_dev: present + runs PRF streams, at most 144 of
-    them) and "prepared-cohort" with the present clients' masks; the compact chain takes one run only, so a gapped compact cohort runs
-    "staged-chain", as does one of more than 144 streams.  present=None and present=all positions give equal plans.
+    them) and "prepared-cohort" with the present clients' masks, and a cohort of more than 144 streams runs "staged-chain".  A gapped
+    COMPACT cohort depends on compact_runs, whether the engine has the gapped compact launch
+    (flashe_quantize_encrypt_cohort_runs_u32_dev): False (the default) plans it "staged-chain" -- the compact chain then takes one run
+    only --, True lets it through to the 144-stream rule like the wide one.  present=None and present=all positions give equal plans,
+    whatever compact_runs says.
     Touches no device.  The library's own answer stays the last word: a "cohort-chain" plan it declines runs "staged-chain", a
     "prepared-cohort" one "prepared-staged"."""
     if len(weights_list) < 1:
@@ -1298,7 +1301,7 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
         path, reason = STAGED_CHAIN, "the vector does not fill the chip uncut"
     elif not compact and (n_elems < cohort_admission_length(cu_count) or n_elems > 2 ** 32):
         path, reason = STAGED_CHAIN, "the vector does not fill the chip uncut"
-    elif runs > 1 and compact:
+    elif runs > 1 and compact and not compact_runs:
         path, reason = STAGED_CHAIN, f"clients dropped out ({runs} runs of indices): the compact chain takes one run of consecutive clients"
     elif C + runs > _COHORT_MAX_STREAMS:
         path, reason = STAGED_CHAIN, f"clients dropped out: {C} clients in {runs} runs need more than {_COHORT_MAX_STREAMS} PRF streams"
@@ -1350,7 +1353,9 @@ class FlasheCohort(object):
     A round in which clients DROPPED OUT is quantize_encrypt(..., present=[positions]): the present clients' steps one after the other, and
     at int_bits > 64 still one chained launch (flashe_quantize_encrypt_cohort_runs_dev / flashe_quantize_batch_encrypt_cohort_runs_dev)
     over present + runs PRF streams that writes the decrypt mask of the telescoped index lists, so decrypt_unquantize() of that round
-    stays one pass; a gapped compact cohort runs the staged form.
+    stays one pass.  A gapped compact cohort at int_bits 16 / 20 / 23 / 24 / 32 is one chained launch too
+    (flashe_quantize_encrypt_cohort_runs_u32_dev, the same streams), on an engine that has it; no mask is kept there, and
+    decrypt_unquantize() decrypts the sum with the telescoped lists.
     A precompute job ("precompute": {"enable": true}) calls prepare_encrypt() in idle time: the next round's masks of all clients as one
     chain of n_local + 1 streams, held by the cohort; the next quantize_encrypt is then ONE online launch with no AES ("prepared-cohort")
     at any int_bits, batched or not, compact or not.  Without that call the clients' own masks run "per-client" as before."""
@@ -1401,7 +1406,8 @@ class FlasheCohort(object):
         return plan_cohort(weights_list, ld.int_bits, ld.cipher.engine.cu_count, element_bits=ld.quantizer.element_bits, batch=bool(ld.batch),
                            mask=ld.cipher.masking_scheme, num_clients=self.num_clients, precompute=bool(ld.precompute),
                            chain=os.environ.get("FLASHE_CHAIN", "1") != "0", location_masks=ld.cipher.masks is not None, compact=self.compact,
-                           n_jobs=_cipher_mod.N_JOBS, cohort_masks=self._masks is not None, present=present)
+                           n_jobs=_cipher_mod.N_JOBS, cohort_masks=self._masks is not None, present=present,
+                           compact_runs=hasattr(ld.cipher.engine, "quantize_encrypt_cohort_runs_u32_dev"))
 
     def prepare_encrypt(self):
         """A precompute job's idle-time step for the whole cohort.  Double mask: the encrypt masks of iteration iter_index + 1 for all
@@ -1637,8 +1643,11 @@ class FlasheCohort(object):
         dmask = DeviceVector(eng, n_elems) if self.n_local == self.num_clients and not self.compact else None
         outs, mask_buf = [v.buf for v in cts], dmask.buf if dmask is not None else None
         idxs = [self.first_idx + p for p in plan.present]
-        if self.compact:
-            # (one run: plan_cohort sends a gapped compact cohort to the staged form)
+        if self.compact and by_idx and hasattr(eng, "quantize_encrypt_cohort_runs_u32_dev"):
+            took = eng.quantize_encrypt_cohort_runs_u32_dev(c.iter_index, idxs, n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du, outs,
+                                                            psum.buf)
+        elif self.compact:
+            # (one run: without the gapped compact launch plan_cohort sends a gapped compact cohort to the staged form)
             took = eng.quantize_encrypt_cohort_u32_dev(c.iter_index, idxs[0], n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du, outs,
                                                        psum.buf)
         elif by_idx and ld.batch:

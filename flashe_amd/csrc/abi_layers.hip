@@ -763,6 +763,25 @@ int flashe_quantize_encrypt_cohort_runs_dev(flashe_ctx *ctx, uint32_t iter, cons
     return cohort_launched(ctx, launch_prf_cohort_sum(ctx->env, iter, n_clients, idx, cc, nullptr, u_dev, ct_dev, sum_out_dev, n, n_jobs, dmask_dev), who, "cohort");
 }
 
+// the compact layout at int_bits <= 32 (one run: prf_small_cohort_kernel, bit for bit; several runs: prf_small_cohort_runs_kernel): uint32
+// ciphertexts and their uint32 sum, no decrypt mask
+int flashe_quantize_encrypt_cohort_runs_u32_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                                const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                                int element_bits, const double *u_dev, uint32_t *const *ct_dev, uint32_t *sum_out_dev)
+{
+    CHECK_CTX(ctx);
+    static const char who[] = "flashe_quantize_encrypt_cohort_runs_u32_dev";
+    bool too_many = false;
+    int rc = cohort_check_runs(ctx, who, idx, n_clients, n, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, &too_many);
+    if (rc) return rc;
+    if (n_jobs == 0) return fail(ctx, FLASHE_EINVAL, "n_jobs must be >= 1");
+    if ((rc = cohort_check_outs<uint32_t>(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, nullptr))) return rc;
+    if (too_many || flashe_ctx_compact_layout(ctx) != 1 || !small_cohort_admits(ctx->env, n_clients, n, n_jobs, true)) return cohort_declined(ctx, who, "compact cohort");
+    CohortCodec cc{};
+    if ((rc = cohort_stage(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, cc))) return rc;
+    return cohort_launched(ctx, launch_small_cohort_sum(ctx->env, iter, n_clients, idx, cc, u_dev, ct_dev, sum_out_dev, n, n_jobs), who, "compact cohort");
+}
+
 int flashe_quantize_batch_encrypt_cohort_runs_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n_values, uint64_t n_elems,
                                                   uint32_t n_jobs, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
                                                   const int32_t *src_dtype, int element_bits, int field_bits, const double *u_dev, uint64_t *const *ct_dev,

@@ -121,8 +121,8 @@ hipError_t launch_prf_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec,
 // 128 / int_bits elements, per the chunking of n_jobs) for each of the chip's waves.
 bool small_cohort_admits(const LaunchEnv &env, int n_vec, uint64_t n, uint32_t n_jobs, bool summed);
 // The same cohort at int_bits <= 32 in the compact layout (prf_small_cohort_kernel): uint32 ciphertexts and their uint32 sum from the
-// floats, admitted where the summed compact chain is -- small_cohort_admits(summed) and consecutive idx below 2^32 - 1.
-// hipErrorNotSupported: nothing launched.
+// floats, admitted where the summed compact chain is -- small_cohort_admits(summed) and strictly ascending idx below 2^32 - 1 whose
+// streams fit the table (cohort_streams.h; several runs: prf_small_cohort_runs_kernel).  hipErrorNotSupported: nothing launched.
 hipError_t launch_small_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
                                    uint32_t *const *out_dev, uint32_t *sum_out_dev, uint64_t n, uint32_t n_jobs);
 // The sparse job's cohort at the same widths (prf_small_sparse_cohort_kernel): out_dev[c][k] = SINGLE-mask encrypt (idx[c]; any indices) of the

@@ -1300,12 +1300,17 @@ __device__ __forceinline__ void direct32_put(uint32_t *__restrict__ q, const uin
 // the streams software-pipelined against each other (the next stream's first lookups issued before this stream's outputs): 0.2769
 // against 0.2740 at int_bits 20, 127 VGPRs -- what is left between two steps is not what holds these kernels back.
 // (OT = uint64_t: the outputs in the one-limb layout, direct32_put's uint64 form)
-template <int B, bool SINGLE, class SRC = void, class OT = uint32_t>
+// (GP = CohortGaps: the streams of a cohort in several runs -- a stream's output is cohort_stream_link(*gaps, c), scalar; one that completes
+// none only leaves its slots behind.  The other instantiations see neither the parameter nor the pointer.)
+template <int B, bool SINGLE, class SRC = void, class OT = uint32_t, class GP = void>
 __device__ __forceinline__ void small_chain_fast32(const RoundKeys &rk, const LaneRegs lr, const uint32_t *pre_lds, int sbase, int n_streams,
                                                    const uint64_t *const *in_tab, uint64_t *const *out_tab, const CtrVar &xA, const CtrVar &xB,
                                                    uint64_t kA, uint64_t kB, uint32_t *sum32, bool prio,
-                                                   const uint32_t *__restrict__ te4, bool uni, uint32_t x3A, uint32_t x3B, const SRC *src = nullptr)
+                                                   const uint32_t *__restrict__ te4, bool uni, uint32_t x3A, uint32_t x3B, const SRC *src = nullptr,
+                                                   const GP *gaps = nullptr)
 {
+    constexpr bool GAPS = !std::is_void_v<GP>;
+    static_assert(!GAPS || !SINGLE, "several runs are a form of the double-mask chain");
     constexpr int M = 128 / B;
     constexpr uint32_t mask = B >= 32 ? 0xffffffffu : ((1u << (B & 31)) - 1u);
     uint32_t psA[M], psB[M], accA[M], accB[M];
@@ -1343,7 +1348,8 @@ __device__ __forceinline__ void small_chain_fast32(const RoundKeys &rk, const La
         const CtrPrefix pre = prefix_of(pv);
         // the next stream's prefix: on its way under this stream's rounds (the last step re-reads its own)
         pv = *reinterpret_cast<const uint4 *>(pre_lds + 4 * (sbase + (c + 1 < n_streams ? c + 1 : c)));
-        const int link = SINGLE ? c : c - 1;
+        int link = SINGLE ? c : c - 1;
+        if constexpr (GAPS) link = cohort_stream_link(*gaps, c);
         DirectPt<M> dA{}, dB{};
         if (link >= 0) {
             if constexpr (std::is_void_v<SRC>) {
@@ -1356,7 +1362,7 @@ __device__ __forceinline__ void small_chain_fast32(const RoundKeys &rk, const La
             }
         }
         uint32_t s[2][4];
-        if (uni) {
+        if (!GAPS && uni) {
             // both blocks' sixty-four counters share bytes 1 .. 3 (x3A / x3B): the second counter shortcut of the wide kernel, 196 lookups
             // per block instead of 208 (the wave-uniform part of rounds 1-2 through the scalar cache, device_common.h)
             const CtrUniform UA = ctr_uniform(rk, te4, pre, x3A), UB = ctr_uniform(rk, te4, pre, x3B);
@@ -1393,8 +1399,9 @@ __device__ __forceinline__ u128 slot_diff(u128 prev, u128 cur, u128 top, int b)
 template <bool PAIR, class ET = uint64_t, int B = 0>
 __global__ __launch_bounds__(kSmallThreads) void prf_small_chain_kernel(const RoundKeys rk, const SmallChainTable tb, int n_chains, const SmallParams p)
 {
-    constexpr bool COHORT = false;
+    constexpr bool COHORT = false, GAPS = false;
     const CohortCodec cc{};
+    const CohortGaps cg{};
 #include "prf_small_chain_body.inc"
 }
 
@@ -1408,7 +1415,21 @@ template <int B>
 __global__ __launch_bounds__(kSmallThreads) void prf_small_cohort_kernel(const RoundKeys rk, const SmallChainTable tb, int n_chains, const SmallParams p,
                                                                           const CohortCodec cc)
 {
-    constexpr bool PAIR = true, COHORT = true;
+    constexpr bool PAIR = true, COHORT = true, GAPS = false;
+    using ET = uint32_t;
+    const CohortGaps cg{};
+#include "prf_small_chain_body.inc"
+}
+
+// GAPS: the same cohort for cipher indices in SEVERAL runs -- a round in which clients dropped out (cohort_streams.h; GAPS in
+// prf_small_chain_body.inc).  The one chain's streams are the |P| + runs of tb.idx; cg tells which of them complete an output, and the launch
+// still writes every present client's uint32 ciphertext and their sum (the decrypt takes the telescoped lists; no mask at these widths).
+// A separate kernel: the one-run launches keep their code objects.
+template <int B>
+__global__ __launch_bounds__(kSmallThreads) void prf_small_cohort_runs_kernel(const RoundKeys rk, const SmallChainTable tb, int n_chains, const SmallParams p,
+                                                                               const CohortCodec cc, const CohortGaps cg)
+{
+    constexpr bool PAIR = true, COHORT = true, GAPS = true;
     using ET = uint32_t;
 #include "prf_small_chain_body.inc"
 }
@@ -1430,8 +1451,9 @@ template <int B>
 __global__ __launch_bounds__(kSmallThreads) void prf_small_sparse_cohort_kernel(const RoundKeys rk, const SmallChainTable tb, int n_chains, const SmallParams p,
                                                                                  const CohortCodec cc, const SparseCohortTail tail)
 {
-    constexpr bool PAIR = true, COHORT = true;
+    constexpr bool PAIR = true, COHORT = true, GAPS = false;
     using ET = uint64_t;
+    const CohortGaps cg{};
     if (blockIdx.x == 0 && threadIdx.x < static_cast<unsigned>(tail.n_clients)) {
         const int c = threadIdx.x;
         const double v = tail.zzz[c], u = tail.u_n[static_cast<uint64_t>(c) * tail.u_stride];
@@ -1952,6 +1974,21 @@ bool cohort_chain_admits(const LaunchEnv &env, int n_vec, uint64_t n_elems, int 
     return (n_elems + 255) / 256 >= 2 * static_cast<uint64_t>(env.num_cus) * (kPrfThreads / 64);
 }
 
+// CohortGaps of the streams of a cohort in several runs: two bits per stream and, per word of sixteen, the outputs completed before it
+static CohortGaps cohort_gaps_of(const flashe_tables::CohortStreams &st)
+{
+    CohortGaps cg{};
+    const int n_streams = static_cast<int>(st.idx.size());
+    cg.n_streams = n_streams;
+    int done = 0;                        // outputs completed by the streams so far (cohort_streams: links are finished in turn)
+    for (int s = 0; s < n_streams; s++) {
+        if ((s & 15) == 0) cg.base[s >> 6] |= static_cast<uint32_t>(done) << (((s >> 4) & 3) * 8);
+        cg.bits[s >> 4] |= static_cast<uint32_t>(st.bits[s] & 3u) << ((s & 15) * 2);
+        if (st.bits[s] & flashe_tables::kStreamCompletes) done++;
+    }
+    return cg;
+}
+
 // The shape launch_prf_batch_sum admits (one uncut summed double-mask chain of whole vectors), with the quantising front end per output;
 // cb: the batched form (prf_chain_cohort_batch_kernel), the same uncut chain over the n batched elements with one draw per VALUE.
 hipError_t launch_prf_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const CohortBatch *cb,
@@ -1980,14 +2017,7 @@ hipError_t launch_prf_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec,
     masks_of(env.b, &lo, &hi);
     const dim3 grid(static_cast<unsigned>(std::min<uint64_t>(tiles, static_cast<uint64_t>(env.num_cus)))), block(kPrfThreads);
     if (st.runs > 1) {
-        CohortGaps cg{};
-        cg.n_streams = n_streams;
-        int done = 0;                        // outputs completed by the streams so far (cohort_streams: links are finished in turn)
-        for (int s = 0; s < n_streams; s++) {
-            if ((s & 15) == 0) cg.base[s >> 6] |= static_cast<uint32_t>(done) << (((s >> 4) & 3) * 8);
-            cg.bits[s >> 4] |= static_cast<uint32_t>(st.bits[s] & 3u) << ((s & 15) * 2);
-            if (st.bits[s] & flashe_tables::kStreamCompletes) done++;
-        }
+        const CohortGaps cg = cohort_gaps_of(st);
 #define COHORT_BATCH_RUNS(BS) hipLaunchKernelGGL((prf_chain_cohort_batch_runs_kernel<kPrfThreads, BS>), grid, block, 0, env.stream, env.rk, tb, 1, 0, iter, lo, hi, env.te0_dev, dmask_dev, cc, *cb, cg)
         switch (bs) {
         case 0: hipLaunchKernelGGL((prf_chain_cohort_runs_kernel<kPrfThreads>), grid, block, 0, env.stream, env.rk, tb, 1, 0, iter, lo, hi, env.te0_dev, dmask_dev, cc, cg); break;
@@ -2596,30 +2626,41 @@ static SmallParams small_cohort_params(const LaunchEnv &env, uint32_t iter, int 
 }
 
 // The summed compact chain over whole vectors with the quantising front end per output (prf_small_cohort_kernel): the admission of the
-// summed chain of launch_small_chains -- a compiled-in width, one uncut run of consecutive clients, enough AES blocks for the paired
-// kernel -- and launch_prf_cohort_sum's contract: hipErrorNotSupported = nothing launched.
+// summed chain of launch_small_chains -- a compiled-in width, one uncut chain, enough AES blocks for the paired kernel -- and
+// launch_prf_cohort_sum's contract: any strictly ascending idx (one run launches the kernel it always has with the table it always had,
+// several runs prf_small_cohort_runs_kernel over |P| + runs streams), hipErrorNotSupported = nothing launched.
 hipError_t launch_small_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
                                    uint32_t *const *out_dev, uint32_t *sum_out_dev, uint64_t n, uint32_t n_jobs)
 {
     if (!small_cohort_admits(env, n_vec, n, n_jobs, true) || !sum_out_dev || !u_dev || cc.n_layers < 1) return hipErrorNotSupported;
-    for (int v = 1; v < n_vec; v++) if (idx[v] != idx[v - 1] + 1u) return hipErrorNotSupported;
-    if (idx[n_vec - 1] == 0xffffffffu) return hipErrorNotSupported;
+    flashe_tables::CohortStreams st;
+    if (flashe_tables::cohort_streams(idx, n_vec, kMaxLinks + kMaxChains, st) != flashe_tables::kCohortStreamsOk) return hipErrorNotSupported;
     for (int v = 0; v < n_vec; v++) if (!out_dev[v]) return hipErrorNotSupported;
+    const int n_streams = static_cast<int>(st.idx.size());      // (one run: idx and the index behind its last, n_vec + 1 streams)
     uint64_t blocks;
     const SmallParams p = small_cohort_params(env, iter, n_vec, n, n_jobs, &blocks);
     SmallChainTable tb{};
     tb.first[0] = 0; tb.count[0] = n; tb.blk_first[0] = 0; tb.blk_count[0] = blocks;
     tb.len[0] = static_cast<uint8_t>(n_vec);
-    for (int s = 0; s < n_vec; s++) tb.idx[s] = idx[s];
-    tb.idx[n_vec] = idx[n_vec - 1] + 1u;
+    for (int s = 0; s < n_streams; s++) tb.idx[s] = st.idx[s];
     for (int l = 0; l < n_vec; l++) {
         tb.in[l] = reinterpret_cast<const uint64_t *>(u_dev + static_cast<uint64_t>(l) * n);       // the link's draws (CohortDirect, CohortWalk)
         tb.out[l] = reinterpret_cast<uint64_t *>(out_dev[l]);
     }
     tb.sum_out[0] = reinterpret_cast<uint64_t *>(sum_out_dev);
     const uint64_t tiles = (blocks + 127) / 128, cus = static_cast<uint64_t>(env.num_cus);
-    tb.wend[0] = tiles * static_cast<uint64_t>(n_vec + 1);
+    tb.wend[0] = tiles * static_cast<uint64_t>(n_streams);
     const int grid = static_cast<int>(tiles < cus ? tiles : cus);
+    if (st.runs > 1) {
+        const CohortGaps cg = cohort_gaps_of(st);
+        switch (env.b) {
+#define FLASHE_FIXED32(B) case B: hipLaunchKernelGGL((prf_small_cohort_runs_kernel<B>), dim3(grid), dim3(kSmallThreads), 0, env.stream, env.rk, tb, 1, p, cc, cg); break;
+            FLASHE_FIXED32_WIDTHS(FLASHE_FIXED32)
+#undef FLASHE_FIXED32
+        default: return hipErrorNotSupported;
+        }
+        return hipGetLastError();
+    }
     switch (env.b) {
 #define FLASHE_FIXED32(B) case B: hipLaunchKernelGGL((prf_small_cohort_kernel<B>), dim3(grid), dim3(kSmallThreads), 0, env.stream, env.rk, tb, 1, p, cc); break;
         FLASHE_FIXED32_WIDTHS(FLASHE_FIXED32)

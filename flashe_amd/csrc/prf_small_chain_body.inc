@@ -1,13 +1,21 @@
 // The body of prf_small_chain_kernel<PAIR, ET, B> and prf_small_cohort_kernel<B> (kernels.hip), included INSIDE each kernel: the kernel
-// defines PAIR, ET, B and COHORT as compile-time constants and has the arguments rk, tb, n_chains, p and cc in scope (included text
+// defines PAIR, ET, B, COHORT and GAPS as compile-time constants and has the arguments rk, tb, n_chains, p, cc and cg in scope (included text
 // compiles to exactly the kernel it was before: prf_chain_body.inc).
 // COHORT (PAIR, the compact layout at a compile-time width, one summed double-mask chain over whole vectors): the plaintext of output
 // `link` at element k is the quantisation of client link's float k (CohortCodec cc; tb.in[link] = that client's draws) -- whole tiles
 // through CohortDirect, the tiles that walk through CohortWalk.
 // COHORT with ET = uint64_t (prf_small_sparse_cohort_kernel<B>, the sparse job's cohort): the same front end on SINGLE-mask chains without a
 // sum, the outputs in the one-limb layout -- a whole block's M words go out as M uint64 elements (direct32_put's uint64 form).
+// GAPS (COHORT with ET = uint32_t only, prf_small_cohort_runs_kernel<B>): the cohort's cipher indices form SEVERAL runs -- clients dropped out.
+// The one chain's streams are the cg.n_streams of tb.idx (cohort_streams.h); the output a stream completes is cohort_stream_link(cg, c), a
+// scalar lookup in the kernel's arguments at a wave-uniform index, and a stream that completes none (it only opens a run) requests no
+// float and no draw, stores nothing and adds nothing to the running sums -- its slots are kept for the next step.  A completing stream's
+// predecessor in the list is stream s - 1, so prevA / prevB (psA / psB in small_chain_fast32) mean what they always do.  Every branch on
+// GAPS is an `if constexpr` or a conditional on the constant: the other instantiations compile to the code objects they were.
     static_assert(!COHORT || (PAIR && B != 0 && B <= 32), "the cohort front end rides on the paired chain at a compile-time width");
+    static_assert(!GAPS || (COHORT && sizeof(ET) == 4), "several runs of indices are a form of the summed compact cohort chain");
     (void)cc;
+    (void)cg;
     constexpr bool LIMB_OUT = COHORT && sizeof(ET) == 8;
     static_assert(B == 0 || (PAIR && ((sizeof(ET) == 4 && B <= 32) || (sizeof(ET) == 8 && (B == 64 || LIMB_OUT)))), "compile-time widths: the paired kernel, compact layout or int_bits 64");
     constexpr uint32_t WAVES = kSmallThreads / 64, TILE = PAIR ? 128u : 64u;
@@ -21,7 +29,7 @@
     const LaneRegs lr = lane_regs(tab);
     {
         const int last = n_chains - 1;
-        const int n_streams = tb.sbase[last] + tb.len[last] + ((tb.flags[last] & 1) ? 0 : 1);
+        const int n_streams = GAPS ? cg.n_streams : tb.sbase[last] + tb.len[last] + ((tb.flags[last] & 1) ? 0 : 1);
         for (int s = threadIdx.x; s < n_streams; s += kSmallThreads) {
             const CtrPrefix c = ctr_prefix(rk, lr, iter, tb.idx[s], 0u);          // n < 2^32 (host-checked): the high counter word is 0
             *reinterpret_cast<uint4 *>(pre_lds + 4 * s) = make_uint4(c.u[0], c.u[1], c.u[2], c.u[3]);
@@ -29,7 +37,7 @@
         if (threadIdx.x < static_cast<unsigned>(n_chains)) {                          // this workgroup's tiles of every chain (see prf_chain_kernel)
             const int i = threadIdx.x;
             const uint64_t Wt = tb.wend[last], cw = i ? tb.wend[i - 1] : 0;
-            const uint32_t w = tb.len[i] + ((tb.flags[i] & 1) ? 0u : 1u);
+            const uint32_t w = GAPS ? static_cast<uint32_t>(cg.n_streams) : tb.len[i] + ((tb.flags[i] & 1) ? 0u : 1u);      // (GAPS: tiles are weighted by the streams they compute)
             uint64_t a, b, T;
             if (Wt <= 0xffffffffull && gridDim.x <= 0xffffu) {
                 const uint32_t W32 = static_cast<uint32_t>(Wt), G = gridDim.x, g = blockIdx.x, c32 = static_cast<uint32_t>(cw);
@@ -73,7 +81,7 @@
         const uint64_t Bw = (uniform64(d_tlo[cur]) + (q - cbeg)) * TILE;             // the tile's first block (chain-local)
         const int link0 = tb.link0[cur], sbase = tb.sbase[cur];
         const bool single = tb.flags[cur] & 1;
-        const int n_streams = tb.len[cur] + (single ? 0 : 1);
+        const int n_streams = GAPS ? cg.n_streams : tb.len[cur] + (single ? 0 : 1);
         // per-lane block(s): chunk arithmetic and the counter-dependent quarter of round 1, once for all streams
         const bool vA = Bw + lane < blk_count, vB = PAIR && Bw + 64u + lane < blk_count;
         uint64_t j0A = 0, j0B = 0;
@@ -127,12 +135,17 @@
                 // it saves (tests/perf/experiments/README.md)
                 constexpr int kU2MaxStreams = 2;
                 const uint32_t bA = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(ctrA)), bB = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(ctrB));
-                const bool uni = n_streams <= kU2MaxStreams && __ballot(ctrA - bA == lane && ctrB - bB == lane) == ~0ull &&
+                const bool uni = !GAPS && n_streams <= kU2MaxStreams && __ballot(ctrA - bA == lane && ctrB - bB == lane) == ~0ull &&
                                  (bA & 255u) <= 192u && (bB & 255u) <= 192u;
                 if constexpr (LIMB_OUT) {
                     const CohortDirect csrc{cc, tb.in + link0, link0, {layA, layB}};
                     small_chain_fast32<B, true, CohortDirect, uint64_t>(rk, lr, pre_lds, sbase, n_streams, tb.in + link0, tb.out + link0, xA, xB, j0A - first, j0B - first,
                                                                         nullptr, p.swp_prio != 0, p.te0, uni, bA ^ rk.w[3], bB ^ rk.w[3], &csrc);
+                    continue;
+                } else if constexpr (GAPS) {                       // (several runs never take the second counter shortcut: more than two streams)
+                    const CohortDirect csrc{cc, tb.in + link0, link0, {layA, layB}};
+                    small_chain_fast32<B, false, CohortDirect, uint32_t, CohortGaps>(rk, lr, pre_lds, sbase, n_streams, tb.in + link0, tb.out + link0, xA, xB, j0A - first, j0B - first,
+                                                                                     sum32, p.swp_prio != 0, p.te0, false, 0u, 0u, &csrc, &cg);
                     continue;
                 } else if constexpr (COHORT) {
                     const CohortDirect csrc{cc, tb.in + link0, link0, {layA, layB}};
@@ -151,7 +164,7 @@
             // two blocks per lane on the same prefix, one stream per step
             for (int c = 0; c < n_streams; c++) {
                 const CtrPrefix pre = load_prefix(pre_lds, sbase + c);
-                const int link = single ? c : c - 1;
+                const int link = GAPS ? cohort_stream_link(cg, c) : single ? c : c - 1;      // the output this stream completes
                 WalkPt ptA{}, ptB{};
                 DirectPt<MB> dA{}, dB{};
                 u64x2 qA = {0ull, 0ull}, qB = {0ull, 0ull};

@@ -769,6 +769,19 @@ class Engine:
                                                                self._ptr(sum_out), self._ptr(dmask))
         return self._took(rc)
 
+    def quantize_encrypt_cohort_runs_u32_dev(self, it, idx, n, n_jobs, layers, srcs, dtypes, element_bits, u, cts, sum_out):
+        """quantize_encrypt_cohort_u32_dev for a round in which clients dropped out (flashe_quantize_encrypt_cohort_runs_u32_dev, int_bits
+        16 / 20 / 23 / 24 / 32): idx as in quantize_encrypt_cohort_runs_dev, cts and sum_out uint32 vectors of n elements, no decrypt mask
+        (decrypt the sum with telescope(idx)).  One run of consecutive indices is quantize_encrypt_cohort_u32_dev bit for bit.  Returns
+        False -- nothing was launched -- when the library declines the shape (FLASHE_ENOTSUP: also more than 144 streams), True otherwise."""
+        arr, nl = self._tensor_layers(layers)
+        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
+        pc, _k = self._ptr_array(cts)
+        pi, _ki = self._cohort_idx(idx, C)
+        rc = self._lib.flashe_quantize_encrypt_cohort_runs_u32_dev(self._h, it, pi, C, int(n), n_jobs, arr, nl, ps, pd, element_bits, self._ptr(u),
+                                                                   pc, self._ptr(sum_out))
+        return self._took(rc)
+
     def quantize_batch_encrypt_cohort_runs_dev(self, it, idx, n_values, n_elems, n_jobs, layers, srcs, dtypes, element_bits, field_bits, u, cts,
                                                sum_out, dmask=None):
         """quantize_batch_encrypt_cohort_dev with the cipher indices of the clients that report

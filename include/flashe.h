@@ -81,7 +81,8 @@ typedef struct flashe_ctx flashe_ctx;
  *      flashe_quantize_combine_cohort_dev / flashe_quantize_combine_cohort_u32_dev / flashe_quantize_batch_combine_cohort_dev (a
  *      precompute job's cohort online: C float models + C caller-held masks to C ciphertexts and their sum in one pass, no AES);
  *      flashe_quantize_encrypt_cohort_runs_dev / flashe_quantize_batch_encrypt_cohort_runs_dev (the cohort's chained launches for a round
- *      in which clients dropped out: any strictly ascending cipher indices); flashe_stage_row + flashe_stage_layers_dev and
+ *      in which clients dropped out: any strictly ascending cipher indices) and flashe_quantize_encrypt_cohort_runs_u32_dev (the same
+ *      round in the compact layout, int_bits 16 / 20 / 23 / 24 / 32); flashe_stage_row + flashe_stage_layers_dev and
  *      flashe_finish_row + flashe_finish_layers_dev (the aggregator's degree scaling either side of the fused client step: the multiply
  *      in the stage pass, the two divisions and the last round's model in the store + statistics pass);
  *      flashe_encrypt_batch_sum_decrypt_dev (a co-located round's encrypts, their sum and the decrypt of the sum: one launch at
@@ -752,6 +753,20 @@ int flashe_quantize_batch_encrypt_cohort_runs_dev(flashe_ctx *ctx, uint32_t iter
                                                   uint32_t n_jobs, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
                                                   const int32_t *src_dtype, int element_bits, int field_bits, const double *u_dev, uint64_t *const *ct_dev,
                                                   uint64_t *sum_out_dev, uint64_t *dmask_dev);
+/* The compact cohort for a round in which clients DROPPED OUT (new), jzf_flashe.py:349-367, jzf_aggregator.py:424-430:
+ * flashe_quantize_encrypt_cohort_u32_dev with the cipher indices idx of the n_clients clients that report, strictly ascending, in place
+ * of first_idx; everything indexed by client counts the clients of idx, as in flashe_quantize_encrypt_cohort_runs_dev.  ONE chained launch
+ * over the |P| + runs streams of S = { s : s in P or s - 1 in P } writes ct_dev[c] (uint32, n elements: the values of
+ * flashe_quantize_encrypt_tensors_dev with cipher index idx[c]) and sum_out_dev = sum_c ct_dev[c] mod 2^b; no decrypt mask at these
+ * widths -- decrypt the sum with flashe_telescope(idx).  One run of consecutive indices launches exactly what
+ * flashe_quantize_encrypt_cohort_u32_dev launches and writes its bytes.
+ * FLASHE_EINVAL: idx NULL, not strictly ascending (unsorted, duplicates) or holding 2^32 - 1, n_jobs = 0, and the argument errors of
+ * flashe_quantize_encrypt_cohort_u32_dev.  FLASHE_ENOTSUP -- nothing launched, every output untouched -- outside that function's
+ * admission with n_clients = |P|, and when |P| + runs exceeds the 144 streams one launch holds; the caller then quantises per client and
+ * uses flashe_encrypt_batch_sum_u32_dev, which takes any indices.  The table uploads synchronise; not capturable. */
+int flashe_quantize_encrypt_cohort_runs_u32_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                                const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                                int element_bits, const double *u_dev, uint32_t *const *ct_dev, uint32_t *sum_out_dev);
 /* A precompute job's cohort (new), jzf_flashe.py:599-631, 456-488: every client computes its next round's encrypt mask in idle time and
  * its online step is a quantise plus a mask add.  For a cohort the masks are ONE chain of n_clients + 1 streams into vectors the caller
  * owns, mask[c][j] = term(iter, first_idx + c)[j] - term(iter, first_idx + c + 1)[j] mod 2^b: in the limb layout
