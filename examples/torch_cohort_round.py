@@ -21,6 +21,11 @@ which this example checks.
                own steps and a decrypt told who uploaded (set_idx_list(present)) give, which this example checks; with --compact at
                --bits 16 / 20 / 23 / 24 / 32 the gapped round is one chained launch too (`upload.path` is "cohort-chain"), without a mask:
                the decrypt of the sum takes the telescoped lists
+  --cut        many clients with a SMALL model: forty LeNet-5s of 61,706 parameters, far below the length the summed chain takes uncut.
+               FlasheCohort(cut=True) cuts the chain into runs of consecutive clients and adds the runs' partial sums and decrypt masks
+               in one combine pass (`upload.path` is "cut-chain"): two launches instead of forty quantise passes, forty plaintext
+               vectors and a batch encrypt; with --compact at --bits 16 / 20 / 23 / 24 / 32 the same in the uint32 layout.  Without
+               --cut such a cohort runs "staged-chain"
   --rng philox the stochastic-rounding draws come from one np.random.Generator per client instead of NumPy's global stream
                (quantize_encrypt(rng=[...])): counter-based Philox generators, whose draws for the whole cohort are ONE asynchronous
                launch on the device (models of 65,536 values or more: this example's hold 8,036,426) and whose advanced states come back
@@ -48,8 +53,12 @@ class Weights:
         self._weights = dict(layers)
 
 
-def make_model(seed):
+def make_model(seed, small=False):
     torch.manual_seed(seed)
+    if small:                                                # LeNet-5 on 32 x 32 inputs: 61,706 parameters
+        return torch.nn.Sequential(torch.nn.Conv2d(1, 6, 5), torch.nn.ReLU(), torch.nn.AvgPool2d(2), torch.nn.Conv2d(6, 16, 5), torch.nn.ReLU(),
+                                   torch.nn.AvgPool2d(2), torch.nn.Flatten(), torch.nn.Linear(400, 120), torch.nn.ReLU(), torch.nn.Linear(120, 84),
+                                   torch.nn.ReLU(), torch.nn.Linear(84, 10)).cuda()
     return torch.nn.Sequential(torch.nn.Conv2d(3, 16, 5), torch.nn.ReLU(), torch.nn.Flatten(), torch.nn.Linear(16 * 28 * 28, 640), torch.nn.ReLU(),
                                torch.nn.Linear(640, 10)).cuda()
 
@@ -65,20 +74,22 @@ def main():
     ap.add_argument("--compact", action="store_true")
     ap.add_argument("--batch", action="store_true")
     ap.add_argument("--precompute", action="store_true")
+    ap.add_argument("--cut", action="store_true", help="forty LeNet-sized models through the cut chained launch")
     ap.add_argument("--drop", default="", help="comma-separated clients that miss the round, e.g. 2,7")
     ap.add_argument("--rng", choices=["philox", "pcg64", "sfc64"], default=None, help="draw from one np.random.Generator per client")
     opt = ap.parse_args()
     cm.N_JOBS = 16                                           # every party must use the same value
-    C, key = 10, bytes(range(32))
+    C, key = 40 if opt.cut else 10, bytes(range(32))
     dropped = sorted({int(c) for c in opt.drop.split(",") if c})
     present = [c for c in range(C) if c not in dropped]
-    models = [make_model(c) for c in range(C)]
+    models = [make_model(c, small=opt.cut) for c in range(C)]
     layers = [{name: p.detach() for name, p in m.named_parameters()} for m in models]
     # a precompute job states the length of its uploads: the values of the model, or -- batched -- its elements of bs values, every layer
     # padded to whole elements on its own
-    bs = opt.bits // (16 + int(np.ceil(np.log2(C)))) if opt.batch else 1
+    eb = min(16, opt.bits - int(np.ceil(np.log2(C)))) if opt.cut else 16          # (forty clients: their sum must still fit int_bits)
+    bs = opt.bits // (eb + int(np.ceil(np.log2(C)))) if opt.batch else 1
     num_params = sum((t.numel() + bs - 1) // bs for t in layers[0].values())
-    args = {"quantize": {"int_bits": opt.bits, "batch": opt.batch, "element_bits": 16, "padding": True, "secure": True},
+    args = {"quantize": {"int_bits": opt.bits, "batch": opt.batch, "element_bits": eb, "padding": True, "secure": True},
             "precompute": {"enable": opt.precompute, "num_params": num_params}}
     it = 1 if opt.precompute else 0
 
@@ -91,7 +102,7 @@ def main():
         bitgen = np.random.Philox if opt.rng == "philox" else np.random.SFC64
         return [np.random.Generator(bitgen(1000 + c)) for c in present]
 
-    cohort = FlasheCohort(args, first_idx=0, n_local=C, num_clients=C, prp_seed=key, compact=opt.compact)
+    cohort = FlasheCohort(args, first_idx=0, n_local=C, num_clients=C, prp_seed=key, compact=opt.compact, cut=opt.cut)
     if opt.precompute:
         cohort.set_iter_index(it - 1)
         cohort.prepare_encrypt()                             # in idle time, one round ahead: the masks of iteration `it`

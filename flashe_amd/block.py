@@ -1082,6 +1082,7 @@ class FlasheClient(object):
 # ---- a cohort of consecutive clients hosted on one GPU (new) --------------------------------------------------------------------
 COHORT_CHAIN, STAGED_CHAIN, PER_CLIENT = "cohort-chain", "staged-chain", "per-client"
 PREPARED_COHORT, PREPARED_STAGED = "prepared-cohort", "prepared-staged"   # with the cohort's own mask cache (FlasheCohort.prepare_encrypt)
+CUT_CHAIN = "cut-chain"          # a short cohort's summed chain cut into runs of clients + one combine pass (FlasheCohort(cut=True))
 _COHORT_MAX_LINKS = 128          # outputs of one chained launch (kMaxLinks, kernels.hip)
 _COHORT_MAX_STREAMS = 144        # PRF streams of one chained launch (kCohortMaxStreams, cohort_streams.h): present clients + runs
 
@@ -1098,12 +1099,12 @@ class CohortPlan(object):
     """What plan_cohort returns: names / shapes / sizes / starts of the shared layer table, n (values of one model), n_elems (ciphertext
     elements of one upload: n, or the batched count), draw_offsets (the p-th present client's first draw in the client-major draws), path
     and the reason for it, present (the local positions of the clients that report: all of them unless some dropped out) and runs (the
-    runs of consecutive positions among them)."""
+    runs of consecutive positions among them); parts: the runs of clients a "cut-chain" launch is cut into (1 on every other path)."""
 
-    def __init__(self, names, shapes, sizes, starts, n, n_elems, draw_offsets, path, reason, present=None, runs=1):
+    def __init__(self, names, shapes, sizes, starts, n, n_elems, draw_offsets, path, reason, present=None, runs=1, parts=1):
         self.names, self.shapes, self.sizes, self.starts = names, shapes, sizes, starts
         self.n, self.n_elems, self.draw_offsets, self.path, self.reason = n, n_elems, draw_offsets, path, reason
-        self.present, self.runs = list(range(len(draw_offsets))) if present is None else list(present), runs
+        self.present, self.runs, self.parts = list(range(len(draw_offsets))) if present is None else list(present), runs, parts
 
 
 class CohortUpload(object):
@@ -1214,8 +1215,31 @@ def compact_cohort_admission_length(cu_count, int_bits, n_jobs):
     return lo
 
 
+_CUT_MAX_PARTS, _CUT_MIN_OUTPUTS = 16, 4           # kCutMaxParts, kCutMinOutputs (csrc/cohort_cut.h)
+
+
+def cohort_cut_items(n, int_bits, n_jobs, compact=False):
+    """The items of one uncut chain over an n-element vector (csrc/cohort_cut.h): half tiles of 128 elements in the wide layout, tiles of
+    128 AES blocks in the compact one -- two AES blocks per lane and stream either way."""
+    if compact:
+        return (compact_cohort_blocks(n, int_bits, n_jobs) + 127) // 128
+    return 2 * ((int(n) + 255) // 256)
+
+
+def cohort_cut_parts(n_clients, items, cu_count):
+    """The mirror of cohort_cut_parts in csrc/cohort_cut.h (tests/test_cohort_cut_host.py holds the two against each other): the runs of
+    consecutive clients the cut launch makes of a cohort whose uncut chain has `items` items -- as many as fill the chip once (the
+    largest count whose items do not outnumber the chip's 16 x cu_count waves), never fewer than four clients per piece, at most 16
+    pieces; one piece from half an item per wave upward.
+    0: not a shape of the cut launch.  Piece p holds clients [C p // parts, C (p + 1) // parts)."""
+    C, items, cus = int(n_clients), int(items), int(cu_count)
+    if C < 1 or C > _COHORT_MAX_LINKS or items < 1 or cus < 1:
+        return 0
+    return max(1, min(16 * cus // items, max(1, C // _CUT_MIN_OUTPUTS), _CUT_MAX_PARTS))
+
+
 def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, mask="double", num_clients=None, precompute=False, chain=True,
-                location_masks=False, compact=False, n_jobs=None, cohort_masks=False, present=None, compact_runs=False):
+                location_masks=False, compact=False, n_jobs=None, cohort_masks=False, present=None, compact_runs=False, cut=False):
     """The engine-free part of FlasheCohort.quantize_encrypt: checks that the clients' Weights describe one model (the same layer names
     in the same walking order with the same shapes: ValueError naming the client and the layer otherwise; a sparse upload -- a 'zzz'
     layer or location masks -- is a TypeError), lays out the shared layer table and the client-major draws, and picks the path:
@@ -1246,8 +1270,15 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
     (flashe_quantize_encrypt_cohort_runs_u32_dev): False (the default) plans it "staged-chain" -- the compact chain then takes one run
     only --, True lets it through to the 144-stream rule like the wide one.  present=None and present=all positions give equal plans,
     whatever compact_runs says.
-    Touches no device.  The library's own answer stays the last word: a "cohort-chain" plan it declines runs "staged-chain", a
-    "prepared-cohort" one "prepared-staged"."""
+    cut=True (FlasheCohort(cut=True) on an engine with flashe_quantize_encrypt_cohort_cut_dev) answers
+      "cut-chain"     for a shape whose ONLY obstacle above is "the vector does not fill the chip uncut" -- double mask, not batched, one
+                      run of consecutive clients, every layer float64 for all clients or for none, at most 128 clients: the summed
+                      chain cut into CohortPlan.parts runs of consecutive clients (cohort_cut_parts) and one combine pass, two launches
+                      whatever C is (one when parts == 1) and no plaintext in HBM.  A short cohort that is batched, gapped or mixed
+                      stays "staged-chain", and so does everything the rules above send there for another reason.
+    cut=False: the plans are what they always were.
+    Touches no device.  The library's own answer stays the last word: a "cohort-chain" or "cut-chain" plan it declines runs
+    "staged-chain", a "prepared-cohort" one "prepared-staged"."""
     if len(weights_list) < 1:
         raise ValueError("a cohort needs at least one client's Weights")
     C = len(weights_list)
@@ -1272,6 +1303,7 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
     if batch:
         bs = int_bits // _field_bits(element_bits, num_clients)
         n_elems = sum((s_ + bs - 1) // bs for s_ in sizes)
+    short, parts = False, 1                         # short: the length rule alone keeps the shape from the uncut chain
     if cohort_masks and mask == "double":
         if mixed:
             path, reason = PREPARED_STAGED, "a layer is float64 for some clients only: no shared row of one compute class"
@@ -1298,9 +1330,9 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
     elif not chain:
         path, reason = STAGED_CHAIN, "FLASHE_CHAIN=0"
     elif compact and (n >= 2 ** 32 or compact_cohort_blocks(n, int_bits, n_jobs) < 2 * 128 * 16 * int(cu_count)):
-        path, reason = STAGED_CHAIN, "the vector does not fill the chip uncut"
+        path, reason, short = STAGED_CHAIN, "the vector does not fill the chip uncut", 1 <= n < 2 ** 32
     elif not compact and (n_elems < cohort_admission_length(cu_count) or n_elems > 2 ** 32):
-        path, reason = STAGED_CHAIN, "the vector does not fill the chip uncut"
+        path, reason, short = STAGED_CHAIN, "the vector does not fill the chip uncut", 1 <= n_elems < cohort_admission_length(cu_count)
     elif runs > 1 and compact and not compact_runs:
         path, reason = STAGED_CHAIN, f"clients dropped out ({runs} runs of indices): the compact chain takes one run of consecutive clients"
     elif C + runs > _COHORT_MAX_STREAMS:
@@ -1309,7 +1341,17 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
         path, reason = STAGED_CHAIN, "a layer is float64 for some clients only"
     else:
         path, reason = COHORT_CHAIN, ""
-    return CohortPlan(names, shapes, sizes, starts, n, n_elems, [c * n for c in range(C)], path, reason, present, runs)
+    if cut and short:
+        # the rules behind the length rule, in their order, in the cut launch's terms (one run, un-batched)
+        if batch:
+            reason += "; batched job: the cut chain takes un-batched cohorts"
+        elif runs > 1:
+            reason = f"clients dropped out ({runs} runs of indices): the cut chain takes one run of consecutive clients"
+        elif mixed:
+            reason = "a layer is float64 for some clients only"
+        else:
+            path, reason, parts = CUT_CHAIN, "", cohort_cut_parts(C, cohort_cut_items(n, int_bits, n_jobs, compact), cu_count)
+    return CohortPlan(names, shapes, sizes, starts, n, n_elems, [c * n for c in range(C)], path, reason, present, runs, parts)
 
 
 class _CohortLead(FlasheClient):
@@ -1350,6 +1392,12 @@ class FlasheCohort(object):
     run -- the chained launch goes from the floats to the uint32 ciphertexts and their sum (flashe_quantize_encrypt_cohort_u32_dev: 16
     bytes moved per value and client instead of 36).  No decrypt mask is kept at these widths: decrypt_unquantize() decrypts the
     sum.
+    cut=True (opt-in, like compact): a model too SHORT for the uncut chain -- fewer than cohort_admission_length(cu_count) values, or
+    compact_cohort_admission_length(...) in the compact layout: many clients with a small model -- runs "cut-chain" instead of
+    "staged-chain": the summed chain cut into runs of consecutive clients and one combine pass (flashe_quantize_encrypt_cohort_cut_dev /
+    its _u32 form), two launches whatever n_local is, no plaintext in HBM, the same bytes, and the same decrypt mask kept for
+    decrypt_unquantize().  Short cohorts that are batched, gapped (present= in several runs), single-mask, at int_bits 33 - 64 or of more
+    than 128 clients stay "staged-chain".
     A round in which clients DROPPED OUT is quantize_encrypt(..., present=[positions]): the present clients' steps one after the other, and
     at int_bits > 64 still one chained launch (flashe_quantize_encrypt_cohort_runs_dev / flashe_quantize_batch_encrypt_cohort_runs_dev)
     over present + runs PRF streams that writes the decrypt mask of the telescoped index lists, so decrypt_unquantize() of that round
@@ -1360,13 +1408,15 @@ class FlasheCohort(object):
     chain of n_local + 1 streams, held by the cohort; the next quantize_encrypt is then ONE online launch with no AES ("prepared-cohort")
     at any int_bits, batched or not, compact or not.  Without that call the clients' own masks run "per-client" as before."""
 
-    def __init__(self, args, first_idx, n_local, num_clients, prp_seed, device=0, stream=None, compact=False):
+    def __init__(self, args, first_idx, n_local, num_clients, prp_seed, device=0, stream=None, compact=False, cut=False):
         if n_local < 1 or first_idx < 0 or first_idx + n_local > num_clients:
             raise ValueError(f"clients {first_idx} .. {first_idx + n_local - 1} are not clients of a federation of {num_clients}")
         self.first_idx, self.n_local, self.num_clients = int(first_idx), int(n_local), int(num_clients)
         self.lead = _CohortLead(args, device=device, stream=stream)
         self.lead.create_cipher(self.first_idx, self.num_clients, prp_seed)
         self.compact = bool(compact)
+        self.cut = bool(cut)                           # a short cohort runs "cut-chain" where the engine has the cut launch
+        self._cut_scratch = None                       # the cut launch's scratch, kept from round to round
         if self.compact:
             if self.lead.int_bits > 32:
                 raise ValueError(f"compact=True needs int_bits <= 32, this job runs int_bits {self.lead.int_bits}")
@@ -1407,7 +1457,9 @@ class FlasheCohort(object):
                            mask=ld.cipher.masking_scheme, num_clients=self.num_clients, precompute=bool(ld.precompute),
                            chain=os.environ.get("FLASHE_CHAIN", "1") != "0", location_masks=ld.cipher.masks is not None, compact=self.compact,
                            n_jobs=_cipher_mod.N_JOBS, cohort_masks=self._masks is not None, present=present,
-                           compact_runs=hasattr(ld.cipher.engine, "quantize_encrypt_cohort_runs_u32_dev"))
+                           compact_runs=hasattr(ld.cipher.engine, "quantize_encrypt_cohort_runs_u32_dev"),
+                           cut=self.cut and hasattr(ld.cipher.engine, "quantize_encrypt_cohort_cut_u32_dev" if self.compact
+                                                    else "quantize_encrypt_cohort_cut_dev"))
 
     def prepare_encrypt(self):
         """A precompute job's idle-time step for the whole cohort.  Double mask: the encrypt masks of iteration iter_index + 1 for all
@@ -1493,7 +1545,7 @@ class FlasheCohort(object):
             cts = [DeviceVector(eng, plan.n_elems) for _ in range(C)]
             psum = DeviceVector(eng, plan.n_elems)
         prepared = path in (PREPARED_COHORT, PREPARED_STAGED)       # (the cohort's cache is consumed whatever form runs)
-        if path in (COHORT_CHAIN, PREPARED_COHORT):
+        if path in (COHORT_CHAIN, PREPARED_COHORT, CUT_CHAIN):
             # the shared rows name the compute type; the sources keep their own storage dtypes
             # (with degrees on tensors the tables name the stage pass's output: its code is the compute type)
             rows = [(st, None, al, sh, code if pre is not None else _lib.TENSOR_F64 if layers[0][li][2] == np.float64 else _lib.TENSOR_F32, fl)
@@ -1501,7 +1553,7 @@ class FlasheCohort(object):
             srcs = [[t[1] for t in table] for table in tables]
             dts = [[t[4] for t in table] for table in tables]
             launch = self._launch_prepared if prepared else self._launch_chain
-            if not launch(plan, rows, srcs, dts, du, cts, psum, present is not None):
+            if not launch(plan, rows, srcs, dts, du, cts, psum, present is not None, **({"cut": True} if path == CUT_CHAIN else {})):
                 # the library declined: the planner's guess was wrong, the result is not -- the same bytes from the fallback form
                 path = PREPARED_STAGED if prepared else STAGED_CHAIN
         if path in (STAGED_CHAIN, PREPARED_STAGED) and plan.n_elems:
@@ -1579,13 +1631,13 @@ class FlasheCohort(object):
     def _choose_path(self, plan, layers):
         """The plan's path after what only the layers themselves and `prefer` tell."""
         path = plan.path
-        if any(layer[2] != first[2] for row in layers for layer, first in zip(row, layers[0])) and path in (COHORT_CHAIN, PREPARED_COHORT):
+        if any(layer[2] != first[2] for row in layers for layer, first in zip(row, layers[0])) and path in (COHORT_CHAIN, PREPARED_COHORT, CUT_CHAIN):
             # (a layer that computes in float64 for some clients only: no shared row)
-            path = STAGED_CHAIN if path == COHORT_CHAIN else PREPARED_STAGED
+            path = PREPARED_STAGED if path == PREPARED_COHORT else STAGED_CHAIN
         prepared = path in (PREPARED_COHORT, PREPARED_STAGED)       # (the cohort's cache is consumed whatever `prefer` says)
         if prepared and self.prefer == STAGED_CHAIN:
             return PREPARED_STAGED
-        if not prepared and (self.prefer == PER_CLIENT or (self.prefer == STAGED_CHAIN and path == COHORT_CHAIN)):
+        if not prepared and (self.prefer == PER_CLIENT or (self.prefer == STAGED_CHAIN and path in (COHORT_CHAIN, CUT_CHAIN))):
             return self.prefer
         return path
 
@@ -1629,11 +1681,12 @@ class FlasheCohort(object):
             tables.append(table)
         return tables, keep
 
-    def _launch_chain(self, plan, rows, srcs, dts, du, cts, psum, by_idx=False):
+    def _launch_chain(self, plan, rows, srcs, dts, du, cts, psum, by_idx=False, cut=False):
         """"cohort-chain": ONE chained launch from the floats to the ciphertexts, their sum and -- when the cohort is the whole federation --
         the decrypt mask, which the lead keeps with the add / minus lists it stands for, for the decrypt of that sum.  by_idx (a call with
-        `present`): the launch is given the present clients' cipher indices, any number of runs.  False: the library declined, nothing was
-        launched."""
+        `present`): the launch is given the present clients' cipher indices, any number of runs.  cut ("cut-chain", one run of clients):
+        the chain cut into the library's cohort_cut_parts pieces plus the combine pass, with the scratch the pieces' sums and masks go
+        through; the outputs and the mask kept are those of the uncut launch.  False: the library declined, nothing was launched."""
         from . import cipher as _cipher_mod
         from .engine import DeviceVector
         ld = self.lead
@@ -1643,7 +1696,22 @@ class FlasheCohort(object):
         dmask = DeviceVector(eng, n_elems) if self.n_local == self.num_clients and not self.compact else None
         outs, mask_buf = [v.buf for v in cts], dmask.buf if dmask is not None else None
         idxs = [self.first_idx + p for p in plan.present]
-        if self.compact and by_idx and hasattr(eng, "quantize_encrypt_cohort_runs_u32_dev"):
+        if cut:
+            C = len(idxs)
+            parts = eng.cohort_cut_parts(C, n, _cipher_mod.N_JOBS, compact=self.compact)
+            need = 0 if parts <= 1 else parts * n * 4 if self.compact else parts * n * 16 * (2 if dmask is not None else 1)
+            if need and (self._cut_scratch is None or self._cut_scratch.nbytes < need):
+                self._cut_scratch = eng.alloc(max(need, 16))
+            scratch = self._cut_scratch if need else None
+            if not parts:
+                took = False
+            elif self.compact:
+                took = eng.quantize_encrypt_cohort_cut_u32_dev(c.iter_index, idxs[0], n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du, outs,
+                                                               psum.buf, scratch)
+            else:
+                took = eng.quantize_encrypt_cohort_cut_dev(c.iter_index, idxs[0], n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du, outs,
+                                                           psum.buf, mask_buf, scratch)
+        elif self.compact and by_idx and hasattr(eng, "quantize_encrypt_cohort_runs_u32_dev"):
             took = eng.quantize_encrypt_cohort_runs_u32_dev(c.iter_index, idxs, n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du, outs,
                                                             psum.buf)
         elif self.compact:

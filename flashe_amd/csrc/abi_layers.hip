@@ -713,6 +713,74 @@ int flashe_quantize_encrypt_cohort_u32_dev(flashe_ctx *ctx, uint32_t iter, uint3
     return cohort_launched(ctx, launch_small_cohort_sum(ctx->env, iter, n_clients, idx.data(), cc, u_dev, ct_dev, sum_out_dev, n, n_jobs), who, "compact cohort");
 }
 
+// ---- the SHORT cohort: the two launches above for a vector that does not fill the chip uncut (cohort_cut.h) -- the chain cut into runs of
+// consecutive clients, their sums and decrypt masks added up by one combine pass.  The twins' checks, stage pass and refusals; the
+// admission is theirs without the length rule ----
+int flashe_cohort_cut_parts(flashe_ctx *ctx, int n_clients, uint64_t n, uint32_t n_jobs, int compact, int *parts)
+{
+    CHECK_CTX(ctx);
+    static const char who[] = "flashe_cohort_cut_parts";
+    if (!parts) return fail(ctx, FLASHE_EINVAL, "%s: null argument", who);
+    *parts = 0;
+    if (n_clients < 1) return fail(ctx, FLASHE_EINVAL, "%s: n_clients must be >= 1", who);
+    if (compact && n_jobs == 0) return fail(ctx, FLASHE_EINVAL, "n_jobs must be >= 1");
+    const int k = compact && flashe_ctx_compact_layout(ctx) != 1 ? 0 : cohort_cut_parts_of(ctx->env, n_clients, n, n_jobs, compact != 0);
+    if (!k) return cohort_declined(ctx, who, compact ? "cut compact cohort" : "cut cohort");
+    *parts = k;
+    return FLASHE_OK;
+}
+
+// the scratch of a cut launch: needed from two pieces upward, 16-byte aligned, and none of the launch's outputs
+static int cohort_check_scratch(flashe_ctx *ctx, int parts, int n_clients, const void *scratch_dev, const void *const *ct_dev, const void *sum_out_dev,
+                                const void *dmask_dev)
+{
+    if (!scratch_dev) return parts > 1 ? fail(ctx, FLASHE_EINVAL, "scratch_dev is null: the launch runs %d pieces (flashe_cohort_cut_parts)", parts) : FLASHE_OK;
+    if (!aligned16(scratch_dev)) return fail(ctx, FLASHE_EINVAL, "scratch_dev must be 16-byte aligned");
+    if (scratch_dev == sum_out_dev || scratch_dev == dmask_dev) return fail(ctx, FLASHE_EINVAL, "scratch_dev aliases the sum or the mask");
+    for (int c = 0; c < n_clients; c++)
+        if (scratch_dev == ct_dev[c]) return fail(ctx, FLASHE_EINVAL, "scratch_dev aliases client %d's ciphertext", c);
+    return FLASHE_OK;
+}
+
+int flashe_quantize_encrypt_cohort_cut_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                           const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                           int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev, uint64_t *dmask_dev,
+                                           uint64_t *scratch_dev)
+{
+    CHECK_CTX(ctx);
+    static const char who[] = "flashe_quantize_encrypt_cohort_cut_dev";
+    std::vector<uint32_t> idx;
+    int rc = cohort_check(ctx, who, first_idx, n_clients, n, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, idx);
+    if (rc || (rc = cohort_check_outs(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, dmask_dev))) return rc;
+    const int parts = cohort_cut_parts_of(ctx->env, n_clients, n, n_jobs, false);
+    if (!parts) return cohort_declined(ctx, who, "cut cohort");
+    if ((rc = cohort_check_scratch(ctx, parts, n_clients, scratch_dev, reinterpret_cast<const void *const *>(ct_dev), sum_out_dev, dmask_dev))) return rc;
+    CohortCodec cc{};
+    if ((rc = cohort_stage(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, cc))) return rc;
+    return cohort_launched(ctx, launch_prf_cohort_cut(ctx->env, iter, n_clients, idx.data(), cc, u_dev, ct_dev, sum_out_dev, n, n_jobs, dmask_dev, scratch_dev),
+                           who, "cut cohort");
+}
+
+int flashe_quantize_encrypt_cohort_cut_u32_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                               const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                               int element_bits, const double *u_dev, uint32_t *const *ct_dev, uint32_t *sum_out_dev, uint32_t *scratch_dev)
+{
+    CHECK_CTX(ctx);
+    static const char who[] = "flashe_quantize_encrypt_cohort_cut_u32_dev";
+    std::vector<uint32_t> idx;
+    int rc = cohort_check(ctx, who, first_idx, n_clients, n, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, idx);
+    if (rc) return rc;
+    if (n_jobs == 0) return fail(ctx, FLASHE_EINVAL, "n_jobs must be >= 1");
+    if ((rc = cohort_check_outs<uint32_t>(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, nullptr))) return rc;
+    const int parts = flashe_ctx_compact_layout(ctx) != 1 ? 0 : cohort_cut_parts_of(ctx->env, n_clients, n, n_jobs, true);
+    if (!parts) return cohort_declined(ctx, who, "cut compact cohort");
+    if ((rc = cohort_check_scratch(ctx, parts, n_clients, scratch_dev, reinterpret_cast<const void *const *>(ct_dev), sum_out_dev, nullptr))) return rc;
+    CohortCodec cc{};
+    if ((rc = cohort_stage(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, cc))) return rc;
+    return cohort_launched(ctx, launch_small_cohort_cut(ctx->env, iter, n_clients, idx.data(), cc, u_dev, ct_dev, sum_out_dev, n, n_jobs, scratch_dev), who,
+                           "cut compact cohort");
+}
+
 // the cohort of a BATCHED job (prf_chain_cohort_batch_kernel): the same table, sources and stage pass over the n_values values; the chain
 // runs over the n_elems batched elements
 int flashe_quantize_batch_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n_values, uint64_t n_elems,

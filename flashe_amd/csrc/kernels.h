@@ -133,6 +133,21 @@ hipError_t launch_small_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_ve
 hipError_t launch_small_sparse_cohort(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
                                       uint64_t u_stride, uint64_t *const *out_dev, uint64_t n, uint32_t n_jobs, const double *zzz_dev, bool zzz_f64,
                                       double z_alpha, double z_scale, double z_den, uint64_t *zeros_dev);
+// The SHORT cohort (cohort_cut.h): the two summed cohort launches above without their length rules, the chain cut into runs of consecutive
+// clients whose sums and decrypt masks one combine pass adds up.  cohort_cut_parts_of: the pieces the launch will use -- 0 outside the
+// uncut launch's other conditions (wide: the chained table PRF at int_bits > 64 without a fused codec, 1 .. kMaxLinks clients, n in one
+// counter window; compact: small_cohort_admits(not summed)) -- from the environment and the sizes alone; the caller sizes the scratch
+// from it: parts x n x 16 B for the sums and as much again behind them for the masks (wide, with dmask_dev), parts x n x 4 B (compact),
+// unused when parts == 1.  idx: ONE run of consecutive indices.  hipErrorNotSupported: nothing launched.
+int cohort_cut_parts_of(const LaunchEnv &env, int n_vec, uint64_t n, uint32_t n_jobs, bool compact);
+hipError_t launch_prf_cohort_cut(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
+                                 uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs, uint64_t *dmask_dev, uint64_t *scratch_dev);
+hipError_t launch_small_cohort_cut(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
+                                   uint32_t *const *out_dev, uint32_t *sum_out_dev, uint64_t n, uint32_t n_jobs, uint32_t *scratch_dev);
+// their combine pass (stream.hip): sum_dev[k] = sum_p psum_dev[p n + k] mod 2^b and, with pmask_dev, dmask_dev[k] = sum_p pmask_dev[p n + k]
+hipError_t launch_cohort_cut_combine(const LaunchEnv &env, int parts, uint64_t n, const uint64_t *psum_dev, uint64_t *sum_dev, const uint64_t *pmask_dev,
+                                     uint64_t *dmask_dev);
+hipError_t launch_cohort_cut_combine_u32(const LaunchEnv &env, int parts, uint64_t n, const uint32_t *psum_dev, uint32_t *sum_dev);
 // launch_prf_batch on elements [first, first + count) of the n-element vectors (pointers address element `first`): what a GPU that owns
 // an element slice of every client's vector runs
 hipError_t launch_prf_batch_range(const LaunchEnv &env, uint32_t iter, bool dbl, int n_vec, const uint32_t *idx, const uint64_t *const *in_dev,

@@ -13,6 +13,8 @@
 //     round-robin; there is no inter-workgroup reuse, so no XCD remap is needed.
 #include "device_common.h"
 #include "cohort_streams.h"
+#include "cohort_cut.h"
+#include <cassert>
 #include <type_traits>
 
 namespace flashe {
@@ -377,8 +379,9 @@ __global__ __launch_bounds__(THREADS) void prf_chain_kernel(const RoundKeys rk, 
                                                               uint32_t iter0, uint64_t mask_lo, uint64_t mask_hi,
                                                               const uint32_t *__restrict__ te0, const Codec cq)
 {
-    constexpr bool DMASK = false, D128 = false, COHORT = false, GAPS = false, DEC = false;
+    constexpr bool DMASK = false, D128 = false, COHORT = false, GAPS = false, DEC = false, CUT = false;
     constexpr int BS = 0;
+    constexpr uint64_t cut_stride = 0;
     const CohortGaps cg{};
     uint64_t *const dmask = nullptr;
     const CohortCodec cc{};
@@ -392,8 +395,9 @@ __global__ __launch_bounds__(THREADS) void prf_chain_dmask_kernel(const RoundKey
                                                                     uint32_t iter0, uint64_t mask_lo, uint64_t mask_hi,
                                                                     const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask)
 {
-    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = false, GAPS = false, DEC = false;
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = false, GAPS = false, DEC = false, CUT = false;
     constexpr int BS = 0;
+    constexpr uint64_t cut_stride = 0;
     const CohortGaps cg{};
     const Codec cq{};
     const CohortCodec cc{};
@@ -409,8 +413,9 @@ __global__ __launch_bounds__(THREADS) void prf_dmask_sum128_kernel(const RoundKe
                                                                      uint32_t iter0, uint64_t mask_lo, uint64_t mask_hi,
                                                                      const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask)
 {
-    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = true, COHORT = false, GAPS = false, DEC = false;
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = true, COHORT = false, GAPS = false, DEC = false, CUT = false;
     constexpr int BS = 0;
+    constexpr uint64_t cut_stride = 0;
     const CohortGaps cg{};
     const Codec cq{};
     const CohortCodec cc{};
@@ -428,8 +433,9 @@ __global__ __launch_bounds__(THREADS) void prf_dec_sum128_kernel(const RoundKeys
                                                                    uint32_t iter0, uint64_t mask_lo, uint64_t mask_hi,
                                                                    const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask)
 {
-    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = true, COHORT = false, GAPS = false, DEC = true;
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = true, COHORT = false, GAPS = false, DEC = true, CUT = false;
     constexpr int BS = 0;
+    constexpr uint64_t cut_stride = 0;
     const CohortGaps cg{};
     const Codec cq{};
     const CohortCodec cc{};
@@ -450,7 +456,26 @@ __global__ __launch_bounds__(THREADS) void prf_chain_cohort_kernel(const RoundKe
                                                                      const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask,
                                                                      const CohortCodec cc)
 {
-    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true, GAPS = false, DEC = false;
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true, GAPS = false, DEC = false, CUT = false;
+    constexpr int BS = 0;
+    constexpr uint64_t cut_stride = 0;
+    const Codec cq{};
+    const CohortBatch cb{};
+    const CohortGaps cg{};
+#include "prf_chain_body.inc"
+}
+
+// CUT: the same cohort for a vector too SHORT to fill the chip uncut (CUT in prf_chain_body.inc; cohort_cut.h) -- n_chains runs of
+// consecutive clients, every run a summed double-mask chain of its own over the same elements [0, n) with the one table cc.  Chain p
+// writes the sum of its outputs to tb.sum_out[p] and its decrypt mask to dmask + p * cut_stride (limbs); cohort_cut_combine_kernel
+// (stream.hip) adds them up.  A separate kernel: the uncut launches keep their code objects.
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void prf_chain_cohort_cut_kernel(const RoundKeys rk, const ChainTable tb, int n_chains, int all_half_arg,
+                                                                         uint32_t iter0, uint64_t mask_lo, uint64_t mask_hi,
+                                                                         const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask,
+                                                                         const CohortCodec cc, uint64_t cut_stride)
+{
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true, GAPS = false, DEC = false, CUT = true;
     constexpr int BS = 0;
     const Codec cq{};
     const CohortBatch cb{};
@@ -467,8 +492,9 @@ __global__ __launch_bounds__(THREADS) void prf_chain_cohort_batch_kernel(const R
                                                                            const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask,
                                                                            const CohortCodec cc, const CohortBatch cb)
 {
-    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true, GAPS = false, DEC = false;
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true, GAPS = false, DEC = false, CUT = false;
     constexpr int BS = BS_;
+    constexpr uint64_t cut_stride = 0;
     const Codec cq{};
     const CohortGaps cg{};
 #include "prf_chain_body.inc"
@@ -484,8 +510,9 @@ __global__ __launch_bounds__(THREADS) void prf_chain_cohort_runs_kernel(const Ro
                                                                           const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask,
                                                                           const CohortCodec cc, const CohortGaps cg)
 {
-    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true, GAPS = true, DEC = false;
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true, GAPS = true, DEC = false, CUT = false;
     constexpr int BS = 0;
+    constexpr uint64_t cut_stride = 0;
     const Codec cq{};
     const CohortBatch cb{};
 #include "prf_chain_body.inc"
@@ -497,8 +524,9 @@ __global__ __launch_bounds__(THREADS) void prf_chain_cohort_batch_runs_kernel(co
                                                                                 const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask,
                                                                                 const CohortCodec cc, const CohortBatch cb, const CohortGaps cg)
 {
-    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true, GAPS = true, DEC = false;
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true, GAPS = true, DEC = false, CUT = false;
     constexpr int BS = BS_;
+    constexpr uint64_t cut_stride = 0;
     const Codec cq{};
 #include "prf_chain_body.inc"
 }
@@ -2039,6 +2067,84 @@ hipError_t launch_prf_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec,
     return hipGetLastError();
 }
 
+// ---- the SHORT cohort: the summed chain cut into runs of consecutive clients (cohort_cut.h), then one combine pass ----
+// What the cut launches admit: the uncut launches' conditions without the length rule.  The pieces they will use, 0 = not a shape of theirs
+// (the C ABI asks before it stages anything and tells the caller, who sizes the scratch from it).  compact: launch_small_cohort_cut's.
+int cohort_cut_parts_of(const LaunchEnv &env, int n_vec, uint64_t n, uint32_t n_jobs, bool compact)
+{
+    uint64_t items;
+    if (compact) {
+        if (!small_cohort_admits(env, n_vec, n, n_jobs, false)) return 0;      // (not `summed`: every condition but the length rule)
+        items = flashe_tables::cohort_cut_items_compact(block_of(n - 1, n, n_jobs, 128 / env.b) + 1);
+    } else {
+        if (!env.use_chain || env.b <= 64 || env.codec || !table_prf(env) || n_vec < 1 || n_vec > kMaxLinks) return 0;
+        if (n == 0 || ((n - 1) >> 32)) return 0;                          // one counter window
+        items = flashe_tables::cohort_cut_items_wide(n);
+    }
+    int parts = flashe_tables::cohort_cut_parts(n_vec, items, env.num_cus);
+    // experiment knob (tests/perf/cut_cohort_step.py), read only when FLASHE_CHAIN_TUNE is set in the tuning build
+    static const bool tune = FLASHE_TUNE_ENV("FLASHE_CHAIN_TUNE") != nullptr;
+    if (tune && parts) {
+        if (const char *e = FLASHE_TUNE_ENV("FLASHE_CHAIN_PARTS")) {
+            if (atoi(e) > 0) parts = std::min(std::min(atoi(e), n_vec), kMaxChains);
+        }
+    }
+    return parts;
+}
+
+// the pieces of a cut cohort as chains of one table: piece p holds clients [C p / parts, C (p + 1) / parts), its streams are theirs and the
+// one behind its last client (launch_prf_chains' layout: a cut costs one stream).  T = ChainTable / SmallChainTable.
+template <class T>
+static void cohort_cut_table(T &tb, int n_vec, int parts, const uint32_t *idx, uint64_t n, uint64_t tiles)
+{
+    static_assert(flashe_tables::kCutMaxParts == kMaxChains && flashe_tables::kCutMaxClients == kMaxLinks, "cohort_cut.h states the limits of one chained launch");
+    int streams = 0;
+    uint64_t wend = 0;
+    for (int p = 0; p < parts; p++) {
+        const int a = flashe_tables::cohort_cut_begin(n_vec, parts, p), len = flashe_tables::cohort_cut_begin(n_vec, parts, p + 1) - a;
+        tb.first[p] = 0; tb.count[p] = n;
+        tb.link0[p] = static_cast<uint16_t>(a); tb.sbase[p] = static_cast<uint16_t>(streams);
+        tb.len[p] = static_cast<uint8_t>(len);
+        for (int s = 0; s <= len; s++) tb.idx[streams + s] = idx[a] + static_cast<uint32_t>(s);
+        wend += tiles * static_cast<uint64_t>(len + 1);
+        tb.wend[p] = wend;
+        streams += len + 1;
+    }
+    assert(streams == n_vec + parts && streams <= flashe_tables::kCohortMaxStreams);
+}
+
+// prf_chain_cohort_cut_kernel + cohort_cut_combine_kernel: launch_prf_cohort_sum's outputs for ANY n >= 1.  One run of consecutive cipher
+// indices; scratch_dev: parts x n x 16 B for the pieces' sums and as much again for their masks when dmask_dev is given, unused when the
+// rule gives one piece (the chain then writes the sum and the mask where they belong and no combine pass runs).
+// hipErrorNotSupported = nothing launched.
+hipError_t launch_prf_cohort_cut(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
+                                 uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs, uint64_t *dmask_dev, uint64_t *scratch_dev)
+{
+    const int parts = cohort_cut_parts_of(env, n_vec, n, n_jobs, false);
+    if (!parts || !sum_out_dev || !u_dev || cc.n_layers < 1) return hipErrorNotSupported;
+    for (int v = 0; v < n_vec; v++) if (!out_dev[v] || (v && idx[v] != idx[v - 1] + 1u)) return hipErrorNotSupported;
+    if (parts > 1 && !scratch_dev) return hipErrorInvalidValue;
+    const uint64_t tiles = (n + 255) / 256, stride = 2 * n;                // (limbs of one piece's sum or mask)
+    uint64_t *const psum = scratch_dev, *const pmask = dmask_dev ? scratch_dev + static_cast<uint64_t>(parts) * stride : nullptr;
+    ChainTable tb{};
+    cohort_cut_table(tb, n_vec, parts, idx, n, tiles);
+    for (int p = 0; p < parts; p++) tb.sum_out[p] = parts == 1 ? sum_out_dev : psum + static_cast<uint64_t>(p) * stride;
+    for (int l = 0; l < n_vec; l++) {
+        tb.in[l] = reinterpret_cast<const uint64_t *>(u_dev + static_cast<uint64_t>(l) * n);       // the link's draws (CohortCodec)
+        tb.out[l] = out_dev[l];
+    }
+    uint64_t lo, hi;
+    masks_of(env.b, &lo, &hi);
+    const bool all_half = flashe_tables::cohort_cut_all_half(n, parts, env.num_cus);
+    const uint64_t items = (all_half ? 2 : 1) * tiles * static_cast<uint64_t>(parts), cus = static_cast<uint64_t>(env.num_cus);
+    const dim3 grid(static_cast<unsigned>(items < cus ? items : cus)), block(kPrfThreads);
+    hipLaunchKernelGGL((prf_chain_cohort_cut_kernel<kPrfThreads>), grid, block, 0, env.stream, env.rk, tb, parts, all_half ? 1 : 0, iter, lo, hi, env.te0_dev,
+                       parts == 1 ? dmask_dev : pmask, cc, stride);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || parts == 1) return e;
+    return launch_cohort_cut_combine(env, parts, n, psum, sum_out_dev, pmask, dmask_dev);
+}
+
 // b <= 64 form of launch_prf_jobs
 static hipError_t launch_prf_jobs_small(const LaunchEnv &env, uint32_t iter, bool dbl, int n_entries, const PrfJob *jobs, uint64_t n,
                                         uint32_t n_jobs)
@@ -2668,6 +2774,44 @@ hipError_t launch_small_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_ve
     default: return hipErrorNotSupported;
     }
     return hipGetLastError();
+}
+
+// The SHORT compact cohort (cohort_cut.h): launch_small_cohort_sum's outputs for any n >= 1.  prf_small_cohort_kernel takes several summed
+// chains as it is -- every chain's links, streams and sum are addressed through link0 / sbase / sum_out[cur], and the sums the walked tiles
+// keep in memory start at the chain's own first link -- so the cut is this table: `parts` double-mask chains over the same AES blocks,
+// piece p's uint32 sum in scratch_dev + p * n, then the combine pass.  One piece writes sum_out_dev itself.  One run of consecutive
+// cipher indices; hipErrorNotSupported = nothing launched.
+hipError_t launch_small_cohort_cut(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
+                                   uint32_t *const *out_dev, uint32_t *sum_out_dev, uint64_t n, uint32_t n_jobs, uint32_t *scratch_dev)
+{
+    const int parts = cohort_cut_parts_of(env, n_vec, n, n_jobs, true);
+    if (!parts || !sum_out_dev || !u_dev || cc.n_layers < 1) return hipErrorNotSupported;
+    for (int v = 0; v < n_vec; v++) if (!out_dev[v] || (v && idx[v] != idx[v - 1] + 1u)) return hipErrorNotSupported;
+    if (parts > 1 && !scratch_dev) return hipErrorInvalidValue;
+    uint64_t blocks;
+    const SmallParams p = small_cohort_params(env, iter, n_vec, n, n_jobs, &blocks);
+    const uint64_t tiles = (blocks + 127) / 128, cus = static_cast<uint64_t>(env.num_cus);
+    SmallChainTable tb{};
+    cohort_cut_table(tb, n_vec, parts, idx, n, tiles);
+    for (int k = 0; k < parts; k++) {
+        tb.blk_first[k] = 0; tb.blk_count[k] = blocks;
+        tb.sum_out[k] = reinterpret_cast<uint64_t *>(parts == 1 ? sum_out_dev : scratch_dev + static_cast<uint64_t>(k) * n);
+    }
+    for (int l = 0; l < n_vec; l++) {
+        tb.in[l] = reinterpret_cast<const uint64_t *>(u_dev + static_cast<uint64_t>(l) * n);       // the link's draws (CohortDirect, CohortWalk)
+        tb.out[l] = reinterpret_cast<uint64_t *>(out_dev[l]);
+    }
+    const uint64_t items = tiles * static_cast<uint64_t>(parts);
+    const int grid = static_cast<int>(items < cus ? items : cus);
+    switch (env.b) {
+#define FLASHE_FIXED32(B) case B: hipLaunchKernelGGL((prf_small_cohort_kernel<B>), dim3(grid), dim3(kSmallThreads), 0, env.stream, env.rk, tb, parts, p, cc); break;
+        FLASHE_FIXED32_WIDTHS(FLASHE_FIXED32)
+#undef FLASHE_FIXED32
+    default: return hipErrorNotSupported;
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || parts == 1) return e;
+    return launch_cohort_cut_combine_u32(env, parts, n, scratch_dev, sum_out_dev);
 }
 
 // The sparse cohort's encrypts from the floats (prf_small_sparse_cohort_kernel): ONE single-mask chain of n_vec links over elements [0, n), cut

@@ -1,7 +1,12 @@
 // The body of prf_chain_kernel<THREADS, SUM, CODEC>, prf_chain_dmask_kernel<THREADS>, prf_dmask_sum128_kernel<THREADS>, prf_dec_sum128_kernel<THREADS> and
-// prf_chain_cohort_kernel<THREADS> and prf_chain_cohort_batch_kernel<THREADS, BS> (kernels.hip), included INSIDE each kernel: the kernel defines
-// THREADS, SUM, CODEC, DMASK, D128, COHORT, BS, GAPS and DEC as compile-time constants and has the arguments rk, tb, n_chains, all_half_arg, iter0, mask_lo,
-// mask_hi, te0, cq, cc, cb, cg and dmask in scope.
+// prf_chain_cohort_kernel<THREADS>, prf_chain_cohort_cut_kernel<THREADS> and prf_chain_cohort_batch_kernel<THREADS, BS> (kernels.hip), included INSIDE each kernel: the kernel defines
+// THREADS, SUM, CODEC, DMASK, D128, COHORT, BS, GAPS, DEC and CUT as compile-time constants and has the arguments rk, tb, n_chains, all_half_arg, iter0, mask_lo,
+// mask_hi, te0, cq, cc, cb, cg, dmask and cut_stride in scope.
+// CUT (COHORT only, prf_chain_cohort_cut_kernel): a SHORT cohort cut into n_chains runs of consecutive clients (cohort_cut.h), every run its
+// own summed double-mask chain over the same elements.  tb.sum_out[cur] is per chain already; the decrypt mask of chain `cur` goes to
+// dmask + cur * cut_stride where the other DMASK kernels have one mask for the launch's one chain.  The chains' masks telescope and
+// their sums add up: one combine pass (cohort_cut_combine_kernel, stream.hip) gives what the uncut launch writes.  Every branch on CUT is
+// an `if constexpr`: the other instantiations compile to the kernels they were.
 // DEC (D128 only, prf_dec_sum128_kernel): where the DMASK kernels store the decrypt mask D on the last stream, the launch stores the decrypt of
 // the sum it writes beside it, sum + D mod 2^b; `dmask` addresses that output.  Every branch on DEC is an `if constexpr`.
 // GAPS (COHORT only, prf_chain_cohort_runs_kernel / prf_chain_cohort_batch_runs_kernel): the cohort's cipher indices form SEVERAL runs -- clients
@@ -25,7 +30,9 @@
     static_assert(BS == 0 || COHORT, "batching is a form of the cohort front end");
     static_assert(!GAPS || COHORT, "several runs of indices are a form of the cohort chain");
     static_assert(!DEC || D128, "the decrypted sum is written by the int_bits = 128 specialisation");
+    static_assert(!CUT || (COHORT && BS == 0 && !GAPS), "the cut is a form of the one-run, un-batched cohort chain");
     (void)cg;
+    (void)cut_stride;
     (void)dmask;
     (void)cc;
     (void)cb;
@@ -282,7 +289,16 @@
                                     }
                                 }
                             } else if (last_stream && (!COHORT || dmask != nullptr)) {
-                                if (p == 0) {
+                                if constexpr (CUT) {
+                                    uint64_t *const dm = dmask + static_cast<uint64_t>(cur) * cut_stride;     // (chain cur's own mask)
+                                    if (p == 0) {
+                                        if (a0) st128_nt(dm + 2 * k0, (c0 - dA0) & mask);
+                                        if (a1) st128_nt(dm + 2 * k1, (c1 - dA1) & mask);
+                                    } else {
+                                        if (a0) st128_nt(dm + 2 * k0, (c0 - dB0) & mask);
+                                        if (a1) st128_nt(dm + 2 * k1, (c1 - dB1) & mask);
+                                    }
+                                } else if (p == 0) {
                                     if (a0) st128_nt(dmask + 2 * k0, (c0 - dA0) & mask);
                                     if (a1) st128_nt(dmask + 2 * k1, (c1 - dA1) & mask);
                                 } else {
@@ -448,8 +464,14 @@
                             if (a1) st128_nt(dmask + 2 * k1, (q1 + (c1 - d1)) & mask);
                         }
                     } else if (c == n_streams - 1 && (!COHORT || dmask != nullptr)) {
-                        if (a0) st128_nt(dmask + 2 * k0, (c0 - d0) & mask);
-                        if (a1) st128_nt(dmask + 2 * k1, (c1 - d1) & mask);
+                        if constexpr (CUT) {
+                            uint64_t *const dm = dmask + static_cast<uint64_t>(cur) * cut_stride;
+                            if (a0) st128_nt(dm + 2 * k0, (c0 - d0) & mask);
+                            if (a1) st128_nt(dm + 2 * k1, (c1 - d1) & mask);
+                        } else {
+                            if (a0) st128_nt(dmask + 2 * k0, (c0 - d0) & mask);
+                            if (a1) st128_nt(dmask + 2 * k1, (c1 - d1) & mask);
+                        }
                     }
                 }
                 p0 = c0; p1 = c1;

@@ -395,6 +395,82 @@ hipError_t launch_aggregate_elem(const LaunchEnv &env, int C, const uint64_t *co
     return hipGetLastError();
 }
 
+// ---- the combine pass of a CUT cohort launch (cohort_cut.h; launch_prf_cohort_cut / launch_small_cohort_cut, kernels.hip) ----
+// sum[k] = sum_p psum[p n + k] mod 2^b and, where the launch keeps a decrypt mask, dmask[k] = sum_p pmask[p n + k] mod 2^b: the pieces' sums
+// add up and their masks telescope to what the uncut launch writes.  Two-limb elements, one per lane and trip in 16-byte accesses; the
+// scratch is read once (non-temporal loads), the results are read again by the next pass (plain stores).  parts <= 16.
+__global__ __launch_bounds__(kStreamThreads) void cohort_cut_combine_kernel(int parts, uint64_t n, const uint64_t *__restrict__ psum, uint64_t *__restrict__ sum,
+                                                                            const uint64_t *__restrict__ pmask, uint64_t *__restrict__ dmask,
+                                                                            uint64_t mask_lo, uint64_t mask_hi)
+{
+    const u128 mask = (static_cast<u128>(mask_hi) << 64) | mask_lo;
+    for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * kStreamThreads + threadIdx.x; k < n; k += static_cast<uint64_t>(gridDim.x) * kStreamThreads) {
+        u128 acc = 0, macc = 0;
+#pragma unroll 4
+        for (int p = 0; p < parts; p++) acc += ld128_nt(psum + 2 * (static_cast<uint64_t>(p) * n + k));
+        if (pmask != nullptr) {
+#pragma unroll 4
+            for (int p = 0; p < parts; p++) macc += ld128_nt(pmask + 2 * (static_cast<uint64_t>(p) * n + k));
+        }
+        st128(sum + 2 * k, acc & mask);
+        if (pmask != nullptr) st128(dmask + 2 * k, macc & mask);
+    }
+}
+
+// the compact layout's form: uint32 sums masked to b bits, no mask.  VEC: n is a multiple of four and every pointer 16-byte aligned, so
+// every piece's block is too -- four elements per lane in 16-byte accesses; otherwise one element per lane.
+template <bool VEC>
+__global__ __launch_bounds__(kStreamThreads) void cohort_cut_combine_u32_kernel(int parts, uint64_t n, const uint32_t *__restrict__ psum, uint32_t *__restrict__ sum,
+                                                                                uint32_t mask)
+{
+    if (VEC) {
+        const uint64_t n4 = n / 4;
+        for (uint64_t s = static_cast<uint64_t>(blockIdx.x) * kStreamThreads + threadIdx.x; s < n4; s += static_cast<uint64_t>(gridDim.x) * kStreamThreads) {
+            uint32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+#pragma unroll 4
+            for (int p = 0; p < parts; p++) {
+                const u64x2 v = __builtin_nontemporal_load(reinterpret_cast<const u64x2 *>(psum + static_cast<uint64_t>(p) * n) + s);
+                a0 += static_cast<uint32_t>(v[0]); a1 += static_cast<uint32_t>(v[0] >> 32);
+                a2 += static_cast<uint32_t>(v[1]); a3 += static_cast<uint32_t>(v[1] >> 32);
+            }
+            u64x2 r;
+            r[0] = (a0 & mask) | (static_cast<uint64_t>(a1 & mask) << 32);
+            r[1] = (a2 & mask) | (static_cast<uint64_t>(a3 & mask) << 32);
+            *(reinterpret_cast<u64x2 *>(sum) + s) = r;
+        }
+    } else {
+        for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * kStreamThreads + threadIdx.x; k < n; k += static_cast<uint64_t>(gridDim.x) * kStreamThreads) {
+            uint32_t a = 0;
+#pragma unroll 4
+            for (int p = 0; p < parts; p++) a += __builtin_nontemporal_load(psum + static_cast<uint64_t>(p) * n + k);
+            sum[k] = a & mask;
+        }
+    }
+}
+
+hipError_t launch_cohort_cut_combine(const LaunchEnv &env, int parts, uint64_t n, const uint64_t *psum_dev, uint64_t *sum_dev, const uint64_t *pmask_dev,
+                                     uint64_t *dmask_dev)
+{
+    if (n == 0) return hipSuccess;
+    if (parts < 1 || env.b <= 64 || !psum_dev || !sum_dev || (pmask_dev && !dmask_dev)) return hipErrorInvalidValue;
+    uint64_t lo, hi;
+    masks_of(env.b, &lo, &hi);
+    hipLaunchKernelGGL(cohort_cut_combine_kernel, dim3(stream_grid(env, n)), dim3(kStreamThreads), 0, env.stream, parts, n, psum_dev, sum_dev, pmask_dev,
+                       dmask_dev, lo, hi);
+    return hipGetLastError();
+}
+
+hipError_t launch_cohort_cut_combine_u32(const LaunchEnv &env, int parts, uint64_t n, const uint32_t *psum_dev, uint32_t *sum_dev)
+{
+    if (n == 0) return hipSuccess;
+    if (parts < 1 || env.b > 32 || !psum_dev || !sum_dev) return hipErrorInvalidValue;
+    const uint32_t mask = env.b == 32 ? 0xffffffffu : ((1u << env.b) - 1u);
+    const bool vec = n % 4 == 0 && ((reinterpret_cast<uintptr_t>(psum_dev) | reinterpret_cast<uintptr_t>(sum_dev)) & 15u) == 0;
+    if (vec) hipLaunchKernelGGL(cohort_cut_combine_u32_kernel<true>, dim3(stream_grid(env, n / 4)), dim3(kStreamThreads), 0, env.stream, parts, n, psum_dev, sum_dev, mask);
+    else hipLaunchKernelGGL(cohort_cut_combine_u32_kernel<false>, dim3(stream_grid(env, n)), dim3(kStreamThreads), 0, env.stream, parts, n, psum_dev, sum_dev, mask);
+    return hipGetLastError();
+}
+
 // ---- packed aggregate: C-way add of n_limbs-limb integers with full carry propagation ----
 // Stage 1 (this kernel): per 16-B slot the C-way column sums (lo, hi = overflow count), the
 // fold hi -> next limb, and a (generate, propagate) carry scan inside the 256-slot block via

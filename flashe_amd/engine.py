@@ -741,6 +741,36 @@ class Engine:
                                                               self._ptr(u), pc, self._ptr(sum_out))
         return self._took(rc)
 
+    def cohort_cut_parts(self, n_clients, n, n_jobs, compact=False):
+        """The pieces quantize_encrypt_cohort_cut_dev (compact: its _u32 form) will cut a cohort of n_clients clients with n values into
+        (flashe_cohort_cut_parts): the caller sizes the scratch from it.  0: the library declines the shape (FLASHE_ENOTSUP)."""
+        parts = ctypes.c_int(0)
+        rc = self._lib.flashe_cohort_cut_parts(self._h, int(n_clients), int(n), n_jobs, 1 if compact else 0, ctypes.byref(parts))
+        return parts.value if self._took(rc) else 0
+
+    def quantize_encrypt_cohort_cut_dev(self, it, first_idx, n, n_jobs, layers, srcs, dtypes, element_bits, u, cts, sum_out, dmask=None, scratch=None):
+        """quantize_encrypt_cohort_dev for a vector of ANY length (flashe_quantize_encrypt_cohort_cut_dev): the summed chain cut into
+        cohort_cut_parts(...) runs of consecutive clients and one combine pass.  scratch: 16-byte aligned, parts x n x 16 bytes, twice
+        that with dmask; may be None when parts == 1.  Returns False -- nothing was launched -- when the library declines the shape
+        (FLASHE_ENOTSUP), True otherwise."""
+        arr, nl = self._tensor_layers(layers)
+        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
+        pc, _k = self._ptr_array(cts)
+        rc = self._lib.flashe_quantize_encrypt_cohort_cut_dev(self._h, it, int(first_idx), C, int(n), n_jobs, arr, nl, ps, pd, element_bits,
+                                                              self._ptr(u), pc, self._ptr(sum_out), self._ptr(dmask), self._ptr(scratch))
+        return self._took(rc)
+
+    def quantize_encrypt_cohort_cut_u32_dev(self, it, first_idx, n, n_jobs, layers, srcs, dtypes, element_bits, u, cts, sum_out, scratch=None):
+        """quantize_encrypt_cohort_u32_dev for a vector of ANY length (flashe_quantize_encrypt_cohort_cut_u32_dev, int_bits 16 / 20 / 23 /
+        24 / 32): scratch of cohort_cut_parts(..., compact=True) x n x 4 bytes, 16-byte aligned; may be None when parts == 1.  Returns
+        False -- nothing was launched -- when the library declines the shape (FLASHE_ENOTSUP), True otherwise."""
+        arr, nl = self._tensor_layers(layers)
+        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
+        pc, _k = self._ptr_array(cts)
+        rc = self._lib.flashe_quantize_encrypt_cohort_cut_u32_dev(self._h, it, int(first_idx), C, int(n), n_jobs, arr, nl, ps, pd, element_bits,
+                                                                  self._ptr(u), pc, self._ptr(sum_out), self._ptr(scratch))
+        return self._took(rc)
+
     def quantize_batch_encrypt_cohort_dev(self, it, first_idx, n_values, n_elems, n_jobs, layers, srcs, dtypes, element_bits, field_bits, u, cts,
                                           sum_out, dmask=None):
         """quantize_encrypt_cohort_dev for a BATCHED job (flashe_quantize_batch_encrypt_cohort_dev, int_bits > 64, int_bits // field_bits

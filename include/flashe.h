@@ -86,7 +86,8 @@ typedef struct flashe_ctx flashe_ctx;
  *      flashe_finish_row + flashe_finish_layers_dev (the aggregator's degree scaling either side of the fused client step: the multiply
  *      in the stage pass, the two divisions and the last round's model in the store + statistics pass);
  *      flashe_encrypt_batch_sum_decrypt_dev (a co-located round's encrypts, their sum and the decrypt of the sum: one launch at
- *      int_bits 128) */
+ *      int_bits 128); flashe_cohort_cut_parts + flashe_quantize_encrypt_cohort_cut_dev / flashe_quantize_encrypt_cohort_cut_u32_dev (a
+ *      cohort whose vector does not fill the chip uncut: the summed chain cut into runs of clients and one combine pass) */
 #define FLASHE_ABI_VERSION 4
 int flashe_abi_version(void);
 int flashe_device_count(int *count);
@@ -712,6 +713,38 @@ int flashe_quantize_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uint32_t 
 int flashe_quantize_encrypt_cohort_u32_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs,
                                            const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
                                            int element_bits, const double *u_dev, uint32_t *const *ct_dev, uint32_t *sum_out_dev);
+/* A SHORT cohort (new), jzf_quantize.py:394-491, jzf_flashe.py:349-353, 480-481, jzf_aggregator.py:424-430: the two cohort launches above
+ * decline a vector that does not fill the chip uncut, and many clients with a small model is the shape a federation simulated on one card
+ * most often has.  The three entry points below take any n >= 1: the summed chain is CUT into `parts` runs of consecutive clients,
+ * piece p = clients [C p / parts, C (p + 1) / parts), each a double-mask chain of its own over the same elements (a cut costs one PRF
+ * stream: C + parts streams instead of C + 1).  Every piece writes the sum of its own ciphertexts and its own decrypt mask
+ * term(b_p) - term(a_p) to scratch; the sums add up and the masks telescope (b_p = a_{p+1}), so ONE short memory-bound combine pass
+ * gives sum_out_dev and dmask_dev: two launches whatever C is, no integer plaintext in HBM, every output bit for bit what the uncut
+ * launch (or C flashe_quantize_encrypt_tensors_dev calls and flashe_aggregate_elem_dev) writes.
+ * flashe_cohort_cut_parts: *parts = the pieces the launch will use for n_clients clients and n values -- as many as fill the chip once
+ * (the largest count whose items do not outnumber its 16 x flashe_ctx_cu_count waves; an item: 128 elements at int_bits > 64, 128 AES
+ * blocks in the compact layout), never fewer than four clients per piece, at most 16 pieces; 1 (one launch, no combine, no scratch)
+ * from half an item per wave upward.  compact != 0: the rule of the _u32 entry
+ * point (n_jobs counts its AES blocks; ignored otherwise).  FLASHE_ENOTSUP (*parts = 0) where the launch itself would decline. */
+int flashe_cohort_cut_parts(flashe_ctx *ctx, int n_clients, uint64_t n, uint32_t n_jobs, int compact, int *parts);
+/* flashe_quantize_encrypt_cohort_dev for any n >= 1 (new), jzf_quantize.py:394-491, jzf_flashe.py:349-353, 480-481,
+ * jzf_aggregator.py:424-430: its arguments, checks, stage pass and outputs, plus scratch_dev: caller-allocated, 16-byte aligned,
+ * parts x n x 16 bytes for the pieces' sums and as much again when dmask_dev is given (parts from flashe_cohort_cut_parts); not
+ * touched and may be NULL when parts == 1.  FLASHE_EINVAL: a scratch that is NULL with parts > 1, misaligned, or one of the outputs.
+ * Returns FLASHE_ENOTSUP -- nothing launched -- for int_bits <= 64, more than 128 clients, n = 0 or n > 2^32, FLASHE_CHAIN=0, another
+ * PRF backend.  The table uploads synchronise; not capturable. */
+int flashe_quantize_encrypt_cohort_cut_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                           const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                           int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev, uint64_t *dmask_dev,
+                                           uint64_t *scratch_dev);
+/* flashe_quantize_encrypt_cohort_u32_dev for any n >= 1 (new), jzf_quantize.py:394-491, jzf_flashe.py:349-353, 480-481,
+ * jzf_aggregator.py:424-430: its arguments, checks, stage pass and outputs (uint32 ciphertexts and their uint32 sum at int_bits
+ * 16 / 20 / 23 / 24 / 32, no decrypt mask), plus scratch_dev: caller-allocated, 16-byte aligned, parts x n x 4 bytes; not touched and
+ * may be NULL when parts == 1.  FLASHE_EINVAL as above.  Returns FLASHE_ENOTSUP -- nothing launched -- for a ctx whose
+ * flashe_ctx_compact_layout is 0, another int_bits, more than 128 clients, n = 0 or n >= 2^32.  Not capturable. */
+int flashe_quantize_encrypt_cohort_cut_u32_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                               const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                               int element_bits, const double *u_dev, uint32_t *const *ct_dev, uint32_t *sum_out_dev, uint32_t *scratch_dev);
 /* The same cohort for a BATCHED job at int_bits > 64 (new), jzf_quantize.py:55-67, 162-185, jzf_flashe.py:349-353, jzf_aggregator.py:424-430:
  * ONE chained launch over the n_elems = sum_l ceil(size_l / bs) batched elements of the model (bs = int_bits / field_bits values per
  * element, every layer padded to whole elements on its own, the first value of an element in its most significant field).  It writes
