@@ -1532,10 +1532,11 @@ int flashe_aggregate_elem_dev(flashe_ctx *ctx, int C, const uint64_t *const *cts
 {
     CHECK_CTX(ctx);
     if (C < 1 || !cts_dev || (n && !out_dev)) return fail(ctx, FLASHE_EINVAL, "aggregate_elem: bad arguments (C = %d)", C);
-    // two-limb vectors: 16-byte aligned; one-limb vectors: 8 bytes suffice (a sub-range may start at an odd element: slower 8-byte form)
+    // out of two-limb vectors: 16-byte aligned; one-limb vectors and every operand: 8 bytes suffice (a sub-range may start at an odd element, a
+    // two-limb operand may sit 8 bytes off: slower 8-byte forms -- flashe_aggregate_decrypt_range_dev falls back to this for such an operand)
     const uintptr_t need = ctx->limbs == 2 ? 15u : 7u;
     if (reinterpret_cast<uintptr_t>(out_dev) & need) return fail(ctx, FLASHE_EINVAL, "device vectors must be %d-byte aligned", static_cast<int>(need + 1));
-    if (int rc = check_operands(ctx, C, cts_dev, static_cast<int>(need + 1))) return rc;
+    if (int rc = check_operands(ctx, C, cts_dev, 8)) return rc;
     if (n == 0) return FLASHE_OK;
     // at most kMaxOps operands per pass; later passes fold the running sum (out) back in
     std::vector<const uint64_t *> ops;

@@ -307,6 +307,24 @@ __global__ __launch_bounds__(kStreamThreads) void aggregate_elem8_kernel(int C, 
     }
 }
 
+// two-limb vectors with an operand that is only 8-byte aligned: one element per lane, its limbs in two 8-byte loads (out is 16-byte aligned)
+__global__ __launch_bounds__(kStreamThreads) void aggregate_elem8_wide_kernel(int C, const PtrTable ops, uint64_t n, uint64_t *out, uint64_t mask_lo,
+                                                                              uint64_t mask_hi)
+{
+    const uint64_t *const *tab = ops.p;
+    for (uint64_t j = static_cast<uint64_t>(blockIdx.x) * kStreamThreads + threadIdx.x; j < n; j += static_cast<uint64_t>(gridDim.x) * kStreamThreads) {
+        u128 acc = 0;
+#pragma unroll 4
+        for (int c = 0; c < C; c++) {
+            const uint64_t lo = __builtin_nontemporal_load(tab[c] + 2 * j), hi = __builtin_nontemporal_load(tab[c] + 2 * j + 1);
+            acc += (static_cast<u128>(hi) << 64) | lo;
+        }
+        u64x2 r;
+        r[0] = static_cast<uint64_t>(acc) & mask_lo; r[1] = static_cast<uint64_t>(acc >> 64) & mask_hi;
+        __builtin_nontemporal_store(r, reinterpret_cast<u64x2 *>(out + 2 * j));
+    }
+}
+
 // compact layout (int_bits <= 32, uint32 elements): four elements per lane in 16-byte accesses; 32-bit sums wrap mod 2^32, which 2^b divides
 template <bool VEC>
 __global__ __launch_bounds__(kStreamThreads) void aggregate_elem_u32_kernel(int C, const PtrTable ops, uint64_t n, uint32_t *out, uint32_t mask)
@@ -377,7 +395,11 @@ hipError_t launch_aggregate_elem(const LaunchEnv &env, int C, const uint64_t *co
     bool a16 = (reinterpret_cast<uintptr_t>(out_dev) & 15u) == 0;
     for (int c = 0; c < C; c++) a16 = a16 && (reinterpret_cast<uintptr_t>(ops[c]) & 15u) == 0;
     if (!a16) {
-        if (env.b > 64) return hipErrorInvalidValue;
+        if (env.b > 64) {
+            if (reinterpret_cast<uintptr_t>(out_dev) & 15u) return hipErrorInvalidValue;
+            hipLaunchKernelGGL(aggregate_elem8_wide_kernel, dim3(stream_grid(env, n)), dim3(kStreamThreads), 0, env.stream, C, tab_dev, n, out_dev, lo, hi);
+            return hipGetLastError();
+        }
         hipLaunchKernelGGL(aggregate_elem8_kernel, dim3(stream_grid(env, n)), dim3(kStreamThreads), 0, env.stream, C, tab_dev, n, out_dev, lo);
         return hipGetLastError();
     }
