@@ -32,7 +32,12 @@ which this example checks.
                -- the sequential clients below draw from identically seeded generators and must leave them in the same place;
                --rng pcg64 takes np.random.default_rng(seed) itself (PCG64, a 128-bit LCG): every lane of ONE launch jumps to its first
                draw and walks a fixed stride, and the states come back the same way; --rng sfc64 takes any other Generator: the same
-               call, drawn on the host"""
+               call, drawn on the host
+  --packed     a DENSE job's arbiter adds the clients' bit-packed models as one integer (carries cross from one element into the next),
+               so its global model is not the decrypt of the element-wise sum: cohort.aggregate_packed() is that reduce of the upload
+               -- one pass over the ciphertexts where they lie, no packed vectors -- and decrypt_unquantize(packed=True) decrypts it
+               (after a chained launch still by adding the mask that launch wrote); checked against the clients' own
+               cipher.aggregate(packed=True) and decrypt"""
 import argparse
 import os
 import sys
@@ -76,6 +81,7 @@ def main():
     ap.add_argument("--precompute", action="store_true")
     ap.add_argument("--cut", action="store_true", help="forty LeNet-sized models through the cut chained launch")
     ap.add_argument("--drop", default="", help="comma-separated clients that miss the round, e.g. 2,7")
+    ap.add_argument("--packed", action="store_true", help="reduce the upload as a dense job's arbiter does: on the bit-packed integers")
     ap.add_argument("--rng", choices=["philox", "pcg64", "sfc64"], default=None, help="draw from one np.random.Generator per client")
     opt = ap.parse_args()
     cm.N_JOBS = 16                                           # every party must use the same value
@@ -112,7 +118,8 @@ def main():
         gens = generators()
         upload = cohort.quantize_encrypt([Weights(layers[c]) for c in present], normalize=True, present=present if dropped else None, rng=gens)
         new_global = {name: torch.empty_like(t) for name, t in layers[0].items()}
-        cohort.decrypt_unquantize(out=new_global, unnormalize=True)
+        packed_sum = cohort.aggregate_packed() if opt.packed else None
+        cohort.decrypt_unquantize(out=new_global, unnormalize=True, packed=opt.packed)
     print(f"{C} clients{f' of which {dropped} dropped out' if dropped else ''}, {sum(t.numel() for t in layers[0].values())} parameters each: path {upload.path!r}, "
           f"{len(upload.ciphertexts)} ciphertexts and their sum in HBM ({upload.partial_sum.elem_bytes * upload.partial_sum.limbs} bytes per element)")
 
@@ -133,14 +140,18 @@ def main():
             w = clients[c].quantize_encrypt(Weights(layers[c]), device=True, normalize=True, rng=twins[p] if twins else None)
             cts.append(w._weights[w.walking_order[0]])
         lead = clients[present[0]]
-        agg = lead.cipher.aggregate(cts)
+        agg_elem = lead.cipher.aggregate(cts)
+        agg = lead.cipher.aggregate(cts, packed=True) if opt.packed else agg_elem
         lead.set_idx_list(list(present))                     # who uploaded: the decrypt telescopes the runs of indices
         want = {name: torch.empty_like(t) for name, t in layers[0].items()}
         lead.decrypt_unquantize(Weights({sorted(layers[0])[0]: agg}), out=want, unnormalize=True)
     assert upload.present == present
     for p, c in enumerate(present):
         assert np.array_equal(values(upload.ciphertexts[p]), values(cts[p])), f"client {c}'s upload differs"
-    assert np.array_equal(values(upload.partial_sum), values(agg))
+    assert np.array_equal(values(upload.partial_sum), values(agg_elem))
+    if opt.packed:
+        assert np.array_equal(values(packed_sum), values(agg))
+        print(f"packed reduce: {int((values(packed_sum) != values(agg_elem)).any(axis=1).sum())} of {len(packed_sum)} elements differ from the element-wise sum by a carry")
     if gens:                                                 # the cohort handed every generator back where its client's own step leaves it
         assert all(a.random() == b.random() for a, b in zip(gens, twins))
     for name in want:

@@ -187,6 +187,8 @@ _SIGNATURES = {
     "flashe_narrow_u32_dev": (c_int, [c_vp, c_u64, c_vp, c_vp]),
     "flashe_aggregate_packed_dev": (c_int, [c_vp, c_int, ctypes.POINTER(c_vp), c_u64, c_u64, c_vp]),
     "flashe_aggregate_packed": (c_int, [c_vp, c_int, ctypes.POINTER(c_vp), c_u64, c_u64, c_vp]),
+    "flashe_aggregate_packed_elems_dev": (c_int, [c_vp, c_int, ctypes.POINTER(c_vp), c_u64, c_vp]),
+    "flashe_aggregate_packed_elems_u32_dev": (c_int, [c_vp, c_int, ctypes.POINTER(c_vp), c_u64, c_vp]),
     "flashe_packed_probe_dev": (c_int, [c_vp, c_u64, c_vp, c_vp]),
     "flashe_packed_add_carry_dev": (c_int, [c_vp, c_u64, c_u64, c_u64, c_vp]),
     "flashe_packed_resolve_carry_dev": (c_int, [c_vp, c_u64, c_u64, c_vp, c_int, c_vp]),

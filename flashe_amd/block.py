@@ -1406,7 +1406,10 @@ class FlasheCohort(object):
     decrypt_unquantize() decrypts the sum with the telescoped lists.
     A precompute job ("precompute": {"enable": true}) calls prepare_encrypt() in idle time: the next round's masks of all clients as one
     chain of n_local + 1 streams, held by the cohort; the next quantize_encrypt is then ONE online launch with no AES ("prepared-cohort")
-    at any int_bits, batched or not, compact or not.  Without that call the clients' own masks run "per-client" as before."""
+    at any int_bits, batched or not, compact or not.  Without that call the clients' own masks run "per-client" as before.
+    A DENSE job's arbiter adds the clients' bit-packed models as one integer (jzf_aggregator.py:406-419); CohortUpload.partial_sum is
+    the element-wise sum.  aggregate_packed() is that packed reduce of an upload, one pass over the ciphertexts where they lie, and
+    decrypt_unquantize(packed=True) decrypts it, so that a cohort which simulates a dense job returns the global model the job produces."""
 
     def __init__(self, args, first_idx, n_local, num_clients, prp_seed, device=0, stream=None, compact=False, cut=False):
         if n_local < 1 or first_idx < 0 or first_idx + n_local > num_clients:
@@ -1800,8 +1803,29 @@ class FlasheCohort(object):
         self._last = CohortUpload(cts, psum, PER_CLIENT, [self.first_idx + p for p in present])
         return self._last
 
-    def decrypt_unquantize(self, aggregate=None, uploaded=None, out=None, unnormalize=False, degree=None, total_degree=None, last_round=None):
-        """degree, total_degree, last_round (new): FlasheClient.decrypt_unquantize's, handed to the lead.  When the cohort decrypts its own
+    def aggregate_packed(self, upload=None):
+        """The arbiter's PACKED reduce (jzf_aggregator.py:406-419: the clients' compressed models added as one integer, carries crossing
+        from element j + 1 into element j) of an upload's ciphertexts -- default: the last upload -- as a DeviceVector in the upload's
+        layout: what FlasheCipher.aggregate(ciphertexts, packed=True) returns for the clients' own FlasheClient ciphertexts, one pass
+        over the unpacked vectors where the engine has it (flashe_aggregate_packed_elems_dev / its _u32 form).  A dense job's arbiter
+        reduces this way; CohortUpload.partial_sum is the element-wise sum.  The whole federation's sum is the packed reduce of the
+        cohorts' results, so a partial cohort's result is something an arbiter can add on."""
+        up = self._last if upload is None else upload
+        if up is None:
+            raise ValueError("aggregate_packed() needs the upload of this iteration (quantize_encrypt first)")
+        from . import cipher as _cipher_mod
+        eng = self.lead.cipher.engine
+        res = _cipher_mod.aggregate(list(up.ciphertexts), self.lead.int_bits, packed=True, _engine=eng, keep_on_device=True, _compact_result=self.compact)
+        return res.narrowed(eng) if self.compact and not res.compact else res
+
+    def decrypt_unquantize(self, aggregate=None, uploaded=None, out=None, unnormalize=False, degree=None, total_degree=None, last_round=None,
+                           packed=False):
+        """packed=True (new; only without `aggregate`, ValueError otherwise): the cohort's own upload is reduced as a dense job's arbiter
+        reduces it -- aggregate_packed() -- and THAT sum is decrypted instead of partial_sum: after a "cohort-chain" / "cut-chain" upload
+        still by adding the mask the launch wrote, in one pass (the mask does not depend on which sum it is added to), otherwise with
+        the telescoped lists; present= rounds included.
+
+        degree, total_degree, last_round (new): FlasheClient.decrypt_unquantize's, handed to the lead.  When the cohort decrypts its own
         sum and both degrees are omitted after a quantize_encrypt(degrees=...), degree is the first present client's and total_degree the
         left-to-right sum of the present clients' degrees (what the arbiter reduces, jzf_aggregator.py:380).
 
@@ -1813,12 +1837,16 @@ class FlasheCohort(object):
         (default: all num_clients)."""
         ld = self.lead
         own = aggregate is None
+        if packed and not own:
+            raise ValueError("packed=True decrypts the cohort's own upload: it cannot be combined with aggregate=")
         if aggregate is None:
             if self.n_local != self.num_clients:
                 raise ValueError(f"the cohort holds {self.n_local} of {self.num_clients} clients: decrypt_unquantize needs the federation's aggregate")
             if self._last is None:
                 raise ValueError("decrypt_unquantize() without an aggregate needs the upload of this iteration (quantize_encrypt first)")
             aggregate = self._last.partial_sum
+            if packed:
+                aggregate = packed_sum = self.aggregate_packed(self._last)
         if uploaded is None:
             uploaded = list(self._last.present) if own and self._last.present is not None else list(range(self.num_clients))
         if ld.shape_dict is None:
@@ -1829,7 +1857,14 @@ class FlasheCohort(object):
             degree, total_degree = self._degrees[0], functools.reduce(operator.add, self._degrees)
         degree, total_degree = ld._back_degrees(degree, total_degree)      # (refused before set_idx_list touches the cipher)
         ld.set_idx_list(list(uploaded))
-        return ld.decrypt_unquantize(aggregate, out=out, unnormalize=unnormalize, degree=degree, total_degree=total_degree, last_round=last_round)
+        kept = ld._cohort_mask
+        if packed and kept is not None and kept[0] == self._last.partial_sum.ptr:
+            ld._cohort_mask = (packed_sum.ptr,) + kept[1:]      # the mask the launch wrote decrypts the packed sum of the same upload too
+        try:
+            return ld.decrypt_unquantize(aggregate, out=out, unnormalize=unnormalize, degree=degree, total_degree=total_degree,
+                                         last_round=last_round)
+        finally:
+            ld._cohort_mask = kept
 
 
 # ---- a cohort of sparse-job clients hosted on one GPU (new) ----------------------------------------------------------------------

@@ -770,21 +770,26 @@ class FlasheCipher(object):
         return out
 
 
-def aggregate(ciphertexts, int_bits, packed=False, device=0, _engine=None, keep_on_device=None):
+def aggregate(ciphertexts, int_bits, packed=False, device=0, _engine=None, keep_on_device=None, _compact_result=False):
     """reduce(lambda x, y: (x + y) % mod, models) on the GPU.
 
     packed=False: mod = 1 << int_bits per element (jzf_aggregator.py:424-430).
     packed=True : every operand is bit-packed (JZFTransferableWeights.compress,
     jzf_weights.py:155-195), added mod 1 << (int_bits * n) with carries crossing element
-    boundaries (jzf_aggregator.py:406-419), then unpacked again (decompress, :197-231).
+    boundaries (jzf_aggregator.py:406-419), then unpacked again (decompress, :197-231) -- in one pass over the unpacked vectors
+    (flashe_aggregate_packed_elems_dev) wherever the engine has that call and takes the shape.  All-compact operands are reduced as
+    they are (the _u32 call: nothing is widened but the result, which keeps the one-limb layout packed=True has always returned;
+    _compact_result=True, FlasheCohort's: the uint32 result as it is).
     keep_on_device: True = return a DeviceVector, False = a host array, None = what the first operand is."""
     if len(ciphertexts) == 0:
         raise TypeError("reduce() of empty sequence with no initial value")
     eng = _engine or Engine(bytes(32), int_bits, device=device)
     want_dev = isinstance(ciphertexts[0], DeviceVector) if keep_on_device is None else bool(keep_on_device)
     is_compact = lambda c: (isinstance(c, DeviceVector) and c.compact) or (isinstance(c, np.ndarray) and c.dtype == np.uint32)    # noqa: E731
-    if (int_bits <= 32 and not packed and hasattr(eng, "aggregate_elem_u32_dev") and all(is_compact(c) for c in ciphertexts)):
-        # compact layout: uint32 operands (handles or arrays), uint32 result -- half the bytes of the one-limb reduce
+    if (int_bits <= 32 and hasattr(eng, "aggregate_packed_elems_u32_dev" if packed else "aggregate_elem_u32_dev")
+            and all(is_compact(c) for c in ciphertexts)):
+        # compact layout: uint32 operands (handles or arrays), uint32 result -- half the bytes of the one-limb reduce; packed: the packed
+        # sum computed on the unpacked uint32 vectors in one pass (flashe_aggregate_packed_elems_u32_dev), no operand widened
         ops, held = [], {}
         for c in ciphertexts:
             if id(c) not in held:
@@ -798,8 +803,16 @@ def aggregate(ciphertexts, int_bits, packed=False, device=0, _engine=None, keep_
         if any(len(o) != n for o in ops):
             raise ValueError("operands could not be broadcast together")
         out = DeviceVector(eng, n, 1, elem_bytes=4)
-        eng.aggregate_elem_u32_dev([o.buf for o in ops], n, out.buf)
-        return out.mark_ready() if want_dev else out.to_host()
+        if not packed:
+            eng.aggregate_elem_u32_dev([o.buf for o in ops], n, out.buf)
+            return out.mark_ready() if want_dev else out.to_host()
+        if eng.aggregate_packed_elems_u32_dev([o.buf for o in ops], n, out.buf):
+            if _compact_result:
+                return out.mark_ready() if want_dev else out.to_host()
+            wide = out.mark_ready().widened(eng)
+            first = ciphertexts[0]
+            return wide if want_dev else _from_limbs(wide.to_host(), "u64_1d" if isinstance(first, np.ndarray) and first.ndim == 1 else "u64_2d")
+        # (declined -- more operands than 2^int_bits: widened, packed, reduced and unpacked below)
     # (a compact operand among one-limb ones, or the packed reduce: widened on the device)
     ciphertexts = [c.widened(eng) if (isinstance(c, DeviceVector) and c.compact) else (c.astype(np.uint64) if (isinstance(c, np.ndarray) and c.dtype == np.uint32) else c)
                    for c in ciphertexts]
@@ -836,7 +849,9 @@ def aggregate(ciphertexts, int_bits, packed=False, device=0, _engine=None, keep_
     out = DeviceVector(eng, n)
     if not packed:
         eng.aggregate_elem_dev(dsrc, n, out.buf)
-    else:
+    elif not (hasattr(eng, "aggregate_packed_elems_dev") and eng.aggregate_packed_elems_dev(dsrc, n, out.buf)):
+        # (the packed sum in one pass over the unpacked vectors where the engine has it and takes the shape; otherwise C packs, the
+        # packed reduce and the unpack)
         total_bits = n * int_bits
         n_limbs = (total_bits + 63) // 64
         dpk = [eng.alloc(max(n_limbs * 8, 16)) for _ in arrs]

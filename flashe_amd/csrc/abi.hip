@@ -1654,6 +1654,58 @@ int flashe_aggregate_packed_dev(flashe_ctx *ctx, int C, const uint64_t *const *p
     return FLASHE_OK;
 }
 
+// The packed reduce of UNPACKED vectors (stream.hip, "packed aggregate in the ELEMENT domain"): elem_bytes 4 is the compact layout.
+// A pass takes at most kMaxOps operands and needs them to number at most 2^int_bits (a one-bit carry between elements); partial results
+// -- valid operands themselves -- ping-pong through ctx scratch so that no pass writes a vector it reads.
+static int aggregate_packed_elems(flashe_ctx *ctx, const char *who, int C, const void *const *cts_dev, uint64_t n, void *out_dev, int elem_bytes)
+{
+    if (C < 1 || !cts_dev || (n && !out_dev)) return fail(ctx, FLASHE_EINVAL, "%s: bad arguments (C = %d)", who, C);
+    const int out_align = elem_bytes == 4 ? 4 : ctx->limbs == 2 ? 16 : 8;
+    if (reinterpret_cast<uintptr_t>(out_dev) & static_cast<uintptr_t>(out_align - 1)) return fail(ctx, FLASHE_EINVAL, "%s: out_dev must be %d-byte aligned", who, out_align);
+    if (int rc = check_operands(ctx, C, cts_dev, elem_bytes == 4 ? 4 : 8)) return rc;
+    for (int c = 0; c < C; c++)
+        if (cts_dev[c] == out_dev) return fail(ctx, FLASHE_EINVAL, "%s: out must not alias operand %d", who, c);
+    if (n == 0) return FLASHE_OK;
+    if (ctx->int_bits < 6 && std::min(C, kMaxOps) > (1 << ctx->int_bits))
+        return fail(ctx, FLASHE_ENOTSUP, "%s: %d operands in one pass exceed 2^int_bits = %d (pack, flashe_aggregate_packed_dev, unpack)", who,
+                    std::min(C, kMaxOps), 1 << ctx->int_bits);
+    int rc = ensure(ctx, ctx->summaries, packed_elems_num_blocks(n) * sizeof(uint32_t));
+    if (rc) return rc;
+    uint32_t *summ = static_cast<uint32_t *>(ctx->summaries.p);
+    const int slot_bytes = elem_bytes == 4 ? 4 : 8 * ctx->limbs;
+    std::vector<const uint64_t *> ops;
+    const uint64_t *partial = nullptr;
+    int done = 0, flip = 0;
+    while (done < C) {
+        ops.clear();
+        if (partial) ops.push_back(partial);
+        while (done < C && static_cast<int>(ops.size()) < kMaxOps) ops.push_back(static_cast<const uint64_t *>(cts_dev[done++]));
+        void *dst = out_dev;
+        if (done < C) {
+            rc = ensure(ctx, ctx->acc_tmp[flip], std::max<size_t>(static_cast<size_t>(n) * slot_bytes, 16));
+            if (rc) return rc;
+            dst = ctx->acc_tmp[flip].p;
+            flip ^= 1;
+        }
+        HIP_TRY(ctx, launch_aggregate_packed_elems(ctx->env, static_cast<int>(ops.size()), ops.data(), n, slot_bytes, dst, summ));
+        partial = static_cast<const uint64_t *>(dst);
+    }
+    return FLASHE_OK;
+}
+
+int flashe_aggregate_packed_elems_dev(flashe_ctx *ctx, int C, const uint64_t *const *cts_dev, uint64_t n, uint64_t *out_dev)
+{
+    CHECK_CTX(ctx);
+    return aggregate_packed_elems(ctx, "aggregate_packed_elems", C, reinterpret_cast<const void *const *>(cts_dev), n, out_dev, 8);
+}
+
+int flashe_aggregate_packed_elems_u32_dev(flashe_ctx *ctx, int C, const uint32_t *const *cts_dev, uint64_t n, uint32_t *out_dev)
+{
+    CHECK_CTX(ctx);
+    if (ctx->int_bits > 32) return fail(ctx, FLASHE_EINVAL, "the uint32 layout needs int_bits <= 32, this ctx has %d", ctx->int_bits);
+    return aggregate_packed_elems(ctx, "aggregate_packed_elems_u32", C, reinterpret_cast<const void *const *>(cts_dev), n, out_dev, 4);
+}
+
 int flashe_packed_probe_dev(flashe_ctx *ctx, uint64_t n_limbs, const uint64_t *x_dev, uint64_t *info_dev)
 {
     CHECK_CTX(ctx);

@@ -232,6 +232,14 @@ hipError_t launch_aggregate_packed(const LaunchEnv &env, int C, const uint64_t *
                                    uint64_t n_limbs, uint64_t total_bits, uint64_t *out_dev,
                                    uint32_t *summaries_dev);
 
+// the same sum computed on UNPACKED vectors: out = unpack(sum_c pack(ops[c]) mod 2^(n b)), element j at bit (n - 1 - j) b, with no
+// packed vector.  elem_bytes: 4 (uint32 elements, b <= 32), 8 (b <= 64) or 16 (b > 64; out 16-byte aligned, operands 8).  C <= kMaxOps
+// and C <= 2^b (hipErrorNotSupported otherwise).  summaries_dev: at least packed_elems_num_blocks(n) uint32 words.  out must NOT alias
+// an operand (lanes read their neighbours' columns).
+uint64_t packed_elems_num_blocks(uint64_t n);
+hipError_t launch_aggregate_packed_elems(const LaunchEnv &env, int C, const uint64_t *const *ops, uint64_t n, int elem_bytes, void *out_dev,
+                                         uint32_t *summaries_dev);
+
 // helpers for a packed reduce cut into limb slices across GPUs: (low limb, body-all-ones, carry limb) of a
 // slice sum, and the in-place carry-in ripple
 hipError_t launch_packed_probe(const LaunchEnv &env, uint64_t n_limbs, const uint64_t *x_dev, uint64_t *info_dev);

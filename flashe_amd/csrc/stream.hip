@@ -626,6 +626,263 @@ hipError_t launch_aggregate_packed(const LaunchEnv &env, int C, const uint64_t *
     return hipGetLastError();
 }
 
+// ---- packed aggregate in the ELEMENT domain: unpack(sum_c pack(ct_c) mod 2^(n b)) with no packed vector ----
+// Element j of n sits at bit (n - 1 - j) b of the packed integer (pack_kernel), so a carry leaves element j + 1 and enters element j.
+// With M = 2^b - 1, S_j = sum_c (ct_c[j] & M) = h_j 2^b + s_j (h_j <= C - 1) and t_j = s_j + h_{j+1} the packed sum is a ONE-BIT
+// carry chain over the elements as long as C <= 2^b: g_j = t_j > M, p_j = t_j == M, k_j = g_j | (p_j & k_{j+1}), out_j =
+// (t_j + k_{j+1}) & M.  The same two stages as the packed kernels above: lane `tid` of block B owns rank e = 256 B + tid, element
+// j = n - 1 - e (descending j, so the carry travels towards higher lanes and blocks and the ballot trick applies unchanged; a wave's
+// reversed addresses still coalesce); h of rank e - 1 comes through LDS, the first lane recomputes its neighbour's column.
+// Config 2 (n = 1e7, b = 128, C = 10): 0.317 ms = 5.6 TB/s against 0.938 ms for C packs + the packed reduce + the unpack; ten compact
+// 25,557,032-element operands at b = 20: 0.220 ms = 5.1 TB/s against 1.425 ms (profiles/r31_packed_elems_reduce.log).
+// LAYOUT 0: uint32 elements (b <= 32; one per lane: the form for vectors that are only 4-byte aligned), 1: one uint64 limb (b <= 64), 2: two limbs (b > 64; A16: every operand is 16-byte aligned).
+template <int LAYOUT> struct ElemValue { typedef u128 type; };
+template <> struct ElemValue<0> { typedef uint64_t type; };
+
+template <int LAYOUT, bool A16>
+__device__ __forceinline__ void elem_column(int C, const PtrTable &ops, uint64_t j, int b, typename ElemValue<LAYOUT>::type M,
+                                            typename ElemValue<LAYOUT>::type &s, uint32_t &h)
+{
+    const uint64_t *const *tab = ops.p;
+    if (LAYOUT == 0) {
+        uint64_t acc = 0;
+#pragma unroll 4
+        for (int c = 0; c < C; c++) acc += __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(tab[c]) + j) & static_cast<uint32_t>(M);
+        s = acc & static_cast<uint64_t>(M);
+        h = static_cast<uint32_t>(acc >> b);
+    } else if (LAYOUT == 1) {
+        u128 acc = 0;
+#pragma unroll 4
+        for (int c = 0; c < C; c++) acc += __builtin_nontemporal_load(tab[c] + j) & static_cast<uint64_t>(M);
+        s = acc & M;
+        h = static_cast<uint32_t>(acc >> b);
+    } else {
+        // the sum of up to 64 operands below 2^b needs b + 6 bits: `ov` counts the overflows of the 128-bit adds, and at
+        // 122 <= b < 128 the high part h straddles the accumulator's top bits and that count
+        u128 acc = 0;
+        uint32_t ov = 0;
+#pragma unroll 4
+        for (int c = 0; c < C; c++) {
+            u128 v;
+            if (A16) v = ld128_nt(tab[c] + 2 * j);
+            else v = (static_cast<u128>(__builtin_nontemporal_load(tab[c] + 2 * j + 1)) << 64) | __builtin_nontemporal_load(tab[c] + 2 * j);
+            v &= M;
+            acc += v;
+            ov += acc < v;
+        }
+        s = acc & M;
+        h = b == 128 ? ov : static_cast<uint32_t>(static_cast<uint64_t>(acc >> b) | (static_cast<uint64_t>(ov) << (128 - b)));
+    }
+}
+
+template <int LAYOUT, bool A16>
+__global__ __launch_bounds__(kPackedThreads) void aggregate_packed_elems_kernel(int C, const PtrTable tab, uint64_t n, int b, uint64_t mask_lo,
+                                                                                uint64_t mask_hi, void *out, uint32_t *summaries)
+{
+    typedef typename ElemValue<LAYOUT>::type V;
+    __shared__ uint32_t sh_h[kPackedThreads];
+    __shared__ uint32_t sh_wg[kPackedThreads / 64], sh_wp[kPackedThreads / 64];
+    const V M = LAYOUT == 0 ? static_cast<V>(mask_lo) : static_cast<V>((static_cast<u128>(mask_hi) << 64) | mask_lo);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint64_t e = static_cast<uint64_t>(blockIdx.x) * kPackedThreads + tid;
+    const bool live = e < n;
+    const uint64_t j = n - 1 - e;                   // (only used when live)
+
+    V s = 0;
+    uint32_t h = 0;
+    if (live) elem_column<LAYOUT, A16>(C, tab, j, b, M, s, h);
+    sh_h[tid] = h;
+    __syncthreads();
+    uint32_t h_in = 0;                              // h_{j+1}; h_n = 0
+    if (tid > 0) h_in = sh_h[tid - 1];
+    else if (e > 0 && live) { V ps; elem_column<LAYOUT, A16>(C, tab, j + 1, b, M, ps, h_in); }
+    const V t = s + h_in;                           // <= 2 M: wraps only in the two-limb layout at b = 128
+    const uint32_t g = live ? ((t < s) | (t > M)) : 0u;
+    const V tm = t & M;
+    const uint32_t p = live ? (tm == M) : 1u;       // dead lanes are transparent; g and p exclude each other (t - M - 1 < M)
+    const uint64_t Gm = __ballot(g), Pm = __ballot(p);
+    const uint64_t a = Gm | Pm, bb = Gm;
+    const uint64_t sum0 = a + bb;
+    if (lane == 0) { sh_wg[wave] = sum0 < a; sh_wp[wave] = Pm == ~0ull; }
+    __syncthreads();
+    uint32_t cin = 0;
+    for (int v = 0; v < wave; v++) cin = sh_wg[v] | (sh_wp[v] & cin);
+    const uint64_t cv = (a + bb + cin) ^ Pm;
+    const V r = (tm + static_cast<V>((cv >> lane) & 1u)) & M;
+    if (live) {
+        if (LAYOUT == 0) static_cast<uint32_t *>(out)[j] = static_cast<uint32_t>(r);
+        else if (LAYOUT == 1) static_cast<uint64_t *>(out)[j] = static_cast<uint64_t>(r);
+        else st128(static_cast<uint64_t *>(out) + 2 * j, r);
+    }
+    if (tid == 0) {
+        uint32_t c = 0, pall = 1;
+        for (int v = 0; v < kPackedThreads / 64; v++) { c = sh_wg[v] | (sh_wp[v] & c); pall &= sh_wp[v]; }
+        summaries[blockIdx.x] = c | (pall << 1);
+    }
+}
+
+// The compact layout with every pointer 16-byte aligned: FOUR elements per lane in 16-byte accesses.  The vector is thought padded with
+// zeros below element n - 1 up to n4 = a multiple of four elements (zeros under the least significant element carry nothing), so that
+// a lane's group -- elements [4 m, 4 m + 4), group rank q = n4 / 4 - 1 - m -- is aligned in memory; only the group that holds element
+// n - 1 can be partial.  Inside the lane the carry runs from element 4 m + 3 to 4 m; the lane's (G, P) is the composition of its four.
+__device__ __forceinline__ void elem_column_u32x4(int C, const PtrTable &ops, uint64_t m, uint64_t n, uint32_t M, uint64_t (&a)[4])
+{
+    const uint64_t *const *tab = ops.p;
+    a[0] = a[1] = a[2] = a[3] = 0;
+    if (4 * m + 3 < n) {
+#pragma unroll 4
+        for (int c = 0; c < C; c++) {
+            const u64x2 v = __builtin_nontemporal_load(reinterpret_cast<const u64x2 *>(tab[c]) + m);
+            a[0] += static_cast<uint32_t>(v[0]) & M; a[1] += static_cast<uint32_t>(v[0] >> 32) & M;
+            a[2] += static_cast<uint32_t>(v[1]) & M; a[3] += static_cast<uint32_t>(v[1] >> 32) & M;
+        }
+    } else {
+        for (int c = 0; c < C; c++)
+            for (int i = 0; i < 4; i++)
+                if (4 * m + i < n) a[i] += reinterpret_cast<const uint32_t *>(tab[c])[4 * m + i] & M;
+    }
+}
+
+__global__ __launch_bounds__(kPackedThreads) void aggregate_packed_elems_u32x4_kernel(int C, const PtrTable tab, uint64_t n, int b, uint32_t M,
+                                                                                      uint32_t *out, uint32_t *summaries)
+{
+    __shared__ uint32_t sh_h[kPackedThreads];
+    __shared__ uint32_t sh_wg[kPackedThreads / 64], sh_wp[kPackedThreads / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint64_t groups = (n + 3) / 4;
+    const uint64_t q = static_cast<uint64_t>(blockIdx.x) * kPackedThreads + tid;
+    const bool live = q < groups;
+    const uint64_t m = groups - 1 - q;              // (only used when live)
+
+    uint64_t a[4] = {0, 0, 0, 0};
+    if (live) elem_column_u32x4(C, tab, m, n, M, a);
+    sh_h[tid] = static_cast<uint32_t>(a[0] >> b);
+    __syncthreads();
+    uint32_t h_in = 0;                              // h of element 4 m + 4, the next group's first; 0 under element n - 1
+    if (tid > 0) h_in = sh_h[tid - 1];
+    else if (q > 0 && live) {
+        uint64_t acc = 0;
+        for (int c = 0; c < C; c++) acc += reinterpret_cast<const uint32_t *>(tab.p[c])[4 * (m + 1)] & M;
+        h_in = static_cast<uint32_t>(acc >> b);
+    }
+    uint32_t g[4], p[4], tm[4];
+#pragma unroll
+    for (int i = 3; i >= 0; i--) {
+        const uint64_t t = (a[i] & M) + (i == 3 ? h_in : static_cast<uint32_t>(a[i + 1] >> b));
+        g[i] = t > M; tm[i] = static_cast<uint32_t>(t) & M; p[i] = tm[i] == M;
+    }
+    const uint32_t Gt = live ? (g[0] | (p[0] & (g[1] | (p[1] & (g[2] | (p[2] & g[3])))))) : 0u;
+    const uint32_t Pt = live ? (p[0] & p[1] & p[2] & p[3]) : 1u;
+    const uint64_t Gm = __ballot(Gt), Pm = __ballot(Pt);
+    const uint64_t aa = Gm | Pm, bb = Gm;
+    const uint64_t sum0 = aa + bb;
+    if (lane == 0) { sh_wg[wave] = sum0 < aa; sh_wp[wave] = Pm == ~0ull; }
+    __syncthreads();
+    uint32_t cin = 0;
+    for (int v = 0; v < wave; v++) cin = sh_wg[v] | (sh_wp[v] & cin);
+    const uint64_t cv = (aa + bb + cin) ^ Pm;
+    uint32_t k = static_cast<uint32_t>(cv >> lane) & 1u, r[4];
+#pragma unroll
+    for (int i = 3; i >= 0; i--) { r[i] = (tm[i] + k) & M; k = g[i] | (p[i] & k); }
+    if (live) {
+        if (4 * m + 3 < n) {
+            u64x2 w;
+            w[0] = r[0] | (static_cast<uint64_t>(r[1]) << 32); w[1] = r[2] | (static_cast<uint64_t>(r[3]) << 32);
+            *(reinterpret_cast<u64x2 *>(out) + m) = w;
+        } else {
+            for (int i = 0; i < 4; i++)
+                if (4 * m + i < n) out[4 * m + i] = r[i];
+        }
+    }
+    if (tid == 0) {
+        uint32_t c = 0, pall = 1;
+        for (int v = 0; v < kPackedThreads / 64; v++) { c = sh_wg[v] | (sh_wp[v] & c); pall &= sh_wp[v]; }
+        summaries[blockIdx.x] = c | (pall << 1);
+    }
+}
+
+// Stage 2: block B's carry-in by look-back over the summaries of the blocks below it; the rare +1 ripples through the elements equal to
+// M (they become 0) and stops at the first that is not -- inside the block, whose own P says whether the carry leaves it.
+// (tile: ranks per stage-1 block; n: the length rank 0 is counted from -- the vector kernel's padded length)
+template <int LAYOUT>
+__global__ void packed_elems_fixup_kernel(uint64_t n_blocks, uint64_t n, uint64_t tile, uint64_t mask_lo, uint64_t mask_hi, const uint32_t *summaries,
+                                          void *out)
+{
+    const uint64_t B = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x + 1;
+    if (B >= n_blocks) return;
+    uint32_t cin = 0;
+    for (uint64_t v = B; v-- > 0;) {
+        const uint32_t s = summaries[v];
+        if (s & 1u) { cin = 1; break; }
+        if (!(s & 2u)) break;
+    }
+    if (!cin) return;
+    const uint64_t first = B * tile;
+    uint64_t last = first + tile;
+    if (last > n) last = n;
+    for (uint64_t e = first; e < last; e++) {
+        const uint64_t j = n - 1 - e;
+        bool zero;
+        if (LAYOUT == 0) {
+            uint32_t *q = static_cast<uint32_t *>(out) + j;
+            const uint32_t v = (*q + 1u) & static_cast<uint32_t>(mask_lo);
+            *q = v; zero = v == 0;
+        } else if (LAYOUT == 1) {
+            uint64_t *q = static_cast<uint64_t *>(out) + j;
+            const uint64_t v = (*q + 1u) & mask_lo;
+            *q = v; zero = v == 0;
+        } else {
+            uint64_t *q = static_cast<uint64_t *>(out) + 2 * j;
+            const u128 v = (((static_cast<u128>(q[1]) << 64) | q[0]) + 1u) & ((static_cast<u128>(mask_hi) << 64) | mask_lo);
+            st128(q, v); zero = v == 0;
+        }
+        if (!zero) break;
+    }
+}
+
+uint64_t packed_elems_num_blocks(uint64_t n) { return (n + kPackedThreads - 1) / kPackedThreads; }
+
+hipError_t launch_aggregate_packed_elems(const LaunchEnv &env, int C, const uint64_t *const *ops, uint64_t n, int elem_bytes, void *out_dev,
+                                         uint32_t *summaries_dev)
+{
+    if (n == 0) return hipSuccess;
+    if (C < 1 || C > kMaxOps || (elem_bytes == 4 ? env.b > 32 : elem_bytes != (env.b > 64 ? 16 : 8))) return hipErrorInvalidValue;
+    if (env.b < 6 && C > (1 << env.b)) return hipErrorNotSupported;       // the carry between elements would need more than one bit
+    const PtrTable tab_dev = make_table(C, ops);
+    uint64_t lo, hi;
+    masks_of(env.b, &lo, &hi);
+    const uint64_t nb = packed_elems_num_blocks(n);
+    if (nb > 0x7fffffffull) return hipErrorInvalidValue;
+    const dim3 grid(static_cast<unsigned>(nb)), block(kPackedThreads), fgrid(static_cast<unsigned>((nb - 1 + 255) / 256));
+    const uint64_t tile = kPackedThreads;
+    if (elem_bytes == 4) {
+        bool a16 = (reinterpret_cast<uintptr_t>(out_dev) & 15u) == 0;
+        for (int c = 0; c < C; c++) a16 = a16 && (reinterpret_cast<uintptr_t>(ops[c]) & 15u) == 0;
+        if (a16) {
+            // four elements per lane: blocks of 4 x kPackedThreads ranks counted from the padded length
+            const uint64_t n4 = (n + 3) / 4 * 4, nb4 = (n4 / 4 + kPackedThreads - 1) / kPackedThreads;
+            hipLaunchKernelGGL(aggregate_packed_elems_u32x4_kernel, dim3(static_cast<unsigned>(nb4)), block, 0, env.stream, C, tab_dev, n, env.b,
+                               static_cast<uint32_t>(lo), static_cast<uint32_t *>(out_dev), summaries_dev);
+            if (nb4 > 1)
+                hipLaunchKernelGGL(packed_elems_fixup_kernel<0>, dim3(static_cast<unsigned>((nb4 - 1 + 255) / 256)), dim3(256), 0, env.stream, nb4, n4,
+                                   4 * tile, lo, hi, summaries_dev, out_dev);
+            return hipGetLastError();
+        }
+        hipLaunchKernelGGL((aggregate_packed_elems_kernel<0, false>), grid, block, 0, env.stream, C, tab_dev, n, env.b, lo, hi, out_dev, summaries_dev);
+        if (nb > 1) hipLaunchKernelGGL(packed_elems_fixup_kernel<0>, fgrid, dim3(256), 0, env.stream, nb, n, tile, lo, hi, summaries_dev, out_dev);
+    } else if (elem_bytes == 8) {
+        hipLaunchKernelGGL((aggregate_packed_elems_kernel<1, false>), grid, block, 0, env.stream, C, tab_dev, n, env.b, lo, hi, out_dev, summaries_dev);
+        if (nb > 1) hipLaunchKernelGGL(packed_elems_fixup_kernel<1>, fgrid, dim3(256), 0, env.stream, nb, n, tile, lo, hi, summaries_dev, out_dev);
+    } else {
+        bool a16 = true;
+        for (int c = 0; c < C; c++) a16 = a16 && (reinterpret_cast<uintptr_t>(ops[c]) & 15u) == 0;
+        if (a16) hipLaunchKernelGGL((aggregate_packed_elems_kernel<2, true>), grid, block, 0, env.stream, C, tab_dev, n, env.b, lo, hi, out_dev, summaries_dev);
+        else hipLaunchKernelGGL((aggregate_packed_elems_kernel<2, false>), grid, block, 0, env.stream, C, tab_dev, n, env.b, lo, hi, out_dev, summaries_dev);
+        if (nb > 1) hipLaunchKernelGGL(packed_elems_fixup_kernel<2>, fgrid, dim3(256), 0, env.stream, nb, n, tile, lo, hi, summaries_dev, out_dev);
+    }
+    return hipGetLastError();
+}
+
 // ---- slice helpers for a packed reduce that is cut across GPUs (flashe_amd/dist.py run_packed) ----
 // probe: x holds a slice sum as n_limbs - 1 body limbs plus one carry limb on top.
 // info[0] = x[0], info[1] = 1 iff body limbs [1, n_limbs - 1) are all ~0, info[2] = x[n_limbs - 1].

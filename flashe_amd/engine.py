@@ -1234,6 +1234,18 @@ class Engine:
         p, _keep = self._ptr_array(packed)
         self._check(self._lib.flashe_aggregate_packed_dev(self._h, len(packed), p, n_limbs, total_bits, self._ptr(out)))
 
+    def aggregate_packed_elems_dev(self, cts, n, out):
+        """out = unpack(sum of pack(ct) mod 2^(int_bits n)) of n-element ciphertext vectors in the engine's layout, in one pass with no
+        packed vector; out must not be an operand.  False -- nothing was launched -- when the library declines (FLASHE_ENOTSUP: more
+        operands in a pass than 2^int_bits), True otherwise."""
+        p, _keep = self._ptr_array(cts)
+        return self._took(self._lib.flashe_aggregate_packed_elems_dev(self._h, len(cts), p, n, self._ptr(out)))
+
+    def aggregate_packed_elems_u32_dev(self, cts, n, out):
+        """aggregate_packed_elems_dev on uint32 vectors (the compact layout, int_bits <= 32)."""
+        p, _keep = self._ptr_array(cts)
+        return self._took(self._lib.flashe_aggregate_packed_elems_u32_dev(self._h, len(cts), p, n, self._ptr(out)))
+
     def packed_probe_dev(self, n_limbs, x, info):
         """info (device, 3 words) <- (x[0], body limbs [1, n_limbs-1) all ones, x[n_limbs-1]); asynchronous."""
         self._check(self._lib.flashe_packed_probe_dev(self._h, n_limbs, self._ptr(x), self._ptr(info)))

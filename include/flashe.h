@@ -87,7 +87,9 @@ typedef struct flashe_ctx flashe_ctx;
  *      in the stage pass, the two divisions and the last round's model in the store + statistics pass);
  *      flashe_encrypt_batch_sum_decrypt_dev (a co-located round's encrypts, their sum and the decrypt of the sum: one launch at
  *      int_bits 128); flashe_cohort_cut_parts + flashe_quantize_encrypt_cohort_cut_dev / flashe_quantize_encrypt_cohort_cut_u32_dev (a
- *      cohort whose vector does not fill the chip uncut: the summed chain cut into runs of clients and one combine pass) */
+ *      cohort whose vector does not fill the chip uncut: the summed chain cut into runs of clients and one combine pass);
+ *      flashe_aggregate_packed_elems_dev / flashe_aggregate_packed_elems_u32_dev (the arbiter's packed reduce computed on unpacked
+ *      ciphertext vectors in one pass) */
 #define FLASHE_ABI_VERSION 4
 int flashe_abi_version(void);
 int flashe_device_count(int *count);
@@ -441,6 +443,20 @@ int flashe_aggregate_packed_dev(flashe_ctx *ctx, int C, const uint64_t *const *p
                                 uint64_t n_limbs, uint64_t total_bits, uint64_t *out_dev);
 int flashe_aggregate_packed(flashe_ctx *ctx, int C, const uint64_t *const *packed,
                             uint64_t n_limbs, uint64_t total_bits, uint64_t *out);
+/* new: the same sum (jzf_aggregator.py:406-419) computed on UNPACKED vectors, out = unpack(sum_c pack(cts[c]) mod 2^(int_bits n)) with
+ * element j at bit (n - 1 - j) int_bits, in one pass and with no packed vector: the column sums' high parts and a one-bit carry run
+ * from element n - 1 towards element 0 as a scan over the elements; what leaves element 0 is dropped.  Bits of an operand above int_bits
+ * are ignored, as flashe_pack_dev ignores them.  Operands and out are laid out and aligned as for flashe_aggregate_elem_dev (the _u32
+ * form: as for flashe_aggregate_elem_u32_dev, int_bits <= 32), but out must NOT be one of the operands (FLASHE_EINVAL).  n = 0 is
+ * FLASHE_OK with nothing launched.  More than 64 operands go in passes whose partial results ping-pong through ctx scratch.  The carry
+ * is one bit only while the operands of a pass number at most 2^int_bits: beyond that (int_bits < 6) FLASHE_ENOTSUP -- nothing launched,
+ * out untouched; pack, flashe_aggregate_packed_dev and unpack instead.  The first call on a ctx sizes its block summaries, so it cannot
+ * be inside a graph capture.  Measured by device events against C flashe_pack_dev + flashe_aggregate_packed_dev + flashe_unpack_dev on the
+ * same operands (tests/perf/packed_elems_reduce.py, profiles/r31_packed_elems_reduce.log): n = 1e7, int_bits 128, C = 10: 0.317 against
+ * 0.938 ms; n = 25,557,032, int_bits 20, C = 10, uint32 operands (every pointer 16-byte aligned: four elements per lane): 0.220 against
+ * 1.425 ms with the widens that sequence needs.  Other shapes: not measured. */
+int flashe_aggregate_packed_elems_dev(flashe_ctx *ctx, int C, const uint64_t *const *cts_dev, uint64_t n, uint64_t *out_dev);
+int flashe_aggregate_packed_elems_u32_dev(flashe_ctx *ctx, int C, const uint32_t *const *cts_dev, uint64_t n, uint32_t *out_dev);
 
 /* Slice helpers (new; no reference counterpart): the packed reduce above cut into limb slices
  * over several GPUs ("packed variant") needs each slice's carry-out and
