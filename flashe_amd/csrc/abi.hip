@@ -146,6 +146,14 @@ int ensure(flashe_ctx *ctx, flashe_ctx::Buf &b, size_t bytes)
     return FLASHE_OK;
 }
 
+// The synchronous entry points (they wait for the ctx stream, or copy to or from host memory on it) inside a capture: refused
+// before they touch the stream -- a hipStreamSynchronize on a capturing stream invalidates the capture with an opaque HIP error.
+int refuse_in_capture(flashe_ctx *ctx, const char *what)
+{
+    if (!ctx->capturing) return FLASHE_OK;
+    return fail(ctx, FLASHE_EINVAL, "%s is synchronous: not capturable (call it before flashe_graph_begin or after flashe_graph_end)", what);
+}
+
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 bool ct_aligned(const flashe_ctx *ctx, const void *p) { return (reinterpret_cast<uintptr_t>(p) & (ctx->limbs == 2 ? 15u : 7u)) == 0; }
@@ -471,6 +479,7 @@ int flashe_ctx_destroy(flashe_ctx *ctx)
 int flashe_ctx_set_key(flashe_ctx *ctx, const uint8_t key[32])
 {
     if (!ctx || !key) return FLASHE_EINVAL;
+    if (int rc = refuse_in_capture(ctx, "flashe_ctx_set_key")) return rc;      // (the kernels captured so far carry the old schedule)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->env.stream));
     wipe(&ctx->env.rk, sizeof(ctx->env.rk));
@@ -521,6 +530,7 @@ const char *flashe_last_error(const flashe_ctx *ctx) { return ctx ? ctx->err.c_s
 int flashe_selftest(flashe_ctx *ctx)
 {
     CHECK_CTX(ctx);
+    if (int rc = refuse_in_capture(ctx, "flashe_selftest")) return rc;
     // FIPS-197 C.3 uses its own key; test with the ctx key against the host implementation
     // and with the FIPS key through a temporary key schedule.
     static const uint8_t fips_key[32] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15,
@@ -632,6 +642,7 @@ int flashe_dev_free(flashe_ctx *ctx, void *dptr)
     CHECK_CTX(ctx);
     if (!dptr) return FLASHE_OK;
     flashe_pool::DeviceCache *cache = dev_cache(ctx->device);
+    if (!cache) if (int rc = refuse_in_capture(ctx, "flashe_dev_free without the block cache")) return rc;
     if (!cache) { HIP_TRY(ctx, hipStreamSynchronize(ctx->env.stream)); HIP_TRY(ctx, hipFree(dptr)); return FLASHE_OK; }
     // parked, not freed: the block is handed out again only after a device-wide synchronisation (blockpool.h), which is the
     // guarantee hipFree gave -- kernels of any stream that still read it finish first
@@ -675,12 +686,14 @@ int flashe_host_free(void *hptr)
 int flashe_memcpy_h2d(flashe_ctx *ctx, void *dst, const void *src, size_t bytes)
 {
     CHECK_CTX(ctx);
+    if (int rc = refuse_in_capture(ctx, "flashe_memcpy_h2d")) return rc;
     if (bytes) { HIP_TRY(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->env.stream)); HIP_TRY(ctx, hipStreamSynchronize(ctx->env.stream)); }
     return FLASHE_OK;
 }
 int flashe_memcpy_d2h(flashe_ctx *ctx, void *dst, const void *src, size_t bytes)
 {
     CHECK_CTX(ctx);
+    if (int rc = refuse_in_capture(ctx, "flashe_memcpy_d2h")) return rc;
     if (bytes) { HIP_TRY(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->env.stream)); HIP_TRY(ctx, hipStreamSynchronize(ctx->env.stream)); }
     return check_device_flag(ctx);
 }
@@ -699,6 +712,7 @@ int flashe_memset_dev(flashe_ctx *ctx, void *dst, int byte, size_t bytes)
 int flashe_sync(flashe_ctx *ctx)
 {
     CHECK_CTX(ctx);
+    if (int rc = refuse_in_capture(ctx, "flashe_sync")) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->env.stream));
     return check_device_flag(ctx);
 }
@@ -1192,6 +1206,7 @@ int flashe_mean_std_dev(flashe_ctx *ctx, uint64_t n, const void *x_dev, int x_is
     CHECK_CTX(ctx);
     if (!mean || !stddev || (n && !x_dev)) return fail(ctx, FLASHE_EINVAL, "null argument");
     if (n == 0) return fail(ctx, FLASHE_EINVAL, "mean of an empty vector");
+    if (int rc = refuse_in_capture(ctx, "flashe_mean_std_dev")) return rc;     // (it reads its partial sums back to the host twice)
     const int grid = moments_grid(ctx->env, n);
     int rc = ensure(ctx, ctx->sp_ws, static_cast<size_t>(grid) * sizeof(double));
     if (rc) return rc;
@@ -2265,9 +2280,10 @@ int flashe_sparse_dense_mask_dev(flashe_ctx *ctx, uint32_t iter, int n_lists, co
     CHECK_CTX(ctx);
     if (n_lists < 0 || (n_lists && !sel_dev) || (total && !out_dev)) return fail(ctx, FLASHE_EINVAL, "bad arguments");
     if (int rc = check_wide_aligned(ctx, {out_dev})) return rc;
-    if (total) HIP_TRY(ctx, hipMemsetAsync(out_dev, 0, vec_bytes(ctx, total), ctx->env.stream));
+    // (the scratch first: a call refused because it would grow inside a capture has recorded nothing, not even the clearing of out)
     int rc = ensure(ctx, ctx->stream_tmp, vec_bytes(ctx, total));
     if (rc) return rc;
+    if (total) HIP_TRY(ctx, hipMemsetAsync(out_dev, 0, vec_bytes(ctx, total), ctx->env.stream));
     uint64_t *tmp = static_cast<uint64_t *>(ctx->stream_tmp.p);
     for (int i = 0; i < n_lists; i++) {
         const uint32_t idx = static_cast<uint32_t>(i);
@@ -2283,6 +2299,7 @@ int flashe_sparse_dense_mask_dev(flashe_ctx *ctx, uint32_t iter, int n_lists, co
 int flashe_tune_span_prf_cycles(flashe_ctx *ctx, unsigned long long *out8, int reset)
 {
     CHECK_CTX(ctx);
+    if (int rc = refuse_in_capture(ctx, "flashe_tune_span_prf_cycles")) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->env.stream));
     HIP_TRY(ctx, flashe::span_prf_cycles(out8, reset != 0));
     return FLASHE_OK;

@@ -239,6 +239,7 @@ int flashe_rccl_allreduce_f64(flashe_ctx *ctx, flashe_comm *comm, double *value,
 {
     CHECK_CTX(ctx);
     if (!comm || !value || op < 0 || op > 2) return fail(ctx, FLASHE_EINVAL, "flashe_rccl_allreduce_f64: bad arguments");
+    if (int rc = flashe_host::refuse_in_capture(ctx, "flashe_rccl_allreduce_f64")) return rc;
     if (comm->world == 1) { HIP_TRY(ctx, hipStreamSynchronize(ctx->env.stream)); return FLASHE_OK; }
     HIP_TRY(ctx, hipMemcpyAsync(comm->scratch_dev, value, sizeof(double), hipMemcpyHostToDevice, ctx->env.stream));
     const ncclRedOp_t rop = op == 0 ? ncclMax : op == 1 ? ncclMin : ncclSum;

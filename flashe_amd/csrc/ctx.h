@@ -68,6 +68,9 @@ inline size_t vec_bytes(const flashe_ctx *ctx, uint64_t n) { return static_cast<
 
 // b holds at least `bytes` (grown on demand; FLASHE_EINVAL while a graph is being captured)
 int ensure(flashe_ctx *ctx, flashe_ctx::Buf &b, size_t bytes);
+// FLASHE_OK outside a capture; inside one, FLASHE_EINVAL naming `what`: the first check of every entry point that waits for the ctx
+// stream or copies to or from host memory on it
+int refuse_in_capture(flashe_ctx *ctx, const char *what);
 bool aligned16(const void *p);
 bool ct_aligned(const flashe_ctx *ctx, const void *p);   // aligned like a ciphertext vector: 16 bytes for 2-limb elements, else 8
 

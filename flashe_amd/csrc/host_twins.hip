@@ -100,6 +100,7 @@ bool pipe_wanted(const flashe_ctx *ctx, uint64_t n, const void *out_host)
 template <class Chunk>
 int staged_chunks(flashe_ctx *ctx, uint64_t n, const std::vector<Operand> &ops, Chunk &&chunk)
 {
+    if (int rc = flashe_host::refuse_in_capture(ctx, "a host-pointer call (it copies from and to host memory and waits)")) return rc;
     std::vector<Tmp> blocks(ops.size());
     for (size_t i = 0; i < ops.size(); i++)
         if (!ops[i].absent) HIP_TRY(ctx, blocks[i].alloc(ctx, ops[i].bytes));

@@ -181,6 +181,11 @@ int flashe_event_query(flashe_ctx *ctx, void *event, int *done);
  * LeNet-sized model (six kernels of 10-60 us).  Pointers and scalar arguments are frozen into the graph: replay
  * with new DATA in the same buffers.  Host-pointer twins, syncs and event timing are not capturable, and
  * ctx-owned scratch must already have its size: run the sequence once normally before capturing it.
+ * The synchronous calls return FLASHE_EINVAL between begin and end, before they touch the stream (the capture stays intact and can
+ * still end): flashe_sync, flashe_memcpy_h2d, flashe_memcpy_d2h, flashe_mean_std_dev, flashe_selftest, flashe_ctx_set_key, every
+ * host-pointer twin (flashe_mask, flashe_encrypt, ...), flashe_dynamic_masking_cost_dev, flashe_rccl_allreduce_f64 and
+ * flashe_rccl_barrier; so does a call whose ctx scratch would have to grow -- it has recorded nothing.  flashe_prepared_discard marks
+ * its cache invalid and frees nothing there.
  * What a frozen argument block means for the cipher:
  *   - `iter` is frozen, so flashe_graph_launch REPEATS the captured round's mask streams: never feed it new plaintexts
  *     (ct1 - ct2 would equal pt1 - pt2).  For the NEXT rounds use flashe_graph_launch_shifted: every PRF kernel adds a
