@@ -25,7 +25,9 @@ which this example checks.
                FlasheCohort(cut=True) cuts the chain into runs of consecutive clients and adds the runs' partial sums and decrypt masks
                in one combine pass (`upload.path` is "cut-chain"): two launches instead of forty quantise passes, forty plaintext
                vectors and a batch encrypt; with --compact at --bits 16 / 20 / 23 / 24 / 32 the same in the uint32 layout.  Without
-               --cut such a cohort runs "staged-chain"
+               --cut such a cohort runs "staged-chain".  With --drop 2,7 (a gap in the cipher indices is a cut the round imposes) or
+               with --bits 120 --batch (five 22-bit fields per element) the example asks for FlasheCohort(cut="any"), which takes
+               gapped and batched short cohorts through the cut launch too and keeps the decrypt mask of the telescoped lists
   --rng philox the stochastic-rounding draws come from one np.random.Generator per client instead of NumPy's global stream
                (quantize_encrypt(rng=[...])): counter-based Philox generators, whose draws for the whole cohort are ONE asynchronous
                launch on the device (models of 65,536 values or more: this example's hold 8,036,426) and whose advanced states come back
@@ -108,7 +110,8 @@ def main():
         bitgen = np.random.Philox if opt.rng == "philox" else np.random.SFC64
         return [np.random.Generator(bitgen(1000 + c)) for c in present]
 
-    cohort = FlasheCohort(args, first_idx=0, n_local=C, num_clients=C, prp_seed=key, compact=opt.compact, cut=opt.cut)
+    cohort = FlasheCohort(args, first_idx=0, n_local=C, num_clients=C, prp_seed=key, compact=opt.compact,
+                          cut="any" if opt.cut and (dropped or opt.batch) else opt.cut)
     if opt.precompute:
         cohort.set_iter_index(it - 1)
         cohort.prepare_encrypt()                             # in idle time, one round ahead: the masks of iteration `it`
@@ -159,9 +162,10 @@ def main():
     if dropped:
         print(f"new global model equals {len(present)} FlasheClient steps and their dropout-aware decrypt bit for bit")
         return
-    mean = sum(l["5.bias"].double() for l in layers) / C
-    print("new global model equals ten FlasheClient steps bit for bit; |5.bias - mean of the clients'| <=",
-          float((new_global["5.bias"].double() - mean).abs().max()))
+    last = list(layers[0])[-1]                               # the last layer's bias ("5.bias"; "11.bias" of the small model)
+    mean = sum(l[last].double() for l in layers) / C
+    print(f"new global model equals {C} FlasheClient steps bit for bit; |{last} - mean of the clients'| <=",
+          float((new_global[last].double() - mean).abs().max()))
 
 
 if __name__ == "__main__":

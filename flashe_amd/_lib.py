@@ -249,6 +249,16 @@ _SIGNATURES = {
     "flashe_quantize_batch_encrypt_cohort_runs_dev": (c_int, [c_vp, c_u32, ctypes.POINTER(c_u32), c_int, c_u64, c_u64, c_u32, ctypes.POINTER(TensorLayer),
                                                               c_int, ctypes.POINTER(c_vp), ctypes.POINTER(ctypes.c_int32), c_int, c_int, c_vp,
                                                               ctypes.POINTER(c_vp), c_vp, c_vp]),
+    "flashe_cohort_cut_pieces": (c_int, [c_vp, ctypes.POINTER(c_u32), c_int, c_u64, c_u32, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "flashe_quantize_encrypt_cohort_cut_runs_dev": (c_int, [c_vp, c_u32, ctypes.POINTER(c_u32), c_int, c_u64, c_u32, ctypes.POINTER(TensorLayer), c_int,
+                                                            ctypes.POINTER(c_vp), ctypes.POINTER(ctypes.c_int32), c_int, c_vp, ctypes.POINTER(c_vp), c_vp, c_vp,
+                                                            c_vp]),
+    "flashe_quantize_encrypt_cohort_cut_runs_u32_dev": (c_int, [c_vp, c_u32, ctypes.POINTER(c_u32), c_int, c_u64, c_u32, ctypes.POINTER(TensorLayer), c_int,
+                                                                ctypes.POINTER(c_vp), ctypes.POINTER(ctypes.c_int32), c_int, c_vp, ctypes.POINTER(c_vp), c_vp,
+                                                                c_vp]),
+    "flashe_quantize_batch_encrypt_cohort_cut_runs_dev": (c_int, [c_vp, c_u32, ctypes.POINTER(c_u32), c_int, c_u64, c_u64, c_u32,
+                                                                  ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp), ctypes.POINTER(ctypes.c_int32),
+                                                                  c_int, c_int, c_vp, ctypes.POINTER(c_vp), c_vp, c_vp, c_vp]),
     "flashe_cohort_masks_u32_dev": (c_int, [c_vp, c_u32, c_u32, c_int, c_u64, c_u32, ctypes.POINTER(c_vp)]),
     "flashe_quantize_combine_cohort_dev": (c_int, [c_vp, c_int, c_u64, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp),
                                                    ctypes.POINTER(ctypes.c_int32), c_int, c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),

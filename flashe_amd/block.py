@@ -1218,12 +1218,13 @@ def compact_cohort_admission_length(cu_count, int_bits, n_jobs):
 _CUT_MAX_PARTS, _CUT_MIN_OUTPUTS = 16, 4           # kCutMaxParts, kCutMinOutputs (csrc/cohort_cut.h)
 
 
-def cohort_cut_items(n, int_bits, n_jobs, compact=False):
+def cohort_cut_items(n, int_bits, n_jobs, compact=False, n_elems=None):
     """The items of one uncut chain over an n-element vector (csrc/cohort_cut.h): half tiles of 128 elements in the wide layout, tiles of
-    128 AES blocks in the compact one -- two AES blocks per lane and stream either way."""
+    128 AES blocks in the compact one -- two AES blocks per lane and stream either way.  n_elems (a BATCHED job, wide layout): the chain
+    runs over the model's batched elements, 2 * ceil(n_elems / 256) half tiles."""
     if compact:
         return (compact_cohort_blocks(n, int_bits, n_jobs) + 127) // 128
-    return 2 * ((int(n) + 255) // 256)
+    return 2 * ((int(n if n_elems is None else n_elems) + 255) // 256)
 
 
 def cohort_cut_parts(n_clients, items, cu_count):
@@ -1238,8 +1239,36 @@ def cohort_cut_parts(n_clients, items, cu_count):
     return max(1, min(16 * cus // items, max(1, C // _CUT_MIN_OUTPUTS), _CUT_MAX_PARTS))
 
 
+def cohort_cut_pieces(idxs, items, cu_count):
+    """The mirror of cohort_cut_pieces in csrc/cohort_cut.h (tests/test_cohort_cut_pieces_host.py holds the two against each other): the
+    pieces of a cohort given by ANY strictly ascending cipher indices -- every gap is a cut the round imposes.  Every run of consecutive
+    indices starts as one piece; while the pieces number fewer than max(runs, cohort_cut_parts(...)) the run with the most clients per
+    piece takes one more (the lower run on a tie), as long as its pieces keep four clients; inside a run the pieces are even.
+    Returns begins: the position in idxs of every piece's first client and len(idxs) at the end (len(begins) - 1 pieces); [] where the
+    cut launch declines -- cohort_cut_parts' cases, more than 16 runs, indices that are not strictly ascending or hold 2^32 - 1."""
+    idxs = [int(i) for i in idxs]
+    C = len(idxs)
+    rule = cohort_cut_parts(C, items, cu_count)
+    if not rule or any(i < 0 or i >= 2 ** 32 - 1 for i in idxs) or any(b <= a for a, b in zip(idxs, idxs[1:])):
+        return []
+    start = [0] + [v for v in range(1, C) if idxs[v] != idxs[v - 1] + 1] + [C]
+    runs = len(start) - 1
+    if runs > _CUT_MAX_PARTS:
+        return []
+    lens, k = [start[r + 1] - start[r] for r in range(runs)], [1] * runs
+    for _ in range(runs, max(rule, runs)):
+        best = -1
+        for r in range(runs):
+            if lens[r] // (k[r] + 1) >= _CUT_MIN_OUTPUTS and (best < 0 or lens[r] * k[best] > lens[best] * k[r]):
+                best = r
+        if best < 0:
+            break
+        k[best] += 1
+    return [start[r] + lens[r] * q // k[r] for r in range(runs) for q in range(k[r])] + [C]
+
+
 def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, mask="double", num_clients=None, precompute=False, chain=True,
-                location_masks=False, compact=False, n_jobs=None, cohort_masks=False, present=None, compact_runs=False, cut=False):
+                location_masks=False, compact=False, n_jobs=None, cohort_masks=False, present=None, compact_runs=False, cut=False, cut_any=False):
     """The engine-free part of FlasheCohort.quantize_encrypt: checks that the clients' Weights describe one model (the same layer names
     in the same walking order with the same shapes: ValueError naming the client and the layer otherwise; a sparse upload -- a 'zzz'
     layer or location masks -- is a TypeError), lays out the shared layer table and the client-major draws, and picks the path:
@@ -1277,6 +1306,12 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
                       whatever C is (one when parts == 1) and no plaintext in HBM.  A short cohort that is batched, gapped or mixed
                       stays "staged-chain", and so does everything the rules above send there for another reason.
     cut=False: the plans are what they always were.
+    cut_any=True beside cut=True (FlasheCohort(cut="any") on an engine with the flashe_*_cohort_cut_runs_* entry points) widens that:
+      "cut-chain"     also for a short cohort whose present clients form 2 .. 16 runs, wide and compact -- every gap is a cut the round
+                      imposes, the pieces are cohort_cut_pieces' and never fewer than two --, and for a short BATCHED cohort at
+                      int_bits > 64 with bs 5, 6 or 7, in one run or several (the rule counts the batched elements).  A cohort of more
+                      than 16 runs (one table holds 16 chains) and a mixed-float64 one stay "staged-chain".
+    cut_any=False: every plan is what it is without the keyword.
     Touches no device.  The library's own answer stays the last word: a "cohort-chain" or "cut-chain" plan it declines runs
     "staged-chain", a "prepared-cohort" one "prepared-staged"."""
     if len(weights_list) < 1:
@@ -1341,7 +1376,17 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
         path, reason = STAGED_CHAIN, "a layer is float64 for some clients only"
     else:
         path, reason = COHORT_CHAIN, ""
-    if cut and short:
+    if cut and cut_any and short:
+        # (batched: only the compiled batch sizes at int_bits > 64 get here -- the rules before the length rule sent the others away)
+        if mixed:
+            reason = "a layer is float64 for some clients only"
+        elif runs > _CUT_MAX_PARTS:
+            reason = f"clients dropped out ({runs} runs of indices): the cut chain takes at most {_CUT_MAX_PARTS} runs, one table holds as many chains"
+        else:
+            begins = cohort_cut_pieces(present, cohort_cut_items(n, int_bits, n_jobs, compact, n_elems if batch else None), cu_count)
+            if begins:
+                path, reason, parts = CUT_CHAIN, "", len(begins) - 1
+    elif cut and short:
         # the rules behind the length rule, in their order, in the cut launch's terms (one run, un-batched)
         if batch:
             reason += "; batched job: the cut chain takes un-batched cohorts"
@@ -1398,6 +1443,12 @@ class FlasheCohort(object):
     its _u32 form), two launches whatever n_local is, no plaintext in HBM, the same bytes, and the same decrypt mask kept for
     decrypt_unquantize().  Short cohorts that are batched, gapped (present= in several runs), single-mask, at int_bits 33 - 64 or of more
     than 128 clients stay "staged-chain".
+    cut="any" (opt-in; an engine without the entry points behaves as cut=True): "cut-chain" also for a short cohort in which clients
+    DROPPED OUT -- present= in 2 .. 16 runs, wide and compact: every gap is a cut, flashe_quantize_encrypt_cohort_cut_runs_dev / its _u32
+    form -- and for a short BATCHED cohort at int_bits > 64 with 5, 6 or 7 values per element, in one run or several
+    (flashe_quantize_batch_encrypt_cohort_cut_runs_dev).  The wide forms keep the decrypt mask of the telescoped lists, so
+    decrypt_unquantize() of such a round stays one combine (+ unbatch) pass; the compact form keeps none.  Any other value of cut:
+    ValueError.
     A round in which clients DROPPED OUT is quantize_encrypt(..., present=[positions]): the present clients' steps one after the other, and
     at int_bits > 64 still one chained launch (flashe_quantize_encrypt_cohort_runs_dev / flashe_quantize_batch_encrypt_cohort_runs_dev)
     over present + runs PRF streams that writes the decrypt mask of the telescoped index lists, so decrypt_unquantize() of that round
@@ -1418,7 +1469,10 @@ class FlasheCohort(object):
         self.lead = _CohortLead(args, device=device, stream=stream)
         self.lead.create_cipher(self.first_idx, self.num_clients, prp_seed)
         self.compact = bool(compact)
+        if isinstance(cut, str) and cut != "any" or not isinstance(cut, str) and cut not in (True, False):
+            raise ValueError(f"cut: True, False or \"any\", got {cut!r}")
         self.cut = bool(cut)                           # a short cohort runs "cut-chain" where the engine has the cut launch
+        self.cut_any = cut == "any"                    # ... gapped or batched too, where the engine has the launches that take indices
         self._cut_scratch = None                       # the cut launch's scratch, kept from round to round
         if self.compact:
             if self.lead.int_bits > 32:
@@ -1462,7 +1516,14 @@ class FlasheCohort(object):
                            n_jobs=_cipher_mod.N_JOBS, cohort_masks=self._masks is not None, present=present,
                            compact_runs=hasattr(ld.cipher.engine, "quantize_encrypt_cohort_runs_u32_dev"),
                            cut=self.cut and hasattr(ld.cipher.engine, "quantize_encrypt_cohort_cut_u32_dev" if self.compact
-                                                    else "quantize_encrypt_cohort_cut_dev"))
+                                                    else "quantize_encrypt_cohort_cut_dev"),
+                           cut_any=self.cut_any and all(hasattr(ld.cipher.engine, name) for name in self._cut_any_methods()))
+
+    def _cut_any_methods(self):
+        """The engine methods cut="any" needs for this cohort's layout."""
+        if self.compact:
+            return ("cohort_cut_pieces", "quantize_encrypt_cohort_cut_runs_u32_dev")
+        return ("cohort_cut_pieces", "quantize_batch_encrypt_cohort_cut_runs_dev" if self.lead.batch else "quantize_encrypt_cohort_cut_runs_dev")
 
     def prepare_encrypt(self):
         """A precompute job's idle-time step for the whole cohort.  Double mask: the encrypt masks of iteration iter_index + 1 for all
@@ -1689,7 +1750,9 @@ class FlasheCohort(object):
         the decrypt mask, which the lead keeps with the add / minus lists it stands for, for the decrypt of that sum.  by_idx (a call with
         `present`): the launch is given the present clients' cipher indices, any number of runs.  cut ("cut-chain", one run of clients):
         the chain cut into the library's cohort_cut_parts pieces plus the combine pass, with the scratch the pieces' sums and masks go
-        through; the outputs and the mask kept are those of the uncut launch.  False: the library declined, nothing was launched."""
+        through; the outputs and the mask kept are those of the uncut launch.  A gapped or batched "cut-chain" (cut="any") goes through
+        the launches that take the cipher indices, with the library's cohort_cut_pieces count; the mask kept is that of the telescoped
+        lists.  False: the library declined, nothing was launched."""
         from . import cipher as _cipher_mod
         from .engine import DeviceVector
         ld = self.lead
@@ -1699,7 +1762,24 @@ class FlasheCohort(object):
         dmask = DeviceVector(eng, n_elems) if self.n_local == self.num_clients and not self.compact else None
         outs, mask_buf = [v.buf for v in cts], dmask.buf if dmask is not None else None
         idxs = [self.first_idx + p for p in plan.present]
-        if cut:
+        if cut and (plan.runs > 1 or ld.batch):
+            parts = eng.cohort_cut_pieces(idxs, n_elems, _cipher_mod.N_JOBS, compact=self.compact)[0]
+            need = 0 if parts <= 1 else parts * n_elems * 4 if self.compact else parts * n_elems * 16 * (2 if dmask is not None else 1)
+            if need and (self._cut_scratch is None or self._cut_scratch.nbytes < need):
+                self._cut_scratch = eng.alloc(max(need, 16))
+            scratch = self._cut_scratch if need else None
+            if not parts:
+                took = False
+            elif self.compact:
+                took = eng.quantize_encrypt_cohort_cut_runs_u32_dev(c.iter_index, idxs, n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du, outs,
+                                                                    psum.buf, scratch)
+            elif ld.batch:
+                took = eng.quantize_batch_encrypt_cohort_cut_runs_dev(c.iter_index, idxs, n, n_elems, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits,
+                                                                      _field_bits(q.element_bits, q.num_clients), du, outs, psum.buf, mask_buf, scratch)
+            else:
+                took = eng.quantize_encrypt_cohort_cut_runs_dev(c.iter_index, idxs, n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du, outs,
+                                                                psum.buf, mask_buf, scratch)
+        elif cut:
             C = len(idxs)
             parts = eng.cohort_cut_parts(C, n, _cipher_mod.N_JOBS, compact=self.compact)
             need = 0 if parts <= 1 else parts * n * 4 if self.compact else parts * n * 16 * (2 if dmask is not None else 1)

@@ -5,6 +5,7 @@
 #include "ctx.h"
 #include "layer_tables.h"
 #include "cohort_streams.h"
+#include "cohort_cut.h"
 
 #include <algorithm>
 #include <cmath>
@@ -878,6 +879,104 @@ int flashe_quantize_batch_encrypt_cohort_runs_dev(flashe_ctx *ctx, uint32_t iter
     cb.field_bits = field_bits;
     return cohort_launched(ctx, launch_prf_cohort_sum(ctx->env, iter, n_clients, idx, cc, &cb, u_dev, ct_dev, sum_out_dev, n_elems, n_jobs, dmask_dev),
                            who, "batched cohort");
+}
+
+// ---- the SHORT cohort for any strictly ascending cipher indices in at most kCutMaxParts runs, and for a batched job (cohort_cut_pieces,
+// cohort_cut.h: every gap is a cut): the _runs_ entry points' checks, the _cut_ entry points' scratch and admission ----
+int flashe_cohort_cut_pieces(flashe_ctx *ctx, const uint32_t *idx, int n_clients, uint64_t n, uint32_t n_jobs, int compact, int *parts, int *begins)
+{
+    CHECK_CTX(ctx);
+    static const char who[] = "flashe_cohort_cut_pieces";
+    if (!parts) return fail(ctx, FLASHE_EINVAL, "%s: null argument", who);
+    *parts = 0;
+    if (n_clients < 1) return fail(ctx, FLASHE_EINVAL, "%s: n_clients must be >= 1", who);
+    if (compact && n_jobs == 0) return fail(ctx, FLASHE_EINVAL, "n_jobs must be >= 1");
+    flashe_tables::CohortStreams st;
+    if (flashe_tables::cohort_streams(idx, n_clients, 2 * n_clients, st) == flashe_tables::kCohortStreamsBadIdx)
+        return fail(ctx, FLASHE_EINVAL, "%s: the cipher indices must be strictly ascending and below 2^32 - 1", who);
+    int own[flashe_tables::kCutMaxParts + 1];
+    const int k = compact && flashe_ctx_compact_layout(ctx) != 1 ? 0 : cohort_cut_pieces_of(ctx->env, n_clients, idx, n, n_jobs, compact != 0, 0, own);
+    if (!k) return cohort_declined(ctx, who, compact ? "cut compact cohort" : "cut cohort");
+    *parts = k;
+    if (begins) for (int p = 0; p <= k; p++) begins[p] = own[p];
+    return FLASHE_OK;
+}
+
+int flashe_quantize_encrypt_cohort_cut_runs_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                                const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                                int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev,
+                                                uint64_t *dmask_dev, uint64_t *scratch_dev)
+{
+    CHECK_CTX(ctx);
+    static const char who[] = "flashe_quantize_encrypt_cohort_cut_runs_dev";
+    bool too_many = false;
+    int rc = cohort_check_runs(ctx, who, idx, n_clients, n, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, &too_many);
+    if (rc || (rc = cohort_check_outs(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, dmask_dev))) return rc;
+    int begins[flashe_tables::kCutMaxParts + 1];
+    const int parts = too_many ? 0 : cohort_cut_pieces_of(ctx->env, n_clients, idx, n, n_jobs, false, 0, begins);
+    if (!parts) return cohort_declined(ctx, who, "cut cohort");
+    if ((rc = cohort_check_scratch(ctx, parts, n_clients, scratch_dev, reinterpret_cast<const void *const *>(ct_dev), sum_out_dev, dmask_dev))) return rc;
+    CohortCodec cc{};
+    if ((rc = cohort_stage(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, cc))) return rc;
+    return cohort_launched(ctx, launch_prf_cohort_cut(ctx->env, iter, n_clients, idx, cc, u_dev, ct_dev, sum_out_dev, n, n_jobs, dmask_dev, scratch_dev), who,
+                           "cut cohort");
+}
+
+int flashe_quantize_encrypt_cohort_cut_runs_u32_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                                    const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
+                                                    const int32_t *src_dtype, int element_bits, const double *u_dev, uint32_t *const *ct_dev,
+                                                    uint32_t *sum_out_dev, uint32_t *scratch_dev)
+{
+    CHECK_CTX(ctx);
+    static const char who[] = "flashe_quantize_encrypt_cohort_cut_runs_u32_dev";
+    bool too_many = false;
+    int rc = cohort_check_runs(ctx, who, idx, n_clients, n, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, &too_many);
+    if (rc) return rc;
+    if (n_jobs == 0) return fail(ctx, FLASHE_EINVAL, "n_jobs must be >= 1");
+    if ((rc = cohort_check_outs<uint32_t>(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, nullptr))) return rc;
+    int begins[flashe_tables::kCutMaxParts + 1];
+    const int parts = too_many || flashe_ctx_compact_layout(ctx) != 1 ? 0 : cohort_cut_pieces_of(ctx->env, n_clients, idx, n, n_jobs, true, 0, begins);
+    if (!parts) return cohort_declined(ctx, who, "cut compact cohort");
+    if ((rc = cohort_check_scratch(ctx, parts, n_clients, scratch_dev, reinterpret_cast<const void *const *>(ct_dev), sum_out_dev, nullptr))) return rc;
+    CohortCodec cc{};
+    if ((rc = cohort_stage(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, cc))) return rc;
+    return cohort_launched(ctx, launch_small_cohort_cut(ctx->env, iter, n_clients, idx, cc, u_dev, ct_dev, sum_out_dev, n, n_jobs, scratch_dev), who,
+                           "cut compact cohort");
+}
+
+int flashe_quantize_batch_encrypt_cohort_cut_runs_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n_values,
+                                                      uint64_t n_elems, uint32_t n_jobs, const flashe_tensor_layer *layers, int n_layers,
+                                                      const void *const *src_dev, const int32_t *src_dtype, int element_bits, int field_bits,
+                                                      const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev, uint64_t *dmask_dev,
+                                                      uint64_t *scratch_dev)
+{
+    CHECK_CTX(ctx);
+    static const char who[] = "flashe_quantize_batch_encrypt_cohort_cut_runs_dev";
+    bool too_many = false;
+    uint64_t bs = 0;
+    int rc = cohort_check_runs(ctx, who, idx, n_clients, n_values, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, &too_many);
+    if (rc || (rc = check_batch_bits(ctx, element_bits, field_bits, &bs))) return rc;
+    std::vector<uint64_t> rows;
+    auto size_of = [&](int l) { return layer_end(layers, n_layers, l, n_values) - layers[l].start; };
+    const uint64_t e = flashe_tables::batched_elems(n_layers, bs, size_of, [&](int l, uint64_t elem, uint64_t) { rows.push_back(elem); rows.push_back(size_of(l)); });
+    if ((rc = check_batched_count(ctx, e, n_elems))) return rc;
+    if ((rc = cohort_check_outs(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, dmask_dev))) return rc;
+    int begins[flashe_tables::kCutMaxParts + 1];
+    const int parts = too_many || bs < 5 || bs > 7 ? 0 : cohort_cut_pieces_of(ctx->env, n_clients, idx, n_elems, n_jobs, false, static_cast<int>(bs), begins);
+    if (!parts) return cohort_declined(ctx, who, "cut batched cohort");
+    if ((rc = cohort_check_scratch(ctx, parts, n_clients, scratch_dev, reinterpret_cast<const void *const *>(ct_dev), sum_out_dev, dmask_dev))) return rc;
+    CohortCodec cc{};
+    const char *rows_dev = nullptr;
+    if ((rc = cohort_stage(ctx, n_clients, n_values, layers, n_layers, src_dev, src_dtype, element_bits, cc, rows.data(), rows.size() * sizeof(uint64_t),
+                           &rows_dev)))
+        return rc;
+    CohortBatch cb{};
+    cb.rows = reinterpret_cast<const uint64_t *>(rows_dev);
+    cb.n_values = n_values;
+    cb.field_bits = field_bits;
+    return cohort_launched(ctx, launch_prf_cohort_batch_cut(ctx->env, iter, n_clients, idx, cc, cb, u_dev, ct_dev, sum_out_dev, n_elems, n_jobs, dmask_dev,
+                                                            scratch_dev),
+                           who, "cut batched cohort");
 }
 
 // ---- the cohort's ONLINE step with masks the caller holds (a precompute job's cohort: the mask chain ran in idle time) ----

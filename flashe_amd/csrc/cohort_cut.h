@@ -55,4 +55,51 @@ inline bool cohort_cut_all_half(uint64_t n, int parts, int num_cus)
     return ((n + 255) / 256) * static_cast<uint64_t>(parts) < 2 * static_cast<uint64_t>(num_cus) * kCutWavesPerCu;
 }
 
+// ---- pieces that respect RUNS: a round in which clients dropped out (any strictly ascending cipher indices) ----
+// A gap in the cipher indices is a cut the round imposes: a run of consecutive present clients [a .. b] is by itself a chain over streams
+// a .. b + 1, and the pieces' masks S(b_p + 1) - S(a_p) add up to the decrypt mask of the telescoped lists (jzf_flashe.py:356-367) whether
+// the cuts come from gaps or from the rule above.  So: every run starts as one piece; while the pieces number fewer than
+// max(runs, cohort_cut_parts(...)) the run with the most clients per piece takes one more (compared as len_r k_best > len_best k_r, the
+// lower run on a tie), as long as its pieces keep kCutMinOutputs clients (len / (k + 1), rounded down); inside a run of k pieces that
+// starts at position a, piece q begins at a + len q / k.  One run gives exactly cohort_cut_parts / cohort_cut_begin.  More runs than
+// kCutMaxParts do not fit one table: 0, as for every shape cohort_cut_parts declines and for indices that are not strictly ascending or
+// hold 2^32 - 1 (cohort_streams.h).  A gapped cohort never has one piece: it always runs the combine pass.
+// (The tie-break and the floor for split runs are first guesses: tests/perf/cut_cohort_any_step.py times the 16-run shape.)
+constexpr int kCutMaxStreams = kCutMaxClients + kCutMaxParts;      // kCohortMaxStreams (cohort_streams.h): C + pieces never exceeds it
+
+// idx[0 .. n_clients) -> begins[0 .. parts] (the first present-client POSITION of every piece, begins[parts] = n_clients); returns parts.
+// begins holds kCutMaxParts + 1 entries.
+inline int cohort_cut_pieces(const uint32_t *idx, int n_clients, uint64_t items, int num_cus, int *begins)
+{
+    const int rule = cohort_cut_parts(n_clients, items, num_cus);
+    if (!idx || !begins || !rule) return 0;
+    int start[kCutMaxParts + 1], k[kCutMaxParts], runs = 0;
+    for (int v = 0; v < n_clients; v++) {
+        if (idx[v] == 0xffffffffu || (v && idx[v] <= idx[v - 1])) return 0;
+        if (v == 0 || idx[v] != idx[v - 1] + 1u) {
+            if (runs == kCutMaxParts) return 0;
+            start[runs] = v; k[runs] = 1; runs++;
+        }
+    }
+    start[runs] = n_clients;
+    const int want = rule > runs ? rule : runs;
+    for (int pieces = runs; pieces < want; pieces++) {
+        int best = -1;
+        for (int r = 0; r < runs; r++) {
+            const int len = start[r + 1] - start[r];
+            if (len / (k[r] + 1) < kCutMinOutputs) continue;
+            if (best < 0 || static_cast<int64_t>(len) * k[best] > static_cast<int64_t>(start[best + 1] - start[best]) * k[r]) best = r;
+        }
+        if (best < 0) break;
+        k[best]++;
+    }
+    int parts = 0;
+    for (int r = 0; r < runs; r++) {
+        const int len = start[r + 1] - start[r];
+        for (int q = 0; q < k[r]; q++) begins[parts++] = start[r] + static_cast<int>(static_cast<int64_t>(len) * q / k[r]);
+    }
+    begins[parts] = n_clients;
+    return parts;
+}
+
 }  // namespace flashe_tables

@@ -138,8 +138,16 @@ hipError_t launch_small_sparse_cohort(const LaunchEnv &env, uint32_t iter, int n
 // uncut launch's other conditions (wide: the chained table PRF at int_bits > 64 without a fused codec, 1 .. kMaxLinks clients, n in one
 // counter window; compact: small_cohort_admits(not summed)) -- from the environment and the sizes alone; the caller sizes the scratch
 // from it: parts x n x 16 B for the sums and as much again behind them for the masks (wide, with dmask_dev), parts x n x 4 B (compact),
-// unused when parts == 1.  idx: ONE run of consecutive indices.  hipErrorNotSupported: nothing launched.
+// unused when parts == 1.  hipErrorNotSupported: nothing launched.
+// idx: any strictly ascending indices in at most 16 runs -- every gap is a cut (cohort_cut_pieces, cohort_cut.h).  cohort_cut_pieces_of: the
+// pieces of such a cohort under the same admission, begins[0 .. parts] the first present-client position of each (kCutMaxParts + 1 entries);
+// one run: cohort_cut_parts_of's pieces exactly.  bs: 0, or the values per element of a BATCHED cohort (launch_prf_cohort_batch_cut: wide
+// only, bs 5 .. 7, n = the batched elements, launch_prf_cohort_sum's batched arguments).
 int cohort_cut_parts_of(const LaunchEnv &env, int n_vec, uint64_t n, uint32_t n_jobs, bool compact);
+int cohort_cut_pieces_of(const LaunchEnv &env, int n_vec, const uint32_t *idx, uint64_t n, uint32_t n_jobs, bool compact, int bs, int *begins);
+hipError_t launch_prf_cohort_batch_cut(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const CohortBatch &cb,
+                                       const double *u_dev, uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs,
+                                       uint64_t *dmask_dev, uint64_t *scratch_dev);
 hipError_t launch_prf_cohort_cut(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
                                  uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs, uint64_t *dmask_dev, uint64_t *scratch_dev);
 hipError_t launch_small_cohort_cut(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,

@@ -500,6 +500,22 @@ __global__ __launch_bounds__(THREADS) void prf_chain_cohort_batch_kernel(const R
 #include "prf_chain_body.inc"
 }
 
+// CUT with BS > 0: the batched cohort too SHORT to fill the chip uncut -- prf_chain_cohort_cut_kernel's n_chains summed chains, every one a run
+// of consecutive clients over the same batched elements, with the batched front end per output; cut_stride in limbs of the n batched
+// elements.  A separate kernel: the uncut batched launches keep their code objects.
+template <int THREADS, int BS_>
+__global__ __launch_bounds__(THREADS) void prf_chain_cohort_batch_cut_kernel(const RoundKeys rk, const ChainTable tb, int n_chains, int all_half_arg,
+                                                                               uint32_t iter0, uint64_t mask_lo, uint64_t mask_hi,
+                                                                               const uint32_t *__restrict__ te0, uint64_t *__restrict__ dmask,
+                                                                               const CohortCodec cc, const CohortBatch cb, uint64_t cut_stride)
+{
+    constexpr bool SUM = true, CODEC = false, DMASK = true, D128 = false, COHORT = true, GAPS = false, DEC = false, CUT = true;
+    constexpr int BS = BS_;
+    const Codec cq{};
+    const CohortGaps cg{};
+#include "prf_chain_body.inc"
+}
+
 // GAPS: the two cohort chains for cipher indices in SEVERAL runs -- a round in which clients dropped out (cohort_streams.h; GAPS in
 // prf_chain_body.inc).  The one chain's streams are the |P| + runs of tb.idx; cg tells which of them complete an output and which open a
 // client, and the launch still writes every present client's ciphertext, their sum and the decrypt mask of the telescoped lists
@@ -2070,17 +2086,20 @@ hipError_t launch_prf_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec,
 // ---- the SHORT cohort: the summed chain cut into runs of consecutive clients (cohort_cut.h), then one combine pass ----
 // What the cut launches admit: the uncut launches' conditions without the length rule.  The pieces they will use, 0 = not a shape of theirs
 // (the C ABI asks before it stages anything and tells the caller, who sizes the scratch from it).  compact: launch_small_cohort_cut's.
-int cohort_cut_parts_of(const LaunchEnv &env, int n_vec, uint64_t n, uint32_t n_jobs, bool compact)
+static uint64_t cohort_cut_items_of(const LaunchEnv &env, int n_vec, uint64_t n, uint32_t n_jobs, bool compact)
 {
-    uint64_t items;
     if (compact) {
         if (!small_cohort_admits(env, n_vec, n, n_jobs, false)) return 0;      // (not `summed`: every condition but the length rule)
-        items = flashe_tables::cohort_cut_items_compact(block_of(n - 1, n, n_jobs, 128 / env.b) + 1);
-    } else {
-        if (!env.use_chain || env.b <= 64 || env.codec || !table_prf(env) || n_vec < 1 || n_vec > kMaxLinks) return 0;
-        if (n == 0 || ((n - 1) >> 32)) return 0;                          // one counter window
-        items = flashe_tables::cohort_cut_items_wide(n);
+        return flashe_tables::cohort_cut_items_compact(block_of(n - 1, n, n_jobs, 128 / env.b) + 1);
     }
+    if (!env.use_chain || env.b <= 64 || env.codec || !table_prf(env) || n_vec < 1 || n_vec > kMaxLinks) return 0;
+    if (n == 0 || ((n - 1) >> 32)) return 0;                          // one counter window
+    return flashe_tables::cohort_cut_items_wide(n);
+}
+
+int cohort_cut_parts_of(const LaunchEnv &env, int n_vec, uint64_t n, uint32_t n_jobs, bool compact)
+{
+    const uint64_t items = cohort_cut_items_of(env, n_vec, n, n_jobs, compact);
     int parts = flashe_tables::cohort_cut_parts(n_vec, items, env.num_cus);
     // experiment knob (tests/perf/cut_cohort_step.py), read only when FLASHE_CHAIN_TUNE is set in the tuning build
     static const bool tune = FLASHE_TUNE_ENV("FLASHE_CHAIN_TUNE") != nullptr;
@@ -2092,16 +2111,33 @@ int cohort_cut_parts_of(const LaunchEnv &env, int n_vec, uint64_t n, uint32_t n_
     return parts;
 }
 
-// the pieces of a cut cohort as chains of one table: piece p holds clients [C p / parts, C (p + 1) / parts), its streams are theirs and the
-// one behind its last client (launch_prf_chains' layout: a cut costs one stream).  T = ChainTable / SmallChainTable.
+// The pieces of a cohort given by ANY strictly ascending cipher indices (cohort_cut_pieces, cohort_cut.h: every gap is a cut), under the
+// same admission; bs: 0, or the values per element of a BATCHED cohort (wide layout only, the compiled 5 .. 7; n counts its batched
+// elements).  begins[0 .. parts]: the first present-client position of every piece.  One run: cohort_cut_parts_of's pieces, exactly.
+int cohort_cut_pieces_of(const LaunchEnv &env, int n_vec, const uint32_t *idx, uint64_t n, uint32_t n_jobs, bool compact, int bs, int *begins)
+{
+    if (!idx || (bs != 0 && (compact || bs < 5 || bs > 7))) return 0;
+    int runs = 1;
+    for (int v = 1; v < n_vec; v++) runs += idx[v] != idx[v - 1] + 1u;
+    if (runs > 1) return flashe_tables::cohort_cut_pieces(idx, n_vec, cohort_cut_items_of(env, n_vec, n, n_jobs, compact), env.num_cus, begins);
+    const int parts = cohort_cut_parts_of(env, n_vec, n, n_jobs, compact);
+    if (!parts) return 0;
+    for (int p = 0; p <= parts; p++) begins[p] = flashe_tables::cohort_cut_begin(n_vec, parts, p);
+    return parts;
+}
+
+// the pieces of a cut cohort as chains of one table: piece p holds the present clients at positions [begins[p], begins[p + 1]) -- one run of
+// consecutive cipher indices --, its streams are theirs and the one behind its last client (launch_prf_chains' layout: a cut costs one
+// stream).  T = ChainTable / SmallChainTable.
 template <class T>
-static void cohort_cut_table(T &tb, int n_vec, int parts, const uint32_t *idx, uint64_t n, uint64_t tiles)
+static void cohort_cut_table(T &tb, int n_vec, int parts, const int *begins, const uint32_t *idx, uint64_t n, uint64_t tiles)
 {
     static_assert(flashe_tables::kCutMaxParts == kMaxChains && flashe_tables::kCutMaxClients == kMaxLinks, "cohort_cut.h states the limits of one chained launch");
+    static_assert(flashe_tables::kCutMaxStreams == flashe_tables::kCohortMaxStreams, "cohort_cut.h and cohort_streams.h state one table's streams");
     int streams = 0;
     uint64_t wend = 0;
     for (int p = 0; p < parts; p++) {
-        const int a = flashe_tables::cohort_cut_begin(n_vec, parts, p), len = flashe_tables::cohort_cut_begin(n_vec, parts, p + 1) - a;
+        const int a = begins[p], len = begins[p + 1] - a;
         tb.first[p] = 0; tb.count[p] = n;
         tb.link0[p] = static_cast<uint16_t>(a); tb.sbase[p] = static_cast<uint16_t>(streams);
         tb.len[p] = static_cast<uint8_t>(len);
@@ -2113,24 +2149,28 @@ static void cohort_cut_table(T &tb, int n_vec, int parts, const uint32_t *idx, u
     assert(streams == n_vec + parts && streams <= flashe_tables::kCohortMaxStreams);
 }
 
-// prf_chain_cohort_cut_kernel + cohort_cut_combine_kernel: launch_prf_cohort_sum's outputs for ANY n >= 1.  One run of consecutive cipher
-// indices; scratch_dev: parts x n x 16 B for the pieces' sums and as much again for their masks when dmask_dev is given, unused when the
-// rule gives one piece (the chain then writes the sum and the mask where they belong and no combine pass runs).
-// hipErrorNotSupported = nothing launched.
-hipError_t launch_prf_cohort_cut(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
-                                 uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs, uint64_t *dmask_dev, uint64_t *scratch_dev)
+// prf_chain_cohort_cut_kernel + cohort_cut_combine_kernel: launch_prf_cohort_sum's outputs for ANY n >= 1.  Any strictly ascending cipher
+// indices in at most kCutMaxParts runs (every gap is a cut: cohort_cut_pieces); scratch_dev: parts x n x 16 B for the pieces' sums and as
+// much again for their masks when dmask_dev is given, unused when the rule gives one piece (the chain then writes the sum and the mask
+// where they belong and no combine pass runs).  cb: the BATCHED form (prf_chain_cohort_batch_cut_kernel, launch_prf_cohort_batch_cut): n
+// counts the batched elements, one draw per VALUE.  hipErrorNotSupported = nothing launched.
+static hipError_t launch_prf_cohort_cut_any(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const CohortBatch *cb,
+                                            const double *u_dev, uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs,
+                                            uint64_t *dmask_dev, uint64_t *scratch_dev)
 {
-    const int parts = cohort_cut_parts_of(env, n_vec, n, n_jobs, false);
-    if (!parts || !sum_out_dev || !u_dev || cc.n_layers < 1) return hipErrorNotSupported;
-    for (int v = 0; v < n_vec; v++) if (!out_dev[v] || (v && idx[v] != idx[v - 1] + 1u)) return hipErrorNotSupported;
+    const int bs = !cb ? 0 : (cb->field_bits < 1 || cb->field_bits > env.b) ? -1 : env.b / cb->field_bits;
+    int begins[flashe_tables::kCutMaxParts + 1];
+    const int parts = cohort_cut_pieces_of(env, n_vec, idx, n, n_jobs, false, bs, begins);
+    if (!parts || !sum_out_dev || !u_dev || cc.n_layers < 1 || (cb && !cb->rows)) return hipErrorNotSupported;
+    for (int v = 0; v < n_vec; v++) if (!out_dev[v]) return hipErrorNotSupported;
     if (parts > 1 && !scratch_dev) return hipErrorInvalidValue;
-    const uint64_t tiles = (n + 255) / 256, stride = 2 * n;                // (limbs of one piece's sum or mask)
+    const uint64_t tiles = (n + 255) / 256, stride = 2 * n, u_stride = cb ? cb->n_values : n;                // (stride: limbs of one piece's sum or mask)
     uint64_t *const psum = scratch_dev, *const pmask = dmask_dev ? scratch_dev + static_cast<uint64_t>(parts) * stride : nullptr;
     ChainTable tb{};
-    cohort_cut_table(tb, n_vec, parts, idx, n, tiles);
+    cohort_cut_table(tb, n_vec, parts, begins, idx, n, tiles);
     for (int p = 0; p < parts; p++) tb.sum_out[p] = parts == 1 ? sum_out_dev : psum + static_cast<uint64_t>(p) * stride;
     for (int l = 0; l < n_vec; l++) {
-        tb.in[l] = reinterpret_cast<const uint64_t *>(u_dev + static_cast<uint64_t>(l) * n);       // the link's draws (CohortCodec)
+        tb.in[l] = reinterpret_cast<const uint64_t *>(u_dev + static_cast<uint64_t>(l) * u_stride);       // the link's draws (CohortCodec)
         tb.out[l] = out_dev[l];
     }
     uint64_t lo, hi;
@@ -2138,11 +2178,36 @@ hipError_t launch_prf_cohort_cut(const LaunchEnv &env, uint32_t iter, int n_vec,
     const bool all_half = flashe_tables::cohort_cut_all_half(n, parts, env.num_cus);
     const uint64_t items = (all_half ? 2 : 1) * tiles * static_cast<uint64_t>(parts), cus = static_cast<uint64_t>(env.num_cus);
     const dim3 grid(static_cast<unsigned>(items < cus ? items : cus)), block(kPrfThreads);
-    hipLaunchKernelGGL((prf_chain_cohort_cut_kernel<kPrfThreads>), grid, block, 0, env.stream, env.rk, tb, parts, all_half ? 1 : 0, iter, lo, hi, env.te0_dev,
-                       parts == 1 ? dmask_dev : pmask, cc, stride);
+#define COHORT_BATCH_CUT(BS) hipLaunchKernelGGL((prf_chain_cohort_batch_cut_kernel<kPrfThreads, BS>), grid, block, 0, env.stream, env.rk, tb, parts, all_half ? 1 : 0, iter, lo, hi, \
+                                                env.te0_dev, parts == 1 ? dmask_dev : pmask, cc, *cb, stride)
+    switch (bs) {
+    case 0:
+        hipLaunchKernelGGL((prf_chain_cohort_cut_kernel<kPrfThreads>), grid, block, 0, env.stream, env.rk, tb, parts, all_half ? 1 : 0, iter, lo, hi, env.te0_dev,
+                           parts == 1 ? dmask_dev : pmask, cc, stride);
+        break;
+    case 5: COHORT_BATCH_CUT(5); break;
+    case 6: COHORT_BATCH_CUT(6); break;
+    default: COHORT_BATCH_CUT(7); break;
+    }
+#undef COHORT_BATCH_CUT
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess || parts == 1) return e;
     return launch_cohort_cut_combine(env, parts, n, psum, sum_out_dev, pmask, dmask_dev);
+}
+
+hipError_t launch_prf_cohort_cut(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
+                                 uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs, uint64_t *dmask_dev, uint64_t *scratch_dev)
+{
+    return launch_prf_cohort_cut_any(env, iter, n_vec, idx, cc, nullptr, u_dev, out_dev, sum_out_dev, n, n_jobs, dmask_dev, scratch_dev);
+}
+
+// the batched cohort of ANY length: launch_prf_cohort_sum's batched arguments (n = the batched elements, cb.n_values draws per client) and
+// the cut launch's scratch, parts x n x 16 B and as much again with dmask_dev
+hipError_t launch_prf_cohort_batch_cut(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const CohortBatch &cb,
+                                       const double *u_dev, uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs,
+                                       uint64_t *dmask_dev, uint64_t *scratch_dev)
+{
+    return launch_prf_cohort_cut_any(env, iter, n_vec, idx, cc, &cb, u_dev, out_dev, sum_out_dev, n, n_jobs, dmask_dev, scratch_dev);
 }
 
 // b <= 64 form of launch_prf_jobs
@@ -2779,20 +2844,21 @@ hipError_t launch_small_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_ve
 // The SHORT compact cohort (cohort_cut.h): launch_small_cohort_sum's outputs for any n >= 1.  prf_small_cohort_kernel takes several summed
 // chains as it is -- every chain's links, streams and sum are addressed through link0 / sbase / sum_out[cur], and the sums the walked tiles
 // keep in memory start at the chain's own first link -- so the cut is this table: `parts` double-mask chains over the same AES blocks,
-// piece p's uint32 sum in scratch_dev + p * n, then the combine pass.  One piece writes sum_out_dev itself.  One run of consecutive
-// cipher indices; hipErrorNotSupported = nothing launched.
+// piece p's uint32 sum in scratch_dev + p * n, then the combine pass.  One piece writes sum_out_dev itself.  Any strictly ascending cipher
+// indices in at most kCutMaxParts runs (cohort_cut_pieces); hipErrorNotSupported = nothing launched.
 hipError_t launch_small_cohort_cut(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
                                    uint32_t *const *out_dev, uint32_t *sum_out_dev, uint64_t n, uint32_t n_jobs, uint32_t *scratch_dev)
 {
-    const int parts = cohort_cut_parts_of(env, n_vec, n, n_jobs, true);
+    int begins[flashe_tables::kCutMaxParts + 1];
+    const int parts = cohort_cut_pieces_of(env, n_vec, idx, n, n_jobs, true, 0, begins);
     if (!parts || !sum_out_dev || !u_dev || cc.n_layers < 1) return hipErrorNotSupported;
-    for (int v = 0; v < n_vec; v++) if (!out_dev[v] || (v && idx[v] != idx[v - 1] + 1u)) return hipErrorNotSupported;
+    for (int v = 0; v < n_vec; v++) if (!out_dev[v]) return hipErrorNotSupported;
     if (parts > 1 && !scratch_dev) return hipErrorInvalidValue;
     uint64_t blocks;
     const SmallParams p = small_cohort_params(env, iter, n_vec, n, n_jobs, &blocks);
     const uint64_t tiles = (blocks + 127) / 128, cus = static_cast<uint64_t>(env.num_cus);
     SmallChainTable tb{};
-    cohort_cut_table(tb, n_vec, parts, idx, n, tiles);
+    cohort_cut_table(tb, n_vec, parts, begins, idx, n, tiles);
     for (int k = 0; k < parts; k++) {
         tb.blk_first[k] = 0; tb.blk_count[k] = blocks;
         tb.sum_out[k] = reinterpret_cast<uint64_t *>(parts == 1 ? sum_out_dev : scratch_dev + static_cast<uint64_t>(k) * n);

@@ -1,8 +1,9 @@
 // The body of prf_chain_kernel<THREADS, SUM, CODEC>, prf_chain_dmask_kernel<THREADS>, prf_dmask_sum128_kernel<THREADS>, prf_dec_sum128_kernel<THREADS> and
-// prf_chain_cohort_kernel<THREADS>, prf_chain_cohort_cut_kernel<THREADS> and prf_chain_cohort_batch_kernel<THREADS, BS> (kernels.hip), included INSIDE each kernel: the kernel defines
+// prf_chain_cohort_kernel<THREADS>, prf_chain_cohort_cut_kernel<THREADS>, prf_chain_cohort_batch_kernel<THREADS, BS> and prf_chain_cohort_batch_cut_kernel<THREADS, BS> (kernels.hip), included INSIDE each kernel: the kernel defines
 // THREADS, SUM, CODEC, DMASK, D128, COHORT, BS, GAPS, DEC and CUT as compile-time constants and has the arguments rk, tb, n_chains, all_half_arg, iter0, mask_lo,
 // mask_hi, te0, cq, cc, cb, cg, dmask and cut_stride in scope.
-// CUT (COHORT only, prf_chain_cohort_cut_kernel): a SHORT cohort cut into n_chains runs of consecutive clients (cohort_cut.h), every run its
+// CUT (COHORT only, prf_chain_cohort_cut_kernel; with BS > 0 prf_chain_cohort_batch_cut_kernel, whose elements are the batched ones -- the
+// front end and the mask store address a chain's clients alike, link0 + link): a SHORT cohort cut into n_chains runs of consecutive clients (cohort_cut.h), every run its
 // own summed double-mask chain over the same elements.  tb.sum_out[cur] is per chain already; the decrypt mask of chain `cur` goes to
 // dmask + cur * cut_stride where the other DMASK kernels have one mask for the launch's one chain.  The chains' masks telescope and
 // their sums add up: one combine pass (cohort_cut_combine_kernel, stream.hip) gives what the uncut launch writes.  Every branch on CUT is
@@ -30,7 +31,7 @@
     static_assert(BS == 0 || COHORT, "batching is a form of the cohort front end");
     static_assert(!GAPS || COHORT, "several runs of indices are a form of the cohort chain");
     static_assert(!DEC || D128, "the decrypted sum is written by the int_bits = 128 specialisation");
-    static_assert(!CUT || (COHORT && BS == 0 && !GAPS), "the cut is a form of the one-run, un-batched cohort chain");
+    static_assert(!CUT || (COHORT && !GAPS), "the cut is a form of the cohort chain whose every piece is one run of clients");
     (void)cg;
     (void)cut_stride;
     (void)dmask;

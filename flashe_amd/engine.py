@@ -824,6 +824,54 @@ class Engine:
                                                                      element_bits, field_bits, self._ptr(u), pc, self._ptr(sum_out), self._ptr(dmask))
         return self._took(rc)
 
+    def cohort_cut_pieces(self, idx, n, n_jobs, compact=False):
+        """(parts, begins) of the cut launches that take cipher indices (flashe_cohort_cut_pieces): the pieces a cohort of the clients idx --
+        strictly ascending, any number of runs up to 16 -- with n ELEMENTS (a batched job: its batched elements) is cut into, and the
+        position in idx of every piece's first client (begins[parts] = len(idx)).  The caller sizes the scratch from parts.  (0, []): the
+        library declines the shape (FLASHE_ENOTSUP)."""
+        pi, _ki = self._cohort_idx(idx, len(idx))
+        parts, begins = ctypes.c_int(0), (ctypes.c_int * 17)()
+        rc = self._lib.flashe_cohort_cut_pieces(self._h, pi, len(idx), int(n), n_jobs, 1 if compact else 0, ctypes.byref(parts), begins)
+        return (parts.value, list(begins[:parts.value + 1])) if self._took(rc) else (0, [])
+
+    def quantize_encrypt_cohort_cut_runs_dev(self, it, idx, n, n_jobs, layers, srcs, dtypes, element_bits, u, cts, sum_out, dmask=None, scratch=None):
+        """quantize_encrypt_cohort_cut_dev with the cipher indices of the clients that report (flashe_quantize_encrypt_cohort_cut_runs_dev):
+        quantize_encrypt_cohort_runs_dev's outputs for a vector of ANY length, every gap of idx a cut.  scratch: 16-byte aligned,
+        cohort_cut_pieces(idx, n, ...) parts x n x 16 bytes, twice that with dmask.  Returns False -- nothing was launched -- when the
+        library declines the shape (FLASHE_ENOTSUP: also more than 16 runs), True otherwise."""
+        arr, nl = self._tensor_layers(layers)
+        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
+        pc, _k = self._ptr_array(cts)
+        pi, _ki = self._cohort_idx(idx, C)
+        rc = self._lib.flashe_quantize_encrypt_cohort_cut_runs_dev(self._h, it, pi, C, int(n), n_jobs, arr, nl, ps, pd, element_bits, self._ptr(u),
+                                                                   pc, self._ptr(sum_out), self._ptr(dmask), self._ptr(scratch))
+        return self._took(rc)
+
+    def quantize_encrypt_cohort_cut_runs_u32_dev(self, it, idx, n, n_jobs, layers, srcs, dtypes, element_bits, u, cts, sum_out, scratch=None):
+        """The same in the compact layout (flashe_quantize_encrypt_cohort_cut_runs_u32_dev, int_bits 16 / 20 / 23 / 24 / 32): scratch of
+        cohort_cut_pieces(idx, n, ..., compact=True) parts x n x 4 bytes; no decrypt mask (decrypt the sum with telescope(idx))."""
+        arr, nl = self._tensor_layers(layers)
+        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
+        pc, _k = self._ptr_array(cts)
+        pi, _ki = self._cohort_idx(idx, C)
+        rc = self._lib.flashe_quantize_encrypt_cohort_cut_runs_u32_dev(self._h, it, pi, C, int(n), n_jobs, arr, nl, ps, pd, element_bits,
+                                                                       self._ptr(u), pc, self._ptr(sum_out), self._ptr(scratch))
+        return self._took(rc)
+
+    def quantize_batch_encrypt_cohort_cut_runs_dev(self, it, idx, n_values, n_elems, n_jobs, layers, srcs, dtypes, element_bits, field_bits, u, cts,
+                                                   sum_out, dmask=None, scratch=None):
+        """quantize_batch_encrypt_cohort_runs_dev for a model of ANY length (flashe_quantize_batch_encrypt_cohort_cut_runs_dev): the batched
+        chain cut into cohort_cut_pieces(idx, n_elems, ...) pieces and one combine pass.  scratch: parts x n_elems x 16 bytes, twice that
+        with dmask."""
+        arr, nl = self._tensor_layers(layers)
+        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
+        pc, _k = self._ptr_array(cts)
+        pi, _ki = self._cohort_idx(idx, C)
+        rc = self._lib.flashe_quantize_batch_encrypt_cohort_cut_runs_dev(self._h, it, pi, C, int(n_values), int(n_elems), n_jobs, arr, nl, ps, pd,
+                                                                         element_bits, field_bits, self._ptr(u), pc, self._ptr(sum_out),
+                                                                         self._ptr(dmask), self._ptr(scratch))
+        return self._took(rc)
+
     @staticmethod
     def _cohort_idx(idx, C):
         """The cipher indices of a cohort's C clients as a uint32 array (nothing is reduced mod 2^32 on the way)."""

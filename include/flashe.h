@@ -89,7 +89,9 @@ typedef struct flashe_ctx flashe_ctx;
  *      int_bits 128); flashe_cohort_cut_parts + flashe_quantize_encrypt_cohort_cut_dev / flashe_quantize_encrypt_cohort_cut_u32_dev (a
  *      cohort whose vector does not fill the chip uncut: the summed chain cut into runs of clients and one combine pass);
  *      flashe_aggregate_packed_elems_dev / flashe_aggregate_packed_elems_u32_dev (the arbiter's packed reduce computed on unpacked
- *      ciphertext vectors in one pass) */
+ *      ciphertext vectors in one pass); flashe_cohort_cut_pieces + flashe_quantize_encrypt_cohort_cut_runs_dev /
+ *      flashe_quantize_encrypt_cohort_cut_runs_u32_dev / flashe_quantize_batch_encrypt_cohort_cut_runs_dev (the cut launch for a round in
+ *      which clients dropped out -- every gap is a cut -- and for a batched job) */
 #define FLASHE_ABI_VERSION 4
 int flashe_abi_version(void);
 int flashe_device_count(int *count);
@@ -821,6 +823,46 @@ int flashe_quantize_batch_encrypt_cohort_runs_dev(flashe_ctx *ctx, uint32_t iter
 int flashe_quantize_encrypt_cohort_runs_u32_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n, uint32_t n_jobs,
                                                 const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
                                                 int element_bits, const double *u_dev, uint32_t *const *ct_dev, uint32_t *sum_out_dev);
+/* A SHORT cohort in which clients DROPPED OUT, and a short BATCHED cohort (new), jzf_flashe.py:349-367, jzf_aggregator.py:424-430: a gap in
+ * the cipher indices is a cut the round imposes -- a run of consecutive present clients a .. b is by itself a chain over streams
+ * a .. b + 1 --, and the pieces' masks term(b_p + 1) - term(a_p) add up to the decrypt mask of the telescoped lists whether the cuts come
+ * from gaps or from the rule of flashe_cohort_cut_parts.  So the cut launches take any strictly ascending idx in at most 16 runs.
+ * flashe_cohort_cut_pieces: *parts = the pieces the launches below will use for the n_clients clients of idx and n ELEMENTS (a batched
+ * job passes n_elems), and, when begins is not NULL, begins[0 .. *parts] = the position in idx of every piece's first client
+ * (begins[*parts] = n_clients; room for 17 entries).  Every run starts as one piece; while they number fewer than
+ * max(runs, flashe_cohort_cut_parts' count) the run with the most clients per piece takes one more, as long as its pieces keep four
+ * clients; inside a run the pieces are even.  One run: flashe_cohort_cut_parts' pieces.  A gapped cohort always has parts >= 2.
+ * FLASHE_EINVAL: idx NULL, not strictly ascending or holding 2^32 - 1, n_clients < 1, compact with n_jobs = 0.  FLASHE_ENOTSUP
+ * (*parts = 0) where the launch would decline: flashe_cohort_cut_parts' cases and more than 16 runs. */
+int flashe_cohort_cut_pieces(flashe_ctx *ctx, const uint32_t *idx, int n_clients, uint64_t n, uint32_t n_jobs, int compact, int *parts, int *begins);
+/* flashe_quantize_encrypt_cohort_cut_dev with the cipher indices idx of the n_clients clients that report in place of first_idx (new),
+ * jzf_quantize.py:394-491, jzf_flashe.py:349-367, jzf_aggregator.py:424-430: everything indexed by client counts the clients of idx, as
+ * in flashe_quantize_encrypt_cohort_runs_dev, whose outputs it writes -- ct_dev[c], their sum and, with dmask_dev, the decrypt mask of the
+ * telescoped lists -- for any n >= 1.  scratch_dev: parts x n x 16 bytes and as much again when dmask_dev is given, parts from
+ * flashe_cohort_cut_pieces.  One run launches what flashe_quantize_encrypt_cohort_cut_dev launches and writes its bytes.
+ * FLASHE_EINVAL: a bad idx (as above), a bad scratch, and that function's argument errors.  FLASHE_ENOTSUP -- nothing launched, every
+ * output untouched -- outside its admission and for more than 16 runs.  Not capturable. */
+int flashe_quantize_encrypt_cohort_cut_runs_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                                const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                                int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev,
+                                                uint64_t *dmask_dev, uint64_t *scratch_dev);
+/* The same for the compact layout (new), jzf_quantize.py:394-491, jzf_flashe.py:349-367, jzf_aggregator.py:424-430:
+ * flashe_quantize_encrypt_cohort_cut_u32_dev with idx in place of first_idx; scratch_dev: parts x n x 4 bytes, parts from
+ * flashe_cohort_cut_pieces(compact = 1).  No mask is kept: decrypt the sum with flashe_telescope(idx). */
+int flashe_quantize_encrypt_cohort_cut_runs_u32_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                                    const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
+                                                    const int32_t *src_dtype, int element_bits, const double *u_dev, uint32_t *const *ct_dev,
+                                                    uint32_t *sum_out_dev, uint32_t *scratch_dev);
+/* The BATCHED cohort at int_bits > 64 for any n_elems >= 1 (new), jzf_quantize.py:162-185, jzf_flashe.py:349-367, jzf_aggregator.py:424-430:
+ * flashe_quantize_batch_encrypt_cohort_runs_dev's arguments, checks and outputs without its length rule (bs = 5 .. 7; one run or several,
+ * at most 16), the chain cut into the pieces of flashe_cohort_cut_pieces(ctx, idx, n_clients, n_elems, ...) over the batched elements;
+ * scratch_dev: parts x n_elems x 16 bytes and as much again when dmask_dev is given (feed the mask to
+ * flashe_combine_unbatch_unquantize_model_dev).  FLASHE_EINVAL / FLASHE_ENOTSUP as above.  Not capturable. */
+int flashe_quantize_batch_encrypt_cohort_cut_runs_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n_values,
+                                                      uint64_t n_elems, uint32_t n_jobs, const flashe_tensor_layer *layers, int n_layers,
+                                                      const void *const *src_dev, const int32_t *src_dtype, int element_bits, int field_bits,
+                                                      const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev, uint64_t *dmask_dev,
+                                                      uint64_t *scratch_dev);
 /* A precompute job's cohort (new), jzf_flashe.py:599-631, 456-488: every client computes its next round's encrypt mask in idle time and
  * its online step is a quantise plus a mask add.  For a cohort the masks are ONE chain of n_clients + 1 streams into vectors the caller
  * owns, mask[c][j] = term(iter, first_idx + c)[j] - term(iter, first_idx + c + 1)[j] mod 2^b: in the limb layout
