@@ -264,6 +264,12 @@ _SIGNATURES = {
                                                    ctypes.POINTER(ctypes.c_int32), c_int, c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
     "flashe_quantize_combine_cohort_u32_dev": (c_int, [c_vp, c_int, c_u64, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp),
                                                        ctypes.POINTER(ctypes.c_int32), c_int, c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
+    "flashe_quantize_combine_cohort_philox_dev": (c_int, [c_vp, c_int, c_u64, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp),
+                                                          ctypes.POINTER(ctypes.c_int32), c_int, ctypes.POINTER(PhiloxSegment), c_int,
+                                                          ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
+    "flashe_quantize_combine_cohort_philox_u32_dev": (c_int, [c_vp, c_int, c_u64, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp),
+                                                              ctypes.POINTER(ctypes.c_int32), c_int, ctypes.POINTER(PhiloxSegment), c_int,
+                                                              ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
     "flashe_quantize_batch_combine_cohort_dev": (c_int, [c_vp, c_int, c_u64, c_u64, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp),
                                                          ctypes.POINTER(ctypes.c_int32), c_int, c_int, c_vp, ctypes.POINTER(c_vp),
                                                          ctypes.POINTER(c_vp), c_vp]),

@@ -313,6 +313,36 @@ def _cohort_draws(eng, C, per_client, seeds, rng=None):
     return du
 
 
+# Is the inline form the default of a shape class (compact layout?, every client's stream starts at a Philox block?) -- the round-9 rule:
+# only where its median beat the buffer form's by more than the larger of the two spreads.  FLASHE_INLINE_DRAWS=1 forces it elsewhere.
+_INLINE_DRAWS_DEFAULT = {(False, True): True, (False, False): True, (True, True): True, (True, False): True}
+
+
+def _draws_aligned(rng, C, n):
+    """Does every client's stretch start at a block of its Philox stream (a run of four values is then ONE block)?  A list: every
+    generator's buffer is fresh or exhausted (buffer_pos 4, or 0 set by hand); one shared generator: that, and n % 4 == 0 or one client."""
+    if isinstance(rng, list):
+        return all(int(g.bit_generator.state["buffer_pos"]) in (0, 4) for g in rng)
+    return int(rng.bit_generator.state["buffer_pos"]) in (0, 4) and (n % 4 == 0 or C <= 1)
+
+
+def _inline_draws(eng, rng, batched, compact=False, C=1, n=0):
+    """Does a "prepared-cohort" round generate its draws INSIDE the online launch (eng.quantize_combine_cohort_philox_dev: no draw
+    buffer, one launch less)?  An un-batched job, every (present) client's Generator over np.random.Philox, FLASHE_DEVICE_RNG not 0, an
+    engine that has the call, and FLASHE_INLINE_DRAWS (the A/B switch, read per call): 0 never, 1 always, unset the default of the
+    round's shape class (_INLINE_DRAWS_DEFAULT).  No DEVICE_RNG_MIN threshold: there is no extra launch to amortise.  A batched job
+    reads the draw buffer (an element's 5 - 7 values span Philox blocks that neighbouring lanes would each recompute)."""
+    if batched or rng is None or not hasattr(eng, "quantize_combine_cohort_philox_dev"):
+        return False
+    switch = os.environ.get("FLASHE_INLINE_DRAWS", "")
+    if os.environ.get("FLASHE_DEVICE_RNG", "1") == "0" or switch == "0":
+        return False
+    gens = rng if isinstance(rng, list) else [rng]
+    if len(gens) > eng.PHILOX_MAX_SEGMENTS or not all(isinstance(g.bit_generator, np.random.Philox) for g in gens):
+        return False
+    return switch == "1" or _INLINE_DRAWS_DEFAULT[(bool(compact), _draws_aligned(rng, C, n))]
+
+
 class FlasheClient(object):
     """`jzf_flashe_block._Client` without the transport: holds a FlasheCipher and forwards to it with the
     reference's method names, so `JZFWeights.encrypted(cipher)` / `.decrypted(cipher)`
@@ -1110,10 +1140,11 @@ class CohortPlan(object):
 class CohortUpload(object):
     """FlasheCohort.quantize_encrypt's result: ciphertexts (one DeviceVector per present client), partial_sum (their sum mod 2^b), path
     and present (the GLOBAL cipher indices of the clients the upload holds, ascending: what a decrypt of the sum passes to
-    set_idx_list)."""
+    set_idx_list), and draws: "inline" when the launch that consumed the stochastic-rounding draws generated them itself (a prepared
+    un-batched cohort over Philox generators), "buffer" when they were materialised in HBM first."""
 
-    def __init__(self, ciphertexts, partial_sum, path, present=None):
-        self.ciphertexts, self.partial_sum, self.path, self.present = ciphertexts, partial_sum, path, present
+    def __init__(self, ciphertexts, partial_sum, path, present=None, draws="buffer"):
+        self.ciphertexts, self.partial_sum, self.path, self.present, self.draws = ciphertexts, partial_sum, path, present, draws
 
 
 def _present_runs(present, count):
@@ -1287,7 +1318,9 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
     cohort_masks=True (the cohort holds the masks of FlasheCohort.prepare_encrypt: a precompute job under the double mask) answers
       "prepared-cohort"  one online launch from the floats and the masks, no AES (flashe_quantize_combine_cohort_dev, its _u32 form with
                          compact=True, flashe_quantize_batch_combine_cohort_dev for a batched job): any int_bits, any length, any number
-                         of clients;
+                         of clients.  The draws are laid out client-major for a buffer in HBM (draw_offsets); an un-batched round
+                         whose rng= generators are over np.random.Philox materialises none -- the launch generates them at those
+                         positions (flashe_quantize_combine_cohort_philox_dev / _u32_dev, FlasheCohort.quantize_encrypt);
       "prepared-staged"  a layer that is float64 for some clients only (no shared row), or a batched job in the compact layout: a
                          quantise (+ batch) pass per client into plaintexts, then flashe_combine_batch_sum_dev with the masks.
     present=[positions] (a round in which clients dropped out: the strictly ascending local positions of the clients that report, one
@@ -1457,7 +1490,9 @@ class FlasheCohort(object):
     decrypt_unquantize() decrypts the sum with the telescoped lists.
     A precompute job ("precompute": {"enable": true}) calls prepare_encrypt() in idle time: the next round's masks of all clients as one
     chain of n_local + 1 streams, held by the cohort; the next quantize_encrypt is then ONE online launch with no AES ("prepared-cohort")
-    at any int_bits, batched or not, compact or not.  Without that call the clients' own masks run "per-client" as before.
+    at any int_bits, batched or not, compact or not.  Without that call the clients' own masks run "per-client" as before.  Un-batched and
+    with rng= generators over np.random.Philox that launch also generates the stochastic-rounding draws (CohortUpload.draws == "inline":
+    no draw buffer in HBM); every other cohort materialises its draws first ("buffer").
     A DENSE job's arbiter adds the clients' bit-packed models as one integer (jzf_aggregator.py:406-419); CohortUpload.partial_sum is
     the element-wise sum.  aggregate_packed() is that packed reduce of an upload, one pass over the ciphertexts where they lie, and
     decrypt_unquantize(packed=True) decrypts it, so that a cohort which simulates a dense job returns the global model the job produces."""
@@ -1580,8 +1615,14 @@ class FlasheCohort(object):
         launch over present + runs PRF streams that writes the decrypt mask of the telescoped index lists.  present=None: everyone, the
         call as it always was.  seeds=None: the stochastic-rounding draws come from NumPy's global stream in client order (client c takes draws
         [c n, (c + 1) n) and the generator is left where n_local sequential steps leave it); seeds=[s_0 ..]: client c draws after
-        np.random.seed(s_c), as separate processes would.  The draws of ALL clients are materialised in HBM (8 bytes each: 2.3 GB for ten
-        29.2 M-parameter models), on the device under quantize_encrypt's conditions (MT19937, DEVICE_RNG_MIN).  Mismatched Weights raise
+        np.random.seed(s_c), as separate processes would.  The draws of all clients are materialised in HBM (8 bytes each: 2.3 GB for ten
+        29.2 M-parameter models), on the device under quantize_encrypt's conditions (MT19937, DEVICE_RNG_MIN) -- except on the path
+        "prepared-cohort" of an un-batched job whose rng= generators are all over np.random.Philox: its online launch generates the draws
+        itself (flashe_quantize_combine_cohort_philox_dev: a lane's four values are one Philox block of its client's stream), no draw
+        buffer is allocated, written or read, whatever the model's length (no DEVICE_RNG_MIN: there is no extra launch to amortise), and
+        CohortUpload.draws says "inline" instead of "buffer".  FLASHE_INLINE_DRAWS=0 (read per call) or FLASHE_DEVICE_RNG=0 keeps the
+        buffer; so do a batched job (an element's 5 - 7 values span blocks that neighbouring lanes would each recompute), the staged form
+        and every other generator; the bytes are the same either way.  Mismatched Weights raise
         ValueError and unusable tensors are refused before anything is launched.  Own-stream engines keep the tensors alive until the
         last kernel that reads them has finished."""
         from .engine import DeviceVector
@@ -1601,7 +1642,9 @@ class FlasheCohort(object):
             raise TypeError("FlasheCohort needs the fused client step (fuse=True, a keyed cipher, no location masks)")
         alphas = self._begin_round(plan)
         tables, keep = self._tables(plan, layers, alphas, normalize, degrees if pre is not None else None, pre)
-        du = _cohort_draws(eng, C, plan.n, seeds, rng)
+        # (a prepared un-batched cohort over Philox generators draws inside its online launch: no draw buffer)
+        inline = path == PREPARED_COHORT and _inline_draws(eng, rng, bool(ld.batch), self.compact, C, plan.n)
+        du = None if inline else _cohort_draws(eng, C, plan.n, seeds, rng)
         if self.compact:
             cts = [DeviceVector(eng, plan.n_elems, 1, elem_bytes=4) for _ in range(C)]
             psum = DeviceVector(eng, plan.n_elems, 1, elem_bytes=4)
@@ -1617,7 +1660,10 @@ class FlasheCohort(object):
             srcs = [[t[1] for t in table] for table in tables]
             dts = [[t[4] for t in table] for table in tables]
             launch = self._launch_prepared if prepared else self._launch_chain
-            if not launch(plan, rows, srcs, dts, du, cts, psum, present is not None, **({"cut": True} if path == CUT_CHAIN else {})):
+            if inline and not self._launch_prepared_inline(plan, rows, srcs, dts, rng, cts, psum):
+                # the library declined the inline form: today's form, from the same generators (nothing has been advanced)
+                inline, du = False, _cohort_draws(eng, C, plan.n, seeds, rng)
+            if not inline and not launch(plan, rows, srcs, dts, du, cts, psum, present is not None, **({"cut": True} if path == CUT_CHAIN else {})):
                 # the library declined: the planner's guess was wrong, the result is not -- the same bytes from the fallback form
                 path = PREPARED_STAGED if prepared else STAGED_CHAIN
         if path in (STAGED_CHAIN, PREPARED_STAGED) and plan.n_elems:
@@ -1626,7 +1672,7 @@ class FlasheCohort(object):
         if prepared:
             keep += list(self._masks)
             self._masks = None                         # consumed by this call, whatever the iteration (the reference does not check it either)
-        eng.hold(keep + [du])
+        eng.hold(keep + ([] if du is None else [du]))
         if ld.batch:
             bs = ld.int_bits // _field_bits(q.element_bits, q.num_clients)
             q.shape_list = list(plan.shapes)
@@ -1636,7 +1682,7 @@ class FlasheCohort(object):
         for v in cts:
             v.mark_ready()
         psum.mark_ready()
-        self._last = CohortUpload(cts, psum, path, [self.first_idx + p for p in plan.present])
+        self._last = CohortUpload(cts, psum, path, [self.first_idx + p for p in plan.present], draws="inline" if inline else "buffer")
         return self._last
 
     def _collect(self, weights_list, seeds, present=None, rng=None, degrees=None):
@@ -1825,6 +1871,17 @@ class FlasheCohort(object):
         return ld.cipher.engine.quantize_combine_cohort_dev(plan.n, rows, srcs, dts, q.element_bits, du, [self._masks[p].buf for p in plan.present],
                                                             [v.buf for v in cts], psum.buf, compact=self.compact,
                                                             batch=(plan.n_elems, _field_bits(q.element_bits, q.num_clients)) if ld.batch else None)
+
+    def _launch_prepared_inline(self, plan, rows, srcs, dts, rng, cts, psum):
+        """"prepared-cohort" with the draws generated inside the online launch (_inline_draws): one Generator gives ONE stretch of C n
+        draws, the p-th present client taking [p n, (p + 1) n); a list client p's stretch from rng[p].  The generators get their
+        advanced states back.  False: the library declined, nothing was launched and nothing advanced."""
+        ld = self.lead
+        C, n = len(plan.present), plan.n
+        gens, counts, offsets = (rng, [n] * C, [p * n for p in range(C)]) if isinstance(rng, list) else ([rng], [C * n], [0])
+        return ld.cipher.engine.quantize_combine_cohort_philox_dev(n, rows, srcs, dts, ld.quantizer.element_bits, gens, counts, offsets,
+                                                                   [self._masks[p].buf for p in plan.present], [v.buf for v in cts], psum.buf,
+                                                                   compact=self.compact)
 
     def _launch_staged(self, plan, tables, du, cts, psum, prepared):
         """A quantise (+ batch) pass per client into plaintexts -- un-batched: one value per element, field_bits = int_bits -- then

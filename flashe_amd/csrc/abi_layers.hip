@@ -6,6 +6,8 @@
 #include "layer_tables.h"
 #include "cohort_streams.h"
 #include "cohort_cut.h"
+#include "draw_launch.h"
+#include "philox_stream.h"
 
 #include <algorithm>
 #include <cmath>
@@ -983,13 +985,16 @@ int flashe_quantize_batch_encrypt_cohort_cut_runs_dev(flashe_ctx *ctx, uint32_t 
 // What the three entry points below share: the checks of the chained cohorts (cohort_check's, without cipher indices), the vectors -- every
 // mask and ciphertext given and aligned to its element, the sum apart from all of them and from every source --, cohort_stage's table,
 // sources and stage pass with the mask and ciphertext pointers (and the batched rows) behind it in the same upload, one launch.
+// plans (un-batched only): one draw plan per client, uploaded behind the pointers (flashe_tables::prepared_draws_block) -- the launch
+// generates the draws and u_dev is not read.
 static int quantize_combine_cohort(flashe_ctx *ctx, const char *who, int elem_bytes, int n_clients, uint64_t n_values, uint64_t n_elems, const uint64_t *n_elems_arg,
                                    const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype, int element_bits,
-                                   int field_bits, const double *u_dev, const void *const *mask_dev, void *const *ct_dev, void *sum_out_dev)
+                                   int field_bits, const double *u_dev, const void *const *mask_dev, void *const *ct_dev, void *sum_out_dev,
+                                   const std::vector<flashe_philox::ClientPlan> *plans = nullptr)
 {
     const bool batched = n_elems_arg != nullptr;
     if (n_clients < 1) return fail(ctx, FLASHE_EINVAL, "%s: n_clients must be >= 1", who);
-    if (!src_dev || !mask_dev || !ct_dev || (n_values && !u_dev)) return fail(ctx, FLASHE_EINVAL, "%s: null argument", who);
+    if (!src_dev || !mask_dev || !ct_dev || (n_values && !u_dev && !plans)) return fail(ctx, FLASHE_EINVAL, "%s: null argument", who);
     int rc = check_element_bits(ctx, element_bits);
     if (rc || (rc = check_f64_aligned(ctx, u_dev, "u_dev")) || (rc = check_tensor_layers(ctx, n_values, layers, n_layers, false))) return rc;
     std::vector<uint64_t> extra(2 * static_cast<size_t>(n_clients));
@@ -1015,13 +1020,26 @@ static int quantize_combine_cohort(flashe_ctx *ctx, const char *who, int elem_by
             if (src_dev[i] == sum_out_dev) return fail(ctx, FLASHE_EINVAL, "the sum aliases a source (client %d layer %d)", static_cast<int>(i / n_layers), static_cast<int>(i % n_layers));
     if (elem_bytes == 4 && flashe_ctx_compact_layout(ctx) != 1) return cohort_declined(ctx, who, "prepared compact cohort");
     if (n_elems == 0) return FLASHE_OK;                                    // (an empty model: nothing staged, nothing launched)
+    constexpr size_t plan_words = sizeof(flashe_philox::ClientPlan) / sizeof(uint64_t);
+    if (plans) {
+        extra.resize(flashe_tables::prepared_draws_block(n_clients, plan_words).words);
+        memcpy(extra.data() + 2 * static_cast<size_t>(n_clients), plans->data(), plans->size() * sizeof(flashe_philox::ClientPlan));
+    }
     CohortCodec cc{};
     const char *extra_dev = nullptr;
     if ((rc = cohort_stage(ctx, n_clients, n_values, layers, n_layers, src_dev, src_dtype, element_bits, cc, extra.data(), extra.size() * sizeof(uint64_t), &extra_dev)))
         return rc;
-    const flashe_tables::PreparedBlock at = flashe_tables::prepared_block(n_clients);
     PrepCohort pc{};
     pc.layers = cc.layers; pc.src = cc.src; pc.n_layers = cc.n_layers;
+    if (plans) {
+        const flashe_tables::PreparedDrawsBlock at = flashe_tables::prepared_draws_block(n_clients, plan_words);
+        pc.mask = reinterpret_cast<const void *const *>(extra_dev + at.mask);
+        pc.ct = reinterpret_cast<void *const *>(extra_dev + at.ct);
+        pc.sum = sum_out_dev; pc.n = n_elems; pc.n_values = n_values; pc.n_clients = n_clients;
+        HIP_TRY(ctx, launch_quantize_philox_combine_cohort(ctx->env, pc, reinterpret_cast<const flashe_philox::ClientPlan *>(extra_dev + at.plans), elem_bytes));
+        return FLASHE_OK;
+    }
+    const flashe_tables::PreparedBlock at = flashe_tables::prepared_block(n_clients);
     pc.mask = reinterpret_cast<const void *const *>(extra_dev + at.mask);
     pc.ct = reinterpret_cast<void *const *>(extra_dev + at.ct);
     pc.rows = reinterpret_cast<const uint64_t *>(extra_dev + at.rows);
@@ -1048,6 +1066,53 @@ int flashe_quantize_combine_cohort_u32_dev(flashe_ctx *ctx, int n_clients, uint6
     if (ctx->int_bits > 32) return fail(ctx, FLASHE_EINVAL, "the uint32 layout needs int_bits <= 32, this ctx has %d", ctx->int_bits);
     return quantize_combine_cohort(ctx, "flashe_quantize_combine_cohort_u32_dev", 4, n_clients, n, n, nullptr, layers, n_layers, src_dev, src_dtype, element_bits, 0,
                                    u_dev, reinterpret_cast<const void *const *>(mask_dev), reinterpret_cast<void *const *>(ct_dev), sum_out_dev);
+}
+
+// The un-batched launch with the draws of Philox streams generated inside it.  The segment table's own refusals come first
+// (flashe_philox_random_dev's, without a draw buffer), then the tiling of the clients' stretches, then quantize_combine_cohort's; the
+// segments are advanced only after the launch has been made.
+static int quantize_combine_cohort_philox(flashe_ctx *ctx, const char *who, int elem_bytes, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers,
+                                          const void *const *src_dev, const int32_t *src_dtype, int element_bits, flashe_philox_segment *segments, int n_segments,
+                                          const void *const *mask_dev, void *const *ct_dev, void *sum_out_dev)
+{
+    if (n_clients < 1) return fail(ctx, FLASHE_EINVAL, "%s: n_clients must be >= 1", who);
+    std::vector<flashe_philox::Segment> segs;
+    if (int rc = flashe_draw::read_segments(ctx, who, segments, n_segments, nullptr, flashe_philox::from_c<flashe_philox_segment>, flashe_philox::check_segments,
+                                            "a buffer_pos above 4", segs, false))
+        return rc;
+    std::vector<flashe_philox::ClientPlan> plans;
+    switch (flashe_philox::cohort_plans(segs.data(), n_segments, static_cast<uint64_t>(n_clients), n, plans)) {
+    case flashe_philox::kCohortPlansOk: break;
+    case flashe_philox::kCohortPlansSplitClient: return fail(ctx, FLASHE_EINVAL, "%s: a client's n draws must come from one segment", who);
+    case flashe_philox::kCohortPlansTooMany: return fail(ctx, FLASHE_EINVAL, "%s: n_clients x n draws overflow", who);
+    default: return fail(ctx, FLASHE_EINVAL, "%s: the segments must tile the draws [0, n_clients x n) exactly", who);
+    }
+    if (int rc = quantize_combine_cohort(ctx, who, elem_bytes, n_clients, n, n, nullptr, layers, n_layers, src_dev, src_dtype, element_bits, 0, nullptr, mask_dev, ct_dev,
+                                         sum_out_dev, &plans))
+        return rc;
+    for (int s = 0; n && s < n_segments; s++)
+        flashe_philox::advance(segments[s].key, segments[s].counter, segments[s].buffer_pos, segments[s].buffer, segments[s].n);
+    return FLASHE_OK;
+}
+
+int flashe_quantize_combine_cohort_philox_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
+                                              const int32_t *src_dtype, int element_bits, flashe_philox_segment *segments, int n_segments,
+                                              const uint64_t *const *mask_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev)
+{
+    CHECK_CTX(ctx);
+    return quantize_combine_cohort_philox(ctx, "flashe_quantize_combine_cohort_philox_dev", ctx->limbs == 2 ? 16 : 8, n_clients, n, layers, n_layers, src_dev, src_dtype,
+                                          element_bits, segments, n_segments, reinterpret_cast<const void *const *>(mask_dev), reinterpret_cast<void *const *>(ct_dev),
+                                          sum_out_dev);
+}
+
+int flashe_quantize_combine_cohort_philox_u32_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers,
+                                                  const void *const *src_dev, const int32_t *src_dtype, int element_bits, flashe_philox_segment *segments,
+                                                  int n_segments, const uint32_t *const *mask_dev, uint32_t *const *ct_dev, uint32_t *sum_out_dev)
+{
+    CHECK_CTX(ctx);
+    if (ctx->int_bits > 32) return fail(ctx, FLASHE_EINVAL, "the uint32 layout needs int_bits <= 32, this ctx has %d", ctx->int_bits);
+    return quantize_combine_cohort_philox(ctx, "flashe_quantize_combine_cohort_philox_u32_dev", 4, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits,
+                                          segments, n_segments, reinterpret_cast<const void *const *>(mask_dev), reinterpret_cast<void *const *>(ct_dev), sum_out_dev);
 }
 
 // the BATCHED job over its n_elems elements (any bs = int_bits / field_bits >= 1)

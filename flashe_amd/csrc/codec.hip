@@ -1,5 +1,6 @@
 // gfx950 kernels of the quantise / batch codec either side of the cipher and the host-side descriptors of the fused codec.
 #include "device_common.h"
+#include "philox_stream.h"
 
 namespace flashe {
 
@@ -515,33 +516,76 @@ __device__ __forceinline__ void prep_src4(const void *x, bool f64, uint64_t r, u
     }
 }
 
+// Where a launch's stochastic-rounding draws come from.  BufferDraws: the client-major buffer pc.u an earlier launch wrote -- the bits of
+// four draws are loaded with the group's other streams (load4) and turned into doubles when the client is computed (draws4).
+// PhiloxDraws: np.random.Philox streams generated here (philox_stream.h: client c's draw for value k is word (skip_c + k) % 4 of
+// block(base_c + (skip_c + k) / 4)) from one 56-byte plan per client -- nothing is loaded; a lane's four values are one block where
+// skip_c = 0, else words skip_c .. 3 of one block and 0 .. skip_c - 1 of the next, both computed by the lane (sharing the second with
+// the neighbouring lane is not built); skip_c is uniform over the launch, so that choice is a scalar branch.
+struct BufferDraws {
+    const double *u;
+    uint64_t n_values;
+    __device__ __forceinline__ void load4(int c, uint64_t k0, uint64_t (&ub)[4]) const { prep_ld4(u, static_cast<uint64_t>(c) * n_values + k0, ub); }
+    __device__ __forceinline__ void draws4(int, uint64_t, const uint64_t (&ub)[4], double (&d)[4]) const
+    {
+#pragma unroll
+        for (int t = 0; t < 4; t++) d[t] = __longlong_as_double(static_cast<long long>(ub[t]));
+    }
+    __device__ __forceinline__ double draw(int c, uint64_t k) const
+    {
+        return __longlong_as_double(static_cast<long long>(ld64_nt_g(reinterpret_cast<const uint64_t *>(u) + static_cast<uint64_t>(c) * n_values + k)));
+    }
+};
+using flashe_philox::ClientPlan;
+static_assert(sizeof(ClientPlan) == 56, "the plan rows are 56 bytes");
+struct PhiloxDraws {
+    const ClientPlan *__restrict__ plans;
+    __device__ __forceinline__ void load4(int, uint64_t, uint64_t (&)[4]) const {}
+    __device__ __forceinline__ void draws4(int c, uint64_t k0, const uint64_t (&)[4], double (&d)[4]) const
+    {
+        __asm__ volatile("" ::: "memory");            // (one client's plan in scalar registers at a time)
+        const ClientPlan &p = plans[c];
+        const uint64_t key[2] = {p.key[0], p.key[1]}, base[4] = {p.base[0], p.base[1], p.base[2], p.base[3]};
+        flashe_philox::client_draws4(key, base, p.skip, k0, d);
+    }
+    __device__ __forceinline__ double draw(int c, uint64_t k) const
+    {
+        const ClientPlan &p = plans[c];
+        const uint64_t key[2] = {p.key[0], p.key[1]}, base[4] = {p.base[0], p.base[1], p.base[2], p.base[3]};
+        return flashe_philox::client_draw(key, base, p.skip, k);
+    }
+};
+
 // clients c .. c + G - 1 over the four values k0 .. k0 + 3 of table row `row` (r = k0 - the row's start)
-template <class E, int G>
-__device__ __forceinline__ void prep_cohort_run(const PrepCohort &pc, int row, bool f64, double p0, double p1, double p2, int c, uint64_t k0, uint64_t r,
-                                                E modmask, E (&sum)[4])
+template <class E, int G, class Draws>
+__device__ __forceinline__ void prep_cohort_run(const PrepCohort &pc, const Draws &dr, int row, bool f64, double p0, double p1, double p2, int c, uint64_t k0,
+                                                uint64_t r, E modmask, E (&sum)[4])
 {
     uint64_t raw[G][4], ub[G][4];
     E mk[G][4];
 #pragma unroll
     for (int i = 0; i < G; i++) {
         prep_src4(pc.src[static_cast<size_t>(c + i) * pc.n_layers + row], f64, r, raw[i]);
-        prep_ld4(pc.u, static_cast<uint64_t>(c + i) * pc.n_values + k0, ub[i]);
+        dr.load4(c + i, k0, ub[i]);
         prep_ld4(pc.mask[c + i], k0, mk[i]);
     }
 #pragma unroll
     for (int i = 0; i < G; i++) {
+        double d[4];
+        dr.draws4(c + i, k0, ub[i], d);
         E v[4];
 #pragma unroll
         for (int t = 0; t < 4; t++) {
-            v[t] = (static_cast<E>(cohort_quantize_raw(raw[i][t], f64, p0, p1, p2, __longlong_as_double(static_cast<long long>(ub[i][t])))) + mk[i][t]) & modmask;
+            v[t] = (static_cast<E>(cohort_quantize_raw(raw[i][t], f64, p0, p1, p2, d[t])) + mk[i][t]) & modmask;
             sum[t] += v[t];
         }
         prep_st4(pc.ct[c + i], k0, v);
     }
 }
 
-template <class E, int G>
-__global__ __launch_bounds__(kStreamThreads) void quantize_combine_cohort_kernel(const PrepCohort pc, E modmask)
+// the un-batched launch over either source of draws: the layer of a lane's run of four, the run for the clients in groups of G, and
+// value by value for a run across a layer boundary or the model's tail
+template <class E, int G, class Draws> __device__ __forceinline__ void prep_cohort_body(const PrepCohort &pc, const Draws &dr, E modmask)
 {
     const uint64_t n = pc.n, runs = (n + 3) / 4;
     const int C = pc.n_clients;
@@ -560,8 +604,8 @@ __global__ __launch_bounds__(kStreamThreads) void quantize_combine_cohort_kernel
             const uint64_t r = k0 - L->start;
             E sum[4] = {0, 0, 0, 0};
             int c = 0;
-            for (; c + G <= C; c += G) prep_cohort_run<E, G>(pc, lo, f64, p0, p1, p2, c, k0, r, modmask, sum);
-            for (; c < C; c++) prep_cohort_run<E, 1>(pc, lo, f64, p0, p1, p2, c, k0, r, modmask, sum);
+            for (; c + G <= C; c += G) prep_cohort_run<E, G>(pc, dr, lo, f64, p0, p1, p2, c, k0, r, modmask, sum);
+            for (; c < C; c++) prep_cohort_run<E, 1>(pc, dr, lo, f64, p0, p1, p2, c, k0, r, modmask, sum);
             if (pc.sum) {
 #pragma unroll
                 for (int t = 0; t < 4; t++) sum[t] &= modmask;
@@ -577,7 +621,7 @@ __global__ __launch_bounds__(kStreamThreads) void quantize_combine_cohort_kernel
             const bool f64 = L->x_is_f64 != 0;
             E sum = 0;
             for (int c = 0; c < C; c++) {
-                const double u = __longlong_as_double(static_cast<long long>(ld64_nt_g(reinterpret_cast<const uint64_t *>(pc.u) + static_cast<uint64_t>(c) * pc.n_values + k)));
+                const double u = dr.draw(c, k);
                 const uint64_t q = cohort_quantize_raw(cohort_load(pc.src[static_cast<size_t>(c) * pc.n_layers + lo], f64, k - L->start), f64, L->p0, L->p1, L->p2, u);
                 const E v = (static_cast<E>(q) + prep_ld<E>(pc.mask[c], k)) & modmask;
                 prep_st<E>(pc.ct[c], k, v);
@@ -586,6 +630,21 @@ __global__ __launch_bounds__(kStreamThreads) void quantize_combine_cohort_kernel
             if (pc.sum) prep_st<E>(pc.sum, k, sum & modmask);
         }
     }
+}
+
+template <class E, int G>
+__global__ __launch_bounds__(kStreamThreads) void quantize_combine_cohort_kernel(const PrepCohort pc, E modmask)
+{
+    prep_cohort_body<E, G>(pc, BufferDraws{pc.u, pc.n_values}, modmask);
+}
+
+// the same launch with the draws generated inside it (flashe_quantize_combine_cohort_philox*_dev): no draw buffer is written by an earlier
+// launch and none is read here -- 16 bytes less per value and client, one launch less.  pc.u is not read.  The batched kernel below has
+// no such form: an element's 5 - 7 values span 2 - 3 blocks that neighbouring lanes would each recompute; it reads the draw buffer.
+template <class E, int G>
+__global__ __launch_bounds__(kStreamThreads) void quantize_philox_combine_cohort_kernel(const PrepCohort pc, const ClientPlan *__restrict__ plans, E modmask)
+{
+    prep_cohort_body<E, G>(pc, PhiloxDraws{plans}, modmask);
 }
 
 // The batched job: a lane owns one batched element of every client -- quantize_batch_model_kernel's plaintext (every layer padded to whole
@@ -673,6 +732,26 @@ hipError_t launch_quantize_combine_cohort(const LaunchEnv &env, const PrepCohort
     if (elem_bytes == 4) return env.b > 32 ? hipErrorInvalidValue : launch_prep_cohort<uint32_t>(env, pc, batched, group, static_cast<uint32_t>(lo));
     if (elem_bytes == 8) return env.b > 64 ? hipErrorInvalidValue : launch_prep_cohort<uint64_t>(env, pc, batched, group, lo);
     if (elem_bytes == 16) return env.b <= 64 ? hipErrorInvalidValue : launch_prep_cohort<u128>(env, pc, batched, group, (static_cast<u128>(hi) << 64) | lo);
+    return hipErrorInvalidValue;
+}
+
+// ---- the un-batched launch with the draws generated inside it (quantize_philox_combine_cohort_kernel above) ----
+template <class E> static hipError_t launch_prep_philox(const LaunchEnv &env, const PrepCohort &pc, const ClientPlan *plans, E modmask)
+{
+    const dim3 g(stream_grid(env, (pc.n + 3) / 4)), t(kStreamThreads);
+    hipLaunchKernelGGL((quantize_philox_combine_cohort_kernel<E, kPrepCohortGroup>), g, t, 0, env.stream, pc, plans, modmask);
+    return hipGetLastError();
+}
+
+hipError_t launch_quantize_philox_combine_cohort(const LaunchEnv &env, const PrepCohort &pc, const ClientPlan *plans, int elem_bytes)
+{
+    if (pc.n == 0 || pc.n_clients == 0) return hipSuccess;
+    if (pc.n_layers < 1 || !plans) return hipErrorInvalidValue;
+    uint64_t lo, hi;
+    masks_of(env.b, &lo, &hi);
+    if (elem_bytes == 4) return env.b > 32 ? hipErrorInvalidValue : launch_prep_philox<uint32_t>(env, pc, plans, static_cast<uint32_t>(lo));
+    if (elem_bytes == 8) return env.b > 64 ? hipErrorInvalidValue : launch_prep_philox<uint64_t>(env, pc, plans, lo);
+    if (elem_bytes == 16) return env.b <= 64 ? hipErrorInvalidValue : launch_prep_philox<u128>(env, pc, plans, (static_cast<u128>(hi) << 64) | lo);
     return hipErrorInvalidValue;
 }
 

@@ -47,10 +47,11 @@ int launch_plans(flashe_ctx *ctx, const std::vector<Plan> &plans, uint64_t tiles
 }
 
 // The front of the entry point `name`: the caller's table as the kind's segments, refused (FLASHE_EINVAL, the message set) for its count, a null table,
-// a graph being captured, what the kind's check_segments finds (`own`: its words for kSegmentsOwn) and, when there is anything to draw, for u_dev.
+// a graph being captured, what the kind's check_segments finds (`own`: its words for kSegmentsOwn) and, when there is anything to draw, for u_dev
+// (with_out = false: a call that writes no draw buffer).
 template <class CSegment, class Segment>
 int read_segments(flashe_ctx *ctx, const char *name, const CSegment *segments, int n_segments, const double *u_dev, void (*to_segment)(const CSegment &, Segment &),
-                  SegmentsStatus (*check_segments)(const Segment *, int, int), const char *own, std::vector<Segment> &segs)
+                  SegmentsStatus (*check_segments)(const Segment *, int, int), const char *own, std::vector<Segment> &segs, bool with_out = true)
 {
     using flashe_host::fail;
     if (n_segments < 0 || n_segments > kMaxSegments) return fail(ctx, FLASHE_EINVAL, "%s: %d segments, a launch holds 0 .. %d", name, n_segments, kMaxSegments);
@@ -69,7 +70,7 @@ int read_segments(flashe_ctx *ctx, const char *name, const CSegment *segments, i
     case kSegmentsOverlap: return fail(ctx, FLASHE_EINVAL, "%s: two segments' output ranges overlap", name);
     default: return fail(ctx, FLASHE_EINVAL, "%s: bad segment table", name);
     }
-    if (any && (!u_dev || (reinterpret_cast<uintptr_t>(u_dev) & 7u))) return fail(ctx, FLASHE_EINVAL, "%s: u_dev must be an 8-byte aligned device pointer", name);
+    if (with_out && any && (!u_dev || (reinterpret_cast<uintptr_t>(u_dev) & 7u))) return fail(ctx, FLASHE_EINVAL, "%s: u_dev must be an 8-byte aligned device pointer", name);
     return FLASHE_OK;
 }
 

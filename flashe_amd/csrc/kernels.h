@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+namespace flashe_philox { struct ClientPlan; }        // (philox_stream.h)
+
 namespace flashe {
 
 // AES-256 expanded key, 60 big-endian words; passed to kernels by value (lands in SGPRs).
@@ -384,6 +386,9 @@ struct PrepCohort {
 };
 // elem_bytes = what masks, ciphertexts and sum are made of: 4 (uint32, int_bits <= 32, un-batched), 8 (one limb, int_bits <= 64) or 16
 hipError_t launch_quantize_combine_cohort(const LaunchEnv &env, const PrepCohort &pc, int elem_bytes, bool batched);
+// The un-batched launch with the draws of np.random.Philox streams generated inside it: pc.u is not read; plans = a DEVICE table of one
+// flashe_philox::ClientPlan (philox_stream.h) per client, client c's draw for value k = word (skip + k) % 4 of block(base + (skip + k) / 4).
+hipError_t launch_quantize_philox_combine_cohort(const LaunchEnv &env, const PrepCohort &pc, const flashe_philox::ClientPlan *plans, int elem_bytes);
 hipError_t launch_unbatch(const LaunchEnv &env, uint64_t nb, const uint64_t *in_dev, int field_bits, uint64_t *out_dev);
 
 // Caller-owned tensors either side of the model-wide codec (tensors.hip).  dtype / flags as in flashe_tensor_layer (include/flashe.h);

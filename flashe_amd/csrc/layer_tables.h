@@ -84,6 +84,14 @@ inline PreparedBlock prepared_block(int n_clients, size_t n_rows = 0)
     const size_t c = static_cast<size_t>(n_clients);
     return PreparedBlock{0, c * 8, 2 * c * 8, 2 * c + 2 * n_rows};
 }
+// The block of the prepared cohort launch that generates its own draws (un-batched only): the n_clients mask pointers, the n_clients
+// ciphertext pointers, then one draw plan of plan_words 8-byte words per client.
+struct PreparedDrawsBlock { size_t mask, ct, plans, words; };
+inline PreparedDrawsBlock prepared_draws_block(int n_clients, size_t plan_words)
+{
+    const size_t c = static_cast<size_t>(n_clients);
+    return PreparedDrawsBlock{0, c * 8, 2 * c * 8, 2 * c + plan_words * c};
+}
 // entries of a cohort's n_clients x n_layers source table
 inline size_t cohort_sources(int n_clients, int n_layers) { return static_cast<size_t>(n_clients) * static_cast<size_t>(n_layers); }
 

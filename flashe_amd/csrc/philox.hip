@@ -77,13 +77,6 @@ __global__ __launch_bounds__(flashe::kStreamThreads) void philox_random_table_ke
     philox_tiles(plans, n_plans, tiles, out);
 }
 
-void to_segment(const flashe_philox_segment &s, flashe_philox::Segment &o)
-{
-    o.key[0] = s.key[0]; o.key[1] = s.key[1];
-    for (int w = 0; w < 4; w++) o.counter[w] = s.counter[w];
-    o.buffer_pos = s.buffer_pos; o.n = s.n; o.offset = s.offset;
-}
-
 }  // namespace
 
 extern "C" int flashe_philox_block(const uint64_t counter[4], const uint64_t key[2], uint64_t words[4])
@@ -113,7 +106,7 @@ extern "C" int flashe_philox_random_dev(flashe_ctx *ctx, flashe_philox_segment *
 {
     CHECK_CTX(ctx);
     std::vector<flashe_philox::Segment> segs;
-    if (int rc = flashe_draw::read_segments(ctx, "flashe_philox_random_dev", segments, n_segments, u_dev, to_segment, flashe_philox::check_segments, "a buffer_pos above 4", segs))
+    if (int rc = flashe_draw::read_segments(ctx, "flashe_philox_random_dev", segments, n_segments, u_dev, flashe_philox::from_c<flashe_philox_segment>, flashe_philox::check_segments, "a buffer_pos above 4", segs))
         return rc;
     std::vector<Plan> plans;
     const uint64_t tiles = flashe_philox::plan_segments(segs.data(), n_segments, plans);

@@ -121,4 +121,94 @@ inline uint64_t plan_segments(const Segment *segs, int n_segments, std::vector<P
     return tiles;
 }
 
+// A caller's segment struct (flashe_philox_segment's fields) as a Segment.
+template <class CSegment> inline void from_c(const CSegment &s, Segment &o)
+{
+    o.key[0] = s.key[0]; o.key[1] = s.key[1];
+    for (int w = 0; w < 4; w++) o.counter[w] = s.counter[w];
+    o.buffer_pos = s.buffer_pos; o.n = s.n; o.offset = s.offset;
+}
+
+// ---- the draws of a cohort generated inside the launch that consumes them (codec.hip's quantize_philox_combine_cohort_kernel) ----
+// One plan per client, 56 bytes: the client's draw for its value k is word (skip + k) % 4 of block(base + (skip + k) / 4), skip < 4.
+struct ClientPlan { uint64_t key[2]; uint64_t base[4]; uint32_t skip, reserved; };
+
+// The plan of the stretch that starts at draw `first` of a segment's state.
+inline ClientPlan client_plan(const Segment &s, uint64_t first)
+{
+    ClientPlan p{};
+    p.key[0] = s.key[0]; p.key[1] = s.key[1];
+    position(s.counter, s.buffer_pos, first, p.base, p.skip);
+    return p;
+}
+
+// The draw of value k under a plan, one draw at a time (the launch's value-by-value path; its runs of four take whole blocks).
+FLASHE_HD double client_draw(const uint64_t key[2], const uint64_t base[4], uint32_t skip, uint64_t k)
+{
+    const uint64_t v = skip + k;
+    uint64_t at[4], w[4];
+    counter_add(base, v >> 2, at);
+    block(at, key, w);
+    const uint32_t i = static_cast<uint32_t>(v & 3);
+    return to_double(i == 0 ? w[0] : i == 1 ? w[1] : i == 2 ? w[2] : w[3]);
+}
+
+// The four draws of values k0 .. k0 + 3 (k0 % 4 == 0) under a plan: one block where skip is 0, else the tail of one and the head of the next.
+FLASHE_HD void client_draws4(const uint64_t key[2], const uint64_t base[4], uint32_t skip, uint64_t k0, double d[4])
+{
+    uint64_t at[4], w[8];
+    counter_add(base, k0 >> 2, at);
+    block(at, key, w);
+    if (skip) {
+        uint64_t nx[4], again[2] = {key[0], key[1]};
+        counter_add(at, 1, nx);
+#if defined(__HIP_DEVICE_COMPILE__)
+        // (the key is uniform over the launch: taken as new here, so that the round keys of the first block are not kept in scalar
+        // registers for the second -- the kernels that call this hold no spare ones)
+        __asm__ volatile("" : "+s"(again[0]), "+s"(again[1]));
+#endif
+        block(nx, again, w + 4);
+    } else {
+        w[4] = w[5] = w[6] = 0;
+    }
+FLASHE_UNROLL
+    for (int t = 0; t < 4; t++) d[t] = to_double(skip == 0 ? w[t] : skip == 1 ? w[t + 1] : skip == 2 ? w[t + 2] : w[t + 3]);
+}
+
+enum CohortPlansStatus { kCohortPlansOk = 0, kCohortPlansTooMany = 1, kCohortPlansNotTiled = 2, kCohortPlansSplitClient = 3 };
+
+// The plans of n_clients clients of n draws each from checked segments (check_segments: no overlap, nothing overflows): the non-empty
+// segments must tile the client-major draws [0, n_clients n) exactly -- no gap, nothing beyond (kCohortPlansNotTiled; an overlap is
+// check_segments' to find) -- and every client's stretch [c n, (c + 1) n) must lie inside ONE segment, since a client has one plan
+// (kCohortPlansSplitClient).  kCohortPlansTooMany: n_clients n above kMaxDraws.  n = 0: every segment must be empty; no plans.
+inline CohortPlansStatus cohort_plans(const Segment *segs, int n_segments, uint64_t n_clients, uint64_t n, std::vector<ClientPlan> &plans)
+{
+    plans.clear();
+    if (n && n_clients > kMaxDraws / n) return kCohortPlansTooMany;
+    const uint64_t total = n_clients * n;
+    std::vector<int> order;
+    for (int s = 0; s < n_segments; s++)
+        if (segs[s].n) order.push_back(s);
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return segs[a].offset < segs[b].offset; });
+    uint64_t at = 0;
+    for (const int s : order) {
+        if (segs[s].offset != at) return kCohortPlansNotTiled;
+        at += segs[s].n;
+    }
+    if (at != total) return kCohortPlansNotTiled;
+    if (!n) return kCohortPlansOk;
+    size_t i = 0;
+    for (uint64_t c = 0; c < n_clients; c++) {
+        const uint64_t first = c * n;
+        while (segs[order[i]].offset + segs[order[i]].n <= first) i++;
+        const Segment &s = segs[order[i]];
+        if (first + n > s.offset + s.n) {
+            plans.clear();
+            return kCohortPlansSplitClient;
+        }
+        plans.push_back(client_plan(s, first - s.offset));
+    }
+    return kCohortPlansOk;
+}
+
 }  // namespace flashe_philox

@@ -91,7 +91,9 @@ typedef struct flashe_ctx flashe_ctx;
  *      flashe_aggregate_packed_elems_dev / flashe_aggregate_packed_elems_u32_dev (the arbiter's packed reduce computed on unpacked
  *      ciphertext vectors in one pass); flashe_cohort_cut_pieces + flashe_quantize_encrypt_cohort_cut_runs_dev /
  *      flashe_quantize_encrypt_cohort_cut_runs_u32_dev / flashe_quantize_batch_encrypt_cohort_cut_runs_dev (the cut launch for a round in
- *      which clients dropped out -- every gap is a cut -- and for a batched job) */
+ *      which clients dropped out -- every gap is a cut -- and for a batched job); flashe_quantize_combine_cohort_philox_dev /
+ *      flashe_quantize_combine_cohort_philox_u32_dev (a precompute job's cohort online with the draws of np.random.Philox streams
+ *      generated inside the launch: no draw buffer) */
 #define FLASHE_ABI_VERSION 4
 int flashe_abi_version(void);
 int flashe_device_count(int *count);
@@ -897,6 +899,27 @@ int flashe_quantize_combine_cohort_u32_dev(flashe_ctx *ctx, int n_clients, uint6
 int flashe_quantize_batch_combine_cohort_dev(flashe_ctx *ctx, int n_clients, uint64_t n_values, uint64_t n_elems, const flashe_tensor_layer *layers,
                                              int n_layers, const void *const *src_dev, const int32_t *src_dtype, int element_bits, int field_bits,
                                              const double *u_dev, const uint64_t *const *mask_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev);
+struct flashe_philox_segment;                   /* (defined with flashe_philox_random_dev below) */
+/* The un-batched online step with the draws of np.random.Philox streams generated INSIDE the launch (new): the arguments of
+ * flashe_quantize_combine_cohort_dev / _u32_dev with u_dev replaced by a segment table of flashe_philox_random_dev's type and meaning
+ * (declared below) -- segment s gives n draws of its generator state to the client-major draw positions [offset, offset + n), client c
+ * rounding its value k with draw c * n + k.  One segment covers all clients of a shared generator, one segment per client a list of
+ * generators.  No draw buffer exists: a lane's four values are one Philox4x64 block of its client's stream, so the launch moves 16 bytes
+ * less per value and client than flashe_philox_random_dev + flashe_quantize_combine_cohort_dev, whose ciphertexts and sum it reproduces bit
+ * for bit.  The non-empty segments must tile [0, n_clients * n) exactly, and every client's n draws must lie in one segment;
+ * FLASHE_EINVAL otherwise, for everything flashe_philox_random_dev refuses in a table (a buffer_pos above 4, more than 128 segments,
+ * overflowing or overlapping ranges, a graph being captured) and for everything flashe_quantize_combine_cohort_dev / _u32_dev refuse;
+ * FLASHE_ENOTSUP as there.  On success every segment is advanced in place as flashe_philox_random_dev advances it; on any refusal
+ * nothing is advanced, staged or launched.  n = 0 (every segment empty): FLASHE_OK, nothing launched or advanced.  A batched job has
+ * no such form (an element's 5 - 7 values span blocks that neighbouring lanes would each recompute): it reads a draw buffer. */
+int flashe_quantize_combine_cohort_philox_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers,
+                                              const void *const *src_dev, const int32_t *src_dtype, int element_bits,
+                                              struct flashe_philox_segment *segments, int n_segments, const uint64_t *const *mask_dev,
+                                              uint64_t *const *ct_dev, uint64_t *sum_out_dev);
+int flashe_quantize_combine_cohort_philox_u32_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers,
+                                                  const void *const *src_dev, const int32_t *src_dtype, int element_bits,
+                                                  struct flashe_philox_segment *segments, int n_segments, const uint32_t *const *mask_dev,
+                                                  uint32_t *const *ct_dev, uint32_t *sum_out_dev);
 /* The codec back end over caller-held vectors (new), jzf_quantize.py:102-107: out[k] = unquantize((in[k] + add[k] - minus[k]) mod 2^b)
  * as float64 for the n elements of a flattened model, one memory-bound pass; add_dev / minus_dev may be NULL (zeros).  With in = a
  * cohort's sum and add = its decrypt mask this is the cohort's decrypt_unquantize. */
