@@ -273,6 +273,9 @@ _SIGNATURES = {
     "flashe_quantize_batch_combine_cohort_dev": (c_int, [c_vp, c_int, c_u64, c_u64, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp),
                                                          ctypes.POINTER(ctypes.c_int32), c_int, c_int, c_vp, ctypes.POINTER(c_vp),
                                                          ctypes.POINTER(c_vp), c_vp]),
+    "flashe_quantize_batch_combine_cohort_philox_dev": (c_int, [c_vp, c_int, c_u64, c_u64, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp),
+                                                                ctypes.POINTER(ctypes.c_int32), c_int, c_int, ctypes.POINTER(PhiloxSegment), c_int,
+                                                                ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
     "flashe_combine_unquantize_model_dev": (c_int, [c_vp, c_u64, c_vp, c_vp, c_vp, ctypes.POINTER(CodecLayer), c_int, c_int, c_int, c_vp]),
     "flashe_combine_unbatch_unquantize_model_dev": (c_int, [c_vp, ctypes.POINTER(BatchLayer), c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_u64, c_vp]),
     "flashe_decrypt_prepared_unquantize_model_dev": (c_int, [c_vp, c_u32, c_u32p, c_int, c_u32p, c_int, c_u64, c_u32, c_vp, ctypes.POINTER(CodecLayer),

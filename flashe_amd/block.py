@@ -326,13 +326,33 @@ def _draws_aligned(rng, C, n):
     return int(rng.bit_generator.state["buffer_pos"]) in (0, 4) and (n % 4 == 0 or C <= 1)
 
 
-def _inline_draws(eng, rng, batched, compact=False, C=1, n=0):
+# The same rule for a BATCHED job that asked for the inline form (FlasheCohort(inline_draws=True)): (values per element, ONE Generator
+# shared by the clients?, every client's stream starts at a Philox block?) -> inline by default.  A class that is not listed -- one that
+# lost the measurement (tests/perf/prepared_cohort_batched_inline_draws.py) or was not measured -- keeps the buffer.  Measured
+# (profiles/r34_prepared_cohort_batched_inline_draws.log): one shared generator at a misaligned length -- the buffer form's draw launch
+# is slow there -- wins at six and seven values per element by 34 - 82 % against spreads of 6 - 11 %; a list of fresh generators
+# (aligned) loses or ties (A / B 0.67 - 1.04: the launch is bound by its Philox rounds), and five values per element lost both ways
+# on a hundred small models (A / B 0.25 - 0.38).  Not measured, so not listed: a list of generators at odd positions, one shared
+# generator whose clients all start at a block, and every run-time bs.
+_INLINE_BATCHED_DEFAULT = {(6, True, False): True, (7, True, False): True}
+
+
+def _batched_draws_class(rng, bs, C, n):
+    """The key of a batched round in _INLINE_BATCHED_DEFAULT."""
+    return (int(bs), not isinstance(rng, list), _draws_aligned(rng, C, n))
+
+
+def _inline_draws(eng, rng, batched, compact=False, C=1, n=0, inline_batched=False, bs=0):
     """Does a "prepared-cohort" round generate its draws INSIDE the online launch (eng.quantize_combine_cohort_philox_dev: no draw
-    buffer, one launch less)?  An un-batched job, every (present) client's Generator over np.random.Philox, FLASHE_DEVICE_RNG not 0, an
-    engine that has the call, and FLASHE_INLINE_DRAWS (the A/B switch, read per call): 0 never, 1 always, unset the default of the
-    round's shape class (_INLINE_DRAWS_DEFAULT).  No DEVICE_RNG_MIN threshold: there is no extra launch to amortise.  A batched job
-    reads the draw buffer (an element's 5 - 7 values span Philox blocks that neighbouring lanes would each recompute)."""
-    if batched or rng is None or not hasattr(eng, "quantize_combine_cohort_philox_dev"):
+    buffer, one launch less)?  Every (present) client's Generator over np.random.Philox, FLASHE_DEVICE_RNG not 0, an engine that has the
+    call, and FLASHE_INLINE_DRAWS (the A/B switch, read per call): 0 never, 1 always, unset the default of the round's shape class
+    (_INLINE_DRAWS_DEFAULT).  No DEVICE_RNG_MIN threshold: there is no extra launch to amortise.  A batched job (bs values per element, n
+    values per client) reads the draw buffer unless the cohort asked for the inline form (inline_batched: FlasheCohort(inline_draws=True))
+    and the engine has eng.quantize_batch_combine_cohort_philox_dev -- a lane of that launch owns four elements, so that no Philox
+    block is computed twice; its class defaults are _INLINE_BATCHED_DEFAULT's."""
+    if rng is None or not hasattr(eng, "quantize_batch_combine_cohort_philox_dev" if batched else "quantize_combine_cohort_philox_dev"):
+        return False
+    if batched and not inline_batched:
         return False
     switch = os.environ.get("FLASHE_INLINE_DRAWS", "")
     if os.environ.get("FLASHE_DEVICE_RNG", "1") == "0" or switch == "0":
@@ -340,7 +360,11 @@ def _inline_draws(eng, rng, batched, compact=False, C=1, n=0):
     gens = rng if isinstance(rng, list) else [rng]
     if len(gens) > eng.PHILOX_MAX_SEGMENTS or not all(isinstance(g.bit_generator, np.random.Philox) for g in gens):
         return False
-    return switch == "1" or _INLINE_DRAWS_DEFAULT[(bool(compact), _draws_aligned(rng, C, n))]
+    if switch == "1":
+        return True
+    if batched:
+        return _INLINE_BATCHED_DEFAULT.get(_batched_draws_class(rng, bs, C, n), False)
+    return _INLINE_DRAWS_DEFAULT[(bool(compact), _draws_aligned(rng, C, n))]
 
 
 class FlasheClient(object):
@@ -1492,12 +1516,13 @@ class FlasheCohort(object):
     chain of n_local + 1 streams, held by the cohort; the next quantize_encrypt is then ONE online launch with no AES ("prepared-cohort")
     at any int_bits, batched or not, compact or not.  Without that call the clients' own masks run "per-client" as before.  Un-batched and
     with rng= generators over np.random.Philox that launch also generates the stochastic-rounding draws (CohortUpload.draws == "inline":
-    no draw buffer in HBM); every other cohort materialises its draws first ("buffer").
+    no draw buffer in HBM); every other cohort materialises its draws first ("buffer").  inline_draws=True (opt-in, as compact= and cut=
+    are) lets a BATCHED precompute job do the same in the shape classes where the measurement says it wins.
     A DENSE job's arbiter adds the clients' bit-packed models as one integer (jzf_aggregator.py:406-419); CohortUpload.partial_sum is
     the element-wise sum.  aggregate_packed() is that packed reduce of an upload, one pass over the ciphertexts where they lie, and
     decrypt_unquantize(packed=True) decrypts it, so that a cohort which simulates a dense job returns the global model the job produces."""
 
-    def __init__(self, args, first_idx, n_local, num_clients, prp_seed, device=0, stream=None, compact=False, cut=False):
+    def __init__(self, args, first_idx, n_local, num_clients, prp_seed, device=0, stream=None, compact=False, cut=False, inline_draws=False):
         if n_local < 1 or first_idx < 0 or first_idx + n_local > num_clients:
             raise ValueError(f"clients {first_idx} .. {first_idx + n_local - 1} are not clients of a federation of {num_clients}")
         self.first_idx, self.n_local, self.num_clients = int(first_idx), int(n_local), int(num_clients)
@@ -1507,6 +1532,7 @@ class FlasheCohort(object):
         if isinstance(cut, str) and cut != "any" or not isinstance(cut, str) and cut not in (True, False):
             raise ValueError(f"cut: True, False or \"any\", got {cut!r}")
         self.cut = bool(cut)                           # a short cohort runs "cut-chain" where the engine has the cut launch
+        self.inline_draws = bool(inline_draws)         # a BATCHED "prepared-cohort" round may draw inside its online launch (_inline_draws)
         self.cut_any = cut == "any"                    # ... gapped or batched too, where the engine has the launches that take indices
         self._cut_scratch = None                       # the cut launch's scratch, kept from round to round
         if self.compact:
@@ -1621,8 +1647,11 @@ class FlasheCohort(object):
         itself (flashe_quantize_combine_cohort_philox_dev: a lane's four values are one Philox block of its client's stream), no draw
         buffer is allocated, written or read, whatever the model's length (no DEVICE_RNG_MIN: there is no extra launch to amortise), and
         CohortUpload.draws says "inline" instead of "buffer".  FLASHE_INLINE_DRAWS=0 (read per call) or FLASHE_DEVICE_RNG=0 keeps the
-        buffer; so do a batched job (an element's 5 - 7 values span blocks that neighbouring lanes would each recompute), the staged form
-        and every other generator; the bytes are the same either way.  Mismatched Weights raise
+        buffer; so do the staged form and every other generator; the bytes are the same either way.  A BATCHED job keeps the buffer
+        unless the cohort was made with inline_draws=True: its online launch then generates the draws too
+        (flashe_quantize_batch_combine_cohort_philox_dev: a lane owns four elements and computes each Philox block of their 4 bs values
+        once) in the shape classes where that form won its measurement (_INLINE_BATCHED_DEFAULT), and in every class under
+        FLASHE_INLINE_DRAWS=1.  Mismatched Weights raise
         ValueError and unusable tensors are refused before anything is launched.  Own-stream engines keep the tensors alive until the
         last kernel that reads them has finished."""
         from .engine import DeviceVector
@@ -1642,8 +1671,9 @@ class FlasheCohort(object):
             raise TypeError("FlasheCohort needs the fused client step (fuse=True, a keyed cipher, no location masks)")
         alphas = self._begin_round(plan)
         tables, keep = self._tables(plan, layers, alphas, normalize, degrees if pre is not None else None, pre)
-        # (a prepared un-batched cohort over Philox generators draws inside its online launch: no draw buffer)
-        inline = path == PREPARED_COHORT and _inline_draws(eng, rng, bool(ld.batch), self.compact, C, plan.n)
+        # (a prepared cohort over Philox generators draws inside its online launch: no draw buffer; a batched one where it asked to)
+        inline = path == PREPARED_COHORT and _inline_draws(eng, rng, bool(ld.batch), self.compact, C, plan.n, inline_batched=self.inline_draws,
+                                                           bs=ld.int_bits // _field_bits(q.element_bits, q.num_clients) if ld.batch else 0)
         du = None if inline else _cohort_draws(eng, C, plan.n, seeds, rng)
         if self.compact:
             cts = [DeviceVector(eng, plan.n_elems, 1, elem_bytes=4) for _ in range(C)]
@@ -1879,9 +1909,11 @@ class FlasheCohort(object):
         ld = self.lead
         C, n = len(plan.present), plan.n
         gens, counts, offsets = (rng, [n] * C, [p * n for p in range(C)]) if isinstance(rng, list) else ([rng], [C * n], [0])
-        return ld.cipher.engine.quantize_combine_cohort_philox_dev(n, rows, srcs, dts, ld.quantizer.element_bits, gens, counts, offsets,
+        q = ld.quantizer
+        return ld.cipher.engine.quantize_combine_cohort_philox_dev(n, rows, srcs, dts, q.element_bits, gens, counts, offsets,
                                                                    [self._masks[p].buf for p in plan.present], [v.buf for v in cts], psum.buf,
-                                                                   compact=self.compact)
+                                                                   compact=self.compact,
+                                                                   **({"batch": (plan.n_elems, _field_bits(q.element_bits, q.num_clients))} if ld.batch else {}))
 
     def _launch_staged(self, plan, tables, du, cts, psum, prepared):
         """A quantise (+ batch) pass per client into plaintexts -- un-batched: one value per element, field_bits = int_bits -- then

@@ -985,8 +985,8 @@ int flashe_quantize_batch_encrypt_cohort_cut_runs_dev(flashe_ctx *ctx, uint32_t 
 // What the three entry points below share: the checks of the chained cohorts (cohort_check's, without cipher indices), the vectors -- every
 // mask and ciphertext given and aligned to its element, the sum apart from all of them and from every source --, cohort_stage's table,
 // sources and stage pass with the mask and ciphertext pointers (and the batched rows) behind it in the same upload, one launch.
-// plans (un-batched only): one draw plan per client, uploaded behind the pointers (flashe_tables::prepared_draws_block) -- the launch
-// generates the draws and u_dev is not read.
+// plans: one draw plan per client, uploaded behind the pointers (flashe_tables::prepared_draws_block; batched: behind the rows and the
+// rows' first groups, prepared_batch_draws_block) -- the launch generates the draws and u_dev is not read.
 static int quantize_combine_cohort(flashe_ctx *ctx, const char *who, int elem_bytes, int n_clients, uint64_t n_values, uint64_t n_elems, const uint64_t *n_elems_arg,
                                    const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype, int element_bits,
                                    int field_bits, const double *u_dev, const void *const *mask_dev, void *const *ct_dev, void *sum_out_dev,
@@ -1021,7 +1021,14 @@ static int quantize_combine_cohort(flashe_ctx *ctx, const char *who, int elem_by
     if (elem_bytes == 4 && flashe_ctx_compact_layout(ctx) != 1) return cohort_declined(ctx, who, "prepared compact cohort");
     if (n_elems == 0) return FLASHE_OK;                                    // (an empty model: nothing staged, nothing launched)
     constexpr size_t plan_words = sizeof(flashe_philox::ClientPlan) / sizeof(uint64_t);
-    if (plans) {
+    const size_t n_rows = extra.size() / 2 - static_cast<size_t>(n_clients);                  // (batched: two words per row so far)
+    uint64_t n_groups = 0;
+    if (plans && batched) {
+        const flashe_tables::PreparedBatchDrawsBlock at = flashe_tables::prepared_batch_draws_block(n_clients, n_rows, plan_words);
+        extra.resize(at.words);
+        n_groups = flashe_tables::batched_groups(extra.data() + at.rows / 8, n_rows, bs, extra.data() + at.groups / 8);
+        memcpy(extra.data() + at.plans / 8, plans->data(), plans->size() * sizeof(flashe_philox::ClientPlan));
+    } else if (plans) {
         extra.resize(flashe_tables::prepared_draws_block(n_clients, plan_words).words);
         memcpy(extra.data() + 2 * static_cast<size_t>(n_clients), plans->data(), plans->size() * sizeof(flashe_philox::ClientPlan));
     }
@@ -1031,6 +1038,16 @@ static int quantize_combine_cohort(flashe_ctx *ctx, const char *who, int elem_by
         return rc;
     PrepCohort pc{};
     pc.layers = cc.layers; pc.src = cc.src; pc.n_layers = cc.n_layers;
+    if (plans && batched) {
+        const flashe_tables::PreparedBatchDrawsBlock at = flashe_tables::prepared_batch_draws_block(n_clients, n_rows, plan_words);
+        pc.mask = reinterpret_cast<const void *const *>(extra_dev + at.mask);
+        pc.ct = reinterpret_cast<void *const *>(extra_dev + at.ct);
+        pc.rows = reinterpret_cast<const uint64_t *>(extra_dev + at.rows);
+        pc.sum = sum_out_dev; pc.n = n_elems; pc.n_values = n_values; pc.n_clients = n_clients; pc.field_bits = field_bits; pc.bs = static_cast<int>(bs);
+        HIP_TRY(ctx, launch_quantize_batch_philox_combine_cohort(ctx->env, pc, reinterpret_cast<const flashe_philox::ClientPlan *>(extra_dev + at.plans),
+                                                                 reinterpret_cast<const uint64_t *>(extra_dev + at.groups), n_groups, elem_bytes));
+        return FLASHE_OK;
+    }
     if (plans) {
         const flashe_tables::PreparedDrawsBlock at = flashe_tables::prepared_draws_block(n_clients, plan_words);
         pc.mask = reinterpret_cast<const void *const *>(extra_dev + at.mask);
@@ -1071,9 +1088,10 @@ int flashe_quantize_combine_cohort_u32_dev(flashe_ctx *ctx, int n_clients, uint6
 // The un-batched launch with the draws of Philox streams generated inside it.  The segment table's own refusals come first
 // (flashe_philox_random_dev's, without a draw buffer), then the tiling of the clients' stretches, then quantize_combine_cohort's; the
 // segments are advanced only after the launch has been made.
+// n_elems_arg (the batched job): n counts the clients' VALUES, which is what the segments tile.
 static int quantize_combine_cohort_philox(flashe_ctx *ctx, const char *who, int elem_bytes, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers,
                                           const void *const *src_dev, const int32_t *src_dtype, int element_bits, flashe_philox_segment *segments, int n_segments,
-                                          const void *const *mask_dev, void *const *ct_dev, void *sum_out_dev)
+                                          const void *const *mask_dev, void *const *ct_dev, void *sum_out_dev, const uint64_t *n_elems_arg = nullptr, int field_bits = 0)
 {
     if (n_clients < 1) return fail(ctx, FLASHE_EINVAL, "%s: n_clients must be >= 1", who);
     std::vector<flashe_philox::Segment> segs;
@@ -1087,8 +1105,8 @@ static int quantize_combine_cohort_philox(flashe_ctx *ctx, const char *who, int 
     case flashe_philox::kCohortPlansTooMany: return fail(ctx, FLASHE_EINVAL, "%s: n_clients x n draws overflow", who);
     default: return fail(ctx, FLASHE_EINVAL, "%s: the segments must tile the draws [0, n_clients x n) exactly", who);
     }
-    if (int rc = quantize_combine_cohort(ctx, who, elem_bytes, n_clients, n, n, nullptr, layers, n_layers, src_dev, src_dtype, element_bits, 0, nullptr, mask_dev, ct_dev,
-                                         sum_out_dev, &plans))
+    if (int rc = quantize_combine_cohort(ctx, who, elem_bytes, n_clients, n, n_elems_arg ? 0 : n, n_elems_arg, layers, n_layers, src_dev, src_dtype, element_bits,
+                                         field_bits, nullptr, mask_dev, ct_dev, sum_out_dev, &plans))
         return rc;
     for (int s = 0; n && s < n_segments; s++)
         flashe_philox::advance(segments[s].key, segments[s].counter, segments[s].buffer_pos, segments[s].buffer, segments[s].n);
@@ -1113,6 +1131,18 @@ int flashe_quantize_combine_cohort_philox_u32_dev(flashe_ctx *ctx, int n_clients
     if (ctx->int_bits > 32) return fail(ctx, FLASHE_EINVAL, "the uint32 layout needs int_bits <= 32, this ctx has %d", ctx->int_bits);
     return quantize_combine_cohort_philox(ctx, "flashe_quantize_combine_cohort_philox_u32_dev", 4, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits,
                                           segments, n_segments, reinterpret_cast<const void *const *>(mask_dev), reinterpret_cast<void *const *>(ct_dev), sum_out_dev);
+}
+
+// the BATCHED job with the draws generated inside the launch: the segments tile the clients' n_values values
+int flashe_quantize_batch_combine_cohort_philox_dev(flashe_ctx *ctx, int n_clients, uint64_t n_values, uint64_t n_elems, const flashe_tensor_layer *layers, int n_layers,
+                                                    const void *const *src_dev, const int32_t *src_dtype, int element_bits, int field_bits,
+                                                    flashe_philox_segment *segments, int n_segments, const uint64_t *const *mask_dev, uint64_t *const *ct_dev,
+                                                    uint64_t *sum_out_dev)
+{
+    CHECK_CTX(ctx);
+    return quantize_combine_cohort_philox(ctx, "flashe_quantize_batch_combine_cohort_philox_dev", ctx->limbs == 2 ? 16 : 8, n_clients, n_values, layers, n_layers, src_dev,
+                                          src_dtype, element_bits, segments, n_segments, reinterpret_cast<const void *const *>(mask_dev),
+                                          reinterpret_cast<void *const *>(ct_dev), sum_out_dev, &n_elems, field_bits);
 }
 
 // the BATCHED job over its n_elems elements (any bs = int_bits / field_bits >= 1)

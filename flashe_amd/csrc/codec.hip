@@ -639,8 +639,8 @@ __global__ __launch_bounds__(kStreamThreads) void quantize_combine_cohort_kernel
 }
 
 // the same launch with the draws generated inside it (flashe_quantize_combine_cohort_philox*_dev): no draw buffer is written by an earlier
-// launch and none is read here -- 16 bytes less per value and client, one launch less.  pc.u is not read.  The batched kernel below has
-// no such form: an element's 5 - 7 values span 2 - 3 blocks that neighbouring lanes would each recompute; it reads the draw buffer.
+// launch and none is read here -- 16 bytes less per value and client, one launch less.  pc.u is not read.  The batched job's form is
+// quantize_batch_philox_combine_cohort_kernel further down: its lane owns four elements, so that no block is computed twice.
 template <class E, int G>
 __global__ __launch_bounds__(kStreamThreads) void quantize_philox_combine_cohort_kernel(const PrepCohort pc, const ClientPlan *__restrict__ plans, E modmask)
 {
@@ -699,6 +699,146 @@ __global__ __launch_bounds__(kStreamThreads) void quantize_batch_combine_cohort_
 // (4 takes up to 178).  tests/perf/prepared_cohort_step.py alternates 1 / 2 / 4 in one process on the tuning build; no log of it exists.
 constexpr int kPrepCohortGroup = 2;
 
+// ---- the batched job with the draws generated inside the launch (flashe_quantize_batch_combine_cohort_philox_dev): pc.u is not read ----
+// A lane owns a GROUP of four consecutive elements of one row (groups[r] = row r's first group; a row's last group may hold fewer).  The
+// 4 BS values of four whole elements are consecutive values of the client, so they are words of BS Philox blocks where the client's
+// stream is block-aligned at the group's first value and of BS + 1 where it is not (philox_stream.h: RunBlocks; the phase is the same for
+// every group of a client and row, so the branch on it diverges only in a wave that straddles rows): the lane computes each block once,
+// in order, reads the four floats that go with it in one 16-byte access (two for float64), one run ahead of the block that rounds
+// them, and packs the four elements as the blocks arrive -- one element at a time: its mask is requested when its first value is
+// packed, and it is masked, stored and added to the sum when its last one is (four packed elements and four masks at once do not fit
+// the streaming budget at 128 bits); the sum is stored four elements at a time.
+// A client's body is BS + 1 inlined blocks long, so the clients are walked by a ROLLED loop and not kPrepCohortGroup at a time: two
+// bodies would not leave the registers of the streaming budget, and three (a group and the remainder) would not fit the instruction cache.
+// A row's last fewer-than-four elements, an element with pads and every element of a run-time bs (BS = 0) walk value by value with
+// RunWalk: the current block is kept and a new one computed only when its words run out.
+// It shares no body with quantize_batch_combine_cohort_kernel: that one's lane owns ONE element (its draws are a load), and giving it
+// the groups of four would change the code the buffer form runs.
+template <class E> __device__ __forceinline__ E prep_shl(E x, int s) { return s >= static_cast<int>(8 * sizeof(E)) ? static_cast<E>(0) : x << s; }
+
+// client c over the four whole elements e0 .. e0 + 3 of row `row`: the row's values j0 .. j0 + 4 BS - 1 (vstart = the row's first flat value)
+template <class E, int BS, bool f64>
+__device__ __forceinline__ void prep_batch_group4(const PrepCohort &pc, const ClientPlan *__restrict__ plans, int row, double p0, double p1, double p2,
+                                                  uint64_t vstart, uint64_t j0, int c, uint64_t e0, E modmask, E (&sum)[4])
+{
+    __asm__ volatile("" ::: "memory");                // (one client's plan in scalar registers at a time)
+    const ClientPlan &p = plans[c];
+    const uint64_t key[2] = {p.key[0], p.key[1]}, base[4] = {p.base[0], p.base[1], p.base[2], p.base[3]};
+    const void *xs = pc.src[static_cast<size_t>(c) * pc.n_layers + row];
+    E mk[4];
+    uint64_t raw[4];
+    prep_src4(xs, f64, j0, raw);
+    flashe_philox::RunBlocks rb;
+    rb.start(key, base, p.skip, vstart + j0);
+    E x = 0;                                          // the element being packed: one at a time, masked, stored and summed when its last value is in
+#pragma unroll
+    for (int i = 0; i < BS; i++) {
+        uint64_t ahead[4] = {0, 0, 0, 0};
+        double d[4];
+        if (i + 1 < BS) prep_src4(xs, f64, j0 + 4 * (i + 1), ahead);
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+            if ((4 * i + t) % BS == 0) mk[(4 * i + t) / BS] = prep_ld<E>(pc.mask[c], e0 + (4 * i + t) / BS);      // (an element's mask: asked for a block before it is used)
+        __asm__ volatile("" ::: "memory");            // (the later runs are not requested before this block: they would all be live at once)
+        rb.step(key, i == 0, d);
+        uint64_t q[4];
+#pragma unroll
+        for (int t = 0; t < 4; t++) q[t] = cohort_quantize_raw(raw[t], f64, p0, p1, p2, d[t]);
+        // (the next block's counter is made to wait for these four: left to itself the scheduler computes all the blocks first, while the
+        // floats arrive, and keeps every block's words)
+        __asm__ volatile("" : "+v"(q[0]), "+v"(q[1]), "+v"(q[2]), "+v"(q[3]), "+v"(rb.at[0]));
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const int m = 4 * i + t;                                                                    // value m of the group: slot m % BS of element m / BS
+            x = (x << pc.field_bits) + static_cast<E>(q[t]);                                            // temp *= mod; temp += value
+            if (m % BS == BS - 1) {
+                const E v = (x + mk[m / BS]) & modmask;
+                prep_st<E>(pc.ct[c], e0 + m / BS, v);
+                sum[m / BS] += v;
+                x = 0;
+            }
+            raw[t] = ahead[t];
+        }
+    }
+}
+
+// client c over the ne <= 4 elements from e0 on, value by value: the row's values from j0 on, those at or past `size` are pads
+template <class E>
+__device__ __forceinline__ void prep_batch_group_walk(const PrepCohort &pc, const ClientPlan *__restrict__ plans, int row, bool f64, double p0, double p1, double p2,
+                                                      uint64_t vstart, uint64_t j0, uint64_t size, int bs, int ne, int c, uint64_t e0, E modmask, E (&sum)[4])
+{
+    __asm__ volatile("" ::: "memory");
+    const ClientPlan &p = plans[c];
+    const uint64_t key[2] = {p.key[0], p.key[1]}, base[4] = {p.base[0], p.base[1], p.base[2], p.base[3]};
+    const void *xs = pc.src[static_cast<size_t>(c) * pc.n_layers + row];
+    flashe_philox::RunWalk rw;
+    rw.start(key, base, p.skip, vstart + j0);     // (j0 < size: the group's first element holds a value)
+    uint64_t j = j0;
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+        if (t < ne) {
+            E x = 0;
+#pragma unroll 1
+            for (int i = 0; i < bs; i++, j++) {
+                uint64_t q = 0;
+                if (j < size) q = cohort_quantize_raw(cohort_load(xs, f64, j), f64, p0, p1, p2, rw.next(key));
+                x = prep_shl<E>(x, pc.field_bits) + static_cast<E>(q);
+            }
+            const E v = (x + prep_ld<E>(pc.mask[c], e0 + t)) & modmask;
+            prep_st<E>(pc.ct[c], e0 + t, v);
+            sum[t] += v;
+        }
+    }
+}
+
+template <class E, int BS>
+__global__ __launch_bounds__(kStreamThreads) void quantize_batch_philox_combine_cohort_kernel(const PrepCohort pc, const ClientPlan *__restrict__ plans,
+                                                                                              const uint64_t *__restrict__ groups, uint64_t n_groups, E modmask)
+{
+    const int C = pc.n_clients, bs = BS ? BS : pc.bs;
+    for (uint64_t g = static_cast<uint64_t>(blockIdx.x) * kStreamThreads + threadIdx.x; g < n_groups; g += static_cast<uint64_t>(gridDim.x) * kStreamThreads) {
+        int lo = 0, hi = pc.n_layers - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (groups[mid] <= g) lo = mid; else hi = mid - 1;
+        }
+        const CodecLayer *L = pc.layers + lo;
+        const bool f64 = L->x_is_f64 != 0;
+        const double p0 = L->p0, p1 = L->p1, p2 = L->p2;
+        const uint64_t vstart = L->start, size = pc.rows[2 * lo + 1], first = 4 * (g - groups[lo]);       // first: the group's first element of the row
+        const uint64_t e0 = pc.rows[2 * lo] + first, j0 = first * static_cast<uint64_t>(bs);
+        E sum[4] = {0, 0, 0, 0};
+        int c = 0;
+        if (BS != 0 && j0 + 4 * static_cast<uint64_t>(BS) <= size) {
+            if constexpr (BS != 0) {
+                // (the row's float type picks the body: its rounding is not decided value by value)
+                if (f64) {
+#pragma unroll 1
+                    for (; c < C; c++) prep_batch_group4<E, BS, true>(pc, plans, lo, p0, p1, p2, vstart, j0, c, e0, modmask, sum);
+                } else {
+#pragma unroll 1
+                    for (; c < C; c++) prep_batch_group4<E, BS, false>(pc, plans, lo, p0, p1, p2, vstart, j0, c, e0, modmask, sum);
+                }
+            }
+            if (pc.sum) {
+#pragma unroll
+                for (int t = 0; t < 4; t++) sum[t] &= modmask;
+                prep_st4(pc.sum, e0, sum);
+            }
+            continue;
+        }
+        const uint64_t left = (size - j0 + static_cast<uint64_t>(bs) - 1) / static_cast<uint64_t>(bs);     // the row's elements from e0 on, >= 1
+        const int ne = left < 4 ? static_cast<int>(left) : 4;
+#pragma unroll 1
+        for (; c < C; c++) prep_batch_group_walk<E>(pc, plans, lo, f64, p0, p1, p2, vstart, j0, size, bs, ne, c, e0, modmask, sum);
+        if (pc.sum) {
+#pragma unroll
+            for (int t = 0; t < 4; t++)
+                if (t < ne) prep_st<E>(pc.sum, e0 + t, sum[t] & modmask);
+        }
+    }
+}
+
 template <class E> static hipError_t launch_prep_cohort(const LaunchEnv &env, const PrepCohort &pc, bool batched, int group, E modmask)
 {
     const dim3 g(stream_grid(env, batched ? pc.n : (pc.n + 3) / 4)), t(kStreamThreads);
@@ -752,6 +892,30 @@ hipError_t launch_quantize_philox_combine_cohort(const LaunchEnv &env, const Pre
     if (elem_bytes == 4) return env.b > 32 ? hipErrorInvalidValue : launch_prep_philox<uint32_t>(env, pc, plans, static_cast<uint32_t>(lo));
     if (elem_bytes == 8) return env.b > 64 ? hipErrorInvalidValue : launch_prep_philox<uint64_t>(env, pc, plans, lo);
     if (elem_bytes == 16) return env.b <= 64 ? hipErrorInvalidValue : launch_prep_philox<u128>(env, pc, plans, (static_cast<u128>(hi) << 64) | lo);
+    return hipErrorInvalidValue;
+}
+
+// ---- the batched launch with the draws generated inside it (quantize_batch_philox_combine_cohort_kernel above) ----
+template <class E>
+static hipError_t launch_prep_batch_philox(const LaunchEnv &env, const PrepCohort &pc, const ClientPlan *plans, const uint64_t *groups, uint64_t n_groups, E modmask)
+{
+    const dim3 g(stream_grid(env, n_groups)), t(kStreamThreads);
+    if (pc.bs == 5) hipLaunchKernelGGL((quantize_batch_philox_combine_cohort_kernel<E, 5>), g, t, 0, env.stream, pc, plans, groups, n_groups, modmask);
+    else if (pc.bs == 6) hipLaunchKernelGGL((quantize_batch_philox_combine_cohort_kernel<E, 6>), g, t, 0, env.stream, pc, plans, groups, n_groups, modmask);
+    else if (pc.bs == 7) hipLaunchKernelGGL((quantize_batch_philox_combine_cohort_kernel<E, 7>), g, t, 0, env.stream, pc, plans, groups, n_groups, modmask);
+    else hipLaunchKernelGGL((quantize_batch_philox_combine_cohort_kernel<E, 0>), g, t, 0, env.stream, pc, plans, groups, n_groups, modmask);
+    return hipGetLastError();
+}
+
+hipError_t launch_quantize_batch_philox_combine_cohort(const LaunchEnv &env, const PrepCohort &pc, const ClientPlan *plans, const uint64_t *groups, uint64_t n_groups,
+                                                       int elem_bytes)
+{
+    if (pc.n == 0 || pc.n_clients == 0 || n_groups == 0) return hipSuccess;
+    if (pc.n_layers < 1 || !plans || !groups || pc.bs < 1 || pc.field_bits < 1 || pc.field_bits > env.b) return hipErrorInvalidValue;
+    uint64_t lo, hi;
+    masks_of(env.b, &lo, &hi);
+    if (elem_bytes == 8) return env.b > 64 ? hipErrorInvalidValue : launch_prep_batch_philox<uint64_t>(env, pc, plans, groups, n_groups, lo);
+    if (elem_bytes == 16) return env.b <= 64 ? hipErrorInvalidValue : launch_prep_batch_philox<u128>(env, pc, plans, groups, n_groups, (static_cast<u128>(hi) << 64) | lo);
     return hipErrorInvalidValue;
 }
 

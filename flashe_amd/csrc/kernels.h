@@ -389,6 +389,11 @@ hipError_t launch_quantize_combine_cohort(const LaunchEnv &env, const PrepCohort
 // The un-batched launch with the draws of np.random.Philox streams generated inside it: pc.u is not read; plans = a DEVICE table of one
 // flashe_philox::ClientPlan (philox_stream.h) per client, client c's draw for value k = word (skip + k) % 4 of block(base + (skip + k) / 4).
 hipError_t launch_quantize_philox_combine_cohort(const LaunchEnv &env, const PrepCohort &pc, const flashe_philox::ClientPlan *plans, int elem_bytes);
+// The BATCHED launch with the draws generated inside it: a lane owns a GROUP of four consecutive elements of one row (the row's last group
+// may hold fewer); groups = a DEVICE table of every row's first group, n_groups the launch's groups; client c's draw for its flat value k
+// (the rows' values in walking order, pads draw nothing) = word (skip + k) % 4 of block(base + (skip + k) / 4).  pc.u is not read.
+hipError_t launch_quantize_batch_philox_combine_cohort(const LaunchEnv &env, const PrepCohort &pc, const flashe_philox::ClientPlan *plans, const uint64_t *groups,
+                                                       uint64_t n_groups, int elem_bytes);
 hipError_t launch_unbatch(const LaunchEnv &env, uint64_t nb, const uint64_t *in_dev, int field_bits, uint64_t *out_dev);
 
 // Caller-owned tensors either side of the model-wide codec (tensors.hip).  dtype / flags as in flashe_tensor_layer (include/flashe.h);

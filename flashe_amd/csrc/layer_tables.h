@@ -92,6 +92,24 @@ inline PreparedDrawsBlock prepared_draws_block(int n_clients, size_t plan_words)
     const size_t c = static_cast<size_t>(n_clients);
     return PreparedDrawsBlock{0, c * 8, 2 * c * 8, 2 * c + plan_words * c};
 }
+// The block of the BATCHED prepared cohort launch that generates its own draws: the pointers, the two words per batched row, then one
+// word per row -- the row's first GROUP of four elements in the launch (a lane owns a group; a row's last group may hold fewer) --
+// then the plans.  rows = the (first element, value count) pairs of n_rows rows; returns the launch's groups.
+struct PreparedBatchDrawsBlock { size_t mask, ct, rows, groups, plans, words; };
+inline PreparedBatchDrawsBlock prepared_batch_draws_block(int n_clients, size_t n_rows, size_t plan_words)
+{
+    const size_t c = static_cast<size_t>(n_clients);
+    return PreparedBatchDrawsBlock{0, c * 8, 2 * c * 8, (2 * c + 2 * n_rows) * 8, (2 * c + 3 * n_rows) * 8, 2 * c + 3 * n_rows + plan_words * c};
+}
+inline uint64_t batched_groups(const uint64_t *rows, size_t n_rows, uint64_t bs, uint64_t *first_group)
+{
+    uint64_t g = 0;
+    for (size_t r = 0; r < n_rows; r++) {
+        first_group[r] = g;
+        g += ((rows[2 * r + 1] + bs - 1) / bs + 3) / 4;
+    }
+    return g;
+}
 // entries of a cohort's n_clients x n_layers source table
 inline size_t cohort_sources(int n_clients, int n_layers) { return static_cast<size_t>(n_clients) * static_cast<size_t>(n_layers); }
 

@@ -175,6 +175,94 @@ FLASHE_UNROLL
     for (int t = 0; t < 4; t++) d[t] = to_double(skip == 0 ? w[t] : skip == 1 ? w[t + 1] : skip == 2 ? w[t + 2] : w[t + 3]);
 }
 
+// block() for a caller that computes many blocks under one launch-uniform key: on the device the key is taken as new at every call, so
+// that the round keys of one block are not kept in scalar registers for the next (client_draws4's note).
+FLASHE_HD void block_fresh_key(const uint64_t counter[4], const uint64_t key[2], uint64_t word[4])
+{
+    uint64_t again[2] = {key[0], key[1]};
+#if defined(__HIP_DEVICE_COMPILE__)
+    __asm__ volatile("" : "+s"(again[0]), "+s"(again[1]));
+#endif
+    block(counter, again, word);
+}
+
+// ---- a RUN of values [k, k + m) under a plan (codec.hip's quantize_batch_philox_combine_cohort_kernel: the values of a group of
+// batched elements are consecutive values of their client) ----
+// Stated once: the run's draws are words word, word + 1, ... of block(first), block(first + 1), ...; it touches `blocks` blocks -- m / 4
+// where the run starts at a block's first word and m is a multiple of four, one more where it does not.  m = 0: no block.
+FLASHE_HD void client_run(const uint64_t base[4], uint32_t skip, uint64_t k, uint64_t m, uint64_t first[4], uint64_t &blocks, uint32_t &word)
+{
+    const uint64_t v = skip + k;
+    counter_add(base, v >> 2, first);
+    word = static_cast<uint32_t>(v & 3);
+    blocks = m ? (word + m + 3) / 4 : 0;
+}
+
+// The run walked one draw at a time: the current block is kept and a new one is computed only when the word index wraps, so m draws
+// cost client_run's `blocks` blocks (made counts them) and never one per value.
+struct RunWalk {
+    uint64_t at[4], w[4];
+    uint32_t word, made;
+    FLASHE_HD void start(const uint64_t key[2], const uint64_t base[4], uint32_t skip, uint64_t k)
+    {
+        uint64_t blocks;
+        client_run(base, skip, k, 1, at, blocks, word);
+        block_fresh_key(at, key, w);
+        made = 1;
+    }
+    FLASHE_HD double next(const uint64_t key[2])
+    {
+        if (word == 4) {
+            uint64_t nx[4];
+            counter_add(at, 1, nx);
+FLASHE_UNROLL
+            for (int i = 0; i < 4; i++) at[i] = nx[i];
+            block_fresh_key(at, key, w);
+            word = 0;
+            made++;
+        }
+        const uint64_t x = word == 0 ? w[0] : word == 1 ? w[1] : word == 2 ? w[2] : w[3];
+        word++;
+        return to_double(x);
+    }
+};
+
+// The draws of the 4 Q values k0 .. k0 + 4 Q - 1 for a lane that takes them four at a time, in order: step(i) gives values
+// k0 + 4 i .. k0 + 4 i + 3.  Every block of the run is computed once -- Q where the run starts at a block's first word, Q + 1 where it
+// does not (the words behind the run's start of one block, then the words in front of it of the next).
+struct RunBlocks {
+    uint64_t at[4], w[8];
+    uint32_t word;
+    FLASHE_HD void start(const uint64_t key[2], const uint64_t base[4], uint32_t skip, uint64_t k0)
+    {
+        uint64_t blocks;
+        client_run(base, skip, k0, 4, at, blocks, word);
+        block_fresh_key(at, key, w + 4);
+    }
+    FLASHE_HD void next_block(const uint64_t key[2])
+    {
+        uint64_t nx[4];
+        counter_add(at, 1, nx);
+FLASHE_UNROLL
+        for (int i = 0; i < 4; i++) at[i] = nx[i];
+        block_fresh_key(at, key, w + 4);
+    }
+    // first: the run's first four values (the block start() made is theirs)
+    FLASHE_HD void step(const uint64_t key[2], bool first, double d[4])
+    {
+FLASHE_UNROLL
+        for (int t = 0; t < 4; t++) w[t] = w[t + 4];
+        if (word || !first) next_block(key);
+        // word 0: w[t + 4], else w[t + word] -- picked with masks, so that the four picks stay straight-line code on the device
+        const uint64_t odd = 0 - static_cast<uint64_t>(word & 1), high = 0 - static_cast<uint64_t>((word >> 1) & 1);
+FLASHE_UNROLL
+        for (int t = 0; t < 4; t++) {
+            const uint64_t a = w[t + 4] ^ ((w[t + 4] ^ w[t + 1]) & odd), b = w[t + 2] ^ ((w[t + 2] ^ w[t + 3]) & odd);
+            d[t] = to_double(a ^ ((a ^ b) & high));
+        }
+    }
+};
+
 enum CohortPlansStatus { kCohortPlansOk = 0, kCohortPlansTooMany = 1, kCohortPlansNotTiled = 2, kCohortPlansSplitClient = 3 };
 
 // The plans of n_clients clients of n draws each from checked segments (check_segments: no overlap, nothing overflows): the non-empty

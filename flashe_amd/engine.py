@@ -911,24 +911,38 @@ class Engine:
         return self._took(rc)
 
     def quantize_combine_cohort_philox_dev(self, n, layers, srcs, dtypes, element_bits, generators_or_states, counts, offsets, masks, cts, sum_out,
-                                           compact=False):
+                                           compact=False, batch=None):
         """quantize_combine_cohort_dev (un-batched) with the draws of np.random.Philox streams generated INSIDE the launch
         (flashe_quantize_combine_cohort_philox_dev; compact=True: its _u32 form): no draw buffer exists.  generators_or_states, counts,
         offsets: philox_random_dev's table (_draw_table) over the client-major draw positions -- client c rounds its value k with draw
         c n + k; one entry covers all clients of a shared generator, one entry per client a list of generators, and the same Generator
         listed twice continues itself in list order.  The entries must tile [0, C n) exactly, every client's draws inside one entry.  The
         advanced states are handed back only after the call has succeeded; a refusal raises and advances nothing.  Returns False --
-        nothing was launched, nothing advanced -- when the library declines (FLASHE_ENOTSUP), True otherwise."""
+        nothing was launched, nothing advanced -- when the library declines (FLASHE_ENOTSUP), True otherwise.
+        batch=(n_elems, field_bits): the batched job (flashe_quantize_batch_combine_cohort_philox_dev) -- n counts the clients' VALUES,
+        which is what the table tiles: client c rounds its flat value k with draw c n + k, an element's pads draw nothing."""
         arr, nl = self._tensor_layers(layers)
         C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
         pm, _a = self._ptr_array(masks)
         pc, _b = self._ptr_array(cts)
         segs, counts, offsets, hand_back = _draw_table(_PhiloxDraws, generators_or_states, counts, offsets)
-        fn = self._lib.flashe_quantize_combine_cohort_philox_u32_dev if compact else self._lib.flashe_quantize_combine_cohort_philox_dev
-        took = self._took(fn(self._h, C, int(n), arr, nl, ps, pd, element_bits, segs, len(counts), pm, pc, self._ptr(sum_out)))
+        if batch is not None:
+            n_elems, field_bits = batch
+            rc = self._lib.flashe_quantize_batch_combine_cohort_philox_dev(self._h, C, int(n), int(n_elems), arr, nl, ps, pd, element_bits, int(field_bits),
+                                                                           segs, len(counts), pm, pc, self._ptr(sum_out))
+        else:
+            fn = self._lib.flashe_quantize_combine_cohort_philox_u32_dev if compact else self._lib.flashe_quantize_combine_cohort_philox_dev
+            rc = fn(self._h, C, int(n), arr, nl, ps, pd, element_bits, segs, len(counts), pm, pc, self._ptr(sum_out))
+        took = self._took(rc)
         if took:
             hand_back()
         return took
+
+    def quantize_batch_combine_cohort_philox_dev(self, n_values, n_elems, field_bits, layers, srcs, dtypes, element_bits, generators_or_states, counts,
+                                                 offsets, masks, cts, sum_out):
+        """quantize_combine_cohort_philox_dev(..., batch=(n_elems, field_bits)) under the name FlasheCohort looks the batched form up by."""
+        return self.quantize_combine_cohort_philox_dev(n_values, layers, srcs, dtypes, element_bits, generators_or_states, counts, offsets, masks, cts,
+                                                       sum_out, batch=(n_elems, field_bits))
 
     def combine_unbatch_unquantize_model_dev(self, layers, element_bits, field_bits, num_clients, inp, add, minus, n_elems, out):
         """unbatch_unquantize_model_dev over (inp + add - minus) mod 2^b, one memory-bound pass (add / minus: device vectors of n_elems

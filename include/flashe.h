@@ -93,7 +93,7 @@ typedef struct flashe_ctx flashe_ctx;
  *      flashe_quantize_encrypt_cohort_cut_runs_u32_dev / flashe_quantize_batch_encrypt_cohort_cut_runs_dev (the cut launch for a round in
  *      which clients dropped out -- every gap is a cut -- and for a batched job); flashe_quantize_combine_cohort_philox_dev /
  *      flashe_quantize_combine_cohort_philox_u32_dev (a precompute job's cohort online with the draws of np.random.Philox streams
- *      generated inside the launch: no draw buffer) */
+ *      generated inside the launch: no draw buffer) and flashe_quantize_batch_combine_cohort_philox_dev (the same for a batched job) */
 #define FLASHE_ABI_VERSION 4
 int flashe_abi_version(void);
 int flashe_device_count(int *count);
@@ -910,8 +910,8 @@ struct flashe_philox_segment;                   /* (defined with flashe_philox_r
  * FLASHE_EINVAL otherwise, for everything flashe_philox_random_dev refuses in a table (a buffer_pos above 4, more than 128 segments,
  * overflowing or overlapping ranges, a graph being captured) and for everything flashe_quantize_combine_cohort_dev / _u32_dev refuse;
  * FLASHE_ENOTSUP as there.  On success every segment is advanced in place as flashe_philox_random_dev advances it; on any refusal
- * nothing is advanced, staged or launched.  n = 0 (every segment empty): FLASHE_OK, nothing launched or advanced.  A batched job has
- * no such form (an element's 5 - 7 values span blocks that neighbouring lanes would each recompute): it reads a draw buffer. */
+ * nothing is advanced, staged or launched.  n = 0 (every segment empty): FLASHE_OK, nothing launched or advanced.  The batched
+ * job's form is flashe_quantize_batch_combine_cohort_philox_dev below. */
 int flashe_quantize_combine_cohort_philox_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers,
                                               const void *const *src_dev, const int32_t *src_dtype, int element_bits,
                                               struct flashe_philox_segment *segments, int n_segments, const uint64_t *const *mask_dev,
@@ -920,6 +920,21 @@ int flashe_quantize_combine_cohort_philox_u32_dev(flashe_ctx *ctx, int n_clients
                                                   const void *const *src_dev, const int32_t *src_dtype, int element_bits,
                                                   struct flashe_philox_segment *segments, int n_segments, const uint32_t *const *mask_dev,
                                                   uint32_t *const *ct_dev, uint32_t *sum_out_dev);
+/* The BATCHED online step with the draws generated inside the launch (new): flashe_quantize_batch_combine_cohort_dev's arguments and
+ * refusals with u_dev replaced by a segment table under flashe_quantize_combine_cohort_philox_dev's rules over the clients' VALUES --
+ * client c rounds its flat value k (the layers' values in order; an element's pads draw nothing) with draw c * n_values + k, the
+ * non-empty segments tile [0, n_clients * n_values) exactly (a table that tiles n_clients * n_elems is refused) and every client lies
+ * in one segment.  A lane owns four consecutive elements of one layer and computes each Philox4x64 block their 4 bs values are words
+ * of once: bs blocks where the client's stream is block-aligned at the layer's first value, bs + 1 where it is not (bs 5 / 6 / 7
+ * compiled in; every other bs, a layer's last elements and elements with pads keep the current block and compute a new one when its
+ * words run out).  No draw buffer exists: per element and client at bs 6 the launch moves 56 bytes where flashe_philox_random_dev +
+ * flashe_quantize_batch_combine_cohort_dev move 152, and it reproduces their ciphertexts and sum bit for bit.  On success every
+ * segment is advanced in place; on any refusal nothing is advanced, staged or launched.  n_values = 0: FLASHE_OK.  Not capturable. */
+int flashe_quantize_batch_combine_cohort_philox_dev(flashe_ctx *ctx, int n_clients, uint64_t n_values, uint64_t n_elems,
+                                                    const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
+                                                    const int32_t *src_dtype, int element_bits, int field_bits,
+                                                    struct flashe_philox_segment *segments, int n_segments, const uint64_t *const *mask_dev,
+                                                    uint64_t *const *ct_dev, uint64_t *sum_out_dev);
 /* The codec back end over caller-held vectors (new), jzf_quantize.py:102-107: out[k] = unquantize((in[k] + add[k] - minus[k]) mod 2^b)
  * as float64 for the n elements of a flattened model, one memory-bound pass; add_dev / minus_dev may be NULL (zeros).  With in = a
  * cohort's sum and add = its decrypt mask this is the cohort's decrypt_unquantize. */
