@@ -89,6 +89,27 @@ class FlasheError(RuntimeError):
         self.code = code
 
 
+# The chained cohort launches (abi_layers.hip, quantize_encrypt_cohort).  What a name says: _runs_ = the cipher indices as a list in place of
+# first_idx, batch = n_values and n_elems in place of n and a field_bits, _u32_ = the compact layout without a decrypt mask, _cut_ = a
+# trailing scratch.
+COHORT_LAUNCHES = (
+    "flashe_quantize_encrypt_cohort_dev", "flashe_quantize_encrypt_cohort_u32_dev",
+    "flashe_quantize_encrypt_cohort_cut_dev", "flashe_quantize_encrypt_cohort_cut_u32_dev",
+    "flashe_quantize_encrypt_cohort_runs_dev", "flashe_quantize_encrypt_cohort_runs_u32_dev",
+    "flashe_quantize_encrypt_cohort_cut_runs_dev", "flashe_quantize_encrypt_cohort_cut_runs_u32_dev",
+    "flashe_quantize_batch_encrypt_cohort_dev", "flashe_quantize_batch_encrypt_cohort_runs_dev",
+    "flashe_quantize_batch_encrypt_cohort_cut_runs_dev",
+)
+
+
+def _cohort_signature(name):
+    batched = "_batch_" in name
+    return (c_int, [c_vp, c_u32, ctypes.POINTER(c_u32) if "_runs_" in name else c_u32, c_int] + [c_u64] * (2 if batched else 1)    # ctx, iter, idx, n_clients, n
+            + [c_u32, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp), ctypes.POINTER(ctypes.c_int32)]                  # n_jobs, table, sources
+            + [c_int] * (2 if batched else 1) + [c_vp, ctypes.POINTER(c_vp), c_vp]                                                 # bits, u, cts, sum
+            + [c_vp] * (("_u32_" not in name) + ("_cut_" in name)))                                                                 # dmask, scratch
+
+
 _SIGNATURES = {
     # name: (restype, argtypes)
     "flashe_abi_version": (c_int, []),
@@ -230,35 +251,9 @@ _SIGNATURES = {
     "flashe_quantize_encrypt_prepared_tensors_dev": (c_int, [c_vp, c_u64, c_u64, c_u64, ctypes.POINTER(TensorLayer), c_int, c_int, c_vp, c_vp]),
     "flashe_quantize_batch_encrypt_prepared_model_dev": (c_int, [c_vp, ctypes.POINTER(BatchLayer), c_int, c_int, c_int, c_vp, c_u64, c_vp]),
     "flashe_quantize_batch_encrypt_prepared_tensors_dev": (c_int, [c_vp, ctypes.POINTER(TensorLayer), c_int, c_u64, c_int, c_int, c_vp, c_u64, c_vp]),
-    "flashe_quantize_encrypt_cohort_dev": (c_int, [c_vp, c_u32, c_u32, c_int, c_u64, c_u32, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp),
-                                                   ctypes.POINTER(ctypes.c_int32), c_int, c_vp, ctypes.POINTER(c_vp), c_vp, c_vp]),
-    "flashe_quantize_encrypt_cohort_u32_dev": (c_int, [c_vp, c_u32, c_u32, c_int, c_u64, c_u32, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp),
-                                                       ctypes.POINTER(ctypes.c_int32), c_int, c_vp, ctypes.POINTER(c_vp), c_vp]),
+    **{name: _cohort_signature(name) for name in COHORT_LAUNCHES},
     "flashe_cohort_cut_parts": (c_int, [c_vp, c_int, c_u64, c_u32, c_int, ctypes.POINTER(c_int)]),
-    "flashe_quantize_encrypt_cohort_cut_dev": (c_int, [c_vp, c_u32, c_u32, c_int, c_u64, c_u32, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp),
-                                                       ctypes.POINTER(ctypes.c_int32), c_int, c_vp, ctypes.POINTER(c_vp), c_vp, c_vp, c_vp]),
-    "flashe_quantize_encrypt_cohort_cut_u32_dev": (c_int, [c_vp, c_u32, c_u32, c_int, c_u64, c_u32, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp),
-                                                           ctypes.POINTER(ctypes.c_int32), c_int, c_vp, ctypes.POINTER(c_vp), c_vp, c_vp]),
-    "flashe_quantize_batch_encrypt_cohort_dev": (c_int, [c_vp, c_u32, c_u32, c_int, c_u64, c_u64, c_u32, ctypes.POINTER(TensorLayer), c_int,
-                                                         ctypes.POINTER(c_vp), ctypes.POINTER(ctypes.c_int32), c_int, c_int, c_vp, ctypes.POINTER(c_vp),
-                                                         c_vp, c_vp]),
-    "flashe_quantize_encrypt_cohort_runs_dev": (c_int, [c_vp, c_u32, ctypes.POINTER(c_u32), c_int, c_u64, c_u32, ctypes.POINTER(TensorLayer), c_int,
-                                                        ctypes.POINTER(c_vp), ctypes.POINTER(ctypes.c_int32), c_int, c_vp, ctypes.POINTER(c_vp), c_vp, c_vp]),
-    "flashe_quantize_encrypt_cohort_runs_u32_dev": (c_int, [c_vp, c_u32, ctypes.POINTER(c_u32), c_int, c_u64, c_u32, ctypes.POINTER(TensorLayer), c_int,
-                                                            ctypes.POINTER(c_vp), ctypes.POINTER(ctypes.c_int32), c_int, c_vp, ctypes.POINTER(c_vp), c_vp]),
-    "flashe_quantize_batch_encrypt_cohort_runs_dev": (c_int, [c_vp, c_u32, ctypes.POINTER(c_u32), c_int, c_u64, c_u64, c_u32, ctypes.POINTER(TensorLayer),
-                                                              c_int, ctypes.POINTER(c_vp), ctypes.POINTER(ctypes.c_int32), c_int, c_int, c_vp,
-                                                              ctypes.POINTER(c_vp), c_vp, c_vp]),
     "flashe_cohort_cut_pieces": (c_int, [c_vp, ctypes.POINTER(c_u32), c_int, c_u64, c_u32, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
-    "flashe_quantize_encrypt_cohort_cut_runs_dev": (c_int, [c_vp, c_u32, ctypes.POINTER(c_u32), c_int, c_u64, c_u32, ctypes.POINTER(TensorLayer), c_int,
-                                                            ctypes.POINTER(c_vp), ctypes.POINTER(ctypes.c_int32), c_int, c_vp, ctypes.POINTER(c_vp), c_vp, c_vp,
-                                                            c_vp]),
-    "flashe_quantize_encrypt_cohort_cut_runs_u32_dev": (c_int, [c_vp, c_u32, ctypes.POINTER(c_u32), c_int, c_u64, c_u32, ctypes.POINTER(TensorLayer), c_int,
-                                                                ctypes.POINTER(c_vp), ctypes.POINTER(ctypes.c_int32), c_int, c_vp, ctypes.POINTER(c_vp), c_vp,
-                                                                c_vp]),
-    "flashe_quantize_batch_encrypt_cohort_cut_runs_dev": (c_int, [c_vp, c_u32, ctypes.POINTER(c_u32), c_int, c_u64, c_u64, c_u32,
-                                                                  ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp), ctypes.POINTER(ctypes.c_int32),
-                                                                  c_int, c_int, c_vp, ctypes.POINTER(c_vp), c_vp, c_vp, c_vp]),
     "flashe_cohort_masks_u32_dev": (c_int, [c_vp, c_u32, c_u32, c_int, c_u64, c_u32, ctypes.POINTER(c_vp)]),
     "flashe_quantize_combine_cohort_dev": (c_int, [c_vp, c_int, c_u64, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp),
                                                    ctypes.POINTER(ctypes.c_int32), c_int, c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),

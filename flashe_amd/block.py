@@ -1838,57 +1838,25 @@ class FlasheCohort(object):
         dmask = DeviceVector(eng, n_elems) if self.n_local == self.num_clients and not self.compact else None
         outs, mask_buf = [v.buf for v in cts], dmask.buf if dmask is not None else None
         idxs = [self.first_idx + p for p in plan.present]
-        if cut and (plan.runs > 1 or ld.batch):
-            parts = eng.cohort_cut_pieces(idxs, n_elems, _cipher_mod.N_JOBS, compact=self.compact)[0]
-            need = 0 if parts <= 1 else parts * n_elems * 4 if self.compact else parts * n_elems * 16 * (2 if dmask is not None else 1)
+        jobs, batch = _cipher_mod.N_JOBS, bool(ld.batch) and not self.compact
+        # the form: the cipher indices as a list for a gapped or batched cut and for a call with `present` (one run of a compact cohort
+        # without the gapped compact launch: plan_cohort sends a gapped one to the staged form), else the first index
+        by_list = (plan.runs > 1 or bool(ld.batch)) if cut else (by_idx and (not self.compact or hasattr(eng, "quantize_encrypt_cohort_runs_u32_dev")))
+        name = f"quantize_{'batch_' if batch else ''}encrypt_cohort{'_cut' if cut else ''}{'_runs' if by_list else ''}{'_u32' if self.compact else ''}_dev"
+        scratch = ()
+        if cut:
+            # the library's piece count sizes the scratch: the pieces' sums (compact: uint32) and, behind them, their decrypt masks
+            elems = n_elems if by_list else n
+            parts = eng.cohort_cut_pieces(idxs, elems, jobs, compact=self.compact)[0] if by_list else eng.cohort_cut_parts(len(idxs), elems, jobs, compact=self.compact)
+            if not parts:
+                return False
+            need = 0 if parts == 1 else parts * elems * (4 if self.compact else 16 * (2 if dmask is not None else 1))
             if need and (self._cut_scratch is None or self._cut_scratch.nbytes < need):
                 self._cut_scratch = eng.alloc(max(need, 16))
-            scratch = self._cut_scratch if need else None
-            if not parts:
-                took = False
-            elif self.compact:
-                took = eng.quantize_encrypt_cohort_cut_runs_u32_dev(c.iter_index, idxs, n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du, outs,
-                                                                    psum.buf, scratch)
-            elif ld.batch:
-                took = eng.quantize_batch_encrypt_cohort_cut_runs_dev(c.iter_index, idxs, n, n_elems, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits,
-                                                                      _field_bits(q.element_bits, q.num_clients), du, outs, psum.buf, mask_buf, scratch)
-            else:
-                took = eng.quantize_encrypt_cohort_cut_runs_dev(c.iter_index, idxs, n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du, outs,
-                                                                psum.buf, mask_buf, scratch)
-        elif cut:
-            C = len(idxs)
-            parts = eng.cohort_cut_parts(C, n, _cipher_mod.N_JOBS, compact=self.compact)
-            need = 0 if parts <= 1 else parts * n * 4 if self.compact else parts * n * 16 * (2 if dmask is not None else 1)
-            if need and (self._cut_scratch is None or self._cut_scratch.nbytes < need):
-                self._cut_scratch = eng.alloc(max(need, 16))
-            scratch = self._cut_scratch if need else None
-            if not parts:
-                took = False
-            elif self.compact:
-                took = eng.quantize_encrypt_cohort_cut_u32_dev(c.iter_index, idxs[0], n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du, outs,
-                                                               psum.buf, scratch)
-            else:
-                took = eng.quantize_encrypt_cohort_cut_dev(c.iter_index, idxs[0], n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du, outs,
-                                                           psum.buf, mask_buf, scratch)
-        elif self.compact and by_idx and hasattr(eng, "quantize_encrypt_cohort_runs_u32_dev"):
-            took = eng.quantize_encrypt_cohort_runs_u32_dev(c.iter_index, idxs, n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du, outs,
-                                                            psum.buf)
-        elif self.compact:
-            # (one run: without the gapped compact launch plan_cohort sends a gapped compact cohort to the staged form)
-            took = eng.quantize_encrypt_cohort_u32_dev(c.iter_index, idxs[0], n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du, outs,
-                                                       psum.buf)
-        elif by_idx and ld.batch:
-            took = eng.quantize_batch_encrypt_cohort_runs_dev(c.iter_index, idxs, n, n_elems, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits,
-                                                              _field_bits(q.element_bits, q.num_clients), du, outs, psum.buf, mask_buf)
-        elif by_idx:
-            took = eng.quantize_encrypt_cohort_runs_dev(c.iter_index, idxs, n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du, outs, psum.buf,
-                                                        mask_buf)
-        elif ld.batch:
-            took = eng.quantize_batch_encrypt_cohort_dev(c.iter_index, self.first_idx, n, n_elems, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits,
-                                                         _field_bits(q.element_bits, q.num_clients), du, outs, psum.buf, mask_buf)
-        else:
-            took = eng.quantize_encrypt_cohort_dev(c.iter_index, self.first_idx, n, _cipher_mod.N_JOBS, rows, srcs, dts, q.element_bits, du, outs,
-                                                   psum.buf, mask_buf)
+            scratch = (self._cut_scratch if need else None,)
+        took = getattr(eng, name)(c.iter_index, idxs if by_list else idxs[0] if idxs else self.first_idx, *((n, n_elems) if batch else (n,)), jobs, rows,
+                                  srcs, dts, q.element_bits, *((_field_bits(q.element_bits, q.num_clients),) if batch else ()), du, outs, psum.buf,
+                                  *(() if self.compact else (mask_buf,)), *scratch)
         if took and dmask is not None:
             ld._cohort_mask = (psum.ptr, dmask, c.iter_index) + _telescoped(idxs)
         return took

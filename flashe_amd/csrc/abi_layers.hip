@@ -530,36 +530,10 @@ static int cohort_check_args(flashe_ctx *ctx, const char *who, int n_clients, ui
     return FLASHE_OK;
 }
 
-// the same checks for a cohort given by the cipher indices of the clients that report (the *_cohort_runs_dev entry points): strictly
-// ascending and below 2^32 - 1 (cohort_streams.h).  *too_many: the indices need more streams than one launch holds -- not an error of the
-// arguments but a shape the launch declines.
-static int cohort_check_runs(flashe_ctx *ctx, const char *who, const uint32_t *idx, int n_clients, uint64_t n, const flashe_tensor_layer *layers,
-                             int n_layers, const void *const *src_dev, bool outs, int element_bits, const double *u_dev, bool *too_many)
-{
-    if (int rc = cohort_check_args(ctx, who, n_clients, n, layers, n_layers, src_dev, outs && idx, element_bits, u_dev)) return rc;
-    flashe_tables::CohortStreams st;
-    const flashe_tables::CohortStreamsStatus v = flashe_tables::cohort_streams(idx, n_clients, flashe_tables::kCohortMaxStreams, st);
-    if (v == flashe_tables::kCohortStreamsBadIdx)
-        return fail(ctx, FLASHE_EINVAL, "%s: the cipher indices must be strictly ascending and below 2^32 - 1 (idx + 1 has to fit the 4-byte prefix field, jzf_flashe.py:352-353)", who);
-    *too_many = v == flashe_tables::kCohortStreamsTooMany;
-    return FLASHE_OK;
-}
-
 // ---- a cohort of co-located clients: C float models -> C ciphertexts + their sum (+ the decrypt mask) in one chained launch ----
 // The shared layer table, the C x n_layers sources and their storage dtypes.  A source already in its row's compute type without SHIFT is
 // read where it lies; every other one goes through ONE stage pass (tensors.hip) into ctx scratch, all clients together.
-// (the two entry points below share their argument checks -- cohort_check -- and their table and stage pass -- cohort_stage)
-static int cohort_check(flashe_ctx *ctx, const char *who, uint32_t first_idx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers,
-                        const void *const *src_dev, bool outs, int element_bits, const double *u_dev, std::vector<uint32_t> &idx)
-{
-    if (int rc = cohort_check_args(ctx, who, n_clients, n, layers, n_layers, src_dev, outs, element_bits, u_dev)) return rc;
-    idx.resize(static_cast<size_t>(n_clients));
-    for (int c = 0; c < n_clients; c++) {
-        idx[c] = first_idx + static_cast<uint32_t>(c);
-        if (idx[c] < first_idx) return fail(ctx, FLASHE_EINVAL, "the cohort's cipher indices wrap around 2^32");
-    }
-    return check_double_idx(ctx, FLASHE_SCHEME_DOUBLE, idx.data(), n_clients);
-}
+// (every form of the launch runs through one body, quantize_encrypt_cohort below)
 
 // a cohort's shared row names the type its layer is computed in
 static int check_compute_row(flashe_ctx *ctx, int l, int32_t dtype)
@@ -682,20 +656,104 @@ static int cohort_launched(flashe_ctx *ctx, hipError_t e, const char *who, const
     return FLASHE_OK;
 }
 
+// the scratch of a cut launch: needed from two pieces upward, 16-byte aligned, and none of the launch's outputs
+static int cohort_check_scratch(flashe_ctx *ctx, int parts, int n_clients, const void *scratch_dev, const void *const *ct_dev, const void *sum_out_dev,
+                                const void *dmask_dev)
+{
+    if (!scratch_dev) return parts > 1 ? fail(ctx, FLASHE_EINVAL, "scratch_dev is null: the launch runs %d pieces (flashe_cohort_cut_parts)", parts) : FLASHE_OK;
+    if (!aligned16(scratch_dev)) return fail(ctx, FLASHE_EINVAL, "scratch_dev must be 16-byte aligned");
+    if (scratch_dev == sum_out_dev || scratch_dev == dmask_dev) return fail(ctx, FLASHE_EINVAL, "scratch_dev aliases the sum or the mask");
+    for (int c = 0; c < n_clients; c++)
+        if (scratch_dev == ct_dev[c]) return fail(ctx, FLASHE_EINVAL, "scratch_dev aliases client %d's ciphertext", c);
+    return FLASHE_OK;
+}
+
+// What tells the eleven chained cohort entry points apart, besides the element type T of their vectors (uint64_t: the wide two-limb
+// layout; uint32_t: the compact one, no decrypt mask).  `what` names the launch in a refusal.
+struct CohortForm {
+    const char *who, *what;
+    bool by_list;            // the cipher indices: the list idx of the clients that report (the *_runs_* forms), else first_idx + c
+    bool batched;            // a batched job: the table and sources over n_values values, the chain over n_elems batched elements
+    bool cut;                // the short cohort (cohort_cut.h): no length rule, the chain cut into pieces, scratch_dev
+};
+
+// The one body of those entry points, every step once and in the order the refusals are documented in: the arguments and the cipher
+// indices (a list that needs more streams than one launch holds is not an error of the arguments but a shape the launch declines), the
+// batched rows and their count, the outputs, the admission -- asked of the launcher's own predicate before anything is staged --, the
+// scratch of a cut launch, the stage pass, and launch(idx, cc, cb) (cb: null unless batched).  Not batched: n_values == n_elems.
+extern "C++" template <class T, class Launch>
+static int quantize_encrypt_cohort(flashe_ctx *ctx, const CohortForm &f, uint32_t first_idx, const uint32_t *idx, int n_clients, uint64_t n_values,
+                                   uint64_t n_elems, uint32_t n_jobs, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
+                                   const int32_t *src_dtype, int element_bits, int field_bits, const double *u_dev, T *const *ct_dev, T *sum_out_dev,
+                                   T *dmask_dev, T *scratch_dev, Launch launch)
+{
+    constexpr bool compact = sizeof(T) == 4;
+    int rc = cohort_check_args(ctx, f.who, n_clients, n_values, layers, n_layers, src_dev, ct_dev && sum_out_dev && (idx || !f.by_list), element_bits, u_dev);
+    if (rc) return rc;
+    std::vector<uint32_t> consecutive;
+    bool too_many = false;
+    if (f.by_list) {
+        // strictly ascending and below 2^32 - 1 (cohort_streams.h)
+        flashe_tables::CohortStreams st;
+        const flashe_tables::CohortStreamsStatus v = flashe_tables::cohort_streams(idx, n_clients, flashe_tables::kCohortMaxStreams, st);
+        if (v == flashe_tables::kCohortStreamsBadIdx)
+            return fail(ctx, FLASHE_EINVAL, "%s: the cipher indices must be strictly ascending and below 2^32 - 1 (idx + 1 has to fit the 4-byte prefix field, jzf_flashe.py:352-353)", f.who);
+        too_many = v == flashe_tables::kCohortStreamsTooMany;
+    } else {
+        consecutive.resize(static_cast<size_t>(n_clients));
+        for (int c = 0; c < n_clients; c++) {
+            consecutive[c] = first_idx + static_cast<uint32_t>(c);
+            if (consecutive[c] < first_idx) return fail(ctx, FLASHE_EINVAL, "the cohort's cipher indices wrap around 2^32");
+        }
+        idx = consecutive.data();
+        if ((rc = check_double_idx(ctx, FLASHE_SCHEME_DOUBLE, idx, n_clients))) return rc;
+    }
+    // the batched rows of the non-empty layers (cohort_stage's rows, in its order): first element, value count
+    uint64_t bs = 0;
+    std::vector<uint64_t> rows;
+    if (f.batched) {
+        if ((rc = check_batch_bits(ctx, element_bits, field_bits, &bs))) return rc;
+        auto size_of = [&](int l) { return layer_end(layers, n_layers, l, n_values) - layers[l].start; };
+        const uint64_t e = flashe_tables::batched_elems(n_layers, bs, size_of, [&](int l, uint64_t elem, uint64_t) { rows.push_back(elem); rows.push_back(size_of(l)); });
+        if ((rc = check_batched_count(ctx, e, n_elems))) return rc;
+    }
+    if (compact && n_jobs == 0) return fail(ctx, FLASHE_EINVAL, "n_jobs must be >= 1");
+    if ((rc = cohort_check_outs<T>(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, compact ? nullptr : dmask_dev))) return rc;
+    // a cut launch answers with its pieces (consecutive clients: cohort_cut_parts_of; a list, where every gap is a cut: cohort_cut_pieces_of)
+    const bool gated = too_many || (compact && flashe_ctx_compact_layout(ctx) != 1);
+    int parts = 0, begins[flashe_tables::kCutMaxParts + 1];
+    if (f.cut && !gated && !(f.batched && (bs < 5 || bs > 7)))
+        parts = f.by_list ? cohort_cut_pieces_of(ctx->env, n_clients, idx, n_elems, n_jobs, compact, static_cast<int>(bs), begins)
+                          : cohort_cut_parts_of(ctx->env, n_clients, n_elems, n_jobs, compact);
+    const bool admitted = f.cut ? parts != 0
+                                : !gated && (compact ? small_cohort_admits(ctx->env, n_clients, n_elems, n_jobs, true)
+                                                     : cohort_chain_admits(ctx->env, n_clients, n_elems, static_cast<int>(bs)));
+    if (!admitted) return cohort_declined(ctx, f.who, f.what);
+    if (f.cut && (rc = cohort_check_scratch(ctx, parts, n_clients, scratch_dev, reinterpret_cast<const void *const *>(ct_dev), sum_out_dev,
+                                            compact ? nullptr : dmask_dev)))
+        return rc;
+    CohortCodec cc{};
+    const char *rows_dev = nullptr;
+    if ((rc = cohort_stage(ctx, n_clients, n_values, layers, n_layers, src_dev, src_dtype, element_bits, cc, f.batched ? rows.data() : nullptr,
+                           rows.size() * sizeof(uint64_t), &rows_dev)))
+        return rc;
+    CohortBatch cb{};
+    cb.rows = reinterpret_cast<const uint64_t *>(rows_dev);
+    cb.n_values = n_values;
+    cb.field_bits = field_bits;
+    return cohort_launched(ctx, launch(idx, cc, f.batched ? &cb : nullptr), f.who, f.what);
+}
+
 int flashe_quantize_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs,
                                        const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
                                        int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev, uint64_t *dmask_dev)
 {
     CHECK_CTX(ctx);
-    static const char who[] = "flashe_quantize_encrypt_cohort_dev";
-    std::vector<uint32_t> idx;
-    int rc = cohort_check(ctx, who, first_idx, n_clients, n, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, idx);
-    if (rc || (rc = cohort_check_outs(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, dmask_dev))) return rc;
-    if (!cohort_chain_admits(ctx->env, n_clients, n, 0)) return cohort_declined(ctx, who, "cohort");
-    CohortCodec cc{};
-    if ((rc = cohort_stage(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, cc))) return rc;
-    return cohort_launched(ctx, launch_prf_cohort_sum(ctx->env, iter, n_clients, idx.data(), cc, nullptr, u_dev, ct_dev, sum_out_dev, n, n_jobs, dmask_dev),
-                           who, "cohort");
+    return quantize_encrypt_cohort<uint64_t>(
+        ctx, {"flashe_quantize_encrypt_cohort_dev", "cohort", false, false, false}, first_idx, nullptr, n_clients, n, n, n_jobs, layers, n_layers, src_dev,
+        src_dtype, element_bits, 0, u_dev, ct_dev, sum_out_dev, dmask_dev, nullptr, [&](const uint32_t *ids, const CohortCodec &cc, const CohortBatch *) {
+            return launch_prf_cohort_sum(ctx->env, iter, n_clients, ids, cc, nullptr, u_dev, ct_dev, sum_out_dev, n, n_jobs, dmask_dev);
+        });
 }
 
 // the same cohort in the compact layout at int_bits <= 32 (prf_small_cohort_kernel): uint32 ciphertexts and their uint32 sum, no decrypt mask
@@ -704,16 +762,68 @@ int flashe_quantize_encrypt_cohort_u32_dev(flashe_ctx *ctx, uint32_t iter, uint3
                                            int element_bits, const double *u_dev, uint32_t *const *ct_dev, uint32_t *sum_out_dev)
 {
     CHECK_CTX(ctx);
-    static const char who[] = "flashe_quantize_encrypt_cohort_u32_dev";
-    std::vector<uint32_t> idx;
-    int rc = cohort_check(ctx, who, first_idx, n_clients, n, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, idx);
-    if (rc) return rc;
-    if (n_jobs == 0) return fail(ctx, FLASHE_EINVAL, "n_jobs must be >= 1");
-    if ((rc = cohort_check_outs<uint32_t>(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, nullptr))) return rc;
-    if (flashe_ctx_compact_layout(ctx) != 1 || !small_cohort_admits(ctx->env, n_clients, n, n_jobs, true)) return cohort_declined(ctx, who, "compact cohort");
-    CohortCodec cc{};
-    if ((rc = cohort_stage(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, cc))) return rc;
-    return cohort_launched(ctx, launch_small_cohort_sum(ctx->env, iter, n_clients, idx.data(), cc, u_dev, ct_dev, sum_out_dev, n, n_jobs), who, "compact cohort");
+    return quantize_encrypt_cohort<uint32_t>(
+        ctx, {"flashe_quantize_encrypt_cohort_u32_dev", "compact cohort", false, false, false}, first_idx, nullptr, n_clients, n, n, n_jobs, layers, n_layers,
+        src_dev, src_dtype, element_bits, 0, u_dev, ct_dev, sum_out_dev, nullptr, nullptr, [&](const uint32_t *ids, const CohortCodec &cc, const CohortBatch *) {
+            return launch_small_cohort_sum(ctx->env, iter, n_clients, ids, cc, u_dev, ct_dev, sum_out_dev, n, n_jobs);
+        });
+}
+
+// the cohort of a BATCHED job (prf_chain_cohort_batch_kernel): the same table, sources and stage pass over the n_values values; the chain
+// runs over the n_elems batched elements
+int flashe_quantize_batch_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n_values, uint64_t n_elems,
+                                             uint32_t n_jobs, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
+                                             const int32_t *src_dtype, int element_bits, int field_bits, const double *u_dev, uint64_t *const *ct_dev,
+                                             uint64_t *sum_out_dev, uint64_t *dmask_dev)
+{
+    CHECK_CTX(ctx);
+    return quantize_encrypt_cohort<uint64_t>(
+        ctx, {"flashe_quantize_batch_encrypt_cohort_dev", "batched cohort", false, true, false}, first_idx, nullptr, n_clients, n_values, n_elems, n_jobs, layers,
+        n_layers, src_dev, src_dtype, element_bits, field_bits, u_dev, ct_dev, sum_out_dev, dmask_dev, nullptr,
+        [&](const uint32_t *ids, const CohortCodec &cc, const CohortBatch *cb) {
+            return launch_prf_cohort_sum(ctx->env, iter, n_clients, ids, cc, cb, u_dev, ct_dev, sum_out_dev, n_elems, n_jobs, dmask_dev);
+        });
+}
+
+// ---- the same three launches for a round in which clients DROPPED OUT: the cipher indices of the clients that report, any strictly
+// ascending list (one run: the launches above, bit for bit; several runs: prf_chain_cohort_runs_kernel / prf_small_cohort_runs_kernel /
+// prf_chain_cohort_batch_runs_kernel) ----
+int flashe_quantize_encrypt_cohort_runs_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                            const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                            int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev, uint64_t *dmask_dev)
+{
+    CHECK_CTX(ctx);
+    return quantize_encrypt_cohort<uint64_t>(
+        ctx, {"flashe_quantize_encrypt_cohort_runs_dev", "cohort", true, false, false}, 0, idx, n_clients, n, n, n_jobs, layers, n_layers, src_dev, src_dtype,
+        element_bits, 0, u_dev, ct_dev, sum_out_dev, dmask_dev, nullptr, [&](const uint32_t *ids, const CohortCodec &cc, const CohortBatch *) {
+            return launch_prf_cohort_sum(ctx->env, iter, n_clients, ids, cc, nullptr, u_dev, ct_dev, sum_out_dev, n, n_jobs, dmask_dev);
+        });
+}
+
+int flashe_quantize_encrypt_cohort_runs_u32_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                                const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                                int element_bits, const double *u_dev, uint32_t *const *ct_dev, uint32_t *sum_out_dev)
+{
+    CHECK_CTX(ctx);
+    return quantize_encrypt_cohort<uint32_t>(
+        ctx, {"flashe_quantize_encrypt_cohort_runs_u32_dev", "compact cohort", true, false, false}, 0, idx, n_clients, n, n, n_jobs, layers, n_layers, src_dev,
+        src_dtype, element_bits, 0, u_dev, ct_dev, sum_out_dev, nullptr, nullptr, [&](const uint32_t *ids, const CohortCodec &cc, const CohortBatch *) {
+            return launch_small_cohort_sum(ctx->env, iter, n_clients, ids, cc, u_dev, ct_dev, sum_out_dev, n, n_jobs);
+        });
+}
+
+int flashe_quantize_batch_encrypt_cohort_runs_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n_values, uint64_t n_elems,
+                                                  uint32_t n_jobs, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
+                                                  const int32_t *src_dtype, int element_bits, int field_bits, const double *u_dev, uint64_t *const *ct_dev,
+                                                  uint64_t *sum_out_dev, uint64_t *dmask_dev)
+{
+    CHECK_CTX(ctx);
+    return quantize_encrypt_cohort<uint64_t>(
+        ctx, {"flashe_quantize_batch_encrypt_cohort_runs_dev", "batched cohort", true, true, false}, 0, idx, n_clients, n_values, n_elems, n_jobs, layers,
+        n_layers, src_dev, src_dtype, element_bits, field_bits, u_dev, ct_dev, sum_out_dev, dmask_dev, nullptr,
+        [&](const uint32_t *ids, const CohortCodec &cc, const CohortBatch *cb) {
+            return launch_prf_cohort_sum(ctx->env, iter, n_clients, ids, cc, cb, u_dev, ct_dev, sum_out_dev, n_elems, n_jobs, dmask_dev);
+        });
 }
 
 // ---- the SHORT cohort: the two launches above for a vector that does not fill the chip uncut (cohort_cut.h) -- the chain cut into runs of
@@ -731,156 +841,6 @@ int flashe_cohort_cut_parts(flashe_ctx *ctx, int n_clients, uint64_t n, uint32_t
     if (!k) return cohort_declined(ctx, who, compact ? "cut compact cohort" : "cut cohort");
     *parts = k;
     return FLASHE_OK;
-}
-
-// the scratch of a cut launch: needed from two pieces upward, 16-byte aligned, and none of the launch's outputs
-static int cohort_check_scratch(flashe_ctx *ctx, int parts, int n_clients, const void *scratch_dev, const void *const *ct_dev, const void *sum_out_dev,
-                                const void *dmask_dev)
-{
-    if (!scratch_dev) return parts > 1 ? fail(ctx, FLASHE_EINVAL, "scratch_dev is null: the launch runs %d pieces (flashe_cohort_cut_parts)", parts) : FLASHE_OK;
-    if (!aligned16(scratch_dev)) return fail(ctx, FLASHE_EINVAL, "scratch_dev must be 16-byte aligned");
-    if (scratch_dev == sum_out_dev || scratch_dev == dmask_dev) return fail(ctx, FLASHE_EINVAL, "scratch_dev aliases the sum or the mask");
-    for (int c = 0; c < n_clients; c++)
-        if (scratch_dev == ct_dev[c]) return fail(ctx, FLASHE_EINVAL, "scratch_dev aliases client %d's ciphertext", c);
-    return FLASHE_OK;
-}
-
-int flashe_quantize_encrypt_cohort_cut_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs,
-                                           const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
-                                           int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev, uint64_t *dmask_dev,
-                                           uint64_t *scratch_dev)
-{
-    CHECK_CTX(ctx);
-    static const char who[] = "flashe_quantize_encrypt_cohort_cut_dev";
-    std::vector<uint32_t> idx;
-    int rc = cohort_check(ctx, who, first_idx, n_clients, n, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, idx);
-    if (rc || (rc = cohort_check_outs(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, dmask_dev))) return rc;
-    const int parts = cohort_cut_parts_of(ctx->env, n_clients, n, n_jobs, false);
-    if (!parts) return cohort_declined(ctx, who, "cut cohort");
-    if ((rc = cohort_check_scratch(ctx, parts, n_clients, scratch_dev, reinterpret_cast<const void *const *>(ct_dev), sum_out_dev, dmask_dev))) return rc;
-    CohortCodec cc{};
-    if ((rc = cohort_stage(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, cc))) return rc;
-    return cohort_launched(ctx, launch_prf_cohort_cut(ctx->env, iter, n_clients, idx.data(), cc, u_dev, ct_dev, sum_out_dev, n, n_jobs, dmask_dev, scratch_dev),
-                           who, "cut cohort");
-}
-
-int flashe_quantize_encrypt_cohort_cut_u32_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs,
-                                               const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
-                                               int element_bits, const double *u_dev, uint32_t *const *ct_dev, uint32_t *sum_out_dev, uint32_t *scratch_dev)
-{
-    CHECK_CTX(ctx);
-    static const char who[] = "flashe_quantize_encrypt_cohort_cut_u32_dev";
-    std::vector<uint32_t> idx;
-    int rc = cohort_check(ctx, who, first_idx, n_clients, n, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, idx);
-    if (rc) return rc;
-    if (n_jobs == 0) return fail(ctx, FLASHE_EINVAL, "n_jobs must be >= 1");
-    if ((rc = cohort_check_outs<uint32_t>(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, nullptr))) return rc;
-    const int parts = flashe_ctx_compact_layout(ctx) != 1 ? 0 : cohort_cut_parts_of(ctx->env, n_clients, n, n_jobs, true);
-    if (!parts) return cohort_declined(ctx, who, "cut compact cohort");
-    if ((rc = cohort_check_scratch(ctx, parts, n_clients, scratch_dev, reinterpret_cast<const void *const *>(ct_dev), sum_out_dev, nullptr))) return rc;
-    CohortCodec cc{};
-    if ((rc = cohort_stage(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, cc))) return rc;
-    return cohort_launched(ctx, launch_small_cohort_cut(ctx->env, iter, n_clients, idx.data(), cc, u_dev, ct_dev, sum_out_dev, n, n_jobs, scratch_dev), who,
-                           "cut compact cohort");
-}
-
-// the cohort of a BATCHED job (prf_chain_cohort_batch_kernel): the same table, sources and stage pass over the n_values values; the chain
-// runs over the n_elems batched elements
-int flashe_quantize_batch_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n_values, uint64_t n_elems,
-                                             uint32_t n_jobs, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
-                                             const int32_t *src_dtype, int element_bits, int field_bits, const double *u_dev, uint64_t *const *ct_dev,
-                                             uint64_t *sum_out_dev, uint64_t *dmask_dev)
-{
-    CHECK_CTX(ctx);
-    static const char who[] = "flashe_quantize_batch_encrypt_cohort_dev";
-    std::vector<uint32_t> idx;
-    uint64_t bs = 0;
-    int rc = cohort_check(ctx, who, first_idx, n_clients, n_values, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, idx);
-    if (rc || (rc = check_batch_bits(ctx, element_bits, field_bits, &bs))) return rc;
-    // the batched rows of the non-empty layers (cohort_stage's rows, in its order): first element, value count
-    std::vector<uint64_t> rows;
-    auto size_of = [&](int l) { return layer_end(layers, n_layers, l, n_values) - layers[l].start; };
-    const uint64_t e = flashe_tables::batched_elems(n_layers, bs, size_of, [&](int l, uint64_t elem, uint64_t) { rows.push_back(elem); rows.push_back(size_of(l)); });
-    if ((rc = check_batched_count(ctx, e, n_elems))) return rc;
-    if ((rc = cohort_check_outs(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, dmask_dev))) return rc;
-    if (!cohort_chain_admits(ctx->env, n_clients, n_elems, static_cast<int>(bs))) return cohort_declined(ctx, who, "batched cohort");
-    CohortCodec cc{};
-    const char *rows_dev = nullptr;
-    if ((rc = cohort_stage(ctx, n_clients, n_values, layers, n_layers, src_dev, src_dtype, element_bits, cc, rows.data(), rows.size() * sizeof(uint64_t),
-                           &rows_dev)))
-        return rc;
-    CohortBatch cb{};
-    cb.rows = reinterpret_cast<const uint64_t *>(rows_dev);
-    cb.n_values = n_values;
-    cb.field_bits = field_bits;
-    return cohort_launched(ctx, launch_prf_cohort_sum(ctx->env, iter, n_clients, idx.data(), cc, &cb, u_dev, ct_dev, sum_out_dev, n_elems, n_jobs, dmask_dev),
-                           who, "batched cohort");
-}
-
-// ---- the same two launches for a round in which clients DROPPED OUT: the cipher indices of the clients that report, any strictly
-// ascending list (one run: the launches above, bit for bit; several runs: prf_chain_cohort_runs_kernel / prf_chain_cohort_batch_runs_kernel) ----
-int flashe_quantize_encrypt_cohort_runs_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n, uint32_t n_jobs,
-                                            const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
-                                            int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev, uint64_t *dmask_dev)
-{
-    CHECK_CTX(ctx);
-    static const char who[] = "flashe_quantize_encrypt_cohort_runs_dev";
-    bool too_many = false;
-    int rc = cohort_check_runs(ctx, who, idx, n_clients, n, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, &too_many);
-    if (rc || (rc = cohort_check_outs(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, dmask_dev))) return rc;
-    if (too_many || !cohort_chain_admits(ctx->env, n_clients, n, 0)) return cohort_declined(ctx, who, "cohort");
-    CohortCodec cc{};
-    if ((rc = cohort_stage(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, cc))) return rc;
-    return cohort_launched(ctx, launch_prf_cohort_sum(ctx->env, iter, n_clients, idx, cc, nullptr, u_dev, ct_dev, sum_out_dev, n, n_jobs, dmask_dev), who, "cohort");
-}
-
-// the compact layout at int_bits <= 32 (one run: prf_small_cohort_kernel, bit for bit; several runs: prf_small_cohort_runs_kernel): uint32
-// ciphertexts and their uint32 sum, no decrypt mask
-int flashe_quantize_encrypt_cohort_runs_u32_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n, uint32_t n_jobs,
-                                                const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
-                                                int element_bits, const double *u_dev, uint32_t *const *ct_dev, uint32_t *sum_out_dev)
-{
-    CHECK_CTX(ctx);
-    static const char who[] = "flashe_quantize_encrypt_cohort_runs_u32_dev";
-    bool too_many = false;
-    int rc = cohort_check_runs(ctx, who, idx, n_clients, n, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, &too_many);
-    if (rc) return rc;
-    if (n_jobs == 0) return fail(ctx, FLASHE_EINVAL, "n_jobs must be >= 1");
-    if ((rc = cohort_check_outs<uint32_t>(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, nullptr))) return rc;
-    if (too_many || flashe_ctx_compact_layout(ctx) != 1 || !small_cohort_admits(ctx->env, n_clients, n, n_jobs, true)) return cohort_declined(ctx, who, "compact cohort");
-    CohortCodec cc{};
-    if ((rc = cohort_stage(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, cc))) return rc;
-    return cohort_launched(ctx, launch_small_cohort_sum(ctx->env, iter, n_clients, idx, cc, u_dev, ct_dev, sum_out_dev, n, n_jobs), who, "compact cohort");
-}
-
-int flashe_quantize_batch_encrypt_cohort_runs_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n_values, uint64_t n_elems,
-                                                  uint32_t n_jobs, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
-                                                  const int32_t *src_dtype, int element_bits, int field_bits, const double *u_dev, uint64_t *const *ct_dev,
-                                                  uint64_t *sum_out_dev, uint64_t *dmask_dev)
-{
-    CHECK_CTX(ctx);
-    static const char who[] = "flashe_quantize_batch_encrypt_cohort_runs_dev";
-    bool too_many = false;
-    uint64_t bs = 0;
-    int rc = cohort_check_runs(ctx, who, idx, n_clients, n_values, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, &too_many);
-    if (rc || (rc = check_batch_bits(ctx, element_bits, field_bits, &bs))) return rc;
-    std::vector<uint64_t> rows;
-    auto size_of = [&](int l) { return layer_end(layers, n_layers, l, n_values) - layers[l].start; };
-    const uint64_t e = flashe_tables::batched_elems(n_layers, bs, size_of, [&](int l, uint64_t elem, uint64_t) { rows.push_back(elem); rows.push_back(size_of(l)); });
-    if ((rc = check_batched_count(ctx, e, n_elems))) return rc;
-    if ((rc = cohort_check_outs(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, dmask_dev))) return rc;
-    if (too_many || !cohort_chain_admits(ctx->env, n_clients, n_elems, static_cast<int>(bs))) return cohort_declined(ctx, who, "batched cohort");
-    CohortCodec cc{};
-    const char *rows_dev = nullptr;
-    if ((rc = cohort_stage(ctx, n_clients, n_values, layers, n_layers, src_dev, src_dtype, element_bits, cc, rows.data(), rows.size() * sizeof(uint64_t),
-                           &rows_dev)))
-        return rc;
-    CohortBatch cb{};
-    cb.rows = reinterpret_cast<const uint64_t *>(rows_dev);
-    cb.n_values = n_values;
-    cb.field_bits = field_bits;
-    return cohort_launched(ctx, launch_prf_cohort_sum(ctx->env, iter, n_clients, idx, cc, &cb, u_dev, ct_dev, sum_out_dev, n_elems, n_jobs, dmask_dev),
-                           who, "batched cohort");
 }
 
 // ---- the SHORT cohort for any strictly ascending cipher indices in at most kCutMaxParts runs, and for a batched job (cohort_cut_pieces,
@@ -904,24 +864,43 @@ int flashe_cohort_cut_pieces(flashe_ctx *ctx, const uint32_t *idx, int n_clients
     return FLASHE_OK;
 }
 
+int flashe_quantize_encrypt_cohort_cut_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                           const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                           int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev, uint64_t *dmask_dev,
+                                           uint64_t *scratch_dev)
+{
+    CHECK_CTX(ctx);
+    return quantize_encrypt_cohort<uint64_t>(
+        ctx, {"flashe_quantize_encrypt_cohort_cut_dev", "cut cohort", false, false, true}, first_idx, nullptr, n_clients, n, n, n_jobs, layers, n_layers, src_dev,
+        src_dtype, element_bits, 0, u_dev, ct_dev, sum_out_dev, dmask_dev, scratch_dev, [&](const uint32_t *ids, const CohortCodec &cc, const CohortBatch *) {
+            return launch_prf_cohort_cut(ctx->env, iter, n_clients, ids, cc, u_dev, ct_dev, sum_out_dev, n, n_jobs, dmask_dev, scratch_dev);
+        });
+}
+
+int flashe_quantize_encrypt_cohort_cut_u32_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                               const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                               int element_bits, const double *u_dev, uint32_t *const *ct_dev, uint32_t *sum_out_dev, uint32_t *scratch_dev)
+{
+    CHECK_CTX(ctx);
+    return quantize_encrypt_cohort<uint32_t>(
+        ctx, {"flashe_quantize_encrypt_cohort_cut_u32_dev", "cut compact cohort", false, false, true}, first_idx, nullptr, n_clients, n, n, n_jobs, layers,
+        n_layers, src_dev, src_dtype, element_bits, 0, u_dev, ct_dev, sum_out_dev, nullptr, scratch_dev,
+        [&](const uint32_t *ids, const CohortCodec &cc, const CohortBatch *) {
+            return launch_small_cohort_cut(ctx->env, iter, n_clients, ids, cc, u_dev, ct_dev, sum_out_dev, n, n_jobs, scratch_dev);
+        });
+}
+
 int flashe_quantize_encrypt_cohort_cut_runs_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n, uint32_t n_jobs,
                                                 const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
                                                 int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev,
                                                 uint64_t *dmask_dev, uint64_t *scratch_dev)
 {
     CHECK_CTX(ctx);
-    static const char who[] = "flashe_quantize_encrypt_cohort_cut_runs_dev";
-    bool too_many = false;
-    int rc = cohort_check_runs(ctx, who, idx, n_clients, n, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, &too_many);
-    if (rc || (rc = cohort_check_outs(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, dmask_dev))) return rc;
-    int begins[flashe_tables::kCutMaxParts + 1];
-    const int parts = too_many ? 0 : cohort_cut_pieces_of(ctx->env, n_clients, idx, n, n_jobs, false, 0, begins);
-    if (!parts) return cohort_declined(ctx, who, "cut cohort");
-    if ((rc = cohort_check_scratch(ctx, parts, n_clients, scratch_dev, reinterpret_cast<const void *const *>(ct_dev), sum_out_dev, dmask_dev))) return rc;
-    CohortCodec cc{};
-    if ((rc = cohort_stage(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, cc))) return rc;
-    return cohort_launched(ctx, launch_prf_cohort_cut(ctx->env, iter, n_clients, idx, cc, u_dev, ct_dev, sum_out_dev, n, n_jobs, dmask_dev, scratch_dev), who,
-                           "cut cohort");
+    return quantize_encrypt_cohort<uint64_t>(
+        ctx, {"flashe_quantize_encrypt_cohort_cut_runs_dev", "cut cohort", true, false, true}, 0, idx, n_clients, n, n, n_jobs, layers, n_layers, src_dev,
+        src_dtype, element_bits, 0, u_dev, ct_dev, sum_out_dev, dmask_dev, scratch_dev, [&](const uint32_t *ids, const CohortCodec &cc, const CohortBatch *) {
+            return launch_prf_cohort_cut(ctx->env, iter, n_clients, ids, cc, u_dev, ct_dev, sum_out_dev, n, n_jobs, dmask_dev, scratch_dev);
+        });
 }
 
 int flashe_quantize_encrypt_cohort_cut_runs_u32_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n, uint32_t n_jobs,
@@ -930,20 +909,12 @@ int flashe_quantize_encrypt_cohort_cut_runs_u32_dev(flashe_ctx *ctx, uint32_t it
                                                     uint32_t *sum_out_dev, uint32_t *scratch_dev)
 {
     CHECK_CTX(ctx);
-    static const char who[] = "flashe_quantize_encrypt_cohort_cut_runs_u32_dev";
-    bool too_many = false;
-    int rc = cohort_check_runs(ctx, who, idx, n_clients, n, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, &too_many);
-    if (rc) return rc;
-    if (n_jobs == 0) return fail(ctx, FLASHE_EINVAL, "n_jobs must be >= 1");
-    if ((rc = cohort_check_outs<uint32_t>(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, nullptr))) return rc;
-    int begins[flashe_tables::kCutMaxParts + 1];
-    const int parts = too_many || flashe_ctx_compact_layout(ctx) != 1 ? 0 : cohort_cut_pieces_of(ctx->env, n_clients, idx, n, n_jobs, true, 0, begins);
-    if (!parts) return cohort_declined(ctx, who, "cut compact cohort");
-    if ((rc = cohort_check_scratch(ctx, parts, n_clients, scratch_dev, reinterpret_cast<const void *const *>(ct_dev), sum_out_dev, nullptr))) return rc;
-    CohortCodec cc{};
-    if ((rc = cohort_stage(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, cc))) return rc;
-    return cohort_launched(ctx, launch_small_cohort_cut(ctx->env, iter, n_clients, idx, cc, u_dev, ct_dev, sum_out_dev, n, n_jobs, scratch_dev), who,
-                           "cut compact cohort");
+    return quantize_encrypt_cohort<uint32_t>(
+        ctx, {"flashe_quantize_encrypt_cohort_cut_runs_u32_dev", "cut compact cohort", true, false, true}, 0, idx, n_clients, n, n, n_jobs, layers, n_layers,
+        src_dev, src_dtype, element_bits, 0, u_dev, ct_dev, sum_out_dev, nullptr, scratch_dev,
+        [&](const uint32_t *ids, const CohortCodec &cc, const CohortBatch *) {
+            return launch_small_cohort_cut(ctx->env, iter, n_clients, ids, cc, u_dev, ct_dev, sum_out_dev, n, n_jobs, scratch_dev);
+        });
 }
 
 int flashe_quantize_batch_encrypt_cohort_cut_runs_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n_values,
@@ -953,36 +924,16 @@ int flashe_quantize_batch_encrypt_cohort_cut_runs_dev(flashe_ctx *ctx, uint32_t 
                                                       uint64_t *scratch_dev)
 {
     CHECK_CTX(ctx);
-    static const char who[] = "flashe_quantize_batch_encrypt_cohort_cut_runs_dev";
-    bool too_many = false;
-    uint64_t bs = 0;
-    int rc = cohort_check_runs(ctx, who, idx, n_clients, n_values, layers, n_layers, src_dev, ct_dev && sum_out_dev, element_bits, u_dev, &too_many);
-    if (rc || (rc = check_batch_bits(ctx, element_bits, field_bits, &bs))) return rc;
-    std::vector<uint64_t> rows;
-    auto size_of = [&](int l) { return layer_end(layers, n_layers, l, n_values) - layers[l].start; };
-    const uint64_t e = flashe_tables::batched_elems(n_layers, bs, size_of, [&](int l, uint64_t elem, uint64_t) { rows.push_back(elem); rows.push_back(size_of(l)); });
-    if ((rc = check_batched_count(ctx, e, n_elems))) return rc;
-    if ((rc = cohort_check_outs(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, dmask_dev))) return rc;
-    int begins[flashe_tables::kCutMaxParts + 1];
-    const int parts = too_many || bs < 5 || bs > 7 ? 0 : cohort_cut_pieces_of(ctx->env, n_clients, idx, n_elems, n_jobs, false, static_cast<int>(bs), begins);
-    if (!parts) return cohort_declined(ctx, who, "cut batched cohort");
-    if ((rc = cohort_check_scratch(ctx, parts, n_clients, scratch_dev, reinterpret_cast<const void *const *>(ct_dev), sum_out_dev, dmask_dev))) return rc;
-    CohortCodec cc{};
-    const char *rows_dev = nullptr;
-    if ((rc = cohort_stage(ctx, n_clients, n_values, layers, n_layers, src_dev, src_dtype, element_bits, cc, rows.data(), rows.size() * sizeof(uint64_t),
-                           &rows_dev)))
-        return rc;
-    CohortBatch cb{};
-    cb.rows = reinterpret_cast<const uint64_t *>(rows_dev);
-    cb.n_values = n_values;
-    cb.field_bits = field_bits;
-    return cohort_launched(ctx, launch_prf_cohort_batch_cut(ctx->env, iter, n_clients, idx, cc, cb, u_dev, ct_dev, sum_out_dev, n_elems, n_jobs, dmask_dev,
-                                                            scratch_dev),
-                           who, "cut batched cohort");
+    return quantize_encrypt_cohort<uint64_t>(
+        ctx, {"flashe_quantize_batch_encrypt_cohort_cut_runs_dev", "cut batched cohort", true, true, true}, 0, idx, n_clients, n_values, n_elems, n_jobs, layers,
+        n_layers, src_dev, src_dtype, element_bits, field_bits, u_dev, ct_dev, sum_out_dev, dmask_dev, scratch_dev,
+        [&](const uint32_t *ids, const CohortCodec &cc, const CohortBatch *cb) {
+            return launch_prf_cohort_batch_cut(ctx->env, iter, n_clients, ids, cc, *cb, u_dev, ct_dev, sum_out_dev, n_elems, n_jobs, dmask_dev, scratch_dev);
+        });
 }
 
 // ---- the cohort's ONLINE step with masks the caller holds (a precompute job's cohort: the mask chain ran in idle time) ----
-// What the three entry points below share: the checks of the chained cohorts (cohort_check's, without cipher indices), the vectors -- every
+// What the three entry points below share: the checks of the chained cohorts (cohort_check_args', without cipher indices), the vectors -- every
 // mask and ciphertext given and aligned to its element, the sum apart from all of them and from every source --, cohort_stage's table,
 // sources and stage pass with the mask and ciphertext pointers (and the batched rows) behind it in the same upload, one launch.
 // plans: one draw plan per client, uploaded behind the pointers (flashe_tables::prepared_draws_block; batched: behind the rows and the

@@ -717,29 +717,31 @@ class Engine:
         self._check(self._lib.flashe_quantize_encrypt_tensors_dev(self._h, it, idx, scheme, n, n_jobs, first, count, arr, nl, element_bits,
                                                                   self._ptr(u), self._ptr(ct)))
 
+    def _cohort_launch(self, name, it, idx, ns, n_jobs, layers, srcs, dtypes, bits, u, cts, *vecs):
+        """The library's chained cohort launch `name` (_lib.COHORT_LAUNCHES): the shared table, the sources, the ciphertext pointers and -- a
+        _runs_ form -- the checked cipher indices marshalled, one call.  ns = (n,) or (n_values, n_elems), bits = (element_bits,) or
+        (element_bits, field_bits), vecs = the sum and what the form takes behind it (dmask, scratch).  False: the library declined."""
+        arr, nl = self._tensor_layers(layers)
+        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
+        pc, _k = self._ptr_array(cts)
+        idx = self._cohort_idx(idx, C)[0] if "_runs_" in name else int(idx)
+        rc = getattr(self._lib, name)(self._h, it, idx, C, *(int(n) for n in ns), n_jobs, arr, nl, ps, pd, *bits, self._ptr(u), pc,
+                                      *(self._ptr(v) for v in vecs))
+        return self._took(rc)
+
     def quantize_encrypt_cohort_dev(self, it, first_idx, n, n_jobs, layers, srcs, dtypes, element_bits, u, cts, sum_out, dmask=None):
         """A cohort's client steps as ONE chained launch (flashe_quantize_encrypt_cohort_dev): layers = the shared table, (start, None,
         alpha, shift, compute dtype code, flags) per layer; srcs[c][l] / dtypes[c][l] = device pointer and storage dtype code of client
         c's layer l; u = the len(srcs) * n draws, client-major; cts = one n-element vector per client; sum_out / dmask (optional) = their
         sum and the cohort's decrypt mask.  Returns False -- nothing was launched -- when the library declines the shape (FLASHE_ENOTSUP:
         the caller quantises per client and calls encrypt_batch_sum_dev), True otherwise."""
-        arr, nl = self._tensor_layers(layers)
-        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
-        pc, _k = self._ptr_array(cts)
-        rc = self._lib.flashe_quantize_encrypt_cohort_dev(self._h, it, int(first_idx), C, int(n), n_jobs, arr, nl, ps, pd, element_bits,
-                                                          self._ptr(u), pc, self._ptr(sum_out), self._ptr(dmask))
-        return self._took(rc)
+        return self._cohort_launch("flashe_quantize_encrypt_cohort_dev", it, first_idx, (n,), n_jobs, layers, srcs, dtypes, (element_bits,), u, cts, sum_out, dmask)
 
     def quantize_encrypt_cohort_u32_dev(self, it, first_idx, n, n_jobs, layers, srcs, dtypes, element_bits, u, cts, sum_out):
         """quantize_encrypt_cohort_dev in the compact layout (flashe_quantize_encrypt_cohort_u32_dev, int_bits 16 / 20 / 23 / 24 / 32): cts and
         sum_out are uint32 vectors of n elements, there is no decrypt mask.  Returns False -- nothing was launched -- when the library
         declines the shape (FLASHE_ENOTSUP: the caller quantises per client and calls encrypt_batch_sum_u32_dev), True otherwise."""
-        arr, nl = self._tensor_layers(layers)
-        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
-        pc, _k = self._ptr_array(cts)
-        rc = self._lib.flashe_quantize_encrypt_cohort_u32_dev(self._h, it, int(first_idx), C, int(n), n_jobs, arr, nl, ps, pd, element_bits,
-                                                              self._ptr(u), pc, self._ptr(sum_out))
-        return self._took(rc)
+        return self._cohort_launch("flashe_quantize_encrypt_cohort_u32_dev", it, first_idx, (n,), n_jobs, layers, srcs, dtypes, (element_bits,), u, cts, sum_out)
 
     def cohort_cut_parts(self, n_clients, n, n_jobs, compact=False):
         """The pieces quantize_encrypt_cohort_cut_dev (compact: its _u32 form) will cut a cohort of n_clients clients with n values into
@@ -753,23 +755,15 @@ class Engine:
         cohort_cut_parts(...) runs of consecutive clients and one combine pass.  scratch: 16-byte aligned, parts x n x 16 bytes, twice
         that with dmask; may be None when parts == 1.  Returns False -- nothing was launched -- when the library declines the shape
         (FLASHE_ENOTSUP), True otherwise."""
-        arr, nl = self._tensor_layers(layers)
-        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
-        pc, _k = self._ptr_array(cts)
-        rc = self._lib.flashe_quantize_encrypt_cohort_cut_dev(self._h, it, int(first_idx), C, int(n), n_jobs, arr, nl, ps, pd, element_bits,
-                                                              self._ptr(u), pc, self._ptr(sum_out), self._ptr(dmask), self._ptr(scratch))
-        return self._took(rc)
+        return self._cohort_launch("flashe_quantize_encrypt_cohort_cut_dev", it, first_idx, (n,), n_jobs, layers, srcs, dtypes, (element_bits,), u, cts, sum_out,
+                                   dmask, scratch)
 
     def quantize_encrypt_cohort_cut_u32_dev(self, it, first_idx, n, n_jobs, layers, srcs, dtypes, element_bits, u, cts, sum_out, scratch=None):
         """quantize_encrypt_cohort_u32_dev for a vector of ANY length (flashe_quantize_encrypt_cohort_cut_u32_dev, int_bits 16 / 20 / 23 /
         24 / 32): scratch of cohort_cut_parts(..., compact=True) x n x 4 bytes, 16-byte aligned; may be None when parts == 1.  Returns
         False -- nothing was launched -- when the library declines the shape (FLASHE_ENOTSUP), True otherwise."""
-        arr, nl = self._tensor_layers(layers)
-        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
-        pc, _k = self._ptr_array(cts)
-        rc = self._lib.flashe_quantize_encrypt_cohort_cut_u32_dev(self._h, it, int(first_idx), C, int(n), n_jobs, arr, nl, ps, pd, element_bits,
-                                                                  self._ptr(u), pc, self._ptr(sum_out), self._ptr(scratch))
-        return self._took(rc)
+        return self._cohort_launch("flashe_quantize_encrypt_cohort_cut_u32_dev", it, first_idx, (n,), n_jobs, layers, srcs, dtypes, (element_bits,), u, cts,
+                                   sum_out, scratch)
 
     def quantize_batch_encrypt_cohort_dev(self, it, first_idx, n_values, n_elems, n_jobs, layers, srcs, dtypes, element_bits, field_bits, u, cts,
                                           sum_out, dmask=None):
@@ -778,12 +772,8 @@ class Engine:
         client-major; cts, sum_out and dmask (optional) are vectors of the n_elems batched elements.  Returns False -- nothing was
         launched -- when the library declines the shape (FLASHE_ENOTSUP: the caller runs quantize_batch_tensors_dev per client and
         encrypt_batch_sum_dev), True otherwise."""
-        arr, nl = self._tensor_layers(layers)
-        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
-        pc, _k = self._ptr_array(cts)
-        rc = self._lib.flashe_quantize_batch_encrypt_cohort_dev(self._h, it, int(first_idx), C, int(n_values), int(n_elems), n_jobs, arr, nl, ps, pd,
-                                                                element_bits, field_bits, self._ptr(u), pc, self._ptr(sum_out), self._ptr(dmask))
-        return self._took(rc)
+        return self._cohort_launch("flashe_quantize_batch_encrypt_cohort_dev", it, first_idx, (n_values, n_elems), n_jobs, layers, srcs, dtypes,
+                                   (element_bits, field_bits), u, cts, sum_out, dmask)
 
     def quantize_encrypt_cohort_runs_dev(self, it, idx, n, n_jobs, layers, srcs, dtypes, element_bits, u, cts, sum_out, dmask=None):
         """quantize_encrypt_cohort_dev for a round in which clients dropped out (flashe_quantize_encrypt_cohort_runs_dev): idx = the cipher
@@ -791,38 +781,21 @@ class Engine:
         dtypes, the draws and cts hold one entry per index.  One run of consecutive indices is quantize_encrypt_cohort_dev bit for bit;
         several runs share |idx| + runs streams and dmask receives the decrypt mask of telescope(idx).  Returns False -- nothing was
         launched -- when the library declines the shape (FLASHE_ENOTSUP: also more than 144 streams), True otherwise."""
-        arr, nl = self._tensor_layers(layers)
-        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
-        pc, _k = self._ptr_array(cts)
-        pi, _ki = self._cohort_idx(idx, C)
-        rc = self._lib.flashe_quantize_encrypt_cohort_runs_dev(self._h, it, pi, C, int(n), n_jobs, arr, nl, ps, pd, element_bits, self._ptr(u), pc,
-                                                               self._ptr(sum_out), self._ptr(dmask))
-        return self._took(rc)
+        return self._cohort_launch("flashe_quantize_encrypt_cohort_runs_dev", it, idx, (n,), n_jobs, layers, srcs, dtypes, (element_bits,), u, cts, sum_out, dmask)
 
     def quantize_encrypt_cohort_runs_u32_dev(self, it, idx, n, n_jobs, layers, srcs, dtypes, element_bits, u, cts, sum_out):
         """quantize_encrypt_cohort_u32_dev for a round in which clients dropped out (flashe_quantize_encrypt_cohort_runs_u32_dev, int_bits
         16 / 20 / 23 / 24 / 32): idx as in quantize_encrypt_cohort_runs_dev, cts and sum_out uint32 vectors of n elements, no decrypt mask
         (decrypt the sum with telescope(idx)).  One run of consecutive indices is quantize_encrypt_cohort_u32_dev bit for bit.  Returns
         False -- nothing was launched -- when the library declines the shape (FLASHE_ENOTSUP: also more than 144 streams), True otherwise."""
-        arr, nl = self._tensor_layers(layers)
-        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
-        pc, _k = self._ptr_array(cts)
-        pi, _ki = self._cohort_idx(idx, C)
-        rc = self._lib.flashe_quantize_encrypt_cohort_runs_u32_dev(self._h, it, pi, C, int(n), n_jobs, arr, nl, ps, pd, element_bits, self._ptr(u),
-                                                                   pc, self._ptr(sum_out))
-        return self._took(rc)
+        return self._cohort_launch("flashe_quantize_encrypt_cohort_runs_u32_dev", it, idx, (n,), n_jobs, layers, srcs, dtypes, (element_bits,), u, cts, sum_out)
 
     def quantize_batch_encrypt_cohort_runs_dev(self, it, idx, n_values, n_elems, n_jobs, layers, srcs, dtypes, element_bits, field_bits, u, cts,
                                                sum_out, dmask=None):
         """quantize_batch_encrypt_cohort_dev with the cipher indices of the clients that report
         (flashe_quantize_batch_encrypt_cohort_runs_dev), under quantize_encrypt_cohort_runs_dev's rules."""
-        arr, nl = self._tensor_layers(layers)
-        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
-        pc, _k = self._ptr_array(cts)
-        pi, _ki = self._cohort_idx(idx, C)
-        rc = self._lib.flashe_quantize_batch_encrypt_cohort_runs_dev(self._h, it, pi, C, int(n_values), int(n_elems), n_jobs, arr, nl, ps, pd,
-                                                                     element_bits, field_bits, self._ptr(u), pc, self._ptr(sum_out), self._ptr(dmask))
-        return self._took(rc)
+        return self._cohort_launch("flashe_quantize_batch_encrypt_cohort_runs_dev", it, idx, (n_values, n_elems), n_jobs, layers, srcs, dtypes,
+                                   (element_bits, field_bits), u, cts, sum_out, dmask)
 
     def cohort_cut_pieces(self, idx, n, n_jobs, compact=False):
         """(parts, begins) of the cut launches that take cipher indices (flashe_cohort_cut_pieces): the pieces a cohort of the clients idx --
@@ -839,38 +812,22 @@ class Engine:
         quantize_encrypt_cohort_runs_dev's outputs for a vector of ANY length, every gap of idx a cut.  scratch: 16-byte aligned,
         cohort_cut_pieces(idx, n, ...) parts x n x 16 bytes, twice that with dmask.  Returns False -- nothing was launched -- when the
         library declines the shape (FLASHE_ENOTSUP: also more than 16 runs), True otherwise."""
-        arr, nl = self._tensor_layers(layers)
-        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
-        pc, _k = self._ptr_array(cts)
-        pi, _ki = self._cohort_idx(idx, C)
-        rc = self._lib.flashe_quantize_encrypt_cohort_cut_runs_dev(self._h, it, pi, C, int(n), n_jobs, arr, nl, ps, pd, element_bits, self._ptr(u),
-                                                                   pc, self._ptr(sum_out), self._ptr(dmask), self._ptr(scratch))
-        return self._took(rc)
+        return self._cohort_launch("flashe_quantize_encrypt_cohort_cut_runs_dev", it, idx, (n,), n_jobs, layers, srcs, dtypes, (element_bits,), u, cts, sum_out,
+                                   dmask, scratch)
 
     def quantize_encrypt_cohort_cut_runs_u32_dev(self, it, idx, n, n_jobs, layers, srcs, dtypes, element_bits, u, cts, sum_out, scratch=None):
         """The same in the compact layout (flashe_quantize_encrypt_cohort_cut_runs_u32_dev, int_bits 16 / 20 / 23 / 24 / 32): scratch of
         cohort_cut_pieces(idx, n, ..., compact=True) parts x n x 4 bytes; no decrypt mask (decrypt the sum with telescope(idx))."""
-        arr, nl = self._tensor_layers(layers)
-        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
-        pc, _k = self._ptr_array(cts)
-        pi, _ki = self._cohort_idx(idx, C)
-        rc = self._lib.flashe_quantize_encrypt_cohort_cut_runs_u32_dev(self._h, it, pi, C, int(n), n_jobs, arr, nl, ps, pd, element_bits,
-                                                                       self._ptr(u), pc, self._ptr(sum_out), self._ptr(scratch))
-        return self._took(rc)
+        return self._cohort_launch("flashe_quantize_encrypt_cohort_cut_runs_u32_dev", it, idx, (n,), n_jobs, layers, srcs, dtypes, (element_bits,), u, cts,
+                                   sum_out, scratch)
 
     def quantize_batch_encrypt_cohort_cut_runs_dev(self, it, idx, n_values, n_elems, n_jobs, layers, srcs, dtypes, element_bits, field_bits, u, cts,
                                                    sum_out, dmask=None, scratch=None):
         """quantize_batch_encrypt_cohort_runs_dev for a model of ANY length (flashe_quantize_batch_encrypt_cohort_cut_runs_dev): the batched
         chain cut into cohort_cut_pieces(idx, n_elems, ...) pieces and one combine pass.  scratch: parts x n_elems x 16 bytes, twice that
         with dmask."""
-        arr, nl = self._tensor_layers(layers)
-        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
-        pc, _k = self._ptr_array(cts)
-        pi, _ki = self._cohort_idx(idx, C)
-        rc = self._lib.flashe_quantize_batch_encrypt_cohort_cut_runs_dev(self._h, it, pi, C, int(n_values), int(n_elems), n_jobs, arr, nl, ps, pd,
-                                                                         element_bits, field_bits, self._ptr(u), pc, self._ptr(sum_out),
-                                                                         self._ptr(dmask), self._ptr(scratch))
-        return self._took(rc)
+        return self._cohort_launch("flashe_quantize_batch_encrypt_cohort_cut_runs_dev", it, idx, (n_values, n_elems), n_jobs, layers, srcs, dtypes,
+                                   (element_bits, field_bits), u, cts, sum_out, dmask, scratch)
 
     @staticmethod
     def _cohort_idx(idx, C):

@@ -9,8 +9,9 @@ keeps each case at exactly one fault.  The arguments Engine does pass through ar
 
 Shapes: a model of n = 13 values in three layers of 5, 0 and 8 (starts 0, 5, 5: the empty layer takes the start == end skip), engines at
 int_bits 128 (two limbs, 16-byte vectors) and 20 (one limb), the batched form at 128 with element_bits 16 in fields of 24 bits (5 values
-per element: 1 + 0 + 2 = 3 elements), cohorts of 2 clients.  The dense cohorts check their sources and alphas only once the chained
-launch has admitted the shape, so those cases run at the smallest size it admits on one compute unit.
+per element: 1 + 0 + 2 = 3 elements), cohorts of 2 clients.  The dense cohorts -- all eleven forms of the chained launch: first_idx or an
+index list, wide, compact or batched, whole or cut -- check their sources and alphas only once the launch has admitted the shape, so those
+cases run at the smallest size it admits on one compute unit (the cut forms: n = 13 as it is).
 """
 import copy
 import ctypes
@@ -125,6 +126,7 @@ class Rig:
         self.pt = [out("pt%d" % c, (n + 1) * 8) for c in range(2)]
         self.tail = [out("tail%d" % c, 16) for c in range(2)]
         self.zeros = out("zeros", 16)
+        self.scratch = out("scratch", 4 * vb)                              # (a cut launch's: two pieces' sums and masks would fit)
         self.poison()
 
     def poison(self):
@@ -158,7 +160,7 @@ class Rig:
                  k=[2, 0, 3], residual=self.residual, loc=self.loc, vals=self.vals, packed=self.packed, pbits=8, first_idx=0, n_clients=2,
                  src=[p for c in range(2) for p in self.layer_ptrs(self.x[c], 4)], sdt=[F32] * (2 * len(self.starts)), cts=list(self.ct),
                  sum=self.sum, dmask=self.dmask, rstride=64, lstride=8, vstride=24, pstride=1, u_stride=n + 1, zzz=[0.5, 0.25], zf64=1,
-                 pts=list(self.pt), tails=list(self.tail), zeros=self.zeros, cidx=[0, 1])
+                 pts=list(self.pt), tails=list(self.tail), zeros=self.zeros, cidx=[0, 1], scratch=self.scratch)
         a["layers"] = copy.deepcopy({"C": C, "B": B, "T": T, "S": S}[ep.table])
         if ep.name == "store_layers_dev":
             for l in range(len(self.starts)):
@@ -211,6 +213,24 @@ EPS = [
        ok=ENOTSUP, cohort=True),
     EP("quantize_batch_encrypt_cohort_dev", "iter first_idx n_clients n_values n_elems n_jobs layers:T n_layers src:P sdt:I32 eb fb u cts:P sum dmask", "S",
        widths=(128,), ok=ENOTSUP, cohort=True),
+    # the other forms of the same launch: the cipher indices as a list (cidx in place of first_idx), the cut chain (a trailing scratch; it
+    # has no length rule, so n = 13 is admitted and the valid call runs)
+    EP("quantize_encrypt_cohort_cut_dev", "iter first_idx n_clients n n_jobs layers:T n_layers src:P sdt:I32 eb u cts:P sum dmask scratch", "S",
+       widths=(128,), cohort=True),
+    EP("quantize_encrypt_cohort_cut_u32_dev", "iter first_idx n_clients n n_jobs layers:T n_layers src:P sdt:I32 eb u cts:P sum scratch", "S",
+       widths=(20,), cohort=True),
+    EP("quantize_encrypt_cohort_runs_dev", "iter cidx:U32 n_clients n n_jobs layers:T n_layers src:P sdt:I32 eb u cts:P sum dmask", "S", widths=(128,),
+       ok=ENOTSUP, cohort=True),
+    EP("quantize_encrypt_cohort_runs_u32_dev", "iter cidx:U32 n_clients n n_jobs layers:T n_layers src:P sdt:I32 eb u cts:P sum", "S", widths=(20,),
+       ok=ENOTSUP, cohort=True),
+    EP("quantize_batch_encrypt_cohort_runs_dev", "iter cidx:U32 n_clients n_values n_elems n_jobs layers:T n_layers src:P sdt:I32 eb fb u cts:P sum dmask",
+       "S", widths=(128,), ok=ENOTSUP, cohort=True),
+    EP("quantize_encrypt_cohort_cut_runs_dev", "iter cidx:U32 n_clients n n_jobs layers:T n_layers src:P sdt:I32 eb u cts:P sum dmask scratch", "S",
+       widths=(128,), cohort=True),
+    EP("quantize_encrypt_cohort_cut_runs_u32_dev", "iter cidx:U32 n_clients n n_jobs layers:T n_layers src:P sdt:I32 eb u cts:P sum scratch", "S",
+       widths=(20,), cohort=True),
+    EP("quantize_batch_encrypt_cohort_cut_runs_dev",
+       "iter cidx:U32 n_clients n_values n_elems n_jobs layers:T n_layers src:P sdt:I32 eb fb u cts:P sum dmask scratch", "S", widths=(128,), cohort=True),
     EP("sparsify_cohort_tensors_dev", "n_clients n layers:T n_layers k:U64 src:P sdt:I32 residual rstride loc lstride vals vstride packed pstride pbits",
        "S", cohort=True),
     EP("quantize_cohort_dev", "n_clients n layers:T n_layers src:P sdt:I32 eb u u_stride zzz:D zf64 cts:P tails:P zeros", "S", cohort=True),
@@ -226,7 +246,10 @@ CODEC_FRONT = {"quantize_encrypt_model_dev", "quantize_encrypt_prepared_model_de
                "quantize_encrypt_prepared_tensors_dev"}
 BATCH_FRONT = {"quantize_batch_model_dev", "quantize_batch_encrypt_prepared_model_dev", "quantize_batch_tensors_dev",
                "quantize_batch_encrypt_prepared_tensors_dev"}
-DENSE = {"quantize_encrypt_cohort_dev", "quantize_encrypt_cohort_u32_dev", "quantize_batch_encrypt_cohort_dev"}
+DENSE = {"quantize_encrypt_cohort_dev", "quantize_encrypt_cohort_u32_dev", "quantize_batch_encrypt_cohort_dev",
+         "quantize_encrypt_cohort_cut_dev", "quantize_encrypt_cohort_cut_u32_dev",
+         "quantize_encrypt_cohort_runs_dev", "quantize_encrypt_cohort_runs_u32_dev", "quantize_batch_encrypt_cohort_runs_dev",
+         "quantize_encrypt_cohort_cut_runs_dev", "quantize_encrypt_cohort_cut_runs_u32_dev", "quantize_batch_encrypt_cohort_cut_runs_dev"}
 SPARSE_Q = {"quantize_cohort_dev", "quantize_encrypt_sparse_cohort_dev"}
 NO_ALPHA = {"store_layers_dev", "sparsify_tensors_dev", "sparsify_cohort_tensors_dev"} | DENSE   # (the dense cohorts: cases_admitted)
 
@@ -328,7 +351,6 @@ def cases(ep, bits):
         bad += [("n_clients 0", put("n_clients", 0), w + "n_clients must be >= 1"), ("null src", put("src", None), w + "null argument"),
                 ("null cts", put("cts", None), w + "null argument"), ("null sum", put("sum", None), w + "null argument"),
                 ("null u", put("u", None), w + "null argument"), ("u + 4", off("u", 4), U8),
-                ("first_idx 2^32 - 1", put("first_idx", 2 ** 32 - 1), "the cohort's cipher indices wrap around 2^32"),
                 ("null ciphertext", item("cts", 1, None), "client 1: null ciphertext"),
                 ("ciphertext aliases the sum", item("cts", 1, lambda a, r: a["sum"]), "client 1: the ciphertext aliases the sum")]
         if u32:
@@ -338,6 +360,20 @@ def cases(ep, bits):
             bad += [("ct + 8", item("cts", 0, lambda a, r: a["cts"][0] + 8), A16), ("sum + 8", off("sum", 8), "sum_out_dev must be aligned like a ciphertext vector"),
                     ("dmask + 8", off("dmask", 8), "dmask_dev must be 16-byte aligned and apart from the sum"),
                     ("ciphertext aliases the mask", item("cts", 0, lambda a, r: a["dmask"]), "client 0: the ciphertext aliases the sum or the mask")]
+        if "cidx" in names:
+            ascending = w + "the cipher indices must be strictly ascending and below 2^32 - 1"
+            bad += [("null idx", put("cidx", None), w + "null argument"), ("idx 1, 1", put("cidx", [1, 1]), ascending),
+                    ("idx 1, 0", put("cidx", [1, 0]), ascending), ("idx 0, 2^32 - 1", put("cidx", [0, 2 ** 32 - 1]), ascending)]
+        else:
+            bad += [("first_idx 2^32 - 1", put("first_idx", 2 ** 32 - 1), "the cohort's cipher indices wrap around 2^32")]
+        if "scratch" in names:
+            # (two consecutive clients are one piece, which needs no scratch: a null one passes; the cut edge tests refuse it from two pieces upward)
+            bad += [("scratch + 8", off("scratch", 8), "scratch_dev must be 16-byte aligned"),
+                    ("scratch aliases the sum", lambda a, r: a.__setitem__("scratch", a["sum"]), "scratch_dev aliases the sum or the mask"),
+                    ("scratch aliases a ciphertext", lambda a, r: a.__setitem__("scratch", a["cts"][1]), "scratch_dev aliases client 1's ciphertext")]
+            if not u32:
+                bad += [("scratch aliases the mask", lambda a, r: a.__setitem__("scratch", a["dmask"]), "scratch_dev aliases the sum or the mask")]
+            good += [("null scratch at one piece", put("scratch", None))]
     if name == "sparsify_cohort_tensors_dev":
         bad += [("n_clients 0", put("n_clients", 0), who + "n_clients must be in [1, 65535]"), ("null k", put("k", None), who + "null argument"),
                 ("null src", put("src", None), who + "null argument"), ("null dtypes", put("sdt", None), who + "null argument"),
@@ -469,6 +505,8 @@ def test_refusals_leave_the_ctx_as_it_was(rigs, bits):
 def admitted_n(ep, bits, cus=1):
     """The smallest n the chained launch of the dense cohort `ep` takes with one job on `cus` compute units (kernels.hip:
     cohort_chain_admits, small_cohort_admits: two whole tiles, or 2 x 128 AES blocks, for each of the 16 waves of a workgroup)."""
+    if "_cut_" in ep.name:
+        return N                             # (the cut chain has no length rule)
     if ep.name.endswith("u32_dev"):
         return (2 * 128 * cus * 16 - 1) * (128 // bits) + 1
     return ((2 * cus * 16 - 1) * 256 + 1) * (bits // FB if "batch" in ep.name else 1)
