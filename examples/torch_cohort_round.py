@@ -39,7 +39,10 @@ which this example checks.
                generate the Philox draws itself (no draw buffer; a lane owns four elements and computes each Philox block of their 24
                values once) in the shape classes where that form won its measurement (one shared generator at a misaligned length; this
                example's generator per client is not one), and FLASHE_INLINE_DRAWS=1 forces it;
-               `upload.draws` says "inline" or "buffer", and the bytes are the same either way
+               `upload.draws` says "inline" or "buffer", and the bytes are the same either way.  With --precompute --rng pcg64 (no
+               --batch): FlasheCohort(inline_draws="any") -- the un-batched online launch may generate default_rng's PCG64 draws itself
+               (a lane keeps one jump of the LCG for all clients; no draw buffer), which won its measurement in both layouts;
+               FLASHE_INLINE_DRAWS=0 keeps the buffer
   --packed     a DENSE job's arbiter adds the clients' bit-packed models as one integer (carries cross from one element into the next),
                so its global model is not the decrypt of the element-wise sum: cohort.aggregate_packed() is that reduce of the upload
                -- one pass over the ciphertexts where they lie, no packed vectors -- and decrypt_unquantize(packed=True) decrypts it
@@ -89,7 +92,7 @@ def main():
     ap.add_argument("--cut", action="store_true", help="forty LeNet-sized models through the cut chained launch")
     ap.add_argument("--drop", default="", help="comma-separated clients that miss the round, e.g. 2,7")
     ap.add_argument("--packed", action="store_true", help="reduce the upload as a dense job's arbiter does: on the bit-packed integers")
-    ap.add_argument("--inline-draws", action="store_true", help="a batched precompute cohort may draw its Philox stream inside the online launch")
+    ap.add_argument("--inline-draws", action="store_true", help="a batched precompute cohort may draw its Philox stream inside the online launch; with --rng pcg64: inline_draws=\"any\"")
     ap.add_argument("--rng", choices=["philox", "pcg64", "sfc64"], default=None, help="draw from one np.random.Generator per client")
     opt = ap.parse_args()
     cm.N_JOBS = 16                                           # every party must use the same value
@@ -117,7 +120,7 @@ def main():
         return [np.random.Generator(bitgen(1000 + c)) for c in present]
 
     cohort = FlasheCohort(args, first_idx=0, n_local=C, num_clients=C, prp_seed=key, compact=opt.compact,
-                          cut="any" if opt.cut and (dropped or opt.batch) else opt.cut, inline_draws=opt.inline_draws)
+                          cut="any" if opt.cut and (dropped or opt.batch) else opt.cut, inline_draws="any" if opt.inline_draws and opt.rng == "pcg64" else opt.inline_draws)
     if opt.precompute:
         cohort.set_iter_index(it - 1)
         cohort.prepare_encrypt()                             # in idle time, one round ahead: the masks of iteration `it`

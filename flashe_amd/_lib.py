@@ -287,6 +287,14 @@ _SIGNATURES = {
     "flashe_pcg64_random_dev": (c_int, [c_vp, ctypes.POINTER(Pcg64Segment), c_int, c_vp]),
     "flashe_pcg64_advance": (c_int, [c_u32, c_u64p, c_u64p, c_u64p]),
     "flashe_pcg64_grid": (c_int, [c_vp, c_u64, c_u32p, c_u64p, c_u32p]),
+    "flashe_quantize_combine_cohort_pcg64_dev": (c_int, [c_vp, c_int, c_u64, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp),
+                                                         ctypes.POINTER(ctypes.c_int32), c_int, ctypes.POINTER(Pcg64Segment), c_int,
+                                                         ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
+    "flashe_quantize_combine_cohort_pcg64_u32_dev": (c_int, [c_vp, c_int, c_u64, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp),
+                                                             ctypes.POINTER(ctypes.c_int32), c_int, ctypes.POINTER(Pcg64Segment), c_int,
+                                                             ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
+    "flashe_pcg64_cohort_grid": (c_int, [c_vp, c_u64, c_u32p]),
+    "flashe_pcg64_cohort_lane_draws": (c_int, [c_u32, c_u64p, c_u64p, c_u64, c_u32, c_u64, c_u64, c_vp]),
     "flashe_quantize_dev": (c_int, [c_vp, c_u64, c_vp, c_int, ctypes.c_double, c_int, c_vp, c_vp]),
     "flashe_quantize": (c_int, [c_vp, c_u64, c_vp, c_int, ctypes.c_double, c_int, c_vp, c_vp]),
     "flashe_unquantize_dev": (c_int, [c_vp, c_u64, c_vp, c_int, ctypes.c_double, c_int, c_int, c_vp]),

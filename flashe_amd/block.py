@@ -367,6 +367,34 @@ def _inline_draws(eng, rng, batched, compact=False, C=1, n=0, inline_batched=Fal
     return _INLINE_DRAWS_DEFAULT[(bool(compact), _draws_aligned(rng, C, n))]
 
 
+# The same rule for the generators of the PCG64 family (np.random.default_rng's) in a cohort made with inline_draws="any": compact layout?
+# -> inline by default, and only where the inline median beat the buffer form's by more than the larger of the two spreads in EVERY case
+# of the layout.  Measured (tests/perf/prepared_cohort_pcg64_inline_draws.py, profiles/r35_prepared_cohort_pcg64_inline_draws.log: ten
+# clients of 1e7 and 25,557,032 values, PCG64 and PCG64DXSM, one shared generator and a list): int_bits 128 wins by 18 - 25 % against
+# spreads of 2 - 6 %, int_bits 20 compact by 35 - 75 % against 10 - 16 %.
+_INLINE_PCG64_DEFAULT = {False: True, True: True}
+
+
+def _inline_pcg64_draws(eng, rng, batched, compact=False):
+    """_inline_draws for generators over np.random.PCG64 or np.random.PCG64DXSM (eng.quantize_combine_cohort_pcg64_dev), asked only by a
+    cohort made with inline_draws="any": an un-batched round (the launch has no batched form), every (present) client's Generator of ONE
+    of the two variants -- the launch's lanes share one jump --, at most eng.PCG64_MAX_SEGMENTS of them, FLASHE_DEVICE_RNG not 0, an engine
+    that has the call, and FLASHE_INLINE_DRAWS: 0 never, 1 always, unset the default of the layout (_INLINE_PCG64_DEFAULT)."""
+    if rng is None or batched or not hasattr(eng, "quantize_combine_cohort_pcg64_dev"):
+        return False
+    switch = os.environ.get("FLASHE_INLINE_DRAWS", "")
+    if os.environ.get("FLASHE_DEVICE_RNG", "1") == "0" or switch == "0":
+        return False
+    gens = rng if isinstance(rng, list) else [rng]
+    if len(gens) > eng.PCG64_MAX_SEGMENTS:
+        return False
+    if not any(all(type(g.bit_generator) is kind for g in gens) for kind in (np.random.PCG64, np.random.PCG64DXSM)):
+        return False
+    if switch == "1":
+        return True
+    return _INLINE_PCG64_DEFAULT[bool(compact)]
+
+
 class FlasheClient(object):
     """`jzf_flashe_block._Client` without the transport: holds a FlasheCipher and forwards to it with the
     reference's method names, so `JZFWeights.encrypted(cipher)` / `.decrypted(cipher)`
@@ -1517,12 +1545,18 @@ class FlasheCohort(object):
     at any int_bits, batched or not, compact or not.  Without that call the clients' own masks run "per-client" as before.  Un-batched and
     with rng= generators over np.random.Philox that launch also generates the stochastic-rounding draws (CohortUpload.draws == "inline":
     no draw buffer in HBM); every other cohort materialises its draws first ("buffer").  inline_draws=True (opt-in, as compact= and cut=
-    are) lets a BATCHED precompute job do the same in the shape classes where the measurement says it wins.
+    are) lets a BATCHED precompute job do the same in the shape classes where the measurement says it wins.  inline_draws="any" (as
+    cut="any" is to cut=True) does all of that and lets an un-batched "prepared-cohort" round whose generators are all over
+    np.random.PCG64 -- np.random.default_rng's -- or all over np.random.PCG64DXSM draw inside its launch too
+    (flashe_quantize_combine_cohort_pcg64_dev), under FLASHE_INLINE_DRAWS=1 and in the layouts where _INLINE_PCG64_DEFAULT says so.  Any
+    other string: ValueError.
     A DENSE job's arbiter adds the clients' bit-packed models as one integer (jzf_aggregator.py:406-419); CohortUpload.partial_sum is
     the element-wise sum.  aggregate_packed() is that packed reduce of an upload, one pass over the ciphertexts where they lie, and
     decrypt_unquantize(packed=True) decrypts it, so that a cohort which simulates a dense job returns the global model the job produces."""
 
     def __init__(self, args, first_idx, n_local, num_clients, prp_seed, device=0, stream=None, compact=False, cut=False, inline_draws=False):
+        if isinstance(inline_draws, str) and inline_draws != "any":
+            raise ValueError(f"inline_draws: True, False or \"any\", got {inline_draws!r}")
         if n_local < 1 or first_idx < 0 or first_idx + n_local > num_clients:
             raise ValueError(f"clients {first_idx} .. {first_idx + n_local - 1} are not clients of a federation of {num_clients}")
         self.first_idx, self.n_local, self.num_clients = int(first_idx), int(n_local), int(num_clients)
@@ -1533,6 +1567,7 @@ class FlasheCohort(object):
             raise ValueError(f"cut: True, False or \"any\", got {cut!r}")
         self.cut = bool(cut)                           # a short cohort runs "cut-chain" where the engine has the cut launch
         self.inline_draws = bool(inline_draws)         # a BATCHED "prepared-cohort" round may draw inside its online launch (_inline_draws)
+        self.inline_any = inline_draws == "any"        # ... and an un-batched one over PCG64 / PCG64DXSM generators (_inline_pcg64_draws)
         self.cut_any = cut == "any"                    # ... gapped or batched too, where the engine has the launches that take indices
         self._cut_scratch = None                       # the cut launch's scratch, kept from round to round
         if self.compact:
@@ -1651,7 +1686,9 @@ class FlasheCohort(object):
         unless the cohort was made with inline_draws=True: its online launch then generates the draws too
         (flashe_quantize_batch_combine_cohort_philox_dev: a lane owns four elements and computes each Philox block of their 4 bs values
         once) in the shape classes where that form won its measurement (_INLINE_BATCHED_DEFAULT), and in every class under
-        FLASHE_INLINE_DRAWS=1.  Mismatched Weights raise
+        FLASHE_INLINE_DRAWS=1.  A cohort made with inline_draws="any" also draws inside an UN-BATCHED "prepared-cohort" launch when
+        every (present) generator is over np.random.PCG64 (np.random.default_rng's) or every one over np.random.PCG64DXSM
+        (flashe_quantize_combine_cohort_pcg64_dev: a lane keeps one jump of the LCG for all clients; _inline_pcg64_draws).  Mismatched Weights raise
         ValueError and unusable tensors are refused before anything is launched.  Own-stream engines keep the tensors alive until the
         last kernel that reads them has finished."""
         from .engine import DeviceVector
@@ -1674,6 +1711,8 @@ class FlasheCohort(object):
         # (a prepared cohort over Philox generators draws inside its online launch: no draw buffer; a batched one where it asked to)
         inline = path == PREPARED_COHORT and _inline_draws(eng, rng, bool(ld.batch), self.compact, C, plan.n, inline_batched=self.inline_draws,
                                                            bs=ld.int_bits // _field_bits(q.element_bits, q.num_clients) if ld.batch else 0)
+        pcg64 = not inline and path == PREPARED_COHORT and self.inline_any and _inline_pcg64_draws(eng, rng, bool(ld.batch), self.compact)
+        inline = inline or pcg64
         du = None if inline else _cohort_draws(eng, C, plan.n, seeds, rng)
         if self.compact:
             cts = [DeviceVector(eng, plan.n_elems, 1, elem_bytes=4) for _ in range(C)]
@@ -1690,7 +1729,7 @@ class FlasheCohort(object):
             srcs = [[t[1] for t in table] for table in tables]
             dts = [[t[4] for t in table] for table in tables]
             launch = self._launch_prepared if prepared else self._launch_chain
-            if inline and not self._launch_prepared_inline(plan, rows, srcs, dts, rng, cts, psum):
+            if inline and not self._launch_prepared_inline(plan, rows, srcs, dts, rng, cts, psum, pcg64):
                 # the library declined the inline form: today's form, from the same generators (nothing has been advanced)
                 inline, du = False, _cohort_draws(eng, C, plan.n, seeds, rng)
             if not inline and not launch(plan, rows, srcs, dts, du, cts, psum, present is not None, **({"cut": True} if path == CUT_CHAIN else {})):
@@ -1870,14 +1909,19 @@ class FlasheCohort(object):
                                                             [v.buf for v in cts], psum.buf, compact=self.compact,
                                                             batch=(plan.n_elems, _field_bits(q.element_bits, q.num_clients)) if ld.batch else None)
 
-    def _launch_prepared_inline(self, plan, rows, srcs, dts, rng, cts, psum):
-        """"prepared-cohort" with the draws generated inside the online launch (_inline_draws): one Generator gives ONE stretch of C n
-        draws, the p-th present client taking [p n, (p + 1) n); a list client p's stretch from rng[p].  The generators get their
-        advanced states back.  False: the library declined, nothing was launched and nothing advanced."""
+    def _launch_prepared_inline(self, plan, rows, srcs, dts, rng, cts, psum, pcg64=False):
+        """"prepared-cohort" with the draws generated inside the online launch (_inline_draws; pcg64: _inline_pcg64_draws, the PCG64
+        family's call): one Generator gives ONE stretch of C n draws, the p-th present client taking [p n, (p + 1) n); a list client
+        p's stretch from rng[p].  The generators get their advanced states back.  False: the library declined or refused the table,
+        nothing was launched and nothing advanced."""
         ld = self.lead
         C, n = len(plan.present), plan.n
         gens, counts, offsets = (rng, [n] * C, [p * n for p in range(C)]) if isinstance(rng, list) else ([rng], [C * n], [0])
         q = ld.quantizer
+        if pcg64:
+            return ld.cipher.engine.quantize_combine_cohort_pcg64_dev(n, rows, srcs, dts, q.element_bits, gens, counts, offsets,
+                                                                      [self._masks[p].buf for p in plan.present], [v.buf for v in cts], psum.buf,
+                                                                      compact=self.compact)
         return ld.cipher.engine.quantize_combine_cohort_philox_dev(n, rows, srcs, dts, q.element_bits, gens, counts, offsets,
                                                                    [self._masks[p].buf for p in plan.present], [v.buf for v in cts], psum.buf,
                                                                    compact=self.compact,

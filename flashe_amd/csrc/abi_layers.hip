@@ -7,6 +7,7 @@
 #include "cohort_streams.h"
 #include "cohort_cut.h"
 #include "draw_launch.h"
+#include "pcg64_stream.h"
 #include "philox_stream.h"
 
 #include <algorithm>
@@ -938,10 +939,19 @@ int flashe_quantize_batch_encrypt_cohort_cut_runs_dev(flashe_ctx *ctx, uint32_t 
 // sources and stage pass with the mask and ciphertext pointers (and the batched rows) behind it in the same upload, one launch.
 // plans: one draw plan per client, uploaded behind the pointers (flashe_tables::prepared_draws_block; batched: behind the rows and the
 // rows' first groups, prepared_batch_draws_block) -- the launch generates the draws and u_dev is not read.
+// (the rows of either kind of generator: flashe_philox::ClientPlan, variant < 0, or flashe_pcg64::ClientPlan of the one variant)
+struct DrawPlans {
+    const void *rows;
+    size_t count, row_bytes;
+    int variant;
+    DrawPlans(const std::vector<flashe_philox::ClientPlan> &p) : rows(p.data()), count(p.size()), row_bytes(sizeof(flashe_philox::ClientPlan)), variant(-1) {}
+    DrawPlans(const std::vector<flashe_pcg64::ClientPlan> &p, flashe_pcg64::Variant v)
+        : rows(p.data()), count(p.size()), row_bytes(sizeof(flashe_pcg64::ClientPlan)), variant(static_cast<int>(v)) {}
+};
 static int quantize_combine_cohort(flashe_ctx *ctx, const char *who, int elem_bytes, int n_clients, uint64_t n_values, uint64_t n_elems, const uint64_t *n_elems_arg,
                                    const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype, int element_bits,
                                    int field_bits, const double *u_dev, const void *const *mask_dev, void *const *ct_dev, void *sum_out_dev,
-                                   const std::vector<flashe_philox::ClientPlan> *plans = nullptr)
+                                   const DrawPlans *plans = nullptr)
 {
     const bool batched = n_elems_arg != nullptr;
     if (n_clients < 1) return fail(ctx, FLASHE_EINVAL, "%s: n_clients must be >= 1", who);
@@ -971,17 +981,17 @@ static int quantize_combine_cohort(flashe_ctx *ctx, const char *who, int elem_by
             if (src_dev[i] == sum_out_dev) return fail(ctx, FLASHE_EINVAL, "the sum aliases a source (client %d layer %d)", static_cast<int>(i / n_layers), static_cast<int>(i % n_layers));
     if (elem_bytes == 4 && flashe_ctx_compact_layout(ctx) != 1) return cohort_declined(ctx, who, "prepared compact cohort");
     if (n_elems == 0) return FLASHE_OK;                                    // (an empty model: nothing staged, nothing launched)
-    constexpr size_t plan_words = sizeof(flashe_philox::ClientPlan) / sizeof(uint64_t);
+    const size_t plan_words = plans ? plans->row_bytes / sizeof(uint64_t) : 0;
     const size_t n_rows = extra.size() / 2 - static_cast<size_t>(n_clients);                  // (batched: two words per row so far)
     uint64_t n_groups = 0;
     if (plans && batched) {
         const flashe_tables::PreparedBatchDrawsBlock at = flashe_tables::prepared_batch_draws_block(n_clients, n_rows, plan_words);
         extra.resize(at.words);
         n_groups = flashe_tables::batched_groups(extra.data() + at.rows / 8, n_rows, bs, extra.data() + at.groups / 8);
-        memcpy(extra.data() + at.plans / 8, plans->data(), plans->size() * sizeof(flashe_philox::ClientPlan));
+        memcpy(extra.data() + at.plans / 8, plans->rows, plans->count * plans->row_bytes);
     } else if (plans) {
         extra.resize(flashe_tables::prepared_draws_block(n_clients, plan_words).words);
-        memcpy(extra.data() + 2 * static_cast<size_t>(n_clients), plans->data(), plans->size() * sizeof(flashe_philox::ClientPlan));
+        memcpy(extra.data() + 2 * static_cast<size_t>(n_clients), plans->rows, plans->count * plans->row_bytes);
     }
     CohortCodec cc{};
     const char *extra_dev = nullptr;
@@ -1004,6 +1014,11 @@ static int quantize_combine_cohort(flashe_ctx *ctx, const char *who, int elem_by
         pc.mask = reinterpret_cast<const void *const *>(extra_dev + at.mask);
         pc.ct = reinterpret_cast<void *const *>(extra_dev + at.ct);
         pc.sum = sum_out_dev; pc.n = n_elems; pc.n_values = n_values; pc.n_clients = n_clients;
+        if (plans->variant >= 0) {
+            HIP_TRY(ctx, launch_quantize_pcg64_combine_cohort(ctx->env, pc, reinterpret_cast<const flashe_pcg64::ClientPlan *>(extra_dev + at.plans),
+                                                              static_cast<uint32_t>(plans->variant), elem_bytes));
+            return FLASHE_OK;
+        }
         HIP_TRY(ctx, launch_quantize_philox_combine_cohort(ctx->env, pc, reinterpret_cast<const flashe_philox::ClientPlan *>(extra_dev + at.plans), elem_bytes));
         return FLASHE_OK;
     }
@@ -1056,8 +1071,9 @@ static int quantize_combine_cohort_philox(flashe_ctx *ctx, const char *who, int 
     case flashe_philox::kCohortPlansTooMany: return fail(ctx, FLASHE_EINVAL, "%s: n_clients x n draws overflow", who);
     default: return fail(ctx, FLASHE_EINVAL, "%s: the segments must tile the draws [0, n_clients x n) exactly", who);
     }
+    const DrawPlans rows(plans);
     if (int rc = quantize_combine_cohort(ctx, who, elem_bytes, n_clients, n, n_elems_arg ? 0 : n, n_elems_arg, layers, n_layers, src_dev, src_dtype, element_bits,
-                                         field_bits, nullptr, mask_dev, ct_dev, sum_out_dev, &plans))
+                                         field_bits, nullptr, mask_dev, ct_dev, sum_out_dev, &rows))
         return rc;
     for (int s = 0; n && s < n_segments; s++)
         flashe_philox::advance(segments[s].key, segments[s].counter, segments[s].buffer_pos, segments[s].buffer, segments[s].n);
@@ -1082,6 +1098,81 @@ int flashe_quantize_combine_cohort_philox_u32_dev(flashe_ctx *ctx, int n_clients
     if (ctx->int_bits > 32) return fail(ctx, FLASHE_EINVAL, "the uint32 layout needs int_bits <= 32, this ctx has %d", ctx->int_bits);
     return quantize_combine_cohort_philox(ctx, "flashe_quantize_combine_cohort_philox_u32_dev", 4, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits,
                                           segments, n_segments, reinterpret_cast<const void *const *>(mask_dev), reinterpret_cast<void *const *>(ct_dev), sum_out_dev);
+}
+
+// The un-batched launch with the draws of PCG64 / PCG64DXSM streams generated inside it: the order of refusals and the hand-back are the
+// Philox form's -- flashe_pcg64_random_dev's segment checks (without a draw buffer), the tiling, the split client and a table of both
+// variants, then quantize_combine_cohort's; one advance per segment on the host, after the launch has been made.
+static int quantize_combine_cohort_pcg64(flashe_ctx *ctx, const char *who, int elem_bytes, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers,
+                                         const void *const *src_dev, const int32_t *src_dtype, int element_bits, flashe_pcg64_segment *segments, int n_segments,
+                                         const void *const *mask_dev, void *const *ct_dev, void *sum_out_dev)
+{
+    if (n_clients < 1) return fail(ctx, FLASHE_EINVAL, "%s: n_clients must be >= 1", who);
+    std::vector<flashe_pcg64::Segment> segs;
+    if (int rc = flashe_draw::read_segments(ctx, who, segments, n_segments, nullptr, flashe_pcg64::from_c<flashe_pcg64_segment>, flashe_pcg64::check_segments,
+                                            "a variant that is neither PCG64 (0) nor PCG64DXSM (1)", segs, false))
+        return rc;
+    std::vector<flashe_pcg64::ClientPlan> plans;
+    flashe_pcg64::Variant variant = flashe_pcg64::kPcg64;
+    switch (flashe_pcg64::cohort_plans(segs.data(), n_segments, static_cast<uint64_t>(n_clients), n, plans, &variant)) {
+    case flashe_pcg64::kCohortPlansOk: break;
+    case flashe_pcg64::kCohortPlansSplitClient: return fail(ctx, FLASHE_EINVAL, "%s: a client's n draws must come from one segment", who);
+    case flashe_pcg64::kCohortPlansTooMany: return fail(ctx, FLASHE_EINVAL, "%s: n_clients x n draws overflow", who);
+    case flashe_pcg64::kCohortPlansMixedVariants: return fail(ctx, FLASHE_EINVAL, "%s: PCG64 and PCG64DXSM segments in one table: a launch has one variant", who);
+    default: return fail(ctx, FLASHE_EINVAL, "%s: the segments must tile the draws [0, n_clients x n) exactly", who);
+    }
+    const DrawPlans rows(plans, variant);
+    if (int rc = quantize_combine_cohort(ctx, who, elem_bytes, n_clients, n, n, nullptr, layers, n_layers, src_dev, src_dtype, element_bits, 0, nullptr, mask_dev, ct_dev,
+                                         sum_out_dev, &rows))
+        return rc;
+    for (int s = 0; n && s < n_segments; s++) {
+        const flashe_pcg64::u128 a = flashe_pcg64::advance(static_cast<flashe_pcg64::Variant>(segs[s].variant), segs[s].state, segs[s].inc, segs[s].n);
+        segments[s].state[0] = flashe_pcg64::lo64(a); segments[s].state[1] = flashe_pcg64::hi64(a);
+    }
+    return FLASHE_OK;
+}
+
+int flashe_quantize_combine_cohort_pcg64_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
+                                             const int32_t *src_dtype, int element_bits, flashe_pcg64_segment *segments, int n_segments,
+                                             const uint64_t *const *mask_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev)
+{
+    CHECK_CTX(ctx);
+    return quantize_combine_cohort_pcg64(ctx, "flashe_quantize_combine_cohort_pcg64_dev", ctx->limbs == 2 ? 16 : 8, n_clients, n, layers, n_layers, src_dev, src_dtype,
+                                         element_bits, segments, n_segments, reinterpret_cast<const void *const *>(mask_dev), reinterpret_cast<void *const *>(ct_dev),
+                                         sum_out_dev);
+}
+
+int flashe_quantize_combine_cohort_pcg64_u32_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers,
+                                                 const void *const *src_dev, const int32_t *src_dtype, int element_bits, flashe_pcg64_segment *segments,
+                                                 int n_segments, const uint32_t *const *mask_dev, uint32_t *const *ct_dev, uint32_t *sum_out_dev)
+{
+    CHECK_CTX(ctx);
+    if (ctx->int_bits > 32) return fail(ctx, FLASHE_EINVAL, "the uint32 layout needs int_bits <= 32, this ctx has %d", ctx->int_bits);
+    return quantize_combine_cohort_pcg64(ctx, "flashe_quantize_combine_cohort_pcg64_u32_dev", 4, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits,
+                                         segments, n_segments, reinterpret_cast<const void *const *>(mask_dev), reinterpret_cast<void *const *>(ct_dev), sum_out_dev);
+}
+
+// host only: the grid of that launch for n values, and one lane's draws through the header functions its kernel compiles
+int flashe_pcg64_cohort_grid(flashe_ctx *ctx, uint64_t n, uint32_t *workgroups)
+{
+    if (!ctx || !workgroups || n > flashe_pcg64::kMaxDraws) return FLASHE_EINVAL;
+    *workgroups = static_cast<uint32_t>(prep_pcg64_grid(ctx->env, n));
+    return FLASHE_OK;
+}
+
+int flashe_pcg64_cohort_lane_draws(uint32_t variant, const uint64_t state[2], const uint64_t inc[2], uint64_t first, uint32_t workgroups, uint64_t run,
+                                   uint64_t iterations, double *out)
+{
+    using namespace flashe_pcg64;
+    if (!state || !inc || (iterations && !out) || variant >= kVariants || workgroups < 1 || run >= static_cast<uint64_t>(workgroups) * kLanes) return FLASHE_EINVAL;
+    if (first > kMaxDraws || iterations > kMaxDraws / kRunDraws) return FLASHE_EINVAL;
+    static const Pow2Table pow2[kVariants] = {make_pow2_table(kPcg64), make_pow2_table(kDxsm)};
+    static const RunTable runs[kVariants] = {make_run_table(kPcg64), make_run_table(kDxsm)};
+    Segment seg{make128(state[1], state[0]), make128(inc[1], inc[0]), variant, 0, 0};
+    const ClientPlan plan = client_plan(seg, first);
+    if (variant == kPcg64) lane_draws<kPcg64>(pow2[0], runs[0], plan, workgroups, run, iterations, out);
+    else lane_draws<kDxsm>(pow2[1], runs[1], plan, workgroups, run, iterations, out);
+    return FLASHE_OK;
 }
 
 // the BATCHED job with the draws generated inside the launch: the segments tile the clients' n_values values

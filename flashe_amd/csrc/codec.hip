@@ -1,5 +1,6 @@
 // gfx950 kernels of the quantise / batch codec either side of the cipher and the host-side descriptors of the fused codec.
 #include "device_common.h"
+#include "pcg64_stream.h"
 #include "philox_stream.h"
 
 namespace flashe {
@@ -535,6 +536,8 @@ struct BufferDraws {
     {
         return __longlong_as_double(static_cast<long long>(ld64_nt_g(reinterpret_cast<const uint64_t *>(u) + static_cast<uint64_t>(c) * n_values + k)));
     }
+    __device__ __forceinline__ void start() {}
+    __device__ __forceinline__ void next_pass() {}
 };
 using flashe_philox::ClientPlan;
 static_assert(sizeof(ClientPlan) == 56, "the plan rows are 56 bytes");
@@ -553,6 +556,47 @@ struct PhiloxDraws {
         const ClientPlan &p = plans[c];
         const uint64_t key[2] = {p.key[0], p.key[1]}, base[4] = {p.base[0], p.base[1], p.base[2], p.base[3]};
         return flashe_philox::client_draw(key, base, p.skip, k);
+    }
+    __device__ __forceinline__ void start() {}
+    __device__ __forceinline__ void next_pass() {}
+};
+
+// Pcg64Draws: np.random.PCG64 / PCG64DXSM streams generated here (pcg64_stream.h: client c's draw for value k outputs from
+// A^k origin_c + G_k inc_c) from one 32-byte plan per client -- nothing is loaded.  The lane holds ONE jump, over 4 g steps for its run g,
+// whatever the client: start() builds it from the tables (the workgroup's part is uniform), next_pass() composes it with the grid's
+// stride jump; a client is then its plan, read as scalars: apply, four outputs, three steps between them.  The value-by-value path takes
+// the same run's draws and indexes them.  One launch is one variant V.  (The Pow2 rows are built by the function pcg64.hip builds its own
+// with; device code is not linked across translation units here, so each keeps its 4 KiB.)
+alignas(32) __device__ const flashe_pcg64::Pow2Table kCohortPow2[flashe_pcg64::kVariants] = {flashe_pcg64::make_pow2_table(flashe_pcg64::kPcg64),
+                                                                                          flashe_pcg64::make_pow2_table(flashe_pcg64::kDxsm)};
+alignas(32) __device__ const flashe_pcg64::RunTable kCohortRun[flashe_pcg64::kVariants] = {flashe_pcg64::make_run_table(flashe_pcg64::kPcg64),
+                                                                                        flashe_pcg64::make_run_table(flashe_pcg64::kDxsm)};
+static_assert(flashe_pcg64::kLanes == kStreamThreads, "a RunTable row per thread of a stream workgroup");
+static_assert(sizeof(flashe_pcg64::ClientPlan) == 32, "the plan rows are 32 bytes");
+template <flashe_pcg64::Variant V> struct Pcg64Draws {
+    const flashe_pcg64::ClientPlan *__restrict__ plans;
+    flashe_pcg64::Jump stride, lane;
+    __device__ __forceinline__ void start()
+    {
+        const uint64_t *row = kCohortRun[V].row[threadIdx.x].mul;
+        const flashe_pcg64::Row mine{{row[0], row[1]}, {row[2], row[3]}};
+        lane = flashe_pcg64::lane_jump(flashe_pcg64::workgroup_jump(kCohortPow2[V], blockIdx.x), mine);
+    }
+    __device__ __forceinline__ void next_pass() { lane = flashe_pcg64::next_pass(lane, stride); }
+    __device__ __forceinline__ void load4(int, uint64_t, uint64_t (&)[4]) const {}
+    __device__ __forceinline__ void draws4(int c, uint64_t, const uint64_t (&)[4], double (&d)[4]) const
+    {
+        const flashe_pcg64::ClientPlan &p = plans[c];
+        uint64_t w[4];
+        flashe_pcg64::run_words<V>(lane, flashe_pcg64::make128(p.origin[1], p.origin[0]), flashe_pcg64::make128(p.inc[1], p.inc[0]), w);
+#pragma unroll
+        for (int t = 0; t < 4; t++) d[t] = flashe_pcg64::to_double(w[t]);
+    }
+    __device__ __forceinline__ double draw(int c, uint64_t k) const
+    {
+        const flashe_pcg64::ClientPlan &p = plans[c];
+        return flashe_pcg64::to_double(flashe_pcg64::run_word<V>(lane, flashe_pcg64::make128(p.origin[1], p.origin[0]),
+                                                                 flashe_pcg64::make128(p.inc[1], p.inc[0]), static_cast<uint32_t>(k & 3)));
     }
 };
 
@@ -584,12 +628,15 @@ __device__ __forceinline__ void prep_cohort_run(const PrepCohort &pc, const Draw
 }
 
 // the un-batched launch over either source of draws: the layer of a lane's run of four, the run for the clients in groups of G, and
-// value by value for a run across a layer boundary or the model's tail
-template <class E, int G, class Draws> __device__ __forceinline__ void prep_cohort_body(const PrepCohort &pc, const Draws &dr, E modmask)
+// value by value for a run across a layer boundary or the model's tail.  A source that keeps lane state is told where the walk starts
+// (start: run blockIdx.x kStreamThreads + threadIdx.x) and of every pass on (next_pass: gridDim.x kStreamThreads runs further).
+template <class E, int G, class Draws> __device__ __forceinline__ void prep_cohort_body(const PrepCohort &pc, Draws &dr, E modmask)
 {
     const uint64_t n = pc.n, runs = (n + 3) / 4;
     const int C = pc.n_clients;
-    for (uint64_t g = static_cast<uint64_t>(blockIdx.x) * kStreamThreads + threadIdx.x; g < runs; g += static_cast<uint64_t>(gridDim.x) * kStreamThreads) {
+    dr.start();
+    for (uint64_t g = static_cast<uint64_t>(blockIdx.x) * kStreamThreads + threadIdx.x; g < runs;
+         g += static_cast<uint64_t>(gridDim.x) * kStreamThreads, dr.next_pass()) {
         const uint64_t k0 = 4 * g;
         int lo = 0, hi = pc.n_layers - 1;
         while (lo < hi) {
@@ -635,7 +682,8 @@ template <class E, int G, class Draws> __device__ __forceinline__ void prep_coho
 template <class E, int G>
 __global__ __launch_bounds__(kStreamThreads) void quantize_combine_cohort_kernel(const PrepCohort pc, E modmask)
 {
-    prep_cohort_body<E, G>(pc, BufferDraws{pc.u, pc.n_values}, modmask);
+    BufferDraws dr{pc.u, pc.n_values};
+    prep_cohort_body<E, G>(pc, dr, modmask);
 }
 
 // the same launch with the draws generated inside it (flashe_quantize_combine_cohort_philox*_dev): no draw buffer is written by an earlier
@@ -644,7 +692,18 @@ __global__ __launch_bounds__(kStreamThreads) void quantize_combine_cohort_kernel
 template <class E, int G>
 __global__ __launch_bounds__(kStreamThreads) void quantize_philox_combine_cohort_kernel(const PrepCohort pc, const ClientPlan *__restrict__ plans, E modmask)
 {
-    prep_cohort_body<E, G>(pc, PhiloxDraws{plans}, modmask);
+    PhiloxDraws dr{plans};
+    prep_cohort_body<E, G>(pc, dr, modmask);
+}
+
+// the same with the draws of np.random.PCG64 (V = kPcg64) or np.random.PCG64DXSM (kDxsm) streams generated inside it
+// (flashe_quantize_combine_cohort_pcg64*_dev): Pcg64Draws.  stride: the jump over 4 kStreamThreads gridDim.x steps.  pc.u is not read.
+template <class E, int G, flashe_pcg64::Variant V>
+__global__ __launch_bounds__(kStreamThreads) void quantize_pcg64_combine_cohort_kernel(const PrepCohort pc, const flashe_pcg64::ClientPlan *__restrict__ plans,
+                                                                                       const flashe_pcg64::Row stride, E modmask)
+{
+    Pcg64Draws<V> dr{plans, flashe_pcg64::from_row(stride), {}};
+    prep_cohort_body<E, G>(pc, dr, modmask);
 }
 
 // The batched job: a lane owns one batched element of every client -- quantize_batch_model_kernel's plaintext (every layer padded to whole
@@ -892,6 +951,33 @@ hipError_t launch_quantize_philox_combine_cohort(const LaunchEnv &env, const Pre
     if (elem_bytes == 4) return env.b > 32 ? hipErrorInvalidValue : launch_prep_philox<uint32_t>(env, pc, plans, static_cast<uint32_t>(lo));
     if (elem_bytes == 8) return env.b > 64 ? hipErrorInvalidValue : launch_prep_philox<uint64_t>(env, pc, plans, lo);
     if (elem_bytes == 16) return env.b <= 64 ? hipErrorInvalidValue : launch_prep_philox<u128>(env, pc, plans, (static_cast<u128>(hi) << 64) | lo);
+    return hipErrorInvalidValue;
+}
+
+// ---- the un-batched launch with PCG64 / PCG64DXSM draws generated inside it (quantize_pcg64_combine_cohort_kernel above) ----
+int prep_pcg64_grid(const LaunchEnv &env, uint64_t n) { return stream_grid(env, (n + 3) / 4); }
+
+template <class E> static hipError_t launch_prep_pcg64(const LaunchEnv &env, const PrepCohort &pc, const flashe_pcg64::ClientPlan *plans, uint32_t variant, E modmask)
+{
+    const int workgroups = prep_pcg64_grid(env, pc.n);
+    const dim3 g(workgroups), t(kStreamThreads);
+    const flashe_pcg64::Row stride = flashe_pcg64::to_row(flashe_pcg64::stride_jump(static_cast<flashe_pcg64::Variant>(variant), static_cast<uint64_t>(workgroups)));
+    if (variant == flashe_pcg64::kPcg64)
+        hipLaunchKernelGGL((quantize_pcg64_combine_cohort_kernel<E, kPrepCohortGroup, flashe_pcg64::kPcg64>), g, t, 0, env.stream, pc, plans, stride, modmask);
+    else
+        hipLaunchKernelGGL((quantize_pcg64_combine_cohort_kernel<E, kPrepCohortGroup, flashe_pcg64::kDxsm>), g, t, 0, env.stream, pc, plans, stride, modmask);
+    return hipGetLastError();
+}
+
+hipError_t launch_quantize_pcg64_combine_cohort(const LaunchEnv &env, const PrepCohort &pc, const flashe_pcg64::ClientPlan *plans, uint32_t variant, int elem_bytes)
+{
+    if (pc.n == 0 || pc.n_clients == 0) return hipSuccess;
+    if (pc.n_layers < 1 || !plans || variant >= flashe_pcg64::kVariants) return hipErrorInvalidValue;
+    uint64_t lo, hi;
+    masks_of(env.b, &lo, &hi);
+    if (elem_bytes == 4) return env.b > 32 ? hipErrorInvalidValue : launch_prep_pcg64<uint32_t>(env, pc, plans, variant, static_cast<uint32_t>(lo));
+    if (elem_bytes == 8) return env.b > 64 ? hipErrorInvalidValue : launch_prep_pcg64<uint64_t>(env, pc, plans, variant, lo);
+    if (elem_bytes == 16) return env.b <= 64 ? hipErrorInvalidValue : launch_prep_pcg64<u128>(env, pc, plans, variant, (static_cast<u128>(hi) << 64) | lo);
     return hipErrorInvalidValue;
 }
 

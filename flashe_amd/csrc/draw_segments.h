@@ -61,4 +61,42 @@ template <class Plan> FLASHE_HD const Plan &tile_plan(const Plan *plans, int n_p
     return plans[lo];
 }
 
+// ---- the draws of a cohort generated inside the launch that consumes them: the walk the kinds share ----
+// kCohortPlansOwn is the kind's own refusal, which it names itself (pcg64_stream.h: kCohortPlansMixedVariants).
+enum CohortPlansStatus { kCohortPlansOk = 0, kCohortPlansTooMany = 1, kCohortPlansNotTiled = 2, kCohortPlansSplitClient = 3, kCohortPlansOwn = 4 };
+
+// n_clients clients of n draws each from checked segments (check_segments: no overlap, nothing overflows): the non-empty segments must tile
+// the client-major draws [0, n_clients n) exactly -- no gap, nothing beyond (kCohortPlansNotTiled; an overlap is check_segments' to find)
+// -- and every client's stretch [c n, (c + 1) n) must lie inside ONE segment, since a client has one plan (kCohortPlansSplitClient).
+// kCohortPlansTooMany: n_clients n above kMaxDraws.  tiled() is asked once the tiling holds (the kind's own refusal of the table as a whole: its
+// status is returned unless it is kCohortPlansOk); emit(segment, first) is then called for every client in order: its stretch starts
+// `first` draws into that segment.  n = 0: every segment must be empty; nothing is emitted.
+template <class Segment, class Tiled, class Emit>
+inline CohortPlansStatus cohort_stretches(const Segment *segs, int n_segments, uint64_t n_clients, uint64_t n, Tiled tiled, Emit emit)
+{
+    if (n && n_clients > kMaxDraws / n) return kCohortPlansTooMany;
+    const uint64_t total = n_clients * n;
+    std::vector<int> order;
+    for (int s = 0; s < n_segments; s++)
+        if (segs[s].n) order.push_back(s);
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return segs[a].offset < segs[b].offset; });
+    uint64_t at = 0;
+    for (const int s : order) {
+        if (segs[s].offset != at) return kCohortPlansNotTiled;
+        at += segs[s].n;
+    }
+    if (at != total) return kCohortPlansNotTiled;
+    if (const CohortPlansStatus own = tiled()) return own;
+    if (!n) return kCohortPlansOk;
+    size_t i = 0;
+    for (uint64_t c = 0; c < n_clients; c++) {                   // (a client that no segment holds whole is found before anything of it is emitted)
+        const uint64_t first = c * n;
+        while (segs[order[i]].offset + segs[order[i]].n <= first) i++;
+        const Segment &s = segs[order[i]];
+        if (first + n > s.offset + s.n) return kCohortPlansSplitClient;
+        emit(s, first - s.offset);
+    }
+    return kCohortPlansOk;
+}
+
 }  // namespace flashe_draw

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 namespace flashe_philox { struct ClientPlan; }        // (philox_stream.h)
+namespace flashe_pcg64 { struct ClientPlan; }         // (pcg64_stream.h)
 
 namespace flashe {
 
@@ -394,6 +395,12 @@ hipError_t launch_quantize_philox_combine_cohort(const LaunchEnv &env, const Pre
 // (the rows' values in walking order, pads draw nothing) = word (skip + k) % 4 of block(base + (skip + k) / 4).  pc.u is not read.
 hipError_t launch_quantize_batch_philox_combine_cohort(const LaunchEnv &env, const PrepCohort &pc, const flashe_philox::ClientPlan *plans, const uint64_t *groups,
                                                        uint64_t n_groups, int elem_bytes);
+// The un-batched launch with the draws of np.random.PCG64 / PCG64DXSM streams generated inside it: pc.u is not read; plans = a DEVICE table
+// of one flashe_pcg64::ClientPlan (pcg64_stream.h) per client, all of the one variant (0 PCG64, 1 PCG64DXSM); a lane keeps the jump to its
+// run of four values and composes it with the stride jump of the grid, which prep_pcg64_grid gives for n values and the launch computes.
+int prep_pcg64_grid(const LaunchEnv &env, uint64_t n);
+hipError_t launch_quantize_pcg64_combine_cohort(const LaunchEnv &env, const PrepCohort &pc, const flashe_pcg64::ClientPlan *plans, uint32_t variant,
+                                                int elem_bytes);
 hipError_t launch_unbatch(const LaunchEnv &env, uint64_t nb, const uint64_t *in_dev, int field_bits, uint64_t *out_dev);
 
 // Caller-owned tensors either side of the model-wide codec (tensors.hip).  dtype / flags as in flashe_tensor_layer (include/flashe.h);

@@ -80,12 +80,6 @@ __global__ __launch_bounds__(flashe::kStreamThreads) void pcg64_random_table_ker
 
 u128 from_words(const uint64_t w[2]) { return flashe_pcg64::make128(w[1], w[0]); }
 
-void to_segment(const flashe_pcg64_segment &s, flashe_pcg64::Segment &o)
-{
-    o.state = from_words(s.state); o.inc = from_words(s.inc);
-    o.variant = s.variant; o.n = s.n; o.offset = s.offset;
-}
-
 // One variant's segments of the table: a launch of their tiles (none: nothing).  Rows [0, *tab_rows) of the ctx table are in use by the
 // launch of the other variant; the rows this one takes are added.
 template <Variant V>
@@ -121,7 +115,7 @@ extern "C" int flashe_pcg64_random_dev(flashe_ctx *ctx, flashe_pcg64_segment *se
 {
     CHECK_CTX(ctx);
     std::vector<flashe_pcg64::Segment> segs;
-    if (int rc = flashe_draw::read_segments(ctx, "flashe_pcg64_random_dev", segments, n_segments, u_dev, to_segment, flashe_pcg64::check_segments,
+    if (int rc = flashe_draw::read_segments(ctx, "flashe_pcg64_random_dev", segments, n_segments, u_dev, flashe_pcg64::from_c<flashe_pcg64_segment>, flashe_pcg64::check_segments,
                                             "a variant that is neither PCG64 (0) nor PCG64DXSM (1)", segs))
         return rc;
     size_t tab_rows = 0;

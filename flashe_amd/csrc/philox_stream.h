@@ -263,40 +263,15 @@ FLASHE_UNROLL
     }
 };
 
-enum CohortPlansStatus { kCohortPlansOk = 0, kCohortPlansTooMany = 1, kCohortPlansNotTiled = 2, kCohortPlansSplitClient = 3 };
-
-// The plans of n_clients clients of n draws each from checked segments (check_segments: no overlap, nothing overflows): the non-empty
-// segments must tile the client-major draws [0, n_clients n) exactly -- no gap, nothing beyond (kCohortPlansNotTiled; an overlap is
-// check_segments' to find) -- and every client's stretch [c n, (c + 1) n) must lie inside ONE segment, since a client has one plan
-// (kCohortPlansSplitClient).  kCohortPlansTooMany: n_clients n above kMaxDraws.  n = 0: every segment must be empty; no plans.
+// The plans of n_clients clients of n draws each from checked segments: draw_segments.h's cohort_stretches (its contract and status
+// values: kCohortPlansTooMany, kCohortPlansNotTiled, kCohortPlansSplitClient), one client_plan per stretch.  No plans unless kCohortPlansOk.
 inline CohortPlansStatus cohort_plans(const Segment *segs, int n_segments, uint64_t n_clients, uint64_t n, std::vector<ClientPlan> &plans)
 {
     plans.clear();
-    if (n && n_clients > kMaxDraws / n) return kCohortPlansTooMany;
-    const uint64_t total = n_clients * n;
-    std::vector<int> order;
-    for (int s = 0; s < n_segments; s++)
-        if (segs[s].n) order.push_back(s);
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return segs[a].offset < segs[b].offset; });
-    uint64_t at = 0;
-    for (const int s : order) {
-        if (segs[s].offset != at) return kCohortPlansNotTiled;
-        at += segs[s].n;
-    }
-    if (at != total) return kCohortPlansNotTiled;
-    if (!n) return kCohortPlansOk;
-    size_t i = 0;
-    for (uint64_t c = 0; c < n_clients; c++) {
-        const uint64_t first = c * n;
-        while (segs[order[i]].offset + segs[order[i]].n <= first) i++;
-        const Segment &s = segs[order[i]];
-        if (first + n > s.offset + s.n) {
-            plans.clear();
-            return kCohortPlansSplitClient;
-        }
-        plans.push_back(client_plan(s, first - s.offset));
-    }
-    return kCohortPlansOk;
+    const CohortPlansStatus st = cohort_stretches(segs, n_segments, n_clients, n, [] { return kCohortPlansOk; },
+                                                  [&](const Segment &s, uint64_t first) { plans.push_back(client_plan(s, first)); });
+    if (st != kCohortPlansOk) plans.clear();
+    return st;
 }
 
 }  // namespace flashe_philox

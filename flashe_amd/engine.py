@@ -895,6 +895,26 @@ class Engine:
             hand_back()
         return took
 
+    def quantize_combine_cohort_pcg64_dev(self, n, layers, srcs, dtypes, element_bits, generators_or_states, counts, offsets, masks, cts, sum_out,
+                                          compact=False):
+        """quantize_combine_cohort_philox_dev (un-batched; there is no batched form) for generators over np.random.PCG64 -- the one
+        np.random.default_rng returns -- or np.random.PCG64DXSM (flashe_quantize_combine_cohort_pcg64_dev; compact=True: its _u32 form):
+        the launch generates the draws, no draw buffer exists.  generators_or_states, counts, offsets: pcg64_random_dev's table
+        (_draw_table) over the client-major draw positions, under the same rules -- the entries tile [0, C n) exactly, every client's
+        draws inside one entry -- and all of ONE variant.  The advanced states are handed back only after the call has succeeded (with
+        has_uint32 / uinteger as they were); a refusal raises and advances nothing.  Returns False -- nothing was launched, nothing
+        advanced -- when the library declines (FLASHE_ENOTSUP), True otherwise."""
+        arr, nl = self._tensor_layers(layers)
+        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
+        pm, _a = self._ptr_array(masks)
+        pc, _b = self._ptr_array(cts)
+        segs, counts, offsets, hand_back = _draw_table(_Pcg64Draws, generators_or_states, counts, offsets)
+        fn = self._lib.flashe_quantize_combine_cohort_pcg64_u32_dev if compact else self._lib.flashe_quantize_combine_cohort_pcg64_dev
+        took = self._took(fn(self._h, C, int(n), arr, nl, ps, pd, element_bits, segs, len(counts), pm, pc, self._ptr(sum_out)))
+        if took:
+            hand_back()
+        return took
+
     def quantize_batch_combine_cohort_philox_dev(self, n_values, n_elems, field_bits, layers, srcs, dtypes, element_bits, generators_or_states, counts,
                                                  offsets, masks, cts, sum_out):
         """quantize_combine_cohort_philox_dev(..., batch=(n_elems, field_bits)) under the name FlasheCohort looks the batched form up by."""
@@ -1589,6 +1609,25 @@ class Engine:
         wg, tiles, draws = c_u32(0), c_u64(0), c_u32(0)
         self._check(self._lib.flashe_pcg64_grid(self._h, int(n), ctypes.byref(wg), ctypes.byref(tiles), ctypes.byref(draws)))
         return int(wg.value), int(tiles.value), int(draws.value)
+
+    def pcg64_cohort_grid(self, n):
+        """The workgroups of the launch quantize_combine_cohort_pcg64_dev makes for n values per client (256 lanes each, a lane owning runs
+        of four values: more runs than lanes are further passes, which compose the lane's jump with the grid's stride jump)."""
+        wg = c_u32(0)
+        self._check(self._lib.flashe_pcg64_cohort_grid(self._h, int(n), ctypes.byref(wg)))
+        return int(wg.value)
+
+    @staticmethod
+    def pcg64_cohort_lane_draws(generator_or_state, first, workgroups, run, iterations):
+        """Host only: the 4 x iterations draws the lane that owns run `run` of that launch on a grid of `workgroups` generates in its first
+        `iterations` passes for a client whose stretch starts `first` draws into the generator (flashe_pcg64_cohort_lane_draws: the
+        header functions the kernel compiles) -- values 4 (run + 256 workgroups p) + i of that client.  Nothing is advanced."""
+        g = generator_or_state
+        seg = _Pcg64Draws.segment(g.bit_generator.state if isinstance(g, np.random.Generator) else g)
+        out = np.empty(4 * int(iterations), dtype=np.float64)
+        _lib.check(None, _lib.load().flashe_pcg64_cohort_lane_draws(seg.variant, seg.state, seg.inc, int(first), int(workgroups), int(run), int(iterations),
+                                                                   out.ctypes.data_as(c_vp)))
+        return out
 
     def quantize_encrypt_dev(self, it, idx, scheme, n, n_jobs, x, x_is_f64, alpha, element_bits, u, ct):
         """ct = encrypt(quantize(x)) in one launch (un-batched values); x float32 / float64, u float64 uniforms, all device-resident."""

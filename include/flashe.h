@@ -93,7 +93,9 @@ typedef struct flashe_ctx flashe_ctx;
  *      flashe_quantize_encrypt_cohort_cut_runs_u32_dev / flashe_quantize_batch_encrypt_cohort_cut_runs_dev (the cut launch for a round in
  *      which clients dropped out -- every gap is a cut -- and for a batched job); flashe_quantize_combine_cohort_philox_dev /
  *      flashe_quantize_combine_cohort_philox_u32_dev (a precompute job's cohort online with the draws of np.random.Philox streams
- *      generated inside the launch: no draw buffer) and flashe_quantize_batch_combine_cohort_philox_dev (the same for a batched job) */
+ *      generated inside the launch: no draw buffer) and flashe_quantize_batch_combine_cohort_philox_dev (the same for a batched job);
+ *      flashe_quantize_combine_cohort_pcg64_dev / flashe_quantize_combine_cohort_pcg64_u32_dev (the un-batched form for the streams of
+ *      np.random.PCG64 / PCG64DXSM, np.random.default_rng's generator) with flashe_pcg64_cohort_grid + flashe_pcg64_cohort_lane_draws */
 #define FLASHE_ABI_VERSION 4
 int flashe_abi_version(void);
 int flashe_device_count(int *count);
@@ -1128,6 +1130,39 @@ int flashe_pcg64_advance(uint32_t variant, uint64_t state[2], const uint64_t inc
  * draws, 16 per lane at a stride of 256, and its workgroups (at most 8 per compute unit the ctx may use; more tiles than that are further
  * trips). */
 int flashe_pcg64_grid(flashe_ctx *ctx, uint64_t n, uint32_t *workgroups, uint64_t *tiles, uint32_t *tile_draws);
+/* A precompute cohort's un-batched online step with the draws of np.random.PCG64 / np.random.PCG64DXSM streams generated INSIDE the launch
+ * (new): the arguments, results and refusals of flashe_quantize_combine_cohort_philox_dev / _u32_dev with a table of flashe_pcg64_segment
+ * in place of the Philox one -- segment s gives n draws of its generator to the client-major draw positions [offset, offset + n), client c
+ * rounding its value k with draw c * n + k; a stretch may start anywhere in its generator's stream.  No draw buffer exists.  A lane owns
+ * runs of four values and keeps ONE jump (A^k, G_k) of the LCG for all clients -- over the 4 g steps to its run g, built once from tables
+ * and composed with the grid's stride jump after every pass --; a client is a 32-byte plan (the state its first draw outputs from, and its
+ * inc): two 128-bit low products apply the jump, three step on.  The ciphertexts and the sum are those of flashe_pcg64_random_dev +
+ * flashe_quantize_combine_cohort_dev / _u32_dev bit for bit.  Refused with FLASHE_EINVAL, in this order: everything
+ * flashe_pcg64_random_dev refuses in a table (a variant above 1, more than 128 segments, overflowing or overlapping ranges, a graph
+ * being captured); non-empty segments that do not tile [0, n_clients * n) exactly, a client whose n draws lie in two segments, PCG64 and
+ * PCG64DXSM segments in one table (the lane's jump is shared by the clients, so a launch has one variant); everything
+ * flashe_quantize_combine_cohort_dev / _u32_dev refuse.  FLASHE_ENOTSUP as there.  On success every segment's state is advanced in
+ * place on the host as flashe_pcg64_random_dev advances it -- nothing is read back, the call does not synchronise; on any refusal
+ * nothing is advanced, staged or launched.  n = 0 (every segment empty): FLASHE_OK, nothing launched or advanced.  There is no batched
+ * form. */
+int flashe_quantize_combine_cohort_pcg64_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers,
+                                             const void *const *src_dev, const int32_t *src_dtype, int element_bits,
+                                             flashe_pcg64_segment *segments, int n_segments, const uint64_t *const *mask_dev,
+                                             uint64_t *const *ct_dev, uint64_t *sum_out_dev);
+int flashe_quantize_combine_cohort_pcg64_u32_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers,
+                                                 const void *const *src_dev, const int32_t *src_dtype, int element_bits,
+                                                 flashe_pcg64_segment *segments, int n_segments, const uint32_t *const *mask_dev,
+                                                 uint32_t *const *ct_dev, uint32_t *sum_out_dev);
+/* Host only (new): the workgroups of the grid flashe_quantize_combine_cohort_pcg64_dev / _u32_dev launch for n values per client (a lane
+ * owns runs of four values; at most 8 workgroups of 256 lanes per compute unit the ctx may use: more runs than that are further passes). */
+int flashe_pcg64_cohort_grid(flashe_ctx *ctx, uint64_t n, uint32_t *workgroups);
+/* Host only (new): the draws the lane that owns run `run` (lane run % 256 of workgroup run / 256; run < 256 * workgroups) of that launch
+ * on a grid of `workgroups` generates in its first `iterations` passes for a client whose stretch starts `first` draws into the generator
+ * (variant, state, inc): out[4 p + i] = the draw of value 4 * (run + 256 * workgroups * p) + i of that client, through exactly the
+ * functions the kernel compiles (the tables, the workgroup's and the lane's jump, the stride jump, apply and three steps) -- so that
+ * the stride arithmetic can be compared with NumPy for grids and lengths no test launches.  out: 4 * iterations doubles. */
+int flashe_pcg64_cohort_lane_draws(uint32_t variant, const uint64_t state[2], const uint64_t inc[2], uint64_t first, uint32_t workgroups,
+                                   uint64_t run, uint64_t iterations, double *out);
 
 /* _static_quantize_padding_asymmetric -- federatedml/secureprotol/jzf_quantize.py:55-67:
  * q = floor(clip(x, -alpha, alpha) + alpha) * (2^element_bits - 1) / (2 alpha) + u), with numpy's
