@@ -110,6 +110,24 @@ def _cohort_signature(name):
             + [c_vp] * (("_u32_" not in name) + ("_cut_" in name)))                                                                 # dmask, scratch
 
 
+# The prepared cohort's online launches (abi_layers.hip, quantize_combine_cohort).  What a name says: batch_ = n_values and n_elems in place
+# of n and a field_bits, philox / pcg64 = a segment table and its count in place of u_dev; _u32_ changes the vectors' elements only.
+PREPARED_COHORT_LAUNCHES = (
+    "flashe_quantize_combine_cohort_dev", "flashe_quantize_combine_cohort_u32_dev",
+    "flashe_quantize_combine_cohort_philox_dev", "flashe_quantize_combine_cohort_philox_u32_dev",
+    "flashe_quantize_combine_cohort_pcg64_dev", "flashe_quantize_combine_cohort_pcg64_u32_dev",
+    "flashe_quantize_batch_combine_cohort_dev", "flashe_quantize_batch_combine_cohort_philox_dev",
+)
+
+
+def _prepared_cohort_signature(name):
+    batched = "_batch_" in name
+    seg = PhiloxSegment if "_philox_" in name else Pcg64Segment if "_pcg64_" in name else None
+    return (c_int, [c_vp, c_int] + [c_u64] * (2 if batched else 1)                                                                 # ctx, n_clients, n
+            + [ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp), ctypes.POINTER(ctypes.c_int32)] + [c_int] * (2 if batched else 1)   # table, sources, bits
+            + ([ctypes.POINTER(seg), c_int] if seg else [c_vp]) + [ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp])           # draws, masks, cts, sum
+
+
 _SIGNATURES = {
     # name: (restype, argtypes)
     "flashe_abi_version": (c_int, []),
@@ -255,22 +273,7 @@ _SIGNATURES = {
     "flashe_cohort_cut_parts": (c_int, [c_vp, c_int, c_u64, c_u32, c_int, ctypes.POINTER(c_int)]),
     "flashe_cohort_cut_pieces": (c_int, [c_vp, ctypes.POINTER(c_u32), c_int, c_u64, c_u32, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "flashe_cohort_masks_u32_dev": (c_int, [c_vp, c_u32, c_u32, c_int, c_u64, c_u32, ctypes.POINTER(c_vp)]),
-    "flashe_quantize_combine_cohort_dev": (c_int, [c_vp, c_int, c_u64, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp),
-                                                   ctypes.POINTER(ctypes.c_int32), c_int, c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
-    "flashe_quantize_combine_cohort_u32_dev": (c_int, [c_vp, c_int, c_u64, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp),
-                                                       ctypes.POINTER(ctypes.c_int32), c_int, c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
-    "flashe_quantize_combine_cohort_philox_dev": (c_int, [c_vp, c_int, c_u64, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp),
-                                                          ctypes.POINTER(ctypes.c_int32), c_int, ctypes.POINTER(PhiloxSegment), c_int,
-                                                          ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
-    "flashe_quantize_combine_cohort_philox_u32_dev": (c_int, [c_vp, c_int, c_u64, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp),
-                                                              ctypes.POINTER(ctypes.c_int32), c_int, ctypes.POINTER(PhiloxSegment), c_int,
-                                                              ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
-    "flashe_quantize_batch_combine_cohort_dev": (c_int, [c_vp, c_int, c_u64, c_u64, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp),
-                                                         ctypes.POINTER(ctypes.c_int32), c_int, c_int, c_vp, ctypes.POINTER(c_vp),
-                                                         ctypes.POINTER(c_vp), c_vp]),
-    "flashe_quantize_batch_combine_cohort_philox_dev": (c_int, [c_vp, c_int, c_u64, c_u64, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp),
-                                                                ctypes.POINTER(ctypes.c_int32), c_int, c_int, ctypes.POINTER(PhiloxSegment), c_int,
-                                                                ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
+    **{name: _prepared_cohort_signature(name) for name in PREPARED_COHORT_LAUNCHES},
     "flashe_combine_unquantize_model_dev": (c_int, [c_vp, c_u64, c_vp, c_vp, c_vp, ctypes.POINTER(CodecLayer), c_int, c_int, c_int, c_vp]),
     "flashe_combine_unbatch_unquantize_model_dev": (c_int, [c_vp, ctypes.POINTER(BatchLayer), c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_u64, c_vp]),
     "flashe_decrypt_prepared_unquantize_model_dev": (c_int, [c_vp, c_u32, c_u32p, c_int, c_u32p, c_int, c_u64, c_u32, c_vp, ctypes.POINTER(CodecLayer),
@@ -287,12 +290,6 @@ _SIGNATURES = {
     "flashe_pcg64_random_dev": (c_int, [c_vp, ctypes.POINTER(Pcg64Segment), c_int, c_vp]),
     "flashe_pcg64_advance": (c_int, [c_u32, c_u64p, c_u64p, c_u64p]),
     "flashe_pcg64_grid": (c_int, [c_vp, c_u64, c_u32p, c_u64p, c_u32p]),
-    "flashe_quantize_combine_cohort_pcg64_dev": (c_int, [c_vp, c_int, c_u64, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp),
-                                                         ctypes.POINTER(ctypes.c_int32), c_int, ctypes.POINTER(Pcg64Segment), c_int,
-                                                         ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
-    "flashe_quantize_combine_cohort_pcg64_u32_dev": (c_int, [c_vp, c_int, c_u64, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp),
-                                                             ctypes.POINTER(ctypes.c_int32), c_int, ctypes.POINTER(Pcg64Segment), c_int,
-                                                             ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
     "flashe_pcg64_cohort_grid": (c_int, [c_vp, c_u64, c_u32p]),
     "flashe_pcg64_cohort_lane_draws": (c_int, [c_u32, c_u64p, c_u64p, c_u64, c_u32, c_u64, c_u64, c_vp]),
     "flashe_quantize_dev": (c_int, [c_vp, c_u64, c_vp, c_int, ctypes.c_double, c_int, c_vp, c_vp]),

@@ -1904,10 +1904,13 @@ class FlasheCohort(object):
         """"prepared-cohort": ONE online launch, every client's floats and its precomputed mask -> its ciphertext, and their sum; no AES.
         False: the library declined, nothing was launched."""
         ld = self.lead
-        q = ld.quantizer
-        return ld.cipher.engine.quantize_combine_cohort_dev(plan.n, rows, srcs, dts, q.element_bits, du, [self._masks[p].buf for p in plan.present],
-                                                            [v.buf for v in cts], psum.buf, compact=self.compact,
-                                                            batch=(plan.n_elems, _field_bits(q.element_bits, q.num_clients)) if ld.batch else None)
+        masks, outs, batch = self._prepared_vectors(plan, cts)
+        return ld.cipher.engine.quantize_combine_cohort_dev(plan.n, rows, srcs, dts, ld.quantizer.element_bits, du, masks, outs, psum.buf, compact=self.compact, batch=batch)
+
+    def _prepared_vectors(self, plan, cts):
+        """What either "prepared-cohort" launch is given: the present clients' masks, the ciphertexts, and batch= (None: not a batched job)."""
+        q, masks = self.lead.quantizer, [self._masks[p].buf for p in plan.present]
+        return masks, [v.buf for v in cts], (plan.n_elems, _field_bits(q.element_bits, q.num_clients)) if self.lead.batch else None
 
     def _launch_prepared_inline(self, plan, rows, srcs, dts, rng, cts, psum, pcg64=False):
         """"prepared-cohort" with the draws generated inside the online launch (_inline_draws; pcg64: _inline_pcg64_draws, the PCG64
@@ -1917,15 +1920,12 @@ class FlasheCohort(object):
         ld = self.lead
         C, n = len(plan.present), plan.n
         gens, counts, offsets = (rng, [n] * C, [p * n for p in range(C)]) if isinstance(rng, list) else ([rng], [C * n], [0])
-        q = ld.quantizer
+        masks, outs, batch = self._prepared_vectors(plan, cts)
+        eng, bits = ld.cipher.engine, ld.quantizer.element_bits
         if pcg64:
-            return ld.cipher.engine.quantize_combine_cohort_pcg64_dev(n, rows, srcs, dts, q.element_bits, gens, counts, offsets,
-                                                                      [self._masks[p].buf for p in plan.present], [v.buf for v in cts], psum.buf,
-                                                                      compact=self.compact)
-        return ld.cipher.engine.quantize_combine_cohort_philox_dev(n, rows, srcs, dts, q.element_bits, gens, counts, offsets,
-                                                                   [self._masks[p].buf for p in plan.present], [v.buf for v in cts], psum.buf,
-                                                                   compact=self.compact,
-                                                                   **({"batch": (plan.n_elems, _field_bits(q.element_bits, q.num_clients))} if ld.batch else {}))
+            return eng.quantize_combine_cohort_pcg64_dev(n, rows, srcs, dts, bits, gens, counts, offsets, masks, outs, psum.buf, compact=self.compact)
+        return eng.quantize_combine_cohort_philox_dev(n, rows, srcs, dts, bits, gens, counts, offsets, masks, outs, psum.buf, compact=self.compact,
+                                                      **({"batch": batch} if batch else {}))
 
     def _launch_staged(self, plan, tables, du, cts, psum, prepared):
         """A quantise (+ batch) pass per client into plaintexts -- un-batched: one value per element, field_bits = int_bits -- then

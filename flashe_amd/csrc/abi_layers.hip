@@ -934,110 +934,160 @@ int flashe_quantize_batch_encrypt_cohort_cut_runs_dev(flashe_ctx *ctx, uint32_t 
 }
 
 // ---- the cohort's ONLINE step with masks the caller holds (a precompute job's cohort: the mask chain ran in idle time) ----
-// What the three entry points below share: the checks of the chained cohorts (cohort_check_args', without cipher indices), the vectors -- every
-// mask and ciphertext given and aligned to its element, the sum apart from all of them and from every source --, cohort_stage's table,
-// sources and stage pass with the mask and ciphertext pointers (and the batched rows) behind it in the same upload, one launch.
-// plans: one draw plan per client, uploaded behind the pointers (flashe_tables::prepared_draws_block; batched: behind the rows and the
-// rows' first groups, prepared_batch_draws_block) -- the launch generates the draws and u_dev is not read.
-// (the rows of either kind of generator: flashe_philox::ClientPlan, variant < 0, or flashe_pcg64::ClientPlan of the one variant)
-struct DrawPlans {
-    const void *rows;
-    size_t count, row_bytes;
-    int variant;
-    DrawPlans(const std::vector<flashe_philox::ClientPlan> &p) : rows(p.data()), count(p.size()), row_bytes(sizeof(flashe_philox::ClientPlan)), variant(-1) {}
-    DrawPlans(const std::vector<flashe_pcg64::ClientPlan> &p, flashe_pcg64::Variant v)
-        : rows(p.data()), count(p.size()), row_bytes(sizeof(flashe_pcg64::ClientPlan)), variant(static_cast<int>(v)) {}
-};
-static int quantize_combine_cohort(flashe_ctx *ctx, const char *who, int elem_bytes, int n_clients, uint64_t n_values, uint64_t n_elems, const uint64_t *n_elems_arg,
-                                   const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype, int element_bits,
-                                   int field_bits, const double *u_dev, const void *const *mask_dev, void *const *ct_dev, void *sum_out_dev,
-                                   const DrawPlans *plans = nullptr)
+// What tells the eight entry points apart, besides where their draws come from: what masks, ciphertexts and sum are made of, and whether
+// the job is batched (then the table and the draws are over n_values values and the launch over the n_elems batched elements).
+struct PrepForm { const char *who; int elem_bytes; bool batched; };
+// the draw plans of a form that draws inside the launch: one row per client (flashe_philox::ClientPlan, or flashe_pcg64::ClientPlan of the one variant)
+struct DrawPlans { PrepDraws::Kind kind; const void *rows; size_t count, row_bytes; uint32_t variant; };
+
+// The one body, every step once and in the order of its refusals:
+//    1. n_clients < 1
+//    2. drawn forms: the segment table's own refusals (flashe_draw::read_segments: its count, a null table, a capture, check_segments)
+//    3. drawn forms: the plan statuses -- overflow, not tiled, split client and, for PCG64, mixed variants
+//    4. null argument
+//    5. element_bits
+//    6. u_dev's alignment
+//    7. the layer table
+//    8. batched: the batch bits, then the batched count
+//    9. per client: null, then misaligned, then the sum aliases its mask or ciphertext
+//   10. the sum's alignment
+//   11. the sum aliases a source
+//   12. the compact layout declined (FLASHE_ENOTSUP)
+//   13. the empty model: FLASHE_OK with nothing staged
+//   14. stage: cohort_stage's table, sources and stage pass, with the block of flashe_tables::prepared_block behind them in the same upload
+//   15. launch (launch_prep_cohort)
+//   16. drawn forms: the caller's segments advance -- after the launch has been made, and only when n != 0
+// Steps 2, 3 and 16 are quantize_combine_cohort_drawn's, below.  plans: the launch generates the draws and u_dev is not read.
+static int quantize_combine_cohort(flashe_ctx *ctx, const PrepForm &f, int n_clients, uint64_t n_values, uint64_t n_elems_arg, const flashe_tensor_layer *layers,
+                                   int n_layers, const void *const *src_dev, const int32_t *src_dtype, int element_bits, int field_bits, const double *u_dev,
+                                   const void *const *mask_dev, void *const *ct_dev, void *sum_out_dev, const DrawPlans *plans = nullptr)
 {
-    const bool batched = n_elems_arg != nullptr;
-    if (n_clients < 1) return fail(ctx, FLASHE_EINVAL, "%s: n_clients must be >= 1", who);
-    if (!src_dev || !mask_dev || !ct_dev || (n_values && !u_dev && !plans)) return fail(ctx, FLASHE_EINVAL, "%s: null argument", who);
+    if (n_clients < 1) return fail(ctx, FLASHE_EINVAL, "%s: n_clients must be >= 1", f.who);
+    if (!src_dev || !mask_dev || !ct_dev || (n_values && !u_dev && !plans)) return fail(ctx, FLASHE_EINVAL, "%s: null argument", f.who);
     int rc = check_element_bits(ctx, element_bits);
     if (rc || (rc = check_f64_aligned(ctx, u_dev, "u_dev")) || (rc = check_tensor_layers(ctx, n_values, layers, n_layers, false))) return rc;
-    std::vector<uint64_t> extra(2 * static_cast<size_t>(n_clients));
-    uint64_t bs = 1;
-    if (batched) {
+    // the batched rows of the non-empty layers (cohort_stage's rows, in its order): first element, value count
+    uint64_t bs = 1, n_elems = n_values;
+    std::vector<uint64_t> rows;
+    if (f.batched) {
         if ((rc = check_batch_bits(ctx, element_bits, field_bits, &bs))) return rc;
         auto size_of = [&](int l) { return layer_end(layers, n_layers, l, n_values) - layers[l].start; };
-        n_elems = flashe_tables::batched_elems(n_layers, bs, size_of, [&](int l, uint64_t elem, uint64_t) { extra.push_back(elem); extra.push_back(size_of(l)); });
-        if ((rc = check_batched_count(ctx, n_elems, *n_elems_arg))) return rc;
+        n_elems = flashe_tables::batched_elems(n_layers, bs, size_of, [&](int l, uint64_t elem, uint64_t) { rows.push_back(elem); rows.push_back(size_of(l)); });
+        if ((rc = check_batched_count(ctx, n_elems, n_elems_arg))) return rc;
     }
-    const uintptr_t amask = static_cast<uintptr_t>(elem_bytes - 1);
+    const uintptr_t amask = static_cast<uintptr_t>(f.elem_bytes - 1);
     for (int c = 0; c < n_clients; c++) {
         if (n_elems && (!mask_dev[c] || !ct_dev[c])) return fail(ctx, FLASHE_EINVAL, "client %d: null mask or ciphertext", c);
         if ((reinterpret_cast<uintptr_t>(mask_dev[c]) | reinterpret_cast<uintptr_t>(ct_dev[c])) & amask)
-            return fail(ctx, FLASHE_EINVAL, "client %d: the mask or the ciphertext is not %d-byte aligned", c, elem_bytes);
+            return fail(ctx, FLASHE_EINVAL, "client %d: the mask or the ciphertext is not %d-byte aligned", c, f.elem_bytes);
         if (sum_out_dev && (mask_dev[c] == sum_out_dev || ct_dev[c] == sum_out_dev)) return fail(ctx, FLASHE_EINVAL, "client %d: the sum aliases the mask or the ciphertext", c);
-        extra[static_cast<size_t>(c)] = reinterpret_cast<uintptr_t>(mask_dev[c]);
-        extra[static_cast<size_t>(n_clients) + c] = reinterpret_cast<uintptr_t>(ct_dev[c]);
     }
-    if (reinterpret_cast<uintptr_t>(sum_out_dev) & amask) return fail(ctx, FLASHE_EINVAL, "sum_out_dev must be %d-byte aligned", elem_bytes);
+    if (reinterpret_cast<uintptr_t>(sum_out_dev) & amask) return fail(ctx, FLASHE_EINVAL, "sum_out_dev must be %d-byte aligned", f.elem_bytes);
     if (sum_out_dev)
         for (size_t i = 0; i < flashe_tables::cohort_sources(n_clients, n_layers); i++)
             if (src_dev[i] == sum_out_dev) return fail(ctx, FLASHE_EINVAL, "the sum aliases a source (client %d layer %d)", static_cast<int>(i / n_layers), static_cast<int>(i % n_layers));
-    if (elem_bytes == 4 && flashe_ctx_compact_layout(ctx) != 1) return cohort_declined(ctx, who, "prepared compact cohort");
+    if (f.elem_bytes == 4 && flashe_ctx_compact_layout(ctx) != 1) return cohort_declined(ctx, f.who, "prepared compact cohort");
     if (n_elems == 0) return FLASHE_OK;                                    // (an empty model: nothing staged, nothing launched)
-    const size_t plan_words = plans ? plans->row_bytes / sizeof(uint64_t) : 0;
-    const size_t n_rows = extra.size() / 2 - static_cast<size_t>(n_clients);                  // (batched: two words per row so far)
-    uint64_t n_groups = 0;
-    if (plans && batched) {
-        const flashe_tables::PreparedBatchDrawsBlock at = flashe_tables::prepared_batch_draws_block(n_clients, n_rows, plan_words);
-        extra.resize(at.words);
-        n_groups = flashe_tables::batched_groups(extra.data() + at.rows / 8, n_rows, bs, extra.data() + at.groups / 8);
-        memcpy(extra.data() + at.plans / 8, plans->rows, plans->count * plans->row_bytes);
-    } else if (plans) {
-        extra.resize(flashe_tables::prepared_draws_block(n_clients, plan_words).words);
-        memcpy(extra.data() + 2 * static_cast<size_t>(n_clients), plans->rows, plans->count * plans->row_bytes);
+    // the block behind cohort_stage's tables: the pointers, the rows, a batched drawn form's groups, the plans
+    const bool grouped = plans && f.batched;
+    const size_t n_rows = rows.size() / 2;
+    const flashe_tables::PreparedBlock at = flashe_tables::prepared_block(n_clients, n_rows, plans ? plans->row_bytes / sizeof(uint64_t) : 0, grouped);
+    std::vector<uint64_t> extra(at.words);
+    for (int c = 0; c < n_clients; c++) {
+        extra[at.mask / 8 + static_cast<size_t>(c)] = reinterpret_cast<uintptr_t>(mask_dev[c]);
+        extra[at.ct / 8 + static_cast<size_t>(c)] = reinterpret_cast<uintptr_t>(ct_dev[c]);
     }
+    std::copy(rows.begin(), rows.end(), extra.begin() + at.rows / 8);
+    PrepDraws draws{plans ? plans->kind : PrepDraws::kBuffer, f.batched, nullptr, plans ? plans->variant : 0, nullptr, 0};
+    if (grouped) draws.n_groups = flashe_tables::batched_groups(rows.data(), n_rows, bs, extra.data() + at.groups / 8);
+    if (plans) memcpy(extra.data() + at.plans / 8, plans->rows, plans->count * plans->row_bytes);
     CohortCodec cc{};
     const char *extra_dev = nullptr;
     if ((rc = cohort_stage(ctx, n_clients, n_values, layers, n_layers, src_dev, src_dtype, element_bits, cc, extra.data(), extra.size() * sizeof(uint64_t), &extra_dev)))
         return rc;
+    const bool no_rows = plans && !f.batched;      // (an un-batched drawn form reads neither rows nor bs: it keeps the null and the 0 it has been launched with)
     PrepCohort pc{};
     pc.layers = cc.layers; pc.src = cc.src; pc.n_layers = cc.n_layers;
-    if (plans && batched) {
-        const flashe_tables::PreparedBatchDrawsBlock at = flashe_tables::prepared_batch_draws_block(n_clients, n_rows, plan_words);
-        pc.mask = reinterpret_cast<const void *const *>(extra_dev + at.mask);
-        pc.ct = reinterpret_cast<void *const *>(extra_dev + at.ct);
-        pc.rows = reinterpret_cast<const uint64_t *>(extra_dev + at.rows);
-        pc.sum = sum_out_dev; pc.n = n_elems; pc.n_values = n_values; pc.n_clients = n_clients; pc.field_bits = field_bits; pc.bs = static_cast<int>(bs);
-        HIP_TRY(ctx, launch_quantize_batch_philox_combine_cohort(ctx->env, pc, reinterpret_cast<const flashe_philox::ClientPlan *>(extra_dev + at.plans),
-                                                                 reinterpret_cast<const uint64_t *>(extra_dev + at.groups), n_groups, elem_bytes));
-        return FLASHE_OK;
-    }
-    if (plans) {
-        const flashe_tables::PreparedDrawsBlock at = flashe_tables::prepared_draws_block(n_clients, plan_words);
-        pc.mask = reinterpret_cast<const void *const *>(extra_dev + at.mask);
-        pc.ct = reinterpret_cast<void *const *>(extra_dev + at.ct);
-        pc.sum = sum_out_dev; pc.n = n_elems; pc.n_values = n_values; pc.n_clients = n_clients;
-        if (plans->variant >= 0) {
-            HIP_TRY(ctx, launch_quantize_pcg64_combine_cohort(ctx->env, pc, reinterpret_cast<const flashe_pcg64::ClientPlan *>(extra_dev + at.plans),
-                                                              static_cast<uint32_t>(plans->variant), elem_bytes));
-            return FLASHE_OK;
-        }
-        HIP_TRY(ctx, launch_quantize_philox_combine_cohort(ctx->env, pc, reinterpret_cast<const flashe_philox::ClientPlan *>(extra_dev + at.plans), elem_bytes));
-        return FLASHE_OK;
-    }
-    const flashe_tables::PreparedBlock at = flashe_tables::prepared_block(n_clients);
-    pc.mask = reinterpret_cast<const void *const *>(extra_dev + at.mask);
-    pc.ct = reinterpret_cast<void *const *>(extra_dev + at.ct);
-    pc.rows = reinterpret_cast<const uint64_t *>(extra_dev + at.rows);
-    pc.u = u_dev; pc.sum = sum_out_dev; pc.n = n_elems; pc.n_values = n_values; pc.n_clients = n_clients; pc.field_bits = field_bits; pc.bs = static_cast<int>(bs);
-    HIP_TRY(ctx, launch_quantize_combine_cohort(ctx->env, pc, elem_bytes, batched));
+    pc.mask = reinterpret_cast<const void *const *>(extra_dev + at.mask); pc.ct = reinterpret_cast<void *const *>(extra_dev + at.ct);
+    pc.rows = no_rows ? nullptr : reinterpret_cast<const uint64_t *>(extra_dev + at.rows);
+    pc.u = u_dev; pc.sum = sum_out_dev; pc.n = n_elems; pc.n_values = n_values; pc.n_clients = n_clients; pc.field_bits = field_bits; pc.bs = no_rows ? 0 : static_cast<int>(bs);
+    if (plans) draws.plans = extra_dev + at.plans;
+    if (grouped) draws.groups = reinterpret_cast<const uint64_t *>(extra_dev + at.groups);
+    HIP_TRY(ctx, launch_prep_cohort(ctx->env, pc, draws, f.elem_bytes));
     return FLASHE_OK;
 }
+
+// What a kind of generator brings to the forms that draw inside the launch: its C segment and how it is read and checked
+// (flashe_draw::read_segments; own_segment: its words for the kind's own refusal of a segment), its plans (own_plans: its words for the
+// kind's own refusal of the table as a whole, none: it has no such status), and how a segment is advanced and handed back.
+struct PhiloxKind {
+    using CSegment = flashe_philox_segment; using Segment = flashe_philox::Segment; using Plan = flashe_philox::ClientPlan;
+    static constexpr PrepDraws::Kind kind = PrepDraws::kPhilox;
+    static constexpr const char *own_segment = "a buffer_pos above 4", *own_plans = nullptr;
+    static constexpr auto from_c = flashe_philox::from_c<CSegment>;
+    static constexpr flashe_draw::SegmentsStatus (*check_segments)(const Segment *, int, int) = flashe_philox::check_segments;
+    static auto cohort_plans(const Segment *segs, int n_segs, uint64_t C, uint64_t n, std::vector<Plan> &plans, flashe_pcg64::Variant *)
+    { return flashe_philox::cohort_plans(segs, n_segs, C, n, plans); }
+    static void advance(CSegment &c, const Segment &) { flashe_philox::advance(c.key, c.counter, c.buffer_pos, c.buffer, c.n); }
+};
+struct Pcg64Kind {
+    using CSegment = flashe_pcg64_segment; using Segment = flashe_pcg64::Segment; using Plan = flashe_pcg64::ClientPlan;
+    static constexpr PrepDraws::Kind kind = PrepDraws::kPcg64;
+    static constexpr const char *own_segment = "a variant that is neither PCG64 (0) nor PCG64DXSM (1)",
+                                *own_plans = "PCG64 and PCG64DXSM segments in one table: a launch has one variant";
+    static constexpr auto from_c = flashe_pcg64::from_c<CSegment>;
+    static constexpr flashe_draw::SegmentsStatus (*check_segments)(const Segment *, int, int) = flashe_pcg64::check_segments;
+    static auto cohort_plans(const Segment *segs, int n_segs, uint64_t C, uint64_t n, std::vector<Plan> &plans, flashe_pcg64::Variant *v)
+    { return flashe_pcg64::cohort_plans(segs, n_segs, C, n, plans, v); }
+    static void advance(CSegment &c, const Segment &s)
+    {
+        const flashe_pcg64::u128 a = flashe_pcg64::advance(static_cast<flashe_pcg64::Variant>(s.variant), s.state, s.inc, s.n);
+        c.state[0] = flashe_pcg64::lo64(a); c.state[1] = flashe_pcg64::hi64(a);
+    }
+};
+
+// The forms with the draws of the caller's generators generated inside the launch: the segment table's own refusals come first (those of
+// the kind's flashe_*_random_dev, without a draw buffer), then the tiling of the clients' stretches, then quantize_combine_cohort's; one
+// advance per segment on the host, after the launch has been made.  The segments tile the clients' n_values VALUES, batched or not.
+extern "C++" template <class K>
+static int quantize_combine_cohort_drawn(flashe_ctx *ctx, const PrepForm &f, int n_clients, uint64_t n_values, uint64_t n_elems_arg, const flashe_tensor_layer *layers,
+                                         int n_layers, const void *const *src_dev, const int32_t *src_dtype, int element_bits, int field_bits,
+                                         typename K::CSegment *segments, int n_segments, const void *const *mask_dev, void *const *ct_dev, void *sum_out_dev)
+{
+    if (n_clients < 1) return fail(ctx, FLASHE_EINVAL, "%s: n_clients must be >= 1", f.who);
+    std::vector<typename K::Segment> segs;
+    if (int rc = flashe_draw::read_segments(ctx, f.who, segments, n_segments, nullptr, K::from_c, K::check_segments, K::own_segment, segs, false)) return rc;
+    std::vector<typename K::Plan> plans;
+    flashe_pcg64::Variant variant = flashe_pcg64::kPcg64;
+    switch (K::cohort_plans(segs.data(), n_segments, static_cast<uint64_t>(n_clients), n_values, plans, &variant)) {
+    case flashe_draw::kCohortPlansOk: break;
+    case flashe_draw::kCohortPlansSplitClient: return fail(ctx, FLASHE_EINVAL, "%s: a client's n draws must come from one segment", f.who);
+    case flashe_draw::kCohortPlansTooMany: return fail(ctx, FLASHE_EINVAL, "%s: n_clients x n draws overflow", f.who);
+    case flashe_draw::kCohortPlansOwn:
+        if (K::own_plans) return fail(ctx, FLASHE_EINVAL, "%s: %s", f.who, K::own_plans);
+        [[fallthrough]];
+    default: return fail(ctx, FLASHE_EINVAL, "%s: the segments must tile the draws [0, n_clients x n) exactly", f.who);
+    }
+    const DrawPlans rows{K::kind, plans.data(), plans.size(), sizeof(typename K::Plan), variant};
+    if (int rc = quantize_combine_cohort(ctx, f, n_clients, n_values, n_elems_arg, layers, n_layers, src_dev, src_dtype, element_bits, field_bits, nullptr, mask_dev,
+                                         ct_dev, sum_out_dev, &rows))
+        return rc;
+    for (int s = 0; n_values && s < n_segments; s++) K::advance(segments[s], segs[s]);
+    return FLASHE_OK;
+}
+
+// the vectors' element: a two-limb or a one-limb element of the ctx's layout; the _u32 forms': 4 bytes
+static int prep_elem_bytes(const flashe_ctx *ctx) { return ctx->limbs == 2 ? 16 : 8; }
+static const void *const *prep_in(const void *p) { return static_cast<const void *const *>(p); }
+static void *const *prep_out(const void *p) { return static_cast<void *const *>(const_cast<void *>(p)); }
 
 int flashe_quantize_combine_cohort_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
                                        const int32_t *src_dtype, int element_bits, const double *u_dev, const uint64_t *const *mask_dev,
                                        uint64_t *const *ct_dev, uint64_t *sum_out_dev)
 {
     CHECK_CTX(ctx);
-    return quantize_combine_cohort(ctx, "flashe_quantize_combine_cohort_dev", ctx->limbs == 2 ? 16 : 8, n_clients, n, n, nullptr, layers, n_layers, src_dev, src_dtype,
-                                   element_bits, 0, u_dev, reinterpret_cast<const void *const *>(mask_dev), reinterpret_cast<void *const *>(ct_dev), sum_out_dev);
+    return quantize_combine_cohort(ctx, {"flashe_quantize_combine_cohort_dev", prep_elem_bytes(ctx), false}, n_clients, n, n, layers, n_layers, src_dev, src_dtype,
+                                   element_bits, 0, u_dev, prep_in(mask_dev), prep_out(ct_dev), sum_out_dev);
 }
 
 // the same in the compact layout at int_bits <= 32 (any such width: there is no AES here): uint32 masks, ciphertexts and sum
@@ -1047,47 +1097,28 @@ int flashe_quantize_combine_cohort_u32_dev(flashe_ctx *ctx, int n_clients, uint6
 {
     CHECK_CTX(ctx);
     if (ctx->int_bits > 32) return fail(ctx, FLASHE_EINVAL, "the uint32 layout needs int_bits <= 32, this ctx has %d", ctx->int_bits);
-    return quantize_combine_cohort(ctx, "flashe_quantize_combine_cohort_u32_dev", 4, n_clients, n, n, nullptr, layers, n_layers, src_dev, src_dtype, element_bits, 0,
-                                   u_dev, reinterpret_cast<const void *const *>(mask_dev), reinterpret_cast<void *const *>(ct_dev), sum_out_dev);
+    return quantize_combine_cohort(ctx, {"flashe_quantize_combine_cohort_u32_dev", 4, false}, n_clients, n, n, layers, n_layers, src_dev, src_dtype, element_bits, 0,
+                                   u_dev, prep_in(mask_dev), prep_out(ct_dev), sum_out_dev);
 }
 
-// The un-batched launch with the draws of Philox streams generated inside it.  The segment table's own refusals come first
-// (flashe_philox_random_dev's, without a draw buffer), then the tiling of the clients' stretches, then quantize_combine_cohort's; the
-// segments are advanced only after the launch has been made.
-// n_elems_arg (the batched job): n counts the clients' VALUES, which is what the segments tile.
-static int quantize_combine_cohort_philox(flashe_ctx *ctx, const char *who, int elem_bytes, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers,
-                                          const void *const *src_dev, const int32_t *src_dtype, int element_bits, flashe_philox_segment *segments, int n_segments,
-                                          const void *const *mask_dev, void *const *ct_dev, void *sum_out_dev, const uint64_t *n_elems_arg = nullptr, int field_bits = 0)
+// the BATCHED job over its n_elems elements (any bs = int_bits / field_bits >= 1)
+int flashe_quantize_batch_combine_cohort_dev(flashe_ctx *ctx, int n_clients, uint64_t n_values, uint64_t n_elems, const flashe_tensor_layer *layers, int n_layers,
+                                             const void *const *src_dev, const int32_t *src_dtype, int element_bits, int field_bits, const double *u_dev,
+                                             const uint64_t *const *mask_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev)
 {
-    if (n_clients < 1) return fail(ctx, FLASHE_EINVAL, "%s: n_clients must be >= 1", who);
-    std::vector<flashe_philox::Segment> segs;
-    if (int rc = flashe_draw::read_segments(ctx, who, segments, n_segments, nullptr, flashe_philox::from_c<flashe_philox_segment>, flashe_philox::check_segments,
-                                            "a buffer_pos above 4", segs, false))
-        return rc;
-    std::vector<flashe_philox::ClientPlan> plans;
-    switch (flashe_philox::cohort_plans(segs.data(), n_segments, static_cast<uint64_t>(n_clients), n, plans)) {
-    case flashe_philox::kCohortPlansOk: break;
-    case flashe_philox::kCohortPlansSplitClient: return fail(ctx, FLASHE_EINVAL, "%s: a client's n draws must come from one segment", who);
-    case flashe_philox::kCohortPlansTooMany: return fail(ctx, FLASHE_EINVAL, "%s: n_clients x n draws overflow", who);
-    default: return fail(ctx, FLASHE_EINVAL, "%s: the segments must tile the draws [0, n_clients x n) exactly", who);
-    }
-    const DrawPlans rows(plans);
-    if (int rc = quantize_combine_cohort(ctx, who, elem_bytes, n_clients, n, n_elems_arg ? 0 : n, n_elems_arg, layers, n_layers, src_dev, src_dtype, element_bits,
-                                         field_bits, nullptr, mask_dev, ct_dev, sum_out_dev, &rows))
-        return rc;
-    for (int s = 0; n && s < n_segments; s++)
-        flashe_philox::advance(segments[s].key, segments[s].counter, segments[s].buffer_pos, segments[s].buffer, segments[s].n);
-    return FLASHE_OK;
+    CHECK_CTX(ctx);
+    return quantize_combine_cohort(ctx, {"flashe_quantize_batch_combine_cohort_dev", prep_elem_bytes(ctx), true}, n_clients, n_values, n_elems, layers, n_layers,
+                                   src_dev, src_dtype, element_bits, field_bits, u_dev, prep_in(mask_dev), prep_out(ct_dev), sum_out_dev);
 }
 
+// the draws of np.random.Philox streams generated inside the launch
 int flashe_quantize_combine_cohort_philox_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
                                               const int32_t *src_dtype, int element_bits, flashe_philox_segment *segments, int n_segments,
                                               const uint64_t *const *mask_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev)
 {
     CHECK_CTX(ctx);
-    return quantize_combine_cohort_philox(ctx, "flashe_quantize_combine_cohort_philox_dev", ctx->limbs == 2 ? 16 : 8, n_clients, n, layers, n_layers, src_dev, src_dtype,
-                                          element_bits, segments, n_segments, reinterpret_cast<const void *const *>(mask_dev), reinterpret_cast<void *const *>(ct_dev),
-                                          sum_out_dev);
+    return quantize_combine_cohort_drawn<PhiloxKind>(ctx, {"flashe_quantize_combine_cohort_philox_dev", prep_elem_bytes(ctx), false}, n_clients, n, n, layers, n_layers,
+                                                     src_dev, src_dtype, element_bits, 0, segments, n_segments, prep_in(mask_dev), prep_out(ct_dev), sum_out_dev);
 }
 
 int flashe_quantize_combine_cohort_philox_u32_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers,
@@ -1096,50 +1127,30 @@ int flashe_quantize_combine_cohort_philox_u32_dev(flashe_ctx *ctx, int n_clients
 {
     CHECK_CTX(ctx);
     if (ctx->int_bits > 32) return fail(ctx, FLASHE_EINVAL, "the uint32 layout needs int_bits <= 32, this ctx has %d", ctx->int_bits);
-    return quantize_combine_cohort_philox(ctx, "flashe_quantize_combine_cohort_philox_u32_dev", 4, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits,
-                                          segments, n_segments, reinterpret_cast<const void *const *>(mask_dev), reinterpret_cast<void *const *>(ct_dev), sum_out_dev);
+    return quantize_combine_cohort_drawn<PhiloxKind>(ctx, {"flashe_quantize_combine_cohort_philox_u32_dev", 4, false}, n_clients, n, n, layers, n_layers, src_dev,
+                                                     src_dtype, element_bits, 0, segments, n_segments, prep_in(mask_dev), prep_out(ct_dev), sum_out_dev);
 }
 
-// The un-batched launch with the draws of PCG64 / PCG64DXSM streams generated inside it: the order of refusals and the hand-back are the
-// Philox form's -- flashe_pcg64_random_dev's segment checks (without a draw buffer), the tiling, the split client and a table of both
-// variants, then quantize_combine_cohort's; one advance per segment on the host, after the launch has been made.
-static int quantize_combine_cohort_pcg64(flashe_ctx *ctx, const char *who, int elem_bytes, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers,
-                                         const void *const *src_dev, const int32_t *src_dtype, int element_bits, flashe_pcg64_segment *segments, int n_segments,
-                                         const void *const *mask_dev, void *const *ct_dev, void *sum_out_dev)
+// the BATCHED job with the draws generated inside the launch: the segments tile the clients' n_values values
+int flashe_quantize_batch_combine_cohort_philox_dev(flashe_ctx *ctx, int n_clients, uint64_t n_values, uint64_t n_elems, const flashe_tensor_layer *layers, int n_layers,
+                                                    const void *const *src_dev, const int32_t *src_dtype, int element_bits, int field_bits,
+                                                    flashe_philox_segment *segments, int n_segments, const uint64_t *const *mask_dev, uint64_t *const *ct_dev,
+                                                    uint64_t *sum_out_dev)
 {
-    if (n_clients < 1) return fail(ctx, FLASHE_EINVAL, "%s: n_clients must be >= 1", who);
-    std::vector<flashe_pcg64::Segment> segs;
-    if (int rc = flashe_draw::read_segments(ctx, who, segments, n_segments, nullptr, flashe_pcg64::from_c<flashe_pcg64_segment>, flashe_pcg64::check_segments,
-                                            "a variant that is neither PCG64 (0) nor PCG64DXSM (1)", segs, false))
-        return rc;
-    std::vector<flashe_pcg64::ClientPlan> plans;
-    flashe_pcg64::Variant variant = flashe_pcg64::kPcg64;
-    switch (flashe_pcg64::cohort_plans(segs.data(), n_segments, static_cast<uint64_t>(n_clients), n, plans, &variant)) {
-    case flashe_pcg64::kCohortPlansOk: break;
-    case flashe_pcg64::kCohortPlansSplitClient: return fail(ctx, FLASHE_EINVAL, "%s: a client's n draws must come from one segment", who);
-    case flashe_pcg64::kCohortPlansTooMany: return fail(ctx, FLASHE_EINVAL, "%s: n_clients x n draws overflow", who);
-    case flashe_pcg64::kCohortPlansMixedVariants: return fail(ctx, FLASHE_EINVAL, "%s: PCG64 and PCG64DXSM segments in one table: a launch has one variant", who);
-    default: return fail(ctx, FLASHE_EINVAL, "%s: the segments must tile the draws [0, n_clients x n) exactly", who);
-    }
-    const DrawPlans rows(plans, variant);
-    if (int rc = quantize_combine_cohort(ctx, who, elem_bytes, n_clients, n, n, nullptr, layers, n_layers, src_dev, src_dtype, element_bits, 0, nullptr, mask_dev, ct_dev,
-                                         sum_out_dev, &rows))
-        return rc;
-    for (int s = 0; n && s < n_segments; s++) {
-        const flashe_pcg64::u128 a = flashe_pcg64::advance(static_cast<flashe_pcg64::Variant>(segs[s].variant), segs[s].state, segs[s].inc, segs[s].n);
-        segments[s].state[0] = flashe_pcg64::lo64(a); segments[s].state[1] = flashe_pcg64::hi64(a);
-    }
-    return FLASHE_OK;
+    CHECK_CTX(ctx);
+    return quantize_combine_cohort_drawn<PhiloxKind>(ctx, {"flashe_quantize_batch_combine_cohort_philox_dev", prep_elem_bytes(ctx), true}, n_clients, n_values, n_elems,
+                                                     layers, n_layers, src_dev, src_dtype, element_bits, field_bits, segments, n_segments, prep_in(mask_dev),
+                                                     prep_out(ct_dev), sum_out_dev);
 }
 
+// the draws of np.random.PCG64 / PCG64DXSM streams generated inside the launch (un-batched only)
 int flashe_quantize_combine_cohort_pcg64_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev,
                                              const int32_t *src_dtype, int element_bits, flashe_pcg64_segment *segments, int n_segments,
                                              const uint64_t *const *mask_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev)
 {
     CHECK_CTX(ctx);
-    return quantize_combine_cohort_pcg64(ctx, "flashe_quantize_combine_cohort_pcg64_dev", ctx->limbs == 2 ? 16 : 8, n_clients, n, layers, n_layers, src_dev, src_dtype,
-                                         element_bits, segments, n_segments, reinterpret_cast<const void *const *>(mask_dev), reinterpret_cast<void *const *>(ct_dev),
-                                         sum_out_dev);
+    return quantize_combine_cohort_drawn<Pcg64Kind>(ctx, {"flashe_quantize_combine_cohort_pcg64_dev", prep_elem_bytes(ctx), false}, n_clients, n, n, layers, n_layers,
+                                                    src_dev, src_dtype, element_bits, 0, segments, n_segments, prep_in(mask_dev), prep_out(ct_dev), sum_out_dev);
 }
 
 int flashe_quantize_combine_cohort_pcg64_u32_dev(flashe_ctx *ctx, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers,
@@ -1148,8 +1159,8 @@ int flashe_quantize_combine_cohort_pcg64_u32_dev(flashe_ctx *ctx, int n_clients,
 {
     CHECK_CTX(ctx);
     if (ctx->int_bits > 32) return fail(ctx, FLASHE_EINVAL, "the uint32 layout needs int_bits <= 32, this ctx has %d", ctx->int_bits);
-    return quantize_combine_cohort_pcg64(ctx, "flashe_quantize_combine_cohort_pcg64_u32_dev", 4, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits,
-                                         segments, n_segments, reinterpret_cast<const void *const *>(mask_dev), reinterpret_cast<void *const *>(ct_dev), sum_out_dev);
+    return quantize_combine_cohort_drawn<Pcg64Kind>(ctx, {"flashe_quantize_combine_cohort_pcg64_u32_dev", 4, false}, n_clients, n, n, layers, n_layers, src_dev,
+                                                    src_dtype, element_bits, 0, segments, n_segments, prep_in(mask_dev), prep_out(ct_dev), sum_out_dev);
 }
 
 // host only: the grid of that launch for n values, and one lane's draws through the header functions its kernel compiles
@@ -1173,29 +1184,6 @@ int flashe_pcg64_cohort_lane_draws(uint32_t variant, const uint64_t state[2], co
     if (variant == kPcg64) lane_draws<kPcg64>(pow2[0], runs[0], plan, workgroups, run, iterations, out);
     else lane_draws<kDxsm>(pow2[1], runs[1], plan, workgroups, run, iterations, out);
     return FLASHE_OK;
-}
-
-// the BATCHED job with the draws generated inside the launch: the segments tile the clients' n_values values
-int flashe_quantize_batch_combine_cohort_philox_dev(flashe_ctx *ctx, int n_clients, uint64_t n_values, uint64_t n_elems, const flashe_tensor_layer *layers, int n_layers,
-                                                    const void *const *src_dev, const int32_t *src_dtype, int element_bits, int field_bits,
-                                                    flashe_philox_segment *segments, int n_segments, const uint64_t *const *mask_dev, uint64_t *const *ct_dev,
-                                                    uint64_t *sum_out_dev)
-{
-    CHECK_CTX(ctx);
-    return quantize_combine_cohort_philox(ctx, "flashe_quantize_batch_combine_cohort_philox_dev", ctx->limbs == 2 ? 16 : 8, n_clients, n_values, layers, n_layers, src_dev,
-                                          src_dtype, element_bits, segments, n_segments, reinterpret_cast<const void *const *>(mask_dev),
-                                          reinterpret_cast<void *const *>(ct_dev), sum_out_dev, &n_elems, field_bits);
-}
-
-// the BATCHED job over its n_elems elements (any bs = int_bits / field_bits >= 1)
-int flashe_quantize_batch_combine_cohort_dev(flashe_ctx *ctx, int n_clients, uint64_t n_values, uint64_t n_elems, const flashe_tensor_layer *layers, int n_layers,
-                                             const void *const *src_dev, const int32_t *src_dtype, int element_bits, int field_bits, const double *u_dev,
-                                             const uint64_t *const *mask_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev)
-{
-    CHECK_CTX(ctx);
-    return quantize_combine_cohort(ctx, "flashe_quantize_batch_combine_cohort_dev", ctx->limbs == 2 ? 16 : 8, n_clients, n_values, 0, &n_elems, layers, n_layers, src_dev,
-                                   src_dtype, element_bits, field_bits, u_dev, reinterpret_cast<const void *const *>(mask_dev), reinterpret_cast<void *const *>(ct_dev),
-                                   sum_out_dev);
 }
 
 int flashe_combine_unquantize_model_dev(flashe_ctx *ctx, uint64_t n, const uint64_t *in_dev, const uint64_t *add_dev, const uint64_t *minus_dev,

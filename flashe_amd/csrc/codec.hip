@@ -3,6 +3,8 @@
 #include "pcg64_stream.h"
 #include "philox_stream.h"
 
+#include <type_traits>
+
 namespace flashe {
 
 // ------------------------------------------------------------------------------------------
@@ -898,111 +900,89 @@ __global__ __launch_bounds__(kStreamThreads) void quantize_batch_philox_combine_
     }
 }
 
-template <class E> static hipError_t launch_prep_cohort(const LaunchEnv &env, const PrepCohort &pc, bool batched, int group, E modmask)
-{
-    const dim3 g(stream_grid(env, batched ? pc.n : (pc.n + 3) / 4)), t(kStreamThreads);
-#define FLASHE_PREP_LAUNCH(G)                                                                                                                  \
-    do {                                                                                                                                       \
-        if (!batched) hipLaunchKernelGGL((quantize_combine_cohort_kernel<E, G>), g, t, 0, env.stream, pc, modmask);                             \
-        else if constexpr (sizeof(E) == 4) return hipErrorInvalidValue;                                                                        \
-        else if (pc.bs == 5) hipLaunchKernelGGL((quantize_batch_combine_cohort_kernel<E, G, 5>), g, t, 0, env.stream, pc, modmask);            \
-        else if (pc.bs == 6) hipLaunchKernelGGL((quantize_batch_combine_cohort_kernel<E, G, 6>), g, t, 0, env.stream, pc, modmask);            \
-        else if (pc.bs == 7) hipLaunchKernelGGL((quantize_batch_combine_cohort_kernel<E, G, 7>), g, t, 0, env.stream, pc, modmask);            \
-        else hipLaunchKernelGGL((quantize_batch_combine_cohort_kernel<E, G, 0>), g, t, 0, env.stream, pc, modmask);                            \
-    } while (0)
-#ifdef FLASHE_TUNING
-    if (group == 1) FLASHE_PREP_LAUNCH(1);           // (the alternatives of the A/B ride in the tuning build only)
-    else if (group == 4) FLASHE_PREP_LAUNCH(4);
-    else
-#endif
-    FLASHE_PREP_LAUNCH(kPrepCohortGroup);
-#undef FLASHE_PREP_LAUNCH
-    return hipGetLastError();
-}
-
-hipError_t launch_quantize_combine_cohort(const LaunchEnv &env, const PrepCohort &pc, int elem_bytes, bool batched)
-{
-    if (pc.n == 0 || pc.n_clients == 0) return hipSuccess;
-    if (pc.n_layers < 1 || (batched && (pc.bs < 1 || pc.field_bits < 1 || pc.field_bits > env.b))) return hipErrorInvalidValue;
-    int group = kPrepCohortGroup;
-    if (const char *e = FLASHE_TUNE_ENV("FLASHE_PREP_COHORT_GROUP")) group = atoi(e);      // (read per call: an in-process A/B alternates it)
-    uint64_t lo, hi;
-    masks_of(env.b, &lo, &hi);
-    if (elem_bytes == 4) return env.b > 32 ? hipErrorInvalidValue : launch_prep_cohort<uint32_t>(env, pc, batched, group, static_cast<uint32_t>(lo));
-    if (elem_bytes == 8) return env.b > 64 ? hipErrorInvalidValue : launch_prep_cohort<uint64_t>(env, pc, batched, group, lo);
-    if (elem_bytes == 16) return env.b <= 64 ? hipErrorInvalidValue : launch_prep_cohort<u128>(env, pc, batched, group, (static_cast<u128>(hi) << 64) | lo);
-    return hipErrorInvalidValue;
-}
-
-// ---- the un-batched launch with the draws generated inside it (quantize_philox_combine_cohort_kernel above) ----
-template <class E> static hipError_t launch_prep_philox(const LaunchEnv &env, const PrepCohort &pc, const ClientPlan *plans, E modmask)
-{
-    const dim3 g(stream_grid(env, (pc.n + 3) / 4)), t(kStreamThreads);
-    hipLaunchKernelGGL((quantize_philox_combine_cohort_kernel<E, kPrepCohortGroup>), g, t, 0, env.stream, pc, plans, modmask);
-    return hipGetLastError();
-}
-
-hipError_t launch_quantize_philox_combine_cohort(const LaunchEnv &env, const PrepCohort &pc, const ClientPlan *plans, int elem_bytes)
-{
-    if (pc.n == 0 || pc.n_clients == 0) return hipSuccess;
-    if (pc.n_layers < 1 || !plans) return hipErrorInvalidValue;
-    uint64_t lo, hi;
-    masks_of(env.b, &lo, &hi);
-    if (elem_bytes == 4) return env.b > 32 ? hipErrorInvalidValue : launch_prep_philox<uint32_t>(env, pc, plans, static_cast<uint32_t>(lo));
-    if (elem_bytes == 8) return env.b > 64 ? hipErrorInvalidValue : launch_prep_philox<uint64_t>(env, pc, plans, lo);
-    if (elem_bytes == 16) return env.b <= 64 ? hipErrorInvalidValue : launch_prep_philox<u128>(env, pc, plans, (static_cast<u128>(hi) << 64) | lo);
-    return hipErrorInvalidValue;
-}
-
-// ---- the un-batched launch with PCG64 / PCG64DXSM draws generated inside it (quantize_pcg64_combine_cohort_kernel above) ----
+// ---- the one launcher of the kernels above (kernels.h: PrepDraws says where the draws come from) ----
 int prep_pcg64_grid(const LaunchEnv &env, uint64_t n) { return stream_grid(env, (n + 3) / 4); }
 
-template <class E> static hipError_t launch_prep_pcg64(const LaunchEnv &env, const PrepCohort &pc, const flashe_pcg64::ClientPlan *plans, uint32_t variant, E modmask)
+// f(modmask): the vectors' element type -- uint32_t, uint64_t or u128, by elem_bytes and the ctx's int_bits -- and its mask of env.b bits
+template <class F> static hipError_t prep_with_elem(const LaunchEnv &env, int elem_bytes, F &&f)
 {
-    const int workgroups = prep_pcg64_grid(env, pc.n);
-    const dim3 g(workgroups), t(kStreamThreads);
-    const flashe_pcg64::Row stride = flashe_pcg64::to_row(flashe_pcg64::stride_jump(static_cast<flashe_pcg64::Variant>(variant), static_cast<uint64_t>(workgroups)));
-    if (variant == flashe_pcg64::kPcg64)
-        hipLaunchKernelGGL((quantize_pcg64_combine_cohort_kernel<E, kPrepCohortGroup, flashe_pcg64::kPcg64>), g, t, 0, env.stream, pc, plans, stride, modmask);
-    else
-        hipLaunchKernelGGL((quantize_pcg64_combine_cohort_kernel<E, kPrepCohortGroup, flashe_pcg64::kDxsm>), g, t, 0, env.stream, pc, plans, stride, modmask);
-    return hipGetLastError();
-}
-
-hipError_t launch_quantize_pcg64_combine_cohort(const LaunchEnv &env, const PrepCohort &pc, const flashe_pcg64::ClientPlan *plans, uint32_t variant, int elem_bytes)
-{
-    if (pc.n == 0 || pc.n_clients == 0) return hipSuccess;
-    if (pc.n_layers < 1 || !plans || variant >= flashe_pcg64::kVariants) return hipErrorInvalidValue;
     uint64_t lo, hi;
     masks_of(env.b, &lo, &hi);
-    if (elem_bytes == 4) return env.b > 32 ? hipErrorInvalidValue : launch_prep_pcg64<uint32_t>(env, pc, plans, variant, static_cast<uint32_t>(lo));
-    if (elem_bytes == 8) return env.b > 64 ? hipErrorInvalidValue : launch_prep_pcg64<uint64_t>(env, pc, plans, variant, lo);
-    if (elem_bytes == 16) return env.b <= 64 ? hipErrorInvalidValue : launch_prep_pcg64<u128>(env, pc, plans, variant, (static_cast<u128>(hi) << 64) | lo);
+    if (elem_bytes == 4) return env.b > 32 ? hipErrorInvalidValue : f(static_cast<uint32_t>(lo));
+    if (elem_bytes == 8) return env.b > 64 ? hipErrorInvalidValue : f(lo);
+    if (elem_bytes == 16) return env.b <= 64 ? hipErrorInvalidValue : f((static_cast<u128>(hi) << 64) | lo);
     return hipErrorInvalidValue;
 }
 
-// ---- the batched launch with the draws generated inside it (quantize_batch_philox_combine_cohort_kernel above) ----
-template <class E>
-static hipError_t launch_prep_batch_philox(const LaunchEnv &env, const PrepCohort &pc, const ClientPlan *plans, const uint64_t *groups, uint64_t n_groups, E modmask)
+// f(BS): the batched kernels' compiled-in values per element, 5 / 6 / 7, or 0 for any other bs (read from pc.bs)
+template <class F> static void prep_with_bs(int bs, F &&f)
 {
-    const dim3 g(stream_grid(env, n_groups)), t(kStreamThreads);
-    if (pc.bs == 5) hipLaunchKernelGGL((quantize_batch_philox_combine_cohort_kernel<E, 5>), g, t, 0, env.stream, pc, plans, groups, n_groups, modmask);
-    else if (pc.bs == 6) hipLaunchKernelGGL((quantize_batch_philox_combine_cohort_kernel<E, 6>), g, t, 0, env.stream, pc, plans, groups, n_groups, modmask);
-    else if (pc.bs == 7) hipLaunchKernelGGL((quantize_batch_philox_combine_cohort_kernel<E, 7>), g, t, 0, env.stream, pc, plans, groups, n_groups, modmask);
-    else hipLaunchKernelGGL((quantize_batch_philox_combine_cohort_kernel<E, 0>), g, t, 0, env.stream, pc, plans, groups, n_groups, modmask);
+    if (bs == 5) f(std::integral_constant<int, 5>{});
+    else if (bs == 6) f(std::integral_constant<int, 6>{});
+    else if (bs == 7) f(std::integral_constant<int, 7>{});
+    else f(std::integral_constant<int, 0>{});
+}
+
+// the buffer form with G clients per group (there is no batched job on uint32 vectors)
+template <class E, int G> static hipError_t prep_launch_buffer(const LaunchEnv &env, const PrepCohort &pc, bool batched, E modmask)
+{
+    const dim3 g(stream_grid(env, batched ? pc.n : (pc.n + 3) / 4)), t(kStreamThreads);
+    if (!batched) hipLaunchKernelGGL((quantize_combine_cohort_kernel<E, G>), g, t, 0, env.stream, pc, modmask);
+    else if constexpr (sizeof(E) == 4) return hipErrorInvalidValue;
+    else prep_with_bs(pc.bs, [&](auto bs) { hipLaunchKernelGGL((quantize_batch_combine_cohort_kernel<E, G, decltype(bs)::value>), g, t, 0, env.stream, pc, modmask); });
     return hipGetLastError();
 }
 
-hipError_t launch_quantize_batch_philox_combine_cohort(const LaunchEnv &env, const PrepCohort &pc, const ClientPlan *plans, const uint64_t *groups, uint64_t n_groups,
-                                                       int elem_bytes)
+hipError_t launch_prep_cohort(const LaunchEnv &env, const PrepCohort &pc, const PrepDraws &draws, int elem_bytes)
 {
-    if (pc.n == 0 || pc.n_clients == 0 || n_groups == 0) return hipSuccess;
-    if (pc.n_layers < 1 || !plans || !groups || pc.bs < 1 || pc.field_bits < 1 || pc.field_bits > env.b) return hipErrorInvalidValue;
-    uint64_t lo, hi;
-    masks_of(env.b, &lo, &hi);
-    if (elem_bytes == 8) return env.b > 64 ? hipErrorInvalidValue : launch_prep_batch_philox<uint64_t>(env, pc, plans, groups, n_groups, lo);
-    if (elem_bytes == 16) return env.b <= 64 ? hipErrorInvalidValue : launch_prep_batch_philox<u128>(env, pc, plans, groups, n_groups, (static_cast<u128>(hi) << 64) | lo);
-    return hipErrorInvalidValue;
+    const bool drawn = draws.kind != PrepDraws::kBuffer, grouped = drawn && draws.batched;       // grouped: a lane owns a group of four elements
+    if (pc.n == 0 || pc.n_clients == 0 || (grouped && draws.n_groups == 0)) return hipSuccess;
+    if (pc.n_layers < 1 || (drawn && !draws.plans) || (grouped && !draws.groups)) return hipErrorInvalidValue;
+    if (draws.batched && (elem_bytes == 4 || draws.kind == PrepDraws::kPcg64 || pc.bs < 1 || pc.field_bits < 1 || pc.field_bits > env.b)) return hipErrorInvalidValue;
+    const dim3 t(kStreamThreads);
+    if (!drawn) {
+        int group = kPrepCohortGroup;
+        if (const char *e = FLASHE_TUNE_ENV("FLASHE_PREP_COHORT_GROUP")) group = atoi(e);      // (read per call: an in-process A/B alternates it)
+        return prep_with_elem(env, elem_bytes, [&](auto modmask) {
+            using E = decltype(modmask);
+#ifdef FLASHE_TUNING
+            if (group == 1) return prep_launch_buffer<E, 1>(env, pc, draws.batched, modmask);      // (the alternatives of the A/B ride in the tuning build only)
+            if (group == 4) return prep_launch_buffer<E, 4>(env, pc, draws.batched, modmask);
+#endif
+            (void)group;
+            return prep_launch_buffer<E, kPrepCohortGroup>(env, pc, draws.batched, modmask);
+        });
+    }
+    if (draws.kind == PrepDraws::kPhilox && !draws.batched)
+        return prep_with_elem(env, elem_bytes, [&](auto modmask) {
+            hipLaunchKernelGGL((quantize_philox_combine_cohort_kernel<decltype(modmask), kPrepCohortGroup>), dim3(stream_grid(env, (pc.n + 3) / 4)), t, 0, env.stream, pc,
+                               static_cast<const ClientPlan *>(draws.plans), modmask);
+            return hipGetLastError();
+        });
+    if (draws.kind == PrepDraws::kPcg64) {
+        if (draws.variant >= flashe_pcg64::kVariants) return hipErrorInvalidValue;
+        const flashe_pcg64::ClientPlan *plans = static_cast<const flashe_pcg64::ClientPlan *>(draws.plans);
+        const int workgroups = prep_pcg64_grid(env, pc.n);
+        const flashe_pcg64::Row stride = flashe_pcg64::to_row(flashe_pcg64::stride_jump(static_cast<flashe_pcg64::Variant>(draws.variant), static_cast<uint64_t>(workgroups)));
+        return prep_with_elem(env, elem_bytes, [&](auto modmask) {
+            using E = decltype(modmask);
+            if (draws.variant == flashe_pcg64::kPcg64)
+                hipLaunchKernelGGL((quantize_pcg64_combine_cohort_kernel<E, kPrepCohortGroup, flashe_pcg64::kPcg64>), dim3(workgroups), t, 0, env.stream, pc, plans, stride, modmask);
+            else
+                hipLaunchKernelGGL((quantize_pcg64_combine_cohort_kernel<E, kPrepCohortGroup, flashe_pcg64::kDxsm>), dim3(workgroups), t, 0, env.stream, pc, plans, stride, modmask);
+            return hipGetLastError();
+        });
+    }
+    // the batched job drawing its Philox streams
+    return prep_with_elem(env, elem_bytes, [&](auto modmask) {
+        using E = decltype(modmask);
+        if constexpr (sizeof(E) != 4)
+            prep_with_bs(pc.bs, [&](auto bs) {
+                hipLaunchKernelGGL((quantize_batch_philox_combine_cohort_kernel<E, decltype(bs)::value>), dim3(stream_grid(env, draws.n_groups)), t, 0, env.stream, pc,
+                                   static_cast<const ClientPlan *>(draws.plans), draws.groups, draws.n_groups, modmask);
+            });
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_batch(const LaunchEnv &env, uint64_t n, const uint64_t *vals_dev, int field_bits, uint64_t *out_dev)

@@ -385,22 +385,21 @@ struct PrepCohort {
     uint64_t n, n_values;
     int n_layers, n_clients, field_bits, bs;
 };
-// elem_bytes = what masks, ciphertexts and sum are made of: 4 (uint32, int_bits <= 32, un-batched), 8 (one limb, int_bits <= 64) or 16
-hipError_t launch_quantize_combine_cohort(const LaunchEnv &env, const PrepCohort &pc, int elem_bytes, bool batched);
-// The un-batched launch with the draws of np.random.Philox streams generated inside it: pc.u is not read; plans = a DEVICE table of one
-// flashe_philox::ClientPlan (philox_stream.h) per client, client c's draw for value k = word (skip + k) % 4 of block(base + (skip + k) / 4).
-hipError_t launch_quantize_philox_combine_cohort(const LaunchEnv &env, const PrepCohort &pc, const flashe_philox::ClientPlan *plans, int elem_bytes);
-// The BATCHED launch with the draws generated inside it: a lane owns a GROUP of four consecutive elements of one row (the row's last group
-// may hold fewer); groups = a DEVICE table of every row's first group, n_groups the launch's groups; client c's draw for its flat value k
-// (the rows' values in walking order, pads draw nothing) = word (skip + k) % 4 of block(base + (skip + k) / 4).  pc.u is not read.
-hipError_t launch_quantize_batch_philox_combine_cohort(const LaunchEnv &env, const PrepCohort &pc, const flashe_philox::ClientPlan *plans, const uint64_t *groups,
-                                                       uint64_t n_groups, int elem_bytes);
-// The un-batched launch with the draws of np.random.PCG64 / PCG64DXSM streams generated inside it: pc.u is not read; plans = a DEVICE table
-// of one flashe_pcg64::ClientPlan (pcg64_stream.h) per client, all of the one variant (0 PCG64, 1 PCG64DXSM); a lane keeps the jump to its
-// run of four values and composes it with the stride jump of the grid, which prep_pcg64_grid gives for n values and the launch computes.
+// Where that launch takes its draws from.  kBuffer: pc.u.  kPhilox / kPcg64: the draws of np.random.Philox / PCG64 / PCG64DXSM streams are
+// generated inside the launch and pc.u is not read; plans = a DEVICE table of one flashe_philox::ClientPlan (philox_stream.h: client c's
+// draw for its flat value k = word (skip + k) % 4 of block(base + (skip + k) / 4); a batched job's pads draw nothing) or one
+// flashe_pcg64::ClientPlan (pcg64_stream.h) per client, those all of the one variant (0 PCG64, 1 PCG64DXSM; never batched): a lane keeps the
+// jump to its run of four values and composes it with the stride jump of the grid, which prep_pcg64_grid gives for n values.  Batched
+// kPhilox: a lane owns a GROUP of four consecutive elements of one row (the row's last group may hold fewer); groups = a DEVICE table of
+// every row's first group, n_groups the launch's groups.
+struct PrepDraws {
+    enum Kind { kBuffer, kPhilox, kPcg64 } kind; bool batched;
+    const void *plans; uint32_t variant;                 // drawn forms; kPcg64
+    const uint64_t *groups; uint64_t n_groups;           // batched kPhilox
+};
 int prep_pcg64_grid(const LaunchEnv &env, uint64_t n);
-hipError_t launch_quantize_pcg64_combine_cohort(const LaunchEnv &env, const PrepCohort &pc, const flashe_pcg64::ClientPlan *plans, uint32_t variant,
-                                                int elem_bytes);
+// elem_bytes = what masks, ciphertexts and sum are made of: 4 (uint32, int_bits <= 32, un-batched), 8 (one limb, int_bits <= 64) or 16
+hipError_t launch_prep_cohort(const LaunchEnv &env, const PrepCohort &pc, const PrepDraws &draws, int elem_bytes);
 hipError_t launch_unbatch(const LaunchEnv &env, uint64_t nb, const uint64_t *in_dev, int field_bits, uint64_t *out_dev);
 
 // Caller-owned tensors either side of the model-wide codec (tensors.hip).  dtype / flags as in flashe_tensor_layer (include/flashe.h);

@@ -77,30 +77,16 @@ struct StageSlots {
 };
 
 // The block the prepared cohort launches upload behind cohort_stage's tables (8-byte words): the n_clients mask pointers, the n_clients
-// ciphertext pointers, then two words per batched row.  Byte offsets inside the block, and its words for n_rows batched rows.
-struct PreparedBlock { size_t mask, ct, rows, words; };
-inline PreparedBlock prepared_block(int n_clients, size_t n_rows = 0)
+// ciphertext pointers, two words per batched row (first element, value count), with_groups: one word per row -- the row's first GROUP of
+// four elements in the launch that draws inside a batched job (a lane owns a group; a row's last group may hold fewer, batched_groups) --
+// then one draw plan of plan_words words per client.  Byte offsets inside the block, and its words; a part that is absent is empty.
+struct PreparedBlock { size_t mask, ct, rows, groups, plans, words; };
+inline PreparedBlock prepared_block(int n_clients, size_t n_rows = 0, size_t plan_words = 0, bool with_groups = false)
 {
-    const size_t c = static_cast<size_t>(n_clients);
-    return PreparedBlock{0, c * 8, 2 * c * 8, 2 * c + 2 * n_rows};
+    const size_t c = static_cast<size_t>(n_clients), groups = 2 * c + 2 * n_rows, plans = groups + (with_groups ? n_rows : 0);
+    return PreparedBlock{0, c * 8, 2 * c * 8, groups * 8, plans * 8, plans + plan_words * c};
 }
-// The block of the prepared cohort launch that generates its own draws (un-batched only): the n_clients mask pointers, the n_clients
-// ciphertext pointers, then one draw plan of plan_words 8-byte words per client.
-struct PreparedDrawsBlock { size_t mask, ct, plans, words; };
-inline PreparedDrawsBlock prepared_draws_block(int n_clients, size_t plan_words)
-{
-    const size_t c = static_cast<size_t>(n_clients);
-    return PreparedDrawsBlock{0, c * 8, 2 * c * 8, 2 * c + plan_words * c};
-}
-// The block of the BATCHED prepared cohort launch that generates its own draws: the pointers, the two words per batched row, then one
-// word per row -- the row's first GROUP of four elements in the launch (a lane owns a group; a row's last group may hold fewer) --
-// then the plans.  rows = the (first element, value count) pairs of n_rows rows; returns the launch's groups.
-struct PreparedBatchDrawsBlock { size_t mask, ct, rows, groups, plans, words; };
-inline PreparedBatchDrawsBlock prepared_batch_draws_block(int n_clients, size_t n_rows, size_t plan_words)
-{
-    const size_t c = static_cast<size_t>(n_clients);
-    return PreparedBatchDrawsBlock{0, c * 8, 2 * c * 8, (2 * c + 2 * n_rows) * 8, (2 * c + 3 * n_rows) * 8, 2 * c + 3 * n_rows + plan_words * c};
-}
+// rows = the (first element, value count) pairs of n_rows rows; first_group[r] = row r's first group; returns the launch's groups
 inline uint64_t batched_groups(const uint64_t *rows, size_t n_rows, uint64_t bs, uint64_t *first_group)
 {
     uint64_t g = 0;

@@ -849,23 +849,35 @@ class Engine:
         elif n and n_clients:
             self.prf_jobs_dev(it, n, n_jobs, [(int(first_idx) + c, int(first_idx) + c + 1, 0, n, None, 0, self._ptr(masks[c])) for c in range(n_clients)])
 
+    def _prepared_cohort_launch(self, name, n, layers, srcs, dtypes, element_bits, draws, masks, cts, sum_out, batch=None):
+        """The library's prepared cohort launch `name` (_lib.PREPARED_COHORT_LAUNCHES; a batch_ form: batch=(n_elems, field_bits)): the
+        shared table, the sources, the mask and the ciphertext pointers marshalled, one call.  draws = the draw buffer, or _draw_table's
+        arguments (kind, generators_or_states, counts, offsets): the generators get their advanced states back only when the call took.
+        False: the library declined."""
+        arr, nl = self._tensor_layers(layers)
+        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
+        pm, _a = self._ptr_array(masks)
+        pc, _b = self._ptr_array(cts)
+        hand_back = None
+        if isinstance(draws, tuple):
+            segs, counts, _offsets, hand_back = _draw_table(*draws)
+            draws = (segs, len(counts))
+        else:
+            draws = (self._ptr(draws),)
+        ns, bits = ((n,), (element_bits,)) if batch is None else ((n, batch[0]), (element_bits, int(batch[1])))
+        took = self._took(getattr(self._lib, name)(self._h, C, *(int(v) for v in ns), arr, nl, ps, pd, *bits, *draws, pm, pc, self._ptr(sum_out)))
+        if took and hand_back:
+            hand_back()
+        return took
+
     def quantize_combine_cohort_dev(self, n, layers, srcs, dtypes, element_bits, u, masks, cts, sum_out, compact=False, batch=None):
         """A precompute cohort's ONLINE step in one pass, no AES (flashe_quantize_combine_cohort_dev; compact=True: _u32_dev on uint32
         vectors; batch=(n_elems, field_bits): flashe_quantize_batch_combine_cohort_dev over the batched elements): cts[c] = (client c's
         plaintext + masks[c]) mod 2^b and sum_out (optional) = their sum.  layers / srcs / dtypes / u as quantize_encrypt_cohort_dev.
         Returns False -- nothing was launched -- when the library declines (FLASHE_ENOTSUP), True otherwise."""
-        arr, nl = self._tensor_layers(layers)
-        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
-        pm, _a = self._ptr_array(masks)
-        pc, _b = self._ptr_array(cts)
-        if batch is not None:
-            n_elems, field_bits = batch
-            rc = self._lib.flashe_quantize_batch_combine_cohort_dev(self._h, C, int(n), int(n_elems), arr, nl, ps, pd, element_bits, int(field_bits),
-                                                                    self._ptr(u), pm, pc, self._ptr(sum_out))
-        else:
-            fn = self._lib.flashe_quantize_combine_cohort_u32_dev if compact else self._lib.flashe_quantize_combine_cohort_dev
-            rc = fn(self._h, C, int(n), arr, nl, ps, pd, element_bits, self._ptr(u), pm, pc, self._ptr(sum_out))
-        return self._took(rc)
+        name = ("flashe_quantize_batch_combine_cohort_dev" if batch is not None else
+                "flashe_quantize_combine_cohort_u32_dev" if compact else "flashe_quantize_combine_cohort_dev")
+        return self._prepared_cohort_launch(name, n, layers, srcs, dtypes, element_bits, u, masks, cts, sum_out, batch)
 
     def quantize_combine_cohort_philox_dev(self, n, layers, srcs, dtypes, element_bits, generators_or_states, counts, offsets, masks, cts, sum_out,
                                            compact=False, batch=None):
@@ -878,22 +890,10 @@ class Engine:
         nothing was launched, nothing advanced -- when the library declines (FLASHE_ENOTSUP), True otherwise.
         batch=(n_elems, field_bits): the batched job (flashe_quantize_batch_combine_cohort_philox_dev) -- n counts the clients' VALUES,
         which is what the table tiles: client c rounds its flat value k with draw c n + k, an element's pads draw nothing."""
-        arr, nl = self._tensor_layers(layers)
-        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
-        pm, _a = self._ptr_array(masks)
-        pc, _b = self._ptr_array(cts)
-        segs, counts, offsets, hand_back = _draw_table(_PhiloxDraws, generators_or_states, counts, offsets)
-        if batch is not None:
-            n_elems, field_bits = batch
-            rc = self._lib.flashe_quantize_batch_combine_cohort_philox_dev(self._h, C, int(n), int(n_elems), arr, nl, ps, pd, element_bits, int(field_bits),
-                                                                           segs, len(counts), pm, pc, self._ptr(sum_out))
-        else:
-            fn = self._lib.flashe_quantize_combine_cohort_philox_u32_dev if compact else self._lib.flashe_quantize_combine_cohort_philox_dev
-            rc = fn(self._h, C, int(n), arr, nl, ps, pd, element_bits, segs, len(counts), pm, pc, self._ptr(sum_out))
-        took = self._took(rc)
-        if took:
-            hand_back()
-        return took
+        name = ("flashe_quantize_batch_combine_cohort_philox_dev" if batch is not None else
+                "flashe_quantize_combine_cohort_philox_u32_dev" if compact else "flashe_quantize_combine_cohort_philox_dev")
+        return self._prepared_cohort_launch(name, n, layers, srcs, dtypes, element_bits, (_PhiloxDraws, generators_or_states, counts, offsets), masks, cts,
+                                            sum_out, batch)
 
     def quantize_combine_cohort_pcg64_dev(self, n, layers, srcs, dtypes, element_bits, generators_or_states, counts, offsets, masks, cts, sum_out,
                                           compact=False):
@@ -904,16 +904,8 @@ class Engine:
         draws inside one entry -- and all of ONE variant.  The advanced states are handed back only after the call has succeeded (with
         has_uint32 / uinteger as they were); a refusal raises and advances nothing.  Returns False -- nothing was launched, nothing
         advanced -- when the library declines (FLASHE_ENOTSUP), True otherwise."""
-        arr, nl = self._tensor_layers(layers)
-        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
-        pm, _a = self._ptr_array(masks)
-        pc, _b = self._ptr_array(cts)
-        segs, counts, offsets, hand_back = _draw_table(_Pcg64Draws, generators_or_states, counts, offsets)
-        fn = self._lib.flashe_quantize_combine_cohort_pcg64_u32_dev if compact else self._lib.flashe_quantize_combine_cohort_pcg64_dev
-        took = self._took(fn(self._h, C, int(n), arr, nl, ps, pd, element_bits, segs, len(counts), pm, pc, self._ptr(sum_out)))
-        if took:
-            hand_back()
-        return took
+        name = "flashe_quantize_combine_cohort_pcg64_u32_dev" if compact else "flashe_quantize_combine_cohort_pcg64_dev"
+        return self._prepared_cohort_launch(name, n, layers, srcs, dtypes, element_bits, (_Pcg64Draws, generators_or_states, counts, offsets), masks, cts, sum_out)
 
     def quantize_batch_combine_cohort_philox_dev(self, n_values, n_elems, field_bits, layers, srcs, dtypes, element_bits, generators_or_states, counts,
                                                  offsets, masks, cts, sum_out):

@@ -1,5 +1,5 @@
 // Host check of the run arithmetic the BATCHED prepared cohort launch that generates its own Philox draws added to
-// flashe_amd/csrc/philox_stream.h (client_run, RunWalk, RunBlocks) and to layer_tables.h (batched_groups, prepared_batch_draws_block),
+// flashe_amd/csrc/philox_stream.h (client_run, RunWalk, RunBlocks) and to layer_tables.h (batched_groups, prepared_block with groups and plans),
 // built with -fsanitize=address,undefined by tests/test_batch_philox_run_host.py.  Everything is compared with brute force: position() +
 // block(), value by value.  Every skip 0 .. 3, bs 1 .. 10 and 128, row starts 0 .. 7, runs of four whole elements and runs that end
 // in pads, counters whose increment carries into word 1 and wraps at 2^256; the blocks a walk computes are counted; a segment table that
@@ -96,7 +96,7 @@ static void check_tables()
     CHECK(batched_groups(rows, 5, bs, first_group) == 13);
     const uint64_t want[] = {0, 1, 2, 4, 6};
     CHECK(memcmp(first_group, want, sizeof want) == 0);
-    const PreparedBatchDrawsBlock at = prepared_batch_draws_block(3, 5, sizeof(ClientPlan) / 8);
+    const PreparedBlock at = prepared_block(3, 5, sizeof(ClientPlan) / 8, true);
     CHECK(at.mask == 0 && at.ct == 24 && at.rows == 48 && at.groups == 48 + 80 && at.plans == 48 + 120 && at.words == 6 + 15 + 21);
     CHECK(at.rows == prepared_block(3, 5).rows && at.groups == 8 * prepared_block(3, 5).words);       // (the buffer form's block, then groups and plans)
     // the segments tile the clients' VALUES: a table over the elements is refused

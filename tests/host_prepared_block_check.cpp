@@ -36,6 +36,7 @@ static void check_block(int n_clients, int n_layers, const uint64_t *size, uint6
     CHECK(at.mask == 0 && at.ct == 8 * static_cast<size_t>(n_clients) && at.rows == 16 * static_cast<size_t>(n_clients));
     CHECK(at.mask % 8 == 0 && at.ct % 8 == 0 && at.rows % 8 == 0 && at.rows + 16 * n_rows == 8 * at.words);
     CHECK(prepared_block(n_clients).rows == at.rows && prepared_block(n_clients).words == 2 * static_cast<size_t>(n_clients));
+    CHECK(at.groups == 8 * at.words && at.plans == 8 * at.words);                      // (no groups, no plans: both empty, at the block's end)
     // behind cohort_stage's tables in one upload: the block starts at a 16-byte boundary and every word is where the kernel reads it
     Blob blob;
     std::vector<char> front(front_bytes, 'x');

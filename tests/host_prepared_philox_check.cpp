@@ -1,5 +1,5 @@
 // Host check of what the prepared cohort launch that generates its own Philox draws added to flashe_amd/csrc/philox_stream.h (client_plan,
-// client_draw, client_draws4, cohort_plans) and to layer_tables.h (prepared_draws_block), built with -fsanitize=address,undefined by
+// client_draw, client_draws4, cohort_plans) and to layer_tables.h (prepared_block with plans), built with -fsanitize=address,undefined by
 // tests/test_prepared_philox_host.py.  Every client's plan -- from one segment shared by all clients, from a segment per client in any
 // table order, from a generator continued over several segments -- against a generator written here that walks the stream ONE draw at a
 // time the way NumPy does: every buffer_pos 0 .. 4, client offsets of every residue mod 4, counters whose increment carries and wraps;
@@ -91,12 +91,12 @@ static void check_block(const std::vector<ClientPlan> &plans, size_t front_bytes
         extra[static_cast<size_t>(c)] = 0x1000u + 16u * static_cast<uint64_t>(c);
         extra[static_cast<size_t>(C) + c] = 0x900000u + 16u * static_cast<uint64_t>(c);
     }
-    const PreparedDrawsBlock at = prepared_draws_block(C, plan_words);
+    const PreparedBlock at = prepared_block(C, 0, plan_words);
     extra.resize(at.words);
     memcpy(extra.data() + 2 * static_cast<size_t>(C), plans.data(), plans.size() * sizeof(ClientPlan));
     CHECK(at.mask == 0 && at.ct == 8 * static_cast<size_t>(C) && at.plans == 16 * static_cast<size_t>(C) && at.words == 9 * static_cast<size_t>(C));
     CHECK(at.plans + sizeof(ClientPlan) * plans.size() == 8 * at.words);
-    CHECK(prepared_block(C).rows == at.plans);                      // (the pointers lie where the buffer form has them)
+    CHECK(prepared_block(C).rows == at.plans && at.rows == at.plans && at.groups == at.plans);      // (the pointers lie where the buffer form has them; no rows, no groups)
     Blob blob;
     std::vector<char> front(front_bytes, 'x');
     blob.add(front.data(), front.size());

@@ -1,5 +1,5 @@
 """CPU-only: the run arithmetic of the batched prepared cohort launch that generates its own Philox draws (flashe_amd/csrc/philox_stream.h:
-client_run, RunWalk, RunBlocks; layer_tables.h: batched_groups, prepared_batch_draws_block) against brute force -- position() + block(),
+client_run, RunWalk, RunBlocks; layer_tables.h: batched_groups, prepared_block with groups and plans) against brute force -- position() + block(),
 value by value -- at every skip, bs 1 .. 10 and 128, row starts 0 .. 7, runs that end in pads, the counter's carry and its wrap; and
 cohort_plans' refusal of a table that tiles the elements instead of the values.  Built with AddressSanitizer + UBSan as a stand-alone
 program (tests/host_batch_philox_run_check.cpp)."""

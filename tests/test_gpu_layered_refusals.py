@@ -1,5 +1,6 @@
 """GPU: the refusals of the entry points that take a per-layer table (flashe_amd/csrc/abi_layers.hip): the model-wide and batched
-codec, the tensor forms, the prepared client step, the dense and sparse cohorts, the layer-wise sparsifier and flashe_store_layers_dev.
+codec, the tensor forms, the prepared client step, the dense, prepared and sparse cohorts, the layer-wise sparsifier and
+flashe_store_layers_dev.
 
 Every case is a valid call with ONE bad argument, so no precedence between checks can matter; it asserts the code (FLASHE_EINVAL), a
 substring of the message, and that every output buffer still holds its poison pattern.  The calls go through the ctypes handle that
@@ -11,7 +12,9 @@ Shapes: a model of n = 13 values in three layers of 5, 0 and 8 (starts 0, 5, 5: 
 int_bits 128 (two limbs, 16-byte vectors) and 20 (one limb), the batched form at 128 with element_bits 16 in fields of 24 bits (5 values
 per element: 1 + 0 + 2 = 3 elements), cohorts of 2 clients.  The dense cohorts -- all eleven forms of the chained launch: first_idx or an
 index list, wide, compact or batched, whole or cut -- check their sources and alphas only once the launch has admitted the shape, so those
-cases run at the smallest size it admits on one compute unit (the cut forms: n = 13 as it is).
+cases run at the smallest size it admits on one compute unit (the cut forms: n = 13 as it is).  The prepared cohorts -- all eight forms of
+the online launch: a draw buffer or a Philox / PCG64 segment table, wide, compact or batched -- have no admission, so every case runs at
+n = 13; a form that draws inside the launch is given ONE segment tiling the clients' 2 n values, and every refusal leaves it as it was.
 """
 import copy
 import ctypes
@@ -63,6 +66,7 @@ def _layers(kind, rows):
 
 
 _ARRAYS = {"U32": ctypes.c_uint32, "U64": ctypes.c_uint64, "I32": ctypes.c_int32, "D": ctypes.c_double, "P": c_vp}
+_SEGMENTS = {"PX": _lib.PhiloxSegment, "PG": _lib.Pcg64Segment}          # a segment table: one dict of fields per segment, tuples for the arrays
 
 
 def _marshal(kind, v):
@@ -72,6 +76,12 @@ def _marshal(kind, v):
         return _layers(kind, v)
     if kind in _ARRAYS:
         return (_ARRAYS[kind] * max(len(v), 1))(*v)
+    if kind in _SEGMENTS:
+        arr = (_SEGMENTS[kind] * max(len(v), 1))()
+        for seg, fields in zip(arr, v):
+            for field, value in fields.items():
+                setattr(seg, field, type(getattr(seg, field))(*value) if isinstance(value, tuple) else value)
+        return arr
     return v
 
 
@@ -85,6 +95,7 @@ class EP:
     def call(self, r, a):
         fn = getattr(r.lib, "flashe_" + self.name)
         keep = [_marshal(kind, a[name]) for name, kind in self.args]
+        r.kept = {name: v for (name, _kind), v in zip(self.args, keep)}       # (what the call was given, as the call left it)
         rc = fn(r.h, *keep)
         msg = r.lib.flashe_last_error(r.h)
         return rc, (msg.decode() if msg else "")
@@ -119,6 +130,7 @@ class Rig:
         mask = (1 << min(bits, 64)) - 1
         for name in ("vin", "add", "minus"):
             setattr(self, name, inp(name, rng.integers(0, 2 ** 63, n * L, dtype=np.uint64) & np.uint64(mask)))
+        self.mask = [inp("mask%d" % c, rng.integers(0, 2 ** 63, n * L, dtype=np.uint64) & np.uint64(mask)) for c in range(2)]
         self.ct = [out("ct%d" % c, vb + 8) for c in range(2)]
         self.sum, self.dmask, self.fout = out("sum", vb), out("dmask", vb), out("fout", n * 8)
         self.store, self.stats = out("store", n * 4), out("stats", 2 * len(starts) * 8)
@@ -160,7 +172,11 @@ class Rig:
                  k=[2, 0, 3], residual=self.residual, loc=self.loc, vals=self.vals, packed=self.packed, pbits=8, first_idx=0, n_clients=2,
                  src=[p for c in range(2) for p in self.layer_ptrs(self.x[c], 4)], sdt=[F32] * (2 * len(self.starts)), cts=list(self.ct),
                  sum=self.sum, dmask=self.dmask, rstride=64, lstride=8, vstride=24, pstride=1, u_stride=n + 1, zzz=[0.5, 0.25], zf64=1,
-                 pts=list(self.pt), tails=list(self.tail), zeros=self.zeros, cidx=[0, 1], scratch=self.scratch)
+                 pts=list(self.pt), tails=list(self.tail), zeros=self.zeros, cidx=[0, 1], scratch=self.scratch, masks=list(self.mask), n_segs=1)
+        if "philox" in ep.name:
+            a["segs"] = [dict(key=(1, 2), counter=(3, 4, 5, 6), buffer=(7, 8, 9, 10), buffer_pos=2, n=2 * n, offset=0)]
+        if "pcg64" in ep.name:
+            a["segs"] = [dict(state=(11, 12), inc=(13, 14), variant=0, n=2 * n, offset=0)]
         a["layers"] = copy.deepcopy({"C": C, "B": B, "T": T, "S": S}[ep.table])
         if ep.name == "store_layers_dev":
             for l in range(len(self.starts)):
@@ -240,6 +256,19 @@ EPS = [
     EP("quantize_encrypt_sparse_cohort_dev", "iter n_clients cidx:U32 n n_jobs layers:T n_layers src:P sdt:I32 eb u u_stride zzz:D zf64 cts:P zeros", "S",
        widths=(20,), cohort=True),
 ]
+# the prepared cohort's online launch, all eight forms: the draws from a buffer, or generated inside the launch from a segment table
+PREP = "n_clients n layers:T n_layers src:P sdt:I32 eb u masks:P cts:P sum"
+PREP_BATCH = "n_clients n_values n_elems layers:T n_layers src:P sdt:I32 eb fb u masks:P cts:P sum"
+EPS += [
+    EP("quantize_combine_cohort_dev", PREP, "S", cohort=True),
+    EP("quantize_combine_cohort_u32_dev", PREP, "S", widths=(20,), cohort=True),
+    EP("quantize_batch_combine_cohort_dev", PREP_BATCH, "S", widths=(128,), cohort=True),
+    EP("quantize_combine_cohort_philox_dev", PREP.replace(" u ", " segs:PX n_segs "), "S", cohort=True),
+    EP("quantize_combine_cohort_philox_u32_dev", PREP.replace(" u ", " segs:PX n_segs "), "S", widths=(20,), cohort=True),
+    EP("quantize_batch_combine_cohort_philox_dev", PREP_BATCH.replace(" u ", " segs:PX n_segs "), "S", widths=(128,), cohort=True),
+    EP("quantize_combine_cohort_pcg64_dev", PREP.replace(" u ", " segs:PG n_segs "), "S", cohort=True),
+    EP("quantize_combine_cohort_pcg64_u32_dev", PREP.replace(" u ", " segs:PG n_segs "), "S", widths=(20,), cohort=True),
+]
 BY_NAME = {ep.name: ep for ep in EPS}
 
 CODEC_FRONT = {"quantize_encrypt_model_dev", "quantize_encrypt_prepared_model_dev", "quantize_encrypt_tensors_dev",
@@ -250,6 +279,8 @@ DENSE = {"quantize_encrypt_cohort_dev", "quantize_encrypt_cohort_u32_dev", "quan
          "quantize_encrypt_cohort_cut_dev", "quantize_encrypt_cohort_cut_u32_dev",
          "quantize_encrypt_cohort_runs_dev", "quantize_encrypt_cohort_runs_u32_dev", "quantize_batch_encrypt_cohort_runs_dev",
          "quantize_encrypt_cohort_cut_runs_dev", "quantize_encrypt_cohort_cut_runs_u32_dev", "quantize_batch_encrypt_cohort_cut_runs_dev"}
+PREPARED = {"quantize_%scombine_cohort%s_dev" % f for f in (("", ""), ("", "_u32"), ("batch_", ""), ("", "_philox"), ("", "_philox_u32"), ("batch_", "_philox"),
+                                                          ("", "_pcg64"), ("", "_pcg64_u32"))}
 SPARSE_Q = {"quantize_cohort_dev", "quantize_encrypt_sparse_cohort_dev"}
 NO_ALPHA = {"store_layers_dev", "sparsify_tensors_dev", "sparsify_cohort_tensors_dev"} | DENSE   # (the dense cohorts: cases_admitted)
 
@@ -297,7 +328,7 @@ def cases(ep, bits):
         bad += [("dtype 77", layer(1, 4, 77), "layer 1: unknown dtype 77"), ("flag 8", layer(2, 5, 8), "layer 2: unknown flags 0x8")]
     # -- widths and counts --
     if "eb" in names:
-        msg = BITS_FRONT if name in CODEC_FRONT | DENSE | SPARSE_Q else BITS_BATCH if "fb" in names else BITS_BACK
+        msg = BITS_FRONT if name in CODEC_FRONT | DENSE | PREPARED | SPARSE_Q else BITS_BATCH if "fb" in names else BITS_BACK
         bad += [("element_bits 0", put("eb", 0), msg), ("element_bits 63", put("eb", 63), msg)]
         if not wide and msg == BITS_FRONT:
             bad += [("element_bits int_bits + 1", put("eb", bits + 1), msg)]
@@ -374,6 +405,29 @@ def cases(ep, bits):
             if not u32:
                 bad += [("scratch aliases the mask", lambda a, r: a.__setitem__("scratch", a["dmask"]), "scratch_dev aliases the sum or the mask")]
             good += [("null scratch at one piece", put("scratch", None))]
+    if name in PREPARED:
+        w = "flashe_" + name + ": "
+        es = 4 if name.endswith("u32_dev") else 16 if wide else 8       # what masks, ciphertexts and sum are made of
+        bad += [("n_clients 0", put("n_clients", 0), w + "n_clients must be >= 1"), ("null masks", put("masks", None), w + "null argument"),
+                ("null ciphertext", item("cts", 1, None), "client 1: null mask or ciphertext"),
+                ("mask + %d" % (es // 2), item("masks", 0, lambda a, r: a["masks"][0] + es // 2), "client 0: the mask or the ciphertext is not %d-byte aligned" % es),
+                ("sum + %d" % (es // 2), off("sum", es // 2), "sum_out_dev must be %d-byte aligned" % es),
+                ("sum aliases a ciphertext", lambda a, r: a.__setitem__("sum", a["cts"][1]), "client 1: the sum aliases the mask or the ciphertext"),
+                ("sum aliases a source", lambda a, r: a.__setitem__("sum", a["src"][3]), "the sum aliases a source (client 1 layer 0)")]
+        if "u" in names:
+            bad += [("u + 4", off("u", 4), U8)]
+        if "segs" in names:
+            # one segment over the 2 n values cut in two: with a gap, and through client 0's last value
+            def cut(first, gap=0, **second):
+                return lambda a, r: a.update(n_segs=2, segs=[dict(a["segs"][0], n=first), dict(a["segs"][0], n=2 * N - first - gap, offset=first + gap, **second)])
+            bad += [("n_segments -1", put("n_segs", -1), w + "-1 segments, a launch holds 0 .. 128"),
+                    ("a gap", cut(N, gap=1), w + "the segments must tile the draws [0, n_clients x n) exactly"),
+                    ("a split client", cut(N - 1), w + "a client's n draws must come from one segment")]
+            if "philox" in name:
+                bad += [("buffer_pos 5", lambda a, r: a["segs"][0].__setitem__("buffer_pos", 5), w + "a buffer_pos above 4")]
+            else:
+                bad += [("variant 2", lambda a, r: a["segs"][0].__setitem__("variant", 2), w + "a variant that is neither PCG64 (0) nor PCG64DXSM (1)"),
+                        ("both variants", cut(N, variant=1), w + "PCG64 and PCG64DXSM segments in one table: a launch has one variant")]
     if name == "sparsify_cohort_tensors_dev":
         bad += [("n_clients 0", put("n_clients", 0), who + "n_clients must be in [1, 65535]"), ("null k", put("k", None), who + "null argument"),
                 ("null src", put("src", None), who + "null argument"), ("null dtypes", put("sdt", None), who + "null argument"),
@@ -430,6 +484,8 @@ def run_cases(r, ep):
         dirty = r.dirty()
         if rc != EINVAL or want not in msg or dirty:
             wrong.append("%s [%s]: code %d, message %r (want %r), written: %s" % (ep.name, label, rc, msg, want, dirty))
+        if a.get("segs") is not None and bytes(r.kept["segs"]) != bytes(_marshal(dict(ep.args)["segs"], a["segs"])):
+            wrong.append("%s [%s]: the refused call changed the caller's segment table" % (ep.name, label))
         if ep.prep and label == "prepared for another length":
             held, n, _a, _m = r.eng.prepared_query(1 if ep.prep[0] == "enc" else 2)
             if not held or n != a["_prep"]:
@@ -462,24 +518,34 @@ def test_one_fault_is_einval_with_its_message_and_writes_nothing(rigs, ep, bits)
     assert not wrong, "\n".join(wrong)
 
 
-@pytest.mark.parametrize("ep", [ep for ep in EPS if ep.ok == ENOTSUP], ids=lambda ep: ep.name)
-def test_refusal_comes_before_admission(rigs, ep):
-    """A valid call the chained launch does not take is FLASHE_ENOTSUP; the same call with one bad argument is FLASHE_EINVAL."""
-    r = rigs(ep.widths[0])
-    rc, msg = r.run(ep, r.defaults(ep))
-    assert rc == ENOTSUP and "not a shape of the chained" in msg, (rc, msg)
-    a = r.defaults(ep)
-    a["eb"] = 63
-    rc, msg = r.run(ep, a)
-    assert rc == EINVAL and BITS_FRONT in msg, (rc, msg)
-    assert not r.dirty()
+@pytest.mark.parametrize("ep", [ep for ep in EPS if ep.ok == ENOTSUP or (ep.name in PREPARED and ep.name.endswith("u32_dev"))], ids=lambda ep: ep.name)
+def test_refusal_comes_before_admission(rigs, ep, monkeypatch):
+    """A valid call the chained launch does not take is FLASHE_ENOTSUP; the same call with one bad argument is FLASHE_EINVAL.  The prepared
+    cohort's _u32 forms decline only a ctx without the compact layout: one created with the chained kernels switched off."""
+    own = ep.name in PREPARED
+    if own:
+        monkeypatch.setenv("FLASHE_CHAIN", "0")
+    r = Rig(ep.widths[0]) if own else rigs(ep.widths[0])
+    try:
+        assert not (own and r.eng.compact_supported())
+        rc, msg = r.run(ep, r.defaults(ep))
+        assert rc == ENOTSUP and "not a shape of the chained" in msg, (rc, msg)
+        a = r.defaults(ep)
+        a["eb"] = 63
+        rc, msg = r.run(ep, a)
+        assert rc == EINVAL and BITS_FRONT in msg, (rc, msg)
+        assert not r.dirty()
+    finally:
+        if own:
+            r.eng.close()
 
 
 @pytest.mark.parametrize("bits", [128, 20])
 def test_refusals_leave_the_ctx_as_it_was(rigs, bits):
-    """One valid call per non-cohort entry point, every refusal, the valid calls again: bit-identical outputs (no half-written scratch or table)."""
+    """One valid call per non-cohort entry point and of one prepared cohort form that draws inside its launch, every refusal, the valid calls
+    again: bit-identical outputs (no half-written scratch or table)."""
     r = rigs(bits)
-    eps = [ep for ep in EPS if not ep.cohort and bits in ep.widths]
+    eps = [ep for ep in EPS if (not ep.cohort or ep.name == "quantize_combine_cohort_philox_dev") and bits in ep.widths]
 
     def valid():
         got = {}

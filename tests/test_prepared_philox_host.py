@@ -1,5 +1,5 @@
 """CPU-only: the per-client draw plans of the prepared cohort launch that generates its own Philox draws (flashe_amd/csrc/philox_stream.h:
-client_plan, client_draw, client_draws4, cohort_plans) and its staging block (layer_tables.h: prepared_draws_block) against a generator
+client_plan, client_draw, client_draws4, cohort_plans) and its staging block (layer_tables.h: prepared_block with plans) against a generator
 that walks the stream one draw at a time -- every buffer_pos, client offsets of every residue, the counter's carry and its wrap -- and
 the tiling check of the segments (gap, overlap, overrun), built with AddressSanitizer + UBSan as a stand-alone program
 (tests/host_prepared_philox_check.cpp)."""
