@@ -10,6 +10,9 @@ which this example checks.
   --bits B     int_bits of the job (default 128; the reference's shipped un-batched jobs run 20)
   --compact    with --bits <= 32: uint32 ciphertexts and sum (FlasheCohort(compact=True)); at int_bits 16 / 20 / 23 / 24 / 32 the chained
                launch then goes from the floats to the uint32 ciphertexts
+  --one-limb   with --bits 33 .. 64 (say --bits 40 or --bits 64): FlasheCohort(one_limb=True) -- the chained launch goes from the floats to
+               the one-limb uint64 ciphertexts and their sum (`upload.path` is "cohort-chain"; without the flag these widths run
+               "staged-chain"), no mask is kept and the decrypt of the sum takes the telescoped lists; the new global model is the same
   --batch      a batched job (the reference's *_q16_b6_pad jobs: --bits 120 --batch packs six 20-bit fields per element); the chained
                launch takes it when the model has enough batched elements to fill the chip
   --precompute a precompute job ("precompute": {"enable": true}): the cohort calls prepare_encrypt() one round ahead -- the masks of all
@@ -87,6 +90,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--bits", type=int, default=128)
     ap.add_argument("--compact", action="store_true")
+    ap.add_argument("--one-limb", action="store_true", help="with --bits 33 .. 64: the chained launch from the floats in the one-limb layout")
     ap.add_argument("--batch", action="store_true")
     ap.add_argument("--precompute", action="store_true")
     ap.add_argument("--cut", action="store_true", help="forty LeNet-sized models through the cut chained launch")
@@ -119,7 +123,7 @@ def main():
         bitgen = np.random.Philox if opt.rng == "philox" else np.random.SFC64
         return [np.random.Generator(bitgen(1000 + c)) for c in present]
 
-    cohort = FlasheCohort(args, first_idx=0, n_local=C, num_clients=C, prp_seed=key, compact=opt.compact,
+    cohort = FlasheCohort(args, first_idx=0, n_local=C, num_clients=C, prp_seed=key, compact=opt.compact, one_limb=opt.one_limb,
                           cut="any" if opt.cut and (dropped or opt.batch) else opt.cut, inline_draws="any" if opt.inline_draws and opt.rng == "pcg64" else opt.inline_draws)
     if opt.precompute:
         cohort.set_iter_index(it - 1)

@@ -90,15 +90,15 @@ class FlasheError(RuntimeError):
 
 
 # The chained cohort launches (abi_layers.hip, quantize_encrypt_cohort).  What a name says: _runs_ = the cipher indices as a list in place of
-# first_idx, batch = n_values and n_elems in place of n and a field_bits, _u32_ = the compact layout without a decrypt mask, _cut_ = a
-# trailing scratch.
+# first_idx, batch = n_values and n_elems in place of n and a field_bits, _u32_ = the compact layout without a decrypt mask, _u64_ = the
+# one-limb layout (int_bits 33 .. 64) without one, _cut_ = a trailing scratch.
 COHORT_LAUNCHES = (
     "flashe_quantize_encrypt_cohort_dev", "flashe_quantize_encrypt_cohort_u32_dev",
     "flashe_quantize_encrypt_cohort_cut_dev", "flashe_quantize_encrypt_cohort_cut_u32_dev",
     "flashe_quantize_encrypt_cohort_runs_dev", "flashe_quantize_encrypt_cohort_runs_u32_dev",
     "flashe_quantize_encrypt_cohort_cut_runs_dev", "flashe_quantize_encrypt_cohort_cut_runs_u32_dev",
     "flashe_quantize_batch_encrypt_cohort_dev", "flashe_quantize_batch_encrypt_cohort_runs_dev",
-    "flashe_quantize_batch_encrypt_cohort_cut_runs_dev",
+    "flashe_quantize_batch_encrypt_cohort_cut_runs_dev", "flashe_quantize_encrypt_cohort_u64_dev",
 )
 
 
@@ -107,7 +107,7 @@ def _cohort_signature(name):
     return (c_int, [c_vp, c_u32, ctypes.POINTER(c_u32) if "_runs_" in name else c_u32, c_int] + [c_u64] * (2 if batched else 1)    # ctx, iter, idx, n_clients, n
             + [c_u32, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp), ctypes.POINTER(ctypes.c_int32)]                  # n_jobs, table, sources
             + [c_int] * (2 if batched else 1) + [c_vp, ctypes.POINTER(c_vp), c_vp]                                                 # bits, u, cts, sum
-            + [c_vp] * (("_u32_" not in name) + ("_cut_" in name)))                                                                 # dmask, scratch
+            + [c_vp] * (("_u32_" not in name and "_u64_" not in name) + ("_cut_" in name)))                                                                 # dmask, scratch
 
 
 # The prepared cohort's online launches (abi_layers.hip, quantize_combine_cohort).  What a name says: batch_ = n_values and n_elems in place

@@ -1351,7 +1351,8 @@ def cohort_cut_pieces(idxs, items, cu_count):
 
 
 def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, mask="double", num_clients=None, precompute=False, chain=True,
-                location_masks=False, compact=False, n_jobs=None, cohort_masks=False, present=None, compact_runs=False, cut=False, cut_any=False):
+                location_masks=False, compact=False, n_jobs=None, cohort_masks=False, present=None, compact_runs=False, cut=False, cut_any=False,
+                one_limb=False):
     """The engine-free part of FlasheCohort.quantize_encrypt: checks that the clients' Weights describe one model (the same layer names
     in the same walking order with the same shapes: ValueError naming the client and the layer otherwise; a sparse upload -- a 'zzz'
     layer or location masks -- is a TypeError), lays out the shared layer table and the client-major draws, and picks the path:
@@ -1397,6 +1398,12 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
                       int_bits > 64 with bs 5, 6 or 7, in one run or several (the rule counts the batched elements).  A cohort of more
                       than 16 runs (one table holds 16 chains) and a mixed-float64 one stay "staged-chain".
     cut_any=False: every plan is what it is without the keyword.
+    one_limb=True (FlasheCohort(one_limb=True) on an engine with flashe_quantize_encrypt_cohort_u64_dev) at int_bits 33 .. 64 in the one-limb
+    layout replaces the rule "int_bits <= 64" by the compact chain's: "cohort-chain" (uint64 ciphertexts and their sum from the floats, no
+    decrypt mask) for a double-mask, un-batched cohort of at most 128 clients in ONE run of consecutive clients whose model has at least
+    compact_cohort_admission_length(cu_count, int_bits, n_jobs) values and fewer than 2^32, every layer float64 for all clients or for
+    none; a shorter model stays "staged-chain" (the cut launch does not take these widths), and so does a round in which clients dropped
+    out in several runs.  Other widths and one_limb=False: every plan is what it is without the keyword.
     Touches no device.  The library's own answer stays the last word: a "cohort-chain" or "cut-chain" plan it declines runs
     "staged-chain", a "prepared-cohort" one "prepared-staged"."""
     if len(weights_list) < 1:
@@ -1424,6 +1431,7 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
         bs = int_bits // _field_bits(element_bits, num_clients)
         n_elems = sum((s_ + bs - 1) // bs for s_ in sizes)
     short, parts = False, 1                         # short: the length rule alone keeps the shape from the uncut chain
+    limb = bool(one_limb) and not compact and 33 <= int_bits <= 64      # the one-limb chain: the compact chain's rules at these widths
     if cohort_masks and mask == "double":
         if mixed:
             path, reason = PREPARED_STAGED, "a layer is float64 for some clients only: no shared row of one compute class"
@@ -1439,9 +1447,9 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
         path, reason = STAGED_CHAIN, "single mask: no stream is shared"
     elif compact and int_bits not in _COMPACT_COHORT_WIDTHS:
         path, reason = STAGED_CHAIN, f"int_bits {int_bits} is not a width of the compact chain {_COMPACT_COHORT_WIDTHS}"
-    elif not compact and int_bits <= 64:
+    elif not compact and not limb and int_bits <= 64:
         path, reason = STAGED_CHAIN, "int_bits <= 64"
-    elif batch and compact:
+    elif batch and (compact or limb):
         path, reason = STAGED_CHAIN, "batched job"
     elif batch and bs not in _COHORT_BATCH_SIZES:
         path, reason = STAGED_CHAIN, f"batched job with bs {bs}: the chained launch packs {_COHORT_BATCH_SIZES} values per element"
@@ -1449,10 +1457,12 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
         path, reason = STAGED_CHAIN, f"more than {_COHORT_MAX_LINKS} clients"
     elif not chain:
         path, reason = STAGED_CHAIN, "FLASHE_CHAIN=0"
-    elif compact and (n >= 2 ** 32 or compact_cohort_blocks(n, int_bits, n_jobs) < 2 * 128 * 16 * int(cu_count)):
-        path, reason, short = STAGED_CHAIN, "the vector does not fill the chip uncut", 1 <= n < 2 ** 32
-    elif not compact and (n_elems < cohort_admission_length(cu_count) or n_elems > 2 ** 32):
+    elif (compact or limb) and (n >= 2 ** 32 or compact_cohort_blocks(n, int_bits, n_jobs) < 2 * 128 * 16 * int(cu_count)):
+        path, reason, short = STAGED_CHAIN, "the vector does not fill the chip uncut", bool(compact) and 1 <= n < 2 ** 32
+    elif not compact and not limb and (n_elems < cohort_admission_length(cu_count) or n_elems > 2 ** 32):
         path, reason, short = STAGED_CHAIN, "the vector does not fill the chip uncut", 1 <= n_elems < cohort_admission_length(cu_count)
+    elif runs > 1 and limb:
+        path, reason = STAGED_CHAIN, f"clients dropped out ({runs} runs of indices): the one-limb chain takes one run of consecutive clients"
     elif runs > 1 and compact and not compact_runs:
         path, reason = STAGED_CHAIN, f"clients dropped out ({runs} runs of indices): the compact chain takes one run of consecutive clients"
     elif C + runs > _COHORT_MAX_STREAMS:
@@ -1522,6 +1532,12 @@ class FlasheCohort(object):
     run -- the chained launch goes from the floats to the uint32 ciphertexts and their sum (flashe_quantize_encrypt_cohort_u32_dev: 16
     bytes moved per value and client instead of 36).  No decrypt mask is kept at these widths: decrypt_unquantize() decrypts the
     sum.
+    one_limb=True (opt-in, like compact; int_bits 33 .. 64, ValueError otherwise; an engine without the entry point behaves as
+    one_limb=False): the widths of a job that quantises finer than the compact chain carries -- element_bits 32 with 2 .. 10 clients,
+    int_bits 64 -- chain from the floats too (flashe_quantize_encrypt_cohort_u64_dev: 20 bytes moved per value and client instead of 36).
+    The ciphertexts and the sum are the ordinary one-limb DeviceVectors of these widths whatever path ran; no decrypt mask is kept, and
+    decrypt_unquantize() decrypts the sum with the telescoped lists.  A model shorter than compact_cohort_admission_length(...), a batched
+    job, the single mask and a round in which clients dropped out in several runs stay "staged-chain".
     cut=True (opt-in, like compact): a model too SHORT for the uncut chain -- fewer than cohort_admission_length(cu_count) values, or
     compact_cohort_admission_length(...) in the compact layout: many clients with a small model -- runs "cut-chain" instead of
     "staged-chain": the summed chain cut into runs of consecutive clients and one combine pass (flashe_quantize_encrypt_cohort_cut_dev /
@@ -1554,7 +1570,8 @@ class FlasheCohort(object):
     the element-wise sum.  aggregate_packed() is that packed reduce of an upload, one pass over the ciphertexts where they lie, and
     decrypt_unquantize(packed=True) decrypts it, so that a cohort which simulates a dense job returns the global model the job produces."""
 
-    def __init__(self, args, first_idx, n_local, num_clients, prp_seed, device=0, stream=None, compact=False, cut=False, inline_draws=False):
+    def __init__(self, args, first_idx, n_local, num_clients, prp_seed, device=0, stream=None, compact=False, cut=False, inline_draws=False,
+                 one_limb=False):
         if isinstance(inline_draws, str) and inline_draws != "any":
             raise ValueError(f"inline_draws: True, False or \"any\", got {inline_draws!r}")
         if n_local < 1 or first_idx < 0 or first_idx + n_local > num_clients:
@@ -1576,6 +1593,10 @@ class FlasheCohort(object):
             ask = getattr(self.lead.cipher.engine, "compact_supported", None)
             if ask is None or not ask():
                 raise ValueError("compact=True needs an engine with the uint32 entry points (the table PRF backend, FLASHE_CHAIN not 0)")
+        if one_limb and not 33 <= self.lead.int_bits <= 64:
+            raise ValueError(f"one_limb=True needs int_bits 33 .. 64, this job runs int_bits {self.lead.int_bits}")
+        # the chained launch from the floats at int_bits 33 .. 64, where the engine has it (else the cohort is what it is without the keyword)
+        self.one_limb = bool(one_limb) and hasattr(self.lead.cipher.engine, "quantize_encrypt_cohort_u64_dev")
         self._clients = None
         if self.lead.precompute:                       # precomputed masks are per cipher: every client its own, one quantiser state
             self._clients = [self.lead]
@@ -1613,7 +1634,8 @@ class FlasheCohort(object):
                            compact_runs=hasattr(ld.cipher.engine, "quantize_encrypt_cohort_runs_u32_dev"),
                            cut=self.cut and hasattr(ld.cipher.engine, "quantize_encrypt_cohort_cut_u32_dev" if self.compact
                                                     else "quantize_encrypt_cohort_cut_dev"),
-                           cut_any=self.cut_any and all(hasattr(ld.cipher.engine, name) for name in self._cut_any_methods()))
+                           cut_any=self.cut_any and all(hasattr(ld.cipher.engine, name) for name in self._cut_any_methods()),
+                           one_limb=self.one_limb)
 
     def _cut_any_methods(self):
         """The engine methods cut="any" needs for this cohort's layout."""
@@ -1873,6 +1895,10 @@ class FlasheCohort(object):
         ld = self.lead
         q, c, eng = ld.quantizer, ld.cipher, ld.cipher.engine
         n, n_elems = plan.n, plan.n_elems
+        if self.one_limb:
+            # (int_bits 33 .. 64: one run of consecutive clients, no cut, and no decrypt mask -- the decrypt of the sum is 2 / m AES blocks per element)
+            return eng.quantize_encrypt_cohort_u64_dev(c.iter_index, self.first_idx + plan.present[0], n, _cipher_mod.N_JOBS, rows, srcs, dts,
+                                                       q.element_bits, du, [v.buf for v in cts], psum.buf)
         # (no decrypt mask at the compact widths: the decrypt of the sum is 2 / m AES blocks per element)
         dmask = DeviceVector(eng, n_elems) if self.n_local == self.num_clients and not self.compact else None
         outs, mask_buf = [v.buf for v in cts], dmask.buf if dmask is not None else None

@@ -669,13 +669,14 @@ static int cohort_check_scratch(flashe_ctx *ctx, int parts, int n_clients, const
     return FLASHE_OK;
 }
 
-// What tells the eleven chained cohort entry points apart, besides the element type T of their vectors (uint64_t: the wide two-limb
-// layout; uint32_t: the compact one, no decrypt mask).  `what` names the launch in a refusal.
+// What tells the twelve chained cohort entry points apart, besides the element type T of their vectors (uint64_t: the wide two-limb
+// layout, or the one-limb layout of the `one_limb` form; uint32_t: the compact one, no decrypt mask).  `what` names the launch in a refusal.
 struct CohortForm {
     const char *who, *what;
     bool by_list;            // the cipher indices: the list idx of the clients that report (the *_runs_* forms), else first_idx + c
     bool batched;            // a batched job: the table and sources over n_values values, the chain over n_elems batched elements
     bool cut;                // the short cohort (cohort_cut.h): no length rule, the chain cut into pieces, scratch_dev
+    bool one_limb;           // int_bits 33 .. 64 in the one-limb layout (limb_cohort_admits): uint64 vectors, no decrypt mask
 };
 
 // The one body of those entry points, every step once and in the order the refusals are documented in: the arguments and the cipher
@@ -727,8 +728,9 @@ static int quantize_encrypt_cohort(flashe_ctx *ctx, const CohortForm &f, uint32_
         parts = f.by_list ? cohort_cut_pieces_of(ctx->env, n_clients, idx, n_elems, n_jobs, compact, static_cast<int>(bs), begins)
                           : cohort_cut_parts_of(ctx->env, n_clients, n_elems, n_jobs, compact);
     const bool admitted = f.cut ? parts != 0
-                                : !gated && (compact ? small_cohort_admits(ctx->env, n_clients, n_elems, n_jobs, true)
-                                                     : cohort_chain_admits(ctx->env, n_clients, n_elems, static_cast<int>(bs)));
+                                : !gated && (compact      ? small_cohort_admits(ctx->env, n_clients, n_elems, n_jobs, true)
+                                             : f.one_limb ? limb_cohort_admits(ctx->env, n_clients, n_elems, n_jobs)
+                                                          : cohort_chain_admits(ctx->env, n_clients, n_elems, static_cast<int>(bs)));
     if (!admitted) return cohort_declined(ctx, f.who, f.what);
     if (f.cut && (rc = cohort_check_scratch(ctx, parts, n_clients, scratch_dev, reinterpret_cast<const void *const *>(ct_dev), sum_out_dev,
                                             compact ? nullptr : dmask_dev)))
@@ -767,6 +769,19 @@ int flashe_quantize_encrypt_cohort_u32_dev(flashe_ctx *ctx, uint32_t iter, uint3
         ctx, {"flashe_quantize_encrypt_cohort_u32_dev", "compact cohort", false, false, false}, first_idx, nullptr, n_clients, n, n, n_jobs, layers, n_layers,
         src_dev, src_dtype, element_bits, 0, u_dev, ct_dev, sum_out_dev, nullptr, nullptr, [&](const uint32_t *ids, const CohortCodec &cc, const CohortBatch *) {
             return launch_small_cohort_sum(ctx->env, iter, n_clients, ids, cc, u_dev, ct_dev, sum_out_dev, n, n_jobs);
+        });
+}
+
+// the same cohort in the one-limb layout at int_bits 33 .. 64 (prf_limb_cohort_kernel): uint64 ciphertexts and their uint64 sum, no decrypt mask
+int flashe_quantize_encrypt_cohort_u64_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                           const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                           int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev)
+{
+    CHECK_CTX(ctx);
+    return quantize_encrypt_cohort<uint64_t>(
+        ctx, {"flashe_quantize_encrypt_cohort_u64_dev", "one-limb cohort", false, false, false, true}, first_idx, nullptr, n_clients, n, n, n_jobs, layers, n_layers,
+        src_dev, src_dtype, element_bits, 0, u_dev, ct_dev, sum_out_dev, nullptr, nullptr, [&](const uint32_t *ids, const CohortCodec &cc, const CohortBatch *) {
+            return launch_limb_cohort_sum(ctx->env, iter, n_clients, ids, cc, u_dev, ct_dev, sum_out_dev, n, n_jobs);
         });
 }
 

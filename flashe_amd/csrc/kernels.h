@@ -128,6 +128,15 @@ bool small_cohort_admits(const LaunchEnv &env, int n_vec, uint64_t n, uint32_t n
 // streams fit the table (cohort_streams.h; several runs: prf_small_cohort_runs_kernel).  hipErrorNotSupported: nothing launched.
 hipError_t launch_small_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
                                    uint32_t *const *out_dev, uint32_t *sum_out_dev, uint64_t n, uint32_t n_jobs);
+// The shapes the one-limb cohort launch below takes, in the same terms: int_bits 33 .. 64, the chained table PRF without a fused codec,
+// 1 .. kMaxLinks clients, 0 < n < 2^32, n_jobs != 0 and at least 2 x 128 AES blocks (of 128 / int_bits elements, per the chunking of
+// n_jobs) for each of the chip's waves.
+bool limb_cohort_admits(const LaunchEnv &env, int n_vec, uint64_t n, uint32_t n_jobs);
+// The same cohort at int_bits 33 .. 64 in the one-limb layout (prf_limb_cohort_kernel<2 | 3>): uint64 ciphertexts (8-byte aligned) and
+// their uint64 sum from the floats, no decrypt mask.  Admitted where limb_cohort_admits says and idx is ONE run of consecutive indices
+// below 2^32 - 1 (cohort_streams.h).  hipErrorNotSupported: nothing launched.
+hipError_t launch_limb_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
+                                  uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs);
 // The sparse job's cohort at the same widths (prf_small_sparse_cohort_kernel): out_dev[c][k] = SINGLE-mask encrypt (idx[c]; any indices) of the
 // quantisation of client c's compact value k with the draw u_dev[c * u_stride + k], k < n, in the ONE-LIMB layout (uint64 elements, 8-byte
 // aligned), and out_dev[c][n] = zeros_dev[c] = the client's 'zzz' value zzz_dev[c] quantised in plain with (z_alpha, z_scale, z_den) in

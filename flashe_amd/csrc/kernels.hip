@@ -1194,6 +1194,12 @@ struct CohortDirect {
     template <int M> __device__ __forceinline__ DirectPt<M> block(int link, uint64_t k, int half) const
     {
         DirectPt<M> r;
+        words<M>(link, k, half, r.v);
+        return r;
+    }
+    // W = uint32_t: the M words of block(); uint64_t: the same plaintexts as whole 64-bit values (prf_limb_cohort_kernel, int_bits 33 .. 64)
+    template <int M, class W> __device__ __forceinline__ void words(int link, uint64_t k, int half, W (&r)[M]) const
+    {
         uint64_t ub[M];
         cohort_load_run<M>(u[link] + k, ub);
         const int lay = row[half];
@@ -1207,15 +1213,14 @@ struct CohortDirect {
             cohort_load_run<M>(static_cast<const uint64_t *>(xs) + (k - ls), raw);
 #pragma unroll
             for (int t = 0; t < M; t++)
-                r.v[t] = static_cast<uint32_t>(cohort_quantize_raw(raw[t], true, p0, p1, p2, __longlong_as_double(static_cast<long long>(ub[t]))));
+                r[t] = static_cast<W>(cohort_quantize_raw(raw[t], true, p0, p1, p2, __longlong_as_double(static_cast<long long>(ub[t]))));
         } else {
             uint32_t raw[M];
             cohort_load_run<M>(static_cast<const uint32_t *>(xs) + (k - ls), raw);
 #pragma unroll
             for (int t = 0; t < M; t++)
-                r.v[t] = static_cast<uint32_t>(cohort_quantize_raw(raw[t], false, p0, p1, p2, __longlong_as_double(static_cast<long long>(ub[t]))));
+                r[t] = static_cast<W>(cohort_quantize_raw(raw[t], false, p0, p1, p2, __longlong_as_double(static_cast<long long>(ub[t]))));
         }
-        return r;
     }
 };
 // the same front end element by element with the row looked up per lane (cohort_quantize_lane), for the tiles that walk: chunk ends, the
@@ -1508,6 +1513,142 @@ __global__ __launch_bounds__(kSmallThreads) void prf_small_sparse_cohort_kernel(
         tb.out[c][tail.n] = q;
     }
 #include "prf_small_chain_body.inc"
+}
+
+// ---- the cohort's chained launch from the floats at int_bits 33 .. 64, the one-limb layout (flashe_quantize_encrypt_cohort_u64_dev) ----
+// prf_small_cohort_kernel's scheme -- one summed double-mask chain over whole vectors, C + 1 streams for C consecutive cipher indices, a
+// wave owns 2 x 64 AES blocks per tile, counters by small_block_params, every stream's prefix from the LDS table, the lane that owns a
+// block quantises its M values of client `link` BEFORE that stream's AES rounds -- with M = 2 (int_bits 43 .. 64) or 3 (33 .. 42) whole
+// uint64 plaintexts per block and the width itself at run time (SmallParams, as prf_small_chain_kernel<PAIR, uint64_t, 0> takes it).  Per
+// value and client the launch reads 4 + 8 bytes and writes 8, against 36 through a quantise pass and the summed one-limb encrypt.
+// A body of its own: the chained kernels of prf_small_chain_body.inc keep their code objects.
+
+// bits [b t, b t + 64) of S for the slots of these widths, unmasked (t == 1 straddles the halves below b = 64, t == 2 lies in the high
+// half: 2 b >= 66); no shift by 64 is formed
+__device__ __forceinline__ uint64_t limb_slot(u128 S, int t, int b)
+{
+    const uint64_t lo = static_cast<uint64_t>(S), hi = static_cast<uint64_t>(S >> 64);
+    if (t == 0) return lo;
+    if (t == 1) return b == 64 ? hi : (lo >> b) | (hi << (64 - b));
+    return hi >> (2 * b - 64);
+}
+
+// the M elements of a whole block, masked, at q (8-byte aligned, every other block of M = 3 and any block of a chunk that begins at an odd
+// element starts 8 bytes past a 16-byte boundary): small_direct's measured form, one 16-byte access at M = 2, 16 + 8 bytes at M = 3
+template <int M, bool NT>
+__device__ __forceinline__ void limb_put(uint64_t *__restrict__ q, const uint64_t (&r)[M], uint64_t mask)
+{
+    u64x2 x;
+    x[0] = r[0] & mask; x[1] = r[1] & mask;
+    if (NT) __builtin_nontemporal_store(x, reinterpret_cast<u64x2 *>(q));
+    else *reinterpret_cast<u64x2 *>(q) = x;
+    if constexpr (M == 3) {
+        if (NT) __builtin_nontemporal_store(r[2] & mask, q + 2);
+        else q[2] = r[2] & mask;
+    }
+}
+
+template <int M>
+__global__ __launch_bounds__(kSmallThreads) void prf_limb_cohort_kernel(const RoundKeys rk, const SmallChainTable tb, const SmallParams p, const CohortCodec cc)
+{
+    static_assert(M == 2 || M == 3, "int_bits 43 .. 64 or 33 .. 42");
+    constexpr uint32_t WAVES = kSmallThreads / 64;
+    __shared__ uint32_t tab[kTabWords];
+    __shared__ uint32_t scratch[WAVES * 256 + 8];
+    __shared__ __attribute__((aligned(16))) uint32_t pre_lds[(kMaxLinks + kMaxChains) * 4];
+    const uint32_t iter = p.iter + p.te0[kIterShiftWord];
+    fill_tables(tab, p.te0);
+    const LaneRegs lr = lane_regs(tab);
+    const int n_streams = tb.len[0] + 1;
+    for (int s = threadIdx.x; s < n_streams; s += kSmallThreads) {
+        const CtrPrefix c = ctr_prefix(rk, lr, iter, tb.idx[s], 0u);              // n < 2^32 (host-checked): the high counter word is 0
+        *reinterpret_cast<uint4 *>(pre_lds + 4 * s) = make_uint4(c.u[0], c.u[1], c.u[2], c.u[3]);
+    }
+    __syncthreads();
+    const uint64_t n = p.n, J = p.n_jobs, d = n / J, r = n % J, blk_count = tb.blk_count[0];
+    const uint32_t nb1_32 = static_cast<uint32_t>((d + 1 + M - 1) / M), nb0_32 = static_cast<uint32_t>(d ? (d + M - 1) / M : 0);
+    const uint32_t d32 = static_cast<uint32_t>(d), r32 = static_cast<uint32_t>(r);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
+    uint32_t *row0 = scratch + wave * 256;
+    const u128 top = (static_cast<u128>(p.top_hi) << 64) | p.top_lo;
+    uint64_t *const sum = tb.sum_out[0];
+    // this workgroup's share of the vector's tiles, dealt to its waves in turn
+    const uint64_t T = (blk_count + 127u) / 128u, G = gridDim.x, g = blockIdx.x;
+    const uint64_t t_lo = T / G * g + (T % G) * g / G, t_hi = T / G * (g + 1) + (T % G) * (g + 1) / G;
+    for (uint64_t q = t_lo + wave; q < t_hi; q += WAVES) {
+        const uint64_t Bw = q * 128u;
+        const bool vA = Bw + lane < blk_count, vB = Bw + 64u + lane < blk_count;
+        uint64_t j0A = 0, j0B = 0;
+        int cntA = 0, cntB = 0;
+        uint32_t ctrA = 0, ctrB = 0;
+        small_block_params(static_cast<uint32_t>(vA ? Bw + lane : 0), nb1_32, nb0_32, d32, r32, M, p, &j0A, &cntA, &ctrA);
+        small_block_params(static_cast<uint32_t>(vB ? Bw + 64u + lane : 0), nb1_32, nb0_32, d32, r32, M, p, &j0B, &cntB, &ctrB);
+        const CtrVar xA = ctr_var(rk, lr, ctrA), xB = ctr_var(rk, lr, ctrB);
+        // a half tile of 64 whole blocks is one contiguous run of 64 M elements; the table row that holds all of it is found once, with
+        // scalar loads (CohortDirect).  Every other half -- a chunk end with a partial block, the range end, the last partial tile, a half
+        // that straddles a layer row -- walks (small_walk with CohortWalk) and keeps its sums in memory
+        const uint64_t e0A = uniform64(j0A), e0B = uniform64(j0B);
+        bool fastA = __ballot(vA && cntA == M) == ~0ull && e0A + 64u * M <= n;
+        bool fastB = __ballot(vB && cntB == M) == ~0ull && e0B + 64u * M <= n;
+        int layA = -1, layB = -1;
+        if (fastA) {
+            layA = cohort_layer_of(cc, e0A);
+            if (layA + 1 < cc.n_layers && *FLASHE_CONSTANT(const uint64_t, &cc.layers[layA + 1].start) < e0A + 64u * M) layA = -1;
+        }
+        if (fastB) {
+            layB = cohort_layer_of(cc, e0B);
+            if (layB + 1 < cc.n_layers && *FLASHE_CONSTANT(const uint64_t, &cc.layers[layB + 1].start) < e0B + 64u * M) layB = -1;
+        }
+        fastA = fastA && layA >= 0;
+        fastB = fastB && layB >= 0;
+        const CohortDirect csrc{cc, tb.in, 0, {layA, layB}};
+        u128 prevA = 0, prevB = 0;
+        uint64_t accA[M], accB[M];                                 // the whole blocks' running sums, unmasked: sums mod 2^64 agree with sums mod 2^b
+#pragma unroll
+        for (int t = 0; t < M; t++) { accA[t] = 0ull; accB[t] = 0ull; }
+        for (int c = 0; c < n_streams; c++) {
+            const CtrPrefix pre = load_prefix(pre_lds, c);
+            const int link = c - 1;                                // the output this stream completes
+            uint64_t ptA[M], ptB[M];
+#pragma unroll
+            for (int t = 0; t < M; t++) { ptA[t] = 0ull; ptB[t] = 0ull; }
+            if (link >= 0 && fastA) csrc.template words<M>(link, j0A, 0, ptA);
+            if (link >= 0 && fastB) csrc.template words<M>(link, j0B, 1, ptB);
+            uint32_t s[2][4];
+            ctr_round1(pre, xA, s[0]);
+            ctr_round1(pre, xB, s[1]);
+            aes256_rounds<2, 2>(rk, lr, s, p.swp_prio != 0);
+            const u128 SA = words_to_u128(s[0]), SB = words_to_u128(s[1]);
+            if (link >= 0) {
+                uint64_t *out = tb.out[link];
+                const CohortWalk cw{cc, tb.in[link], link};
+                if (fastA) {
+                    uint64_t v[M];
+#pragma unroll
+                    for (int t = 0; t < M; t++) {
+                        v[t] = ptA[t] + limb_slot(prevA, t, p.b) - limb_slot(SA, t, p.b);
+                        accA[t] += v[t];
+                    }
+                    limb_put<M, true>(out + j0A, v, p.mask_lo);
+                } else
+                    small_walk(row0, lane, vA, cntA, j0A, slot_diff(prevA, SA, top, p.b), static_cast<const uint64_t *>(nullptr), out, 0, n, p, sum, link == 0, &cw);
+                if (fastB) {
+                    uint64_t v[M];
+#pragma unroll
+                    for (int t = 0; t < M; t++) {
+                        v[t] = ptB[t] + limb_slot(prevB, t, p.b) - limb_slot(SB, t, p.b);
+                        accB[t] += v[t];
+                    }
+                    limb_put<M, true>(out + j0B, v, p.mask_lo);
+                } else
+                    small_walk(row0, lane, vB, cntB, j0B, slot_diff(prevB, SB, top, p.b), static_cast<const uint64_t *>(nullptr), out, 0, n, p, sum, link == 0, &cw);
+            }
+            prevA = SA; prevB = SB;
+        }
+        if (fastA) limb_put<M, false>(sum + j0A, accA, p.mask_lo);
+        if (fastB) limb_put<M, false>(sum + j0B, accB, p.mask_lo);
+    }
 }
 
 
@@ -2838,6 +2979,45 @@ hipError_t launch_small_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_ve
 #undef FLASHE_FIXED32
     default: return hipErrorNotSupported;
     }
+    return hipGetLastError();
+}
+
+// What the one-limb cohort launch admits (cohort_chain_admits' contract): int_bits 33 .. 64, the chained table PRF without a fused codec,
+// and the summed compact chain's length rule on the blocks of these widths -- the chain is never cut.
+bool limb_cohort_admits(const LaunchEnv &env, int n_vec, uint64_t n, uint32_t n_jobs)
+{
+    if (!env.use_chain || env.b < 33 || env.b > 64 || env.codec || !table_prf(env) || n_vec < 1 || n_vec > kMaxLinks) return false;
+    if (n == 0 || n >= (1ull << 32) || n_jobs == 0) return false;
+    return block_of(n - 1, n, n_jobs, 128 / env.b) + 1 >= 2 * 128 * static_cast<uint64_t>(env.num_cus) * (kSmallThreads / 64);
+}
+
+// The same summed chain over whole vectors at int_bits 33 .. 64 in the one-limb layout (prf_limb_cohort_kernel): cipher indices in ONE run
+// (a round in which clients dropped out stays with the staged launches), hipErrorNotSupported = nothing launched.
+hipError_t launch_limb_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
+                                  uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs)
+{
+    if (!limb_cohort_admits(env, n_vec, n, n_jobs) || !sum_out_dev || !u_dev || cc.n_layers < 1) return hipErrorNotSupported;
+    flashe_tables::CohortStreams st;
+    if (flashe_tables::cohort_streams(idx, n_vec, kMaxLinks + kMaxChains, st) != flashe_tables::kCohortStreamsOk || st.runs > 1) return hipErrorNotSupported;
+    for (int v = 0; v < n_vec; v++) if (!out_dev[v]) return hipErrorNotSupported;
+    const int n_streams = static_cast<int>(st.idx.size());      // (one run: idx and the index behind its last, n_vec + 1 streams)
+    SmallParams p = small_params_of(env, iter, n, n_jobs);
+    p.swp_prio = small_swp_prio(env, p, n_vec);
+    const uint64_t blocks = block_of(n - 1, n, n_jobs, p.m) + 1;
+    SmallChainTable tb{};
+    tb.first[0] = 0; tb.count[0] = n; tb.blk_first[0] = 0; tb.blk_count[0] = blocks;
+    tb.len[0] = static_cast<uint8_t>(n_vec);
+    for (int s = 0; s < n_streams; s++) tb.idx[s] = st.idx[s];
+    for (int l = 0; l < n_vec; l++) {
+        tb.in[l] = reinterpret_cast<const uint64_t *>(u_dev + static_cast<uint64_t>(l) * n);       // the link's draws (CohortDirect, CohortWalk)
+        tb.out[l] = out_dev[l];
+    }
+    tb.sum_out[0] = sum_out_dev;
+    const uint64_t tiles = (blocks + 127) / 128, cus = static_cast<uint64_t>(env.num_cus);
+    tb.wend[0] = tiles * static_cast<uint64_t>(n_streams);
+    const int grid = static_cast<int>(tiles < cus ? tiles : cus);
+    if (p.m == 2) hipLaunchKernelGGL((prf_limb_cohort_kernel<2>), dim3(grid), dim3(kSmallThreads), 0, env.stream, env.rk, tb, p, cc);
+    else hipLaunchKernelGGL((prf_limb_cohort_kernel<3>), dim3(grid), dim3(kSmallThreads), 0, env.stream, env.rk, tb, p, cc);
     return hipGetLastError();
 }
 

@@ -743,6 +743,12 @@ class Engine:
         declines the shape (FLASHE_ENOTSUP: the caller quantises per client and calls encrypt_batch_sum_u32_dev), True otherwise."""
         return self._cohort_launch("flashe_quantize_encrypt_cohort_u32_dev", it, first_idx, (n,), n_jobs, layers, srcs, dtypes, (element_bits,), u, cts, sum_out)
 
+    def quantize_encrypt_cohort_u64_dev(self, it, first_idx, n, n_jobs, layers, srcs, dtypes, element_bits, u, cts, sum_out):
+        """quantize_encrypt_cohort_dev in the one-limb layout (flashe_quantize_encrypt_cohort_u64_dev, int_bits 33 .. 64): cts and sum_out are
+        uint64 vectors of n elements, 8-byte aligned, there is no decrypt mask.  Returns False -- nothing was launched -- when the library
+        declines the shape (FLASHE_ENOTSUP: the caller quantises per client and calls encrypt_batch_sum_dev), True otherwise."""
+        return self._cohort_launch("flashe_quantize_encrypt_cohort_u64_dev", it, first_idx, (n,), n_jobs, layers, srcs, dtypes, (element_bits,), u, cts, sum_out)
+
     def cohort_cut_parts(self, n_clients, n, n_jobs, compact=False):
         """The pieces quantize_encrypt_cohort_cut_dev (compact: its _u32 form) will cut a cohort of n_clients clients with n values into
         (flashe_cohort_cut_parts): the caller sizes the scratch from it.  0: the library declines the shape (FLASHE_ENOTSUP)."""

@@ -95,7 +95,8 @@ typedef struct flashe_ctx flashe_ctx;
  *      flashe_quantize_combine_cohort_philox_u32_dev (a precompute job's cohort online with the draws of np.random.Philox streams
  *      generated inside the launch: no draw buffer) and flashe_quantize_batch_combine_cohort_philox_dev (the same for a batched job);
  *      flashe_quantize_combine_cohort_pcg64_dev / flashe_quantize_combine_cohort_pcg64_u32_dev (the un-batched form for the streams of
- *      np.random.PCG64 / PCG64DXSM, np.random.default_rng's generator) with flashe_pcg64_cohort_grid + flashe_pcg64_cohort_lane_draws */
+ *      np.random.PCG64 / PCG64DXSM, np.random.default_rng's generator) with flashe_pcg64_cohort_grid + flashe_pcg64_cohort_lane_draws;
+ *      flashe_quantize_encrypt_cohort_u64_dev (the cohort's chained launch in the one-limb layout, int_bits 33 .. 64) */
 #define FLASHE_ABI_VERSION 4
 int flashe_abi_version(void);
 int flashe_device_count(int *count);
@@ -740,6 +741,20 @@ int flashe_quantize_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uint32_t 
 int flashe_quantize_encrypt_cohort_u32_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs,
                                            const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
                                            int element_bits, const double *u_dev, uint32_t *const *ct_dev, uint32_t *sum_out_dev);
+/* The same cohort at int_bits 33 .. 64 in the one-limb layout (new), jzf_quantize.py:55-67, jzf_flashe.py:349-353, jzf_aggregator.py:424-430:
+ * the widths of a job that quantises finer than the compact layout carries (element_bits 32 with 2 .. 10 clients: int_bits 33 .. 36).
+ * ct_dev[c] and sum_out_dev are uint64 arrays of n elements (8-byte aligned: the values of flashe_quantize_encrypt_tensors_dev of client c
+ * and their sum mod 2^b), no decrypt mask (a decrypt at these widths is 2 / m AES blocks per element, m = 128 / int_bits = 2 or 3).  ONE
+ * chained launch from the floats: per value and client it reads the float and its draw and writes 8 bytes; no integer plaintext exists
+ * in HBM.  layers, src_dev, src_dtype, u_dev and the stage pass are those of flashe_quantize_encrypt_cohort_dev; the counters follow the
+ * chunking of n_jobs.
+ * Returns FLASHE_ENOTSUP -- nothing launched -- for every shape outside the launch: another int_bits, more than 128 clients, n = 0 or
+ * n >= 2^32, fewer AES blocks than 2 x 128 x 16 x flashe_ctx_cu_count (counted as for flashe_quantize_encrypt_cohort_u32_dev),
+ * FLASHE_CHAIN=0, another PRF backend; the caller then quantises per client and uses flashe_encrypt_batch_sum_dev.  The table uploads
+ * synchronise; not capturable. */
+int flashe_quantize_encrypt_cohort_u64_dev(flashe_ctx *ctx, uint32_t iter, uint32_t first_idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                           const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                           int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev);
 /* A SHORT cohort (new), jzf_quantize.py:394-491, jzf_flashe.py:349-353, 480-481, jzf_aggregator.py:424-430: the two cohort launches above
  * decline a vector that does not fill the chip uncut, and many clients with a small model is the shape a federation simulated on one card
  * most often has.  The three entry points below take any n >= 1: the summed chain is CUT into `parts` runs of consecutive clients,
