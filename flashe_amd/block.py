@@ -1895,19 +1895,20 @@ class FlasheCohort(object):
         ld = self.lead
         q, c, eng = ld.quantizer, ld.cipher, ld.cipher.engine
         n, n_elems = plan.n, plan.n_elems
-        if self.one_limb:
-            # (int_bits 33 .. 64: one run of consecutive clients, no cut, and no decrypt mask -- the decrypt of the sum is 2 / m AES blocks per element)
-            return eng.quantize_encrypt_cohort_u64_dev(c.iter_index, self.first_idx + plan.present[0], n, _cipher_mod.N_JOBS, rows, srcs, dts,
-                                                       q.element_bits, du, [v.buf for v in cts], psum.buf)
-        # (no decrypt mask at the compact widths: the decrypt of the sum is 2 / m AES blocks per element)
-        dmask = DeviceVector(eng, n_elems) if self.n_local == self.num_clients and not self.compact else None
+        # (no decrypt mask at the compact widths or in the one-limb layout: the decrypt of the sum is 2 / m AES blocks per element)
+        narrow = self.compact or self.one_limb
+        dmask = DeviceVector(eng, n_elems) if self.n_local == self.num_clients and not narrow else None
         outs, mask_buf = [v.buf for v in cts], dmask.buf if dmask is not None else None
         idxs = [self.first_idx + p for p in plan.present]
-        jobs, batch = _cipher_mod.N_JOBS, bool(ld.batch) and not self.compact
+        jobs, batch = _cipher_mod.N_JOBS, bool(ld.batch) and not narrow
         # the form: the cipher indices as a list for a gapped or batched cut and for a call with `present` (one run of a compact cohort
-        # without the gapped compact launch: plan_cohort sends a gapped one to the staged form), else the first index
+        # without the gapped compact launch: plan_cohort sends a gapped one to the staged form), else the first index.  One limb
+        # (int_bits 33 .. 64): one run of consecutive clients from its first index, never cut
+        if self.one_limb:
+            cut = by_idx = False
         by_list = (plan.runs > 1 or bool(ld.batch)) if cut else (by_idx and (not self.compact or hasattr(eng, "quantize_encrypt_cohort_runs_u32_dev")))
-        name = f"quantize_{'batch_' if batch else ''}encrypt_cohort{'_cut' if cut else ''}{'_runs' if by_list else ''}{'_u32' if self.compact else ''}_dev"
+        layout = "_u32" if self.compact else "_u64" if self.one_limb else ""
+        name = f"quantize_{'batch_' if batch else ''}encrypt_cohort{'_cut' if cut else ''}{'_runs' if by_list else ''}{layout}_dev"
         scratch = ()
         if cut:
             # the library's piece count sizes the scratch: the pieces' sums (compact: uint32) and, behind them, their decrypt masks
@@ -1921,7 +1922,7 @@ class FlasheCohort(object):
             scratch = (self._cut_scratch if need else None,)
         took = getattr(eng, name)(c.iter_index, idxs if by_list else idxs[0] if idxs else self.first_idx, *((n, n_elems) if batch else (n,)), jobs, rows,
                                   srcs, dts, q.element_bits, *((_field_bits(q.element_bits, q.num_clients),) if batch else ()), du, outs, psum.buf,
-                                  *(() if self.compact else (mask_buf,)), *scratch)
+                                  *(() if narrow else (mask_buf,)), *scratch)
         if took and dmask is not None:
             ld._cohort_mask = (psum.ptr, dmask, c.iter_index) + _telescoped(idxs)
         return took

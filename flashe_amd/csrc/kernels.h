@@ -128,9 +128,8 @@ bool small_cohort_admits(const LaunchEnv &env, int n_vec, uint64_t n, uint32_t n
 // streams fit the table (cohort_streams.h; several runs: prf_small_cohort_runs_kernel).  hipErrorNotSupported: nothing launched.
 hipError_t launch_small_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
                                    uint32_t *const *out_dev, uint32_t *sum_out_dev, uint64_t n, uint32_t n_jobs);
-// The shapes the one-limb cohort launch below takes, in the same terms: int_bits 33 .. 64, the chained table PRF without a fused codec,
-// 1 .. kMaxLinks clients, 0 < n < 2^32, n_jobs != 0 and at least 2 x 128 AES blocks (of 128 / int_bits elements, per the chunking of
-// n_jobs) for each of the chip's waves.
+// The shapes the one-limb cohort launch below takes: int_bits 33 .. 64 and, at these widths, the conditions of small_cohort_admits(summed)
+// (the precondition and the length rule are each stated once in kernels.hip; 0 < n < 2^32, n_jobs != 0).
 bool limb_cohort_admits(const LaunchEnv &env, int n_vec, uint64_t n, uint32_t n_jobs);
 // The same cohort at int_bits 33 .. 64 in the one-limb layout (prf_limb_cohort_kernel<2 | 3>): uint64 ciphertexts (8-byte aligned) and
 // their uint64 sum from the floats, no decrypt mask.  Admitted where limb_cohort_admits says and idx is ONE run of consecutive indices
@@ -147,8 +146,8 @@ hipError_t launch_small_sparse_cohort(const LaunchEnv &env, uint32_t iter, int n
                                       double z_alpha, double z_scale, double z_den, uint64_t *zeros_dev);
 // The SHORT cohort (cohort_cut.h): the two summed cohort launches above without their length rules, the chain cut into runs of consecutive
 // clients whose sums and decrypt masks one combine pass adds up.  cohort_cut_parts_of: the pieces the launch will use -- 0 outside the
-// uncut launch's other conditions (wide: the chained table PRF at int_bits > 64 without a fused codec, 1 .. kMaxLinks clients, n in one
-// counter window; compact: small_cohort_admits(not summed)) -- from the environment and the sizes alone; the caller sizes the scratch
+// uncut launch's other conditions (wide: cohort_chain_admits' without the length rule and the batch size; compact:
+// small_cohort_admits(not summed)) -- from the environment and the sizes alone; the caller sizes the scratch
 // from it: parts x n x 16 B for the sums and as much again behind them for the masks (wide, with dmask_dev), parts x n x 4 B (compact),
 // unused when parts == 1.  hipErrorNotSupported: nothing launched.
 // idx: any strictly ascending indices in at most 16 runs -- every gap is a cut (cohort_cut_pieces, cohort_cut.h).  cohort_cut_pieces_of: the

@@ -14,7 +14,7 @@
 #include "device_common.h"
 #include "cohort_streams.h"
 #include "cohort_cut.h"
-#include <cassert>
+#include "cohort_chain_table.h"
 #include <type_traits>
 
 namespace flashe {
@@ -2150,10 +2150,14 @@ hipError_t launch_prf_batch_sum(const LaunchEnv &env, uint32_t iter, int n_vec, 
 // begins with its predicate; the C ABI asks the same predicate before it stages anything ----
 static bool table_prf(const LaunchEnv &env) { return env.prf_backend == PRF_AUTO || env.prf_backend == PRF_TABLE; }
 
+// every layout's precondition: the chained kernels without a fused codec, the table PRF, 1 .. kMaxLinks clients
+static bool cohort_env_admits(const LaunchEnv &env, int n_vec) { return env.use_chain && !env.codec && table_prf(env) && n_vec >= 1 && n_vec <= kMaxLinks; }
+// n elements, at least one, in ONE counter window: the last counter fits 32 bits (the int_bits <= 64 layouts ask n itself to: n < 2^32)
+static bool one_counter_window(uint64_t n) { return n != 0 && !((n - 1) >> 32); }
+
 bool cohort_chain_admits(const LaunchEnv &env, int n_vec, uint64_t n_elems, int bs)
 {
-    if (!env.use_chain || env.b <= 64 || env.codec || !table_prf(env) || n_vec < 1 || n_vec > kMaxLinks) return false;
-    if (n_elems == 0 || ((n_elems - 1) >> 32)) return false;            // one counter window
+    if (!cohort_env_admits(env, n_vec) || env.b <= 64 || !one_counter_window(n_elems)) return false;
     if (bs != 0 && (bs < 5 || bs > 7)) return false;                    // the compiled batch sizes
     // (launch_prf_batch_sum's rule, counted in elements: two whole 256-element tiles per wave, uncut)
     return (n_elems + 255) / 256 >= 2 * static_cast<uint64_t>(env.num_cus) * (kPrfThreads / 64);
@@ -2174,53 +2178,54 @@ static CohortGaps cohort_gaps_of(const flashe_tables::CohortStreams &st)
     return cg;
 }
 
+// the values per element of a cohort's job: 0 = not batched; -1 (no admission takes it): no rows, or a field that no element holds
+static int cohort_batch_bs(const LaunchEnv &env, const CohortBatch *cb)
+{
+    return !cb ? 0 : (!cb->rows || cb->field_bits < 1 || cb->field_bits > env.b) ? -1 : env.b / cb->field_bits;
+}
+
+// the arguments every cohort launch needs: the sum (has_sum: the sparse launch has none), the draws, a table row, every client's ciphertext
+template <class E> static bool cohort_args_present(const CohortCodec &cc, const double *u_dev, E *const *out_dev, int n_vec, bool has_sum = true)
+{
+    if (!has_sum || !u_dev || cc.n_layers < 1) return false;
+    for (int v = 0; v < n_vec; v++) if (!out_dev[v]) return false;
+    return true;
+}
+
+// The launch of a wide cohort kernel by the values per element: PLAIN<kPrfThreads> un-batched (bs 0), BATCH<kPrfThreads, 5 | 6 | 7> with *cb
+// behind the table, then the kernel's own last arguments.  Reads the launcher's env, iter, cc, cb, bs, grid, block, tb, lo and hi.
+#define COHORT_LAUNCH_ONE(KERNEL, N_CHAINS, ALL_HALF, DMASK, ...) \
+    hipLaunchKernelGGL(KERNEL, grid, block, 0, env.stream, env.rk, tb, N_CHAINS, ALL_HALF, iter, lo, hi, env.te0_dev, DMASK, cc, ##__VA_ARGS__)
+#define COHORT_LAUNCH_BS(PLAIN, BATCH, N_CHAINS, ALL_HALF, DMASK, ...)                                                    \
+    switch (bs) {                                                                                                         \
+    case 0: COHORT_LAUNCH_ONE((PLAIN<kPrfThreads>), N_CHAINS, ALL_HALF, DMASK, ##__VA_ARGS__); break;                     \
+    case 5: COHORT_LAUNCH_ONE((BATCH<kPrfThreads, 5>), N_CHAINS, ALL_HALF, DMASK, *cb, ##__VA_ARGS__); break;             \
+    case 6: COHORT_LAUNCH_ONE((BATCH<kPrfThreads, 6>), N_CHAINS, ALL_HALF, DMASK, *cb, ##__VA_ARGS__); break;             \
+    default: COHORT_LAUNCH_ONE((BATCH<kPrfThreads, 7>), N_CHAINS, ALL_HALF, DMASK, *cb, ##__VA_ARGS__); break;            \
+    }
+
 // The shape launch_prf_batch_sum admits (one uncut summed double-mask chain of whole vectors), with the quantising front end per output;
 // cb: the batched form (prf_chain_cohort_batch_kernel), the same uncut chain over the n batched elements with one draw per VALUE.
 hipError_t launch_prf_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const CohortBatch *cb,
                                  const double *u_dev, uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs, uint64_t *dmask_dev)
 {
     (void)n_jobs;                            // (int_bits > 64: counters do not depend on the chunking)
-    const int bs = !cb ? 0 : (cb->field_bits < 1 || cb->field_bits > env.b) ? -1 : env.b / cb->field_bits;
-    if (!cohort_chain_admits(env, n_vec, n, bs) || !sum_out_dev || !u_dev || cc.n_layers < 1 || (cb && !cb->rows)) return hipErrorNotSupported;
+    const int bs = cohort_batch_bs(env, cb);
+    if (!cohort_chain_admits(env, n_vec, n, bs) || !cohort_args_present(cc, u_dev, out_dev, n_vec, sum_out_dev != nullptr)) return hipErrorNotSupported;
     // (any strictly ascending idx: one run launches the kernels it always has, several runs the GAPS ones over |P| + runs streams)
     flashe_tables::CohortStreams st;
     if (flashe_tables::cohort_streams(idx, n_vec, kMaxLinks + kMaxChains, st) != flashe_tables::kCohortStreamsOk) return hipErrorNotSupported;
-    for (int v = 0; v < n_vec; v++) if (!out_dev[v]) return hipErrorNotSupported;
-    const uint64_t tiles = (n + 255) / 256, u_stride = cb ? cb->n_values : n;
-    const int n_streams = static_cast<int>(st.idx.size());
+    const uint64_t tiles = (n + 255) / 256;
     ChainTable tb{};
-    tb.first[0] = 0; tb.count[0] = n;
-    tb.len[0] = static_cast<uint8_t>(n_vec);
-    tb.sum_out[0] = sum_out_dev;
-    for (int s = 0; s < n_streams; s++) tb.idx[s] = st.idx[s];
-    for (int l = 0; l < n_vec; l++) {
-        tb.in[l] = reinterpret_cast<const uint64_t *>(u_dev + static_cast<uint64_t>(l) * u_stride);       // the link's draws, one per value (CohortCodec)
-        tb.out[l] = out_dev[l];
-    }
-    tb.wend[0] = tiles * static_cast<uint64_t>(n_streams);
+    flashe_tables::cohort_whole_chain(tb, st, n_vec, n, tiles, u_dev, cb ? cb->n_values : n, out_dev, sum_out_dev);
     uint64_t lo, hi;
     masks_of(env.b, &lo, &hi);
     const dim3 grid(static_cast<unsigned>(std::min<uint64_t>(tiles, static_cast<uint64_t>(env.num_cus)))), block(kPrfThreads);
     if (st.runs > 1) {
         const CohortGaps cg = cohort_gaps_of(st);
-#define COHORT_BATCH_RUNS(BS) hipLaunchKernelGGL((prf_chain_cohort_batch_runs_kernel<kPrfThreads, BS>), grid, block, 0, env.stream, env.rk, tb, 1, 0, iter, lo, hi, env.te0_dev, dmask_dev, cc, *cb, cg)
-        switch (bs) {
-        case 0: hipLaunchKernelGGL((prf_chain_cohort_runs_kernel<kPrfThreads>), grid, block, 0, env.stream, env.rk, tb, 1, 0, iter, lo, hi, env.te0_dev, dmask_dev, cc, cg); break;
-        case 5: COHORT_BATCH_RUNS(5); break;
-        case 6: COHORT_BATCH_RUNS(6); break;
-        default: COHORT_BATCH_RUNS(7); break;
-        }
-#undef COHORT_BATCH_RUNS
-        return hipGetLastError();
-    }
-#define COHORT_BATCH(BS) hipLaunchKernelGGL((prf_chain_cohort_batch_kernel<kPrfThreads, BS>), grid, block, 0, env.stream, env.rk, tb, 1, 0, iter, lo, hi, env.te0_dev, dmask_dev, cc, *cb)
-    switch (bs) {
-    case 0: hipLaunchKernelGGL((prf_chain_cohort_kernel<kPrfThreads>), grid, block, 0, env.stream, env.rk, tb, 1, 0, iter, lo, hi, env.te0_dev, dmask_dev, cc); break;
-    case 5: COHORT_BATCH(5); break;
-    case 6: COHORT_BATCH(6); break;
-    default: COHORT_BATCH(7); break;
-    }
-#undef COHORT_BATCH
+        COHORT_LAUNCH_BS(prf_chain_cohort_runs_kernel, prf_chain_cohort_batch_runs_kernel, 1, 0, dmask_dev, cg);
+    } else
+        COHORT_LAUNCH_BS(prf_chain_cohort_kernel, prf_chain_cohort_batch_kernel, 1, 0, dmask_dev);
     return hipGetLastError();
 }
 
@@ -2233,8 +2238,7 @@ static uint64_t cohort_cut_items_of(const LaunchEnv &env, int n_vec, uint64_t n,
         if (!small_cohort_admits(env, n_vec, n, n_jobs, false)) return 0;      // (not `summed`: every condition but the length rule)
         return flashe_tables::cohort_cut_items_compact(block_of(n - 1, n, n_jobs, 128 / env.b) + 1);
     }
-    if (!env.use_chain || env.b <= 64 || env.codec || !table_prf(env) || n_vec < 1 || n_vec > kMaxLinks) return 0;
-    if (n == 0 || ((n - 1) >> 32)) return 0;                          // one counter window
+    if (!cohort_env_admits(env, n_vec) || env.b <= 64 || !one_counter_window(n)) return 0;
     return flashe_tables::cohort_cut_items_wide(n);
 }
 
@@ -2267,29 +2271,6 @@ int cohort_cut_pieces_of(const LaunchEnv &env, int n_vec, const uint32_t *idx, u
     return parts;
 }
 
-// the pieces of a cut cohort as chains of one table: piece p holds the present clients at positions [begins[p], begins[p + 1]) -- one run of
-// consecutive cipher indices --, its streams are theirs and the one behind its last client (launch_prf_chains' layout: a cut costs one
-// stream).  T = ChainTable / SmallChainTable.
-template <class T>
-static void cohort_cut_table(T &tb, int n_vec, int parts, const int *begins, const uint32_t *idx, uint64_t n, uint64_t tiles)
-{
-    static_assert(flashe_tables::kCutMaxParts == kMaxChains && flashe_tables::kCutMaxClients == kMaxLinks, "cohort_cut.h states the limits of one chained launch");
-    static_assert(flashe_tables::kCutMaxStreams == flashe_tables::kCohortMaxStreams, "cohort_cut.h and cohort_streams.h state one table's streams");
-    int streams = 0;
-    uint64_t wend = 0;
-    for (int p = 0; p < parts; p++) {
-        const int a = begins[p], len = begins[p + 1] - a;
-        tb.first[p] = 0; tb.count[p] = n;
-        tb.link0[p] = static_cast<uint16_t>(a); tb.sbase[p] = static_cast<uint16_t>(streams);
-        tb.len[p] = static_cast<uint8_t>(len);
-        for (int s = 0; s <= len; s++) tb.idx[streams + s] = idx[a] + static_cast<uint32_t>(s);
-        wend += tiles * static_cast<uint64_t>(len + 1);
-        tb.wend[p] = wend;
-        streams += len + 1;
-    }
-    assert(streams == n_vec + parts && streams <= flashe_tables::kCohortMaxStreams);
-}
-
 // prf_chain_cohort_cut_kernel + cohort_cut_combine_kernel: launch_prf_cohort_sum's outputs for ANY n >= 1.  Any strictly ascending cipher
 // indices in at most kCutMaxParts runs (every gap is a cut: cohort_cut_pieces); scratch_dev: parts x n x 16 B for the pieces' sums and as
 // much again for their masks when dmask_dev is given, unused when the rule gives one piece (the chain then writes the sum and the mask
@@ -2299,38 +2280,23 @@ static hipError_t launch_prf_cohort_cut_any(const LaunchEnv &env, uint32_t iter,
                                             const double *u_dev, uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs,
                                             uint64_t *dmask_dev, uint64_t *scratch_dev)
 {
-    const int bs = !cb ? 0 : (cb->field_bits < 1 || cb->field_bits > env.b) ? -1 : env.b / cb->field_bits;
+    const int bs = cohort_batch_bs(env, cb);
     int begins[flashe_tables::kCutMaxParts + 1];
     const int parts = cohort_cut_pieces_of(env, n_vec, idx, n, n_jobs, false, bs, begins);
-    if (!parts || !sum_out_dev || !u_dev || cc.n_layers < 1 || (cb && !cb->rows)) return hipErrorNotSupported;
-    for (int v = 0; v < n_vec; v++) if (!out_dev[v]) return hipErrorNotSupported;
+    if (!parts || !cohort_args_present(cc, u_dev, out_dev, n_vec, sum_out_dev != nullptr)) return hipErrorNotSupported;
     if (parts > 1 && !scratch_dev) return hipErrorInvalidValue;
-    const uint64_t tiles = (n + 255) / 256, stride = 2 * n, u_stride = cb ? cb->n_values : n;                // (stride: limbs of one piece's sum or mask)
+    const uint64_t tiles = (n + 255) / 256, stride = 2 * n;                // (stride: limbs of one piece's sum or mask)
     uint64_t *const psum = scratch_dev, *const pmask = dmask_dev ? scratch_dev + static_cast<uint64_t>(parts) * stride : nullptr;
     ChainTable tb{};
-    cohort_cut_table(tb, n_vec, parts, begins, idx, n, tiles);
+    if (!flashe_tables::cohort_cut_table(tb, n_vec, parts, begins, idx, n, tiles)) return hipErrorNotSupported;       // (never: the begins are pieces)
+    flashe_tables::cohort_chain_links(tb, n_vec, u_dev, cb ? cb->n_values : n, out_dev);
     for (int p = 0; p < parts; p++) tb.sum_out[p] = parts == 1 ? sum_out_dev : psum + static_cast<uint64_t>(p) * stride;
-    for (int l = 0; l < n_vec; l++) {
-        tb.in[l] = reinterpret_cast<const uint64_t *>(u_dev + static_cast<uint64_t>(l) * u_stride);       // the link's draws (CohortCodec)
-        tb.out[l] = out_dev[l];
-    }
     uint64_t lo, hi;
     masks_of(env.b, &lo, &hi);
     const bool all_half = flashe_tables::cohort_cut_all_half(n, parts, env.num_cus);
     const uint64_t items = (all_half ? 2 : 1) * tiles * static_cast<uint64_t>(parts), cus = static_cast<uint64_t>(env.num_cus);
     const dim3 grid(static_cast<unsigned>(items < cus ? items : cus)), block(kPrfThreads);
-#define COHORT_BATCH_CUT(BS) hipLaunchKernelGGL((prf_chain_cohort_batch_cut_kernel<kPrfThreads, BS>), grid, block, 0, env.stream, env.rk, tb, parts, all_half ? 1 : 0, iter, lo, hi, \
-                                                env.te0_dev, parts == 1 ? dmask_dev : pmask, cc, *cb, stride)
-    switch (bs) {
-    case 0:
-        hipLaunchKernelGGL((prf_chain_cohort_cut_kernel<kPrfThreads>), grid, block, 0, env.stream, env.rk, tb, parts, all_half ? 1 : 0, iter, lo, hi, env.te0_dev,
-                           parts == 1 ? dmask_dev : pmask, cc, stride);
-        break;
-    case 5: COHORT_BATCH_CUT(5); break;
-    case 6: COHORT_BATCH_CUT(6); break;
-    default: COHORT_BATCH_CUT(7); break;
-    }
-#undef COHORT_BATCH_CUT
+    COHORT_LAUNCH_BS(prf_chain_cohort_cut_kernel, prf_chain_cohort_batch_cut_kernel, parts, all_half ? 1 : 0, parts == 1 ? dmask_dev : pmask, stride);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess || parts == 1) return e;
     return launch_cohort_cut_combine(env, parts, n, psum, sum_out_dev, pmask, dmask_dev);
@@ -2916,109 +2882,96 @@ static hipError_t launch_small_chains(const LaunchEnv &env, uint32_t iter, int n
     return hipSuccess;
 }
 
+// the length rule of the int_bits <= 64 layouts' uncut summed chain: the vector's AES blocks (of 128 / int_bits elements, per the chunking
+// of n_jobs) are at least 2 x 128 for each of the chip's waves -- enough for the paired kernel (launch_small_chains' `pair`)
+static bool small_chain_long_enough(const LaunchEnv &env, uint64_t n, uint32_t n_jobs)
+{
+    return block_of(n - 1, n, n_jobs, 128 / env.b) + 1 >= 2 * 128 * static_cast<uint64_t>(env.num_cus) * (kSmallThreads / 64);
+}
+
 // What the compact cohort launches admit (cohort_chain_admits' contract): a compiled-in width, the table PRF, the chained kernels, and for
 // the `summed` chain, which is never cut, enough AES blocks for the paired kernel (launch_small_chains' `pair`).
 bool small_cohort_admits(const LaunchEnv &env, int n_vec, uint64_t n, uint32_t n_jobs, bool summed)
 {
-    if (!env.use_chain || env.b > 32 || !fixed32_width(env.b) || env.codec || !table_prf(env) || n_vec < 1 || n_vec > kMaxLinks) return false;
-    if (n == 0 || n >= (1ull << 32) || n_jobs == 0 || small_no_fixed_width()) return false;
-    return !summed || block_of(n - 1, n, n_jobs, 128 / env.b) + 1 >= 2 * 128 * static_cast<uint64_t>(env.num_cus) * (kSmallThreads / 64);
+    if (!cohort_env_admits(env, n_vec) || env.b > 32 || !fixed32_width(env.b) || n == 0 || n >= (1ull << 32) || n_jobs == 0 || small_no_fixed_width()) return false;
+    return !summed || small_chain_long_enough(env, n, n_jobs);
 }
 
-// what the two launches below share: the compact layout's constants with its measured priority table, and the vector's AES blocks
-static SmallParams small_cohort_params(const LaunchEnv &env, uint32_t iter, int n_vec, uint64_t n, uint32_t n_jobs, uint64_t *blocks)
+// What the one-limb cohort launch admits (the same contract): int_bits 33 .. 64, and the length rule -- its chain is never cut.
+bool limb_cohort_admits(const LaunchEnv &env, int n_vec, uint64_t n, uint32_t n_jobs)
 {
-    LaunchEnv e32 = env;
-    e32.elem32 = 1;                           // (the sparse launch too: its outputs are one-limb, the priority table is the compile-time widths')
-    SmallParams p = small_params_of(e32, iter, n, n_jobs);
-    p.no_direct = 1;                          // (the compact layout walks its rows: launch_small_chains)
-    p.swp_prio = small_swp_prio(e32, p, n_vec);
+    return cohort_env_admits(env, n_vec) && env.b >= 33 && env.b <= 64 && n != 0 && n < (1ull << 32) && n_jobs != 0 && small_chain_long_enough(env, n, n_jobs);
+}
+
+// what the int_bits <= 64 launches below share: the layout's constants with its measured priority table, and the vector's AES blocks.
+// compact: the uint32 layout's (the sparse launch's too: its outputs are one-limb, the priority table is the compile-time widths').
+static SmallParams small_cohort_params(const LaunchEnv &env, uint32_t iter, int n_vec, uint64_t n, uint32_t n_jobs, uint64_t *blocks, bool compact = true)
+{
+    LaunchEnv e = env;
+    if (compact) e.elem32 = 1;
+    SmallParams p = small_params_of(e, iter, n, n_jobs);
+    if (compact) p.no_direct = 1;             // (the compact layout walks its rows: launch_small_chains)
+    p.swp_prio = small_swp_prio(e, p, n_vec);
     *blocks = block_of(n - 1, n, n_jobs, p.m) + 1;
     return p;
 }
+
+// KERNEL<env.b> of a compact cohort over the launcher's `grid` workgroups; hipErrorNotSupported, nothing launched, at a width not compiled in
+template <class F> static hipError_t cohort_fixed32_launch(int b, F &&launch)
+{
+    switch (b) {
+#define FLASHE_FIXED32(B) case B: launch(std::integral_constant<int, B>{}); return hipGetLastError();
+        FLASHE_FIXED32_WIDTHS(FLASHE_FIXED32)
+#undef FLASHE_FIXED32
+    }
+    return hipErrorNotSupported;
+}
+#define COHORT_LAUNCH_FIXED32(KERNEL, ...) \
+    cohort_fixed32_launch(env.b, [&](auto w) { hipLaunchKernelGGL((KERNEL<decltype(w)::value>), dim3(grid), dim3(kSmallThreads), 0, env.stream, env.rk, __VA_ARGS__); })
 
 // The summed compact chain over whole vectors with the quantising front end per output (prf_small_cohort_kernel): the admission of the
 // summed chain of launch_small_chains -- a compiled-in width, one uncut chain, enough AES blocks for the paired kernel -- and
 // launch_prf_cohort_sum's contract: any strictly ascending idx (one run launches the kernel it always has with the table it always had,
 // several runs prf_small_cohort_runs_kernel over |P| + runs streams), hipErrorNotSupported = nothing launched.
+// The same chain at int_bits 33 .. 64 in the one-limb layout (E = uint64_t, prf_limb_cohort_kernel): cipher indices in ONE run only (a
+// round in which clients dropped out stays with the staged launches).
+template <class E>
+static hipError_t launch_whole_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
+                                          E *const *out_dev, E *sum_out_dev, uint64_t n, uint32_t n_jobs)
+{
+    constexpr bool compact = sizeof(E) == 4;
+    const bool admitted = compact ? small_cohort_admits(env, n_vec, n, n_jobs, true) : limb_cohort_admits(env, n_vec, n, n_jobs);
+    if (!admitted || !cohort_args_present(cc, u_dev, out_dev, n_vec, sum_out_dev != nullptr)) return hipErrorNotSupported;
+    flashe_tables::CohortStreams st;            // (one run: idx and the index behind its last, n_vec + 1 streams)
+    if (flashe_tables::cohort_streams(idx, n_vec, kMaxLinks + kMaxChains, st) != flashe_tables::kCohortStreamsOk || (!compact && st.runs > 1)) return hipErrorNotSupported;
+    uint64_t blocks;
+    const SmallParams p = small_cohort_params(env, iter, n_vec, n, n_jobs, &blocks, compact);
+    const uint64_t tiles = (blocks + 127) / 128, cus = static_cast<uint64_t>(env.num_cus);
+    SmallChainTable tb{};
+    flashe_tables::cohort_whole_chain(tb, st, n_vec, n, tiles, u_dev, n, out_dev, sum_out_dev);
+    flashe_tables::cohort_chain_blocks(tb, 1, blocks);
+    const int grid = static_cast<int>(tiles < cus ? tiles : cus);
+    if constexpr (!compact) {
+        if (p.m == 2) hipLaunchKernelGGL((prf_limb_cohort_kernel<2>), dim3(grid), dim3(kSmallThreads), 0, env.stream, env.rk, tb, p, cc);
+        else hipLaunchKernelGGL((prf_limb_cohort_kernel<3>), dim3(grid), dim3(kSmallThreads), 0, env.stream, env.rk, tb, p, cc);
+        return hipGetLastError();
+    } else if (st.runs > 1) {
+        const CohortGaps cg = cohort_gaps_of(st);
+        return COHORT_LAUNCH_FIXED32(prf_small_cohort_runs_kernel, tb, 1, p, cc, cg);
+    } else
+        return COHORT_LAUNCH_FIXED32(prf_small_cohort_kernel, tb, 1, p, cc);
+}
+
 hipError_t launch_small_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
                                    uint32_t *const *out_dev, uint32_t *sum_out_dev, uint64_t n, uint32_t n_jobs)
 {
-    if (!small_cohort_admits(env, n_vec, n, n_jobs, true) || !sum_out_dev || !u_dev || cc.n_layers < 1) return hipErrorNotSupported;
-    flashe_tables::CohortStreams st;
-    if (flashe_tables::cohort_streams(idx, n_vec, kMaxLinks + kMaxChains, st) != flashe_tables::kCohortStreamsOk) return hipErrorNotSupported;
-    for (int v = 0; v < n_vec; v++) if (!out_dev[v]) return hipErrorNotSupported;
-    const int n_streams = static_cast<int>(st.idx.size());      // (one run: idx and the index behind its last, n_vec + 1 streams)
-    uint64_t blocks;
-    const SmallParams p = small_cohort_params(env, iter, n_vec, n, n_jobs, &blocks);
-    SmallChainTable tb{};
-    tb.first[0] = 0; tb.count[0] = n; tb.blk_first[0] = 0; tb.blk_count[0] = blocks;
-    tb.len[0] = static_cast<uint8_t>(n_vec);
-    for (int s = 0; s < n_streams; s++) tb.idx[s] = st.idx[s];
-    for (int l = 0; l < n_vec; l++) {
-        tb.in[l] = reinterpret_cast<const uint64_t *>(u_dev + static_cast<uint64_t>(l) * n);       // the link's draws (CohortDirect, CohortWalk)
-        tb.out[l] = reinterpret_cast<uint64_t *>(out_dev[l]);
-    }
-    tb.sum_out[0] = reinterpret_cast<uint64_t *>(sum_out_dev);
-    const uint64_t tiles = (blocks + 127) / 128, cus = static_cast<uint64_t>(env.num_cus);
-    tb.wend[0] = tiles * static_cast<uint64_t>(n_streams);
-    const int grid = static_cast<int>(tiles < cus ? tiles : cus);
-    if (st.runs > 1) {
-        const CohortGaps cg = cohort_gaps_of(st);
-        switch (env.b) {
-#define FLASHE_FIXED32(B) case B: hipLaunchKernelGGL((prf_small_cohort_runs_kernel<B>), dim3(grid), dim3(kSmallThreads), 0, env.stream, env.rk, tb, 1, p, cc, cg); break;
-            FLASHE_FIXED32_WIDTHS(FLASHE_FIXED32)
-#undef FLASHE_FIXED32
-        default: return hipErrorNotSupported;
-        }
-        return hipGetLastError();
-    }
-    switch (env.b) {
-#define FLASHE_FIXED32(B) case B: hipLaunchKernelGGL((prf_small_cohort_kernel<B>), dim3(grid), dim3(kSmallThreads), 0, env.stream, env.rk, tb, 1, p, cc); break;
-        FLASHE_FIXED32_WIDTHS(FLASHE_FIXED32)
-#undef FLASHE_FIXED32
-    default: return hipErrorNotSupported;
-    }
-    return hipGetLastError();
+    return launch_whole_cohort_sum(env, iter, n_vec, idx, cc, u_dev, out_dev, sum_out_dev, n, n_jobs);
 }
 
-// What the one-limb cohort launch admits (cohort_chain_admits' contract): int_bits 33 .. 64, the chained table PRF without a fused codec,
-// and the summed compact chain's length rule on the blocks of these widths -- the chain is never cut.
-bool limb_cohort_admits(const LaunchEnv &env, int n_vec, uint64_t n, uint32_t n_jobs)
-{
-    if (!env.use_chain || env.b < 33 || env.b > 64 || env.codec || !table_prf(env) || n_vec < 1 || n_vec > kMaxLinks) return false;
-    if (n == 0 || n >= (1ull << 32) || n_jobs == 0) return false;
-    return block_of(n - 1, n, n_jobs, 128 / env.b) + 1 >= 2 * 128 * static_cast<uint64_t>(env.num_cus) * (kSmallThreads / 64);
-}
-
-// The same summed chain over whole vectors at int_bits 33 .. 64 in the one-limb layout (prf_limb_cohort_kernel): cipher indices in ONE run
-// (a round in which clients dropped out stays with the staged launches), hipErrorNotSupported = nothing launched.
 hipError_t launch_limb_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
                                   uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs)
 {
-    if (!limb_cohort_admits(env, n_vec, n, n_jobs) || !sum_out_dev || !u_dev || cc.n_layers < 1) return hipErrorNotSupported;
-    flashe_tables::CohortStreams st;
-    if (flashe_tables::cohort_streams(idx, n_vec, kMaxLinks + kMaxChains, st) != flashe_tables::kCohortStreamsOk || st.runs > 1) return hipErrorNotSupported;
-    for (int v = 0; v < n_vec; v++) if (!out_dev[v]) return hipErrorNotSupported;
-    const int n_streams = static_cast<int>(st.idx.size());      // (one run: idx and the index behind its last, n_vec + 1 streams)
-    SmallParams p = small_params_of(env, iter, n, n_jobs);
-    p.swp_prio = small_swp_prio(env, p, n_vec);
-    const uint64_t blocks = block_of(n - 1, n, n_jobs, p.m) + 1;
-    SmallChainTable tb{};
-    tb.first[0] = 0; tb.count[0] = n; tb.blk_first[0] = 0; tb.blk_count[0] = blocks;
-    tb.len[0] = static_cast<uint8_t>(n_vec);
-    for (int s = 0; s < n_streams; s++) tb.idx[s] = st.idx[s];
-    for (int l = 0; l < n_vec; l++) {
-        tb.in[l] = reinterpret_cast<const uint64_t *>(u_dev + static_cast<uint64_t>(l) * n);       // the link's draws (CohortDirect, CohortWalk)
-        tb.out[l] = out_dev[l];
-    }
-    tb.sum_out[0] = sum_out_dev;
-    const uint64_t tiles = (blocks + 127) / 128, cus = static_cast<uint64_t>(env.num_cus);
-    tb.wend[0] = tiles * static_cast<uint64_t>(n_streams);
-    const int grid = static_cast<int>(tiles < cus ? tiles : cus);
-    if (p.m == 2) hipLaunchKernelGGL((prf_limb_cohort_kernel<2>), dim3(grid), dim3(kSmallThreads), 0, env.stream, env.rk, tb, p, cc);
-    else hipLaunchKernelGGL((prf_limb_cohort_kernel<3>), dim3(grid), dim3(kSmallThreads), 0, env.stream, env.rk, tb, p, cc);
-    return hipGetLastError();
+    return launch_whole_cohort_sum(env, iter, n_vec, idx, cc, u_dev, out_dev, sum_out_dev, n, n_jobs);
 }
 
 // The SHORT compact cohort (cohort_cut.h): launch_small_cohort_sum's outputs for any n >= 1.  prf_small_cohort_kernel takes several summed
@@ -3031,31 +2984,19 @@ hipError_t launch_small_cohort_cut(const LaunchEnv &env, uint32_t iter, int n_ve
 {
     int begins[flashe_tables::kCutMaxParts + 1];
     const int parts = cohort_cut_pieces_of(env, n_vec, idx, n, n_jobs, true, 0, begins);
-    if (!parts || !sum_out_dev || !u_dev || cc.n_layers < 1) return hipErrorNotSupported;
-    for (int v = 0; v < n_vec; v++) if (!out_dev[v]) return hipErrorNotSupported;
+    if (!parts || !cohort_args_present(cc, u_dev, out_dev, n_vec, sum_out_dev != nullptr)) return hipErrorNotSupported;
     if (parts > 1 && !scratch_dev) return hipErrorInvalidValue;
     uint64_t blocks;
     const SmallParams p = small_cohort_params(env, iter, n_vec, n, n_jobs, &blocks);
     const uint64_t tiles = (blocks + 127) / 128, cus = static_cast<uint64_t>(env.num_cus);
     SmallChainTable tb{};
-    cohort_cut_table(tb, n_vec, parts, begins, idx, n, tiles);
-    for (int k = 0; k < parts; k++) {
-        tb.blk_first[k] = 0; tb.blk_count[k] = blocks;
-        tb.sum_out[k] = reinterpret_cast<uint64_t *>(parts == 1 ? sum_out_dev : scratch_dev + static_cast<uint64_t>(k) * n);
-    }
-    for (int l = 0; l < n_vec; l++) {
-        tb.in[l] = reinterpret_cast<const uint64_t *>(u_dev + static_cast<uint64_t>(l) * n);       // the link's draws (CohortDirect, CohortWalk)
-        tb.out[l] = reinterpret_cast<uint64_t *>(out_dev[l]);
-    }
+    if (!flashe_tables::cohort_cut_table(tb, n_vec, parts, begins, idx, n, tiles)) return hipErrorNotSupported;       // (never: the begins are pieces)
+    flashe_tables::cohort_chain_links(tb, n_vec, u_dev, n, out_dev);
+    flashe_tables::cohort_chain_blocks(tb, parts, blocks);
+    for (int k = 0; k < parts; k++) tb.sum_out[k] = reinterpret_cast<uint64_t *>(parts == 1 ? sum_out_dev : scratch_dev + static_cast<uint64_t>(k) * n);
     const uint64_t items = tiles * static_cast<uint64_t>(parts);
     const int grid = static_cast<int>(items < cus ? items : cus);
-    switch (env.b) {
-#define FLASHE_FIXED32(B) case B: hipLaunchKernelGGL((prf_small_cohort_kernel<B>), dim3(grid), dim3(kSmallThreads), 0, env.stream, env.rk, tb, parts, p, cc); break;
-        FLASHE_FIXED32_WIDTHS(FLASHE_FIXED32)
-#undef FLASHE_FIXED32
-    default: return hipErrorNotSupported;
-    }
-    const hipError_t e = hipGetLastError();
+    const hipError_t e = COHORT_LAUNCH_FIXED32(prf_small_cohort_kernel, tb, parts, p, cc);
     if (e != hipSuccess || parts == 1) return e;
     return launch_cohort_cut_combine_u32(env, parts, n, scratch_dev, sum_out_dev);
 }
@@ -3067,8 +3008,7 @@ hipError_t launch_small_sparse_cohort(const LaunchEnv &env, uint32_t iter, int n
                                       uint64_t u_stride, uint64_t *const *out_dev, uint64_t n, uint32_t n_jobs, const double *zzz_dev, bool zzz_f64,
                                       double z_alpha, double z_scale, double z_den, uint64_t *zeros_dev)
 {
-    if (!small_cohort_admits(env, n_vec, n, n_jobs, false) || !u_dev || cc.n_layers < 1) return hipErrorNotSupported;
-    for (int v = 0; v < n_vec; v++) if (!out_dev[v]) return hipErrorNotSupported;
+    if (!small_cohort_admits(env, n_vec, n, n_jobs, false) || !cohort_args_present(cc, u_dev, out_dev, n_vec)) return hipErrorNotSupported;
     uint64_t blocks;
     const SmallParams p = small_cohort_params(env, iter, n_vec, n, n_jobs, &blocks);
     const uint64_t waves = static_cast<uint64_t>(env.num_cus) * (kSmallThreads / 64), tiles = (blocks + 127) / 128;
@@ -3087,21 +3027,12 @@ hipError_t launch_small_sparse_cohort(const LaunchEnv &env, uint32_t iter, int n
         tb.wend[nc] = wend;
         nc++;
     }
-    for (int l = 0; l < n_vec; l++) {
-        tb.idx[l] = idx[l];
-        tb.in[l] = reinterpret_cast<const uint64_t *>(u_dev + static_cast<uint64_t>(l) * u_stride);       // the link's draws (CohortDirect, CohortWalk)
-        tb.out[l] = out_dev[l];
-    }
+    for (int l = 0; l < n_vec; l++) tb.idx[l] = idx[l];
+    flashe_tables::cohort_chain_links(tb, n_vec, u_dev, u_stride, out_dev);
     const SparseCohortTail tail{zzz_dev, zeros_dev, u_dev + n, u_stride, n, z_alpha, z_scale, z_den, zzz_f64 ? 1 : 0, n_vec};
     const uint64_t items = tiles * static_cast<uint64_t>(nc), cus = static_cast<uint64_t>(env.num_cus);
     const int grid = static_cast<int>(items < cus ? items : cus);
-    switch (env.b) {
-#define FLASHE_FIXED32(B) case B: hipLaunchKernelGGL((prf_small_sparse_cohort_kernel<B>), dim3(grid), dim3(kSmallThreads), 0, env.stream, env.rk, tb, nc, p, cc, tail); break;
-        FLASHE_FIXED32_WIDTHS(FLASHE_FIXED32)
-#undef FLASHE_FIXED32
-    default: return hipErrorNotSupported;
-    }
-    return hipGetLastError();
+    return COHORT_LAUNCH_FIXED32(prf_small_sparse_cohort_kernel, tb, nc, p, cc, tail);
 }
 
 hipError_t launch_aes_blocks(const LaunchEnv &env, uint32_t nblk, const uint32_t *in_words_dev, uint32_t *out_words_dev)

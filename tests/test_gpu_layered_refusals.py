@@ -9,9 +9,9 @@ non-zero reserved field or a count that disagrees with the table cannot be said 
 keeps each case at exactly one fault.  The arguments Engine does pass through are checked through it as well (test_through_engine).
 
 Shapes: a model of n = 13 values in three layers of 5, 0 and 8 (starts 0, 5, 5: the empty layer takes the start == end skip), engines at
-int_bits 128 (two limbs, 16-byte vectors) and 20 (one limb), the batched form at 128 with element_bits 16 in fields of 24 bits (5 values
-per element: 1 + 0 + 2 = 3 elements), cohorts of 2 clients.  The dense cohorts -- all eleven forms of the chained launch: first_idx or an
-index list, wide, compact or batched, whole or cut -- check their sources and alphas only once the launch has admitted the shape, so those
+int_bits 128 (two limbs, 16-byte vectors), 20 and -- the one-limb cohort -- 40 (one limb), the batched form at 128 with element_bits 16 in fields of 24 bits (5 values
+per element: 1 + 0 + 2 = 3 elements), cohorts of 2 clients.  The dense cohorts -- all twelve forms of the chained launch: first_idx or an
+index list, wide, compact, one-limb or batched, whole or cut -- check their sources and alphas only once the launch has admitted the shape, so those
 cases run at the smallest size it admits on one compute unit (the cut forms: n = 13 as it is).  The prepared cohorts -- all eight forms of
 the online launch: a draw buffer or a Philox / PCG64 segment table, wide, compact or batched -- have no admission, so every case runs at
 n = 13; a form that draws inside the launch is given ONE segment tiling the clients' 2 n values, and every refusal leaves it as it was.
@@ -227,6 +227,8 @@ EPS = [
        ok=ENOTSUP, cohort=True),
     EP("quantize_encrypt_cohort_u32_dev", "iter first_idx n_clients n n_jobs layers:T n_layers src:P sdt:I32 eb u cts:P sum", "S", widths=(20,),
        ok=ENOTSUP, cohort=True),
+    EP("quantize_encrypt_cohort_u64_dev", "iter first_idx n_clients n n_jobs layers:T n_layers src:P sdt:I32 eb u cts:P sum", "S", widths=(40,),
+       ok=ENOTSUP, cohort=True),
     EP("quantize_batch_encrypt_cohort_dev", "iter first_idx n_clients n_values n_elems n_jobs layers:T n_layers src:P sdt:I32 eb fb u cts:P sum dmask", "S",
        widths=(128,), ok=ENOTSUP, cohort=True),
     # the other forms of the same launch: the cipher indices as a list (cidx in place of first_idx), the cut chain (a trailing scratch; it
@@ -275,7 +277,7 @@ CODEC_FRONT = {"quantize_encrypt_model_dev", "quantize_encrypt_prepared_model_de
                "quantize_encrypt_prepared_tensors_dev"}
 BATCH_FRONT = {"quantize_batch_model_dev", "quantize_batch_encrypt_prepared_model_dev", "quantize_batch_tensors_dev",
                "quantize_batch_encrypt_prepared_tensors_dev"}
-DENSE = {"quantize_encrypt_cohort_dev", "quantize_encrypt_cohort_u32_dev", "quantize_batch_encrypt_cohort_dev",
+DENSE = {"quantize_encrypt_cohort_dev", "quantize_encrypt_cohort_u32_dev", "quantize_encrypt_cohort_u64_dev", "quantize_batch_encrypt_cohort_dev",
          "quantize_encrypt_cohort_cut_dev", "quantize_encrypt_cohort_cut_u32_dev",
          "quantize_encrypt_cohort_runs_dev", "quantize_encrypt_cohort_runs_u32_dev", "quantize_batch_encrypt_cohort_runs_dev",
          "quantize_encrypt_cohort_cut_runs_dev", "quantize_encrypt_cohort_cut_runs_u32_dev", "quantize_batch_encrypt_cohort_cut_runs_dev"}
@@ -387,6 +389,10 @@ def cases(ep, bits):
         if u32:
             bad += [("ct + 2", item("cts", 0, lambda a, r: a["cts"][0] + 2), "client 0: the ciphertext is not 4-byte aligned"),
                     ("sum + 2", off("sum", 2), "sum_out_dev must be 4-byte aligned"), ("n_jobs 0", put("n_jobs", 0), "n_jobs must be >= 1")]
+        elif name.endswith("u64_dev"):
+            # (the one-limb layout: uint64 vectors of a one-limb ctx, cohort_check_outs<uint64_t> without a mask)
+            bad += [("ct + 4", item("cts", 0, lambda a, r: a["cts"][0] + 4), A8), ("sum + 4", off("sum", 4), "sum_out_dev must be aligned like a ciphertext vector"),
+                    ("n_jobs 0", put("n_jobs", 0), "n_jobs must be >= 1")]
         else:
             bad += [("ct + 8", item("cts", 0, lambda a, r: a["cts"][0] + 8), A16), ("sum + 8", off("sum", 8), "sum_out_dev must be aligned like a ciphertext vector"),
                     ("dmask + 8", off("dmask", 8), "dmask_dev must be 16-byte aligned and apart from the sum"),
@@ -570,10 +576,11 @@ def test_refusals_leave_the_ctx_as_it_was(rigs, bits):
 
 def admitted_n(ep, bits, cus=1):
     """The smallest n the chained launch of the dense cohort `ep` takes with one job on `cus` compute units (kernels.hip:
-    cohort_chain_admits, small_cohort_admits: two whole tiles, or 2 x 128 AES blocks, for each of the 16 waves of a workgroup)."""
+    cohort_chain_admits, small_cohort_admits, limb_cohort_admits: two whole tiles, or 2 x 128 AES blocks of 128 // int_bits values, for each of
+    the 16 waves of a workgroup)."""
     if "_cut_" in ep.name:
         return N                             # (the cut chain has no length rule)
-    if ep.name.endswith("u32_dev"):
+    if ep.name.endswith(("u32_dev", "u64_dev")):
         return (2 * 128 * cus * 16 - 1) * (128 // bits) + 1
     return ((2 * cus * 16 - 1) * 256 + 1) * (bits // FB if "batch" in ep.name else 1)
 
