@@ -23,7 +23,8 @@ which this example checks.
                streams, whose decrypt mask is that of the telescoped index lists; the new global model is what the present clients'
                own steps and a decrypt told who uploaded (set_idx_list(present)) give, which this example checks; with --compact at
                --bits 16 / 20 / 23 / 24 / 32 the gapped round is one chained launch too (`upload.path` is "cohort-chain"), without a mask:
-               the decrypt of the sum takes the telescoped lists
+               the decrypt of the sum takes the telescoped lists; and so it is with --one-limb at --bits 33 .. 64
+               (--bits 40 --one-limb --drop 2,7: "cohort-chain" over eight clients' eleven PRF streams, uint64 ciphertexts)
   --cut        many clients with a SMALL model: forty LeNet-5s of 61,706 parameters, far below the length the summed chain takes uncut.
                FlasheCohort(cut=True) cuts the chain into runs of consecutive clients and adds the runs' partial sums and decrypt masks
                in one combine pass (`upload.path` is "cut-chain"): two launches instead of forty quantise passes, forty plaintext

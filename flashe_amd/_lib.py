@@ -99,6 +99,7 @@ COHORT_LAUNCHES = (
     "flashe_quantize_encrypt_cohort_cut_runs_dev", "flashe_quantize_encrypt_cohort_cut_runs_u32_dev",
     "flashe_quantize_batch_encrypt_cohort_dev", "flashe_quantize_batch_encrypt_cohort_runs_dev",
     "flashe_quantize_batch_encrypt_cohort_cut_runs_dev", "flashe_quantize_encrypt_cohort_u64_dev",
+    "flashe_quantize_encrypt_cohort_runs_u64_dev",
 )
 
 

@@ -1352,7 +1352,7 @@ def cohort_cut_pieces(idxs, items, cu_count):
 
 def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, mask="double", num_clients=None, precompute=False, chain=True,
                 location_masks=False, compact=False, n_jobs=None, cohort_masks=False, present=None, compact_runs=False, cut=False, cut_any=False,
-                one_limb=False):
+                one_limb=False, limb_runs=False):
     """The engine-free part of FlasheCohort.quantize_encrypt: checks that the clients' Weights describe one model (the same layer names
     in the same walking order with the same shapes: ValueError naming the client and the layer otherwise; a sparse upload -- a 'zzz'
     layer or location masks -- is a TypeError), lays out the shared layer table and the client-major draws, and picks the path:
@@ -1402,8 +1402,11 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
     layout replaces the rule "int_bits <= 64" by the compact chain's: "cohort-chain" (uint64 ciphertexts and their sum from the floats, no
     decrypt mask) for a double-mask, un-batched cohort of at most 128 clients in ONE run of consecutive clients whose model has at least
     compact_cohort_admission_length(cu_count, int_bits, n_jobs) values and fewer than 2^32, every layer float64 for all clients or for
-    none; a shorter model stays "staged-chain" (the cut launch does not take these widths), and so does a round in which clients dropped
-    out in several runs.  Other widths and one_limb=False: every plan is what it is without the keyword.
+    none; a shorter model stays "staged-chain" (the cut launch does not take these widths).  A round in which clients dropped out in
+    several runs depends on limb_runs, whether the engine has the gapped one-limb launch (flashe_quantize_encrypt_cohort_runs_u64_dev):
+    False (the default) plans it "staged-chain" -- the one-limb chain then takes one run only --, True lets it through to the 144-stream
+    rule and the mixed-float64 rule like a compact cohort with compact_runs=True.  Other widths and one_limb=False: every plan is what it
+    is without the keywords.
     Touches no device.  The library's own answer stays the last word: a "cohort-chain" or "cut-chain" plan it declines runs
     "staged-chain", a "prepared-cohort" one "prepared-staged"."""
     if len(weights_list) < 1:
@@ -1461,7 +1464,7 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
         path, reason, short = STAGED_CHAIN, "the vector does not fill the chip uncut", bool(compact) and 1 <= n < 2 ** 32
     elif not compact and not limb and (n_elems < cohort_admission_length(cu_count) or n_elems > 2 ** 32):
         path, reason, short = STAGED_CHAIN, "the vector does not fill the chip uncut", 1 <= n_elems < cohort_admission_length(cu_count)
-    elif runs > 1 and limb:
+    elif runs > 1 and limb and not limb_runs:
         path, reason = STAGED_CHAIN, f"clients dropped out ({runs} runs of indices): the one-limb chain takes one run of consecutive clients"
     elif runs > 1 and compact and not compact_runs:
         path, reason = STAGED_CHAIN, f"clients dropped out ({runs} runs of indices): the compact chain takes one run of consecutive clients"
@@ -1537,7 +1540,7 @@ class FlasheCohort(object):
     int_bits 64 -- chain from the floats too (flashe_quantize_encrypt_cohort_u64_dev: 20 bytes moved per value and client instead of 36).
     The ciphertexts and the sum are the ordinary one-limb DeviceVectors of these widths whatever path ran; no decrypt mask is kept, and
     decrypt_unquantize() decrypts the sum with the telescoped lists.  A model shorter than compact_cohort_admission_length(...), a batched
-    job, the single mask and a round in which clients dropped out in several runs stay "staged-chain".
+    job and the single mask stay "staged-chain".
     cut=True (opt-in, like compact): a model too SHORT for the uncut chain -- fewer than cohort_admission_length(cu_count) values, or
     compact_cohort_admission_length(...) in the compact layout: many clients with a small model -- runs "cut-chain" instead of
     "staged-chain": the summed chain cut into runs of consecutive clients and one combine pass (flashe_quantize_encrypt_cohort_cut_dev /
@@ -1554,8 +1557,9 @@ class FlasheCohort(object):
     at int_bits > 64 still one chained launch (flashe_quantize_encrypt_cohort_runs_dev / flashe_quantize_batch_encrypt_cohort_runs_dev)
     over present + runs PRF streams that writes the decrypt mask of the telescoped index lists, so decrypt_unquantize() of that round
     stays one pass.  A gapped compact cohort at int_bits 16 / 20 / 23 / 24 / 32 is one chained launch too
-    (flashe_quantize_encrypt_cohort_runs_u32_dev, the same streams), on an engine that has it; no mask is kept there, and
-    decrypt_unquantize() decrypts the sum with the telescoped lists.
+    (flashe_quantize_encrypt_cohort_runs_u32_dev, the same streams), on an engine that has it, and so is a gapped one_limb=True cohort
+    at int_bits 33 .. 64 (flashe_quantize_encrypt_cohort_runs_u64_dev); no mask is kept there, and decrypt_unquantize() decrypts the sum
+    with the telescoped lists.
     A precompute job ("precompute": {"enable": true}) calls prepare_encrypt() in idle time: the next round's masks of all clients as one
     chain of n_local + 1 streams, held by the cohort; the next quantize_encrypt is then ONE online launch with no AES ("prepared-cohort")
     at any int_bits, batched or not, compact or not.  Without that call the clients' own masks run "per-client" as before.  Un-batched and
@@ -1635,7 +1639,7 @@ class FlasheCohort(object):
                            cut=self.cut and hasattr(ld.cipher.engine, "quantize_encrypt_cohort_cut_u32_dev" if self.compact
                                                     else "quantize_encrypt_cohort_cut_dev"),
                            cut_any=self.cut_any and all(hasattr(ld.cipher.engine, name) for name in self._cut_any_methods()),
-                           one_limb=self.one_limb)
+                           one_limb=self.one_limb, limb_runs=hasattr(ld.cipher.engine, "quantize_encrypt_cohort_runs_u64_dev"))
 
     def _cut_any_methods(self):
         """The engine methods cut="any" needs for this cohort's layout."""
@@ -1902,12 +1906,12 @@ class FlasheCohort(object):
         idxs = [self.first_idx + p for p in plan.present]
         jobs, batch = _cipher_mod.N_JOBS, bool(ld.batch) and not narrow
         # the form: the cipher indices as a list for a gapped or batched cut and for a call with `present` (one run of a compact cohort
-        # without the gapped compact launch: plan_cohort sends a gapped one to the staged form), else the first index.  One limb
-        # (int_bits 33 .. 64): one run of consecutive clients from its first index, never cut
+        # or one-limb cohort without its gapped launch: plan_cohort sends a gapped one to the staged form), else the first index.  One
+        # limb (int_bits 33 .. 64): never cut
         if self.one_limb:
-            cut = by_idx = False
-        by_list = (plan.runs > 1 or bool(ld.batch)) if cut else (by_idx and (not self.compact or hasattr(eng, "quantize_encrypt_cohort_runs_u32_dev")))
+            cut = False
         layout = "_u32" if self.compact else "_u64" if self.one_limb else ""
+        by_list = (plan.runs > 1 or bool(ld.batch)) if cut else (by_idx and (not narrow or hasattr(eng, f"quantize_encrypt_cohort_runs{layout}_dev")))
         name = f"quantize_{'batch_' if batch else ''}encrypt_cohort{'_cut' if cut else ''}{'_runs' if by_list else ''}{layout}_dev"
         scratch = ()
         if cut:

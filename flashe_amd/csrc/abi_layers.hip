@@ -669,7 +669,7 @@ static int cohort_check_scratch(flashe_ctx *ctx, int parts, int n_clients, const
     return FLASHE_OK;
 }
 
-// What tells the twelve chained cohort entry points apart, besides the element type T of their vectors (uint64_t: the wide two-limb
+// What tells the thirteen chained cohort entry points apart, besides the element type T of their vectors (uint64_t: the wide two-limb
 // layout, or the one-limb layout of the `one_limb` form; uint32_t: the compact one, no decrypt mask).  `what` names the launch in a refusal.
 struct CohortForm {
     const char *who, *what;
@@ -801,9 +801,9 @@ int flashe_quantize_batch_encrypt_cohort_dev(flashe_ctx *ctx, uint32_t iter, uin
         });
 }
 
-// ---- the same three launches for a round in which clients DROPPED OUT: the cipher indices of the clients that report, any strictly
+// ---- the same four launches for a round in which clients DROPPED OUT: the cipher indices of the clients that report, any strictly
 // ascending list (one run: the launches above, bit for bit; several runs: prf_chain_cohort_runs_kernel / prf_small_cohort_runs_kernel /
-// prf_chain_cohort_batch_runs_kernel) ----
+// prf_limb_cohort_runs_kernel / prf_chain_cohort_batch_runs_kernel) ----
 int flashe_quantize_encrypt_cohort_runs_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n, uint32_t n_jobs,
                                             const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
                                             int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev, uint64_t *dmask_dev)
@@ -825,6 +825,19 @@ int flashe_quantize_encrypt_cohort_runs_u32_dev(flashe_ctx *ctx, uint32_t iter, 
         ctx, {"flashe_quantize_encrypt_cohort_runs_u32_dev", "compact cohort", true, false, false}, 0, idx, n_clients, n, n, n_jobs, layers, n_layers, src_dev,
         src_dtype, element_bits, 0, u_dev, ct_dev, sum_out_dev, nullptr, nullptr, [&](const uint32_t *ids, const CohortCodec &cc, const CohortBatch *) {
             return launch_small_cohort_sum(ctx->env, iter, n_clients, ids, cc, u_dev, ct_dev, sum_out_dev, n, n_jobs);
+        });
+}
+
+// the one-limb layout at int_bits 33 .. 64 (several runs: prf_limb_cohort_runs_kernel): uint64 ciphertexts and their uint64 sum, no decrypt mask
+int flashe_quantize_encrypt_cohort_runs_u64_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                                const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                                int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev)
+{
+    CHECK_CTX(ctx);
+    return quantize_encrypt_cohort<uint64_t>(
+        ctx, {"flashe_quantize_encrypt_cohort_runs_u64_dev", "one-limb cohort", true, false, false, true}, 0, idx, n_clients, n, n, n_jobs, layers, n_layers, src_dev,
+        src_dtype, element_bits, 0, u_dev, ct_dev, sum_out_dev, nullptr, nullptr, [&](const uint32_t *ids, const CohortCodec &cc, const CohortBatch *) {
+            return launch_limb_cohort_sum(ctx->env, iter, n_clients, ids, cc, u_dev, ct_dev, sum_out_dev, n, n_jobs);
         });
 }
 

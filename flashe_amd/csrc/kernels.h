@@ -132,8 +132,8 @@ hipError_t launch_small_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_ve
 // (the precondition and the length rule are each stated once in kernels.hip; 0 < n < 2^32, n_jobs != 0).
 bool limb_cohort_admits(const LaunchEnv &env, int n_vec, uint64_t n, uint32_t n_jobs);
 // The same cohort at int_bits 33 .. 64 in the one-limb layout (prf_limb_cohort_kernel<2 | 3>): uint64 ciphertexts (8-byte aligned) and
-// their uint64 sum from the floats, no decrypt mask.  Admitted where limb_cohort_admits says and idx is ONE run of consecutive indices
-// below 2^32 - 1 (cohort_streams.h).  hipErrorNotSupported: nothing launched.
+// their uint64 sum from the floats, no decrypt mask.  Admitted where limb_cohort_admits says, for strictly ascending idx below 2^32 - 1
+// whose streams fit the table (cohort_streams.h; several runs: prf_limb_cohort_runs_kernel<2 | 3>).  hipErrorNotSupported: nothing launched.
 hipError_t launch_limb_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
                                   uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs);
 // The sparse job's cohort at the same widths (prf_small_sparse_cohort_kernel): out_dev[c][k] = SINGLE-mask encrypt (idx[c]; any indices) of the

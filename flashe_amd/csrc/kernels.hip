@@ -1521,7 +1521,7 @@ __global__ __launch_bounds__(kSmallThreads) void prf_small_sparse_cohort_kernel(
 // block quantises its M values of client `link` BEFORE that stream's AES rounds -- with M = 2 (int_bits 43 .. 64) or 3 (33 .. 42) whole
 // uint64 plaintexts per block and the width itself at run time (SmallParams, as prf_small_chain_kernel<PAIR, uint64_t, 0> takes it).  Per
 // value and client the launch reads 4 + 8 bytes and writes 8, against 36 through a quantise pass and the summed one-limb encrypt.
-// A body of its own: the chained kernels of prf_small_chain_body.inc keep their code objects.
+// A body of its own (prf_limb_cohort_body.inc): the chained kernels of prf_small_chain_body.inc keep their code objects.
 
 // bits [b t, b t + 64) of S for the slots of these widths, unmasked (t == 1 straddles the halves below b = 64, t == 2 lies in the high
 // half: 2 b >= 66); no shift by 64 is formed
@@ -1551,104 +1551,21 @@ __device__ __forceinline__ void limb_put(uint64_t *__restrict__ q, const uint64_
 template <int M>
 __global__ __launch_bounds__(kSmallThreads) void prf_limb_cohort_kernel(const RoundKeys rk, const SmallChainTable tb, const SmallParams p, const CohortCodec cc)
 {
-    static_assert(M == 2 || M == 3, "int_bits 43 .. 64 or 33 .. 42");
-    constexpr uint32_t WAVES = kSmallThreads / 64;
-    __shared__ uint32_t tab[kTabWords];
-    __shared__ uint32_t scratch[WAVES * 256 + 8];
-    __shared__ __attribute__((aligned(16))) uint32_t pre_lds[(kMaxLinks + kMaxChains) * 4];
-    const uint32_t iter = p.iter + p.te0[kIterShiftWord];
-    fill_tables(tab, p.te0);
-    const LaneRegs lr = lane_regs(tab);
-    const int n_streams = tb.len[0] + 1;
-    for (int s = threadIdx.x; s < n_streams; s += kSmallThreads) {
-        const CtrPrefix c = ctr_prefix(rk, lr, iter, tb.idx[s], 0u);              // n < 2^32 (host-checked): the high counter word is 0
-        *reinterpret_cast<uint4 *>(pre_lds + 4 * s) = make_uint4(c.u[0], c.u[1], c.u[2], c.u[3]);
-    }
-    __syncthreads();
-    const uint64_t n = p.n, J = p.n_jobs, d = n / J, r = n % J, blk_count = tb.blk_count[0];
-    const uint32_t nb1_32 = static_cast<uint32_t>((d + 1 + M - 1) / M), nb0_32 = static_cast<uint32_t>(d ? (d + M - 1) / M : 0);
-    const uint32_t d32 = static_cast<uint32_t>(d), r32 = static_cast<uint32_t>(r);
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
-    uint32_t *row0 = scratch + wave * 256;
-    const u128 top = (static_cast<u128>(p.top_hi) << 64) | p.top_lo;
-    uint64_t *const sum = tb.sum_out[0];
-    // this workgroup's share of the vector's tiles, dealt to its waves in turn
-    const uint64_t T = (blk_count + 127u) / 128u, G = gridDim.x, g = blockIdx.x;
-    const uint64_t t_lo = T / G * g + (T % G) * g / G, t_hi = T / G * (g + 1) + (T % G) * (g + 1) / G;
-    for (uint64_t q = t_lo + wave; q < t_hi; q += WAVES) {
-        const uint64_t Bw = q * 128u;
-        const bool vA = Bw + lane < blk_count, vB = Bw + 64u + lane < blk_count;
-        uint64_t j0A = 0, j0B = 0;
-        int cntA = 0, cntB = 0;
-        uint32_t ctrA = 0, ctrB = 0;
-        small_block_params(static_cast<uint32_t>(vA ? Bw + lane : 0), nb1_32, nb0_32, d32, r32, M, p, &j0A, &cntA, &ctrA);
-        small_block_params(static_cast<uint32_t>(vB ? Bw + 64u + lane : 0), nb1_32, nb0_32, d32, r32, M, p, &j0B, &cntB, &ctrB);
-        const CtrVar xA = ctr_var(rk, lr, ctrA), xB = ctr_var(rk, lr, ctrB);
-        // a half tile of 64 whole blocks is one contiguous run of 64 M elements; the table row that holds all of it is found once, with
-        // scalar loads (CohortDirect).  Every other half -- a chunk end with a partial block, the range end, the last partial tile, a half
-        // that straddles a layer row -- walks (small_walk with CohortWalk) and keeps its sums in memory
-        const uint64_t e0A = uniform64(j0A), e0B = uniform64(j0B);
-        bool fastA = __ballot(vA && cntA == M) == ~0ull && e0A + 64u * M <= n;
-        bool fastB = __ballot(vB && cntB == M) == ~0ull && e0B + 64u * M <= n;
-        int layA = -1, layB = -1;
-        if (fastA) {
-            layA = cohort_layer_of(cc, e0A);
-            if (layA + 1 < cc.n_layers && *FLASHE_CONSTANT(const uint64_t, &cc.layers[layA + 1].start) < e0A + 64u * M) layA = -1;
-        }
-        if (fastB) {
-            layB = cohort_layer_of(cc, e0B);
-            if (layB + 1 < cc.n_layers && *FLASHE_CONSTANT(const uint64_t, &cc.layers[layB + 1].start) < e0B + 64u * M) layB = -1;
-        }
-        fastA = fastA && layA >= 0;
-        fastB = fastB && layB >= 0;
-        const CohortDirect csrc{cc, tb.in, 0, {layA, layB}};
-        u128 prevA = 0, prevB = 0;
-        uint64_t accA[M], accB[M];                                 // the whole blocks' running sums, unmasked: sums mod 2^64 agree with sums mod 2^b
-#pragma unroll
-        for (int t = 0; t < M; t++) { accA[t] = 0ull; accB[t] = 0ull; }
-        for (int c = 0; c < n_streams; c++) {
-            const CtrPrefix pre = load_prefix(pre_lds, c);
-            const int link = c - 1;                                // the output this stream completes
-            uint64_t ptA[M], ptB[M];
-#pragma unroll
-            for (int t = 0; t < M; t++) { ptA[t] = 0ull; ptB[t] = 0ull; }
-            if (link >= 0 && fastA) csrc.template words<M>(link, j0A, 0, ptA);
-            if (link >= 0 && fastB) csrc.template words<M>(link, j0B, 1, ptB);
-            uint32_t s[2][4];
-            ctr_round1(pre, xA, s[0]);
-            ctr_round1(pre, xB, s[1]);
-            aes256_rounds<2, 2>(rk, lr, s, p.swp_prio != 0);
-            const u128 SA = words_to_u128(s[0]), SB = words_to_u128(s[1]);
-            if (link >= 0) {
-                uint64_t *out = tb.out[link];
-                const CohortWalk cw{cc, tb.in[link], link};
-                if (fastA) {
-                    uint64_t v[M];
-#pragma unroll
-                    for (int t = 0; t < M; t++) {
-                        v[t] = ptA[t] + limb_slot(prevA, t, p.b) - limb_slot(SA, t, p.b);
-                        accA[t] += v[t];
-                    }
-                    limb_put<M, true>(out + j0A, v, p.mask_lo);
-                } else
-                    small_walk(row0, lane, vA, cntA, j0A, slot_diff(prevA, SA, top, p.b), static_cast<const uint64_t *>(nullptr), out, 0, n, p, sum, link == 0, &cw);
-                if (fastB) {
-                    uint64_t v[M];
-#pragma unroll
-                    for (int t = 0; t < M; t++) {
-                        v[t] = ptB[t] + limb_slot(prevB, t, p.b) - limb_slot(SB, t, p.b);
-                        accB[t] += v[t];
-                    }
-                    limb_put<M, true>(out + j0B, v, p.mask_lo);
-                } else
-                    small_walk(row0, lane, vB, cntB, j0B, slot_diff(prevB, SB, top, p.b), static_cast<const uint64_t *>(nullptr), out, 0, n, p, sum, link == 0, &cw);
-            }
-            prevA = SA; prevB = SB;
-        }
-        if (fastA) limb_put<M, false>(sum + j0A, accA, p.mask_lo);
-        if (fastB) limb_put<M, false>(sum + j0B, accB, p.mask_lo);
-    }
+    constexpr bool GAPS = false;
+    const CohortGaps cg{};
+#include "prf_limb_cohort_body.inc"
+}
+
+// GAPS: the same cohort for cipher indices in SEVERAL runs -- a round in which clients dropped out (cohort_streams.h; GAPS in
+// prf_limb_cohort_body.inc).  The one chain's streams are the |P| + runs of tb.idx; cg tells which of them complete an output, and the launch
+// still writes every present client's uint64 ciphertext and their sum (the decrypt takes the telescoped lists; no mask at these widths).
+// A separate kernel: the one-run launches keep their code objects.
+template <int M>
+__global__ __launch_bounds__(kSmallThreads) void prf_limb_cohort_runs_kernel(const RoundKeys rk, const SmallChainTable tb, const SmallParams p, const CohortCodec cc,
+                                                                              const CohortGaps cg)
+{
+    constexpr bool GAPS = true;
+#include "prf_limb_cohort_body.inc"
 }
 
 
@@ -2933,8 +2850,8 @@ template <class F> static hipError_t cohort_fixed32_launch(int b, F &&launch)
 // summed chain of launch_small_chains -- a compiled-in width, one uncut chain, enough AES blocks for the paired kernel -- and
 // launch_prf_cohort_sum's contract: any strictly ascending idx (one run launches the kernel it always has with the table it always had,
 // several runs prf_small_cohort_runs_kernel over |P| + runs streams), hipErrorNotSupported = nothing launched.
-// The same chain at int_bits 33 .. 64 in the one-limb layout (E = uint64_t, prf_limb_cohort_kernel): cipher indices in ONE run only (a
-// round in which clients dropped out stays with the staged launches).
+// The same chain at int_bits 33 .. 64 in the one-limb layout (E = uint64_t): the same contract -- one run launches prf_limb_cohort_kernel
+// with the table it always had, several runs prf_limb_cohort_runs_kernel over |P| + runs streams.
 template <class E>
 static hipError_t launch_whole_cohort_sum(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
                                           E *const *out_dev, E *sum_out_dev, uint64_t n, uint32_t n_jobs)
@@ -2943,7 +2860,7 @@ static hipError_t launch_whole_cohort_sum(const LaunchEnv &env, uint32_t iter, i
     const bool admitted = compact ? small_cohort_admits(env, n_vec, n, n_jobs, true) : limb_cohort_admits(env, n_vec, n, n_jobs);
     if (!admitted || !cohort_args_present(cc, u_dev, out_dev, n_vec, sum_out_dev != nullptr)) return hipErrorNotSupported;
     flashe_tables::CohortStreams st;            // (one run: idx and the index behind its last, n_vec + 1 streams)
-    if (flashe_tables::cohort_streams(idx, n_vec, kMaxLinks + kMaxChains, st) != flashe_tables::kCohortStreamsOk || (!compact && st.runs > 1)) return hipErrorNotSupported;
+    if (flashe_tables::cohort_streams(idx, n_vec, kMaxLinks + kMaxChains, st) != flashe_tables::kCohortStreamsOk) return hipErrorNotSupported;
     uint64_t blocks;
     const SmallParams p = small_cohort_params(env, iter, n_vec, n, n_jobs, &blocks, compact);
     const uint64_t tiles = (blocks + 127) / 128, cus = static_cast<uint64_t>(env.num_cus);
@@ -2952,7 +2869,11 @@ static hipError_t launch_whole_cohort_sum(const LaunchEnv &env, uint32_t iter, i
     flashe_tables::cohort_chain_blocks(tb, 1, blocks);
     const int grid = static_cast<int>(tiles < cus ? tiles : cus);
     if constexpr (!compact) {
-        if (p.m == 2) hipLaunchKernelGGL((prf_limb_cohort_kernel<2>), dim3(grid), dim3(kSmallThreads), 0, env.stream, env.rk, tb, p, cc);
+        if (st.runs > 1) {
+            const CohortGaps cg = cohort_gaps_of(st);
+            if (p.m == 2) hipLaunchKernelGGL((prf_limb_cohort_runs_kernel<2>), dim3(grid), dim3(kSmallThreads), 0, env.stream, env.rk, tb, p, cc, cg);
+            else hipLaunchKernelGGL((prf_limb_cohort_runs_kernel<3>), dim3(grid), dim3(kSmallThreads), 0, env.stream, env.rk, tb, p, cc, cg);
+        } else if (p.m == 2) hipLaunchKernelGGL((prf_limb_cohort_kernel<2>), dim3(grid), dim3(kSmallThreads), 0, env.stream, env.rk, tb, p, cc);
         else hipLaunchKernelGGL((prf_limb_cohort_kernel<3>), dim3(grid), dim3(kSmallThreads), 0, env.stream, env.rk, tb, p, cc);
         return hipGetLastError();
     } else if (st.runs > 1) {

@@ -796,6 +796,13 @@ class Engine:
         False -- nothing was launched -- when the library declines the shape (FLASHE_ENOTSUP: also more than 144 streams), True otherwise."""
         return self._cohort_launch("flashe_quantize_encrypt_cohort_runs_u32_dev", it, idx, (n,), n_jobs, layers, srcs, dtypes, (element_bits,), u, cts, sum_out)
 
+    def quantize_encrypt_cohort_runs_u64_dev(self, it, idx, n, n_jobs, layers, srcs, dtypes, element_bits, u, cts, sum_out):
+        """quantize_encrypt_cohort_u64_dev for a round in which clients dropped out (flashe_quantize_encrypt_cohort_runs_u64_dev, int_bits
+        33 .. 64): idx as in quantize_encrypt_cohort_runs_dev, cts and sum_out uint64 vectors of n elements, 8-byte aligned, no decrypt mask
+        (decrypt the sum with telescope(idx)).  One run of consecutive indices is quantize_encrypt_cohort_u64_dev bit for bit.  Returns
+        False -- nothing was launched -- when the library declines the shape (FLASHE_ENOTSUP: also more than 144 streams), True otherwise."""
+        return self._cohort_launch("flashe_quantize_encrypt_cohort_runs_u64_dev", it, idx, (n,), n_jobs, layers, srcs, dtypes, (element_bits,), u, cts, sum_out)
+
     def quantize_batch_encrypt_cohort_runs_dev(self, it, idx, n_values, n_elems, n_jobs, layers, srcs, dtypes, element_bits, field_bits, u, cts,
                                                sum_out, dmask=None):
         """quantize_batch_encrypt_cohort_dev with the cipher indices of the clients that report

@@ -96,7 +96,8 @@ typedef struct flashe_ctx flashe_ctx;
  *      generated inside the launch: no draw buffer) and flashe_quantize_batch_combine_cohort_philox_dev (the same for a batched job);
  *      flashe_quantize_combine_cohort_pcg64_dev / flashe_quantize_combine_cohort_pcg64_u32_dev (the un-batched form for the streams of
  *      np.random.PCG64 / PCG64DXSM, np.random.default_rng's generator) with flashe_pcg64_cohort_grid + flashe_pcg64_cohort_lane_draws;
- *      flashe_quantize_encrypt_cohort_u64_dev (the cohort's chained launch in the one-limb layout, int_bits 33 .. 64) */
+ *      flashe_quantize_encrypt_cohort_u64_dev (the cohort's chained launch in the one-limb layout, int_bits 33 .. 64);
+ *      flashe_quantize_encrypt_cohort_runs_u64_dev (the same launch for a round in which clients dropped out) */
 #define FLASHE_ABI_VERSION 4
 int flashe_abi_version(void);
 int flashe_device_count(int *count);
@@ -842,6 +843,21 @@ int flashe_quantize_batch_encrypt_cohort_runs_dev(flashe_ctx *ctx, uint32_t iter
 int flashe_quantize_encrypt_cohort_runs_u32_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n, uint32_t n_jobs,
                                                 const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
                                                 int element_bits, const double *u_dev, uint32_t *const *ct_dev, uint32_t *sum_out_dev);
+/* The one-limb cohort for a round in which clients DROPPED OUT (new), jzf_flashe.py:349-367, jzf_aggregator.py:424-430:
+ * flashe_quantize_encrypt_cohort_u64_dev with the cipher indices idx of the n_clients clients that report, strictly ascending, in place
+ * of first_idx; everything indexed by client counts the clients of idx, as in flashe_quantize_encrypt_cohort_runs_dev.  ONE chained launch
+ * over the |P| + runs streams of S = { s : s in P or s - 1 in P } writes ct_dev[c] (uint64, n elements, 8-byte aligned: the values of
+ * flashe_quantize_encrypt_tensors_dev with cipher index idx[c]) and sum_out_dev = sum_c ct_dev[c] mod 2^b; no decrypt mask at these
+ * widths -- decrypt the sum with flashe_telescope(idx).  One run of consecutive indices launches exactly what
+ * flashe_quantize_encrypt_cohort_u64_dev launches and writes its bytes.
+ * FLASHE_EINVAL: idx NULL, not strictly ascending (unsorted, duplicates) or holding 2^32 - 1, and the argument errors of
+ * flashe_quantize_encrypt_cohort_u64_dev.  FLASHE_ENOTSUP -- nothing launched, every output untouched -- outside that function's
+ * admission with n_clients = |P| (int_bits 33 .. 64, the length rule), and when |P| + runs exceeds the 144 streams one launch holds; the
+ * caller then quantises per client and uses flashe_encrypt_batch_sum_dev, which takes any indices.  The table uploads synchronise; not
+ * capturable. */
+int flashe_quantize_encrypt_cohort_runs_u64_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                                const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                                int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev);
 /* A SHORT cohort in which clients DROPPED OUT, and a short BATCHED cohort (new), jzf_flashe.py:349-367, jzf_aggregator.py:424-430: a gap in
  * the cipher indices is a cut the round imposes -- a run of consecutive present clients a .. b is by itself a chain over streams
  * a .. b + 1 --, and the pieces' masks term(b_p + 1) - term(a_p) add up to the decrypt mask of the telescoped lists whether the cuts come
