@@ -31,7 +31,10 @@ which this example checks.
                vectors and a batch encrypt; with --compact at --bits 16 / 20 / 23 / 24 / 32 the same in the uint32 layout.  Without
                --cut such a cohort runs "staged-chain".  With --drop 2,7 (a gap in the cipher indices is a cut the round imposes) or
                with --bits 120 --batch (five 22-bit fields per element) the example asks for FlasheCohort(cut="any"), which takes
-               gapped and batched short cohorts through the cut launch too and keeps the decrypt mask of the telescoped lists
+               gapped and batched short cohorts through the cut launch too and keeps the decrypt mask of the telescoped lists.
+               --bits 40 --one-limb --cut [--drop 2,7]: the one-limb layout's cut launch (uint64 ciphertexts, (piece, tile) items over
+               the chip's waves and a combine pass over the pieces' uint64 sums; one launch form for one run of clients or several, no
+               mask kept); without --cut these forty models run "staged-chain" at these widths
   --rng philox the stochastic-rounding draws come from one np.random.Generator per client instead of NumPy's global stream
                (quantize_encrypt(rng=[...])): counter-based Philox generators, whose draws for the whole cohort are ONE asynchronous
                launch on the device (models of 65,536 values or more: this example's hold 8,036,426) and whose advanced states come back

@@ -91,7 +91,8 @@ class FlasheError(RuntimeError):
 
 # The chained cohort launches (abi_layers.hip, quantize_encrypt_cohort).  What a name says: _runs_ = the cipher indices as a list in place of
 # first_idx, batch = n_values and n_elems in place of n and a field_bits, _u32_ = the compact layout without a decrypt mask, _u64_ = the
-# one-limb layout (int_bits 33 .. 64) without one, _cut_ = a trailing scratch.
+# one-limb layout (int_bits 33 .. 64) without one, _cut_ = a trailing scratch (_cut_u64_: the one-limb cut launch has the one form, which
+# takes the list).
 COHORT_LAUNCHES = (
     "flashe_quantize_encrypt_cohort_dev", "flashe_quantize_encrypt_cohort_u32_dev",
     "flashe_quantize_encrypt_cohort_cut_dev", "flashe_quantize_encrypt_cohort_cut_u32_dev",
@@ -99,13 +100,18 @@ COHORT_LAUNCHES = (
     "flashe_quantize_encrypt_cohort_cut_runs_dev", "flashe_quantize_encrypt_cohort_cut_runs_u32_dev",
     "flashe_quantize_batch_encrypt_cohort_dev", "flashe_quantize_batch_encrypt_cohort_runs_dev",
     "flashe_quantize_batch_encrypt_cohort_cut_runs_dev", "flashe_quantize_encrypt_cohort_u64_dev",
-    "flashe_quantize_encrypt_cohort_runs_u64_dev",
+    "flashe_quantize_encrypt_cohort_runs_u64_dev", "flashe_quantize_encrypt_cohort_cut_u64_dev",
 )
+
+
+def cohort_by_list(name):
+    """Does the chained cohort launch `name` take the cipher indices as a list?"""
+    return "_runs_" in name or "_cut_u64_" in name
 
 
 def _cohort_signature(name):
     batched = "_batch_" in name
-    return (c_int, [c_vp, c_u32, ctypes.POINTER(c_u32) if "_runs_" in name else c_u32, c_int] + [c_u64] * (2 if batched else 1)    # ctx, iter, idx, n_clients, n
+    return (c_int, [c_vp, c_u32, ctypes.POINTER(c_u32) if cohort_by_list(name) else c_u32, c_int] + [c_u64] * (2 if batched else 1)    # ctx, iter, idx, n_clients, n
             + [c_u32, ctypes.POINTER(TensorLayer), c_int, ctypes.POINTER(c_vp), ctypes.POINTER(ctypes.c_int32)]                  # n_jobs, table, sources
             + [c_int] * (2 if batched else 1) + [c_vp, ctypes.POINTER(c_vp), c_vp]                                                 # bits, u, cts, sum
             + [c_vp] * (("_u32_" not in name and "_u64_" not in name) + ("_cut_" in name)))                                                                 # dmask, scratch
@@ -273,6 +279,7 @@ _SIGNATURES = {
     **{name: _cohort_signature(name) for name in COHORT_LAUNCHES},
     "flashe_cohort_cut_parts": (c_int, [c_vp, c_int, c_u64, c_u32, c_int, ctypes.POINTER(c_int)]),
     "flashe_cohort_cut_pieces": (c_int, [c_vp, ctypes.POINTER(c_u32), c_int, c_u64, c_u32, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "flashe_cohort_cut_pieces_u64": (c_int, [c_vp, ctypes.POINTER(c_u32), c_int, c_u64, c_u32, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "flashe_cohort_masks_u32_dev": (c_int, [c_vp, c_u32, c_u32, c_int, c_u64, c_u32, ctypes.POINTER(c_vp)]),
     **{name: _prepared_cohort_signature(name) for name in PREPARED_COHORT_LAUNCHES},
     "flashe_combine_unquantize_model_dev": (c_int, [c_vp, c_u64, c_vp, c_vp, c_vp, ctypes.POINTER(CodecLayer), c_int, c_int, c_int, c_vp]),

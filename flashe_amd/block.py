@@ -1352,7 +1352,7 @@ def cohort_cut_pieces(idxs, items, cu_count):
 
 def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, mask="double", num_clients=None, precompute=False, chain=True,
                 location_masks=False, compact=False, n_jobs=None, cohort_masks=False, present=None, compact_runs=False, cut=False, cut_any=False,
-                one_limb=False, limb_runs=False):
+                one_limb=False, limb_runs=False, limb_cut=False):
     """The engine-free part of FlasheCohort.quantize_encrypt: checks that the clients' Weights describe one model (the same layer names
     in the same walking order with the same shapes: ValueError naming the client and the layer otherwise; a sparse upload -- a 'zzz'
     layer or location masks -- is a TypeError), lays out the shared layer table and the client-major draws, and picks the path:
@@ -1402,11 +1402,17 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
     layout replaces the rule "int_bits <= 64" by the compact chain's: "cohort-chain" (uint64 ciphertexts and their sum from the floats, no
     decrypt mask) for a double-mask, un-batched cohort of at most 128 clients in ONE run of consecutive clients whose model has at least
     compact_cohort_admission_length(cu_count, int_bits, n_jobs) values and fewer than 2^32, every layer float64 for all clients or for
-    none; a shorter model stays "staged-chain" (the cut launch does not take these widths).  A round in which clients dropped out in
+    none; a shorter model stays "staged-chain" unless limb_cut says otherwise (below).  A round in which clients dropped out in
     several runs depends on limb_runs, whether the engine has the gapped one-limb launch (flashe_quantize_encrypt_cohort_runs_u64_dev):
     False (the default) plans it "staged-chain" -- the one-limb chain then takes one run only --, True lets it through to the 144-stream
     rule and the mixed-float64 rule like a compact cohort with compact_runs=True.  Other widths and one_limb=False: every plan is what it
     is without the keywords.
+    limb_cut=True beside one_limb=True and cut=True (an engine with flashe_quantize_encrypt_cohort_cut_u64_dev) answers
+      "cut-chain"     for a one-limb cohort whose ONLY obstacle is the length rule, its present clients in 1 .. 16 runs (the launch has the
+                      one form, which takes the cipher indices: cut_any is not asked): CohortPlan.parts from cohort_cut_pieces over
+                      cohort_cut_items(n, int_bits, n_jobs, True) tiles of 128 AES blocks.  A mixed-float64 cohort, more than 16 runs, a
+                      batched job and the single mask keep their reasons.
+    limb_cut=False (the default): every plan is what it is without the keyword.
     Touches no device.  The library's own answer stays the last word: a "cohort-chain" or "cut-chain" plan it declines runs
     "staged-chain", a "prepared-cohort" one "prepared-staged"."""
     if len(weights_list) < 1:
@@ -1461,7 +1467,7 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
     elif not chain:
         path, reason = STAGED_CHAIN, "FLASHE_CHAIN=0"
     elif (compact or limb) and (n >= 2 ** 32 or compact_cohort_blocks(n, int_bits, n_jobs) < 2 * 128 * 16 * int(cu_count)):
-        path, reason, short = STAGED_CHAIN, "the vector does not fill the chip uncut", bool(compact) and 1 <= n < 2 ** 32
+        path, reason, short = STAGED_CHAIN, "the vector does not fill the chip uncut", (bool(compact) or (limb and bool(limb_cut))) and 1 <= n < 2 ** 32
     elif not compact and not limb and (n_elems < cohort_admission_length(cu_count) or n_elems > 2 ** 32):
         path, reason, short = STAGED_CHAIN, "the vector does not fill the chip uncut", 1 <= n_elems < cohort_admission_length(cu_count)
     elif runs > 1 and limb and not limb_runs:
@@ -1474,14 +1480,14 @@ def plan_cohort(weights_list, int_bits, cu_count, element_bits=16, batch=False, 
         path, reason = STAGED_CHAIN, "a layer is float64 for some clients only"
     else:
         path, reason = COHORT_CHAIN, ""
-    if cut and cut_any and short:
+    if cut and short and (cut_any or limb):
         # (batched: only the compiled batch sizes at int_bits > 64 get here -- the rules before the length rule sent the others away)
         if mixed:
             reason = "a layer is float64 for some clients only"
         elif runs > _CUT_MAX_PARTS:
             reason = f"clients dropped out ({runs} runs of indices): the cut chain takes at most {_CUT_MAX_PARTS} runs, one table holds as many chains"
         else:
-            begins = cohort_cut_pieces(present, cohort_cut_items(n, int_bits, n_jobs, compact, n_elems if batch else None), cu_count)
+            begins = cohort_cut_pieces(present, cohort_cut_items(n, int_bits, n_jobs, compact or limb, n_elems if batch else None), cu_count)
             if begins:
                 path, reason, parts = CUT_CHAIN, "", len(begins) - 1
     elif cut and short:
@@ -1539,14 +1545,15 @@ class FlasheCohort(object):
     one_limb=False): the widths of a job that quantises finer than the compact chain carries -- element_bits 32 with 2 .. 10 clients,
     int_bits 64 -- chain from the floats too (flashe_quantize_encrypt_cohort_u64_dev: 20 bytes moved per value and client instead of 36).
     The ciphertexts and the sum are the ordinary one-limb DeviceVectors of these widths whatever path ran; no decrypt mask is kept, and
-    decrypt_unquantize() decrypts the sum with the telescoped lists.  A model shorter than compact_cohort_admission_length(...), a batched
-    job and the single mask stay "staged-chain".
+    decrypt_unquantize() decrypts the sum with the telescoped lists.  A model shorter than compact_cohort_admission_length(...) stays
+    "staged-chain" without cut= (below); a batched job and the single mask do so always.
     cut=True (opt-in, like compact): a model too SHORT for the uncut chain -- fewer than cohort_admission_length(cu_count) values, or
     compact_cohort_admission_length(...) in the compact layout: many clients with a small model -- runs "cut-chain" instead of
     "staged-chain": the summed chain cut into runs of consecutive clients and one combine pass (flashe_quantize_encrypt_cohort_cut_dev /
     its _u32 form), two launches whatever n_local is, no plaintext in HBM, the same bytes, and the same decrypt mask kept for
-    decrypt_unquantize().  Short cohorts that are batched, gapped (present= in several runs), single-mask, at int_bits 33 - 64 or of more
-    than 128 clients stay "staged-chain".
+    decrypt_unquantize().  Short cohorts that are batched, gapped (present= in several runs), single-mask or of more than 128 clients
+    stay "staged-chain".  With one_limb=True (int_bits 33 .. 64, an engine with flashe_quantize_encrypt_cohort_cut_u64_dev) cut=True or
+    "any" runs the one-limb layout's cut launch, which takes present= in 1 .. 16 runs alike and keeps no mask.
     cut="any" (opt-in; an engine without the entry points behaves as cut=True): "cut-chain" also for a short cohort in which clients
     DROPPED OUT -- present= in 2 .. 16 runs, wide and compact: every gap is a cut, flashe_quantize_encrypt_cohort_cut_runs_dev / its _u32
     form -- and for a short BATCHED cohort at int_bits > 64 with 5, 6 or 7 values per element, in one run or several
@@ -1639,7 +1646,8 @@ class FlasheCohort(object):
                            cut=self.cut and hasattr(ld.cipher.engine, "quantize_encrypt_cohort_cut_u32_dev" if self.compact
                                                     else "quantize_encrypt_cohort_cut_dev"),
                            cut_any=self.cut_any and all(hasattr(ld.cipher.engine, name) for name in self._cut_any_methods()),
-                           one_limb=self.one_limb, limb_runs=hasattr(ld.cipher.engine, "quantize_encrypt_cohort_runs_u64_dev"))
+                           one_limb=self.one_limb, limb_runs=hasattr(ld.cipher.engine, "quantize_encrypt_cohort_runs_u64_dev"),
+                           limb_cut=all(hasattr(ld.cipher.engine, name) for name in ("cohort_cut_pieces_u64", "quantize_encrypt_cohort_cut_u64_dev")))
 
     def _cut_any_methods(self):
         """The engine methods cut="any" needs for this cohort's layout."""
@@ -1893,7 +1901,8 @@ class FlasheCohort(object):
         the chain cut into the library's cohort_cut_parts pieces plus the combine pass, with the scratch the pieces' sums and masks go
         through; the outputs and the mask kept are those of the uncut launch.  A gapped or batched "cut-chain" (cut="any") goes through
         the launches that take the cipher indices, with the library's cohort_cut_pieces count; the mask kept is that of the telescoped
-        lists.  False: the library declined, nothing was launched."""
+        lists.  A one-limb "cut-chain" has the one launch, which takes the cipher indices (cohort_cut_pieces_u64's count, 8-byte sums in
+        the scratch, no mask).  False: the library declined, nothing was launched."""
         from . import cipher as _cipher_mod
         from .engine import DeviceVector
         ld = self.lead
@@ -1906,21 +1915,23 @@ class FlasheCohort(object):
         idxs = [self.first_idx + p for p in plan.present]
         jobs, batch = _cipher_mod.N_JOBS, bool(ld.batch) and not narrow
         # the form: the cipher indices as a list for a gapped or batched cut and for a call with `present` (one run of a compact cohort
-        # or one-limb cohort without its gapped launch: plan_cohort sends a gapped one to the staged form), else the first index.  One
-        # limb (int_bits 33 .. 64): never cut
-        if self.one_limb:
-            cut = False
+        # or one-limb cohort without its gapped launch: plan_cohort sends a gapped one to the staged form), else the first index.  The
+        # one-limb cut launch has the one form, which takes the list
+        limb_cut = cut and self.one_limb
         layout = "_u32" if self.compact else "_u64" if self.one_limb else ""
-        by_list = (plan.runs > 1 or bool(ld.batch)) if cut else (by_idx and (not narrow or hasattr(eng, f"quantize_encrypt_cohort_runs{layout}_dev")))
-        name = f"quantize_{'batch_' if batch else ''}encrypt_cohort{'_cut' if cut else ''}{'_runs' if by_list else ''}{layout}_dev"
+        by_list = (limb_cut or plan.runs > 1 or bool(ld.batch)) if cut else (by_idx and (not narrow or hasattr(eng, f"quantize_encrypt_cohort_runs{layout}_dev")))
+        name = f"quantize_{'batch_' if batch else ''}encrypt_cohort{'_cut' if cut else ''}{'_runs' if by_list and not limb_cut else ''}{layout}_dev"
         scratch = ()
         if cut:
             # the library's piece count sizes the scratch: the pieces' sums (compact: uint32) and, behind them, their decrypt masks
             elems = n_elems if by_list else n
-            parts = eng.cohort_cut_pieces(idxs, elems, jobs, compact=self.compact)[0] if by_list else eng.cohort_cut_parts(len(idxs), elems, jobs, compact=self.compact)
+            if limb_cut:
+                parts = eng.cohort_cut_pieces_u64(idxs, elems, jobs)[0]
+            else:
+                parts = eng.cohort_cut_pieces(idxs, elems, jobs, compact=self.compact)[0] if by_list else eng.cohort_cut_parts(len(idxs), elems, jobs, compact=self.compact)
             if not parts:
                 return False
-            need = 0 if parts == 1 else parts * elems * (4 if self.compact else 16 * (2 if dmask is not None else 1))
+            need = 0 if parts == 1 else parts * elems * (4 if self.compact else 8 if limb_cut else 16 * (2 if dmask is not None else 1))
             if need and (self._cut_scratch is None or self._cut_scratch.nbytes < need):
                 self._cut_scratch = eng.alloc(max(need, 16))
             scratch = (self._cut_scratch if need else None,)

@@ -669,14 +669,14 @@ static int cohort_check_scratch(flashe_ctx *ctx, int parts, int n_clients, const
     return FLASHE_OK;
 }
 
-// What tells the thirteen chained cohort entry points apart, besides the element type T of their vectors (uint64_t: the wide two-limb
+// What tells the fourteen chained cohort entry points apart, besides the element type T of their vectors (uint64_t: the wide two-limb
 // layout, or the one-limb layout of the `one_limb` form; uint32_t: the compact one, no decrypt mask).  `what` names the launch in a refusal.
 struct CohortForm {
     const char *who, *what;
     bool by_list;            // the cipher indices: the list idx of the clients that report (the *_runs_* forms), else first_idx + c
     bool batched;            // a batched job: the table and sources over n_values values, the chain over n_elems batched elements
     bool cut;                // the short cohort (cohort_cut.h): no length rule, the chain cut into pieces, scratch_dev
-    bool one_limb;           // int_bits 33 .. 64 in the one-limb layout (limb_cohort_admits): uint64 vectors, no decrypt mask
+    bool one_limb;           // int_bits 33 .. 64 in the one-limb layout (limb_cohort_admits; cut: limb_cohort_cut_pieces_of): uint64 vectors, no decrypt mask
 };
 
 // The one body of those entry points, every step once and in the order the refusals are documented in: the arguments and the cipher
@@ -721,12 +721,14 @@ static int quantize_encrypt_cohort(flashe_ctx *ctx, const CohortForm &f, uint32_
     }
     if (compact && n_jobs == 0) return fail(ctx, FLASHE_EINVAL, "n_jobs must be >= 1");
     if ((rc = cohort_check_outs<T>(ctx, n_clients, n_jobs, ct_dev, sum_out_dev, compact ? nullptr : dmask_dev))) return rc;
-    // a cut launch answers with its pieces (consecutive clients: cohort_cut_parts_of; a list, where every gap is a cut: cohort_cut_pieces_of)
+    // a cut launch answers with its pieces (consecutive clients: cohort_cut_parts_of; a list, where every gap is a cut: cohort_cut_pieces_of,
+    // the one-limb layout's limb_cohort_cut_pieces_of)
     const bool gated = too_many || (compact && flashe_ctx_compact_layout(ctx) != 1);
     int parts = 0, begins[flashe_tables::kCutMaxParts + 1];
     if (f.cut && !gated && !(f.batched && (bs < 5 || bs > 7)))
-        parts = f.by_list ? cohort_cut_pieces_of(ctx->env, n_clients, idx, n_elems, n_jobs, compact, static_cast<int>(bs), begins)
-                          : cohort_cut_parts_of(ctx->env, n_clients, n_elems, n_jobs, compact);
+        parts = f.one_limb ? limb_cohort_cut_pieces_of(ctx->env, n_clients, idx, n_elems, n_jobs, begins)
+                : f.by_list ? cohort_cut_pieces_of(ctx->env, n_clients, idx, n_elems, n_jobs, compact, static_cast<int>(bs), begins)
+                            : cohort_cut_parts_of(ctx->env, n_clients, n_elems, n_jobs, compact);
     const bool admitted = f.cut ? parts != 0
                                 : !gated && (compact      ? small_cohort_admits(ctx->env, n_clients, n_elems, n_jobs, true)
                                              : f.one_limb ? limb_cohort_admits(ctx->env, n_clients, n_elems, n_jobs)
@@ -958,6 +960,40 @@ int flashe_quantize_batch_encrypt_cohort_cut_runs_dev(flashe_ctx *ctx, uint32_t 
         n_layers, src_dev, src_dtype, element_bits, field_bits, u_dev, ct_dev, sum_out_dev, dmask_dev, scratch_dev,
         [&](const uint32_t *ids, const CohortCodec &cc, const CohortBatch *cb) {
             return launch_prf_cohort_batch_cut(ctx->env, iter, n_clients, ids, cc, *cb, u_dev, ct_dev, sum_out_dev, n_elems, n_jobs, dmask_dev, scratch_dev);
+        });
+}
+
+// ---- the SHORT one-limb cohort at int_bits 33 .. 64 (prf_limb_cohort_cut_kernel<2 | 3> + cohort_cut_combine_u64_kernel): the cipher indices of
+// the clients that report, one run or several, one entry point -- flashe_quantize_encrypt_cohort_runs_u64_dev's checks and stage pass, the
+// _cut_ entry points' scratch, the admission limb_cohort_admits' without the length rule ----
+int flashe_cohort_cut_pieces_u64(flashe_ctx *ctx, const uint32_t *idx, int n_clients, uint64_t n, uint32_t n_jobs, int *parts, int *begins)
+{
+    CHECK_CTX(ctx);
+    static const char who[] = "flashe_cohort_cut_pieces_u64";
+    if (!parts) return fail(ctx, FLASHE_EINVAL, "%s: null argument", who);
+    *parts = 0;
+    if (n_clients < 1) return fail(ctx, FLASHE_EINVAL, "%s: n_clients must be >= 1", who);
+    flashe_tables::CohortStreams st;
+    if (flashe_tables::cohort_streams(idx, n_clients, 2 * n_clients, st) == flashe_tables::kCohortStreamsBadIdx)
+        return fail(ctx, FLASHE_EINVAL, "%s: the cipher indices must be strictly ascending and below 2^32 - 1", who);
+    int own[flashe_tables::kCutMaxParts + 1];
+    const int k = limb_cohort_cut_pieces_of(ctx->env, n_clients, idx, n, n_jobs, own);
+    if (!k) return cohort_declined(ctx, who, "cut one-limb cohort");
+    *parts = k;
+    if (begins) for (int p = 0; p <= k; p++) begins[p] = own[p];
+    return FLASHE_OK;
+}
+
+int flashe_quantize_encrypt_cohort_cut_u64_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                               const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                               int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev, uint64_t *scratch_dev)
+{
+    CHECK_CTX(ctx);
+    return quantize_encrypt_cohort<uint64_t>(
+        ctx, {"flashe_quantize_encrypt_cohort_cut_u64_dev", "cut one-limb cohort", true, false, true, true}, 0, idx, n_clients, n, n, n_jobs, layers, n_layers,
+        src_dev, src_dtype, element_bits, 0, u_dev, ct_dev, sum_out_dev, nullptr, scratch_dev,
+        [&](const uint32_t *ids, const CohortCodec &cc, const CohortBatch *) {
+            return launch_limb_cohort_cut(ctx->env, iter, n_clients, ids, cc, u_dev, ct_dev, sum_out_dev, n, n_jobs, scratch_dev);
         });
 }
 

@@ -167,6 +167,14 @@ hipError_t launch_small_cohort_cut(const LaunchEnv &env, uint32_t iter, int n_ve
 hipError_t launch_cohort_cut_combine(const LaunchEnv &env, int parts, uint64_t n, const uint64_t *psum_dev, uint64_t *sum_dev, const uint64_t *pmask_dev,
                                      uint64_t *dmask_dev);
 hipError_t launch_cohort_cut_combine_u32(const LaunchEnv &env, int parts, uint64_t n, const uint32_t *psum_dev, uint32_t *sum_dev);
+// The SHORT one-limb cohort (prf_limb_cohort_cut_kernel<2 | 3>): launch_limb_cohort_sum's outputs at int_bits 33 .. 64 for any n >= 1 --
+// limb_cohort_admits without the length rule.  limb_cohort_cut_pieces_of: the pieces the launch will use for any strictly ascending idx in
+// at most 16 runs (items of 128 AES blocks; begins as cohort_cut_pieces_of's), 0 = not a shape of the launch; the caller sizes the scratch
+// from it: parts x n x 8 B, unused when parts == 1.  The combine pass has no mask output.  hipErrorNotSupported: nothing launched.
+int limb_cohort_cut_pieces_of(const LaunchEnv &env, int n_vec, const uint32_t *idx, uint64_t n, uint32_t n_jobs, int *begins);
+hipError_t launch_limb_cohort_cut(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
+                                  uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs, uint64_t *scratch_dev);
+hipError_t launch_cohort_cut_combine_u64(const LaunchEnv &env, int parts, uint64_t n, const uint64_t *psum_dev, uint64_t *sum_dev);
 // launch_prf_batch on elements [first, first + count) of the n-element vectors (pointers address element `first`): what a GPU that owns
 // an element slice of every client's vector runs
 hipError_t launch_prf_batch_range(const LaunchEnv &env, uint32_t iter, bool dbl, int n_vec, const uint32_t *idx, const uint64_t *const *in_dev,

@@ -1568,6 +1568,142 @@ __global__ __launch_bounds__(kSmallThreads) void prf_limb_cohort_runs_kernel(con
 #include "prf_limb_cohort_body.inc"
 }
 
+// CUT: the same cohort for a vector too SHORT to fill the chip uncut (cohort_cut.h) -- n_chains pieces of consecutive clients, every one
+// its own double-mask chain over the SAME AES blocks: piece c completes outputs link0[c] .. link0[c] + len[c] - 1 from the len[c] + 1
+// streams at sbase[c] of the prefix table (a cut costs one stream) and writes the sum of ITS outputs to tb.sum_out[c]; one combine pass
+// (cohort_cut_combine_u64_kernel, stream.hip) adds the pieces' sums.  A round in which clients dropped out needs no form of its own: every
+// gap is a cut (cohort_cut_pieces), so every piece is one run.
+// The work is dealt in (piece, tile) items: a workgroup takes its share of the tiles x streams of all pieces (tb.wend, as
+// prf_small_cohort_kernel deals its chains' tiles -- a tile weighs the streams its piece computes) and its waves take that share's items in
+// turn.  An item is what a tile is to the uncut kernel -- 2 x 64 blocks per wave, the counter-dependent quarter of round 1 once for all the
+// piece's streams, M values of client `link` quantised before that stream's AES rounds, whole half tiles in registers and the others
+// walked -- with everything that names a client or a stream offset by the piece: the piece is chosen from the item number against LDS
+// totals read as scalars (wave-uniform, so tb's rows stay scalar loads), the previous stream's slots start from nothing at the piece's first
+// stream, and a walked half's sum in memory is started by the piece's own first output.  A kernel of its own: the uncut kernels keep their
+// code objects.
+template <int M>
+__global__ __launch_bounds__(kSmallThreads) void prf_limb_cohort_cut_kernel(const RoundKeys rk, const SmallChainTable tb, int n_chains, const SmallParams p,
+                                                                             const CohortCodec cc)
+{
+    static_assert(M == 2 || M == 3, "int_bits 43 .. 64 or 33 .. 42");
+    constexpr uint32_t WAVES = kSmallThreads / 64;
+    __shared__ uint32_t tab[kTabWords];
+    __shared__ uint32_t scratch[WAVES * 256 + 8];
+    __shared__ __attribute__((aligned(16))) uint32_t pre_lds[(kMaxLinks + kMaxChains) * 4];
+    __shared__ uint64_t d_tlo[kMaxChains], d_cend[kMaxChains];
+    const uint32_t iter = p.iter + p.te0[kIterShiftWord];
+    fill_tables(tab, p.te0);
+    const LaneRegs lr = lane_regs(tab);
+    {
+        const int last = n_chains - 1, n_streams = tb.sbase[last] + tb.len[last] + 1;       // all pieces': n_vec + n_chains
+        for (int s = threadIdx.x; s < n_streams; s += kSmallThreads) {
+            const CtrPrefix c = ctr_prefix(rk, lr, iter, tb.idx[s], 0u);                  // n < 2^32 (host-checked): the high counter word is 0
+            *reinterpret_cast<uint4 *>(pre_lds + 4 * s) = make_uint4(c.u[0], c.u[1], c.u[2], c.u[3]);
+        }
+        if (threadIdx.x < static_cast<unsigned>(n_chains)) {                               // this workgroup's tiles of every piece
+            const int i = threadIdx.x;
+            const uint64_t Wt = tb.wend[last], cw = i ? tb.wend[i - 1] : 0, w = tb.len[i] + 1u, T = (tb.wend[i] - cw) / w;
+            const uint64_t G = gridDim.x, g = blockIdx.x;
+            const uint64_t lo = Wt / G * g + (Wt % G) * g / G, hi = Wt / G * (g + 1) + (Wt % G) * (g + 1) / G;
+            uint64_t a = lo > cw ? (lo - cw + w - 1) / w : 0, b = hi > cw ? (hi - cw + w - 1) / w : 0;
+            if (a > T) a = T;
+            if (b > T) b = T;
+            d_tlo[i] = a; d_cend[i] = b - a;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint64_t acc = 0;
+            for (int i = 0; i < n_chains; i++) { acc += d_cend[i]; d_cend[i] = acc; }
+        }
+        __syncthreads();
+    }
+    const uint64_t n = p.n, J = p.n_jobs, d = n / J, r = n % J;
+    const uint32_t nb1_32 = static_cast<uint32_t>((d + 1 + M - 1) / M), nb0_32 = static_cast<uint32_t>(d ? (d + M - 1) / M : 0);
+    const uint32_t d32 = static_cast<uint32_t>(d), r32 = static_cast<uint32_t>(r);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
+    uint32_t *row0 = scratch + wave * 256;
+    const u128 top = (static_cast<u128>(p.top_hi) << 64) | p.top_lo;
+    const uint64_t Ng = uniform64(d_cend[n_chains - 1]);
+    int cur = 0;
+    uint64_t cbeg = 0;
+    for (uint64_t q = wave; q < Ng; q += WAVES) {
+        while (q >= uniform64(d_cend[cur])) cbeg = uniform64(d_cend[cur++]);            // (q and the totals are scalars: cur is wave-uniform)
+        const uint64_t blk_count = tb.blk_count[cur], Bw = (uniform64(d_tlo[cur]) + (q - cbeg)) * 128u;
+        const int link0 = tb.link0[cur], sbase = tb.sbase[cur], n_streams = tb.len[cur] + 1;
+        uint64_t *const sum = tb.sum_out[cur];
+        const bool vA = Bw + lane < blk_count, vB = Bw + 64u + lane < blk_count;
+        uint64_t j0A = 0, j0B = 0;
+        int cntA = 0, cntB = 0;
+        uint32_t ctrA = 0, ctrB = 0;
+        small_block_params(static_cast<uint32_t>(vA ? Bw + lane : 0), nb1_32, nb0_32, d32, r32, M, p, &j0A, &cntA, &ctrA);
+        small_block_params(static_cast<uint32_t>(vB ? Bw + 64u + lane : 0), nb1_32, nb0_32, d32, r32, M, p, &j0B, &cntB, &ctrB);
+        const CtrVar xA = ctr_var(rk, lr, ctrA), xB = ctr_var(rk, lr, ctrB);
+        // a half of 64 whole blocks is one contiguous run of 64 M elements inside one table row: registers (CohortDirect); every other half
+        // -- a chunk end with a partial block, the range end, the last partial tile, a half that straddles a row -- walks (CohortWalk)
+        const uint64_t e0A = uniform64(j0A), e0B = uniform64(j0B);
+        bool fastA = __ballot(vA && cntA == M) == ~0ull && e0A + 64u * M <= n;
+        bool fastB = __ballot(vB && cntB == M) == ~0ull && e0B + 64u * M <= n;
+        int layA = -1, layB = -1;
+        if (fastA) {
+            layA = cohort_layer_of(cc, e0A);
+            if (layA + 1 < cc.n_layers && *FLASHE_CONSTANT(const uint64_t, &cc.layers[layA + 1].start) < e0A + 64u * M) layA = -1;
+        }
+        if (fastB) {
+            layB = cohort_layer_of(cc, e0B);
+            if (layB + 1 < cc.n_layers && *FLASHE_CONSTANT(const uint64_t, &cc.layers[layB + 1].start) < e0B + 64u * M) layB = -1;
+        }
+        fastA = fastA && layA >= 0;
+        fastB = fastB && layB >= 0;
+        const CohortDirect csrc{cc, tb.in + link0, link0, {layA, layB}};                  // (addressed by the piece's link, as the walk's rows are by the cohort's)
+        u128 prevA = 0, prevB = 0;                                                        // the piece's first stream completes nothing
+        uint64_t accA[M], accB[M];                                                        // the whole blocks' running sums of THIS piece, unmasked
+#pragma unroll
+        for (int t = 0; t < M; t++) { accA[t] = 0ull; accB[t] = 0ull; }
+        for (int c = 0; c < n_streams; c++) {
+            const CtrPrefix pre = load_prefix(pre_lds, sbase + c);
+            const int link = c - 1;                                                       // the piece's output this stream completes (-1: none)
+            uint64_t ptA[M], ptB[M];
+#pragma unroll
+            for (int t = 0; t < M; t++) { ptA[t] = 0ull; ptB[t] = 0ull; }
+            if (link >= 0 && fastA) csrc.template words<M>(link, j0A, 0, ptA);
+            if (link >= 0 && fastB) csrc.template words<M>(link, j0B, 1, ptB);
+            uint32_t s[2][4];
+            ctr_round1(pre, xA, s[0]);
+            ctr_round1(pre, xB, s[1]);
+            aes256_rounds<2, 2>(rk, lr, s, p.swp_prio != 0);
+            const u128 SA = words_to_u128(s[0]), SB = words_to_u128(s[1]);
+            if (link >= 0) {
+                uint64_t *out = tb.out[link0 + link];
+                const CohortWalk cw{cc, tb.in[link0 + link], link0 + link};
+                if (fastA) {
+                    uint64_t v[M];
+#pragma unroll
+                    for (int t = 0; t < M; t++) {
+                        v[t] = ptA[t] + limb_slot(prevA, t, p.b) - limb_slot(SA, t, p.b);
+                        accA[t] += v[t];
+                    }
+                    limb_put<M, true>(out + j0A, v, p.mask_lo);
+                } else
+                    small_walk(row0, lane, vA, cntA, j0A, slot_diff(prevA, SA, top, p.b), static_cast<const uint64_t *>(nullptr), out, 0, n, p, sum, link == 0, &cw);
+                if (fastB) {
+                    uint64_t v[M];
+#pragma unroll
+                    for (int t = 0; t < M; t++) {
+                        v[t] = ptB[t] + limb_slot(prevB, t, p.b) - limb_slot(SB, t, p.b);
+                        accB[t] += v[t];
+                    }
+                    limb_put<M, true>(out + j0B, v, p.mask_lo);
+                } else
+                    small_walk(row0, lane, vB, cntB, j0B, slot_diff(prevB, SB, top, p.b), static_cast<const uint64_t *>(nullptr), out, 0, n, p, sum, link == 0, &cw);
+            }
+            prevA = SA; prevB = SB;
+        }
+        if (fastA) limb_put<M, false>(sum + j0A, accA, p.mask_lo);
+        if (fastB) limb_put<M, false>(sum + j0B, accB, p.mask_lo);
+    }
+}
+
 
 // ---- b <= 64: the reduce fused with the decrypt of its result (one add, at most one minus prefix) ----
 // out[j] = (sum_c ct_c[j] + term(add, j) - term(minus, j)) mod 2^b (jzf_aggregator.py:424-430 followed by jzf_flashe.py:570-571 with the
@@ -2814,10 +2950,15 @@ bool small_cohort_admits(const LaunchEnv &env, int n_vec, uint64_t n, uint32_t n
     return !summed || small_chain_long_enough(env, n, n_jobs);
 }
 
-// What the one-limb cohort launch admits (the same contract): int_bits 33 .. 64, and the length rule -- its chain is never cut.
+// What the one-limb cohort launches admit (the same contract): int_bits 33 .. 64 -- every condition but the length rule, which the cut
+// launch (launch_limb_cohort_cut) does without -- and, for the uncut chain, the length rule.
+static bool limb_cohort_shape(const LaunchEnv &env, int n_vec, uint64_t n, uint32_t n_jobs)
+{
+    return cohort_env_admits(env, n_vec) && env.b >= 33 && env.b <= 64 && n != 0 && n < (1ull << 32) && n_jobs != 0;
+}
 bool limb_cohort_admits(const LaunchEnv &env, int n_vec, uint64_t n, uint32_t n_jobs)
 {
-    return cohort_env_admits(env, n_vec) && env.b >= 33 && env.b <= 64 && n != 0 && n < (1ull << 32) && n_jobs != 0 && small_chain_long_enough(env, n, n_jobs);
+    return limb_cohort_shape(env, n_vec, n, n_jobs) && small_chain_long_enough(env, n, n_jobs);
 }
 
 // what the int_bits <= 64 launches below share: the layout's constants with its measured priority table, and the vector's AES blocks.
@@ -2920,6 +3061,42 @@ hipError_t launch_small_cohort_cut(const LaunchEnv &env, uint32_t iter, int n_ve
     const hipError_t e = COHORT_LAUNCH_FIXED32(prf_small_cohort_kernel, tb, parts, p, cc);
     if (e != hipSuccess || parts == 1) return e;
     return launch_cohort_cut_combine_u32(env, parts, n, scratch_dev, sum_out_dev);
+}
+
+// The SHORT one-limb cohort (int_bits 33 .. 64): launch_limb_cohort_sum's outputs for any n >= 1, admitted where limb_cohort_shape says --
+// limb_cohort_admits without the length rule.  The pieces are cohort_cut_pieces' over items of 128 AES blocks, for any strictly ascending
+// cipher indices in at most kCutMaxParts runs; 0 = not a shape of the launch.
+int limb_cohort_cut_pieces_of(const LaunchEnv &env, int n_vec, const uint32_t *idx, uint64_t n, uint32_t n_jobs, int *begins)
+{
+    if (!idx || !limb_cohort_shape(env, n_vec, n, n_jobs)) return 0;
+    return flashe_tables::cohort_cut_pieces(idx, n_vec, flashe_tables::cohort_cut_items_compact(block_of(n - 1, n, n_jobs, 128 / env.b) + 1), env.num_cus, begins);
+}
+
+// prf_limb_cohort_cut_kernel<2 | 3> over cohort_cut_table's pieces -- `parts` double-mask chains over the same AES blocks, piece p's uint64
+// sum in scratch_dev + p * n -- then cohort_cut_combine_u64_kernel.  One piece writes sum_out_dev itself and no combine pass runs.
+// hipErrorNotSupported = nothing launched.
+hipError_t launch_limb_cohort_cut(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
+                                  uint64_t *const *out_dev, uint64_t *sum_out_dev, uint64_t n, uint32_t n_jobs, uint64_t *scratch_dev)
+{
+    int begins[flashe_tables::kCutMaxParts + 1];
+    const int parts = limb_cohort_cut_pieces_of(env, n_vec, idx, n, n_jobs, begins);
+    if (!parts || !cohort_args_present(cc, u_dev, out_dev, n_vec, sum_out_dev != nullptr)) return hipErrorNotSupported;
+    if (parts > 1 && !scratch_dev) return hipErrorInvalidValue;
+    uint64_t blocks;
+    const SmallParams p = small_cohort_params(env, iter, n_vec, n, n_jobs, &blocks, false);
+    const uint64_t tiles = (blocks + 127) / 128, cus = static_cast<uint64_t>(env.num_cus);
+    SmallChainTable tb{};
+    if (!flashe_tables::cohort_cut_table(tb, n_vec, parts, begins, idx, n, tiles)) return hipErrorNotSupported;       // (never: the begins are pieces)
+    flashe_tables::cohort_chain_links(tb, n_vec, u_dev, n, out_dev);
+    flashe_tables::cohort_chain_blocks(tb, parts, blocks);
+    for (int k = 0; k < parts; k++) tb.sum_out[k] = parts == 1 ? sum_out_dev : scratch_dev + static_cast<uint64_t>(k) * n;
+    const uint64_t items = tiles * static_cast<uint64_t>(parts);
+    const dim3 grid(static_cast<unsigned>(items < cus ? items : cus)), block(kSmallThreads);
+    if (p.m == 2) hipLaunchKernelGGL((prf_limb_cohort_cut_kernel<2>), grid, block, 0, env.stream, env.rk, tb, parts, p, cc);
+    else hipLaunchKernelGGL((prf_limb_cohort_cut_kernel<3>), grid, block, 0, env.stream, env.rk, tb, parts, p, cc);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || parts == 1) return e;
+    return launch_cohort_cut_combine_u64(env, parts, n, scratch_dev, sum_out_dev);
 }
 
 // The sparse cohort's encrypts from the floats (prf_small_sparse_cohort_kernel): ONE single-mask chain of n_vec links over elements [0, n), cut

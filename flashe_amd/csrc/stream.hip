@@ -470,6 +470,41 @@ __global__ __launch_bounds__(kStreamThreads) void cohort_cut_combine_u32_kernel(
     }
 }
 
+// the one-limb layout's form (int_bits 33 .. 64; launch_limb_cohort_cut, kernels.hip): uint64 sums masked to b bits, no mask.  Two elements
+// per lane and trip in 16-byte accesses -- piece p begins at element p n of the scratch, so for an odd n every other piece is 8 bytes past a
+// 16-byte boundary, as the sum may be (cohort_u64x2: aligned to 8) --, an odd n's last element by one lane on its own.
+__global__ __launch_bounds__(kStreamThreads) void cohort_cut_combine_u64_kernel(int parts, uint64_t n, const uint64_t *__restrict__ psum, uint64_t *__restrict__ sum,
+                                                                                uint64_t mask)
+{
+    const uint64_t n2 = n / 2;
+    for (uint64_t s = static_cast<uint64_t>(blockIdx.x) * kStreamThreads + threadIdx.x; s < n2; s += static_cast<uint64_t>(gridDim.x) * kStreamThreads) {
+        uint64_t a0 = 0, a1 = 0;
+#pragma unroll 4
+        for (int p = 0; p < parts; p++) {
+            const cohort_u64x2 v = __builtin_nontemporal_load(reinterpret_cast<const cohort_u64x2 *>(psum + static_cast<uint64_t>(p) * n + 2 * s));
+            a0 += v[0]; a1 += v[1];
+        }
+        cohort_u64x2 r;
+        r[0] = a0 & mask; r[1] = a1 & mask;
+        *reinterpret_cast<cohort_u64x2 *>(sum + 2 * s) = r;
+    }
+    if ((n & 1u) && blockIdx.x == 0 && threadIdx.x == 0) {
+        uint64_t a = 0;
+        for (int p = 0; p < parts; p++) a += __builtin_nontemporal_load(psum + static_cast<uint64_t>(p) * n + (n - 1));
+        sum[n - 1] = a & mask;
+    }
+}
+
+hipError_t launch_cohort_cut_combine_u64(const LaunchEnv &env, int parts, uint64_t n, const uint64_t *psum_dev, uint64_t *sum_dev)
+{
+    if (n == 0) return hipSuccess;
+    if (parts < 1 || env.b < 33 || env.b > 64 || !psum_dev || !sum_dev) return hipErrorInvalidValue;
+    uint64_t mask, hi;
+    masks_of(env.b, &mask, &hi);
+    hipLaunchKernelGGL(cohort_cut_combine_u64_kernel, dim3(stream_grid(env, n / 2 + 1)), dim3(kStreamThreads), 0, env.stream, parts, n, psum_dev, sum_dev, mask);
+    return hipGetLastError();
+}
+
 hipError_t launch_cohort_cut_combine(const LaunchEnv &env, int parts, uint64_t n, const uint64_t *psum_dev, uint64_t *sum_dev, const uint64_t *pmask_dev,
                                      uint64_t *dmask_dev)
 {

@@ -719,12 +719,12 @@ class Engine:
 
     def _cohort_launch(self, name, it, idx, ns, n_jobs, layers, srcs, dtypes, bits, u, cts, *vecs):
         """The library's chained cohort launch `name` (_lib.COHORT_LAUNCHES): the shared table, the sources, the ciphertext pointers and -- a
-        _runs_ form -- the checked cipher indices marshalled, one call.  ns = (n,) or (n_values, n_elems), bits = (element_bits,) or
+        form that takes them as a list (_lib.cohort_by_list) -- the checked cipher indices marshalled, one call.  ns = (n,) or (n_values, n_elems), bits = (element_bits,) or
         (element_bits, field_bits), vecs = the sum and what the form takes behind it (dmask, scratch).  False: the library declined."""
         arr, nl = self._tensor_layers(layers)
         C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
         pc, _k = self._ptr_array(cts)
-        idx = self._cohort_idx(idx, C)[0] if "_runs_" in name else int(idx)
+        idx = self._cohort_idx(idx, C)[0] if _lib.cohort_by_list(name) else int(idx)
         rc = getattr(self._lib, name)(self._h, it, idx, C, *(int(n) for n in ns), n_jobs, arr, nl, ps, pd, *bits, self._ptr(u), pc,
                                       *(self._ptr(v) for v in vecs))
         return self._took(rc)
@@ -841,6 +841,22 @@ class Engine:
         with dmask."""
         return self._cohort_launch("flashe_quantize_batch_encrypt_cohort_cut_runs_dev", it, idx, (n_values, n_elems), n_jobs, layers, srcs, dtypes,
                                    (element_bits, field_bits), u, cts, sum_out, dmask, scratch)
+
+    def cohort_cut_pieces_u64(self, idx, n, n_jobs):
+        """(parts, begins) of quantize_encrypt_cohort_cut_u64_dev (flashe_cohort_cut_pieces_u64, int_bits 33 .. 64): cohort_cut_pieces' answer
+        for the one-limb layout's cut launch -- the caller sizes the scratch from parts.  (0, []): the library declines the shape."""
+        pi, _ki = self._cohort_idx(idx, len(idx))
+        parts, begins = ctypes.c_int(0), (ctypes.c_int * 17)()
+        rc = self._lib.flashe_cohort_cut_pieces_u64(self._h, pi, len(idx), int(n), n_jobs, ctypes.byref(parts), begins)
+        return (parts.value, list(begins[:parts.value + 1])) if self._took(rc) else (0, [])
+
+    def quantize_encrypt_cohort_cut_u64_dev(self, it, idx, n, n_jobs, layers, srcs, dtypes, element_bits, u, cts, sum_out, scratch=None):
+        """quantize_encrypt_cohort_runs_u64_dev for a vector of ANY length (flashe_quantize_encrypt_cohort_cut_u64_dev, int_bits 33 .. 64): the
+        one-limb chain cut into cohort_cut_pieces_u64(idx, n, ...) pieces and one combine pass; idx in one run or several (at most 16, every
+        gap a cut).  scratch: 16-byte aligned, parts x n x 8 bytes; may be None when parts == 1.  No decrypt mask (decrypt the sum with
+        telescope(idx)).  Returns False -- nothing was launched -- when the library declines the shape (FLASHE_ENOTSUP), True otherwise."""
+        return self._cohort_launch("flashe_quantize_encrypt_cohort_cut_u64_dev", it, idx, (n,), n_jobs, layers, srcs, dtypes, (element_bits,), u, cts,
+                                   sum_out, scratch)
 
     @staticmethod
     def _cohort_idx(idx, C):

@@ -97,7 +97,8 @@ typedef struct flashe_ctx flashe_ctx;
  *      flashe_quantize_combine_cohort_pcg64_dev / flashe_quantize_combine_cohort_pcg64_u32_dev (the un-batched form for the streams of
  *      np.random.PCG64 / PCG64DXSM, np.random.default_rng's generator) with flashe_pcg64_cohort_grid + flashe_pcg64_cohort_lane_draws;
  *      flashe_quantize_encrypt_cohort_u64_dev (the cohort's chained launch in the one-limb layout, int_bits 33 .. 64);
- *      flashe_quantize_encrypt_cohort_runs_u64_dev (the same launch for a round in which clients dropped out) */
+ *      flashe_quantize_encrypt_cohort_runs_u64_dev (the same launch for a round in which clients dropped out);
+ *      flashe_cohort_cut_pieces_u64 + flashe_quantize_encrypt_cohort_cut_u64_dev (the one-limb cohort's cut launch for a short vector) */
 #define FLASHE_ABI_VERSION 4
 int flashe_abi_version(void);
 int flashe_device_count(int *count);
@@ -898,6 +899,25 @@ int flashe_quantize_batch_encrypt_cohort_cut_runs_dev(flashe_ctx *ctx, uint32_t 
                                                       const void *const *src_dev, const int32_t *src_dtype, int element_bits, int field_bits,
                                                       const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev, uint64_t *dmask_dev,
                                                       uint64_t *scratch_dev);
+/* A SHORT one-limb cohort at int_bits 33 .. 64 (new), jzf_quantize.py:394-491, jzf_flashe.py:349-367, jzf_aggregator.py:424-430: the cut
+ * launch of the one-limb layout -- flashe_quantize_encrypt_cohort_runs_u64_dev's arguments, checks, stage pass and outputs without its
+ * length rule, for any n >= 1.  It takes the cipher indices idx of the n_clients clients that report, one run or several (at most 16:
+ * every gap is a cut), through this one entry point.  The summed chain is cut into pieces of consecutive clients, (piece, tile) items go to
+ * the chip's waves, and one combine pass adds the pieces' uint64 sums: two launches whatever n_clients is, one when parts == 1.  No mask is
+ * kept: decrypt the sum with flashe_telescope(idx).
+ * flashe_cohort_cut_pieces_u64: *parts = the pieces that launch will use (items of 128 AES blocks of 128 / int_bits elements, the rule of
+ * flashe_cohort_cut_pieces) and, when begins is not NULL, begins[0 .. *parts] as there (room for 17 entries).  FLASHE_EINVAL: idx NULL,
+ * not strictly ascending or holding 2^32 - 1, n_clients < 1.  FLASHE_ENOTSUP (*parts = 0) where the launch would decline.
+ * scratch_dev: parts x n x 8 bytes, 16-byte aligned, may be NULL when parts == 1.
+ * FLASHE_EINVAL: a bad idx (as above), a bad scratch (NULL with parts > 1, misaligned, aliasing an output), and the argument errors of
+ * flashe_quantize_encrypt_cohort_runs_u64_dev.  FLASHE_ENOTSUP -- nothing launched, every output untouched -- outside int_bits 33 .. 64, for
+ * more than 128 clients, more than 16 runs, n = 0 or n >= 2^32, under FLASHE_CHAIN=0 and with another PRF backend; the caller then
+ * quantises per client and uses flashe_encrypt_batch_sum_dev.  The table uploads synchronise; not capturable. */
+int flashe_cohort_cut_pieces_u64(flashe_ctx *ctx, const uint32_t *idx, int n_clients, uint64_t n, uint32_t n_jobs, int *parts, int *begins);
+int flashe_quantize_encrypt_cohort_cut_u64_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *idx, int n_clients, uint64_t n, uint32_t n_jobs,
+                                               const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                               int element_bits, const double *u_dev, uint64_t *const *ct_dev, uint64_t *sum_out_dev,
+                                               uint64_t *scratch_dev);
 /* A precompute job's cohort (new), jzf_flashe.py:599-631, 456-488: every client computes its next round's encrypt mask in idle time and
  * its online step is a quantise plus a mask add.  For a cohort the masks are ONE chain of n_clients + 1 streams into vectors the caller
  * owns, mask[c][j] = term(iter, first_idx + c)[j] - term(iter, first_idx + c + 1)[j] mod 2^b: in the limb layout
