@@ -1,0 +1,47 @@
+"""One dense round in the WIRE form: every client goes from its float model straight to the packed integer it sends
+(quantize_encrypt(packed=True): one launch at int_bits 16 .. 64), the arbiter adds the packed integers where they lie, and a client takes
+the packed sum back to floats in one launch.  Run on a machine with a GPU:  python examples/wire_round.py"""
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from flashe_amd.block import FlasheClient  # noqa: E402
+
+ARGS = {"quantize": {"int_bits": 20, "batch": False, "element_bits": 16, "padding": True, "secure": True},
+        "precompute": {"enable": False, "num_params": None}}
+SHAPES = {"conv.w": (6, 25), "fc.w": (120, 84), "fc.b": (84,)}
+C = 3
+
+
+class Weights:
+    def __init__(self, layers):
+        self.walking_order, self._weights = sorted(layers), dict(layers)
+
+
+def main():
+    rs = np.random.RandomState(0)
+    models = [{k: rs.normal(0, 0.05, s).astype(np.float32) for k, s in SHAPES.items()} for _ in range(C)]
+    clients = []
+    for i in range(C):
+        cl = FlasheClient(ARGS)
+        cl.create_cipher(i, C, bytes(range(32)))
+        cl.set_iter_index(1)
+        cl.quantizer.past_layer_mean_list = [np.float64(0.0)] * len(SHAPES)
+        cl.quantizer.past_layer_std_list = [np.float64(0.05)] * len(SHAPES)
+        clients.append(cl)
+    uploads = []
+    for cl, m in zip(clients, models):
+        w = cl.quantize_encrypt(Weights(m), packed=True)
+        uploads.append(w._weights[w.walking_order[0]])                 # a PackedVector; .to_int() is what goes on the wire
+    print("upload path:", uploads[0].path, "-", (uploads[0].to_int().bit_length() + 7) // 8, "bytes per client")
+    total = clients[0].cipher.aggregate(uploads, packed=True)           # the arbiter: the packed integers added where they lie
+    clients[0].set_idx_list(list(range(C)))
+    mean = clients[0].decrypt_unquantize(Weights({"sum": total}))
+    want = sum(m["fc.b"].astype(np.float64) for m in models)
+    print("max |error| of the summed fc.b:", float(np.abs(mean._weights["fc.b"] - want).max()))
+
+
+if __name__ == "__main__":
+    main()

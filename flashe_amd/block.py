@@ -17,6 +17,10 @@ from .cipher import FlasheCipher, _CtxMask
 from .quantize import ACIQ, QuantizingClient, _check_rng, _global_on_device, _loop_dtype, _rng_on_device
 
 _RNG_RUN_MAX = 1 << 26          # draws per device call of quantize_encrypt (512 MiB of float64)
+# quantize_encrypt(packed=True) takes the one launch to the wire form up to this width: measured against tensors_dev + pack_dev it wins by more
+# than either form's spread at int_bits 20 and 23 (x 1.40 - 1.78) and leads within the spread at 64 (x 1.10 - 1.14: the fill of 8-byte limbs),
+# so 33 .. 64 stay staged; the way back takes its one launch at every width 16 .. 64 (x 1.22 - 1.81).  profiles/r39_wire_client_step.log
+_WIRE_OUT_MAX_BITS = 32
 
 __all__ = ["dynamic_masking_choice", "FlasheClient", "FlasheCohort", "CohortPlan", "CohortUpload", "plan_cohort", "FlasheSparseCohort",
            "SparseCohortPlan", "SparseCohortEncoding", "SparseCohortUpload", "plan_sparse_cohort"]
@@ -569,8 +573,13 @@ class FlasheClient(object):
         _skip_draws(n_values, rng)
         c._check_prepared_len(cache, n_ct)
 
-    def quantize_encrypt(self, weights, device=True, normalize=False, rng=None, degree=None):
-        """degree (new): `weights *= degree` first (jzf_aggregator.py:676, the client's sample count times aggregate_every_n_epoch): every
+    def quantize_encrypt(self, weights, device=True, normalize=False, rng=None, degree=None, packed=False):
+        """packed (new): the one key of the result holds the ciphertext in its WIRE form -- a PackedVector (device=True) or the Python int
+        JZFTransferableWeights.compress builds (device=False).  A dense un-batched job at int_bits 16 .. 32 goes from the floats to the
+        packed limbs in ONE launch (flashe_quantize_encrypt_pack_tensors_dev, path "fused"); a batched job, the sparse job's 'zzz', a
+        consumed precompute cache, other widths and a cipher with `masks` run today's step followed by pack_dev (path "staged").
+
+        degree (new): `weights *= degree` first (jzf_aggregator.py:676, the client's sample count times aggregate_every_n_epoch): every
         layer but the sparse job's 'zzz' becomes a NEW array `layer * degree` in the dtype NumPy gives that product (a float32 layer stays
         float32 under a Python number and becomes float64 under an np.float64), the caller's arrays and tensors are never written; host
         layers are multiplied on the host, framework tensors in the stage pass that normalisation pays anyway
@@ -610,6 +619,12 @@ class FlasheClient(object):
         q = self.quantizer
         rng = _check_rng(rng)
         self.degree = _check_degree(degree, "degree")
+        if packed:
+            self._to_wire = True                      # (_encrypt_tail: take the one launch where the step admits it)
+            try:
+                return self._packed_result(self.quantize_encrypt(weights, True, normalize, rng, degree), device)
+            finally:
+                self._to_wire = False
         if any(interop.is_foreign(weights._weights[k]) for k in weights.walking_order):
             return self._quantize_encrypt_tensors(weights, device, normalize, rng, degree)
         if degree is not None:
@@ -631,6 +646,42 @@ class FlasheClient(object):
             weights._weights[k0] = np.append(ct, [zero_quantized]) if sparse else ct
             return weights
         return self._encrypt_tail(weights, device, *self._host_front_end(weights), rng=rng)
+
+    def _packed_result(self, weights, device):
+        """quantize_encrypt(packed=True)'s result from the step's: a PackedVector the one launch made stays; anything else -- a
+        DeviceVector, limbs, the call-by-call step's object ints -- is packed as compress() packs it (path "staged")."""
+        from .engine import DeviceVector, PackedVector
+        from .weights import to_big_int
+        eng = self.cipher.engine
+        if not weights.walking_order:
+            return weights
+        k0 = weights.walking_order[0]
+        v = weights._weights[k0]
+        if isinstance(v, DeviceVector):
+            dv = v.widened(eng) if v.compact else v
+            pv = PackedVector(eng, len(dv), self.int_bits)
+            if len(dv):
+                eng.pack_dev(len(dv), dv.buf, pv.buf)
+            eng.hold([dv])
+            v = pv.mark_ready()
+        elif not isinstance(v, PackedVector):
+            big, n = to_big_int(v, self.int_bits, getattr(eng, "device", 0))
+            v = PackedVector.from_int(eng, big, n, self.int_bits)
+        weights._weights[k0] = v if device else v.to_int()
+        return weights
+
+    def _unpacked(self, pv):
+        """A PackedVector as the DeviceVector today's passes read (unpack_dev)."""
+        from .engine import DeviceVector
+        eng = self.cipher.engine
+        if pv.bits != self.int_bits:
+            raise ValueError(f"a PackedVector of {pv.bits}-bit fields cannot be decrypted by a {self.int_bits}-bit cipher")
+        pv.wait_on(eng)
+        dv = DeviceVector(eng, len(pv))
+        if len(pv):
+            eng.unpack_dev(len(pv), pv.buf, dv.buf)
+        eng.hold([pv])
+        return dv.mark_ready()
 
     def _host_front_end(self, weights):
         """The fused step's front end for host layers (normalised on the host already, layer_size_list set): every layer goes up once,
@@ -703,8 +754,19 @@ class FlasheClient(object):
             # prepared masks the launches add them in place of the PRF streams; the run that ends the vector consumes them.
             if mode == "ctx":
                 self._refuse_prepared_len(n, n, rng)
-            ct = DeviceVector(eng, n + (1 if zzz is not None else 0))
-            at = 0
+            wire = None
+            if getattr(self, "_to_wire", False) and mode != "ctx" and zzz is None and 0 < n <= _RNG_RUN_MAX and 16 <= self.int_bits <= _WIRE_OUT_MAX_BITS:
+                # straight to the wire form: the whole model is one run of draws and ONE launch (tensor rows; a host front end's
+                # (start, pointer, alpha, is float64) rows are plain float32 / float64 rows without flags)
+                from ._lib import TENSOR_F32, TENSOR_F64
+                from .engine import PackedVector
+                wrows = rows if len(rows[0]) == 6 else [(s_, p_, a_, 0.0, TENSOR_F64 if f64 else TENSOR_F32, 0) for s_, p_, a_, f64 in rows]
+                wire, du = PackedVector(eng, n, self.int_bits, path="fused"), _draws(eng, n, rng)
+                if not eng.quantize_encrypt_pack_tensors_dev(c.iter_index, c.idx, scheme, n, _cipher_mod.N_JOBS, wrows, q.element_bits, du, wire.buf):
+                    wire = DeviceVector(eng, n)               # (declined: today's launch on the same draws; _packed_result packs it)
+                    online(c.iter_index, c.idx, scheme, n, _cipher_mod.N_JOBS, 0, n, rows, q.element_bits, du, wire.ptr)
+            ct = wire if wire is not None else DeviceVector(eng, n + (1 if zzz is not None else 0))
+            at = len(order) if wire is not None else 0
             while at < len(order):
                 end, tot = at, 0
                 while end < len(order) and (end == at or tot + sizes[end] <= _RNG_RUN_MAX):
@@ -838,6 +900,9 @@ class FlasheClient(object):
             weights._weights[k0] = dout.download(np.float64, n)
             return self.unflatten_weights(weights)
         if not fus:
+            from .engine import PackedVector
+            if isinstance(weights._weights[k0], PackedVector):
+                weights._weights[k0] = self._unpacked(weights._weights[k0])
             res = self.cipher.decrypt(weights._weights[k0], device=False)
             if isinstance(res, np.ndarray) and res.dtype == np.uint64 and res.ndim == 2:
                 from .cipher import _from_limbs
@@ -878,11 +943,13 @@ class FlasheClient(object):
         """The flattened aggregate -- a DeviceVector, uint64 limbs, object ints or, with `keep` (out=), a framework integer tensor, read
         in place and its owner appended to keep -- as a DeviceVector of L limbs in HBM (a compact uint32 aggregate widened: the fused
         launches read one-limb vectors)."""
-        from .engine import DeviceVector
+        from .engine import DeviceVector, PackedVector
         c = self.cipher
         if keep is not None and interop.is_foreign(v):
             v, kv = c._foreign_vec(c.engine, v, "aggregate")
             keep.append(kv)
+        elif isinstance(v, PackedVector):
+            return v                                  # (_decrypt_floats takes it in one launch, or unpacks it)
         elif not isinstance(v, DeviceVector):
             v = np.asarray(v)
             if v.dtype == object:
@@ -915,8 +982,11 @@ class FlasheClient(object):
     def _sparse_floats(self, v, sizes, keep):
         """The sparse job's back end: the minus-mask pass over the aggregate v (result in HBM, appended to keep), then the unquantise of
         the dense model in a second launch.  Returns (the n float64 values as a device buffer, n)."""
+        from .engine import PackedVector
         q, c = self.quantizer, self.cipher
         eng = c.engine
+        if isinstance(v, PackedVector):
+            v = self._unpacked(v)
         dec = c._as_wide(c.decrypt(v, device=True))
         n = len(dec)
         table = self._back_table(sizes, n)
@@ -933,8 +1003,11 @@ class FlasheClient(object):
         all n elements, the last layer running to the end (decrypt + unquantise in one launch).  mode "ctx": with the ctx's prepared
         decrypt masks, the prefix lists being the extras, in ONE launch either way (two with extras); the cache is consumed."""
         from . import cipher as _cipher_mod
+        from .engine import PackedVector
         q, c = self.quantizer, self.cipher
         eng, n = c.engine, len(dv)
+        if isinstance(dv, PackedVector) and (self.batch or mode == "ctx" or dv.bits != self.int_bits):
+            dv = self._unpacked(dv)
         if mode == "ctx":
             c._check_prepared_len(c.next_iter_decrypt_prepared['add'], n)          # (the call-by-call decrypt's error; the cache stays)
         if self.batch:
@@ -952,6 +1025,16 @@ class FlasheClient(object):
             return dout
         table = self._back_table(sizes, n)
         dout = eng.alloc(max(8 * n, 16))
+        if isinstance(dv, PackedVector):
+            # the packed sum straight to the floats in ONE launch; declined (prefix lists longer than one each: dropouts, the single
+            # mask's decrypt) it is unpacked for today's launch
+            dv.wait_on(eng)
+            if n and eng.unpack_decrypt_unquantize_model_dev(c.iter_index, add_idx, minus_idx, n, _cipher_mod.N_JOBS, dv.buf, table, q.element_bits,
+                                                             q.num_clients, dout):
+                eng.hold([dv])
+                self._decrypt_done(mode)
+                return dout
+            dv = self._unpacked(dv)
         if mode == "ctx":
             eng.decrypt_prepared_unquantize_model_dev(c.iter_index, add_idx, minus_idx, n, _cipher_mod.N_JOBS, dv.buf, table, q.element_bits,
                                                       q.num_clients, dout)

@@ -734,10 +734,30 @@ class FlasheCipher(object):
         (jzf_aggregator.py:424-430) or, with packed=True, on the bit-packed integers
         (jzf_aggregator.py:406-419), returned unpacked.  Operands may be DeviceVectors (they stay where they are) or framework integer
         device tensors (read in place); device: as for encrypt() -- None returns a DeviceVector iff the first operand is one (or a
-        framework tensor).  out (new, element-wise only): a framework integer device tensor that receives the sum; `out` is returned."""
+        framework tensor).  out (new, element-wise only): a framework integer device tensor that receives the sum; `out` is returned.
+        PackedVector operands (new, packed=True only, all of one (n, bits)): summed where they lie (flashe_aggregate_packed_dev), the
+        result is a PackedVector; mixed operand kinds raise TypeError."""
         kw = {"stream": self._stream} if self._stream else {}
         eng = self._engine or self._engine_cls(bytes(32), self.int_bits, device=self._device, **kw)
         from . import interop
+        from .engine import PackedVector
+        if any(isinstance(c, PackedVector) for c in ciphertexts):
+            # operands already in their wire form (new): summed where they lie by the packed reduce, the result a PackedVector -- no pack,
+            # no unpack (jzf_aggregator.py:406-419 on the integers compress() built)
+            if not packed or out is not None or not all(isinstance(c, PackedVector) for c in ciphertexts):
+                raise TypeError("PackedVector operands: all of them, with packed=True and without out=")
+            n, bits = len(ciphertexts[0]), ciphertexts[0].bits
+            if bits != self.int_bits or any((len(c), c.bits) != (n, bits) for c in ciphertexts):
+                raise ValueError(f"PackedVector operands must all hold {n} elements of {self.int_bits} bits")
+            t0 = self._begin("aggregation")
+            res = PackedVector(eng, n, bits, path=ciphertexts[0].path)
+            for c in ciphertexts:
+                c.wait_on(eng)
+            if n:
+                eng.aggregate_packed_dev([c.buf for c in ciphertexts], res.n_limbs, n * bits, res.buf)
+            eng.hold(list(ciphertexts))
+            self._phase("aggregation", n, t0)
+            return res.mark_ready()
         if out is not None or any(interop.is_foreign(c) for c in ciphertexts):
             if out is not None and packed:
                 raise TypeError("out= is not supported for packed=True aggregation")

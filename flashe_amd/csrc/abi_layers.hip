@@ -520,6 +520,52 @@ int flashe_quantize_encrypt_tensors_dev(flashe_ctx *ctx, uint32_t iter, uint32_t
     return quantize_encrypt_model(ctx, iter, idx, scheme, n, n_jobs, first, count, cl.data(), n_layers, element_bits, u_dev, ct_dev);
 }
 
+// ---- the dense client step straight to and from the packed wire form (wire.hip; jzf_weights.py:155-231, jzf_aggregator.py:721-743 / :881-899) ----
+// what both directions admit, asked before anything else looks at the arguments: nothing is launched, staged or cleared outside it
+static int wire_admit(flashe_ctx *ctx, const char *who, uint64_t n, uint32_t n_jobs)
+{
+    if (small_wire_admits(ctx->env, n, n_jobs)) return FLASHE_OK;
+    return fail(ctx, FLASHE_ENOTSUP, "%s: needs 16 <= int_bits <= 64, 1 <= n < 2^32, n_jobs >= 1 and the table PRF (run the two calls it fuses)", who);
+}
+
+int flashe_quantize_encrypt_pack_tensors_dev(flashe_ctx *ctx, uint32_t iter, uint32_t idx, int scheme, uint64_t n, uint32_t n_jobs,
+                                             const flashe_tensor_layer *layers, int n_layers, int element_bits, const double *u_dev, uint64_t *packed_dev)
+{
+    CHECK_CTX(ctx);
+    int rc = check_scheme(ctx, scheme);
+    if (rc || (rc = wire_admit(ctx, "flashe_quantize_encrypt_pack_tensors_dev", n, n_jobs))) return rc;
+    if ((rc = check_model_front(ctx, n, n_jobs, 0, n, element_bits, u_dev, packed_dev)) || (rc = check_tensor_layers(ctx, n, layers, n_layers, true)) ||
+        (rc = check_double_idx(ctx, scheme, &idx, 1)))
+        return rc;
+    std::vector<flashe_codec_layer> cl;
+    Codec cq{};
+    if ((rc = tensor_codec_layers(ctx, n, layers, n_layers, 0, n, cl)) ||
+        (rc = stage_codec_layers(ctx, n, cl.data(), n_layers, true, element_bits, 1, 0, n, u_dev, nullptr, &cq)))
+        return rc;
+    HIP_TRY(ctx, launch_small_pack(ctx->env, iter, idx, scheme == FLASHE_SCHEME_DOUBLE, idx + 1, n, n_jobs, cq, packed_dev));
+    return FLASHE_OK;
+}
+
+int flashe_unpack_decrypt_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx, int n_minus,
+                                               uint64_t n, uint32_t n_jobs, const uint64_t *packed_dev, const flashe_codec_layer *layers, int n_layers,
+                                               int element_bits, int num_clients, double *out_dev)
+{
+    CHECK_CTX(ctx);
+    int rc = wire_admit(ctx, "flashe_unpack_decrypt_unquantize_model_dev", n, n_jobs);
+    if (rc) return rc;
+    if (n_add > 1 || n_minus > 1)
+        return fail(ctx, FLASHE_ENOTSUP, "flashe_unpack_decrypt_unquantize_model_dev: at most one add and one minus prefix (flashe_unpack_dev + flashe_decrypt_unquantize_model_dev take lists)");
+    if (!packed_dev || !out_dev) return fail(ctx, FLASHE_EINVAL, "null vector");
+    if (num_clients < 1) return fail(ctx, FLASHE_EINVAL, "num_clients must be >= 1");
+    if (n_add < 0 || n_minus < 0 || n_add + n_minus == 0) return fail(ctx, FLASHE_EINVAL, "unpack_decrypt_unquantize_model: at least one prefix (a round always has one)");
+    if ((n_add && !add_idx) || (n_minus && !minus_idx)) return fail(ctx, FLASHE_EINVAL, "null prefix list");
+    if ((rc = check_codec_bits(ctx, element_bits)) || (rc = check_aligned(ctx, {packed_dev, out_dev}, 8))) return rc;
+    Codec cq{};
+    if ((rc = stage_codec_layers(ctx, n, layers, n_layers, false, element_bits, num_clients, 0, n, nullptr, out_dev, &cq))) return rc;
+    HIP_TRY(ctx, launch_small_unpack(ctx->env, iter, n_add == 1, n_add ? add_idx[0] : 0u, n_minus == 1, n_minus ? minus_idx[0] : 0u, n, n_jobs, packed_dev, cq));
+    return FLASHE_OK;
+}
+
 // what every chained cohort asks of its arguments before its cipher indices
 static int cohort_check_args(flashe_ctx *ctx, const char *who, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers,
                              const void *const *src_dev, bool outs, int element_bits, const double *u_dev)

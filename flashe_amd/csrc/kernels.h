@@ -280,6 +280,18 @@ hipError_t launch_packed_resolve_carry(const LaunchEnv &env, uint64_t n_limbs, u
 hipError_t launch_pack(const LaunchEnv &env, uint64_t n, const uint64_t *in_dev, uint64_t *out_dev);
 hipError_t launch_unpack(const LaunchEnv &env, uint64_t n, const uint64_t *in_dev, uint64_t *out_dev);
 
+// The dense client step straight to and from the packed wire form (wire.hip; pack_kernel's layout: element j of n at bit (n - 1 - j) b).
+// small_wire_admits: 16 <= int_bits <= 64, 1 <= n < 2^32, n_jobs != 0, the table PRF.  Whole vectors only -- the packed form has no sub-range.
+// launch_small_pack: packed_dev[0 .. ceil(n b / 64)) = pack(encrypt(quantise)) of the model behind cq (a front-end layer table with the
+// draws, k0 = 0), add prefix add_idx and, dbl, minus prefix minus_idx: one fill of the packed limbs and one launch (prf_small_pack_kernel).
+// launch_small_unpack: cq.fout[j] = unquantise(element j of the packed sum + term(add_idx) - term(minus_idx)), either prefix optional
+// but not both (cq: a back-end layer table, k0 = 0): one launch (prf_small_unpack_kernel).  hipErrorNotSupported: nothing launched.
+bool small_wire_admits(const LaunchEnv &env, uint64_t n, uint32_t n_jobs);
+hipError_t launch_small_pack(const LaunchEnv &env, uint32_t iter, uint32_t add_idx, bool dbl, uint32_t minus_idx, uint64_t n, uint32_t n_jobs, const Codec &cq,
+                             uint64_t *packed_dev);
+hipError_t launch_small_unpack(const LaunchEnv &env, uint32_t iter, bool has_add, uint32_t add_idx, bool has_minus, uint32_t minus_idx, uint64_t n,
+                               uint32_t n_jobs, const uint64_t *packed_dev, const Codec &cq);
+
 hipError_t launch_fill(const LaunchEnv &env, uint64_t n, uint64_t lo, uint64_t hi, uint64_t *out_dev);
 // locations >= total are skipped and reported through env.err_flag (the reference raises IndexError, jzf_aggregator.py:150-165)
 hipError_t launch_scatter(const LaunchEnv &env, uint64_t total, uint64_t k, const uint32_t *loc_dev,

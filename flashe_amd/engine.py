@@ -376,6 +376,48 @@ class DeviceVector:
             pass
 
 
+class PackedVector:
+    """A ciphertext vector in its WIRE form, resident in HBM: the ceil(n bits / 64) limbs of the one integer
+    JZFTransferableWeights.compress builds (jzf_weights.py:155-195; element j of n at bits [bits (n - 1 - j), bits (n - j))).  What
+    FlasheClient.quantize_encrypt(packed=True) returns, FlasheCipher.aggregate(packed=True) sums and decrypt_unquantize takes; `path` says
+    how it was made: "fused" (one launch from the floats) or "staged" (today's passes + pack_dev), as CohortUpload.path."""
+
+    def __init__(self, engine, n, bits, buf=None, path="staged"):
+        self.engine, self.n, self.bits, self.path = engine, int(n), int(bits), path
+        self.n_limbs = (self.n * self.bits + 63) // 64
+        self.buf = buf if buf is not None else engine.alloc(max(8 * self.n_limbs, 16))
+        self._ready = None
+
+    def __len__(self):
+        return self.n
+
+    @property
+    def ptr(self):
+        return self.buf.ptr
+
+    @property
+    def device(self):
+        return getattr(self.engine, "device", 0)
+
+    mark_ready = DeviceVector.mark_ready
+    wait_on = DeviceVector.wait_on
+    __del__ = DeviceVector.__del__
+
+    def to_int(self):
+        """The Python int of the wire form: downloads the packed bytes only."""
+        return int.from_bytes(self.buf.download(np.uint64, self.n_limbs).tobytes(), "little")
+
+    @classmethod
+    def from_int(cls, engine, big_int, n, bits):
+        """Upload the packed integer of n elements of `bits` bits."""
+        out = cls(engine, n, bits)
+        big_int = int(big_int)
+        if big_int < 0 or big_int >> (out.n * out.bits):
+            raise ValueError(f"the integer does not fit {out.n} elements of {out.bits} bits")
+        out.buf.upload(np.frombuffer(big_int.to_bytes(8 * max(out.n_limbs, 1), "little"), dtype=np.uint64))
+        return out.mark_ready()
+
+
 class Graph:
     """A captured sequence of device calls (flashe_graph); launch() replays it on the engine's stream."""
 
@@ -716,6 +758,23 @@ class Engine:
         arr, nl = self._tensor_layers(layers)
         self._check(self._lib.flashe_quantize_encrypt_tensors_dev(self._h, it, idx, scheme, n, n_jobs, first, count, arr, nl, element_bits,
                                                                   self._ptr(u), self._ptr(ct)))
+
+    def quantize_encrypt_pack_tensors_dev(self, it, idx, scheme, n, n_jobs, layers, element_bits, u, packed):
+        """quantize_encrypt_tensors_dev over the whole vector + pack_dev in ONE launch (flashe_quantize_encrypt_pack_tensors_dev): packed =
+        ceil(n int_bits / 64) limbs.  False -- nothing was launched -- when the library declines the shape (FLASHE_ENOTSUP: the caller
+        runs the two calls), True otherwise."""
+        arr, nl = self._tensor_layers(layers)
+        return self._took(self._lib.flashe_quantize_encrypt_pack_tensors_dev(self._h, it, idx, scheme, n, n_jobs, arr, nl, element_bits, self._ptr(u),
+                                                                             self._ptr(packed)))
+
+    def unpack_decrypt_unquantize_model_dev(self, it, add_idx, minus_idx, n, n_jobs, packed, layers, element_bits, num_clients, out):
+        """unpack_dev + decrypt_unquantize_model_dev over the whole vector in ONE launch (flashe_unpack_decrypt_unquantize_model_dev);
+        False -- nothing was launched -- when the library declines (prefix lists longer than one each, another width), True otherwise."""
+        pa, _a = _u32_list(add_idx)
+        pm, _m = _u32_list(minus_idx)
+        arr, nl = self._codec_layers(layers)
+        return self._took(self._lib.flashe_unpack_decrypt_unquantize_model_dev(self._h, it, pa, len(add_idx), pm, len(minus_idx), n, n_jobs, self._ptr(packed),
+                                                                               arr, nl, element_bits, num_clients, self._ptr(out)))
 
     def _cohort_launch(self, name, it, idx, ns, n_jobs, layers, srcs, dtypes, bits, u, cts, *vecs):
         """The library's chained cohort launch `name` (_lib.COHORT_LAUNCHES): the shared table, the sources, the ciphertext pointers and -- a

@@ -24,8 +24,12 @@ def _engine(bits, device=0):
 
 def to_big_int(flatten_array, num_bits, device=0):
     """`_to_bytes(flatten_array, num_bits)` / `_to_bytes_old` (jzf_weights.py:36-84) -> (int, length).  A `DeviceVector` (a ciphertext
-    that stayed in HBM) is packed where it lies: only the n * num_bits / 8 packed bytes come down."""
-    from .engine import DeviceVector
+    that stayed in HBM) is packed where it lies: only the n * num_bits / 8 packed bytes come down.  A `PackedVector` (a ciphertext that was
+    made in its wire form) needs no pack launch at all: its bytes come down as they are."""
+    from .engine import DeviceVector, PackedVector
+    if isinstance(flatten_array, PackedVector):
+        _check_packed_bits(flatten_array, num_bits)
+        return (flatten_array.to_int() if len(flatten_array) else 0), len(flatten_array)
     eng = _engine(num_bits, device)
     if isinstance(flatten_array, DeviceVector):
         dv = flatten_array.widened(eng) if flatten_array.compact else flatten_array
@@ -52,11 +56,20 @@ def to_big_int(flatten_array, num_bits, device=0):
     return int.from_bytes(packed.tobytes(), "little"), n
 
 
+def _check_packed_bits(pv, bits):
+    if pv.bits != bits:
+        raise ValueError(f"a PackedVector of {pv.bits}-bit fields cannot pass as {bits}-bit fields")
+
+
 def from_big_int(big_int, length, num_bits, device=0, as_object=True, as_device=False):
     """`_from_bytes(...)` followed by `reverse()` (jzf_weights.py:87-137, :225-228): the values in their
-    original order.  as_device: unpacked in HBM and returned as a `DeviceVector` (the arbiter's operands of `aggregate`)."""
-    from .engine import DeviceVector
+    original order.  as_device: unpacked in HBM and returned as a `DeviceVector` (the arbiter's operands of `aggregate`);
+    as_device="packed": uploaded as it is and returned as a `PackedVector` -- no unpack launch (the operands of
+    `aggregate(packed=True)`, what `FlasheClient.decrypt_unquantize` takes in one launch)."""
+    from .engine import DeviceVector, PackedVector
     eng = _engine(num_bits, device)
+    if as_device == "packed":
+        return PackedVector.from_int(eng, big_int, length, num_bits)
     if length == 0:
         return DeviceVector(eng, 0) if as_device else np.array([], dtype=object if as_object else np.uint64)
     n_limbs = (length * num_bits + 63) // 64
@@ -80,8 +93,12 @@ class TransferableWeights(object):
 
     def compress(self):
         res, self._shape = {}, {}
-        from .engine import DeviceVector
+        from .engine import DeviceVector, PackedVector
         for k, w in self._weights.items():
+            if isinstance(w, PackedVector):                  # already in its wire form: no pack launch, the packed bytes come down
+                self._shape[k] = (len(w),)
+                res[k] = to_big_int(w, self._bits, self._device)[0]
+                continue
             if isinstance(w, DeviceVector):                  # a ciphertext that stayed in HBM: packed there, only the packed bytes come down
                 self._shape[k] = (len(w),)
                 res[k] = to_big_int(w, self._bits, self._device)[0]
@@ -92,7 +109,8 @@ class TransferableWeights(object):
         self._weights = res
 
     def decompress(self, as_device=False):
-        """as_device: every layer comes back as a flat `DeviceVector` in HBM (the arbiter's operands of `aggregate`) instead of an object array."""
+        """as_device: every layer comes back as a flat `DeviceVector` in HBM (the arbiter's operands of `aggregate`) instead of an object
+        array; as_device="packed": as a `PackedVector`, uploaded as it is with no unpack launch."""
         out = {}
         for k, big in self._weights.items():
             shape = self._shape[k]

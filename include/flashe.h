@@ -98,7 +98,9 @@ typedef struct flashe_ctx flashe_ctx;
  *      np.random.PCG64 / PCG64DXSM, np.random.default_rng's generator) with flashe_pcg64_cohort_grid + flashe_pcg64_cohort_lane_draws;
  *      flashe_quantize_encrypt_cohort_u64_dev (the cohort's chained launch in the one-limb layout, int_bits 33 .. 64);
  *      flashe_quantize_encrypt_cohort_runs_u64_dev (the same launch for a round in which clients dropped out);
- *      flashe_cohort_cut_pieces_u64 + flashe_quantize_encrypt_cohort_cut_u64_dev (the one-limb cohort's cut launch for a short vector) */
+ *      flashe_cohort_cut_pieces_u64 + flashe_quantize_encrypt_cohort_cut_u64_dev (the one-limb cohort's cut launch for a short vector);
+ *      flashe_quantize_encrypt_pack_tensors_dev / flashe_unpack_decrypt_unquantize_model_dev (the dense client step straight to and from
+ *      the packed wire form at int_bits 16 .. 64: one launch each way, no unpacked ciphertext vector) */
 #define FLASHE_ABI_VERSION 4
 int flashe_abi_version(void);
 int flashe_device_count(int *count);
@@ -712,6 +714,25 @@ typedef struct flashe_tensor_layer {
 int flashe_quantize_encrypt_tensors_dev(flashe_ctx *ctx, uint32_t iter, uint32_t idx, int scheme, uint64_t n, uint32_t n_jobs,
                                         uint64_t first, uint64_t count, const flashe_tensor_layer *layers, int n_layers,
                                         int element_bits, const double *u_dev, uint64_t *ct_dev);
+/* The dense client step straight to the packed WIRE form (new; jzf_weights.py:155-231, jzf_aggregator.py:721-743 / :881-899): what
+ * flashe_quantize_encrypt_tensors_dev over the whole vector followed by flashe_pack_dev computes, bit for bit, in one fill of the packed
+ * limbs and ONE launch -- the uint64 ciphertext vector never exists.  packed_dev: ceil(n int_bits / 64) limbs, 8-byte aligned, element j
+ * at bits [int_bits (n - 1 - j), int_bits (n - j)), the unused top bits of the last limb zero.  Layers are staged exactly as
+ * flashe_quantize_encrypt_tensors_dev stages them.  Whole vectors only: the packed form has no sub-range.
+ * FLASHE_ENOTSUP -- checked before anything else, nothing launched, staged or cleared -- unless 16 <= int_bits <= 64, 1 <= n < 2^32,
+ * n_jobs >= 1 and the PRF backend is the table one; FLASHE_EINVAL as flashe_quantize_encrypt_tensors_dev.  Not capturable. */
+int flashe_quantize_encrypt_pack_tensors_dev(flashe_ctx *ctx, uint32_t iter, uint32_t idx, int scheme, uint64_t n, uint32_t n_jobs,
+                                             const flashe_tensor_layer *layers, int n_layers, int element_bits, const double *u_dev,
+                                             uint64_t *packed_dev);
+/* The way back (new; jzf_weights.py:155-231, jzf_aggregator.py:721-743 / :881-899): what flashe_unpack_dev followed by
+ * flashe_decrypt_unquantize_model_dev over the whole vector computes, bit for bit, in ONE launch -- the unpacked element vector never
+ * exists.  packed_dev: the packed sum as above (read only); out_dev: n float64 values.
+ * FLASHE_ENOTSUP -- checked first, nothing launched -- outside the admission above, and for n_add > 1 or n_minus > 1 (a round with
+ * dropouts, the single mask's decrypt: those lists stay with the two calls); FLASHE_EINVAL as flashe_decrypt_unquantize_model_dev. */
+int flashe_unpack_decrypt_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx,
+                                               int n_minus, uint64_t n, uint32_t n_jobs, const uint64_t *packed_dev,
+                                               const flashe_codec_layer *layers, int n_layers, int element_bits, int num_clients,
+                                               double *out_dev);
 /* A COHORT of n_clients consecutive clients (cipher indices first_idx .. first_idx + n_clients - 1, double mask) hosted on this GPU (new):
  * ONE chained launch quantises every client's float model (jzf_quantize.py:55-67, client c's element k with the draw
  * u_dev[c * n + k]), encrypts with the PRF streams the consecutive clients share (n_clients + 1 streams instead of 2 n_clients,

@@ -1,0 +1,33 @@
+"""CPU test: the wire kernels (wire.hip: prf_small_pack_kernel<DBL>, prf_small_unpack_kernel) fit the budget that keeps one 1,024-thread
+workgroup resident per CU beside the AES tables -- at most 128 VGPRs, no scratch, no VGPR spills, static LDS no larger than
+prf_small_chain_kernel's -- per the code objects inside the built library (tools/kernel_resources.py); their entry points are exported,
+bound and indexed without an ABI bump."""
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "flashe_amd", "libflashe_hip.so")
+SYMS = ("flashe_quantize_encrypt_pack_tensors_dev", "flashe_unpack_decrypt_unquantize_model_dev")
+
+
+def test_wire_kernels_fit_the_budget():
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_resources
+    res = kernel_resources.resources(LIB)
+    wire = {k: r for k, r in res.items() if "prf_small_pack_kernel<" in k or "prf_small_unpack_kernel(" in k}
+    assert len(wire) == 3, sorted(wire)
+    chain_lds = max(r["lds_bytes_static"] for k, r in res.items() if "prf_small_chain_kernel<" in k)
+    for k, r in wire.items():
+        assert r["scratch_bytes_per_lane"] == 0 and r["vgpr_spills"] == 0, (k, r)
+        assert r["vgpr"] + r["agpr"] <= 128, (k, r)
+        assert r["max_workgroup"] == 1024, (k, r)
+        assert r["lds_bytes_static"] <= chain_lds, (k, r, chain_lds)
+
+
+def test_the_entry_points_are_exported_bound_and_indexed():
+    from flashe_amd import _lib
+    lib = _lib.load()
+    index = open(os.path.join(ROOT, "include", "ENTRY_POINTS.md")).read()
+    for sym in SYMS:
+        assert sym in _lib.EXPORTED_SYMBOLS and hasattr(lib, sym) and f"`{sym}`" in index, sym
+    assert lib.flashe_abi_version() == 4
