@@ -1,6 +1,7 @@
 """One dense round in the WIRE form: every client goes from its float model straight to the packed integer it sends
 (quantize_encrypt(packed=True): one launch at int_bits 16 .. 64), the arbiter adds the packed integers where they lie, and a client takes
-the packed sum back to floats in one launch.  Run on a machine with a GPU:  python examples/wire_round.py"""
+the packed sum back to floats in one launch.  --batch: the batched int_bits 120 job (six quantised values per element), which takes its one
+launch out with packed="fused".  Run on a machine with a GPU:  python examples/wire_round.py [--batch]"""
 import os
 import sys
 
@@ -21,6 +22,9 @@ class Weights:
 
 
 def main():
+    batch = "--batch" in sys.argv[1:]
+    if batch:
+        ARGS["quantize"].update(int_bits=120, batch=True)
     rs = np.random.RandomState(0)
     models = [{k: rs.normal(0, 0.05, s).astype(np.float32) for k, s in SHAPES.items()} for _ in range(C)]
     clients = []
@@ -33,7 +37,7 @@ def main():
         clients.append(cl)
     uploads = []
     for cl, m in zip(clients, models):
-        w = cl.quantize_encrypt(Weights(m), packed=True)
+        w = cl.quantize_encrypt(Weights(m), packed="fused" if batch else True)
         uploads.append(w._weights[w.walking_order[0]])                 # a PackedVector; .to_int() is what goes on the wire
     print("upload path:", uploads[0].path, "-", (uploads[0].to_int().bit_length() + 7) // 8, "bytes per client")
     total = clients[0].cipher.aggregate(uploads, packed=True)           # the arbiter: the packed integers added where they lie

@@ -21,6 +21,12 @@ _RNG_RUN_MAX = 1 << 26          # draws per device call of quantize_encrypt (512
 # than either form's spread at int_bits 20 and 23 (x 1.40 - 1.78) and leads within the spread at 64 (x 1.10 - 1.14: the fill of 8-byte limbs),
 # so 33 .. 64 stay staged; the way back takes its one launch at every width 16 .. 64 (x 1.22 - 1.81).  profiles/r39_wire_client_step.log
 _WIRE_OUT_MAX_BITS = 32
+# decrypt_unquantize takes a BATCHED job's packed sum (int_bits 65 .. 128) to the floats in one launch from this many batched elements on:
+# measured against unpack_dev + decrypt_dev + unbatch_unquantize_model_dev at int_bits 120 / 128 in two processes, it wins by more than
+# either form's spread at 1,666,668 and 4,259,506 elements in both (x 1.46 - 1.66); at 10,285 .. 500,001 elements the medians lead too
+# (x 1.09 - 1.49) but single outliers of 0.04 - 0.12 ms turn the verdict in one process or the other, so those stay staged.  A coarse
+# threshold: nothing was measured between 500,001 and 1,666,668.  profiles/r40_wire_batched_step.log
+_WIDE_WIRE_BACK_MIN_ELEMS = 1_666_668
 
 __all__ = ["dynamic_masking_choice", "FlasheClient", "FlasheCohort", "CohortPlan", "CohortUpload", "plan_cohort", "FlasheSparseCohort",
            "SparseCohortPlan", "SparseCohortEncoding", "SparseCohortUpload", "plan_sparse_cohort"]
@@ -578,6 +584,12 @@ class FlasheClient(object):
         JZFTransferableWeights.compress builds (device=False).  A dense un-batched job at int_bits 16 .. 32 goes from the floats to the
         packed limbs in ONE launch (flashe_quantize_encrypt_pack_tensors_dev, path "fused"); a batched job, the sparse job's 'zzz', a
         consumed precompute cache, other widths and a cipher with `masks` run today's step followed by pack_dev (path "staged").
+        packed="fused" (new) takes the one launch WHEREVER the library admits it: a batched job at int_bits 65 .. 128 goes from the floats
+        to the packed limbs in one launch too (flashe_quantize_batch_encrypt_pack_model_dev / _tensors_dev: quantise + batch + encrypt +
+        pack, no 16-byte vector in HBM), and an un-batched job takes its launch at int_bits 33 .. 64 as well.  The same integer as
+        packed=True, bit for bit; a consumed precompute cache, the sparse job's 'zzz', a model above _RNG_RUN_MAX values, an engine
+        without the entry point and a call the library declines run the staged sequence on the same draws (path "staged").  Any other
+        value of `packed` is read as true or false.
 
         degree (new): `weights *= degree` first (jzf_aggregator.py:676, the client's sample count times aggregate_every_n_epoch): every
         layer but the sparse job's 'zzz' becomes a NEW array `layer * degree` in the dtype NumPy gives that product (a float32 layer stays
@@ -620,7 +632,8 @@ class FlasheClient(object):
         rng = _check_rng(rng)
         self.degree = _check_degree(degree, "degree")
         if packed:
-            self._to_wire = True                      # (_encrypt_tail: take the one launch where the step admits it)
+            # (_encrypt_tail: True = take the one launch where it is the measured choice; "fused" = wherever the library admits it)
+            self._to_wire = "fused" if isinstance(packed, str) and packed == "fused" else True
             try:
                 return self._packed_result(self.quantize_encrypt(weights, True, normalize, rng, degree), device)
             finally:
@@ -711,13 +724,14 @@ class FlasheClient(object):
         ptrs, keep = _stage_host_layers(eng, host)
         rows = [(sizes[li] if self.batch else starts[li], ptrs[li], q.alpha_list[li], host[li].dtype == np.float64) for li in range(len(order))]
         launch = (eng.quantize_encrypt_model_dev, eng.quantize_encrypt_prepared_model_dev, eng.quantize_batch_model_dev,
-                  eng.quantize_batch_encrypt_prepared_model_dev)
+                  eng.quantize_batch_encrypt_prepared_model_dev, getattr(eng, "quantize_batch_encrypt_pack_model_dev", None))
         return mode, order, zzz, sizes, starts, shape_dict, rows, launch, keep
 
     def _encrypt_tail(self, weights, device, mode, order, zzz, sizes, starts, shape_dict, rows, launch, keep, hold=None, normalize=False,
                       rng=None):
         """The fused step behind either front end: the draws, the launches and the result.  `rows` are the layers `order` (sizes, starts,
-        shape_dict) as the four entry points in `launch` -- un-batched online and prepared, batched online and prepared -- read them; mode
+        shape_dict) as the entry points in `launch` -- un-batched online and prepared, batched online and prepared, and the batched job's one
+        launch to the wire form (None: the engine has none) -- read them; mode
         is _prepared_mode of the encrypt cache; zzz the sparse job's trailing value (host) or None; keep what the launches read: it lives to
         the end of the call.  The tensor front end also passes hold (the owners of the caller's tensors: held on the engine until the
         launches have finished) and normalize (the 'zzz' value is still to be normalised -- the host front end has normalised the whole
@@ -726,7 +740,7 @@ class FlasheClient(object):
         from .engine import DeviceVector
         q, c = self.quantizer, self.cipher
         eng, n = c.engine, sum(sizes)
-        online, prepared, batch, batch_prepared = launch
+        online, prepared, batch, batch_prepared, batch_wire = launch
         scheme = 1 if c.masking_scheme == "double" else 0
         if self.batch:
             # quantise + batch of the whole model in ONE launch (per-layer alpha, per-layer zero padding), then the encrypt of the flattened
@@ -738,10 +752,20 @@ class FlasheClient(object):
             if mode == "ctx":
                 self._refuse_prepared_len(n_elems, n, rng)
             du = _draws(eng, n, rng) if n else eng.alloc(16)
-            ct = DeviceVector(eng, n_elems)
-            if mode == "ctx":                   # quantise + batch + the prepared masks: one launch, no AES
+            ct = None
+            if (getattr(self, "_to_wire", False) == "fused" and mode != "ctx" and zzz is None and 0 < n <= _RNG_RUN_MAX and batch_wire is not None
+                    and self.int_bits > 64):
+                # straight to the wire form: quantise + batch + encrypt + pack in ONE launch (its limbs are allocated only at the widths
+                # the launch exists for; the library has the last word); declined: the staged launches below on the same draws
+                from .engine import PackedVector
+                ct = PackedVector(eng, n_elems, self.int_bits, path="fused")
+                if not batch_wire(c.iter_index, c.idx, scheme, rows, q.element_bits, field_bits, du, n_elems, ct.buf):
+                    ct = None
+            if ct is None and mode == "ctx":    # quantise + batch + the prepared masks: one launch, no AES
+                ct = DeviceVector(eng, n_elems)
                 batch_prepared(rows, q.element_bits, field_bits, du, n_elems, ct.buf)
-            else:
+            elif ct is None:
+                ct = DeviceVector(eng, n_elems)
                 pt = eng.alloc_vec(max(n_elems, 1))
                 batch(rows, q.element_bits, field_bits, du, n_elems, pt)
                 if n_elems:
@@ -755,7 +779,9 @@ class FlasheClient(object):
             if mode == "ctx":
                 self._refuse_prepared_len(n, n, rng)
             wire = None
-            if getattr(self, "_to_wire", False) and mode != "ctx" and zzz is None and 0 < n <= _RNG_RUN_MAX and 16 <= self.int_bits <= _WIRE_OUT_MAX_BITS:
+            to_wire = getattr(self, "_to_wire", False)
+            if (to_wire and mode != "ctx" and zzz is None and 0 < n <= _RNG_RUN_MAX and 16 <= self.int_bits <= (64 if to_wire == "fused" else _WIRE_OUT_MAX_BITS)
+                    and hasattr(eng, "quantize_encrypt_pack_tensors_dev")):
                 # straight to the wire form: the whole model is one run of draws and ONE launch (tensor rows; a host front end's
                 # (start, pointer, alpha, is float64) rows are plain float32 / float64 rows without flags)
                 from ._lib import TENSOR_F32, TENSOR_F64
@@ -1006,13 +1032,25 @@ class FlasheClient(object):
         from .engine import PackedVector
         q, c = self.quantizer, self.cipher
         eng, n = c.engine, len(dv)
-        if isinstance(dv, PackedVector) and (self.batch or mode == "ctx" or dv.bits != self.int_bits):
+        wide_wire = (isinstance(dv, PackedVector) and self.batch and mode != "ctx" and dv.bits == self.int_bits and n >= _WIDE_WIRE_BACK_MIN_ELEMS
+                     and hasattr(eng, "unpack_decrypt_unbatch_unquantize_model_dev"))
+        if isinstance(dv, PackedVector) and not wide_wire and (self.batch or mode == "ctx" or dv.bits != self.int_bits):
             dv = self._unpacked(dv)
         if mode == "ctx":
             c._check_prepared_len(c.next_iter_decrypt_prepared['add'], n)          # (the call-by-call decrypt's error; the cache stays)
         if self.batch:
             layers, field_bits = self._batched_back_table(sizes, n)
             dout = eng.alloc(max(8 * sum(sizes), 16))
+            if wide_wire:
+                # the packed sum of a batched job straight to the floats in ONE launch (int_bits 65 .. 128); declined (prefix lists
+                # longer than one each, another width) it is unpacked for today's launches
+                dv.wait_on(eng)
+                if n and eng.unpack_decrypt_unbatch_unquantize_model_dev(c.iter_index, add_idx, minus_idx, layers, q.element_bits, field_bits,
+                                                                         q.num_clients, dv.buf, n, dout):
+                    eng.hold([dv])
+                    self._decrypt_done(mode)
+                    return dout
+                dv = self._unpacked(dv)
             if mode == "ctx":
                 eng.decrypt_prepared_unbatch_unquantize_model_dev(c.iter_index, add_idx, minus_idx, _cipher_mod.N_JOBS, layers, q.element_bits, field_bits,
                                                                   q.num_clients, dv.buf, n, dout)
@@ -1109,7 +1147,9 @@ class FlasheClient(object):
             n += size
         launch = (eng.quantize_encrypt_tensors_dev, eng.quantize_encrypt_prepared_tensors_dev,                # (the batched two also take n)
                   lambda r, *a: eng.quantize_batch_tensors_dev(r, n, *a),
-                  lambda r, *a: eng.quantize_batch_encrypt_prepared_tensors_dev(r, n, *a))
+                  lambda r, *a: eng.quantize_batch_encrypt_prepared_tensors_dev(r, n, *a),
+                  (lambda it, idx, sch, r, *a: eng.quantize_batch_encrypt_pack_tensors_dev(it, idx, sch, r, n, *a))
+                  if hasattr(eng, "quantize_batch_encrypt_pack_tensors_dev") else None)
         shape_dict = {k: layer[4] for k, layer in zip(order, layers)}
         return self._encrypt_tail(weights, device, mode, order, zzz, sizes, starts, shape_dict, rows, launch, keep, hold=owners, normalize=normalize,
                                   rng=rng)

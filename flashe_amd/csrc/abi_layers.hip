@@ -1336,6 +1336,63 @@ int flashe_quantize_batch_tensors_dev(flashe_ctx *ctx, const flashe_tensor_layer
     return flashe_quantize_batch_model_dev(ctx, bl.data(), n_layers, element_bits, field_bits, u_dev, n_elems, out_dev);
 }
 
+// ---- the batched client step straight to and from the packed wire form (wire_wide.hip; jzf_weights.py:155-231) ----
+// what both directions admit, asked before anything else looks at the arguments: nothing is launched or staged outside it
+static int wide_wire_admit(flashe_ctx *ctx, const char *who, uint64_t n_elems)
+{
+    if (wide_wire_admits(ctx->env, n_elems)) return FLASHE_OK;
+    return fail(ctx, FLASHE_ENOTSUP, "%s: needs 65 <= int_bits <= 128, 1 <= n_elems < 2^32 and the table PRF (run the calls it fuses)", who);
+}
+
+int flashe_quantize_batch_encrypt_pack_model_dev(flashe_ctx *ctx, uint32_t iter, uint32_t idx, int scheme, const flashe_batch_layer *layers, int n_layers,
+                                                 int element_bits, int field_bits, const double *u_dev, uint64_t n_elems, uint64_t *packed_dev)
+{
+    CHECK_CTX(ctx);
+    int rc = check_scheme(ctx, scheme);
+    if (rc || (rc = wide_wire_admit(ctx, "flashe_quantize_batch_encrypt_pack_model_dev", n_elems)) || (rc = check_double_idx(ctx, scheme, &idx, 1))) return rc;
+    BatchTab bt;
+    if ((rc = stage_batch_layers(ctx, layers, n_layers, true, element_bits, field_bits, 1, n_elems, &bt))) return rc;
+    if (!u_dev || !packed_dev) return fail(ctx, FLASHE_EINVAL, "null vector");
+    if ((rc = check_vec_aligned(ctx, {packed_dev})) || (rc = check_aligned(ctx, {u_dev}, 8))) return rc;
+    HIP_TRY(ctx, launch_wide_pack(ctx->env, iter, idx, scheme == FLASHE_SCHEME_DOUBLE, idx + 1, bt.tab, bt.n_tab, field_bits, u_dev, n_elems, packed_dev));
+    return FLASHE_OK;
+}
+
+int flashe_quantize_batch_encrypt_pack_tensors_dev(flashe_ctx *ctx, uint32_t iter, uint32_t idx, int scheme, const flashe_tensor_layer *layers, int n_layers,
+                                                   uint64_t n_values, int element_bits, int field_bits, const double *u_dev, uint64_t n_elems,
+                                                   uint64_t *packed_dev)
+{
+    CHECK_CTX(ctx);
+    int rc = check_scheme(ctx, scheme);
+    if (rc || (rc = wide_wire_admit(ctx, "flashe_quantize_batch_encrypt_pack_tensors_dev", n_elems)) || (rc = check_double_idx(ctx, scheme, &idx, 1)) ||
+        (rc = check_tensor_layers(ctx, n_values, layers, n_layers, true)))
+        return rc;
+    std::vector<flashe_batch_layer> bl;
+    if ((rc = tensor_batch_layers(ctx, layers, n_layers, n_values, element_bits, field_bits, u_dev, n_elems, packed_dev, bl))) return rc;
+    return flashe_quantize_batch_encrypt_pack_model_dev(ctx, iter, idx, scheme, bl.data(), n_layers, element_bits, field_bits, u_dev, n_elems, packed_dev);
+}
+
+int flashe_unpack_decrypt_unbatch_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx, int n_minus,
+                                                       const flashe_batch_layer *layers, int n_layers, int element_bits, int field_bits, int num_clients,
+                                                       const uint64_t *packed_dev, uint64_t n_elems, double *out_dev)
+{
+    CHECK_CTX(ctx);
+    int rc = wide_wire_admit(ctx, "flashe_unpack_decrypt_unbatch_unquantize_model_dev", n_elems);
+    if (rc) return rc;
+    if (n_add > 1 || n_minus > 1)
+        return fail(ctx, FLASHE_ENOTSUP, "flashe_unpack_decrypt_unbatch_unquantize_model_dev: at most one add and one minus prefix (flashe_unpack_dev, flashe_decrypt_dev and flashe_unbatch_unquantize_model_dev take lists)");
+    if (num_clients < 1) return fail(ctx, FLASHE_EINVAL, "num_clients must be >= 1");
+    if (n_add < 0 || n_minus < 0 || n_add + n_minus == 0) return fail(ctx, FLASHE_EINVAL, "unpack_decrypt_unbatch_unquantize_model: at least one prefix (a round always has one)");
+    if ((n_add && !add_idx) || (n_minus && !minus_idx)) return fail(ctx, FLASHE_EINVAL, "null prefix list");
+    BatchTab bt;
+    if ((rc = stage_batch_layers(ctx, layers, n_layers, false, element_bits, field_bits, num_clients, n_elems, &bt))) return rc;
+    if (!packed_dev || !out_dev) return fail(ctx, FLASHE_EINVAL, "null vector");
+    if ((rc = check_aligned(ctx, {packed_dev, out_dev}, 8))) return rc;
+    HIP_TRY(ctx, launch_wide_unpack(ctx->env, iter, n_add == 1, n_add ? add_idx[0] : 0u, n_minus == 1, n_minus ? minus_idx[0] : 0u, bt.tab, bt.n_tab, field_bits,
+                                    packed_dev, n_elems, out_dev));
+    return FLASHE_OK;
+}
+
 int flashe_store_layers_dev(flashe_ctx *ctx, const double *in_dev, uint64_t n, const flashe_tensor_layer *layers, int n_layers, uint64_t block,
                             double *stats_dev)
 {

@@ -292,6 +292,20 @@ hipError_t launch_small_pack(const LaunchEnv &env, uint32_t iter, uint32_t add_i
 hipError_t launch_small_unpack(const LaunchEnv &env, uint32_t iter, bool has_add, uint32_t add_idx, bool has_minus, uint32_t minus_idx, uint64_t n,
                                uint32_t n_jobs, const uint64_t *packed_dev, const Codec &cq);
 
+// The BATCHED client step straight to and from the packed wire form at int_bits 65 .. 128 (wire_wide.hip; BatchLayer tables as
+// launch_quantize_batch_model / launch_unbatch_unquantize_model take them, bs = int_bits / field_bits values per element).
+// wide_wire_admits: 65 <= int_bits <= 128, 1 <= n_elems < 2^32, the table PRF.  Whole vectors only.
+// launch_wide_pack: packed_dev[0 .. ceil(n_elems b / 64)) = pack(encrypt(quantize_batch_model)) in ONE launch (prf_wide_pack_kernel): every
+// limb is written, none needs clearing; packed_dev 16-byte aligned.  launch_wide_unpack: out_dev[value] = unbatch_unquantize_model of
+// (the packed sum + term(add_idx) - term(minus_idx)), either prefix optional but not both, in ONE launch (prf_wide_unpack_kernel).
+// hipErrorNotSupported: nothing launched.
+bool wide_wire_admits(const LaunchEnv &env, uint64_t n_elems);
+struct BatchLayer;
+hipError_t launch_wide_pack(const LaunchEnv &env, uint32_t iter, uint32_t add_idx, bool dbl, uint32_t minus_idx, const BatchLayer *layers_dev, int n_layers,
+                            int field_bits, const double *u_dev, uint64_t n_elems, uint64_t *packed_dev);
+hipError_t launch_wide_unpack(const LaunchEnv &env, uint32_t iter, bool has_add, uint32_t add_idx, bool has_minus, uint32_t minus_idx, const BatchLayer *layers_dev,
+                              int n_layers, int field_bits, const uint64_t *packed_dev, uint64_t n_elems, double *out_dev);
+
 hipError_t launch_fill(const LaunchEnv &env, uint64_t n, uint64_t lo, uint64_t hi, uint64_t *out_dev);
 // locations >= total are skipped and reported through env.err_flag (the reference raises IndexError, jzf_aggregator.py:150-165)
 hipError_t launch_scatter(const LaunchEnv &env, uint64_t total, uint64_t k, const uint32_t *loc_dev,

@@ -776,6 +776,30 @@ class Engine:
         return self._took(self._lib.flashe_unpack_decrypt_unquantize_model_dev(self._h, it, pa, len(add_idx), pm, len(minus_idx), n, n_jobs, self._ptr(packed),
                                                                                arr, nl, element_bits, num_clients, self._ptr(out)))
 
+    def quantize_batch_encrypt_pack_model_dev(self, it, idx, scheme, layers, element_bits, field_bits, u, n_elems, packed):
+        """quantize_batch_model_dev + encrypt_dev + pack_dev of a batched job at int_bits 65 .. 128 in ONE launch
+        (flashe_quantize_batch_encrypt_pack_model_dev): packed = ceil(n_elems int_bits / 64) limbs, every one written.  False -- nothing
+        was launched -- when the library declines (FLASHE_ENOTSUP: the caller runs the three calls), True otherwise."""
+        arr, nl = self._batch_layers(layers)
+        return self._took(self._lib.flashe_quantize_batch_encrypt_pack_model_dev(self._h, it, idx, scheme, arr, nl, element_bits, field_bits, self._ptr(u),
+                                                                                 int(n_elems), self._ptr(packed)))
+
+    def quantize_batch_encrypt_pack_tensors_dev(self, it, idx, scheme, layers, n_values, element_bits, field_bits, u, n_elems, packed):
+        """The same with tensor layers, staged as quantize_batch_tensors_dev stages them (flashe_quantize_batch_encrypt_pack_tensors_dev)."""
+        arr, nl = self._tensor_layers(layers)
+        return self._took(self._lib.flashe_quantize_batch_encrypt_pack_tensors_dev(self._h, it, idx, scheme, arr, nl, int(n_values), element_bits, field_bits,
+                                                                                   self._ptr(u), int(n_elems), self._ptr(packed)))
+
+    def unpack_decrypt_unbatch_unquantize_model_dev(self, it, add_idx, minus_idx, layers, element_bits, field_bits, num_clients, packed, n_elems, out):
+        """unpack_dev + decrypt_dev + unbatch_unquantize_model_dev in ONE launch (flashe_unpack_decrypt_unbatch_unquantize_model_dev);
+        False -- nothing was launched -- when the library declines (prefix lists longer than one each, another width), True otherwise."""
+        pa, _a = _u32_list(add_idx)
+        pm, _m = _u32_list(minus_idx)
+        arr, nl = self._batch_layers(layers)
+        return self._took(self._lib.flashe_unpack_decrypt_unbatch_unquantize_model_dev(self._h, it, pa, len(add_idx), pm, len(minus_idx), arr, nl, element_bits,
+                                                                                       field_bits, num_clients, self._ptr(packed), int(n_elems),
+                                                                                       self._ptr(out)))
+
     def _cohort_launch(self, name, it, idx, ns, n_jobs, layers, srcs, dtypes, bits, u, cts, *vecs):
         """The library's chained cohort launch `name` (_lib.COHORT_LAUNCHES): the shared table, the sources, the ciphertext pointers and -- a
         form that takes them as a list (_lib.cohort_by_list) -- the checked cipher indices marshalled, one call.  ns = (n,) or (n_values, n_elems), bits = (element_bits,) or

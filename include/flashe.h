@@ -100,7 +100,10 @@ typedef struct flashe_ctx flashe_ctx;
  *      flashe_quantize_encrypt_cohort_runs_u64_dev (the same launch for a round in which clients dropped out);
  *      flashe_cohort_cut_pieces_u64 + flashe_quantize_encrypt_cohort_cut_u64_dev (the one-limb cohort's cut launch for a short vector);
  *      flashe_quantize_encrypt_pack_tensors_dev / flashe_unpack_decrypt_unquantize_model_dev (the dense client step straight to and from
- *      the packed wire form at int_bits 16 .. 64: one launch each way, no unpacked ciphertext vector) */
+ *      the packed wire form at int_bits 16 .. 64: one launch each way, no unpacked ciphertext vector);
+ *      flashe_quantize_batch_encrypt_pack_model_dev / flashe_quantize_batch_encrypt_pack_tensors_dev /
+ *      flashe_unpack_decrypt_unbatch_unquantize_model_dev (the BATCHED client step straight to and from the packed wire form at int_bits
+ *      65 .. 128: one launch each way, no 16-byte plaintext or ciphertext vector) */
 #define FLASHE_ABI_VERSION 4
 int flashe_abi_version(void);
 int flashe_device_count(int *count);
@@ -733,6 +736,33 @@ int flashe_unpack_decrypt_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, c
                                                int n_minus, uint64_t n, uint32_t n_jobs, const uint64_t *packed_dev,
                                                const flashe_codec_layer *layers, int n_layers, int element_bits, int num_clients,
                                                double *out_dev);
+/* The BATCHED client step straight to the packed wire form at int_bits 65 .. 128 (new; jzf_quantize.py:162-185, 436-451 then
+ * jzf_flashe.py:431-594 then jzf_weights.py:155-231): what flashe_quantize_batch_model_dev, flashe_encrypt_dev (cipher index idx, `scheme`)
+ * over the n_elems batched elements and flashe_pack_dev compute, bit for bit, in ONE launch -- neither the batched plaintext nor the
+ * ciphertext vector exists.  layers / element_bits / field_bits / u_dev / n_elems as flashe_quantize_batch_model_dev takes them.
+ * packed_dev: ceil(n_elems int_bits / 64) limbs, aligned like a ciphertext vector (16 bytes), element j at bits
+ * [int_bits (n_elems - 1 - j), int_bits (n_elems - j)); EVERY limb is written (the unused top bits of the last one zero), none needs
+ * to be zero on entry and nothing is cleared beforehand.
+ * FLASHE_ENOTSUP -- checked before anything else, nothing launched or staged -- unless 65 <= int_bits <= 128, 1 <= n_elems < 2^32 and the
+ * PRF backend is the table one; FLASHE_EINVAL as flashe_quantize_batch_model_dev / flashe_encrypt_dev.  Not capturable. */
+int flashe_quantize_batch_encrypt_pack_model_dev(flashe_ctx *ctx, uint32_t iter, uint32_t idx, int scheme, const flashe_batch_layer *layers,
+                                                 int n_layers, int element_bits, int field_bits, const double *u_dev, uint64_t n_elems,
+                                                 uint64_t *packed_dev);
+/* The same with tensor layers (new; jzf_quantize.py:55-67, 162-185 then jzf_flashe.py:431-594 then jzf_weights.py:155-231): the layers
+ * are checked and staged exactly as flashe_quantize_batch_tensors_dev checks and stages them (n_values = the model's values). */
+int flashe_quantize_batch_encrypt_pack_tensors_dev(flashe_ctx *ctx, uint32_t iter, uint32_t idx, int scheme, const flashe_tensor_layer *layers,
+                                                   int n_layers, uint64_t n_values, int element_bits, int field_bits, const double *u_dev,
+                                                   uint64_t n_elems, uint64_t *packed_dev);
+/* The way back (new; jzf_weights.py:155-231 then jzf_flashe.py:431-594 then jzf_quantize.py:234-251, 102-107): what flashe_unpack_dev,
+ * flashe_decrypt_dev over the n_elems elements and flashe_unbatch_unquantize_model_dev compute, bit for bit, in ONE launch.  packed_dev:
+ * the packed sum as above (read only, 8-byte aligned); out_dev: the model's float64 values in walking order, 8-byte aligned.
+ * FLASHE_ENOTSUP -- checked first, nothing launched or staged -- outside the admission above, and for n_add > 1 or n_minus > 1 (a round
+ * with dropouts, the single mask's decrypt: those lists stay with the three calls); FLASHE_EINVAL as flashe_unbatch_unquantize_model_dev,
+ * and for no prefix at all. */
+int flashe_unpack_decrypt_unbatch_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add,
+                                                       const uint32_t *minus_idx, int n_minus, const flashe_batch_layer *layers, int n_layers,
+                                                       int element_bits, int field_bits, int num_clients, const uint64_t *packed_dev,
+                                                       uint64_t n_elems, double *out_dev);
 /* A COHORT of n_clients consecutive clients (cipher indices first_idx .. first_idx + n_clients - 1, double mask) hosted on this GPU (new):
  * ONE chained launch quantises every client's float model (jzf_quantize.py:55-67, client c's element k with the draw
  * u_dev[c * n + k]), encrypts with the PRF streams the consecutive clients share (n_clients + 1 streams instead of 2 n_clients,
