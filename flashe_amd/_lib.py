@@ -271,12 +271,16 @@ _SIGNATURES = {
     "flashe_quantize_encrypt_pack_tensors_dev": (c_int, [c_vp, c_u32, c_u32, c_int, c_u64, c_u32, ctypes.POINTER(TensorLayer), c_int, c_int, c_vp, c_vp]),
     "flashe_unpack_decrypt_unquantize_model_dev": (c_int, [c_vp, c_u32, c_u32p, c_int, c_u32p, c_int, c_u64, c_u32, c_vp, ctypes.POINTER(CodecLayer),
                                                            c_int, c_int, c_int, c_vp]),
+    "flashe_unpack_decrypt_lists_unquantize_model_dev": (c_int, [c_vp, c_u32, c_u32p, c_int, c_u32p, c_int, c_u64, c_u32, c_vp, ctypes.POINTER(CodecLayer),
+                                                                 c_int, c_int, c_int, c_vp]),
     "flashe_quantize_batch_tensors_dev": (c_int, [c_vp, ctypes.POINTER(TensorLayer), c_int, c_u64, c_int, c_int, c_vp, c_u64, c_vp]),
     "flashe_quantize_batch_encrypt_pack_model_dev": (c_int, [c_vp, c_u32, c_u32, c_int, ctypes.POINTER(BatchLayer), c_int, c_int, c_int, c_vp, c_u64, c_vp]),
     "flashe_quantize_batch_encrypt_pack_tensors_dev": (c_int, [c_vp, c_u32, c_u32, c_int, ctypes.POINTER(TensorLayer), c_int, c_u64, c_int, c_int, c_vp, c_u64,
                                                                c_vp]),
     "flashe_unpack_decrypt_unbatch_unquantize_model_dev": (c_int, [c_vp, c_u32, c_u32p, c_int, c_u32p, c_int, ctypes.POINTER(BatchLayer), c_int, c_int, c_int,
                                                                    c_int, c_vp, c_u64, c_vp]),
+    "flashe_unpack_decrypt_lists_unbatch_unquantize_model_dev": (c_int, [c_vp, c_u32, c_u32p, c_int, c_u32p, c_int, ctypes.POINTER(BatchLayer), c_int, c_int,
+                                                                         c_int, c_int, c_vp, c_u64, c_vp]),
     "flashe_store_layers_dev": (c_int, [c_vp, c_vp, c_u64, ctypes.POINTER(TensorLayer), c_int, c_u64, c_vp]),
     "flashe_stage_layers_dev": (c_int, [c_vp, ctypes.POINTER(StageRow), c_int]),
     "flashe_finish_layers_dev": (c_int, [c_vp, c_vp, c_u64, ctypes.POINTER(FinishRow), c_int, c_u64, c_vp]),

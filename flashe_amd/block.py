@@ -27,6 +27,16 @@ _WIRE_OUT_MAX_BITS = 32
 # (x 1.09 - 1.49) but single outliers of 0.04 - 0.12 ms turn the verdict in one process or the other, so those stay staged.  A coarse
 # threshold: nothing was measured between 500,001 and 1,666,668.  profiles/r40_wire_batched_step.log
 _WIDE_WIRE_BACK_MIN_ELEMS = 1_666_668
+# decrypt_unquantize takes a packed sum whose decrypt has prefix LISTS (a round with a dropout: one add and one minus prefix per run of
+# uploaders; the single mask: one minus prefix per uploader) to the floats in one launch from this many elements on and up to this many
+# prefixes in all, per width class (int_bits 16 .. 64 un-batched; 65 .. 128 batched).  Measured against unpack_dev + the lists launch(es)
+# at lists 2 + 2, 4 + 4 and 0 + 10 in two processes, the fused median leads everywhere (x 1.25 - 1.75, falling as the lists grow); a win
+# by more than either form's spread in BOTH processes: un-batched at 25,557,032 elements, all three lists at int_bits 20 and 64 (x 1.33 -
+# 1.75) -- at 1e7 no list shape wins at both widths, single outliers of 0.1 - 0.2 ms turn one process -- and batched (int_bits 120) 2 + 2
+# at 1,666,668 and 4,259,506 elements (x 1.40 - 1.50), while 4 + 4 and 0 + 10 (x 1.25 - 1.34) lose one process each and stay staged.
+# Coarse thresholds: nothing was measured between the shapes.  profiles/r41_wire_lists_back.log
+_WIRE_LISTS_MIN_ELEMS, _WIRE_LISTS_MAX_PREFIXES = 25_557_032, 10
+_WIDE_WIRE_LISTS_MIN_ELEMS, _WIDE_WIRE_LISTS_MAX_PREFIXES = 1_666_668, 4
 
 __all__ = ["dynamic_masking_choice", "FlasheClient", "FlasheCohort", "CohortPlan", "CohortUpload", "plan_cohort", "FlasheSparseCohort",
            "SparseCohortPlan", "SparseCohortEncoding", "SparseCohortUpload", "plan_sparse_cohort"]
@@ -1034,19 +1044,26 @@ class FlasheClient(object):
         eng, n = c.engine, len(dv)
         wide_wire = (isinstance(dv, PackedVector) and self.batch and mode != "ctx" and dv.bits == self.int_bits and n >= _WIDE_WIRE_BACK_MIN_ELEMS
                      and hasattr(eng, "unpack_decrypt_unbatch_unquantize_model_dev"))
-        if isinstance(dv, PackedVector) and not wide_wire and (self.batch or mode == "ctx" or dv.bits != self.int_bits):
+        # the lists launch (a dropout, the single mask's decrypt): asked behind the one-prefix one, where it was measured to win
+        lists = (isinstance(dv, PackedVector) and mode != "ctx" and dv.bits == self.int_bits and max(len(add_idx), len(minus_idx)) > 1
+                 and hasattr(eng, "unpack_decrypt_lists_unbatch_unquantize_model_dev" if self.batch else "unpack_decrypt_lists_unquantize_model_dev")
+                 and n >= (_WIDE_WIRE_LISTS_MIN_ELEMS if self.batch else _WIRE_LISTS_MIN_ELEMS)
+                 and len(add_idx) + len(minus_idx) <= (_WIDE_WIRE_LISTS_MAX_PREFIXES if self.batch else _WIRE_LISTS_MAX_PREFIXES))
+        if isinstance(dv, PackedVector) and not wide_wire and not (self.batch and lists) and (self.batch or mode == "ctx" or dv.bits != self.int_bits):
             dv = self._unpacked(dv)
         if mode == "ctx":
             c._check_prepared_len(c.next_iter_decrypt_prepared['add'], n)          # (the call-by-call decrypt's error; the cache stays)
         if self.batch:
             layers, field_bits = self._batched_back_table(sizes, n)
             dout = eng.alloc(max(8 * sum(sizes), 16))
-            if wide_wire:
-                # the packed sum of a batched job straight to the floats in ONE launch (int_bits 65 .. 128); declined (prefix lists
-                # longer than one each, another width) it is unpacked for today's launches
+            if wide_wire or lists:
+                # the packed sum of a batched job straight to the floats in ONE launch (int_bits 65 .. 128): the one-prefix launch, which
+                # declines prefix lists longer than one each, then the lists launch where it is routed; declined by both (another width,
+                # a list above the cap) it is unpacked for today's launches
                 dv.wait_on(eng)
-                if n and eng.unpack_decrypt_unbatch_unquantize_model_dev(c.iter_index, add_idx, minus_idx, layers, q.element_bits, field_bits,
-                                                                         q.num_clients, dv.buf, n, dout):
+                args = (c.iter_index, add_idx, minus_idx, layers, q.element_bits, field_bits, q.num_clients, dv.buf, n, dout)
+                if n and ((wide_wire and eng.unpack_decrypt_unbatch_unquantize_model_dev(*args))
+                          or (lists and eng.unpack_decrypt_lists_unbatch_unquantize_model_dev(*args))):
                     eng.hold([dv])
                     self._decrypt_done(mode)
                     return dout
@@ -1064,11 +1081,11 @@ class FlasheClient(object):
         table = self._back_table(sizes, n)
         dout = eng.alloc(max(8 * n, 16))
         if isinstance(dv, PackedVector):
-            # the packed sum straight to the floats in ONE launch; declined (prefix lists longer than one each: dropouts, the single
-            # mask's decrypt) it is unpacked for today's launch
+            # the packed sum straight to the floats in ONE launch: the one-prefix launch, which declines prefix lists longer than one each
+            # (dropouts, the single mask's decrypt), then the lists launch where it is routed; declined by both it is unpacked for today's launch
             dv.wait_on(eng)
-            if n and eng.unpack_decrypt_unquantize_model_dev(c.iter_index, add_idx, minus_idx, n, _cipher_mod.N_JOBS, dv.buf, table, q.element_bits,
-                                                             q.num_clients, dout):
+            args = (c.iter_index, add_idx, minus_idx, n, _cipher_mod.N_JOBS, dv.buf, table, q.element_bits, q.num_clients, dout)
+            if n and (eng.unpack_decrypt_unquantize_model_dev(*args) or (lists and eng.unpack_decrypt_lists_unquantize_model_dev(*args))):
                 eng.hold([dv])
                 self._decrypt_done(mode)
                 return dout

@@ -546,15 +546,18 @@ int flashe_quantize_encrypt_pack_tensors_dev(flashe_ctx *ctx, uint32_t iter, uin
     return FLASHE_OK;
 }
 
-int flashe_unpack_decrypt_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx, int n_minus,
-                                               uint64_t n, uint32_t n_jobs, const uint64_t *packed_dev, const flashe_codec_layer *layers, int n_layers,
-                                               int element_bits, int num_clients, double *out_dev)
+// The way back in its two forms: `lists` false, at most one prefix per list (prf_small_unpack_kernel); true, up to kMaxIdx each (prf_small_unpack_lists_kernel).
+static int unpack_decrypt_unquantize_model(flashe_ctx *ctx, const char *who, bool lists, uint32_t iter, const uint32_t *add_idx, int n_add,
+                                           const uint32_t *minus_idx, int n_minus, uint64_t n, uint32_t n_jobs, const uint64_t *packed_dev,
+                                           const flashe_codec_layer *layers, int n_layers, int element_bits, int num_clients, double *out_dev)
 {
     CHECK_CTX(ctx);
-    int rc = wire_admit(ctx, "flashe_unpack_decrypt_unquantize_model_dev", n, n_jobs);
+    int rc = wire_admit(ctx, who, n, n_jobs);
     if (rc) return rc;
-    if (n_add > 1 || n_minus > 1)
-        return fail(ctx, FLASHE_ENOTSUP, "flashe_unpack_decrypt_unquantize_model_dev: at most one add and one minus prefix (flashe_unpack_dev + flashe_decrypt_unquantize_model_dev take lists)");
+    if (!lists && (n_add > 1 || n_minus > 1))
+        return fail(ctx, FLASHE_ENOTSUP, "%s: at most one add and one minus prefix (flashe_unpack_decrypt_lists_unquantize_model_dev, or flashe_unpack_dev + flashe_decrypt_unquantize_model_dev, take lists)", who);
+    if (n_add > kMaxIdx || n_minus > kMaxIdx)
+        return fail(ctx, FLASHE_ENOTSUP, "%s: at most %d prefixes per list (flashe_unpack_dev + flashe_decrypt_unquantize_model_dev take longer ones)", who, kMaxIdx);
     if (!packed_dev || !out_dev) return fail(ctx, FLASHE_EINVAL, "null vector");
     if (num_clients < 1) return fail(ctx, FLASHE_EINVAL, "num_clients must be >= 1");
     if (n_add < 0 || n_minus < 0 || n_add + n_minus == 0) return fail(ctx, FLASHE_EINVAL, "unpack_decrypt_unquantize_model: at least one prefix (a round always has one)");
@@ -562,8 +565,25 @@ int flashe_unpack_decrypt_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, c
     if ((rc = check_codec_bits(ctx, element_bits)) || (rc = check_aligned(ctx, {packed_dev, out_dev}, 8))) return rc;
     Codec cq{};
     if ((rc = stage_codec_layers(ctx, n, layers, n_layers, false, element_bits, num_clients, 0, n, nullptr, out_dev, &cq))) return rc;
-    HIP_TRY(ctx, launch_small_unpack(ctx->env, iter, n_add == 1, n_add ? add_idx[0] : 0u, n_minus == 1, n_minus ? minus_idx[0] : 0u, n, n_jobs, packed_dev, cq));
+    if (lists) HIP_TRY(ctx, launch_small_unpack_lists(ctx->env, iter, add_idx, n_add, minus_idx, n_minus, n, n_jobs, packed_dev, cq));
+    else HIP_TRY(ctx, launch_small_unpack(ctx->env, iter, n_add == 1, n_add ? add_idx[0] : 0u, n_minus == 1, n_minus ? minus_idx[0] : 0u, n, n_jobs, packed_dev, cq));
     return FLASHE_OK;
+}
+
+int flashe_unpack_decrypt_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx, int n_minus,
+                                               uint64_t n, uint32_t n_jobs, const uint64_t *packed_dev, const flashe_codec_layer *layers, int n_layers,
+                                               int element_bits, int num_clients, double *out_dev)
+{
+    return unpack_decrypt_unquantize_model(ctx, "flashe_unpack_decrypt_unquantize_model_dev", false, iter, add_idx, n_add, minus_idx, n_minus, n, n_jobs, packed_dev,
+                                           layers, n_layers, element_bits, num_clients, out_dev);
+}
+
+int flashe_unpack_decrypt_lists_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx, int n_minus,
+                                                     uint64_t n, uint32_t n_jobs, const uint64_t *packed_dev, const flashe_codec_layer *layers, int n_layers,
+                                                     int element_bits, int num_clients, double *out_dev)
+{
+    return unpack_decrypt_unquantize_model(ctx, "flashe_unpack_decrypt_lists_unquantize_model_dev", true, iter, add_idx, n_add, minus_idx, n_minus, n, n_jobs,
+                                           packed_dev, layers, n_layers, element_bits, num_clients, out_dev);
 }
 
 // what every chained cohort asks of its arguments before its cipher indices
@@ -1372,15 +1392,18 @@ int flashe_quantize_batch_encrypt_pack_tensors_dev(flashe_ctx *ctx, uint32_t ite
     return flashe_quantize_batch_encrypt_pack_model_dev(ctx, iter, idx, scheme, bl.data(), n_layers, element_bits, field_bits, u_dev, n_elems, packed_dev);
 }
 
-int flashe_unpack_decrypt_unbatch_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx, int n_minus,
-                                                       const flashe_batch_layer *layers, int n_layers, int element_bits, int field_bits, int num_clients,
-                                                       const uint64_t *packed_dev, uint64_t n_elems, double *out_dev)
+// The way back in its two forms: `lists` false, at most one prefix per list (prf_wide_unpack_kernel); true, up to kMaxIdx each (prf_wide_unpack_lists_kernel).
+static int unpack_decrypt_unbatch_unquantize_model(flashe_ctx *ctx, const char *who, bool lists, uint32_t iter, const uint32_t *add_idx, int n_add,
+                                                   const uint32_t *minus_idx, int n_minus, const flashe_batch_layer *layers, int n_layers, int element_bits,
+                                                   int field_bits, int num_clients, const uint64_t *packed_dev, uint64_t n_elems, double *out_dev)
 {
     CHECK_CTX(ctx);
-    int rc = wide_wire_admit(ctx, "flashe_unpack_decrypt_unbatch_unquantize_model_dev", n_elems);
+    int rc = wide_wire_admit(ctx, who, n_elems);
     if (rc) return rc;
-    if (n_add > 1 || n_minus > 1)
-        return fail(ctx, FLASHE_ENOTSUP, "flashe_unpack_decrypt_unbatch_unquantize_model_dev: at most one add and one minus prefix (flashe_unpack_dev, flashe_decrypt_dev and flashe_unbatch_unquantize_model_dev take lists)");
+    if (!lists && (n_add > 1 || n_minus > 1))
+        return fail(ctx, FLASHE_ENOTSUP, "%s: at most one add and one minus prefix (flashe_unpack_decrypt_lists_unbatch_unquantize_model_dev, or flashe_unpack_dev, flashe_decrypt_dev and flashe_unbatch_unquantize_model_dev, take lists)", who);
+    if (n_add > kMaxIdx || n_minus > kMaxIdx)
+        return fail(ctx, FLASHE_ENOTSUP, "%s: at most %d prefixes per list (flashe_unpack_dev, flashe_decrypt_dev and flashe_unbatch_unquantize_model_dev take longer ones)", who, kMaxIdx);
     if (num_clients < 1) return fail(ctx, FLASHE_EINVAL, "num_clients must be >= 1");
     if (n_add < 0 || n_minus < 0 || n_add + n_minus == 0) return fail(ctx, FLASHE_EINVAL, "unpack_decrypt_unbatch_unquantize_model: at least one prefix (a round always has one)");
     if ((n_add && !add_idx) || (n_minus && !minus_idx)) return fail(ctx, FLASHE_EINVAL, "null prefix list");
@@ -1388,9 +1411,26 @@ int flashe_unpack_decrypt_unbatch_unquantize_model_dev(flashe_ctx *ctx, uint32_t
     if ((rc = stage_batch_layers(ctx, layers, n_layers, false, element_bits, field_bits, num_clients, n_elems, &bt))) return rc;
     if (!packed_dev || !out_dev) return fail(ctx, FLASHE_EINVAL, "null vector");
     if ((rc = check_aligned(ctx, {packed_dev, out_dev}, 8))) return rc;
-    HIP_TRY(ctx, launch_wide_unpack(ctx->env, iter, n_add == 1, n_add ? add_idx[0] : 0u, n_minus == 1, n_minus ? minus_idx[0] : 0u, bt.tab, bt.n_tab, field_bits,
-                                    packed_dev, n_elems, out_dev));
+    if (lists) HIP_TRY(ctx, launch_wide_unpack_lists(ctx->env, iter, add_idx, n_add, minus_idx, n_minus, bt.tab, bt.n_tab, field_bits, packed_dev, n_elems, out_dev));
+    else HIP_TRY(ctx, launch_wide_unpack(ctx->env, iter, n_add == 1, n_add ? add_idx[0] : 0u, n_minus == 1, n_minus ? minus_idx[0] : 0u, bt.tab, bt.n_tab, field_bits,
+                                         packed_dev, n_elems, out_dev));
     return FLASHE_OK;
+}
+
+int flashe_unpack_decrypt_unbatch_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx, int n_minus,
+                                                       const flashe_batch_layer *layers, int n_layers, int element_bits, int field_bits, int num_clients,
+                                                       const uint64_t *packed_dev, uint64_t n_elems, double *out_dev)
+{
+    return unpack_decrypt_unbatch_unquantize_model(ctx, "flashe_unpack_decrypt_unbatch_unquantize_model_dev", false, iter, add_idx, n_add, minus_idx, n_minus, layers,
+                                                   n_layers, element_bits, field_bits, num_clients, packed_dev, n_elems, out_dev);
+}
+
+int flashe_unpack_decrypt_lists_unbatch_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx,
+                                                             int n_minus, const flashe_batch_layer *layers, int n_layers, int element_bits, int field_bits,
+                                                             int num_clients, const uint64_t *packed_dev, uint64_t n_elems, double *out_dev)
+{
+    return unpack_decrypt_unbatch_unquantize_model(ctx, "flashe_unpack_decrypt_lists_unbatch_unquantize_model_dev", true, iter, add_idx, n_add, minus_idx, n_minus,
+                                                   layers, n_layers, element_bits, field_bits, num_clients, packed_dev, n_elems, out_dev);
 }
 
 int flashe_store_layers_dev(flashe_ctx *ctx, const double *in_dev, uint64_t n, const flashe_tensor_layer *layers, int n_layers, uint64_t block,

@@ -291,6 +291,10 @@ hipError_t launch_small_pack(const LaunchEnv &env, uint32_t iter, uint32_t add_i
                              uint64_t *packed_dev);
 hipError_t launch_small_unpack(const LaunchEnv &env, uint32_t iter, bool has_add, uint32_t add_idx, bool has_minus, uint32_t minus_idx, uint64_t n,
                                uint32_t n_jobs, const uint64_t *packed_dev, const Codec &cq);
+// launch_small_unpack_lists: the same with HOST prefix lists of 0 .. kMaxIdx each, at least one prefix in all, repeats summed:
+// cq.fout[j] = unquantise(element j + sum_k term(add[k]) - sum_k term(minus[k])) in ONE launch (prf_small_unpack_lists_kernel, wire_lists.h).
+hipError_t launch_small_unpack_lists(const LaunchEnv &env, uint32_t iter, const uint32_t *add, int n_add, const uint32_t *minus, int n_minus, uint64_t n,
+                                     uint32_t n_jobs, const uint64_t *packed_dev, const Codec &cq);
 
 // The BATCHED client step straight to and from the packed wire form at int_bits 65 .. 128 (wire_wide.hip; BatchLayer tables as
 // launch_quantize_batch_model / launch_unbatch_unquantize_model take them, bs = int_bits / field_bits values per element).
@@ -305,6 +309,10 @@ hipError_t launch_wide_pack(const LaunchEnv &env, uint32_t iter, uint32_t add_id
                             int field_bits, const double *u_dev, uint64_t n_elems, uint64_t *packed_dev);
 hipError_t launch_wide_unpack(const LaunchEnv &env, uint32_t iter, bool has_add, uint32_t add_idx, bool has_minus, uint32_t minus_idx, const BatchLayer *layers_dev,
                               int n_layers, int field_bits, const uint64_t *packed_dev, uint64_t n_elems, double *out_dev);
+// launch_wide_unpack_lists: the same with HOST prefix lists of 0 .. kMaxIdx each, at least one prefix in all, repeats summed, in ONE launch
+// (prf_wide_unpack_lists_kernel, wire_lists.h).
+hipError_t launch_wide_unpack_lists(const LaunchEnv &env, uint32_t iter, const uint32_t *add, int n_add, const uint32_t *minus, int n_minus,
+                                    const BatchLayer *layers_dev, int n_layers, int field_bits, const uint64_t *packed_dev, uint64_t n_elems, double *out_dev);
 
 hipError_t launch_fill(const LaunchEnv &env, uint64_t n, uint64_t lo, uint64_t hi, uint64_t *out_dev);
 // locations >= total are skipped and reported through env.err_flag (the reference raises IndexError, jzf_aggregator.py:150-165)

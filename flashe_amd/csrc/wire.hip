@@ -2,6 +2,7 @@
 // jzf_weights.py:155-231: element j of n at bits [b (n - 1 - j), b (n - j)) of one integer, element 0 most significant):
 //   prf_small_pack_kernel<DBL>   float model + draws -> quantise -> encrypt -> packed limbs       (no uint64 ciphertext vector in HBM)
 //   prf_small_unpack_kernel      packed limbs of the sum -> decrypt -> unquantise -> float64 model (no uint64 element vector in HBM)
+//   prf_small_unpack_lists_kernel  the same with prefix LISTS of up to kMaxIdx each (a dropout, the single mask's decrypt; wire_lists.h)
 // Both are siblings of prf_small_jobs_kernel (kernels.hip): a wave owns 64 consecutive AES blocks per tile, counters and chunking by
 // small_block_params, prefixes through ctr_prefix / ctr_round1, the T-tables in LDS.  The structural fact they rest on: a lane's AES block
 // masks m = 128 / b CONSECUTIVE elements, and consecutive elements are one CONTIGUOUS cnt * b-bit field of the packed integer with the
@@ -18,6 +19,7 @@
 // RAGGED tiles -- a tile with a partial block (a chunk end with cnt < m; at most one tile per chunk) -- take a per-lane path: every valid
 // lane ORs its own field into the at most three limbs it touches, atomically (pack), or stores its own cnt floats (unpack).
 #include "small_blocks.h"
+#include "wire_lists.h"
 
 namespace flashe {
 
@@ -224,24 +226,17 @@ __global__ __launch_bounds__(kSmallThreads) void prf_small_pack_kernel(const Rou
     }
 }
 
-// out[j] = unquantise((element j of the packed sum + S_add - S_minus) mod 2^b); flags: bit 0 = an add prefix, bit 1 = a minus prefix
-__global__ __launch_bounds__(kSmallThreads) void prf_small_unpack_kernel(const RoundKeys rk, const SmallParams p, uint32_t add_idx, uint32_t minus_idx, int flags,
-                                                                         uint64_t n_blocks, const uint64_t *__restrict__ packed, uint64_t n_limbs)
+// The way back, shared by the one-prefix and the lists kernel: mid(x, top) = the lane's slot-wise mask S_add - S_minus at counter part x.
+template <class Mid>
+__device__ __forceinline__ void small_unpack_tiles(const RoundKeys &rk, const SmallParams &p, const LaneRegs lr, uint32_t *scratch, const Mid &mid, uint64_t n_blocks,
+                                                   const uint64_t *__restrict__ packed, uint64_t n_limbs)
 {
-    const uint32_t iter = p.iter + p.te0[kIterShiftWord];
-    __shared__ uint32_t tab[kTabWords];
-    __shared__ uint32_t scratch[(kSmallThreads / 64) * 256 + 8];
-    fill_tables(tab, p.te0);
-    const LaneRegs lr = lane_regs(tab);
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
     uint32_t *row0 = scratch + wave * 256;
     const u128 top = (static_cast<u128>(p.top_hi) << 64) | p.top_lo;
     const WireChunks ch = wire_chunks(p);
     const uint32_t b = static_cast<uint32_t>(p.b), m = static_cast<uint32_t>(p.m);
-    const bool has_add = (flags & 1) != 0, has_minus = (flags & 2) != 0;
-    const CtrPrefix pre_a = scalar_prefix(ctr_prefix(rk, lr, iter, has_add ? add_idx : minus_idx, 0u));        // n < 2^32 (host-checked)
-    const CtrPrefix pre_b = scalar_prefix(ctr_prefix(rk, lr, iter, minus_idx, 0u));
     double *const out = p.cq.fout;
     const uint64_t n_tiles = (n_blocks + 63) / 64, n_waves = static_cast<uint64_t>(gridDim.x) * (kSmallThreads / 64);
     for (uint64_t t = static_cast<uint64_t>(blockIdx.x) * (kSmallThreads / 64) + wave; t < n_tiles; t += n_waves) {
@@ -257,21 +252,7 @@ __global__ __launch_bounds__(kSmallThreads) void prf_small_unpack_kernel(const R
             if (l + 2 < n_limbs && sh + fbits > 128u) g2 = __builtin_nontemporal_load(packed + l + 2);
         }
         // 2. the prefixes the host's telescoping left
-        u128 D;
-        const CtrVar x = ctr_var(rk, lr, w.ctr);
-        if (has_add && has_minus) {
-            uint32_t s[2][4];
-            ctr_round1(pre_a, x, s[0]);
-            ctr_round1(pre_b, x, s[1]);
-            aes256_rounds<2, 2>(rk, lr, s, true);
-            D = wire_slot_sub(words_to_u128(s[0]), words_to_u128(s[1]), top);
-        } else {
-            uint32_t s[1][4];
-            ctr_round1(pre_a, x, s[0]);
-            aes256_rounds<1, 2>(rk, lr, s, true);
-            D = words_to_u128(s[0]);
-            if (!has_add) D = wire_slot_sub(0, D, top);
-        }
+        const u128 D = mid(ctr_var(rk, lr, w.ctr), top);
         u128 F = (static_cast<u128>(g1) << 64) | g0;
         if (sh) F = (F >> sh) | (static_cast<u128>(g2) << (128u - sh));
         if (fbits < 128u) F &= (static_cast<u128>(1) << fbits) - 1;
@@ -314,6 +295,53 @@ __global__ __launch_bounds__(kSmallThreads) void prf_small_unpack_kernel(const R
     }
 }
 
+// out[j] = unquantise((element j of the packed sum + S_add - S_minus) mod 2^b); flags: bit 0 = an add prefix, bit 1 = a minus prefix
+__global__ __launch_bounds__(kSmallThreads) void prf_small_unpack_kernel(const RoundKeys rk, const SmallParams p, uint32_t add_idx, uint32_t minus_idx, int flags,
+                                                                         uint64_t n_blocks, const uint64_t *__restrict__ packed, uint64_t n_limbs)
+{
+    const uint32_t iter = p.iter + p.te0[kIterShiftWord];
+    __shared__ uint32_t tab[kTabWords];
+    __shared__ uint32_t scratch[(kSmallThreads / 64) * 256 + 8];
+    fill_tables(tab, p.te0);
+    const LaneRegs lr = lane_regs(tab);
+    const bool has_add = (flags & 1) != 0, has_minus = (flags & 2) != 0;
+    const CtrPrefix pre_a = scalar_prefix(ctr_prefix(rk, lr, iter, has_add ? add_idx : minus_idx, 0u));        // n < 2^32 (host-checked)
+    const CtrPrefix pre_b = scalar_prefix(ctr_prefix(rk, lr, iter, minus_idx, 0u));
+    small_unpack_tiles(rk, p, lr, scratch, [&](const CtrVar &x, u128 top) {
+        if (has_add && has_minus) {
+            uint32_t s[2][4];
+            ctr_round1(pre_a, x, s[0]);
+            ctr_round1(pre_b, x, s[1]);
+            aes256_rounds<2, 2>(rk, lr, s, true);
+            return wire_slot_sub(words_to_u128(s[0]), words_to_u128(s[1]), top);
+        }
+        uint32_t s[1][4];
+        ctr_round1(pre_a, x, s[0]);
+        aes256_rounds<1, 2>(rk, lr, s, true);
+        const u128 D = words_to_u128(s[0]);
+        return has_add ? D : wire_slot_sub(0, D, top);
+    }, n_blocks, packed, n_limbs);
+}
+
+// The same with prefix LISTS (a round with a dropout, the single mask's decrypt): out[j] = unquantise((element j of the packed sum +
+// sum_k S(add[k]) - sum_k S(minus[k])) mod 2^b), the prefixes' round-1 states in an LDS table the kernel builds (wire_lists.h).  The
+// running mask is kept slot-wise (SWAR under `top`): no carry or borrow of one prefix's block crosses into the next slot.
+__global__ __launch_bounds__(kSmallThreads) void prf_small_unpack_lists_kernel(const RoundKeys rk, const SmallParams p, const WireLists ls, uint64_t n_blocks,
+                                                                               const uint64_t *__restrict__ packed, uint64_t n_limbs)
+{
+    const uint32_t iter = p.iter + p.te0[kIterShiftWord];
+    __shared__ uint32_t tab[kTabWords];
+    __shared__ uint32_t scratch[(kSmallThreads / 64) * 256 + 8];
+    __shared__ uint4 pre[2 * kMaxIdx];
+    fill_tables(tab, p.te0);
+    const LaneRegs lr = lane_regs(tab);
+    wire_prefix_table(rk, lr, iter, ls, pre);
+    small_unpack_tiles(rk, p, lr, scratch, [&](const CtrVar &x, u128 top) {
+        return wire_lists_mask<false>(rk, lr, pre, ls.n_add, ls.n, x,
+                                      [top](u128 D, u128 S, bool add) { return add ? wire_slot_add(D, S, top) : wire_slot_sub(D, S, top); });
+    }, n_blocks, packed, n_limbs);
+}
+
 bool small_wire_admits(const LaunchEnv &env, uint64_t n, uint32_t n_jobs)
 {
     return env.b >= 16 && env.b <= 64 && n >= 1 && n < (1ull << 32) && n_jobs >= 1 && (env.prf_backend == PRF_AUTO || env.prf_backend == PRF_TABLE);
@@ -351,6 +379,18 @@ hipError_t launch_small_unpack(const LaunchEnv &env, uint32_t iter, bool has_add
     const uint64_t n_blocks = block_of(n - 1, n, n_jobs, p.m) + 1, n_limbs = (n * static_cast<uint64_t>(env.b) + 63) / 64;
     hipLaunchKernelGGL(prf_small_unpack_kernel, dim3(wire_grid(env, n_blocks)), dim3(kSmallThreads), 0, env.stream, env.rk, p, add_idx, minus_idx,
                        (has_add ? 1 : 0) | (has_minus ? 2 : 0), n_blocks, packed_dev, n_limbs);
+    return hipGetLastError();
+}
+
+hipError_t launch_small_unpack_lists(const LaunchEnv &env, uint32_t iter, const uint32_t *add, int n_add, const uint32_t *minus, int n_minus, uint64_t n,
+                                     uint32_t n_jobs, const uint64_t *packed_dev, const Codec &cq)
+{
+    if (!small_wire_admits(env, n, n_jobs) || !wire_lists_admit(n_add, n_minus) || !cq.layers || !cq.fout) return hipErrorNotSupported;
+    SmallParams p = small_params_of(env, iter, n, n_jobs);
+    p.cq = cq;
+    const uint64_t n_blocks = block_of(n - 1, n, n_jobs, p.m) + 1, n_limbs = (n * static_cast<uint64_t>(env.b) + 63) / 64;
+    hipLaunchKernelGGL(prf_small_unpack_lists_kernel, dim3(wire_grid(env, n_blocks)), dim3(kSmallThreads), 0, env.stream, env.rk, p,
+                       wire_lists_of(add, n_add, minus, n_minus), n_blocks, packed_dev, n_limbs);
     return hipGetLastError();
 }
 

@@ -2,6 +2,7 @@
 // quantised values per element; JZFTransferableWeights.compress / decompress, jzf_weights.py:155-231):
 //   prf_wide_pack_kernel<DBL, BS>   float model + draws -> quantise -> batch -> encrypt -> packed limbs   (no 16-byte vector in HBM)
 //   prf_wide_unpack_kernel<BS>      packed limbs of the sum -> decrypt -> unbatch -> unquantise -> float64 model
+//   prf_wide_unpack_lists_kernel<BS>  the same with prefix LISTS of up to kMaxIdx each (a dropout, the single mask's decrypt; wire_lists.h)
 // At these widths an element is ONE AES block and its counter is the element index: the chunking does not enter, and nothing ties the
 // tiling to AES blocks.  It is tied to the LIMBS of the integer instead, and anchored at the END of the vector: element j of n sits at bits
 // [b (n - 1 - j), b (n - j)); with k = n - 1 - j, tile t = the elements k in [64 t, 64 t + 64) covers bits [64 b t, 64 b (t + 1)) --
@@ -18,6 +19,7 @@
 //   inside one row goes through the wave's rows and is walked lane-contiguously (64 bs consecutive float64 values, coalesced stores); a
 //   tile that crosses rows or holds a row's padded last element stores from registers, the row looked up per lane.
 #include "device_common.h"
+#include "wire_lists.h"
 
 namespace flashe {
 
@@ -170,27 +172,18 @@ __global__ __launch_bounds__(kWideWireThreads) void prf_wide_pack_kernel(const R
     }
 }
 
-// out[value] = unquantise(field of (element of the packed sum + S_add - S_minus) mod 2^b); flags: bit 0 = an add prefix, bit 1 = a minus prefix
-template <int BS>
-__global__ __launch_bounds__(kWideWireThreads) void prf_wide_unpack_kernel(const RoundKeys rk, const WideWire p, uint32_t add_idx, uint32_t minus_idx, int flags,
-                                                                          const uint64_t *__restrict__ packed)
+// The way back, shared by the one-prefix and the lists kernel: mid(x) = the element's mask S_add - S_minus (mod 2^128) at counter part x.
+template <int BS, class Mid>
+__device__ __forceinline__ void wide_unpack_tiles(const RoundKeys &rk, const WideWire &p, const LaneRegs lr, uint32_t *rows, const Mid &mid,
+                                                  const uint64_t *__restrict__ packed)
 {
 #pragma clang fp contract(off)
-    const uint32_t iter = p.iter + p.te0[kIterShiftWord];
-    __shared__ uint32_t tab[kTabWords];
-    __shared__ uint32_t rows[(kWideWireThreads / 64) * 256];
-    fill_tables(tab, p.te0);
-    const LaneRegs lr = lane_regs(tab);
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
     uint32_t *row0 = rows + wave * 256;
     const u128 mask = (static_cast<u128>(p.mask_hi) << 64) | p.mask_lo;
     const uint32_t b = static_cast<uint32_t>(p.b), fb = static_cast<uint32_t>(p.field_bits);
     const u128 fmask = fb >= 128u ? ~static_cast<u128>(0) : (static_cast<u128>(1) << fb) - 1;
-    const bool has_add = (flags & 1) != 0, has_minus = (flags & 2) != 0;
-    const CtrPrefix pre_a = scalar_prefix(ctr_prefix(rk, lr, iter, has_add ? add_idx : minus_idx, 0u));        // n < 2^32 (host-checked)
-    CtrPrefix pre_b{};
-    if (has_add && has_minus) pre_b = scalar_prefix(ctr_prefix(rk, lr, iter, minus_idx, 0u));
     double *const out = p.out;
     const uint64_t n_tiles = (p.n + 63) / 64;
     for (uint64_t t = static_cast<uint64_t>(blockIdx.x) * (kWideWireThreads / 64) + wave; t < n_tiles; t += wide_wire_grid_waves()) {
@@ -209,21 +202,7 @@ __global__ __launch_bounds__(kWideWireThreads) void prf_wide_unpack_kernel(const
             if (sh + b > 128u) g2 = __builtin_nontemporal_load(packed + l + 2);
         }
         // 2. the prefixes the host's telescoping left
-        u128 D;
-        const CtrVar x = ctr_var(rk, lr, static_cast<uint32_t>(e));
-        if (has_add && has_minus) {
-            uint32_t s[2][4];
-            ctr_round1(pre_a, x, s[0]);
-            ctr_round1(pre_b, x, s[1]);
-            aes256_rounds<2, 2>(rk, lr, s, true);
-            D = words_to_u128(s[0]) - words_to_u128(s[1]);
-        } else {
-            uint32_t s[4];
-            ctr_round1(pre_a, x, s);
-            aes256_rounds1_deep<2>(rk, lr, s, true);
-            D = words_to_u128(s);
-            if (!has_add) D = -D;
-        }
+        const u128 D = mid(ctr_var(rk, lr, static_cast<uint32_t>(e)));
         u128 F = (static_cast<u128>(g1) << 64) | g0;
         if (sh) F = (F >> sh) | (static_cast<u128>(g2) << (128u - sh));
         const u128 X = (F + D) & mask;                                                       // the decrypted element
@@ -256,6 +235,54 @@ __global__ __launch_bounds__(kWideWireThreads) void prf_wide_unpack_kernel(const
             }
         }
     }
+}
+
+// out[value] = unquantise(field of (element of the packed sum + S_add - S_minus) mod 2^b); flags: bit 0 = an add prefix, bit 1 = a minus prefix
+template <int BS>
+__global__ __launch_bounds__(kWideWireThreads) void prf_wide_unpack_kernel(const RoundKeys rk, const WideWire p, uint32_t add_idx, uint32_t minus_idx, int flags,
+                                                                          const uint64_t *__restrict__ packed)
+{
+    const uint32_t iter = p.iter + p.te0[kIterShiftWord];
+    __shared__ uint32_t tab[kTabWords];
+    __shared__ uint32_t rows[(kWideWireThreads / 64) * 256];
+    fill_tables(tab, p.te0);
+    const LaneRegs lr = lane_regs(tab);
+    const bool has_add = (flags & 1) != 0, has_minus = (flags & 2) != 0;
+    const CtrPrefix pre_a = scalar_prefix(ctr_prefix(rk, lr, iter, has_add ? add_idx : minus_idx, 0u));        // n < 2^32 (host-checked)
+    CtrPrefix pre_b{};
+    if (has_add && has_minus) pre_b = scalar_prefix(ctr_prefix(rk, lr, iter, minus_idx, 0u));
+    wide_unpack_tiles<BS>(rk, p, lr, rows, [&](const CtrVar &x) {
+        if (has_add && has_minus) {
+            uint32_t s[2][4];
+            ctr_round1(pre_a, x, s[0]);
+            ctr_round1(pre_b, x, s[1]);
+            aes256_rounds<2, 2>(rk, lr, s, true);
+            return words_to_u128(s[0]) - words_to_u128(s[1]);
+        }
+        uint32_t s[4];
+        ctr_round1(pre_a, x, s);
+        aes256_rounds1_deep<2>(rk, lr, s, true);
+        const u128 D = words_to_u128(s);
+        return has_add ? D : -D;
+    }, packed);
+}
+
+// The same with prefix LISTS (a round with a dropout, the single mask's decrypt): the element's mask is sum_k S(add[k]) - sum_k S(minus[k])
+// mod 2^128 (the back end masks to b bits), the prefixes' round-1 states in an LDS table the kernel builds (wire_lists.h).
+template <int BS>
+__global__ __launch_bounds__(kWideWireThreads) void prf_wide_unpack_lists_kernel(const RoundKeys rk, const WideWire p, const WireLists ls,
+                                                                                const uint64_t *__restrict__ packed)
+{
+    const uint32_t iter = p.iter + p.te0[kIterShiftWord];
+    __shared__ uint32_t tab[kTabWords];
+    __shared__ uint32_t rows[(kWideWireThreads / 64) * 256];
+    __shared__ uint4 pre[2 * kMaxIdx];
+    fill_tables(tab, p.te0);
+    const LaneRegs lr = lane_regs(tab);
+    wire_prefix_table(rk, lr, iter, ls, pre);
+    wide_unpack_tiles<BS>(rk, p, lr, rows, [&](const CtrVar &x) {
+        return wire_lists_mask<true>(rk, lr, pre, ls.n_add, ls.n, x, [](u128 D, u128 S, bool add) { return add ? D + S : D - S; });
+    }, packed);
 }
 
 bool wide_wire_admits(const LaunchEnv &env, uint64_t n_elems)
@@ -316,6 +343,25 @@ hipError_t launch_wide_unpack(const LaunchEnv &env, uint32_t iter, bool has_add,
     case 6: hipLaunchKernelGGL(prf_wide_unpack_kernel<6>, grid, block, 0, env.stream, env.rk, p, add_idx, minus_idx, flags, packed_dev); break;
     case 7: hipLaunchKernelGGL(prf_wide_unpack_kernel<7>, grid, block, 0, env.stream, env.rk, p, add_idx, minus_idx, flags, packed_dev); break;
     default: hipLaunchKernelGGL(prf_wide_unpack_kernel<0>, grid, block, 0, env.stream, env.rk, p, add_idx, minus_idx, flags, packed_dev); break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_wide_unpack_lists(const LaunchEnv &env, uint32_t iter, const uint32_t *add, int n_add, const uint32_t *minus, int n_minus,
+                                    const BatchLayer *layers_dev, int n_layers, int field_bits, const uint64_t *packed_dev, uint64_t n_elems, double *out_dev)
+{
+    if (!wide_wire_admits(env, n_elems) || !wire_lists_admit(n_add, n_minus) || !layers_dev || n_layers < 1 || !packed_dev || !out_dev || field_bits < 1 ||
+        field_bits > env.b)
+        return hipErrorNotSupported;
+    WideWire p = wide_wire_params(env, iter, layers_dev, n_layers, field_bits, n_elems);
+    p.out = out_dev;
+    const dim3 grid = wide_wire_grid(env, n_elems), block(kWideWireThreads);
+    const WireLists ls = wire_lists_of(add, n_add, minus, n_minus);
+    switch (p.bs) {
+    case 5: hipLaunchKernelGGL(prf_wide_unpack_lists_kernel<5>, grid, block, 0, env.stream, env.rk, p, ls, packed_dev); break;
+    case 6: hipLaunchKernelGGL(prf_wide_unpack_lists_kernel<6>, grid, block, 0, env.stream, env.rk, p, ls, packed_dev); break;
+    case 7: hipLaunchKernelGGL(prf_wide_unpack_lists_kernel<7>, grid, block, 0, env.stream, env.rk, p, ls, packed_dev); break;
+    default: hipLaunchKernelGGL(prf_wide_unpack_lists_kernel<0>, grid, block, 0, env.stream, env.rk, p, ls, packed_dev); break;
     }
     return hipGetLastError();
 }

@@ -767,14 +767,22 @@ class Engine:
         return self._took(self._lib.flashe_quantize_encrypt_pack_tensors_dev(self._h, it, idx, scheme, n, n_jobs, arr, nl, element_bits, self._ptr(u),
                                                                              self._ptr(packed)))
 
-    def unpack_decrypt_unquantize_model_dev(self, it, add_idx, minus_idx, n, n_jobs, packed, layers, element_bits, num_clients, out):
+    def unpack_decrypt_unquantize_model_dev(self, it, add_idx, minus_idx, n, n_jobs, packed, layers, element_bits, num_clients, out,
+                                            fn="flashe_unpack_decrypt_unquantize_model_dev"):
         """unpack_dev + decrypt_unquantize_model_dev over the whole vector in ONE launch (flashe_unpack_decrypt_unquantize_model_dev);
-        False -- nothing was launched -- when the library declines (prefix lists longer than one each, another width), True otherwise."""
+        False -- nothing was launched -- when the library declines (prefix lists longer than one each: the lists method below takes
+        those; another width), True otherwise."""
         pa, _a = _u32_list(add_idx)
         pm, _m = _u32_list(minus_idx)
         arr, nl = self._codec_layers(layers)
-        return self._took(self._lib.flashe_unpack_decrypt_unquantize_model_dev(self._h, it, pa, len(add_idx), pm, len(minus_idx), n, n_jobs, self._ptr(packed),
-                                                                               arr, nl, element_bits, num_clients, self._ptr(out)))
+        return self._took(getattr(self._lib, fn)(self._h, it, pa, len(add_idx), pm, len(minus_idx), n, n_jobs, self._ptr(packed), arr, nl, element_bits,
+                                                 num_clients, self._ptr(out)))
+
+    def unpack_decrypt_lists_unquantize_model_dev(self, it, add_idx, minus_idx, n, n_jobs, packed, layers, element_bits, num_clients, out):
+        """The same with prefix lists of up to 96 each, repeats summed (a round with a dropout, the single mask's decrypt), still ONE launch
+        (flashe_unpack_decrypt_lists_unquantize_model_dev); False -- nothing was launched -- for a longer list or another width."""
+        return Engine.unpack_decrypt_unquantize_model_dev(self, it, add_idx, minus_idx, n, n_jobs, packed, layers, element_bits, num_clients, out,
+                                                          fn="flashe_unpack_decrypt_lists_unquantize_model_dev")
 
     def quantize_batch_encrypt_pack_model_dev(self, it, idx, scheme, layers, element_bits, field_bits, u, n_elems, packed):
         """quantize_batch_model_dev + encrypt_dev + pack_dev of a batched job at int_bits 65 .. 128 in ONE launch
@@ -790,15 +798,22 @@ class Engine:
         return self._took(self._lib.flashe_quantize_batch_encrypt_pack_tensors_dev(self._h, it, idx, scheme, arr, nl, int(n_values), element_bits, field_bits,
                                                                                    self._ptr(u), int(n_elems), self._ptr(packed)))
 
-    def unpack_decrypt_unbatch_unquantize_model_dev(self, it, add_idx, minus_idx, layers, element_bits, field_bits, num_clients, packed, n_elems, out):
+    def unpack_decrypt_unbatch_unquantize_model_dev(self, it, add_idx, minus_idx, layers, element_bits, field_bits, num_clients, packed, n_elems, out,
+                                                    fn="flashe_unpack_decrypt_unbatch_unquantize_model_dev"):
         """unpack_dev + decrypt_dev + unbatch_unquantize_model_dev in ONE launch (flashe_unpack_decrypt_unbatch_unquantize_model_dev);
-        False -- nothing was launched -- when the library declines (prefix lists longer than one each, another width), True otherwise."""
+        False -- nothing was launched -- when the library declines (prefix lists longer than one each: the lists method below takes
+        those; another width), True otherwise."""
         pa, _a = _u32_list(add_idx)
         pm, _m = _u32_list(minus_idx)
         arr, nl = self._batch_layers(layers)
-        return self._took(self._lib.flashe_unpack_decrypt_unbatch_unquantize_model_dev(self._h, it, pa, len(add_idx), pm, len(minus_idx), arr, nl, element_bits,
-                                                                                       field_bits, num_clients, self._ptr(packed), int(n_elems),
-                                                                                       self._ptr(out)))
+        return self._took(getattr(self._lib, fn)(self._h, it, pa, len(add_idx), pm, len(minus_idx), arr, nl, element_bits, field_bits, num_clients,
+                                                 self._ptr(packed), int(n_elems), self._ptr(out)))
+
+    def unpack_decrypt_lists_unbatch_unquantize_model_dev(self, it, add_idx, minus_idx, layers, element_bits, field_bits, num_clients, packed, n_elems, out):
+        """The same with prefix lists of up to 96 each, repeats summed, still ONE launch (flashe_unpack_decrypt_lists_unbatch_unquantize_model_dev);
+        False -- nothing was launched -- for a longer list or another width."""
+        return Engine.unpack_decrypt_unbatch_unquantize_model_dev(self, it, add_idx, minus_idx, layers, element_bits, field_bits, num_clients, packed, n_elems,
+                                                                  out, fn="flashe_unpack_decrypt_lists_unbatch_unquantize_model_dev")
 
     def _cohort_launch(self, name, it, idx, ns, n_jobs, layers, srcs, dtypes, bits, u, cts, *vecs):
         """The library's chained cohort launch `name` (_lib.COHORT_LAUNCHES): the shared table, the sources, the ciphertext pointers and -- a

@@ -103,7 +103,9 @@ typedef struct flashe_ctx flashe_ctx;
  *      the packed wire form at int_bits 16 .. 64: one launch each way, no unpacked ciphertext vector);
  *      flashe_quantize_batch_encrypt_pack_model_dev / flashe_quantize_batch_encrypt_pack_tensors_dev /
  *      flashe_unpack_decrypt_unbatch_unquantize_model_dev (the BATCHED client step straight to and from the packed wire form at int_bits
- *      65 .. 128: one launch each way, no 16-byte plaintext or ciphertext vector) */
+ *      65 .. 128: one launch each way, no 16-byte plaintext or ciphertext vector);
+ *      flashe_unpack_decrypt_lists_unquantize_model_dev / flashe_unpack_decrypt_lists_unbatch_unquantize_model_dev (both ways back with
+ *      prefix lists of up to 96 each: a round with a dropout, the single mask's decrypt) */
 #define FLASHE_ABI_VERSION 4
 int flashe_abi_version(void);
 int flashe_device_count(int *count);
@@ -731,11 +733,22 @@ int flashe_quantize_encrypt_pack_tensors_dev(flashe_ctx *ctx, uint32_t iter, uin
  * flashe_decrypt_unquantize_model_dev over the whole vector computes, bit for bit, in ONE launch -- the unpacked element vector never
  * exists.  packed_dev: the packed sum as above (read only); out_dev: n float64 values.
  * FLASHE_ENOTSUP -- checked first, nothing launched -- outside the admission above, and for n_add > 1 or n_minus > 1 (a round with
- * dropouts, the single mask's decrypt: those lists stay with the two calls); FLASHE_EINVAL as flashe_decrypt_unquantize_model_dev. */
+ * dropouts, the single mask's decrypt: the lists form below takes those); FLASHE_EINVAL as flashe_decrypt_unquantize_model_dev. */
 int flashe_unpack_decrypt_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx,
                                                int n_minus, uint64_t n, uint32_t n_jobs, const uint64_t *packed_dev,
                                                const flashe_codec_layer *layers, int n_layers, int element_bits, int num_clients,
                                                double *out_dev);
+/* The way back with prefix LISTS (new; jzf_flashe.py:126-150, 311-314 then as above): the same contract for a round in which a client
+ * dropped out (one add and one minus prefix per run of uploaders) and for the single mask's decrypt (one minus prefix per uploader):
+ * 0 .. 96 prefixes per list, at least one in all, repeated prefixes summed as flashe_decrypt_dev sums them -- still ONE launch, which
+ * builds the prefixes' round-1 states in an LDS table and walks it two prefixes at a time.  Bit for bit flashe_unpack_dev followed by
+ * flashe_decrypt_unquantize_model_dev with the same lists.
+ * FLASHE_ENOTSUP -- checked first, nothing launched, staged or written -- outside the admission above and for a list longer than 96
+ * (run the two calls); FLASHE_EINVAL as flashe_unpack_decrypt_unquantize_model_dev. */
+int flashe_unpack_decrypt_lists_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add,
+                                                     const uint32_t *minus_idx, int n_minus, uint64_t n, uint32_t n_jobs,
+                                                     const uint64_t *packed_dev, const flashe_codec_layer *layers, int n_layers,
+                                                     int element_bits, int num_clients, double *out_dev);
 /* The BATCHED client step straight to the packed wire form at int_bits 65 .. 128 (new; jzf_quantize.py:162-185, 436-451 then
  * jzf_flashe.py:431-594 then jzf_weights.py:155-231): what flashe_quantize_batch_model_dev, flashe_encrypt_dev (cipher index idx, `scheme`)
  * over the n_elems batched elements and flashe_pack_dev compute, bit for bit, in ONE launch -- neither the batched plaintext nor the
@@ -757,12 +770,21 @@ int flashe_quantize_batch_encrypt_pack_tensors_dev(flashe_ctx *ctx, uint32_t ite
  * flashe_decrypt_dev over the n_elems elements and flashe_unbatch_unquantize_model_dev compute, bit for bit, in ONE launch.  packed_dev:
  * the packed sum as above (read only, 8-byte aligned); out_dev: the model's float64 values in walking order, 8-byte aligned.
  * FLASHE_ENOTSUP -- checked first, nothing launched or staged -- outside the admission above, and for n_add > 1 or n_minus > 1 (a round
- * with dropouts, the single mask's decrypt: those lists stay with the three calls); FLASHE_EINVAL as flashe_unbatch_unquantize_model_dev,
+ * with dropouts, the single mask's decrypt: the lists form below takes those); FLASHE_EINVAL as flashe_unbatch_unquantize_model_dev,
  * and for no prefix at all. */
 int flashe_unpack_decrypt_unbatch_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add,
                                                        const uint32_t *minus_idx, int n_minus, const flashe_batch_layer *layers, int n_layers,
                                                        int element_bits, int field_bits, int num_clients, const uint64_t *packed_dev,
                                                        uint64_t n_elems, double *out_dev);
+/* The batched way back with prefix LISTS (new; jzf_flashe.py:126-150, 311-314 then as above): 0 .. 96 prefixes per list, at least one in
+ * all, repeats summed -- a round with a dropout, the single mask's decrypt -- in ONE launch; bit for bit flashe_unpack_dev, flashe_decrypt_dev
+ * with the same lists and flashe_unbatch_unquantize_model_dev.
+ * FLASHE_ENOTSUP -- checked first, nothing launched, staged or written -- outside the admission above and for a list longer than 96 (run
+ * the three calls); FLASHE_EINVAL as flashe_unpack_decrypt_unbatch_unquantize_model_dev. */
+int flashe_unpack_decrypt_lists_unbatch_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add,
+                                                             const uint32_t *minus_idx, int n_minus, const flashe_batch_layer *layers,
+                                                             int n_layers, int element_bits, int field_bits, int num_clients,
+                                                             const uint64_t *packed_dev, uint64_t n_elems, double *out_dev);
 /* A COHORT of n_clients consecutive clients (cipher indices first_idx .. first_idx + n_clients - 1, double mask) hosted on this GPU (new):
  * ONE chained launch quantises every client's float model (jzf_quantize.py:55-67, client c's element k with the draw
  * u_dev[c * n + k]), encrypts with the PRF streams the consecutive clients share (n_clients + 1 streams instead of 2 n_clients,
