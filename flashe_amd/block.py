@@ -21,6 +21,13 @@ _RNG_RUN_MAX = 1 << 26          # draws per device call of quantize_encrypt (512
 # than either form's spread at int_bits 20 and 23 (x 1.40 - 1.78) and leads within the spread at 64 (x 1.10 - 1.14: the fill of 8-byte limbs),
 # so 33 .. 64 stay staged; the way back takes its one launch at every width 16 .. 64 (x 1.22 - 1.81).  profiles/r39_wire_client_step.log
 _WIRE_OUT_MAX_BITS = 32
+# A PRECOMPUTE job (the masks cached in the ctx) goes to and from the wire form in one launch without AES (wire_prepared.hip) only on
+# request: on the way out under packed="fused", on the way back for a client whose upload was made with packed="fused" -- or for every
+# client under this switch.  The launches move 30.5 / 26.5 bytes per value against the staged 46.5 / 42.5 at int_bits 20 (119 / 95 against
+# 151 / 127 per element at 120, bs 6), counted from the code.  Measured against the staged sequences in two processes they win by more than
+# either form's spread everywhere (x 1.35 - 2.38) but on the way out at 1e7 values, int_bits 20 and 64 (x 1.22 - 1.28, inside the fused
+# form's spread); no threshold was fitted, so the ROUTING is unmeasured and stays opt-in.  profiles/r42_wire_prepared_step.log
+_WIRE_PREPARED_BACK = False
 # decrypt_unquantize takes a BATCHED job's packed sum (int_bits 65 .. 128) to the floats in one launch from this many batched elements on:
 # measured against unpack_dev + decrypt_dev + unbatch_unquantize_model_dev at int_bits 120 / 128 in two processes, it wins by more than
 # either form's spread at 1,666,668 and 4,259,506 elements in both (x 1.46 - 1.66); at 10,285 .. 500,001 elements the medians lead too
@@ -593,13 +600,16 @@ class FlasheClient(object):
         """packed (new): the one key of the result holds the ciphertext in its WIRE form -- a PackedVector (device=True) or the Python int
         JZFTransferableWeights.compress builds (device=False).  A dense un-batched job at int_bits 16 .. 32 goes from the floats to the
         packed limbs in ONE launch (flashe_quantize_encrypt_pack_tensors_dev, path "fused"); a batched job, the sparse job's 'zzz', a
-        consumed precompute cache, other widths and a cipher with `masks` run today's step followed by pack_dev (path "staged").
+        consumed precompute cache (under packed=True), other widths and a cipher with `masks` run today's step followed by pack_dev
+        (path "staged").
         packed="fused" (new) takes the one launch WHEREVER the library admits it: a batched job at int_bits 65 .. 128 goes from the floats
         to the packed limbs in one launch too (flashe_quantize_batch_encrypt_pack_model_dev / _tensors_dev: quantise + batch + encrypt +
         pack, no 16-byte vector in HBM), and an un-batched job takes its launch at int_bits 33 .. 64 as well.  The same integer as
-        packed=True, bit for bit; a consumed precompute cache, the sparse job's 'zzz', a model above _RNG_RUN_MAX values, an engine
-        without the entry point and a call the library declines run the staged sequence on the same draws (path "staged").  Any other
-        value of `packed` is read as true or false.
+        packed=True, bit for bit; the sparse job's 'zzz', a model above _RNG_RUN_MAX values, an engine
+        without the entry point and a call the library declines run the staged sequence on the same draws (path "staged").  A consumed
+        precompute cache takes its own one launch, which runs no AES (flashe_quantize_encrypt_prepared_pack_tensors_dev, the batched job
+        flashe_quantize_batch_encrypt_prepared_pack_model_dev / _tensors_dev; path "fused"), and the client remembers the request:
+        decrypt_unquantize then takes the packed sum back in one launch as well.  Any other value of `packed` is read as true or false.
 
         degree (new): `weights *= degree` first (jzf_aggregator.py:676, the client's sample count times aggregate_every_n_epoch): every
         layer but the sparse job's 'zzz' becomes a NEW array `layer * degree` in the dtype NumPy gives that product (a float32 layer stays
@@ -644,10 +654,13 @@ class FlasheClient(object):
         if packed:
             # (_encrypt_tail: True = take the one launch where it is the measured choice; "fused" = wherever the library admits it)
             self._to_wire = "fused" if isinstance(packed, str) and packed == "fused" else True
+            self._upload_fused = self._to_wire == "fused"            # (_decrypt_floats: the way back of a precompute job follows the request)
             try:
                 return self._packed_result(self.quantize_encrypt(weights, True, normalize, rng, degree), device)
             finally:
                 self._to_wire = False
+        if not getattr(self, "_to_wire", False):
+            self._upload_fused = False
         if any(interop.is_foreign(weights._weights[k]) for k in weights.walking_order):
             return self._quantize_encrypt_tensors(weights, device, normalize, rng, degree)
         if degree is not None:
@@ -734,14 +747,15 @@ class FlasheClient(object):
         ptrs, keep = _stage_host_layers(eng, host)
         rows = [(sizes[li] if self.batch else starts[li], ptrs[li], q.alpha_list[li], host[li].dtype == np.float64) for li in range(len(order))]
         launch = (eng.quantize_encrypt_model_dev, eng.quantize_encrypt_prepared_model_dev, eng.quantize_batch_model_dev,
-                  eng.quantize_batch_encrypt_prepared_model_dev, getattr(eng, "quantize_batch_encrypt_pack_model_dev", None))
+                  eng.quantize_batch_encrypt_prepared_model_dev, getattr(eng, "quantize_batch_encrypt_pack_model_dev", None),
+                  getattr(eng, "quantize_batch_encrypt_prepared_pack_model_dev", None))
         return mode, order, zzz, sizes, starts, shape_dict, rows, launch, keep
 
     def _encrypt_tail(self, weights, device, mode, order, zzz, sizes, starts, shape_dict, rows, launch, keep, hold=None, normalize=False,
                       rng=None):
         """The fused step behind either front end: the draws, the launches and the result.  `rows` are the layers `order` (sizes, starts,
         shape_dict) as the entry points in `launch` -- un-batched online and prepared, batched online and prepared, and the batched job's one
-        launch to the wire form (None: the engine has none) -- read them; mode
+        launch to the wire form, online and prepared (None: the engine has none) -- read them; mode
         is _prepared_mode of the encrypt cache; zzz the sparse job's trailing value (host) or None; keep what the launches read: it lives to
         the end of the call.  The tensor front end also passes hold (the owners of the caller's tensors: held on the engine until the
         launches have finished) and normalize (the 'zzz' value is still to be normalised -- the host front end has normalised the whole
@@ -750,8 +764,10 @@ class FlasheClient(object):
         from .engine import DeviceVector
         q, c = self.quantizer, self.cipher
         eng, n = c.engine, sum(sizes)
-        online, prepared, batch, batch_prepared, batch_wire = launch
+        online, prepared, batch, batch_prepared, batch_wire, batch_prepared_wire = launch
         scheme = 1 if c.masking_scheme == "double" else 0
+        # a consumed precompute cache straight to the wire form: on request only (packed="fused"), the routing is unmeasured
+        prepared_wire = getattr(self, "_to_wire", False) == "fused" and mode == "ctx" and zzz is None and 0 < n <= _RNG_RUN_MAX
         if self.batch:
             # quantise + batch of the whole model in ONE launch (per-layer alpha, per-layer zero padding), then the encrypt of the flattened
             # batched vector: the draws are one stretch of NumPy's stream over all VALUES in walking order
@@ -770,6 +786,12 @@ class FlasheClient(object):
                 from .engine import PackedVector
                 ct = PackedVector(eng, n_elems, self.int_bits, path="fused")
                 if not batch_wire(c.iter_index, c.idx, scheme, rows, q.element_bits, field_bits, du, n_elems, ct.buf):
+                    ct = None
+            elif prepared_wire and batch_prepared_wire is not None and self.int_bits > 64:
+                # the same with the prepared masks: quantise + batch + masks + pack in ONE launch, no AES; declined: today's prepared launch
+                from .engine import PackedVector
+                ct = PackedVector(eng, n_elems, self.int_bits, path="fused")
+                if not batch_prepared_wire(rows, q.element_bits, field_bits, du, n_elems, ct.buf):
                     ct = None
             if ct is None and mode == "ctx":    # quantise + batch + the prepared masks: one launch, no AES
                 ct = DeviceVector(eng, n_elems)
@@ -801,6 +823,15 @@ class FlasheClient(object):
                 if not eng.quantize_encrypt_pack_tensors_dev(c.iter_index, c.idx, scheme, n, _cipher_mod.N_JOBS, wrows, q.element_bits, du, wire.buf):
                     wire = DeviceVector(eng, n)               # (declined: today's launch on the same draws; _packed_result packs it)
                     online(c.iter_index, c.idx, scheme, n, _cipher_mod.N_JOBS, 0, n, rows, q.element_bits, du, wire.ptr)
+            elif prepared_wire and 16 <= self.int_bits <= 64 and hasattr(eng, "quantize_encrypt_prepared_pack_tensors_dev"):
+                # the same with the prepared masks (no AES): one run of draws, ONE launch; declined: today's prepared launch over the whole vector
+                from ._lib import TENSOR_F32, TENSOR_F64
+                from .engine import PackedVector
+                wrows = rows if len(rows[0]) == 6 else [(s_, p_, a_, 0.0, TENSOR_F64 if f64 else TENSOR_F32, 0) for s_, p_, a_, f64 in rows]
+                wire, du = PackedVector(eng, n, self.int_bits, path="fused"), _draws(eng, n, rng)
+                if not eng.quantize_encrypt_prepared_pack_tensors_dev(n, wrows, q.element_bits, du, wire.buf):
+                    wire = DeviceVector(eng, n)
+                    prepared(n, 0, n, rows, q.element_bits, du, wire.ptr)
             ct = wire if wire is not None else DeviceVector(eng, n + (1 if zzz is not None else 0))
             at = len(order) if wire is not None else 0
             while at < len(order):
@@ -906,7 +937,9 @@ class FlasheClient(object):
         added by the same one launch in place of the PRF streams (flashe_decrypt_prepared_unquantize_model_dev / _unbatch_: the batched job's
         decrypt + unbatch becomes one launch); the prefixes set_idx_list leaves uncovered (dropouts) go through a PRF launch first.  The
         cache is consumed as the call-by-call decrypt consumes it; the encrypt cache of the next round is not touched.  Masks a caller
-        assigned as plain arrays take the same sequence call by call."""
+        assigned as plain arrays take the same sequence call by call.  A PackedVector aggregate of a precompute job whose upload was made
+        with packed="fused" comes back in ONE launch without AES when nobody dropped out (flashe_unpack_decrypt_prepared_unquantize_model_dev
+        / _unbatch_); with extras it is unpacked for the sequence above."""
         q, c = self.quantizer, self.cipher
         degree, total_degree = self._back_degrees(degree, total_degree)
         if out is not None:
@@ -1049,13 +1082,27 @@ class FlasheClient(object):
                  and hasattr(eng, "unpack_decrypt_lists_unbatch_unquantize_model_dev" if self.batch else "unpack_decrypt_lists_unquantize_model_dev")
                  and n >= (_WIDE_WIRE_LISTS_MIN_ELEMS if self.batch else _WIRE_LISTS_MIN_ELEMS)
                  and len(add_idx) + len(minus_idx) <= (_WIDE_WIRE_LISTS_MAX_PREFIXES if self.batch else _WIRE_LISTS_MAX_PREFIXES))
-        if isinstance(dv, PackedVector) and not wide_wire and not (self.batch and lists) and (self.batch or mode == "ctx" or dv.bits != self.int_bits):
+        # a precompute job's packed sum straight to the floats in ONE launch without AES (wire_prepared.hip), when no prefix is left uncovered:
+        # taken on request only -- the upload was made with packed="fused", or _WIRE_PREPARED_BACK -- because the routing is unmeasured
+        prep_wire = (isinstance(dv, PackedVector) and mode == "ctx" and not add_idx and not minus_idx and dv.bits == self.int_bits and n > 0
+                     and (getattr(self, "_upload_fused", False) or _WIRE_PREPARED_BACK)
+                     and hasattr(eng, "unpack_decrypt_prepared_unbatch_unquantize_model_dev" if self.batch else "unpack_decrypt_prepared_unquantize_model_dev"))
+        if (isinstance(dv, PackedVector) and not wide_wire and not (self.batch and lists) and not prep_wire
+                and (self.batch or mode == "ctx" or dv.bits != self.int_bits)):
             dv = self._unpacked(dv)
         if mode == "ctx":
             c._check_prepared_len(c.next_iter_decrypt_prepared['add'], n)          # (the call-by-call decrypt's error; the cache stays)
         if self.batch:
             layers, field_bits = self._batched_back_table(sizes, n)
             dout = eng.alloc(max(8 * sum(sizes), 16))
+            if prep_wire:
+                dv.wait_on(eng)
+                if eng.unpack_decrypt_prepared_unbatch_unquantize_model_dev(c.iter_index, add_idx, minus_idx, _cipher_mod.N_JOBS, layers, q.element_bits,
+                                                                            field_bits, q.num_clients, dv.buf, n, dout):
+                    eng.hold([dv])
+                    self._decrypt_done(mode)
+                    return dout
+                dv = self._unpacked(dv)                       # (declined: today's prepared launch)
             if wide_wire or lists:
                 # the packed sum of a batched job straight to the floats in ONE launch (int_bits 65 .. 128): the one-prefix launch, which
                 # declines prefix lists longer than one each, then the lists launch where it is routed; declined by both (another width,
@@ -1080,6 +1127,14 @@ class FlasheClient(object):
             return dout
         table = self._back_table(sizes, n)
         dout = eng.alloc(max(8 * n, 16))
+        if prep_wire:
+            dv.wait_on(eng)
+            if eng.unpack_decrypt_prepared_unquantize_model_dev(c.iter_index, add_idx, minus_idx, n, _cipher_mod.N_JOBS, dv.buf, table, q.element_bits,
+                                                                q.num_clients, dout):
+                eng.hold([dv])
+                self._decrypt_done(mode)
+                return dout
+            dv = self._unpacked(dv)                           # (declined: today's prepared launch)
         if isinstance(dv, PackedVector):
             # the packed sum straight to the floats in ONE launch: the one-prefix launch, which declines prefix lists longer than one each
             # (dropouts, the single mask's decrypt), then the lists launch where it is routed; declined by both it is unpacked for today's launch
@@ -1166,7 +1221,9 @@ class FlasheClient(object):
                   lambda r, *a: eng.quantize_batch_tensors_dev(r, n, *a),
                   lambda r, *a: eng.quantize_batch_encrypt_prepared_tensors_dev(r, n, *a),
                   (lambda it, idx, sch, r, *a: eng.quantize_batch_encrypt_pack_tensors_dev(it, idx, sch, r, n, *a))
-                  if hasattr(eng, "quantize_batch_encrypt_pack_tensors_dev") else None)
+                  if hasattr(eng, "quantize_batch_encrypt_pack_tensors_dev") else None,
+                  (lambda r, *a: eng.quantize_batch_encrypt_prepared_pack_tensors_dev(r, n, *a))
+                  if hasattr(eng, "quantize_batch_encrypt_prepared_pack_tensors_dev") else None)
         shape_dict = {k: layer[4] for k, layer in zip(order, layers)}
         return self._encrypt_tail(weights, device, mode, order, zzz, sizes, starts, shape_dict, rows, launch, keep, hold=owners, normalize=normalize,
                                   rng=rng)

@@ -1729,6 +1729,107 @@ int flashe_decrypt_prepared_unbatch_unquantize_model_dev(flashe_ctx *ctx, uint32
     return FLASHE_OK;
 }
 
+// ---- the same client step straight to and from the packed wire form (wire_prepared.hip): the five calls above that take whole vectors,
+// with the ciphertext / the sum in its wire form.  What the launch does not take -- a width outside its class, n outside [1, 2^32), extra
+// prefixes on the way back (prepared_extras needs the unpacked vector) -- is declined first: nothing launched, staged, written or consumed ----
+static int prepared_wire_admit(flashe_ctx *ctx, const char *who, bool wide, uint64_t n, bool extras)
+{
+    if (!(wide ? combine_wide_wire_admits(ctx->env, n) : combine_small_wire_admits(ctx->env, n)))
+        return fail(ctx, FLASHE_ENOTSUP, "%s: needs %s and 1 <= n < 2^32 (run the prepared call and flashe_pack_dev / flashe_unpack_dev)", who,
+                    wide ? "65 <= int_bits <= 128" : "16 <= int_bits <= 64");
+    if (extras) return fail(ctx, FLASHE_ENOTSUP, "%s: prefixes the prepared masks do not cover (run flashe_unpack_dev and the prepared decrypt)", who);
+    return FLASHE_OK;
+}
+
+int flashe_quantize_encrypt_prepared_pack_tensors_dev(flashe_ctx *ctx, uint64_t n, const flashe_tensor_layer *layers, int n_layers, int element_bits,
+                                                      const double *u_dev, uint64_t *packed_dev)
+{
+    CHECK_CTX(ctx);
+    flashe_ctx::Prepared &pr = ctx->prep_enc;
+    int rc = prepared_wire_admit(ctx, "flashe_quantize_encrypt_prepared_pack_tensors_dev", false, n, false);
+    if (rc || (rc = check_prepared(ctx, pr, n, "encrypt"))) return rc;
+    if ((rc = check_model_front(ctx, n, 1, 0, n, element_bits, u_dev, packed_dev)) || (rc = check_tensor_layers(ctx, n, layers, n_layers, true))) return rc;
+    std::vector<flashe_codec_layer> cl;
+    Codec cq{};
+    if ((rc = tensor_codec_layers(ctx, n, layers, n_layers, 0, n, cl)) ||
+        (rc = stage_codec_layers(ctx, n, cl.data(), n_layers, true, element_bits, 1, 0, n, u_dev, nullptr, &cq)))
+        return rc;
+    HIP_TRY(ctx, launch_combine_small_pack(ctx->env, n, cq, prepared_at(ctx, pr.add, true, 0), prepared_at(ctx, pr.minus, pr.has_minus, 0), packed_dev));
+    pr.valid = false;
+    return FLASHE_OK;
+}
+
+int flashe_unpack_decrypt_prepared_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx,
+                                                        int n_minus, uint64_t n, uint32_t n_jobs, const uint64_t *packed_dev, const flashe_codec_layer *layers,
+                                                        int n_layers, int element_bits, int num_clients, double *out_dev)
+{
+    CHECK_CTX(ctx);
+    (void)iter; (void)add_idx; (void)minus_idx;                          // (the masks are the cached ones; a call with extras is declined)
+    flashe_ctx::Prepared &pr = ctx->prep_dec;
+    int rc = prepared_wire_admit(ctx, "flashe_unpack_decrypt_prepared_unquantize_model_dev", false, n, n_add > 0 || n_minus > 0);
+    if (rc || (rc = check_prepared(ctx, pr, n, "decrypt"))) return rc;
+    if (!packed_dev || !out_dev) return fail(ctx, FLASHE_EINVAL, "null vector");
+    if (num_clients < 1) return fail(ctx, FLASHE_EINVAL, "num_clients must be >= 1");
+    if (n_add < 0 || n_minus < 0 || n_jobs < 1) return fail(ctx, FLASHE_EINVAL, "negative prefix count or n_jobs 0");
+    if ((rc = check_codec_bits(ctx, element_bits)) || (rc = check_aligned(ctx, {packed_dev, out_dev}, 8))) return rc;
+    Codec cq{};
+    if ((rc = stage_codec_layers(ctx, n, layers, n_layers, false, element_bits, num_clients, 0, n, nullptr, out_dev, &cq))) return rc;
+    HIP_TRY(ctx, launch_combine_small_unpack(ctx->env, n, packed_dev, prepared_at(ctx, pr.add, true, 0), prepared_at(ctx, pr.minus, pr.has_minus, 0), cq));
+    pr.valid = false;
+    return FLASHE_OK;
+}
+
+int flashe_quantize_batch_encrypt_prepared_pack_model_dev(flashe_ctx *ctx, const flashe_batch_layer *layers, int n_layers, int element_bits, int field_bits,
+                                                          const double *u_dev, uint64_t n_elems, uint64_t *packed_dev)
+{
+    CHECK_CTX(ctx);
+    flashe_ctx::Prepared &pr = ctx->prep_enc;
+    BatchTab bt;
+    int rc = prepared_wire_admit(ctx, "flashe_quantize_batch_encrypt_prepared_pack_model_dev", true, n_elems, false);
+    if (rc || (rc = check_prepared(ctx, pr, n_elems, "encrypt")) ||
+        (rc = stage_batch_layers(ctx, layers, n_layers, true, element_bits, field_bits, 1, n_elems, &bt)))
+        return rc;
+    if (!u_dev || !packed_dev) return fail(ctx, FLASHE_EINVAL, "null vector");
+    if ((rc = check_vec_aligned(ctx, {packed_dev})) || (rc = check_aligned(ctx, {u_dev}, 8))) return rc;
+    HIP_TRY(ctx, launch_combine_wide_pack(ctx->env, bt.tab, bt.n_tab, field_bits, u_dev, n_elems, prepared_at(ctx, pr.add, true, 0),
+                                          prepared_at(ctx, pr.minus, pr.has_minus, 0), packed_dev));
+    pr.valid = false;
+    return FLASHE_OK;
+}
+
+int flashe_quantize_batch_encrypt_prepared_pack_tensors_dev(flashe_ctx *ctx, const flashe_tensor_layer *layers, int n_layers, uint64_t n_values,
+                                                            int element_bits, int field_bits, const double *u_dev, uint64_t n_elems, uint64_t *packed_dev)
+{
+    CHECK_CTX(ctx);
+    int rc = prepared_wire_admit(ctx, "flashe_quantize_batch_encrypt_prepared_pack_tensors_dev", true, n_elems, false);
+    std::vector<flashe_batch_layer> bl;
+    if (rc || (rc = check_prepared(ctx, ctx->prep_enc, n_elems, "encrypt")) || (rc = check_tensor_layers(ctx, n_values, layers, n_layers, true)) ||
+        (rc = tensor_batch_layers(ctx, layers, n_layers, n_values, element_bits, field_bits, u_dev, n_elems, packed_dev, bl)))
+        return rc;
+    return flashe_quantize_batch_encrypt_prepared_pack_model_dev(ctx, bl.data(), n_layers, element_bits, field_bits, u_dev, n_elems, packed_dev);
+}
+
+int flashe_unpack_decrypt_prepared_unbatch_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx,
+                                                                int n_minus, uint32_t n_jobs, const flashe_batch_layer *layers, int n_layers, int element_bits,
+                                                                int field_bits, int num_clients, const uint64_t *packed_dev, uint64_t n_elems, double *out_dev)
+{
+    CHECK_CTX(ctx);
+    (void)iter; (void)add_idx; (void)minus_idx;
+    flashe_ctx::Prepared &pr = ctx->prep_dec;
+    int rc = prepared_wire_admit(ctx, "flashe_unpack_decrypt_prepared_unbatch_unquantize_model_dev", true, n_elems, n_add > 0 || n_minus > 0);
+    if (rc || (rc = check_prepared(ctx, pr, n_elems, "decrypt"))) return rc;
+    if (num_clients < 1) return fail(ctx, FLASHE_EINVAL, "num_clients must be >= 1");
+    if (n_add < 0 || n_minus < 0 || n_jobs < 1) return fail(ctx, FLASHE_EINVAL, "negative prefix count or n_jobs 0");
+    BatchTab bt;
+    if ((rc = stage_batch_layers(ctx, layers, n_layers, false, element_bits, field_bits, num_clients, n_elems, &bt))) return rc;
+    if (!packed_dev || !out_dev) return fail(ctx, FLASHE_EINVAL, "null vector");
+    if ((rc = check_aligned(ctx, {packed_dev, out_dev}, 8))) return rc;
+    HIP_TRY(ctx, launch_combine_wide_unpack(ctx->env, bt.tab, bt.n_tab, field_bits, packed_dev, n_elems, prepared_at(ctx, pr.add, true, 0),
+                                            prepared_at(ctx, pr.minus, pr.has_minus, 0), out_dev));
+    pr.valid = false;
+    return FLASHE_OK;
+}
+
 // Every layer of a model where its owner keeps it (include/flashe.h): the tables are built on the host in the caller's layer order, sorted
 // by compute class for the launches, uploaded once.
 int flashe_sparsify_tensors_dev(flashe_ctx *ctx, uint64_t n, const flashe_tensor_layer *layers, int n_layers, const uint64_t *k, void *residual_dev,

@@ -314,6 +314,23 @@ hipError_t launch_wide_unpack(const LaunchEnv &env, uint32_t iter, bool has_add,
 hipError_t launch_wide_unpack_lists(const LaunchEnv &env, uint32_t iter, const uint32_t *add, int n_add, const uint32_t *minus, int n_minus,
                                     const BatchLayer *layers_dev, int n_layers, int field_bits, const uint64_t *packed_dev, uint64_t n_elems, double *out_dev);
 
+// A PRECOMPUTE job's online client step straight to and from the packed wire form (wire_prepared.hip): the launches above with masks the
+// caller holds in place of the PRF streams -- ct = (plaintext + add - minus) mod 2^b and out = unquantise((element + add - minus) mod 2^b),
+// add_dev / minus_dev one vector element per element (8 bytes at int_bits <= 64, 16 above), minus_dev null for a single-mask cache.  No AES,
+// so no PRF backend is asked for: combine_small_wire_admits = 16 <= int_bits <= 64 and 1 <= n < 2^32, combine_wide_wire_admits = 65 <=
+// int_bits <= 128 and 1 <= n_elems < 2^32.  ONE launch each; every packed limb is written once with a plain store, none needs clearing.
+// cq: launch_small_pack's / launch_small_unpack's tables (k0 = 0); the batched arguments as launch_wide_pack / launch_wide_unpack take them.
+// hipErrorNotSupported: nothing launched.
+bool combine_small_wire_admits(const LaunchEnv &env, uint64_t n);
+bool combine_wide_wire_admits(const LaunchEnv &env, uint64_t n_elems);
+hipError_t launch_combine_small_pack(const LaunchEnv &env, uint64_t n, const Codec &cq, const uint64_t *add_dev, const uint64_t *minus_dev, uint64_t *packed_dev);
+hipError_t launch_combine_small_unpack(const LaunchEnv &env, uint64_t n, const uint64_t *packed_dev, const uint64_t *add_dev, const uint64_t *minus_dev,
+                                       const Codec &cq);
+hipError_t launch_combine_wide_pack(const LaunchEnv &env, const BatchLayer *layers_dev, int n_layers, int field_bits, const double *u_dev, uint64_t n_elems,
+                                    const uint64_t *add_dev, const uint64_t *minus_dev, uint64_t *packed_dev);
+hipError_t launch_combine_wide_unpack(const LaunchEnv &env, const BatchLayer *layers_dev, int n_layers, int field_bits, const uint64_t *packed_dev,
+                                      uint64_t n_elems, const uint64_t *add_dev, const uint64_t *minus_dev, double *out_dev);
+
 hipError_t launch_fill(const LaunchEnv &env, uint64_t n, uint64_t lo, uint64_t hi, uint64_t *out_dev);
 // locations >= total are skipped and reported through env.err_flag (the reference raises IndexError, jzf_aggregator.py:150-165)
 hipError_t launch_scatter(const LaunchEnv &env, uint64_t total, uint64_t k, const uint32_t *loc_dev,

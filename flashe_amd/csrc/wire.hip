@@ -20,6 +20,7 @@
 // lane ORs its own field into the at most three limbs it touches, atomically (pack), or stores its own cnt floats (unpack).
 #include "small_blocks.h"
 #include "wire_lists.h"
+#include "wire_tiles.h"
 
 namespace flashe {
 
@@ -39,26 +40,6 @@ __device__ __forceinline__ u128 wire_reverse(u128 v, int cnt, int b, uint64_t ma
         v >>= b;
     }
     return f;
-}
-
-// the wave-uniform table row that holds flat element `key` (the last row with start <= key), found with scalar loads
-__device__ __forceinline__ int wire_row_of(const CodecLayer *layers, int n_layers, uint64_t key)
-{
-    int lo = 0, hi = n_layers - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (*FLASHE_CONSTANT(const uint64_t, &layers[mid].start) <= key) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-// The row that holds ALL of the elements [e0, e1) of a tile, or -1 when they straddle a row boundary (at most one tile per layer: those
-// look every element's row up per lane).  e0, e1: wave-uniform.
-__device__ __forceinline__ int wire_tile_row(const Codec &cq, uint64_t e0, uint64_t e1, uint64_t n)
-{
-    const int row = wire_row_of(cq.layers, cq.n_layers, cq.k0 + e0);
-    const uint64_t end = row + 1 < cq.n_layers ? *FLASHE_CONSTANT(const uint64_t, &cq.layers[row + 1].start) : cq.k0 + n;
-    return cq.k0 + e1 <= end ? row : -1;
 }
 
 // The M plaintexts of a WHOLE block inside one table row, for the lane that owns it (the front end the compact cohort kernels call

@@ -1284,6 +1284,43 @@ class Engine:
                                                                                    element_bits, field_bits, num_clients, self._ptr(inp), int(n_elems),
                                                                                    self._ptr(out)))
 
+    # the same online step straight to and from the packed wire form (wire_prepared.hip: ONE launch, no AES, whole vectors).  False --
+    # nothing was launched or consumed -- when the library declines (FLASHE_ENOTSUP: another width class, extra prefixes on the way back:
+    # the caller runs the prepared call and pack_dev / unpack_dev); the cache rules raise as above
+    def quantize_encrypt_prepared_pack_tensors_dev(self, n, layers, element_bits, u, packed):
+        """quantize_encrypt_prepared_tensors_dev over the whole vector + pack_dev in one launch, int_bits 16 .. 64."""
+        arr, nl = self._tensor_layers(layers)
+        return self._took(self._lib.flashe_quantize_encrypt_prepared_pack_tensors_dev(self._h, n, arr, nl, element_bits, self._ptr(u), self._ptr(packed)))
+
+    def unpack_decrypt_prepared_unquantize_model_dev(self, it, add_idx, minus_idx, n, n_jobs, packed, layers, element_bits, num_clients, out):
+        """unpack_dev + decrypt_prepared_unquantize_model_dev in one launch, int_bits 16 .. 64; declined with extra prefixes."""
+        pa, _a = _u32_list(add_idx)
+        pm, _m = _u32_list(minus_idx)
+        arr, nl = self._codec_layers(layers)
+        return self._took(self._lib.flashe_unpack_decrypt_prepared_unquantize_model_dev(self._h, it, pa, len(add_idx), pm, len(minus_idx), n, n_jobs,
+                                                                                        self._ptr(packed), arr, nl, element_bits, num_clients, self._ptr(out)))
+
+    def quantize_batch_encrypt_prepared_pack_model_dev(self, layers, element_bits, field_bits, u, n_elems, packed):
+        """quantize_batch_encrypt_prepared_model_dev + pack_dev in one launch, int_bits 65 .. 128."""
+        arr, nl = self._batch_layers(layers)
+        return self._took(self._lib.flashe_quantize_batch_encrypt_prepared_pack_model_dev(self._h, arr, nl, element_bits, field_bits, self._ptr(u), int(n_elems),
+                                                                                          self._ptr(packed)))
+
+    def quantize_batch_encrypt_prepared_pack_tensors_dev(self, layers, n_values, element_bits, field_bits, u, n_elems, packed):
+        arr, nl = self._tensor_layers(layers)
+        return self._took(self._lib.flashe_quantize_batch_encrypt_prepared_pack_tensors_dev(self._h, arr, nl, int(n_values), element_bits, field_bits,
+                                                                                            self._ptr(u), int(n_elems), self._ptr(packed)))
+
+    def unpack_decrypt_prepared_unbatch_unquantize_model_dev(self, it, add_idx, minus_idx, n_jobs, layers, element_bits, field_bits, num_clients, packed,
+                                                             n_elems, out):
+        """unpack_dev + decrypt_prepared_unbatch_unquantize_model_dev in one launch, int_bits 65 .. 128; declined with extra prefixes."""
+        pa, _a = _u32_list(add_idx)
+        pm, _m = _u32_list(minus_idx)
+        arr, nl = self._batch_layers(layers)
+        return self._took(self._lib.flashe_unpack_decrypt_prepared_unbatch_unquantize_model_dev(self._h, it, pa, len(add_idx), pm, len(minus_idx), n_jobs, arr,
+                                                                                                nl, element_bits, field_bits, num_clients,
+                                                                                                self._ptr(packed), int(n_elems), self._ptr(out)))
+
     def decrypt_dev(self, it, add_idx, minus_idx, n, n_jobs, inp, out):
         pa, _a = _u32_list(add_idx)
         pm, _m = _u32_list(minus_idx)

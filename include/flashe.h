@@ -1178,6 +1178,33 @@ int flashe_decrypt_prepared_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter,
 int flashe_decrypt_prepared_unbatch_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx,
                                                          int n_minus, uint32_t n_jobs, const flashe_batch_layer *layers, int n_layers, int element_bits,
                                                          int field_bits, int num_clients, const uint64_t *in_dev, uint64_t n_elems, double *out_dev);
+/* The same online step straight to and from the packed WIRE form (new; jzf_flashe.py:456-488, :537-582 then jzf_weights.py:155-231): what
+ * the prepared call of the same name without `pack` / `unpack` over the WHOLE vector computes, followed by flashe_pack_dev / preceded by
+ * flashe_unpack_dev, bit for bit, in ONE launch that runs no AES -- the unpacked ciphertext vector never exists.  packed_dev: ceil(n
+ * int_bits / 64) limbs, element j at bits [int_bits (n - 1 - j), int_bits (n - j)), 8-byte aligned (the batched way out: aligned like a
+ * ciphertext vector); on the way out EVERY limb is written once (the unused top bits of the last one zero), none needs to be zero on entry
+ * and nothing is cleared beforehand.  Tables, draws and outputs as the prepared siblings take them; iter, n_jobs and the prefix lists of the
+ * way back are those siblings' arguments (the masks are the cached ones).
+ * FLASHE_ENOTSUP -- checked first; nothing launched, staged, written or consumed -- unless 16 <= int_bits <= 64 (the un-batched forms) or
+ * 65 <= int_bits <= 128 (the batched forms) and 1 <= n < 2^32, and on the way back for n_add + n_minus > 0: the prefixes a dropout leaves
+ * uncovered need the unpacked vector (flashe_unpack_dev, then the prepared decrypt).  No PRF backend is asked for.  Cache rules: those
+ * above -- FLASHE_EINVAL without a valid cache of the direction, FLASHE_EINVAL with the cache kept on a length mismatch, consumed by the
+ * call that takes it.  Whole vectors only.  Not capturable. */
+int flashe_quantize_encrypt_prepared_pack_tensors_dev(flashe_ctx *ctx, uint64_t n, const flashe_tensor_layer *layers, int n_layers, int element_bits,
+                                                      const double *u_dev, uint64_t *packed_dev);
+int flashe_unpack_decrypt_prepared_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add, const uint32_t *minus_idx,
+                                                        int n_minus, uint64_t n, uint32_t n_jobs, const uint64_t *packed_dev,
+                                                        const flashe_codec_layer *layers, int n_layers, int element_bits, int num_clients,
+                                                        double *out_dev);
+int flashe_quantize_batch_encrypt_prepared_pack_model_dev(flashe_ctx *ctx, const flashe_batch_layer *layers, int n_layers, int element_bits,
+                                                          int field_bits, const double *u_dev, uint64_t n_elems, uint64_t *packed_dev);
+int flashe_quantize_batch_encrypt_prepared_pack_tensors_dev(flashe_ctx *ctx, const flashe_tensor_layer *layers, int n_layers, uint64_t n_values,
+                                                            int element_bits, int field_bits, const double *u_dev, uint64_t n_elems,
+                                                            uint64_t *packed_dev);
+int flashe_unpack_decrypt_prepared_unbatch_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, const uint32_t *add_idx, int n_add,
+                                                                const uint32_t *minus_idx, int n_minus, uint32_t n_jobs,
+                                                                const flashe_batch_layer *layers, int n_layers, int element_bits, int field_bits,
+                                                                int num_clients, const uint64_t *packed_dev, uint64_t n_elems, double *out_dev);
 
 /* np.random.random(n) ON THE DEVICE, bit for bit (new): the stochastic-rounding draws of _static_quantize_padding_asymmetric
  * (jzf_quantize.py:61, `np.random.random(value.shape)`) come from NumPy's global MT19937 generator; this writes the same n doubles
