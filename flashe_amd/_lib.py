@@ -273,6 +273,8 @@ _SIGNATURES = {
                                                            c_int, c_int, c_int, c_vp]),
     "flashe_unpack_decrypt_lists_unquantize_model_dev": (c_int, [c_vp, c_u32, c_u32p, c_int, c_u32p, c_int, c_u64, c_u32, c_vp, ctypes.POINTER(CodecLayer),
                                                                  c_int, c_int, c_int, c_vp]),
+    "flashe_unpack_sparse_decrypt_unquantize_model_dev": (c_int, [c_vp, c_u32, c_int, ctypes.POINTER(c_vp), c_u64p, c_u64, c_u32, c_vp, c_vp,
+                                                                  ctypes.POINTER(CodecLayer), c_int, c_int, c_int, c_vp]),
     "flashe_quantize_batch_tensors_dev": (c_int, [c_vp, ctypes.POINTER(TensorLayer), c_int, c_u64, c_int, c_int, c_vp, c_u64, c_vp]),
     "flashe_quantize_batch_encrypt_pack_model_dev": (c_int, [c_vp, c_u32, c_u32, c_int, ctypes.POINTER(BatchLayer), c_int, c_int, c_int, c_vp, c_u64, c_vp]),
     "flashe_quantize_batch_encrypt_pack_tensors_dev": (c_int, [c_vp, c_u32, c_u32, c_int, ctypes.POINTER(TensorLayer), c_int, c_u64, c_int, c_int, c_vp, c_u64,

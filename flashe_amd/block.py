@@ -45,6 +45,17 @@ _WIDE_WIRE_BACK_MIN_ELEMS = 1_666_668
 _WIRE_LISTS_MIN_ELEMS, _WIRE_LISTS_MAX_PREFIXES = 25_557_032, 10
 _WIDE_WIRE_LISTS_MIN_ELEMS, _WIDE_WIRE_LISTS_MAX_PREFIXES = 1_666_668, 4
 
+# decrypt_unquantize takes the SPARSE job's packed sum (single mask, un-batched, int_bits 16 .. 64, at most 64 clients) to the floats in one
+# launch (the span reduce with the PRF inside reading the packed limbs and storing the unquantised float64: stream.hip,
+# span_prf_small_wire_kernel) only under this switch.  The launch moves int_bits / 8 + 8 bytes per dense position against the 40 +
+# int_bits / 8 of unpack_dev + sparse_decrypt_dev + unquantize_model_dev (10.5 against 42.5 at int_bits 20), counted from the code.
+# Measured against that sequence in two processes the fused median leads everywhere (x 1.26 - 1.50) and wins by more than either form's spread in
+# both at 25,557,032 positions with 50 clients at 1 % and at 1e7 positions with 10 clients at 10 %, int_bits 20 and 64; at 25,557,032 positions
+# with 10 clients at 10 % one fused sample of 0.58 - 0.59 ms turns one process at each width.  The class that loses lies between two that win and
+# nothing was measured between the three shapes, so no threshold was fitted: the ROUTING is unmeasured and stays opt-in.
+# profiles/r43_wire_sparse_back.log
+_WIRE_SPARSE_BACK = False
+
 __all__ = ["dynamic_masking_choice", "FlasheClient", "FlasheCohort", "CohortPlan", "CohortUpload", "plan_cohort", "FlasheSparseCohort",
            "SparseCohortPlan", "SparseCohortEncoding", "SparseCohortUpload", "plan_sparse_cohort"]
 
@@ -1050,11 +1061,29 @@ class FlasheClient(object):
 
     def _sparse_floats(self, v, sizes, keep):
         """The sparse job's back end: the minus-mask pass over the aggregate v (result in HBM, appended to keep), then the unquantise of
-        the dense model in a second launch.  Returns (the n float64 values as a device buffer, n)."""
+        the dense model in a second launch.  Returns (the n float64 values as a device buffer, n).  Under _WIRE_SPARSE_BACK a PackedVector
+        of the cipher's width whose minus-mask is still a promise for this iter (strictly increasing lists) goes to the floats in ONE
+        launch (flashe_unpack_sparse_decrypt_unquantize_model_dev); declined -- another width, more than 64 clients -- it is unpacked for
+        the sequence above.  The sparse + double mask, batched sparse jobs, int_bits > 64 and the way out (the 'zzz' upload) stay staged."""
+        from . import cipher as _cipher_mod
+        from .cipher import _SparseMinus
         from .engine import PackedVector
         q, c = self.quantizer, self.cipher
         eng = c.engine
         if isinstance(v, PackedVector):
+            minus = c.next_iter_decrypt_prepared.get('minus')
+            if (_WIRE_SPARSE_BACK and v.bits == self.int_bits and len(v) and isinstance(minus, _SparseMinus) and not minus.materialized
+                    and minus.sorted_lists and minus.it == c.iter_index and hasattr(eng, "unpack_sparse_decrypt_unquantize_model_dev")):
+                n = len(v)
+                c._check_prepared_len(minus, n)
+                table = self._back_table(sizes, n)
+                dout = eng.alloc(max(8 * n, 16))
+                v.wait_on(eng)
+                if eng.unpack_sparse_decrypt_unquantize_model_dev(minus.it, minus.dloc, minus.ks, n, _cipher_mod.N_JOBS, v.buf, table, q.element_bits,
+                                                                  q.num_clients, dout, bounds=minus.bounds):
+                    eng.hold([v])
+                    del c.next_iter_decrypt_prepared['minus']         # (consumed as cipher.decrypt consumes it)
+                    return dout, n
             v = self._unpacked(v)
         dec = c._as_wide(c.decrypt(v, device=True))
         n = len(dec)

@@ -2174,6 +2174,30 @@ int flashe_sparse_decrypt_bounds_dev(flashe_ctx *ctx, uint32_t iter, int C, cons
     return sparse_minus_mask_impl(ctx, iter, C, loc_dev, k, total, n_jobs, true, agg_dev, out_dev, bounds);
 }
 
+// What flashe_unpack_sparse_decrypt_unquantize_model_dev (abi_layers.hip) shares with the decrypt above: the lists checked as
+// sparse_minus_mask_impl checks them, and *start = the bounds of one group of C <= kMaxScatter strictly increasing lists at kSpanFused --
+// the handle's table once it is known to describe exactly these lists, or ctx->bounds computed on the stream.
+extern "C++" int flashe_host::sparse_fused_bounds(flashe_ctx *ctx, const flashe_span_bounds *bounds, uint64_t total, int C, const uint32_t *const *loc_dev,
+                                     const uint64_t *k, const uint32_t **start)
+{
+    if (C < 1 || C > kMaxScatter || !loc_dev || !k) return fail(ctx, FLASHE_EINVAL, "bad arguments");
+    if (int rc = check_bounds(ctx, bounds, total, C, loc_dev, k)) return rc;
+    for (int c = 0; c < C; c++) {
+        if (k[c] > total) return fail(ctx, FLASHE_EINVAL, "client %d: more locations (%llu) than positions (%llu)", c,
+                                      static_cast<unsigned long long>(k[c]), static_cast<unsigned long long>(total));
+        if (k[c] && !loc_dev[c]) return fail(ctx, FLASHE_EINVAL, "client %d: null list", c);
+    }
+    if (bounds) {
+        if (!bounds->start_fused) return fail(ctx, FLASHE_EINVAL, "the span bounds were computed by a ctx of another int_bits / PRF backend");
+        *start = bounds->start_fused;
+        return FLASHE_OK;
+    }
+    if (int rc = ensure(ctx, ctx->bounds, span_table_words(total, C) * sizeof(uint32_t))) return rc;
+    HIP_TRY(ctx, launch_span_bounds(ctx->env, C, loc_dev, k, total, nullptr, static_cast<uint32_t *>(ctx->bounds.p)));
+    *start = static_cast<const uint32_t *>(ctx->bounds.p);
+    return FLASHE_OK;
+}
+
 int flashe_sparse_decrypt_range_dev(flashe_ctx *ctx, uint32_t iter, int C, const uint32_t *const *loc_dev, const uint64_t *k, uint64_t total,
                                     uint32_t n_jobs, const flashe_span_bounds *bounds, uint64_t first, uint64_t count, const uint64_t *agg_dev,
                                     uint64_t *out_dev)

@@ -586,6 +586,28 @@ int flashe_unpack_decrypt_lists_unquantize_model_dev(flashe_ctx *ctx, uint32_t i
                                            packed_dev, layers, n_layers, element_bits, num_clients, out_dev);
 }
 
+// The sparse job's way back: the span reduce with the PRF inside, from the packed sum to the floats (stream.hip, span_prf_small_wire_kernel)
+int flashe_unpack_sparse_decrypt_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, int C, const uint32_t *const *loc_dev, const uint64_t *k, uint64_t total,
+                                                      uint32_t n_jobs, const flashe_span_bounds *bounds, const uint64_t *packed_dev,
+                                                      const flashe_codec_layer *layers, int n_layers, int element_bits, int num_clients, double *out_dev)
+{
+    CHECK_CTX(ctx);
+    if (!span_wire_admits(ctx->env, C, total, n_jobs))
+        return fail(ctx, FLASHE_ENOTSUP, "flashe_unpack_sparse_decrypt_unquantize_model_dev: needs 16 <= int_bits <= 64, the table PRF, 1 <= C <= %d, "
+                                         "1 <= total < 2^32 and n_jobs >= 1 (run the three calls it fuses)", kMaxScatter);
+    if (!packed_dev || !out_dev) return fail(ctx, FLASHE_EINVAL, "null vector");
+    if (num_clients < 1) return fail(ctx, FLASHE_EINVAL, "num_clients must be >= 1");
+    int rc = check_codec_bits(ctx, element_bits);
+    if (rc || (rc = check_aligned(ctx, {packed_dev, out_dev}, 8))) return rc;
+    const uint32_t *start = nullptr;
+    Codec cq{};
+    if ((rc = stage_codec_layers(ctx, total, layers, n_layers, false, element_bits, num_clients, 0, total, nullptr, out_dev, &cq)) ||
+        (rc = sparse_fused_bounds(ctx, bounds, total, C, loc_dev, k, &start)))
+        return rc;
+    HIP_TRY(ctx, launch_span_prf_small_unpack(ctx->env, iter, n_jobs, C, loc_dev, k, total, start, packed_dev, cq));
+    return FLASHE_OK;
+}
+
 // what every chained cohort asks of its arguments before its cipher indices
 static int cohort_check_args(flashe_ctx *ctx, const char *who, int n_clients, uint64_t n, const flashe_tensor_layer *layers, int n_layers,
                              const void *const *src_dev, bool outs, int element_bits, const double *u_dev)

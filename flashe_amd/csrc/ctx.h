@@ -87,6 +87,10 @@ int check_prf_args(flashe_ctx *ctx, int n_add, int n_minus, uint32_t n_jobs, con
 hipError_t prf_lists(flashe_ctx *ctx, uint32_t iter, const uint32_t *add, int n_add, const uint32_t *minus, int n_minus, uint64_t n, uint32_t n_jobs,
                      uint64_t first, uint64_t count, const uint64_t *in_dev, int in_limbs, uint64_t *out_dev);
 
+// the checked lists of a sparse pass with the PRF inside and their span bounds, from the handle or computed on the stream (abi.hip)
+int sparse_fused_bounds(flashe_ctx *ctx, const flashe_span_bounds *bounds, uint64_t total, int C, const uint32_t *const *loc_dev, const uint64_t *k,
+                        const uint32_t **start);
+
 // RAII temp device buffer for the host-pointer twins.  Staging blocks are kept by the ctx and reused: a hipMalloc + hipFree
 // pair of a 160 MB block costs more than moving 160 MB over PCIe Gen5 on this platform (measured 7 ms against 2.9 ms,
 // tests/perf/e2e_calls.py).  The blocks a ctx keeps are bounded by a byte budget (FLASHE_STAGING_POOL_MB, default 8 GiB of the

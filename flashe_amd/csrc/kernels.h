@@ -369,6 +369,14 @@ hipError_t launch_span_bounds(const LaunchEnv &env, int C, const uint32_t *const
 hipError_t launch_span_prf(const LaunchEnv &env, uint32_t iter, uint32_t n_jobs, int C, const uint32_t *idx, const uint32_t *const *loc_dev, const uint64_t *k,
                            const uint64_t *const *pt_dev, int pt_limbs, uint64_t *const *ct_dev, const uint64_t *sub, uint64_t base_lo, uint64_t base_hi,
                            uint64_t total, const uint32_t *start_dev, const uint64_t *src_dev, bool negate, uint64_t *out_dev, uint64_t first, uint64_t count);
+// The sparse single-mask decrypt straight from the packed wire sum to the floats (stream.hip, span_prf_small_wire_kernel): the decrypt
+// form of launch_span_prf over the whole vector (client c's prefix = c) reading position p from the packed integer (element j of n at bit
+// (n - 1 - j) b) and storing cq.fout[p] = unquantise(position p - its masks) with cq's back-end layer table (k0 = 0): ONE launch.
+// span_wire_admits: 16 <= int_bits <= 64, the table PRF, 1 <= C <= kMaxScatter, 1 <= total < 2^32, n_jobs != 0.
+// hipErrorNotSupported: nothing launched.
+bool span_wire_admits(const LaunchEnv &env, int C, uint64_t total, uint32_t n_jobs);
+hipError_t launch_span_prf_small_unpack(const LaunchEnv &env, uint32_t iter, uint32_t n_jobs, int C, const uint32_t *const *loc_dev, const uint64_t *k,
+                                        uint64_t total, const uint32_t *start_dev, const uint64_t *packed_dev, const Codec &cq);
 #ifdef FLASHE_TUNING
 hipError_t span_prf_cycles(unsigned long long *out8, bool reset);      // phase cycle sums of span_prf_kernel's workgroup 0 (FLASHE_SPAN_PROBE=9)
 #endif

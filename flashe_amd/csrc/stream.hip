@@ -2,6 +2,7 @@
 // and packed reduces with their multi-GPU slice helpers, the bit-packing codec, and the sparse passes (span bounds / span reduce,
 // scatter, run-edge masks, shared positions).  The AES core they need comes from device_common.h.
 #include "device_common.h"
+#include "wire_tiles.h"
 
 namespace flashe {
 
@@ -1853,14 +1854,32 @@ __device__ __forceinline__ uint32_t small_block_of(const uint4 g, uint32_t q, ui
 
 constexpr int kSmallBatch = 8;       // entries of a block whose position / plaintext loads are in flight at once (the first batch under the rounds)
 
-template <bool ENC, bool SRC>
-__global__ __launch_bounds__(kPrfThreads) void span_prf_small_kernel(const RoundKeys rk, const SpanSmallTable tb, int C, uint32_t iter0, uint32_t n_jobs,
-                                                                     uint32_t b, uint64_t total, uint32_t n_spans, uint32_t sp_first, uint32_t sp_end,
-                                                                     const uint32_t *__restrict__ start, uint64_t base, uint64_t mask, const uint64_t *src,
-                                                                     bool negate, uint64_t *out, const uint32_t *__restrict__ te0, uint32_t *err_flag)
+// The decrypt straight from the packed WIRE sum to the floats (span_prf_small_wire_kernel: WIRE, with ENC false and SRC true) changes
+// what enters and what leaves a span, nothing between:
+//   entering: from[] is not read from a uint64 vector but cut out of the packed integer (wire.hip's contract: position p of `total` at
+//   bits [b (total - 1 - p), b (total - p)) of little-endian limbs) -- the lane requests the one or two limbs its field overlaps where
+//   from[] is requested, ahead of the span's rounds, and funnel-shifts them at the write-out.  Lanes of ascending position read
+//   descending, neighbouring or equal limbs: b / 8 bytes per position from HBM.  A second limb is asked for only when the field crosses
+//   into it, so no load reaches past the limb that holds the integer's top bit b total - 1 (a span of kSpanFused b bits starts mid-limb
+//   at most widths; a run of limbs staged in LDS would have to fit beside 148.7 KiB and was not tried);
+//   leaving: the position's unquantised float64 -- codec_unquantize's arithmetic with the back-end table of the model's layers -- in
+//   place of the masked uint64.  Wave 0 finds the layer that holds the span's first position beside the span table; a span inside that
+//   layer (nearly every one) takes the parameters from SGPRs, the others step from it per lane (a layer may be one position long).
+struct SpanWire {
+    const uint64_t *packed;          // ceil(total b / 64) limbs, the unused top bits of the last one zero
+    const CodecLayer *layers;        // back-end rows, starts strictly ascending from 0, the last one running to `total`
+    int n_layers;
+    double *fout;                    // total float64 values
+};
+
+template <bool ENC, bool SRC, bool WIRE>
+__device__ __forceinline__ void span_prf_small_body(const RoundKeys &rk, const SpanSmallTable &tb, int C, uint32_t iter, uint32_t n_jobs, uint32_t b,
+                                                    uint64_t total, uint32_t n_spans, uint32_t sp_first, uint32_t sp_end, const uint32_t *__restrict__ start,
+                                                    uint64_t base, uint64_t mask, const uint64_t *src, bool negate, uint64_t *out,
+                                                    const uint32_t *__restrict__ te0, uint32_t *err_flag, const SpanWire &ww)
 {
+    static_assert(!WIRE || (!ENC && SRC), "the wire form is a decrypt of a given sum");
     constexpr int SPAN = kSpanFused, THREADS = kPrfThreads, PER = (SPAN + THREADS - 1) / THREADS;
-    const uint32_t iter = iter0 + te0[kIterShiftWord];
     const uint32_t m = 128u / b;
     __shared__ uint32_t tab[kTabWords];
     __shared__ unsigned long long acc[SPAN];
@@ -1873,6 +1892,7 @@ __global__ __launch_bounds__(kPrfThreads) void span_prf_small_kernel(const Round
     // the span in flight: client c's entries [s_f0[c], s_f1[c]) lie in it and touch its blocks s_g0[c] ..; work items s_w[c] .. s_w[c + 1]
     // are client c's (s_w[C] = the span's blocks; the entries past C are sentinels, so the owner search needs no bounds)
     __shared__ uint32_t s_w[kMaxScatter + 1], s_f0[kMaxScatter], s_f1[kMaxScatter], s_g0[kMaxScatter];
+    __shared__ int s_row;                                     // WIRE: the table row that holds the first position of the span in flight
     fill_tables(tab, te0);
     const LaneRegs lr = lane_regs(tab);
     const int tid = threadIdx.x;
@@ -1902,6 +1922,7 @@ __global__ __launch_bounds__(kPrfThreads) void span_prf_small_kernel(const Round
         if (tid == 0) s_w[0] = 0;
         if (tid < C) { s_f0[tid] = f0; s_f1[tid] = f1; s_g0[tid] = g0; }
         s_w[tid + 1] = tid < C ? run : 0xffffffffu;
+        if (WIRE && tid == 0) s_row = wire_row_of(ww.layers, ww.n_layers, sp * SPAN);
     };
     uint64_t sp = static_cast<uint64_t>(sp_first) + blockIdx.x;
     const uint32_t stride = gridDim.x;
@@ -1911,11 +1932,32 @@ __global__ __launch_bounds__(kPrfThreads) void span_prf_small_kernel(const Round
         const uint64_t p0 = sp * SPAN;
         const uint32_t span_len = static_cast<uint32_t>(total - p0 < SPAN ? total - p0 : SPAN);
         // the dense values this lane writes out at the end of the span, requested ahead of the span's rounds
-        uint64_t from[PER];
+        uint64_t from[PER], from_hi[WIRE ? PER : 1];
 #pragma unroll
         for (int e = 0; e < PER; e++) {
             const uint32_t r = tid + e * THREADS;
-            from[e] = SRC && r < span_len ? __builtin_nontemporal_load(src + p0 + r) : base;
+            if constexpr (WIRE) {
+                from[e] = 0; from_hi[e] = 0;
+                if (r < span_len) {
+                    const uint64_t pos = static_cast<uint64_t>(b) * (total - 1 - (p0 + r));          // the field's lowest bit; its top bit is below b total
+                    const uint64_t *limb = ww.packed + (pos >> 6);
+                    from[e] = __builtin_nontemporal_load(limb);
+                    if ((static_cast<uint32_t>(pos) & 63u) + b > 64u) from_hi[e] = __builtin_nontemporal_load(limb + 1);
+                }
+            } else {
+                from[e] = SRC && r < span_len ? __builtin_nontemporal_load(src + p0 + r) : base;
+            }
+        }
+        // WIRE: the row of the span's first position (read before the barrier behind which wave 0 replaces it) and, when the whole span
+        // lies in that row, its parameters in SGPRs
+        int row0 = 0;
+        bool one_row = false;
+        double q0 = 0, q1 = 0, q2 = 0;
+        if constexpr (WIRE) {
+            row0 = __builtin_amdgcn_readfirstlane(s_row);
+            const CodecLayer *L = ww.layers + row0;
+            one_row = row0 + 1 >= ww.n_layers || p0 + span_len <= *FLASHE_CONSTANT(const uint64_t, &L[1].start);
+            q0 = *FLASHE_CONSTANT(const double, &L->p0); q1 = *FLASHE_CONSTANT(const double, &L->p1); q2 = *FLASHE_CONSTANT(const double, &L->p2);
         }
         const uint32_t n_work = s_w[C];
         for (uint32_t w = tid; w < n_work; w += THREADS) {
@@ -1974,19 +2016,60 @@ __global__ __launch_bounds__(kPrfThreads) void span_prf_small_kernel(const Round
             }
         }
         __syncthreads();                                                           // every entry of the span is in
+        int row = row0;
 #pragma unroll
         for (int e = 0; e < PER; e++) {
             const uint32_t r = tid + e * THREADS;
             if (r < span_len) {
                 const uint64_t v = acc[r];
                 acc[r] = 0;
-                __builtin_nontemporal_store((negate ? from[e] - v : from[e] + v) & mask, out + p0 + r);
+                if constexpr (WIRE) {
+#pragma clang fp contract(off)
+                    const uint32_t sh = (b * static_cast<uint32_t>(total - 1 - (p0 + r))) & 63u;       // (pos mod 64 needs the low word only)
+                    uint64_t f = from[e] >> sh;
+                    if (sh) f |= from_hi[e] << (64u - sh);                      // (zero unless the field crosses into the next limb)
+                    const double x = static_cast<double>((f - v) & mask);
+                    double p_0 = q0, p_1 = q1, p_2 = q2;
+                    if (!one_row) {
+                        while (row + 1 < ww.n_layers && ww.layers[row + 1].start <= p0 + r) row++;
+                        const CodecLayer *L = ww.layers + row;
+                        p_0 = L->p0; p_1 = L->p1; p_2 = L->p2;
+                    }
+                    __builtin_nontemporal_store(x * p_1 / p_2 - p_0, ww.fout + p0 + r);             // codec_unquantize's arithmetic
+                } else {
+                    __builtin_nontemporal_store((negate ? from[e] - v : from[e] + v) & mask, out + p0 + r);
+                }
             }
         }
         // (the span table was last read before the barrier above)
         if (tid < 64 && sp + stride < sp_end) span_table(sp + stride);
         __syncthreads();
     }
+}
+
+template <bool ENC, bool SRC>
+__global__ __launch_bounds__(kPrfThreads) void span_prf_small_kernel(const RoundKeys rk, const SpanSmallTable tb, int C, uint32_t iter0, uint32_t n_jobs,
+                                                                     uint32_t b, uint64_t total, uint32_t n_spans, uint32_t sp_first, uint32_t sp_end,
+                                                                     const uint32_t *__restrict__ start, uint64_t base, uint64_t mask, const uint64_t *src,
+                                                                     bool negate, uint64_t *out, const uint32_t *__restrict__ te0, uint32_t *err_flag)
+{
+    span_prf_small_body<ENC, SRC, false>(rk, tb, C, iter0 + te0[kIterShiftWord], n_jobs, b, total, n_spans, sp_first, sp_end, start, base, mask, src, negate, out, te0, err_flag,
+                                         SpanWire{});
+}
+
+// fout[p] = unquantise((position p of the packed sum - the sum of the masks at p) mod 2^b) for every p < total
+__global__ __launch_bounds__(kPrfThreads) void span_prf_small_wire_kernel(const RoundKeys rk, const SpanSmallTable tb, int C, uint32_t iter0, uint32_t n_jobs,
+                                                                            uint32_t b, uint64_t total, uint32_t n_spans, const uint32_t *__restrict__ start,
+                                                                            uint64_t mask, const SpanWire ww, const uint32_t *__restrict__ te0,
+                                                                            uint32_t *err_flag)
+{
+    span_prf_small_body<false, true, true>(rk, tb, C, iter0 + te0[kIterShiftWord], n_jobs, b, total, n_spans, 0u, n_spans, start, 0, mask, nullptr, true, nullptr, te0, err_flag, ww);
+}
+
+bool span_wire_admits(const LaunchEnv &env, int C, uint64_t total, uint32_t n_jobs)
+{
+    return env.b >= 16 && env.b <= 64 && (env.prf_backend == PRF_AUTO || env.prf_backend == PRF_TABLE) && C >= 1 && C <= kMaxScatter && total >= 1 &&
+           total < (1ull << 32) && n_jobs >= 1;
 }
 
 // launch_span_prf at int_bits <= 64 (the arguments checked there, src_dev / out_dev already moved back to position 0)
@@ -2010,6 +2093,27 @@ static hipError_t launch_span_prf_small(const LaunchEnv &env, uint32_t iter, uin
     if (!pt_dev) { if (src_dev) SPAN_PRF_SMALL_LAUNCH(false, true); else SPAN_PRF_SMALL_LAUNCH(false, false); }
     else { if (src_dev) SPAN_PRF_SMALL_LAUNCH(true, true); else SPAN_PRF_SMALL_LAUNCH(true, false); }
 #undef SPAN_PRF_SMALL_LAUNCH
+    return hipGetLastError();
+}
+
+// The sparse single-mask decrypt of the packed wire sum straight to the floats: cq.fout[p] = unquantise((position p of packed_dev - sum of
+// the masks of the list entries at p) mod 2^b), p < total, client c's prefix = c; cq: a back-end layer table, k0 = 0; start_dev: the
+// bounds of exactly these lists at kSpanFused.  hipErrorNotSupported: nothing launched.
+hipError_t launch_span_prf_small_unpack(const LaunchEnv &env, uint32_t iter, uint32_t n_jobs, int C, const uint32_t *const *loc_dev, const uint64_t *k,
+                                        uint64_t total, const uint32_t *start_dev, const uint64_t *packed_dev, const Codec &cq)
+{
+    if (!span_wire_admits(env, C, total, n_jobs) || !cq.layers || !cq.fout || cq.k0) return hipErrorNotSupported;
+    SpanSmallTable tb{};
+    for (int c = 0; c < C; c++) {
+        if (k[c] >= (1ull << 32)) return hipErrorInvalidValue;
+        tb.loc[c] = loc_dev[c]; tb.k[c] = static_cast<uint32_t>(k[c]); tb.idx[c] = static_cast<uint32_t>(c);
+    }
+    uint64_t lo, hi;
+    masks_of(env.b, &lo, &hi);
+    const uint64_t n_spans = span_count(total, kSpanFused);
+    const dim3 grid(static_cast<unsigned>(std::min<uint64_t>(n_spans, static_cast<uint64_t>(std::max(env.num_cus, 1)))));
+    hipLaunchKernelGGL(span_prf_small_wire_kernel, grid, dim3(kPrfThreads), 0, env.stream, env.rk, tb, C, iter, n_jobs, static_cast<uint32_t>(env.b), total,
+                       static_cast<uint32_t>(n_spans), start_dev, lo, SpanWire{packed_dev, cq.layers, cq.n_layers, cq.fout}, env.te0_dev, env.err_flag);
     return hipGetLastError();
 }
 

@@ -784,6 +784,18 @@ class Engine:
         return Engine.unpack_decrypt_unquantize_model_dev(self, it, add_idx, minus_idx, n, n_jobs, packed, layers, element_bits, num_clients, out,
                                                           fn="flashe_unpack_decrypt_lists_unquantize_model_dev")
 
+    def unpack_sparse_decrypt_unquantize_model_dev(self, it, locs, ks, total, n_jobs, packed, layers, element_bits, num_clients, out, bounds=None):
+        """unpack_dev + sparse_decrypt_dev (strictly increasing lists, client c's prefix = c) + unquantize_model_dev over the whole vector in
+        ONE launch (flashe_unpack_sparse_decrypt_unquantize_model_dev); bounds: a SpanBounds of exactly these lists, else they are computed
+        first.  False -- nothing was launched -- when the library declines (another width or PRF backend, more than 64 clients), True
+        otherwise."""
+        p, _keep = self._ptr_array(locs)
+        k = _u64_array(ks)
+        arr, nl = self._codec_layers(layers)
+        return self._took(self._lib.flashe_unpack_sparse_decrypt_unquantize_model_dev(self._h, it, len(locs), p, ctypes.cast(k, c_u64p), total, n_jobs,
+                                                                                      bounds._h if bounds is not None else None, self._ptr(packed), arr, nl,
+                                                                                      element_bits, num_clients, self._ptr(out)))
+
     def quantize_batch_encrypt_pack_model_dev(self, it, idx, scheme, layers, element_bits, field_bits, u, n_elems, packed):
         """quantize_batch_model_dev + encrypt_dev + pack_dev of a batched job at int_bits 65 .. 128 in ONE launch
         (flashe_quantize_batch_encrypt_pack_model_dev): packed = ceil(n_elems int_bits / 64) limbs, every one written.  False -- nothing

@@ -749,6 +749,21 @@ int flashe_unpack_decrypt_lists_unquantize_model_dev(flashe_ctx *ctx, uint32_t i
                                                      const uint32_t *minus_idx, int n_minus, uint64_t n, uint32_t n_jobs,
                                                      const uint64_t *packed_dev, const flashe_codec_layer *layers, int n_layers,
                                                      int element_bits, int num_clients, double *out_dev);
+/* The SPARSE job's way back (new; jzf_flashe.py:316-343, 531-532 then jzf_aggregator.py:652-671 / :887-899): what flashe_unpack_dev,
+ * flashe_sparse_decrypt_bounds_dev (flashe_sparse_decrypt_dev with sorted = 1 when bounds is NULL) and flashe_unquantize_model_dev over
+ * the whole vector compute, bit for bit, in ONE launch -- the span reduce with the PRF inside reads each position out of the packed sum
+ * and stores its unquantised float64; neither uint64 element vector exists.  loc_dev / k: the C clients' STRICTLY INCREASING location
+ * lists, client c masked with prefix c (a list that is not strictly increasing is reported as the sparse passes report it: its offending
+ * entries are skipped and the next synchronising call fails with FLASHE_EINVAL).  packed_dev: ceil(total int_bits / 64) limbs as above (read only); out_dev: total float64 values.
+ * bounds: a handle of exactly these lists, or NULL -- the bounds are then computed on the stream first, in ctx scratch.
+ * FLASHE_ENOTSUP -- checked first, nothing launched, staged or written -- unless 16 <= int_bits <= 64, the PRF backend is the table one,
+ * 1 <= C <= 64, 1 <= total < 2^32 and n_jobs >= 1 (more clients take two passes, the second over the first one's output: run the three
+ * calls); FLASHE_EINVAL as flashe_sparse_decrypt_bounds_dev (a handle made for other lists included) and flashe_unquantize_model_dev.
+ * Not capturable: the layer table is staged per call, as by every model-wide codec call. */
+int flashe_unpack_sparse_decrypt_unquantize_model_dev(flashe_ctx *ctx, uint32_t iter, int C, const uint32_t *const *loc_dev, const uint64_t *k,
+                                                      uint64_t total, uint32_t n_jobs, const flashe_span_bounds *bounds,
+                                                      const uint64_t *packed_dev, const flashe_codec_layer *layers, int n_layers,
+                                                      int element_bits, int num_clients, double *out_dev);
 /* The BATCHED client step straight to the packed wire form at int_bits 65 .. 128 (new; jzf_quantize.py:162-185, 436-451 then
  * jzf_flashe.py:431-594 then jzf_weights.py:155-231): what flashe_quantize_batch_model_dev, flashe_encrypt_dev (cipher index idx, `scheme`)
  * over the n_elems batched elements and flashe_pack_dev compute, bit for bit, in ONE launch -- neither the batched plaintext nor the
