@@ -188,6 +188,7 @@ _SIGNATURES = {
     "flashe_span_bounds_create": (c_int, [c_vp, c_u64, c_int, ctypes.POINTER(c_vp), c_u64p, ctypes.POINTER(c_vp)]),
     "flashe_span_bounds_recompute": (c_int, [c_vp, c_vp, ctypes.POINTER(c_vp), c_u64p]),
     "flashe_span_bounds_destroy": (None, [c_vp]),
+    "flashe_sparse_aggregate_packed_dev": (c_int, [c_vp, c_u64, c_int, ctypes.POINTER(c_vp), c_u64p, ctypes.POINTER(c_vp), c_vp, c_vp]),
     "flashe_sparse_aggregate_bounds_dev": (c_int, [c_vp, c_u64, c_int, ctypes.POINTER(c_vp), c_u64p, ctypes.POINTER(c_vp), c_u64p, c_vp, c_vp]),
     "flashe_sparse_decrypt_bounds_dev": (c_int, [c_vp, c_u32, c_int, ctypes.POINTER(c_vp), c_u64p, c_u64, c_u32, c_vp, c_vp, c_vp]),
     "flashe_sparse_encrypt_aggregate_dev": (c_int, [c_vp, c_u32, c_u32, c_u64, c_int, c_u32p, ctypes.POINTER(c_vp), c_u64p, ctypes.POINTER(c_vp), c_int,

@@ -56,6 +56,16 @@ _WIDE_WIRE_LISTS_MIN_ELEMS, _WIDE_WIRE_LISTS_MAX_PREFIXES = 1_666_668, 4
 # profiles/r43_wire_sparse_back.log
 _WIRE_SPARSE_BACK = False
 
+# aggregate_sparse_uploads takes PackedVector uploads (int_bits 16 .. 64, at most 64 clients, strictly increasing lists) to the packed dense
+# sum in one launch (stream.hip, span_reduce_wire_kernel) under this switch; without it, and where the launch declines, it unpacks every
+# upload, runs the span reduce and packs the sum.  The launch moves int_bits / 8 + 4 bytes per list entry and int_bits / 8 per dense
+# position against the staged int_bits / 8 + 20 and 16 + int_bits / 8 (about 150 MB against 760 MB at int_bits 20, 25,557,032 positions,
+# 50 clients at 1 %), counted from the code, in C + 1 launches fewer and without the C synchronous downloads of the zeros.  Measured against
+# the staged launches (the downloads not counted) in two processes it wins by more than either form's spread in both at every class:
+# 25,557,032 positions with 50 clients at 1 % and with 10 clients at 10 %, 1e7 positions with 10 clients at 10 %, int_bits 20 and 64
+# (x 2.54 - 3.60), so it is the default.  profiles/r44_wire_sparse_agg.log
+_WIRE_SPARSE_AGG = True
+
 __all__ = ["dynamic_masking_choice", "FlasheClient", "FlasheCohort", "CohortPlan", "CohortUpload", "plan_cohort", "FlasheSparseCohort",
            "SparseCohortPlan", "SparseCohortEncoding", "SparseCohortUpload", "plan_sparse_cohort"]
 
@@ -95,11 +105,18 @@ def aggregate_sparse_uploads(engine, uploads, locations, total, device=True):
       uploads   per client: a DeviceVector of k + 1 elements as FlasheClient.quantize_encrypt leaves it (it stays where it is), uint64 limbs
                 [k + 1, L] or object ints [k + 1]
       locations per client: k sorted positions (host integers, or a device buffer of uint32)
-    Returns the dense aggregate of `total` elements: a DeviceVector (device=True) or uint64 limbs [total, L]."""
-    from .engine import DeviceBuffer, DeviceVector
+    Returns the dense aggregate of `total` elements: a DeviceVector (device=True) or uint64 limbs [total, L].
+    uploads that are ALL PackedVectors (new: the wire form quantize_encrypt(packed=True) returns, k + 1 fields of the engine's int_bits
+    each) give the sum in its wire form too -- a PackedVector of `total` fields or, device=False, its Python int
+    (_aggregate_packed_uploads); a mix of PackedVectors and other operands raises TypeError."""
+    from .engine import DeviceVector, PackedVector
+    if any(isinstance(up, PackedVector) for up in uploads):
+        if not all(isinstance(up, PackedVector) for up in uploads):
+            raise TypeError("PackedVector uploads: all of them")
+        return _aggregate_packed_uploads(engine, list(uploads), list(locations), int(total), device)
     lim = engine.limbs
-    vals, zeros, ks, locs, sorted_all = [], [], [], [], True
-    for up, loc in zip(uploads, locations):
+    vals, zeros, ks = [], [], []
+    for up in uploads:
         if isinstance(up, DeviceVector):
             dv = up.widened(engine) if up.compact else up
             k = len(dv) - 1
@@ -117,18 +134,61 @@ def aggregate_sparse_uploads(engine, uploads, locations, total, device=True):
             vals.append(engine.upload(a[:k]) if k else engine.alloc(16))
         zeros.append([int(v) for v in z])
         ks.append(k)
-        if isinstance(loc, DeviceBuffer):
-            locs.append(loc)
-        else:
-            la = np.asarray(loc, dtype=np.int64).reshape(-1)
-            if la.size != k:
-                raise ValueError(f"{la.size} locations for an upload of {k} values")
-            sorted_all = sorted_all and bool(np.all(la[1:] > la[:-1]))
-            locs.append(engine.upload(la.astype(np.uint32)) if k else engine.alloc(16))
+    locs, sorted_all = _device_locations(engine, locations, ks)
     out = DeviceVector(engine, int(total))
     if total:
         engine.sparse_aggregate_dev(int(total), locs, ks, vals, zeros, out.buf, sorted_lists=sorted_all)
     return out.mark_ready() if device else out.to_host()
+
+
+def _device_locations(engine, locations, ks):
+    """The clients' location lists on the device and whether every one is known to be strictly increasing: a device buffer is taken as it
+    is (sorted by contract), host integers are checked -- ks[c] of them, else ValueError -- and uploaded as uint32."""
+    from .engine import DeviceBuffer
+    locs, sorted_all = [], True
+    for loc, k in zip(locations, ks):
+        if isinstance(loc, DeviceBuffer):
+            locs.append(loc)
+            continue
+        la = np.asarray(loc, dtype=np.int64).reshape(-1)
+        if la.size != k:
+            raise ValueError(f"{la.size} locations for an upload of {k} values")
+        sorted_all = sorted_all and bool(np.all(la[1:] > la[:-1]))
+        locs.append(engine.upload(la.astype(np.uint32)) if k else engine.alloc(16))
+    return locs, sorted_all
+
+
+def _aggregate_packed_uploads(engine, uploads, locations, total, device):
+    """aggregate_sparse_uploads for uploads in their WIRE form (what quantize_encrypt(packed=True) returns for a sparse job): the arbiter's
+    decompress of every upload, expand_to_dense, the reduce and the compress of the sum (jzf_aggregator.py:287-357, :150-165, :382-384,
+    :424-430, then for_remote()).  Under _WIRE_SPARSE_AGG one launch goes from the packed uploads to the packed sum
+    (flashe_sparse_aggregate_packed_dev, path "fused"); otherwise, and when that launch declines (int_bits outside 16 .. 64, more than 64
+    clients) or host lists are not strictly increasing, every upload is unpacked, sparse_aggregate_dev sums them -- the span reduce, or
+    fill + scatter for lists that are not strictly increasing -- and pack_dev packs the sum (path "staged"): the same limbs.  Returns a
+    PackedVector of `total` fields (device=True) or its Python int."""
+    from .engine import DeviceVector, PackedVector
+    for up in uploads:
+        if up.bits != engine.int_bits or len(up) < 1:
+            raise ValueError(f"a PackedVector of {len(up)} fields of {up.bits} bits is no upload of a {engine.int_bits}-bit sparse job")
+    ks = [len(up) - 1 for up in uploads]
+    locs, sorted_all = _device_locations(engine, locations, ks)
+    for up in uploads:
+        up.wait_on(engine)
+    out = PackedVector(engine, total, engine.int_bits)
+    if total and _WIRE_SPARSE_AGG and sorted_all and engine.sparse_aggregate_packed_dev(total, locs, ks, [up.buf for up in uploads], out.buf):
+        out.path = "fused"
+        engine.hold([uploads, locs])
+    elif total:
+        dvs, lim = [DeviceVector(engine, len(up)) for up in uploads], engine.limbs
+        for up, dv in zip(uploads, dvs):
+            engine.unpack_dev(len(up), up.buf, dv.buf)
+        zeros = [[int(v) for v in dv.buf.download(np.uint64, len(dv) * lim)[(len(dv) - 1) * lim:]] for dv in dvs]
+        dense = DeviceVector(engine, total)
+        engine.sparse_aggregate_dev(total, locs, ks, [dv.buf for dv in dvs], zeros, dense.buf, sorted_lists=sorted_all)
+        engine.pack_dev(total, dense.buf, out.buf)
+        engine.hold([uploads, locs, dvs, dense])
+    out.mark_ready()
+    return out if device else out.to_int()
 
 
 # ---- the client step's front-end rules, each stated once (FlasheClient's tensor step and both cohorts) ---------------------------------

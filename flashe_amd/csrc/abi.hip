@@ -1946,6 +1946,31 @@ int flashe_sparse_aggregate_bounds_dev(flashe_ctx *ctx, uint64_t total, int C, c
     return sparse_aggregate_impl(ctx, total, C, loc_dev, k, vals_dev, zeros, 1, bounds, out_dev);
 }
 
+// The same reduce from the clients' PACKED uploads to the PACKED dense sum in one launch (stream.hip, span_reduce_wire_kernel): the zeros
+// are read from the uploads on the device, so nothing is staged and nothing synchronises.
+int flashe_sparse_aggregate_packed_dev(flashe_ctx *ctx, uint64_t total, int C, const uint32_t *const *loc_dev, const uint64_t *k,
+                                       const uint64_t *const *packed_dev, const flashe_span_bounds *bounds, uint64_t *out_packed_dev)
+{
+    CHECK_CTX(ctx);
+    if (!span_reduce_wire_admits(ctx->env, C, total, k))
+        return fail(ctx, FLASHE_ENOTSUP, "flashe_sparse_aggregate_packed_dev: needs 16 <= int_bits <= 64, 1 <= C <= %d, 1 <= total < 2^32 and every "
+                                         "k < 2^32 - 1 (run flashe_unpack_dev, flashe_sparse_aggregate_dev and flashe_pack_dev)", kMaxScatter);
+    if (!loc_dev || !packed_dev || !out_packed_dev) return fail(ctx, FLASHE_EINVAL, "bad arguments");
+    if (int rc = check_bounds(ctx, bounds, total, C, loc_dev, k)) return rc;
+    for (int c = 0; c < C; c++) {
+        if (k[c] > total) return fail(ctx, FLASHE_EINVAL, "client %d: more locations (%llu) than positions (%llu)", c,
+                                      static_cast<unsigned long long>(k[c]), static_cast<unsigned long long>(total));
+        if (!packed_dev[c] || (reinterpret_cast<uintptr_t>(packed_dev[c]) & 7u) || (k[c] && !loc_dev[c]))
+            return fail(ctx, FLASHE_EINVAL, "client %d: null list, null or misaligned upload", c);
+    }
+    if (reinterpret_cast<uintptr_t>(out_packed_dev) & 7u) return fail(ctx, FLASHE_EINVAL, "misaligned vector");
+    int rc = bounds ? ensure_reduce_table(ctx, bounds) : ensure(ctx, ctx->bounds, span_table_words(total, C) * sizeof(uint32_t));
+    if (rc) return rc;
+    HIP_TRY(ctx, launch_span_reduce_wire(ctx->env, C, loc_dev, packed_dev, k, total, bounds ? bounds->start : static_cast<uint32_t *>(ctx->bounds.p),
+                                         out_packed_dev, bounds != nullptr));
+    return FLASHE_OK;
+}
+
 // The sparse twin of flashe_encrypt_batch_sum_dev: the C clients this device plays encrypt their compact uploads (single mask over the
 // compact positions, jzf_flashe.py:471-478 on the values Client.sparsify kept) and the sum of the C expanded uploads -- what
 // Arbiter.expand_to_dense + the reduce make of them (jzf_aggregator.py:150-165, :419-430) -- is written in the same pass.

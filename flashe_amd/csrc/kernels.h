@@ -355,6 +355,15 @@ inline size_t span_table_words(uint64_t total, int C) { return static_cast<size_
 hipError_t launch_span_reduce(const LaunchEnv &env, int C, const uint32_t *const *loc_dev, const uint64_t *const *vals_dev,
                               const uint64_t *k, const uint64_t *sub, uint64_t base_lo, uint64_t base_hi, uint64_t total,
                               uint32_t *start_dev, const uint64_t *src_dev, bool negate, uint64_t *out_dev, bool bounds_ready = false);
+// The same reduce from the clients' packed WIRE uploads to the packed dense sum (stream.hip, span_reduce_wire_kernel): upload c is the
+// integer of its k[c] + 1 b-bit fields (field q at bit (k[c] - q) b; the last one, bits [0, b) of limb 0, is the un-encrypted zero z_c
+// -- read on the device), out_packed_dev the ceil(total b / 64) limbs with position p at bit (total - 1 - p) b holding
+// (sum_c z_c + sum_{c, q: loc[c][q] == p} (field q of c - z_c)) mod 2^b, every limb written exactly once.  ONE launch behind the bounds
+// pass (skipped under bounds_ready), stream-ordered.  span_reduce_wire_admits: 16 <= int_bits <= 64, 1 <= C <= kMaxScatter,
+// 1 <= total < 2^32, every k[c] < 2^32 - 1.  hipErrorNotSupported: nothing launched.
+bool span_reduce_wire_admits(const LaunchEnv &env, int C, uint64_t total, const uint64_t *k);
+hipError_t launch_span_reduce_wire(const LaunchEnv &env, int C, const uint32_t *const *loc_dev, const uint64_t *const *packed_dev, const uint64_t *k,
+                                   uint64_t total, uint32_t *start_dev, uint64_t *out_packed_dev, bool bounds_ready);
 // the first list entry of each of the C <= kMaxScatter clients in every span, at kSpanReduce and / or kSpanFused positions per span
 // (either table may be null): (span_count(total, span) + 1) * C words each, one pass over the lists
 hipError_t launch_span_bounds(const LaunchEnv &env, int C, const uint32_t *const *loc_dev, const uint64_t *k, uint64_t total, uint32_t *start_reduce_dev,

@@ -1363,6 +1363,181 @@ hipError_t launch_span_reduce(const LaunchEnv &env, int C, const uint32_t *const
     return hipGetLastError();
 }
 
+// ---- the span reduce from the packed WIRE uploads to the packed dense sum (int_bits 16 .. 64) ---------------------------------------
+// Upload c is the integer sum_j x[j] 2^(b (k_c - j)) over k_c + 1 fields: field q < k_c the ciphertext of the client's q-th location,
+// field k_c -- bits [0, b) of limb 0 -- its un-encrypted zero z_c.  The output is the packed dense sum: position p at bit
+// (total - 1 - p) b,  out[p] = (sum_c z_c + sum over the entries at p of (x_c[q] - z_c)) mod 2^b.  The spans, the bounds table, the flat
+// entry space and the owner search are span_reduce_kernel's; what differs:
+//   * wave 0 reads z_c from limb 0 of the upload itself and reduces base = sum z_c with shuffles -- nothing comes from the host;
+//   * an entry's value is cut out of the one or two limbs its field overlaps (the second one requested only when shift + b > 64: it then
+//     holds bits of this field, so no load passes the upload's last limb);
+//   * the write-out builds LIMBS: 4,096 b is a multiple of 64, so every span edge cuts a limb at the same bit (total b) mod 64.  A cut
+//     limb belongs to the span that holds its lowest bit: span s owns limb i iff lo_bit <= 64 i < hi_bit, with [lo_bit, hi_bit) the bits
+//     of its positions -- every limb has exactly one owner (the partial top limb span 0, its unused bits zero) and is written once with a
+//     plain non-temporal store: no clearing pass, no global atomics.  The owner's top limb reaches up to 63 bits = at most kWireHalo
+//     positions into the PREVIOUS span: these are kWireHalo extra accumulators in front of the span's, fed by one lane per (client,
+//     j < halo) that looks at entry begin_c - 1 - j of the sorted list (inside the halo iff its position >= p0 - halo).
+// Accumulators are 64-bit words (32.8 KiB) at every width: a 1,024-thread workgroup fills half of a CU's wave slots, so 32-bit words at
+// int_bits <= 32 would not bring a third workgroup onto the CU.
+constexpr int kWireHalo = 4;        // ceil(63 / 16): positions of the previous span a cut limb can hold
+struct SpanWireTable {
+    const uint32_t *loc[kMaxScatter];
+    const uint64_t *packed[kMaxScatter];
+    uint32_t k[kMaxScatter];
+};
+
+// field q of an upload of k + 1 b-bit fields: the limbs it overlaps, requested (wire_field_load) and cut (wire_field_cut) apart so that a
+// lane keeps several entries' loads in flight
+struct WireField { uint64_t lo, hi; uint32_t s; };
+
+__device__ __forceinline__ WireField wire_field_load(const uint64_t *packed, uint32_t k, uint32_t q, uint32_t b)
+{
+    const uint64_t bit = static_cast<uint64_t>(k - q) * b;
+    const uint64_t *p = packed + (bit >> 6);
+    WireField f;
+    f.s = static_cast<uint32_t>(bit) & 63u;
+    f.lo = ld64_g(p);
+    f.hi = f.s + b > 64u ? ld64_g(p + 1) : 0;
+    return f;
+}
+
+__device__ __forceinline__ uint64_t wire_field_cut(const WireField &f, uint64_t mask)
+{
+    return ((f.lo >> f.s) | (f.s ? f.hi << (64u - f.s) : 0)) & mask;
+}
+
+__global__ __launch_bounds__(kSpanThreads) void span_reduce_wire_kernel(const SpanWireTable tb, int C, uint32_t b, uint32_t b_magic, uint64_t total,
+                                                                        const uint32_t *__restrict__ start, uint64_t mask, uint64_t *__restrict__ out,
+                                                                        uint32_t *err_flag)
+{
+    __shared__ unsigned long long acc[kWireHalo + kSpan];         // acc[kWireHalo + r]: position p0 + r, r in [-halo, span_len)
+    __shared__ uint32_t s_begin[kMaxScatter], s_k[kMaxScatter], s_prefix[2 * kMaxScatter + 2];
+    __shared__ const uint32_t *s_loc[kMaxScatter];
+    __shared__ const uint64_t *s_pk[kMaxScatter];
+    __shared__ uint64_t s_z[kMaxScatter], s_base;
+    const uint64_t span = blockIdx.x, p0 = span * kSpan;
+    const uint32_t span_len = static_cast<uint32_t>(total - p0 < kSpan ? total - p0 : kSpan);
+    const int tid = threadIdx.x;
+    // the bits of this span's positions, the limbs it owns and the positions of the previous span its top limb holds
+    const uint64_t lo_bit = (total - p0 - span_len) * b, hi_bit = (total - p0) * b;
+    const uint64_t i0 = (lo_bit + 63) >> 6, i1 = (hi_bit + 63) >> 6;
+    const uint32_t over = static_cast<uint32_t>((i1 << 6) - hi_bit);                              // < 64
+    const uint32_t halo = span ? min(__umulhi(over + b - 1, b_magic), static_cast<uint32_t>(kWireHalo)) : 0u;
+    for (int i = tid; i < kWireHalo + kSpan; i += kSpanThreads) acc[i] = 0;
+    if (tid < 64) {
+        uint32_t cnt = 0;
+        uint64_t z = 0;
+        if (tid < C) {
+            const uint32_t kc = tb.k[tid];
+            const uint32_t b0 = min(start[span * C + tid], kc), b1 = min(start[(span + 1) * C + tid], kc);
+            cnt = b1 > b0 ? b1 - b0 : 0;
+            z = ld64_g(tb.packed[tid]) & mask;
+            s_begin[tid] = b0; s_k[tid] = kc;
+            s_loc[tid] = tb.loc[tid]; s_pk[tid] = tb.packed[tid];
+            s_z[tid] = z;
+        }
+        uint32_t run = cnt;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t up = __shfl_up(run, d, 64);
+            if (tid >= d) run += up;
+            z += __shfl_xor(z, d, 64);                             // (only needed mod 2^b, and 2^b divides 2^64)
+        }
+        if (tid == 0) { s_prefix[0] = 0; s_base = z; }
+        s_prefix[tid + 1] = tid < C ? run : 0xffffffffu;        // sentinels: the owner search needs no bounds
+        s_prefix[tid + 65] = 0xffffffffu;
+    }
+    __syncthreads();
+    // the halo: entry begin_c - 1 - j of client c, if it lies in the last `halo` positions of the previous span (no err flag here: a
+    // malformed list is reported by the bounds pass and by the span that owns the position; the cut limb's content is then unspecified)
+    if (tid < kMaxScatter * kWireHalo) {
+        const int c = tid / kWireHalo;
+        const uint32_t j = static_cast<uint32_t>(tid % kWireHalo);
+        if (c < C && j < halo && s_begin[c] > j) {
+            const uint32_t q = s_begin[c] - 1u - j;                // < k_c: s_begin is clamped
+            const uint32_t r = ld32_g(s_loc[c] + q) - (static_cast<uint32_t>(p0) - halo);
+            if (r < halo) {
+                const uint64_t v = wire_field_cut(wire_field_load(s_pk[c], s_k[c], q, b), mask);
+                atomicAdd(&acc[kWireHalo - halo + r], static_cast<unsigned long long>(v - s_z[c]));
+            }
+        }
+    }
+    const uint32_t n_entries = s_prefix[C];
+    for (uint32_t f0 = tid; f0 < n_entries; f0 += kSpanBatch * kSpanThreads) {
+        uint32_t r[kSpanBatch];
+        int own[kSpanBatch];
+        WireField fld[kSpanBatch];
+#pragma unroll
+        for (int e = 0; e < kSpanBatch; e++) {
+            const uint32_t fe = f0 + e * kSpanThreads;
+            const uint32_t f = fe < n_entries ? fe : f0;       // surplus slots re-read the first entry (f0 < n_entries) and are not added
+            int c = 0;
+#pragma unroll
+            for (int step = 32; step; step >>= 1)
+                if (s_prefix[c + step] <= f) c += step;
+            own[e] = c;
+            const uint32_t q = s_begin[c] + (f - s_prefix[c]);     // < k_c
+            r[e] = ld32_g(s_loc[c] + q) - static_cast<uint32_t>(p0);
+            fld[e] = wire_field_load(s_pk[c], s_k[c], q, b);
+        }
+#pragma unroll
+        for (int e = 0; e < kSpanBatch; e++) {
+            if (f0 + e * kSpanThreads >= n_entries) break;
+            if (r[e] >= span_len) { *err_flag = 1; continue; }      // position >= total, or a list that is not strictly increasing
+            atomicAdd(&acc[kWireHalo + r[e]], static_cast<unsigned long long>(wire_field_cut(fld[e], mask) - s_z[own[e]]));
+        }
+    }
+    __syncthreads();
+    // limb i = the fields of the positions whose bits overlap [64 i, 64 i + 64).  Counted from the span's END, position e = span_len - 1 - r
+    // lies at bit lo_bit + e b: the first one is e0 = floor(t / b) with t = 64 i - lo_bit < 2^19 (a 32-bit multiply-high), the last one
+    // may be a halo position (r < 0); beyond the halo there is nothing (the top of span 0's partial limb stays zero).
+    const uint64_t base = s_base;
+    for (uint64_t i = i0 + tid; i < i1; i += kSpanThreads) {
+        const uint32_t t = static_cast<uint32_t>((i << 6) - lo_bit);
+        const uint32_t e0 = __umulhi(t, b_magic);
+        uint64_t limb = 0;
+        int r = static_cast<int>(span_len) - 1 - static_cast<int>(e0);
+        for (int sh = -static_cast<int>(t - e0 * b); sh < 64 && r >= -static_cast<int>(halo); sh += static_cast<int>(b), r--) {
+            const uint64_t v = (acc[kWireHalo + r] + base) & mask;
+            limb |= sh >= 0 ? v << sh : v >> -sh;
+        }
+        __builtin_nontemporal_store(limb, out + i);
+    }
+}
+
+bool span_reduce_wire_admits(const LaunchEnv &env, int C, uint64_t total, const uint64_t *k)
+{
+    if (env.b < 16 || env.b > 64 || C < 1 || C > kMaxScatter || total < 1 || total >= (1ull << 32) || !k) return false;
+    for (int c = 0; c < C; c++)
+        if (k[c] >= (1ull << 32) - 1) return false;
+    return true;
+}
+
+// out_packed_dev = the packed sum of the C packed uploads expanded to `total` positions (layouts above); start_dev: (span_count(total,
+// kSpanReduce) + 1) * C words, filled here unless bounds_ready.  Stream-ordered: no host synchronisation, no staged table.
+// hipErrorNotSupported: nothing launched.
+hipError_t launch_span_reduce_wire(const LaunchEnv &env, int C, const uint32_t *const *loc_dev, const uint64_t *const *packed_dev, const uint64_t *k,
+                                   uint64_t total, uint32_t *start_dev, uint64_t *out_packed_dev, bool bounds_ready)
+{
+    if (!span_reduce_wire_admits(env, C, total, k)) return hipErrorNotSupported;
+    if (!start_dev || !out_packed_dev) return hipErrorInvalidValue;
+    SpanWireTable tb{};
+    for (int c = 0; c < C; c++) {
+        if (!packed_dev[c] || (k[c] && !loc_dev[c]) || k[c] > total) return hipErrorInvalidValue;
+        tb.loc[c] = loc_dev[c]; tb.packed[c] = packed_dev[c]; tb.k[c] = static_cast<uint32_t>(k[c]);
+    }
+    uint64_t lo, hi;
+    masks_of(env.b, &lo, &hi);
+    if (!bounds_ready) {
+        const hipError_t e = launch_span_bounds(env, C, loc_dev, k, total, start_dev, nullptr);
+        if (e != hipSuccess) return e;
+    }
+    const uint32_t b = static_cast<uint32_t>(env.b);
+    hipLaunchKernelGGL(span_reduce_wire_kernel, dim3(static_cast<unsigned>(span_count(total, kSpanReduce))), dim3(kSpanThreads), 0, env.stream, tb, C, b,
+                       static_cast<uint32_t>(((1ull << 32) + b - 1) / b), total, start_dev, lo, out_packed_dev, env.err_flag);
+    return hipGetLastError();
+}
+
 // ---- the span reduce with the PRF inside (int_bits > 64, table PRF) ---------------------------------------------------------------
 // The sparse single-mask passes spend more time generating their compact mask streams (one AES block per list entry, LDS-lookup bound)
 // than reducing them (HBM bound), and the streams make a round trip through HBM in between.  Here the two run in ONE persistent kernel,

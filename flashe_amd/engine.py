@@ -1520,6 +1520,18 @@ class Engine:
         self._check(self._lib.flashe_sparse_aggregate_dev(self._h, total, len(locs), pl, ctypes.cast(k, c_u64p), pv,
                                                           ctypes.cast(zz, c_u64p), 1 if sorted_lists else 0, self._ptr(out)))
 
+    def sparse_aggregate_packed_dev(self, total, locs, ks, packed, out, bounds=None):
+        """unpack_dev of every client's packed upload (ks[c] + 1 fields, the last one its un-encrypted zero) + sparse_aggregate_dev over
+        strictly increasing lists + pack_dev of the dense sum in ONE launch (flashe_sparse_aggregate_packed_dev): out = the
+        ceil(total int_bits / 64) limbs of the sum, every one written; nothing is downloaded.  bounds: a SpanBounds of exactly these lists,
+        else they are computed first.  False -- nothing was launched -- when the library declines (int_bits outside 16 .. 64, more than 64
+        clients), True otherwise."""
+        pl, _kl = self._ptr_array(locs)
+        pp, _kp = self._ptr_array(packed)
+        k = _u64_array(ks)
+        return self._took(self._lib.flashe_sparse_aggregate_packed_dev(self._h, total, len(locs), pl, ctypes.cast(k, c_u64p), pp,
+                                                                       bounds._h if bounds is not None else None, self._ptr(out)))
+
     def sparse_encrypt_aggregate_dev(self, it, idx, locs, ks, pts, pt_limbs, zeros, total, n_jobs, cts, agg, bounds=None, position_range=None):
         """The clients this device plays encrypt their compact uploads (single mask) and the sum of the expanded uploads is written in
         the same pass: cts[c] = encrypt(it, idx[c], SINGLE) of pts[c], agg = sparse_aggregate_dev(locs, cts, zeros).  Strictly increasing

@@ -105,7 +105,8 @@ typedef struct flashe_ctx flashe_ctx;
  *      flashe_unpack_decrypt_unbatch_unquantize_model_dev (the BATCHED client step straight to and from the packed wire form at int_bits
  *      65 .. 128: one launch each way, no 16-byte plaintext or ciphertext vector);
  *      flashe_unpack_decrypt_lists_unquantize_model_dev / flashe_unpack_decrypt_lists_unbatch_unquantize_model_dev (both ways back with
- *      prefix lists of up to 96 each: a round with a dropout, the single mask's decrypt) */
+ *      prefix lists of up to 96 each: a round with a dropout, the single mask's decrypt);
+ *      flashe_sparse_aggregate_packed_dev (the sparse job's packed uploads reduced to the packed dense sum in one launch) */
 #define FLASHE_ABI_VERSION 4
 int flashe_abi_version(void);
 int flashe_device_count(int *count);
@@ -568,6 +569,21 @@ int flashe_sparse_aggregate_bounds_dev(flashe_ctx *ctx, uint64_t total, int C, c
 int flashe_sparse_decrypt_bounds_dev(flashe_ctx *ctx, uint32_t iter, int C, const uint32_t *const *loc_dev, const uint64_t *k,
                                      uint64_t total, uint32_t n_jobs, const flashe_span_bounds *bounds, const uint64_t *agg_dev,
                                      uint64_t *out_dev);
+/* The arbiter's side of the sparse job on the WIRE form (new; jzf_aggregator.py:150-165, 382-384, 424-430 between jzf_weights.py:155-231's
+ * decompress of every upload and compress of the sum): what C flashe_unpack_dev calls, flashe_sparse_aggregate_dev with sorted = 1 (the
+ * zeros taken from the uploads) and flashe_pack_dev compute, limb for limb, in ONE launch with nothing downloaded and no uint64 element
+ * vector.  packed_dev[c]: client c's upload as it travels, ceil((k[c] + 1) int_bits / 64) little-endian limbs of the integer
+ * sum_j x[j] 2^(int_bits (k[c] - j)) -- field q < k[c] the ciphertext of its q-th location, field k[c] (bits [0, int_bits) of limb 0) the
+ * un-encrypted quantised zero z_c (read only); loc_dev[c]: its k[c] STRICTLY INCREASING locations (a list that is not, or that reaches
+ * beyond total, is reported as the sparse passes report it: the offending entries are skipped and the next synchronising call fails with
+ * FLASHE_EINVAL).  out_packed_dev: ceil(total int_bits / 64) limbs, position p at bit (total - 1 - p) int_bits holding
+ * (sum_c z_c + sum over c, q with loc[c][q] == p of (x_c[q] - z_c)) mod 2^int_bits, the unused top bits of the last limb zero; every limb
+ * is written exactly once (no fill in front).  bounds: a handle of exactly these lists -- one made for the plain reduce serves -- or NULL:
+ * the bounds are then computed on the stream first, in ctx scratch.  Stream-ordered: no host synchronisation, no staged table.
+ * FLASHE_ENOTSUP -- checked first, nothing launched or written -- unless 16 <= int_bits <= 64, 1 <= C <= 64, 1 <= total < 2^32 and every
+ * k[c] < 2^32 - 1; FLASHE_EINVAL as flashe_sparse_aggregate_bounds_dev (a handle made for other lists included). */
+int flashe_sparse_aggregate_packed_dev(flashe_ctx *ctx, uint64_t total, int C, const uint32_t *const *loc_dev, const uint64_t *k,
+                                       const uint64_t *const *packed_dev, const flashe_span_bounds *bounds, uint64_t *out_packed_dev);
 /* The sparse twin of flashe_encrypt_batch_sum_dev (new): the C clients this device plays encrypt their compact uploads with the single
  * mask -- ct_dev[c] = flashe_encrypt_dev(iter, idx[c], SINGLE, k[c], n_jobs) of pt_dev[c] (jzf_flashe.py:471-478) -- AND the sum of
  * their expanded uploads, flashe_sparse_aggregate_dev(loc_dev, ct_dev, zeros) (jzf_aggregator.py:150-165, :419-430), is written to
