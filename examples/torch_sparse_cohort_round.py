@@ -5,7 +5,10 @@ FlasheSparseCohort mirrors the sparse job's steps one to one -- sparsify (top 10
 the arbiter's masking choice from the clients' location lists, quantise + encrypt of the kept values with the dense aggregate of the ten
 uploads, decrypt + unquantise into `out` -- with the device work of the whole cohort in a number of launches that does not grow with
 the number of clients.  The result is bit for bit what ten Sparsifiers + FlasheClients produce one after the other, which this example
-checks."""
+checks.
+
+--wire: the round on the packed wire form, quantize_encrypt(packed="fused") -- floats -> packed uploads -> packed dense sum -> floats,
+no uint64 element vector in HBM; prints the paths that ran and checks the floats against the unpacked round's."""
 import os
 import sys
 
@@ -31,6 +34,28 @@ def make_model(seed):
     return torch.nn.Sequential(torch.nn.Conv2d(3, 16, 5), torch.nn.ReLU(), torch.nn.Flatten(), torch.nn.Linear(16 * 28 * 28, 10)).cuda()
 
 
+def wire_round(args, layers, C, key, sparsity):
+    """One round twice on the same seeds: unpacked, then on the wire form."""
+    floats = {}
+    for packed in (False, "fused"):
+        cohort = FlasheSparseCohort(args, first_idx=0, n_local=C, num_clients=C, prp_seed=key, sparsity=sparsity)
+        with torch.no_grad():
+            cohort.set_iter_index(0)
+            cohort.sparsify(layers)
+            cohort.dynamic_masking()
+            np.random.seed(0)
+            upload = cohort.quantize_encrypt(normalize=True, packed=packed)
+            floats[packed] = {name: torch.empty_like(t) for name, t in layers[0].items()}
+            cohort.decrypt_unquantize(out=floats[packed], unnormalize=True)
+        if packed:
+            n_bytes = sum(8 * u.n_limbs for u in upload.uploads)
+            print(f"wire round: front end {upload.front_end!r}, uploads {sorted({u.path for u in upload.uploads})}, aggregate {upload.aggregate.path!r}; "
+                  f"{C} uploads of {len(upload.uploads[0])} fields in {n_bytes} bytes")
+    for name in floats[False]:
+        assert torch.equal(floats[False][name].view(torch.uint8), floats["fused"][name].view(torch.uint8)), name
+    print("the wire round's new global model equals the unpacked round's bit for bit")
+
+
 def main():
     cm.N_JOBS = 16                                           # every party must use the same value
     C, key, sparsity, rounds = 10, bytes(range(32)), 0.1, 2
@@ -39,6 +64,8 @@ def main():
     models = [make_model(c) for c in range(C)]
     layers = [{name: p.detach() for name, p in m.named_parameters()} for m in models]
     names = sorted(layers[0])
+    if "--wire" in sys.argv[1:]:
+        return wire_round(args, layers, C, key, sparsity)
 
     cohort = FlasheSparseCohort(args, first_idx=0, n_local=C, num_clients=C, prp_seed=key, sparsity=sparsity)
     # the same rounds as ten Sparsifiers + FlasheClients, one after the other (every client's history from the same global model)

@@ -65,6 +65,17 @@ _WIRE_SPARSE_BACK = False
 # 25,557,032 positions with 50 clients at 1 % and with 10 clients at 10 %, 1e7 positions with 10 clients at 10 %, int_bits 20 and 64
 # (x 2.54 - 3.60), so it is the default.  profiles/r44_wire_sparse_agg.log
 _WIRE_SPARSE_AGG = True
+# FlasheSparseCohort.quantize_encrypt(packed=True) takes the cohort's uploads from the floats straight to their packed wire form in one
+# launch (int_bits 16 .. 64, at most 192 clients: wire.hip, prf_small_pack_cohort_kernel) only under this switch; packed="fused" asks for it
+# outright.  Without it, and where the launch declines, today's front end runs and every upload goes through pack_dev.  Per compact value
+# and client the launch moves 4 + 8 bytes in and int_bits / 8 out plus int_bits / 8 for the one clearing fill (14.5 + 2.5 at int_bits 20
+# with float32 layers) against 4 + 8 in, 8 out, then 8 in and int_bits / 8 out through the one-limb uploads and C pack launches (30.5),
+# counted from the code.  Measured against that sequence (the chained front end where it exists, + C pack_dev) in two processes the fused
+# median leads everywhere (x 1.22 - 4.34) and wins by more than either form's spread in both at ten clients with K = 2,555,703, at fifty
+# with K = 255,570 (both at int_bits 20 and 64) and at ten with K = 1,000,000 at int_bits 64; at ten clients with K = 1,000,000 and
+# int_bits 20 one fused sample of 0.145 ms (median 0.107 against 0.141) turns the first process.  Not every class wins in both processes
+# and no threshold was fitted, so the ROUTING stays opt-in.  profiles/r45_wire_sparse_cohort_out.log
+_WIRE_SPARSE_OUT = False
 
 __all__ = ["dynamic_masking_choice", "FlasheClient", "FlasheCohort", "CohortPlan", "CohortUpload", "plan_cohort", "FlasheSparseCohort",
            "SparseCohortPlan", "SparseCohortEncoding", "SparseCohortUpload", "plan_sparse_cohort"]
@@ -2379,6 +2390,8 @@ class FlasheCohort(object):
 # ---- a cohort of sparse-job clients hosted on one GPU (new) ----------------------------------------------------------------------
 SPARSE_COHORT = "sparse-cohort"
 FRONT_FUSED, FRONT_STAGED = "fused", "staged"
+FRONT_WIRE = "wire"              # the uploads in ONE launch from the floats straight to their packed wire form (quantize_encrypt(packed=...))
+_WIRE_COHORT_MAX_CLIENTS = 192   # clients of that launch (kMaxPackCohort, kernels.h)
 
 
 class SparseCohortPlan(object):
@@ -2408,7 +2421,8 @@ class SparseCohortEncoding(object):
 class SparseCohortUpload(object):
     """FlasheSparseCohort.quantize_encrypt's result: uploads (one DeviceVector of K + 1 elements per client: the K ciphertexts and the
     un-encrypted quantised zero), aggregate (aggregate_sparse_uploads of them: `total` elements), path and front_end ("fused" / "staged":
-    the form that made the uploads)."""
+    the form that made the uploads).  Under packed= every upload and the aggregate are PackedVectors (K + 1 and `total` fields of
+    int_bits bits; their own .path says how each was made) and front_end may be "wire": one launch from the floats to the packed limbs."""
 
     def __init__(self, uploads, aggregate, path, front_end=FRONT_STAGED):
         self.uploads, self.aggregate, self.path, self.front_end = uploads, aggregate, path, front_end
@@ -2496,7 +2510,9 @@ class FlasheSparseCohort(object):
     (flashe_quantize_encrypt_sparse_cohort_dev, front_end "fused": no plaintext vector in HBM) followed by the sparse aggregate -- at
     the other widths one quantise launch (flashe_quantize_cohort_dev) and the fused encrypt + aggregate
     (flashe_sparse_encrypt_aggregate_dev; at int_bits <= 64 one batched encrypt launch and the aggregate) -- with the span bounds of
-    the round's lists computed once, and the sparse decrypt + unquantise + store.  One engine and one stream carry everything, the sparsifier passes included.  `path` of an upload names the form that ran."""
+    the round's lists computed once, and the sparse decrypt + unquantise + store.  One engine and one stream carry everything, the sparsifier passes included.  `path` of an upload names the form that ran.
+    quantize_encrypt(packed=...) runs the round on the packed wire form: the uploads from the floats straight to their packed limbs in one
+    launch at int_bits 16 .. 64 (flashe_quantize_encrypt_pack_sparse_cohort_dev, front_end "wire"), the packed dense sum, the same floats."""
 
     def __init__(self, args, first_idx, n_local, num_clients, prp_seed, sparsity, device=0, stream=None):
         if n_local < 1 or first_idx < 0 or first_idx + n_local > num_clients:
@@ -2707,8 +2723,16 @@ class FlasheSparseCohort(object):
         return self._host_masks
 
     # ---- Client.secure_aggregate's quantise + encrypt, and the arbiter's expand + reduce --------------------------------------------
-    def quantize_encrypt(self, normalize=False, seeds=None, compact=None, rng=None):
-        """rng (new): the draws come from the caller's np.random.Generator (one: the clients draw one after the other, K + 1 each, the last
+    def quantize_encrypt(self, normalize=False, seeds=None, compact=None, rng=None, packed=False):
+        """packed (new): False runs exactly the step below.  True or "fused": every upload is a PackedVector of K + 1 fields of int_bits
+        bits -- the wire form JZFTransferableWeights.compress gives the upload -- and `aggregate` the packed dense sum, a PackedVector of
+        `total` fields, which decrypt_unquantize() takes as it is: the same integers and the same floats, bit for bit.  "fused" takes the
+        ONE launch from the floats to the packed limbs of all C uploads (front_end "wire": no uint64 element vector in HBM, no download
+        of the zeros when the packed reduce takes the sum) wherever the library admits it -- int_bits 16 .. 64, at most 192 clients; True
+        only under _WIRE_SPARSE_OUT.  Otherwise (a batched job, a precompute cache, mixed dtypes, prefer_front_end "staged", a declined
+        launch) today's front end runs and pack_dev packs every upload and the aggregate.  Another value: ValueError.
+
+        rng (new): the draws come from the caller's np.random.Generator (one: the clients draw one after the other, K + 1 each, the last
         one a client's 'zzz' draw) or a list of one Generator per client, as FlasheCohort.quantize_encrypt takes them: np.random.random(k)
         replaced by the generator's .random(k) on every path, the global stream untouched, Philox and PCG64-family generators on the device in ONE launch per kind.
         rng with seeds or a list of another length: ValueError; not a Generator: TypeError.
@@ -2730,6 +2754,8 @@ class FlasheSparseCohort(object):
             raise ValueError(f"seeds: one per client ({C}), got {len(seeds)}")
         if rng is not None and seeds is not None:
             raise ValueError("rng and seeds: one source of draws at a time")
+        if packed not in (False, True, "fused"):
+            raise ValueError(f"packed: False, True or 'fused', not {packed!r}")
         rng = _check_rng(rng, C)
         zzzs = [np.array([0.0])] * C
         if compact is not None:
@@ -2752,7 +2778,7 @@ class FlasheSparseCohort(object):
                                      mixed or len(zdt) != 1)
         self._last = None
         if path == PER_CLIENT:
-            return self._per_client(per_client_layers, names, zzzs, all_host, normalize, seeds, rng)
+            return self._per_client(per_client_layers, names, zzzs, all_host, normalize, seeds, rng, packed)
         # one quantiser state: the compact layers and the one-value 'zzz' layer are the layer_size_list, the lists hold the L compact layers
         alphas = _round_alphas(q, list(ks) + [1])
         q.r_max_list = [alphas[li] * q.num_clients for li in range(L)]
@@ -2773,11 +2799,18 @@ class FlasheSparseCohort(object):
             at += ks[li]
         zvals, z64 = self._zzz_values(zzzs, normalize, L)
         du = _cohort_draws(eng, C, K + 1, seeds, rng)
-        ups = [DeviceVector(eng, K + 1) for _ in range(C)]
         zbuf = eng.alloc(max(8 * C, 16))
-        front, ptbuf, pts = self._launch_uploads(path, K, table, srcs, dts, du, zvals, z64, ups, zbuf)
-        zeros = [int(v) for v in zbuf.download(np.uint64, C)]          # the C quantised zeros: the one download of the step
-        agg, bounds = self._aggregate(front, K, pts, ups, zeros)
+        ups = self._launch_wire(K, table, srcs, dts, du, zvals, z64, zbuf) if packed == "fused" or (packed and _WIRE_SPARSE_OUT) else None
+        if ups is not None:
+            front, ptbuf = FRONT_WIRE, None
+            agg, bounds = self._aggregate_wire(ups)
+        else:
+            ups = [DeviceVector(eng, K + 1) for _ in range(C)]
+            front, ptbuf, pts = self._launch_uploads(path, K, table, srcs, dts, du, zvals, z64, ups, zbuf)
+            zeros = [int(v) for v in zbuf.download(np.uint64, C)]          # the C quantised zeros: the one download of the step
+            agg, bounds = self._aggregate(front, K, pts, ups, zeros)
+            if packed:
+                ups, agg = [self._packed_of(u) for u in ups], self._packed_of(agg)
         eng.hold(keep + [du, zbuf] + ([ptbuf] if ptbuf is not None else []))
         ld.shape_dict = {k: (kl,) for k, kl in zip(names, ks)}
         for u in ups:
@@ -2861,6 +2894,59 @@ class FlasheSparseCohort(object):
         eng.quantize_cohort_dev(K, table, srcs, dts, q.element_bits, du, K + 1, zvals, z64, pts, [u.ptr + 8 * eng.limbs * K for u in ups], zbuf)
         return FRONT_STAGED, ptbuf, pts
 
+    def _launch_wire(self, K, table, srcs, dts, du, zvals, z64, zbuf):
+        """The uploads straight in their wire form: ONE launch from the floats to the packed limbs of all clients, the C uploads an even
+        number of limbs apart in ONE buffer that one fill clears (flashe_quantize_encrypt_pack_sparse_cohort_dev).  Returns the C
+        PackedVectors (path "fused"), or None -- nothing was written -- under prefer_front_end "staged", without the symbol, or when the
+        library declines: the caller runs today's front end."""
+        from . import cipher as _cipher_mod
+        from .engine import DeviceBufferView, PackedVector
+        ld = self.lead
+        q, c = ld.quantizer, ld.cipher
+        eng, C = c.engine, self.n_local
+        wire = getattr(eng, "quantize_encrypt_pack_sparse_cohort_dev", None)
+        if wire is None or self.prefer_front_end == FRONT_STAGED or C > _WIRE_COHORT_MAX_CLIENTS or not 16 <= ld.int_bits <= 64:
+            return None
+        n_limbs = ((K + 1) * ld.int_bits + 63) // 64
+        stride = (n_limbs + 1) & ~1
+        buf = eng.alloc(8 * C * stride)
+        if not wire(c.iter_index, [self.first_idx + ci for ci in range(C)], K, _cipher_mod.N_JOBS, table, srcs, dts, q.element_bits, du, K + 1, zvals, z64,
+                    buf, stride, zbuf):
+            return None
+        return [PackedVector(eng, K + 1, ld.int_bits, buf=DeviceBufferView(buf, 8 * ci * stride, 8 * n_limbs), path="fused") for ci in range(C)]
+
+    def _aggregate_wire(self, ups):
+        """(the packed dense sum, span bounds or None) of uploads in their wire form, by aggregate_sparse_uploads' route for PackedVectors:
+        over strictly increasing lists the one launch from the packed uploads to the packed sum with the round's bounds handle (path
+        "fused": limb 0 of every upload holds its zero, nothing is downloaded); its staged fallback for lists that are not, and where
+        that launch declines (more than 64 clients)."""
+        from .engine import PackedVector
+        c = self.lead.cipher
+        eng, C = c.engine, self.n_local
+        own = self._lists[self.first_idx:self.first_idx + C]
+        locs, lks = [b for b, _k in own], [k for _b, k in own]
+        total = int(c.total)
+        bounds = self._round_bounds(total, locs, lks) if self._sorted else None
+        if bounds is not None and total and _WIRE_SPARSE_AGG:
+            agg = PackedVector(eng, total, eng.int_bits, path="fused")
+            if eng.sparse_aggregate_packed_dev(total, locs, lks, [u.buf for u in ups], agg.buf, bounds=bounds):
+                eng.hold([ups, locs])
+                return agg, bounds
+        for u in ups:
+            u.mark_ready()
+        return aggregate_sparse_uploads(eng, ups, locs if self._sorted else self._host_lists()[self.first_idx:self.first_idx + C], total), bounds
+
+    def _packed_of(self, dv):
+        """A DeviceVector of the staged step in its wire form (pack_dev; path "staged")."""
+        from .engine import PackedVector
+        eng = self.engine
+        dv = dv.widened(eng) if dv.compact else dv
+        pv = PackedVector(eng, len(dv), eng.int_bits)
+        if len(dv):
+            eng.pack_dev(len(dv), dv.buf, pv.buf)
+        eng.hold([dv])
+        return pv
+
     def _aggregate(self, front, K, pts, ups, zeros):
         """(aggregate, span bounds or None) of the cohort's uploads: the sparse aggregate of the ciphertexts the fused front end wrote, or
         the encrypts of the staged front end's plaintexts with it -- one fused launch over strictly increasing lists, which takes their
@@ -2900,7 +2986,7 @@ class FlasheSparseCohort(object):
         self._bounds = (bounds, shape)
         return bounds
 
-    def _per_client(self, per_client_layers, names, zzzs, all_host, normalize, seeds, rng=None):
+    def _per_client(self, per_client_layers, names, zzzs, all_host, normalize, seeds, rng=None, packed=False):
         """The clients' own FlasheClient steps one after the other on the shared quantiser state (one cipher re-indexed per client; with
         precompute: every client's own cipher), then aggregate_sparse_uploads of what they wrote.  What FlasheClient refuses is refused
         by the first client's step, before any draw is taken."""
@@ -2925,6 +3011,8 @@ class FlasheSparseCohort(object):
         finally:
             ld.cipher.idx = self.first_idx
         own = self._lists[self.first_idx:self.first_idx + self.n_local]
+        if packed:                                    # (packed uploads give the packed sum: aggregate_sparse_uploads' own route)
+            ups = [self._packed_of(u).mark_ready() for u in ups]
         agg = aggregate_sparse_uploads(eng, ups, [b for b, _k in own] if self._sorted else masks[self.first_idx:self.first_idx + self.n_local],
                                        int(ld.cipher.total), device=True)
         self._last = SparseCohortUpload(ups, agg, PER_CLIENT)

@@ -2053,4 +2053,38 @@ int flashe_quantize_encrypt_sparse_cohort_dev(flashe_ctx *ctx, uint32_t iter, in
                            who, "sparse cohort");
 }
 
+// The same uploads straight in their packed WIRE form at every int_bits 16 .. 64 (prf_small_pack_cohort_kernel, wire.hip): upload c = the
+// ceil((n + 1) int_bits / 64) limbs at packed_dev + c * packed_stride, the C uploads in ONE allocation so that one fill clears them.  The
+// checks are quantize_cohort_check's, the table and the stage pass cohort_stage's; a width outside 16 .. 64, more than kMaxPackCohort
+// clients, n = 0 or another PRF backend is refused with FLASHE_ENOTSUP before anything is staged, cleared or written.  Not capturable:
+// the table upload synchronises, as in every model-wide codec call.
+int flashe_quantize_encrypt_pack_sparse_cohort_dev(flashe_ctx *ctx, uint32_t iter, int n_clients, const uint32_t *idx, uint64_t n, uint32_t n_jobs,
+                                                   const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                                   int element_bits, const double *u_dev, uint64_t u_stride, const double *zzz, int zzz_is_f64,
+                                                   uint64_t *packed_dev, uint64_t packed_stride, uint64_t *zeros_dev)
+{
+    CHECK_CTX(ctx);
+    static const char who[] = "flashe_quantize_encrypt_pack_sparse_cohort_dev";
+    std::vector<int> row_of;
+    int rc = quantize_cohort_check(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, u_dev, u_stride, zzz, packed_dev, zeros_dev, row_of);
+    if (rc) return rc;
+    if (!idx) return fail(ctx, FLASHE_EINVAL, "%s: null argument", who);
+    if (n_jobs == 0) return fail(ctx, FLASHE_EINVAL, "n_jobs must be >= 1");
+    if (reinterpret_cast<uintptr_t>(packed_dev) & 7u) return fail(ctx, FLASHE_EINVAL, "%s: packed_dev must be 8-byte aligned", who);
+    if (!small_pack_cohort_admits(ctx->env, n_clients, n, n_jobs)) return cohort_declined(ctx, who, "packed sparse cohort");
+    const uint64_t n_limbs = ((n + 1) * static_cast<uint64_t>(ctx->env.b) + 63) / 64;
+    if (packed_stride < n_limbs) return fail(ctx, FLASHE_EINVAL, "%s: packed_stride must cover an upload's %llu limbs", who, static_cast<unsigned long long>(n_limbs));
+    if (zeros_dev >= packed_dev && zeros_dev < packed_dev + static_cast<uint64_t>(n_clients - 1) * packed_stride + n_limbs)
+        return fail(ctx, FLASHE_EINVAL, "%s: zeros_dev lies inside the uploads", who);
+    const Codec z = codec_quantize_front(nullptr, zzz_is_f64 != 0, 1.0, element_bits, nullptr);
+    CohortCodec cc{};
+    const char *zzz_dev = nullptr;
+    if ((rc = cohort_stage(ctx, n_clients, n, layers, n_layers, src_dev, src_dtype, element_bits, cc, zzz, static_cast<size_t>(n_clients) * sizeof(double),
+                           &zzz_dev, &row_of)))
+        return rc;
+    return cohort_launched(ctx, launch_small_pack_cohort(ctx->env, iter, n_clients, idx, cc, u_dev, u_stride, n, n_jobs, packed_dev, packed_stride,
+                                                         reinterpret_cast<const double *>(zzz_dev), z.x_is_f64 != 0, z.alpha, z.scale, z.den, zeros_dev),
+                           who, "packed sparse cohort");
+}
+
 }  // extern "C"

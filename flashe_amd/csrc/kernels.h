@@ -291,6 +291,17 @@ hipError_t launch_small_pack(const LaunchEnv &env, uint32_t iter, uint32_t add_i
                              uint64_t *packed_dev);
 hipError_t launch_small_unpack(const LaunchEnv &env, uint32_t iter, bool has_add, uint32_t add_idx, bool has_minus, uint32_t minus_idx, uint64_t n,
                                uint32_t n_jobs, const uint64_t *packed_dev, const Codec &cq);
+// launch_small_pack_cohort: launch_small_sparse_cohort's uploads in their WIRE form (prf_small_pack_cohort_kernel): upload c = the
+// ceil((n + 1) b / 64) limbs at packed_dev + c * packed_stride of the n single-mask ciphertexts (idx[c]; any indices) of client c's
+// quantised compact values followed by its plain quantised 'zzz' value (n + 1 fields; also zeros_dev[c]); cc, u_dev, u_stride and the
+// 'zzz' arguments as launch_small_sparse_cohort takes them.  One fill of limbs [0, (n_vec - 1) packed_stride + n_limbs) and one launch.
+// small_pack_cohort_admits: small_wire_admits and 1 .. kMaxPackCohort clients (the prefix table of the launch).  hipErrorNotSupported:
+// nothing launched; hipErrorInvalidValue: a stride shorter than an upload or than a client's n + 1 draws.
+constexpr int kMaxPackCohort = 2 * kMaxIdx;
+bool small_pack_cohort_admits(const LaunchEnv &env, int n_vec, uint64_t n, uint32_t n_jobs);
+hipError_t launch_small_pack_cohort(const LaunchEnv &env, uint32_t iter, int n_vec, const uint32_t *idx, const CohortCodec &cc, const double *u_dev,
+                                    uint64_t u_stride, uint64_t n, uint32_t n_jobs, uint64_t *packed_dev, uint64_t packed_stride, const double *zzz_dev,
+                                    bool zzz_f64, double z_alpha, double z_scale, double z_den, uint64_t *zeros_dev);
 // launch_small_unpack_lists: the same with HOST prefix lists of 0 .. kMaxIdx each, at least one prefix in all, repeats summed:
 // cq.fout[j] = unquantise(element j + sum_k term(add[k]) - sum_k term(minus[k])) in ONE launch (prf_small_unpack_lists_kernel, wire_lists.h).
 hipError_t launch_small_unpack_lists(const LaunchEnv &env, uint32_t iter, const uint32_t *add, int n_add, const uint32_t *minus, int n_minus, uint64_t n,

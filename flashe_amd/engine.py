@@ -1983,6 +1983,22 @@ class Engine:
                                                                  int(u_stride), pz, 1 if zzz_is_f64 else 0, pc, self._ptr(zeros))
         return self._took(rc)
 
+    def quantize_encrypt_pack_sparse_cohort_dev(self, it, idx, n, n_jobs, layers, srcs, dtypes, element_bits, u, u_stride, zzz, zzz_is_f64, packed,
+                                                packed_stride, zeros):
+        """quantize_encrypt_sparse_cohort_dev + pack_dev of every upload as ONE launch from the floats at int_bits 16 .. 64
+        (flashe_quantize_encrypt_pack_sparse_cohort_dev): the same arguments, with the C uploads in ONE buffer -- client c's
+        ceil((n + 1) int_bits / 64) limbs at packed + 8 c packed_stride bytes (n + 1 fields: the ciphertexts, then the plain quantised
+        'zzz' in the low bits of limb 0).  Returns False -- nothing was staged, cleared or launched -- when the library declines (a width
+        outside 16 .. 64, more than 192 clients, n = 0), True otherwise."""
+        arr, nl = self._tensor_layers(layers)
+        C, ps, pd = self._cohort_sources(srcs, dtypes, nl)
+        pz = (ctypes.c_double * max(C, 1))(*[float(z) for z in zzz])
+        ii = (ctypes.c_uint32 * max(C, 1))(*[int(v) for v in idx])
+        rc = self._lib.flashe_quantize_encrypt_pack_sparse_cohort_dev(self._h, it, C, ii, int(n), n_jobs, arr, nl, ps, pd, int(element_bits), self._ptr(u),
+                                                                      int(u_stride), pz, 1 if zzz_is_f64 else 0, self._ptr(packed), int(packed_stride),
+                                                                      self._ptr(zeros))
+        return self._took(rc)
+
     def sparsify_batch(self, layers, ks, residuals=None):
         """[(loc uint32[k_l] ascending, vals[k_l], new residual or None) per layer] -- Client.sparsify's layer loop
         (jzf_aggregator.py:585-613) as ONE upload, one set of launches and one download.  All layers share one float type."""

@@ -106,7 +106,8 @@ typedef struct flashe_ctx flashe_ctx;
  *      65 .. 128: one launch each way, no 16-byte plaintext or ciphertext vector);
  *      flashe_unpack_decrypt_lists_unquantize_model_dev / flashe_unpack_decrypt_lists_unbatch_unquantize_model_dev (both ways back with
  *      prefix lists of up to 96 each: a round with a dropout, the single mask's decrypt);
- *      flashe_sparse_aggregate_packed_dev (the sparse job's packed uploads reduced to the packed dense sum in one launch) */
+ *      flashe_sparse_aggregate_packed_dev (the sparse job's packed uploads reduced to the packed dense sum in one launch);
+ *      flashe_quantize_encrypt_pack_sparse_cohort_dev (a sparse cohort's uploads from the floats straight to the packed wire form) */
 #define FLASHE_ABI_VERSION 4
 int flashe_abi_version(void);
 int flashe_device_count(int *count);
@@ -1448,6 +1449,21 @@ int flashe_quantize_encrypt_sparse_cohort_dev(flashe_ctx *ctx, uint32_t iter, in
                                               const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
                                               int element_bits, const double *u_dev, uint64_t u_stride, const double *zzz, int zzz_is_f64,
                                               uint64_t *const *ct_dev, uint64_t *zeros_dev);
+/* The same uploads straight in their packed WIRE form (new): what flashe_quantize_encrypt_sparse_cohort_dev followed by flashe_pack_dev of
+ * every upload writes (jzf_quantize.py:433-465, jzf_aggregator.py:717-743, jzf_flashe.py:471-478, jzf_weights.py:155-195), in ONE launch
+ * from the floats at every int_bits 16 .. 64: no uint64 element vector exists in HBM.  Every argument but the outputs exactly as
+ * flashe_quantize_encrypt_sparse_cohort_dev takes it.  packed_dev (device, 8-byte aligned), packed_stride (limbs, at least
+ * ceil((n + 1) int_bits / 64)): client c's upload is the ceil((n + 1) int_bits / 64) limbs at packed_dev + c * packed_stride -- n + 1
+ * fields of int_bits bits, field j at bits [int_bits (n - j), int_bits (n + 1 - j)): the n single-mask ciphertexts, then the plain
+ * quantised 'zzz' value in bits [0, int_bits) of limb 0, which also goes to zeros_dev[c].  The uploads share ONE allocation so that the
+ * clearing is one fill: limbs [0, (n_clients - 1) packed_stride + ceil((n + 1) int_bits / 64)) are written, the gaps of the stride with 0.
+ * flashe_sparse_aggregate_packed_dev takes the uploads as they are.
+ * FLASHE_ENOTSUP -- nothing was staged, cleared or launched -- unless 16 <= int_bits <= 64, the PRF backend the table one, n_clients <= 192
+ * and 0 < n < 2^32.  The tables are uploaded synchronously: not inside a graph capture. */
+int flashe_quantize_encrypt_pack_sparse_cohort_dev(flashe_ctx *ctx, uint32_t iter, int n_clients, const uint32_t *idx, uint64_t n, uint32_t n_jobs,
+                                                   const flashe_tensor_layer *layers, int n_layers, const void *const *src_dev, const int32_t *src_dtype,
+                                                   int element_bits, const double *u_dev, uint64_t u_stride, const double *zzz, int zzz_is_f64,
+                                                   uint64_t *packed_dev, uint64_t packed_stride, uint64_t *zeros_dev);
 
 /* ---- multi-GPU exchange (RCCL over xGMI; one process per GPU) ----------------------------------------------- */
 /* Replaces, inside one node, the arbiter's gather of client models + reduce in Python + broadcast of the aggregate
